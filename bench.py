@@ -20,10 +20,19 @@ Multi-GPU: `--gpus N` with N > 1 and no WORLD_SIZE in the environmen
 RCCL); under an external torchrun the ranks are taken from the environment and must equal `--gpus`.  `--dry-run` drives the
 same rank path on CPU with the gloo backend and no kernels (tests/test_dist_cpu.py).
 
-Besides the headline value the line carries `config.c3_literal`: BASELINE C3's literal batch (64 scenes in total) dealt to
-the ranks like the reference's DistributedSampler, and - at N = 1 - the 8-scene leg one GPU of an 8-way shard would run.
+A plain run does only what the headline needs: it builds the scenes and the engine, runs `--warmup` untimed rollouts, times
+exactly `--steps` rollouts, writes their outputs if `--dump-outputs DIR` is given and prints the line (`value`, `ms_per_step`).
+Everything else moves behind `--full`: the CPU baseline, the parity gate, the roofline legs, the secondary legs (`fp32_mfma`,
+`rhat24`, `two_streams`, `multi_rollout`, `prologue`) and `config.c3_literal` - BASELINE C3's literal batch (64 scenes in
+total) dealt to the ranks like the reference's DistributedSampler, and - at N = 1 - the 8-scene leg one GPU of an 8-way shard
+would run.  Without `--full` those keys of the line are null.
 
-Prints ONE JSON line on rank 0.  `roofline` follows SURVEY section 8d: algorithmic bytes and FLOPs
+`--dump-outputs DIR` writes what the last timed rollout returns to a caller (`RolloutEngine.outputs_device`, one dict per
+scene) as DIR/<key>.npy: the per-scene arrays of a fixed, seeded sample of the scenes concatenated along the agent axis,
+float32 (floats, booleans) or float64 (integers), at most 64 MB in all; `scene_index.npy` names the sampled scenes.  Inputs
+are seeded, so two builds given the same arguments can be compared output for output.
+
+Prints ONE JSON line on rank 0.  `roofline` (with `--full`) follows SURVEY section 8d: algorithmic bytes and FLOPs
 (the figures of 8d, evaluated on the edge counts the device reports) over measured time, for the
 dominant kernel and for the whole step; DESIGN.md "Measurement" has the arithmetic.
 """
@@ -82,10 +91,37 @@ def load_shapes():
         return {k: tuple(v) for k, v in json.load(f).items()}
 
 
-def build_scenes(cfg, indices, agents, map_tokens):
+def host_procs(world=1):
+    """processes for host-side work of one rank: the CPUs it may run on, at most 16 (and OMP_NUM_THREADS where set), shared by the ranks"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get('OMP_NUM_THREADS', n)))
+    except ValueError:
+        pass
+    return max(1, min(16, n) // max(1, world))
+
+
+def _scene_worker(job):
+    """one process of build_scenes: the scenes of a chunk of indices"""
+    cfg, indices, agents, map_tokens = job
+    return build_scenes(cfg, indices, agents, map_tokens, procs=1)[0]
+
+
+def build_scenes(cfg, indices, agents, map_tokens, procs=1):
+    """the synthetic scenes `indices` (each seeded by its index, so a pool of `procs` spawned processes builds the same arrays
+    as one process: ~65 ms of host time per C3 scene)"""
     vocab = synth.make_agent_vocab(cfg.token_size)
     map_vocab = synth.make_map_vocab()
     grid = synth.build_grid(cfg.grid_range, cfg.grid_interval, cfg.pl2seed_radius)
+    indices = list(indices)
+    if procs > 1 and len(indices) >= 64:
+        import multiprocessing as mp
+        from concurrent.futures import ProcessPoolExecutor       # (a worker that dies raises here instead of being replaced)
+        chunks = [indices[k::procs] for k in range(procs)]
+        with ProcessPoolExecutor(procs, mp_context=mp.get_context('spawn')) as pool:
+            parts = list(pool.map(_scene_worker, [(cfg, c, agents, map_tokens) for c in chunks]))
+        by_index = {i: sc for c, part in zip(chunks, parts) for i, sc in zip(c, part)}
+        return [by_index[i] for i in indices], vocab, map_vocab, grid
     scenes = [synth.make_scene(synth.scene_seed(3, i), agents, map_tokens, cfg, half_extent=60.0,
                                ego_last=True, vocab=vocab, grid=grid) for i in indices]
     return scenes, vocab, map_vocab, grid
@@ -295,210 +331,67 @@ def timed(ranks, fn, steps):
     return time.perf_counter() - t0
 
 
-def dry_run(args, ranks):
-    """the rank path of a run without kernels: scene sharding, barriers, the closing reductions - on gloo"""
-    mine = (igdist.scenes_for_rank_strided(ranks.rank, ranks.world, args.total_scenes) if args.scaling == 'strong'
-            else igdist.scenes_for_rank_weak(ranks.rank, args.scenes))
-    literal = igdist.scenes_for_rank_strided(ranks.rank, ranks.world, 64)
-    balance = None
-    if args.insertion and ranks.world > 1 and not args.no_balance:
-        # the pilot's cost exchange and the cost-sorted re-deal of a real insertion run, on synthetic per-scene costs
-        total = args.total_scenes if args.scaling == 'strong' else ranks.world * args.scenes
-        local = [(i, igdist.scene_cost(args.agents + (37 * (i + 1)) % 53, args.map_tokens)) for i in mine]
-        costs = igdist.gather_costs(local, total, ranks.dev)
-        dealt = [igdist.scenes_for_rank_strided(r, ranks.world, total) if args.scaling == 'strong'
-                 else igdist.scenes_for_rank_weak(r, args.scenes) for r in range(ranks.world)]
-        parts = [igdist.scenes_for_rank_balanced(costs, r, ranks.world) for r in range(ranks.world)]
-        balance = {'max_over_mean_before': igdist.partition_spread(costs, dealt),
-                   'max_over_mean_after': igdist.partition_spread(costs, parts), 'scenes_per_rank': [len(p_) for p_ in parts],
-                   'all_scenes_dealt_once': sorted(i for p_ in parts for i in p_) == list(range(total))}
-        mine = parts[ranks.rank]
-    dt = timed(ranks, lambda: time.sleep(0.002 * (ranks.rank + 1)), args.steps)
-    steps_local = float(len(mine) * args.agents * args.rollout_steps * args.steps)
-    per_rank = igdist.gather_metrics([1e3 * dt / args.steps, float(len(mine)), float(len(literal))], ranks.dev)
-    dt, agent_steps = igdist.reduce_run(dt, steps_local, ranks.dev)
-    if ranks.rank == 0:
-        print(json.dumps({'metric': 'agent-steps/sec (closed-loop rollout)', 'value': None, 'unit': 'agent-steps/s',
-                          'n_gpus': ranks.world, 'rccl_ranks': 0, 'ranks': ranks.world, 'backend': ranks.backend, 'dry_run': True, 'steps': args.steps,
-                          'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps, 'scaling': args.scaling,
-                          'agent_steps_counted': agent_steps, 'per_rank_ms': [r[0] for r in per_rank],
-                          'scenes_per_rank': [int(r[1]) for r in per_rank],
-                          'c3_literal_scenes_per_rank': [int(r[2]) for r in per_rank], 'insertion_balance': balance}))
+DUMP_BYTES = 60_000_000       # --dump-outputs: .npy data in all (the 64 MB cap, with room for the headers)
+DUMP_SEED = 0
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=5)
-    ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--scenes', type=int, default=1024, help='scenes per GPU (weak scaling; 512 until round 4: 25.7 M, 1024: 27.2 M)')
-    ap.add_argument('--scaling', choices=('weak', 'strong'), default='weak',
-                    help='strong: a fixed batch of --total-scenes scenes dealt to the ranks (scene i -> rank i mod N)')
-    ap.add_argument('--total-scenes', type=int, default=64, help='batch size of --scaling strong (BASELINE C3: 64)')
-    ap.add_argument('--overlap', type=int, default=-1, help='infgen_set_overlap (default: library default)')
-    ap.add_argument('--roofline-kernel', default='', help='report the roofline of this kernel instead of the dominant one')
-    ap.add_argument('--agents', type=int, default=64)
-    ap.add_argument('--map-tokens', type=int, default=1024)
-    ap.add_argument('--insertion', action='store_true', help='scenario insertion on (configs/ours_long_term.yaml style)')
-    ap.add_argument('--insert-headroom', type=int, default=None,
-                    help='rows per scene reserved for inserted agents (default: min(10 per decode step, 96), doubled until the '
-                         'rollout fits; A_cap <= 1024)')
-    ap.add_argument('--rollout-steps', type=int, default=80, help='R = num_recurrent_steps_val (multiple of 5)')
-    ap.add_argument('--streams', type=int, default=1, help='split the per-GPU batch over this many HIP streams')
-    ap.add_argument('--gemm-terms', type=int, default=3, choices=(1, 2, 3),
-                    help='3: round-to-nearest hi + lo fp16 operand split, three MFMA terms = fp32 arithmetic (default); the reduced-precision '
-                         'modes for BASELINE config C5 (outside the 1e-3 parity bar): 2 = bf16 operands (weights and activations rounded to '
-                         '8 significant bits, fp32 accumulation), 1 = fp16 operands')
-    ap.add_argument('--attn-mode', type=int, default=-1, choices=(-1, 0, 1, 2, 3),
-                    help='infgen_set_attn_mode: 2 (library default) node kernels by launch size, 1 the split kernels on 64-row tiles always')
-    ap.add_argument('--edge-fuse', type=int, default=-1, choices=(-1, 0, 1, 2),
-                    help='infgen_set_edge_fuse: 1 (library default) k_edge_fused from 257 rows, 0 the unfused sequence with U / Z in HBM')
-    ap.add_argument('--edge-loop', type=int, default=-1, choices=(-1, 4, 6, 8))
-    ap.add_argument('--edge-kernel', type=int, default=-1, choices=(-1, 0, 1, 2),
-                    help='infgen_set_edge_kernel: 0 k_edge_fused, 1 k_edge_fused3 for launches beyond 4 k rows, 2 k_edge_fused3 always')
-    ap.add_argument('--graph', type=int, default=-1, choices=(-1, 0, 1, 2),
-                    help='replay the decode steps of a rollout from a captured HIP graph: 1 always, 0 never, -1 (default) the '
-                         'engine\'s rule (off unless INFGEN_GRAPH=1)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true')
-    ap.add_argument('--no-literal', action='store_true', help='skip the config.c3_literal legs')
-    ap.add_argument('--no-strict', action='store_true', help='skip the secondary legs (fp32_mfma, rhat24, two_streams, multi_rollout, prologue)')
-    ap.add_argument('--no-balance', action='store_true',
-                    help='insertion on several ranks: keep the initial deal instead of the cost-sorted one (dist.scenes_for_rank_balanced)')
-    ap.add_argument('--cpu-budget', type=float, default=20.0)
-    ap.add_argument('--dry-run', action='store_true',
-                    help='the rank path only (launcher, sharding, barriers, reductions) on CPU with the gloo backend; no kernels')
-    args = ap.parse_args()
+def dump_outputs(out_dir, engines):
+    """--dump-outputs: what the last rollout returns to a caller (outputs_device, one dict per scene) for a seeded sample of the
+    scenes, each key's per-scene arrays concatenated along the agent axis (scalars: one value per scene), as out_dir/<key>.npy in
+    float32 (floats, booleans) or float64 (integers).  The sample is a prefix of a seeded permutation of the scenes, as long as
+    its upper bound (every scene at its row capacity) fits DUMP_BYTES: it depends on the arguments only, not on the outputs."""
+    outs = [o for e in engines for o in e.outputs_device()]
+    caps = [e.A_cap for e in engines for _ in e.hosts]
+    out_dtype = lambda a: np.float64 if a.dtype.kind in 'iu' else np.float32
 
-    if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
-        sys.exit(spawn_ranks(args.gpus))
-    ranks = Ranks(args)
-    rank, world, dev = ranks.rank, ranks.world, ranks.dev
-    if args.dry_run:
-        dry_run(args, ranks)
-        ranks.close()
-        return
+    def arrays(o):
+        res = {}
+        for k in o.keys():
+            v = o[k]
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu().numpy()
+            elif isinstance(v, (bool, int, float, np.integer, np.floating, np.bool_)):
+                v = np.asarray(v)
+            elif not isinstance(v, np.ndarray):
+                continue                        # (agent_labels of an insertion run: strings)
+            res[k] = v.astype(out_dtype(v))
+        return res
 
-    log(f'cpu_count={os.cpu_count()} device={torch.cuda.get_device_name(dev)}')
-    # the CPU baseline runs first (rank 0, N = 1 only), before this process holds GPU work
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(args, args.cpu_budget)
-        log(f'cpu baseline done: {cpu}')
+    order = np.random.default_rng(DUMP_SEED).permutation(len(outs))
+    first = arrays(outs[int(order[0])])
+    # bytes of a scene at its row capacity: the per-agent arrays (leading dimension = the scene's agents) scale with the rows;
+    # scalars and the per-map-token rows (x_pt) do not (+ its scene_index entry)
+    n_a = first['agent_id'].shape[0] if 'agent_id' in first else -1
+    bound = lambda cap: sum((v.nbytes // max(1, n_a)) * cap if v.ndim and v.shape[0] == n_a else v.nbytes
+                            for v in first.values()) + 8
+    keep, total = [], 0
+    for s in order:
+        b = bound(caps[int(s)])
+        if keep and total + b > DUMP_BYTES:
+            break
+        keep.append(int(s))
+        total += b
+    keep.sort()
+    cols = {}
+    for s in keep:
+        for k, v in (first if s == int(order[0]) else arrays(outs[s])).items():
+            cols.setdefault(k, []).append(v if v.ndim else v.reshape(1))
+    cols['scene_index'] = [np.asarray(keep, np.float64)]
+    for k, parts in cols.items():
+        if any(p.shape[1:] != parts[0].shape[1:] for p in parts):
+            parts = [p.reshape(-1) for p in parts]
+        cols[k] = np.concatenate(parts, axis=0)
+    written = sum(a.nbytes for a in cols.values())
+    assert written <= DUMP_BYTES, f'--dump-outputs: {written} bytes over the bound'
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in cols.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+    return written
 
-    cfg = synth.standard_config(disable_insertion=not args.insertion, num_recurrent_steps_val=args.rollout_steps)
-    sd = synth.fill_state_dict(load_shapes(), seed=1, rich=True)
-    if args.scaling == 'strong':
-        mine = igdist.scenes_for_rank_strided(rank, world, args.total_scenes)
-    else:
-        mine = igdist.scenes_for_rank_weak(rank, args.scenes)
-    scenes, vocab, map_vocab, grid = build_scenes(cfg, mine, args.agents, args.map_tokens)
-    log(f'{len(scenes)} scenes built')
-    lib = _lib.load()
-    if args.overlap >= 0:
-        _lib.check(lib.infgen_set_overlap(args.overlap))
-    _lib.check(lib.infgen_set_gemm_terms(args.gemm_terms))
-    if args.attn_mode >= 0:
-        _lib.check(lib.infgen_set_attn_mode(args.attn_mode))
-    if args.edge_loop >= 0:
-        _lib.check(lib.infgen_set_edge_loop(args.edge_loop))
-    if args.edge_fuse >= 0:
-        _lib.check(lib.infgen_set_edge_fuse(args.edge_fuse))
-    if args.edge_kernel >= 0:
-        _lib.check(lib.infgen_set_edge_kernel(args.edge_kernel))
 
-    parity = None
-    if rank == 0 and not args.no_parity and args.gemm_terms == 3:
-        parity = parity_gate(dev)
-        log(f'parity: {parity}')
-
-    w = engine.PackedWeights(sd, cfg, dev, operand_bits=8 if args.gemm_terms == 2 else 11)
-    ns = max(1, args.streams)
-    per = (len(scenes) + ns - 1) // ns
-    use_graph = None if args.graph < 0 else ('all' if args.graph == 2 else bool(args.graph))       # 2: the whole rollout as one graph
-
-    def make_engines(headroom):
-        return [engine.RolloutEngine(w, scenes[i * per:(i + 1) * per], vocab, map_vocab, grid, store_logits=False,
-                                     insert_headroom=headroom, use_graph=use_graph)
-                for i in range(ns) if scenes[i * per:(i + 1) * per]]
-    engines = make_engines(args.insert_headroom)
-    streams = [torch.cuda.Stream(device=dev) for _ in engines] if ns > 1 else [None]
-
-    class _Multi:
-        """the per-GPU batch split over several HIP streams (memory-bound edge attention of one group
-        overlaps the MFMA-bound kernels of another)"""
-        def rollout(self):
-            engine.rollout_many(engines, streams if ns > 1 else None)
-
-        def agent_steps(self):
-            return sum(e.agent_steps() for e in engines)
-
-        @property
-        def n_agents(self):
-            return torch.cat([e.n_agents for e in engines])
-
-        @property
-        def hosts(self):
-            return [h for e in engines for h in e.hosts]
-    eng = _Multi()
-    log('engine built')
-
-    # warm-up; with insertion the row head-room is doubled until the (deterministic) rollout fits - an engine never drops
-    # an insertion silently
-    def warm_up():
-        done = 0
-        while done < max(args.warmup, 1 if args.insertion else 0):
-            try:
-                eng.rollout()
-                torch.cuda.synchronize(dev)
-                done += 1
-            except engine.InsertionHeadroomError:
-                limit = lib.infgen_layout_query(_lib.Q_MAX_AGENTS)
-                if engines[0].A_cap >= limit:
-                    raise
-                engines[:] = make_engines(min(2 * engines[0].A_cap, limit) - args.agents)
-                log(f'insertion head-room exhausted: rows per scene -> {engines[0].A_cap}')
-                done = 0
-            log('warmup rollout done')
-    warm_up()
-    # insertion on several ranks: per-scene cost is data dependent (SURVEY 8e).  The warm-up rollout is the pilot: every rank
-    # contributes the agents its scenes ended with, the cost vector is all-reduced, and the scenes are dealt again longest
-    # first (dist.scenes_for_rank_balanced) - a control-plane exchange before the timed region, none inside it
-    balance = None
-    if args.insertion and world > 1 and not args.no_balance:
-        total = args.total_scenes if args.scaling == 'strong' else world * args.scenes
-        fin = eng.n_agents.tolist()
-        local = [(i, igdist.scene_cost(n, args.map_tokens)) for i, n in zip(mine, fin)]
-        costs = igdist.gather_costs(local, total, dev)
-        dealt = [igdist.scenes_for_rank_strided(r, world, total) if args.scaling == 'strong' else igdist.scenes_for_rank_weak(r, args.scenes)
-                 for r in range(world)]
-        parts = [igdist.scenes_for_rank_balanced(costs, r, world) for r in range(world)]
-        balance = {'cost': 'agents at the end of the pilot rollout x (1 + map tokens / 8192)',
-                   'max_over_mean_before': igdist.partition_spread(costs, dealt),
-                   'max_over_mean_after': igdist.partition_spread(costs, parts), 'scenes_per_rank': [len(p_) for p_ in parts]}
-        log(f'balanced dealing: {balance}')
-        mine = parts[rank]
-        del engines[:]
-        torch.cuda.empty_cache()
-        scenes, vocab, map_vocab, grid = build_scenes(cfg, mine, args.agents, args.map_tokens)
-        per = (len(scenes) + ns - 1) // ns
-        engines[:] = make_engines(args.insert_headroom)
-        warm_up()
-    # roofline leg 1 (untimed): one rollout with HIP events around EVERY kernel -> which kernel dominates
-    # (an engine that replays a HIP graph runs this rollout eagerly: events are not part of the captured graph)
-    _lib.prof_enable((1 << len(_lib.KERNEL_IDS)) - 1)
-    eng.rollout()
-    per_kernel = _lib.prof_collect()
-    dominant = args.roofline_kernel or max(per_kernel, key=lambda k: per_kernel[k]['ms'])
-    log('per-kernel ms of one rollout: ' + ', '.join(f'{k}={v["ms"]:.2f}' for k, v in per_kernel.items()))
-    # roofline leg 2: events only around the dominant kernel's launches, inside the timed region - and only around every
-    # PROF_STRIDE-th of its decode-step launches (an event pair costs ~5 us of launch-stream time: ~3 ms per rollout with all 306
-    # bracketed).  5 is coprime to the 18 launches of a step (6 layers x temporal, map, agent): every position is sampled equally often
-    _lib.prof_enable(1 << _lib.KERNEL_IDS.index(dominant))
-    _lib.prof_set_stride(PROF_STRIDE)
-    dt_local = timed(ranks, eng.rollout, args.steps)
-    log(f'timed region done: {1e3 * dt_local / args.steps:.2f} ms per step')
-    dt = dt_local
+def roofline(args, cfg, eng, engines, scenes, per_kernel, dominant, dt):
+    """the `roofline` block of the line (--full): leg 2's events of the timed region, priced by SURVEY 8d; `per_kernel` = leg 1,
+    `dt` = this rank's seconds of the timed region"""
     timed_k = _lib.prof_collect()
     seen_k = _lib.prof_seen()[dominant]
     dom = timed_k[dominant]
@@ -604,12 +497,232 @@ def main():
                 'algorithmic_flop_per_launch': flops / dom['calls'], **common}
     if roof is not None and roof.get('traffic') is None and dominant != 'k_edge_attn':
         roof['traffic'] = pmc_traffic(dominant, args)
+    return roof
+
+
+def dry_run(args, ranks):
+    """the rank path of a run without kernels: scene sharding, barriers, the closing reductions - on gloo"""
+    mine = (igdist.scenes_for_rank_strided(ranks.rank, ranks.world, args.total_scenes) if args.scaling == 'strong'
+            else igdist.scenes_for_rank_weak(ranks.rank, args.scenes))
+    literal = igdist.scenes_for_rank_strided(ranks.rank, ranks.world, 64)
+    balance = None
+    if args.insertion and ranks.world > 1 and not args.no_balance:
+        # the pilot's cost exchange and the cost-sorted re-deal of a real insertion run, on synthetic per-scene costs
+        total = args.total_scenes if args.scaling == 'strong' else ranks.world * args.scenes
+        local = [(i, igdist.scene_cost(args.agents + (37 * (i + 1)) % 53, args.map_tokens)) for i in mine]
+        costs = igdist.gather_costs(local, total, ranks.dev)
+        dealt = [igdist.scenes_for_rank_strided(r, ranks.world, total) if args.scaling == 'strong'
+                 else igdist.scenes_for_rank_weak(r, args.scenes) for r in range(ranks.world)]
+        parts = [igdist.scenes_for_rank_balanced(costs, r, ranks.world) for r in range(ranks.world)]
+        balance = {'max_over_mean_before': igdist.partition_spread(costs, dealt),
+                   'max_over_mean_after': igdist.partition_spread(costs, parts), 'scenes_per_rank': [len(p_) for p_ in parts],
+                   'all_scenes_dealt_once': sorted(i for p_ in parts for i in p_) == list(range(total))}
+        mine = parts[ranks.rank]
+    dt = timed(ranks, lambda: time.sleep(0.002 * (ranks.rank + 1)), args.steps)
+    steps_local = float(len(mine) * args.agents * args.rollout_steps * args.steps)
+    per_rank = igdist.gather_metrics([1e3 * dt / args.steps, float(len(mine)), float(len(literal))], ranks.dev)
+    dt, agent_steps = igdist.reduce_run(dt, steps_local, ranks.dev)
+    if ranks.rank == 0:
+        print(json.dumps({'metric': 'agent-steps/sec (closed-loop rollout)', 'value': None, 'unit': 'agent-steps/s',
+                          'n_gpus': ranks.world, 'rccl_ranks': 0, 'ranks': ranks.world, 'backend': ranks.backend, 'dry_run': True, 'steps': args.steps,
+                          'warmup': args.warmup, 'ms_per_step': 1e3 * dt / args.steps, 'scaling': args.scaling,
+                          'agent_steps_counted': agent_steps, 'per_rank_ms': [r[0] for r in per_rank],
+                          'scenes_per_rank': [int(r[1]) for r in per_rank],
+                          'c3_literal_scenes_per_rank': [int(r[2]) for r in per_rank], 'insertion_balance': balance}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gpus', type=int, default=1)
+    ap.add_argument('--steps', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--scenes', type=int, default=1024, help='scenes per GPU (weak scaling; 512 until round 4: 25.7 M, 1024: 27.2 M)')
+    ap.add_argument('--scaling', choices=('weak', 'strong'), default='weak',
+                    help='strong: a fixed batch of --total-scenes scenes dealt to the ranks (scene i -> rank i mod N)')
+    ap.add_argument('--total-scenes', type=int, default=64, help='batch size of --scaling strong (BASELINE C3: 64)')
+    ap.add_argument('--overlap', type=int, default=-1, help='infgen_set_overlap (default: library default)')
+    ap.add_argument('--roofline-kernel', default='', help='report the roofline of this kernel instead of the dominant one')
+    ap.add_argument('--agents', type=int, default=64)
+    ap.add_argument('--map-tokens', type=int, default=1024)
+    ap.add_argument('--insertion', action='store_true', help='scenario insertion on (configs/ours_long_term.yaml style)')
+    ap.add_argument('--insert-headroom', type=int, default=None,
+                    help='rows per scene reserved for inserted agents (default: min(10 per decode step, 96), doubled until the '
+                         'rollout fits; A_cap <= 1024)')
+    ap.add_argument('--rollout-steps', type=int, default=80, help='R = num_recurrent_steps_val (multiple of 5)')
+    ap.add_argument('--streams', type=int, default=1, help='split the per-GPU batch over this many HIP streams')
+    ap.add_argument('--gemm-terms', type=int, default=3, choices=(1, 2, 3),
+                    help='3: round-to-nearest hi + lo fp16 operand split, three MFMA terms = fp32 arithmetic (default); the reduced-precision '
+                         'modes for BASELINE config C5 (outside the 1e-3 parity bar): 2 = bf16 operands (weights and activations rounded to '
+                         '8 significant bits, fp32 accumulation), 1 = fp16 operands')
+    ap.add_argument('--attn-mode', type=int, default=-1, choices=(-1, 0, 1, 2, 3),
+                    help='infgen_set_attn_mode: 2 (library default) node kernels by launch size, 1 the split kernels on 64-row tiles always')
+    ap.add_argument('--edge-fuse', type=int, default=-1, choices=(-1, 0, 1, 2),
+                    help='infgen_set_edge_fuse: 1 (library default) k_edge_fused from 257 rows, 0 the unfused sequence with U / Z in HBM')
+    ap.add_argument('--edge-loop', type=int, default=-1, choices=(-1, 4, 6, 8))
+    ap.add_argument('--edge-kernel', type=int, default=-1, choices=(-1, 0, 1, 2),
+                    help='infgen_set_edge_kernel: 0 k_edge_fused, 1 k_edge_fused3 for launches beyond 4 k rows, 2 k_edge_fused3 always')
+    ap.add_argument('--graph', type=int, default=-1, choices=(-1, 0, 1, 2),
+                    help='replay the decode steps of a rollout from a captured HIP graph: 1 always, 0 never, -1 (default) the '
+                         'engine\'s rule (off unless INFGEN_GRAPH=1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-parity', action='store_true')
+    ap.add_argument('--no-literal', action='store_true', help='skip the config.c3_literal legs')
+    ap.add_argument('--no-strict', action='store_true', help='skip the secondary legs (fp32_mfma, rhat24, two_streams, multi_rollout, prologue)')
+    ap.add_argument('--no-balance', action='store_true',
+                    help='insertion on several ranks: keep the initial deal instead of the cost-sorted one (dist.scenes_for_rank_balanced)')
+    ap.add_argument('--cpu-budget', type=float, default=20.0)
+    ap.add_argument('--dry-run', action='store_true',
+                    help='the rank path only (launcher, sharding, barriers, reductions) on CPU with the gloo backend; no kernels')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: CPU baseline, parity gate, roofline legs, the secondary legs and '
+                         'config.c3_literal (the --no-* switches select among them); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed rollout (a seeded sample of the scenes, <= 64 MB) as DIR/<key>.npy')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+
+    if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
+        sys.exit(spawn_ranks(args.gpus))
+    ranks = Ranks(args)
+    rank, world, dev = ranks.rank, ranks.world, ranks.dev
+    if args.dry_run:
+        dry_run(args, ranks)
+        ranks.close()
+        return
+
+    log(f'cpu_count={os.cpu_count()} device={torch.cuda.get_device_name(dev)}')
+    # the CPU baseline runs first (rank 0, N = 1 only), before this process holds GPU work
+    cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline(args, args.cpu_budget)
+        log(f'cpu baseline done: {cpu}')
+
+    cfg = synth.standard_config(disable_insertion=not args.insertion, num_recurrent_steps_val=args.rollout_steps)
+    sd = synth.fill_state_dict(load_shapes(), seed=1, rich=True)
+    if args.scaling == 'strong':
+        mine = igdist.scenes_for_rank_strided(rank, world, args.total_scenes)
+    else:
+        mine = igdist.scenes_for_rank_weak(rank, args.scenes)
+    scenes, vocab, map_vocab, grid = build_scenes(cfg, mine, args.agents, args.map_tokens, procs=host_procs(world))
+    log(f'{len(scenes)} scenes built')
+    lib = _lib.load()
+    if args.overlap >= 0:
+        _lib.check(lib.infgen_set_overlap(args.overlap))
+    _lib.check(lib.infgen_set_gemm_terms(args.gemm_terms))
+    if args.attn_mode >= 0:
+        _lib.check(lib.infgen_set_attn_mode(args.attn_mode))
+    if args.edge_loop >= 0:
+        _lib.check(lib.infgen_set_edge_loop(args.edge_loop))
+    if args.edge_fuse >= 0:
+        _lib.check(lib.infgen_set_edge_fuse(args.edge_fuse))
+    if args.edge_kernel >= 0:
+        _lib.check(lib.infgen_set_edge_kernel(args.edge_kernel))
+
+    parity = None
+    if args.full and rank == 0 and not args.no_parity and args.gemm_terms == 3:
+        parity = parity_gate(dev)
+        log(f'parity: {parity}')
+
+    w = engine.PackedWeights(sd, cfg, dev, operand_bits=8 if args.gemm_terms == 2 else 11)
+    ns = max(1, args.streams)
+    per = (len(scenes) + ns - 1) // ns
+    use_graph = None if args.graph < 0 else ('all' if args.graph == 2 else bool(args.graph))       # 2: the whole rollout as one graph
+
+    def make_engines(headroom):
+        return [engine.RolloutEngine(w, scenes[i * per:(i + 1) * per], vocab, map_vocab, grid, store_logits=False,
+                                     insert_headroom=headroom, use_graph=use_graph)
+                for i in range(ns) if scenes[i * per:(i + 1) * per]]
+    engines = make_engines(args.insert_headroom)
+    streams = [torch.cuda.Stream(device=dev) for _ in engines] if ns > 1 else [None]
+
+    class _Multi:
+        """the per-GPU batch split over several HIP streams (memory-bound edge attention of one group
+        overlaps the MFMA-bound kernels of another)"""
+        def rollout(self):
+            engine.rollout_many(engines, streams if ns > 1 else None)
+
+        def agent_steps(self):
+            return sum(e.agent_steps() for e in engines)
+
+        @property
+        def n_agents(self):
+            return torch.cat([e.n_agents for e in engines])
+
+        @property
+        def hosts(self):
+            return [h for e in engines for h in e.hosts]
+    eng = _Multi()
+    log('engine built')
+
+    # warm-up; with insertion the row head-room is doubled until the (deterministic) rollout fits - an engine never drops
+    # an insertion silently
+    def warm_up():
+        done = 0
+        while done < max(args.warmup, 1 if args.insertion else 0):
+            try:
+                eng.rollout()
+                torch.cuda.synchronize(dev)
+                done += 1
+            except engine.InsertionHeadroomError:
+                limit = lib.infgen_layout_query(_lib.Q_MAX_AGENTS)
+                if engines[0].A_cap >= limit:
+                    raise
+                engines[:] = make_engines(min(2 * engines[0].A_cap, limit) - args.agents)
+                log(f'insertion head-room exhausted: rows per scene -> {engines[0].A_cap}')
+                done = 0
+            log('warmup rollout done')
+    warm_up()
+    # insertion on several ranks: per-scene cost is data dependent (SURVEY 8e).  The warm-up rollout is the pilot: every rank
+    # contributes the agents its scenes ended with, the cost vector is all-reduced, and the scenes are dealt again longest
+    # first (dist.scenes_for_rank_balanced) - a control-plane exchange before the timed region, none inside it
+    balance = None
+    if args.insertion and world > 1 and not args.no_balance:
+        total = args.total_scenes if args.scaling == 'strong' else world * args.scenes
+        fin = eng.n_agents.tolist()
+        local = [(i, igdist.scene_cost(n, args.map_tokens)) for i, n in zip(mine, fin)]
+        costs = igdist.gather_costs(local, total, dev)
+        dealt = [igdist.scenes_for_rank_strided(r, world, total) if args.scaling == 'strong' else igdist.scenes_for_rank_weak(r, args.scenes)
+                 for r in range(world)]
+        parts = [igdist.scenes_for_rank_balanced(costs, r, world) for r in range(world)]
+        balance = {'cost': 'agents at the end of the pilot rollout x (1 + map tokens / 8192)',
+                   'max_over_mean_before': igdist.partition_spread(costs, dealt),
+                   'max_over_mean_after': igdist.partition_spread(costs, parts), 'scenes_per_rank': [len(p_) for p_ in parts]}
+        log(f'balanced dealing: {balance}')
+        mine = parts[rank]
+        del engines[:]
+        torch.cuda.empty_cache()
+        scenes, vocab, map_vocab, grid = build_scenes(cfg, mine, args.agents, args.map_tokens, procs=host_procs(world))
+        per = (len(scenes) + ns - 1) // ns
+        engines[:] = make_engines(args.insert_headroom)
+        warm_up()
+    if args.full:
+        # roofline leg 1 (untimed): one rollout with HIP events around EVERY kernel -> which kernel dominates
+        # (an engine that replays a HIP graph runs this rollout eagerly: events are not part of the captured graph)
+        _lib.prof_enable((1 << len(_lib.KERNEL_IDS)) - 1)
+        eng.rollout()
+        per_kernel = _lib.prof_collect()
+        dominant = args.roofline_kernel or max(per_kernel, key=lambda k: per_kernel[k]['ms'])
+        log('per-kernel ms of one rollout: ' + ', '.join(f'{k}={v["ms"]:.2f}' for k, v in per_kernel.items()))
+        # roofline leg 2: events only around the dominant kernel's launches, inside the timed region - and only around every
+        # PROF_STRIDE-th of its decode-step launches (an event pair costs ~5 us of launch-stream time: ~3 ms per rollout with all 306
+        # bracketed).  5 is coprime to the 18 launches of a step (6 layers x temporal, map, agent): every position is sampled equally often
+        _lib.prof_enable(1 << _lib.KERNEL_IDS.index(dominant))
+        _lib.prof_set_stride(PROF_STRIDE)
+    # (with --full the timed region carries HIP events around the dominant kernel: launches are issued eagerly, never replayed)
+    graph_used = any(bool(e.use_graph) for e in engines) and not _lib.prof_active()
+    dt_local = timed(ranks, eng.rollout, args.steps)
+    log(f'timed region done: {1e3 * dt_local / args.steps:.2f} ms per step')
+    dt = dt_local
+    roof = roofline(args, cfg, eng, engines, scenes, per_kernel, dominant, dt) if args.full else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engines)
+        log(f'outputs written to {args.dump_outputs}')
 
     agent_steps = float(eng.agent_steps() * args.steps)       # (with insertion: the rows decoded at every step of the last rollout)
     inserted = int((eng.n_agents.sum().item() - sum(h['A'] for h in eng.hosts))) if args.insertion else 0
     n_scenes_local = len(scenes)
     rows_per_scene = engines[0].A_cap
-    graph_used = False      # (the timed region carries HIP events around the dominant kernel: launches are issued eagerly)
     per_rank = igdist.gather_metrics([1e3 * dt_local / args.steps, float(n_scenes_local)], dev)
     dt, agent_steps = igdist.reduce_run(dt, agent_steps, dev)
 
@@ -619,7 +732,7 @@ def main():
     # ---- config.rhat24: the headline's kernels with the relative-position rows between the Fourier and the edge kernels packed
     # into 24 bits (InfgenOptions.rhat_format = 1: 2^-17 per value - a reduced-precision mode, never the headline)
     strict = r24leg = None
-    if not args.no_strict and args.gemm_terms == 3 and not args.insertion and ns == 1:
+    if args.full and not args.no_strict and args.gemm_terms == 3 and not args.insertion and ns == 1:
         def opt_leg(options, what):
             e = engine.RolloutEngine(w, scenes, vocab, map_vocab, grid, store_logits=False, use_graph=False, options=options)
             e.rollout()
@@ -641,7 +754,7 @@ def main():
     # the headline, not as it: with two streams the per-kernel HIP-event durations overlap, and the roofline of the line is the
     # single-stream kernel's.
     two = None
-    if not args.no_strict and args.gemm_terms == 3 and not args.insertion and ns == 1 and len(scenes) >= 128:
+    if args.full and not args.no_strict and args.gemm_terms == 3 and not args.insertion and ns == 1 and len(scenes) >= 128:
         log('two-stream leg')
         half = (len(scenes) + 1) // 2
         es = [engine.RolloutEngine(w, scenes[i * half:(i + 1) * half], vocab, map_vocab, grid, store_logits=False, use_graph=False)
@@ -663,7 +776,7 @@ def main():
     # scene's map ONCE (one pt <-> pt graph, one map encoder pass, one set of map K / V rows per scene: what the reference's
     # inference_no_map(data, map_enc), infgen_decoder.py:132-134, is for), next to the same 1024 rollouts run as independent scenes
     multi = None
-    if c3_shapes(args) and not args.insertion and not args.no_strict and args.gemm_terms == 3 and ns == 1 and len(scenes) >= 32:
+    if args.full and c3_shapes(args) and not args.insertion and not args.no_strict and args.gemm_terms == 3 and ns == 1 and len(scenes) >= 32:
         log('multi-rollout leg')
         n_sc, n_ro = 32, 32
         rng = np.random.default_rng(11)
@@ -701,7 +814,7 @@ def main():
     # prologue (state reset, map encoder, map K / V, edgeless column-0 chain) of the same batch timed on its own; the decode
     # steps are the rest of the timed rollout
     prologue = None
-    if ns == 1 and engines and not args.insertion and not args.no_strict:      # (--no-strict: the timed region only, e.g. under rocprofv3)
+    if args.full and ns == 1 and engines and not args.insertion and not args.no_strict:      # (--no-strict: the timed region only)
         log('prologue leg')
         e0 = engines[0]
         psteps = max(1, min(3, args.steps))
@@ -717,7 +830,7 @@ def main():
     # DistributedSampler (scene i -> rank i mod N); at N = 1 also the 8 scenes one GPU of an 8-way shard owns
     c3 = args.agents == 64 and args.map_tokens == 1024 and args.rollout_steps == 80 and not args.insertion
     literal = None
-    if c3 and not args.no_literal and args.gemm_terms == 3:
+    if args.full and c3 and not args.no_literal and args.gemm_terms == 3:
         del engines[:]
         eng = None
         torch.cuda.empty_cache()
@@ -766,6 +879,7 @@ def main():
             'per_rank_ms_spread': max(r[0] for r in per_rank) / (sum(r[0] for r in per_rank) / len(per_rank)),
             'steps': args.steps,
             'warmup': args.warmup,
+            'full': bool(args.full),
             'ms_per_step': 1e3 * dt / args.steps,
             'higher_is_better': True,
             'scaling': args.scaling,

@@ -5,7 +5,7 @@ O=gpurun_out/suite; mkdir -p $O
 bash tools/prof_round.sh > $O/prof_round.log 2>&1
 bash tools/prof_sq.sh > $O/prof_sq.log 2>&1
 bash tools/edge_by_set2.sh "" k_edge_fused3 > $O/edge_by_set.txt 2>&1
-timeout 900 python bench.py > $O/bench_s1024.json 2> $O/bench_s1024.err
+timeout 900 python bench.py --full > $O/bench_s1024.json 2> $O/bench_s1024.err
 python - <<'PY'
 import json
 d = json.load(open('gpurun_out/suite/bench_s1024.json'))
