@@ -549,6 +549,52 @@ int infgen_prof_collect_steps(double* total_ms, int* calls, double* total_macs, 
 int infgen_prof_set_stride(int stride);
 int infgen_prof_seen(int* seen, int* seen_step);
 
+/* ---- ragged batch ingest (a PyG-style Batch of B graphs: rows of every graph concatenated, `ptr` offsets) ----
+ * infgen_ingest_batch writes a rollout's scene buffers straight from the Batch's device tensors, the statements of the
+ * reference's inference setup (infgen/modules/agent_decoder.py:1609-1719: filter rows invalid at column hc - 1, pad, zero the
+ * future, masks) per agent-side scene s < S of graph src_graph[s].  Graph g's copies are adjacent (copies per graph); the map
+ * side is written once per graph, at map scene s / copies.  Every element of every destination is written (padding included):
+ * the result equals the host-side setup bit for bit.  One workgroup per (scene, part); no atomics.
+ * Inputs (rows N = agent_ptr[B], tokens P_tok = pt_ptr[B]; all contiguous):
+ *   agent_ptr / pt_ptr [B + 1], av_index [B] (global rows), src_graph [S];
+ *   state_idx, token_idx, grid_token_idx int64 [N][T0]; token_pos f32 [N][T0][2]; token_heading f32 [N][T0];
+ *   raw_valid u8 [N][T0]; valid_mask u8 [N][P]; shape f32 [N][P][3]; position f32 [N][P][pos_dim]; heading f32 [N][P];
+ *   type u8 [N]; id int64 [N]; pt_position f32 [P_tok][pt_pos_dim]; pt_orientation f32, pt_token_idx int64, pt_type u8,
+ *   pt_pl_type u8 [P_tok]; pt_polygon int64 [P_tok] (edge_index[1] of pt_token -> map_polygon, global); light_type u8 [n_polygons].
+ * Outputs: the [S][T][A_cap] / [S][A_cap] / [S0][M_cap] rollout arrays (S0 = S / copies), the epilogue inputs
+ * ([S][A_cap][...]: htok, hst, p0, h0, shp, gt [S][A_cap][P - H][2], val [S][A_cap][T], ids - fresh ids max + 1 + k on the rows
+ * past the kept ones) and counts [S][3]: kept rows, ego row after filtering, rows removed before the ego.
+ * The caller checks the offsets (rows per graph <= A_cap <= INFGEN_Q_MAX_AGENTS, tokens <= M_cap, every ego inside its graph,
+ * hc <= T0 <= T) before the call: the offsets live on the device, the entry re-checks only the scalar geometry.  A graph that
+ * breaks the row bound is not written out of bounds - its scene keeps its first min(A_cap, INFGEN_Q_MAX_AGENTS) kept rows -
+ * but its results are then wrong, as are those of a graph with more tokens than M_cap (its first M_cap are kept).  Offsets past
+ * the arrays' rows, or src_graph entries >= B, read past the inputs. */
+typedef struct InfgenBatchIngest {
+  int S, copies, A_cap, M_cap, T, T0, P, hc, H, motion_cols, pos_dim, pt_pos_dim, n_polygons, _pad0;
+  const long long* agent_ptr; const long long* pt_ptr; const long long* av_index; const int* src_graph;
+  const long long* state_idx; const long long* token_idx; const long long* grid_token_idx;
+  const float* token_pos; const float* token_heading; const unsigned char* raw_valid;
+  const unsigned char* valid_mask; const float* shape; const float* position; const float* heading;
+  const unsigned char* type; const long long* id;
+  const float* pt_position; const float* pt_orientation; const long long* pt_token_idx; const unsigned char* pt_type;
+  const unsigned char* pt_pl_type; const long long* pt_polygon; const unsigned char* light_type;
+  /* destinations */
+  float* pos; float* head; int* state; int* token; int* gridtok; unsigned char* tmask; unsigned char* imask;
+  unsigned char* catflag; int* atype; int* bos; float* shape10; int* n_agents; int* av;
+  int* n_map; float* map_pos; float* map_orient; long long* map_tok; long long* map_type; long long* map_pl; long long* map_light;
+  long long* htok; long long* hst; float* p0; float* h0; float* shp; float* gt; unsigned char* val; long long* ids;
+  int* counts;
+} InfgenBatchIngest;
+int infgen_ingest_batch(const InfgenBatchIngest* a, void* stream);
+
+/* Ragged row pack: for every key k < n_keys (<= 32) and scene i < n_scenes (scene s = scene0 + i * scene_step) copy the first
+ * counts[k][s * count_stride[k]] rows of src[k] + s * src_stride[k] (bytes; rows of row_bytes[k] bytes, contiguous) to dst[k] at
+ * row offset sum_{i' < i} counts of scene i' (the exclusive scan runs in the kernel).  The arrays describing the keys are HOST
+ * arrays; src / dst / counts are device pointers.  16-byte copies where the addresses and the byte count allow. */
+int infgen_pack_rows(int n_keys, const void* const* src, const long long* src_stride, const int* row_bytes,
+                     const int* const* counts, const int* count_stride, void* const* dst, int n_scenes, int scene0, int scene_step,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

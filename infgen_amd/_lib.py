@@ -102,6 +102,19 @@ class Rollout(C.Structure):
     ]
 
 
+class BatchIngest(C.Structure):
+    """InfgenBatchIngest (include/infgen_hip.h): a ragged Batch's device arrays and the rollout buffers they are written to"""
+    _fields_ = ([(k, _i) for k in ('S', 'copies', 'A_cap', 'M_cap', 'T', 'T0', 'P', 'hc', 'H', 'motion_cols', 'pos_dim',
+                                   'pt_pos_dim', 'n_polygons', '_pad0')] +
+                [(k, _p) for k in ('agent_ptr', 'pt_ptr', 'av_index', 'src_graph', 'state_idx', 'token_idx', 'grid_token_idx',
+                                   'token_pos', 'token_heading', 'raw_valid', 'valid_mask', 'shape', 'position', 'heading', 'type',
+                                   'id', 'pt_position', 'pt_orientation', 'pt_token_idx', 'pt_type', 'pt_pl_type', 'pt_polygon',
+                                   'light_type',
+                                   'pos', 'head', 'state', 'token', 'gridtok', 'tmask', 'imask', 'catflag', 'atype', 'bos',
+                                   'shape10', 'n_agents', 'av', 'n_map', 'map_pos', 'map_orient', 'map_tok', 'map_type', 'map_pl',
+                                   'map_light', 'htok', 'hst', 'p0', 'h0', 'shp', 'gt', 'val', 'ids', 'counts')])
+
+
 # symbol -> (restype, argtypes); every symbol include/infgen_hip.h declares
 SYMBOLS = {
     'infgen_layout_query': (_i, [_i]),
@@ -179,6 +192,9 @@ SYMBOLS = {
                                        C.POINTER(C.c_double), C.POINTER(_i)]),
     'infgen_prof_set_stride': (_i, [_i]),
     'infgen_prof_seen': (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    'infgen_ingest_batch': (_i, [C.POINTER(BatchIngest), _p]),
+    'infgen_pack_rows': (_i, [_i, C.POINTER(_p), C.POINTER(C.c_longlong), C.POINTER(_i), C.POINTER(_p), C.POINTER(_i),
+                              C.POINTER(_p), _i, _i, _i, _p]),
 }
 
 Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_ATTN_CAP, Q_MAX_AGENTS, \

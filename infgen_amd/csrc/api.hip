@@ -206,7 +206,7 @@ extern "C" int infgen_layout_query(int what) {
     case INFGEN_Q_FOURIER_PACK_SIZE_N4: return fourier_pack_size(4);
     case INFGEN_Q_TILE_ROWS: return TR;
     case INFGEN_Q_EDGE_ATTN_CAP: return 1 << 30;   /* single-pass kernel: no per-row edge cap */
-    case INFGEN_Q_MAX_AGENTS: return 1024;
+    case INFGEN_Q_MAX_AGENTS: return MAX_SCENE_AGENTS;
     case INFGEN_Q_ABI_VERSION: return 1;
     case INFGEN_Q_SIZEOF_ROLLOUT: return (int)sizeof(InfgenRollout);
     default: return -1;
@@ -1821,4 +1821,46 @@ extern "C" int infgen_insert_heading(const InfgenRollout* r, const InfgenInserti
   hipLaunchKernelGGL(k_note_riders, dim3(ceil_div(S, NT)), dim3(NT), 0, hs, I->new_row, I->inserted, S, I->prev_row, I->prev_mask,
                      I->pend_row, I->pend_mask);
   return check_launch("k_note_riders");
+}
+
+// ---------------------------------------------------------------------------------- ragged batch ingest / row pack
+extern "C" int infgen_ingest_batch(const InfgenBatchIngest* a, void* stream) {
+  if (!a) return fail("infgen_ingest_batch", "null argument block");
+  if (a->S <= 0) return 0;
+  if (a->copies < 1 || a->S % a->copies) return fail("infgen_ingest_batch", "S must be a positive multiple of copies");
+  if (a->A_cap < 1 || a->A_cap > MAX_SCENE_AGENTS) return fail("infgen_ingest_batch", "A_cap must be in 1..INFGEN_Q_MAX_AGENTS");
+  if (a->M_cap < 1) return fail("infgen_ingest_batch", "M_cap must be positive");
+  if (a->hc < 1 || a->T0 < a->hc || a->T0 > a->T) return fail("infgen_ingest_batch", "need 1 <= hc <= T0 <= T");
+  if (a->H < 1 || a->P <= a->H || a->pos_dim < 2 || a->pt_pos_dim < 2 || a->motion_cols < 0)
+    return fail("infgen_ingest_batch", "bad step geometry (need P > H >= 1, pos_dim >= 2, pt_pos_dim >= 2)");
+  const void* need[] = {a->agent_ptr, a->pt_ptr, a->av_index, a->src_graph, a->state_idx, a->token_idx, a->grid_token_idx,
+                        a->token_pos, a->token_heading, a->raw_valid, a->valid_mask, a->shape, a->position, a->heading, a->type,
+                        a->id, a->pt_position, a->pt_orientation, a->pt_token_idx, a->pt_type, a->pt_pl_type, a->pt_polygon,
+                        a->light_type, a->pos, a->head, a->state, a->token, a->gridtok, a->tmask, a->imask, a->catflag, a->atype,
+                        a->bos, a->shape10, a->n_agents, a->av, a->n_map, a->map_pos, a->map_orient, a->map_tok, a->map_type,
+                        a->map_pl, a->map_light, a->htok, a->hst, a->p0, a->h0, a->shp, a->gt, a->val, a->ids, a->counts};
+  for (const void* p : need)
+    if (!p) return fail("infgen_ingest_batch", "null input or destination pointer");
+  hipLaunchKernelGGL(k_ingest_batch, dim3(a->S, 3), dim3(256), 0, (hipStream_t)stream, *a);
+  return check_launch("infgen_ingest_batch");
+}
+
+extern "C" int infgen_pack_rows(int n_keys, const void* const* src, const long long* src_stride, const int* row_bytes,
+                                const int* const* counts, const int* count_stride, void* const* dst, int n_scenes, int scene0,
+                                int scene_step, void* stream) {
+  if (n_keys <= 0 || n_scenes <= 0) return 0;
+  if (n_keys > PACK_MAX_KEYS) return fail("infgen_pack_rows", "at most 32 keys per call");
+  if (!src || !src_stride || !row_bytes || !counts || !count_stride || !dst || scene0 < 0 || scene_step < 1)
+    return fail("infgen_pack_rows", "null key table or bad scene range");
+  PackRowsArgs a{};
+  for (int k = 0; k < n_keys; ++k) {
+    if (!src[k] || !dst[k] || !counts[k] || row_bytes[k] < 0 || count_stride[k] < 1)
+      return fail("infgen_pack_rows", "null pointer or bad row size / count stride in the key table");
+    a.src[k] = static_cast<const char*>(src[k]); a.dst[k] = static_cast<char*>(dst[k]);
+    a.src_stride[k] = src_stride[k]; a.row_bytes[k] = row_bytes[k];
+    a.counts[k] = counts[k]; a.count_stride[k] = count_stride[k];
+  }
+  a.n_keys = n_keys; a.n_scenes = n_scenes; a.scene0 = scene0; a.scene_step = scene_step;
+  hipLaunchKernelGGL(k_pack_rows, dim3(n_scenes, n_keys), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("infgen_pack_rows");
 }

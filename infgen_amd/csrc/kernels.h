@@ -2,6 +2,7 @@
 #pragma once
 #include "tile.cuh"
 #include "layout.h"
+#include "../../include/infgen_hip.h"
 
 namespace ig {
 
@@ -520,5 +521,17 @@ __global__ void k_sample_topk(SampleArgs a);
 __global__ void k_layernorm(const float* X, int rows, const float* g, const float* b, float* Y);
 __global__ void k_radius_edges(RadiusEdgesArgs a);            // forward_kernels.hip
 __global__ void k_motion_features(MotionFeatArgs a);
+
+// agent rows one scene can hold (INFGEN_Q_MAX_AGENTS); the ingest kernel's per-scene LDS tables are this long
+constexpr int MAX_SCENE_AGENTS = 1024;
+// ragged batch ingest / row pack (ingest_kernels.hip; the ingest's argument block is InfgenBatchIngest of include/infgen_hip.h)
+constexpr int PACK_MAX_KEYS = 32;
+struct PackRowsArgs {
+  const char* src[PACK_MAX_KEYS]; char* dst[PACK_MAX_KEYS]; long long src_stride[PACK_MAX_KEYS];
+  const int* counts[PACK_MAX_KEYS]; int count_stride[PACK_MAX_KEYS]; int row_bytes[PACK_MAX_KEYS];
+  int n_keys, n_scenes, scene0, scene_step;
+};
+__global__ void k_ingest_batch(InfgenBatchIngest a);
+__global__ void k_pack_rows(PackRowsArgs a);
 
 }  // namespace ig

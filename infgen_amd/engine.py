@@ -418,6 +418,95 @@ class Ops:
         return x
 
 
+def _edge_index(data):
+    try:
+        return data[('pt_token', 'to', 'map_polygon')]['edge_index']
+    except (KeyError, TypeError):
+        return data['pt_token__to__map_polygon']['edge_index']
+
+
+def read_batch_layout(data, T: int, hc: int, max_rows: int, extra: Sequence[torch.Tensor] = ()) -> Dict:
+    """the offsets of a ragged PyG-style ``Batch`` (rows of every graph concatenated, ``agent.ptr`` / ``pt_token.ptr`` [B + 1],
+    ``agent.av_index`` [B] as GLOBAL rows, i.e. ``av_index + ptr[:-1]``) with ONE device -> host copy: the two ``ptr`` and
+    ``av_index`` concatenated (plus the raw bytes of the ``extra`` device tensors, returned as host arrays of their dtype and
+    shape).  Raises ValueError on a malformed batch - before anything is launched."""
+    ag, pt = data['agent'], data['pt_token']
+    if 'ptr' not in ag or 'ptr' not in pt:
+        raise ValueError('a Batch needs agent.ptr and pt_token.ptr')
+    aptr, mptr = torch.as_tensor(ag['ptr']), torch.as_tensor(pt['ptr'])
+    av = torch.as_tensor(ag['av_index']).reshape(-1)
+    B = int(aptr.numel()) - 1
+    if B < 1 or int(mptr.numel()) != B + 1 or int(av.numel()) != B:
+        raise ValueError(f'agent.ptr {tuple(aptr.shape)}, pt_token.ptr {tuple(mptr.shape)} and av_index {tuple(av.shape)} '
+                         'do not describe one batch of B graphs ([B + 1], [B + 1], [B])')
+    dev = aptr.device
+    parts = [aptr.to(dev, torch.int64), mptr.to(dev, torch.int64), av.to(dev, torch.int64)]
+    ex = [e for e in extra if isinstance(e, torch.Tensor) and e.device == dev]
+    flat = [p_.contiguous().view(torch.uint8) for p_ in parts] + [e.detach().contiguous().reshape(-1).view(torch.uint8) for e in ex]
+    host = torch.cat(flat).cpu().numpy() if len(flat) > 1 else flat[0].cpu().numpy()
+    head = host[:(3 * B + 2) * 8].view(np.int64)
+    a, m, v = head[:B + 1], head[B + 1:2 * B + 2], head[2 * B + 2:]
+    extra_host, o = [], (3 * B + 2) * 8
+    for e in extra:
+        if isinstance(e, torch.Tensor) and e.device == dev:
+            nb = e.numel() * e.element_size()
+            extra_host.append(host[o:o + nb].view(_lib_np_dtype(e.dtype)).reshape(tuple(e.shape)))
+            o += nb
+        else:
+            extra_host.append(e.detach().cpu().numpy() if isinstance(e, torch.Tensor) else np.asarray(e))
+    A, M = np.diff(a), np.diff(m)
+    if a[0] != 0 or m[0] != 0 or (A < 0).any() or (M < 0).any():
+        raise ValueError('agent.ptr / pt_token.ptr must start at 0 and be non-decreasing')
+    st = ag['state_idx']
+    if int(st.shape[0]) != int(a[-1]) or int(pt['position'].shape[0]) != int(m[-1]):
+        raise ValueError(f'ptr ends ({int(a[-1])} agents, {int(m[-1])} map tokens) do not match the arrays '
+                         f'({int(st.shape[0])}, {int(pt["position"].shape[0])})')
+    if int(_edge_index(data).shape[1]) != int(m[-1]):
+        raise ValueError('pt_token -> map_polygon edge_index must hold one edge per map token')
+    T0 = int(st.shape[1])
+    if not hc <= T0 <= T:
+        raise ValueError(f'token columns {T0} outside [{hc}, {T}]')
+    if int(A.max()) > max_rows:
+        raise ValueError(f'a graph holds {int(A.max())} agents, more than the {max_rows} rows a scene can have')
+    if (A < 1).any():
+        raise ValueError('every graph needs at least one agent (its ego)')
+    if not ((v >= a[:-1]) & (v < a[1:])).all():
+        bad = int(np.nonzero(~((v >= a[:-1]) & (v < a[1:])))[0][0])
+        raise ValueError(f'av_index[{bad}] = {int(v[bad])} lies outside graph {bad} (rows {int(a[bad])} .. {int(a[bad + 1]) - 1}); '
+                         'a Batch carries global ego rows (av_index + ptr[:-1])')
+    return dict(B=B, agent_ptr=a.copy(), pt_ptr=m.copy(), av=v.copy(), A=A, M=M, amax=int(A.max()), mmax=int(max(M.max(), 1)),
+                T0=T0, P=int(ag['position'].shape[1]), device=dev, extra=extra_host)
+
+
+def pack_rows(srcs: Sequence[torch.Tensor], counts: Sequence[torch.Tensor], totals: Sequence[int], n_scenes: int,
+              scene0: int = 0, scene_step: int = 1) -> List[torch.Tensor]:
+    """infgen_pack_rows: per key k, the first counts[k][s] rows of every scene s = scene0 + i scene_step (i < n_scenes) of
+    srcs[k] ([scenes][rows][...], contiguous, on one device) concatenated into a new [totals[k]][...] tensor.  counts[k]: an
+    int32 device vector or a column of an int32 matrix (its stride is used); totals[k] must be the sum of those counts."""
+    n = len(srcs)
+    dev = srcs[0].device
+    for t_, c_ in zip(srcs, counts):
+        if not (t_.is_contiguous() and c_.dtype == torch.int32 and t_.device == c_.device == dev and t_.dim() >= 2):
+            raise ValueError('pack_rows takes contiguous [scenes][rows][...] sources and int32 counts on one device')
+    outs = [torch.empty((int(tot),) + tuple(t_.shape[2:]), dtype=t_.dtype, device=dev) for t_, tot in zip(srcs, totals)]
+    P_ = C.c_void_p * n
+    src = P_(*[t_.data_ptr() for t_ in srcs])
+    dst = P_(*[o.data_ptr() if o.numel() else t_.data_ptr() for o, t_ in zip(outs, srcs)])     # (an empty output gets no row)
+    stride = (C.c_longlong * n)(*[t_.stride(0) * t_.element_size() for t_ in srcs])
+    rb = (C.c_int * n)(*[int(np.prod(t_.shape[2:], dtype=np.int64)) * t_.element_size() for t_ in srcs])
+    cnt = P_(*[c_.data_ptr() for c_ in counts])
+    cst = (C.c_int * n)(*[c_.stride(0) for c_ in counts])
+    lib = _lib.load()
+    _lib.check(lib.infgen_pack_rows(n, src, stride, rb, cnt, cst, dst, n_scenes, scene0, scene_step,
+                                    torch.cuda.current_stream(dev).cuda_stream), 'infgen_pack_rows')
+    return outs
+
+
+def _lib_np_dtype(dt):
+    return {torch.float32: np.float32, torch.int64: np.int64, torch.int32: np.int32, torch.uint8: np.uint8,
+            torch.bool: np.bool_, torch.float64: np.float64}[dt]
+
+
 class RolloutEngine:
     """Device state + launch sequence for a batch of scenes."""
     copies = 1          # rollouts per scene over one map encoding (instance attribute when given; see __init__)
@@ -430,7 +519,10 @@ class RolloutEngine:
                  sample_k: int = 1, sample_uniforms: Optional[np.ndarray] = None, options: Optional[Mapping[str, int]] = None,
                  insert_k: int = 1, insert_uniforms: Optional[np.ndarray] = None, seed_outputs: bool = False,
                  use_graph: Optional[bool] = None, copies: int = 1, flags: Optional[Mapping[str, bool]] = None,
-                 tap_layers: bool = False):
+                 tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None):
+        """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
+        is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
+        never exceed) and set up on the device by the ingest kernel (``reload_batch``)"""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -457,8 +549,15 @@ class RolloutEngine:
         self.copies = int(copies)
         assert self.copies >= 1
         self.scenes = scenes
-        self.S0 = len(scenes)
-        self.S = S = len(scenes) * self.copies
+        self._batch_lay = None
+        self._bc_host = None
+        if batch is not None:
+            assert scenes is None and teacher is None and x_pt_override is None, 'a Batch engine takes no host scenes / teacher'
+            batch_layout = batch_layout or read_batch_layout(batch, cfg.num_columns, cfg.hist_columns,
+                                                             self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
+            self._batch_lay = batch_layout
+        self.S0 = len(scenes) if batch is None else batch_layout['B']
+        self.S = S = self.S0 * self.copies
         self.T = T = cfg.num_columns
         self.R = R = cfg.num_recurrent_steps_val
         self.hc = hc = cfg.hist_columns
@@ -501,10 +600,14 @@ class RolloutEngine:
         # ------------------------------------------------ host-side scene setup
         self._stacked = None
         self._hosts_light = False
-        hosts = self._replicate(self._setup_scenes(scenes))
-        self.hosts = hosts
-        amax = max(h['A'] for h in hosts)
-        mmax = max(h['M'] for h in hosts)
+        if batch is None:
+            hosts = self._replicate(self._setup_scenes(scenes))
+            self.hosts = hosts
+            amax = max(h['A'] for h in hosts)
+            mmax = max(h['M'] for h in hosts)
+        else:                                  # (the padded fill arrays below; the ingest kernel writes the scenes)
+            hosts, self.hosts = [], None
+            amax, mmax = batch_layout['amax'], batch_layout['mmax']
         self._amax0 = amax
         head = 0
         if self.insertion:
@@ -593,6 +696,9 @@ class RolloutEngine:
         self._map_nbr_cap = 40          # compacted pt<->pt edges per map token (grown on overflow)
         self._prologue_done = False
         self._decoded_rows = torch.zeros((), device=dev, dtype=torch.int64)
+        self._ing = None
+        if batch is not None:
+            self._ingest(batch, batch_layout)
 
     # ------------------------------------------------------------------ scene arrays (host -> device)
     _SCENE_ARRAYS = ('pos', 'head', 'state', 'token', 'gridtok', 'tmask', 'imask', 'catflag', 'atype', 'bos', 'n_agents', 'n_map',
@@ -822,6 +928,109 @@ class RolloutEngine:
             self._epi = epi
             self._hosts_light = False
         return self.hosts
+
+    # ------------------------------------------------------------------ a ragged Batch on the device
+    def fits_batch(self, layout: Mapping) -> bool:
+        """``fits`` for a ragged Batch (``read_batch_layout``): same graph count, unfiltered rows + insertion head-room and map
+        tokens inside this engine's rows, token columns inside T"""
+        if self._batch_lay is None or layout['B'] != self.S0 or self.teacher_token is not None:
+            return False
+        head = (self.A_cap - self._amax0) if self.insertion else 0
+        return layout['amax'] + head <= self.A_cap and layout['mmax'] <= self.M_cap and layout['T0'] <= self.T
+
+    def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
+                     insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None):
+        """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
+        writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
+        only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
+        given).  ``src_graph`` [S] (int32, device): the graph of every agent-side scene; default: graph i's copies adjacent."""
+        if layout is None:
+            layout = read_batch_layout(batch, self.T, self.hc, self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
+        assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
+        if self.sample_k > 1:
+            assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
+            self.sample_u.copy_(torch.from_numpy(self._uniform_rows(sample_uniforms, layout['amax'])))
+        if self.insert_k > 1:
+            assert insert_uniforms is not None, 'cell sampling needs caller-supplied uniforms [steps][10][S]'
+            self._insert_u.copy_(torch.from_numpy(np.ascontiguousarray(insert_uniforms, dtype=np.float32)))
+        self._ingest(batch, layout, src_graph)
+        self._init = None
+        self._wgraph = None
+        self._mg_checked = False
+        self._prologue_done = False
+
+    def _ingest(self, batch, layout, src_graph=None):
+        cfg, dev, lib = self.cfg, self.device, self.lib
+        S, A_cap, M_cap, T, hc, H = self.S, self.A_cap, self.M_cap, self.T, self.hc, cfg.num_historical_steps
+        ag, pt = batch['agent'], batch['pt_token']
+        keep = []                                   # converted inputs stay referenced until the launch is enqueued
+
+        def arr(x, dtype):
+            t_ = torch.as_tensor(x, device=dev)
+            if t_.dtype != dtype:
+                t_ = t_.view(torch.uint8) if (t_.dtype == torch.bool and dtype == torch.uint8) else t_.to(dtype)
+            t_ = t_.contiguous()
+            keep.append(t_)
+            return t_.data_ptr()
+        P = layout['P']
+        Rg = P - H
+        i64, f32, u8 = torch.int64, torch.float32, torch.uint8
+        if self._ing is None or self._ing['gt'].shape[2] != Rg:
+            z = lambda *shape, dt=f32: torch.zeros(*shape, dtype=dt, device=dev)
+            self._ing = dict(htok=z(S, A_cap, hc, dt=i64), hst=z(S, A_cap, hc, dt=i64), p0=z(S, A_cap, 2), h0=z(S, A_cap),
+                             ids=z(S, A_cap, dt=i64), shp=z(S, A_cap, 3), gt=z(S, A_cap, Rg, 2), val=z(S, A_cap, T, dt=torch.bool),
+                             counts=z(S, 3, dt=torch.int32))
+        E = self._ing
+        if src_graph is None:
+            src_graph = (torch.arange(S, device=dev, dtype=torch.int32) // self.copies)
+        src_graph = src_graph.to(dev, torch.int32).contiguous()
+        a = _lib.BatchIngest()
+        a.S, a.copies, a.A_cap, a.M_cap, a.T, a.T0, a.P = S, self.copies, A_cap, M_cap, T, layout['T0'], P
+        a.hc, a.H, a.motion_cols = hc, H, H // cfg.shift
+        pos_t, ppos_t = torch.as_tensor(ag['position']), torch.as_tensor(pt['position'])
+        a.pos_dim, a.pt_pos_dim = int(pos_t.shape[2]), int(ppos_t.shape[1])
+        light = torch.as_tensor(batch['map_polygon']['light_type'])
+        a.n_polygons = int(light.shape[0])
+        a.agent_ptr, a.pt_ptr, a.av_index = arr(ag['ptr'], i64), arr(pt['ptr'], i64), arr(torch.as_tensor(ag['av_index']).reshape(-1), i64)
+        a.src_graph = src_graph.data_ptr()
+        a.state_idx, a.token_idx, a.grid_token_idx = arr(ag['state_idx'], i64), arr(ag['token_idx'], i64), arr(ag['grid_token_idx'], i64)
+        a.token_pos, a.token_heading = arr(ag['token_pos'], f32), arr(ag['token_heading'], f32)
+        a.raw_valid, a.valid_mask = arr(ag['raw_agent_valid_mask'], u8), arr(ag['valid_mask'], u8)
+        a.shape, a.position, a.heading = arr(ag['shape'], f32), arr(pos_t, f32), arr(ag['heading'], f32)
+        a.type, a.id = arr(ag['type'], u8), arr(ag['id'], i64)
+        a.pt_position, a.pt_orientation = arr(ppos_t, f32), arr(pt['orientation'], f32)
+        a.pt_token_idx, a.pt_type, a.pt_pl_type = arr(pt['token_idx'], i64), arr(pt['type'], u8), arr(pt['pl_type'], u8)
+        a.pt_polygon = arr(torch.as_tensor(_edge_index(batch))[1], i64)
+        a.light_type = arr(light, u8)
+        for k_ in ('pos', 'head', 'state', 'token', 'gridtok', 'tmask', 'imask', 'catflag', 'atype', 'bos', 'n_agents', 'av', 'n_map',
+                   'map_pos', 'map_orient'):
+            setattr(a, k_, getattr(self, k_).data_ptr())
+        a.shape10 = self._shape10.data_ptr()
+        a.map_tok, a.map_type, a.map_pl, a.map_light = (t_.data_ptr() for t_ in self._map_cat)
+        for k_ in ('htok', 'hst', 'p0', 'h0', 'shp', 'gt', 'val', 'ids', 'counts'):
+            setattr(a, k_, E[k_].data_ptr())
+        _lib.check(lib.infgen_ingest_batch(C.byref(a), self.ops.stream), 'infgen_ingest_batch')
+        del keep
+        self._batch_lay = layout
+        self._bc_host = None
+        self.scenes, self.hosts, self._stacked, self._hosts_light = None, None, None, False
+        self._gt_len = [Rg] * S
+        self._epi = dict(htok=E['htok'], hst=E['hst'], p0=E['p0'], h0=E['h0'], ids=E['ids'], shp=E['shp'], gt=E['gt'], val=E['val'],
+                         n0=E['counts'][:, 0].long(), n0_host=None,
+                         eval_shape=torch.tensor([[4.3, 1.8, 1.0], [0.5, 0.5, 1.0], [1.9, 0.5, 1.0]], device=dev))
+
+    def batch_counts(self):
+        """(final agent counts [S], ingest counts [S][3]: kept rows, ego row after filtering, rows removed before the ego) of an
+        ingested Batch - the one device -> host copy after its rollout; also rebuilds the light per-scene host dicts"""
+        if self._bc_host is None:
+            S = self.S
+            h = torch.cat([self.n_agents, self._ing['counts'].reshape(-1)]).cpu().numpy().astype(np.int64)
+            n_fin, c = h[:S], h[S:].reshape(S, 3)
+            self._bc_host = (n_fin, c)
+            M = self._batch_lay['M']
+            self.hosts = [dict(A=int(c[s, 0]), M=int(M[s // self.copies]), av=int(c[s, 1]), removed=int(c[s, 2])) for s in range(S)]
+            self._epi['n0_host'] = c[:, 0].copy()
+        return self._bc_host
 
     def _uniform_rows(self, sample_uniforms, amax) -> np.ndarray:
         steps, S, A_cap = self.cfg.num_decode_steps, self.S, self.A_cap
@@ -1132,6 +1341,7 @@ class RolloutEngine:
 
     def rollout(self):
         """one full pass of the hot path over the batch: prologue + every decode step"""
+        self._bc_host = None
         if (self._graph_all and not self.insertion and self._x_pt_override is None and self._mg_checked and self._init is not None
                 and self._ctx is not None and not _lib.prof_active()):
             self._rollout_graph()                # (the first rollout of a batch runs eagerly: buffers, tables, edge capacities)
@@ -1465,6 +1675,8 @@ class RolloutEngine:
     def outputs(self) -> List[Dict[str, np.ndarray]]:
         """the reference's return dict per scene (agent_decoder.py:2303-2389); rows appended by the
         insertion loop follow the initial ones like in the reference"""
+        if self._batch_lay is not None:
+            raise RuntimeError('an ingested Batch has no host-side scenes: use outputs_batch() / outputs_device()')
         torch.cuda.synchronize(self.device)
         self._full_hosts()
         cfg, hc, H = self.cfg, self.hc, self.cfg.num_historical_steps
@@ -1579,13 +1791,8 @@ class RolloutEngine:
         return dict(htok=t(htok), hst=t(hst), p0=t(p0), h0=t(h0), ids=t(ids), shp=t(shp), gt=t(gt), val=t(val), n0=t(n0),
                          n0_host=n0, eval_shape=t(np.asarray([[4.3, 1.8, 1.0], [0.5, 0.5, 1.0], [1.9, 0.5, 1.0]], np.float32)))
 
-    def outputs_device(self, detach: bool = False) -> List[Dict[str, torch.Tensor]]:
-        """``outputs`` without the host round trip: the same per-scene dicts as device tensors (views of the batch arrays where
-        the layout allows), the epilogue of agent_decoder.py:2303-2389 evaluated for all scenes at once on the device.
-        VIEWS: the per-scene tensors are slices of batch-wide results of this call (an in-place edit of one scene's tensor edits
-        that slice only); ``pos_a`` / ``head_a`` / ``logits`` / ``x_pt`` additionally alias this engine's own buffers, which the next
-        rollout overwrites - ``detach=True`` copies those four batch arrays once (what ``InfGenDecoder`` does, whose engines are
-        reused across calls)."""
+    def _epilogue_arrays(self, detach: bool):
+        """the batch-wide arrays of the epilogue of agent_decoder.py:2303-2389 ([S][A_cap][...], all on the device)"""
         cfg, hc, H, dev = self.cfg, self.hc, self.cfg.num_historical_steps, self.device
         S, A_cap, T, R = self.S, self.A_cap, self.T, self.R
         if getattr(self, '_epi', None) is None:
@@ -1634,12 +1841,26 @@ class RolloutEngine:
         if self.ins is not None:
             pshape = torch.where(init[..., None], E['shp'], self.ins['shape_all'].view(S, A_cap, 3))
         eval_shape = E['eval_shape'][atype]
+        batch = dict(agent_id=E['ids'], pos_a=pos_a, head_a=head_a, pred_traj=pt, pred_head=ph, pred_state=ps, pred_valid=pvalid,
+                     pred_type=atype, pred_shape=pshape, eval_shape=eval_shape, next_token_idx=ntok, next_state_idx=nstate)
+        return batch, E, ph, lg_all, x_pt_all, n_fin
+
+    def outputs_device(self, detach: bool = False) -> List[Dict[str, torch.Tensor]]:
+        """``outputs`` without the host round trip: the same per-scene dicts as device tensors (views of the batch arrays where
+        the layout allows), the epilogue of agent_decoder.py:2303-2389 evaluated for all scenes at once on the device.
+        VIEWS: the per-scene tensors are slices of batch-wide results of this call (an in-place edit of one scene's tensor edits
+        that slice only); ``pos_a`` / ``head_a`` / ``logits`` / ``x_pt`` additionally alias this engine's own buffers, which the next
+        rollout overwrites - ``detach=True`` copies those four batch arrays once (what ``InfGenDecoder`` does, whose engines are
+        reused across calls)."""
+        if self._batch_lay is not None:
+            self.batch_counts()
+        batch, E, ph, lg_all, x_pt_all, n_fin = self._epilogue_arrays(detach)
+        cfg, hc, H, dev = self.cfg, self.hc, self.cfg.num_historical_steps, self.device
+        S, A_cap, T, R = self.S, self.A_cap, self.T, self.R
         # the only host copy: the final agent counts - known without asking when nothing can be inserted (then the call returns
         # with the epilogue enqueued behind the rollout and nothing waited for)
         n_host = n_fin.cpu().numpy() if self.insertion else E['n0_host']
         outs = []
-        batch = dict(agent_id=E['ids'], pos_a=pos_a, head_a=head_a, pred_traj=pt, pred_head=ph, pred_state=ps, pred_valid=pvalid,
-                     pred_type=atype, pred_shape=pshape, eval_shape=eval_shape, next_token_idx=ntok, next_state_idx=nstate)
         gt_all, val_all, gt_len = E['gt'], E['val'], self._gt_len
         seed_out, ins = self.seed_out, self.ins
         A_capl, M_capl = A_cap, self.M_cap
@@ -1676,11 +1897,71 @@ class RolloutEngine:
             outs.append(o)
         return outs
 
+    _PACK_FIN = ('agent_id', 'pos_a', 'head_a', 'pred_traj', 'pred_head', 'pred_state', 'pred_valid', 'pred_type', 'pred_shape',
+                 'eval_shape', 'next_token_idx', 'next_state_idx')
+
+    def outputs_batch(self) -> List[Dict]:
+        """the batched epilogue of an ingested Batch: one dict per copy (``copies`` rollouts of every graph), each holding the B
+        graphs' agents concatenated in graph order - graph s's rows are exactly ``outputs_device()``'s rows of its scene - plus
+        ``agent_batch`` [N] / ``agent_ptr`` [B + 1] / ``ego_index`` [B] (rows into the concatenation) and ``x_pt`` [sum M][D] in
+        pt_token order.  ``valid_mask`` / ``gt_traj`` hold the initial agents only (as per scene).  The rows are gathered by
+        infgen_pack_rows (one launch per copy); the one host copy is ``batch_counts()``."""
+        assert self._batch_lay is not None, 'outputs_batch() needs an engine set up from a Batch (reload_batch)'
+        n_fin, c = self.batch_counts()
+        batch, E, ph, lg_all, x_pt_all, _ = self._epilogue_arrays(False)
+        S, A_cap, T, B, n, dev = self.S, self.A_cap, self.T, self.S0, self.copies, self.device
+        fin, init = self.n_agents, self._ing['counts'][:, 0]
+        keys = self._PACK_FIN + ('valid_mask', 'gt_traj')
+        srcs = [batch[k].contiguous() for k in self._PACK_FIN] + [E['val'], E['gt']]
+        x_pt = None
+        if x_pt_all is not None:
+            M = self._batch_lay['M']
+            x_pt = pack_rows([x_pt_all.view(B, self.M_cap, -1)], [self.n_map], [int(M.sum())], B)[0]
+        outs = []
+        for j in range(n):
+            f_j, i_j = n_fin[j::n], c[j::n, 0]
+            tots = [int(f_j.sum())] * len(self._PACK_FIN) + [int(i_j.sum())] * 2
+            cols = [fin] * len(self._PACK_FIN) + [init] * 2
+            packed = dict(zip(keys, pack_rows(srcs, cols, tots, B, scene0=j, scene_step=n)))
+            ptr = np.concatenate([[0], np.cumsum(f_j)])
+            o = dict(packed)
+            o['pred_z'] = torch.zeros(int(f_j.sum()), ph.shape[2], device=dev)
+            o['agent_ptr'] = torch.from_numpy(ptr).to(dev)
+            o['agent_batch'] = torch.repeat_interleave(torch.arange(B, device=dev), torch.from_numpy(f_j).to(dev), output_size=int(f_j.sum()))
+            o['ego_index'] = torch.from_numpy(ptr[:-1] + c[j::n, 1]).to(dev)
+            o['num_inserted'] = torch.from_numpy(f_j - i_j).to(dev)
+            if x_pt is not None:
+                o['x_pt'] = x_pt
+            if self.ins is not None:
+                labels = []
+                for g in range(B):
+                    s = g * n + j
+                    A = int(n_fin[s])
+                    lab = [[None] * T for _ in range(A)]
+                    per_step = {}
+                    for r_, t_ in self.ins['inserted_rows'][s]:
+                        k_ = per_step[t_] = per_step.get(t_, 0) + 1
+                        a_ = r_ - s * A_cap
+                        if a_ < A and self.hc + t_ < T:
+                            lab[a_][self.hc + t_] = f'A{k_}'
+                    labels.extend(lab)
+                o['agent_labels'] = labels
+            if self.seed_out is not None:
+                so = self.seed_out
+                for k_out, k_in in (('next_state_prob_seed', 'state'), ('next_pos_rel_prob_seed', 'pos'), ('grid_agent_occ_seed', 'occ_a'),
+                                    ('grid_pt_occ_seed', 'occ_p'), ('grid_agent_occ_gt_seed', 'occ_gt')):
+                    v = so[k_in][j::n]
+                    o[k_out] = v.reshape((-1,) + tuple(v.shape[2:])).clone()
+            outs.append(o)
+        return outs
+
     def agent_steps(self) -> int:
         """agent-steps (10 Hz) decoded by the last full rollout of this batch (the rows decoded at every step, incl. the
         ones scenario insertion appended, x 5 simulated steps per decode step)"""
         if self.insertion and self._prologue_done:
             return int(self._decoded_rows.item()) * self.cfg.shift
+        if self.hosts is None:
+            self.batch_counts()
         return int(sum(h['A'] for h in self.hosts)) * self.R
 
 

@@ -39,9 +39,18 @@ def format_rollouts(data, rollouts: Sequence[Dict[str, Tensor]], to_cpu: bool = 
                 agent_id='agent_id')
     out = {k: torch.stack([r[src] for r in rollouts], dim=1) for k, src in keys.items()}
     first = rollouts[0]
+    if 'agent_batch' in first:
+        # a multi-graph Batch decoded at once (InfGenDecoder.inference): rows of every graph concatenated, agent_batch per row,
+        # ego_index [B] rows into the concatenation; av_id one per graph (a plain int for one graph, like the single-scene dict)
+        ego = torch.as_tensor(first['ego_index']).reshape(-1).long()
+        av = first['agent_id'][ego.to(first['agent_id'].device)].long()
+        av_id = av if av.numel() > 1 else int(av[0])
+        agent_batch = first['agent_batch'].long()
+    else:
+        av_id = int(first['agent_id'][int(first['ego_index'])])
+        agent_batch = torch.zeros(out['pred_traj'].shape[0], dtype=torch.long, device=out['pred_traj'].device)
     out = dict(_scenario_id=data['scenario_id'], scenario_id=get_scenario_id_int_tensor(data['scenario_id']),
-               av_id=int(first['agent_id'][int(first['ego_index'])]),
-               agent_batch=torch.zeros(out['pred_traj'].shape[0], dtype=torch.long, device=out['pred_traj'].device),
+               av_id=av_id, agent_batch=agent_batch,
                tfrecord_path=data['tfrecord_path'] if 'tfrecord_path' in data else None, **out)
     if to_cpu:
         out = {k: v.cpu() if torch.is_tensor(v) else v for k, v in out.items()}
@@ -95,8 +104,11 @@ def output_to_rollouts(scenario: Dict) -> List[ScenarioRollouts]:
     n_scen = sid.shape[0]
     n_step = scenario['pred_traj'].shape[2]
     state = scenario['pred_state'] if 'pred_state' in scenario else torch.zeros_like(scenario['pred_z']).long()
+    av_all = scenario.get('av_id', -1)
     out = []
     for s in range(n_scen):
+        # av_id: one int for the scenario, or one per scenario of a batched dict
+        av_s = int(av_all[s]) if torch.is_tensor(av_all) and av_all.numel() > 1 else av_all
         rows = torch.nonzero(batch == s)[:, 0]
         g = lambda k: scenario[k].index_select(0, rows)
         traj, shape, ids = g('pred_traj'), g('pred_shape'), g('agent_id')
@@ -109,7 +121,7 @@ def output_to_rollouts(scenario: Dict) -> List[ScenarioRollouts]:
                 length=sh[..., 0], width=sh[..., 1], height=sh[..., 2], valid=g('pred_valid')[:, r], state=st[:, r],
                 object_id=ids[:, r], processed_object_id=ids[:, r], object_type=g('pred_type')[:, r],
                 token_pos=g('token_pos')[:, r, :, :2], token_heading=g('token_head')[:, r],
-                av_id=scenario.get('av_id', -1), processed_av_id=scenario.get('av_id', -1)))
+                av_id=av_s, processed_av_id=av_s))
         out.append(ScenarioRollouts(joint_scenes=scenes, scenario_id=''.join(chr(c) for c in sid[s].tolist() if c > 0)))
     return out
 

@@ -209,11 +209,13 @@ class InfGen(nn.Module):
             pt['ptr'] = torch.tensor([0, pt['position'].shape[0]], device=dev)
         data['batch_size_a'] = ag['ptr'][1:] - ag['ptr'][:-1]
         data['batch_size_pl'] = pt['ptr'][1:] - pt['ptr'][:-1]
+        # batched graphs: the ego rows in the global form, once for both branches (:610-616) - the open-loop forward and the
+        # closed-loop rollout of a multi-graph Batch (InfGenDecoder.inference) read them so
+        if isinstance(ag['av_index'], torch.Tensor) and ag['av_index'].numel() > 1:
+            ag['av_index'] = ag['av_index'] + ag['ptr'][:-1]
         if self.val_open_loop or int(os.getenv('OPEN_LOOP', 0)):
             # reference :627-686: teacher-forced forward, token + state cross-entropies as 'val_loss' (the occupancy plots of
             # that branch are not part of the HIP path)
-            if isinstance(ag['av_index'], torch.Tensor) and ag['av_index'].numel() > 1:
-                ag['av_index'] = ag['av_index'] + ag['ptr'][:-1]                    # batched graphs (:610-611)
             pred = self(data)
             self.open_loop_pred = pred
             loss = torch.zeros((), device=pred['next_token_prob'].device)

@@ -6,6 +6,7 @@ libinfgen_hip.so; ``inference_batch`` is the throughput entry (many scenes in lo
 """
 from __future__ import annotations
 
+import os
 import weakref
 from typing import Dict, List, Mapping, Optional, Sequence
 
@@ -14,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import InsertionHeadroomError, PackedWeights, RolloutEngine
+from ..engine import InsertionHeadroomError, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
 from .attr_tokenizer import Attr_Tokenizer
@@ -150,6 +151,63 @@ def stack_datas(datas, min_scenes: int = 8, any_device: bool = False):
                 'edge_index': stack([edge(d) for d in datas])}
     except (KeyError, TypeError, AttributeError, RuntimeError):
         return None
+
+
+def num_graphs(data) -> int:
+    """graphs in ``data``: ``num_graphs`` of a PyG-style Batch, else the length of ``agent.ptr`` - 1, else 1"""
+    ng = getattr(data, 'num_graphs', None)
+    if ng is None and isinstance(data, Mapping):
+        ng = data.get('num_graphs')
+    ag = data['agent']
+    if 'ptr' in ag and ag['ptr'] is not None:
+        ng = max(int(ng or 1), int(torch.as_tensor(ag['ptr']).numel()) - 1)
+    return int(ng or 1)
+
+
+def batch_datas(datas) -> Dict:
+    """single-graph ``data`` dicts (device tensors) -> one PyG-style Batch dict, laid out like ``Batch.from_data_list`` of the
+    reference's HeteroData: the rows of every key concatenated, ``agent.ptr`` / ``pt_token.ptr`` / ``*.batch``, the pt_token ->
+    map_polygon edges offset by the token and polygon counts, ``num_graphs``; ``av_index`` in the global form (``av_index +
+    ptr[:-1]``) that ``InfGen.validation_step`` hands to the decoder.  The trajectory-token vocabularies are taken from the first
+    graph (they are one table)."""
+    dev = torch.as_tensor(datas[0]['agent']['state_idx']).device
+    cat = lambda vals: torch.cat([torch.as_tensor(v).to(dev) for v in vals])
+    A = [int(d['agent']['state_idx'].shape[0]) for d in datas]
+    M = [int(d['pt_token']['position'].shape[0]) for d in datas]
+    L = [int(d['map_polygon']['light_type'].shape[0]) for d in datas]
+    aptr, mptr, lptr = (torch.from_numpy(np.concatenate([[0], np.cumsum(x)])).to(dev) for x in (A, M, L))
+    B = len(datas)
+    agent = {k: cat([d['agent'][k] for d in datas]) for k in _STACK_AGENT_KEYS if k != 'av_index'}
+    agent['av_index'] = cat([torch.as_tensor(d['agent']['av_index']).reshape(-1)[:1].to(dev) for d in datas]) + aptr[:-1]
+    for k in ('trajectory_token_veh', 'trajectory_token_ped', 'trajectory_token_cyc'):
+        agent[k] = datas[0]['agent'][k]
+    agent['ptr'] = aptr
+    agent['batch'] = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(A, device=dev))
+    agent['num_nodes'] = sum(A)
+    pt = {k: cat([d['pt_token'][k] for d in datas]) for k in _STACK_PT_KEYS}
+    pt['ptr'] = mptr
+    pt['batch'] = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(M, device=dev))
+    pt['num_nodes'] = sum(M)
+    key = ('pt_token', 'to', 'map_polygon')
+
+    def edge(d):
+        try:
+            return d[key]['edge_index']
+        except (KeyError, TypeError):
+            return d['pt_token__to__map_polygon']['edge_index']
+    off = lambda i: torch.tensor([[int(mptr[i])], [int(lptr[i])]], device=dev)
+    out = {'agent': agent, 'pt_token': pt, 'map_polygon': {'light_type': cat([d['map_polygon']['light_type'] for d in datas])},
+           key: {'edge_index': torch.cat([torch.as_tensor(edge(d)).to(dev) + off(i) for i, d in enumerate(datas)], dim=1)},
+           'num_graphs': B}
+    for k in ('agent_valid_mask', 'category', 'valid_mask', 'shape', 'batch_size_a'):
+        if all(k in d for d in datas):
+            out[k] = cat([d[k] for d in datas])
+    if all('av_index' in d for d in datas):
+        out['av_index'] = agent['av_index']
+    if all('scenario_id' in d for d in datas):
+        out['scenario_id'] = [x for d in datas for x in (d['scenario_id'] if isinstance(d['scenario_id'], (list, tuple))
+                                                         else [d['scenario_id']])]
+    return out
 
 
 class _LazyScenes:
@@ -376,6 +434,141 @@ class InfGenDecoder(nn.Module):
             res.append(r)
         return res if batch is not None else res[0]
 
+    _HOST_CACHE = 4             # entries of each host-copy cache below
+
+    @staticmethod
+    def _tensor_key(t):
+        """identity of a tensor's contents for the host-copy caches: address, layout and version counter.  The cache entry
+        keeps the tensor itself alive, so its storage cannot be freed and handed to another tensor while the key is held."""
+        return (t.device, t.data_ptr(), t.dtype, tuple(t.shape), tuple(t.stride()), t._version)
+
+    def _cached(self, name, tensors, make):
+        cache = self.__dict__.setdefault(name, {})
+        key = tuple(self._tensor_key(t) for t in tensors)
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) >= self._HOST_CACHE:
+                cache.pop(next(iter(cache)))
+            hit = cache[key] = (tuple(tensors), make())
+        return hit[1]
+
+    def _host_const(self, t):
+        """host copy of a module constant (grid, map vocabulary), made again only when the tensor changes"""
+        if not isinstance(t, torch.Tensor):
+            return np.asarray(t)
+        return self._cached('_host_consts', [t], lambda: t.detach().cpu().numpy())
+
+    def _run_graphs(self, data, sample_uniforms=None, copies: int = 1, mutate: bool = True) -> List[Dict]:
+        """a ragged multi-graph Batch of device tensors through RolloutEngine.reload_batch (the ingest kernel: filter, pad and
+        set up every scene on the device) and the batched epilogue (outputs_batch: infgen_pack_rows).  One device -> host copy
+        before the first launch (the offsets and av_index; the token vocabularies the tables are keyed by ride along unless the
+        same vocabulary tensors were seen before) and one after the rollout (the agent counts).  -> ``copies`` dicts"""
+        ae = self.agent_encoder
+        w = self._last_w = self._weights()
+        cfg = w.cfg
+        ag = data['agent']
+        copies = int(copies)
+        if ae.num_recurrent_steps_val == -1:
+            ae.num_recurrent_steps_val = int(ag['position'].shape[1]) - ae.num_historical_steps
+            cfg.num_recurrent_steps_val = ae.num_recurrent_steps_val
+        lib = _lib.load()
+        ts = cfg.token_size
+        voc_t = [torch.as_tensor(ag[f'trajectory_token_{k}']) for k in ('veh', 'ped', 'cyc')]
+        map_vocab = np.asarray(self._host_const(self.map_encoder.map_token['traj_src']), np.float32)
+        grid = self._host_const(ae.attr_tokenizer.grid)
+        # the token vocabularies key the engine's tables by content: their host copy (1.2 MB) and hash are made once per set of
+        # vocabulary tensors - the TokenProcessor hands the same module buffers every call; other tensors ride along with the
+        # offsets in the one host copy
+        cache = self.__dict__.setdefault('_vocab_host', {})
+        src = self.map_encoder.map_token['traj_src'], ae.attr_tokenizer.grid
+        keep = list(voc_t) + [t for t in src if isinstance(t, torch.Tensor)]
+        # cached only for one table per type (what the TokenProcessor hands over): a collated Batch's per-graph copies are new
+        # tensors every batch and would only be kept alive here; host-array constants have no identity to key by
+        cacheable = all(isinstance(t, torch.Tensor) for t in src) and all(int(t.shape[0]) == ts for t in voc_t)
+        key = tuple(self._tensor_key(t) for t in keep)
+        hit = cache.get(key) if cacheable else None
+        lay = read_batch_layout(data, cfg.num_columns, cfg.hist_columns, lib.infgen_layout_query(_lib.Q_MAX_AGENTS),
+                                extra=() if hit is not None else [t[:ts] for t in voc_t])
+        if hit is None:
+            vocab_ = {k: np.asarray(v, np.float32) for k, v in zip(('veh', 'ped', 'cyc'), lay['extra'])}
+            tkey_ = PackedWeights.tables_key(*(vocab_[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab)
+            hit = (tuple(keep), vocab_, tkey_)
+            if cacheable:
+                if len(cache) >= self._HOST_CACHE:
+                    cache.pop(next(iter(cache)))
+                cache[key] = hit
+        _, vocab, tkey = hit
+        B = lay['B']
+        S = B * copies
+        cfg.disable_insertion = bool(ae.disable_insertion)
+        k = int(getattr(ae, 'motion_beam_size', 1))
+        if k > 1 and sample_uniforms is None:
+            ucols = lay['amax'] if cfg.disable_insertion else int(lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
+            sample_uniforms = torch.rand(cfg.num_decode_steps, S, ucols).numpy()
+        elif sample_uniforms is not None:
+            sample_uniforms = _np(sample_uniforms)
+        ik = int(getattr(ae, 'insert_beam_size', 1))
+        insert_uniforms = None
+        if ik > 1 and not cfg.disable_insertion:
+            insert_uniforms = torch.rand(cfg.num_decode_steps, 10, S).numpy()
+        debug = bool(int(os.getenv('DEBUG', 0)))
+
+        def make_engine(headroom=None):
+            return RolloutEngine(w, None, vocab, map_vocab, grid, insert_headroom=headroom, force_enter=debug, sample_k=k,
+                                 sample_uniforms=sample_uniforms, insert_k=ik if insert_uniforms is not None else 1,
+                                 insert_uniforms=insert_uniforms, seed_outputs=not cfg.disable_insertion, copies=copies,
+                                 options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay)
+        ekey = ('graphs', S, tkey,
+                bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies)
+        eng = self._engines.get(ekey)
+        if eng is not None and eng.fits_batch(lay):
+            eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay)
+        else:
+            eng = make_engine()
+            if len(self._engines) >= 2:
+                self._engines.pop(next(iter(self._engines)))
+            self._engines[ekey] = eng
+        while True:
+            try:
+                eng.rollout()
+                break
+            except InsertionHeadroomError:
+                limit = lib.infgen_layout_query(_lib.Q_MAX_AGENTS)
+                if eng.A_cap >= limit:
+                    raise
+                eng = self._engines[ekey] = make_engine(headroom=min(2 * eng.A_cap, limit) - lay['amax'])
+        outs = eng.outputs_batch()
+        n_fin, c = eng.batch_counts()
+        dev, steps, G, T_cols = w.device, cfg.num_decode_steps, ae.grid_size, cfg.num_columns
+        map_keys = {'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
+                    'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=dev),
+                    'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=dev),
+                    'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=dev)}
+        passthrough = {k_: data[k_] for k_ in self.data_keys if k_ in data}
+        res = []
+        for j, o in enumerate(outs):
+            for k_, shp_ in (('next_state_prob_seed', (11, steps)), ('next_pos_rel_prob_seed', (11, steps, G)),
+                             ('grid_agent_occ_seed', (11, steps, G)), ('grid_pt_occ_seed', (11, steps, G)),
+                             ('grid_agent_occ_gt_seed', (11, steps, G))):
+                if k_ not in o:
+                    o[k_] = torch.zeros((B * shp_[0],) + shp_[1:], device=dev)
+            if 'agent_labels' not in o:
+                o['agent_labels'] = [[None] * T_cols for _ in range(int(n_fin[j::copies].sum()))]
+            ins = (n_fin - c[:, 0])[j::copies]
+            o['log_message'] = '\n'.join('No agents inserted!' if int(x) == 0 else f'Number of total inserted agents: {int(x)}'
+                                         for x in ins)
+            res.append({**map_keys, **o, **passthrough})
+        # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649), per graph
+        removed = c[::copies, 2]
+        if mutate and removed.any() and 'batch_size_a' in data:
+            try:
+                bsa = data['batch_size_a']
+                bsa -= torch.as_tensor(removed, device=bsa.device, dtype=bsa.dtype) if isinstance(bsa, torch.Tensor) else removed
+                data['batch_size_a'] = bsa
+            except (KeyError, TypeError):
+                pass
+        return res
+
     def get_agent_inputs(self, data):
         raise NotImplementedError('training-only helper (agent_decoder.py:933) — out of the hot path')
 
@@ -403,7 +596,15 @@ class InfGenDecoder(nn.Module):
     def inference(self, data, sample_uniforms=None) -> Dict[str, torch.Tensor]:
         """map encoder + closed-loop rollout of one scene (reference infgen_decoder.py:123-130).
         Greedy unless ``agent_encoder.motion_beam_size > 1``; then tokens are drawn by inverse CDF over the
-        top-k probabilities with ``sample_uniforms`` ([steps][1][A]) or torch.rand when omitted."""
+        top-k probabilities with ``sample_uniforms`` ([steps][1][A]) or torch.rand when omitted.
+        A multi-graph ``data`` (a PyG-style Batch: ``num_graphs > 1`` / ``agent.ptr`` of more than 2 entries, ``av_index`` in
+        the global form) is decoded as B scenes in lockstep (``_run_graphs``): one dict whose per-agent arrays concatenate the
+        graphs' rows in graph order, with ``agent_batch`` / ``agent_ptr`` and ``ego_index`` [B]; ``sample_uniforms`` is then
+        [steps][B][cols], graph s's slice indexed like a single-graph call's; cols must cover every graph's row count BEFORE
+        the filter of agent_decoder.py:1609 (with insertion on: INFGEN_Q_MAX_AGENTS), since the kept counts are only known on
+        the device when the uniforms are checked."""
+        if num_graphs(data) > 1:
+            return self._run_graphs(data, sample_uniforms=sample_uniforms)[0]
         r = self._run(data, sample_uniforms=sample_uniforms)
         x_pt = r.pop('x_pt')
         map_enc = {'x_pt': x_pt, 'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=x_pt.device),
@@ -427,6 +628,8 @@ class InfGenDecoder(nn.Module):
         # one engine batch of n copies of the scene over ONE map encoding (RolloutEngine(copies=n): the map-token graph, the map
         # encoder and the map K / V rows exist once - the reference offers inference_no_map(data, map_enc) for the same purpose);
         # every rollout carries what ``inference`` returns for it: the seed node's outputs and the map_next_token_* keys too
+        if num_graphs(data) > 1:            # B graphs x n copies as one engine batch over B map encodings; n batched dicts
+            return self._run_graphs(data, copies=int(n), mutate=False)
         return self.inference_batch([data.clone() if hasattr(data, 'clone') else dict(data)], seed_outputs=True, copies=int(n))
 
     @torch.no_grad()

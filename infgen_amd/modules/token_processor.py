@@ -48,9 +48,17 @@ class TokenProcessor(torch.nn.Module):
         for k in ('polygon_is_intersection', 'route_type'):
             if 'map_polygon' in data and k in data['map_polygon']:
                 del data['map_polygon'][k]
-        av = int(data['agent']['av_idx'])
-        data['ego_pos'] = data['agent']['token_pos'][[av]]
-        data['ego_heading'] = data['agent']['token_heading'][[av]]
+        ag = data['agent']
+        av_idx = ag['av_idx']
+        if isinstance(av_idx, torch.Tensor) and av_idx.numel() > 1:
+            # a Batch of several graphs: av_idx is per graph, inside it (PyG does not offset it); the ego rows are av_idx + ptr[:-1]
+            rows = av_idx.reshape(-1).to(ag['token_pos'].device).long() + torch.as_tensor(ag['ptr'], device=ag['token_pos'].device)[:-1]
+            data['ego_pos'] = ag['token_pos'][rows]
+            data['ego_heading'] = ag['token_heading'][rows]
+            return data
+        av = int(av_idx)
+        data['ego_pos'] = ag['token_pos'][[av]]
+        data['ego_heading'] = ag['token_heading'][[av]]
         return data
 
     @torch.no_grad()
