@@ -131,7 +131,7 @@ typedef struct InfgenRollout {
   /* packed weights */
   const float* attn_t[INFGEN_MAX_LAYERS]; const float* attn_m[INFGEN_MAX_LAYERS]; const float* attn_a[INFGEN_MAX_LAYERS];
   const float* four_t; const float* four_m; const float* four_a; const float* four_xa;
-  const float* fusion_pack;    /* MLPEmbedding(512): P(512,128) b ln | P(128,128) b ln | P(128,128) b */
+  const float* fusion_pack;    /* MLPEmbedding(512; 384 with no_grid_token): P(K0,128) b ln | P(128,128) b ln | P(128,128) b */
   const float* tok_head_pack; const float* st_head_pack;
   const float* tok_tab; const float* grid_tab; const float* state_emb;
   const float* cat_agent; const float* cat_seed; const float* vocab; const float* grid_xy;
@@ -182,6 +182,10 @@ typedef struct InfgenRollout {
    * (infgen/modules/agent_decoder.py:2133-2158).  A context with tap_x runs the per-sublayer launches (k_layers_p keeps the
    * stream in registers across the triples) */
   float* tap_x;
+  /* the reference's token ablations (agent_decoder.py use_grid_token / use_state_token; 0 = the full-token model).
+   * no_grid_token: the fusion embedding takes [token | x_a | state] (fusion_pack packed with K0 = 384, fus_in keeps its 512
+   * stride) and no grid_tab row is gathered.  no_state_token: after the ego override a predicted 'exit' becomes 'valid'. */
+  int no_grid_token; int no_state_token;
 } InfgenRollout;
 
 int infgen_linear(const float* X, int ldx, const int* gather, int rows, int K,
@@ -390,6 +394,13 @@ typedef struct InfgenInsertion {
   int* host_dec;                              /* PINNED HOST memory [3][S]: inserted, new_row, active */
   float r_seed, r_a2sa, r_pl2sa, angle_interval;
   int n_heading, force_enter, insert_k, max_new;
+  /* the ablated insertion heads (0 / NULL = the full-token model).  no_grid_token: no occupancy embedding, no occ2sa layers (the seed
+   * chain is pt2sa -> a2sa x 3), head_pos_xy (seed_pos_rel_xy_predict_head, MLPLayer 128 -> 2) replaces head_pos / head_offset: the new
+   * row sits at tanh(xy) * r_seed + ego pos (world frame), its grid cell is -1, insert_k is ignored.  no_head_token:
+   * head_heading_theta (seed_heading_rel_theta_predict_head, 128 -> 1) replaces head_heading: heading tanh(theta) * pi + ego heading,
+   * not wrapped (agent_decoder.py:1910-1912, :2060-2074) */
+  const float* head_pos_xy; const float* head_heading_theta;
+  int no_grid_token; int no_head_token;
 } InfgenInsertion;
 /* it: iteration of the step (0: map edges of the seed are built and the agents' edgeless chains are computed); riders != 0: the
  * previous iteration appended rows (prev_row / prev_mask); uniform: [S] for the cell draw when insert_k > 1 */

@@ -59,7 +59,8 @@ class Insertion(C.Structure):
                 ('hid', _p), ('lg_state', _p), ('lg_type', _p), ('shape', _p), ('lg_pos', _p), ('lg_heading', _p), ('offset', _p),
                 ('t1', _p), ('t2', _p), ('shp', _p), ('host_dec', _p),
                 ('r_seed', C.c_float), ('r_a2sa', C.c_float), ('r_pl2sa', C.c_float), ('angle_interval', C.c_float),
-                ('n_heading', _i), ('force_enter', _i), ('insert_k', _i), ('max_new', _i)]
+                ('n_heading', _i), ('force_enter', _i), ('insert_k', _i), ('max_new', _i),
+                ('head_pos_xy', _p), ('head_heading_theta', _p), ('no_grid_token', _i), ('no_head_token', _i)]
 
 
 class Options(C.Structure):
@@ -99,6 +100,7 @@ class Rollout(C.Structure):
         ('teacher_pos', _p), ('teacher_head', _p),
         ('map_scene', _p),
         ('tap_x', _p),
+        ('no_grid_token', _i), ('no_state_token', _i),
     ]
 
 

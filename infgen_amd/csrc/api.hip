@@ -896,6 +896,7 @@ static int validate(const InfgenRollout* r, const char* where) {
   if (r->num_layers <= 0 || r->num_layers > INFGEN_MAX_LAYERS) return fail(where, "bad num_layers");
   if (r->ring <= r->W) return fail(where, "ring must exceed the temporal window");
   if (r->W > 16) return fail(where, "temporal window larger than 16 columns is not supported");
+  if ((r->no_grid_token | r->no_state_token) & ~1) return fail(where, "no_grid_token / no_state_token must be 0 or 1");
   return 0;
 }
 
@@ -954,7 +955,7 @@ static int integrate_impl(const InfgenRollout* r, int t, void* stream, unsigned 
   a.zero_sync = zero_sync ? reinterpret_cast<int*>(r->SIG) : nullptr;       // (k_layers_p's per-scene counters: layers_p_launch)
   a.do_prep = prep ? 1 : 0;
   if (prep) a.prep = rawfeat_args(r, 2 + t);
-  a.st = scene_of(r); a.c = 1 + t; a.t = t; a.R = r->R; a.force_valid = r->force_valid;
+  a.st = scene_of(r); a.c = 1 + t; a.t = t; a.R = r->R; a.force_valid = r->force_valid; a.no_state = r->no_state_token;
   a.next_token = r->next_token; a.next_state = r->next_state;
   a.teacher_token = r->teacher_token; a.teacher_state = r->teacher_state; a.teacher_grid = r->teacher_grid;
   a.teacher_pos = r->teacher_pos; a.teacher_head = r->teacher_head;
@@ -977,7 +978,7 @@ static RawFeatArgs rawfeat_args(const InfgenRollout* r, int col) {
   a.st = scene_of(r); a.col = col; a.tok_tab = r->tok_tab; a.token_size = r->token_size;
   a.grid_tab = r->grid_tab; a.grid_size = r->grid_size; a.state_emb = r->state_emb;
   a.cat_agent = r->cat_agent; a.cat_seed = r->cat_seed; a.raw2 = r->raw2; a.cat = r->cat; a.fus_in = r->fus_in;
-  a.row_list = nullptr; a.row_mask = nullptr; a.n_list = 0;
+  a.row_list = nullptr; a.row_mask = nullptr; a.n_list = 0; a.no_grid = r->no_grid_token;
   return a;
 }
 
@@ -1026,9 +1027,12 @@ extern "C" int infgen_mlp_embedding(const float* X, int ldx, int rows, int K0, c
   return mlp_embedding_impl(X, ldx, rows, K0, pack, tmp1, tmp2, Y, ldy, stream, "infgen_mlp_embedding");
 }
 
+// inputs of fusion_emb: [token | x_a | state | grid] (K0 = 512), without the grid embedding for use_grid_token = False (K0 = 384)
+static inline int fusion_k0(const InfgenRollout* r) { return r->no_grid_token ? 384 : 512; }
+
 // fusion_emb of the gathered rows (fus_in [rows][512]) -> X
 static int raw_feature_fusion(const InfgenRollout* r, void* stream) {
-  return mlp_embedding_impl(r->fus_in, 512, r->S * r->A_cap, 512, r->fusion_pack, r->tmp1, r->tmp2, r->X, 128, stream,
+  return mlp_embedding_impl(r->fus_in, 512, r->S * r->A_cap, fusion_k0(r), r->fusion_pack, r->tmp1, r->tmp2, r->X, 128, stream,
                             "infgen_raw_feature/fusion");
 }
 
@@ -1045,25 +1049,26 @@ extern "C" int infgen_raw_feature_rows(const InfgenRollout* r, int col, const in
   a.st = scene_of(r); a.col = col; a.tok_tab = r->tok_tab; a.token_size = r->token_size;
   a.grid_tab = r->grid_tab; a.grid_size = r->grid_size; a.state_emb = r->state_emb;
   a.cat_agent = r->cat_agent; a.cat_seed = r->cat_seed; a.raw2 = r->raw2; a.cat = r->cat; a.fus_in = r->fus_in;
-  a.row_list = row_list; a.row_mask = row_mask; a.n_list = n;
+  a.row_list = row_list; a.row_mask = row_mask; a.n_list = n; a.no_grid = r->no_grid_token;
   { ProfScope _ps(INFGEN_KID_RAWFEAT, stream);
     hipLaunchKernelGGL(k_rawfeat_prep, dim3(ceil_div(n * 32, NT)), dim3(NT), 0, (hipStream_t)stream, a); }
   RET_IF(check_launch("infgen_raw_feature_rows/prep"));
   RET_IF(infgen_fourier_embed(r->raw2, 2, nullptr, n, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, stream));
   const float* P = r->fusion_pack;
+  const int K0 = fusion_k0(r);
   if (O().attn_mode != 0) {
-    MlpEmbHArgs m{r->fus_in, 512, n, 512, P, r->tmp1, 128};
+    MlpEmbHArgs m{r->fus_in, 512, n, K0, P, r->tmp1, 128};
     int grid = ceil_div(n, 64);
     if (grid > 512) grid = 512;
-    { ProfScope _ps(INFGEN_KID_LINEAR, stream, (double)n * (512 + 128 + 128) * 128.0);
+    { ProfScope _ps(INFGEN_KID_LINEAR, stream, (double)n * (K0 + 128 + 128) * 128.0);
       if (O().gemm_terms == 1) hipLaunchKernelGGL(k_mlpemb_h<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m);
       else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_mlpemb_h_b16<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m);
       else hipLaunchKernelGGL(k_mlpemb_h<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m); }
     RET_IF(check_launch("infgen_raw_feature_rows/fusion"));
   } else {
-    const int o2 = mlpemb_off2(512), o3 = mlpemb_off3(512);
-    RET_IF(infgen_linear(r->fus_in, 512, nullptr, n, 512, P, 128, P + 512 * 128, 128, nullptr, nullptr,
-                         P + 512 * 128 + 128, P + 512 * 128 + 256, 1, r->tmp1, 128, stream));
+    const int o2 = mlpemb_off2(K0), o3 = mlpemb_off3(K0);
+    RET_IF(infgen_linear(r->fus_in, 512, nullptr, n, K0, P, 128, P + K0 * 128, 128, nullptr, nullptr,
+                         P + K0 * 128 + 128, P + K0 * 128 + 256, 1, r->tmp1, 128, stream));
     RET_IF(infgen_linear(r->tmp1, 128, nullptr, n, 128, P + o2, 128, P + o2 + 16384, 128, nullptr, nullptr,
                          P + o2 + 16384 + 128, P + o2 + 16384 + 256, 1, r->tmp2, 128, stream));
     RET_IF(infgen_linear(r->tmp2, 128, nullptr, n, 128, P + o3, 128, P + o3 + 16384, 128, nullptr, nullptr,
@@ -1592,7 +1597,8 @@ extern "C" int infgen_point_edges(const InfgenRollout* r, int c, const int* cent
 static int insert_decide_impl(const InfgenRollout* r, int t, int force_enter, int max_new,
                               const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
                               const float* occ, int* active, int* n_new, int* inserted, int* new_row,
-                              float* new_shape, int* new_cell, int sample_k, const float* uniform, void* stream) {
+                              float* new_shape, int* new_cell, int sample_k, const float* uniform, void* stream,
+                              bool grid = true, float r_seed = 0.f) {
   RET_IF(validate(r, "infgen_insert_decide"));
   if (sample_k > 16) return fail("infgen_insert_decide", "sample_k must be <= 16");
   if (sample_k > 1 && !uniform) return fail("infgen_insert_decide", "cell sampling needs uniforms");
@@ -1603,7 +1609,9 @@ static int insert_decide_impl(const InfgenRollout* r, int t, int force_enter, in
   a.lg_pos = lg_pos; a.occ = occ; a.n_agents = const_cast<int*>(r->n_agents); a.type = const_cast<int*>(r->type);
   a.active = active; a.n_new = n_new; a.inserted = inserted; a.new_row = new_row; a.new_shape = new_shape;
   a.new_cell = new_cell; a.pred_traj = r->pred_traj; a.pred_head = r->pred_head; a.pred_state = r->pred_state;
-  hipLaunchKernelGGL(k_insert_decide, dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
+  a.r_seed = r_seed;
+  if (grid) hipLaunchKernelGGL(k_insert_decide<true>, dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_insert_decide<false>, dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
   return check_launch("infgen_insert_decide");
 }
 
@@ -1626,13 +1634,23 @@ extern "C" int infgen_insert_decide_topk(const InfgenRollout* r, int t, int forc
                             new_shape, new_cell, sample_k, uniform, stream);
 }
 
+static int insert_finalize_impl(const InfgenRollout* r, int c, float angle_interval, const int* inserted, const int* new_row,
+                                const float* lg_heading, int n_heading, const float* offset, float* hv_ovr, void* stream,
+                                bool head_token = true, bool xy_offset = true) {
+  RET_IF(validate(r, "infgen_insert_finalize"));
+  InsertFinalizeArgs a{scene_of(r), c, angle_interval, inserted, new_row, lg_heading, n_heading, offset, hv_ovr};
+  const hipStream_t hs = (hipStream_t)stream;
+  if (head_token && xy_offset) hipLaunchKernelGGL((k_insert_finalize<true, true>), dim3(r->S), dim3(64), 0, hs, a);
+  else if (xy_offset) hipLaunchKernelGGL((k_insert_finalize<false, true>), dim3(r->S), dim3(64), 0, hs, a);
+  else if (head_token) hipLaunchKernelGGL((k_insert_finalize<true, false>), dim3(r->S), dim3(64), 0, hs, a);
+  else hipLaunchKernelGGL((k_insert_finalize<false, false>), dim3(r->S), dim3(64), 0, hs, a);
+  return check_launch("infgen_insert_finalize");
+}
+
 extern "C" int infgen_insert_finalize(const InfgenRollout* r, int c, float angle_interval, const int* inserted,
                                       const int* new_row, const float* lg_heading, int n_heading, const float* offset,
                                       float* hv_ovr, void* stream) {
-  RET_IF(validate(r, "infgen_insert_finalize"));
-  InsertFinalizeArgs a{scene_of(r), c, angle_interval, inserted, new_row, lg_heading, n_heading, offset, hv_ovr};
-  hipLaunchKernelGGL(k_insert_finalize, dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
-  return check_launch("infgen_insert_finalize");
+  return insert_finalize_impl(r, c, angle_interval, inserted, new_row, lg_heading, n_heading, offset, hv_ovr, stream);
 }
 
 // ---------------------------------------------------------------------------------- teacher-forced forward
@@ -1688,11 +1706,16 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
                                   void* stream) {
   RET_IF(validate(r, "infgen_insert_seed"));
   if (!I) return fail("infgen_insert_seed", "null insertion block");
+  if (I->no_grid_token != r->no_grid_token) return fail("infgen_insert_seed", "no_grid_token differs between the context and the block");
+  if (I->no_grid_token && !I->head_pos_xy) return fail("infgen_insert_seed", "no_grid_token needs head_pos_xy");
   OptScope _opts(r);
   hipStream_t hs = (hipStream_t)stream;
   const int S = r->S, rows = r->S * r->A_cap, c = 1 + t, G = r->grid_size;
-  RET_IF(occupancy_embed_impl(r, c, I->occ, I->occ_embed, I->occ_emb, I->active, stream));
-  for (int i = 0; i < 3; ++i) RET_IF(infgen_attn_pre(I->occ_emb, S, I->attn_occ2sa[i], 1, nullptr, nullptr, I->Kocc[i], I->Vocc[i], stream));
+  const bool grid = !I->no_grid_token;      // use_grid_token = False: no occupancy, no occ2sa sublayers (agent_decoder.py:1851-1868)
+  if (grid) {
+    RET_IF(occupancy_embed_impl(r, c, I->occ, I->occ_embed, I->occ_emb, I->active, stream));
+    for (int i = 0; i < 3; ++i) RET_IF(infgen_attn_pre(I->occ_emb, S, I->attn_occ2sa[i], 1, nullptr, nullptr, I->Kocc[i], I->Vocc[i], stream));
+  }
   // edges into the seed node (the ego's pose): agents every iteration, map tokens once per step
   RET_IF(infgen_point_edges(r, c, r->av_index, I->active, 0, it == 0 ? 3 : 1, I->r_seed, 300, I->r_seed, 2048, &I->ea_s, &I->em_s, stream));
   RET_IF(infgen_fourier_embed(I->ea_s.raw, 3, I->ea_s.total, I->ea_s.cap, I->four_a2sa, nullptr, 0, I->ea_s.rhat, 128, 1, stream));
@@ -1702,7 +1725,7 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
     if (hipMemcpyAsync(I->Xc, r->X, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice, hs) != hipSuccess)
       return fail("infgen_insert_seed", "copy failed");
     for (int i = 0; i < 3; ++i) {
-      RET_IF(edgeless(I->Xc, rows, I->attn_occ2sa[i], I, stream));
+      if (grid) RET_IF(edgeless(I->Xc, rows, I->attn_occ2sa[i], I, stream));
       // the post part of the map sublayer and the K / V projections of the agent sublayer in one launch
       RET_IF(infgen_attn_post_pre(I->Xc, rows, I->attn_pt2sa[i], I->zero_agg, I->zero_z, I->zero_sig, 0, I->attn_a2sa[i], nullptr, nullptr,
                                   I->Ksa[i], I->Vsa[i], stream));
@@ -1713,12 +1736,15 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
   const int R = riders ? 2 * S : S;
   RET_IF(gather_rows(I->f_seed, nullptr, nullptr, S, 1, I->XS, stream));
   if (riders) RET_IF(gather_rows(r->X, I->prev_row, I->prev_mask, S, rows, I->XS + (size_t)S * D, stream));
-  RET_IF(infgen_attn_pre(I->XS, R, I->attn_occ2sa[0], 0, I->QS, nullptr, nullptr, nullptr, stream));
+  if (grid) RET_IF(infgen_attn_pre(I->XS, R, I->attn_occ2sa[0], 0, I->QS, nullptr, nullptr, nullptr, stream));
+  else RET_IF(infgen_attn_pre(I->XS, R, I->attn_pt2sa[0], 0, I->QS, I->US, nullptr, nullptr, stream));
   for (int i = 0; i < 3; ++i) {
-    RET_IF(infgen_edge_attn(S, I->QS, nullptr, I->Kocc[i], I->Vocc[i], I->occ_off, I->occ_cnt, I->occ_src, nullptr, I->AGGS, nullptr,
-                            I->SIGS, stream));
-    RET_IF(infgen_attn_post_pre(I->XS, R, I->attn_occ2sa[i], I->AGGS, I->ZS, I->SIGS, 0, I->attn_pt2sa[i], I->QS, I->US, nullptr, nullptr,
-                                stream));
+    if (grid) {
+      RET_IF(infgen_edge_attn(S, I->QS, nullptr, I->Kocc[i], I->Vocc[i], I->occ_off, I->occ_cnt, I->occ_src, nullptr, I->AGGS, nullptr,
+                              I->SIGS, stream));
+      RET_IF(infgen_attn_post_pre(I->XS, R, I->attn_occ2sa[i], I->AGGS, I->ZS, I->SIGS, 0, I->attn_pt2sa[i], I->QS, I->US, nullptr, nullptr,
+                                  stream));
+    }
     // (the map edges of a step are built once: scenes that stopped inserting are masked out instead, their seed rows are not read)
     RET_IF(edge_attn_impl(S, I->QS, I->US, I->mapK[i], I->mapV[i], I->em_s.off, I->em_s.cnt, I->em_s.src, I->em_s.rhat, I->AGGS,
                           I->ZS, I->SIGS, 1, stream, I->active));
@@ -1729,21 +1755,29 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
     }
     RET_IF(infgen_edge_attn_mode(S, I->QS, I->US, I->Ksa[i], I->Vsa[i], I->ea_s.off, I->ea_s.cnt, I->ea_s.src, I->ea_s.rhat, I->AGGS,
                                  I->ZS, I->SIGS, 1, stream));
-    if (i < 2) RET_IF(infgen_attn_post_pre(I->XS, R, I->attn_a2sa[i], I->AGGS, I->ZS, I->SIGS, 1, I->attn_occ2sa[i + 1], I->QS, nullptr,
-                                           nullptr, nullptr, stream));
+    // a2sa[i] feeds occ2sa[i + 1] (full model) or pt2sa[i + 1] (use_grid_token = False)
+    if (i < 2 && grid) RET_IF(infgen_attn_post_pre(I->XS, R, I->attn_a2sa[i], I->AGGS, I->ZS, I->SIGS, 1, I->attn_occ2sa[i + 1], I->QS,
+                                                   nullptr, nullptr, nullptr, stream));
+    else if (i < 2) RET_IF(infgen_attn_post_pre(I->XS, R, I->attn_a2sa[i], I->AGGS, I->ZS, I->SIGS, 1, I->attn_pt2sa[i + 1], I->QS, I->US,
+                                                nullptr, nullptr, stream));
     else RET_IF(infgen_attn_post(I->XS, R, I->attn_a2sa[i], I->AGGS, I->ZS, I->SIGS, 1, stream));
   }
-  // the four seed heads in two launches
+  // the four seed heads in two launches (the position head: the cell logits, or the xy regression for use_grid_token = False)
   InfgenLinearDesc d1[4], d2[4];
   const size_t hs_ = (size_t)S * 128;
   mlp_layer_descs(I->XS, S, I->head_state, 2, I->hid, I->lg_state, d1[0], d2[0]);
   mlp_layer_descs(I->XS, S, I->head_type, 3, I->hid + hs_, I->lg_type, d1[1], d2[1]);
   mlp_layer_descs(I->XS, S, I->head_shape, 3, I->hid + 2 * hs_, I->shape, d1[2], d2[2]);
-  mlp_layer_descs(I->XS, S, I->head_pos, G, I->hid + 3 * hs_, I->lg_pos, d1[3], d2[3]);
+  if (grid) mlp_layer_descs(I->XS, S, I->head_pos, G, I->hid + 3 * hs_, I->lg_pos, d1[3], d2[3]);
+  else mlp_layer_descs(I->XS, S, I->head_pos_xy, 2, I->hid + 3 * hs_, I->lg_pos, d1[3], d2[3]);
   RET_IF(infgen_linear_multi(d1, 4, stream));
   RET_IF(infgen_linear_multi(d2, 4, stream));
-  RET_IF(infgen_insert_decide_topk(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, I->occ, I->active,
-                                   I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, I->insert_k, uniform, stream));
+  if (grid)
+    RET_IF(infgen_insert_decide_topk(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, I->occ, I->active,
+                                     I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, I->insert_k, uniform, stream));
+  else
+    RET_IF(insert_decide_impl(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, nullptr, I->active,
+                              I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, 1, nullptr, stream, false, I->r_seed));
   // hand-over to the host: did any scene insert, into which rows, which scenes go on?
   // (one copy when the caller laid the three arrays out back to back, as infgen_amd/engine.py does)
   if (I->new_row == I->inserted + S && I->active == I->inserted + 2 * S) {
@@ -1759,6 +1793,7 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
 extern "C" int infgen_insert_heading(const InfgenRollout* r, const InfgenInsertion* I, int t, int h_ready, int riders, void* stream) {
   RET_IF(validate(r, "infgen_insert_heading"));
   if (!I) return fail("infgen_insert_heading", "null insertion block");
+  if (I->no_head_token && !I->head_heading_theta) return fail("infgen_insert_heading", "no_head_token needs head_heading_theta");
   OptScope _opts(r);
   hipStream_t hs = (hipStream_t)stream;
   const int S = r->S, rows = r->S * r->A_cap, c = 1 + t;
@@ -1809,13 +1844,17 @@ extern "C" int infgen_insert_heading(const InfgenRollout* r, const InfgenInserti
                                            nullptr, stream));
     else RET_IF(infgen_attn_post(I->XS, R, r->attn_a[i], I->AGGS, I->ZS, I->SIGS, 1, stream));
   }
+  // heading head (token logits, or the theta regression for use_head_token = False) and, with the grid, the xy-offset head
   InfgenLinearDesc d1[2], d2[2];
   const size_t hs_ = (size_t)S * 128;
-  mlp_layer_descs(I->XS, S, I->head_heading, I->n_heading, I->hid + 4 * hs_, I->lg_heading, d1[0], d2[0]);
-  mlp_layer_descs(I->XS, S, I->head_offset, 2, I->hid + 5 * hs_, I->offset, d1[1], d2[1]);
-  RET_IF(infgen_linear_multi(d1, 2, stream));
-  RET_IF(infgen_linear_multi(d2, 2, stream));
-  RET_IF(infgen_insert_finalize(r, c, I->angle_interval, I->inserted, I->new_row, I->lg_heading, I->n_heading, I->offset, I->hv_ovr, stream));
+  const bool head_tok = !I->no_head_token, offset = !I->no_grid_token;
+  if (head_tok) mlp_layer_descs(I->XS, S, I->head_heading, I->n_heading, I->hid + 4 * hs_, I->lg_heading, d1[0], d2[0]);
+  else mlp_layer_descs(I->XS, S, I->head_heading_theta, 1, I->hid + 4 * hs_, I->lg_heading, d1[0], d2[0]);
+  if (offset) mlp_layer_descs(I->XS, S, I->head_offset, 2, I->hid + 5 * hs_, I->offset, d1[1], d2[1]);
+  RET_IF(infgen_linear_multi(d1, offset ? 2 : 1, stream));
+  RET_IF(infgen_linear_multi(d2, offset ? 2 : 1, stream));
+  RET_IF(insert_finalize_impl(r, c, I->angle_interval, I->inserted, I->new_row, I->lg_heading, head_tok ? I->n_heading : 1, I->offset,
+                              I->hv_ovr, stream, head_tok, offset));
   RET_IF(infgen_raw_feature_rows(r, c, I->new_row, I->inserted, S, stream));
   // the rows of this iteration ride along in the next seed chain / heading stage
   hipLaunchKernelGGL(k_note_riders, dim3(ceil_div(S, NT)), dim3(NT), 0, hs, I->new_row, I->inserted, S, I->prev_row, I->prev_mask,

@@ -569,6 +569,7 @@ __global__ __launch_bounds__(BT) void k_integrate(IntegrateArgs a) {
     int ns = a.next_state[row];
     if (ns == 2) ns = EXIT;                     // valid_state_type index 2 == 'exit'
     if (t == av) ns = VALID;                    // ego forced valid
+    if (a.no_state && ns == EXIT) ns = VALID;   // use_state_token = False (agent_decoder.py:2170-2171)
     if (a.force_valid) ns = VALID;              // disable_insertion
     if (a.teacher_token) { tok = a.teacher_token[sidx(st, s, n, t)]; if (tok < 0) tok = 0; }
     if (a.teacher_state) ns = a.teacher_state[sidx(st, s, n, t)];
@@ -702,13 +703,14 @@ __device__ __forceinline__ void rawfeat_prep_item(const RawFeatArgs& a, int row,
   if (tok < 0) tok += a.token_size + 2;             // python negative indexing: -1 no_token, -2 bos
   const int ty = st.type[row];
   const float* tsrc = a.tok_tab + ((size_t)ty * (a.token_size + 2) + tok) * D;
-  int g = st.grid[i];
-  if (g < 0) g += a.grid_size + 1;                  // -1 -> invalid row
-  const float* gsrc = a.grid_tab + (size_t)g * D;
   const float* ssrc = a.state_emb + (size_t)stj * D;
   float* f = a.fus_in + (size_t)slot * 512;
   *reinterpret_cast<float4*>(f + 4 * c4) = *reinterpret_cast<const float4*>(tsrc + 4 * c4);
   *reinterpret_cast<float4*>(f + 256 + 4 * c4) = *reinterpret_cast<const float4*>(ssrc + 4 * c4);
+  if (a.no_grid) return;                            // use_grid_token = False: the fusion reads columns 0..383 only
+  int g = st.grid[i];
+  if (g < 0) g += a.grid_size + 1;                  // -1 -> invalid row
+  const float* gsrc = a.grid_tab + (size_t)g * D;
   *reinterpret_cast<float4*>(f + 384 + 4 * c4) = *reinterpret_cast<const float4*>(gsrc + 4 * c4);
 }
 
@@ -967,17 +969,21 @@ __global__ __launch_bounds__(NT) void k_occupancy_embed(OccEmbedArgs a) {
 
 // k_insert_decide: heads of the seed node -> enter? / type / shape / grid cell; occupied-cell
 // rejection; append the new row (:1883-1999).  One wave per scene.
+// kGrid = false (use_grid_token = False, :1910-1912): no cell and no occupancy test; the new row sits at
+// tanh(lg_pos[s][0..1]) * r_seed + ego pos in the world frame (not rotated by the ego heading) with grid cell -1.
+template <bool kGrid>
 __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   const SceneState& st = a.st;
   const int s = blockIdx.x, lane = threadIdx.x;
   const int c = a.c;
   if (!a.active[s]) { if (lane == 0) a.inserted[s] = 0; return; }
+  int bi = 0x7fffffff;
+  if (kGrid) {
   // the position head's cell: arg-max (softmax is monotone; first index on ties) or, with sample_k > 1, the reference's
   // softmax -> topk(insert_beam_size) -> multinomial (:1900-1904) in its reproducible form: the k largest in (value desc,
   // index asc) order, inverse CDF over their probabilities with the caller's uniform (like k_sample_topk)
   const float* lp = a.lg_pos + (size_t)s * a.grid_size;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
   {
     const int k = a.sample_k > 1 ? min(a.sample_k, 16) : 1;
     float topv[16];
@@ -1012,8 +1018,9 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
       bi = topi[0];
     }
   }
+  }
   if (lane != 0) return;
-  const int cell = bi;
+  const int cell = kGrid ? bi : -1;
   const float* ls = a.lg_state + 2 * s;
   bool enter = ls[1] > ls[0];
   if (a.force_enter) enter = true;
@@ -1021,7 +1028,7 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   int ty = 0;
   if (lt[1] > lt[ty]) ty = 1;
   if (lt[2] > lt[ty]) ty = 2;
-  const bool occupied = a.occ[(size_t)s * a.grid_size + cell] != 0.f;
+  const bool occupied = kGrid && a.occ[(size_t)s * a.grid_size + cell] != 0.f;
   const int A = a.n_agents[s];
   // :1906-1909: an occupied cell `continue`s - the iteration is spent, nothing is appended and, when cells are sampled, the
   // next iteration draws again (greedy: it would pick the same cell until the iterations run out, so the scene stops)
@@ -1033,12 +1040,18 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   const int av = st.av_index[s];
   const size_t ie = sidx(st, s, c, av);
   const float ex = st.pos[2 * ie], ey = st.pos[2 * ie + 1], eh = st.head[ie];
-  // decode_pos (attr_tokenizer.py:91-99): grid[cell] @ Rot(theta_ego - pi/2) + ego pos
-  const float phi = eh - HALF_PI_F;
-  const float cs = cosf(phi), sn = sinf(phi);
-  const float gx = a.grid_xy[2 * cell], gy = a.grid_xy[2 * cell + 1];
-  const float nx = (gx * cs + gy * (-sn)) + ex;
-  const float ny = (gx * sn + gy * cs) + ey;
+  float nx, ny;
+  if (kGrid) {
+    // decode_pos (attr_tokenizer.py:91-99): grid[cell] @ Rot(theta_ego - pi/2) + ego pos
+    const float phi = eh - HALF_PI_F;
+    const float cs = cosf(phi), sn = sinf(phi);
+    const float gx = a.grid_xy[2 * cell], gy = a.grid_xy[2 * cell + 1];
+    nx = (gx * cs + gy * (-sn)) + ex;
+    ny = (gx * sn + gy * cs) + ey;
+  } else {
+    nx = tanhf(a.lg_pos[2 * s]) * a.r_seed + ex;
+    ny = tanhf(a.lg_pos[2 * s + 1]) * a.r_seed + ey;
+  }
   const int row = s * st.A_cap + A;
   for (int j = 0; j < st.T; ++j) {
     const size_t i = sidx(st, s, j, A);
@@ -1065,8 +1078,13 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   a.new_row[s] = row;
   a.inserted[s] = 1;
 }
+template __global__ void k_insert_decide<true>(InsertDecideArgs);
+template __global__ void k_insert_decide<false>(InsertDecideArgs);
 
-// k_insert_finalize: heading token + xy offset of the new row (:2060-2074), head-vector override
+// k_insert_finalize: heading token + xy offset of the new row (:2060-2074), head-vector override.
+// kHeadToken = false (use_head_token = False): heading tanh(lg_heading[s][0]) * pi + ego heading, not wrapped;
+// kOffset = false (use_grid_token = False): the position stays the regressed one
+template <bool kHeadToken, bool kOffset>
 __global__ __launch_bounds__(64) void k_insert_finalize(InsertFinalizeArgs a) {
   const SceneState& st = a.st;
   const int s = blockIdx.x;
@@ -1074,20 +1092,31 @@ __global__ __launch_bounds__(64) void k_insert_finalize(InsertFinalizeArgs a) {
   const int row = a.new_row[s];
   const int ag = row - s * st.A_cap;
   const float* lh = a.lg_heading + (size_t)s * a.n_heading;
-  int bi = 0;
-  for (int k = 1; k < a.n_heading; ++k) if (lh[k] > lh[bi]) bi = k;
   const size_t ie = sidx(st, s, a.c, st.av_index[s]);
   const float eh = st.head[ie];
-  // decode_heading (attr_tokenizer.py:106-110): (idx * interval - 180) / 360 * 2 pi
-  const float dec = ((float)bi * a.angle_interval - 180.0f) / 360.0f * TWO_PI_F;
-  const float nh = wrap_angle(dec + eh);
+  float nh;
+  if (kHeadToken) {
+    int bi = 0;
+    for (int k = 1; k < a.n_heading; ++k) if (lh[k] > lh[bi]) bi = k;
+    // decode_heading (attr_tokenizer.py:106-110): (idx * interval - 180) / 360 * 2 pi
+    const float dec = ((float)bi * a.angle_interval - 180.0f) / 360.0f * TWO_PI_F;
+    nh = wrap_angle(dec + eh);
+  } else {
+    nh = tanhf(lh[0]) * PI_F + eh;
+  }
   const size_t in_ = sidx(st, s, a.c, ag);
   st.head[in_] = nh;
-  st.pos[2 * in_] += tanhf(a.offset[2 * s]) * 2.0f;
-  st.pos[2 * in_ + 1] += tanhf(a.offset[2 * s + 1]) * 2.0f;
+  if (kOffset) {
+    st.pos[2 * in_] += tanhf(a.offset[2 * s]) * 2.0f;
+    st.pos[2 * in_ + 1] += tanhf(a.offset[2 * s + 1]) * 2.0f;
+  }
   a.hv_ovr[2 * s] = cosf(nh);
   a.hv_ovr[2 * s + 1] = sinf(nh);
 }
+template __global__ void k_insert_finalize<true, true>(InsertFinalizeArgs);
+template __global__ void k_insert_finalize<false, true>(InsertFinalizeArgs);
+template __global__ void k_insert_finalize<true, false>(InsertFinalizeArgs);
+template __global__ void k_insert_finalize<false, false>(InsertFinalizeArgs);
 
 
 // ------------------------------------------------------------------------------------------

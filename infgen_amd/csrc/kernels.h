@@ -356,6 +356,7 @@ struct RawFeatArgs {
   float* cat;                       // [rows][128]
   float* fus_in;                    // [rows][512]
   const int* row_list; const int* row_mask; int n_list;   // optional: only these rows (row_mask[k] != 0), outputs compact at k
+  int no_grid;                      // use_grid_token = False: fus_in columns 384..511 are not written (the fusion runs at K0 = 384)
 };
 
 struct IntegrateArgs {
@@ -364,6 +365,7 @@ struct IntegrateArgs {
   int t;                            // decode step
   int R;                            // num_recurrent_steps_val
   int force_valid;                  // disable_insertion: every state := valid
+  int no_state;                     // use_state_token = False: 'exit' := valid after the ego override
   const int* next_token; const int* next_state;   // [rows] from the heads
   const int* teacher_token; const int* teacher_state;   // optional [S][T][A_cap]
   const int* teacher_grid;                               // optional [S][T][A_cap], < -1: none
@@ -416,7 +418,8 @@ struct InsertDecideArgs {
   const float* lg_state;            // [S][2]
   const float* lg_type;             // [S][3]
   const float* shape;               // [S][3]
-  const float* lg_pos;              // [S][grid_size]
+  const float* lg_pos;              // [S][grid_size]; k_insert_decide<false>: [S][2], seed_pos_rel_xy_predict_head (pre-tanh)
+  float r_seed;                     // pl2seed_radius (k_insert_decide<false>)
   const float* occ;                 // [S][grid_size]
   int* n_agents;                    // [S] (mutable view of st.n_agents)
   int* type;                        // [S][A_cap]
@@ -515,8 +518,10 @@ __global__ void k_map_graph(MapGraphArgs a);
 __global__ void k_point_edges(PointEdgesArgs a);
 __global__ void k_occupancy(OccupancyArgs a);
 __global__ void k_occupancy_embed(OccEmbedArgs a);
-__global__ void k_insert_decide(InsertDecideArgs a);
-__global__ void k_insert_finalize(InsertFinalizeArgs a);
+// kGrid = false: use_grid_token = False (regressed world-frame position, no cell, no occupancy test)
+template <bool kGrid> __global__ void k_insert_decide(InsertDecideArgs a);
+// kHeadToken = false: use_head_token = False (tanh * pi heading, unwrapped); kOffset = false: no xy offset (use_grid_token = False)
+template <bool kHeadToken, bool kOffset> __global__ void k_insert_finalize(InsertFinalizeArgs a);
 __global__ void k_sample_topk(SampleArgs a);
 __global__ void k_layernorm(const float* X, int rows, const float* g, const float* b, float* Y);
 __global__ void k_radius_edges(RadiusEdgesArgs a);            // forward_kernels.hip

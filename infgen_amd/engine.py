@@ -192,6 +192,11 @@ class PackedWeights:
         self.four_a = dev(packing.pack_fourier(sd, f'{ap}.r_a2a_emb', 3))
         self.four_xa = dev(packing.pack_fourier(sd, f'{ap}.x_a_emb', 2))
         self.four_pt = dev(packing.pack_fourier(sd, f'{mp}.r_pt2pt_emb', 3))
+        # fusion_emb: [token | x_a | state | grid] -> 128, K0 = 384 without the grid embedding (use_grid_token = False)
+        self.fusion_k0 = D * (4 if cfg.use_grid_token else 3)
+        k0 = packing._get(sd, f'{ap}.fusion_emb.mlp.0.weight').shape[1]
+        if k0 != self.fusion_k0:
+            raise ValueError(f'fusion_emb takes {k0} inputs, use_grid_token = {cfg.use_grid_token} needs {self.fusion_k0}')
         self.fusion = dev(packing.pack_mlp_embedding(sd, f'{ap}.fusion_emb'))
         self.shape_emb = dev(packing.pack_mlp_embedding(sd, f'{ap}.shape_emb'))
         self.tok_emb = [dev(packing.pack_mlp_embedding(sd, f'{ap}.token_emb_{k}')) for k in ('veh', 'ped', 'cyc')]
@@ -215,10 +220,14 @@ class PackedWeights:
                             for i in range(3)]
         self.four_pt2sa = dev(packing.pack_fourier(sd, f'{ap}.r_pt2sa_emb', 3))
         self.four_a2sa = dev(packing.pack_fourier(sd, f'{ap}.r_a2sa_emb', 3))
-        self.heads = {k: dev(packing.pack_mlp_layer(sd, f'{ap}.{k}')) for k in
-                      ('seed_state_predict_head', 'seed_type_predict_head', 'seed_shape_predict_head',
-                       'seed_pos_rel_token_predict_head', 'seed_heading_rel_token_predict_head',
-                       'seed_offset_xy_predict_head', 'seed_agent_occ_embed')}
+        # the heads of the variant's state_dict: use_grid_token = False replaces the cell / offset heads and the occupancy embedding
+        # by seed_pos_rel_xy_predict_head, use_head_token = False the heading-token head by seed_heading_rel_theta_predict_head
+        # (agent_decoder.py:267-283)
+        heads = ['seed_state_predict_head', 'seed_type_predict_head', 'seed_shape_predict_head']
+        heads += (['seed_pos_rel_token_predict_head', 'seed_offset_xy_predict_head', 'seed_agent_occ_embed'] if cfg.use_grid_token
+                  else ['seed_pos_rel_xy_predict_head'])
+        heads += ['seed_heading_rel_token_predict_head' if cfg.use_head_token else 'seed_heading_rel_theta_predict_head']
+        self.heads = {k: dev(packing.pack_mlp_layer(sd, f'{ap}.{k}')) for k in heads}
         self._tables = None
         self._tables_key = None
         self._tables_by_key = {}
@@ -267,12 +276,13 @@ class PackedWeights:
         map_tab = ops.mlp_embedding(map_vocab_dev, self.map_tok_emb, map_vocab_dev.shape[1])
         # the all-invalid seed query row (agent_decoder.py:1814-1818): a constant of the weights
         raw = torch.tensor([[2.0 * 2.0 ** 0.5, -2.356194490192345, 0.0, 0.0]], device=dev)   # |(-2,-2)|, atan2(-2,-2)
-        fus = torch.zeros(1, 4 * D, device=dev)
+        fus = torch.zeros(1, self.fusion_k0, device=dev)
         fus[0, :D] = self.no_token[0]
         fus[0, 2 * D:3 * D] = self.state_a_emb[0]
-        fus[0, 3 * D:] = grid_tab[G // 2]
+        if self.cfg.use_grid_token:
+            fus[0, 3 * D:] = grid_tab[G // 2]
         ops.fourier(raw, 2, self.four_xa, fus[:, D:2 * D], cat=cat_seed[None].contiguous())
-        f_seed = ops.mlp_embedding(fus, self.fusion, 4 * D)
+        f_seed = ops.mlp_embedding(fus, self.fusion, self.fusion_k0)
         self._tables = dict(tok_tab=tok_tab, grid_tab=grid_tab, cat_seed=cat_seed, map_tab=map_tab, f_seed=f_seed)
         self._tables_key = key
         self._tables_by_key[key] = self._tables
@@ -569,7 +579,8 @@ class RolloutEngine:
         self._sample_uniforms = sample_uniforms      # [steps][S][A] float32 in [0,1) (top-k inverse-CDF sampling)
         # scenario insertion: the cell of a new agent from the insert_k most probable ones (reference insert_beam_size = 10,
         # agent_decoder.py:1900-1904) with insert_uniforms [steps][10][S]; 1: arg-max
-        self.insert_k = int(insert_k)
+        # (use_grid_token = False: no cell is drawn - the position is regressed - and insert_k is accepted and ignored, as in the reference)
+        self.insert_k = int(insert_k) if cfg.use_grid_token else 1
         self._insert_u = None
         # record the seed node's per-insertion outputs of the reference's return dict (agent_decoder.py:2099-2113, :2364-2386:
         # next_state_prob_seed, next_pos_rel_prob_seed, grid_*_occ_seed - plot inputs of the reference; two more heads per iteration)
@@ -611,7 +622,11 @@ class RolloutEngine:
         self._amax0 = amax
         head = 0
         if self.insertion:
-            head = insert_headroom if insert_headroom is not None else min(10 * cfg.num_decode_steps, 96)
+            # rows kept free for inserted agents.  The full model's grid rejects occupied cells, so 96 rows have been plenty; without the
+            # grid nothing is rejected and forced / eager seed heads append the maximum 10 rows at every step: room for all of them
+            # (up to the layout's row limit - a scene that still runs out raises InsertionHeadroomError, nothing is dropped)
+            default = min(10 * cfg.num_decode_steps, 96) if cfg.use_grid_token else 10 * cfg.num_decode_steps
+            head = insert_headroom if insert_headroom is not None else default
         self.A_cap = A_cap = a_cap or min(_round_up(max(amax + head, 1), 32), self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
         self.M_cap = M_cap = m_cap or _round_up(max(mmax, 1), 32)
         assert amax <= A_cap <= self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS) and A_cap % 32 == 0
@@ -631,7 +646,10 @@ class RolloutEngine:
         vocab_np = np.stack([vocab[k] for k in ('veh', 'ped', 'cyc')]).astype(np.float32)
         map_vocab_np = np.asarray(map_vocab, dtype=np.float32).reshape(map_vocab.shape[0], -1)
         grid_np = np.asarray(grid, dtype=np.float32)
-        self._tables_key = PackedWeights.tables_key(vocab_np, grid_np, map_vocab_np)
+        # (the token ablations select the fusion input of the fused seed row: part of the tables' content)
+        flags = (cfg.use_grid_token, cfg.use_head_token, cfg.use_state_token)
+        extra = () if all(flags) else (np.asarray(flags, np.int8),)
+        self._tables_key = PackedWeights.tables_key(vocab_np, grid_np, map_vocab_np, *extra)
         self.vocab, self._map_vocab, self.grid_xy = t(vocab_np), t(map_vocab_np), t(grid_np)
         self.G = int(grid.shape[0])
         self.teacher_token = self.teacher_state = None
@@ -1415,7 +1433,10 @@ class RolloutEngine:
         # inserted | new_row | active back to back: one device-to-host copy per iteration hands all three over
         d3 = self.ins['dec3']
         self.ins['inserted'], self.ins['new_row'], self.ins['active'] = d3[:S], d3[S:2 * S], d3[2 * S:]
-        if self.seed_outputs:
+        if self.seed_outputs and not self.cfg.use_grid_token:
+            # use_grid_token = False: next_pos_rel_prob_seed and grid_*_occ_seed are None in the reference (agent_decoder.py:2376-2386)
+            self.seed_out = dict(state=f(S, 11, self.cfg.num_decode_steps))
+        elif self.seed_outputs:
             steps = self.cfg.num_decode_steps
             self.seed_out = dict(state=f(S, 11, steps), pos=f(S, 11, steps, G), occ_a=f(S, 11, steps, G), occ_p=f(S, 11, steps, G),
                                  occ_gt=f(S, 11, steps, G))
@@ -1439,10 +1460,13 @@ class RolloutEngine:
             b.Kocc[i], b.Vocc[i], b.mapK[i], b.mapV[i] = P(I['Kocc'][i]), P(I['Vocc'][i]), P(I['mapK'][i]), P(I['mapV'][i])
             b.Ksa[i], b.Vsa[i], b.Kh[i], b.Vh[i] = P(I['Ksa'][i]), P(I['Vsa'][i]), P(I['Kh'][i]), P(I['Vh'][i])
         H = w.heads
+        Pn = lambda k: P(H[k]) if k in H else None         # (the heads of the other variants: NULL)
         b.four_a2sa, b.four_pt2sa = P(w.four_a2sa), P(w.four_pt2sa)
         b.head_state, b.head_type, b.head_shape = P(H['seed_state_predict_head']), P(H['seed_type_predict_head']), P(H['seed_shape_predict_head'])
-        b.head_pos, b.head_heading = P(H['seed_pos_rel_token_predict_head']), P(H['seed_heading_rel_token_predict_head'])
-        b.head_offset, b.occ_embed = P(H['seed_offset_xy_predict_head']), P(H['seed_agent_occ_embed'])
+        b.head_pos, b.head_heading = Pn('seed_pos_rel_token_predict_head'), Pn('seed_heading_rel_token_predict_head')
+        b.head_offset, b.occ_embed = Pn('seed_offset_xy_predict_head'), Pn('seed_agent_occ_embed')
+        b.head_pos_xy, b.head_heading_theta = Pn('seed_pos_rel_xy_predict_head'), Pn('seed_heading_rel_theta_predict_head')
+        b.no_grid_token, b.no_head_token = int(not cfg.use_grid_token), int(not cfg.use_head_token)
         b.shape_emb, b.type_a_emb, b.f_seed = P(w.shape_emb), P(w.type_a_emb), P(self.f_seed)
         b.occ, b.occ_emb, b.Xc = P(I['occ']), P(I['occ_emb']), P(I['Xc'])
         b.zero_agg, b.zero_z, b.zero_sig = P(I['AGG0']), P(I['Z0']), P(I['SIG0'])
@@ -1507,10 +1531,11 @@ class RolloutEngine:
                 so, slot = self.seed_out, I['n_new'][ins].long()
                 XS_in = I['XS'][:S][ins].contiguous()
                 so['state'][ins, slot, t] = torch.softmax(I['lg_state'][ins], dim=-1)[:, -1]
-                so['pos'][ins, slot, t] = torch.softmax(I['lg_pos'][ins], dim=-1)
-                so['occ_a'][ins, slot, t] = ops.mlp_layer(XS_in, w.fwd_heads['grid_agent_occ_head'], D, self.G)
-                so['occ_p'][ins, slot, t] = ops.mlp_layer(XS_in, w.fwd_heads['grid_pt_occ_head'], D, self.G)
-                so['occ_gt'][ins, slot, t] = I['occ'][ins]
+                if 'pos' in so:                  # (the grid's outputs: not recorded for use_grid_token = False)
+                    so['pos'][ins, slot, t] = torch.softmax(I['lg_pos'][ins], dim=-1)
+                    so['occ_a'][ins, slot, t] = ops.mlp_layer(XS_in, w.fwd_heads['grid_agent_occ_head'], D, self.G)
+                    so['occ_p'][ins, slot, t] = ops.mlp_layer(XS_in, w.fwd_heads['grid_pt_occ_head'], D, self.G)
+                    so['occ_gt'][ins, slot, t] = I['occ'][ins]
             # heading stage of the rows just appended; the rows of the previous heading stage ride along (their K / V of the motion
             # layers 0..2 are refreshed) - not necessarily the previous iteration's: an occupied sampled cell spends iterations
             _lib.check(lib.infgen_insert_heading(ctx, blk, t, int(h_ready), int(riders_h and h_ready), self.ops.stream), 'infgen_insert_heading')
@@ -1523,6 +1548,7 @@ class RolloutEngine:
         c.S, c.A_cap, c.T, c.M_cap, c.W, c.ring, c.R = self.S, self.A_cap, self.T, self.M_cap, self.W, self.ring, self.R
         c.token_size, c.grid_size, c.num_layers = cfg.token_size, self.G, cfg.num_agent_layers
         c.force_valid, c.store_logits = int(self.force_valid), int(self.store_logits)
+        c.no_grid_token, c.no_state_token = int(not cfg.use_grid_token), int(not cfg.use_state_token)
         c.r_map, c.r_agent = float(cfg.pl2a_radius), float(cfg.a2a_radius)
         P = _lib.ptr
         c.n_agents, c.n_map, c.av_index = P(self.n_agents), P(self.n_map), P(self.av)
@@ -1748,9 +1774,8 @@ class RolloutEngine:
                 o['agent_labels'] = labels
             if self.seed_out is not None:
                 so = self.seed_out
-                o.update(next_state_prob_seed=so['state'][s].cpu().numpy(), next_pos_rel_prob_seed=so['pos'][s].cpu().numpy(),
-                         grid_agent_occ_seed=so['occ_a'][s].cpu().numpy(), grid_pt_occ_seed=so['occ_p'][s].cpu().numpy(),
-                         grid_agent_occ_gt_seed=so['occ_gt'][s].cpu().numpy())
+                for k_out, k_in in self._SEED_KEYS:
+                    o[k_out] = so[k_in][s].cpu().numpy() if k_in in so else None
             if logits is not None:
                 o['logits'] = logits[:, s * self.A_cap:s * self.A_cap + A].copy()
             if x_pt is not None:
@@ -1887,15 +1912,18 @@ class RolloutEngine:
                 o.set_lazy('agent_labels', labels)
             if seed_out is not None:
                 # (detach: the seed arrays are engine-owned and zeroed / rewritten by the next rollout of a reused engine - cloned NOW)
-                for k_out, k_in in (('next_state_prob_seed', 'state'), ('next_pos_rel_prob_seed', 'pos'), ('grid_agent_occ_seed', 'occ_a'),
-                                    ('grid_pt_occ_seed', 'occ_p'), ('grid_agent_occ_gt_seed', 'occ_gt')):
-                    o[k_out] = seed_out[k_in][s].clone() if detach else seed_out[k_in][s]
+                for k_out, k_in in self._SEED_KEYS:
+                    o[k_out] = None if k_in not in seed_out else seed_out[k_in][s].clone() if detach else seed_out[k_in][s]
             if lg_all is not None:
                 o.set_lazy('logits', (lambda s=s, A=A: lg_all[:, s * A_capl:s * A_capl + A]))
             if x_pt_all is not None:
                 o.set_lazy('x_pt', (lambda ms=s // self.copies, M=M: x_pt_all[ms * M_capl:ms * M_capl + M]))
             outs.append(o)
         return outs
+
+    # the seed node's outputs (reference return dict key, seed_out key); the grid's are None for use_grid_token = False
+    _SEED_KEYS = (('next_state_prob_seed', 'state'), ('next_pos_rel_prob_seed', 'pos'), ('grid_agent_occ_seed', 'occ_a'),
+                  ('grid_pt_occ_seed', 'occ_p'), ('grid_agent_occ_gt_seed', 'occ_gt'))
 
     _PACK_FIN = ('agent_id', 'pos_a', 'head_a', 'pred_traj', 'pred_head', 'pred_state', 'pred_valid', 'pred_type', 'pred_shape',
                  'eval_shape', 'next_token_idx', 'next_state_idx')
@@ -1948,10 +1976,9 @@ class RolloutEngine:
                 o['agent_labels'] = labels
             if self.seed_out is not None:
                 so = self.seed_out
-                for k_out, k_in in (('next_state_prob_seed', 'state'), ('next_pos_rel_prob_seed', 'pos'), ('grid_agent_occ_seed', 'occ_a'),
-                                    ('grid_pt_occ_seed', 'occ_p'), ('grid_agent_occ_gt_seed', 'occ_gt')):
-                    v = so[k_in][j::n]
-                    o[k_out] = v.reshape((-1,) + tuple(v.shape[2:])).clone()
+                for k_out, k_in in self._SEED_KEYS:
+                    v = so[k_in][j::n] if k_in in so else None
+                    o[k_out] = None if v is None else v.reshape((-1,) + tuple(v.shape[2:])).clone()
             outs.append(o)
         return outs
 

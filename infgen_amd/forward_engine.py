@@ -59,6 +59,8 @@ class ForwardEngine:
         if getattr(weights, 'operand_bits', 11) != 11:
             raise ValueError('the teacher-forced forward runs in fp32 arithmetic: it takes default packs (operand_bits=11), not the '
                              'bf16-operand packs of the rollout\'s reduced mode')
+        if not (self.cfg.use_grid_token and self.cfg.use_head_token and self.cfg.use_state_token):
+            raise ValueError('the teacher-forced forward implements the full-token model (use_grid/head/state_token = True)')
         self.ops = Ops(self.device)
         self.lib = self.ops.lib
         self.batch = batch

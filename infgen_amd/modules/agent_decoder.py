@@ -11,6 +11,10 @@ otherwise drawn from the top-k cells the same way (the reference's top-10 multin
 retry after an occupied cell).  The seed-loop outputs (``next_state_prob_seed``, ``next_pos_rel_prob_seed``, ``grid_*_occ_seed``,
 ``agent_labels``) are filled like the reference's by ``inference`` / ``inference_rollouts``; ``inference_batch`` returns zeros
 there unless called with ``seed_outputs=True``.
+
+The reference's token ablations (``use_grid_token`` / ``use_head_token`` / ``use_state_token`` = False, its
+configs/experiments/ablate_*_tokens.yaml) build the same submodules under the same names and shapes and roll out through the
+same library ("Token ablations"); the teacher-forced ``forward`` implements the full-token model only.
 """
 from __future__ import annotations
 
@@ -50,8 +54,6 @@ class InfGenAgentDecoder(nn.Module):
         self.num_recurrent_steps_val = num_recurrent_steps_val
         self.loss_weight, self.logger = loss_weight, logger
         self.attr_tokenizer = attr_tokenizer
-        if not (use_grid_token and use_head_token and use_state_token):
-            raise ValueError('the HIP path implements the full-token model (use_grid/head/state_token = True)')
         self.state_type = list(state_token.keys())
         self.state_token = state_token
         self.invalid_state, self.valid_state = int(state_token['invalid']), int(state_token['valid'])
@@ -76,7 +78,8 @@ class InfGenAgentDecoder(nn.Module):
         self.no_token_emb = nn.Embedding(1, hidden_dim)
         self.bos_token_emb = nn.Embedding(1, hidden_dim)
         self.invalid_offset_token_emb = nn.Embedding(1, hidden_dim)
-        self.fusion_emb = MLPEmbedding(input_dim=hidden_dim * 4, hidden_dim=hidden_dim)
+        # [token | x_a | state | grid], without the grid embedding when use_grid_token is False (reference :216-220)
+        self.fusion_emb = MLPEmbedding(input_dim=hidden_dim * (4 if use_grid_token else 3), hidden_dim=hidden_dim)
 
         def layers(n, bipartite, pos=True):
             return nn.ModuleList([AttentionLayer(hidden_dim=hidden_dim, num_heads=num_heads, head_dim=head_dim,
@@ -97,10 +100,17 @@ class InfGenAgentDecoder(nn.Module):
         self.seed_shape_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=3)
         self.grid_size = self.attr_tokenizer.grid_size
         self.angle_size = self.attr_tokenizer.angle_size
-        self.seed_pos_rel_token_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=self.grid_size)
-        self.seed_offset_xy_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=2)
-        self.seed_agent_occ_embed = MLPLayer(input_dim=self.grid_size, hidden_dim=hidden_dim, output_dim=hidden_dim)
-        self.seed_heading_rel_token_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=self.angle_size)
+        # the ablation models' heads (reference :267-282): a regressed world-frame position / an unwrapped regressed heading
+        if use_grid_token:
+            self.seed_pos_rel_token_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=self.grid_size)
+            self.seed_offset_xy_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=2)
+            self.seed_agent_occ_embed = MLPLayer(input_dim=self.grid_size, hidden_dim=hidden_dim, output_dim=hidden_dim)
+        else:
+            self.seed_pos_rel_xy_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=2)
+        if use_head_token:
+            self.seed_heading_rel_token_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=self.angle_size)
+        else:
+            self.seed_heading_rel_theta_predict_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=1)
         if self.predict_occ:
             self.grid_agent_occ_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=self.grid_size)
             self.grid_pt_occ_head = MLPLayer(input_dim=hidden_dim, hidden_dim=hidden_dim, output_dim=self.grid_size)

@@ -271,7 +271,8 @@ class InfGenDecoder(nn.Module):
                             pl2sa_radius=pl2sa_radius, pl2seed_radius=pl2seed_radius,
                             time_span=time_span if time_span is not None else num_historical_steps,
                             seed_size=seed_size, buffer_size=buffer_size, disable_insertion=disable_insertion,
-                            state_token=dict(state_token))
+                            state_token=dict(state_token), use_grid_token=bool(use_grid_token),
+                            use_head_token=bool(use_head_token), use_state_token=bool(use_state_token))
         # arithmetic of the rollout's GEMM kernels - the counterpart of the trainer's `precision` flag, which the reference's run.py
         # never passes (fp32): '32' (default) the fp32-accurate operand split; 'bf16' bf16 operands with fp32 accumulation (packs of
         # bf16 weights, InfgenOptions.gemm_terms = 2; BASELINE config C5); '16' fp16 operands (gemm_terms = 1).  Set it before a call.
@@ -349,7 +350,7 @@ class InfGenDecoder(nn.Module):
             sample_uniforms = torch.rand(w.cfg.num_decode_steps, len(scenes) * copies, ucols).numpy()
         ik = int(getattr(ae, 'insert_beam_size', 1))
         insert_uniforms = None
-        if ik > 1 and not w.cfg.disable_insertion and not map_only:
+        if ik > 1 and not w.cfg.disable_insertion and not map_only and w.cfg.use_grid_token:
             # the cell of an inserted agent from the insert_beam_size most probable ones (agent_decoder.py:1900-1904), torch's RNG
             insert_uniforms = torch.rand(w.cfg.num_decode_steps, 10, len(scenes) * copies).numpy()
         def make_engine(headroom=None):
@@ -416,7 +417,8 @@ class InfGenDecoder(nn.Module):
                              ('grid_agent_occ_seed', (11, steps, G)), ('grid_pt_occ_seed', (11, steps, G)),
                              ('grid_agent_occ_gt_seed', (11, steps, G))):
                 if k_ not in r:
-                    r[k_] = z(*shp_)
+                    # (use_grid_token = False: the grid's outputs are None, reference :2376-2386)
+                    r[k_] = z(*shp_) if w.cfg.use_grid_token or k_ == 'next_state_prob_seed' else None
             if 'agent_labels' not in r:
                 r.set_lazy('agent_labels', (lambda n=eng.hosts[i_]['A'] + o['num_inserted']: [[None] * T_cols for _ in range(n)]))
             r['log_message'] = ('No agents inserted!' if o['num_inserted'] == 0 else
@@ -509,7 +511,7 @@ class InfGenDecoder(nn.Module):
             sample_uniforms = _np(sample_uniforms)
         ik = int(getattr(ae, 'insert_beam_size', 1))
         insert_uniforms = None
-        if ik > 1 and not cfg.disable_insertion:
+        if ik > 1 and not cfg.disable_insertion and cfg.use_grid_token:
             insert_uniforms = torch.rand(cfg.num_decode_steps, 10, S).numpy()
         debug = bool(int(os.getenv('DEBUG', 0)))
 
@@ -551,7 +553,8 @@ class InfGenDecoder(nn.Module):
                              ('grid_agent_occ_seed', (11, steps, G)), ('grid_pt_occ_seed', (11, steps, G)),
                              ('grid_agent_occ_gt_seed', (11, steps, G))):
                 if k_ not in o:
-                    o[k_] = torch.zeros((B * shp_[0],) + shp_[1:], device=dev)
+                    o[k_] = (torch.zeros((B * shp_[0],) + shp_[1:], device=dev) if cfg.use_grid_token or k_ == 'next_state_prob_seed'
+                             else None)
             if 'agent_labels' not in o:
                 o['agent_labels'] = [[None] * T_cols for _ in range(int(n_fin[j::copies].sum()))]
             ins = (n_fin - c[:, 0])[j::copies]
@@ -579,6 +582,11 @@ class InfGenDecoder(nn.Module):
         through the HIP kernels).  The candidate rows of the refine stage and the neighbour-grid evaluation masks are drawn
         with ``torch.randperm`` from torch's CPU generator in the reference's order."""
         from ..forward_engine import ForwardEngine
+        ae = self.agent_encoder
+        for flag in ('use_grid_token', 'use_head_token', 'use_state_token'):
+            if not getattr(ae, flag):
+                raise NotImplementedError(f'InfGenDecoder.forward (teacher-forced) implements the full-token model only: {flag} is False '
+                                          f'(the ablation models roll out through inference)')
         w = self._weights()                 # (raises on a CPU module: no CPU fallback)
         batch = batch_from_data(data)
         vocab = {k: batch['agent'][f'trajectory_token_{k}'] for k in ('veh', 'ped', 'cyc')}

@@ -59,6 +59,10 @@ class RolloutConfig:
     buffer_size: int = 128
     num_recurrent_steps_val: int = 80
     disable_insertion: bool = True
+    # the reference's token ablations (agent_decoder.py:123-125; configs/experiments/ablate_*_tokens.yaml)
+    use_grid_token: bool = True
+    use_head_token: bool = True
+    use_state_token: bool = True
     state_token: Dict[str, int] = field(default_factory=lambda: dict(invalid=0, valid=1, enter=2, exit=3))
 
     @property
@@ -374,6 +378,15 @@ def fill_state_dict(shapes: Dict[str, tuple], seed: int = 0, rich: bool = True,
         else:
             w = rng.normal(0.0, 0.02, size=shape)
         out[name] = np.asarray(w, dtype=np.float32).reshape(shape)
+    return out
+
+
+def ablation_shapes(full: Dict[str, tuple], delta: Dict) -> Dict[str, tuple]:
+    """state_dict shapes of a token-ablation variant: the full model's without ``delta['removed']``, with ``delta['shapes']``
+    added or reshaped (tests/golden/state_dict_shapes_ablation.json holds that difference per variant)"""
+    removed = set(delta['removed'])
+    out = {k: tuple(v) for k, v in full.items() if k not in removed}
+    out.update({k: tuple(v) for k, v in delta['shapes'].items()})
     return out
 
 
