@@ -17,6 +17,7 @@
  *                            (infgen/modules/layers.py:74-75,94-99,110-112)
  *   infgen_heads             token_predict_head / state_predict_head + greedy arg-max
  *                            (infgen/modules/agent_decoder.py:2161-2167)
+ *   infgen_map_token_head    the map encoder's token_predict_head + top-10 (infgen/modules/map_decoder.py:119-121)
  *   infgen_map_graph         torch_cluster.radius_graph over map tokens + relative features
  *                            (infgen/modules/map_decoder.py:91-114)
  *   infgen_build_edges       _build_temporal_edge / _build_interaction_edge / _build_map2agent_edge
@@ -302,6 +303,13 @@ int infgen_attn_post_pre(float* X, int rows, const float* pack, const float* AGG
                          int has_pos, const float* next_pack, float* nQ, float* nU, float* nK, float* nV, void* stream);
 int infgen_heads(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
                  float* logits, int* next_token, int* next_state, void* stream);
+/* the map encoder's token_predict_head (infgen/modules/map_decoder.py:119-121) on the rows gather[k] (k < n) of X [..][ldx]:
+ * logits [n][token_size] (raw, fp32) and top_idx [n][10] (int64), the indices of the 10 largest logits in descending order (softmax
+ * is monotone), equal values lower index first.  pack = infgen_amd.packing.pack_mlp_layer of the head; token_size must be 1024.
+ * Arithmetic as infgen_heads: the split kernel (one launch, ranking fused) under gemm_terms 1 / 2 and from the attn_mode row count,
+ * else fp32 MFMA through hidden [n][128] (scratch, always pass it). */
+int infgen_map_token_head(const float* X, int ldx, const int* gather, int n, const float* pack, int token_size,
+                          float* hidden, float* logits, long long* top_idx, void* stream);
 /* out[k][:] = tab0[idx0[k]] + ((tab1[idx1[k]] + tab2[idx2[k]]) + tab3[idx3[k]]), rows of 128 floats, int64 indices (clamped to
  * the table sizes n0 .. n3): the map-token embedding plus the sum of its three nn.Embedding rows in one pass
  * (infgen/modules/map_decoder.py:87-89 and the token table of :70-86), in torch's summation order */
@@ -546,7 +554,7 @@ int infgen_set_gemm_terms(int terms);
 enum {
   INFGEN_KID_LINEAR = 0, INFGEN_KID_FOURIER, INFGEN_KID_ATTN_PRE, INFGEN_KID_EDGE_ATTN, INFGEN_KID_ATTN_POST,
   INFGEN_KID_HEADS, INFGEN_KID_BUILD_EDGES, INFGEN_KID_INTEGRATE, INFGEN_KID_RAWFEAT, INFGEN_KID_MAP_GRAPH,
-  INFGEN_KID_COUNT
+  INFGEN_KID_MAP_HEAD, INFGEN_KID_COUNT
 };
 int infgen_prof_enable(unsigned mask, int max_launches);
 int infgen_prof_collect(double* total_ms, int* calls, double* total_macs, unsigned long long* counters);

@@ -171,6 +171,7 @@ SYMBOLS = {
     'infgen_attn_post': (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
     'infgen_attn_post_pre': (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
     'infgen_heads': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p]),
+    'infgen_map_token_head': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
     'infgen_map_graph': (_i, [_i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p]),
     'infgen_build_edges': (_i, [C.POINTER(Rollout), _i, _i, _p]),
     'infgen_integrate': (_i, [C.POINTER(Rollout), _i, _p]),
@@ -203,7 +204,7 @@ Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_
     Q_ABI_VERSION, Q_SIZEOF_ROLLOUT = range(9)
 
 KERNEL_IDS = ['k_linear', 'k_fourier', 'k_attn_pre', 'k_edge_attn', 'k_attn_post', 'k_heads', 'k_build_edges',
-              'k_integrate', 'k_rawfeat_prep', 'k_map_graph']
+              'k_integrate', 'k_rawfeat_prep', 'k_map_graph', 'k_map_head']
 
 _lib: Optional[C.CDLL] = None
 

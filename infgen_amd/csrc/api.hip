@@ -852,6 +852,38 @@ extern "C" int infgen_heads(const float* X, int rows, const float* tok_pack, con
   return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream);
 }
 
+// the map encoder's token_predict_head (map_decoder.py:119-121) on the rows gather[k] of X.  Split arithmetic (k_map_head_h: one
+// launch, the ranking fused) under gemm_terms 1 / 2 and where attn_split picks it; otherwise the fp32 MFMA path of infgen_heads'
+// by-size rule: two k_linear launches through `hidden` [n][128] and k_map_topk
+extern "C" int infgen_map_token_head(const float* X, int ldx, const int* gather, int n, const float* pack, int token_size,
+                                     float* hidden, float* logits, long long* top_idx, void* stream) {
+  if (n <= 0) return 0;
+  if (token_size != MAP_HEAD_N) return fail("infgen_map_token_head", "token_size must be 1024 (map_decoder.py:58)");
+  if (!X || !gather || !pack || !logits || !top_idx || ldx < D || ldx % 4)
+    return fail("infgen_map_token_head", "null pointer, or ldx not a multiple of 4 of at least 128");
+  MapHeadArgs a{X, ldx, gather, n, pack, logits, top_idx};
+  const hipStream_t s = (hipStream_t)stream;
+  ProfScope _ps(INFGEN_KID_MAP_HEAD, stream, (double)n * (16384.0 + 128.0 * token_size));
+  if (O().gemm_terms != 3 || attn_split(n)) {
+    int grid = ceil_div(n, 64);
+    if (grid > 512) grid = 512;
+    if (O().gemm_terms == 1) hipLaunchKernelGGL(k_map_head_h<1>, dim3(grid), dim3(256), 0, s, a);
+    else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_map_head_h_b16<1>, dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_map_head_h<3>, dim3(grid), dim3(256), 0, s, a);
+    return check_launch("infgen_map_token_head");
+  }
+  if (!hidden) return fail("infgen_map_token_head", "the fp32 path needs hidden [n][128]");
+  const int W3 = 16768, tiles = ceil_div(n, TR), passes = token_size / 128;
+  LinearArgs l0{X, ldx, gather, n, D, D, pack, D, pack + 16384, D, nullptr, nullptr, pack + 16512, pack + 16640, 1, hidden, D};
+  hipLaunchKernelGGL(k_linear, dim3(tiles), dim3(NT), 0, s, l0);
+  LinearArgs l1{hidden, D, nullptr, n, D, D, pack + W3, token_size, pack + W3 + (size_t)128 * token_size, token_size,
+                nullptr, nullptr, nullptr, nullptr, 0, logits, token_size};
+  const int gy = tiles < 512 ? min(passes, ceil_div(512, tiles)) : 1;
+  hipLaunchKernelGGL(k_linear, dim3(tiles, gy), dim3(NT), 0, s, l1);
+  hipLaunchKernelGGL(k_map_topk, dim3(ceil_div(n, 4)), dim3(256), 0, s, a);
+  return check_launch("infgen_map_token_head");
+}
+
 extern "C" int infgen_embedding_sum4(const float* tab0, const long long* idx0, int n0, const float* tab1, const long long* idx1, int n1,
                                      const float* tab2, const long long* idx2, int n2, const float* tab3, const long long* idx3, int n3,
                                      int rows, float* out, void* stream) {

@@ -279,6 +279,15 @@ struct HeadsArgs {
   // (max, first index) into part[row] as an ordered 64-bit key (atomicMax; zeroed by the caller), k_heads_finish decodes them
   unsigned long long* part; int nsplit;
 };
+
+// the map encoder's token_predict_head (map_decoder.py:119-121) over gathered rows: logits and the 10 most probable tokens
+constexpr int MAP_HEAD_N = 1024, MAP_TOPK = 10;
+struct MapHeadArgs {
+  const float* X; int ldx; const int* gather; int rows;
+  const float* pack;        // MLPLayer pack (packing.pack_mlp_layer): P(128,128) W0, b0, ln g/b, P(128,1024) W3, b3, split section
+  float* logits;            // [rows][MAP_HEAD_N]
+  long long* top;           // [rows][MAP_TOPK], descending
+};
 __global__ void k_heads_finish(const unsigned long long* part, int rows, int* next_token);
 
 // ---- per-scene state (column-major per scene: [S][T][A_cap]) -----------------------------------
@@ -476,6 +485,9 @@ __global__ void k_placement(PlacementArgs a);
 __global__ void k_window_loglik(WindowLoglikArgs a);
 __global__ void k_road_edge(RoadEdgeArgs a);
 template <int TERMS> __global__ void k_heads_h(HeadsArgs a);
+template <int TERMS> __global__ void k_map_head_h(MapHeadArgs a);     // mlp_h.hip
+template <int TERMS> __global__ void k_map_head_h_b16(MapHeadArgs a);
+__global__ void k_map_topk(MapHeadArgs a);
 __global__ void k_match_map_tokens(MatchMapArgs a);
 __global__ void k_tokenize_prep(TokenizeArgs a);
 __global__ void k_fetch_enterings(EnteringsArgs a);

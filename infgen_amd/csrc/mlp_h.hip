@@ -194,6 +194,110 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
   }
 }
 
+// top-10 of one MAP_HEAD_N-logit row on one wave (map_decoder.py:120-121: topk of the softmax, which is monotone, so the logits
+// are ranked): 16 logits per lane (columns 256 i + 4 lane + c), ten rounds of a wave arg-max over the logits not yet taken.
+// Equal values take the lower index first, like k_heads_h's arg-max.
+__device__ __forceinline__ void map_topk_row(const float* lg, long long* top, int lane) {
+  float v[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 x = *reinterpret_cast<const float4*>(lg + 256 * i + 4 * lane);
+    v[4 * i] = x.x; v[4 * i + 1] = x.y; v[4 * i + 2] = x.z; v[4 * i + 3] = x.w;
+  }
+  unsigned taken = 0;
+#pragma unroll
+  for (int r = 0; r < MAP_TOPK; ++r) {
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int k = 0; k < 16; ++k)          // (ascending column order: the first of equal values stays)
+      if (!((taken >> k) & 1u) && (bi == 0x7fffffff || v[k] > bv)) { bv = v[k]; bi = 256 * (k >> 2) + 4 * lane + (k & 3); }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float ov = __shfl_xor(bv, off, 64);
+      const int oi = __shfl_xor(bi, off, 64);
+      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (((bi & 255) >> 2) == lane) taken |= 1u << (4 * (bi >> 8) + (bi & 3));
+    if (lane == 0) top[r] = bi;
+  }
+}
+
+// the map encoder's token_predict_head (map_decoder.py:119-121): rows gather[k] of X -> Linear(128,128) LN ReLU Linear(128,1024),
+// the logits stored, then every wave ranks its own 16 rows (map_topk_row) from what it just stored
+template <int TERMS>
+__global__ __launch_bounds__(MH_NT, 2) void k_map_head_h(MapHeadArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned short Wb[MH_RING][QUARTER];
+  __shared__ __attribute__((aligned(16))) float Vt[16 + 384];      // hdr | b0 g0 be0
+  __shared__ const unsigned short* seg_ptr[2];
+  __shared__ int seg_n[2];
+  const int ntiles = (a.rows + MH_TILE - 1) / MH_TILE;
+  if ((int)blockIdx.x >= ntiles) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, j = lane & 15, rg = lane >> 4;
+  constexpr int nchunk = MAP_HEAD_N / 128;
+  const float* P = a.pack;
+  const int W3 = 16768;                                      // P(128, MAP_HEAD_N), then b3
+  const int oh = W3 + 128 * MAP_HEAD_N + MAP_HEAD_N;         // split section
+  if (tid == 0) {
+    const unsigned short* q = reinterpret_cast<const unsigned short*>(P + oh + 16);
+    seg_ptr[0] = q;                seg_n[0] = 4;             // W0
+    seg_ptr[1] = q + 4 * QUARTER;  seg_n[1] = 4 * nchunk;    // W3 chunks
+  }
+  if (tid < 16) Vt[tid] = P[oh + tid];
+  for (int i = tid; i < 384; i += MH_NT) Vt[16 + i] = P[16384 + i];
+  __syncthreads();
+  QuarterStream<MH_NT, MH_RING> qs;
+  qs.init(seg_ptr, seg_n, 2, (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x, Wb, tid);
+  const float* b3 = P + W3 + (size_t)128 * MAP_HEAD_N;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int row = tile * MH_TILE + w * 16 + j;
+    const bool valid = row < a.rows;
+    u32x4 Bh[4], Bl[4];
+    f32x4 h[8];
+    mh_load_row(h, valid ? a.X + (size_t)a.gather[row] * a.ldx : nullptr, rg);
+    const float inv_x = frags_scaled(h, Bh, Bl);
+    mh_zero(h);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) gemm_quarter<TERMS>(h, qs.take(), Bh[s], Bl[s], lane);
+    mh_scale_bias(h, inv_x * Vt[0], Vt + 16, rg);
+    ln_regs<true, true>(h, Vt + 16 + 128, Vt + 16 + 256, rg);
+    const float inv_h = frags_scaled(h, Bh, Bl) * Vt[1];
+    for (int c = 0; c < nchunk; ++c) {
+      f32x4 lg[8];
+      mh_zero(lg);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) gemm_quarter<TERMS>(lg, qs.take(), Bh[s], Bl[s], lane);
+      if (valid) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+          const int col = 128 * c + 16 * t + 4 * rg;
+          const float4 bb = *reinterpret_cast<const float4*>(b3 + col);
+          *reinterpret_cast<float4*>(a.logits + (size_t)row * MAP_HEAD_N + col) =
+              make_float4(lg[t][0] * inv_h + bb.x, lg[t][1] * inv_h + bb.y, lg[t][2] * inv_h + bb.z, lg[t][3] * inv_h + bb.w);
+        }
+      }
+    }
+    // the wave's stores complete before its lanes read each other's columns back (one CU: no cache maintenance needed)
+    __threadfence_block();
+    const int r0 = tile * MH_TILE + w * 16;
+    for (int rr = 0; rr < 16 && r0 + rr < a.rows; ++rr)
+      map_topk_row(a.logits + (size_t)(r0 + rr) * MAP_HEAD_N, a.top + (size_t)(r0 + rr) * MAP_TOPK, lane);
+  }
+}
+
+#if !IG_BF16_OPERANDS
+// the ranking alone, one row per wave: the fp32-MFMA path of infgen_map_token_head (k_linear wrote the logits)
+__global__ __launch_bounds__(256) void k_map_topk(MapHeadArgs a) {
+  const int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (row >= a.rows) return;
+  map_topk_row(a.logits + (size_t)row * MAP_HEAD_N, a.top + (size_t)row * MAP_TOPK, threadIdx.x & 63);
+}
+#endif
+
+#if !IG_BF16_OPERANDS
+template __global__ void k_map_head_h<3>(MapHeadArgs);
+#endif
+template __global__ void k_map_head_h<1>(MapHeadArgs);
 #if !IG_BF16_OPERANDS
 template __global__ void k_mlpemb_h<3>(MlpEmbHArgs);
 #endif

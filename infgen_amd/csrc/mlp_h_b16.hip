@@ -3,4 +3,5 @@
 #define IG_BF16_OPERANDS 1
 #define k_mlpemb_h k_mlpemb_h_b16
 #define k_heads_h k_heads_h_b16
+#define k_map_head_h k_map_head_h_b16
 #include "mlp_h.hip"

@@ -202,6 +202,8 @@ class PackedWeights:
         self.tok_emb = [dev(packing.pack_mlp_embedding(sd, f'{ap}.token_emb_{k}')) for k in ('veh', 'ped', 'cyc')]
         self.grid_emb = dev(packing.pack_mlp_embedding(sd, f'{ap}.token_emb_grid'))
         self.map_tok_emb = dev(packing.pack_mlp_embedding(sd, f'{mp}.token_emb'))
+        # the map-token prediction head (map_decoder.py:59-60, 119-121; infgen_map_token_head)
+        self.map_head = dev(packing.pack_mlp_layer(sd, f'{mp}.token_predict_head'))
         self.tok_head = dev(packing.pack_mlp_layer(sd, f'{ap}.token_predict_head'))
         self.st_head = dev(packing.pack_mlp_layer(sd, f'{ap}.state_predict_head', row_major_out=True))
         g = lambda k: dev(packing._get(sd, k))
@@ -325,6 +327,24 @@ class Ops:
                                           base + 4 * w_off, npad, bias, n, prg, prb, pg, pb, int(relu),
                                           _lib.ptr(out), out.stride(0), self.stream), 'infgen_linear')
         return out
+
+    def map_token_head(self, x, rows, pack, token_size=1024):
+        """the map encoder's token_predict_head on rows ``rows`` (int32, device) of ``x`` [..][128] (map_decoder.py:119-121) ->
+        logits [n][token_size], the indices of the 10 largest [n][10] (int64, descending)"""
+        n = int(rows.numel())
+        logits = torch.empty(n, token_size, device=self.device)
+        top = torch.empty(n, 10, device=self.device, dtype=torch.long)
+        if n:
+            # the fp32 path's scratch only where that path runs (the entry's rule: split kernel under gemm_terms 1 / 2, with
+            # attn_mode 1, or from 10,241 rows under the by-size modes)
+            o = _lib.Options()
+            _lib.check(self.lib.infgen_get_effective_options(C.byref(o)), 'infgen_get_effective_options')
+            split = o.gemm_terms != 3 or o.attn_mode == 1 or (o.attn_mode >= 2 and n > 10240)
+            hidden = None if split else torch.empty(n, D, device=self.device)
+            _lib.check(self.lib.infgen_map_token_head(_lib.ptr(x), x.stride(0), _lib.ptr(rows), n, _lib.ptr(pack), int(token_size),
+                                                      _lib.ptr(hidden), _lib.ptr(logits), _lib.ptr(top), self.stream),
+                       'infgen_map_token_head')
+        return logits, top
 
     def mlp_embedding(self, x, pack, k0, out=None):
         """MLPEmbedding.forward (reference infgen/modules/layers.py:180-192)"""
@@ -1323,6 +1343,14 @@ class RolloutEngine:
         if map_only:
             return
         self._finish_prologue()
+
+    def map_token_head(self, rows: torch.Tensor):
+        """the map encoder's token_predict_head (map_decoder.py:119-121) on rows ``rows`` (int32, device) of this engine's map
+        encoding ``x_pt`` [S0 * M_cap][128] - map scene ms's token m is row ms * M_cap + m - under this engine's arithmetic (the
+        prologue's option block).  Runs after the prologue: x_pt is final once the map layers ran and nothing later writes it.
+        -> logits [n][1024], top-10 indices [n][10] (int64, descending)"""
+        with _lib.thread_options(self._effective_options()):
+            return self.ops.map_token_head(self.x_pt, rows.to(self.device, torch.int32).contiguous(), self.w.map_head)
 
     def _prologue_with_given_map(self):
         """inference_no_map: x_pt comes from the caller (reference infgen_decoder.py:132-134)"""

@@ -52,7 +52,80 @@ class _Edges:
         return b
 
 
-class ForwardEngine:
+class MapEncoder:
+    """the map encoder alone (map_decoder.py:70-118) over a (batched) set of map tokens, the operators of the forward: what the
+    map-pretraining model (predict_map only) runs - no agent state, no RolloutEngine.  ``batch``: host arrays of ``pt_token``
+    (position, orientation, type, pl_type, token_idx, ptr), ``map_polygon.light_type`` and ``pt_token__to__map_polygon``."""
+
+    def __init__(self, weights: PackedWeights, batch: Mapping, map_vocab: np.ndarray):
+        self.w, self.cfg, self.device = weights, weights.cfg, weights.device
+        if getattr(weights, 'operand_bits', 11) != 11:
+            raise ValueError('the map encoder alone runs in fp32 arithmetic: it takes default packs (operand_bits=11)')
+        self.ops = Ops(self.device)
+        self.lib = self.ops.lib
+        self.batch = batch
+        pt = batch['pt_token']
+        self.h = {'pt_ptr': np.asarray(pt['ptr']).astype(np.int64)}
+        self.B = int(self.h['pt_ptr'].size) - 1
+        dev = self.device
+        self._map_vocab = torch.from_numpy(np.ascontiguousarray(np.asarray(map_vocab, np.float32).reshape(map_vocab.shape[0], -1))).to(dev)
+        self.map_pos = torch.from_numpy(np.ascontiguousarray(np.asarray(pt['position'], np.float32)[:, :2])).to(dev)
+        self.map_orient = torch.from_numpy(np.ascontiguousarray(np.asarray(pt['orientation'], np.float32))).to(dev)
+        self.M = int(self.map_pos.shape[0])
+
+    def run(self) -> torch.Tensor:
+        """-> x_pt (M, 128), rows in the tokens' order"""
+        tab = self.ops.mlp_embedding(self._map_vocab, self.w.map_tok_emb, self._map_vocab.shape[1])
+        return self.map_encoder({'map_tab': tab})
+
+    def _queries(self, **cols):
+        """int32 device arrays of one query list"""
+        return {k: torch.from_numpy(np.ascontiguousarray(np.asarray(v).astype(np.int32))).to(self.device) for k, v in cols.items()}
+
+    def _build(self, e: _Edges, q, p, c, radius, K, gap_rule=0, index_diff=0, self_drop=False, pair=None, base=0, cap=None,
+               total=None, off=None, cnt=None):
+        """one infgen_radius_edges launch; p / c = (pos, head, inv[, ok, src]) device arrays of queries / candidates"""
+        if q['node'].numel() == 0:
+            return
+        r = _lib.RadiusEdges()
+        P = _lib.ptr
+        r.n_q = int(q['node'].numel())
+        r.q_node, r.q_pt, r.q_c0, r.q_c1 = P(q['node']), P(q['pt']), P(q['c0']), P(q['c1'])
+        r.q_self = P(q['pt']) if self_drop else None
+        r.q_pair_off = P(q['pair']) if pair is not None else None
+        r.pair_ok = P(pair)
+        r.p_pos, r.p_head, r.p_inv = P(p[0]), P(p[1]), P(p[2])
+        r.c_pos, r.c_head, r.c_inv = P(c[0]), P(c[1]), P(c[2])
+        r.c_ok = P(c[3]) if len(c) > 3 else None
+        r.c_src = P(c[4]) if len(c) > 4 else None
+        r.radius, r.K, r.gap_rule, r.index_diff, r.e_base = float(radius), int(K), int(gap_rule), int(index_diff), int(base)
+        eb = e.struct(base, cap, total, off, cnt)
+        _lib.check(self.lib.infgen_radius_edges(C.byref(r), C.byref(eb), self.ops.stream), 'infgen_radius_edges')
+
+    # ------------------------------------------------------------------ map encoder (map_decoder.py:70-130)
+    def map_encoder(self, tabs):
+        w, cfg, ops, dev = self.w, self.cfg, self.ops, self.device
+        pt, h, M = self.batch['pt_token'], self.h, self.M
+        lt = lambda a: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev)
+        e2 = np.asarray(self.batch['pt_token__to__map_polygon']['edge_index']).astype(np.int64)
+        light = np.asarray(self.batch['map_polygon']['light_type']).astype(np.int64)[e2[1]]
+        x = tabs['map_tab'][lt(pt['token_idx'])]
+        cat = (w.type_pt_emb[lt(pt['type'])] + w.polygon_type_emb[lt(pt['pl_type'])]) + w.light_pl_emb[lt(light)]
+        x_pt = (x + cat).contiguous()
+        scene_of = np.repeat(np.arange(self.B), np.diff(h['pt_ptr']))
+        q = self._queries(node=np.arange(M), pt=np.arange(M), c0=h['pt_ptr'][scene_of], c1=h['pt_ptr'][scene_of + 1])
+        zero_inv = torch.zeros(M, device=dev, dtype=torch.uint8)
+        cap = int(sum(int(m) * min(int(m) - 1, 100) for m in np.diff(h['pt_ptr'])))
+        e = _Edges(dev, M, cap)
+        arr = (self.map_pos, self.map_orient, zero_inv)
+        self._build(e, q, arr, arr, cfg.pl2pl_radius, 100 + 1, self_drop=True)
+        ops.fourier(e.raw, 3, w.four_pt, e.rhat, count_dev=e.total, rows=e.cap, normalize=True)
+        for i in range(cfg.num_map_layers):
+            ops.attention_layer(x_pt, w.attn_pt[i], e.off, e.cnt, e.src, e.rhat)
+        return x_pt
+
+
+class ForwardEngine(MapEncoder):
     def __init__(self, weights: PackedWeights, batch: Mapping, vocab: Mapping[str, np.ndarray], map_vocab: np.ndarray,
                  grid: np.ndarray):
         self.w, self.cfg, self.device = weights, weights.cfg, weights.device
@@ -144,52 +217,6 @@ class ForwardEngine:
         self.M = int(self.map_pos.shape[0])
         h['node_of'] = node_of
         h['is_agent'] = is_agent
-
-    def _queries(self, **cols):
-        """int32 device arrays of one query list"""
-        return {k: torch.from_numpy(np.ascontiguousarray(np.asarray(v).astype(np.int32))).to(self.device) for k, v in cols.items()}
-
-    def _build(self, e: _Edges, q, p, c, radius, K, gap_rule=0, index_diff=0, self_drop=False, pair=None, base=0, cap=None,
-               total=None, off=None, cnt=None):
-        """one infgen_radius_edges launch; p / c = (pos, head, inv[, ok, src]) device arrays of queries / candidates"""
-        if q['node'].numel() == 0:
-            return
-        r = _lib.RadiusEdges()
-        P = _lib.ptr
-        r.n_q = int(q['node'].numel())
-        r.q_node, r.q_pt, r.q_c0, r.q_c1 = P(q['node']), P(q['pt']), P(q['c0']), P(q['c1'])
-        r.q_self = P(q['pt']) if self_drop else None
-        r.q_pair_off = P(q['pair']) if pair is not None else None
-        r.pair_ok = P(pair)
-        r.p_pos, r.p_head, r.p_inv = P(p[0]), P(p[1]), P(p[2])
-        r.c_pos, r.c_head, r.c_inv = P(c[0]), P(c[1]), P(c[2])
-        r.c_ok = P(c[3]) if len(c) > 3 else None
-        r.c_src = P(c[4]) if len(c) > 4 else None
-        r.radius, r.K, r.gap_rule, r.index_diff, r.e_base = float(radius), int(K), int(gap_rule), int(index_diff), int(base)
-        eb = e.struct(base, cap, total, off, cnt)
-        _lib.check(self.lib.infgen_radius_edges(C.byref(r), C.byref(eb), self.ops.stream), 'infgen_radius_edges')
-
-    # ------------------------------------------------------------------ map encoder (map_decoder.py:70-130)
-    def map_encoder(self, tabs):
-        w, cfg, ops, dev = self.w, self.cfg, self.ops, self.device
-        pt, h, M = self.batch['pt_token'], self.h, self.M
-        lt = lambda a: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev)
-        e2 = np.asarray(self.batch['pt_token__to__map_polygon']['edge_index']).astype(np.int64)
-        light = np.asarray(self.batch['map_polygon']['light_type']).astype(np.int64)[e2[1]]
-        x = tabs['map_tab'][lt(pt['token_idx'])]
-        cat = (w.type_pt_emb[lt(pt['type'])] + w.polygon_type_emb[lt(pt['pl_type'])]) + w.light_pl_emb[lt(light)]
-        x_pt = (x + cat).contiguous()
-        scene_of = np.repeat(np.arange(self.B), np.diff(h['pt_ptr']))
-        q = self._queries(node=np.arange(M), pt=np.arange(M), c0=h['pt_ptr'][scene_of], c1=h['pt_ptr'][scene_of + 1])
-        zero_inv = torch.zeros(M, device=dev, dtype=torch.uint8)
-        cap = int(sum(int(m) * min(int(m) - 1, 100) for m in np.diff(h['pt_ptr'])))
-        e = _Edges(dev, M, cap)
-        arr = (self.map_pos, self.map_orient, zero_inv)
-        self._build(e, q, arr, arr, cfg.pl2pl_radius, 100 + 1, self_drop=True)
-        ops.fourier(e.raw, 3, w.four_pt, e.rhat, count_dev=e.total, rows=e.cap, normalize=True)
-        for i in range(cfg.num_map_layers):
-            ops.attention_layer(x_pt, w.attn_pt[i], e.off, e.cnt, e.src, e.rhat)
-        return x_pt
 
     # ------------------------------------------------------------------ raw features (agent_decoder.py:332-509)
     def _features(self, tabs, state, tok_emb, types_cat, gap_mask=None, head=None):

@@ -153,6 +153,24 @@ def stack_datas(datas, min_scenes: int = 8, any_device: bool = False):
         return None
 
 
+def _pt_mask(data, key) -> Optional[torch.Tensor]:
+    """``data['pt_token'][key]`` (pt_pred_mask / pt_target_mask, filled by InfGen.sample_pt_pred) as a flat bool tensor; None
+    when the data carries none"""
+    try:
+        m = data['pt_token'][key]
+    except (KeyError, TypeError):
+        return None
+    return None if m is None else torch.as_tensor(m).reshape(-1).bool()
+
+
+def _scatter_rows(pm: torch.Tensor, rowmap: torch.Tensor, n: int) -> torch.Tensor:
+    """rowmap[pm] for a mask with n True entries, known on the host: no second count read (every index of the scatter is
+    distinct: the unselected entries land past the first n)"""
+    ar = torch.arange(pm.numel(), device=pm.device)
+    dst = torch.where(pm, torch.cumsum(pm, 0) - 1, n + ar)
+    return torch.empty(n + pm.numel(), dtype=torch.int64, device=pm.device).scatter_(0, dst, rowmap.to(torch.int64))[:n]
+
+
 def num_graphs(data) -> int:
     """graphs in ``data``: ``num_graphs`` of a PyG-style Batch, else the length of ``agent.ptr`` - 1, else 1"""
     ng = getattr(data, 'num_graphs', None)
@@ -382,7 +400,7 @@ class InfGenDecoder(nn.Module):
             self._engines[ekey] = eng
         if map_only:
             eng.prologue(map_only=True)
-            return eng.x_pt[:eng.hosts[0]['M']].clone()
+            return eng.x_pt[:eng.hosts[0]['M']].clone(), self._map_keys(eng, datas)[0]
         # the reference's agent arrays grow without bound; here rows are pre-allocated per scene.  If the inserted agents
         # outgrow them the (deterministic) rollout is repeated with twice the rows instead of dropping insertions
         while True:
@@ -395,6 +413,8 @@ class InfGenDecoder(nn.Module):
                 if eng.A_cap >= limit:
                     raise
                 eng = self._engines[ekey] = make_engine(headroom=min(2 * eng.A_cap, limit) - amax)
+        # the map-token head once per distinct scene (not with a caller's map encoding: inference_no_map passes its map_enc through)
+        mk = self._map_keys(eng, datas) if xo is None else None
         # per-scene dicts of device tensors (no host round trip of the results), detached from the engine's buffers
         outs = eng.outputs_device(detach=True)
         dev = w.device
@@ -412,6 +432,9 @@ class InfGenDecoder(nn.Module):
             datas = [d_ for d_ in datas for _ in range(copies)]
         for i_, (d, o) in enumerate(zip(datas, outs)):
             r = o                                   # (a LazyOut: per-scene views are cut when a key is read, not here)
+            if mk is not None:                      # (copies of a scene share its tensors)
+                for k_, v_ in mk[i_ // copies].items():
+                    r[k_] = v_
             # without insertion (or in the batched entry) these stay what the reference initialises them to (:1746-1750, :1730)
             for k_, shp_ in (('next_state_prob_seed', (11, steps)), ('next_pos_rel_prob_seed', (11, steps, G)),
                              ('grid_agent_occ_seed', (11, steps, G)), ('grid_pt_occ_seed', (11, steps, G)),
@@ -435,6 +458,47 @@ class InfGenDecoder(nn.Module):
                 pass
             res.append(r)
         return res if batch is not None else res[0]
+
+    def _empty_map_keys(self, dev) -> Dict[str, torch.Tensor]:
+        return {'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
+                'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=dev),
+                'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=dev),
+                'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=dev)}
+
+    def _gt_keys(self, data, dev) -> Dict[str, torch.Tensor]:
+        """the empty head keys plus token_idx[pt_target_mask] (map_decoder.py:122) when the data carries the mask"""
+        k = self._empty_map_keys(dev)
+        tm = _pt_mask(data, 'pt_target_mask')
+        if tm is not None:
+            k['map_next_token_idx_gt'] = torch.as_tensor(data['pt_token']['token_idx']).to(dev)[tm.to(dev)]
+        return k
+
+    def _map_keys(self, eng: RolloutEngine, datas: Sequence) -> List[Dict[str, torch.Tensor]]:
+        """the map-token head's keys of the reference's map encoder (map_decoder.py:119-129) for the distinct map scenes of ``eng``
+        (map scene i = datas[i]): logits and top-10 of the pt_pred_mask rows, token_idx[pt_target_mask], the all-True evaluation
+        mask.  One count read for all scenes, and one head launch when some scene has predicted rows."""
+        dev = eng.device
+        out = [self._gt_keys(d, dev) for d in datas]
+        masks = [_pt_mask(d, 'pt_pred_mask') for d in datas]
+        if all(m is None for m in masks):
+            return out
+        M = [int(d['pt_token']['position'].shape[0]) for d in datas]
+        pm = torch.cat([(m if m is not None else torch.zeros(Mi, dtype=torch.bool)).to(dev) for m, Mi in zip(masks, M)])
+        off = np.concatenate([[0], np.cumsum(M)]).astype(np.int64)
+        ends = torch.nn.functional.pad(torch.cumsum(pm, 0), (1, 0))[torch.from_numpy(off).to(dev)].cpu().numpy()
+        cnt, n = np.diff(ends), int(ends[-1])
+        if n == 0:
+            return out
+        base = np.repeat(np.arange(len(M), dtype=np.int64) * eng.M_cap - off[:-1], M)
+        rowmap = torch.arange(int(off[-1]), device=dev) + torch.from_numpy(base).to(dev)
+        lg, top = eng.map_token_head(_scatter_rows(pm, rowmap, n))
+        o = 0
+        for i, c_ in enumerate(cnt.tolist()):
+            if c_:
+                out[i].update(map_next_token_idx=top[o:o + c_], map_next_token_prob=lg[o:o + c_],
+                              map_next_token_eval_mask=torch.ones(c_, dtype=torch.bool, device=dev))
+            o += c_
+        return out
 
     _HOST_CACHE = 4             # entries of each host-copy cache below
 
@@ -489,8 +553,15 @@ class InfGenDecoder(nn.Module):
         cacheable = all(isinstance(t, torch.Tensor) for t in src) and all(int(t.shape[0]) == ts for t in voc_t)
         key = tuple(self._tensor_key(t) for t in keep)
         hit = cache.get(key) if cacheable else None
+        # the map-token head's row count per graph rides along too: the running count of pt_pred_mask at every pt_token.ptr entry
+        pm = _pt_mask(data, 'pt_pred_mask')
+        pm_ext = []
+        if pm is not None:
+            pm = pm.to(torch.as_tensor(ag['ptr']).device)
+            mptr_d = torch.as_tensor(data['pt_token']['ptr']).to(pm.device, torch.int64)
+            pm_ext = [torch.nn.functional.pad(torch.cumsum(pm, 0), (1, 0))[mptr_d]]
         lay = read_batch_layout(data, cfg.num_columns, cfg.hist_columns, lib.infgen_layout_query(_lib.Q_MAX_AGENTS),
-                                extra=() if hit is not None else [t[:ts] for t in voc_t])
+                                extra=(() if hit is not None else tuple(t[:ts] for t in voc_t)) + tuple(pm_ext))
         if hit is None:
             vocab_ = {k: np.asarray(v, np.float32) for k, v in zip(('veh', 'ped', 'cyc'), lay['extra'])}
             tkey_ = PackedWeights.tables_key(*(vocab_[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab)
@@ -542,10 +613,16 @@ class InfGenDecoder(nn.Module):
         outs = eng.outputs_batch()
         n_fin, c = eng.batch_counts()
         dev, steps, G, T_cols = w.device, cfg.num_decode_steps, ae.grid_size, cfg.num_columns
-        map_keys = {'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
-                    'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=dev),
-                    'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=dev),
-                    'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=dev)}
+        # the map-token head once per graph, one launch: the predicted rows of the Batch in graph order (graph g's token p sits at
+        # row g * M_cap + p - ptr[g] of the engine's map encoding), shared by every copy
+        map_keys = self._gt_keys(data, dev)
+        n_pred = int(lay['extra'][-1][-1]) if pm is not None else 0
+        if n_pred:
+            ar = torch.arange(pm.numel(), device=pm.device)
+            g = torch.searchsorted(mptr_d[1:], ar, right=True)
+            lg, top = eng.map_token_head(_scatter_rows(pm, ar - mptr_d[g] + g * eng.M_cap, n_pred))
+            map_keys.update(map_next_token_idx=top, map_next_token_prob=lg,
+                            map_next_token_eval_mask=torch.ones(n_pred, dtype=torch.bool, device=dev))
         passthrough = {k_: data[k_] for k_ in self.data_keys if k_ in data}
         res = []
         for j, o in enumerate(outs):
@@ -582,6 +659,8 @@ class InfGenDecoder(nn.Module):
         through the HIP kernels).  The candidate rows of the refine stage and the neighbour-grid evaluation masks are drawn
         with ``torch.randperm`` from torch's CPU generator in the reference's order."""
         from ..forward_engine import ForwardEngine
+        if self.map_only():
+            return self._map_model(data)
         ae = self.agent_encoder
         for flag in ('use_grid_token', 'use_head_token', 'use_state_token'):
             if not getattr(ae, flag):
@@ -592,13 +671,48 @@ class InfGenDecoder(nn.Module):
         vocab = {k: batch['agent'][f'trajectory_token_{k}'] for k in ('veh', 'ped', 'cyc')}
         map_vocab = _np(self.map_encoder.map_token['traj_src']).astype(np.float32)
         grid = self.agent_encoder.attr_tokenizer.grid.detach().cpu().numpy()
-        out = ForwardEngine(w, batch, vocab, map_vocab, grid).run()
-        dev = w.device
-        map_enc = {'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
-                   'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=dev),
-                   'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=dev),
-                   'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=dev)}
+        fe = ForwardEngine(w, batch, vocab, map_vocab, grid)
+        out = fe.run()
+        map_enc = self._flat_map_keys(out['x_pt'], data, fe.ops, w)
         return {**map_enc, **out, **{k: data[k] for k in self.data_keys if k in data}}
+
+    def _flat_map_keys(self, x_pt, data, ops, w) -> Dict[str, torch.Tensor]:
+        """the head's keys over an x_pt that holds the (batched) tokens in their own order: the rows are the mask's indices (one
+        count read, like the reference's boolean index)"""
+        dev = w.device
+        keys = self._gt_keys(data, dev)
+        pm = _pt_mask(data, 'pt_pred_mask')
+        if pm is not None:
+            rows = pm.to(dev).nonzero().reshape(-1)
+            if rows.numel():
+                lg, top = ops.map_token_head(x_pt, rows.to(torch.int32), w.map_head)
+                keys.update(map_next_token_idx=top, map_next_token_prob=lg,
+                            map_next_token_eval_mask=torch.ones(rows.numel(), dtype=torch.bool, device=dev))
+        return keys
+
+    def map_only(self) -> bool:
+        """the map-pretraining model (configs/pretrain_scalable_map.yaml): no agent prediction, only the map-token head"""
+        return not (self.predict_motion or self.predict_state or self.predict_occ)
+
+    def _map_model(self, data) -> Dict[str, torch.Tensor]:
+        """forward / inference of the map-pretraining model (infgen_decoder.py:114-130 with predict_motion / _state / _occ False): the
+        map encoder's dict plus the data keys.  No agent decoding and no RolloutEngine: the map encoder runs alone
+        (forward_engine.MapEncoder; a Batch's graphs through pt_token.ptr)"""
+        from ..forward_engine import MapEncoder
+        w = self._weights()
+        pt = data['pt_token']
+        ptd = {k: _np(pt[k]) for k in ('position', 'orientation', 'type', 'pl_type', 'token_idx')}
+        ptd['ptr'] = _np(pt['ptr']) if 'ptr' in pt else np.array([0, ptd['position'].shape[0]], np.int64)
+        key = ('pt_token', 'to', 'map_polygon')
+        try:
+            e = data[key]['edge_index']
+        except (KeyError, TypeError):
+            e = data['pt_token__to__map_polygon']['edge_index']
+        enc = MapEncoder(w, {'pt_token': ptd, 'map_polygon': {'light_type': _np(data['map_polygon']['light_type'])},
+                             'pt_token__to__map_polygon': {'edge_index': _np(e)}},
+                         np.asarray(self._host_const(self.map_encoder.map_token['traj_src']), np.float32))
+        x_pt = enc.run()
+        return {'x_pt': x_pt, **self._flat_map_keys(x_pt, data, enc.ops, w), **{k: data[k] for k in self.data_keys if k in data}}
 
     @torch.no_grad()
     def inference(self, data, sample_uniforms=None) -> Dict[str, torch.Tensor]:
@@ -610,7 +724,11 @@ class InfGenDecoder(nn.Module):
         graphs' rows in graph order, with ``agent_batch`` / ``agent_ptr`` and ``ego_index`` [B]; ``sample_uniforms`` is then
         [steps][B][cols], graph s's slice indexed like a single-graph call's; cols must cover every graph's row count BEFORE
         the filter of agent_decoder.py:1609 (with insertion on: INFGEN_Q_MAX_AGENTS), since the kept counts are only known on
-        the device when the uniforms are checked."""
+        the device when the uniforms are checked.
+        The map-pretraining model (predict_motion / predict_state / predict_occ all False) returns the map encoder's dict plus the
+        data keys, single graph or Batch, as the reference does (``_map_model``)."""
+        if self.map_only():
+            return self._map_model(data)
         if num_graphs(data) > 1:
             return self._run_graphs(data, sample_uniforms=sample_uniforms)[0]
         r = self._run(data, sample_uniforms=sample_uniforms)

@@ -40,17 +40,10 @@ class InfGenMapDecoder(nn.Module):
 
     @torch.no_grad()
     def forward(self, data) -> Dict[str, torch.Tensor]:
-        """returns {'x_pt': (M,128), 'map_next_token_*': ...} like the reference; the map-token head
-        only serves the training target (``predict_map``), so its outputs are empty here."""
+        """returns {'x_pt': (M,128), 'map_next_token_*': ...} like the reference (map_decoder.py:119-130): the token head's logits
+        and top-10 on the pt_pred_mask rows (infgen_map_token_head), token_idx[pt_target_mask], the all-True evaluation mask"""
         owner = getattr(self, '_owner', None)
         if owner is None:
             raise RuntimeError('InfGenMapDecoder.forward is driven through InfGenDecoder (shared packed weights)')
-        x_pt = owner()._run(data, map_only=True)
-        dev = x_pt.device
-        pt = data['pt_token']
-        tgt = torch.as_tensor(pt['token_idx'])[torch.as_tensor(pt['pt_target_mask']).bool()]
-        return {'x_pt': x_pt,
-                'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
-                'map_next_token_prob': torch.zeros(0, self.token_size, device=dev),
-                'map_next_token_idx_gt': tgt.to(dev),
-                'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=dev)}
+        x_pt, keys = owner()._run(data, map_only=True)
+        return {'x_pt': x_pt, **keys}

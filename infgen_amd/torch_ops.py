@@ -9,6 +9,7 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.radius_firstk(pos_q (Nq, 2), pos_x (Nx, 2), ptr_q, ptr_x, r, K)    -> idx (Nq, K) int32 (-1 padded), cnt (Nq,)
     torch.ops.infgen_hip.attn_layer(x_dst (N, 128), pack, off, cnt, src, rhat?, x_src?)     -> (N, 128)
     torch.ops.infgen_hip.token_state_head(x (N, 128), tok_pack, st_pack, token_size, want_logits) -> token, state, logits
+    torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
 
@@ -149,6 +150,23 @@ def _(x, tok_pack, st_pack, token_size, want_logits=False):
     n = x.shape[0]
     return (x.new_empty(n, dtype=torch.int32), x.new_empty(n, dtype=torch.int32),
             x.new_empty(n if want_logits else 0, token_size, dtype=torch.float32))
+
+
+@torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
+def map_token_head(x: torch.Tensor, rows: torch.Tensor, pack: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the map encoder's token_predict_head and its top-10 (map_decoder.py:119-121) on rows ``rows`` of ``x`` (N, 128): raw logits
+    (n, 1024) and the indices of the 10 most probable tokens (n, 10) int64, descending; ``pack`` = packing.pack_mlp_layer"""
+    if rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= x.shape[0]):
+        raise IndexError(f'map_token_head: rows must index the {x.shape[0]} rows of x')
+    if x.dim() != 2 or x.shape[1] != D or pack.numel() < 16768 + 129 * 1024:
+        raise ValueError('map_token_head takes x (N, 128) and the MLPLayer pack of a 1024-token head')
+    return _ops(x.device).map_token_head(_f32(x), rows.to(x.device, torch.int32).contiguous(), _f32(pack))
+
+
+@map_token_head.register_fake
+def _(x, rows, pack):
+    n = rows.shape[0]
+    return x.new_empty(n, 1024, dtype=torch.float32), x.new_empty(n, 10, dtype=torch.int64)
 
 
 @torch.library.custom_op('infgen_hip::mlp_layer', mutates_args=())
