@@ -42,6 +42,7 @@
  *   infgen_distance_to_nearest_object, infgen_time_to_collision, infgen_kinematic_features,
  *   infgen_distance_to_road_edge, infgen_placement_features   infgen/metrics/{interact,trajectory,map,placement}_features.py
  *   infgen_window_log_likelihood                       the scoring of LongMetric (infgen/metrics/compute_metrics.py:845-878)
+ *   infgen_bundle_scores                               the same for all rollouts of all scenarios of a batch (:891-1103)
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 / int32 / uint8) borrowed for the duration
  * of the call; outputs are pre-allocated by the caller; `stream` is a hipStream_t; nothing
@@ -523,6 +524,26 @@ int infgen_window_log_likelihood(const float* values, const unsigned char* valid
 int infgen_placement_features(const float* x, const float* y, const float* z, const int* state, const int* av_index,
                               int B, int N, int T, int enter_state, int exit_state, int* num_bos, int* num_eos,
                               float* bos_distance, float* eos_distance, void* stream);
+
+/* Scoring of a whole validation batch in one call (infgen/metrics/compute_metrics.py:891-1103 per scenario, over the rows of
+ * ALL its rollouts as compute_scenario_metrics_for_bundle concatenates them).  Bundle b = scenario * n_rollout + rollout; every
+ * per-object array is padded to [B][N][.] with n_rows [B] real rows per bundle (the rest is never read for a score): valid /
+ * collision bytes and the six 10 Hz features with row stride ld (T steps used), the two placement distances with row stride ld2
+ * and the two counts [B][.] (int64) with row stride ldn (T2 token steps used).  Windows of `size` steps every `step`, and of
+ * size / shift every step / shift at the token rate; both must give the same window count W.  table [11][136] floats, one row
+ * per field in the order linear_speed, linear_acceleration, angular_speed, angular_acceleration,
+ * distance_to_nearest_object, collision_indication, time_to_collision, num_placement, num_removement, distance_placement,
+ * distance_removement: num_bins (<= 64), min_val, max_val, metametric_weight, edges[65], logp[64], 3 unused.
+ * -> scalars [n_scenario][13] (the 11 likelihoods, metametric, simulated_collision_rate), lng [n_scenario][12][W] (the 11
+ * per-window likelihoods - the counts': rollout 0's -, metametric), long_rollout [B][2][W] (num_placement / num_removement per
+ * rollout), counters [3] (scenarios, scenarios with a placement score, with a removement score).  Fixed summation order. */
+int infgen_bundle_scores(const unsigned char* valid, const unsigned char* collision, const float* linear_speed,
+                         const float* linear_acceleration, const float* angular_speed, const float* angular_acceleration,
+                         const float* distance_to_nearest_object, const float* time_to_collision,
+                         const float* distance_placement, const float* distance_removement, const long long* num_placement,
+                         const long long* num_removement, const int* n_rows, const float* table, int n_scenario, int n_rollout,
+                         int N, int T, int ld, int T2, int ld2, int ldn, int size, int step, int shift, float* scalars,
+                         float* lng, float* long_rollout, int* counters, void* stream);
 
 /* Padded row layouts (insertion on: A_cap = agents + head-room rows per scene).  infgen_active_row_groups lists, in
  * ascending order, the 16-row groups of the [S][A_cap] layout with a row below n_agents[s] + margin (groups: capacity

@@ -163,6 +163,7 @@ SYMBOLS = {
     'infgen_distance_to_road_edge': (_i, [_p] * 9 + [_i] * 4 + [_p, _p, _p, _i, _f, _p, _p]),
     'infgen_window_log_likelihood': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
     'infgen_placement_features': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
+    'infgen_bundle_scores': (_i, [_p] * 14 + [_i] * 11 + [_p] * 5),
     'infgen_match_map_tokens': (_i, [_p, _p, _p, _i, _i, _p, _p]),
     'infgen_match_agent_tokens': (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _i, _p, _p, _p]),
     'infgen_attn_pre': (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p]),

@@ -798,6 +798,33 @@ extern "C" int infgen_placement_features(const float* x, const float* y, const f
   return check_launch("infgen_placement_features");
 }
 
+extern "C" int infgen_bundle_scores(const unsigned char* valid, const unsigned char* collision, const float* linear_speed,
+                                   const float* linear_acceleration, const float* angular_speed,
+                                   const float* angular_acceleration, const float* distance_to_nearest_object,
+                                   const float* time_to_collision, const float* distance_placement,
+                                   const float* distance_removement, const long long* num_placement,
+                                   const long long* num_removement, const int* n_rows, const float* table, int n_scenario,
+                                   int n_rollout, int N, int T, int ld, int T2, int ld2, int ldn, int size, int step, int shift,
+                                   float* scalars, float* lng, float* long_rollout, int* counters, void* stream) {
+  if (n_scenario <= 0) return 0;
+  const char* me = "infgen_bundle_scores";
+  if (n_rollout <= 0 || N <= 0) return fail(me, "need at least one rollout and one object row per bundle");
+  if (shift <= 0 || size <= 0 || step <= 0 || size % shift || step % shift) return fail(me, "size and step must be multiples of shift");
+  const int size2 = size / shift, step2 = step / shift;
+  if (size > T || size2 > T2) return fail(me, "a window is longer than the series");
+  if (ld < T || ld2 < T2 || ldn < T2) return fail(me, "row stride shorter than the row");
+  if ((long long)(T2 - 1) * shift >= T) return fail(me, "token columns reach beyond the steps");
+  const int W = (T - size) / step + 1;
+  if ((T2 - size2) / step2 + 1 != W) return fail(me, "window counts of the two rates differ");
+  BundleScoreArgs a{valid, collision, {linear_speed, linear_acceleration, angular_speed, angular_acceleration},
+                    distance_to_nearest_object, time_to_collision, distance_placement, distance_removement, num_placement,
+                    num_removement, n_rows, table, n_scenario, n_rollout, N, T, ld, T2, ld2, ldn, size, step, size2, step2, shift,
+                    W, scalars, lng, long_rollout, counters};
+  hipLaunchKernelGGL(k_bundle_field, dim3(BS_FIELDS, n_scenario), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_bundle_meta, dim3(n_scenario), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
 extern "C" int infgen_match_map_tokens(const float* traj_pos, const float* theta, const float* sample_pt, int P, int n_token,
                                       int* token_idx, void* stream) {
   if (P <= 0) return 0;

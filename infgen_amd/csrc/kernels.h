@@ -237,6 +237,19 @@ struct PlacementArgs {               // placement_features; arrays [B][N][T]
   float* bos_distance; float* eos_distance;            // [B][N][T]
 };
 
+struct BundleScoreArgs {             // k_bundle_field / k_bundle_meta (bundle_scores.hip); bundle b = scenario * R + rollout
+  const unsigned char* valid; const unsigned char* collision;          // [B][N][.] bytes, row stride ld
+  const float* feat[4]; const float* dist; const float* ttc;            // [B][N][.] floats, row stride ld (T columns used)
+  const float* d_place; const float* d_remove;                          // [B][N][.] row stride ld2 (T2 columns used)
+  const long long* n_place; const long long* n_remove;                  // [B][.] row stride ldn (T2 columns used)
+  const int* n_rows;                                                    // [B] object rows of a bundle (the rest is padding)
+  const float* table;                                                   // [11][BS_TABLE_STRIDE] packed histograms
+  int S, R, N, T, ld, T2, ld2, ldn, size, step, size2, step2, shift, W;   // windows: size / step at 10 Hz, size2 / step2 at the token rate
+  float* scalars; float* lng; float* long_rollout; int* counters;       // [S][13], [S][12][W], [B][2][W], [3]
+};
+constexpr int BS_TABLE_STRIDE = 136;  // nb, lo, hi, weight, edges[65], logp[64], pad
+constexpr int BS_FIELDS = 11;
+
 // k_mlpemb_h (mlp_h.hip): MLPEmbedding with K0 = 128 j on the fp16 split
 struct MlpEmbHArgs {
   const float* X; int ldx; int rows; int K0;
@@ -483,6 +496,8 @@ __global__ void k_kinematic(KinematicArgs a);
 __global__ void k_ttc(TtcArgs a);
 __global__ void k_placement(PlacementArgs a);
 __global__ void k_window_loglik(WindowLoglikArgs a);
+__global__ void k_bundle_field(BundleScoreArgs a);
+__global__ void k_bundle_meta(BundleScoreArgs a);
 __global__ void k_road_edge(RoadEdgeArgs a);
 template <int TERMS> __global__ void k_heads_h(HeadsArgs a);
 template <int TERMS> __global__ void k_map_head_h(MapHeadArgs a);     // mlp_h.hip

@@ -9,7 +9,7 @@ import torch
 from torch import Tensor
 
 from .compute_metrics import MetricFeatures
-from .scores import FIELDS, _field, _hist, compute_scenario_metrics
+from .scores import FIELDS, _field, _hist, compute_scenario_metrics, compute_scenario_metrics_batch, pack_score_table
 
 BUCKETS = {'kinematic': ['linear_speed', 'linear_acceleration', 'angular_speed', 'angular_acceleration'],
            'interactive': ['distance_to_nearest_object', 'collision_indication', 'time_to_collision'],
@@ -70,6 +70,7 @@ class LongMetric:
                 raise ValueError('LongMetric needs log_distributions or log_features (the reference loads total_features.pkl)')
             log_distributions = compute_log_distributions(metrics_config, log_features)
         self.log_distributions = log_distributions
+        self._score_tables = {}          # device -> pack_score_table (the batched scoring's histograms, built once)
         self.reset()
 
     def reset(self):
@@ -87,6 +88,20 @@ class LongMetric:
             self.sums[k] += float(scal.get(k, 0.0))
             if k in long:
                 self.longs[k].append(long[k].detach().cpu())
+
+    def update_rollouts(self, rollouts: Dict, road_edge_polylines=None):
+        """the reference's ``LongMetric.update(outputs)`` (:1309): every scenario of a rollouts dict (`format_rollouts`), each
+        scored over ALL its rollouts - batched features, one scoring call, ONE host copy, then the accumulation `update`
+        performs per scenario.  -> the `MetricFeaturesBatch` (device)"""
+        from .compute_metrics import compute_metric_features_batch
+        feats = compute_metric_features_batch(rollouts, road_edge_polylines)
+        dev = feats.valid.device
+        if dev not in self._score_tables:
+            self._score_tables[dev] = pack_score_table(self.metrics_config, self.log_distributions, dev)
+        for m in compute_scenario_metrics_batch(self.metrics_config, self.log_distributions, feats,
+                                                table=self._score_tables[dev], as_dicts=True):
+            self.update(metrics=m)
+        return feats
 
     def state(self) -> Dict:
         """a copy of the accumulated state (safe to pickle / merge elsewhere)"""

@@ -6,13 +6,15 @@ are one launch of `infgen_window_log_likelihood` per feature; what remains is ar
 `config`: the reference's SimAgentMetricsConfig (protobuf) or any object / dict with the same fields per feature
 (`histogram.{min_val, max_val, num_bins}` or `bernoulli`, `metametric_weight`).  `log_distributions`: per feature a
 torch.distributions.Categorical (as the reference's LogDistributions holds) or a tensor of log-probabilities."""
-from typing import Dict, Tuple
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
 
 from .. import _lib
-from .compute_metrics import SHIFT, MetricFeatures
+from . import compute_metrics as _cm
+from .compute_metrics import SHIFT, MetricFeatures, MetricFeaturesBatch
 
 N_SIMULATION_STEPS = 80          # waymo_open_dataset submission_specs
 KINEMATIC = ('linear_speed', 'linear_acceleration', 'angular_speed', 'angular_acceleration')
@@ -125,3 +127,112 @@ def compute_scenario_metrics(config, log_distributions, features: MetricFeatures
     long_out = {k + '_likelihood': long[k] for k in FIELDS}
     long_out['metametric'] = meta_long[None]
     return out, long_out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# all rollouts of all scenarios of a batch in one call: infgen_bundle_scores (csrc/bundle_scores.hip)
+TABLE_STRIDE = 136           # BS_TABLE_STRIDE of csrc/kernels.h: num_bins, min_val, max_val, weight, edges[65], logp[64], 3 unused
+N_SCALAR = len(FIELDS) + 2   # the likelihoods, metametric, simulated_collision_rate
+
+
+def pack_score_table(config, log_distributions, device) -> Tensor:
+    """the histograms of every field as the one table infgen_bundle_scores reads (include/infgen_hip.h): built once per
+    LongMetric.  The edges are the float32 linspace `window_log_likelihood` hands to the per-feature kernel."""
+    tab = torch.zeros(len(FIELDS), TABLE_STRIDE)
+    for i, k in enumerate(FIELDS):
+        lo, hi, nb, w = _hist(config, k)
+        if not 1 <= nb <= 64:
+            raise ValueError(f'{k}: num_bins must be in 1..64')
+        tab[i, 0], tab[i, 1], tab[i, 2], tab[i, 3] = nb, lo, hi, w
+        tab[i, 4:5 + nb] = torch.linspace(lo, hi, nb + 1).float()
+        tab[i, 69:69 + nb] = _logp(log_distributions, k, torch.device('cpu'))
+    return tab.to(device).contiguous()
+
+
+@dataclass(frozen=True)
+class BundleScores:
+    """device results of `compute_scenario_metrics_batch`: views of ONE buffer (`flat`), so one copy brings all to the host"""
+    scalars: Tensor              # [n_scenario][13]: FIELDS' likelihoods, metametric, simulated_collision_rate
+    long: Tensor                 # [n_scenario][12][n_window]: FIELDS' per-window likelihoods (the counts': rollout 0's), metametric
+    long_rollout: Tensor         # [n_scenario][n_rollout][2][n_window]: num_placement / num_removement per rollout
+    counters: Tensor             # [3] int32: scenarios, scenarios with a placement score, with a removement score
+    flat: Tensor
+
+    def to_dicts(self) -> List[Tuple[Dict[str, float], Dict[str, Tensor]]]:
+        """per scenario the `(scalars, per-window)` pair of `compute_scenario_metrics` - with the reference's bundle shapes: the
+        per-window values are (1, n_window), those of num_placement / num_removement (n_rollout, n_window) - after ONE host
+        copy for the whole batch"""
+        host = _cm.to_host(self.flat)
+        S, _, W = self.long.shape
+        R = self.long_rollout.shape[1]
+        a, b = S * N_SCALAR, S * N_SCALAR + S * (len(FIELDS) + 1) * W
+        scal = host[:a].reshape(S, N_SCALAR)
+        long = host[a:b].reshape(S, len(FIELDS) + 1, W)
+        per = host[b:b + S * R * 2 * W].reshape(S, R, 2, W)
+        out = []
+        for s in range(S):
+            sc = {k + '_likelihood': float(scal[s, i]) for i, k in enumerate(FIELDS)}
+            sc['metametric'] = float(scal[s, len(FIELDS)])
+            sc['simulated_collision_rate'] = float(scal[s, len(FIELDS) + 1])
+            lg = {k + '_likelihood': long[s, i][None].clone() for i, k in enumerate(FIELDS)}
+            lg['num_placement_likelihood'] = per[s, :, 0].clone()
+            lg['num_removement_likelihood'] = per[s, :, 1].clone()
+            lg['metametric'] = long[s, len(FIELDS)][None].clone()
+            out.append((sc, lg))
+        return out
+
+
+def _rows(t: Tensor):
+    """-> (tensor, row stride in elements) of a [B][N][n] or [B][n] array whose rows are dense and evenly spaced; a column slice
+    of a contiguous array qualifies as it is, anything else is copied"""
+    ld = t.stride(-2)
+    if not (t.stride(-1) == 1 and ld >= t.shape[-1] and (t.dim() == 2 or t.stride(0) == t.shape[1] * ld)):
+        t = t.contiguous()
+        ld = t.shape[-1]
+    return t, ld
+
+
+def _row_group(tensors, dtypes):
+    """arrays that share one row stride for the library (made dense if they come as views of differently shaped parents)
+    -> (tensors to keep alive, addresses, row stride)"""
+    ts = [t.view(torch.uint8) if t.dtype == torch.bool and d == torch.uint8 else t.to(d) for t, d in zip(tensors, dtypes)]
+    got = [_rows(t) for t in ts]
+    if len({ld for _, ld in got}) > 1:
+        got = [(t.contiguous(), t.shape[-1]) for t in ts]
+    return [t for t, _ in got], [t.data_ptr() for t, _ in got], got[0][1]
+
+
+@torch.no_grad()
+def compute_scenario_metrics_batch(config, log_distributions, features: MetricFeaturesBatch, size: int = N_SIMULATION_STEPS,
+                                   step: int = SHIFT, table: Optional[Tensor] = None, as_dicts: bool = False):
+    """`compute_scenario_metrics` with the reference's bundle semantics (compute_scenario_metrics_for_bundle, :891-1103: the
+    features of all rollouts of a scenario concatenated along the objects) for every scenario of a `MetricFeaturesBatch`, in
+    ONE library call whatever the number of scenarios and rollouts.  -> `BundleScores` (device tensors; nothing is read back),
+    or with ``as_dicts`` the per-scenario `(scalars dict, per-window dict)` list after one host copy.  ``table``: the result of
+    `pack_score_table` when the caller keeps it (LongMetric does)."""
+    f = features
+    dev = f.valid.device
+    if dev.type != 'cuda':
+        raise RuntimeError('compute_scenario_metrics_batch runs on the GPU only (no CPU fallback)')
+    if table is None:
+        table = pack_score_table(config, log_distributions, dev)
+    S, R = f.n_scenario, f.n_rollout
+    B, N, T = f.valid.shape
+    keep10, p10, ld = _row_group([f.valid, f.collision_per_step, f.linear_speed, f.linear_acceleration, f.angular_speed,
+                                  f.angular_acceleration, f.distance_to_nearest_object, f.time_to_collision],
+                                 [torch.uint8] * 2 + [torch.float32] * 6)
+    T2 = f.distance_placement.shape[-1]
+    keep_d, p_d, ld2 = _row_group([f.distance_placement, f.distance_removement], [torch.float32] * 2)
+    keep_n, p_n, ldn = _row_group([f.num_placement, f.num_removement], [torch.int64] * 2)
+    W = (T - size) // step + 1
+    n_scal, n_long, n_per = S * N_SCALAR, S * (len(FIELDS) + 1) * W, B * 2 * W
+    flat = torch.empty(n_scal + n_long + n_per + 3, dtype=torch.float32, device=dev)
+    base = flat.data_ptr()
+    n_rows = f.n_rows.to(torch.int32).contiguous()
+    _lib.check(_lib.load().infgen_bundle_scores(
+        *p10, *p_d, *p_n, _lib.ptr(n_rows), _lib.ptr(table), S, R, N, T, ld, T2, ld2, ldn, size, step, SHIFT, base,
+        base + 4 * n_scal, base + 4 * (n_scal + n_long), base + 4 * (n_scal + n_long + n_per), torch.cuda.current_stream(dev).cuda_stream), 'infgen_bundle_scores')
+    res = BundleScores(scalars=flat[:n_scal].view(S, N_SCALAR), long=flat[n_scal:n_scal + n_long].view(S, len(FIELDS) + 1, W),
+                       long_rollout=flat[n_scal + n_long:n_scal + n_long + n_per].view(S, R, 2, W),
+                       counters=flat[n_scal + n_long + n_per:].view(torch.int32), flat=flat)
+    return res.to_dicts() if as_dicts else res

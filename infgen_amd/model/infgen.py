@@ -86,6 +86,10 @@ class InfGen(nn.Module):
         self._long_metrics = None
         self._online_metric = self._save_validate_reuslts = self._plot_rollouts = False
         self.scenario_rollouts, self.scenario_features = [], []
+        # True: the online metric scores ALL n_rollout_close_val rollouts of every scenario (the reference's bundle,
+        # compute_metrics.py:903-916) through LongMetric.update_rollouts instead of the last rollout alone
+        self.score_all_rollouts = False
+        self.scenario_features_batch = None
 
     # ------------------------------------------------------------------ reference :188-215
     def set(self, mode: str = 'train'):
@@ -247,7 +251,17 @@ class InfGen(nn.Module):
             os.makedirs(self.save_path or '.', exist_ok=True)
             with open(rollouts_path, 'wb') as f:
                 pickle.dump({k: v.cpu() if torch.is_tensor(v) else v for k, v in formatted.items()}, f)
-        if self._online_metric:
+        if self._online_metric and self.score_all_rollouts:
+            # every rollout of every graph in one pass: the copies' dicts brought to one row layout (insertion gives each copy its
+            # own rows), stacked, then batched features and one scoring call
+            aligned, counts, per_copy = compute_metrics.align_rollouts(self.last_rollouts, return_counts=True)
+            every = compute_metrics.format_rollouts(data, aligned)
+            every['agent_count'], every['rollout_rows'] = counts, per_copy
+            if self._long_metrics is not None:
+                self.scenario_features_batch = self._long_metrics.update_rollouts(every)
+            else:
+                self.scenario_features_batch = compute_metrics.compute_metric_features_batch(every)
+        elif self._online_metric:
             sims = compute_metrics.output_to_rollouts(formatted)
             self.scenario_rollouts.extend(sims)
             feats = [compute_metrics.compute_metric_features(s.joint_scenes[0]) for s in sims]
@@ -259,3 +273,4 @@ class InfGen(nn.Module):
 
     def on_validation_start(self):
         self.scenario_rollouts, self.scenario_features = [], []
+        self.scenario_features_batch = None

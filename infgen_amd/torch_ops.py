@@ -12,6 +12,8 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
+    torch.ops.infgen_hip.bundle_scores(valid, collision, 4 kinematic, distance, ttc, 2 placement distances, 2 counts,
+                                       n_rows, table, n_scenario, size, step, shift)        -> scalars, long, long_rollout, counters
 
     torch.ops.infgen_hip.integrate_tokenise(token, state, type, pos, head, n_agents, ego, vocab, grid) -> pos', head', pred_traj, pred_head, grid, state'
     torch.ops.infgen_hip.decode_step(ctx_bytes, t, pos, head, state, token, grid, x, next_token, next_state) -> next_token, next_state
@@ -273,3 +275,46 @@ def decode_step(ctx: torch.Tensor, t: int, pos: torch.Tensor, head: torch.Tensor
 @decode_step.register_fake
 def _(ctx, t, pos, head, state, token, grid, x, next_token, next_state):
     return torch.empty_like(next_token), torch.empty_like(next_state)
+
+
+@torch.library.custom_op('infgen_hip::bundle_scores', mutates_args=())
+def bundle_scores(valid: torch.Tensor, collision: torch.Tensor, linear_speed: torch.Tensor, linear_acceleration: torch.Tensor,
+                  angular_speed: torch.Tensor, angular_acceleration: torch.Tensor, distance_to_nearest_object: torch.Tensor,
+                  time_to_collision: torch.Tensor, distance_placement: torch.Tensor, distance_removement: torch.Tensor,
+                  num_placement: torch.Tensor, num_removement: torch.Tensor, n_rows: torch.Tensor, table: torch.Tensor,
+                  n_scenario: int, size: int = 80, step: int = 5, shift: int = 5
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the realism scores of all rollouts of all scenarios of a batch (reference compute_scenario_metrics_for_bundle,
+    infgen/metrics/compute_metrics.py:891-1103) - ``infgen_bundle_scores``: per-object arrays (B, N, T) [placement distances
+    (B, N, T2), counts (B, T2)] with B = n_scenario * n_rollout bundles padded to N rows, ``n_rows`` (B,) real rows, ``table``
+    from ``infgen_amd.metrics.pack_score_table`` -> scalars (n_scenario, 13), per-window values (n_scenario, 12, W),
+    per-rollout count likelihoods (B, 2, W), counters (3,) int32"""
+    dev = valid.device
+    ops = _ops(dev)
+    B, N, T = valid.shape
+    T2 = distance_placement.shape[-1]
+    W = (T - size) // step + 1
+    u8 = lambda t: t.contiguous().to(torch.uint8)
+    byt = [u8(valid), u8(collision)]
+    flt = [_f32(t) for t in (linear_speed, linear_acceleration, angular_speed, angular_acceleration,
+                             distance_to_nearest_object, time_to_collision, distance_placement, distance_removement)]
+    cnt = [t.contiguous().long() for t in (num_placement, num_removement)]
+    rows, tab = n_rows.contiguous().to(torch.int32), _f32(table)
+    scal = torch.empty(n_scenario, 13, device=dev)
+    lng = torch.empty(n_scenario, 12, max(W, 0), device=dev)
+    per = torch.empty(B, 2, max(W, 0), device=dev)
+    counters = torch.zeros(3, device=dev, dtype=torch.int32)
+    P = _lib.ptr
+    _lib.check(ops.lib.infgen_bundle_scores(*(P(t) for t in byt + flt + cnt), P(rows), P(tab), int(n_scenario),
+                                            B // max(int(n_scenario), 1), N, T, T, T2, T2, T2, int(size), int(step), int(shift),
+                                            P(scal), P(lng), P(per), P(counters), ops.stream), 'infgen_bundle_scores')
+    return scal, lng, per, counters
+
+
+@bundle_scores.register_fake
+def _(valid, collision, linear_speed, linear_acceleration, angular_speed, angular_acceleration, distance_to_nearest_object,
+      time_to_collision, distance_placement, distance_removement, num_placement, num_removement, n_rows, table, n_scenario,
+      size=80, step=5, shift=5):
+    W = (valid.shape[2] - size) // step + 1
+    f = lambda *shape: valid.new_empty(*shape, dtype=torch.float32)
+    return f(n_scenario, 13), f(n_scenario, 12, W), f(valid.shape[0], 2, W), valid.new_empty(3, dtype=torch.int32)
