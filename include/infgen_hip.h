@@ -338,17 +338,19 @@ int infgen_decode_step(const InfgenRollout* r, int t, void* stream);
 int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream);
 
 /* reproducible stand-in for softmax -> topk(k) -> multinomial (agent_decoder.py:2162-2163,2194-2195): the k most
- * probable tokens, inverse-CDF over their probabilities with a caller-supplied uniform per row */
+ * probable tokens, inverse-CDF over their probabilities with a caller-supplied uniform per row; 1 <= k <= min(16, n), else refused */
 int infgen_sample_topk(const float* logits, int rows, int n, int k, const float* uniform, int* token, void* stream);
 
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
- *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854)
+ *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell
  *   infgen_point_edges      _build_a2sa_edge / _build_map2sa_edge for one query point per scene (:760-904):
  *                           first-K agents / map tokens (ascending index) within a radius of centre_row's pose
  *   infgen_insert_decide    seed heads -> enter / type / shape / cell, occupied-cell rejection, row append (:1883-1999);
  *                           inserted[s] = 1 row appended, 0 none, -1 the scene has no free row left (A_cap reached: the
- *                           caller must re-run with more head-room - nothing is dropped silently)
- *   infgen_insert_finalize  heading token + xy offset of the new row (:2060-2074) */
+ *                           caller must re-run with more head-room - nothing is dropped silently); a scene whose cell
+ *                           logits rank no cell (all NaN) stops without a row (inserted = 0, active = 0)
+ *   infgen_insert_finalize  heading token + xy offset of the new row (:2060-2074), for the scenes with inserted[s] > 0 only
+ *                           (0 and -1 appended no row: nothing of the scene is touched) */
 int infgen_occupancy(const InfgenRollout* r, int c, float* occ, void* stream);
 /* the same plus seed_agent_occ_embed of it (MLPLayer pack of infgen_amd.packing.pack_mlp_layer) -> emb [S][128], one launch */
 int infgen_occupancy_embed(const InfgenRollout* r, int c, float* occ, const float* embed_pack, float* emb, void* stream);
@@ -414,7 +416,10 @@ typedef struct InfgenInsertion {
 /* it: iteration of the step (0: map edges of the seed are built and the agents' edgeless chains are computed); riders != 0: the
  * previous iteration appended rows (prev_row / prev_mask); uniform: [S] for the cell draw when insert_k > 1 */
 int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform, void* stream);
-/* h_ready == 0: the agents' edgeless chain through motion layers 0..2 is computed first; riders != 0: pend_row / pend_mask ride */
+/* h_ready == 0: the agents' edgeless chain through motion layers 0..2 is computed first; riders != 0: pend_row / pend_mask ride.
+ * Must not be entered once a scene reported inserted[s] = -1 (host_dec): k_insert_cat and k_insert_finalize skip such a scene, but
+ * the point edges, the raw feature rows and the rider masks of this stage take any non-zero inserted[s] as "a row was appended" and
+ * would use the stale new_row[s].  The caller stops on -1 and re-runs with more head-room (infgen_amd/engine.py does). */
 int infgen_insert_heading(const InfgenRollout* r, const InfgenInsertion* I, int t, int h_ready, int riders, void* stream);
 
 /* ---- edge sets of the teacher-forced forward (reference agent_decoder.py:1104-1603) ----

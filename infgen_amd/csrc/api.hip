@@ -1141,6 +1141,7 @@ extern "C" int infgen_sample_topk(const float* logits, int rows, int n, int k, c
                                   void* stream) {
   if (rows <= 0) return 0;
   if (k < 1 || k > 16) return fail("infgen_sample_topk", "k must be in 1..16");
+  if (k > n) return fail("infgen_sample_topk", "k must not exceed n");      // (the k-th pick of fewer than k logits is no token)
   SampleArgs a{logits, rows, n, k, uniform, token};
   hipLaunchKernelGGL(k_sample_topk, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
   return check_launch("infgen_sample_topk");

@@ -886,7 +886,7 @@ __global__ __launch_bounds__(NT) void k_occupancy(OccupancyArgs a) {
   const int A = st.n_agents[s];
   for (int ag = threadIdx.x; ag < A; ag += NT) {
     const int g = st.grid[sidx(st, s, a.c, ag)];
-    if (g >= 0) o[g] = 1.f;
+    if (g >= 0 && g < a.grid_size) o[g] = 1.f;      // (like k_occupancy_embed: a cell outside the grid marks nothing)
   }
 }
 
@@ -1020,6 +1020,9 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   }
   }
   if (lane != 0) return;
+  // no cell (every logit NaN compares false, or sample_k exceeds the cells that can be ranked): the scene stops without a row -
+  // occ / grid_xy are never indexed with the search's "none" value
+  if (kGrid && (unsigned)bi >= (unsigned)a.grid_size) { a.inserted[s] = 0; a.active[s] = 0; return; }
   const int cell = kGrid ? bi : -1;
   const float* ls = a.lg_state + 2 * s;
   bool enter = ls[1] > ls[0];
@@ -1088,7 +1091,7 @@ template <bool kHeadToken, bool kOffset>
 __global__ __launch_bounds__(64) void k_insert_finalize(InsertFinalizeArgs a) {
   const SceneState& st = a.st;
   const int s = blockIdx.x;
-  if (threadIdx.x != 0 || !a.inserted[s]) return;
+  if (threadIdx.x != 0 || a.inserted[s] <= 0) return;      // (-1: no row was appended, new_row[s] is an older iteration's - like k_insert_cat)
   const int row = a.new_row[s];
   const int ag = row - s * st.A_cap;
   const float* lh = a.lg_heading + (size_t)s * a.n_heading;

@@ -1,0 +1,70 @@
+"""Device-side helpers shared by the operator-level GPU tests (test_edge_builders_gpu.py, test_insertion_ops_gpu.py): guarded
+device buffers, InfgenEdgeBuf / InfgenRollout blocks over device copies of a graph_ref block.  Not a test module and not a conftest;
+torch and the library are only needed by the callers, which are GPU tests."""
+import numpy as np
+import torch
+
+GUARD = 64
+SENT_I, SENT_F = -123456789, -7.25e30
+
+
+def dev():
+    return torch.device('cuda:0')
+
+
+def guarded(n, dtype, width=1):
+    """a device buffer of n (x width) elements plus a guard tail of GUARD (x width), all filled with a sentinel"""
+    t = torch.empty((n + GUARD) * width, device=dev(), dtype=dtype)
+    t.fill_(SENT_F if dtype == torch.float32 else SENT_I)
+    return t
+
+
+def guard_intact(t, n, width=1):
+    tail = t[n * width:]
+    return bool((tail == (SENT_F if t.dtype == torch.float32 else SENT_I)).all())
+
+
+class Edges:
+    """an InfgenEdgeBuf of `rows` destinations and `cap` edges, every array guarded"""
+
+    def __init__(self, rows, cap):
+        from infgen_amd import _lib
+        self.rows, self.cap = rows, cap
+        self.off, self.cnt = guarded(rows, torch.int32), guarded(rows, torch.int32)
+        self.src, self.raw = guarded(cap, torch.int32), guarded(cap, torch.float32, 4)
+        self.total = guarded(1, torch.int32)
+        self.buf = _lib.EdgeBuf()
+        self.buf.off, self.buf.cnt, self.buf.src, self.buf.raw = (t.data_ptr() for t in (self.off, self.cnt, self.src, self.raw))
+        self.buf.total, self.buf.cap = self.total.data_ptr(), cap
+
+    def host(self):
+        torch.cuda.synchronize()
+        assert guard_intact(self.off, self.rows) and guard_intact(self.cnt, self.rows) and guard_intact(self.total, 1)
+        assert guard_intact(self.src, self.cap) and guard_intact(self.raw, self.cap, 4), 'written at or beyond cap'
+        return (self.off[:self.rows].cpu().numpy(), self.cnt[:self.rows].cpu().numpy(), self.src[:self.cap].cpu().numpy(),
+                self.raw[:4 * self.cap].cpu().numpy().reshape(-1, 4), int(self.total[0].item()))
+
+
+def device_block(st, edges=None):
+    """InfgenRollout over device copies of a graph_ref block; -> (block, the tensors by name)"""
+    from infgen_amd import _lib
+    ten = {}
+    for k, v in st.items():
+        if isinstance(v, np.ndarray):
+            ten[k] = torch.from_numpy(np.ascontiguousarray(v)).to(dev())
+    b = _lib.Rollout()
+    b.S, b.A_cap, b.T, b.M_cap, b.W, b.ring, b.R = st['S'], st['A_cap'], st['T'], st['M_cap'], st['W'], st['ring'], st['R']
+    b.token_size, b.grid_size, b.num_layers = 2048, st['grid_size'], 1
+    b.r_map, b.r_agent = st['r_map'], st['r_agent']
+    for k in ('n_agents', 'n_map', 'av_index', 'pos', 'head', 'state', 'token', 'grid', 'tmask', 'imask', 'catflag', 'type', 'bos',
+              'map_pos', 'map_orient', 'map_scene', 'first_new', 'hv_ovr', 'grid_xy', 'pred_traj', 'pred_head', 'pred_state'):
+        if k in ten:
+            setattr(b, k, ten[k].data_ptr())
+    if edges:
+        b.et, b.em, b.ea = edges['t'].buf, edges['m'].buf, edges['a'].buf
+    return b, ten
+
+
+def lib_and_check():
+    from infgen_amd import _lib
+    return _lib.load(), _lib.check

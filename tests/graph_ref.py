@@ -1,0 +1,769 @@
+"""Plain references of the integer-and-geometry kernels (edge builders, insertion decisions, top-k sampling) and the input
+generators their tests share.  numpy only, float64, loops over scenes and destinations; written from the header comments of
+infgen_amd/csrc/edge_kernels.hip and the reference lines they cite (agent_decoder.py:540-904, 1852-2074, 2162-2195;
+map_decoder.py:91-93; attr_tokenizer.py:91-110) - nothing is shared with oracle/ or infgen_amd/.
+
+A scene block (`new_state`) is a dict of numpy arrays in the device layout of InfgenRollout (include/infgen_hip.h): the per-column
+arrays are [S][T][A_cap], the map side [Sm][M_cap]."""
+import math
+
+import numpy as np
+
+INVALID, VALID, ENTER, EXIT = 0, 1, 2, 3
+MOTION_GAP = HEADING_GAP = 1.0
+INVALID_MOTION = INVALID_HEAD = -2.0
+NUM_SEED_FEATURE = 10            # the last 10 rows of a scene are never temporal destinations
+A2A_CANDIDATES = 300 + 1         # radius_graph(max_num_neighbors=300): 301 candidates, self among them
+MAP_NBR = 5
+RULED_DIST, RULED_DTH = 1, 2        # edge_raw: which features of an edge are a gap rule's constants
+
+# Which edges exist is compared exactly, so no candidate may sit closer to a radius than this (relative, in d^2): fp32 rounding
+# of the device's dx*dx + dy*dy and r*r is ~1e-6 at a few hundred metres
+MARGIN = 1e-4
+# the same for the inverse-CDF draws: |u * sum(p) - cdf_j| / sum(p) over the boundaries that change the pick
+CDF_MARGIN = 1e-5
+
+# Largest error of a plain fp32 numpy evaluation of the raw edge features against float64 over the inputs of all generators below:
+# distance [m], bearing [rad], heading difference [rad], angles modulo 2 pi.  The figures are the ones tests/test_graph_ref_cpu.py
+# measures (and asserts not to be exceeded), rounded up in the fourth digit.  The device bar is four times the figure: atan2f /
+# sincosf are a few ulp, not correctly rounded, and a subtraction may be fused.
+FP32_ERR_DIST, FP32_ERR_BEARING, FP32_ERR_DTH = 3.907e-5, 3.595e-7, 5.922e-7
+BAR_DIST, BAR_BEARING, BAR_DTH = 4 * FP32_ERR_DIST, 4 * FP32_ERR_BEARING, 4 * FP32_ERR_DTH
+# occupancy embedding: fp32 numpy in the kernel's summation order (ascending cell) against float64 on gen_occupancy's pack
+FP32_ERR_OCC_EMB = 1.086e-6
+BAR_OCC_EMB = 4 * FP32_ERR_OCC_EMB
+# poses written by the insertion kernels, coordinates within +-200 m: 1e-5 m and 1e-6 rad against float64 - unless the fp32 numpy
+# evaluation already exceeds that, then four times its error.  It does for the position (half an ulp of 200 m is 7.6e-6 m, and the
+# rotation adds to it), it does not for the heading (half an ulp of pi is 1.2e-7 rad).
+FP32_ERR_INS_POS, FP32_ERR_INS_HEAD = 1.301e-5, 2.678e-7
+BAR_INS_POS = 1e-5 if FP32_ERR_INS_POS <= 1e-5 else 4 * FP32_ERR_INS_POS
+BAR_INS_HEAD = 1e-6 if FP32_ERR_INS_HEAD <= 1e-6 else 4 * FP32_ERR_INS_HEAD
+
+
+def wrap(a, f=np.float64):
+    """wrap_angle(a) = -pi + (a + pi) % (2 pi), python-style remainder"""
+    a = np.asarray(a, dtype=f)
+    return f(-math.pi) + np.mod(a + f(math.pi), f(2 * math.pi))
+
+
+def ang_err(a, b):
+    """|a - b| modulo 2 pi"""
+    d = np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)) % (2 * math.pi)
+    return np.minimum(d, 2 * math.pi - d)
+
+
+def first_k_within(centre_xy, cand_xy, r, k):
+    """torch_cluster.radius for one centre: the first k candidates in ascending index with d^2 < r^2 (strict), and the smallest
+    relative gap |d^2 - r^2| / r^2 over ALL candidates (inf without candidates)"""
+    cand = np.asarray(cand_xy, np.float64).reshape(-1, 2)
+    cx, cy = float(centre_xy[0]), float(centre_xy[1])
+    r2 = float(r) * float(r)
+    d2 = (cx - cand[:, 0]) ** 2 + (cy - cand[:, 1]) ** 2
+    hits = np.nonzero(d2 < r2)[0][:k]
+    gap = float(np.min(np.abs(d2 - r2)) / r2) if len(cand) else math.inf
+    return hits, gap
+
+
+def edge_raw(dst_pose, src_pose, dst_inv, src_inv, kind, hv=None, dt=0.0, f=np.float64):
+    """(|d|, bearing of d in the destination's heading frame, wrap(theta_src - theta_dst), dt) of the edges src -> dst, one
+    destination (x, y, theta) and arrays of sources; d = src - dst.  Gap rules by `kind`:
+      'temporal' / 'agent': source INVALID only: d = (-1, -1), dth = -1; destination INVALID only: d = (1, 1) (dth kept);
+                            both: d = (-2, -2), dth = -2
+      'map': destination INVALID: d = (1, 1), dth = 1       'point': none
+    hv: the destination's (cos, sin) when it is overridden.  Also returns per edge which features are a rule's constants, exact in
+    fp32: bit RULED_DIST the distance (sqrt 2 or 2 sqrt 2: the correctly rounded root of 2 or 8), bit RULED_DTH the heading difference."""
+    xd, yd, td = (f(v) for v in dst_pose)
+    xs, ys, ts = (np.atleast_1d(np.asarray(v, dtype=f)) for v in src_pose)
+    dx, dy = xs - xd, ys - yd
+    dth = wrap(ts - td, f)
+    s_inv = np.broadcast_to(np.asarray(src_inv, bool), xs.shape)
+    d_inv = bool(dst_inv)
+    ruled = np.zeros(xs.shape, np.int8)
+    if kind in ('temporal', 'agent'):
+        if not d_inv:
+            dx, dy, dth = (np.where(s_inv, f(v), x) for v, x in ((-MOTION_GAP, dx), (-MOTION_GAP, dy), (-HEADING_GAP, dth)))
+            ruled = np.where(s_inv, RULED_DIST | RULED_DTH, 0).astype(np.int8)
+        else:
+            dx = np.where(s_inv, f(INVALID_MOTION), f(MOTION_GAP)) + 0 * dx
+            dy = dx.copy()
+            dth = np.where(s_inv, f(INVALID_HEAD), dth)
+            ruled = np.where(s_inv, RULED_DIST | RULED_DTH, RULED_DIST).astype(np.int8)      # (destination only: dth is kept)
+    elif kind == 'map':
+        if d_inv:
+            dx, dy, dth = (np.full(xs.shape, f(v)) for v in (MOTION_GAP, MOTION_GAP, HEADING_GAP))
+            ruled = np.full(xs.shape, RULED_DIST | RULED_DTH, np.int8)
+    else:
+        assert kind == 'point'
+    c, s = (np.cos(td), np.sin(td)) if hv is None else (f(hv[0]), f(hv[1]))
+    dist = np.sqrt(dx * dx + dy * dy)
+    # (the dot product as a sum that starts from +0, like torch's: a source exactly at the destination has bearing +-0, never +-pi)
+    bearing = np.arctan2(c * dy - s * dx, (f(0) + c * dx) + s * dy)
+    raw = np.stack([dist, bearing, dth, np.full(xs.shape, f(dt))], axis=-1).astype(f)
+    return raw, ruled
+
+
+# ------------------------------------------------------------------------------------------------ scene blocks
+def new_state(S, A_cap, T, M_cap, Sm=None, W=12, ring=13, r_map=30.0, r_agent=60.0, G=0, R=5):
+    Sm = S if Sm is None else Sm
+    z = lambda *sh, dt=np.float32: np.zeros(sh, dt)
+    return dict(S=S, A_cap=A_cap, T=T, M_cap=M_cap, Sm=Sm, W=W, ring=ring, R=R, grid_size=G,
+                r_map=float(np.float32(r_map)), r_agent=float(np.float32(r_agent)),
+                n_agents=z(S, dt=np.int32), n_map=z(Sm, dt=np.int32), av_index=z(S, dt=np.int32),
+                pos=z(S, T, A_cap, 2), head=z(S, T, A_cap), state=z(S, T, A_cap, dt=np.int32), token=z(S, T, A_cap, dt=np.int32),
+                grid=z(S, T, A_cap, dt=np.int32), tmask=np.ones((S, T, A_cap), np.uint8), imask=np.ones((S, T, A_cap), np.uint8),
+                catflag=np.ones((S, T, A_cap), np.uint8), type=z(S, A_cap, dt=np.int32), bos=z(S, A_cap, dt=np.int32),
+                map_pos=z(Sm, M_cap, 2), map_orient=z(Sm, M_cap), map_scene=None, first_new=None, hv_ovr=None,
+                grid_xy=z(max(G, 1), 2), pred_traj=z(S * A_cap, R, 2), pred_head=z(S * A_cap, R), pred_state=z(S * A_cap, R))
+
+
+def take_scenes(st, scenes):
+    """the block of a subset of scenes (the map side is kept whole, reached through map_scene)"""
+    scenes = list(scenes)
+    out = dict(st)
+    out['S'] = len(scenes)
+    for k in ('n_agents', 'av_index', 'pos', 'head', 'state', 'token', 'grid', 'tmask', 'imask', 'catflag', 'type', 'bos',
+              'first_new', 'hv_ovr'):
+        if st[k] is not None:
+            out[k] = np.ascontiguousarray(st[k][scenes])
+    ms = st['map_scene'] if st['map_scene'] is not None else np.arange(st['S'], dtype=np.int32)
+    out['map_scene'] = np.ascontiguousarray(ms[scenes]).astype(np.int32)
+    return out
+
+
+def _map_slot(st, s):
+    return int(st['map_scene'][s]) if st['map_scene'] is not None else s
+
+
+def build_edges_ref(st, c, f=np.float64):
+    """the three CSR edge sets into column c, per destination row (S * A_cap lists per kind): {'t' | 'm' | 'a': [(src, raw, ruled)]}
+    with src in ascending order.  The lists are always chosen in float64; f is the type the features are evaluated in.
+      temporal  columns j in [c - W, c) with j >= bos and tmask[j], destinations < A - 10, dt = j - c, src = (j % ring) * rows + row
+      map       the first 5 tokens (ascending) within r_map; destination needs imask; src = slot * M_cap + m
+      agent     the first 301 rows (ascending, all rows < A, self among them) within r_agent, then self and imask == 0 sources
+                dropped; destination needs imask; src = s * A_cap + j
+    rows >= first_new[s] carry the head vector hv_ovr[s]."""
+    S, A_cap, W, ring, M_cap = st['S'], st['A_cap'], st['W'], st['ring'], st['M_cap']
+    rows = S * A_cap
+    empty = (np.zeros(0, np.int64), np.zeros((0, 4), f), np.zeros(0, np.int8))
+    out = {k: [empty] * rows for k in 'tma'}
+    for s in range(S):
+        A = int(st['n_agents'][s])
+        ms = _map_slot(st, s)
+        M = int(st['n_map'][ms])
+        P, Hd, St = st['pos'][s], st['head'][s], st['state'][s]
+        mp, mo = st['map_pos'][ms, :M], st['map_orient'][ms, :M]
+        for a in range(A):
+            row = s * A_cap + a
+            hv = None
+            if st['first_new'] is not None and a >= st['first_new'][s]:
+                hv = st['hv_ovr'][s]
+            dpose = (P[c, a, 0], P[c, a, 1], Hd[c, a])
+            d_inv = St[c, a] == INVALID
+            if a < A - NUM_SEED_FEATURE:
+                js = np.asarray([j for j in range(max(c - W, 0), c) if j >= st['bos'][s, a] and st['tmask'][s, j, a]], np.int64)
+                if len(js):
+                    raw, ruled = edge_raw(dpose, (P[js, a, 0], P[js, a, 1], Hd[js, a]), d_inv, St[js, a] == INVALID, 'temporal',
+                                          hv=hv, f=f)
+                    raw[:, 3] = (js - c).astype(f)
+                    out['t'][row] = ((js % ring) * rows + row, raw, ruled)
+            if not st['imask'][s, c, a]:
+                continue
+            m, _ = first_k_within(dpose[:2], mp, st['r_map'], MAP_NBR)
+            if len(m):
+                raw, ruled = edge_raw(dpose, (mp[m, 0], mp[m, 1], mo[m]), d_inv, False, 'map', hv=hv, f=f)
+                out['m'][row] = (ms * M_cap + m, raw, ruled)
+            j, _ = first_k_within(dpose[:2], P[c, :A], st['r_agent'], A2A_CANDIDATES)
+            j = j[(j != a) & (st['imask'][s, c, j] != 0)]
+            if len(j):
+                raw, ruled = edge_raw(dpose, (P[c, j, 0], P[c, j, 1], Hd[c, j]), d_inv, St[c, j] == INVALID, 'agent', hv=hv, f=f)
+                out['a'][row] = (s * A_cap + j, raw, ruled)
+    return out
+
+
+def build_edges_margin(st, c):
+    """smallest relative gap of any (destination, candidate) pair of the map and agent searches of column c"""
+    g = math.inf
+    for s in range(st['S']):
+        A = int(st['n_agents'][s])
+        ms = _map_slot(st, s)
+        M = int(st['n_map'][ms])
+        for a in range(A):
+            g = min(g, first_k_within(st['pos'][s, c, a], st['map_pos'][ms, :M], st['r_map'], 1)[1],
+                    first_k_within(st['pos'][s, c, a], st['pos'][s, c, :A], st['r_agent'], 1)[1])
+    return g
+
+
+def point_edges_ref(st, c, centre_row, active, exclude_centre, r_agent, k_agent, r_map, k_map, f=np.float64):
+    """one query point per scene (the pose of row centre_row[s] at column c): the first K agents / map tokens within a radius in
+    ascending index; among the agents the imask == 0 ones and (exclude_centre) the centre itself are dropped AFTER the cap.
+    -> {'a' | 'm': [(src, raw)] per scene}; inactive scenes have no edges"""
+    out = {'a': [], 'm': []}
+    for s in range(st['S']):
+        A, ms = int(st['n_agents'][s]), _map_slot(st, s)
+        M = int(st['n_map'][ms])
+        cr = int(centre_row[s])
+        P, Hd = st['pos'][s, c], st['head'][s, c]
+        pose = (P[cr, 0], P[cr, 1], Hd[cr])
+        on = active is None or active[s] != 0
+        j = first_k_within(pose[:2], P[:A], r_agent, k_agent)[0] if on else np.zeros(0, np.int64)
+        j = j[st['imask'][s, c, j] != 0]
+        if exclude_centre:
+            j = j[j != cr]
+        out['a'].append((s * st['A_cap'] + j, edge_raw(pose, (P[j, 0], P[j, 1], Hd[j]), False, False, 'point', f=f)[0]))
+        m = first_k_within(pose[:2], st['map_pos'][ms, :M], r_map, k_map)[0] if on else np.zeros(0, np.int64)
+        out['m'].append((ms * st['M_cap'] + m,
+                         edge_raw(pose, (st['map_pos'][ms, m, 0], st['map_pos'][ms, m, 1], st['map_orient'][ms, m]), False, False,
+                                  'point', f=f)[0]))
+    return out
+
+
+def map_graph_ref(n_map, pos, orient, radius, max_nbr, f=np.float64):
+    """radius_graph(loop=False, max_num_neighbors=max_nbr) per scene: per centre the first max_nbr + 1 tokens in ascending index
+    within the radius (self among them), self dropped.  -> ([(src, raw)] per row of [S][M_cap], smallest relative gap)"""
+    S, M_cap = pos.shape[:2]
+    out, gap = [], math.inf
+    for s in range(S):
+        M = int(n_map[s])
+        for i in range(M_cap):
+            if i >= M:
+                out.append((np.zeros(0, np.int64), np.zeros((0, 4), f)))
+                continue
+            m, g = first_k_within(pos[s, i], pos[s, :M], radius, max_nbr + 1)
+            cand = np.delete(pos[s, :M].astype(np.float64), i, axis=0)          # (the centre itself sits at distance 0)
+            gap = min(gap, first_k_within(pos[s, i], cand, radius, 1)[1])
+            m = m[m != i]
+            raw = edge_raw((pos[s, i, 0], pos[s, i, 1], orient[s, i]), (pos[s, m, 0], pos[s, m, 1], orient[s, m]), False, False,
+                           'point', f=f)[0]
+            out.append((s * M_cap + m, raw))
+    return out, gap
+
+
+def raw_errors(ref_lists, other_lists):
+    """largest per-feature difference of two evaluations of the same edge lists: (distance, bearing, heading difference)"""
+    e = np.zeros(3)
+    for a, b in zip(ref_lists, other_lists):
+        ra, rb = np.asarray(a[1], np.float64), np.asarray(b[1], np.float64)
+        if len(ra):
+            e = np.maximum(e, [np.abs(ra[:, 0] - rb[:, 0]).max(), ang_err(ra[:, 1], rb[:, 1]).max(), ang_err(ra[:, 2], rb[:, 2]).max()])
+    return e
+
+
+# ------------------------------------------------------------------------------------------------ insertion / sampling
+def occupancy_ref(st, c):
+    """[S][G] 0 / 1: the cells named by the grid tokens of the scene's first n_agents rows at column c (tokens outside [0, G) none)"""
+    G = st['grid_size']
+    occ = np.zeros((st['S'], G))
+    for s in range(st['S']):
+        for a in range(int(st['n_agents'][s])):
+            g = int(st['grid'][s, c, a])
+            if 0 <= g < G:
+                occ[s, g] = 1.0
+    return occ
+
+
+def mlp_layer_ref(x01, w0, b0, ln_g, ln_b, w3, b3, f=np.float64):
+    """MLPLayer of a 0 / 1 vector: Linear -> LayerNorm (biased variance, eps 1e-5) -> ReLU -> Linear; torch weight layout [out][in].
+    With f = float32 the sums run one term after the other in ascending input index, as the kernel's do."""
+    w0, b0, ln_g, ln_b, w3, b3 = (np.asarray(v, f) for v in (w0, b0, ln_g, ln_b, w3, b3))
+    h = np.zeros(w0.shape[0], f)
+    for g in np.nonzero(np.asarray(x01) != 0)[0]:
+        h = h + w0[:, g]
+    h = h + b0
+    mean = h.sum(dtype=f) / f(h.size)
+    d = h - mean
+    var = (d * d).sum(dtype=f) / f(h.size)
+    hv = np.maximum(d * (f(1.0) / np.sqrt(var + f(1e-5))) * ln_g + ln_b, f(0))
+    acc = np.zeros(w3.shape[0], f)
+    for k in range(w3.shape[1]):
+        acc = acc + hv[k] * w3[:, k]
+    return acc + b3
+
+
+def topk_pick(v, k, u):
+    """the k largest of v in (value descending, index ascending) order; p_j = exp(v_j - v_0); the pick is the first j with
+    u * sum(p) < cdf_j, else the last.  -> (index, smallest |u sum - cdf_j| / sum over the boundaries j < k - 1, the order)"""
+    v = np.asarray(v, np.float64)
+    order = np.lexsort((np.arange(v.size), -v))[:k]
+    if k == 1:
+        return int(order[0]), math.inf, order
+    p = np.exp(v[order] - v[order[0]])
+    cdf = np.cumsum(p)
+    x = float(u) * cdf[-1]
+    pick = k - 1
+    for j in range(k):
+        if x < cdf[j]:
+            pick = j
+            break
+    return int(order[pick]), float(np.min(np.abs(x - cdf[:-1])) / cdf[-1]), order
+
+
+def sample_topk_ref(logits, k, uniform):
+    toks, margins = zip(*[topk_pick(row, k, u)[:2] for row, u in zip(logits, uniform)])
+    return np.asarray(toks, np.int32), np.asarray(margins)
+
+
+def decode_pos(gxy, ego, f=np.float64):
+    """grid_xy[cell] @ Rot(theta_ego - pi / 2) + ego position, Rot(phi) = [[cos, sin], [-sin, cos]] (row vector on the left)"""
+    gx, gy, ex, ey, eh = f(gxy[0]), f(gxy[1]), f(ego[0]), f(ego[1]), f(ego[2])
+    phi = eh - f(math.pi / 2)
+    cs, sn = np.cos(phi), np.sin(phi)
+    return (gx * cs + gy * (-sn)) + ex, (gx * sn + gy * cs) + ey
+
+
+def decode_heading(idx, angle_interval, eh, f=np.float64):
+    """wrap((idx * interval - 180) / 360 * 2 pi + ego heading)"""
+    dec = (f(idx) * f(angle_interval) - f(180.0)) / f(360.0) * f(2 * math.pi)
+    return wrap(dec + f(eh), f)
+
+
+def new_decisions(S, G, n_heading=0):
+    z = lambda *sh, dt=np.float32: np.zeros(sh, dt)
+    return dict(lg_state=z(S, 2), lg_type=z(S, 3), shape=z(S, 3), lg_pos=z(S, G), occ=z(S, G), uniform=z(S),
+                active=np.ones(S, np.int32), n_new=z(S, dt=np.int32), inserted=np.full(S, 77, np.int32),
+                new_row=np.full(S, -5, np.int32), new_shape=np.full((S, 3), -9.0, np.float32), new_cell=np.full(S, -7, np.int32),
+                lg_heading=z(S, max(n_heading, 1)), offset=z(S, 2))
+
+
+def insert_decide_ref(st, dec, s, t, force_enter, max_new, sample_k=1, kgrid=True, r_seed=0.0):
+    """k_insert_decide for scene s, in place on float64 / integer copies of the block and the decision arrays (as_ref)"""
+    c, A_cap, G = 1 + t, st['A_cap'], st['grid_size']
+    if not dec['active'][s]:
+        dec['inserted'][s] = 0
+        return
+    cell = -1
+    if kgrid and np.all(np.isnan(dec['lg_pos'][s])):      # no cell can be ranked: the scene stops without a row
+        dec['inserted'][s], dec['active'][s] = 0, 0
+        return
+    if kgrid:
+        cell = topk_pick(dec['lg_pos'][s], max(sample_k, 1), dec['uniform'][s])[0]
+    enter = bool(dec['lg_state'][s, 1] > dec['lg_state'][s, 0]) or bool(force_enter)
+    ty = 0
+    for k in (1, 2):
+        if dec['lg_type'][s, k] > dec['lg_type'][s, ty]:
+            ty = k
+    occupied = kgrid and dec['occ'][s, cell] != 0
+    A = int(st['n_agents'][s])
+    if occupied and sample_k > 1:             # the iteration is spent, the next one draws again
+        dec['inserted'][s] = 0
+        return
+    ok = enter and not occupied and dec['n_new'][s] + 1 <= max_new
+    if ok and A >= A_cap:                     # no row left: reported, nothing touched
+        dec['inserted'][s], dec['active'][s] = -1, 0
+        return
+    if not ok:
+        dec['inserted'][s], dec['active'][s] = 0, 0
+        return
+    av = int(st['av_index'][s])
+    ego = (st['pos'][s, c, av, 0], st['pos'][s, c, av, 1], st['head'][s, c, av])
+    if kgrid:
+        nx, ny = decode_pos(st['grid_xy'][cell], ego)
+    else:
+        nx, ny = (math.tanh(dec['lg_pos'][s, k]) * r_seed + ego[k] for k in (0, 1))
+    row = s * A_cap + A
+    st['pos'][s, :, A] = 0.0
+    st['head'][s, :, A] = 0.0
+    st['state'][s, :, A], st['token'][s, :, A], st['grid'][s, :, A], st['tmask'][s, :, A] = INVALID, -1, -1, 1
+    st['imask'][s, :, A] = st['catflag'][s, :, A] = (np.arange(st['T']) >= c)
+    st['pos'][s, c, A] = (nx, ny)
+    st['head'][s, c, A] = ego[2]
+    st['state'][s, c, A], st['token'][s, c, A], st['grid'][s, c, A] = ENTER, -2, cell
+    st['type'][s, A], st['bos'][s, A] = ty, c
+    dec['new_shape'][s], dec['new_cell'][s] = dec['shape'][s], cell
+    if t > 0:
+        k = slice((t - 1) * 5, (t - 1) * 5 + 5)
+        st['pred_traj'][row, k] = (nx, ny)
+        st['pred_head'][row, k] = ego[2]
+        st['pred_state'][row, k] = float(ENTER)
+    st['n_agents'][s] = A + 1
+    dec['n_new'][s] += 1
+    dec['new_row'][s], dec['inserted'][s] = row, 1
+
+
+def insert_finalize_ref(st, dec, c, angle_interval, hv_ovr, head_token=True, xy_offset=True):
+    """k_insert_finalize, in place: for the scenes with inserted > 0 the heading (arg-max token, first index on ties, decoded and
+    wrapped - or tanh(lg[0]) * pi + ego heading, not wrapped) and the xy offset tanh(offset) * 2 of row new_row[s], and
+    hv_ovr[s] = (cos, sin) of the heading.  inserted 0 and -1: nothing."""
+    for s in range(st['S']):
+        if dec['inserted'][s] <= 0:
+            continue
+        a = int(dec['new_row'][s]) - s * st['A_cap']
+        eh = st['head'][s, c, int(st['av_index'][s])]
+        lh = dec['lg_heading'][s]
+        if head_token:
+            bi = 0
+            for k in range(1, lh.size):
+                if lh[k] > lh[bi]:
+                    bi = k
+            nh = float(decode_heading(bi, angle_interval, eh))
+        else:
+            nh = math.tanh(lh[0]) * math.pi + eh
+        st['head'][s, c, a] = nh
+        if xy_offset:
+            st['pos'][s, c, a] += np.tanh(dec['offset'][s].astype(np.float64)) * 2.0
+        hv_ovr[s] = (math.cos(nh), math.sin(nh))
+
+
+_F64_KEYS = ('pos', 'head', 'pred_traj', 'pred_head', 'pred_state')
+
+
+def as_ref(d):
+    """a deep copy of a block / decision dict for the in-place references: the float arrays they write in float64"""
+    return {k: (v.astype(np.float64) if k in _F64_KEYS else v.copy()) if isinstance(v, np.ndarray) else v for k, v in d.items()}
+
+
+# ------------------------------------------------------------------------------------------------ generators
+def _resample(rng, draw, offenders, tries=200):
+    """draw() -> points; offenders(points) -> indices of points within MARGIN of a radius; those are drawn again"""
+    pts = draw(None)
+    for _ in range(tries):
+        bad = offenders(pts)
+        if len(bad) == 0:
+            return pts
+        pts[bad] = draw(len(bad))
+    raise AssertionError('generator could not clear the radius margin')
+
+
+def _pairs_near(d2, r):
+    r2 = float(r) ** 2
+    return np.abs(d2 - r2) / r2 < 2 * MARGIN
+
+
+def _cloud_offenders(r, fixed=None, r_fixed=None, self_pairs=True):
+    """points within twice the margin of radius r of another point of the cloud (or of r_fixed of a fixed cloud)"""
+    def off(p):
+        q = p.astype(np.float64)
+        bad = np.zeros(len(q), bool)
+        if self_pairs and len(q) > 1:
+            d2 = ((q[:, None] - q[None]) ** 2).sum(-1)
+            near = _pairs_near(d2, r)
+            np.fill_diagonal(near, False)
+            bad |= np.triu(near, 1).any(0)        # (the later point of a pair moves)
+        if fixed is not None and len(fixed):
+            d2 = ((q[:, None] - fixed.astype(np.float64)[None]) ** 2).sum(-1)
+            bad |= _pairs_near(d2, r_fixed).any(1)
+        return np.nonzero(bad)[0]
+    return off
+
+
+MAP_GRAPH_CASES = {
+    # name: (n_map per scene, M_cap, radius, max_nbr, extent [m], what it is for)
+    'lds_1024': ([1024, 0, 1, 700], 1024, 12.0, 8, 200.0, 'positions in LDS, ragged n_map with 0 and 1, the cap reached'),
+    'global_1000': ([1000, 37, 1000], 1000, 12.0, 8, 200.0, 'global scan; a workgroup of 32 centres spans two scenes'),
+    'global_40': ([40, 0, 1, 17, 40], 40, 8.0, 4, 30.0, 'global scan; S * M_cap not a multiple of 32'),
+    'nomask_4160': ([4160, 4096], 4160, 12.0, 8, 400.0, 'more than 4096 tokens: no lane masks'),
+    'dense_200': ([600, 1024], 1024, 25.0, 200, 200.0, 'a cluster: more than 128 neighbours kept, the chunk path'),
+}
+
+
+def gen_map_graph(name, seed=0):
+    n_map, M_cap, radius, max_nbr, ext, _ = MAP_GRAPH_CASES[name]
+    rng = np.random.default_rng([seed, sum(map(ord, name))])
+    S = len(n_map)
+    radius = float(np.float32(radius))
+    pos = rng.uniform(-500, 500, (S, M_cap, 2)).astype(np.float32)          # (slots >= n_map hold values that must not be read)
+    orient = rng.uniform(-math.pi, math.pi, (S, M_cap)).astype(np.float32)
+    for s, M in enumerate(n_map):
+        def draw(n, M=M, s=s):
+            k = M if n is None else n
+            p = rng.uniform(-ext / 2, ext / 2, (k, 2))
+            if name == 'dense_200' and n is None:
+                nc = M // 2 + 60
+                ang, rad = rng.uniform(0, 2 * math.pi, nc), 9.0 * np.sqrt(rng.uniform(0, 1, nc))
+                p[:nc] = np.stack([rad * np.cos(ang), rad * np.sin(ang)], -1)
+                p = p[rng.permutation(k)]
+            elif name == 'dense_200':
+                p = rng.uniform(-9.0 / 1.5, 9.0 / 1.5, (k, 2))
+            return p.astype(np.float32)
+        if M:
+            pos[s, :M] = _resample(rng, draw, _cloud_offenders(radius))
+    return dict(n_map=np.asarray(n_map, np.int32), pos=pos, orient=orient, radius=radius, max_nbr=max_nbr, M_cap=M_cap, S=S)
+
+
+BUILD_EDGES_CASES = {
+    # name: (A per scene, A_cap, n_map per map slot, M_cap, map_scene, T, c, overrides, what it is for)
+    'cap32': ([1, 10, 11, 32], 32, [0, 3, 700], 704, [2, 1, 0, 2], 18, None, True, 'A = 1 / 10 / 11: the A - 10 rule; shared, permuted map slots'),
+    'cap256': (([1, 10, 11, 63, 64, 65, 200] * 19)[:130], 256, [0, 3, 700], 704, None, 18, 12, True,
+               '130 scenes: the 256-thread instantiation; scans over several 64-lane trips'),
+    'cap1024': ([700, 65], 1024, [4160, 700], 4160, [0, 1], 18, 11, True,
+                'a cluster with more than 301 rows in radius; map tokens scanned in global memory'),
+}
+
+
+def gen_build_edges(name, c=None, seed=0, overrides=None):
+    """a random block for infgen_build_edges: states with INVALID, imask / tmask zeros, bos inside the window, rows >= A filled with
+    plausible values that must not be read; the agent-agent and agent-map pairs of column c clear the margin"""
+    As, A_cap, n_map, M_cap, map_scene, T, c0, ovr, _ = BUILD_EDGES_CASES[name]
+    c = c0 if c is None else c
+    ovr = ovr if overrides is None else overrides
+    rng = np.random.default_rng([seed, sum(map(ord, name)), c])
+    S, Sm = len(As), len(n_map)
+    st = new_state(S, A_cap, T, M_cap, Sm=Sm, W=12, ring=13, r_map=30.0, r_agent=60.0)
+    st['n_agents'][:] = As
+    st['n_map'][:] = n_map
+    st['map_scene'] = (np.arange(S) % Sm if map_scene is None else np.asarray(map_scene)).astype(np.int32)
+    ext = 300.0
+    for m in range(Sm):
+        st['map_pos'][m] = rng.uniform(-ext / 2, ext / 2, (M_cap, 2)).astype(np.float32)
+        st['map_orient'][m] = rng.uniform(-math.pi, math.pi, M_cap).astype(np.float32)
+    st['pos'][:] = rng.uniform(-ext / 2, ext / 2, st['pos'].shape).astype(np.float32)
+    st['head'][:] = rng.uniform(-math.pi, math.pi, st['head'].shape).astype(np.float32)
+    st['state'][:] = rng.choice([INVALID, VALID, VALID, ENTER, EXIT, INVALID], st['state'].shape)
+    st['imask'][:] = rng.uniform(size=st['imask'].shape) > 0.15
+    st['tmask'][:] = rng.uniform(size=st['tmask'].shape) > 0.15
+    st['bos'][:] = np.where(rng.uniform(size=st['bos'].shape) < 0.5, 0, rng.integers(0, max(c, 1) + 1, st['bos'].shape))
+    st['av_index'][:] = [rng.integers(0, A) for A in As]
+    for s, A in enumerate(As):
+        ms = int(st['map_scene'][s])
+        fixed = st['map_pos'][ms, :n_map[ms]]
+
+        def draw(n, A=A):
+            k = A if n is None else n
+            p = rng.uniform(-ext / 2, ext / 2, (k, 2))
+            if A == 700:                          # the cluster: 400 rows within 15 m of each other, far inside r_agent
+                nc = 400 if n is None else k
+                ang, rad = rng.uniform(0, 2 * math.pi, nc), 15.0 * np.sqrt(rng.uniform(0, 1, nc))
+                p[:nc] = np.stack([rad * np.cos(ang), rad * np.sin(ang)], -1)
+                if n is None:
+                    p = p[rng.permutation(k)]
+            return p.astype(np.float32)
+        st['pos'][s, c, :A] = _resample(rng, draw, _cloud_offenders(st['r_agent'], fixed, st['r_map']))
+    if ovr:
+        st['first_new'] = np.asarray([A - min(3, A) if s % 2 == 0 else A_cap for s, A in enumerate(As)], np.int32)
+        ang = rng.uniform(-math.pi, math.pi, S)
+        st['hv_ovr'] = np.stack([np.cos(ang), np.sin(ang)], -1).astype(np.float32)
+    return st, c
+
+
+POINT_EDGES_CASES = {
+    # name: (r_agent, k_agent, r_map, k_map, hit rates of the agents / map tokens per scene, what it is for)
+    'heading_24_128': (10.0, 24, 10.0, 128, [(0.3, 0.6), (0.9, 0.9), (0.05, 0.1), (0.0, 0.0), (0.35, 0.55), (0.3, 0.6)],
+                       'production heading stage: the 24th agent in the second trip, the 128th token in the fourth'),
+    'seed_300_2048': (75.0, 300, 75.0, 2048, [(0.6, 0.75), (0.2, 0.3), (0.0, 0.0), (0.9, 0.95)],
+                      'production seed stage: K = 300 / 2048 over 700 agents / 3000 tokens'),
+}
+
+
+def gen_point_edges(name, seed=0):
+    """scenes of 700 agents / 3000 map tokens (two map slots, shared): every candidate sits either inside 0.8 r or outside 1.3 r of
+    the centre row's position, with a per-scene hit rate; one scene has no hit at all"""
+    ra, ka, rm, km, rates, _ = POINT_EDGES_CASES[name]
+    rng = np.random.default_rng([seed, sum(map(ord, name))])
+    S, Sm, A, M = len(rates), 2, 700, 3000
+    st = new_state(S, 1024, 3, 3008, Sm=Sm)
+    c = 1
+    st['n_agents'][:] = A
+    st['n_agents'][-1] = 650
+    st['n_map'][:] = [M, 2900]
+    st['map_scene'] = (np.arange(S) % Sm)[::-1].astype(np.int32).copy()
+    st['head'][:] = rng.uniform(-math.pi, math.pi, st['head'].shape).astype(np.float32)
+    st['map_orient'][:] = rng.uniform(-math.pi, math.pi, st['map_orient'].shape).astype(np.float32)
+    st['imask'][:] = rng.uniform(size=st['imask'].shape) > 0.2
+    st['av_index'][:] = 0
+    centre_row = rng.integers(1, 600, S).astype(np.int32)
+
+    def ring_points(n, rate, r):
+        hit = rng.uniform(size=n) < rate
+        rad = np.where(hit, r * 0.8 * np.sqrt(rng.uniform(0.0004, 1, n)), r * rng.uniform(1.3, 3.0, n))
+        ang = rng.uniform(0, 2 * math.pi, n)
+        return np.stack([rad * np.cos(ang), rad * np.sin(ang)], -1)
+    # the two map slots are shared by the scenes, so all centres sit at the origin of the map frame, rotated hit patterns apart
+    for m in range(Sm):
+        rate = max(r[1] for s, r in enumerate(rates) if st['map_scene'][s] == m)
+        st['map_pos'][m] = ring_points(st['M_cap'], rate, rm).astype(np.float32)
+    for s, (rate_a, rate_m) in enumerate(rates):
+        st['pos'][s, c] = ring_points(1024, rate_a, ra).astype(np.float32)
+        st['pos'][s, c, centre_row[s]] = 0.0
+        if rate_m == 0.0:                         # the scene without hits: its centre far from every map token and agent
+            st['pos'][s, c, centre_row[s]] = (5000.0, 5000.0)
+    return dict(st=st, c=c, centre_row=centre_row, r_agent=float(np.float32(ra)), k_agent=ka, r_map=float(np.float32(rm)), k_map=km)
+
+
+def gen_strict_radius():
+    """integer coordinates, on which fp32 is exact: points at (3, 4), (6, 8), (5, 12) around the origin are at exactly 5, 10, 13"""
+    pts = np.asarray([[0, 0], [3, 4], [6, 8], [5, 12], [100, 100]], np.float32)
+    cases = []
+    for i, r in ((1, 5.0), (2, 10.0), (3, 13.0)):
+        cases.append((np.float32(r), i, False))
+        cases.append((np.nextafter(np.float32(r), np.float32(np.inf)), i, True))
+    return pts, cases
+
+
+def gen_occupancy(G, seed=0, out_of_range=True):
+    """64 scenes of 0 .. 64 agents (A_cap 64): grid tokens with -1, duplicates, 0 and G - 1 - and, once the kernels guard, values
+    >= G; rows >= n_agents hold valid cells that must not be marked"""
+    rng = np.random.default_rng([seed, G])
+    S, A_cap = 64, 64
+    st = new_state(S, A_cap, 3, 32, G=G)
+    st['n_agents'][:] = np.arange(S)
+    st['n_agents'][5] = A_cap
+    st['n_agents'][7] = 0
+    g = rng.integers(0, G, (S, A_cap))
+    g[rng.uniform(size=g.shape) < 0.15] = -1
+    g[:, 3] = g[:, 2]
+    g[:, 10], g[:, 11] = 0, G - 1
+    if out_of_range:
+        g[:, 20], g[:, 21], g[30:, 22] = G, G + 5, 1 << 20
+    g[9, :] = -1                                  # a scene of 9 agents without an occupied cell
+    st['grid'][:, 1] = g
+    st['grid'][:, 0] = rng.integers(0, G, (S, A_cap))            # (another column: not read)
+    return st, 1
+
+
+def gen_mlp_layer(G, seed=0):
+    rng = np.random.default_rng([seed, G, 17])
+    p = 'occ'
+    return {f'{p}.mlp.0.weight': (rng.standard_normal((128, G)) / 8).astype(np.float32),
+            f'{p}.mlp.0.bias': rng.standard_normal(128).astype(np.float32) * 0.1,
+            f'{p}.mlp.1.weight': (1 + 0.1 * rng.standard_normal(128)).astype(np.float32),
+            f'{p}.mlp.1.bias': rng.standard_normal(128).astype(np.float32) * 0.1,
+            f'{p}.mlp.3.weight': (rng.standard_normal((128, 128)) / 11).astype(np.float32),
+            f'{p}.mlp.3.bias': rng.standard_normal(128).astype(np.float32) * 0.1}, p
+
+
+def gen_sample_topk(rows, n, k, seed=0):
+    """logits on a 0.25 grid in [-4, 4] (ties inside and across the k-th place), -inf entries (fewer than n - k), rows whose k
+    largest are all equal (probabilities exactly 1: u = j / k lands on a partial sum exactly), u = 0 and u = 1 - 2^-24; the other
+    uniforms are drawn until they clear CDF_MARGIN"""
+    rng = np.random.default_rng([seed, rows, n, k])
+    lg = (rng.integers(-16, 17, (rows, n)) * 0.25).astype(np.float32)
+    u = rng.uniform(0, 1, rows).astype(np.float32)
+    kinds = []
+    for r in range(rows):
+        kind = ('ties', 'zero', 'one', 'random', 'neg_inf', 'tied_kth')[r % 6] if rows > 1 else 'ties'
+        if kind == 'ties':                        # the k largest all equal 5.0, at random places
+            lg[r, rng.choice(n, k, replace=False)] = 5.0
+            u[r] = np.float32((r // 6) % k) / np.float32(k) if k in (1, 2, 16) else u[r]
+        elif kind == 'zero':
+            u[r] = 0.0
+        elif kind == 'one':
+            u[r] = np.float32(1.0) - np.float32(2.0 ** -24)
+        elif kind == 'neg_inf':
+            lg[r, rng.choice(n, max(min(n - k - 1, n // 3), 0), replace=False)] = -np.inf
+        elif kind == 'tied_kth':                  # k + 2 copies of the k-th value: the tie runs across the k-th place
+            lg[r, rng.choice(n, min(k + 2, n), replace=False)] = 4.5
+        if kind in ('random', 'neg_inf', 'tied_kth'):
+            for _ in range(100):
+                if topk_pick(lg[r], k, u[r])[1] > CDF_MARGIN:
+                    break
+                u[r] = np.float32(rng.uniform(0, 1))
+        kinds.append(kind)
+    return lg, u, kinds
+
+
+INSERT_DECIDE_BRANCHES = [
+    # name, expected (inserted, active after) without force_enter (insert_decide_expect for the rest)
+    ('inactive', 0, 0), ('enter_below', 0, 0), ('enter_equal', 0, 0), ('enter_above', 1, 1), ('force_enter', 1, 1),
+    ('type_tie_01', 1, 1), ('type_tie_12', 1, 1), ('occupied', 0, None), ('max_new_reached', 0, 0), ('rows_full', -1, 0),
+    ('cell_tie', 1, 1), ('u_zero', 1, 1), ('u_partial_sum', 1, 1), ('u_one', 1, 1), ('nan_logits', 0, 0), ('ego_not_first', 1, 1),
+]
+# the calls of the GPU test, each of which the CPU test runs through the generator and the reference as well:
+# (sample_k, through infgen_insert_decide_topk?, t, force_enter)
+INSERT_DECIDE_CASES = [(1, False, 0, 0), (1, False, 2, 0), (1, True, 2, 1), (2, True, 0, 0), (16, True, 2, 0), (16, True, 0, 1)]
+
+
+def insert_decide_expect(name, sample_k, force_enter):
+    """(inserted, active afterwards) of a named branch: force_enter makes the enter-logit rows enter (strict > otherwise, so equal
+    logits do not); an occupied cell stops the scene when the choice is greedy and spends the iteration when it is sampled"""
+    ins, act = {b[0]: b[1:] for b in INSERT_DECIDE_BRANCHES}[name]
+    if name in ('enter_below', 'enter_equal') and force_enter:
+        ins, act = 1, 1
+    if name == 'occupied':
+        act = 1 if sample_k > 1 else 0
+    return ins, act
+
+
+def gen_insert_decide(G, grid_xy, sample_k, t, force_enter=0, seed=0):
+    """one scene per named branch of k_insert_decide (INSERT_DECIDE_BRANCHES; with force_enter the enter-logit rows all enter).
+    A_cap = 32, T = 4; every array of a scene is filled with values that a reset must replace; poses within +-200 m.
+    -> (block, decisions, names, max_new)"""
+    rng = np.random.default_rng([seed, sample_k, t, force_enter])
+    names = [b[0] for b in INSERT_DECIDE_BRANCHES]
+    S, A_cap, T, max_new = len(names), 32, 4, 10
+    c = 1 + t
+    st = new_state(S, A_cap, T, 32, G=G, R=15)
+    st['grid_xy'] = np.asarray(grid_xy, np.float32).copy()
+    st['pos'][:] = rng.uniform(-200, 200, st['pos'].shape).astype(np.float32)
+    st['head'][:] = rng.uniform(-math.pi, math.pi, st['head'].shape).astype(np.float32)
+    for k, hi in (('state', 4), ('token', 2048), ('grid', G), ('type', 3), ('bos', T)):
+        st[k][:] = rng.integers(0, hi, st[k].shape)
+    for k in ('tmask', 'imask', 'catflag'):
+        st[k][:] = rng.integers(0, 2, st[k].shape)
+    for k in ('pred_traj', 'pred_head', 'pred_state'):
+        st[k][:] = rng.uniform(-5, 5, st[k].shape).astype(np.float32)
+    st['n_agents'][:] = rng.integers(3, 20, S)
+    st['av_index'][:] = 0
+    dec = new_decisions(S, G)
+    dec['lg_pos'][:] = (rng.integers(-12, 13, (S, G)) * 0.25).astype(np.float32)
+    dec['lg_type'][:] = rng.standard_normal((S, 3)).astype(np.float32)
+    dec['shape'][:] = rng.uniform(0.5, 5, (S, 3)).astype(np.float32)
+    dec['lg_state'][:] = (0.0, 1.0)
+    dec['n_new'][:] = rng.integers(0, 5, S)
+    dec['uniform'][:] = rng.uniform(0, 1, S).astype(np.float32)
+    k = max(sample_k, 1)
+    for s, name in enumerate(names):
+        top = rng.choice(G, 16, replace=False)
+        dec['lg_pos'][s, top] = 4.0 + 0.5 * rng.permutation(16).astype(np.float32)      # 16 distinct leaders
+        if name == 'inactive':
+            dec['active'][s] = 0
+        elif name == 'enter_below':
+            dec['lg_state'][s] = (0.5, 0.25)
+        elif name == 'enter_equal':
+            dec['lg_state'][s] = (0.5, 0.5)
+        elif name == 'type_tie_01':
+            dec['lg_type'][s] = (1.5, 1.5, 0.0)
+        elif name == 'type_tie_12':
+            dec['lg_type'][s] = (0.0, 1.5, 1.5)
+        elif name == 'max_new_reached':
+            dec['n_new'][s] = max_new
+        elif name == 'rows_full':
+            st['n_agents'][s] = A_cap
+        elif name in ('cell_tie', 'u_partial_sum', 'occupied'):
+            dec['lg_pos'][s, top] = 9.0           # the 16 leaders all equal: probabilities exactly 1, the lowest index first
+            if name == 'u_partial_sum':
+                dec['uniform'][s] = np.float32(k // 2) / np.float32(k)
+        elif name == 'u_zero':
+            dec['uniform'][s] = 0.0
+        elif name == 'u_one':
+            dec['uniform'][s] = np.float32(1.0) - np.float32(2.0 ** -24)
+        elif name == 'nan_logits':
+            dec['lg_pos'][s] = np.nan
+        elif name == 'ego_not_first':
+            st['av_index'][s] = st['n_agents'][s] - 1
+        if name not in ('u_zero', 'u_one', 'u_partial_sum', 'nan_logits'):
+            for _ in range(100):
+                if topk_pick(dec['lg_pos'][s], k, dec['uniform'][s])[1] > CDF_MARGIN:
+                    break
+                dec['uniform'][s] = np.float32(rng.uniform(0, 1))
+        # occupancy: a few cells, never the one this scene picks - except in the 'occupied' scene, where it is exactly that one
+        dec['occ'][s, rng.choice(G, 12, replace=False)] = 1.0
+        if name != 'nan_logits':
+            cell = topk_pick(dec['lg_pos'][s], k, dec['uniform'][s])[0]
+            dec['occ'][s, cell] = 1.0 if name == 'occupied' else 0.0
+    return st, dec, names, max_new
+
+
+def gen_insert_finalize(seed=0, angle_interval=3.0):
+    """scenes after a decide: inserted in {1, 0, -1}; heading logits with ties at the maximum; a decoded heading whose sum with the
+    ego heading crosses +-pi; offsets with tanh saturating.  new_row of the 0 / -1 scenes names an existing row that must stay."""
+    rng = np.random.default_rng([seed, 99])
+    n_heading = int(360.0 / angle_interval)
+    S, A_cap, T, c = 12, 32, 4, 2
+    st = new_state(S, A_cap, T, 32)
+    st['pos'][:] = rng.uniform(-200, 200, st['pos'].shape).astype(np.float32)
+    st['head'][:] = rng.uniform(-math.pi, math.pi, st['head'].shape).astype(np.float32)
+    st['n_agents'][:] = rng.integers(4, 20, S)
+    st['av_index'][:] = rng.integers(0, 3, S)
+    dec = new_decisions(S, 1, n_heading)
+    dec['lg_heading'][:] = (rng.integers(-8, 9, (S, n_heading)) * 0.25).astype(np.float32)
+    dec['offset'][:] = rng.standard_normal((S, 2)).astype(np.float32)
+    dec['inserted'][:] = [1, 1, 0, -1, 1, 1, 1, 0, -1, 1, 1, 1]
+    dec['new_row'][:] = np.arange(S) * A_cap + st['n_agents'] - 1
+    st['head'][0, c, st['av_index'][0]] = 3.0      # + decoded (119 * 3 - 180) deg = 3.09 rad: beyond pi
+    dec['lg_heading'][0, 119] = 7.0
+    st['head'][1, c, st['av_index'][1]] = -3.0     # + decoded (0 * 3 - 180) deg = -pi: below -pi
+    dec['lg_heading'][1, 0] = 7.0
+    dec['lg_heading'][4, [17, 40, 90]] = 6.0       # ties at the maximum: the first index wins
+    dec['lg_heading'][5, :] = 1.0                  # all equal: index 0
+    dec['offset'][6] = (30.0, -30.0)               # tanh saturates at +-1
+    dec['offset'][9] = (1e-4, 0.0)
+    return st, dec, c, angle_interval, n_heading
