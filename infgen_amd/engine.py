@@ -20,12 +20,12 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, packing
+from . import _lib, packing, scene_setup
+from .scene_setup import EVAL_SHAPE, INVALID_SHAPE
 from .synth import INVALID, VALID, ENTER, EXIT, AGENT_SHAPE, RolloutConfig
 
 D = 128
 SEED_TYPE = 3
-INVALID_SHAPE = 0.1
 
 
 def _round_up(x: int, m: int) -> int:
@@ -629,15 +629,13 @@ class RolloutEngine:
         self.force_enter = force_enter
 
         # ------------------------------------------------ host-side scene setup
-        self._stacked = None
         self._hosts_light = False
         if batch is None:
-            hosts = self._replicate(self._setup_scenes(scenes))
-            self.hosts = hosts
-            amax = max(h['A'] for h in hosts)
-            mmax = max(h['M'] for h in hosts)
+            hosts, staged = self._setup_scenes(scenes)
+            self.hosts = self._replicate(hosts)
+            amax, mmax = int(staged['A'].max()), int(staged['M'].max())
         else:                                  # (the padded fill arrays below; the ingest kernel writes the scenes)
-            hosts, self.hosts = [], None
+            self.hosts, staged = None, None
             amax, mmax = batch_layout['amax'], batch_layout['mmax']
         self._amax0 = amax
         head = 0
@@ -657,7 +655,7 @@ class RolloutEngine:
             # 64 scenes 25.9 ms with and without it (the step is its kernels' dependency chains, not launch overhead)
             self.use_graph = str(self.flags['graph']) == '1' and not self.insertion
 
-        arr = self._map_side(self._scene_arrays(hosts))
+        arr = self._scene_arrays(staged)
         t = lambda a: torch.from_numpy(a).to(dev)
         for k in self._SCENE_ARRAYS:
             setattr(self, k, t(arr[k]))
@@ -746,21 +744,27 @@ class RolloutEngine:
 
     def _replicate(self, hosts0):
         """the per-scene host dicts of the agent-side batch: scene i's copies are adjacent (the dicts are shared, read-only)"""
-        if self.copies == 1:
-            return hosts0
-        self._stacked = None                   # (the stacked one-shape arrays describe the S0 distinct scenes)
-        return [h for h in hosts0 for _ in range(self.copies)]
+        return hosts0 if self.copies == 1 else [h for h in hosts0 for _ in range(self.copies)]
 
-    def _map_side(self, arr):
-        """the map-side arrays of a batch with copies: one entry per DISTINCT scene (every copies-th of the replicated batch)"""
-        if self.copies > 1:
-            for k in self._MAP_SIDE:
-                arr[k] = np.ascontiguousarray(arr[k][::self.copies])
-        return arr
+    def _setup_scenes(self, scenes):
+        """host scenes -> (the per-scene host dicts: A / M / av / filt and numpy views of the batch arrays cut to the scene's
+        agents and map tokens; the batch arrays themselves, [S0, max A, T, ...] / [S0, max M, ...] / A, M, av [S0], the rows
+        beyond a scene's count holding the padding values): ``scene_setup`` for all scenes at once"""
+        ag, av, A, filts = scene_setup.stage_agents(scenes, self.cfg, self.cfg.num_columns)
+        a = {k: v.numpy() for k, v in scene_setup.setup_agents(ag, av, self.cfg, self.cfg.num_columns, A).items()}
+        m, M = scene_setup.stage_map(scenes)
+        hosts = [dict({k: v[s, :A[s]] for k, v in a.items()}, **{k: v[s, :M[s]] for k, v in m.items()},
+                      A=int(A[s]), M=int(M[s]), av=int(av[s]), filt=filts[s]) for s in range(len(scenes))]
+        return hosts, dict(a, **m, A=A, M=M, av=av.numpy())
 
-    def _scene_arrays(self, hosts) -> Dict[str, np.ndarray]:
-        """the padded [S][T][A_cap] / [S][M_cap] arrays of a batch (section 4 of DESIGN.md) from the per-scene host dicts"""
-        S, T, A_cap, M_cap = self.S, self.T, self.A_cap, self.M_cap
+    def _setup_scene(self, scene) -> Dict[str, np.ndarray]:
+        """the host dict of one scene (a batch of one through ``_setup_scenes``)"""
+        return self._setup_scenes([scene])[0][0]
+
+    def _scene_arrays(self, k) -> Dict[str, np.ndarray]:
+        """the padded [S][T][A_cap] / [S0][M_cap] arrays of a batch (section 4 of DESIGN.md) from the batch arrays of
+        ``_setup_scenes`` (None: the padding alone); with copies, every scene's agent side is repeated, its map side is not"""
+        S, S0, T, A_cap, M_cap = self.S, self.S // self.copies, self.T, self.A_cap, self.M_cap
 
         def zeros(shape, dtype):
             return np.zeros(shape, dtype=dtype)
@@ -770,44 +774,52 @@ class RolloutEngine:
                  imask=zeros((S, T, A_cap), np.uint8), catflag=zeros((S, T, A_cap), np.uint8),
                  atype=zeros((S, A_cap), np.int32), bos=zeros((S, A_cap), np.int32),
                  _shape10=np.full((S, A_cap, 3), INVALID_SHAPE, np.float32),
-                 n_agents=zeros((S,), np.int32), n_map=zeros((S,), np.int32), av=zeros((S,), np.int32),
-                 map_pos=zeros((S, M_cap, 2), np.float32), map_orient=zeros((S, M_cap), np.float32),
-                 map_tok=zeros((S, M_cap), np.int64), map_type=zeros((S, M_cap), np.int64),
-                 map_pl=zeros((S, M_cap), np.int64), map_light=zeros((S, M_cap), np.int64))
-        k = getattr(self, '_stacked', None)
-        if k is not None and len(hosts) == S:                      # one-shape batch: the stacked arrays of _setup_scenes_stacked
-            A, M = k['A'], k['M']
-            a['n_agents'][:], a['n_map'][:], a['av'][:] = A, M, k['av']
-            a['pos'][:, :, :A] = k['pos'].transpose(0, 2, 1, 3); a['head'][:, :, :A] = k['head'].transpose(0, 2, 1)
-            for dst, src in (('state', 'state'), ('token', 'token'), ('gridtok', 'grid'), ('tmask', 'tmask'), ('imask', 'imask'),
-                             ('catflag', 'catflag')):
-                a[dst][:, :, :A] = k[src].transpose(0, 2, 1)
-            a['atype'][:, :A] = k['type']; a['bos'][:, :A] = k['bos']; a['_shape10'][:, :A] = k['shape10']
-            a['map_pos'][:, :M] = k['map_pos']; a['map_orient'][:, :M] = k['map_orient']
-            a['map_tok'][:, :M] = k['map_tok']; a['map_type'][:, :M] = k['map_type']
-            a['map_pl'][:, :M] = k['map_pl']; a['map_light'][:, :M] = k['map_light']
+                 n_agents=zeros((S,), np.int32), n_map=zeros((S0,), np.int32), av=zeros((S,), np.int32),
+                 map_pos=zeros((S0, M_cap, 2), np.float32), map_orient=zeros((S0, M_cap), np.float32),
+                 map_tok=zeros((S0, M_cap), np.int64), map_type=zeros((S0, M_cap), np.int64),
+                 map_pl=zeros((S0, M_cap), np.int64), map_light=zeros((S0, M_cap), np.int64))
+        if k is None:
             return a
-        for s, h in enumerate(hosts):
-            A, M = h['A'], h['M']
-            a['n_agents'][s], a['n_map'][s], a['av'][s] = A, M, h['av']
-            a['pos'][s, :, :A] = h['pos'].transpose(1, 0, 2); a['head'][s, :, :A] = h['head'].T
-            a['state'][s, :, :A] = h['state'].T; a['token'][s, :, :A] = h['token'].T; a['gridtok'][s, :, :A] = h['grid'].T
-            a['tmask'][s, :, :A] = h['tmask'].T; a['imask'][s, :, :A] = h['imask'].T; a['catflag'][s, :, :A] = h['catflag'].T
-            a['atype'][s, :A] = h['type']; a['bos'][s, :A] = h['bos']; a['_shape10'][s, :A] = h['shape10']
-            a['map_pos'][s, :M] = h['map_pos']; a['map_orient'][s, :M] = h['map_orient']
-            a['map_tok'][s, :M] = h['map_tok']; a['map_type'][s, :M] = h['map_type']
-            a['map_pl'][s, :M] = h['map_pl']; a['map_light'][s, :M] = h['map_light']
+        rep = (lambda x: x) if self.copies == 1 else (lambda x: np.repeat(x, self.copies, axis=0))
+        A, M = k['pos'].shape[1], k['map_pos'].shape[1]
+        a['n_agents'][:], a['n_map'][:], a['av'][:] = rep(k['A']), k['M'], rep(k['av'])
+        a['pos'][:, :, :A] = rep(k['pos']).transpose(0, 2, 1, 3)
+        for dst, src in (('head', 'head'), ('state', 'state'), ('token', 'token'), ('gridtok', 'grid'), ('tmask', 'tmask'),
+                         ('imask', 'imask'), ('catflag', 'catflag')):
+            a[dst][:, :, :A] = rep(k[src]).transpose(0, 2, 1)
+        a['atype'][:, :A] = rep(k['type']); a['bos'][:, :A] = rep(k['bos']); a['_shape10'][:, :A] = rep(k['shape10'])
+        for key in self._MAP_SIDE[1:]:
+            a[key][:, :M] = k[key]
         return a
 
-    def fits(self, scenes: Sequence[Mapping]) -> bool:
-        """can ``reload`` take this batch? (same scene count, agents + insertion head-room and map tokens inside the rows this
-        engine allocated)"""
-        if len(scenes) != self.S0 or self.teacher_token is not None:
+    def _fits(self, n_scenes: int, amax: int, mmax: int, T0: int = 0) -> bool:
+        """same scene count, agents + insertion head-room and map tokens inside the rows this engine allocated, token columns
+        inside T"""
+        if n_scenes != self.S // self.copies or self.teacher_token is not None:
             return False
+        head = (self.A_cap - self._amax0) if self.insertion else 0
+        return amax + head <= self.A_cap and mmax <= self.M_cap and T0 <= self.T
+
+    def fits(self, scenes: Sequence[Mapping]) -> bool:
+        """can ``reload`` take this batch? (the agents counted after the row filter)"""
         amax = max(int((np.asarray(sc['agent']['state_idx'])[:, self.hc - 1] != INVALID).sum()) for sc in scenes)
         mmax = max(int(np.asarray(sc['pt_token']['position']).shape[0]) for sc in scenes)
-        head = (self.A_cap - self._amax0) if self.insertion else 0
-        return amax + head <= self.A_cap and mmax <= self.M_cap
+        return self._fits(len(scenes), amax, mmax)
+
+    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax):
+        if self.sample_k > 1:
+            assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
+            self.sample_u.copy_(torch.from_numpy(self._uniform_rows(sample_uniforms, amax)))
+        if self.insert_k > 1:
+            assert insert_uniforms is not None, 'cell sampling needs caller-supplied uniforms [steps][10][S]'
+            self._insert_u.copy_(torch.from_numpy(np.ascontiguousarray(insert_uniforms, dtype=np.float32)))
+
+    def _invalidate(self):
+        """what a new batch in the buffers outdates"""
+        self._init = None                  # reset() snapshots the new initial state
+        self._wgraph = None                # (the whole-rollout graph restores the state from the old snapshot's buffers)
+        self._mg_checked = False           # the new map may hold more pt <-> pt edges than the buffers
+        self._prologue_done = False
 
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None):
@@ -815,117 +827,66 @@ class RolloutEngine:
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
         self.scenes = scenes
-        self._stacked = None
         self._hosts_light = False
-        self.hosts = hosts = self._replicate(self._setup_scenes(scenes))
-        arr = self._map_side(self._scene_arrays(hosts))
+        hosts, staged = self._setup_scenes(scenes)
+        self.hosts = self._replicate(hosts)
+        arr = self._scene_arrays(staged)
         for k in self._SCENE_ARRAYS:
             getattr(self, k).copy_(torch.from_numpy(arr[k]), non_blocking=False)
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
-        if self.sample_k > 1:
-            assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
-            self.sample_u.copy_(torch.from_numpy(self._uniform_rows(sample_uniforms, max(h['A'] for h in hosts))))
-        if self.insert_k > 1:
-            assert insert_uniforms is not None, 'cell sampling needs caller-supplied uniforms [steps][10][S]'
-            self._insert_u.copy_(torch.from_numpy(np.ascontiguousarray(insert_uniforms, dtype=np.float32)))
+        self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()))
         self._x_pt_override = x_pt_override
-        self._init = None                  # reset() snapshots the new initial state
-        self._wgraph = None                # (the whole-rollout graph restores the state from the old snapshot's buffers)
         self._epi = None
-        self._mg_checked = False           # the new map may hold more pt <-> pt edges than the buffers
-        self._prologue_done = False
+        self._invalidate()
 
     # ------------------------------------------------------------------ a batch that is already on the device
     def fits_device(self, k: Mapping) -> bool:
         """``fits`` for a stacked device batch (``_setup_device``): shapes only, no host copy"""
-        ag, pt = k['agent'], k['pt_token']
-        if self.copies > 1 or int(ag['state_idx'].shape[0]) != self.S or self.teacher_token is not None:
+        S, A, T0 = (int(n) for n in k['agent']['state_idx'].shape)
+        if self.copies > 1 or A < 1:
             return False                        # (batches with copies take the host path: reload)
-        A, T0, M = int(ag['state_idx'].shape[1]), int(ag['state_idx'].shape[2]), int(pt['position'].shape[1])
-        head = (self.A_cap - self._amax0) if self.insertion else 0
-        return A + head <= self.A_cap and M <= self.M_cap and T0 <= self.T and A >= 1
+        return self._fits(S, A, int(k['pt_token']['position'].shape[1]), T0)
 
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
-        ``modules.infgen_decoder.stack_datas`` returns): the setup statements of ``_setup_scenes_stacked`` / ``_scene_arrays`` and
-        the epilogue's input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
+        ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
+        input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
         round trip of the scene arrays (~70 ms of a 512-scene call before the first launch).  ``scenes`` is the (lazy) host form
         of the same batch, only read if somebody asks for the host-side ``outputs()``.  Returns False, having changed nothing,
-        when a row would be filtered (the per-scene host path handles that: ``reload``)."""
+        when a row would be filtered (the host path handles that: ``reload``)."""
         assert self.fits_device(k), 'batch does not fit this engine (RolloutEngine.fits_device)'
         if not self._setup_device(k):
             return False
         self.scenes = scenes
-        self._stacked = None
-        if self.sample_k > 1:
-            assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
-            self.sample_u.copy_(torch.from_numpy(self._uniform_rows(sample_uniforms, self.hosts[0]['A'])))
-        if self.insert_k > 1:
-            assert insert_uniforms is not None, 'cell sampling needs caller-supplied uniforms [steps][10][S]'
-            self._insert_u.copy_(torch.from_numpy(np.ascontiguousarray(insert_uniforms, dtype=np.float32)))
+        self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'])
         self._x_pt_override = x_pt_override
-        self._init = None
-        self._wgraph = None
-        self._mg_checked = False
-        self._prologue_done = False
+        self._invalidate()
         return True
 
     def _setup_device(self, k: Mapping) -> bool:
-        """reference agent_decoder.py:1609-1719 (pad, zero the future, masks) for a one-shape batch on the device; the same
-        statements as ``_setup_scenes_stacked`` (tests/test_boundary_cpu.py compares the two array by array on CPU tensors)"""
+        """``scene_setup`` for a one-shape batch on the device, written into this engine's buffers"""
         cfg = self.cfg
-        T, hc, H, S, A_cap, M_cap = cfg.num_columns, cfg.hist_columns, cfg.num_historical_steps, self.S, self.A_cap, self.M_cap
+        T, hc, H, S = cfg.num_columns, cfg.hist_columns, cfg.num_historical_steps, self.S
         ag, pt = k['agent'], k['pt_token']
-        state0 = ag['state_idx'].long()                                                   # [S, A, T0]
-        A, T0, M = int(state0.shape[1]), int(state0.shape[2]), int(pt['position'].shape[1])
-        dev = state0.device
+        A, M = int(ag['state_idx'].shape[1]), int(pt['position'].shape[1])
         av = ag['av_index'].reshape(S, -1)[:, 0].long()
         # the one host copy of the way in: the ego rows + "is any row filtered?" (then the host path takes the batch)
-        chk = torch.cat([av, (state0[:, :, hc - 1] == INVALID).any().long()[None]]).cpu().numpy()
+        chk = torch.cat([av, (ag['state_idx'][:, :, hc - 1] == INVALID).any().long()[None]]).cpu().numpy()
         if chk[-1]:
             return False
         av_host = chk[:-1]
-
-        def pad(x, val):
-            if x.shape[2] == T:
-                return x.clone()
-            shp = tuple(x.shape[:2]) + (T - x.shape[2],) + tuple(x.shape[3:])
-            return torch.cat([x, torch.full(shp, val, dtype=x.dtype, device=dev)], dim=2)
-        pos = pad(ag['token_pos'].float(), 0.0)
-        head = pad(ag['token_heading'].float(), 0.0)
-        token = pad(ag['token_idx'].long(), -1)
-        state = pad(state0, INVALID)
-        grid = pad(ag['grid_token_idx'].long(), -1)
-        valid = pad(ag['raw_agent_valid_mask'].bool(), True)
-        pos[:, :, hc:] = 0; head[:, :, hc:] = 0; token[:, :, hc:] = -1; state[:, :, hc:] = INVALID; grid[:, :, hc:] = -1
-        valid[:, :, hc:] = True
-        valid &= ag['valid_mask'][:, :, H - 1].bool()[..., None]
-        is_bos, is_eos = state == ENTER, state == EXIT
-        bos = torch.where(is_bos.any(2), is_bos.int().argmax(2), 0)
-        eos = torch.where(is_eos.any(2), is_eos.int().argmax(2), T - 1)
-        cols = torch.arange(T, device=dev)[None, None, :]
-        motion = (cols > bos[..., None]) & (cols <= eos[..., None])
-        motion[:, :, H // cfg.shift:] = False
-        tmask = torch.where(motion, valid, True)
-        nonmotion = ~motion
-        nonmotion[:, :, H // cfg.shift:] = False
-        imask = ~nonmotion
-        imask |= state == ENTER
-        imask[torch.arange(S, device=dev), av] = True
-        tmask[:, :, hc:] = True
-        imask[:, :, hc:] = True
-        catflag = state != INVALID
+        a = scene_setup.setup_agents(dict(ag, eval_mask=ag['valid_mask'][:, :, H - 1], shape10=ag['shape'][:, :, H - 1]), av, cfg, T)
 
         def put(dst, src, fill=0):          # [S, A, T, ...] -> the engine's [S, T, A_cap, ...]
             dst.fill_(fill)
             dst[:, :, :A] = src.transpose(1, 2)
-        put(self.pos, pos); put(self.head, head); put(self.state, state); put(self.token, token, -1); put(self.gridtok, grid, -1)
-        put(self.tmask, tmask); put(self.imask, imask); put(self.catflag, catflag)
-        self.atype.zero_(); self.atype[:, :A] = ag['type']
-        self.bos.zero_(); self.bos[:, :A] = bos
-        self._shape10.fill_(INVALID_SHAPE); self._shape10[:, :A] = ag['shape'][:, :, H - 1]
+        put(self.pos, a['pos']); put(self.head, a['head']); put(self.state, a['state']); put(self.token, a['token'], -1)
+        put(self.gridtok, a['grid'], -1); put(self.tmask, a['tmask']); put(self.imask, a['imask']); put(self.catflag, a['catflag'])
+        self.atype.zero_(); self.atype[:, :A] = a['type']
+        self.bos.zero_(); self.bos[:, :A] = a['bos']
+        self._shape10.fill_(INVALID_SHAPE); self._shape10[:, :A] = a['shape10']
         self.n_agents.fill_(A); self.n_map.fill_(M); self.av.copy_(av)
         self.map_pos.zero_(); self.map_pos[:, :M] = pt['position'][:, :, :2]
         self.map_orient.zero_(); self.map_orient[:, :M] = pt['orientation']
@@ -933,48 +894,25 @@ class RolloutEngine:
         for dst, src in zip(self._map_cat, (pt['token_idx'], pt['type'], pt['pl_type'], light)):
             dst.zero_()
             dst[:, :M] = src
-        # the epilogue's inputs (outputs_device: E)
-        P = int(ag['position'].shape[2])
-        Rg = P - H
-        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)
-        htok, hst = z(S, A_cap, hc, dt=torch.int64), z(S, A_cap, hc, dt=torch.int64)
-        htok[:, :A] = ag['token_idx'][:, :, :hc]; hst[:, :A] = state0[:, :, :hc]
-        p0, h0, shp = z(S, A_cap, 2), z(S, A_cap), z(S, A_cap, 3)
-        p0[:, :A] = ag['position'][:, :, 0, :2]; h0[:, :A] = ag['heading'][:, :, 0]; shp[:, :A] = ag['shape'][:, :, hc - 1]
-        gt = z(S, A_cap, Rg, 2); gt[:, :A] = ag['position'][:, :, H:, :2]
-        val = z(S, A_cap, T, dt=torch.bool); val[:, :A] = valid
-        ids = z(S, A_cap, dt=torch.int64)
-        i0 = ag['id'].long()
-        ids[:, :A] = i0
-        ids[:, A:] = i0.max(dim=1).values[:, None] + 1 + torch.arange(A_cap - A, device=dev)[None, :]
-        n0_host = np.full(S, A, np.int64)
-        self._gt_len = [Rg] * S
-        self._epi = dict(htok=htok, hst=hst, p0=p0, h0=h0, ids=ids, shp=shp, gt=gt, val=val, n0=torch.full((S,), A, device=dev),
-                         n0_host=n0_host, eval_shape=torch.tensor([[4.3, 1.8, 1.0], [0.5, 0.5, 1.0], [1.9, 0.5, 1.0]], device=dev))
+        self._gt_len = [int(ag['position'].shape[2]) - H] * S
+        self._epi = dict(scene_setup.epilogue_inputs(ag, a['valid'], self.A_cap, cfg), n0_host=np.full(S, A, np.int64))
         filt = np.ones(A, bool)
         self.hosts = [dict(A=A, M=M, av=int(av_host[s]), filt=filt) for s in range(S)]
         self._hosts_light = True             # (the host-side ``outputs()`` rebuilds the full per-scene dicts when asked)
         return True
 
     def _full_hosts(self):
-        """the per-scene host dicts with every array of ``_setup_scene`` (a device-side reload keeps only A / M / av / filt)"""
+        """the per-scene host dicts with every array of ``_setup_scenes`` (a device-side reload keeps only A / M / av / filt)"""
         if getattr(self, '_hosts_light', False):
             self.scenes = list(self.scenes)
-            epi = self._epi
-            self.hosts = self._replicate(self._setup_scenes(self.scenes))
-            self._stacked = None
-            self._epi = epi
+            self.hosts = self._replicate(self._setup_scenes(self.scenes)[0])
             self._hosts_light = False
         return self.hosts
 
     # ------------------------------------------------------------------ a ragged Batch on the device
     def fits_batch(self, layout: Mapping) -> bool:
-        """``fits`` for a ragged Batch (``read_batch_layout``): same graph count, unfiltered rows + insertion head-room and map
-        tokens inside this engine's rows, token columns inside T"""
-        if self._batch_lay is None or layout['B'] != self.S0 or self.teacher_token is not None:
-            return False
-        head = (self.A_cap - self._amax0) if self.insertion else 0
-        return layout['amax'] + head <= self.A_cap and layout['mmax'] <= self.M_cap and layout['T0'] <= self.T
+        """``fits`` for a ragged Batch (``read_batch_layout``): the unfiltered rows counted"""
+        return self._batch_lay is not None and self._fits(layout['B'], layout['amax'], layout['mmax'], layout['T0'])
 
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None):
@@ -985,17 +923,9 @@ class RolloutEngine:
         if layout is None:
             layout = read_batch_layout(batch, self.T, self.hc, self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
-        if self.sample_k > 1:
-            assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
-            self.sample_u.copy_(torch.from_numpy(self._uniform_rows(sample_uniforms, layout['amax'])))
-        if self.insert_k > 1:
-            assert insert_uniforms is not None, 'cell sampling needs caller-supplied uniforms [steps][10][S]'
-            self._insert_u.copy_(torch.from_numpy(np.ascontiguousarray(insert_uniforms, dtype=np.float32)))
+        self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'])
         self._ingest(batch, layout, src_graph)
-        self._init = None
-        self._wgraph = None
-        self._mg_checked = False
-        self._prologue_done = False
+        self._invalidate()
 
     def _ingest(self, batch, layout, src_graph=None):
         cfg, dev, lib = self.cfg, self.device, self.lib
@@ -1051,11 +981,10 @@ class RolloutEngine:
         del keep
         self._batch_lay = layout
         self._bc_host = None
-        self.scenes, self.hosts, self._stacked, self._hosts_light = None, None, None, False
+        self.scenes, self.hosts, self._hosts_light = None, None, False
         self._gt_len = [Rg] * S
         self._epi = dict(htok=E['htok'], hst=E['hst'], p0=E['p0'], h0=E['h0'], ids=E['ids'], shp=E['shp'], gt=E['gt'], val=E['val'],
-                         n0=E['counts'][:, 0].long(), n0_host=None,
-                         eval_shape=torch.tensor([[4.3, 1.8, 1.0], [0.5, 0.5, 1.0], [1.9, 0.5, 1.0]], device=dev))
+                         n0=E['counts'][:, 0].long(), n0_host=None, eval_shape=torch.tensor(EVAL_SHAPE, device=dev))
 
     def batch_counts(self):
         """(final agent counts [S], ingest counts [S][3]: kept rows, ego row after filtering, rows removed before the ego) of an
@@ -1080,141 +1009,6 @@ class RolloutEngine:
         u = np.zeros((steps, S, A_cap), np.float32)
         u[:, :, :min(A_cap, su.shape[2])] = su[:steps, :S, :A_cap]
         return u.reshape(steps, S * A_cap)
-
-    # ------------------------------------------------------------------ host setup of a batch
-    def _setup_scenes(self, scenes) -> List[Dict[str, np.ndarray]]:
-        """``_setup_scene`` for every scene of a batch.  A 512-scene batch spends ~100 ms in 512 x ~40 small numpy calls; when the
-        scenes have one shape (same agent / column / map-token counts) and no row is filtered - what a batch of one dataset
-        looks like - the same statements run once on stacked arrays, and the per-scene dicts are views of them."""
-        try:
-            out = self._setup_scenes_stacked(scenes)
-        except (ValueError, KeyError, TypeError):
-            out = None
-        return out if out is not None else [self._setup_scene(sc) for sc in scenes]
-
-    def _setup_scenes_stacked(self, scenes):
-        cfg = self.cfg
-        T, hc, H = cfg.num_columns, cfg.hist_columns, cfg.num_historical_steps
-        S = len(scenes)
-        if S < 8:
-            return None
-        st = lambda grp, k: np.stack([np.asarray(sc[grp][k]) for sc in scenes])          # raises ValueError on ragged shapes
-        state0 = st('agent', 'state_idx').astype(np.int64)                                # [S, A, T0]
-        if (state0[:, :, hc - 1] == INVALID).any():
-            return None                                                                   # a filtered row: per-scene path
-        A, T0 = state0.shape[1], state0.shape[2]
-        if T0 > T:
-            return None
-        av = np.stack([np.asarray(sc['agent']['av_index']).reshape(-1)[0] for sc in scenes]).astype(np.int64)
-
-        def pad(x, val):
-            if x.shape[2] == T:
-                return x.copy()
-            shp = x.shape[:2] + (T - x.shape[2],) + tuple(x.shape[3:])
-            return np.concatenate([x, np.full(shp, val, dtype=x.dtype)], axis=2)
-        pos = pad(st('agent', 'token_pos').astype(np.float32), 0.0)
-        head = pad(st('agent', 'token_heading').astype(np.float32), 0.0)
-        token = pad(st('agent', 'token_idx').astype(np.int64), -1)
-        state = pad(state0, INVALID)
-        grid = pad(st('agent', 'grid_token_idx').astype(np.int64), -1)
-        valid = pad(st('agent', 'raw_agent_valid_mask').astype(bool), True)
-        pos[:, :, hc:] = 0; head[:, :, hc:] = 0; token[:, :, hc:] = -1; state[:, :, hc:] = INVALID; grid[:, :, hc:] = -1
-        valid[:, :, hc:] = True
-        eval_mask = np.stack([np.asarray(sc['agent']['valid_mask'])[:, H - 1] for sc in scenes]).astype(bool)
-        valid[~eval_mask] = False
-        is_bos, is_eos = state == ENTER, state == EXIT
-        bos = np.where(is_bos.any(2), is_bos.argmax(2), 0)
-        eos = np.where(is_eos.any(2), is_eos.argmax(2), T - 1)
-        cols = np.arange(T)[None, None, :]
-        motion = (cols > bos[..., None]) & (cols <= eos[..., None])
-        motion[:, :, H // cfg.shift:] = False
-        tmask = np.ones((S, A, T), bool)
-        tmask[motion] = valid[motion]
-        imask = np.ones((S, A, T), bool)
-        nonmotion = ~motion
-        nonmotion[:, :, H // cfg.shift:] = False
-        imask[nonmotion] = False
-        imask[state == ENTER] = True
-        imask[np.arange(S), av] = True
-        tmask[:, :, hc:] = True
-        imask[:, :, hc:] = True
-        catflag = state != INVALID
-        atype = st('agent', 'type').astype(np.int64)
-        shape10 = np.stack([np.asarray(sc['agent']['shape'])[:, H - 1] for sc in scenes]).astype(np.float32)
-        mpos = np.stack([np.asarray(sc['pt_token']['position'])[:, :2] for sc in scenes]).astype(np.float32)
-        morient = st('pt_token', 'orientation').astype(np.float32)
-        mtok, mtype, mpl = (st('pt_token', k).astype(np.int64) for k in ('token_idx', 'type', 'pl_type'))
-        e1 = np.stack([np.asarray(sc['pt_token__to__map_polygon']['edge_index'])[1] for sc in scenes]).astype(np.int64)
-        lt = [np.asarray(sc['map_polygon']['light_type']).astype(np.int64) for sc in scenes]
-        light = np.stack([l[e] for l, e in zip(lt, e1)])
-        M = mpos.shape[1]
-        filt = np.ones(A, bool)
-        self._stacked = dict(pos=pos, head=head, state=state, token=token, grid=grid, tmask=tmask, imask=imask, catflag=catflag,
-                             type=atype, bos=bos, shape10=shape10, av=av, map_pos=mpos, map_orient=morient, map_tok=mtok,
-                             map_type=mtype, map_pl=mpl, map_light=light, A=A, M=M)
-        return [dict(A=A, M=M, av=int(av[s]), filt=filt, pos=pos[s], head=head[s], token=token[s], state=state[s], grid=grid[s],
-                     valid=valid[s], tmask=tmask[s], imask=imask[s], catflag=catflag[s], bos=bos[s], type=atype[s],
-                     shape10=shape10[s], map_pos=mpos[s], map_orient=morient[s], map_tok=mtok[s], map_type=mtype[s],
-                     map_pl=mpl[s], map_light=light[s]) for s in range(S)]
-
-    # ------------------------------------------------------------------ host setup of one scene
-    def _setup_scene(self, scene) -> Dict[str, np.ndarray]:
-        """reference agent_decoder.py:1609-1719 (filter, pad, zero the future, masks)"""
-        cfg = self.cfg
-        ag = scene['agent']
-        T, hc = cfg.num_columns, cfg.hist_columns
-        state0 = np.asarray(ag['state_idx']).astype(np.int64)
-        filt = state0[:, hc - 1] != INVALID
-        av0 = int(np.asarray(ag['av_index']).reshape(-1)[0])
-        av = av0 - int((~filt[:av0]).sum())
-
-        def take(k):
-            return np.asarray(ag[k])[filt]
-
-        def pad(x, val):
-            if x.shape[1] >= T:
-                return x[:, :T].copy() if x.shape[1] > T else x.copy()
-            shp = (x.shape[0], T - x.shape[1]) + tuple(x.shape[2:])
-            return np.concatenate([x, np.full(shp, val, dtype=x.dtype)], axis=1)
-        pos = pad(take('token_pos').astype(np.float32), 0.0)
-        head = pad(take('token_heading').astype(np.float32), 0.0)
-        token = pad(take('token_idx').astype(np.int64), -1)
-        state = pad(state0[filt], INVALID)
-        grid = pad(take('grid_token_idx').astype(np.int64), -1)
-        valid = pad(take('raw_agent_valid_mask').astype(bool), True)
-        assert pos.shape[1] == T, 'token arrays longer than the rollout are not supported (SURVEY a-Q15)'
-        A = pos.shape[0]
-        pos[:, hc:] = 0; head[:, hc:] = 0; token[:, hc:] = -1; state[:, hc:] = INVALID; grid[:, hc:] = -1
-        valid[:, hc:] = True
-        eval_mask = np.asarray(ag['valid_mask'])[filt][:, cfg.num_historical_steps - 1].astype(bool)
-        valid[~eval_mask] = False
-        is_bos, is_eos = state == ENTER, state == EXIT
-        bos = np.where(is_bos.any(1), is_bos.argmax(1), 0)
-        eos = np.where(is_eos.any(1), is_eos.argmax(1), T - 1)
-        cols = np.arange(T)[None, :]
-        motion = (cols > bos[:, None]) & (cols <= eos[:, None])
-        motion[:, cfg.num_historical_steps // cfg.shift:] = False
-        tmask = np.ones((A, T), bool)
-        tmask[motion] = valid[motion]
-        imask = np.ones((A, T), bool)
-        nonmotion = ~motion
-        nonmotion[:, cfg.num_historical_steps // cfg.shift:] = False
-        imask[nonmotion] = False
-        imask[state == ENTER] = True
-        imask[av] = True
-        tmask[:, hc:] = True
-        imask[:, hc:] = True
-        catflag = (state != INVALID)
-        pt = scene['pt_token']
-        e = np.asarray(scene['pt_token__to__map_polygon']['edge_index'])
-        light = np.asarray(scene['map_polygon']['light_type']).astype(np.int64)[e[1].astype(np.int64)]
-        return dict(
-            A=A, M=int(np.asarray(pt['position']).shape[0]), av=av, filt=filt, pos=pos, head=head, token=token,
-            state=state, grid=grid, valid=valid, tmask=tmask, imask=imask, catflag=catflag, bos=bos,
-            type=take('type').astype(np.int64), shape10=np.asarray(ag['shape'])[filt][:, cfg.num_historical_steps - 1].astype(np.float32),
-            map_pos=np.asarray(pt['position'])[:, :2].astype(np.float32), map_orient=np.asarray(pt['orientation']).astype(np.float32),
-            map_tok=np.asarray(pt['token_idx']).astype(np.int64), map_type=np.asarray(pt['type']).astype(np.int64),
-            map_pl=np.asarray(pt['pl_type']).astype(np.int64), map_light=light)
 
     def _fourier_split(self) -> bool:
         """is the Fourier embedding of the operator-level entries the split kernel (infgen_set_fourier_mode != 0)?  (they read
@@ -1778,7 +1572,7 @@ class RolloutEngine:
             pt[:A0, 1:H, 1] = hy[:, :, 1:].mean(axis=3).reshape(A0, -1)
             ph[:A0, 1:H] = np.arctan2(hy[:, :, 1:, 0] - hy[:, :, 1:, 3], hx[:, :, 1:, 0] - hx[:, :, 1:, 3]).reshape(A0, -1)
             atype = atype_dev[s, :A].astype(np.int64)
-            eval_shape = np.asarray([[4.3, 1.8, 1.0], [0.5, 0.5, 1.0], [1.9, 0.5, 1.0]], np.float32)[atype]
+            eval_shape = np.asarray(EVAL_SHAPE, np.float32)[atype]
             ids0 = np.asarray(sc['id'])[filt]
             ids = np.concatenate([ids0, ids0.max() + 1 + np.arange(A - A0, dtype=ids0.dtype)])
             pshape = np.asarray(sc['shape'])[filt][:, hc - 1].astype(np.float32)
@@ -1791,15 +1585,7 @@ class RolloutEngine:
                      pred_z=np.zeros_like(ph), next_token_idx=ntok, next_state_idx=nstate,
                      gt_traj=np.asarray(sc['position'])[filt][:, H:, :2].copy(), num_inserted=A - A0)
             if self.ins is not None:
-                # label 'A<k>' on the first column after the bos column of the k-th agent a step inserted (:1996-1999)
-                labels = [[None] * self.T for _ in range(A)]
-                per_step = {}
-                for row, t_ in self.ins['inserted_rows'][s]:
-                    k_ = per_step[t_] = per_step.get(t_, 0) + 1
-                    a_ = row - s * self.A_cap
-                    if a_ < A and hc + t_ < self.T:
-                        labels[a_][hc + t_] = f'A{k_}'
-                o['agent_labels'] = labels
+                o['agent_labels'] = self._agent_labels(s, A)
             if self.seed_out is not None:
                 so = self.seed_out
                 for k_out, k_in in self._SEED_KEYS:
@@ -1812,37 +1598,31 @@ class RolloutEngine:
             outs.append(o)
         return outs
 
+    def _agent_labels(self, s: int, A: int):
+        """[A][T] labels of scene s: 'A<k>' on the first column after the bos column of the k-th agent a step inserted (:1996-1999)"""
+        labels = [[None] * self.T for _ in range(A)]
+        per_step = {}
+        for row, t_ in self.ins['inserted_rows'][s]:
+            k_ = per_step[t_] = per_step.get(t_, 0) + 1
+            a_ = row - s * self.A_cap
+            if a_ < A and self.hc + t_ < self.T:
+                labels[a_][self.hc + t_] = f'A{k_}'
+        return labels
+
     def _epi_from_hosts(self):
-        """padded copies of the inputs the device epilogue reads (``outputs_device``), from the per-scene host dicts: one upload
-        per array (``_setup_device`` builds the same arrays on the device)"""
-        cfg, hc, H, dev = self.cfg, self.hc, self.cfg.num_historical_steps, self.device
-        S, A_cap, T, R = self.S, self.A_cap, self.T, self.R
-        # padded copies of the inputs the epilogue reads (one upload per array)
-        z = lambda *shape, dt=np.float32: np.zeros(shape, dt)
-        Rg = max(int(np.asarray(sc['agent']['position']).shape[1]) - H for sc in self.scenes)
-        row_scenes = self.scenes if self.copies == 1 else [sc for sc in self.scenes for _ in range(self.copies)]
-        htok, hst = z(S, A_cap, hc, dt=np.int64), z(S, A_cap, hc, dt=np.int64)
-        p0, h0, ids, shp = z(S, A_cap, 2), z(S, A_cap), z(S, A_cap, dt=np.int64), z(S, A_cap, 3)
-        gt, val, n0 = z(S, A_cap, Rg, 2), z(S, A_cap, T, dt=bool), z(S, dt=np.int64)
-        for s, (h, sc_) in enumerate(zip(self.hosts, row_scenes)):
-            sc, f, A0 = sc_['agent'], h['filt'], h['A']
-            n0[s] = A0
-            htok[s, :A0] = np.asarray(sc['token_idx'])[f][:, :hc]
-            hst[s, :A0] = np.asarray(sc['state_idx'])[f][:, :hc]
-            pos = np.asarray(sc['position'])[f]
-            p0[s, :A0] = pos[:, 0, :2]
-            g = pos[:, H:, :2]
-            gt[s, :A0, :g.shape[1]] = g
-            h0[s, :A0] = np.asarray(sc['heading'])[f][:, 0]
-            i0 = np.asarray(sc['id'])[f]
-            ids[s, :A0] = i0
-            ids[s, A0:] = (i0.max() if len(i0) else -1) + 1 + np.arange(A_cap - A0)
-            shp[s, :A0] = np.asarray(sc['shape'])[f][:, hc - 1]
-            val[s, :A0] = h['valid']
-        t = lambda a: torch.from_numpy(a).to(dev)
-        self._gt_len = [int(np.asarray(sc['agent']['position']).shape[1]) - H for sc in row_scenes]
-        return dict(htok=t(htok), hst=t(hst), p0=t(p0), h0=t(h0), ids=t(ids), shp=t(shp), gt=t(gt), val=t(val), n0=t(n0),
-                         n0_host=n0, eval_shape=t(np.asarray([[4.3, 1.8, 1.0], [0.5, 0.5, 1.0], [1.9, 0.5, 1.0]], np.float32)))
+        """the inputs of the device epilogue (``scene_setup.epilogue_inputs``) of a batch set up from host scenes, ground truths
+        of differing lengths included: staged on the host, one upload per array"""
+        H, n = self.cfg.num_historical_steps, self.copies
+        hosts = self.hosts[::n]
+        ag = scene_setup.stage_epilogue(self.scenes, [h['filt'] for h in hosts], self.cfg)
+        valid = torch.from_numpy(scene_setup._stack([h['valid'] for h in hosts], False, bool))
+        n0 = np.repeat(np.asarray([h['A'] for h in hosts], np.int64), n)
+        if n > 1:
+            ag = {k: v.repeat_interleave(n, dim=0) for k, v in ag.items()}
+            valid = valid.repeat_interleave(n, dim=0)
+        self._gt_len = [int(np.asarray(sc['agent']['position']).shape[1]) - H for sc in self.scenes for _ in range(n)]
+        E = scene_setup.epilogue_inputs(ag, valid, self.A_cap, self.cfg, n0)
+        return dict({k: v.to(self.device) for k, v in E.items()}, n0_host=n0)
 
     def _epilogue_arrays(self, detach: bool):
         """the batch-wide arrays of the epilogue of agent_decoder.py:2303-2389 ([S][A_cap][...], all on the device)"""
@@ -1928,16 +1708,7 @@ class RolloutEngine:
             lazy['gt_traj'] = (lambda s=s, A0=A0: gt_all[s, :A0, :gt_len[s]])
             o = LazyOut(dict(ego_index=h['av'], num_inserted=A - A0), lazy)
             if ins is not None:
-                def labels(s=s, A=A):
-                    lab = [[None] * T for _ in range(A)]
-                    per_step = {}
-                    for r_, t_ in ins['inserted_rows'][s]:
-                        k_ = per_step[t_] = per_step.get(t_, 0) + 1
-                        a_ = r_ - s * A_capl
-                        if a_ < A and hc + t_ < T:
-                            lab[a_][hc + t_] = f'A{k_}'
-                    return lab
-                o.set_lazy('agent_labels', labels)
+                o.set_lazy('agent_labels', (lambda s=s, A=A: self._agent_labels(s, A)))
             if seed_out is not None:
                 # (detach: the seed arrays are engine-owned and zeroed / rewritten by the next rollout of a reused engine - cloned NOW)
                 for k_out, k_in in self._SEED_KEYS:
@@ -1991,16 +1762,7 @@ class RolloutEngine:
             if self.ins is not None:
                 labels = []
                 for g in range(B):
-                    s = g * n + j
-                    A = int(n_fin[s])
-                    lab = [[None] * T for _ in range(A)]
-                    per_step = {}
-                    for r_, t_ in self.ins['inserted_rows'][s]:
-                        k_ = per_step[t_] = per_step.get(t_, 0) + 1
-                        a_ = r_ - s * A_cap
-                        if a_ < A and self.hc + t_ < T:
-                            lab[a_][self.hc + t_] = f'A{k_}'
-                    labels.extend(lab)
+                    labels.extend(self._agent_labels(g * n + j, int(n_fin[g * n + j])))
                 o['agent_labels'] = labels
             if self.seed_out is not None:
                 so = self.seed_out

@@ -109,7 +109,7 @@ def test_attention_pack_folds_prenorm_r():
 
 
 def test_host_scene_setup_matches_oracle_masks():
-    """engine._setup_scene (reference agent_decoder.py:1609-1719) against the oracle's setup"""
+    """the scene setup (infgen_amd/scene_setup.py; reference agent_decoder.py:1609-1719) against the oracle's setup"""
     from infgen_amd.engine import RolloutEngine
     from oracle import rollout_oracle as ro
     c = load_case('a24_m256_edge')
@@ -315,8 +315,9 @@ def test_operator_level_options_are_per_thread():
 
 
 def test_stacked_host_setup_equals_the_per_scene_path():
-    """RolloutEngine._setup_scenes: a one-shape batch is set up with stacked numpy statements (the drop-in entry's host time);
-    every array must equal the per-scene loop's - history edge cases included - and ragged / filtered batches must fall back"""
+    """RolloutEngine._setup_scenes sets a batch up with one pass of statements over padded arrays: every array and every
+    host-dict entry must equal what the same scenes give when set up one at a time - history edge cases included - for a
+    one-shape batch and for a ragged one (rows beyond a scene's agents are cleared to the buffers' padding values)"""
     from infgen_amd import engine, synth
     cfg = synth.standard_config()
     vocab = synth.make_agent_vocab(cfg.token_size)
@@ -324,37 +325,44 @@ def test_stacked_host_setup_equals_the_per_scene_path():
     e = engine.RolloutEngine.__new__(engine.RolloutEngine)
     e.cfg, e.T, e.hc = cfg, cfg.num_columns, cfg.hist_columns
 
-    def check(scenes, expect_stacked):
+    def check(scenes):
         e.S, e.A_cap = len(scenes), 64
         e.M_cap = max(int(np.asarray(sc['pt_token']['position']).shape[0]) for sc in scenes)
         e.M_cap = (e.M_cap + 31) // 32 * 32
-        e._stacked = None
-        fast = e._setup_scenes(scenes)
-        assert (e._stacked is not None) == expect_stacked
-        arr_fast = e._scene_arrays(fast)
-        e._stacked = None
-        slow = [e._setup_scene(sc) for sc in scenes]
-        arr_slow = e._scene_arrays(slow)
+        fast, staged = e._setup_scenes(scenes)
+        arr_fast = e._scene_arrays(staged)
+        e.S = 1
+        slow, arr_slow = [], []
+        for sc in scenes:
+            h, st = e._setup_scenes([sc])
+            slow.append(h[0])
+            arr_slow.append(e._scene_arrays(st))
         for f, s_ in zip(fast, slow):
             assert f.keys() == s_.keys()
             for k in f:
-                assert np.array_equal(np.asarray(f[k]), np.asarray(s_[k])), k
-        for k in arr_slow:
-            assert arr_fast[k].dtype == arr_slow[k].dtype and np.array_equal(arr_fast[k], arr_slow[k]), k
+                assert np.asarray(f[k]).dtype == np.asarray(s_[k]).dtype and np.array_equal(np.asarray(f[k]), np.asarray(s_[k])), k
+        for k in arr_fast:
+            one = np.concatenate([a[k] for a in arr_slow])
+            assert arr_fast[k].dtype == one.dtype and np.array_equal(arr_fast[k], one), k
 
     uniform = [synth.make_scene(900 + i, 40, 200, cfg, ego_last=(i % 2 == 0), edge_cases=(i % 3 == 0), vocab=vocab, grid=grid)
                for i in range(12)]
     uniform = [sc for sc in uniform if (np.asarray(sc['agent']['state_idx'])[:, 1] != 0).all()]
     assert len(uniform) >= 8
-    check(uniform, True)
+    check(uniform)
     ragged = uniform[:7] + [synth.make_scene(77, 24, 100, cfg, vocab=vocab, grid=grid)] + uniform[7:]
-    check(ragged, False)
+    check(ragged)
+    # (a scene with filtered rows and a moved ego index next to full ones)
+    filtered = synth.make_scene(8201, 30, 120, cfg, ego_last=True, edge_cases=True, vocab=vocab, grid=grid, slip=0.1)
+    assert (np.asarray(filtered['agent']['state_idx'])[:, 1] == 0).any()
+    check(uniform[:3] + [filtered] + uniform[3:])
 
 
 def test_device_side_setup_equals_the_host_setup():
-    """RolloutEngine._setup_device (the drop-in entry's reload of a batch that arrives as device tensors: the setup statements
-    and the epilogue's inputs as torch ops) writes exactly the arrays the host path uploads - run here on CPU tensors against
-    _setup_scenes / _scene_arrays / _epi_from_hosts, history edge cases included; a batch with a filtered row is refused"""
+    """RolloutEngine._setup_device (the drop-in entry's reload of a batch that arrives as device tensors: scene_setup's
+    statements on the stacked tensors, written into the engine's buffers) leaves exactly the arrays the host path uploads -
+    run here on CPU tensors against _setup_scenes / _scene_arrays / _epi_from_hosts (staged from the host scenes), history
+    edge cases included; a batch with a filtered row is refused"""
     from infgen_amd import engine, synth
     from infgen_amd.modules.infgen_decoder import stack_datas, _LazyScenes
     from test_modules_gpu import _to_data
@@ -377,13 +385,13 @@ def test_device_side_setup_equals_the_host_setup():
         e = engine.RolloutEngine.__new__(engine.RolloutEngine)
         e.cfg, e.T, e.hc, e.device = cfg, cfg.num_columns, cfg.hist_columns, dev
         e.S, e.A_cap, e.M_cap, e.R = S, 64, 224, cfg.num_recurrent_steps_val
-        e.insertion, e.teacher_token, e._amax0, e._stacked = False, None, 40, None
+        e.insertion, e.teacher_token, e._amax0 = False, None, 40
         return e
     S = len(scenes)
     host = blank(S)
     host.scenes = scenes
-    host.hosts = host._setup_scenes(scenes)
-    arr = host._scene_arrays(host.hosts)
+    host.hosts, staged = host._setup_scenes(scenes)
+    arr = host._scene_arrays(staged)
     epi_h = host._epi_from_hosts()
     d = blank(S)
     T, A_cap, M_cap = d.T, d.A_cap, d.M_cap
