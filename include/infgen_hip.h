@@ -43,6 +43,8 @@
  *   infgen_distance_to_road_edge, infgen_placement_features   infgen/metrics/{interact,trajectory,map,placement}_features.py
  *   infgen_window_log_likelihood                       the scoring of LongMetric (infgen/metrics/compute_metrics.py:845-878)
  *   infgen_bundle_scores                               the same for all rollouts of all scenarios of a batch (:891-1103)
+ *   infgen_state_accuracy, infgen_grid_overlap, infgen_traj_error, infgen_token_cls, infgen_average_meter,
+ *   infgen_masked_cross_entropy                        the validation step's bookkeeping (infgen/utils/metrics.py) and open-loop loss
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 / int32 / uint8) borrowed for the duration
  * of the call; outputs are pre-allocated by the caller; `stream` is a hipStream_t; nothing
@@ -639,6 +641,45 @@ int infgen_ingest_batch(const InfgenBatchIngest* a, void* stream);
 int infgen_pack_rows(int n_keys, const void* const* src, const long long* src_stride, const int* row_bytes,
                      const int* const* counts, const int* count_stride, void* const* dst, int n_scenes, int scene0, int scene_step,
                      void* stream);
+
+/* ---- validation-step metrics and the open-loop loss (infgen/utils/metrics.py, infgen/model/infgen.py:644-655) ----
+ * Each entry ADDS into a caller-owned device accumulator of 8-byte slots (zeroed by the caller before the first update): integer
+ * counters are int64, floating sums float64, reduced in a fixed order without float atomics (bitwise reproducible).  Index arrays
+ * are int32 (..64 == 0) or int64 (..64 != 0), masks are bytes (torch.bool / uint8); row strides are in elements.  `scratch`:
+ * INFGEN_VM_SCRATCH_DOUBLES doubles the float entries use for the workgroups' partial sums (one per metric object / stream). */
+#define INFGEN_VM_SCRATCH_DOUBLES 3072
+#define INFGEN_GRID_OVERLAP_MAX_CELLS 16384
+
+/* StateAccuracy.update and NumInsertAccuracy.update (infgen/utils/metrics.py:499-543, :632-676; the caller's use is
+ * infgen/model/infgen.py:236-237 and :765): state_idx [N][T]; valid_mask [N][T] or NULL (part 1 only).
+ * acc [4] += valid, valid_count, invalid, invalid_count */
+int infgen_state_accuracy(const void* state_idx, int idx64, int N, int T, long long ld, const unsigned char* valid_mask,
+                          long long ld_mask, int invalid_state, int valid_state, int enter_state, int exit_state, long long* acc,
+                          void* stream);
+/* GridOverlapRate.update (infgen/utils/metrics.py:574-591; infgen/model/infgen.py:241-242) for n_group row ranges ptr[g]..ptr[g+1]
+ * (ptr NULL: one group of all N rows, the reference's behaviour): state_token / grid_index [N][>= num_step], -1 = out of range,
+ * cells in [0, grid_size), grid_size <= INFGEN_GRID_OVERLAP_MAX_CELLS.
+ * acc [4][num_step] += num_overlap_t, num_insert_agent_t, num_total_agent_t, num_exceed_seed_t (once per group) */
+int infgen_grid_overlap(const void* state_token, int state64, long long ld_state, const void* grid_index, int grid64,
+                        long long ld_grid, int N, int num_step, const long long* ptr, int n_group, int grid_size, int enter_state,
+                        int seed_size, long long* acc, void* stream);
+/* minADE.update (infgen/utils/metrics.py:441-464) and minFDE.update (:378-387) in one pass: pred / target [N][T][2], valid [N][T].
+ * ade_acc / fde_acc [2] = (float64 sum, int64 count), either may be NULL */
+int infgen_traj_error(const float* pred, const float* target, const unsigned char* valid, int N, int T, void* ade_acc,
+                      void* fde_acc, double* scratch, void* stream);
+/* pred[mask] + torch.nn.CrossEntropyLoss(weight, label_smoothing) of infgen/model/infgen.py:147-152, :644, :655 without the gather:
+ * logits [R][C] row stride ld, target [R], mask [R], weight [C] or NULL.  acc [3] (float64) += S1 = sum w_y (-log p_y),
+ * S2 = sum_i sum_c w_c (-log p_ic) (only when label_smoothing != 0), S3 = sum w_y over the selected rows; the mean loss is
+ * ((1 - eps) S1 + eps / C S2) / S3.  Masked-out rows are not read; a target outside [0, C) is skipped. */
+int infgen_masked_cross_entropy(const float* logits, long long ld, const void* target, int target64, const unsigned char* mask,
+                                const float* weight, int R, int C, float label_smoothing, double* acc, double* scratch,
+                                void* stream);
+/* TokenCls.update (infgen/utils/metrics.py:326-333; infgen/model/infgen.py:725, :761): pred [R][>= n_guess] row stride ld_pred,
+ * target [R], mask [R].  acc [2] (int64) += hits under the mask, mask count */
+int infgen_token_cls(const void* pred, int pred64, long long ld_pred, int n_guess, const void* target, int target64,
+                     const unsigned char* mask, int R, long long* acc, void* stream);
+/* AverageMeter.update (infgen/utils/metrics.py:477-479): acc [2] = (float64 sum += sum of val [n], int64 count += n) */
+int infgen_average_meter(const float* val, long long n, void* acc, double* scratch, void* stream);
 
 #ifdef __cplusplus
 }

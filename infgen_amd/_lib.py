@@ -199,7 +199,16 @@ SYMBOLS = {
     'infgen_ingest_batch': (_i, [C.POINTER(BatchIngest), _p]),
     'infgen_pack_rows': (_i, [_i, C.POINTER(_p), C.POINTER(C.c_longlong), C.POINTER(_i), C.POINTER(_p), C.POINTER(_i),
                               C.POINTER(_p), _i, _i, _i, _p]),
+    # validation-step metrics (infgen_amd/utils/metrics.py)
+    'infgen_state_accuracy': (_i, [_p, _i, _i, _i, C.c_longlong, _p, C.c_longlong, _i, _i, _i, _i, _p, _p]),
+    'infgen_grid_overlap': (_i, [_p, _i, C.c_longlong, _p, _i, C.c_longlong, _i, _i, _p, _i, _i, _i, _i, _p, _p]),
+    'infgen_traj_error': (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    'infgen_masked_cross_entropy': (_i, [_p, C.c_longlong, _p, _i, _p, _p, _i, _i, _f, _p, _p, _p]),
+    'infgen_token_cls': (_i, [_p, _i, C.c_longlong, _i, _p, _i, _p, _i, _p, _p]),
+    'infgen_average_meter': (_i, [_p, C.c_longlong, _p, _p, _p]),
 }
+VM_SCRATCH_DOUBLES = 3072                # INFGEN_VM_SCRATCH_DOUBLES
+GRID_OVERLAP_MAX_CELLS = 16384           # INFGEN_GRID_OVERLAP_MAX_CELLS
 
 Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_ATTN_CAP, Q_MAX_AGENTS, \
     Q_ABI_VERSION, Q_SIZEOF_ROLLOUT = range(9)

@@ -825,6 +825,126 @@ extern "C" int infgen_bundle_scores(const unsigned char* valid, const unsigned c
   return check_launch(me);
 }
 
+// ---- validation-step metrics (val_metrics.hip).  Arguments are checked before anything is launched.
+static_assert(INFGEN_VM_SCRATCH_DOUBLES == VM_MAX_PARTIALS * 3 && INFGEN_GRID_OVERLAP_MAX_CELLS == GO_MAX_CELLS, "header constants");
+static inline int vm_blocks(long long work_items, int per_block) {
+  const long long nb = (work_items + per_block - 1) / per_block;
+  return (int)(nb < 1 ? 1 : nb > VM_MAX_PARTIALS ? VM_MAX_PARTIALS : nb);
+}
+
+// StateAccuracy.update / NumInsertAccuracy.update (infgen/utils/metrics.py:499-543, :632-676)
+extern "C" int infgen_state_accuracy(const void* state_idx, int idx64, int N, int T, long long ld, const unsigned char* valid_mask,
+                                    long long ld_mask, int invalid_state, int valid_state, int enter_state, int exit_state,
+                                    long long* acc, void* stream) {
+  const char* me = "infgen_state_accuracy";
+  if (N < 0) return fail(me, "N is negative");
+  if (T < 1) return fail(me, "T must be at least 1");
+  if (!acc) return fail(me, "acc is NULL");
+  if (N == 0) return 0;
+  if (!state_idx) return fail(me, "state_idx is NULL");
+  if (ld < T || (valid_mask && ld_mask < T)) return fail(me, "row stride shorter than the row");
+  StateAccArgs a{state_idx, valid_mask, N, T, ld, ld_mask, invalid_state, valid_state, enter_state, exit_state,
+                 (unsigned long long*)acc};
+  const dim3 grid(vm_blocks(N, 4));
+  if (idx64) hipLaunchKernelGGL(k_state_accuracy<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_state_accuracy<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+// GridOverlapRate.update (infgen/utils/metrics.py:574-591)
+extern "C" int infgen_grid_overlap(const void* state_token, int state64, long long ld_state, const void* grid_index, int grid64,
+                                  long long ld_grid, int N, int num_step, const long long* ptr, int n_group, int grid_size,
+                                  int enter_state, int seed_size, long long* acc, void* stream) {
+  const char* me = "infgen_grid_overlap";
+  if (N < 0 || n_group < 0) return fail(me, "N or n_group is negative");
+  if (num_step < 1) return fail(me, "num_step must be at least 1");
+  if (grid_size < 1 || grid_size > GO_MAX_CELLS) return fail(me, "grid_size must be in 1..16384 (the LDS bitmaps)");
+  if (!acc) return fail(me, "acc is NULL");
+  if (!ptr) n_group = 1;
+  if (n_group == 0) return 0;
+  if (N > 0 && (!state_token || !grid_index)) return fail(me, "state_token or grid_index is NULL");
+  if (ld_state < num_step || ld_grid < num_step) return fail(me, "row stride shorter than num_step");
+  GridOverlapArgs a{state_token, grid_index, ld_state, ld_grid, ptr, N, num_step, n_group, grid_size, enter_state, seed_size,
+                    (unsigned long long*)acc};
+  const dim3 grid(num_step, n_group);
+  if (state64 && grid64) hipLaunchKernelGGL((k_grid_overlap<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else if (state64) hipLaunchKernelGGL((k_grid_overlap<true, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else if (grid64) hipLaunchKernelGGL((k_grid_overlap<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_grid_overlap<false, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+// minADE.update (infgen/utils/metrics.py:441-464) and minFDE.update (:378-387)
+extern "C" int infgen_traj_error(const float* pred, const float* target, const unsigned char* valid, int N, int T, void* ade_acc,
+                                void* fde_acc, double* scratch, void* stream) {
+  const char* me = "infgen_traj_error";
+  if (N < 0) return fail(me, "N is negative");
+  if (T < 1) return fail(me, "T must be at least 1");
+  if (!ade_acc && !fde_acc) return fail(me, "both accumulators are NULL");
+  if (!scratch) return fail(me, "scratch is NULL");
+  if (N == 0) return 0;
+  if (!pred || !target || !valid) return fail(me, "pred, target or valid is NULL");
+  const int nb = vm_blocks(N, 256);
+  TrajErrArgs a{pred, target, valid, N, T, ade_acc ? (unsigned long long*)ade_acc + 1 : nullptr,
+                fde_acc ? (unsigned long long*)fde_acc + 1 : nullptr, scratch};
+  hipLaunchKernelGGL(k_traj_error, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_vm_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, 2, (double*)ade_acc,
+                     (double*)fde_acc, (double*)nullptr);
+  return check_launch(me);
+}
+
+// pred[mask] + nn.CrossEntropyLoss (infgen/model/infgen.py:147-152, :644, :655)
+extern "C" int infgen_masked_cross_entropy(const float* logits, long long ld, const void* target, int target64,
+                                          const unsigned char* mask, const float* weight, int R, int C, float label_smoothing,
+                                          double* acc, double* scratch, void* stream) {
+  const char* me = "infgen_masked_cross_entropy";
+  if (R < 0) return fail(me, "R is negative");
+  if (C < 1) return fail(me, "C must be at least 1");
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f)) return fail(me, "label_smoothing must be in [0, 1]");
+  if (!acc || !scratch) return fail(me, "acc or scratch is NULL");
+  if (R == 0) return 0;
+  if (!logits || !target || !mask) return fail(me, "logits, target or mask is NULL");
+  if (ld < C) return fail(me, "row stride shorter than the row");
+  const int nb = vm_blocks(R, 4);
+  MaskedCeArgs a{logits, ld, target, mask, weight, R, C, label_smoothing != 0.f ? 1 : 0, scratch};
+  if (target64) hipLaunchKernelGGL(k_masked_ce<true>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(k_masked_ce<false>, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_vm_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, 3, acc, acc + 1, acc + 2);
+  return check_launch(me);
+}
+
+// TokenCls.update (infgen/utils/metrics.py:326-333)
+extern "C" int infgen_token_cls(const void* pred, int pred64, long long ld_pred, int n_guess, const void* target, int target64,
+                               const unsigned char* mask, int R, long long* acc, void* stream) {
+  const char* me = "infgen_token_cls";
+  if (R < 0 || n_guess < 0) return fail(me, "R or n_guess is negative");
+  if (!acc) return fail(me, "acc is NULL");
+  if (R == 0) return 0;
+  if (!pred || !target || !mask) return fail(me, "pred, target or mask is NULL");
+  if (ld_pred < n_guess) return fail(me, "row stride shorter than n_guess");
+  TokenClsArgs a{pred, ld_pred, n_guess, target, mask, R, (unsigned long long*)acc};
+  const dim3 grid(vm_blocks(R, 256));
+  if (pred64 && target64) hipLaunchKernelGGL((k_token_cls<true, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else if (pred64) hipLaunchKernelGGL((k_token_cls<true, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else if (target64) hipLaunchKernelGGL((k_token_cls<false, true>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_token_cls<false, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+// AverageMeter.update (infgen/utils/metrics.py:477-479)
+extern "C" int infgen_average_meter(const float* val, long long n, void* acc, double* scratch, void* stream) {
+  const char* me = "infgen_average_meter";
+  if (n < 0) return fail(me, "n is negative");
+  if (!acc || !scratch) return fail(me, "acc or scratch is NULL");
+  if (n == 0) return 0;
+  if (!val) return fail(me, "val is NULL");
+  const int nb = vm_blocks(n, 256 * 8);
+  hipLaunchKernelGGL(k_vm_sum, dim3(nb), dim3(256), 0, (hipStream_t)stream, val, n, scratch, (unsigned long long*)acc + 1);
+  hipLaunchKernelGGL(k_vm_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, 1, (double*)acc,
+                     (double*)nullptr, (double*)nullptr);
+  return check_launch(me);
+}
+
 extern "C" int infgen_match_map_tokens(const float* traj_pos, const float* theta, const float* sample_pt, int P, int n_token,
                                       int* token_idx, void* stream) {
   if (P <= 0) return 0;

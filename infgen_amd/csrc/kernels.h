@@ -566,4 +566,49 @@ struct PackRowsArgs {
 __global__ void k_ingest_batch(InfgenBatchIngest a);
 __global__ void k_pack_rows(PackRowsArgs a);
 
+// validation-step metrics and the open-loop loss (val_metrics.hip; reference infgen/utils/metrics.py).  Every kernel ADDS into a
+// caller-owned accumulator of 8-byte slots: integer counters are int64 (integer atomics), floating sums are float64 reduced in a
+// fixed order - rows inside a lane, lanes, then the workgroups' partials by k_vm_finish - without float atomics.
+// Index arrays are int32 or int64 (the bool template arguments: true = int64), masks are bytes (torch.bool / uint8).
+constexpr int VM_MAX_PARTIALS = 1024;     // workgroups of a float kernel; `scratch` holds VM_MAX_PARTIALS x 3 doubles
+constexpr int GO_MAX_CELLS = 16384;       // cells the two LDS bitmaps of k_grid_overlap hold (the tokenizer's grid: 1961)
+struct StateAccArgs {                // k_state_accuracy
+  const void* state; const unsigned char* mask;            // [N][T] row strides ld / ldm (elements); mask may be null (part 1 only)
+  int N, T; long long ld, ldm;
+  int invalid_state, valid_state, enter_state, exit_state;
+  unsigned long long* acc;                                  // [4]: valid, valid_count, invalid, invalid_count
+};
+struct GridOverlapArgs {             // k_grid_overlap
+  const void* state; const void* grid;                      // [N][>= num_step], row strides lds / ldg
+  long long lds, ldg;
+  const long long* ptr;                                     // [n_group + 1] row ranges, or null: one group of all N rows
+  int N, num_step, n_group, grid_size, enter_state, seed_size;
+  unsigned long long* acc;                                  // [4][num_step]: overlap, insert, total, exceed_seed
+};
+struct TrajErrArgs {                 // k_traj_error
+  const float* pred; const float* target; const unsigned char* valid;      // [N][T][2], [N][T][2], [N][T]
+  int N, T;
+  unsigned long long* ade_count; unsigned long long* fde_count;             // slot 1 of the two accumulators; either may be null
+  double* partials;                                                         // [gridDim.x][2]: ade, fde
+};
+struct MaskedCeArgs {                // k_masked_ce
+  const float* logits; long long ld;                        // [R][C], row stride ld
+  const void* target; const unsigned char* mask; const float* weight;      // [R], [R], [C] or null
+  int R, C, smooth;                                         // smooth: label smoothing != 0 (the all-class sum is needed)
+  double* partials;                                         // [gridDim.x][3]
+};
+struct TokenClsArgs {                // k_token_cls
+  const void* pred; long long ldp; int n_guess;             // [R][>= n_guess]
+  const void* target; const unsigned char* mask;            // [R], [R]
+  int R;
+  unsigned long long* acc;                                  // [2]: sum, count
+};
+template <bool I64> __global__ void k_state_accuracy(StateAccArgs a);
+template <bool S64, bool G64> __global__ void k_grid_overlap(GridOverlapArgs a);
+__global__ void k_traj_error(TrajErrArgs a);
+template <bool T64> __global__ void k_masked_ce(MaskedCeArgs a);
+template <bool P64, bool T64> __global__ void k_token_cls(TokenClsArgs a);
+__global__ void k_vm_sum(const float* val, long long n, double* partials, unsigned long long* count);   // AverageMeter: partial sums; *count += n
+__global__ void k_vm_finish(const double* partials, int nb, int K, double* dst0, double* dst1, double* dst2);
+
 }  // namespace ig

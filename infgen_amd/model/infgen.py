@@ -10,6 +10,9 @@ not a dependency): ``self.log`` / trainer hooks are not provided, ``global_rank`
 The open-loop branch (``val_open_loop`` / ``OPEN_LOOP=1``, reference :627-686) runs ``InfGenDecoder.forward`` - the teacher-forced pass
 of SURVEY section 8f rank 3 (infgen_amd/forward_engine.py) - and leaves the token + state cross-entropy in ``self.val_loss``;
 training (autograd) is not built.
+The step's bookkeeping (reference :136-143, :229-247, :765-767, :848-861) runs on the device classes of
+infgen_amd/utils/metrics.py: ``self.logged`` holds what the reference hands to ``self.log`` as device scalars, ``check_inputs``
+and ``on_validation_epoch_end`` mirror the reference's; nothing is read back inside a step.
 
 The reference reads its token tables from ``infgen/tokens/*.pkl`` (data of that repository).  Here they are arguments:
 ``map_token_traj`` (n_token, 11, 2) or ``map_token_traj_path`` (pickle with ['traj_src']), and ``agent_tokens`` /
@@ -26,6 +29,8 @@ import torch.nn as nn
 from ..metrics import compute_metrics
 from ..modules import Attr_Tokenizer, InfGenDecoder, TokenProcessor, fetch_enterings
 from ..modules.token_processor import match_token_map as _match_core
+from ..utils.metrics import (GridOverlapRate, StateAccuracy, TokenCls, masked_cross_entropy, minADE, minFDE,
+                             update_traj_metrics)
 
 
 def _get(cfg, name, default=None):
@@ -78,6 +83,20 @@ class InfGen(nn.Module):
             use_head_token=self.use_head_token, use_state_token=self.use_state_token,
             disable_insertion=self.disable_insertion, seed_size=self.seed_size, buffer_size=dc.buffer_size,
             num_recurrent_steps_val=mc.num_recurrent_steps_val, loss_weight=_get(mc, 'loss_weight'), logger=logger)
+        # reference :136-143 (device classes of infgen_amd/utils/metrics.py; seed_size: the reference passes the agent decoder's
+        # num_seed_feature)
+        self.minADE = minADE(max_guesses=1)
+        self.minFDE = minFDE(max_guesses=1)
+        self.TokenCls = TokenCls(max_guesses=1)
+        self.StateCls = TokenCls(max_guesses=1)
+        self.StateAccuracy = StateAccuracy(state_token=st)
+        self.GridOverlapRate = GridOverlapRate(num_step=18, state_token=st,
+                                               seed_size=getattr(self.encoder.agent_encoder, 'num_seed_feature', self.seed_size),
+                                               grid_size=self.attr_tokenizer.grid_size)
+        # what the reference hands to self.log on every step, as device scalars (nothing is read back inside the step)
+        self.logged: Dict[str, torch.Tensor] = {}
+        # True: minADE / minFDE are fed by the closed-loop step (the reference has these calls commented out, :732-733)
+        self.log_traj_metrics = False
         self.val_open_loop = bool(_get(mc, 'val_open_loop', False))
         self.loss_weight = _get(mc, 'loss_weight')
         self.val_close_loop = bool(_get(mc, 'val_close_loop', True))
@@ -117,6 +136,17 @@ class InfGen(nn.Module):
 
     def get_agent_inputs(self, data):
         return self.encoder.get_agent_inputs(data)
+
+    # ------------------------------------------------------------------ reference :229-247
+    @torch.no_grad()
+    def check_inputs(self, data):
+        """the tokenisation check of a pre-processed scene or Batch (TokenProcessor + _fetch_enterings have run): StateAccuracy
+        and GridOverlapRate fed from get_agent_inputs' arrays on the device, then printed like the reference"""
+        inputs = self.get_agent_inputs(data)
+        self.StateAccuracy.update(state_idx=inputs['next_state_idx_gt'], valid_mask=inputs['raw_agent_valid_mask'])
+        self.GridOverlapRate.update(state_token=inputs['state_token'], grid_index=inputs['grid_index'])
+        print(self.StateAccuracy)
+        print(self.GridOverlapRate)
 
     def forward(self, data):
         """reference infgen/model/infgen.py:217-219"""
@@ -222,16 +252,25 @@ class InfGen(nn.Module):
             # that branch are not part of the HIP path)
             pred = self(data)
             self.open_loop_pred = pred
-            loss = torch.zeros((), device=pred['next_token_prob'].device)
+            # token_cls_loss(pred[mask], gt[mask]) + state_cls_loss(...) (:644, :655) without the boolean gather: one kernel per
+            # head over all rows, masked-out rows skipped, no host read (float64, infgen_amd/utils/metrics.masked_cross_entropy)
+            loss = torch.zeros((), dtype=torch.float64, device=pred['next_token_prob'].device)
             if self.predict_motion:
                 m_ = pred['next_token_eval_mask']
-                loss = loss + torch.nn.functional.cross_entropy(pred['next_token_prob'][m_], pred['next_token_idx_gt'][m_],
-                                                                label_smoothing=0.1)
+                loss = loss + masked_cross_entropy(pred['next_token_prob'], pred['next_token_idx_gt'], m_, label_smoothing=0.1)
+                idx = pred['next_token_idx']           # (:725, commented out in the reference: the top guess under the mask)
+                self.TokenCls.update(pred=idx.reshape(-1, idx.shape[-1]) if idx.dim() > 2 else idx.reshape(-1, 1),
+                                     target=pred['next_token_idx_gt'].reshape(-1), valid_mask=m_.reshape(-1))
+                self.logged['val_token_cls_acc'] = self.TokenCls.compute()
             if self.predict_state:
                 m_ = pred['next_state_eval_mask']
                 sw = torch.tensor(self.loss_weight['state_weight'], device=loss.device) if self.loss_weight else None
-                loss = loss + torch.nn.functional.cross_entropy(pred['next_state_prob'][m_], pred['next_state_idx_gt'][m_], weight=sw)
-            self.val_loss = loss
+                loss = loss + masked_cross_entropy(pred['next_state_prob'], pred['next_state_idx_gt'], m_, weight=sw)
+                idx = pred['next_state_idx']           # (:761)
+                self.StateCls.update(pred=idx.reshape(-1, idx.shape[-1]) if idx.dim() > 2 else idx.reshape(-1, 1),
+                                     target=pred['next_state_idx_gt'].reshape(-1), valid_mask=m_.reshape(-1))
+                self.logged['val_state_cls_acc'] = self.StateCls.compute()
+            self.val_loss = self.logged['val_loss'] = loss
             if not (self.val_close_loop and (self.predict_motion or self.predict_state)):
                 return loss
         if not (self.val_close_loop and (self.predict_motion or self.predict_state)):
@@ -244,6 +283,13 @@ class InfGen(nn.Module):
             rollout = self.encoder.inference(data.clone() if hasattr(data, 'clone') else data)
             self.last_rollouts = [rollout]
         rollouts = [rollout]                                   # the reference appends outside its loop (:704-706): the last one
+        if self.predict_state:
+            # reference :765-767; a multi-graph Batch: the concatenated rows in one call (the counters are sums over rows)
+            self.StateAccuracy.update(state_idx=rollout['next_state_idx'])
+            acc = self.StateAccuracy.compute()
+            self.logged['valid_accuracy'], self.logged['invalid_accuracy'] = acc['valid'], acc['invalid']
+        if self.log_traj_metrics and self.predict_motion:
+            self._update_traj_metrics(data, rollout)
         if not (self._online_metric or self._save_validate_reuslts):
             return rollout
         formatted = compute_metrics.format_rollouts(data, rollouts)
@@ -271,6 +317,43 @@ class InfGen(nn.Module):
                     self._long_metrics.update(features=f)
         return rollout
 
+    def _update_traj_metrics(self, data, rollout):
+        """minADE / minFDE of the rollout against the logged track (reference :729-733, commented out there): rows matched by agent
+        id, valid = the logged valid_mask of agents seen at the current step (the reference's eval_mask, folded into the mask
+        instead of a boolean gather); inserted agents have no logged track and count nowhere.  One graph only."""
+        ag = data['agent']
+        if 'ptr' in ag and ag['ptr'].numel() > 2:
+            raise NotImplementedError('log_traj_metrics: agent ids repeat across the graphs of a Batch; feed one graph per step')
+        ids, rid = ag['id'].reshape(-1), rollout['agent_id'].reshape(-1)
+        order = torch.argsort(ids)
+        row = order[torch.searchsorted(ids[order], rid).clamp(max=ids.numel() - 1)]
+        found = ids[row] == rid
+        vm = ag['valid_mask'].bool()
+        pred = rollout['pred_traj']
+        T = min(pred.shape[1], vm.shape[1])
+        valid = vm[row, :T] & (found & vm[row, self.num_historical_steps - 1])[:, None]
+        update_traj_metrics(self.minADE, self.minFDE, pred[:, :T, :2], ag['position'][row, :T, :2], valid)
+        self.logged['val_minADE'], self.logged['val_minFDE'] = self.minADE.compute(), self.minFDE.compute()
+
     def on_validation_start(self):
         self.scenario_rollouts, self.scenario_features = [], []
         self.scenario_features_batch = None
+
+    # ------------------------------------------------------------------ reference :848-861
+    def on_validation_epoch_end(self) -> Dict:
+        """-> the epoch's metrics (device tensors, and the LongMetric dict when one is assigned) - the reference hands them to its
+        logger -, then resets them (the reference resets minADE, minFDE and StateAccuracy; the classifiers and the overlap rate
+        restart with them here)"""
+        out: Dict = {}
+        if self.val_close_loop:
+            if self._long_metrics is not None:
+                out.update(self._long_metrics.compute())
+                self._long_metrics.reset()
+            acc = self.StateAccuracy.compute()
+            out.update(valid_accuracy=acc['valid'], invalid_accuracy=acc['invalid'], val_minADE=self.minADE.compute(),
+                       val_minFDE=self.minFDE.compute())
+        if self.val_open_loop:
+            out.update(val_token_cls_acc=self.TokenCls.compute(), val_state_cls_acc=self.StateCls.compute())
+        for m in (self.minADE, self.minFDE, self.StateAccuracy, self.TokenCls, self.StateCls, self.GridOverlapRate):
+            m.reset()
+        return out

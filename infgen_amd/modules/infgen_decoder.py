@@ -649,8 +649,16 @@ class InfGenDecoder(nn.Module):
                 pass
         return res
 
-    def get_agent_inputs(self, data):
-        raise NotImplementedError('training-only helper (agent_decoder.py:933) — out of the hot path')
+    def get_agent_inputs(self, data) -> Dict[str, torch.Tensor]:
+        """the arrays of the reference's ``get_inputs`` (agent_decoder.py:933-992) that ``InfGen.check_inputs`` reads, as written
+        there - ``next_state_idx_gt`` is the rolled TOKEN index (:947) -, on the data's device.  ``next_token_eval_mask`` (a Python
+        loop over the enter / exit positions, :949-979; check_inputs clones it and never reads it) is not built."""
+        ag = data['agent']
+        tok = ag['token_idx']
+        return {'token_pos': ag['token_pos'].clone(), 'token_heading': ag['token_heading'].clone(),
+                'next_token_idx_gt': tok.roll(shifts=-1, dims=1), 'next_state_idx_gt': tok.roll(shifts=-1, dims=1),
+                'raw_agent_valid_mask': ag['raw_agent_valid_mask'], 'state_token': ag['state_idx'].clone(),
+                'grid_index': ag['grid_token_idx']}
 
     @torch.no_grad()
     def forward(self, data) -> Dict[str, torch.Tensor]:
