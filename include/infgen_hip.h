@@ -176,6 +176,11 @@ typedef struct InfgenRollout {
    * accumulated pose drift and no radius / first-K decision can flip: logits are comparable row by row with a maximum, and the
    * one-step pose update is checked separately (tests/test_baseline_shapes_gpu.py) */
   const float* teacher_pos; const float* teacher_head;
+  /* optional [S][A_cap] (log replay): with it, teacher_token / teacher_state / teacher_grid / teacher_pos / teacher_head apply only
+   * to the rows flagged 1 - they follow the plan (the logged future or a planner's) - and every other row is generated exactly
+   * as without a teacher.  NULL: the teacher arrays, when given, apply to every row.  Needs teacher_token and teacher_state
+   * (infgen_rollout_validate).  Rows scenario insertion appends are never flagged. */
+  const unsigned char* replay_row;
   /* optional [S]: the map-side scene of agent-side scene s (NULL: s itself).  Several scenes may share ONE set of map tokens - n_map,
    * map_pos / map_orient, the rows [slot * M_cap, (slot + 1) * M_cap) of mapK / mapV (and of InfgenInsertion.mapK / mapV) are then
    * indexed by slot = map_scene[s]: the n rollouts of one scene (reference infgen/model/infgen.py:704-706, inference_no_map
@@ -631,6 +636,15 @@ typedef struct InfgenBatchIngest {
   int* n_map; float* map_pos; float* map_orient; long long* map_tok; long long* map_type; long long* map_pl; long long* map_light;
   long long* htok; long long* hst; float* p0; float* h0; float* shp; float* gt; unsigned char* val; long long* ids;
   int* counts;
+  /* log replay (all optional; replay_row == NULL: nothing of it is read or written).  replay_in u8 [N]: 1 = the row follows
+   * its plan.  The plan is the logged future - columns hc .. T0 - 1 of token_idx / state_idx / token_pos / token_heading - or,
+   * where a plan_* array is given (same shapes), that array.  Written in the rollout's layout for InfgenRollout.teacher_* /
+   * replay_row: teacher_token / teacher_state int [S][T][A_cap], teacher_pos f32 [S][T][A_cap][2], teacher_head f32 [S][T][A_cap]
+   * (teacher_pos / teacher_head may be NULL: a plan of tokens and states only), replay_row u8 [S][A_cap] - the flag of every
+   * row the filter keeps, for every copy of its graph; -1 / 0 everywhere else. */
+  const unsigned char* replay_in;
+  const long long* plan_token; const long long* plan_state; const float* plan_pos; const float* plan_head;
+  int* teacher_token; int* teacher_state; float* teacher_pos; float* teacher_head; unsigned char* replay_row;
 } InfgenBatchIngest;
 int infgen_ingest_batch(const InfgenBatchIngest* a, void* stream);
 

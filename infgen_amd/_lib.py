@@ -98,6 +98,7 @@ class Rollout(C.Structure):
         ('teacher_grid', _p),
         ('four_t_dt', _p),
         ('teacher_pos', _p), ('teacher_head', _p),
+        ('replay_row', _p),
         ('map_scene', _p),
         ('tap_x', _p),
         ('no_grid_token', _i), ('no_state_token', _i),
@@ -114,7 +115,9 @@ class BatchIngest(C.Structure):
                                    'light_type',
                                    'pos', 'head', 'state', 'token', 'gridtok', 'tmask', 'imask', 'catflag', 'atype', 'bos',
                                    'shape10', 'n_agents', 'av', 'n_map', 'map_pos', 'map_orient', 'map_tok', 'map_type', 'map_pl',
-                                   'map_light', 'htok', 'hst', 'p0', 'h0', 'shp', 'gt', 'val', 'ids', 'counts')])
+                                   'map_light', 'htok', 'hst', 'p0', 'h0', 'shp', 'gt', 'val', 'ids', 'counts',
+                                   'replay_in', 'plan_token', 'plan_state', 'plan_pos', 'plan_head',
+                                   'teacher_token', 'teacher_state', 'teacher_pos', 'teacher_head', 'replay_row')])
 
 
 # symbol -> (restype, argtypes); every symbol include/infgen_hip.h declares

@@ -1137,7 +1137,7 @@ static int integrate_impl(const InfgenRollout* r, int t, void* stream, unsigned 
   a.st = scene_of(r); a.c = 1 + t; a.t = t; a.R = r->R; a.force_valid = r->force_valid; a.no_state = r->no_state_token;
   a.next_token = r->next_token; a.next_state = r->next_state;
   a.teacher_token = r->teacher_token; a.teacher_state = r->teacher_state; a.teacher_grid = r->teacher_grid;
-  a.teacher_pos = r->teacher_pos; a.teacher_head = r->teacher_head;
+  a.teacher_pos = r->teacher_pos; a.teacher_head = r->teacher_head; a.replay_row = r->replay_row;
   a.vocab = r->vocab; a.token_size = r->token_size; a.grid_xy = r->grid_xy; a.grid_size = r->grid_size;
   a.pred_traj = r->pred_traj; a.pred_head = r->pred_head; a.pred_state = r->pred_state;
   a.groups = integrate_groups(r);
@@ -1395,6 +1395,10 @@ static bool lp_packs_ok(const InfgenRollout* r, bool refresh = false, void* stre
 // this once (infgen_amd/engine.py: _build_ctx); without it a pack is examined when its address is first seen.  Synchronous.
 extern "C" int infgen_rollout_validate(const InfgenRollout* r) {
   RET_IF(validate(r, "infgen_rollout_validate"));
+  if (r->replay_row && !(r->teacher_token && r->teacher_state))
+    return fail("infgen_rollout_validate", "replay_row needs teacher_token and teacher_state (the plan the flagged rows follow)");
+  if ((r->teacher_pos != nullptr) != (r->teacher_head != nullptr))
+    return fail("infgen_rollout_validate", "teacher_pos and teacher_head come together");
   (void)lp_packs_ok(r, true);
   return 0;
 }
@@ -2060,6 +2064,10 @@ extern "C" int infgen_ingest_batch(const InfgenBatchIngest* a, void* stream) {
                         a->map_pl, a->map_light, a->htok, a->hst, a->p0, a->h0, a->shp, a->gt, a->val, a->ids, a->counts};
   for (const void* p : need)
     if (!p) return fail("infgen_ingest_batch", "null input or destination pointer");
+  if (a->replay_row && !(a->replay_in && a->teacher_token && a->teacher_state))
+    return fail("infgen_ingest_batch", "replay_row needs replay_in, teacher_token and teacher_state");
+  if ((a->teacher_pos != nullptr) != (a->teacher_head != nullptr))
+    return fail("infgen_ingest_batch", "teacher_pos and teacher_head come together");
   hipLaunchKernelGGL(k_ingest_batch, dim3(a->S, 3), dim3(256), 0, (hipStream_t)stream, *a);
   return check_launch("infgen_ingest_batch");
 }

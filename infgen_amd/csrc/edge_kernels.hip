@@ -571,8 +571,11 @@ __global__ __launch_bounds__(BT) void k_integrate(IntegrateArgs a) {
     if (t == av) ns = VALID;                    // ego forced valid
     if (a.no_state && ns == EXIT) ns = VALID;   // use_state_token = False (agent_decoder.py:2170-2171)
     if (a.force_valid) ns = VALID;              // disable_insertion
-    if (a.teacher_token) { tok = a.teacher_token[sidx(st, s, n, t)]; if (tok < 0) tok = 0; }
-    if (a.teacher_state) ns = a.teacher_state[sidx(st, s, n, t)];
+    // log replay: with replay_row the teacher's token / state / pose replace this row's only where its flag is set; the other rows
+    // are generated.  The dup thread reads the EGO's flag (t == av), so every workgroup searches around the pose the ego stores
+    const bool forced = !a.replay_row || a.replay_row[row] != 0;
+    if (a.teacher_token && forced) { tok = a.teacher_token[sidx(st, s, n, t)]; if (tok < 0) tok = 0; }
+    if (a.teacher_state && forced) ns = a.teacher_state[sidx(st, s, n, t)];
     const size_t ic = sidx(st, s, c, t);
     const float th = st.head[ic];
     const float cs = cosf(th), sn = sinf(th);
@@ -600,7 +603,7 @@ __global__ __launch_bounds__(BT) void k_integrate(IntegrateArgs a) {
       }
       if (k == 5) { lx = mx; ly = my; lth = hh; }
     }
-    if (a.teacher_pos) {        // the stored pose is the teacher's (pred_traj / pred_head above keep this step's own result)
+    if (a.teacher_pos && forced) {        // the stored pose is the teacher's (pred_traj / pred_head above keep this step's own result)
       const size_t in_ = sidx(st, s, n, t);
       lx = a.teacher_pos[2 * in_]; ly = a.teacher_pos[2 * in_ + 1]; lth = a.teacher_head[in_];
     }
@@ -644,10 +647,11 @@ __global__ __launch_bounds__(BT) void k_integrate(IntegrateArgs a) {
         st.pos[2 * in_ + 1] = inv ? 0.f : npy[al];
         st.head[in_] = inv ? 0.f : nth[al];
         int cell = bi;
-        if (a.teacher_grid && a.teacher_grid[in_] >= -1) cell = a.teacher_grid[in_];
+        const bool forced = !a.replay_row || a.replay_row[s * st.A_cap + ag] != 0;
+        if (a.teacher_grid && forced && a.teacher_grid[in_] >= -1) cell = a.teacher_grid[in_];
         st.grid[in_] = inv ? -1 : cell;
         int tok = a.heads_part ? a.next_token_w[s * st.A_cap + ag] : a.next_token[s * st.A_cap + ag];
-        if (a.teacher_token) { tok = a.teacher_token[in_]; }
+        if (a.teacher_token && forced) { tok = a.teacher_token[in_]; }
         st.token[in_] = inv ? -1 : tok;
         if (inv) { st.imask[in_] = 0; st.catflag[in_] = 0; }
       }

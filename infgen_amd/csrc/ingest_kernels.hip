@@ -186,6 +186,25 @@ __global__ __launch_bounds__(ING_NT) void k_ingest_batch(InfgenBatchIngest a) {
     a.pos[2 * o] = x; a.pos[2 * o + 1] = y; a.head[o] = hd;
     a.state[o] = st; a.token[o] = tk; a.gridtok[o] = gr;
     a.tmask[o] = tm; a.imask[o] = im; a.catflag[o] = cf;
+    if (a.replay_row) {
+      // log replay: the future columns zeroed above are kept, for the flagged rows, as the plan the rollout forces
+      int ptk = -1, pst = ING_INVALID;
+      float px = 0.f, py = 0.f, ph = 0.f;
+      if (r < n && t >= hc && t < a.T0) {
+        const long long row = base + L.src_row[r];
+        if (a.replay_in[row]) {
+          const long long i = row * a.T0 + t;
+          ptk = (int)(a.plan_token ? a.plan_token : a.token_idx)[i];
+          pst = (int)(a.plan_state ? a.plan_state : a.state_idx)[i];
+          if (a.teacher_pos) {
+            const float* pp = a.plan_pos ? a.plan_pos : a.token_pos;
+            px = pp[2 * i]; py = pp[2 * i + 1]; ph = (a.plan_head ? a.plan_head : a.token_heading)[i];
+          }
+        }
+      }
+      a.teacher_token[o] = ptk; a.teacher_state[o] = pst;
+      if (a.teacher_pos) { a.teacher_pos[2 * o] = px; a.teacher_pos[2 * o + 1] = py; a.teacher_head[o] = ph; }
+    }
   }
   for (int r = tid; r < A_cap; r += ING_NT) {
     const size_t o = (size_t)s * A_cap + r;
@@ -198,6 +217,7 @@ __global__ __launch_bounds__(ING_NT) void k_ingest_batch(InfgenBatchIngest a) {
       s0 = sh[0]; s1 = sh[1]; s2 = sh[2];
     }
     a.atype[o] = ty; a.bos[o] = b;
+    if (a.replay_row) a.replay_row[o] = (r < n && a.replay_in[base + L.src_row[r]]) ? 1 : 0;
     a.shape10[3 * o] = s0; a.shape10[3 * o + 1] = s1; a.shape10[3 * o + 2] = s2;
   }
   if (tid == 0) {

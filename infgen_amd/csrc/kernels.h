@@ -392,6 +392,7 @@ struct IntegrateArgs {
   const int* teacher_token; const int* teacher_state;   // optional [S][T][A_cap]
   const int* teacher_grid;                               // optional [S][T][A_cap], < -1: none
   const float* teacher_pos; const float* teacher_head;   // optional [S][T][A_cap](x2): the stored pose of column c + 1
+  const unsigned char* replay_row;                       // optional [S][A_cap]: teacher_* apply to the rows flagged 1 only (NULL: to every row)
   // the tail of a decode step folded into this launch (infgen_rollout_run with few rows; all optional):
   unsigned long long* heads_part;   // k_heads' split arg-max keys [rows]: decoded here (k_heads_finish) and reset for the next step
   int* next_token_w;                // where the decoded tokens go (the context's next_token array)

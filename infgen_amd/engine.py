@@ -549,10 +549,17 @@ class RolloutEngine:
                  sample_k: int = 1, sample_uniforms: Optional[np.ndarray] = None, options: Optional[Mapping[str, int]] = None,
                  insert_k: int = 1, insert_uniforms: Optional[np.ndarray] = None, seed_outputs: bool = False,
                  use_graph: Optional[bool] = None, copies: int = 1, flags: Optional[Mapping[str, bool]] = None,
-                 tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None):
+                 tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
-        never exceed) and set up on the device by the ingest kernel (``reload_batch``)"""
+        never exceed) and set up on the device by the ingest kernel (``reload_batch``).
+        ``replay``: log replay - the flagged rows follow a plan (their logged future, or a planner's), every other row is
+        generated around them.  Host scenes: one entry per scene, None, a bool mask over the scene's rows (the plan is the
+        scene's own token_idx / state_idx / token_pos / token_heading from column hist_columns on) or (mask, tokens, states[,
+        pos, head]) with (A, T) / (A, T, 2) arrays.  A Batch: a bool mask over its N concatenated rows on the device, or (mask,
+        dict of token_idx / state_idx[, token_pos, token_heading] [N][T0]).  Flags refer to initial rows (rows scenario insertion
+        appends are always generated); a flagged row's logged enter / exit / invalid states are forced like ``teacher``'s.
+        ``reload`` / ``reload_device`` / ``reload_batch`` take a new mask and plan.  ``teacher`` (all rows, test hook) excludes it."""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -691,6 +698,10 @@ class RolloutEngine:
                 self.teacher_grid = t(tg)
             if tp is not None:
                 self.teacher_pos, self.teacher_head = t(tp), t(th)
+        self.replay_row = None                 # [S][A_cap] uint8 once a replay was asked for (InfgenRollout.replay_row)
+        self._replay_pose = None               # the pose buffers of a replay engine (teacher_pos / teacher_head point at them or are None)
+        if replay is not None and teacher is not None:
+            raise ValueError('teacher= forces every row; replay= forces the flagged rows: give one of them')
 
         # ------------------------------------------------ scratch / caches
         f = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)
@@ -734,7 +745,9 @@ class RolloutEngine:
         self._decoded_rows = torch.zeros((), device=dev, dtype=torch.int64)
         self._ing = None
         if batch is not None:
-            self._ingest(batch, batch_layout)
+            self._ingest(batch, batch_layout, replay=replay)
+        elif replay is not None:
+            self._replay_from_hosts(replay)
 
     # ------------------------------------------------------------------ scene arrays (host -> device)
     _SCENE_ARRAYS = ('pos', 'head', 'state', 'token', 'gridtok', 'tmask', 'imask', 'catflag', 'atype', 'bos', 'n_agents', 'n_map',
@@ -795,8 +808,8 @@ class RolloutEngine:
     def _fits(self, n_scenes: int, amax: int, mmax: int, T0: int = 0) -> bool:
         """same scene count, agents + insertion head-room and map tokens inside the rows this engine allocated, token columns
         inside T"""
-        if n_scenes != self.S // self.copies or self.teacher_token is not None:
-            return False
+        if n_scenes != self.S // self.copies or (self.teacher_token is not None and getattr(self, 'replay_row', None) is None):
+            return False                       # (an all-row teacher belongs to its scenes; a replay engine takes a new plan)
         head = (self.A_cap - self._amax0) if self.insertion else 0
         return amax + head <= self.A_cap and mmax <= self.M_cap and T0 <= self.T
 
@@ -821,8 +834,49 @@ class RolloutEngine:
         self._mg_checked = False           # the new map may hold more pt <-> pt edges than the buffers
         self._prologue_done = False
 
+    # ------------------------------------------------------------------ log replay
+    def _alloc_replay(self, with_pose: bool):
+        """the plan buffers of a replay engine (once) and which of them the context points at: a plan without poses leaves
+        teacher_pos / teacher_head NULL (the stored pose is the forced token's integration).  The pointers are static like every
+        other of the context - a new plan changes contents only; a captured graph is dropped when a pointer does change"""
+        S, T, A_cap, dev = self.S, self.T, self.A_cap, self.device
+        changed = False
+        if self.replay_row is None:
+            self.teacher_token = torch.full((S, T, A_cap), -1, dtype=torch.int32, device=dev)
+            self.teacher_state = torch.zeros((S, T, A_cap), dtype=torch.int32, device=dev)
+            self.replay_row = torch.zeros((S, A_cap), dtype=torch.uint8, device=dev)
+            changed = True
+        if with_pose and self._replay_pose is None:
+            self._replay_pose = (torch.zeros((S, T, A_cap, 2), device=dev), torch.zeros((S, T, A_cap), device=dev))
+        if with_pose != (self.teacher_pos is not None):
+            self.teacher_pos, self.teacher_head = self._replay_pose if with_pose else (None, None)
+            changed = True
+        if changed and self._ctx is not None:
+            c, P = self._ctx, _lib.ptr
+            c.teacher_token, c.teacher_state, c.replay_row = P(self.teacher_token), P(self.teacher_state), P(self.replay_row)
+            c.teacher_pos, c.teacher_head = P(self.teacher_pos), P(self.teacher_head)
+            self._graph = self._wgraph = None
+            _lib.check(self.lib.infgen_rollout_validate(C.byref(c)), 'infgen_rollout_validate')
+
+    def _load_replay(self, mask: Optional[torch.Tensor], plan: Optional[Mapping[str, torch.Tensor]]):
+        """row mask [S0, A] + plan ([S0, A, T0, ...], ``scene_setup.replay_arrays``) on any device -> this engine's plan buffers;
+        None: nothing is replayed (an engine that has the buffers clears its flags)"""
+        if mask is None:
+            if self.replay_row is not None:
+                self.replay_row.zero_()
+            return
+        arrs = scene_setup.replay_arrays(mask, plan, self.hc, self.T, self.A_cap, self.copies)
+        self._alloc_replay('teacher_pos' in arrs)
+        for k, v in arrs.items():
+            getattr(self, k).copy_(v)
+
+    def _replay_from_hosts(self, replay):
+        if replay is None:
+            return self._load_replay(None, None)
+        self._load_replay(*scene_setup.stage_replay(self.scenes, [h['filt'] for h in self.hosts[::self.copies]], replay, self.T))
+
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
-               insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None):
+               insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -838,6 +892,7 @@ class RolloutEngine:
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()))
         self._x_pt_override = x_pt_override
         self._epi = None
+        self._replay_from_hosts(replay)
         self._invalidate()
 
     # ------------------------------------------------------------------ a batch that is already on the device
@@ -849,15 +904,17 @@ class RolloutEngine:
         return self._fits(S, A, int(k['pt_token']['position'].shape[1]), T0)
 
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
-                      insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None) -> bool:
+                      insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
         round trip of the scene arrays (~70 ms of a 512-scene call before the first launch).  ``scenes`` is the (lazy) host form
         of the same batch, only read if somebody asks for the host-side ``outputs()``.  Returns False, having changed nothing,
-        when a row would be filtered (the host path handles that: ``reload``)."""
+        when a row would be filtered (the host path handles that: ``reload``).  ``replay``: a bool mask [S, A] on the device (the
+        plan is the stacked logged future) or (mask, dict of stacked token_idx / state_idx[, token_pos, token_heading]) - copied
+        into the plan buffers on the device before the future columns are zeroed."""
         assert self.fits_device(k), 'batch does not fit this engine (RolloutEngine.fits_device)'
-        if not self._setup_device(k):
+        if not self._setup_device(k, replay):
             return False
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'])
@@ -865,7 +922,7 @@ class RolloutEngine:
         self._invalidate()
         return True
 
-    def _setup_device(self, k: Mapping) -> bool:
+    def _setup_device(self, k: Mapping, replay=None) -> bool:
         """``scene_setup`` for a one-shape batch on the device, written into this engine's buffers"""
         cfg = self.cfg
         T, hc, H, S = cfg.num_columns, cfg.hist_columns, cfg.num_historical_steps, self.S
@@ -877,6 +934,11 @@ class RolloutEngine:
         if chk[-1]:
             return False
         av_host = chk[:-1]
+        if replay is not None:                # (the logged future of the flagged rows, before setup_agents zeroes it)
+            mask, plan = replay if isinstance(replay, (tuple, list)) else (replay, None)
+            self._load_replay(mask, {k_: ag[k_] for k_ in scene_setup.PLAN_KEYS} if plan is None else plan)
+        elif getattr(self, 'replay_row', None) is not None:
+            self.replay_row.zero_()
         a = scene_setup.setup_agents(dict(ag, eval_mask=ag['valid_mask'][:, :, H - 1], shape10=ag['shape'][:, :, H - 1]), av, cfg, T)
 
         def put(dst, src, fill=0):          # [S, A, T, ...] -> the engine's [S, T, A_cap, ...]
@@ -915,7 +977,7 @@ class RolloutEngine:
         return self._batch_lay is not None and self._fits(layout['B'], layout['amax'], layout['mmax'], layout['T0'])
 
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
-                     insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None):
+                     insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -924,10 +986,10 @@ class RolloutEngine:
             layout = read_batch_layout(batch, self.T, self.hc, self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'])
-        self._ingest(batch, layout, src_graph)
+        self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
-    def _ingest(self, batch, layout, src_graph=None):
+    def _ingest(self, batch, layout, src_graph=None, replay=None):
         cfg, dev, lib = self.cfg, self.device, self.lib
         S, A_cap, M_cap, T, hc, H = self.S, self.A_cap, self.M_cap, self.T, self.hc, cfg.num_historical_steps
         ag, pt = batch['agent'], batch['pt_token']
@@ -977,6 +1039,29 @@ class RolloutEngine:
         a.map_tok, a.map_type, a.map_pl, a.map_light = (t_.data_ptr() for t_ in self._map_cat)
         for k_ in ('htok', 'hst', 'p0', 'h0', 'shp', 'gt', 'val', 'ids', 'counts'):
             setattr(a, k_, E[k_].data_ptr())
+        if replay is not None:
+            # log replay: the kernel keeps the flagged rows' future columns (or the caller's plan) as the plan buffers' contents
+            mask, plan = replay if isinstance(replay, (tuple, list)) else (replay, None)
+            N = int(torch.as_tensor(ag['state_idx']).shape[0])
+            if int(torch.as_tensor(mask).numel()) != N:
+                raise ValueError(f'replay mask of {int(torch.as_tensor(mask).numel())} rows for a Batch of {N} agent rows')
+            if layout['T0'] < T:
+                raise ValueError(f"the plan covers {layout['T0']} token columns, the rollout has {T}")
+            with_pose = True if plan is None else scene_setup.check_plan(plan)
+            self._alloc_replay(with_pose)
+            a.replay_in = arr(torch.as_tensor(mask).reshape(-1), u8)
+            if plan is not None:
+                for dst, key, dt, shape in (('plan_token', 'token_idx', i64, (N, layout['T0'])), ('plan_state', 'state_idx', i64, (N, layout['T0'])),
+                                            ('plan_pos', 'token_pos', f32, (N, layout['T0'], 2)), ('plan_head', 'token_heading', f32, (N, layout['T0']))):
+                    if plan.get(key) is not None:
+                        if tuple(torch.as_tensor(plan[key]).shape) != shape:
+                            raise ValueError(f'replay plan: {key} has shape {tuple(torch.as_tensor(plan[key]).shape)}, need {shape}')
+                        setattr(a, dst, arr(plan[key], dt))
+            a.teacher_token, a.teacher_state, a.replay_row = (x.data_ptr() for x in (self.teacher_token, self.teacher_state, self.replay_row))
+            if with_pose:
+                a.teacher_pos, a.teacher_head = self.teacher_pos.data_ptr(), self.teacher_head.data_ptr()
+        elif self.replay_row is not None:
+            self.replay_row.zero_()
         _lib.check(lib.infgen_ingest_batch(C.byref(a), self.ops.stream), 'infgen_ingest_batch')
         del keep
         self._batch_lay = layout
@@ -1397,6 +1482,7 @@ class RolloutEngine:
         c.teacher_token, c.teacher_state = P(self.teacher_token), P(self.teacher_state)
         c.teacher_grid = P(self.teacher_grid)
         c.teacher_pos, c.teacher_head = P(self.teacher_pos), P(self.teacher_head)
+        c.replay_row = P(self.replay_row)
         c.pred_traj, c.pred_head, c.pred_state = P(self.pred_traj), P(self.pred_head), P(self.pred_state)
         if self.insertion:
             c.first_new, c.hv_ovr = P(self.ins['first_new']), P(self.ins['hv_ovr'])
@@ -1538,6 +1624,7 @@ class RolloutEngine:
         atype_dev = self.atype.cpu().numpy()
         bos_dev = self.bos.cpu().numpy()
         shape_all = self.ins['shape_all'].cpu().numpy().reshape(self.S, self.A_cap, 3) if self.ins is not None else None
+        replay_row = self.replay_row.cpu().numpy().astype(bool) if self.replay_row is not None else None
         outs = []
         for s, h in enumerate(self.hosts):
             A0, M = h['A'], h['M']
@@ -1584,6 +1671,8 @@ class RolloutEngine:
                      pred_shape=pshape, eval_shape=eval_shape,
                      pred_z=np.zeros_like(ph), next_token_idx=ntok, next_state_idx=nstate,
                      gt_traj=np.asarray(sc['position'])[filt][:, H:, :2].copy(), num_inserted=A - A0)
+            if replay_row is not None:
+                o['replay_mask'] = replay_row[s, :A].copy()        # the rows that followed their plan (inserted rows never do)
             if self.ins is not None:
                 o['agent_labels'] = self._agent_labels(s, A)
             if self.seed_out is not None:
@@ -1676,6 +1765,8 @@ class RolloutEngine:
         eval_shape = E['eval_shape'][atype]
         batch = dict(agent_id=E['ids'], pos_a=pos_a, head_a=head_a, pred_traj=pt, pred_head=ph, pred_state=ps, pred_valid=pvalid,
                      pred_type=atype, pred_shape=pshape, eval_shape=eval_shape, next_token_idx=ntok, next_state_idx=nstate)
+        if self.replay_row is not None:
+            batch['replay_mask'] = self.replay_row.bool()
         return batch, E, ph, lg_all, x_pt_all, n_fin
 
     def outputs_device(self, detach: bool = False) -> List[Dict[str, torch.Tensor]]:
@@ -1738,8 +1829,9 @@ class RolloutEngine:
         batch, E, ph, lg_all, x_pt_all, _ = self._epilogue_arrays(False)
         S, A_cap, T, B, n, dev = self.S, self.A_cap, self.T, self.S0, self.copies, self.device
         fin, init = self.n_agents, self._ing['counts'][:, 0]
-        keys = self._PACK_FIN + ('valid_mask', 'gt_traj')
-        srcs = [batch[k].contiguous() for k in self._PACK_FIN] + [E['val'], E['gt']]
+        pack_fin = self._PACK_FIN + (('replay_mask',) if 'replay_mask' in batch else ())
+        keys = pack_fin + ('valid_mask', 'gt_traj')
+        srcs = [batch[k].contiguous() for k in pack_fin] + [E['val'], E['gt']]
         x_pt = None
         if x_pt_all is not None:
             M = self._batch_lay['M']
@@ -1747,8 +1839,8 @@ class RolloutEngine:
         outs = []
         for j in range(n):
             f_j, i_j = n_fin[j::n], c[j::n, 0]
-            tots = [int(f_j.sum())] * len(self._PACK_FIN) + [int(i_j.sum())] * 2
-            cols = [fin] * len(self._PACK_FIN) + [init] * 2
+            tots = [int(f_j.sum())] * len(pack_fin) + [int(i_j.sum())] * 2
+            cols = [fin] * len(pack_fin) + [init] * 2
             packed = dict(zip(keys, pack_rows(srcs, cols, tots, B, scene0=j, scene_step=n)))
             ptr = np.concatenate([[0], np.cumsum(f_j)])
             o = dict(packed)

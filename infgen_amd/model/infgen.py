@@ -226,7 +226,9 @@ class InfGen(nn.Module):
 
     # ------------------------------------------------------------------ reference :573-842, close-loop branch
     @torch.no_grad()
-    def validation_step(self, data, batch_idx):
+    def validation_step(self, data, batch_idx, replay=None, replay_plan=None):
+        """``replay`` / ``replay_plan``: log replay of the closed-loop branch (``InfGenDecoder.inference``); None: every agent
+        is generated, as in the reference"""
         rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
         rollouts_path = os.path.join(self.save_path, f'idx_{rank}_{batch_idx}_rollouts.pkl')
         if self._save_validate_reuslts and os.path.exists(rollouts_path):
@@ -275,12 +277,13 @@ class InfGen(nn.Module):
                 return loss
         if not (self.val_close_loop and (self.predict_motion or self.predict_state)):
             return
+        rp = {} if replay is None and replay_plan is None else dict(replay=replay, replay_plan=replay_plan)
         if self.n_rollout_close_val > 1:
             # the reference's loop (:704-706) as one batch of n copies of the scene with their own sampling uniforms
-            self.last_rollouts = self.encoder.inference_rollouts(data, self.n_rollout_close_val)
+            self.last_rollouts = self.encoder.inference_rollouts(data, self.n_rollout_close_val, **rp)
             rollout = self.last_rollouts[-1]
         else:
-            rollout = self.encoder.inference(data.clone() if hasattr(data, 'clone') else data)
+            rollout = self.encoder.inference(data.clone() if hasattr(data, 'clone') else data, **rp)
             self.last_rollouts = [rollout]
         rollouts = [rollout]                                   # the reference appends outside its loop (:704-706): the last one
         if self.predict_state:

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib
+from .. import _lib, scene_setup
 from ..engine import InsertionHeadroomError, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -333,8 +333,57 @@ class InfGenDecoder(nn.Module):
         return self._packed
 
     # ------------------------------------------------------------------ driver
+    @staticmethod
+    def _plan_list(replay_plan, counts) -> Optional[List[Dict]]:
+        """``replay_plan`` (one dict over all rows in scene order, or one dict per scene) -> one dict per scene"""
+        if replay_plan is None:
+            return None
+        if isinstance(replay_plan, (list, tuple)):
+            if len(replay_plan) != len(counts):
+                raise ValueError(f'replay_plan lists {len(replay_plan)} plans for {len(counts)} scenes')
+            plans = [dict(p_) for p_ in replay_plan]
+        else:
+            scene_setup.check_plan(replay_plan)
+            cut = {k_: torch.as_tensor(v_).split(list(counts)) for k_, v_ in replay_plan.items() if v_ is not None}
+            plans = [{k_: v_[i] for k_, v_ in cut.items()} for i in range(len(counts))]
+        for p_ in plans:
+            scene_setup.check_plan(p_)
+        return plans
+
+    def _replay_forms(self, datas, stk, replay, replay_plan):
+        """``replay`` / ``replay_plan`` of the public entries -> (device form for ``reload_device`` or None, a function that
+        makes the per-scene host entries ``RolloutEngine(replay=...)`` takes).  The device form is built without a host copy."""
+        if isinstance(replay, str) and replay != 'ego':
+            raise ValueError(f"replay must be 'ego', a bool tensor or a list of bool tensors, not {replay!r}")
+        counts = [int(d_['agent']['state_idx'].shape[0]) for d_ in datas]
+        plans = self._plan_list(replay_plan, counts)
+        if not isinstance(replay, str):                  # (the lengths are checked here, whichever path takes the batch)
+            scene_setup.replay_rows(replay, counts, [0] * len(counts))
+        dev_form = None
+        if stk is not None:
+            sag = stk['agent']
+            S, A = (int(n) for n in sag['state_idx'].shape[:2])
+            dev = sag['state_idx'].device
+            if isinstance(replay, str):
+                mask = torch.zeros(S, A, dtype=torch.bool, device=dev)
+                mask.scatter_(1, sag['av_index'].reshape(S, -1)[:, :1].long(), True)
+            else:
+                mask = torch.stack([m.to(dev) for m in scene_setup.replay_rows(replay, counts, [0] * S)])
+            dev_form = mask if plans is None else (mask, {k_: torch.stack([torch.as_tensor(p_[k_]).to(dev) for p_ in plans])
+                                                          for k_ in scene_setup.PLAN_KEYS if plans[0].get(k_) is not None})
+
+        def host_form():
+            av = [int(_np(d_['agent']['av_index']).reshape(-1)[0]) for d_ in datas]
+            masks = [_np(m) for m in scene_setup.replay_rows(replay, counts, av)]
+            if plans is None:
+                return masks
+            return [(m, _np(p_['token_idx']), _np(p_['state_idx'])) +
+                    ((_np(p_['token_pos']), _np(p_['token_heading'])) if p_.get('token_pos') is not None else ())
+                    for m, p_ in zip(masks, plans)]
+        return dev_form, host_form
+
     def _run(self, data, x_pt=None, map_only=False, batch: Optional[Sequence] = None, sample_uniforms=None,
-             batch_seed_outputs: bool = False, copies: int = 1):
+             batch_seed_outputs: bool = False, copies: int = 1, replay=None, replay_plan=None):
         ae = self.agent_encoder
         datas = list(batch) if batch is not None else [data]
         copies = int(copies)
@@ -344,6 +393,9 @@ class InfGenDecoder(nn.Module):
         # when something reads it (a new engine, a filtered row, the host-side outputs)
         stk = stack_datas(datas) if batch is not None and copies == 1 else None
         scenes = _LazyScenes(datas) if stk is not None else scenes_from_datas(datas)
+        if replay is None and replay_plan is not None:
+            raise ValueError('replay_plan overrides the logged future of the rows replay= flags: give replay= too')
+        rp_dev, rp_host = self._replay_forms(datas, stk, replay, replay_plan) if replay is not None else (None, lambda: None)
         w = self._last_w = self._weights()
         ag0 = datas[0]['agent']
         if ae.num_recurrent_steps_val == -1:
@@ -380,19 +432,20 @@ class InfGenDecoder(nn.Module):
                                  # single-scene entry and the n-copies batch of inference_rollouts; the throughput entry
                                  # (inference_batch) returns the zero arrays the reference initialises them to
                                  seed_outputs=(batch is None or batch_seed_outputs) and not w.cfg.disable_insertion and not map_only,
-                                 copies=copies, options=self._PRECISIONS[str(self.rollout_precision)])
+                                 copies=copies, options=self._PRECISIONS[str(self.rollout_precision)], replay=rp_host())
         # one engine per batch layout is kept across calls: a second call of the same shape re-uploads the scene arrays into
         # the first call's device buffers instead of building (and allocating) an engine again
         ekey = (len(scenes), PackedWeights.tables_key(*(vocab[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab),
                 bool(w.cfg.disable_insertion), w.cfg.num_recurrent_steps_val, k if not map_only else 1,
                 ik if insert_uniforms is not None else 1, bool(int(os.getenv('DEBUG', 0))), batch is None, map_only, xo is None,
-                bool(batch_seed_outputs), copies)
+                bool(batch_seed_outputs), copies, replay is not None)
         eng = self._engines.get(ekey)
         if (stk is not None and eng is not None and eng.fits_device(stk) and
-                eng.reload_device(stk, scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo)):
+                eng.reload_device(stk, scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo,
+                                  replay=rp_dev)):
             pass
         elif eng is not None and eng.fits(scenes):
-            eng.reload(scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo)
+            eng.reload(scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo, replay=rp_host())
         else:
             eng = make_engine()
             if len(self._engines) >= 2:
@@ -524,7 +577,8 @@ class InfGenDecoder(nn.Module):
             return np.asarray(t)
         return self._cached('_host_consts', [t], lambda: t.detach().cpu().numpy())
 
-    def _run_graphs(self, data, sample_uniforms=None, copies: int = 1, mutate: bool = True) -> List[Dict]:
+    def _run_graphs(self, data, sample_uniforms=None, copies: int = 1, mutate: bool = True, replay=None,
+                    replay_plan=None) -> List[Dict]:
         """a ragged multi-graph Batch of device tensors through RolloutEngine.reload_batch (the ingest kernel: filter, pad and
         set up every scene on the device) and the batched epilogue (outputs_batch: infgen_pack_rows).  One device -> host copy
         before the first launch (the offsets and av_index; the token vocabularies the tables are keyed by ride along unless the
@@ -585,17 +639,31 @@ class InfGenDecoder(nn.Module):
         if ik > 1 and not cfg.disable_insertion and cfg.use_grid_token:
             insert_uniforms = torch.rand(cfg.num_decode_steps, 10, S).numpy()
         debug = bool(int(os.getenv('DEBUG', 0)))
+        # log replay: the row mask in the Batch's global row order, on its device (the ingest kernel applies the row filter)
+        rp = None
+        if replay is None and replay_plan is not None:
+            raise ValueError('replay_plan overrides the logged future of the rows replay= flags: give replay= too')
+        if replay is not None:
+            st_idx = torch.as_tensor(ag['state_idx'])
+            rp = scene_setup.replay_global(replay, int(st_idx.shape[0]), torch.as_tensor(ag['av_index']).to(st_idx.device), B)
+            if replay_plan is not None:
+                if isinstance(replay_plan, (list, tuple)):
+                    replay_plan = {k_: torch.cat([torch.as_tensor(p_[k_]) for p_ in replay_plan])
+                                   for k_ in scene_setup.PLAN_KEYS if replay_plan[0].get(k_) is not None}
+                scene_setup.check_plan(replay_plan)
+                rp = (rp, {k_: v_ for k_, v_ in replay_plan.items() if v_ is not None})
 
         def make_engine(headroom=None):
             return RolloutEngine(w, None, vocab, map_vocab, grid, insert_headroom=headroom, force_enter=debug, sample_k=k,
                                  sample_uniforms=sample_uniforms, insert_k=ik if insert_uniforms is not None else 1,
                                  insert_uniforms=insert_uniforms, seed_outputs=not cfg.disable_insertion, copies=copies,
-                                 options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay)
+                                 options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay, replay=rp)
         ekey = ('graphs', S, tkey,
-                bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies)
+                bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies,
+                replay is not None)
         eng = self._engines.get(ekey)
         if eng is not None and eng.fits_batch(lay):
-            eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay)
+            eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay, replay=rp)
         else:
             eng = make_engine()
             if len(self._engines) >= 2:
@@ -723,7 +791,7 @@ class InfGenDecoder(nn.Module):
         return {'x_pt': x_pt, **self._flat_map_keys(x_pt, data, enc.ops, w), **{k: data[k] for k in self.data_keys if k in data}}
 
     @torch.no_grad()
-    def inference(self, data, sample_uniforms=None) -> Dict[str, torch.Tensor]:
+    def inference(self, data, sample_uniforms=None, replay=None, replay_plan=None) -> Dict[str, torch.Tensor]:
         """map encoder + closed-loop rollout of one scene (reference infgen_decoder.py:123-130).
         Greedy unless ``agent_encoder.motion_beam_size > 1``; then tokens are drawn by inverse CDF over the
         top-k probabilities with ``sample_uniforms`` ([steps][1][A]) or torch.rand when omitted.
@@ -734,12 +802,19 @@ class InfGenDecoder(nn.Module):
         the filter of agent_decoder.py:1609 (with insertion on: INFGEN_Q_MAX_AGENTS), since the kept counts are only known on
         the device when the uniforms are checked.
         The map-pretraining model (predict_motion / predict_state / predict_occ all False) returns the map encoder's dict plus the
-        data keys, single graph or Batch, as the reference does (``_map_model``)."""
+        data keys, single graph or Batch, as the reference does (``_map_model``).
+        ``replay`` (log replay; None: every agent is generated): 'ego', a bool tensor over ``data['agent']`` rows (the global row
+        order of a Batch) or a list of such tensors, one per graph - the flagged agents follow their logged future (token_idx /
+        state_idx / token_pos / token_heading from column hist_columns on) and the others are generated around them;
+        ``replay_plan`` = dict(token_idx, state_idx[, token_pos, token_heading]) over the same rows replaces the logged future
+        (a planner in the loop).  The dict then carries ``replay_mask`` (bool per returned row, after the row filter; inserted
+        agents False); the flagged rows' ``next_token_idx`` / ``next_state_idx`` / ``pos_a`` / ``head_a`` are the plan's and their
+        ``pred_traj`` / ``pred_head`` the plan's tokens integrated from the plan's poses."""
         if self.map_only():
             return self._map_model(data)
         if num_graphs(data) > 1:
-            return self._run_graphs(data, sample_uniforms=sample_uniforms)[0]
-        r = self._run(data, sample_uniforms=sample_uniforms)
+            return self._run_graphs(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan)[0]
+        r = self._run(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan)
         x_pt = r.pop('x_pt')
         map_enc = {'x_pt': x_pt, 'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=x_pt.device),
                    'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=x_pt.device),
@@ -754,24 +829,29 @@ class InfGenDecoder(nn.Module):
         return r.merged(first=map_enc)
 
     @torch.no_grad()
-    def inference_rollouts(self, data, n: int) -> List[Dict[str, torch.Tensor]]:
+    def inference_rollouts(self, data, n: int, replay=None, replay_plan=None) -> List[Dict[str, torch.Tensor]]:
         """``n`` independent rollouts of ONE scene (the reference's ``n_rollout_close_val`` loop, infgen/model/infgen.py:704-706,
         which calls ``inference(data.clone())`` n times) as one batch of n copies decoded in lockstep: with
         ``motion_beam_size`` / ``insert_beam_size`` > 1 every copy draws its own uniforms from torch's RNG, so the results are n
-        samples; greedy copies are identical.  ``data`` itself is not mutated (the copies are)."""
+        samples; greedy copies are identical.  ``data`` itself is not mutated (the copies are).  ``replay`` / ``replay_plan``
+        as in ``inference``: every copy replays the same plan."""
         # one engine batch of n copies of the scene over ONE map encoding (RolloutEngine(copies=n): the map-token graph, the map
         # encoder and the map K / V rows exist once - the reference offers inference_no_map(data, map_enc) for the same purpose);
         # every rollout carries what ``inference`` returns for it: the seed node's outputs and the map_next_token_* keys too
         if num_graphs(data) > 1:            # B graphs x n copies as one engine batch over B map encodings; n batched dicts
-            return self._run_graphs(data, copies=int(n), mutate=False)
-        return self.inference_batch([data.clone() if hasattr(data, 'clone') else dict(data)], seed_outputs=True, copies=int(n))
+            return self._run_graphs(data, copies=int(n), mutate=False, replay=replay, replay_plan=replay_plan)
+        return self.inference_batch([data.clone() if hasattr(data, 'clone') else dict(data)], seed_outputs=True, copies=int(n),
+                                    replay=replay, replay_plan=replay_plan)
 
     @torch.no_grad()
-    def inference_batch(self, datas: Sequence, seed_outputs: bool = False, copies: int = 1) -> List[Dict[str, torch.Tensor]]:
+    def inference_batch(self, datas: Sequence, seed_outputs: bool = False, copies: int = 1, replay=None,
+                        replay_plan=None) -> List[Dict[str, torch.Tensor]]:
         """throughput entry: many independent scenes decoded in lockstep on this GPU.  Every dict has the key set of
         ``inference``; the seed node's per-insertion arrays (``*_seed``) are recorded only with ``seed_outputs=True`` (5.5 MB per
-        scene), otherwise they are the zero arrays the reference initialises them to (agent_decoder.py:1746-1750)."""
-        rs = self._run(None, batch=datas, batch_seed_outputs=seed_outputs, copies=copies)
+        scene), otherwise they are the zero arrays the reference initialises them to (agent_decoder.py:1746-1750).
+        ``replay``: 'ego', one bool tensor per scene, or one over all scenes' rows in order; ``replay_plan``: one dict per scene
+        or one over all rows (see ``inference``)."""
+        rs = self._run(None, batch=datas, batch_seed_outputs=seed_outputs, copies=copies, replay=replay, replay_plan=replay_plan)
         if copies > 1:                          # ``copies`` rollouts per scene over one map encoding: scene 0's first, then scene 1's ...
             datas = [d for d in datas for _ in range(int(copies))]
         out = []

@@ -1,6 +1,6 @@
 """Scene setup of a batch (reference agent_decoder.py:1609-1719: filter, pad, zero the future, bos / eos, tmask / imask /
 catflag) and the inputs of the output epilogue - written ONCE, as torch statements over [S, A, ...] arrays on whatever
-device the inputs live on.  Host scene lists are first staged into such arrays (``stage_agents``: the row filter and slice
+device the inputs live on (log replay included: ``replay_arrays``, the plan of the rows that follow their logged future).  Host scene lists are first staged into such arrays (``stage_agents``: the row filter and slice
 copies, nothing else); a batch that arrives as stacked device tensors is passed as it is.  The ingest kernel
 (k_ingest_batch) is the independent second implementation: tests/test_batch_inference_gpu.py compares the two bit for bit.
 Nothing here reads engine state."""
@@ -163,3 +163,140 @@ def epilogue_inputs(ag: Mapping[str, torch.Tensor], valid: torch.Tensor, a_cap: 
                 p0=rows(ag['position'][:, :, 0, :2], f32), h0=rows(ag['heading'][:, :, 0], f32), ids=ids,
                 shp=rows(ag['shape'][:, :, hc - 1], f32), gt=rows(ag['position'][:, :, H:, :2], f32), val=rows(valid, torch.bool),
                 n0=n0, eval_shape=torch.tensor(EVAL_SHAPE, device=dev))
+
+
+# ------------------------------------------------------------------ log replay (RolloutEngine(replay=...))
+PLAN_KEYS = ('token_idx', 'state_idx', 'token_pos', 'token_heading')
+
+
+def replay_rows(replay, counts: Sequence[int], av: Sequence[int], device=None) -> List[torch.Tensor]:
+    """the public forms of ``replay=`` -> one bool row mask per scene.  ``replay``: 'ego', a bool tensor over the rows of all
+    scenes in scene order (the global row order of a Batch; for one scene its own rows), or one bool tensor per scene.
+    ``counts`` [B]: rows per scene (before the row filter), ``av`` [B]: each scene's ego row, local.  Raises ValueError when a
+    mask's length is not its scene's row count."""
+    B = len(counts)
+    if isinstance(replay, str):
+        if replay != 'ego':
+            raise ValueError(f"replay must be 'ego', a bool tensor or a list of bool tensors, not {replay!r}")
+        out = [torch.zeros(int(n), dtype=torch.bool, device=device) for n in counts]
+        for m, a in zip(out, av):
+            m[int(a)] = True
+        return out
+    if isinstance(replay, (list, tuple)):
+        if len(replay) != B:
+            raise ValueError(f'replay lists {len(replay)} masks for {B} scenes')
+        out = [torch.as_tensor(m).bool().reshape(-1) for m in replay]
+    else:
+        flat = torch.as_tensor(replay).bool().reshape(-1)
+        if flat.numel() != int(sum(counts)):
+            raise ValueError(f'replay mask of {flat.numel()} rows for {int(sum(counts))} agent rows')
+        out = list(flat.split([int(n) for n in counts]))
+    for s, (m, n) in enumerate(zip(out, counts)):
+        if m.numel() != int(n):
+            raise ValueError(f'replay mask of scene {s} has {m.numel()} rows, the scene has {int(n)}')
+    return out
+
+
+def replay_global(replay, n_rows: int, av_global: torch.Tensor, n_graphs: int) -> torch.Tensor:
+    """``replay=`` of a ragged Batch -> one bool mask over its N concatenated rows, on the Batch's device and without a host
+    copy ('ego': the global ego rows; a list: the graphs' masks concatenated)"""
+    dev = av_global.device
+    if isinstance(replay, str):
+        if replay != 'ego':
+            raise ValueError(f"replay must be 'ego', a bool tensor or a list of bool tensors, not {replay!r}")
+        m = torch.zeros(n_rows, dtype=torch.bool, device=dev)
+        m[av_global.reshape(-1).long()] = True
+        return m
+    if isinstance(replay, (list, tuple)):
+        if len(replay) != n_graphs:
+            raise ValueError(f'replay lists {len(replay)} masks for {n_graphs} graphs')
+        replay = torch.cat([torch.as_tensor(m).reshape(-1) for m in replay])
+    m = torch.as_tensor(replay).reshape(-1)
+    if m.numel() != n_rows:
+        raise ValueError(f'replay mask of {m.numel()} rows for {n_rows} agent rows')
+    return m.to(dev).bool()
+
+
+def check_plan(plan: Mapping) -> bool:
+    """a plan names its tokens and states; poses come as a pair or not at all.  -> does it carry poses?"""
+    if plan.get('token_idx') is None or plan.get('state_idx') is None:
+        raise ValueError('a replay plan needs token_idx and state_idx (poses - token_pos and token_heading - are optional)')
+    pose = [plan.get(k) is not None for k in ('token_pos', 'token_heading')]
+    if pose[0] != pose[1]:
+        raise ValueError('a replay plan carries token_pos and token_heading together or neither')
+    return pose[0]
+
+
+def stage_replay(scenes: Sequence[Mapping], filts: Sequence[np.ndarray], replay: Sequence, T: int
+                 ) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+    """host scenes + per-scene ``replay`` entries -> (row mask [S, max A] after the row filter, the plan ``replay_arrays``
+    takes: token_idx / state_idx [S, max A, T0] and, unless an explicit plan comes without them, token_pos / token_heading).
+    An entry is None (nothing replayed), a bool mask over the scene's rows - the plan is the scene's own logged future - or
+    (mask, tokens, states[, pos, head]) with (A, T) / (A, T, 2) arrays over the same rows."""
+    if len(replay) != len(scenes):
+        raise ValueError(f'replay has {len(replay)} entries for {len(scenes)} scenes')
+    masks, plans, poses = [], {k: [] for k in PLAN_KEYS}, set()
+    for s, (sc, f, r) in enumerate(zip(scenes, filts, replay)):
+        ag = sc['agent']
+        n = int(np.asarray(ag['state_idx']).shape[0])
+        src = {k: np.asarray(ag[k]) for k in PLAN_KEYS}
+        if isinstance(r, (tuple, list)):
+            if len(r) < 3 or r[1] is None or r[2] is None:
+                raise ValueError(f'replay plan of scene {s}: (mask, tokens, states[, pos, head]) - tokens and states are required')
+            m, explicit = r[0], dict(zip(PLAN_KEYS, list(r[1:]) + [None] * (5 - len(r))))
+            has_pose = check_plan(explicit)
+            src = {k: np.asarray(v) if v is not None else src[k] for k, v in explicit.items()}
+            if np.asarray(m).any():
+                poses.add(has_pose)
+        else:
+            m = np.zeros(n, bool) if r is None else r
+            if np.asarray(m).any():
+                poses.add(True)
+        m = np.asarray(m).astype(bool).reshape(-1)
+        if m.shape[0] != n:
+            raise ValueError(f'replay mask of scene {s} has {m.shape[0]} rows, the scene has {n}')
+        for k, v in src.items():
+            if v.shape[0] != n or v.shape[1] < T:
+                raise ValueError(f'replay plan of scene {s}: {k} has shape {v.shape}, need ({n}, >= {T} columns)')
+            plans[k].append(v[f])
+        masks.append(m[f])
+    if len(poses) > 1:
+        raise ValueError('the plans of one batch carry poses (the logged future always does) or none of them does')
+    plan = dict(token_idx=_stack(plans['token_idx'], -1, np.int64, T), state_idx=_stack(plans['state_idx'], INVALID, np.int64, T))
+    if poses != {False}:
+        plan.update(token_pos=_stack(plans['token_pos'], 0.0, np.float32, T), token_heading=_stack(plans['token_heading'], 0.0, np.float32, T))
+    mask = _stack([m[:, None] for m in masks], False, bool)[:, :, 0]
+    return torch.from_numpy(mask), {k: torch.from_numpy(v) for k, v in plan.items()}
+
+
+def replay_arrays(mask: torch.Tensor, plan: Mapping[str, torch.Tensor], hc: int, T: int, a_cap: int, copies: int = 1
+                  ) -> Dict[str, torch.Tensor]:
+    """the device arrays of a replayed batch in the engine's layout (InfgenRollout.teacher_* / replay_row), as torch statements
+    on whatever device ``mask`` [S, A] and ``plan`` (token_idx / state_idx [S, A, T0], optional token_pos [S, A, T0, 2] /
+    token_heading) live on: teacher_token / teacher_state int32 [S n][T][a_cap], teacher_pos / teacher_head, replay_row uint8
+    [S n][a_cap].  Columns hc .. T - 1 of the flagged rows hold the plan, everything else -1 / INVALID / 0 (what
+    k_ingest_batch writes); with ``copies`` = n every copy of a scene replays the same plan."""
+    has_pose = check_plan(plan)
+    tok, st = plan['token_idx'], plan['state_idx']
+    S, A, T0 = st.shape
+    if T0 < T:
+        raise ValueError(f'the plan covers {T0} token columns, the rollout has {T}')
+    if tuple(mask.shape) != (S, A) or A > a_cap:
+        raise ValueError(f'replay mask {tuple(mask.shape)} against a plan of {(S, A)} rows (at most {a_cap} per scene)')
+    dev = st.device
+    on = mask.to(dev).bool()[:, :, None] & (torch.arange(T, device=dev) >= hc)[None, None, :]
+
+    def put(x, fill, dtype):                 # [S, A, T0, ...] -> [S n][T][a_cap][...]
+        x = x[:, :, :T].to(dtype)
+        sel = on.reshape(on.shape + (1,) * (x.dim() - 3))
+        x = torch.where(sel, x, torch.full((), fill, dtype=dtype, device=dev))
+        out = torch.full((S, T, a_cap) + tuple(x.shape[3:]), fill, dtype=dtype, device=dev)
+        out[:, :, :A] = x.transpose(1, 2)
+        return out.repeat_interleave(copies, dim=0) if copies > 1 else out
+    out = dict(teacher_token=put(tok, -1, torch.int32), teacher_state=put(st, INVALID, torch.int32))
+    if has_pose:
+        out.update(teacher_pos=put(plan['token_pos'][..., :2], 0.0, torch.float32), teacher_head=put(plan['token_heading'], 0.0, torch.float32))
+    row = torch.zeros((S, a_cap), dtype=torch.uint8, device=dev)
+    row[:, :A] = mask.to(dev).to(torch.uint8)
+    out['replay_row'] = row.repeat_interleave(copies, dim=0) if copies > 1 else row
+    return out
