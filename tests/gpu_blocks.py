@@ -1,11 +1,12 @@
-"""Device-side helpers shared by the operator-level GPU tests (test_edge_builders_gpu.py, test_insertion_ops_gpu.py): guarded
+"""Device-side helpers shared by the operator-level GPU tests (test_edge_builders_gpu.py, test_insertion_ops_gpu.py,
+test_step_advance_gpu.py): guarded
 device buffers, InfgenEdgeBuf / InfgenRollout blocks over device copies of a graph_ref block.  Not a test module and not a conftest;
 torch and the library are only needed by the callers, which are GPU tests."""
 import numpy as np
 import torch
 
 GUARD = 64
-SENT_I, SENT_F = -123456789, -7.25e30
+SENT_I, SENT_F, SENT_B = -123456789, -7.25e30, 0xA5
 
 
 def dev():
@@ -19,9 +20,22 @@ def guarded(n, dtype, width=1):
     return t
 
 
+def _sentinel(dtype):
+    return SENT_F if dtype == torch.float32 else SENT_B if dtype == torch.uint8 else SENT_I
+
+
 def guard_intact(t, n, width=1):
     tail = t[n * width:]
-    return bool((tail == (SENT_F if t.dtype == torch.float32 else SENT_I)).all())
+    return bool((tail == _sentinel(t.dtype)).all())
+
+
+def guarded_copy(v):
+    """a flat device copy of a numpy array (float32, int32 or uint8) followed by a guard tail of GUARD sentinels"""
+    flat = torch.from_numpy(np.ascontiguousarray(v).reshape(-1))
+    t = torch.empty(flat.numel() + GUARD, device=dev(), dtype=flat.dtype)
+    t.fill_(_sentinel(flat.dtype))
+    t[:flat.numel()] = flat.to(dev())
+    return t
 
 
 class Edges:
@@ -45,13 +59,21 @@ class Edges:
                 self.raw[:4 * self.cap].cpu().numpy().reshape(-1, 4), int(self.total[0].item()))
 
 
-def device_block(st, edges=None):
-    """InfgenRollout over device copies of a graph_ref block; -> (block, the tensors by name)"""
+STEP_POINTERS = ('next_token', 'next_state', 'teacher_token', 'teacher_state', 'teacher_grid', 'teacher_pos', 'teacher_head',
+                 'replay_row', 'vocab', 'tok_tab', 'grid_tab', 'state_emb', 'cat_agent', 'cat_seed', 'raw2', 'cat', 'fus_in', 'tmp1',
+                 'tmp2', 'X', 'four_xa', 'fusion_pack')
+STEP_SCALARS = ('force_valid', 'no_state_token', 'no_grid_token')
+
+
+def device_block(st, edges=None, guard=()):
+    """InfgenRollout over device copies of a graph_ref block (and, when the dict holds them, of what graph_ref.new_step_ext adds:
+    absent or None keys stay null / zero); the arrays named in `guard` are flat copies with a guard tail (guarded_copy).
+    -> (block, the tensors by name)"""
     from infgen_amd import _lib
     ten = {}
     for k, v in st.items():
         if isinstance(v, np.ndarray):
-            ten[k] = torch.from_numpy(np.ascontiguousarray(v)).to(dev())
+            ten[k] = guarded_copy(v) if k in guard else torch.from_numpy(np.ascontiguousarray(v)).to(dev())
     b = _lib.Rollout()
     b.S, b.A_cap, b.T, b.M_cap, b.W, b.ring, b.R = st['S'], st['A_cap'], st['T'], st['M_cap'], st['W'], st['ring'], st['R']
     b.token_size, b.grid_size, b.num_layers = 2048, st['grid_size'], 1
@@ -60,6 +82,12 @@ def device_block(st, edges=None):
               'map_pos', 'map_orient', 'map_scene', 'first_new', 'hv_ovr', 'grid_xy', 'pred_traj', 'pred_head', 'pred_state'):
         if k in ten:
             setattr(b, k, ten[k].data_ptr())
+    for k in STEP_POINTERS:
+        if k in ten:
+            setattr(b, k, ten[k].data_ptr())
+    for k in STEP_SCALARS:
+        if st.get(k) is not None:
+            setattr(b, k, int(st[k]))
     if edges:
         b.et, b.em, b.ea = edges['t'].buf, edges['m'].buf, edges['a'].buf
     return b, ten

@@ -767,3 +767,421 @@ def gen_insert_finalize(seed=0, angle_interval=3.0):
     dec['offset'][6] = (30.0, -30.0)               # tanh saturates at +-1
     dec['offset'][9] = (1e-4, 0.0)
     return st, dec, c, angle_interval, n_heading
+
+
+# ------------------------------------------------------------------------------------------------ step advance: integrate, raw feature
+TOKEN_SIZE, EMB = 2048, 128
+SCRATCH_FILL = -7.25e30            # the scratch outputs of a block start out with it: what a kernel leaves alone is seen
+
+
+def step_vocab(seed=0):
+    """[3][2048][6][4][2] contours: per (type, token) a random rectangle (0.5 .. 6 m by 0.4 .. 2.5 m) moving on an arc, corners in
+    the order front-left, front-right, rear-right, rear-left (corner 0 - corner 3 points along the heading)"""
+    if seed not in _VOCAB:
+        rng = np.random.default_rng([seed, 4242])
+        n = 3 * TOKEN_SIZE
+        L, Wd = rng.uniform(0.5, 6.0, n), rng.uniform(0.4, 2.5, n)
+        dist, dth = rng.uniform(-1.0, 12.0, n), rng.uniform(-0.6, 0.6, n)
+        k = np.arange(6) / 5.0
+        ang = k[None] * dth[:, None]
+        ctr = np.stack([dist[:, None] * k[None] * np.cos(ang / 2), dist[:, None] * k[None] * np.sin(ang / 2)], -1)       # [n][6][2]
+        cor = np.stack([np.stack([L / 2, Wd / 2], -1), np.stack([L / 2, -Wd / 2], -1), np.stack([-L / 2, -Wd / 2], -1),
+                        np.stack([-L / 2, Wd / 2], -1)], 1)                                                             # [n][4][2]
+        cs, sn = np.cos(ang)[:, :, None], np.sin(ang)[:, :, None]
+        x = cor[:, None, :, 0] * cs - cor[:, None, :, 1] * sn + ctr[:, :, None, 0]
+        y = cor[:, None, :, 0] * sn + cor[:, None, :, 1] * cs + ctr[:, :, None, 1]
+        _VOCAB[seed] = np.stack([x, y], -1).astype(np.float32).reshape(3, TOKEN_SIZE, 6, 4, 2)
+    return _VOCAB[seed]
+
+
+_VOCAB, _CASES = {}, {}
+
+
+def step_grid(G, seed=0, spacing=3.0):
+    """the G innermost points of a square lattice (a circular mask, like the real 1961-cell grid), in shuffled order: the two cells
+    nearest to an agent fall in the same lane of the search (indices equal modulo 64) or in different ones"""
+    rng = np.random.default_rng([seed, G, 7])
+    h = int(math.ceil(math.sqrt(G / math.pi))) + 2
+    ij = np.mgrid[-h:h + 1, -h:h + 1].reshape(2, -1).T
+    keep = np.lexsort((np.arange(len(ij)), (ij ** 2).sum(1)))[:G]
+    assert len(keep) == G
+    return (ij[keep][rng.permutation(G)] * spacing).astype(np.float32)
+
+
+def new_step_ext(st, scratch=False):
+    """what infgen_integrate / infgen_raw_feature read beside a new_state block (kept apart: the dicts of the other tests' callers do
+    not change): scalars, next_token / next_state [S * A_cap], the optional teacher arrays [S][T][A_cap] and replay_row [S][A_cap],
+    the contour vocabulary, the embedding tables and - with scratch - the raw-feature outputs"""
+    rows = st['S'] * st['A_cap']
+    ext = dict(force_valid=0, no_state_token=0, no_grid_token=0,
+               next_token=np.zeros(rows, np.int32), next_state=np.zeros(rows, np.int32),
+               teacher_token=None, teacher_state=None, teacher_grid=None, teacher_pos=None, teacher_head=None, replay_row=None,
+               vocab=step_vocab(), tok_tab=None, grid_tab=None, state_emb=None, cat_agent=None, cat_seed=None)
+    if scratch:
+        for k, w in (('raw2', 4), ('cat', EMB), ('fus_in', 4 * EMB), ('tmp1', EMB), ('tmp2', EMB), ('X', EMB)):
+            ext[k] = np.full((rows, w), SCRATCH_FILL, np.float32)
+    return ext
+
+
+def integrate_ref(st, ext, t, f=np.float64, mutate=None):
+    """k_integrate: one decode step of column c = 1 + t into n = c + 1 (reference agent_decoder.py:2168-2239, attr_tokenizer.py:77-89)
+    -> the arrays of the block after the step (floats in f), plus per row < n_agents: 'new_pose' (x, y, theta before an INVALID row
+    is zeroed), 'search' (the first cell at the smallest distance, before teacher_grid) and 'gap' (second-smallest minus smallest
+    distance; inf with one cell).  Order of the state rules: index 2 -> EXIT, the ego VALID, no_state_token EXIT -> VALID,
+    force_valid all VALID.  Device-only (kernel header): teacher_token (negative: contour of token 0, the stored token stays),
+    teacher_state, teacher_pos / teacher_head (the stored pose, not pred_*), teacher_grid (where >= -1) - each only for the rows
+    replay_row flags (all rows without it); the ego's own flag decides the pose the search is centred on.
+    mutate: a deliberately wrong variant, for the tests that show the cases tell it apart ('old_ego': search centred on the ego's
+    pose of column c; 'dup_ignores_flag': rows outside the ego's 16-row group see the ego's generated pose; 'grid_ge0': teacher_grid
+    honoured from 0 only)."""
+    S, A_cap, G = st['S'], st['A_cap'], st['grid_size']
+    c, n = 1 + t, 2 + t
+    assert n < st['T'] and t * 5 + 5 <= st['R']
+    out = {k: st[k].copy() for k in ('state', 'token', 'grid', 'imask', 'catflag')}
+    for k in ('pos', 'head', 'pred_traj', 'pred_head', 'pred_state'):
+        out[k] = st[k].astype(f)
+    out['gap'] = np.full((S, A_cap), math.inf)
+    out['search'] = np.full((S, A_cap), -1, np.int64)
+    out['new_pose'] = np.zeros((S, A_cap, 3), f)
+    gxy = st['grid_xy'][:G].astype(f)
+    rr = None if ext['replay_row'] is None else ext['replay_row'].reshape(S, A_cap)
+    sl = slice(t * 5, t * 5 + 5)
+    for s in range(S):
+        A, av = int(st['n_agents'][s]), int(st['av_index'][s])
+        if A == 0:
+            continue
+        assert 0 <= av < A
+        rows = s * A_cap + np.arange(A)
+        tok, ns = ext['next_token'][rows].copy(), ext['next_state'][rows].copy()
+        ns[ns == 2] = EXIT
+        ns[av] = VALID
+        if ext['no_state_token']:
+            ns[ns == EXIT] = VALID
+        if ext['force_valid']:
+            ns[:] = VALID
+        forced = np.ones(A, bool) if rr is None else rr[s, :A] != 0
+        stored_tok = tok.copy()
+        if ext['teacher_token'] is not None:
+            tt = ext['teacher_token'][s, n, :A]
+            stored_tok = np.where(forced, tt, tok)
+            tok = np.where(forced, np.maximum(tt, 0), tok)
+        if ext['teacher_state'] is not None:
+            ns = np.where(forced, ext['teacher_state'][s, n, :A], ns)
+        th = st['head'][s, c, :A].astype(f)
+        cs, sn = np.cos(th)[:, None, None], np.sin(th)[:, None, None]
+        b = st['pos'][s, c, :A].astype(f)
+        ct = ext['vocab'][st['type'][s, :A], tok][:, 1:].astype(f)                 # [A][5][4][2]
+        x, y = ct[..., 0], ct[..., 1]
+        cx = (x * cs + y * (-sn)) + b[:, 0, None, None]                             # [x y] @ [[cos, sin], [-sin, cos]] + pos
+        cy = (x * sn + y * cs) + b[:, 1, None, None]
+        mx = (((cx[..., 0] + cx[..., 1]) + cx[..., 2]) + cx[..., 3]) / f(4)
+        my = (((cy[..., 0] + cy[..., 1]) + cy[..., 2]) + cy[..., 3]) / f(4)
+        hh = np.arctan2(cy[..., 0] - cy[..., 3], cx[..., 0] - cx[..., 3])
+        out['pred_traj'][rows, sl, 0], out['pred_traj'][rows, sl, 1] = mx, my
+        out['pred_head'][rows, sl] = hh
+        out['pred_state'][rows, sl] = ns[:, None]
+        lx, ly, lth = mx[:, 4].copy(), my[:, 4].copy(), hh[:, 4].copy()
+        own = (lx[av], ly[av], lth[av])                                             # the ego's generated pose
+        if ext['teacher_pos'] is not None:
+            lx = np.where(forced, ext['teacher_pos'][s, n, :A, 0].astype(f), lx)
+            ly = np.where(forced, ext['teacher_pos'][s, n, :A, 1].astype(f), ly)
+            lth = np.where(forced, ext['teacher_head'][s, n, :A].astype(f), lth)
+        ex, ey, eth = (np.full(A, v) for v in (lx[av], ly[av], lth[av]))
+        if mutate == 'old_ego':
+            ex, ey, eth = (np.full(A, v) for v in (b[av, 0], b[av, 1], th[av]))
+        if mutate == 'dup_ignores_flag' and A_cap > 16 and S <= 128:
+            other = np.arange(A) // 16 != av // 16
+            ex, ey, eth = (np.where(other, o, e) for o, e in zip(own, (ex, ey, eth)))
+        phi = -(eth - f(np.float32(math.pi / 2)))           # pi / 2 as the fp32 reference rounds it (tensor - python scalar), in every f
+        pc, ps = np.cos(phi), np.sin(phi)
+        dx, dy = lx - ex, ly - ey
+        rx, ry = dx * pc + dy * (-ps), dx * ps + dy * pc
+        ux, uy = rx[:, None] - gxy[None, :, 0], ry[:, None] - gxy[None, :, 1]
+        d = np.sqrt(ux * ux + uy * uy)
+        cell = d.argmin(1)                                                          # (the first of equal minima)
+        if G > 1:
+            two = np.partition(d, 1, axis=1)
+            out['gap'][s, :A] = two[:, 1] - two[:, 0]
+        out['search'][s, :A] = cell
+        out['new_pose'][s, :A] = np.stack([lx, ly, lth], -1)
+        inv = ns == INVALID
+        if ext['teacher_grid'] is not None:
+            tg = ext['teacher_grid'][s, n, :A]
+            cell = np.where(forced & (tg >= (0 if mutate == 'grid_ge0' else -1)), tg, cell)
+        out['state'][s, n, :A] = ns
+        out['pos'][s, n, :A, 0], out['pos'][s, n, :A, 1] = np.where(inv, f(0), lx), np.where(inv, f(0), ly)
+        out['head'][s, n, :A] = np.where(inv, f(0), lth)
+        out['grid'][s, n, :A] = np.where(inv, -1, cell)
+        out['token'][s, n, :A] = np.where(inv, -1, stored_tok)
+        out['imask'][s, n, :A] = np.where(inv, 0, st['imask'][s, n, :A])
+        out['catflag'][s, n, :A] = np.where(inv, 0, st['catflag'][s, n, :A])
+    return out
+
+
+def step_errors(ref, other, st, t):
+    """largest difference of two evaluations of a step over the rows < n_agents: (position [m] of the stored pose and pred_traj,
+    heading [rad] of the stored pose and pred_head, modulo 2 pi)"""
+    n, sl = 2 + t, slice(t * 5, t * 5 + 5)
+    live = np.arange(st['A_cap'])[None] < st['n_agents'][:, None]
+    if not live.any():
+        return np.zeros(2)
+    lr = live.reshape(-1)
+    f8 = lambda a: np.asarray(a, np.float64)
+    ep = max(np.abs(f8(ref['pos'])[:, n][live] - f8(other['pos'])[:, n][live]).max(),
+             np.abs(f8(ref['pred_traj'])[lr, sl] - f8(other['pred_traj'])[lr, sl]).max())
+    eh = max(ang_err(ref['head'][:, n][live], other['head'][:, n][live]).max(),
+             ang_err(ref['pred_head'][lr, sl], other['pred_head'][lr, sl]).max())
+    return np.asarray([ep, eh])
+
+
+def rawfeat_prep_ref(st, ext, col, rows=None, mask=None, f=np.float64):
+    """k_rawfeat_prep of column col (agent_decoder.py:2265-2285, _build_vector_a: 426-447) for every row of [S][A_cap] - or for the
+    compact slots of a row subset, a masked-off slot reading row 0.  -> raw2 (motion norm, bearing of the motion in the heading
+    frame), 'ruled' (1: the motion is a gap rule's (+-1, +-1), 2: (-2, -2); the norm is then the rounded root of 2 or 8), the
+    categorical row (cat_agent[row] where catflag, else cat_seed) and the token / state / grid embedding rows, by python indexing
+    (token -1 / -2 and grid -1 count from the end of their tables); grid None with no_grid_token"""
+    A_cap = st['A_cap']
+    if rows is None:
+        rows = np.arange(st['S'] * A_cap)
+    rows = np.asarray(rows, np.int64)
+    if mask is not None:
+        rows = np.where(np.asarray(mask) != 0, rows, 0)
+    s, ag = rows // A_cap, rows % A_cap
+    stj = st['state'][s, col, ag]
+    inv = stj == INVALID
+    m = np.zeros((len(rows), 2), f)
+    ruled = np.zeros(len(rows), np.int8)
+    if col > 0:
+        m = st['pos'][s, col, ag].astype(f) - st['pos'][s, col - 1, ag].astype(f)
+        pinv = st['state'][s, col - 1, ag] == INVALID
+        m[inv], ruled[inv] = f(INVALID_MOTION), 2
+        m[pinv & ~inv], ruled[pinv & ~inv] = f(MOTION_GAP), 1
+        m[~pinv & inv], ruled[~pinv & inv] = f(-MOTION_GAP), 1
+    else:
+        m[inv], ruled[inv] = f(INVALID_MOTION), 2
+        m[stj == ENTER], ruled[stj == ENTER] = f(MOTION_GAP), 1
+    h = st['head'][s, col, ag].astype(f)
+    hc, hs = np.cos(h), np.sin(h)
+    mx, my = m[:, 0], m[:, 1]
+    raw2 = np.stack([np.sqrt(mx * mx + my * my), np.arctan2(hc * my - hs * mx, (f(0) + hc * mx) + hs * my)], -1)
+    cat = np.where(st['catflag'][s, col, ag][:, None] != 0, ext['cat_agent'][rows], ext['cat_seed'][None])
+    tok = np.stack([ext['tok_tab'][int(ty)][int(k)] for ty, k in zip(st['type'][s, ag], st['token'][s, col, ag])])
+    grid = None if ext['no_grid_token'] else np.stack([ext['grid_tab'][int(g)] for g in st['grid'][s, col, ag]])
+    return dict(raw2=raw2, ruled=ruled, cat=cat, tok=tok, state=ext['state_emb'][stj], grid=grid)
+
+
+# Largest error of a plain fp32 numpy evaluation of a step (integrate_ref, the kernel's operation order) and of the raw feature's
+# motion pair against float64 over the inputs of gen_integrate (all INTEGRATE_CASES) and gen_rawfeat: position [m] and heading [rad]
+# of the stored pose and of pred_*, motion norm [m], motion bearing [rad].  As above: the figures tests/test_graph_ref_cpu.py
+# measures, rounded up in the fourth digit; the device bars are four times the figure.
+FP32_ERR_STEP_POS, FP32_ERR_STEP_HEAD, FP32_ERR_MOTION_NORM, FP32_ERR_MOTION_BEARING = 2.099e-5, 2.521e-5, 9.639e-7, 2.877e-7
+BAR_STEP_POS, BAR_STEP_HEAD = 4 * FP32_ERR_STEP_POS, 4 * FP32_ERR_STEP_HEAD
+BAR_MOTION_NORM, BAR_MOTION_BEARING = 4 * FP32_ERR_MOTION_NORM, 4 * FP32_ERR_MOTION_BEARING
+# Which cell is nearest is compared exactly, so outside the tie case no agent's nearest and second-nearest cell may be closer in
+# distance [m] than ten times the position bar
+GRID_MARGIN = 10 * BAR_STEP_POS
+
+STEP_T, STEP_R = 6, 20             # columns / pred slots of the integrate blocks: the last step t = 3 fills both to the end
+_RAGGED = [0, 1, 16, 17, -1]       # n_agents of the scenes of a batch, cycled (-1: A_cap)
+INTEGRATE_CASES = {
+    # name: (S, A_cap, n_agents (cycled; -1: A_cap), ego row (cycled; -1: the last row), G, step, force_valid, no_state_token,
+    #        teacher: None | 'all' (no flags) | 'ego' (mixed flags, the ego flagged) | 'noego' (mixed, the ego generated), what for)
+    'g2_first': (3, 32, [32, 17, 1], [0, 16, 0], 1961, 'first', 0, 0, None, '2 workgroups; the ego in the first / the second'),
+    'g2_last': (3, 32, [16, 0, 32], [15, 0, 31], 63, 'last', 0, 1, None, 'the last step that fits T and R; a scene without agents'),
+    'g2_force': (3, 32, [17, 32, 16], [0, 16, 15], 64, 'first', 1, 0, None, 'force_valid; a second workgroup with one row'),
+    'g2_both': (3, 32, [32, 1, 17], [-1, 0, 16], 65, 'last', 1, 1, None, 'force_valid and no_state_token'),
+    'g2_grid1': (3, 32, [17, 1, 32], [15, -1, 16], 1, 'first', 0, 0, None, 'a grid of one cell'),
+    'g64_global': (1, 1024, [1024], [-1], 2049, 'first', 0, 0, None, '64 workgroups, the ego in the last; the grid in global memory'),
+    'g64_lds': (1, 1024, [700], [0], 2048, 'last', 0, 1, 'ego', '64 workgroups, 20 of them empty, flags; the largest grid held in LDS'),
+    'g1_32': (129, 32, _RAGGED, [0, 15, 16, -1], 1961, 'first', 0, 0, None, '1 workgroup per scene: S > 128'),
+    'g1_96': (129, 96, _RAGGED + [65], [0, 15, 16, -1], 2049, 'last', 0, 0, 'noego', '16 waves loop over up to 96 agents; global grid'),
+    'teach_all': (3, 32, [32, 17, 16], [0, 16, 15], 1961, 'first', 0, 0, 'all', 'the five teacher arrays, no flags'),
+    'replay_ego': (3, 32, [32, 32, 17], [0, -1, 16], 1961, 'last', 0, 0, 'ego', 'flagged ego in another workgroup than flagged rows'),
+    'replay_noego': (3, 32, [32, 17, 32], [16, 0, 15], 65, 'first', 0, 1, 'noego', 'a generated ego among flagged rows'),
+    'replay_g1': (129, 32, _RAGGED, [16, 0, -1, 15], 64, 'last', 0, 0, 'ego', 'flags with one workgroup per scene'),
+    'ties': (3, 32, [32, 17, 32], [16, 0, -1], 197, 'first', 0, 0, 'all', 'agents exactly between 2 or 4 cells: the lowest index'),
+}
+
+
+def integrate_groups(S, A_cap):
+    """workgroups per scene of k_integrate (api.hip: integrate_groups)"""
+    return A_cap // 16 if S <= 128 and A_cap > 16 and A_cap % 16 == 0 else 1
+
+
+def gen_integrate(name, seed=0):
+    """-> (block, ext, t) of a named case.  Every array is filled: columns other than n, rows >= n_agents and the pred_* slots of
+    other steps hold values a step must leave alone.  Poses within +-200 m, headings over the full circle with +-pi among them,
+    types 0..2, tokens with 0 and 2047, next_state over {0, 1, 2} with an ego that predicts INVALID.  Outside 'ties' every agent
+    whose two nearest cells are closer in distance than twice GRID_MARGIN is drawn again.  Cached: do not write to the result."""
+    if (name, seed) in _CASES:
+        return _CASES[name, seed]
+    S, A_cap, nag, avs, G, step, force_valid, no_state, teacher, _ = INTEGRATE_CASES[name]
+    rng = np.random.default_rng([seed, sum(map(ord, name))])
+    T, R = STEP_T, STEP_R
+    t = 0 if step == 'first' else min(T - 3, R // 5 - 1)
+    c, n = 1 + t, 2 + t
+    st = new_state(S, A_cap, T, 32, G=G, R=R)
+    st['grid_xy'] = step_grid(G) if name != 'ties' else _tie_lattice(G, rng)
+    st['n_agents'][:] = [A_cap if nag[s % len(nag)] < 0 else nag[s % len(nag)] for s in range(S)]
+    st['av_index'][:] = [max(min(avs[s % len(avs)] if avs[s % len(avs)] >= 0 else A - 1, A - 1), 0) for s, A in enumerate(st['n_agents'])]
+    centre = rng.uniform(-120, 120, (S, 1, 1, 2))
+    draw_pos = lambda s, k=None: (centre[s, 0, 0] + rng.uniform(-70, 70, (2,) if k is None else (k, 2))).astype(np.float32)
+    st['pos'][:] = (centre + rng.uniform(-70, 70, st['pos'].shape)).astype(np.float32)
+    st['head'][:] = rng.uniform(-math.pi, math.pi, st['head'].shape).astype(np.float32)
+    edge = np.float32(math.pi)
+    st['head'][:, c, 1::7], st['head'][:, c, 2::7] = edge, -edge
+    st['head'][:, c, 3::7], st['head'][:, c, 4::7] = np.nextafter(edge, np.float32(0)), -np.nextafter(edge, np.float32(0))
+    st['state'][:] = rng.integers(0, 4, st['state'].shape)
+    st['token'][:] = rng.integers(-1, TOKEN_SIZE, st['token'].shape)
+    st['grid'][:] = rng.integers(-1, G, st['grid'].shape)
+    for k in ('tmask', 'imask', 'catflag'):
+        st[k][:] = rng.integers(0, 2, st[k].shape)
+    st['type'][:] = rng.integers(0, 3, st['type'].shape)
+    st['bos'][:] = rng.integers(0, T, st['bos'].shape)
+    for k in ('pred_traj', 'pred_head', 'pred_state'):
+        st[k][:] = rng.uniform(-5, 5, st[k].shape).astype(np.float32)
+    ext = new_step_ext(st)
+    ext['force_valid'], ext['no_state_token'] = force_valid, no_state
+    ext['next_token'][:] = rng.integers(0, TOKEN_SIZE, S * A_cap)
+    ext['next_token'][0::5], ext['next_token'][3::5] = 0, TOKEN_SIZE - 1
+    ext['next_state'][:] = rng.integers(0, 3, S * A_cap)
+    ext['next_state'][np.arange(S) * A_cap + st['av_index']] = np.arange(S) % 3          # an ego predicting INVALID / VALID / EXIT
+    if teacher:
+        sh = (S, T, A_cap)
+        ext['teacher_token'] = rng.integers(0, TOKEN_SIZE, sh).astype(np.int32)
+        ext['teacher_token'][:, :, 1::5] = -1
+        ext['teacher_token'][:, :, 2::11], ext['teacher_token'][:, :, 3::11] = TOKEN_SIZE - 1, 0
+        ext['teacher_state'] = rng.choice([INVALID, VALID, VALID, VALID, ENTER, EXIT], sh).astype(np.int32)
+        ext['teacher_grid'] = rng.integers(0, G, sh).astype(np.int32)
+        ext['teacher_grid'][:, :, 0::3], ext['teacher_grid'][:, :, 1::6] = -2, -1
+        ext['teacher_pos'] = (centre + rng.uniform(-70, 70, sh + (2,))).astype(np.float32)
+        ext['teacher_head'] = rng.uniform(-math.pi, math.pi, sh).astype(np.float32)
+        for s in range(S):
+            ext['teacher_state'][s, :, st['av_index'][s]] = VALID
+        if teacher != 'all':
+            ext['replay_row'] = rng.integers(0, 2, (S, A_cap)).astype(np.uint8)
+            ext['replay_row'][np.arange(S), st['av_index']] = 1 if teacher == 'ego' else 0
+    if name == 'ties':
+        _place_ties(st, ext, n, rng)
+    else:
+        for _ in range(100):
+            gap = integrate_ref(st, ext, t)['gap']
+            bad = np.argwhere(gap < 2 * GRID_MARGIN)
+            if len(bad) == 0:
+                break
+            for s, a in bad:
+                st['pos'][s, c, a] = draw_pos(s)
+                if teacher:
+                    ext['teacher_pos'][s, n, a] = draw_pos(s)
+        else:
+            raise AssertionError('generator could not clear the grid margin')
+    _CASES[name, seed] = (st, ext, t)
+    return _CASES[name, seed]
+
+
+def _tie_lattice(G, rng):
+    """the G innermost points of the lattice of spacing 2, shuffled"""
+    h = int(math.ceil(math.sqrt(G / math.pi))) + 2
+    ij = np.mgrid[-h:h + 1, -h:h + 1].reshape(2, -1).T
+    keep = np.lexsort((np.arange(len(ij)), (ij ** 2).sum(1)))[:G]
+    return (ij[keep][rng.permutation(G)] * 2).astype(np.float32)
+
+
+def _place_ties(st, ext, n, rng):
+    """every value of the search exact in fp32: the ego's teacher pose at integer coordinates with heading float32(pi / 2) (the frame
+    rotation is then by exactly 0), every other row's at integer offsets of at most 9 from it, teacher_grid -2 everywhere (the search
+    decides).  A row at (odd, even) or (even, odd) is equidistant from 2 cells, at (odd, odd) from 4.  The cell order is then
+    rearranged so that the two cells of four 2-way rows have indices 64 apart (the same lane) and those of four others sit in
+    different lanes with the lower index in the higher lane."""
+    S, A_cap = st['S'], st['A_cap']
+    ext['teacher_grid'][:] = -2
+    ext['teacher_state'][:, n] = np.where(ext['teacher_state'][:, n] == INVALID, VALID, ext['teacher_state'][:, n])
+    for s in range(S):
+        av = int(st['av_index'][s])
+        e = rng.integers(-150, 150, 2)
+        off = rng.integers(-9, 10, (A_cap, 2))
+        off[av] = 0
+        ext['teacher_pos'][s, n] = (e + off).astype(np.float32)
+        ext['teacher_head'][s, n, av] = np.float32(math.pi / 2)
+    g = st['grid_xy']
+    index_of = lambda p: int(np.nonzero((g == np.asarray(p, np.float32)).all(1))[0][0])
+    used = set()
+
+    def put(cell_xy, index):                      # move the cell at cell_xy to `index` by swapping
+        i = index_of(cell_xy)
+        g[[i, index]] = g[[index, i]]
+        used.update((index,))
+    s, av = 0, int(st['av_index'][0])
+    e = ext['teacher_pos'][0, n, av].astype(np.int64)
+    rows = [a for a in range(int(st['n_agents'][0])) if a != av][:8]
+    for k, a in enumerate(rows):
+        odd = (2 * (k % 4) + 1) * (1 if k % 2 else -1)
+        off = np.asarray([odd, 2 * (k - 3)]) if k < 4 else np.asarray([2 * (k - 6), 2 * (k - 4) + 3])      # 2-way ties, disjoint cells
+        ext['teacher_pos'][0, n, a] = (e + off).astype(np.float32)
+        # in the ego frame (rotation by 0) the row sits at `off`: its two nearest cells differ by +-1 in the odd coordinate
+        d = np.asarray([1, 0]) if k < 4 else np.asarray([0, 1])
+        lo, hi = (3 + k, 3 + k + 64) if k < 4 else (70 + k, 10 + k)                               # same lane / lower index in the higher lane
+        put(off - d, min(lo, hi))
+        put(off + d, max(lo, hi))
+
+
+def gen_rawfeat(seed=0):
+    """-> (block, ext): S = 3, A_cap = 32, T = 4, G = 65, poses a random walk within +-200 m (steps up to 12 m, some of exactly 0).
+    Scene 0 starts with hand-set rows over columns 0, 1, 2 - previous INVALID and current valid, previous valid and current
+    INVALID, both INVALID, ENTER at column 0, tokens -1 and -2, grid -1, catflag 0 and 1 - the rest is random over the same values;
+    rows >= n_agents are gathered like any other row and hold valid indices"""
+    if ('rawfeat', seed) in _CASES:
+        return _CASES['rawfeat', seed]
+    rng = np.random.default_rng([seed, 515])
+    S, A_cap, T, G = 3, 32, 4, 65
+    st = new_state(S, A_cap, T, 32, G=G)
+    st['n_agents'][:] = [32, 17, 1]
+    p = rng.uniform(-150, 150, (S, 1, A_cap, 2)) + np.cumsum(rng.uniform(-8.5, 8.5, (S, T, A_cap, 2)), 1)
+    st['pos'][:] = p.astype(np.float32)
+    st['pos'][:, 2, 5::6] = st['pos'][:, 1, 5::6]                 # stationary rows
+    st['head'][:] = rng.uniform(-math.pi, math.pi, st['head'].shape).astype(np.float32)
+    st['state'][:] = rng.choice([INVALID, VALID, VALID, ENTER, EXIT], st['state'].shape)
+    st['token'][:] = rng.integers(-2, TOKEN_SIZE, st['token'].shape)
+    st['token'][:, :, 3::7], st['token'][:, :, 4::7] = -1, -2
+    st['grid'][:] = rng.integers(-1, G, st['grid'].shape)
+    st['grid'][:, :, 2::5] = -1
+    st['catflag'][:] = rng.integers(0, 2, st['catflag'].shape)
+    st['type'][:] = rng.integers(0, 3, st['type'].shape)
+    hand = [(VALID, VALID, VALID), (INVALID, VALID, INVALID), (INVALID, INVALID, VALID), (ENTER, VALID, EXIT),
+            (VALID, INVALID, INVALID), (EXIT, ENTER, VALID), (INVALID, ENTER, INVALID)]
+    for a, states in enumerate(hand):
+        st['state'][0, :3, a] = states
+        st['type'][0, a] = a % 3
+        st['catflag'][0, :3, a] = (a % 2, 1 - a % 2, a % 2)
+    st['token'][0, :3, 0], st['token'][0, :3, 1], st['grid'][0, :3, 2] = (-1, -2, 5), (-2, -1, 0), (-1, 7, -1)
+    st['token'][0, :3, 3], st['token'][0, :3, 4], st['token'][0, :3, 5] = (0, TOKEN_SIZE - 1, -1), (TOKEN_SIZE - 1, 0, 0), (3, 3, TOKEN_SIZE - 1)
+    st['token'][0, :3, 6] = (-1, -2, 0)
+    st['grid'][0, :3, 3], st['grid'][0, :3, 4], st['grid'][0, :3, 5] = (G - 1, 0, -1), (0, G - 1, G - 1), (G - 1, 0, 0)
+    ext = new_step_ext(st, scratch=True)
+    rows = S * A_cap
+    ext['tok_tab'] = rng.standard_normal((3, TOKEN_SIZE + 2, EMB)).astype(np.float32)
+    ext['grid_tab'] = rng.standard_normal((G + 1, EMB)).astype(np.float32)
+    ext['state_emb'] = rng.standard_normal((4, EMB)).astype(np.float32)
+    ext['cat_agent'] = (rng.standard_normal((rows, EMB)) * 0.1).astype(np.float32)
+    ext['cat_seed'] = (rng.standard_normal(EMB) * 0.1).astype(np.float32)
+    _CASES['rawfeat', seed] = (st, ext)
+    return _CASES['rawfeat', seed]
+
+
+def take_step_scenes(st, ext, scenes):
+    """the block and ext of a list of scenes (repeats allowed): every per-scene array gathered, the shared ones kept"""
+    scenes = np.asarray(list(scenes))
+    S, A_cap = st['S'], st['A_cap']
+    o_st, o_ext = dict(st), dict(ext)
+    o_st['S'] = len(scenes)
+    for d, o in ((st, o_st), (ext, o_ext)):
+        for k, v in d.items():
+            if not isinstance(v, np.ndarray) or k in ('grid_xy', 'vocab', 'tok_tab', 'grid_tab', 'state_emb', 'cat_seed', 'map_pos',
+                                                      'map_orient', 'n_map'):
+                continue
+            if v.shape[0] == S * A_cap and k not in ('n_agents', 'av_index'):
+                o[k] = np.ascontiguousarray(v.reshape((S, A_cap) + v.shape[1:])[scenes].reshape((-1,) + v.shape[1:]))
+            else:
+                assert v.shape[0] == S, k
+                o[k] = np.ascontiguousarray(v[scenes])
+    return o_st, o_ext

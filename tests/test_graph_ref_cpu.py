@@ -361,3 +361,199 @@ def test_insert_finalize_generator():
     assert np.abs(np.tanh(dec['offset'][6].astype(np.float64))).min() == 1.0                 # saturated
     print(f'insert_finalize: fp32 numpy errors heading {herr:.4g} position {perr:.4g}')
     assert herr <= gr.FP32_ERR_INS_HEAD and perr <= gr.FP32_ERR_INS_POS
+
+
+# ------------------------------------------------------------------------------------------------ step advance: integrate, raw feature
+def _butterfly_pick(d, tie_break=True, strict=True):
+    """the kernel's search of one agent in fp32: 64 lanes over the cells g = lane, lane + 64, .. (strict <), then the xor butterfly
+    32 .. 1 with the (distance, index) tie-break; lane 0's result.  tie_break / strict False: the two mutations the tie case catches"""
+    best, bi = np.full(64, np.float32(np.inf)), np.full(64, 0x7fffffff, np.int64)
+    for g, v in enumerate(d):
+        ln = g % 64
+        if v < best[ln] or (not strict and v == best[ln]):
+            best[ln], bi[ln] = v, g
+    for o in (32, 16, 8, 4, 2, 1):
+        ob, oi = best[np.arange(64) ^ o], bi[np.arange(64) ^ o]
+        take = (ob < best) | ((ob == best) & (oi < bi) if tie_break else False)
+        best, bi = np.where(take, ob, best), np.where(take, oi, bi)
+    return int(bi[0])
+
+
+@pytest.mark.parametrize('name', list(gr.INTEGRATE_CASES))
+def test_integrate_generator(name):
+    """every case: the margin holds for every row (none is left uncompared), an fp32 evaluation in the kernel's order picks the
+    same cell, its pose errors stay within the recorded figures, the cell agrees with the oracle's encode_pos on the same new
+    poses, and the wrong variants of the reference differ from it where the case is meant to tell them apart"""
+    from oracle.rollout_oracle import encode_pos
+    st, ext, t = gr.gen_integrate(name)
+    S, A_cap, nag, avs, G, step, fv, nos, teacher, _ = gr.INTEGRATE_CASES[name]
+    n = 2 + t
+    ref, f32 = gr.integrate_ref(st, ext, t), gr.integrate_ref(st, ext, t, f=np.float32)
+    live = np.arange(A_cap)[None] < st['n_agents'][:, None]
+    assert (t == 0) == (step == 'first') and (step == 'first' or (n == st['T'] - 1 and t * 5 + 5 == st['R']))
+    assert (ref['search'][live] >= 0).all() and (ref['search'][~live] == -1).all()
+    if name != 'ties' and G > 1:
+        assert ref['gap'][live].min() > gr.GRID_MARGIN, ref['gap'][live].min()
+    assert np.array_equal(ref['search'], f32['search'])                      # (the tie case too: its distances are exact)
+    for k in ('state', 'token', 'grid', 'imask', 'catflag'):
+        assert np.array_equal(ref[k], f32[k]), k
+    e = gr.step_errors(ref, f32, st, t)
+    print(f'integrate {name}: fp32 numpy errors position {e[0]:.4g} heading {e[1]:.4g}')
+    assert e[0] <= gr.FP32_ERR_STEP_POS and e[1] <= gr.FP32_ERR_STEP_HEAD
+    assert np.abs(ref['new_pose'][..., :2]).max() < 200 + 20
+    grid = torch.from_numpy(st['grid_xy'][:G].astype(np.float64))
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)            # (the oracle builds its rotation in the default type)
+    try:
+        for s in range(S):
+            A, av = int(st['n_agents'][s]), int(st['av_index'][s])
+            if A:
+                p = torch.from_numpy(ref['new_pose'][s, :A])
+                untied = ref['gap'][s, :A] > 0          # (the oracle's frame is turned by pi / 2 - float32(pi / 2): exact ties break)
+                assert np.array_equal(encode_pos(grid, p[:, :2], p[av, :2], p[av, 2]).numpy()[untied], ref['search'][s, :A][untied]), s
+    finally:
+        torch.set_default_dtype(prev)
+    # what the case is for
+    assert gr.integrate_groups(S, A_cap) == (1 if S > 128 else A_cap // 16)
+    valid_new = ref['state'][:, n][live] != gr.INVALID
+    if not fv and teacher != 'all':
+        assert (~valid_new).any()
+    assert not (fv and (~valid_new).any())
+    new_tok = ref['token'][:, n][live]
+    assert set(st['type'][live].tolist()) == {0, 1, 2} or live.sum() < 20
+    if live.sum() >= 20:
+        assert (new_tok == 0).any() and (new_tok == gr.TOKEN_SIZE - 1).any()
+    if teacher:
+        forced = np.ones((S, A_cap), bool) if ext['replay_row'] is None else ext['replay_row'] != 0
+        tg, tt = ext['teacher_grid'][:, n], ext['teacher_token'][:, n]
+        vn = ref['state'][:, n] != gr.INVALID
+        on = live & forced & vn
+        assert (ref['token'][:, n][on & (tt < 0)] == -1).any()                              # the stored token stays negative
+        if name != 'ties':
+            assert (on & (tg == -1)).any() and (on & (tg == -2)).any() and (on & (tg >= 0)).any()
+            assert (ref['grid'][:, n][on & (tg >= -1)] == tg[on & (tg >= -1)]).all()
+            assert (ref['grid'][:, n][on & (tg == -2)] == ref['search'][on & (tg == -2)]).all()
+            assert not np.array_equal(gr.integrate_ref(st, ext, t, mutate='grid_ge0')['grid'], ref['grid'])
+        ego_flag = forced[np.arange(S), st['av_index']][st['n_agents'] > 0]
+        if teacher == 'ego':
+            assert ego_flag.all() and (live & ~forced).any()
+            if S <= 128:                       # a flagged row in another workgroup than the flagged ego: the dup thread's flag
+                grp = np.arange(A_cap)[None] // 16 != (st['av_index'] // 16)[:, None]
+                assert (on & grp).any()
+                mut = gr.integrate_ref(st, ext, t, mutate='dup_ignores_flag')
+                assert (mut['grid'][:, n][on & grp & (tg == -2)] != ref['grid'][:, n][on & grp & (tg == -2)]).any()
+        if teacher == 'noego':
+            assert not ego_flag.any() and (live & forced).any()
+    if G > 1 and name != 'ties' and live.sum() > 1:
+        mut = gr.integrate_ref(st, ext, t, mutate='old_ego')
+        assert (mut['search'][live] != ref['search'][live]).mean() > 0.2                     # the ego's NEW pose is the centre
+
+
+def test_integrate_cases_cover_the_paths():
+    """over all cases: the grid sizes around the 64-lane trip and the 2048-cell LDS limit, n_agents 0 / 1 / 16 / 17 / A_cap, the ego at
+    row 0 / 15 / 16 / the last, in the first / the last / another workgroup, both steps, the flags singly and together, an ego that
+    predicts INVALID, headings at +-pi"""
+    Gs, nags, egos, where, flags, steps = set(), set(), set(), set(), set(), set()
+    for name, (S, A_cap, nag, avs, G, step, fv, nos, teacher, _) in gr.INTEGRATE_CASES.items():
+        st, ext, t = gr.gen_integrate(name)
+        Gs.add(G)
+        flags.add((fv, nos))
+        steps.add(step)
+        groups = gr.integrate_groups(S, A_cap)
+        for s in range(S):
+            A, av = int(st['n_agents'][s]), int(st['av_index'][s])
+            nags.add('cap' if A == A_cap else A)
+            if A:
+                egos.update({av} & {0, 15, 16}, {'last'} if av == A - 1 else set())
+                assert ext['next_state'][s * A_cap + av] == s % 3
+                if groups > 1 and A > 16:
+                    where.update({'first'} if av < 16 else set(), {'last'} if av // 16 == (A - 1) // 16 and av >= 16 else set(),
+                                 {'middle'} if 16 <= av and av // 16 < (A - 1) // 16 else set())
+        h = st['head'][:, 1 + t]
+        assert (h == np.float32(math.pi)).any() and (h == -np.float32(math.pi)).any()
+    assert Gs >= {1, 63, 64, 65, 1961, 2048, 2049}
+    assert nags >= {0, 1, 16, 17, 'cap'} and egos >= {0, 15, 16, 'last'} and where >= {'first', 'last'}
+    assert flags == {(0, 0), (1, 0), (0, 1), (1, 1)} and steps == {'first', 'last'}
+    assert {(S, A) for S, A, *_ in gr.INTEGRATE_CASES.values()} >= {(3, 32), (1, 1024), (129, 32), (129, 96)}
+
+
+def test_integrate_tie_case():
+    """all values of the search are small integers: fp32 is exact, tied distances are equal bit for bit.  2- and 4-way ties occur;
+    the hand-placed pairs sit 64 apart (one lane) and in different lanes with the lower index in the higher lane; the emulated
+    kernel search equals the reference on every row, and differs without the `oi < bi` tie-break and with `<=` inside a lane"""
+    st, ext, t = gr.gen_integrate('ties')
+    n = 2 + t
+    ref = gr.integrate_ref(st, ext, t)
+    g = st['grid_xy'].astype(np.float64)
+    assert np.array_equal(g, np.round(g)) and (g % 2 == 0).all()
+    ways, same_lane, inverted, broke, loose = set(), 0, 0, 0, 0
+    for s in range(st['S']):
+        A, av = int(st['n_agents'][s]), int(st['av_index'][s])
+        assert ext['teacher_head'][s, n, av] == np.float32(math.pi / 2)
+        rel = (ext['teacher_pos'][s, n, :A] - ext['teacher_pos'][s, n, av]).astype(np.float64)
+        assert np.array_equal(rel, np.round(rel)) and np.abs(rel).max() <= 9
+        for a in range(A):
+            d = np.sqrt(((rel[a][None] - g) ** 2).sum(1).astype(np.float32))
+            tied = np.nonzero(d == d.min())[0]
+            ways.add(len(tied))
+            assert len(tied) == (1, 2, 2, 4)[int(rel[a, 0] % 2) + int(rel[a, 1] % 2) * 2 if (rel[a] % 2).sum() < 2 else 3]
+            assert ref['search'][s, a] == tied[0] == ref['grid'][s, n, a] and (ref['gap'][s, a] == 0) == (len(tied) > 1)
+            assert _butterfly_pick(d) == tied[0]
+            broke += _butterfly_pick(d, tie_break=False) != tied[0]
+            loose += _butterfly_pick(d, strict=False) != tied[0]
+            if len(tied) == 2:
+                same_lane += (tied[1] - tied[0]) % 64 == 0
+                inverted += tied[0] % 64 > tied[1] % 64
+    assert ways == {1, 2, 4} and same_lane >= 4 and inverted >= 4 and broke >= 4 and loose >= 4
+    # the rotation of the search frame is by exactly zero in fp32
+    assert -(np.float32(math.pi / 2) - np.float32(math.pi / 2)) == 0
+
+
+def test_rawfeat_generator():
+    """every gap rule at the columns the GPU test calls, tokens -1 / -2, grid -1, both catflags, all types; python indexing of the
+    tables; the fp32 figures of the motion pair"""
+    st, ext = gr.gen_rawfeat()
+    G = st['grid_size']
+    en = eb = 0.0
+    for col in (0, 1, 2):
+        ref, f32 = gr.rawfeat_prep_ref(st, ext, col), gr.rawfeat_prep_ref(st, ext, col, f=np.float32)
+        sc = st['state'][:, col].reshape(-1)
+        inv = sc == gr.INVALID
+        if col:
+            pinv = st['state'][:, col - 1].reshape(-1) == gr.INVALID
+            assert (pinv & ~inv).any() and (~pinv & inv).any() and (pinv & inv).any() and (~pinv & ~inv).any()
+            assert np.array_equal(ref['ruled'], np.where(pinv & inv, 2, np.where(pinv | inv, 1, 0)))
+        else:
+            assert (sc == gr.ENTER).any() and inv.any()
+            assert np.array_equal(ref['ruled'], np.where(inv, 2, np.where(sc == gr.ENTER, 1, 0)))
+            assert (ref['raw2'][ref['ruled'] == 0] == 0).all()                              # no motion into column 0
+        assert np.array_equal(ref['raw2'][ref['ruled'] == 1, 0].astype(np.float32), np.full((ref['ruled'] == 1).sum(), np.float32(math.sqrt(2))))
+        assert np.array_equal(ref['raw2'][ref['ruled'] == 2, 0].astype(np.float32), np.full((ref['ruled'] == 2).sum(), np.float32(2 * math.sqrt(2))))
+        tok, grd, cf = (st[k][:, col].reshape(-1) for k in ('token', 'grid', 'catflag'))
+        assert {-1, -2, 0, gr.TOKEN_SIZE - 1} <= set(tok.tolist()) and {-1, 0, G - 1} <= set(grd.tolist()) and set(cf.tolist()) == {0, 1}
+        ty = st['type'].reshape(-1)
+        assert set(ty.tolist()) == {0, 1, 2}
+        r = int(np.nonzero(tok == -1)[0][0])
+        assert np.array_equal(ref['tok'][r], ext['tok_tab'][ty[r], gr.TOKEN_SIZE + 1])        # no_token row; -2: the bos row
+        r = int(np.nonzero(tok == -2)[0][0])
+        assert np.array_equal(ref['tok'][r], ext['tok_tab'][ty[r], gr.TOKEN_SIZE])
+        r = int(np.nonzero(grd == -1)[0][0])
+        assert np.array_equal(ref['grid'][r], ext['grid_tab'][G])
+        r = int(np.nonzero(cf == 0)[0][0])
+        assert np.array_equal(ref['cat'][r], ext['cat_seed']) and np.array_equal(ref['state'][r], ext['state_emb'][sc[r]])
+        en = max(en, np.abs(ref['raw2'][:, 0] - f32['raw2'][:, 0]).max())
+        eb = max(eb, gr.ang_err(ref['raw2'][:, 1], f32['raw2'][:, 1]).max())
+    # a row subset: compact slots, a masked-off slot reads row 0
+    sub = gr.rawfeat_prep_ref(st, ext, 1, rows=[40, 7, 95], mask=[1, 0, 1])
+    full = gr.rawfeat_prep_ref(st, ext, 1)
+    for k in ('raw2', 'cat', 'tok', 'state', 'grid'):
+        assert np.array_equal(sub[k], full[k][[40, 0, 95]]), k
+    print(f'raw feature: fp32 numpy errors motion norm {en:.4g} bearing {eb:.4g}')
+    assert en <= gr.FP32_ERR_MOTION_NORM and eb <= gr.FP32_ERR_MOTION_BEARING
+
+
+def test_step_figures_are_the_recorded_ones():
+    """GRID_MARGIN is ten times the position bar, the bars four times the figures"""
+    assert gr.GRID_MARGIN == 10 * gr.BAR_STEP_POS == 40 * gr.FP32_ERR_STEP_POS
+    assert (gr.BAR_STEP_HEAD, gr.BAR_MOTION_NORM, gr.BAR_MOTION_BEARING) == (4 * gr.FP32_ERR_STEP_HEAD, 4 * gr.FP32_ERR_MOTION_NORM,
+                                                                           4 * gr.FP32_ERR_MOTION_BEARING)
