@@ -28,15 +28,55 @@ static int check_launch(const char* where) {
 
 extern "C" const char* infgen_last_error(void) { return g_err.c_str(); }
 
+// ---------------------------------------------------------------------------------- environment knobs
+// Experiment and diagnostic switches (tools/, profiles/): each is read once, when the library is loaded.
+static int env_int(const char* name, int dflt, bool* is_set = nullptr) {
+  const char* e = getenv(name);
+  if (is_set) *is_set = e != nullptr;
+  return e ? atoi(e) : dflt;
+}
+static int env_layers_p() { const int v = env_int("INFGEN_LAYERS_P", 1); return v < 0 ? 0 : v > 2 ? 2 : v; }
+static int env_lp_rows_min() {         // INFGEN_LP_ROWS8 (non-zero: 8, zero: 16) takes precedence over INFGEN_LP_ROWS_MIN
+  bool set8 = false;
+  const int rows8 = env_int("INFGEN_LP_ROWS8", 0, &set8);
+  return set8 ? (rows8 ? 8 : 16) : env_int("INFGEN_LP_ROWS_MIN", 4);
+}
+namespace knob {
+const int layers_p = env_layers_p();                              // clamped to 0..2: default of the layers_p option (infgen_set_layers_p)
+const int qs_dbg = env_int("INFGEN_QS_DBG", 0);                   // FourierArgs.dbg / AttnHArgs.dbg (diagnostics; wrong results)
+const int fh12_min = env_int("INFGEN_FH12_MIN", 150000);          // smallest capacity that takes k_fourier_h12 (0: never)
+const int fh12_multi_rows = env_int("INFGEN_FH12_MULTI_ROWS", 0); // smallest launch, in rows, whose multi-set launch takes k_fourier_h12_multi (0: never)
+const int fourier_nomulti = env_int("INFGEN_FOURIER_NOMULTI", 0); // 1: the step's Fourier sets one launch each
+const int attn_hs_max = env_int("INFGEN_ATTN_HS_MAX", 6144);      // attn_mode 2: most rows that take k_attn_hs
+const int attn_waves = env_int("INFGEN_ATTN_WAVES", IG_QSU ? 8 : 4);      // 8: the 128-row variant of k_attn_h
+const int warm = env_int("INFGEN_WARM", 1);                       // 0: no warm workgroups
+const int warm_max_groups = env_int("INFGEN_WARM_MAX_GROUPS", 128);       // launches of more 16-row groups never carry any
+const int edge_dbg = env_int("INFGEN_EDGE_DBG", 0);               // EdgeFusedArgs.dbg (timing experiments; bit 7: trace with -DIG_EF_TRACE=1)
+const int edge_noxcd = env_int("INFGEN_EDGE_NOXCD", 0);           // bit 0: no XCD-aware tile order, bit 1: no kv_once
+const int edge_small = env_int("INFGEN_EDGE_SMALL", 4096);        // most rows of the one-group-per-workgroup k_edge_fused launch
+const int edge_wg2 = env_int("INFGEN_EDGE_WG2", 1);               // 0: one 16-wave workgroup of two groups per CU for large launches
+const int edge_lds_pad = env_int("INFGEN_EDGE_LDS_PAD", 0);       // dynamic LDS bytes on top of k_edge_fused3's own (co-residency experiment)
+const int heads_nosplit = env_int("INFGEN_HEADS_NOSPLIT", 0);     // 1: k_heads never deals its logit chunks to several workgroups
+const int be_wide_scenes = env_int("INFGEN_BE_WIDE_SCENES", 128); // largest batch whose k_build_edges runs 16 waves per workgroup whatever A_cap
+const int int_group_scenes = env_int("INFGEN_INT_GROUP_SCENES", 128);     // largest batch whose k_integrate runs 16 rows per workgroup
+const int no_tail_fold = env_int("INFGEN_NO_TAIL_FOLD", 0);       // 1: infgen_rollout_run is a loop over infgen_decode_step
+const int lp_max_chunks = env_int("INFGEN_LP_MAX_CHUNKS", 2);     // most k_layers_p launches a batch may be split into
+const int lp_max_groups = env_int("INFGEN_LP_MAX_GROUPS", 256);   // most workgroups of one k_layers_p launch
+const int lp_rows_min = env_lp_rows_min();                        // fewest rows per k_layers_p workgroup (4, 8 or 16)
+const int lp_trace = env_int("INFGEN_LP_TRACE", 0);               // n: dump the stamps of the n-th k_layers_p launch (tools/lp_trace.py)
+// polls at a scene counter before k_layers_p traps (layers_p_launch); any strtoul base, and set differs from unset
+const char* const lp_spin_str = getenv("INFGEN_LP_SPIN_LIMIT");
+const unsigned lp_spin_limit = lp_spin_str ? (unsigned)strtoul(lp_spin_str, nullptr, 0) : 0u;
+}  // namespace knob
+
 // ---------------------------------------------------------------------------------- options
 // Every switch that changes what a launch does lives in an InfgenOptions.  g_def holds the process-wide defaults the
 // infgen_set_* functions edit (used by the operator-level entries and by contexts with opts.use == 0); a rollout-level entry
 // called with a context whose opts.use != 0 installs that context's block for the duration of the call (thread-local), so
 // contexts of one process do not see each other's settings.
 namespace {
-int layers_p_default() { const char* e = getenv("INFGEN_LAYERS_P"); const int v = e ? atoi(e) : 1; return v < 0 ? 0 : v > 2 ? 2 : v; }
 InfgenOptions g_def = {0, /*attn_mode*/ 2, /*gemm_terms*/ 3, /*fourier_mode*/ 1, /*edge_fuse*/ 1, /*edge_loop*/ 6, /*overlap*/ 0,
-                       /*row_group_margin*/ 0, /*layers_p*/ layers_p_default(), /*rhat_format*/ 0, /*edge_kernel*/ 1, 0, nullptr, nullptr};
+                       /*row_group_margin*/ 0, /*layers_p*/ knob::layers_p, /*rhat_format*/ 0, /*edge_kernel*/ 1, 0, nullptr, nullptr};
 int g_def_group_rows = 0;                  // rows of the layout the process-wide group list belongs to
 const int* g_def_limit_n_agents = nullptr; // process-wide row limits (infgen_set_row_limits)
 int g_def_limit_A_cap = 0;
@@ -250,6 +290,20 @@ extern "C" int infgen_fourier_pack_offset(const char* f, int n, int dim) {
 
 // ---------------------------------------------------------------------------------- launchers
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// 64-row tiles (k_attn_h<4>, k_heads_h, k_map_head_h, k_mlpemb_h): two workgroups per CU, persistent over the tiles beyond that
+static inline int grid64(int rows) { const int g = ceil_div(rows, 64); return g > 512 ? 512 : g; }
+
+// The kernels of a split family share one signature: k3 the fp16 three-term split (gemm_terms 3), kb16 bf16-precision operands (2),
+// k1 plain fp16 operands (1).  Every launch of such a family picks its kernel here.
+template <typename Kern> static Kern by_terms(Kern k3, Kern kb16, Kern k1) {
+  switch (O().gemm_terms) {
+    case 1: return k1;
+    case 2: return kb16;
+    default: return k3;
+  }
+}
+// k_fourier_h12 and k_layers_p exist in the three-term form only
+static inline bool three_terms() { return O().gemm_terms == 3; }
 
 extern "C" int infgen_linear(const float* X, int ldx, const int* gather, int rows, int K,
                              const float* Wp, int Np, const float* bias, int N,
@@ -326,9 +380,39 @@ extern "C" int infgen_set_fourier_mode(int mode) {
   return 0;
 }
 
-static int qs_dbg() {
-  static const int v = getenv("INFGEN_QS_DBG") ? atoi(getenv("INFGEN_QS_DBG")) : 0;
-  return v;
+// prof: the profiler's row counter, on unless dt_mode == 2 (that launch writes the table, it embeds no rows).  dbg stays 0 here:
+// launch_fourier sets it for the single-set kernels, the multi-set launch leaves it 0
+static FourierArgs fourier_args(const float* raw, int n, const int* count_dev, int e_cap, const float* pack, const float* cat, int ldcat,
+                                float* out, int ldo, int normalize, int out_r24, const float* dt_tab = nullptr, int dt_mode = 0) {
+  return FourierArgs{raw, n, count_dev, e_cap, pack, cat, ldcat, out, ldo, normalize,
+                     (g_prof.mask >> INFGEN_KID_FOURIER) & 1u && dt_mode != 2 ? g_prof.rows_dev : nullptr, out_r24, dt_tab, dt_mode, 0};
+}
+
+// workgroups of a split Fourier launch over `cap` rows: 128-row tiles (8 waves x 16 rows; wide: 192), persistent, one workgroup
+// per CU (fourier_h.hip explains why)
+static inline int fourier_h_grid(int cap, bool wide) {
+  const int grid = ceil_div(cap, wide ? FH12_TILE : FH_TILE);
+  return grid > 256 * FH_WG_PER_CU ? 256 * FH_WG_PER_CU : grid;
+}
+
+// one set in one launch (the entries below have checked the arguments; the step's own sets need no check)
+static int launch_fourier(const FourierArgs& a_in, void* stream) {
+  if (a_in.e_cap <= 0) return 0;
+  FourierArgs a = a_in;
+  a.dbg = knob::qs_dbg;
+  { ProfScope _ps(INFGEN_KID_FOURIER, stream);
+    if (O().fourier_mode == 0) {
+      int grid = ceil_div(a.e_cap, TR);
+      if (grid > 2048) grid = 2048;
+      hipLaunchKernelGGL(k_fourier, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);
+    } else {
+      // large sets: the three-wave-group variant (fourier_h12.hip)
+      const bool wide = knob::fh12_min > 0 && a.e_cap >= knob::fh12_min && three_terms() && FH_WAVES == 8;
+      const int grid = fourier_h_grid(a.e_cap, wide);
+      if (wide) hipLaunchKernelGGL(k_fourier_h12<3>, dim3(grid), dim3(FH12_NT), 0, (hipStream_t)stream, a);
+      else hipLaunchKernelGGL(by_terms(k_fourier_h<3>, k_fourier_h_b16<1>, k_fourier_h<1>), dim3(grid), dim3(FH_NT), 0, (hipStream_t)stream, a);
+    } }
+  return check_launch("infgen_fourier_embed");
 }
 
 // out_r24: rows in the packed 24-bit format of kernels.h (k_fourier_h only; the rollout's private rhat buffers)
@@ -340,26 +424,7 @@ static int fourier_embed_impl(const float* raw, int n, const int* count_dev, int
   if (out_r24 && O().fourier_mode == 0) return fail("infgen_fourier_embed", "packed rows need the split kernel");
   if (dt_mode && (O().fourier_mode == 0 || n < 2 || (dt_mode == 1 && !dt_tab)))
     return fail("infgen_fourier_embed", "the last-dim table needs the split kernel, n_dims >= 2 and a table");
-  FourierArgs a{raw, n, count_dev, e_cap, pack, cat, ldcat, out, ldo, normalize,
-                (g_prof.mask >> INFGEN_KID_FOURIER) & 1u && dt_mode != 2 ? g_prof.rows_dev : nullptr, out_r24, dt_tab, dt_mode, qs_dbg()};
-  if (O().fourier_mode == 0) {
-    int grid = ceil_div(e_cap, TR);
-    if (grid > 2048) grid = 2048;
-    ProfScope _ps(INFGEN_KID_FOURIER, stream);
-    hipLaunchKernelGGL(k_fourier, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);
-  } else {
-    // large sets: the three-wave-group variant (fourier_h12.hip); INFGEN_FH12_MIN = smallest capacity that takes it (0: never)
-    static const int fh12_min = getenv("INFGEN_FH12_MIN") ? atoi(getenv("INFGEN_FH12_MIN")) : 150000;
-    const bool wide = fh12_min > 0 && e_cap >= fh12_min && O().gemm_terms == 3 && FH_WAVES == 8;
-    int grid = ceil_div(e_cap, wide ? FH12_TILE : FH_TILE);     // 128-row tiles (8 waves x 16 rows), persistent
-    if (grid > 256 * FH_WG_PER_CU) grid = 256 * FH_WG_PER_CU;          // one workgroup per CU (fourier_h.hip explains why)
-    ProfScope _ps(INFGEN_KID_FOURIER, stream);
-    if (wide) hipLaunchKernelGGL(k_fourier_h12<3>, dim3(grid), dim3(FH12_NT), 0, (hipStream_t)stream, a);
-    else if (O().gemm_terms == 1) hipLaunchKernelGGL(k_fourier_h<1>, dim3(grid), dim3(FH_NT), 0, (hipStream_t)stream, a);
-    else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_fourier_h_b16<1>, dim3(grid), dim3(FH_NT), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_fourier_h<3>, dim3(grid), dim3(FH_NT), 0, (hipStream_t)stream, a);
-  }
-  return check_launch("infgen_fourier_embed");
+  return launch_fourier(fourier_args(raw, n, count_dev, e_cap, pack, cat, ldcat, out, ldo, normalize, out_r24, dt_tab, dt_mode), stream);
 }
 
 extern "C" int infgen_fourier_embed(const float* raw, int n, const int* count_dev, int e_cap, const float* pack,
@@ -386,10 +451,6 @@ extern "C" int infgen_set_attn_mode(int mode) {
   g_def.attn_mode = mode;
   return 0;
 }
-static int hs_max_rows() {
-  static const int v = getenv("INFGEN_ATTN_HS_MAX") ? atoi(getenv("INFGEN_ATTN_HS_MAX")) : 6144;
-  return v;
-}
 // the kernels of the other split families (k_heads_h, k_mlpemb_h) keep the by-size rule of the 64-row tiles
 static inline bool attn_split(int rows) { return O().attn_mode == 1 || (O().attn_mode >= 2 && rows > 10240); }
 // 0: fp32 kernels, 1: k_attn_h, 2: k_attn_hs
@@ -398,7 +459,7 @@ static inline int attn_kind(int rows) {
     case 0: return 0;
     case 1: return 1;
     case 3: return 2;
-    default: return rows > 10240 ? 1 : rows > hs_max_rows() ? 0 : 2;      // (8 k rows: 60 us for k_attn_hs and the fp32 kernels alike)
+    default: return rows > 10240 ? 1 : rows > knob::attn_hs_max ? 0 : 2;      // (8 k rows: 60 us for k_attn_hs and the fp32 kernels alike)
   }
 }
 
@@ -430,11 +491,6 @@ extern "C" int infgen_active_row_groups(const int* n_agents, int S, int A_cap, i
 // taken (and cleared) by launch_attn_h / edge_fused_launch.  INFGEN_WARM=0 switches them off; launches of more than
 // INFGEN_WARM_MAX_GROUPS 16-row groups (default 128) never carry any - they leave no CU idle.
 static thread_local WarmArgs t_warm = {};
-static int warm_max_groups() {
-  static const int on = getenv("INFGEN_WARM") ? atoi(getenv("INFGEN_WARM")) : 1;
-  static const int mx = getenv("INFGEN_WARM_MAX_GROUPS") ? atoi(getenv("INFGEN_WARM_MAX_GROUPS")) : 128;
-  return on ? mx : 0;
-}
 static void warm_request(const void* p0, int len0, const void* p1, int len1) {
   t_warm.p[0] = (const char*)p0; t_warm.len[0] = p0 ? len0 : 0; t_warm.p[1] = (const char*)p1; t_warm.len[1] = p1 ? len1 : 0;
 }
@@ -443,7 +499,7 @@ static int warm_take(WarmArgs& w, int grid) {
   WarmArgs req = t_warm;
   t_warm = WarmArgs{};
   w = WarmArgs{};
-  if (!(req.len[0] > 0 || req.len[1] > 0) || grid > warm_max_groups()) return grid;
+  if (!(req.len[0] > 0 || req.len[1] > 0) || grid > (knob::warm ? knob::warm_max_groups : 0)) return grid;
   const int wg0 = (grid + 7) & ~7;
   const int per = (256 - wg0) / 8 < 24 ? (256 - wg0) / 8 : 24;
   if (per <= 0) return grid;
@@ -453,42 +509,46 @@ static int warm_take(WarmArgs& w, int grid) {
 
 static void launch_attn_h(const AttnHArgs& a_in, void* stream) {
   AttnHArgs a = a_in;
-  a.dbg = qs_dbg();
+  a.dbg = knob::qs_dbg;
   if (O().row_groups && a.rows == group_rows()) { a.groups = O().row_groups; a.n_groups = O().n_row_groups; }
   if (attn_kind(a.rows) == 2) {            // one 16-row group per workgroup
     const int grid = warm_take(a.warm, ceil_div(a.rows, 16));
-    if (O().gemm_terms == 1) hipLaunchKernelGGL(k_attn_hs<1>, dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
-    else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_attn_hs_b16<1>, dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(k_attn_hs<3>, dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(by_terms(k_attn_hs<3>, k_attn_hs_b16<1>, k_attn_hs<1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
     return;
   }
   t_warm = WarmArgs{};
-  static const int waves = getenv("INFGEN_ATTN_WAVES") ? atoi(getenv("INFGEN_ATTN_WAVES")) : (IG_QSU ? 8 : 4);
-  if (waves != 8) {
-    int grid = ceil_div(a.rows, 64);
-    if (grid > 512) grid = 512;          // two workgroups per CU, persistent over the 64-row tiles beyond that
-    if (O().gemm_terms == 1) hipLaunchKernelGGL((k_attn_h<4, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    else if (O().gemm_terms == 2) hipLaunchKernelGGL((k_attn_h_b16<4, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((k_attn_h<4, 3>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  if (knob::attn_waves != 8) {
+    auto kern = by_terms(k_attn_h<4, 3>, k_attn_h_b16<4, 1>, k_attn_h<4, 1>);
+    hipLaunchKernelGGL(kern, dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
   } else {
+    // the 8-wave variant is launched in its three-term form whatever gemm_terms says ("gemm_terms=2 is not applied
+    // uniformly").  Kept as it was: the fix is by_terms() over the 8-wave kernels here.
     int grid = ceil_div(a.rows, 128);
     if (grid > 256) grid = 256;
     hipLaunchKernelGGL((k_attn_h<8, 3>), dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
   }
 }
 
+// profiler MAC counts of the node kernels: 16384 per row and 128 x 128 projection (whole numbers below 2^53: exact in any order)
+static double attn_pre_macs(int rows, const void* Q, const void* U, const void* K, const void* V) {
+  return (double)rows * 16384.0 * ((Q || U ? 1 : 0) + (K ? 1 : 0) + (V ? 1 : 0) + (U ? 1 : 0));
+}
+// the post part (12 projections' worth, one more with the positional part) and the next layer's pre part
+static double attn_post_macs(int rows, int has_pos, const void* next_pack, const void* nQ, const void* nU, const void* nK, const void* nV) {
+  return (double)rows * (196608.0 + (has_pos ? 16384.0 : 0.0)) + (next_pack ? attn_pre_macs(rows, nQ, nU, nK, nV) : 0.0);
+}
+static double heads_macs(int rows, int token_size) { return (double)rows * (2 * 16384.0 + 128.0 * token_size + 384.0); }
+
 extern "C" int infgen_attn_pre(const float* X, int rows, const float* pack, int use_src_ln,
                                float* Q, float* U, float* K, float* V, void* stream) {
   if (rows <= 0) return 0;
-  if (attn_kind(rows)) {
-    AttnHArgs h{const_cast<float*>(X), rows, nullptr, nullptr, nullptr, nullptr, 0, pack, use_src_ln, Q, U, K, V};
-    { ProfScope _ps(INFGEN_KID_ATTN_PRE, stream, (double)rows * 16384.0 * ((Q || U ? 1 : 0) + (K ? 1 : 0) + (V ? 1 : 0) + (U ? 1 : 0)));
-      launch_attn_h(h, stream); }
-    return check_launch("infgen_attn_pre");
-  }
-  AttnPreArgs a{X, rows, pack, use_src_ln, Q, U, K, V};
-  { ProfScope _ps(INFGEN_KID_ATTN_PRE, stream, (double)rows * 16384.0 * ((Q || U ? 1 : 0) + (K ? 1 : 0) + (V ? 1 : 0) + (U ? 1 : 0)));
-    hipLaunchKernelGGL(k_attn_pre, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a); }
+  { ProfScope _ps(INFGEN_KID_ATTN_PRE, stream, attn_pre_macs(rows, Q, U, K, V));
+    if (attn_kind(rows)) {
+      launch_attn_h(AttnHArgs{const_cast<float*>(X), rows, nullptr, nullptr, nullptr, nullptr, 0, pack, use_src_ln, Q, U, K, V}, stream);
+    } else {
+      AttnPreArgs a{X, rows, pack, use_src_ln, Q, U, K, V};
+      hipLaunchKernelGGL(k_attn_pre, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a);
+    } }
   return check_launch("infgen_attn_pre");
 }
 
@@ -543,15 +603,11 @@ extern "C" int infgen_edge_fused_occupancy(void) {
   return n;
 }
 
-static int edge_fused_launch(int rows, const float* Q, const float* pack, const float* Ksrc, const float* Vsrc,
-                             const int* off, const int* cnt, const int* src, const float* rhat, float* AGG,
-                             int rows_per_scene, int kv_once, void* stream, int r24 = 0) {
+static int edge_fused_launch(int rows, const float* Q, const float* pack, const float* Ksrc, const float* Vsrc, const EdgeSet& es,
+                             float* AGG, int rows_per_scene, int kv_once, void* stream, int r24 = 0) {
   if (rows <= 0) return 0;
-  if (!pack || !rhat) return fail("infgen_edge_attn_fused", "needs the layer pack and rhat");
-  static const int dbg = getenv("INFGEN_EDGE_DBG") ? atoi(getenv("INFGEN_EDGE_DBG")) : 0;
-  static const int no_xcd = getenv("INFGEN_EDGE_NOXCD") ? atoi(getenv("INFGEN_EDGE_NOXCD")) : 0;
-  static const int small_max = getenv("INFGEN_EDGE_SMALL") ? atoi(getenv("INFGEN_EDGE_SMALL")) : 4096;
-  static const int wg2 = getenv("INFGEN_EDGE_WG2") ? atoi(getenv("INFGEN_EDGE_WG2")) : 1;
+  if (!pack || !es.rhat) return fail("infgen_edge_attn_fused", "needs the layer pack and rhat");
+  const int dbg = knob::edge_dbg, no_xcd = knob::edge_noxcd, small_max = knob::edge_small, wg2 = knob::edge_wg2;
   const int G = O().edge_loop;
   // small launches: one 16-row group per workgroup (edge_fused.hip), twice the workgroups for the same rows
   const bool small = rows <= small_max && G == 6;
@@ -559,7 +615,7 @@ static int edge_fused_launch(int rows, const float* Q, const float* pack, const 
   // (128 vs 140 us per launch at 512 scenes; INFGEN_EDGE_WG2=0: one 16-wave workgroup of two groups per CU)
   const bool two = !small && wg2 && G == 6;
   const int tr = (small || two) ? 16 : 32;          // rows per tile
-  EdgeFusedArgs a{rows, Q, pack, Ksrc, Vsrc, EdgeSet{off, cnt, src, rhat}, AGG, nullptr, nullptr, dbg, 0, kv_once};
+  EdgeFusedArgs a{rows, Q, pack, Ksrc, Vsrc, es, AGG, nullptr, nullptr, dbg, 0, kv_once};
   int grid = ceil_div(rows, tr);           // with a group list at most that many
   if (O().row_groups && rows == group_rows()) { a.groups = O().row_groups; a.n_groups = O().n_row_groups; }
   else if (rows_per_scene > tr && rows_per_scene % tr == 0 && !(no_xcd & 1)) {
@@ -584,8 +640,7 @@ static int edge_fused_launch(int rows, const float* Q, const float* pack, const 
       auto k3 = G == 4 ? k_edge_fused3<4> : G == 8 ? k_edge_fused3<8> : k_edge_fused3<6>;
       // (INFGEN_EDGE_LDS_PAD=<bytes>, experiment: dynamic LDS on top of the kernel's 75 KB - from ~6 KB on only ONE workgroup fits a
       // CU, which leaves room for another stream's node kernel; profiles/r06_coresidency_ab.txt)
-      static const int lds_pad = getenv("INFGEN_EDGE_LDS_PAD") ? atoi(getenv("INFGEN_EDGE_LDS_PAD")) : 0;
-      hipLaunchKernelGGL(k3, dim3(mg), dim3(512), lds_pad, (hipStream_t)stream, m); }
+      hipLaunchKernelGGL(k3, dim3(mg), dim3(512), knob::edge_lds_pad, (hipStream_t)stream, m); }
     return check_launch("infgen_edge_attn_fused(k_edge_fused3)");
   }
   a.n_virtual = grid;
@@ -617,7 +672,7 @@ static int edge_fused_launch(int rows, const float* Q, const float* pack, const 
 extern "C" int infgen_edge_attn_fused(int rows, const float* Q, const float* pack, const float* Ksrc, const float* Vsrc,
                                       const int* off, const int* cnt, const int* src, const float* rhat,
                                       float* AGG, void* stream) {
-  return edge_fused_launch(rows, Q, pack, Ksrc, Vsrc, off, cnt, src, rhat, AGG, 0, 0, stream);
+  return edge_fused_launch(rows, Q, pack, Ksrc, Vsrc, EdgeSet{off, cnt, src, rhat}, AGG, 0, 0, stream);
 }
 
 // the same pair of operators with the rows of rhat in the packed 24-bit form (include/infgen_hip.h): what infgen_decode_layers does
@@ -630,7 +685,7 @@ extern "C" int infgen_fourier_embed_r24(const float* raw, int n, const int* coun
 extern "C" int infgen_edge_attn_fused_r24(int rows, const float* Q, const float* pack, const float* Ksrc, const float* Vsrc,
                                           const int* off, const int* cnt, const int* src, const void* rhat24,
                                           float* AGG, void* stream) {
-  return edge_fused_launch(rows, Q, pack, Ksrc, Vsrc, off, cnt, src, static_cast<const float*>(rhat24), AGG, 0, 0, stream, 1);
+  return edge_fused_launch(rows, Q, pack, Ksrc, Vsrc, EdgeSet{off, cnt, src, static_cast<const float*>(rhat24)}, AGG, 0, 0, stream, 1);
 }
 
 // one wave per destination; few destinations (<= 256 rows) get the 8-wave split so that the chip is not idle
@@ -647,7 +702,17 @@ extern "C" int infgen_edge_attn_mode(int rows, const float* Q, const float* U, c
 }
 
 static int attn_post_fused(float* X, int rows, const float* pack, const float* AGG, const float* Z, const float* SIG,
-                           int has_pos, const float* next_pack, float* nQ, float* nU, float* nK, float* nV, void* stream);
+                           int has_pos, const float* next_pack, float* nQ, float* nU, float* nK, float* nV, void* stream) {
+  if (rows <= 0) return 0;
+  { ProfScope _ps(INFGEN_KID_ATTN_POST, stream, attn_post_macs(rows, has_pos, next_pack, nQ, nU, nK, nV));
+    if (attn_kind(rows)) {
+      launch_attn_h(AttnHArgs{X, rows, pack, AGG, Z, SIG, has_pos, next_pack, 0, nQ, nU, nK, nV}, stream);
+    } else {
+      AttnPostArgs a{X, rows, pack, AGG, Z, SIG, has_pos, next_pack, nQ, nU, nK, nV};
+      hipLaunchKernelGGL(k_attn_post, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a);
+    } }
+  return check_launch("infgen_attn_post");
+}
 
 extern "C" int infgen_attn_post(float* X, int rows, const float* pack, const float* AGG, const float* Z,
                                 const float* SIG, int has_pos, void* stream) {
@@ -658,23 +723,6 @@ extern "C" int infgen_attn_post_pre(float* X, int rows, const float* pack, const
                                     const float* SIG, int has_pos, const float* next_pack, float* nQ, float* nU,
                                     float* nK, float* nV, void* stream) {
   return attn_post_fused(X, rows, pack, AGG, Z, SIG, has_pos, next_pack, nQ, nU, nK, nV, stream);
-}
-
-static int attn_post_fused(float* X, int rows, const float* pack, const float* AGG, const float* Z, const float* SIG,
-                           int has_pos, const float* next_pack, float* nQ, float* nU, float* nK, float* nV, void* stream) {
-  if (rows <= 0) return 0;
-  if (attn_kind(rows)) {
-    AttnHArgs h{X, rows, pack, AGG, Z, SIG, has_pos, next_pack, 0, nQ, nU, nK, nV};
-    { ProfScope _ps(INFGEN_KID_ATTN_POST, stream, (double)rows * (196608.0 + (has_pos ? 16384.0 : 0.0) +
-          (next_pack ? 16384.0 * ((nQ || nU ? 1 : 0) + (nK ? 1 : 0) + (nV ? 1 : 0) + (nU ? 1 : 0)) : 0.0)));
-      launch_attn_h(h, stream); }
-    return check_launch("infgen_attn_post");
-  }
-  AttnPostArgs a{X, rows, pack, AGG, Z, SIG, has_pos, next_pack, nQ, nU, nK, nV};
-  { ProfScope _ps(INFGEN_KID_ATTN_POST, stream, (double)rows * (196608.0 + (has_pos ? 16384.0 : 0.0) +
-        (next_pack ? 16384.0 * ((nQ || nU ? 1 : 0) + (nK ? 1 : 0) + (nV ? 1 : 0) + (nU ? 1 : 0)) : 0.0)));
-    hipLaunchKernelGGL(k_attn_post, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a); }
-  return check_launch("infgen_attn_post");
 }
 
 extern "C" int infgen_match_agent_tokens(const unsigned char* valid, const float* pos, const float* heading, const float* shape,
@@ -954,6 +1002,18 @@ extern "C" int infgen_match_map_tokens(const float* traj_pos, const float* theta
   return check_launch("infgen_match_map_tokens");
 }
 
+// the other split families on 64-row tiles (launch_attn_h is the model)
+static void launch_heads_h(const HeadsArgs& a, void* stream) {
+  hipLaunchKernelGGL(by_terms(k_heads_h<3>, k_heads_h_b16<1>, k_heads_h<1>), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
+}
+static void launch_map_head_h(const MapHeadArgs& a, void* stream) {
+  hipLaunchKernelGGL(by_terms(k_map_head_h<3>, k_map_head_h_b16<1>, k_map_head_h<1>), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
+}
+static void launch_mlpemb_h(const MlpEmbHArgs& m, void* stream) {
+  ProfScope _ps(INFGEN_KID_LINEAR, stream, (double)m.rows * (m.K0 + 128 + 128) * 128.0);
+  hipLaunchKernelGGL(by_terms(k_mlpemb_h<3>, k_mlpemb_h_b16<1>, k_mlpemb_h<1>), dim3(grid64(m.rows)), dim3(256), 0, (hipStream_t)stream, m);
+}
+
 // scratch: optional rows x 8 bytes - with it, launches of few row tiles deal the logit chunks to several workgroups per tile
 // keys_stay (infgen_rollout_run's folded tail): the split path neither clears the keys before (k_integrate of the previous step
 // did) nor decodes them after (k_integrate of this step will); *split_used tells the caller whether that path ran
@@ -965,7 +1025,7 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
   if (token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
   HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1};
   if (scratch && !attn_split(rows)) {
-    static const int no_split = getenv("INFGEN_HEADS_NOSPLIT") ? atoi(getenv("INFGEN_HEADS_NOSPLIT")) : 0;
+    const int no_split = knob::heads_nosplit;
     const int tiles = ceil_div(rows, TR), nchunk = token_size / 128;
     int ns = 1;
     while (!no_split && 2 * ns <= nchunk && nchunk % (2 * ns) == 0 && tiles * 2 * ns <= 512) ns *= 2;
@@ -973,7 +1033,7 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
       if (!keys_stay && hipMemsetAsync(scratch, 0, (size_t)rows * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
         return fail("infgen_heads", "memset failed");
       a.part = scratch; a.nsplit = ns;
-      { ProfScope _ps(INFGEN_KID_HEADS, stream, (double)rows * (2 * 16384.0 + 128.0 * token_size + 384.0));
+      { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(rows, token_size));
         hipLaunchKernelGGL(k_heads, dim3(tiles, ns), dim3(NT), 0, (hipStream_t)stream, a);
         if (!keys_stay)
           hipLaunchKernelGGL(k_heads_finish, dim3(ceil_div(rows, NT)), dim3(NT), 0, (hipStream_t)stream, scratch, rows, next_token); }
@@ -981,16 +1041,9 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
       return check_launch("infgen_heads");
     }
   }
-  { ProfScope _ps(INFGEN_KID_HEADS, stream, (double)rows * (2 * 16384.0 + 128.0 * token_size + 384.0));
-    if (attn_split(rows)) {
-      int grid = ceil_div(rows, 64);
-      if (grid > 512) grid = 512;
-      if (O().gemm_terms == 1) hipLaunchKernelGGL(k_heads_h<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-      else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_heads_h_b16<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-      else hipLaunchKernelGGL(k_heads_h<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-      hipLaunchKernelGGL(k_heads, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a);
-    } }
+  { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(rows, token_size));
+    if (attn_split(rows)) launch_heads_h(a, stream);
+    else hipLaunchKernelGGL(k_heads, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a); }
   return check_launch("infgen_heads");
 }
 
@@ -1011,12 +1064,8 @@ extern "C" int infgen_map_token_head(const float* X, int ldx, const int* gather,
   MapHeadArgs a{X, ldx, gather, n, pack, logits, top_idx};
   const hipStream_t s = (hipStream_t)stream;
   ProfScope _ps(INFGEN_KID_MAP_HEAD, stream, (double)n * (16384.0 + 128.0 * token_size));
-  if (O().gemm_terms != 3 || attn_split(n)) {
-    int grid = ceil_div(n, 64);
-    if (grid > 512) grid = 512;
-    if (O().gemm_terms == 1) hipLaunchKernelGGL(k_map_head_h<1>, dim3(grid), dim3(256), 0, s, a);
-    else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_map_head_h_b16<1>, dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_map_head_h<3>, dim3(grid), dim3(256), 0, s, a);
+  if (!three_terms() || attn_split(n)) {
+    launch_map_head_h(a, stream);
     return check_launch("infgen_map_token_head");
   }
   if (!hidden) return fail("infgen_map_token_head", "the fp32 path needs hidden [n][128]");
@@ -1067,6 +1116,7 @@ static SceneState scene_of(const InfgenRollout* r) {
   return st;
 }
 static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src, e.raw, e.total, e.cap}; }
+static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
 static int validate(const InfgenRollout* r, const char* where) {
   if (!r) return fail(where, "null context");
@@ -1079,14 +1129,9 @@ static int validate(const InfgenRollout* r, const char* where) {
   return 0;
 }
 
-static int build_edges_impl(const InfgenRollout* r, int c, int edgeless, void* stream, bool zero_totals, unsigned long long* clear_keys = nullptr,
-                            bool clear_sync = false);
-extern "C" int infgen_build_edges(const InfgenRollout* r, int c, int edgeless, void* stream) {
-  return build_edges_impl(r, c, edgeless, stream, true);
-}
 // zero_totals = false: the three totals were cleared by the previous step's k_integrate (IntegrateArgs.edge_totals)
-static int build_edges_impl(const InfgenRollout* r, int c, int edgeless, void* stream, bool zero_totals, unsigned long long* clear_keys,
-                            bool clear_sync) {
+static int build_edges_impl(const InfgenRollout* r, int c, int edgeless, void* stream, bool zero_totals, unsigned long long* clear_keys = nullptr,
+                            bool clear_sync = false) {
   RET_IF(validate(r, "infgen_build_edges"));
   OptScope _opts(r);
   hipStream_t s = (hipStream_t)stream;
@@ -1108,24 +1153,30 @@ static int build_edges_impl(const InfgenRollout* r, int c, int edgeless, void* s
     a.map_lds = r->M_cap < 4096 ? r->M_cap : 4096;
     const size_t lds = (size_t)a.map_lds * 8;
     // few scenes: 16 waves per workgroup whatever A_cap (INFGEN_BE_WIDE_SCENES: the largest batch that takes them, default 128)
-    static const int wide_scenes = getenv("INFGEN_BE_WIDE_SCENES") ? atoi(getenv("INFGEN_BE_WIDE_SCENES")) : 128;
-    if (r->A_cap <= 256 && r->S > wide_scenes) hipLaunchKernelGGL(k_build_edges<256>, dim3(r->S, 3), dim3(256), lds, s, a);
+    if (r->A_cap <= 256 && r->S > knob::be_wide_scenes) hipLaunchKernelGGL(k_build_edges<256>, dim3(r->S, 3), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(k_build_edges<1024>, dim3(r->S, 3), dim3(1024), lds, s, a); }
   return check_launch("infgen_build_edges");
 }
+extern "C" int infgen_build_edges(const InfgenRollout* r, int c, int edgeless, void* stream) {
+  return build_edges_impl(r, c, edgeless, stream, true);
+}
 
-static RawFeatArgs rawfeat_args(const InfgenRollout* r, int col);
+// all rows of column col; infgen_raw_feature_rows fills in its row list
+static RawFeatArgs rawfeat_args(const InfgenRollout* r, int col) {
+  RawFeatArgs a;
+  a.st = scene_of(r); a.col = col; a.tok_tab = r->tok_tab; a.token_size = r->token_size;
+  a.grid_tab = r->grid_tab; a.grid_size = r->grid_size; a.state_emb = r->state_emb;
+  a.cat_agent = r->cat_agent; a.cat_seed = r->cat_seed; a.raw2 = r->raw2; a.cat = r->cat; a.fus_in = r->fus_in;
+  a.row_list = nullptr; a.row_mask = nullptr; a.n_list = 0; a.no_grid = r->no_grid_token;
+  return a;
+}
+
 // workgroups per scene of k_integrate: 16 rows each for few scenes (INFGEN_INT_GROUP_SCENES: the largest batch, default 128), else 1.
 // With more than one the arg-max keys are reset by the k_build_edges that follows (build_edges_impl: clear_keys), not by k_integrate.
 static int integrate_groups(const InfgenRollout* r) {
-  static const int max_scenes = getenv("INFGEN_INT_GROUP_SCENES") ? atoi(getenv("INFGEN_INT_GROUP_SCENES")) : 128;
-  return (r->S <= max_scenes && r->A_cap % 16 == 0 && r->A_cap > 16) ? r->A_cap / 16 : 1;
+  return (r->S <= knob::int_group_scenes && r->A_cap % 16 == 0 && r->A_cap > 16) ? r->A_cap / 16 : 1;
 }
-static int integrate_impl(const InfgenRollout* r, int t, void* stream, unsigned long long* heads_part, bool zero_totals, bool prep, bool zero_sync = false);
-extern "C" int infgen_integrate(const InfgenRollout* r, int t, void* stream) {
-  return integrate_impl(r, t, stream, nullptr, false, false);
-}
-static int integrate_impl(const InfgenRollout* r, int t, void* stream, unsigned long long* heads_part, bool zero_totals, bool prep, bool zero_sync) {
+static int integrate_impl(const InfgenRollout* r, int t, void* stream, unsigned long long* heads_part, bool zero_totals, bool prep, bool zero_sync = false) {
   RET_IF(validate(r, "infgen_integrate"));
   OptScope _opts(r);
   IntegrateArgs a;
@@ -1147,58 +1198,38 @@ static int integrate_impl(const InfgenRollout* r, int t, void* stream, unsigned 
     hipLaunchKernelGGL(k_integrate<1024>, dim3(r->S, a.groups), dim3(1024), 0, (hipStream_t)stream, a); }
   return check_launch("infgen_integrate");
 }
+extern "C" int infgen_integrate(const InfgenRollout* r, int t, void* stream) {
+  return integrate_impl(r, t, stream, nullptr, false, false);
+}
 
 // MLPEmbedding pack (first Linear K0 -> 128): P(K0p,128) b ln_g ln_b | P(128,128) b ln_g ln_b | P(128,128) b
 static inline int mlpemb_off2(int K0p) { return K0p * 128 + 3 * 128; }
 static inline int mlpemb_off3(int K0p) { return mlpemb_off2(K0p) + 16384 + 3 * 128; }
-
-static RawFeatArgs rawfeat_args(const InfgenRollout* r, int col) {
-  RawFeatArgs a;
-  a.st = scene_of(r); a.col = col; a.tok_tab = r->tok_tab; a.token_size = r->token_size;
-  a.grid_tab = r->grid_tab; a.grid_size = r->grid_size; a.state_emb = r->state_emb;
-  a.cat_agent = r->cat_agent; a.cat_seed = r->cat_seed; a.raw2 = r->raw2; a.cat = r->cat; a.fus_in = r->fus_in;
-  a.row_list = nullptr; a.row_mask = nullptr; a.n_list = 0; a.no_grid = r->no_grid_token;
-  return a;
-}
-
-static int raw_feature_fusion(const InfgenRollout* r, void* stream);
-extern "C" int infgen_raw_feature(const InfgenRollout* r, int col, void* stream) {
-  RET_IF(validate(r, "infgen_raw_feature"));
-  OptScope _opts(r);
-  const int rows = r->S * r->A_cap;
-  RawFeatArgs a = rawfeat_args(r, col);
-  { ProfScope _ps(INFGEN_KID_RAWFEAT, stream);
-    hipLaunchKernelGGL(k_rawfeat_prep, dim3(ceil_div(rows * 32, NT)), dim3(NT), 0, (hipStream_t)stream, a); }
-  RET_IF(check_launch("infgen_raw_feature/prep"));
-  RET_IF(infgen_fourier_embed(r->raw2, 2, nullptr, rows, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, stream));
-  return raw_feature_fusion(r, stream);
+// the three stages as k_linear launches through tmp1 / tmp2 [rows][128]; K inputs padded to K0p in the pack.  Y may be tmp1 (the
+// last stage reads tmp2 only)
+static int mlp_embedding_fp32(const float* X, int ldx, int rows, int K, int K0p, const float* P, float* tmp1, float* tmp2, float* Y,
+                              int ldy, void* stream) {
+  const int o2 = mlpemb_off2(K0p), o3 = mlpemb_off3(K0p);
+  RET_IF(infgen_linear(X, ldx, nullptr, rows, K, P, 128, P + K0p * 128, 128, nullptr, nullptr,
+                       P + K0p * 128 + 128, P + K0p * 128 + 256, 1, tmp1, 128, stream));
+  RET_IF(infgen_linear(tmp1, 128, nullptr, rows, 128, P + o2, 128, P + o2 + 16384, 128, nullptr, nullptr,
+                       P + o2 + 16384 + 128, P + o2 + 16384 + 256, 1, tmp2, 128, stream));
+  return infgen_linear(tmp2, 128, nullptr, rows, 128, P + o3, 128, P + o3 + 16384, 128, nullptr, nullptr,
+                       nullptr, nullptr, 0, Y, ldy, stream);
 }
 
 // MLPEmbedding (reference infgen/modules/layers.py:163-192) with K0 = 128 j inputs: Linear LN ReLU Linear LN ReLU Linear.  Split
 // arithmetic (attn_mode != 0): the three stages in one launch of k_mlpemb_h (any row count: one 25 us chain instead of three dependent
-// fp32 launches of 30-40 us each); attn_mode 0: three k_linear launches through tmp1 / tmp2 [rows][128]
+// fp32 launches of 30-40 us each); attn_mode 0: mlp_embedding_fp32
 static int mlp_embedding_impl(const float* X, int ldx, int rows, int K0, const float* P, float* tmp1, float* tmp2, float* Y, int ldy,
                               void* stream, const char* where) {
   if (rows <= 0) return 0;
   if (O().attn_mode != 0) {
-    MlpEmbHArgs m{X, ldx, rows, K0, P, Y, ldy};
-    int grid = ceil_div(rows, 64);
-    if (grid > 512) grid = 512;
-    { ProfScope _ps(INFGEN_KID_LINEAR, stream, (double)rows * (K0 + 128 + 128) * 128.0);
-      if (O().gemm_terms == 1) hipLaunchKernelGGL(k_mlpemb_h<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m);
-      else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_mlpemb_h_b16<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m);
-      else hipLaunchKernelGGL(k_mlpemb_h<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m); }
+    launch_mlpemb_h(MlpEmbHArgs{X, ldx, rows, K0, P, Y, ldy}, stream);
     return check_launch(where);
   }
   if (!tmp1 || !tmp2) return fail(where, "the fp32 kernels need the two scratch arrays");
-  const int o2 = mlpemb_off2(K0), o3 = mlpemb_off3(K0);
-  RET_IF(infgen_linear(X, ldx, nullptr, rows, K0, P, 128, P + K0 * 128, 128, nullptr, nullptr,
-                       P + K0 * 128 + 128, P + K0 * 128 + 256, 1, tmp1, 128, stream));
-  RET_IF(infgen_linear(tmp1, 128, nullptr, rows, 128, P + o2, 128, P + o2 + 16384, 128, nullptr, nullptr,
-                       P + o2 + 16384 + 128, P + o2 + 16384 + 256, 1, tmp2, 128, stream));
-  RET_IF(infgen_linear(tmp2, 128, nullptr, rows, 128, P + o3, 128, P + o3 + 16384, 128, nullptr, nullptr,
-                       nullptr, nullptr, 0, Y, ldy, stream));
-  return 0;
+  return mlp_embedding_fp32(X, ldx, rows, K0, K0, P, tmp1, tmp2, Y, ldy, stream);
 }
 extern "C" int infgen_mlp_embedding(const float* X, int ldx, int rows, int K0, const float* pack, float* tmp1, float* tmp2,
                                     float* Y, int ldy, void* stream) {
@@ -1215,6 +1246,18 @@ static int raw_feature_fusion(const InfgenRollout* r, void* stream) {
                             "infgen_raw_feature/fusion");
 }
 
+extern "C" int infgen_raw_feature(const InfgenRollout* r, int col, void* stream) {
+  RET_IF(validate(r, "infgen_raw_feature"));
+  OptScope _opts(r);
+  const int rows = r->S * r->A_cap;
+  RawFeatArgs a = rawfeat_args(r, col);
+  { ProfScope _ps(INFGEN_KID_RAWFEAT, stream);
+    hipLaunchKernelGGL(k_rawfeat_prep, dim3(ceil_div(rows * 32, NT)), dim3(NT), 0, (hipStream_t)stream, a); }
+  RET_IF(check_launch("infgen_raw_feature/prep"));
+  RET_IF(infgen_fourier_embed(r->raw2, 2, nullptr, rows, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, stream));
+  return raw_feature_fusion(r, stream);
+}
+
 // the same for a few rows only (insertion: the rows appended in this sub-loop iteration): row_list[k] = row, used where
 // row_mask[k] != 0.  The first n rows of the scratch arrays raw2 / cat / fus_in / tmp1 / tmp2 hold the compact intermediate
 // results (every all-rows call rewrites them); X is updated at the listed rows only.
@@ -1224,35 +1267,15 @@ extern "C" int infgen_raw_feature_rows(const InfgenRollout* r, int col, const in
   OptScope _opts(r);
   if (n <= 0) return 0;
   if (n > r->S * r->A_cap) return fail("infgen_raw_feature_rows", "more rows than the layout holds");
-  RawFeatArgs a;
-  a.st = scene_of(r); a.col = col; a.tok_tab = r->tok_tab; a.token_size = r->token_size;
-  a.grid_tab = r->grid_tab; a.grid_size = r->grid_size; a.state_emb = r->state_emb;
-  a.cat_agent = r->cat_agent; a.cat_seed = r->cat_seed; a.raw2 = r->raw2; a.cat = r->cat; a.fus_in = r->fus_in;
-  a.row_list = row_list; a.row_mask = row_mask; a.n_list = n; a.no_grid = r->no_grid_token;
+  RawFeatArgs a = rawfeat_args(r, col);
+  a.row_list = row_list; a.row_mask = row_mask; a.n_list = n;
   { ProfScope _ps(INFGEN_KID_RAWFEAT, stream);
     hipLaunchKernelGGL(k_rawfeat_prep, dim3(ceil_div(n * 32, NT)), dim3(NT), 0, (hipStream_t)stream, a); }
   RET_IF(check_launch("infgen_raw_feature_rows/prep"));
   RET_IF(infgen_fourier_embed(r->raw2, 2, nullptr, n, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, stream));
-  const float* P = r->fusion_pack;
-  const int K0 = fusion_k0(r);
-  if (O().attn_mode != 0) {
-    MlpEmbHArgs m{r->fus_in, 512, n, K0, P, r->tmp1, 128};
-    int grid = ceil_div(n, 64);
-    if (grid > 512) grid = 512;
-    { ProfScope _ps(INFGEN_KID_LINEAR, stream, (double)n * (K0 + 128 + 128) * 128.0);
-      if (O().gemm_terms == 1) hipLaunchKernelGGL(k_mlpemb_h<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m);
-      else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_mlpemb_h_b16<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m);
-      else hipLaunchKernelGGL(k_mlpemb_h<3>, dim3(grid), dim3(256), 0, (hipStream_t)stream, m); }
-    RET_IF(check_launch("infgen_raw_feature_rows/fusion"));
-  } else {
-    const int o2 = mlpemb_off2(K0), o3 = mlpemb_off3(K0);
-    RET_IF(infgen_linear(r->fus_in, 512, nullptr, n, K0, P, 128, P + K0 * 128, 128, nullptr, nullptr,
-                         P + K0 * 128 + 128, P + K0 * 128 + 256, 1, r->tmp1, 128, stream));
-    RET_IF(infgen_linear(r->tmp1, 128, nullptr, n, 128, P + o2, 128, P + o2 + 16384, 128, nullptr, nullptr,
-                         P + o2 + 16384 + 128, P + o2 + 16384 + 256, 1, r->tmp2, 128, stream));
-    RET_IF(infgen_linear(r->tmp2, 128, nullptr, n, 128, P + o3, 128, P + o3 + 16384, 128, nullptr, nullptr,
-                         nullptr, nullptr, 0, r->tmp1, 128, stream));
-  }
+  // fusion_emb of the compact rows into tmp1 (on the fp32 path tmp1 is also the first stage's output: mlp_embedding_impl)
+  RET_IF(mlp_embedding_impl(r->fus_in, 512, n, fusion_k0(r), r->fusion_pack, r->tmp1, r->tmp2, r->tmp1, 128, stream,
+                            "infgen_raw_feature_rows/fusion"));
   hipLaunchKernelGGL(k_scatter_rows, dim3(ceil_div(n * 32, NT)), dim3(NT), 0, (hipStream_t)stream, r->tmp1, row_list, row_mask, n, r->X);
   return check_launch("infgen_raw_feature_rows/scatter");
 }
@@ -1284,11 +1307,6 @@ extern "C" int infgen_set_overlap(int mode) {
   return 0;
 }
 
-static int fourier_nomulti() {
-  static const int v = getenv("INFGEN_FOURIER_NOMULTI") ? atoi(getenv("INFGEN_FOURIER_NOMULTI")) : 0;
-  return v;
-}
-
 // ---- k_layers_p (layers_p.hip): every sublayer of a step in one launch, one resident workgroup per 16-row group
 extern "C" int infgen_set_layers_p(int mode) {        // (process-wide default, like the other infgen_set_*: contexts carry their own copy)
   if (mode < 0 || mode > 2) return fail("infgen_set_layers_p", "mode must be 0, 1 or 2");
@@ -1300,16 +1318,11 @@ extern "C" int infgen_set_layers_p(int mode) {        // (process-wide default, 
 // per-sublayer launches, whose layers cost 26 - 28 ms there against 2 x 10 ms of two 64-scene launches; from three chunks on the
 // big-batch kernels are as fast
 static int lp_chunk_scenes(const InfgenRollout* r, int limit) {
-  static const int max_chunks = getenv("INFGEN_LP_MAX_CHUNKS") ? atoi(getenv("INFGEN_LP_MAX_CHUNKS")) : 2;
   const int gps = r->A_cap / 16;
   if (gps <= 0 || gps > limit) return 0;
   const int per = limit / gps;                       // scenes per launch
   const int chunks = (r->S + per - 1) / per;
-  return chunks <= max_chunks ? per : 0;
-}
-static int lp_max_groups() {
-  static const int v = getenv("INFGEN_LP_MAX_GROUPS") ? atoi(getenv("INFGEN_LP_MAX_GROUPS")) : 256;
-  return v;
+  return chunks <= knob::lp_max_chunks ? per : 0;
 }
 // the launch shape qualifies (the kernel keeps U / Z on chip like k_edge_fused: step_mode treats it as a fused launch)
 // k_layers_p's workgroups meet at counters in global memory, so a launch needs ALL of them resident at some point:
@@ -1360,8 +1373,12 @@ extern "C" int infgen_layers_p_capacity(void) {       // workgroups one k_layers
 // workgroups a launch may have: the device's resident capacity (a partition with fewer CUs than 256 - DPX / QPX / CPX modes, smaller
 // parts - lowers it), and INFGEN_LP_MAX_GROUPS
 static int lp_limit() {
-  const int cap = infgen_layers_p_capacity(), mx = lp_max_groups();
+  const int cap = infgen_layers_p_capacity(), mx = knob::lp_max_groups;
   return cap < mx ? cap : mx;
+}
+static bool is_capturing(void* stream) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
 }
 // k_layers_p bounds a row's LayerNorm output with header slots 10..13 of the attention packs; a pack without them (an older or
 // foreign packer: slot 14 != AH_HDR_VERSION) would scale its operands by 2^126.  Checked once per pack pointer (a 64-byte
@@ -1372,11 +1389,7 @@ static bool lp_packs_ok(const InfgenRollout* r, bool refresh = false, void* stre
   std::lock_guard<std::mutex> lk(mu);
   // a pack that was never examined needs a synchronous 64-byte copy: not while `stream` is being captured into a graph (the copy
   // would fail and the verdict would stick) - such a launch takes the per-sublayer kernels, the verdict stays open
-  bool capturing = false;
-  if (stream) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    capturing = hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  }
+  const bool capturing = stream && is_capturing(stream);
   auto ok = [&](const float* pack) {
     if (!pack) return false;
     if (!refresh) { auto it = seen.find(pack); if (it != seen.end()) return it->second; }
@@ -1412,7 +1425,7 @@ static bool layers_p_shape(const InfgenRollout* r, int rows, int edgeless, void*
   // sat at ~40 scenes: 2,048 L2 write-backs per layer.)  INFGEN_LP_MAX_GROUPS lowers the limit.
   // (a row-group list of an insertion context is ignored: the launch visits every group - the ones without agents have empty edge
   // lists and run in parallel on CUs that would idle)
-  return O().layers_p && O().edge_fuse != 0 && O().attn_mode != 0 && O().gemm_terms == 3 && O().fourier_mode != 0 &&
+  return O().layers_p && O().edge_fuse != 0 && O().attn_mode != 0 && three_terms() && O().fourier_mode != 0 &&
          !(O().overlap && g_side) && r->A_cap % 16 == 0 && lp_chunk_scenes(r, lp_limit()) > 0 &&
           r->num_layers <= LP_MAX_LAYERS && r->U && r->SIG && !r->tap_x && lp_packs_ok(r, false, stream);
 }
@@ -1434,53 +1447,55 @@ static StepMode step_mode(const InfgenRollout* r, int rows, int edgeless, void* 
 }
 // few rows: the step's Fourier embeddings side by side in one launch (k_fourier_h_multi)
 static bool fourier_multi_ok(int rows, int edgeless) {
-  return !edgeless && O().fourier_mode != 0 && rows <= 10240 && !fourier_nomulti() && !(O().overlap && g_side);
+  return !edgeless && O().fourier_mode != 0 && rows <= 10240 && !knob::fourier_nomulti && !(O().overlap && g_side);
 }
 
-// edge sets of column c + their Fourier embeddings.  zero_totals = false: the totals were cleared by k_integrate; with_xa: the
-// x_a_emb embedding of the rows' raw features (raw2 / cat -> fus_in, infgen_raw_feature's middle launch) rides along as a
-// fourth set of the multi launch
+// The Fourier sets of a step, written once for every launch shape of prepare_edges: the three edge sets (raw -> rhat rows, in the
+// row format of the step) and FS_XA, the x_a_emb embedding of the rows' raw features (raw2 / cat -> fus_in, infgen_raw_feature's
+// middle launch)
+enum FourierSet { FS_TEMPORAL, FS_MAP, FS_AGENT, FS_XA };
+static FourierArgs step_fourier_set(const InfgenRollout* r, FourierSet k, const StepMode& sm) {
+  switch (k) {
+    case FS_TEMPORAL:
+      return fourier_args(r->et.raw, 4, r->et.total, r->et.cap, r->four_t, nullptr, 0, r->et.rhat, 128, 1, sm.r24, sm.dt, sm.dt != nullptr);
+    case FS_MAP: return fourier_args(r->em.raw, 3, r->em.total, r->em.cap, r->four_m, nullptr, 0, r->em.rhat, 128, 1, sm.r24);
+    case FS_AGENT: return fourier_args(r->ea.raw, 3, r->ea.total, r->ea.cap, r->four_a, nullptr, 0, r->ea.rhat, 128, 1, sm.ra);
+    default: return fourier_args(r->raw2, 2, nullptr, r->S * r->A_cap, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, 0);
+  }
+}
+
+// edge sets of column c + their Fourier embeddings.  zero_totals = false: the totals were cleared by k_integrate; with_xa: FS_XA
+// rides along as a fourth set of the multi launch
 static int prepare_edges(const InfgenRollout* r, int c, int edgeless, void* stream, bool zero_totals, bool with_xa,
                          unsigned long long* clear_keys = nullptr, bool clear_sync = false) {
   const int rows = r->S * r->A_cap;
   RET_IF(build_edges_impl(r, c, edgeless, stream, zero_totals, clear_keys, clear_sync));
   const StepMode sm = step_mode(r, rows, edgeless, stream);
-  const bool overlap = sm.overlap; const int r24 = sm.r24, ra = sm.ra; const float* dt = sm.dt;
-  if (overlap) {
+  if (sm.overlap) {
     hipStream_t ms = (hipStream_t)stream;
     if (hipEventRecord(g_ev_fork, ms) != hipSuccess || hipStreamWaitEvent(g_side, g_ev_fork, 0) != hipSuccess)
       return fail("infgen_decode_layers", "fork failed");
-    RET_IF(fourier_embed_impl(r->em.raw, 3, r->em.total, r->em.cap, r->four_m, nullptr, 0, r->em.rhat, 128, 1, r24, g_side));
+    RET_IF(launch_fourier(step_fourier_set(r, FS_MAP, sm), g_side));
     if (hipEventRecord(g_ev_m, g_side) != hipSuccess) return fail("infgen_decode_layers", "event failed");
-    RET_IF(fourier_embed_impl(r->ea.raw, 3, r->ea.total, r->ea.cap, r->four_a, nullptr, 0, r->ea.rhat, 128, 1, ra, g_side));
+    RET_IF(launch_fourier(step_fourier_set(r, FS_AGENT, sm), g_side));
     if (hipEventRecord(g_ev_a, g_side) != hipSuccess) return fail("infgen_decode_layers", "event failed");
-    RET_IF(fourier_embed_impl(r->et.raw, 4, r->et.total, r->et.cap, r->four_t, nullptr, 0, r->et.rhat, 128, 1, r24, stream, dt, dt != nullptr));
+    RET_IF(launch_fourier(step_fourier_set(r, FS_TEMPORAL, sm), stream));
   } else if (fourier_multi_ok(rows, edgeless)) {
     // few rows: the three sets side by side in one launch (each is a handful of 128-edge tiles of 35 - 45 us)
-    unsigned long long* pr = (g_prof.mask >> INFGEN_KID_FOURIER) & 1u ? g_prof.rows_dev : nullptr;
+    const int n_sets = with_xa ? 4 : 3;
     FourierMultiArgs m;
-    m.set[0] = FourierArgs{r->et.raw, 4, r->et.total, r->et.cap, r->four_t, nullptr, 0, r->et.rhat, 128, 1, pr, r24, dt, dt != nullptr};
-    m.set[1] = FourierArgs{r->em.raw, 3, r->em.total, r->em.cap, r->four_m, nullptr, 0, r->em.rhat, 128, 1, pr, r24, nullptr, 0};
-    m.set[2] = FourierArgs{r->ea.raw, 3, r->ea.total, r->ea.cap, r->four_a, nullptr, 0, r->ea.rhat, 128, 1, pr, ra, nullptr, 0};
-    if (with_xa)
-      m.set[3] = FourierArgs{r->raw2, 2, nullptr, rows, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, pr, 0, nullptr, 0};
+    for (int k = 0; k < n_sets; ++k) m.set[k] = step_fourier_set(r, (FourierSet)k, sm);
     int cap = r->et.cap > r->em.cap ? r->et.cap : r->em.cap;
     if (r->ea.cap > cap) cap = r->ea.cap;
-    // (INFGEN_FH12_MULTI_ROWS: smallest launch, in rows, whose multi-set launch takes the three-wave-group kernel; default: never)
-    static const int fh12_rows = getenv("INFGEN_FH12_MULTI_ROWS") ? atoi(getenv("INFGEN_FH12_MULTI_ROWS")) : 0;
-    const bool wide = fh12_rows > 0 && rows >= fh12_rows && O().gemm_terms == 3 && FH_WAVES == 8;
-    int grid = ceil_div(cap, wide ? FH12_TILE : FH_TILE);
-    if (grid > 256 * FH_WG_PER_CU) grid = 256 * FH_WG_PER_CU;
+    const bool wide = knob::fh12_multi_rows > 0 && rows >= knob::fh12_multi_rows && three_terms() && FH_WAVES == 8;
+    const int grid = fourier_h_grid(cap, wide);
     { ProfScope _ps(INFGEN_KID_FOURIER, stream);
-      if (wide) hipLaunchKernelGGL(k_fourier_h12_multi<3>, dim3(grid, with_xa ? 4 : 3), dim3(FH12_NT), 0, (hipStream_t)stream, m);
-      else if (O().gemm_terms == 1) hipLaunchKernelGGL(k_fourier_h_multi<1>, dim3(grid, with_xa ? 4 : 3), dim3(FH_NT), 0, (hipStream_t)stream, m);
-      else if (O().gemm_terms == 2) hipLaunchKernelGGL(k_fourier_h_multi_b16<1>, dim3(grid, with_xa ? 4 : 3), dim3(FH_NT), 0, (hipStream_t)stream, m);
-      else hipLaunchKernelGGL(k_fourier_h_multi<3>, dim3(grid, with_xa ? 4 : 3), dim3(FH_NT), 0, (hipStream_t)stream, m); }
+      if (wide) hipLaunchKernelGGL(k_fourier_h12_multi<3>, dim3(grid, n_sets), dim3(FH12_NT), 0, (hipStream_t)stream, m);
+      else hipLaunchKernelGGL(by_terms(k_fourier_h_multi<3>, k_fourier_h_multi_b16<1>, k_fourier_h_multi<1>), dim3(grid, n_sets),
+                              dim3(FH_NT), 0, (hipStream_t)stream, m); }
     RET_IF(check_launch("infgen_decode_layers(fourier)"));
   } else if (!edgeless) {
-    RET_IF(fourier_embed_impl(r->et.raw, 4, r->et.total, r->et.cap, r->four_t, nullptr, 0, r->et.rhat, 128, 1, r24, stream, dt, dt != nullptr));
-    RET_IF(fourier_embed_impl(r->em.raw, 3, r->em.total, r->em.cap, r->four_m, nullptr, 0, r->em.rhat, 128, 1, r24, stream));
-    RET_IF(fourier_embed_impl(r->ea.raw, 3, r->ea.total, r->ea.cap, r->four_a, nullptr, 0, r->ea.rhat, 128, 1, ra, stream));
+    for (FourierSet k : {FS_TEMPORAL, FS_MAP, FS_AGENT}) RET_IF(launch_fourier(step_fourier_set(r, k, sm), stream));
   }
   return 0;
 }
@@ -1500,12 +1515,10 @@ static int layers_p_launch(const InfgenRollout* r, int c, const StepMode& sm, vo
   // the agent set's K / V rows double buffered by layer parity: the context's Ka / Va, and the first rows of its U array (4 KB per
   // row, unused while U stays on chip); the scenes' counters in its SIG array (unused for the same reason)
   a.Ka[0] = r->Ka; a.Va[0] = r->Va; a.Ka[1] = r->U; a.Va[1] = r->U + (size_t)rows * D;
-  a.et = EdgeSet{r->et.off, r->et.cnt, r->et.src, r->et.rhat};
-  a.em = EdgeSet{r->em.off, r->em.cnt, r->em.src, r->em.rhat};
-  a.ea = EdgeSet{r->ea.off, r->ea.cnt, r->ea.src, r->ea.rhat};
+  a.et = eset(r->et); a.em = eset(r->em); a.ea = eset(r->ea);
   a.sync = reinterpret_cast<int*>(r->SIG);
   a.trace = nullptr;
-  static const int lp_trace = getenv("INFGEN_LP_TRACE") ? atoi(getenv("INFGEN_LP_TRACE")) : 0;
+  const int lp_trace = knob::lp_trace;
   static unsigned long long* trace_dev = nullptr;
   if (lp_trace) {
     if (!trace_dev && hipMalloc(&trace_dev, 2048 * sizeof(unsigned long long)) != hipSuccess) return fail("infgen_decode_layers", "trace buffer");
@@ -1516,13 +1529,11 @@ static int layers_p_launch(const InfgenRollout* r, int c, const StepMode& sm, vo
     return fail("infgen_decode_layers", "memset failed");
   // fewer rows per workgroup while the launch stays within the limit: 8 (one row per wave in the edge loop) up to 256 workgroups,
   // 4 (a row's edge list halved between two waves) up to 128
-  static const int lp_rows_min = getenv("INFGEN_LP_ROWS8") ? (atoi(getenv("INFGEN_LP_ROWS8")) ? 8 : 16)
-                               : getenv("INFGEN_LP_ROWS_MIN") ? atoi(getenv("INFGEN_LP_ROWS_MIN")) : 4;
   // (every bound below is the launch limit lp_limit() = min(resident capacity of THIS device, INFGEN_LP_MAX_GROUPS): a grid beyond the
   // capacity would leave workgroups that never become resident while the resident ones wait for them at the scene counters)
   const int limit = lp_limit();
   a.rows_per_wg = 16;
-  for (int rr = 8; rr >= 4 && rr >= lp_rows_min; rr >>= 1)
+  for (int rr = 8; rr >= 4 && rr >= knob::lp_rows_min; rr >>= 1)
     if (r->A_cap % rr == 0 && rows / rr <= (rr == 4 ? limit / 2 : limit)) a.rows_per_wg = rr;
   const int gps = r->A_cap / a.rows_per_wg;
   // a batch beyond one launch's workgroups: chunks of whole scenes, one launch after the other (each launch's workgroups are all
@@ -1535,14 +1546,11 @@ static int layers_p_launch(const InfgenRollout* r, int c, const StepMode& sm, vo
                                  : (sm.r24 ? k_layers_p<true, 16> : k_layers_p<false, 16>);
   // A stream that is being captured into a HIP graph cannot take a cooperative launch or the cross-stream ordering below: the
   // (opt-in) graph modes keep the plain launch with the spin limit - their caller owns the GPU
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  const bool capturing = is_capturing(stream);
   // polls at a scene counter before the kernel traps: plain launches 2^24 (tens of seconds - a legitimate wait lasts as long as other
   // streams' kernels, milliseconds; only another process's k_layers_p on the same GPU can hold a workgroup off its CU for longer,
   // and a trap is better than a hung device), cooperative launches unlimited, captured launches 2^22; INFGEN_LP_SPIN_LIMIT overrides
-  static const char* spin_str = getenv("INFGEN_LP_SPIN_LIMIT");
-  static const unsigned spin_env = spin_str ? (unsigned)strtoul(spin_str, nullptr, 0) : 0u;
-  a.spin_limit = capturing ? (1u << 22) : spin_str ? spin_env : (O().layers_p == 2 ? 0u : (1u << 24));
+  a.spin_limit = capturing ? (1u << 22) : knob::lp_spin_str ? knob::lp_spin_limit : (O().layers_p == 2 ? 0u : (1u << 24));
   // launches of different streams are ordered behind each other (two half-resident launches would wait for each other for ever):
   // every launch is followed by an event record on ITS stream, the next launch - whatever its stream - waits for that event first
   // (a wait on an event of the same stream is a no-op for the hardware queue).  No stream handle outlives the call: a caller may
@@ -1626,7 +1634,7 @@ static int layers_core(const InfgenRollout* r, int c, int edgeless, void* stream
     if (skip_edges) return 0;
     if (fuse && O().attn_mode != 0)
       warm_request(pack + AH_POST + 4 * (QB / 4), 48 * QB, next_pack ? next_pack + AH_PRE : nullptr, 16 * QB);
-    return fuse ? edge_fused_launch(rows, r->Q, pack, Ks, Vs, e.off, e.cnt, e.src, e.rhat, r->AGG, r->A_cap, kv_once, stream, fmt < 0 ? r24 : fmt)
+    return fuse ? edge_fused_launch(rows, r->Q, pack, Ks, Vs, eset(e), r->AGG, r->A_cap, kv_once, stream, fmt < 0 ? r24 : fmt)
                 : infgen_edge_attn(rows, r->Q, r->U, Ks, Vs, e.off, e.cnt, e.src, e.rhat, r->AGG, r->Z, r->SIG, stream);
   };
   RET_IF(infgen_attn_pre(r->X, rows, r->attn_t[0], 0, r->Q, U, r->ringK[0] + slot, r->ringV[0] + slot, stream));
@@ -1705,9 +1713,8 @@ extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* 
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
-  static const int no_fold = getenv("INFGEN_NO_TAIL_FOLD") ? atoi(getenv("INFGEN_NO_TAIL_FOLD")) : 0;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !no_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));
@@ -1735,7 +1742,7 @@ extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* 
       RET_IF(prepare_edges(r, c + 1, 0, stream, false, true, split && integrate_groups(r) > 1 ? keys : nullptr));
     } else {          // after the last step only the raw feature of the new column is left (kept: the context's X stays what
                       // infgen_decode_step leaves)
-      RET_IF(infgen_fourier_embed(r->raw2, 2, nullptr, rows, r->four_xa, r->cat, 128, r->fus_in + 128, 512, 0, stream));
+      RET_IF(launch_fourier(step_fourier_set(r, FS_XA, sm0), stream));
     }
     RET_IF(raw_feature_fusion(r, stream));
   }
@@ -1845,7 +1852,7 @@ extern "C" int infgen_radius_edges(const InfgenRadiusEdges* r, const InfgenEdgeB
   if (r->gap_rule < 0 || r->gap_rule > 2) return fail("infgen_radius_edges", "gap_rule must be 0, 1 or 2");
   RadiusEdgesArgs a{r->n_q, r->q_node, r->q_pt, r->q_c0, r->q_c1, r->q_self, r->q_pair_off, r->p_pos, r->p_head, r->p_inv,
                     r->c_pos, r->c_head, r->c_inv, r->c_ok, r->c_src, r->pair_ok, r->radius, r->K, r->gap_rule, r->index_diff,
-                    EdgeBuf{e->off, e->cnt, e->src, e->raw, e->total, e->cap}, r->e_base};
+                    ebuf(*e), r->e_base};
   hipLaunchKernelGGL(k_radius_edges, dim3(ceil_div(r->n_q, 4)), dim3(256), 0, (hipStream_t)stream, a);
   return check_launch("infgen_radius_edges");
 }
@@ -1982,16 +1989,8 @@ extern "C" int infgen_insert_heading(const InfgenRollout* r, const InfgenInserti
   hipStream_t hs = (hipStream_t)stream;
   const int S = r->S, rows = r->S * r->A_cap, c = 1 + t;
   // categorical embedding / shape of the new rows (agent_decoder.py:1949-1950, :1993): shape_emb is an MLPEmbedding with K0 = 3
-  {
-    const float* P = I->shape_emb;
-    const int k0p = 8, o2 = mlpemb_off2(k0p), o3 = mlpemb_off3(k0p);
-    RET_IF(infgen_linear(I->new_shape, 3, nullptr, S, 3, P, 128, P + k0p * 128, 128, nullptr, nullptr, P + k0p * 128 + 128,
-                         P + k0p * 128 + 256, 1, I->t1, 128, stream));
-    RET_IF(infgen_linear(I->t1, 128, nullptr, S, 128, P + o2, 128, P + o2 + 16384, 128, nullptr, nullptr, P + o2 + 16384 + 128,
-                         P + o2 + 16384 + 256, 1, I->t2, 128, stream));
-    RET_IF(infgen_linear(I->t2, 128, nullptr, S, 128, P + o3, 128, P + o3 + 16384, 128, nullptr, nullptr, nullptr, nullptr, 0, I->shp, 128,
-                         stream));
-  }
+  // (three inputs, padded to 8 in the pack: the fp32 kernels at every attn_mode)
+  RET_IF(mlp_embedding_fp32(I->new_shape, 3, S, 3, 8, I->shape_emb, I->t1, I->t2, I->shp, 128, stream));
   InsertCatArgs ca{S, r->A_cap, I->inserted, I->new_row, r->type, I->type_a_emb, I->shp, I->new_shape, const_cast<float*>(r->cat_agent),
                    I->shape_all, I->new_local};
   hipLaunchKernelGGL(k_insert_cat, dim3(ceil_div(S * 32, NT)), dim3(NT), 0, hs, ca);

@@ -4,6 +4,7 @@ tokens, grid cells and masks are compared exactly, poses within graph_ref.BAR_ST
 times the error of an fp32 numpy evaluation against float64); everything a call must leave alone is compared bitwise, and every
 array a kernel could write carries a guard tail.  The Fourier embedding and the fusion MLP behind the gather are judged in
 test_ops_gpu.py / test_precision_gpu.py: here only their wiring is checked, bitwise against the same entries called by the test."""
+import contextlib
 import ctypes as C
 import functools
 
@@ -202,10 +203,29 @@ def test_raw_feature(col, no_grid):
         assert same(ten[k].cpu().numpy(), st[k]), k
 
 
-@pytest.mark.parametrize('n', [1, 33, 96])
-def test_raw_feature_rows(n):
+@contextlib.contextmanager
+def attn_mode(mode):
+    """the process-wide attn_mode for the calls inside (0: fusion_emb as three fp32 k_linear launches through tmp1 / tmp2)"""
+    lib, check = lib_and_check()
+    check(lib.infgen_set_attn_mode(mode), 'infgen_set_attn_mode')
+    try:
+        yield
+    finally:
+        check(lib.infgen_set_attn_mode(2), 'infgen_set_attn_mode')
+
+
+@pytest.mark.parametrize('n,mode', [pytest.param(1, 2, id='1'), pytest.param(33, 2, id='33'), pytest.param(96, 2, id='96'),
+                                    pytest.param(1, 0, id='1-fp32'), pytest.param(33, 0, id='33-fp32'), pytest.param(96, 0, id='96-fp32')])
+def test_raw_feature_rows(n, mode):
     """a shuffled row_list with a mask that has holes, n = 1, 33 and S * A_cap: compact slots (a masked-off slot gathers row 0), X
-    written at the listed unmasked rows only - bitwise the fusion of the compact fus_in - and untouched everywhere else"""
+    written at the listed unmasked rows only - bitwise the fusion of the compact fus_in - and untouched everywhere else.  attn_mode 2
+    (the default: k_mlpemb_h) and 0, where the entry's fusion writes tmp1, tmp2 and tmp1 again (its output aliases the first stage's)
+    and must still equal infgen_mlp_embedding with three separate arrays"""
+    with attn_mode(mode):
+        _raw_feature_rows(n)
+
+
+def _raw_feature_rows(n):
     lib, check = lib_and_check()
     st, ext = gr.gen_rawfeat()
     rows, col = st['S'] * st['A_cap'], 2
