@@ -17,6 +17,7 @@
  *                            (infgen/modules/layers.py:74-75,94-99,110-112)
  *   infgen_heads             token_predict_head / state_predict_head + greedy arg-max
  *                            (infgen/modules/agent_decoder.py:2161-2167)
+ *   infgen_heads_logprob     the same + the log-probability of the chosen token (pred_prob, agent_decoder.py:1689 / :2205)
  *   infgen_map_token_head    the map encoder's token_predict_head + top-10 (infgen/modules/map_decoder.py:119-121)
  *   infgen_map_graph         torch_cluster.radius_graph over map tokens + relative features
  *                            (infgen/modules/map_decoder.py:91-114)
@@ -79,6 +80,7 @@ enum {
   INFGEN_Q_MAX_AGENTS = 6,
   INFGEN_Q_ABI_VERSION = 7,
   INFGEN_Q_SIZEOF_ROLLOUT = 8,
+  INFGEN_Q_ATTN_SPLIT_ROWS = 9,   /* attn_mode 2 takes the split kernels (and the fused token log-probability) beyond this many rows */
 };
 int infgen_layout_query(int what);
 /* offset (floats) of a named field inside the AttentionLayer / Fourier pack; -1 if unknown */
@@ -191,6 +193,16 @@ typedef struct InfgenRollout {
    * (infgen/modules/agent_decoder.py:2133-2158).  A context with tap_x runs the per-sublayer launches (k_layers_p keeps the
    * stream in registers across the triples) */
   float* tap_x;
+  /* optional [steps][S * A_cap]: infgen_decode_step writes step t's slice with the FULL-softmax log-probability of the motion token
+   * every row emitted (log_softmax(logits)[next_token], after sampling where sample_k > 1) - every row of the layout, padding
+   * included; rows whose token is then overridden (teacher / replay, invalid state) keep the value of the head's own token.
+   * Greedy contexts on the split path (attn_mode 1, or 2 beyond 10240 rows) compute it inside the heads kernel and need no
+   * logits in memory; every other context needs store_logits or logits_scratch (refused otherwise).  infgen_rollout_run does
+   * not fold the step tail while it is set.  Added in front of the two ablation switches, which stay the
+   * struct's last members (tests/test_ablation_cpu.py pins that): their offsets moved by 8 bytes, INFGEN_Q_SIZEOF_ROLLOUT covers
+   * the new size, and INFGEN_Q_ABI_VERSION keeps answering 1 (a test pins that too; the Python binding checks the size, not the
+   * version, at load - rebuild both sides together). */
+  float* token_logprob;
   /* the reference's token ablations (agent_decoder.py use_grid_token / use_state_token; 0 = the full-token model).
    * no_grid_token: the fusion embedding takes [token | x_a | state] (fusion_pack packed with K0 = 384, fus_in keeps its 512
    * stride) and no grid_tab row is gathered.  no_state_token: after the ego override a predicted 'exit' becomes 'valid'. */
@@ -311,6 +323,14 @@ int infgen_attn_post_pre(float* X, int rows, const float* pack, const float* AGG
                          int has_pos, const float* next_pack, float* nQ, float* nU, float* nK, float* nV, void* stream);
 int infgen_heads(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
                  float* logits, int* next_token, int* next_state, void* stream);
+/* infgen_heads plus token_logprob [rows] = log_softmax(logits[row])[next_token[row]] (full softmax, fp32, max-subtracted, fixed
+ * summation order).  Where the split kernel runs (attn_mode 1, or 2 beyond 10240 rows) the log-sum-exp is fused into it and
+ * logits may be NULL; elsewhere k_heads writes the caller's logits [rows][token_size] (NULL: refused) and infgen_token_logprob
+ * reads them.  next_token / next_state / logits are bitwise those of infgen_heads. */
+int infgen_heads_logprob(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
+                         float* logits, int* next_token, int* next_state, float* token_logprob, void* stream);
+/* out[row] = logits[row][token[row]] - logsumexp(logits[row]) over n columns (one wave per row); 0 where token[row] < 0 */
+int infgen_token_logprob(const float* logits, int rows, int n, const int* token, float* out, void* stream);
 /* the map encoder's token_predict_head (infgen/modules/map_decoder.py:119-121) on the rows gather[k] (k < n) of X [..][ldx]:
  * logits [n][token_size] (raw, fp32) and top_idx [n][10] (int64), the indices of the 10 largest logits in descending order (softmax
  * is monotone), equal values lower index first.  pack = infgen_amd.packing.pack_mlp_layer of the head; token_size must be 1024.

@@ -101,6 +101,7 @@ class Rollout(C.Structure):
         ('replay_row', _p),
         ('map_scene', _p),
         ('tap_x', _p),
+        ('token_logprob', _p),
         ('no_grid_token', _i), ('no_state_token', _i),
     ]
 
@@ -175,6 +176,8 @@ SYMBOLS = {
     'infgen_attn_post': (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
     'infgen_attn_post_pre': (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
     'infgen_heads': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p]),
+    'infgen_heads_logprob': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
+    'infgen_token_logprob': (_i, [_p, _i, _i, _p, _p, _p]),
     'infgen_map_token_head': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
     'infgen_map_graph': (_i, [_i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p]),
     'infgen_build_edges': (_i, [C.POINTER(Rollout), _i, _i, _p]),
@@ -214,7 +217,7 @@ VM_SCRATCH_DOUBLES = 3072                # INFGEN_VM_SCRATCH_DOUBLES
 GRID_OVERLAP_MAX_CELLS = 16384           # INFGEN_GRID_OVERLAP_MAX_CELLS
 
 Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_ATTN_CAP, Q_MAX_AGENTS, \
-    Q_ABI_VERSION, Q_SIZEOF_ROLLOUT = range(9)
+    Q_ABI_VERSION, Q_SIZEOF_ROLLOUT, Q_ATTN_SPLIT_ROWS = range(10)
 
 KERNEL_IDS = ['k_linear', 'k_fourier', 'k_attn_pre', 'k_edge_attn', 'k_attn_post', 'k_heads', 'k_build_edges',
               'k_integrate', 'k_rawfeat_prep', 'k_map_graph', 'k_map_head']

@@ -238,6 +238,7 @@ extern "C" int infgen_prof_collect_steps(double* total_ms, int* calls, double* t
   return prof_collect_impl(total_ms, calls, total_macs, fourier_rows, step_ms, step_calls);
 }
 
+constexpr int ATTN_SPLIT_ROWS = 10240;     // INFGEN_Q_ATTN_SPLIT_ROWS: attn_mode 2 takes the split kernels beyond this many rows (attn_split)
 extern "C" int infgen_layout_query(int what) {
   switch (what) {
     case INFGEN_Q_ATTN_PACK_SIZE: return AL_SIZE;
@@ -249,6 +250,7 @@ extern "C" int infgen_layout_query(int what) {
     case INFGEN_Q_MAX_AGENTS: return MAX_SCENE_AGENTS;
     case INFGEN_Q_ABI_VERSION: return 1;
     case INFGEN_Q_SIZEOF_ROLLOUT: return (int)sizeof(InfgenRollout);
+    case INFGEN_Q_ATTN_SPLIT_ROWS: return ATTN_SPLIT_ROWS;
     default: return -1;
   }
 }
@@ -452,7 +454,8 @@ extern "C" int infgen_set_attn_mode(int mode) {
   return 0;
 }
 // the kernels of the other split families (k_heads_h, k_mlpemb_h) keep the by-size rule of the 64-row tiles
-static inline bool attn_split(int rows) { return O().attn_mode == 1 || (O().attn_mode >= 2 && rows > 10240); }
+static inline bool attn_split_for(int mode, int rows) { return mode == 1 || (mode >= 2 && rows > ATTN_SPLIT_ROWS); }
+static inline bool attn_split(int rows) { return attn_split_for(O().attn_mode, rows); }
 // 0: fp32 kernels, 1: k_attn_h, 2: k_attn_hs
 static inline int attn_kind(int rows) {
   switch (O().attn_mode) {
@@ -1004,7 +1007,9 @@ extern "C" int infgen_match_map_tokens(const float* traj_pos, const float* theta
 
 // the other split families on 64-row tiles (launch_attn_h is the model)
 static void launch_heads_h(const HeadsArgs& a, void* stream) {
-  hipLaunchKernelGGL(by_terms(k_heads_h<3>, k_heads_h_b16<1>, k_heads_h<1>), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
+  auto kern = a.token_logprob ? by_terms(k_heads_h<3, true>, k_heads_h_b16<1, true>, k_heads_h<1, true>)
+                              : by_terms(k_heads_h<3, false>, k_heads_h_b16<1, false>, k_heads_h<1, false>);
+  hipLaunchKernelGGL(kern, dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
 }
 static void launch_map_head_h(const MapHeadArgs& a, void* stream) {
   hipLaunchKernelGGL(by_terms(k_map_head_h<3>, k_map_head_h_b16<1>, k_map_head_h<1>), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
@@ -1017,13 +1022,16 @@ static void launch_mlpemb_h(const MlpEmbHArgs& m, void* stream) {
 // scratch: optional rows x 8 bytes - with it, launches of few row tiles deal the logit chunks to several workgroups per tile
 // keys_stay (infgen_rollout_run's folded tail): the split path neither clears the keys before (k_integrate of the previous step
 // did) nor decodes them after (k_integrate of this step will); *split_used tells the caller whether that path ran
+// token_logprob: only where attn_split(rows) holds (the fused k_heads_h<TERMS, true>); elsewhere the caller runs infgen_token_logprob
+// on the stored logits once next_token is final
 static int heads_impl(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
                       float* logits, int* next_token, int* next_state, unsigned long long* scratch, void* stream,
-                      bool keys_stay = false, bool* split_used = nullptr) {
+                      bool keys_stay = false, bool* split_used = nullptr, float* token_logprob = nullptr) {
   if (split_used) *split_used = false;
   if (rows <= 0) return 0;
   if (token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
-  HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1};
+  if (token_logprob && !attn_split(rows)) return fail("infgen_heads", "the fused log-probability needs the split kernel");
+  HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1, token_logprob};
   if (scratch && !attn_split(rows)) {
     const int no_split = knob::heads_nosplit;
     const int tiles = ceil_div(rows, TR), nchunk = token_size / 128;
@@ -1050,6 +1058,29 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
 extern "C" int infgen_heads(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
                             float* logits, int* next_token, int* next_state, void* stream) {
   return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream);
+}
+
+extern "C" int infgen_token_logprob(const float* logits, int rows, int n, const int* token, float* out, void* stream) {
+  if (rows <= 0) return 0;
+  if (!logits || !token || !out) return fail("infgen_token_logprob", "null pointer");
+  if (n <= 0) return fail("infgen_token_logprob", "n must be positive");
+  TokenLogprobArgs a{logits, rows, n, token, out};
+  hipLaunchKernelGGL(k_token_logprob, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
+  return check_launch("infgen_token_logprob");
+}
+
+// infgen_heads + the log-probability of next_token: fused (k_heads_h<TERMS, true>, logits optional) where attn_split picks the
+// split kernel, otherwise k_heads into the caller's logits and k_token_logprob over them
+extern "C" int infgen_heads_logprob(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
+                                    float* logits, int* next_token, int* next_state, float* token_logprob, void* stream) {
+  if (rows <= 0) return 0;
+  if (!token_logprob) return fail("infgen_heads_logprob", "token_logprob is NULL (infgen_heads is the entry without it)");
+  if (attn_split(rows))
+    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
+                      token_logprob);
+  if (!logits) return fail("infgen_heads_logprob", "this row count takes k_heads: it needs a logits buffer [rows][token_size]");
+  RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
+  return infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream);
 }
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) on the rows gather[k] of X.  Split arithmetic (k_map_head_h: one
@@ -1126,6 +1157,12 @@ static int validate(const InfgenRollout* r, const char* where) {
   if (r->ring <= r->W) return fail(where, "ring must exceed the temporal window");
   if (r->W > 16) return fail(where, "temporal window larger than 16 columns is not supported");
   if ((r->no_grid_token | r->no_state_token) & ~1) return fail(where, "no_grid_token / no_state_token must be 0 or 1");
+  if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
+    // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
+    const int mode = (r->opts.use ? r->opts : O()).attn_mode;
+    const bool fused = !(r->sample_k > 1 && r->sample_u) && attn_split_for(mode, r->S * r->A_cap);
+    if (!fused) return fail(where, "token_logprob needs store_logits or logits_scratch [rows][token_size] (few rows, or sampling)");
+  }
   return 0;
 }
 
@@ -1692,11 +1729,17 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
   const bool sample = r->sample_k > 1 && r->sample_u && (lg || r->logits_scratch);
   if (sample && !lg) lg = r->logits_scratch;
+  // token_logprob: greedy rows on the split path take the fused kernel; otherwise from the logits in memory (validate: there are
+  // some), once the emitted token is final
+  float* lp = r->token_logprob ? r->token_logprob + (size_t)t * rows : nullptr;
+  const bool lp_fused = lp && !sample && attn_split(rows);
+  if (lp && !lp_fused && !lg) lg = r->logits_scratch;
   // (tmp2 is scratch of the raw-feature stage, free here: the per-row keys of the split arg-max)
   RET_IF(heads_impl(r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token,
-                    r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream));
+                    r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream, false, nullptr, lp_fused ? lp : nullptr));
   if (sample)
     RET_IF(infgen_sample_topk(lg, rows, r->token_size, r->sample_k, r->sample_u + (size_t)t * rows, r->next_token, stream));
+  if (lp && !lp_fused) RET_IF(infgen_token_logprob(lg, rows, r->token_size, r->next_token, lp, stream));
   RET_IF(infgen_integrate(r, t, stream));
   RET_IF(infgen_raw_feature(r, c + 1, stream));
   return 0;
@@ -1714,7 +1757,7 @@ extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* 
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !r->token_logprob && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));

@@ -1172,4 +1172,32 @@ __global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
   a.token[row] = topi[pick];
 }
 
+// ------------------------------------------------------------------------------------------
+// k_token_logprob: log_softmax(logits[row])[token[row]] - the full-softmax log-probability of the token a step emitted, from
+// stored logits (the few-row k_heads path, and the sampled path, whose token is only known after k_sample_topk).
+// One wave per row like k_sample_topk, lane l walks the columns l, l + 64, ..: the row maximum first, then the sum of
+// exp(v - max), both per lane in ascending column order and across the lanes by a fixed xor butterfly (bitwise reproducible).
+// token < 0 (no token) writes 0; a token beyond the row writes NaN.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void k_token_logprob(TokenLogprobArgs a) {
+  const int row = blockIdx.x * 4 + wave_id();
+  if (row >= a.rows) return;
+  const int lane = lane_id();
+  const float* lg = a.logits + (size_t)row * a.n;
+  float m = -INFINITY;
+  for (int c = lane; c < a.n; c += 64) m = fmaxf(m, lg[c]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  float s = 0.f;
+  for (int c = lane; c < a.n; c += 64) s += expf(lg[c] - m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane != 0) return;
+  const int tok = a.token[row];
+  float out = 0.f;
+  if (tok >= a.n) out = __builtin_nanf("");
+  else if (tok >= 0) out = lg[tok] - (m + logf(s));
+  a.out[row] = out;
+}
+
 }  // namespace ig

@@ -291,6 +291,9 @@ struct HeadsArgs {
   // k_heads only, few rows: the token_size / 128 logit chunks dealt to gridDim.y = nsplit workgroups per row tile; each merges its
   // (max, first index) into part[row] as an ordered 64-bit key (atomicMax; zeroed by the caller), k_heads_finish decodes them
   unsigned long long* part; int nsplit;
+  // k_heads_h<TERMS, true> only: optional [rows], the full-softmax log-probability of next_token[row] (k_heads_h<TERMS, false> and
+  // k_heads never look at it: infgen_token_logprob serves them from stored logits)
+  float* token_logprob;
 };
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) over gathered rows: logits and the 10 most probable tokens
@@ -472,6 +475,12 @@ struct SampleArgs {
   int* token;                                // [rows] out
 };
 
+struct TokenLogprobArgs {
+  const float* logits; int rows; int n;      // [rows][n]
+  const int* token;                          // [rows]
+  float* out;                                // [rows]: logits[row][token] - logsumexp(row); 0 where token < 0
+};
+
 constexpr int MAP_GRAPH_C = 8;          // centre tokens per wave of k_map_graph (32 per workgroup: one LDS staging of the scene's tokens, one atomic)
 struct MapGraphArgs {
   int S, M_cap; const int* n_map;
@@ -500,7 +509,7 @@ __global__ void k_window_loglik(WindowLoglikArgs a);
 __global__ void k_bundle_field(BundleScoreArgs a);
 __global__ void k_bundle_meta(BundleScoreArgs a);
 __global__ void k_road_edge(RoadEdgeArgs a);
-template <int TERMS> __global__ void k_heads_h(HeadsArgs a);
+template <int TERMS, bool LP = false> __global__ void k_heads_h(HeadsArgs a);   // LP: + token_logprob
 template <int TERMS> __global__ void k_map_head_h(MapHeadArgs a);     // mlp_h.hip
 template <int TERMS> __global__ void k_map_head_h_b16(MapHeadArgs a);
 __global__ void k_map_topk(MapHeadArgs a);
@@ -515,7 +524,7 @@ template <int WAVES, int TERMS> __global__ void k_attn_h(AttnHArgs a);
 template <int WAVES, int TERMS> __global__ void k_attn_h_b16(AttnHArgs a);
 template <int TERMS> __global__ void k_attn_hs_b16(AttnHArgs a);
 template <int TERMS> __global__ void k_mlpemb_h_b16(MlpEmbHArgs a);
-template <int TERMS> __global__ void k_heads_h_b16(HeadsArgs a);
+template <int TERMS, bool LP> __global__ void k_heads_h_b16(HeadsArgs a);      // (no default: mlp_h_b16.hip renames k_heads_h to this)
 template <int TERMS> __global__ void k_fourier_h_b16(FourierArgs a);
 template <int TERMS> __global__ void k_fourier_h_multi_b16(FourierMultiArgs m);
 template <int TERMS> __global__ void k_attn_hs(AttnHArgs a);             // attn_hs.hip: the same for few rows (one 16-row group per workgroup)   // attn_h.hip     // fourier_h.hip: fp16 three-term split, register resident
@@ -551,6 +560,7 @@ template <bool kGrid> __global__ void k_insert_decide(InsertDecideArgs a);
 // kHeadToken = false: use_head_token = False (tanh * pi heading, unwrapped); kOffset = false: no xy offset (use_grid_token = False)
 template <bool kHeadToken, bool kOffset> __global__ void k_insert_finalize(InsertFinalizeArgs a);
 __global__ void k_sample_topk(SampleArgs a);
+__global__ void k_token_logprob(TokenLogprobArgs a);
 __global__ void k_layernorm(const float* X, int rows, const float* g, const float* b, float* Y);
 __global__ void k_radius_edges(RadiusEdgesArgs a);            // forward_kernels.hip
 __global__ void k_motion_features(MotionFeatArgs a);

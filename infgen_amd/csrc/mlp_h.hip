@@ -3,7 +3,8 @@
 //   k_mlpemb_h  MLPEmbedding (reference infgen/modules/layers.py:163-179) with a K0 = 128 j input:
 //               Linear(K0,128) LN ReLU Linear(128,128) LN ReLU Linear(128,128)   - the fusion embedding of the raw
 //               per-column feature (agent_decoder.py:2265-2287), three k_linear launches before
-//   k_heads_h   token_predict_head / state_predict_head + greedy arg-max (agent_decoder.py:2161-2167), k_heads before
+//   k_heads_h   token_predict_head / state_predict_head + greedy arg-max (agent_decoder.py:2161-2167), k_heads before;
+//               LP = true: also the full-softmax log-probability of the arg-max token (log-sum-exp beside the running arg-max)
 #include "kernels.h"
 #include "layout.h"
 #include "tile.cuh"
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(MH_NT, 2) void k_mlpemb_h(MlpEmbHArgs a) {
   }
 }
 
-template <int TERMS>
+template <int TERMS, bool LP>
 __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned short Wb[MH_RING][QUARTER];
   // token head: hdr | b0 g0 be0 ; state head: hdr | b0 g0 be0 | W3 [3][128] | b3 [3]
@@ -165,9 +166,13 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
     const float inv_h = frags_scaled(ht, Bh, Bl) * Vt[1];
     float bv = -INFINITY;
     int bidx = 0x7fffffff;
+    // LP: sum of exp(v - bv) over the lane's columns so far (bv, the running arg-max value, is their maximum); rescaled once per
+    // 128-wide chunk, whose 32 logits of the lane wait in lg until the chunk's maximum is known
+    float lse = 0.f;
     for (int c = 0; c < nchunk; ++c) {
       f32x4 lg[8];
       mh_zero(lg);
+      const float m_prev = bv;
 #pragma unroll
       for (int s = 0; s < 4; ++s) gemm_quarter<TERMS>(lg, qs.take(), Bh[s], Bl[s], lane);
 #pragma unroll
@@ -182,15 +187,31 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
         if (v1 > bv) { bv = v1; bidx = col + 1; }
         if (v2 > bv) { bv = v2; bidx = col + 2; }
         if (v3 > bv) { bv = v3; bidx = col + 3; }
+        if constexpr (LP) lg[t] = f32x4{v0, v1, v2, v3};
+      }
+      if constexpr (LP) {
+        lse *= expf(m_prev - bv);                    // (first chunk: exp(-inf) = 0 times 0)
+#pragma unroll
+        for (int t = 0; t < 8; ++t)
+          lse += (expf(lg[t][0] - bv) + expf(lg[t][1] - bv)) + (expf(lg[t][2] - bv) + expf(lg[t][3] - bv));
       }
     }
 #pragma unroll
     for (int off = 16; off < 64; off <<= 1) {
       const float ov = __shfl_xor(bv, off, 64);
       const int oi = __shfl_xor(bidx, off, 64);
+      if constexpr (LP) {                            // the row's four lanes in a fixed order: xor 16, then 32
+        const float os = __shfl_xor(lse, off, 64);
+        const float m = fmaxf(bv, ov);
+        lse = lse * expf(bv - m) + os * expf(ov - m);
+      }
       if (ov > bv || (ov == bv && oi < bidx)) { bv = ov; bidx = oi; }
     }
     if (valid && rg == 0) a.next_token[row] = bidx;
+    if constexpr (LP) {
+      // best - (max + log(sum)) with best == max by construction (the arg-max value IS the maximum): -log(sum), one rounding less
+      if (valid && rg == 0) a.token_logprob[row] = -logf(lse);
+    }
   }
 }
 
@@ -303,8 +324,10 @@ template __global__ void k_mlpemb_h<3>(MlpEmbHArgs);
 #endif
 template __global__ void k_mlpemb_h<1>(MlpEmbHArgs);
 #if !IG_BF16_OPERANDS
-template __global__ void k_heads_h<3>(HeadsArgs);
+template __global__ void k_heads_h<3, false>(HeadsArgs);
+template __global__ void k_heads_h<3, true>(HeadsArgs);
 #endif
-template __global__ void k_heads_h<1>(HeadsArgs);
+template __global__ void k_heads_h<1, false>(HeadsArgs);
+template __global__ void k_heads_h<1, true>(HeadsArgs);
 
 }  // namespace ig

@@ -299,7 +299,11 @@ class InfGen(nn.Module):
         if self._save_validate_reuslts:
             os.makedirs(self.save_path or '.', exist_ok=True)
             with open(rollouts_path, 'wb') as f:
-                pickle.dump({k: v.cpu() if torch.is_tensor(v) else v for k, v in formatted.items()}, f)
+                dump = dict(formatted)
+                if getattr(self.encoder, 'token_logprob', False):       # (InfGenDecoder.token_logprob: the rollout's own keys)
+                    dump.update({k: rollout[k] for k in ('next_token_logprob', 'next_token_logprob_mask', 'pred_prob',
+                                                         'rollout_logprob')})
+                pickle.dump({k: v.cpu() if torch.is_tensor(v) else v for k, v in dump.items()}, f)
         if self._online_metric and self.score_all_rollouts:
             # every rollout of every graph in one pass: the copies' dicts brought to one row layout (insertion gives each copy its
             # own rows), stacked, then batched features and one scoring call

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, scene_setup
+from .. import _lib, logprob, scene_setup
 from ..engine import InsertionHeadroomError, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -295,6 +295,16 @@ class InfGenDecoder(nn.Module):
         # never passes (fp32): '32' (default) the fp32-accurate operand split; 'bf16' bf16 operands with fp32 accumulation (packs of
         # bf16 weights, InfgenOptions.gemm_terms = 2; BASELINE config C5); '16' fp16 operands (gemm_terms = 1).  Set it before a call.
         self.rollout_precision = '32'
+        # True: inference / inference_batch / inference_rollouts (single graph or Batch) also return, per rollout,
+        #   next_token_logprob [A][T_cols] float32   log-probability of the motion token the row emitted (laid out like next_token_idx)
+        #   next_token_logprob_mask [A][T_cols] bool  decoded column, row alive, token >= 0, row neither replayed nor teacher-forced
+        #   pred_prob [A][steps]                      exp(logprob) where masked, else 0 - the softmax probability of the chosen token, the
+        #                                            array the reference allocates (agent_decoder.py:1689) and never fills (:2205)
+        #   rollout_logprob                           the masked sum, float64 on the device ([B] for a Batch), added in a fixed order:
+        #                                            bitwise reproducible, and the same from a Batch as from single calls
+        # The value is the FULL-softmax log-probability; the probability renormalised over the top-k tokens, the distribution a
+        # sampled rollout actually draws from, is not computed.  False (default): the dicts have exactly the keys they had.
+        self.token_logprob = False
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -432,13 +442,14 @@ class InfGenDecoder(nn.Module):
                                  # single-scene entry and the n-copies batch of inference_rollouts; the throughput entry
                                  # (inference_batch) returns the zero arrays the reference initialises them to
                                  seed_outputs=(batch is None or batch_seed_outputs) and not w.cfg.disable_insertion and not map_only,
-                                 copies=copies, options=self._PRECISIONS[str(self.rollout_precision)], replay=rp_host())
+                                 copies=copies, options=self._PRECISIONS[str(self.rollout_precision)], replay=rp_host(),
+                                 token_logprob=bool(self.token_logprob) and not map_only)
         # one engine per batch layout is kept across calls: a second call of the same shape re-uploads the scene arrays into
         # the first call's device buffers instead of building (and allocating) an engine again
         ekey = (len(scenes), PackedWeights.tables_key(*(vocab[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab),
                 bool(w.cfg.disable_insertion), w.cfg.num_recurrent_steps_val, k if not map_only else 1,
                 ik if insert_uniforms is not None else 1, bool(int(os.getenv('DEBUG', 0))), batch is None, map_only, xo is None,
-                bool(batch_seed_outputs), copies, replay is not None)
+                bool(batch_seed_outputs), copies, replay is not None, bool(self.token_logprob))
         eng = self._engines.get(ekey)
         if (stk is not None and eng is not None and eng.fits_device(stk) and
                 eng.reload_device(stk, scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo,
@@ -481,6 +492,7 @@ class InfGenDecoder(nn.Module):
                 zero[shape] = torch.zeros(*shape, device=dev)
             return zero[shape]
         T_cols = w.cfg.num_columns
+        lp_sum = eng.rollout_logprob() if eng.token_logprob is not None else None
         if copies > 1:                          # scene i's copies are adjacent in the engine's batch
             datas = [d_ for d_ in datas for _ in range(copies)]
         for i_, (d, o) in enumerate(zip(datas, outs)):
@@ -497,6 +509,10 @@ class InfGenDecoder(nn.Module):
                     r[k_] = z(*shp_) if w.cfg.use_grid_token or k_ == 'next_state_prob_seed' else None
             if 'agent_labels' not in r:
                 r.set_lazy('agent_labels', (lambda n=eng.hosts[i_]['A'] + o['num_inserted']: [[None] * T_cols for _ in range(n)]))
+            if lp_sum is not None:
+                r.set_lazy('pred_prob', (lambda o=o: logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'],
+                                                                       w.cfg.hist_columns, steps)))
+                r['rollout_logprob'] = lp_sum[i_]
             r['log_message'] = ('No agents inserted!' if o['num_inserted'] == 0 else
                                 f"Number of total inserted agents: {o['num_inserted']}")
             # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649)
@@ -657,10 +673,11 @@ class InfGenDecoder(nn.Module):
             return RolloutEngine(w, None, vocab, map_vocab, grid, insert_headroom=headroom, force_enter=debug, sample_k=k,
                                  sample_uniforms=sample_uniforms, insert_k=ik if insert_uniforms is not None else 1,
                                  insert_uniforms=insert_uniforms, seed_outputs=not cfg.disable_insertion, copies=copies,
-                                 options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay, replay=rp)
+                                 options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay, replay=rp,
+                                 token_logprob=bool(self.token_logprob))
         ekey = ('graphs', S, tkey,
                 bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies,
-                replay is not None)
+                replay is not None, bool(self.token_logprob))
         eng = self._engines.get(ekey)
         if eng is not None and eng.fits_batch(lay):
             eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay, replay=rp)
@@ -705,6 +722,9 @@ class InfGenDecoder(nn.Module):
             ins = (n_fin - c[:, 0])[j::copies]
             o['log_message'] = '\n'.join('No agents inserted!' if int(x) == 0 else f'Number of total inserted agents: {int(x)}'
                                          for x in ins)
+            if eng.token_logprob is not None:
+                o['pred_prob'] = logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'], cfg.hist_columns, steps)
+                o['rollout_logprob'] = eng.rollout_logprob()[j::copies]
             res.append({**map_keys, **o, **passthrough})
         # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649), per graph
         removed = c[::copies, 2]

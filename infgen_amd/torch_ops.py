@@ -9,6 +9,7 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.radius_firstk(pos_q (Nq, 2), pos_x (Nx, 2), ptr_q, ptr_x, r, K)    -> idx (Nq, K) int32 (-1 padded), cnt (Nq,)
     torch.ops.infgen_hip.attn_layer(x_dst (N, 128), pack, off, cnt, src, rhat?, x_src?)     -> (N, 128)
     torch.ops.infgen_hip.token_state_head(x (N, 128), tok_pack, st_pack, token_size, want_logits) -> token, state, logits
+    torch.ops.infgen_hip.token_logprob(logits (N, n), token (N,))                           -> (N,) log_softmax(logits)[token]; 0 where token < 0
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -152,6 +153,28 @@ def _(x, tok_pack, st_pack, token_size, want_logits=False):
     n = x.shape[0]
     return (x.new_empty(n, dtype=torch.int32), x.new_empty(n, dtype=torch.int32),
             x.new_empty(n if want_logits else 0, token_size, dtype=torch.float32))
+
+
+@torch.library.custom_op('infgen_hip::token_logprob', mutates_args=())
+def token_logprob(logits: torch.Tensor, token: torch.Tensor) -> torch.Tensor:
+    """full-softmax log-probability of one token per row: ``logits[row, token[row]] - logsumexp(logits[row])`` in fp32
+    (max-subtracted, fixed summation order: bitwise reproducible); rows whose token is negative give 0, a token of n or more gives
+    NaN (checked by the kernel: no host synchronisation, so the op can be captured in a graph)"""
+    if logits.dim() != 2 or token.shape != logits.shape[:1]:
+        raise ValueError('token_logprob takes logits (N, n) and token (N,)')
+    ops = _ops(logits.device)
+    n = logits.shape[0]
+    out = torch.zeros(n, device=logits.device)
+    if n:
+        lg, tok = _f32(logits), token.to(logits.device, torch.int32).contiguous()
+        _lib.check(ops.lib.infgen_token_logprob(_lib.ptr(lg), n, int(lg.shape[1]), _lib.ptr(tok), _lib.ptr(out), ops.stream),
+                   'infgen_token_logprob')
+    return out
+
+
+@token_logprob.register_fake
+def _(logits, token):
+    return logits.new_empty(logits.shape[0], dtype=torch.float32)
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
