@@ -81,6 +81,7 @@ enum {
   INFGEN_Q_ABI_VERSION = 7,
   INFGEN_Q_SIZEOF_ROLLOUT = 8,
   INFGEN_Q_ATTN_SPLIT_ROWS = 9,   /* attn_mode 2 takes the split kernels (and the fused token log-probability) beyond this many rows */
+  INFGEN_Q_HEADS_SAMPLE_K = 10,   /* the widest top-k beam the split heads kernel samples itself (infgen_heads_sample_fused) */
 };
 int infgen_layout_query(int what);
 /* offset (floats) of a named field inside the AttentionLayer / Fourier pack; -1 if unknown */
@@ -157,7 +158,8 @@ typedef struct InfgenRollout {
    * hv_ovr[s] as their head vector during the motion stage (agent_decoder.py:2083) */
   const int* first_new; const float* hv_ovr;
   /* reproducible top-k sampling (optional): sample_k > 1 -> every step draws the motion token by inverse CDF over
-   * the sample_k most probable tokens with the uniforms sample_u[t][row]; needs logits_scratch [rows][token_size] */
+   * the sample_k most probable tokens with the uniforms sample_u[t][row]; needs logits_scratch [rows][token_size] unless every
+   * step samples inside the heads kernel (infgen_heads_sample_fused(attn_mode, S * A_cap, sample_k)) */
   int sample_k; int _pad1;
   const float* sample_u; float* logits_scratch;
   /* per-context options (re-entrancy): with opts.use != 0 the rollout-level entries (infgen_decode_layers / _step /
@@ -193,11 +195,18 @@ typedef struct InfgenRollout {
    * (infgen/modules/agent_decoder.py:2133-2158).  A context with tap_x runs the per-sublayer launches (k_layers_p keeps the
    * stream in registers across the triples) */
   float* tap_x;
+  /* optional [steps][S * A_cap]: infgen_decode_step writes step t's slice with the log-probability of the sampled motion token under
+   * the sampler's OWN distribution (the softmax re-normalised over the sample_k best logits) - laid out and overridden like
+   * token_logprob, independent of it.  Written by sampling steps only (sample_k > 1 with sample_u): a greedy step leaves the slice
+   * as it is - the sampler is a point mass there, so a zeroed buffer already holds the answer.  It sits in front of token_logprob and the two
+   * ablation switches, whose places at the struct's end older tests pin; INFGEN_Q_SIZEOF_ROLLOUT covers the new size. */
+  float* sample_logprob;
   /* optional [steps][S * A_cap]: infgen_decode_step writes step t's slice with the FULL-softmax log-probability of the motion token
    * every row emitted (log_softmax(logits)[next_token], after sampling where sample_k > 1) - every row of the layout, padding
    * included; rows whose token is then overridden (teacher / replay, invalid state) keep the value of the head's own token.
-   * Greedy contexts on the split path (attn_mode 1, or 2 beyond 10240 rows) compute it inside the heads kernel and need no
-   * logits in memory; every other context needs store_logits or logits_scratch (refused otherwise).  infgen_rollout_run does
+   * Contexts on the split path (attn_mode 1, or 2 beyond 10240 rows) that decode greedily or sample inside the heads kernel
+   * (infgen_heads_sample_fused) compute it there and need no logits in memory; every other context needs store_logits or
+   * logits_scratch (refused otherwise).  infgen_rollout_run does
    * not fold the step tail while it is set.  Added in front of the two ablation switches, which stay the
    * struct's last members (tests/test_ablation_cpu.py pins that): their offsets moved by 8 bytes, INFGEN_Q_SIZEOF_ROLLOUT covers
    * the new size, and INFGEN_Q_ABI_VERSION keeps answering 1 (a test pins that too; the Python binding checks the size, not the
@@ -331,6 +340,24 @@ int infgen_heads_logprob(const float* X, int rows, const float* tok_pack, const 
                          float* logits, int* next_token, int* next_state, float* token_logprob, void* stream);
 /* out[row] = logits[row][token[row]] - logsumexp(logits[row]) over n columns (one wave per row); 0 where token[row] < 0 */
 int infgen_token_logprob(const float* logits, int rows, int n, const int* token, float* out, void* stream);
+/* infgen_heads with next_token drawn by top-k sampling: the k (1..16, <= token_size) best logits of the row in (value descending,
+ * column ascending) order, inverse CDF over p[j] = exp(v[j] - v[0]) with uniform[row] in [0, 1) - infgen_sample_topk's order and
+ * arithmetic, so the tokens equal infgen_heads + infgen_sample_topk bit for bit.  Optional outputs (NULL: not computed):
+ * logits [rows][token_size]; token_logprob [rows], the FULL-softmax log-probability of the sampled token; sample_logprob [rows], its
+ * log-probability under the re-normalised top-k distribution, (v_pick - v_0) - log(sum_j p[j]).  Where
+ * infgen_heads_sample_fused(attn_mode, rows, k) holds this is ONE launch of the split heads kernel, which keeps a running top-k in
+ * registers and stores no logit unless asked; elsewhere it is infgen_heads into the caller's logits (NULL: refused, "needs a logits
+ * buffer"), infgen_sample_topk_logprob and infgen_token_logprob.  k == 1 is the arg-max (sample_logprob 0). */
+int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                        const float* uniform, float* logits, int* next_token, int* next_state, float* token_logprob,
+                        float* sample_logprob, void* stream);
+/* 1 where top-k sampling with beam k runs inside the split heads kernel: attn_mode 1, or >= 2 beyond INFGEN_Q_ATTN_SPLIT_ROWS
+ * rows, and 2 <= k <= INFGEN_Q_HEADS_SAMPLE_K.  The one statement of the rule: infgen_heads_sample, infgen_decode_step and the
+ * engine's decision to allocate logits_scratch all go through it. */
+int infgen_heads_sample_fused(int attn_mode, int rows, int k);
+/* 1 where the greedy step's token log-probability comes out of the split heads kernel (infgen_heads_logprob's one launch, no logits
+ * in memory): attn_mode 1, or >= 2 beyond INFGEN_Q_ATTN_SPLIT_ROWS rows.  The greedy counterpart of infgen_heads_sample_fused. */
+int infgen_heads_logprob_fused(int attn_mode, int rows);
 /* the map encoder's token_predict_head (infgen/modules/map_decoder.py:119-121) on the rows gather[k] (k < n) of X [..][ldx]:
  * logits [n][token_size] (raw, fp32) and top_idx [n][10] (int64), the indices of the 10 largest logits in descending order (softmax
  * is monotone), equal values lower index first.  pack = infgen_amd.packing.pack_mlp_layer of the head; token_size must be 1024.
@@ -367,6 +394,9 @@ int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream);
 /* reproducible stand-in for softmax -> topk(k) -> multinomial (agent_decoder.py:2162-2163,2194-2195): the k most
  * probable tokens, inverse-CDF over their probabilities with a caller-supplied uniform per row; 1 <= k <= min(16, n), else refused */
 int infgen_sample_topk(const float* logits, int rows, int n, int k, const float* uniform, int* token, void* stream);
+/* the same, plus sample_logprob [rows] (optional): the pick's log-probability under the re-normalised top-k distribution */
+int infgen_sample_topk_logprob(const float* logits, int rows, int n, int k, const float* uniform, int* token,
+                               float* sample_logprob, void* stream);
 
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell

@@ -101,6 +101,7 @@ class Rollout(C.Structure):
         ('replay_row', _p),
         ('map_scene', _p),
         ('tap_x', _p),
+        ('sample_logprob', _p),
         ('token_logprob', _p),
         ('no_grid_token', _i), ('no_state_token', _i),
     ]
@@ -178,6 +179,9 @@ SYMBOLS = {
     'infgen_heads': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p]),
     'infgen_heads_logprob': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     'infgen_token_logprob': (_i, [_p, _i, _i, _p, _p, _p]),
+    'infgen_heads_sample': (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    'infgen_heads_sample_fused': (_i, [_i, _i, _i]),
+    'infgen_heads_logprob_fused': (_i, [_i, _i]),
     'infgen_map_token_head': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
     'infgen_map_graph': (_i, [_i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p]),
     'infgen_build_edges': (_i, [C.POINTER(Rollout), _i, _i, _p]),
@@ -188,6 +192,7 @@ SYMBOLS = {
     'infgen_decode_step': (_i, [C.POINTER(Rollout), _i, _p]),
     'infgen_rollout_run': (_i, [C.POINTER(Rollout), _i, _i, _p]),
     'infgen_sample_topk': (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    'infgen_sample_topk_logprob': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     'infgen_occupancy': (_i, [C.POINTER(Rollout), _i, _p, _p]),
     'infgen_occupancy_embed': (_i, [C.POINTER(Rollout), _i, _p, _p, _p, _p]),
     'infgen_point_edges': (_i, [C.POINTER(Rollout), _i, _p, _p, _i, _i, _f, _i, _f, _i, C.POINTER(EdgeBuf), C.POINTER(EdgeBuf), _p]),
@@ -217,7 +222,7 @@ VM_SCRATCH_DOUBLES = 3072                # INFGEN_VM_SCRATCH_DOUBLES
 GRID_OVERLAP_MAX_CELLS = 16384           # INFGEN_GRID_OVERLAP_MAX_CELLS
 
 Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_ATTN_CAP, Q_MAX_AGENTS, \
-    Q_ABI_VERSION, Q_SIZEOF_ROLLOUT, Q_ATTN_SPLIT_ROWS = range(10)
+    Q_ABI_VERSION, Q_SIZEOF_ROLLOUT, Q_ATTN_SPLIT_ROWS, Q_HEADS_SAMPLE_K = range(11)
 
 KERNEL_IDS = ['k_linear', 'k_fourier', 'k_attn_pre', 'k_edge_attn', 'k_attn_post', 'k_heads', 'k_build_edges',
               'k_integrate', 'k_rawfeat_prep', 'k_map_graph', 'k_map_head']

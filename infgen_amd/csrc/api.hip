@@ -251,6 +251,7 @@ extern "C" int infgen_layout_query(int what) {
     case INFGEN_Q_ABI_VERSION: return 1;
     case INFGEN_Q_SIZEOF_ROLLOUT: return (int)sizeof(InfgenRollout);
     case INFGEN_Q_ATTN_SPLIT_ROWS: return ATTN_SPLIT_ROWS;
+    case INFGEN_Q_HEADS_SAMPLE_K: return HEADS_KS;
     default: return -1;
   }
 }
@@ -456,6 +457,12 @@ extern "C" int infgen_set_attn_mode(int mode) {
 // the kernels of the other split families (k_heads_h, k_mlpemb_h) keep the by-size rule of the 64-row tiles
 static inline bool attn_split_for(int mode, int rows) { return mode == 1 || (mode >= 2 && rows > ATTN_SPLIT_ROWS); }
 static inline bool attn_split(int rows) { return attn_split_for(O().attn_mode, rows); }
+// the by-size rule of top-k sampling: inside the split heads kernel (k_heads_h<TERMS, LP, HEADS_KS>, no logits in memory) where that
+// kernel runs and the beam fits its lists; elsewhere k_sample_topk over stored logits.  One rule for infgen_heads_sample,
+// infgen_decode_step, validate() and, through infgen_heads_sample_fused, the engine
+static inline bool heads_sample_fused_for(int mode, int rows, int k) { return k > 1 && k <= HEADS_KS && attn_split_for(mode, rows); }
+extern "C" int infgen_heads_sample_fused(int attn_mode, int rows, int k) { return heads_sample_fused_for(attn_mode, rows, k) ? 1 : 0; }
+extern "C" int infgen_heads_logprob_fused(int attn_mode, int rows) { return attn_split_for(attn_mode, rows) ? 1 : 0; }
 // 0: fp32 kernels, 1: k_attn_h, 2: k_attn_hs
 static inline int attn_kind(int rows) {
   switch (O().attn_mode) {
@@ -1007,8 +1014,11 @@ extern "C" int infgen_match_map_tokens(const float* traj_pos, const float* theta
 
 // the other split families on 64-row tiles (launch_attn_h is the model)
 static void launch_heads_h(const HeadsArgs& a, void* stream) {
-  auto kern = a.token_logprob ? by_terms(k_heads_h<3, true>, k_heads_h_b16<1, true>, k_heads_h<1, true>)
-                              : by_terms(k_heads_h<3, false>, k_heads_h_b16<1, false>, k_heads_h<1, false>);
+  auto kern = a.sample_k > 1
+      ? (a.token_logprob ? by_terms(k_heads_h<3, true, HEADS_KS>, k_heads_h_b16<1, true, HEADS_KS>, k_heads_h<1, true, HEADS_KS>)
+                         : by_terms(k_heads_h<3, false, HEADS_KS>, k_heads_h_b16<1, false, HEADS_KS>, k_heads_h<1, false, HEADS_KS>))
+      : (a.token_logprob ? by_terms(k_heads_h<3, true, 0>, k_heads_h_b16<1, true, 0>, k_heads_h<1, true, 0>)
+                         : by_terms(k_heads_h<3, false, 0>, k_heads_h_b16<1, false, 0>, k_heads_h<1, false, 0>));
   hipLaunchKernelGGL(kern, dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
 }
 static void launch_map_head_h(const MapHeadArgs& a, void* stream) {
@@ -1024,14 +1034,21 @@ static void launch_mlpemb_h(const MlpEmbHArgs& m, void* stream) {
 // did) nor decodes them after (k_integrate of this step will); *split_used tells the caller whether that path ran
 // token_logprob: only where attn_split(rows) holds (the fused k_heads_h<TERMS, true>); elsewhere the caller runs infgen_token_logprob
 // on the stored logits once next_token is final
+// sample_k > 1 (with uniform [rows], sample_logprob optional): next_token is sampled inside the kernel - only where
+// heads_sample_fused_for holds; elsewhere the caller runs infgen_sample_topk on the stored logits
 static int heads_impl(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
                       float* logits, int* next_token, int* next_state, unsigned long long* scratch, void* stream,
-                      bool keys_stay = false, bool* split_used = nullptr, float* token_logprob = nullptr) {
+                      bool keys_stay = false, bool* split_used = nullptr, float* token_logprob = nullptr,
+                      int sample_k = 0, const float* uniform = nullptr, float* sample_logprob = nullptr) {
   if (split_used) *split_used = false;
   if (rows <= 0) return 0;
   if (token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
   if (token_logprob && !attn_split(rows)) return fail("infgen_heads", "the fused log-probability needs the split kernel");
-  HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1, token_logprob};
+  if (sample_k > 1 && (!uniform || !heads_sample_fused_for(O().attn_mode, rows, sample_k)))
+    return fail("infgen_heads", "sampling inside the kernel needs the split kernel, k within its width and uniforms");
+  if (sample_k <= 1) { sample_k = 0; uniform = nullptr; sample_logprob = nullptr; }
+  HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1, token_logprob,
+              sample_k, uniform, sample_logprob};
   if (scratch && !attn_split(rows)) {
     const int no_split = knob::heads_nosplit;
     const int tiles = ceil_div(rows, TR), nchunk = token_size / 128;
@@ -1081,6 +1098,53 @@ extern "C" int infgen_heads_logprob(const float* X, int rows, const float* tok_p
   if (!logits) return fail("infgen_heads_logprob", "this row count takes k_heads: it needs a logits buffer [rows][token_size]");
   RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
   return infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream);
+}
+
+static int sample_topk_impl(const char* me, const float* logits, int rows, int n, int k, const float* uniform, int* token,
+                            float* sample_logprob, void* stream) {
+  if (rows <= 0) return 0;
+  if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
+  if (k > n) return fail(me, "k must not exceed n");      // (the k-th pick of fewer than k logits is no token)
+  SampleArgs a{logits, rows, n, k, uniform, token, sample_logprob};
+  hipLaunchKernelGGL(k_sample_topk, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+extern "C" int infgen_sample_topk(const float* logits, int rows, int n, int k, const float* uniform, int* token,
+                                  void* stream) {
+  return sample_topk_impl("infgen_sample_topk", logits, rows, n, k, uniform, token, nullptr, stream);
+}
+
+extern "C" int infgen_sample_topk_logprob(const float* logits, int rows, int n, int k, const float* uniform, int* token,
+                                          float* sample_logprob, void* stream) {
+  return sample_topk_impl("infgen_sample_topk_logprob", logits, rows, n, k, uniform, token, sample_logprob, stream);
+}
+
+// infgen_heads with the motion token drawn by top-k sampling (k_sample_topk's order and arithmetic) and, optionally, its two
+// log-probabilities: one launch of k_heads_h<TERMS, LP, HEADS_KS> where heads_sample_fused_for holds (logits optional); elsewhere
+// heads into the caller's logits, k_sample_topk and k_token_logprob over them.  k == 1 is the arg-max (the greedy variant)
+extern "C" int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                                   const float* uniform, float* logits, int* next_token, int* next_state, float* token_logprob,
+                                   float* sample_logprob, void* stream) {
+  const char* me = "infgen_heads_sample";
+  if (rows <= 0) return 0;
+  if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
+  if (k > token_size) return fail(me, "k must not exceed token_size");
+  if (!uniform) return fail(me, "uniform is NULL");
+  if (k == 1) {      // a point mass on the arg-max: the greedy kernels, and log 1
+    if (sample_logprob && hipMemsetAsync(sample_logprob, 0, (size_t)rows * sizeof(float), (hipStream_t)stream) != hipSuccess)
+      return fail(me, "memset failed");
+    if (token_logprob) return infgen_heads_logprob(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, token_logprob, stream);
+    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream);
+  }
+  if (heads_sample_fused_for(O().attn_mode, rows, k))
+    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
+                      token_logprob, k, uniform, sample_logprob);
+  if (!logits) return fail(me, "this row count or beam takes k_sample_topk: it needs a logits buffer [rows][token_size]");
+  RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
+  RET_IF(sample_topk_impl(me, logits, rows, token_size, k, uniform, next_token, sample_logprob, stream));
+  if (token_logprob) RET_IF(infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream));
+  return 0;
 }
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) on the rows gather[k] of X.  Split arithmetic (k_map_head_h: one
@@ -1160,7 +1224,8 @@ static int validate(const InfgenRollout* r, const char* where) {
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
     const int mode = (r->opts.use ? r->opts : O()).attn_mode;
-    const bool fused = !(r->sample_k > 1 && r->sample_u) && attn_split_for(mode, r->S * r->A_cap);
+    const bool sampled = r->sample_k > 1 && r->sample_u;
+    const bool fused = sampled ? heads_sample_fused_for(mode, r->S * r->A_cap, r->sample_k) : attn_split_for(mode, r->S * r->A_cap);
     if (!fused) return fail(where, "token_logprob needs store_logits or logits_scratch [rows][token_size] (few rows, or sampling)");
   }
   return 0;
@@ -1315,16 +1380,6 @@ extern "C" int infgen_raw_feature_rows(const InfgenRollout* r, int col, const in
                             "infgen_raw_feature_rows/fusion"));
   hipLaunchKernelGGL(k_scatter_rows, dim3(ceil_div(n * 32, NT)), dim3(NT), 0, (hipStream_t)stream, r->tmp1, row_list, row_mask, n, r->X);
   return check_launch("infgen_raw_feature_rows/scatter");
-}
-
-extern "C" int infgen_sample_topk(const float* logits, int rows, int n, int k, const float* uniform, int* token,
-                                  void* stream) {
-  if (rows <= 0) return 0;
-  if (k < 1 || k > 16) return fail("infgen_sample_topk", "k must be in 1..16");
-  if (k > n) return fail("infgen_sample_topk", "k must not exceed n");      // (the k-th pick of fewer than k logits is no token)
-  SampleArgs a{logits, rows, n, k, uniform, token};
-  hipLaunchKernelGGL(k_sample_topk, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
-  return check_launch("infgen_sample_topk");
 }
 
 // Optional: the Fourier embeddings of the map and agent edge sets (matrix-pipe / VALU work) run on a side stream while
@@ -1727,18 +1782,24 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   if (t < 0 || c + 1 > r->T - 1) return fail("infgen_decode_step", "step beyond the column range");
   RET_IF(infgen_decode_layers(r, c, 0, stream));
   float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
-  const bool sample = r->sample_k > 1 && r->sample_u && (lg || r->logits_scratch);
-  if (sample && !lg) lg = r->logits_scratch;
-  // token_logprob: greedy rows on the split path take the fused kernel; otherwise from the logits in memory (validate: there are
-  // some), once the emitted token is final
+  // sampling: inside the split heads kernel where the by-size rule allows (no logits in memory: lg stays store_logits' slice or
+  // NULL); otherwise k_sample_topk over the step's logits
+  const bool s_fused = r->sample_k > 1 && r->sample_u && heads_sample_fused_for(O().attn_mode, rows, r->sample_k);
+  const bool sample = r->sample_k > 1 && r->sample_u && (s_fused || lg || r->logits_scratch);
+  if (sample && !s_fused && !lg) lg = r->logits_scratch;
+  const float* su = sample ? r->sample_u + (size_t)t * rows : nullptr;
+  float* slp = (sample && r->sample_logprob) ? r->sample_logprob + (size_t)t * rows : nullptr;
+  // token_logprob: rows on the split path take the fused kernel (greedy, or sampled inside it); otherwise from the logits in
+  // memory (validate: there are some), once the emitted token is final
   float* lp = r->token_logprob ? r->token_logprob + (size_t)t * rows : nullptr;
-  const bool lp_fused = lp && !sample && attn_split(rows);
+  const bool lp_fused = lp && (sample ? s_fused : attn_split(rows));
   if (lp && !lp_fused && !lg) lg = r->logits_scratch;
   // (tmp2 is scratch of the raw-feature stage, free here: the per-row keys of the split arg-max)
   RET_IF(heads_impl(r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token,
-                    r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream, false, nullptr, lp_fused ? lp : nullptr));
-  if (sample)
-    RET_IF(infgen_sample_topk(lg, rows, r->token_size, r->sample_k, r->sample_u + (size_t)t * rows, r->next_token, stream));
+                    r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream, false, nullptr, lp_fused ? lp : nullptr,
+                    s_fused ? r->sample_k : 0, su, slp));
+  if (sample && !s_fused)
+    RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream));
   if (lp && !lp_fused) RET_IF(infgen_token_logprob(lg, rows, r->token_size, r->next_token, lp, stream));
   RET_IF(infgen_integrate(r, t, stream));
   RET_IF(infgen_raw_feature(r, c + 1, stream));

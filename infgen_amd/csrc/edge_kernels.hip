@@ -1131,6 +1131,7 @@ template __global__ void k_insert_finalize<false, false>(InsertFinalizeArgs);
 // (agent_decoder.py:2162-2163,2194-2195: softmax -> topk(motion_beam_size) -> torch.multinomial):
 // the k most probable tokens in descending order, then inverse-CDF sampling over their
 // (re-normalised) probabilities with a caller-supplied uniform.  One wave per row.
+// sample_logprob (optional): the pick's log-probability under that re-normalised distribution.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
   const int row = blockIdx.x * 4 + wave_id();
@@ -1160,16 +1161,10 @@ __global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
     prev_v = best; prev_i = bi;
   }
   if (lane != 0) return;
-  float p[16], sum = 0.f;
-  for (int j = 0; j < a.k; ++j) { p[j] = expf(topv[j] - topv[0]); sum += p[j]; }
-  const float u = a.uniform[row] * sum;
-  float cdf = 0.f;
-  int pick = a.k - 1;
-  for (int j = 0; j < a.k; ++j) {
-    cdf += p[j];
-    if (u < cdf) { pick = j; break; }
-  }
+  float sum;
+  const int pick = topk_inverse_cdf<16>(topv, a.k, a.uniform[row], &sum);
   a.token[row] = topi[pick];
+  if (a.sample_logprob) a.sample_logprob[row] = (topv[pick] - topv[0]) - logf(sum);
 }
 
 // ------------------------------------------------------------------------------------------

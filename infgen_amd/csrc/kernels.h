@@ -294,7 +294,14 @@ struct HeadsArgs {
   // k_heads_h<TERMS, true> only: optional [rows], the full-softmax log-probability of next_token[row] (k_heads_h<TERMS, false> and
   // k_heads never look at it: infgen_token_logprob serves them from stored logits)
   float* token_logprob;
+  // k_heads_h<TERMS, LP, KS> with KS > 0 only (top-k sampling inside the kernel, 2 <= sample_k <= KS): next_token[row] is drawn by
+  // inverse CDF over the row's sample_k best logits with uniform[row] (k_sample_topk's order and arithmetic); token_logprob, when
+  // given, is then the sampled token's; sample_logprob (optional [rows]) its log-probability under the re-normalised top-k
+  int sample_k;
+  const float* uniform;
+  float* sample_logprob;
 };
+constexpr int HEADS_KS = 16;      // the one sampling width k_heads_h is instantiated with (wider beams take k_sample_topk)
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) over gathered rows: logits and the 10 most probable tokens
 constexpr int MAP_HEAD_N = 1024, MAP_TOPK = 10;
@@ -473,7 +480,30 @@ struct SampleArgs {
   int k;                                     // beam size (<= 16)
   const float* uniform;                      // [rows] caller-supplied U[0,1)
   int* token;                                // [rows] out
+  float* sample_logprob;                     // optional [rows] out: log-probability of token[row] under the re-normalised top-k distribution
 };
+
+// the last block of top-k sampling, shared by k_sample_topk and k_heads_h<TERMS, LP, KS> so the two cannot drift apart: inverse CDF
+// over p[j] = exp(topv[j] - topv[0]), j < k (topv descending), with the caller's uniform u01 in [0, 1); the first j with
+// u01 * sum < cdf, else k - 1.  *sum_out: the sum of the p[j] in j order.  Statically indexed (KMAX rounds, guarded by k).
+template <int KMAX> __device__ __forceinline__ int topk_inverse_cdf(const float (&topv)[KMAX], int k, float u01, float* sum_out) {
+  float p[KMAX], sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j)
+    if (j < k) { p[j] = expf(topv[j] - topv[0]); sum += p[j]; }
+  const float u = u01 * sum;
+  float cdf = 0.f;
+  int pick = k - 1;
+  bool found = false;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j)
+    if (j < k && !found) {
+      cdf += p[j];
+      if (u < cdf) { pick = j; found = true; }
+    }
+  *sum_out = sum;
+  return pick;
+}
 
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]
@@ -509,7 +539,7 @@ __global__ void k_window_loglik(WindowLoglikArgs a);
 __global__ void k_bundle_field(BundleScoreArgs a);
 __global__ void k_bundle_meta(BundleScoreArgs a);
 __global__ void k_road_edge(RoadEdgeArgs a);
-template <int TERMS, bool LP = false> __global__ void k_heads_h(HeadsArgs a);   // LP: + token_logprob
+template <int TERMS, bool LP = false, int KS = 0> __global__ void k_heads_h(HeadsArgs a);   // LP: + token_logprob; KS > 0: + top-k sampling
 template <int TERMS> __global__ void k_map_head_h(MapHeadArgs a);     // mlp_h.hip
 template <int TERMS> __global__ void k_map_head_h_b16(MapHeadArgs a);
 __global__ void k_map_topk(MapHeadArgs a);
@@ -524,7 +554,7 @@ template <int WAVES, int TERMS> __global__ void k_attn_h(AttnHArgs a);
 template <int WAVES, int TERMS> __global__ void k_attn_h_b16(AttnHArgs a);
 template <int TERMS> __global__ void k_attn_hs_b16(AttnHArgs a);
 template <int TERMS> __global__ void k_mlpemb_h_b16(MlpEmbHArgs a);
-template <int TERMS, bool LP> __global__ void k_heads_h_b16(HeadsArgs a);      // (no default: mlp_h_b16.hip renames k_heads_h to this)
+template <int TERMS, bool LP, int KS> __global__ void k_heads_h_b16(HeadsArgs a);          // (no default: mlp_h_b16.hip renames k_heads_h to this)
 template <int TERMS> __global__ void k_fourier_h_b16(FourierArgs a);
 template <int TERMS> __global__ void k_fourier_h_multi_b16(FourierMultiArgs m);
 template <int TERMS> __global__ void k_attn_hs(AttnHArgs a);             // attn_hs.hip: the same for few rows (one 16-row group per workgroup)   // attn_h.hip     // fourier_h.hip: fp16 three-term split, register resident

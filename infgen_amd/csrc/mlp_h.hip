@@ -5,6 +5,8 @@
 //               per-column feature (agent_decoder.py:2265-2287), three k_linear launches before
 //   k_heads_h   token_predict_head / state_predict_head + greedy arg-max (agent_decoder.py:2161-2167), k_heads before;
 //               LP = true: also the full-softmax log-probability of the arg-max token (log-sum-exp beside the running arg-max)
+//               KS > 0: top-k sampling (agent_decoder.py:2162-2163, 2194-2195) instead of the arg-max - a running top-KS per lane
+//               beside the running arg-max, merged over the row's four lanes after the last chunk, then k_sample_topk's inverse CDF
 #include "kernels.h"
 #include "layout.h"
 #include "tile.cuh"
@@ -97,7 +99,25 @@ __global__ __launch_bounds__(MH_NT, 2) void k_mlpemb_h(MlpEmbHArgs a) {
   }
 }
 
-template <int TERMS, bool LP>
+// One lane's running top-KS for k_heads_h<TERMS, LP, KS>: (value, column) pairs in k_sample_topk's total order (value descending,
+// then column ascending), statically indexed registers.  A lane meets its columns in ascending order, so a new pair goes behind the
+// entries of equal value: the first strictly smaller entry takes it and every later entry moves down by one (the last one drops out).
+// Only the first k (= sample_k, wave-uniform) slots are kept: the rest stay (-inf, none), which is what the merge shifts in.
+template <int KS> __device__ __forceinline__ void topk_insert(float (&tv)[KS], int (&ti)[KS], int k, float v, int col) {
+  bool sw = false;
+#pragma unroll
+  for (int j = 0; j < KS; ++j) {
+    if (j < k) {
+      sw = sw || v > tv[j];
+      const float ov = tv[j];
+      const int oi = ti[j];
+      tv[j] = sw ? v : ov;  ti[j] = sw ? col : oi;
+      v = sw ? ov : v;      col = sw ? oi : col;
+    }
+  }
+}
+
+template <int TERMS, bool LP, int KS>
 __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned short Wb[MH_RING][QUARTER];
   // token head: hdr | b0 g0 be0 ; state head: hdr | b0 g0 be0 | W3 [3][128] | b3 [3]
@@ -169,6 +189,16 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
     // LP: sum of exp(v - bv) over the lane's columns so far (bv, the running arg-max value, is their maximum); rescaled once per
     // 128-wide chunk, whose 32 logits of the lane wait in lg until the chunk's maximum is known
     float lse = 0.f;
+    // KS: the lane's KS best (value, column) pairs so far (topk_insert); thr, refreshed once per chunk, is the largest sample_k-th
+    // best value among the row's four lanes: a logit below it has sample_k better ones in that lane alone and is skipped (one equal
+    // to it may still win its tie by column and goes through the insertion, which leaves a list it does not beat as it is).  Past
+    // the first chunks few logits pass, so the wave-divergent insertion is rare
+    float tv[KS > 0 ? KS : 1], thr = -INFINITY;
+    int ti[KS > 0 ? KS : 1];
+    if constexpr (KS > 0) {
+#pragma unroll
+      for (int q = 0; q < KS; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
+    }
     for (int c = 0; c < nchunk; ++c) {
       f32x4 lg[8];
       mh_zero(lg);
@@ -188,6 +218,19 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
         if (v2 > bv) { bv = v2; bidx = col + 2; }
         if (v3 > bv) { bv = v3; bidx = col + 3; }
         if constexpr (LP) lg[t] = f32x4{v0, v1, v2, v3};
+        if constexpr (KS > 0) {
+          if (v0 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v0, col);
+          if (v1 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v1, col + 1);
+          if (v2 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v2, col + 2);
+          if (v3 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v3, col + 3);
+        }
+      }
+      if constexpr (KS > 0) {
+        float kth = tv[0];
+#pragma unroll
+        for (int q = 1; q < KS; ++q) kth = q < a.sample_k ? tv[q] : kth;
+        thr = fmaxf(kth, __shfl_xor(kth, 16, 64));
+        thr = fmaxf(thr, __shfl_xor(thr, 32, 64));
       }
       if constexpr (LP) {
         lse *= expf(m_prev - bv);                    // (first chunk: exp(-inf) = 0 times 0)
@@ -207,10 +250,48 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
       }
       if (ov > bv || (ov == bv && oi < bidx)) { bv = ov; bidx = oi; }
     }
-    if (valid && rg == 0) a.next_token[row] = bidx;
-    if constexpr (LP) {
-      // best - (max + log(sum)) with best == max by construction (the arg-max value IS the maximum): -log(sum), one rounding less
-      if (valid && rg == 0) a.token_logprob[row] = -logf(lse);
+    if constexpr (KS == 0) {
+      if (valid && rg == 0) a.next_token[row] = bidx;
+      if constexpr (LP) {
+        // best - (max + log(sum)) with best == max by construction (the arg-max value IS the maximum): -log(sum), one rounding less
+        if (valid && rg == 0) a.token_logprob[row] = -logf(lse);
+      }
+    } else {
+      // the row's top-KS from its four lanes' lists: KS rounds, each takes the best head under the total order (the lanes' columns
+      // are disjoint, so the winner is the lane whose head has the winning column) and that lane's list moves up by one
+      float mv[KS];
+      int mi[KS];
+#pragma unroll
+      for (int r = 0; r < KS; ++r) {
+        mv[r] = -INFINITY; mi[r] = 0x7fffffff;
+        if (r < a.sample_k) {                        // (wave-uniform: only the first sample_k results are read)
+          float wv = tv[0];
+          int wi = ti[0];
+#pragma unroll
+          for (int off = 16; off < 64; off <<= 1) {
+            const float ov = __shfl_xor(wv, off, 64);
+            const int oi = __shfl_xor(wi, off, 64);
+            if (ov > wv || (ov == wv && oi < wi)) { wv = ov; wi = oi; }
+          }
+          mv[r] = wv; mi[r] = wi;
+          const bool won = wi == ti[0];
+#pragma unroll
+          for (int q = 0; q + 1 < KS; ++q) { tv[q] = won ? tv[q + 1] : tv[q]; ti[q] = won ? ti[q + 1] : ti[q]; }
+          tv[KS - 1] = won ? -INFINITY : tv[KS - 1];
+          ti[KS - 1] = won ? 0x7fffffff : ti[KS - 1];
+        }
+      }
+      float sum;
+      const int pick = topk_inverse_cdf<KS>(mv, a.sample_k, valid ? a.uniform[row] : 0.f, &sum);
+      float pv = mv[0];
+      int pi = mi[0];
+#pragma unroll
+      for (int q = 1; q < KS; ++q) { pv = q == pick ? mv[q] : pv; pi = q == pick ? mi[q] : pi; }
+      if (valid && rg == 0) {
+        a.next_token[row] = pi;
+        if (a.sample_logprob) a.sample_logprob[row] = (pv - mv[0]) - logf(sum);
+        if constexpr (LP) a.token_logprob[row] = pv - (bv + logf(lse));
+      }
     }
   }
 }
@@ -324,10 +405,14 @@ template __global__ void k_mlpemb_h<3>(MlpEmbHArgs);
 #endif
 template __global__ void k_mlpemb_h<1>(MlpEmbHArgs);
 #if !IG_BF16_OPERANDS
-template __global__ void k_heads_h<3, false>(HeadsArgs);
-template __global__ void k_heads_h<3, true>(HeadsArgs);
+template __global__ void k_heads_h<3, false, 0>(HeadsArgs);
+template __global__ void k_heads_h<3, true, 0>(HeadsArgs);
+template __global__ void k_heads_h<3, false, HEADS_KS>(HeadsArgs);
+template __global__ void k_heads_h<3, true, HEADS_KS>(HeadsArgs);
 #endif
-template __global__ void k_heads_h<1, false>(HeadsArgs);
-template __global__ void k_heads_h<1, true>(HeadsArgs);
+template __global__ void k_heads_h<1, false, 0>(HeadsArgs);
+template __global__ void k_heads_h<1, true, 0>(HeadsArgs);
+template __global__ void k_heads_h<1, false, HEADS_KS>(HeadsArgs);
+template __global__ void k_heads_h<1, true, HEADS_KS>(HeadsArgs);
 
 }  // namespace ig

@@ -550,7 +550,7 @@ class RolloutEngine:
                  insert_k: int = 1, insert_uniforms: Optional[np.ndarray] = None, seed_outputs: bool = False,
                  use_graph: Optional[bool] = None, copies: int = 1, flags: Optional[Mapping[str, bool]] = None,
                  tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None,
-                 token_logprob: bool = False):
+                 token_logprob: bool = False, sample_logprob: bool = False):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -564,7 +564,12 @@ class RolloutEngine:
         ``token_logprob``: every decode step also records the full-softmax log-probability of the motion token each row emitted
         (``next_token_logprob`` / ``next_token_logprob_mask`` of the outputs; infgen_amd/logprob.py).  Large greedy batches compute
         it inside the heads kernel; small or sampled ones read the step's logits (a [rows][token_size] scratch is allocated when
-        neither ``store_logits`` nor sampling keeps them)."""
+        neither ``store_logits`` nor sampling keeps them).
+        ``sample_logprob``: every decode step also records the log-probability of the sampled motion token under the sampler's OWN
+        distribution, the softmax re-normalised over the ``sample_k`` best logits (``next_token_sample_logprob``, masked by
+        ``next_token_logprob_mask``; ``rollout_sample_logprob()``).  Independent of ``token_logprob``; 0 where masked when
+        ``sample_k <= 1`` (a point mass).  Sampled rollouts whose every step samples inside the heads kernel
+        (``infgen_heads_sample_fused``) keep no logits in memory: ``logits_scratch`` is None."""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -736,11 +741,13 @@ class RolloutEngine:
         if self.sample_k > 1:
             assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
             self.sample_u = torch.from_numpy(self._uniform_rows(sample_uniforms, amax)).to(dev)
-            if self.logits is None:
-                self.logits_scratch = f(rows, cfg.token_size)
+        # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
         self.token_logprob = f(steps, rows) if token_logprob else None
+        # [steps][rows] log-probability of the sampled token under the re-normalised top-k (InfgenRollout.sample_logprob)
+        self.sample_logprob = f(steps, rows) if sample_logprob else None
+        self._rollout_lp = self._rollout_slp = None
         self.tok_tab = self.grid_tab = self.cat_agent = self.cat_seed = None
         self.x_pt = None
         self._ctx = None
@@ -1122,6 +1129,8 @@ class RolloutEngine:
             buf.zero_()
         if self.token_logprob is not None:
             self.token_logprob.zero_()
+        if self.sample_logprob is not None:
+            self.sample_logprob.zero_()
 
     _STATE = ('pos', 'head', 'state', 'token', 'gridtok', 'imask', 'catflag', 'tmask', 'atype', 'bos', 'n_agents')
 
@@ -1498,6 +1507,7 @@ class RolloutEngine:
             c.first_new, c.hv_ovr = P(self.ins['first_new']), P(self.ins['hv_ovr'])
         c.sample_k, c.sample_u, c.logits_scratch = self.sample_k, P(self.sample_u), P(self.logits_scratch)
         c.token_logprob = P(self.token_logprob)
+        c.sample_logprob = P(self.sample_logprob)
         self._ctx = c
         self._refresh_opts()
         _lib.check(self.lib.infgen_rollout_validate(C.byref(c)), 'infgen_rollout_validate')      # (the packs' headers, looked at afresh)
@@ -1518,14 +1528,17 @@ class RolloutEngine:
         self._ctx.four_t_dt = None
         if o.fourier_mode != 0 and self.flags['dt_table']:
             self._ctx.four_t_dt = _lib.ptr(self.w.time_gap_table(self.lib, int(o.gemm_terms), self.ops.stream))
-        if self.token_logprob is not None and self.logits is None and self.logits_scratch is None:
-            # only greedy rows on the split path need no logits in memory (api.hip: attn_split); everything else reads the step's
-            split_rows = self.lib.infgen_layout_query(_lib.Q_ATTN_SPLIT_ROWS)
-            fused = self.sample_k <= 1 and (int(o.attn_mode) == 1 or (int(o.attn_mode) >= 2 and self.rows > split_rows))
-            if not fused:
-                self.logits_scratch = torch.zeros(self.rows, self.cfg.token_size, device=self.device)
-                self._ctx.logits_scratch = _lib.ptr(self.logits_scratch)
-                self._graph = self._wgraph = None          # (a captured graph holds the old pointers)
+        # does a step read logits from memory?  The library's own rules (infgen_heads_sample_fused for a sampled step,
+        # infgen_heads_logprob_fused for a greedy one with token_logprob) - every step of a rollout has the same rows, beam and
+        # switches, so either all of them stay inside the heads kernel or none does
+        if self.sample_k > 1:
+            in_kernel = self.lib.infgen_heads_sample_fused(int(o.attn_mode), self.rows, self.sample_k)
+        else:
+            in_kernel = self.token_logprob is None or self.lib.infgen_heads_logprob_fused(int(o.attn_mode), self.rows)
+        if not in_kernel and self.logits is None and self.logits_scratch is None:
+            self.logits_scratch = torch.zeros(self.rows, self.cfg.token_size, device=self.device)
+            self._ctx.logits_scratch = _lib.ptr(self.logits_scratch)
+            self._graph = self._wgraph = None          # (a captured graph holds the old pointers)
         o.row_groups = o.n_row_groups = None
         o.row_group_margin = 0
         if groups and self.insertion and self.ins is not None and self.flags['row_groups']:
@@ -1645,6 +1658,7 @@ class RolloutEngine:
         shape_all = self.ins['shape_all'].cpu().numpy().reshape(self.S, self.A_cap, 3) if self.ins is not None else None
         replay_row = self.replay_row.cpu().numpy().astype(bool) if self.replay_row is not None else None
         tok_lp = self.token_logprob.cpu().numpy() if self.token_logprob is not None else None
+        smp_lp = self.sample_logprob.cpu().numpy() if self.sample_logprob is not None else None
         outs = []
         for s, h in enumerate(self.hosts):
             A0, M = h['A'], h['M']
@@ -1693,15 +1707,19 @@ class RolloutEngine:
                      gt_traj=np.asarray(sc['position'])[filt][:, H:, :2].copy(), num_inserted=A - A0)
             if replay_row is not None:
                 o['replay_mask'] = replay_row[s, :A].copy()        # the rows that followed their plan (inserted rows never do)
-            if tok_lp is not None:
+            if tok_lp is not None or smp_lp is not None:
+                n_st = (tok_lp if tok_lp is not None else smp_lp).shape[0]
                 first = np.full(A, hc, np.int64)
                 first[A0:] = bos_dev[s, A0:A].astype(np.int64) + 1
                 forced = replay_row[s, :A] if replay_row is not None else np.full(A, self.teacher_token is not None)
-                m = logprob.logprob_mask(torch.from_numpy(ntok), torch.from_numpy(first), hc, tok_lp.shape[0],
+                m = logprob.logprob_mask(torch.from_numpy(ntok), torch.from_numpy(first), hc, n_st,
                                          torch.from_numpy(np.ascontiguousarray(forced))).numpy()
-                lp = np.zeros((A, self.T), np.float32)
-                lp[:, hc:hc + tok_lp.shape[0]] = tok_lp[:, s * self.A_cap:s * self.A_cap + A].T
-                o['next_token_logprob'], o['next_token_logprob_mask'] = np.where(m, lp, np.float32(0)), m
+                for key, buf in (('next_token_logprob', tok_lp), ('next_token_sample_logprob', smp_lp)):
+                    if buf is not None:
+                        lp = np.zeros((A, self.T), np.float32)
+                        lp[:, hc:hc + n_st] = buf[:, s * self.A_cap:s * self.A_cap + A].T
+                        o[key] = np.where(m, lp, np.float32(0))
+                o['next_token_logprob_mask'] = m
             if self.ins is not None:
                 o['agent_labels'] = self._agent_labels(s, A)
             if self.seed_out is not None:
@@ -1796,16 +1814,23 @@ class RolloutEngine:
                      pred_type=atype, pred_shape=pshape, eval_shape=eval_shape, next_token_idx=ntok, next_state_idx=nstate)
         if self.replay_row is not None:
             batch['replay_mask'] = self.replay_row.bool()
-        if self.token_logprob is not None:
-            steps = self.token_logprob.shape[0]
+        if self.token_logprob is not None or self.sample_logprob is not None:
+            steps = (self.token_logprob if self.token_logprob is not None else self.sample_logprob).shape[0]
             first = torch.where(init, torch.full_like(self.bos, hc, dtype=torch.long), self.bos.long() + 1)
             forced = (self.replay_row.bool() if self.replay_row is not None
                       else torch.full((S, A_cap), self.teacher_token is not None, device=dev))
             m = logprob.logprob_mask(ntok, first, hc, steps, forced) & (row < n_fin[:, None])[..., None]
-            lp = zf(S, A_cap, T)
-            lp[:, :, hc:hc + steps] = self.token_logprob.view(steps, S, A_cap).permute(1, 2, 0)
-            batch['next_token_logprob'], batch['next_token_logprob_mask'] = torch.where(m, lp, zf(())), m
-            self._rollout_lp = logprob.rollout_logprob(lp, m)
+            if self.token_logprob is not None:
+                lp = zf(S, A_cap, T)
+                lp[:, :, hc:hc + steps] = self.token_logprob.view(steps, S, A_cap).permute(1, 2, 0)
+                batch['next_token_logprob'] = torch.where(m, lp, zf(()))
+                self._rollout_lp = logprob.rollout_logprob(lp, m)
+            if self.sample_logprob is not None:
+                slp = zf(S, A_cap, T)
+                slp[:, :, hc:hc + steps] = self.sample_logprob.view(steps, S, A_cap).permute(1, 2, 0)
+                batch['next_token_sample_logprob'] = torch.where(m, slp, zf(()))
+                self._rollout_slp = logprob.rollout_logprob(slp, m)
+            batch['next_token_logprob_mask'] = m
         return batch, E, ph, lg_all, x_pt_all, n_fin
 
     def outputs_device(self, detach: bool = False) -> List[Dict[str, torch.Tensor]]:
@@ -1868,7 +1893,8 @@ class RolloutEngine:
         batch, E, ph, lg_all, x_pt_all, _ = self._epilogue_arrays(False)
         S, A_cap, T, B, n, dev = self.S, self.A_cap, self.T, self.S0, self.copies, self.device
         fin, init = self.n_agents, self._ing['counts'][:, 0]
-        pack_fin = self._PACK_FIN + tuple(k for k in ('replay_mask', 'next_token_logprob', 'next_token_logprob_mask') if k in batch)
+        pack_fin = self._PACK_FIN + tuple(k for k in ('replay_mask', 'next_token_logprob', 'next_token_sample_logprob',
+                                                  'next_token_logprob_mask') if k in batch)
         keys = pack_fin + ('valid_mask', 'gt_traj')
         srcs = [batch[k].contiguous() for k in pack_fin] + [E['val'], E['gt']]
         x_pt = None
@@ -1908,6 +1934,11 @@ class RolloutEngine:
         ``outputs_batch()`` call, added up in an order that does not depend on the batch (``logprob.fixed_order_sum``)"""
         assert getattr(self, '_rollout_lp', None) is not None, 'needs token_logprob=True and an outputs_device() / outputs_batch() call'
         return self._rollout_lp
+
+    def rollout_sample_logprob(self) -> torch.Tensor:
+        """[S] float64 on the device: every scene's masked sum of ``next_token_sample_logprob``, as ``rollout_logprob`` sums"""
+        assert getattr(self, '_rollout_slp', None) is not None, 'needs sample_logprob=True and an outputs_device() / outputs_batch() call'
+        return self._rollout_slp
 
     def agent_steps(self) -> int:
         """agent-steps (10 Hz) decoded by the last full rollout of this batch (the rows decoded at every step, incl. the

@@ -10,7 +10,9 @@ the CPU as well as on the device:
     rollout_logprob   the masked sum in float64, added up in an order that depends on nothing but the element positions
 
 The value is the log-probability under the full softmax over the vocabulary.  A sampled rollout draws from the distribution
-renormalised over its top-k tokens; that probability is a different quantity and is not computed here.
+renormalised over its top-k tokens; that probability is a different quantity, written by the same kernels into
+``InfgenRollout.sample_logprob`` (``RolloutEngine(sample_logprob=True)``: ``next_token_sample_logprob``, under the same mask and
+summed by the same ``rollout_logprob``).
 """
 from __future__ import annotations
 

@@ -303,6 +303,9 @@ class InfGen(nn.Module):
                 if getattr(self.encoder, 'token_logprob', False):       # (InfGenDecoder.token_logprob: the rollout's own keys)
                     dump.update({k: rollout[k] for k in ('next_token_logprob', 'next_token_logprob_mask', 'pred_prob',
                                                          'rollout_logprob')})
+                if getattr(self.encoder, 'sample_logprob', False):      # (InfGenDecoder.sample_logprob: under the sampler's own top-k)
+                    dump.update({k: rollout[k] for k in ('next_token_sample_logprob', 'next_token_logprob_mask',
+                                                         'rollout_sample_logprob')})
                 pickle.dump({k: v.cpu() if torch.is_tensor(v) else v for k, v in dump.items()}, f)
         if self._online_metric and self.score_all_rollouts:
             # every rollout of every graph in one pass: the copies' dicts brought to one row layout (insertion gives each copy its

@@ -303,8 +303,15 @@ class InfGenDecoder(nn.Module):
         #   rollout_logprob                           the masked sum, float64 on the device ([B] for a Batch), added in a fixed order:
         #                                            bitwise reproducible, and the same from a Batch as from single calls
         # The value is the FULL-softmax log-probability; the probability renormalised over the top-k tokens, the distribution a
-        # sampled rollout actually draws from, is not computed.  False (default): the dicts have exactly the keys they had.
+        # sampled rollout actually draws from, is ``sample_logprob``'s.  False (default): the dicts have exactly the keys they had.
         self.token_logprob = False
+        # True: the same entries also return, per rollout, the probability under the sampler's OWN distribution (the softmax
+        # re-normalised over the motion_beam_size best logits; what reweighting or fine-tuning on sampled rollouts needs)
+        #   next_token_sample_logprob [A][T_cols] float32   laid out and masked like next_token_logprob (next_token_logprob_mask comes
+        #                                                   with either flag); 0 where masked for a greedy rollout (a point mass)
+        #   rollout_sample_logprob                          the masked sum, float64 on the device ([B] for a Batch), rollout_logprob's order
+        # Independent of token_logprob.  False (default): the dicts have exactly the keys they had.
+        self.sample_logprob = False
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -443,13 +450,14 @@ class InfGenDecoder(nn.Module):
                                  # (inference_batch) returns the zero arrays the reference initialises them to
                                  seed_outputs=(batch is None or batch_seed_outputs) and not w.cfg.disable_insertion and not map_only,
                                  copies=copies, options=self._PRECISIONS[str(self.rollout_precision)], replay=rp_host(),
-                                 token_logprob=bool(self.token_logprob) and not map_only)
+                                 token_logprob=bool(self.token_logprob) and not map_only,
+                                 sample_logprob=bool(self.sample_logprob) and not map_only)
         # one engine per batch layout is kept across calls: a second call of the same shape re-uploads the scene arrays into
         # the first call's device buffers instead of building (and allocating) an engine again
         ekey = (len(scenes), PackedWeights.tables_key(*(vocab[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab),
                 bool(w.cfg.disable_insertion), w.cfg.num_recurrent_steps_val, k if not map_only else 1,
                 ik if insert_uniforms is not None else 1, bool(int(os.getenv('DEBUG', 0))), batch is None, map_only, xo is None,
-                bool(batch_seed_outputs), copies, replay is not None, bool(self.token_logprob))
+                bool(batch_seed_outputs), copies, replay is not None, bool(self.token_logprob), bool(self.sample_logprob))
         eng = self._engines.get(ekey)
         if (stk is not None and eng is not None and eng.fits_device(stk) and
                 eng.reload_device(stk, scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo,
@@ -493,6 +501,7 @@ class InfGenDecoder(nn.Module):
             return zero[shape]
         T_cols = w.cfg.num_columns
         lp_sum = eng.rollout_logprob() if eng.token_logprob is not None else None
+        slp_sum = eng.rollout_sample_logprob() if eng.sample_logprob is not None else None
         if copies > 1:                          # scene i's copies are adjacent in the engine's batch
             datas = [d_ for d_ in datas for _ in range(copies)]
         for i_, (d, o) in enumerate(zip(datas, outs)):
@@ -513,6 +522,8 @@ class InfGenDecoder(nn.Module):
                 r.set_lazy('pred_prob', (lambda o=o: logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'],
                                                                        w.cfg.hist_columns, steps)))
                 r['rollout_logprob'] = lp_sum[i_]
+            if slp_sum is not None:
+                r['rollout_sample_logprob'] = slp_sum[i_]
             r['log_message'] = ('No agents inserted!' if o['num_inserted'] == 0 else
                                 f"Number of total inserted agents: {o['num_inserted']}")
             # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649)
@@ -674,10 +685,10 @@ class InfGenDecoder(nn.Module):
                                  sample_uniforms=sample_uniforms, insert_k=ik if insert_uniforms is not None else 1,
                                  insert_uniforms=insert_uniforms, seed_outputs=not cfg.disable_insertion, copies=copies,
                                  options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay, replay=rp,
-                                 token_logprob=bool(self.token_logprob))
+                                 token_logprob=bool(self.token_logprob), sample_logprob=bool(self.sample_logprob))
         ekey = ('graphs', S, tkey,
                 bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies,
-                replay is not None, bool(self.token_logprob))
+                replay is not None, bool(self.token_logprob), bool(self.sample_logprob))
         eng = self._engines.get(ekey)
         if eng is not None and eng.fits_batch(lay):
             eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay, replay=rp)
@@ -725,6 +736,8 @@ class InfGenDecoder(nn.Module):
             if eng.token_logprob is not None:
                 o['pred_prob'] = logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'], cfg.hist_columns, steps)
                 o['rollout_logprob'] = eng.rollout_logprob()[j::copies]
+            if eng.sample_logprob is not None:
+                o['rollout_sample_logprob'] = eng.rollout_sample_logprob()[j::copies]
             res.append({**map_keys, **o, **passthrough})
         # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649), per graph
         removed = c[::copies, 2]

@@ -10,6 +10,8 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.attn_layer(x_dst (N, 128), pack, off, cnt, src, rhat?, x_src?)     -> (N, 128)
     torch.ops.infgen_hip.token_state_head(x (N, 128), tok_pack, st_pack, token_size, want_logits) -> token, state, logits
     torch.ops.infgen_hip.token_logprob(logits (N, n), token (N,))                           -> (N,) log_softmax(logits)[token]; 0 where token < 0
+    torch.ops.infgen_hip.heads_sample(x (N, 128), tok_pack, st_pack, token_size, k, uniform (N,), want_logits, want_logprob,
+                                      want_sample_logprob)                                  -> token, state, logits, token_logprob, sample_logprob
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -175,6 +177,46 @@ def token_logprob(logits: torch.Tensor, token: torch.Tensor) -> torch.Tensor:
 @token_logprob.register_fake
 def _(logits, token):
     return logits.new_empty(logits.shape[0], dtype=torch.float32)
+
+
+@torch.library.custom_op('infgen_hip::heads_sample', mutates_args=())
+def heads_sample(x: torch.Tensor, tok_pack: torch.Tensor, st_pack: torch.Tensor, token_size: int, k: int, uniform: torch.Tensor,
+                 want_logits: bool = False, want_logprob: bool = False, want_sample_logprob: bool = False
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """token_predict_head / state_predict_head with the motion token drawn by top-k sampling (agent_decoder.py:2162-2163, 2194-2195;
+    ``infgen_heads_sample``): the ``k`` (1..16) best logits of a row in (value descending, column ascending) order, inverse CDF
+    over their re-normalised probabilities with ``uniform[row]`` in [0, 1).  Returns next token (N,), next state (N,) and, each on
+    request (else an empty tensor), the (N, token_size) logits, the full-softmax log-probability of the sampled token (N,) and its
+    log-probability under the re-normalised top-k distribution (N,).  Where the library samples inside the split heads kernel
+    (``infgen_heads_sample_fused``) no logit reaches memory unless asked for; elsewhere the op holds the logits itself"""
+    if x.dim() != 2 or x.shape[1] != D or uniform.shape != x.shape[:1]:
+        raise ValueError('heads_sample takes x (N, 128) and uniform (N,)')
+    ops = _ops(x.device)
+    n = x.shape[0]
+    tok = torch.zeros(n, device=x.device, dtype=torch.int32)
+    st = torch.zeros(n, device=x.device, dtype=torch.int32)
+    o = _lib.Options()
+    _lib.check(ops.lib.infgen_get_effective_options(C.byref(o)), 'infgen_get_effective_options')
+    keep = want_logits or not ops.lib.infgen_heads_sample_fused(int(o.attn_mode), n, int(k))
+    lg = torch.empty(n if keep else 0, token_size, device=x.device)
+    lp = torch.zeros(n if want_logprob else 0, device=x.device)
+    slp = torch.zeros(n if want_sample_logprob else 0, device=x.device)
+    if n:
+        u = uniform.to(x.device, torch.float32).contiguous()
+        _lib.check(ops.lib.infgen_heads_sample(_lib.ptr(_f32(x)), n, _lib.ptr(_f32(tok_pack)), _lib.ptr(_f32(st_pack)),
+                                               int(token_size), int(k), _lib.ptr(u), _lib.ptr(lg) if keep else None, _lib.ptr(tok),
+                                               _lib.ptr(st), _lib.ptr(lp) if want_logprob else None,
+                                               _lib.ptr(slp) if want_sample_logprob else None, ops.stream), 'infgen_heads_sample')
+    return tok, st, (lg if want_logits else lg.new_empty(0, token_size)), lp, slp
+
+
+@heads_sample.register_fake
+def _(x, tok_pack, st_pack, token_size, k, uniform, want_logits=False, want_logprob=False, want_sample_logprob=False):
+    n = x.shape[0]
+    return (x.new_empty(n, dtype=torch.int32), x.new_empty(n, dtype=torch.int32),
+            x.new_empty(n if want_logits else 0, token_size, dtype=torch.float32),
+            x.new_empty(n if want_logprob else 0, dtype=torch.float32),
+            x.new_empty(n if want_sample_logprob else 0, dtype=torch.float32))
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
