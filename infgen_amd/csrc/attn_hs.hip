@@ -128,7 +128,7 @@ __global__ __launch_bounds__(512, 1) void k_attn_hs(AttnHArgs a) {
   if (P) {
     const float* hdr = Vt + VT_HDR;
     if (a.has_pos) {
-      // z-GEMM of head w (k_attn_h's, k_edge_fused's phase 3): B fragments straight from Z[row][w][:], |z| <= sqrt(127)
+      // z-GEMM of head w (k_attn_h's; edge_tile.cuh: z_gemm is the fused edge kernels' copy): B fragments straight from Z[row][w][:], |z| <= sqrt(127)
       const float* zrow = a.Z + (size_t)rowc * (H * D) + w * D;
       const unsigned short* Wl = post + (size_t)(w >> 1) * QUARTER + (size_t)((w & 1) * 4) * 2 * 512 + lane * 8;
       const float zs = 1024.0f, zinv = hdr[4] * (1.0f / 1024.0f);
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(512, 1) void k_attn_hs(AttnHArgs a) {
       if (a.nQ && valid) *reinterpret_cast<float4*>(a.nQ + (size_t)row * D + own) = make_float4(q[0], q[1], q[2], q[3]);
       if (need_u) {
         // u_w = q_w W'_kr,w (K = 16: v_mfma_f32_16x16x16_f16): the head's query is this wave's own C tile; per (row, head)
-        // power-of-two scale into the fp16 range (k_edge_fused's phase 1)
+        // power-of-two scale into the fp16 range (edge_tile.cuh: u_gemm is the fused edge kernels' copy, loads not interleaved)
         const unsigned short* Wk = pre + (size_t)(4 + (w >> 1)) * QUARTER + (size_t)((w & 1) * 8) * 2 * 256 + lane * 4;
         float m = fmaxf(fmaxf(fabsf(q[0]), fabsf(q[1])), fmaxf(fabsf(q[2]), fabsf(q[3])));
         m = fmaxf(m, __shfl_xor(m, 16, 64));

@@ -1,6 +1,7 @@
-// The per-destination edge-attention loop shared by k_edge_attn / k_edge_attn_wide (edge_kernels.hip) and
-// the fused tile kernel k_edge_fused (edge_fused.hip): one wavefront per destination row, single pass over the row's
-// incoming edges with an online (running-max) softmax; every global access is a coalesced 512-byte row.
+// The per-edge arithmetic of edge attention (EdgeAcc) and the per-destination loop of k_edge_attn / k_edge_attn_wide
+// (edge_kernels.hip): one wavefront per destination row, single pass over the row's incoming edges with an online (running-max)
+// softmax; every global access is a coalesced 512-byte row.  The fused tile kernels (k_edge_fused, k_edge_fused3, k_layers_p) drive
+// EdgeAcc through edge_tile.cuh, which holds the blocks around it (row loop over LDS tiles, u-GEMM / z-GEMM, row ranking).
 #pragma once
 #include "kernels.h"
 

@@ -21,6 +21,7 @@
 #include "tile.cuh"
 #include "split.cuh"
 #include "edge_attn.cuh"
+#include "edge_tile.cuh"
 
 namespace ig {
 
@@ -57,22 +58,14 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_edge_fused(EdgeFusedArgs a) {
   __shared__ int next_row;
   const int ngroups = a.groups ? *a.n_groups : (a.rows + 15) / 16;        // 16-row groups; a tile takes HALVES of them
   const int ntiles = (ngroups + HALVES - 1) / HALVES;
-  // XCD-aware tile order: consecutive workgroups go to consecutive XCDs (b % 8), each with its own L2.  With tps tiles per
-  // scene, workgroups b, b + 8, ..., b + 8 (tps - 1) - one XCD - take the tiles of ONE scene, so that the scene's K / V rows
-  // (agent set: read by every row of the scene) are fetched into one L2 instead of tps of them.
   if (HALVES == 1 && WAVES == 16 && warm_l2(a.warm, blockIdx.x, threadIdx.x, 64 * WAVES)) return;       // kernels.h: WarmArgs
-  int tile = blockIdx.x;
-  if (a.tiles_per_scene > 1) {
-    const int tps = a.tiles_per_scene, grp = 8 * tps;
-    const int bq = tile / grp, br = tile % grp;
-    tile = bq * grp + (br % 8) * tps + br / 8;
-  }
+  const int tile = xcd_tile(blockIdx.x, a.tiles_per_scene);      // (edge_tile.cuh: a scene's tiles share an L2)
   if (tile >= ntiles) return;
   EF_STAMP(0);
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int j = lane & 15, g = lane >> 4;
-  const int h = w & 7, half = w >> 3, hp = h >> 1, hh = h & 1;
+  const int h = w & 7, half = w >> 3;
   // first row of each half (-1: no such group)
   int r0h[HALVES];
 #pragma unroll
@@ -87,10 +80,8 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_edge_fused(EdgeFusedArgs a) {
   const bool valid = mat && r0 >= 0 && row < a.rows;
   const float* hdr = a.pack + AH_HDR;
   if (threadIdx.x == 0) next_row = 0;
-  // Longest rows first: the tile's rows are dealt to the waves in descending order of their edge counts (the agent set's lists
-  // run from a few to 60+ edges; dealt in index order a long row that comes last is the tile's tail while the other waves
-  // wait at the barrier).  Only the ORDER in which rows are picked changes - every row is still summed edge by edge by one wave,
-  // results are bitwise the same.  The last wave ranks the rows (a load of ROWS counts, ROWS compares) while phase 1 runs.
+  // Longest rows first (edge_tile.cuh: rank_by_count): the last wave ranks the rows (a load of ROWS counts, ROWS compares) while
+  // phase 1 runs.
   constexpr bool SORT_ROWS = !(HALVES == 1 && WAVES == 16);            // (one row per wave: nothing to order)
   __shared__ unsigned char row_order[ROWS];
   if (SORT_ROWS && w == WAVES - 1) {
@@ -98,12 +89,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_edge_fused(EdgeFusedArgs a) {
     const int rb = (HALVES > 1 && (rl >> 4)) ? r0h[HALVES - 1] : r0h[0];
     const int dr = rb + (rl & 15);
     const int cnt = (rb >= 0 && dr < a.rows) ? a.es.cnt[dr] : 0;
-    int rank = 0;
-#pragma unroll
-    for (int k = 0; k < ROWS; ++k) {
-      const int ck = __shfl(cnt, k, 64);
-      rank += (ck > cnt || (ck == cnt && k < rl)) ? 1 : 0;
-    }
+    const int rank = rank_by_count<false>(cnt, rl, ROWS);
     if (lane < ROWS) row_order[rank] = (unsigned char)rl;
   }
 
@@ -112,41 +98,10 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_edge_fused(EdgeFusedArgs a) {
   if (mat) {
     float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (valid) qv = *reinterpret_cast<const float4*>(a.Q + (size_t)row * D + DH * h + 4 * g);
-    const unsigned short* Wk = reinterpret_cast<const unsigned short*>(a.pack + AH_PRE) + (size_t)(4 + hp) * QUARTER +
-                               (size_t)(hh * 8) * 2 * 256 + lane * 4;
     v4h ah[8], al[8];
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) {
-      ah[ct] = *reinterpret_cast<const v4h*>(Wk + (ct * 2) * 256);
-      al[ct] = *reinterpret_cast<const v4h*>(Wk + (ct * 2 + 1) * 256);
-    }
+    load_wkr(reinterpret_cast<const unsigned short*>(a.pack + AH_PRE), h, lane, ah, al);
     *reinterpret_cast<float4*>(AG + jl * EF_LDA + DH * h + 4 * g) = qv;
-    // per (row, head) power-of-two scale into the fp16 range, as frags_scaled does per row
-    float m = fmaxf(fmaxf(fabsf(qv.x), fabsf(qv.y)), fmaxf(fabsf(qv.z), fabsf(qv.w)));
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    unsigned ebits = __float_as_uint(m) >> 23;
-    ebits = min(max(ebits, 15u), 253u);
-    const float sc = __uint_as_float((268u - ebits) << 23), inv = __uint_as_float((ebits - 14u) << 23);
-    u32x2 qh, ql;
-    {
-      unsigned hi, lo;
-      split_pair(qv.x * sc, qv.y * sc, hi, lo); qh[0] = hi; ql[0] = lo;
-      split_pair(qv.z * sc, qv.w * sc, hi, lo); qh[1] = hi; ql[1] = lo;
-    }
-    const v4h vqh = __builtin_bit_cast(v4h, qh), vql = __builtin_bit_cast(v4h, ql);
-    const float cq = inv * hdr[1];
-    f32x4 acc[8];
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], vqh, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], vql, acc[ct], 0, 0, 0);
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(al[ct], vqh, acc[ct], 0, 0, 0);
-    float* urow = UZ + jl * EF_LDU + h * D + 4 * g;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct)
-      *reinterpret_cast<float4*>(urow + 16 * ct) = make_float4(acc[ct][0] * cq, acc[ct][1] * cq, acc[ct][2] * cq, acc[ct][3] * cq);
+    u_gemm(f32x4{qv.x, qv.y, qv.z, qv.w}, ah, al, hdr, UZ + jl * EF_LDU + h * D + 4 * g, MaxShfl());
   }
   EF_STAMP(2);
   __syncthreads();
@@ -154,19 +109,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_edge_fused(EdgeFusedArgs a) {
 
   // ---- phase 2: edge loop, one wave per destination row
   {
-    const bool b3 = lane & 8;
     const bool kv_once = a.kv_once != 0;
-    const unsigned lo8 = 8u * (unsigned)lane;
-    auto ld8 = [&](const float* base, bool nt) {
-      return ea_ld(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + lo8), nt);
-    };
-    // packed 24-bit rhat row e (kernels.h): this lane's two columns = one dword of the 16-bit plane + one short of the 8-bit plane
-    auto ld_r24 = [&](size_t e) {
-      const char* rowp = reinterpret_cast<const char*>(a.es.rhat) + e * R24_ROW_BYTES;
-      const unsigned hi = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(rowp + 4 * lane));
-      const unsigned lo = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(rowp + R24_LO_PLANE + 2 * lane));
-      return pk2{__uint_as_float((hi << 16) | ((lo & 0xffu) << 8)), __uint_as_float((hi & 0xffff0000u) | (lo & 0xff00u))};
-    };
     // rows are dealt to the waves through an LDS counter (the agent set's lists vary in length)
     auto take_row = [&]() {
       int r = 0;
@@ -185,88 +128,27 @@ __global__ __launch_bounds__(64 * WAVES, 4) void k_edge_fused(EdgeFusedArgs a) {
       acc.q = *reinterpret_cast<const float2*>(AG + rl * EF_LDA + 2 * lane);
       acc.load_u(uz, lane);
       acc.reset();
-      for (int c0 = 0; c0 < E; c0 += 64) {
-        const int mc = min(64, E - c0);
-        if (c0 > 0) sv = a.es.src[e_base + c0 + min(lane, mc - 1)];        // lists beyond 64 edges: next chunk of indices
-        // G edges per trip: all their K / V / rhat rows are requested at the top of the trip (index clamped at the end of the
-        // list: no branch around the loads, the waits are counted ones) and consumed in turn; nothing is carried in registers
-        // from trip to trip (edge_attn.cuh explains why), the trip's fill latency is hidden by the SIMD's other waves.  (A
-        // tail trip of exactly the remaining length was tried: same time on lists of any raggedness - the loop is bound by
-        // its gathers, DESIGN.md section 9 - and ten spilled registers.)
-        for (int i0 = 0; i0 < mc; i0 += G) {
-          pk2 kb[G], vb[G], rb[G];
-#pragma unroll
-          for (int s = 0; s < G; ++s) {
-            const int ic = min(i0 + s, mc - 1);
-            const int sj = __builtin_amdgcn_readlane(sv, ic);
-            kb[s] = ld8(a.Ksrc + (size_t)sj * D, kv_once);
-            vb[s] = ld8(a.Vsrc + (size_t)sj * D, kv_once);
-            if constexpr (R24) rb[s] = ld_r24((size_t)(e_base + c0 + ic));
-            else rb[s] = ld8(a.es.rhat + (size_t)(e_base + c0 + ic) * D, true);
-          }
-#pragma unroll
-          for (int s = 0; s < G; ++s) acc.step(kb[s], vb[s], rb[s], i0 + s < mc, b3);
-        }
-      }
-      const float inv = 1.0f / (acc.lsum + 1e-16f);
-      *reinterpret_cast<float2*>(AG + rl * EF_LDA + 2 * lane) = make_float2(acc.ag[0] * inv, acc.ag[1] * inv);
-#pragma unroll
-      for (int hd = 0; hd < H; ++hd) {
-        const float ih = readlane_f(inv, 8 * hd);
-        *reinterpret_cast<float2*>(uz + hd * D + 2 * lane) = make_float2(acc.zz[hd][0] * ih, acc.zz[hd][1] * ih);
-      }
-      if ((lane & 7) == 0) SG[rl * H + (lane >> 3)] = acc.lsum * inv;
+      edge_row_loop<G, R24>(acc, a.es, a.Ksrc, a.Vsrc, kv_once, E, e_base, sv, lane);
+      edge_row_finish(acc, uz, AG + rl * EF_LDA, SG + rl * H, lane);
     }
   }
   EF_STAMP(4);
   // (phase 3's weight fragments are requested BEFORE the barrier: a wave that has finished its rows waits there anyway, and the
   // fragments' L2 latency runs under that wait)
   v8h p3h[4], p3l[4];
-  if (mat) {
-    const unsigned short* Wv = reinterpret_cast<const unsigned short*>(a.pack + AH_POST) + (size_t)hp * QUARTER +
-                               (size_t)(hh * 4) * 2 * 512 + lane * 8;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      p3h[s] = *reinterpret_cast<const v8h*>(Wv + (s * 2) * 512);
-      p3l[s] = *reinterpret_cast<const v8h*>(Wv + (s * 2 + 1) * 512);
-    }
-  }
+  if (mat) load_wvr(reinterpret_cast<const unsigned short*>(a.pack + AH_POST), h, lane, p3h, p3l);
   EF_STAMP(5);
   __syncthreads();
   EF_STAMP(6);
 
   // ---- phase 3: agg' = agg + W'_vr,h z_h + b'_h sigma_h  (k_attn_h's z-GEMM: |z| <= sqrt(127), static prescale 1024)
   if (mat) {
-    const float* zrow = UZ + jl * EF_LDU + h * D + 8 * g;
-    v8h (&ah)[4] = p3h;
-    v8h (&al)[4] = p3l;
-    const float zs = 1024.0f, zinv = hdr[4] * (1.0f / 1024.0f);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float4 z0 = *reinterpret_cast<const float4*>(zrow + 32 * s);
-      const float4 z1 = *reinterpret_cast<const float4*>(zrow + 32 * s + 4);
-      u32x4 bh, bl;
-      unsigned hi, lo;
-      split_pair(z0.x * zs, z0.y * zs, hi, lo); bh[0] = hi; bl[0] = lo;
-      split_pair(z0.z * zs, z0.w * zs, hi, lo); bh[1] = hi; bl[1] = lo;
-      split_pair(z1.x * zs, z1.y * zs, hi, lo); bh[2] = hi; bl[2] = lo;
-      split_pair(z1.z * zs, z1.w * zs, hi, lo); bh[3] = hi; bl[3] = lo;
-      const v8h vbh = __builtin_bit_cast(v8h, bh), vbl = __builtin_bit_cast(v8h, bl);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[s], vbh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[s], vbl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[s], vbh, acc, 0, 0, 0);
-    }
+    const f32x4 wz = z_gemm(UZ + jl * EF_LDU + h * D + 8 * g, p3h, p3l, hdr[4]);
     if (valid) {
       const float sg = SG[jl * H + h];
-      const float4 bvr = *reinterpret_cast<const float4*>(a.pack + AL_BVR + DH * h + 4 * g);
-      const float4 ag = *reinterpret_cast<const float4*>(AG + jl * EF_LDA + DH * h + 4 * g);
-      float4 o;
-      o.x = ag.x + (acc[0] * zinv + bvr.x * sg);
-      o.y = ag.y + (acc[1] * zinv + bvr.y * sg);
-      o.z = ag.z + (acc[2] * zinv + bvr.z * sg);
-      o.w = ag.w + (acc[3] * zinv + bvr.w * sg);
-      *reinterpret_cast<float4*>(a.AGG + (size_t)row * D + DH * h + 4 * g) = o;
+      const f32x4 bvr = lds4(a.pack + AL_BVR + DH * h + 4 * g);
+      const f32x4 o = agg_out(lds4(AG + jl * EF_LDA + DH * h + 4 * g), wz, bvr, sg);
+      *reinterpret_cast<float4*>(a.AGG + (size_t)row * D + DH * h + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
     }
   }
   EF_STAMP(7);

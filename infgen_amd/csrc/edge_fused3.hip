@@ -16,7 +16,8 @@
 // wave's ring is the U / Z slot of the ROW IT IS PROCESSING (4112 B = 8 rows of 512 B) - the row's u tile is in registers by then
 // and its z is written into the slot when the row is done.  Rows are dealt statically: the tile's rows sorted by edge count,
 // wave w takes the (w + 1)-th longest and then the (w + 1)-th shortest.  K / V rows keep the (2 l, 2 l + 1) mapping (lane l's two
-// columns belong to head l >> 3).  Phases 1 (u = q W'_kr) and 3 (agg' = agg + W'_vr z + b' sigma) are k_edge_fused's.
+// columns belong to head l >> 3).  Phases 1 (u = q W'_kr) and 3 (agg' = agg + W'_vr z + b' sigma), the ranking and the tile order
+// are k_edge_fused's: the shared blocks of edge_tile.cuh.
 //
 // 512 threads = 8 waves = one 16-row group, 75 KB of LDS: two workgroups per CU, like k_edge_fused<6, *, 1, 8>.
 #include "kernels.h"
@@ -24,6 +25,7 @@
 #include "tile.cuh"
 #include "split.cuh"
 #include "edge_attn.cuh"
+#include "edge_tile.cuh"
 
 namespace ig {
 
@@ -39,17 +41,12 @@ __global__ __launch_bounds__(512, 4) void k_edge_fused3(EdgeFusedArgs a) {
   __shared__ __attribute__((aligned(16))) float AG[16 * E3_LDA];     // q tile (phase 1 -> 2), then agg (phase 2 -> 3)
   __shared__ float SG[16 * H];
   const int ngroups = a.groups ? *a.n_groups : (a.rows + 15) / 16;
-  int tile = blockIdx.x;
-  if (a.tiles_per_scene > 1) {              // XCD-aware tile order (edge_fused.hip): a scene's tiles share an L2
-    const int tps = a.tiles_per_scene, grp = 8 * tps;
-    const int bq = tile / grp, br = tile % grp;
-    tile = bq * grp + (br % 8) * tps + br / 8;
-  }
+  const int tile = xcd_tile(blockIdx.x, a.tiles_per_scene);      // (edge_tile.cuh: a scene's tiles share an L2)
   if (tile >= ngroups) return;
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int j = lane & 15, g = lane >> 4;
-  const int h = w, hp = h >> 1, hh = h & 1;
+  const int h = w;
   const int r0 = 16 * (a.groups ? a.groups[tile] : tile);
   const int row = r0 + j;
   const bool valid = row < a.rows;
@@ -65,15 +62,7 @@ __global__ __launch_bounds__(512, 4) void k_edge_fused3(EdgeFusedArgs a) {
   float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);
   if (valid) qv = *reinterpret_cast<const float4*>(a.Q + (size_t)row * D + DH * h + 4 * g);
   v4h ah[8], al[8];
-  {
-    const unsigned short* Wk = reinterpret_cast<const unsigned short*>(a.pack + AH_PRE) + (size_t)(4 + hp) * QUARTER +
-                               (size_t)(hh * 8) * 2 * 256 + lane * 4;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) {
-      ah[ct] = *reinterpret_cast<const v4h*>(Wk + (ct * 2) * 256);
-      al[ct] = *reinterpret_cast<const v4h*>(Wk + (ct * 2 + 1) * 256);
-    }
-  }
+  load_wkr(reinterpret_cast<const unsigned short*>(a.pack + AH_PRE), h, lane, ah, al);
   // Every wave ranks the tile's rows by edge count itself (16 counts, 16 compares: the same two loads in all eight waves) and takes
   // the (w + 1)-th longest and the (w + 1)-th shortest row; the first 64 source indices of both rows are requested HERE, in front of
   // phase 1's arithmetic: a workgroup's life is a chain of dependent memory round trips (count -> indices -> K / V rows, for two rows),
@@ -83,12 +72,7 @@ __global__ __launch_bounds__(512, 4) void k_edge_fused3(EdgeFusedArgs a) {
   int E2[2], eb2[2], sv2[2], rl2[2];
   {
     const int rl = bk_rl, cnt = bk_cnt, off = bk_off;
-    int rank = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int ck = __builtin_amdgcn_readlane(cnt, k);          // (lanes 0..15 hold the 16 counts: no LDS round trip like __shfl)
-      rank += (ck > cnt || (ck == cnt && k < rl)) ? 1 : 0;
-    }
+    const int rank = rank_by_count<true>(cnt, rl, 16);      // (lanes 0..15 hold the 16 counts: v_readlane, no LDS round trip like __shfl)
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const int want = p ? 15 - w : w;
@@ -100,44 +84,14 @@ __global__ __launch_bounds__(512, 4) void k_edge_fused3(EdgeFusedArgs a) {
       sv2[p] = E2[p] > 0 ? a.es.src[eb2[p] + min(lane, min(E2[p], 64) - 1)] : 0;
     }
   }
-  {
-    *reinterpret_cast<float4*>(AG + j * E3_LDA + DH * h + 4 * g) = qv;
-    float m = fmaxf(fmaxf(fabsf(qv.x), fabsf(qv.y)), fmaxf(fabsf(qv.z), fabsf(qv.w)));
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    unsigned ebits = __float_as_uint(m) >> 23;
-    ebits = min(max(ebits, 15u), 253u);
-    const float sc = __uint_as_float((268u - ebits) << 23), inv = __uint_as_float((ebits - 14u) << 23);
-    u32x2 qh, ql;
-    {
-      unsigned hi, lo;
-      split_pair(qv.x * sc, qv.y * sc, hi, lo); qh[0] = hi; ql[0] = lo;
-      split_pair(qv.z * sc, qv.w * sc, hi, lo); qh[1] = hi; ql[1] = lo;
-    }
-    const v4h vqh = __builtin_bit_cast(v4h, qh), vql = __builtin_bit_cast(v4h, ql);
-    const float cq = inv * hdr[1];
-    f32x4 acc[8];
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], vqh, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], vql, acc[ct], 0, 0, 0);
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(al[ct], vqh, acc[ct], 0, 0, 0);
-    float* urow = UZ + j * E3_LDU + h * D + 4 * g;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct)
-      *reinterpret_cast<float4*>(urow + 16 * ct) = make_float4(acc[ct][0] * cq, acc[ct][1] * cq, acc[ct][2] * cq, acc[ct][3] * cq);
-  }
+  *reinterpret_cast<float4*>(AG + j * E3_LDA + DH * h + 4 * g) = qv;
+  u_gemm(f32x4{qv.x, qv.y, qv.z, qv.w}, ah, al, hdr, UZ + j * E3_LDU + h * D + 4 * g, MaxShfl());
   __syncthreads();
 
   // ---- phase 2: the edge loop; lane = (head eh, slice ei): columns 32 k + 4 ei .. + 3 (k = 0..3) of head eh
   {
     const int eh = lane >> 3, ei = lane & 7;
     const bool kv_once = a.kv_once != 0;
-    const unsigned lo8 = 8u * (unsigned)lane;
-    auto ld8 = [&](const float* base, bool nt) {
-      return ea_ld(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + lo8), nt);
-    };
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
       const int rl = pass ? rl2[1] : rl2[0];
@@ -189,8 +143,8 @@ __global__ __launch_bounds__(512, 4) void k_edge_fused3(EdgeFusedArgs a) {
           for (int s = 0; s < G; ++s) {
             const int ic = min(i0 + s, mc - 1);
             const int sj = __builtin_amdgcn_readlane(sv, ic);
-            kb[s] = ld8(a.Ksrc + (size_t)sj * D, kv_once);
-            vb[s] = ld8(a.Vsrc + (size_t)sj * D, kv_once);
+            kb[s] = ld8(a.Ksrc + (size_t)sj * D, kv_once, lane);
+            vb[s] = ld8(a.Vsrc + (size_t)sj * D, kv_once, lane);
           }
           // the 2 G loads above are the only vector-memory operations younger than the LDS-DMA pieces: at most 2 G outstanding
           // means every piece has landed (vmcnt retires in order; the compiler barrier keeps the loads in front of the wait)
@@ -256,47 +210,17 @@ __global__ __launch_bounds__(512, 4) void k_edge_fused3(EdgeFusedArgs a) {
   }
   // (phase 3's weight fragments are requested BEFORE the barrier: their L2 latency runs under the wait for the other waves)
   v8h p3h[4], p3l[4];
-  {
-    const unsigned short* Wv = reinterpret_cast<const unsigned short*>(a.pack + AH_POST) + (size_t)hp * QUARTER +
-                               (size_t)(hh * 4) * 2 * 512 + lane * 8;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      p3h[s] = *reinterpret_cast<const v8h*>(Wv + (s * 2) * 512);
-      p3l[s] = *reinterpret_cast<const v8h*>(Wv + (s * 2 + 1) * 512);
-    }
-  }
+  load_wvr(reinterpret_cast<const unsigned short*>(a.pack + AH_POST), h, lane, p3h, p3l);
   __syncthreads();
 
   // ---- phase 3: agg' = agg + W'_vr,h z_h + b'_h sigma_h  (k_attn_h's z-GEMM: |z| <= sqrt(127), static prescale 1024)
   {
-    const float* zrow = UZ + j * E3_LDU + h * D + 8 * g;
-    const float zs = 1024.0f, zinv = hdr[4] * (1.0f / 1024.0f);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float4 z0 = *reinterpret_cast<const float4*>(zrow + 32 * s);
-      const float4 z1 = *reinterpret_cast<const float4*>(zrow + 32 * s + 4);
-      u32x4 bh, bl;
-      unsigned hi, lo;
-      split_pair(z0.x * zs, z0.y * zs, hi, lo); bh[0] = hi; bl[0] = lo;
-      split_pair(z0.z * zs, z0.w * zs, hi, lo); bh[1] = hi; bl[1] = lo;
-      split_pair(z1.x * zs, z1.y * zs, hi, lo); bh[2] = hi; bl[2] = lo;
-      split_pair(z1.z * zs, z1.w * zs, hi, lo); bh[3] = hi; bl[3] = lo;
-      const v8h vbh = __builtin_bit_cast(v8h, bh), vbl = __builtin_bit_cast(v8h, bl);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p3h[s], vbh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p3h[s], vbl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p3l[s], vbh, acc, 0, 0, 0);
-    }
+    const f32x4 wz = z_gemm(UZ + j * E3_LDU + h * D + 8 * g, p3h, p3l, hdr[4]);
     if (valid) {
       const float sg = SG[j * H + h];
-      const float4 bvr = *reinterpret_cast<const float4*>(a.pack + AL_BVR + DH * h + 4 * g);
-      const float4 ag = *reinterpret_cast<const float4*>(AG + j * E3_LDA + DH * h + 4 * g);
-      float4 o;
-      o.x = ag.x + (acc[0] * zinv + bvr.x * sg);
-      o.y = ag.y + (acc[1] * zinv + bvr.y * sg);
-      o.z = ag.z + (acc[2] * zinv + bvr.z * sg);
-      o.w = ag.w + (acc[3] * zinv + bvr.w * sg);
-      *reinterpret_cast<float4*>(a.AGG + (size_t)row * D + DH * h + 4 * g) = o;
+      const f32x4 bvr = lds4(a.pack + AL_BVR + DH * h + 4 * g);
+      const f32x4 o = agg_out(lds4(AG + j * E3_LDA + DH * h + 4 * g), wz, bvr, sg);
+      *reinterpret_cast<float4*>(a.AGG + (size_t)row * D + DH * h + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
     }
   }
 }

@@ -13,8 +13,9 @@
 //     layout, layout.h AH_*: slots 0..3 of k-step s are tile 2 s, slots 4..7 tile 2 s + 1), each tile's accumulator
 //     multiplied by its own inverse scale - same three-term split (2^-21 per product), no row-wide maximum to exchange;
 //   * LayerNorm statistics are merged from per-tile (mean, M2) pairs (Chan's update: as accurate as two passes);
-//   * the edge loop (edge_attn.cuh: EdgeAcc, k_edge_fused's phase 2) takes q and the absorbed query u from LDS where the
-//     previous sublayer's node part left them, two rows per wave; phase 3 (W'_vr z) leaves agg in the owner's registers;
+//   * the edge loop (edge_tile.cuh: edge_row_loop over edge_attn.cuh's EdgeAcc, k_edge_fused's phase 2) takes q and the absorbed
+//     query u from LDS where the previous sublayer's node part left them, two rows per wave; phase 3 (edge_tile.cuh: z_gemm, W'_vr z)
+//     leaves agg in the owner's registers;
 //   * temporal and map sublayers need nothing from other rows of the step; the agent sublayer reads the K / V rows of its
 //     whole scene, so the A_cap / 16 workgroups of a scene meet once per layer at a counter in global memory (release /
 //     acquire at agent scope; all workgroups are co-resident: one per CU, grid <= 256).  K / V of the agent set are double
@@ -30,6 +31,7 @@
 #include "split.cuh"
 #include "attn_h.cuh"
 #include "edge_attn.cuh"
+#include "edge_tile.cuh"
 
 #ifndef IG_LP_NOLOAD
 #define IG_LP_NOLOAD 0           // timing experiments (wrong results): 1 no weight-fragment loads, IG_LP_NOMFMA no products in the
@@ -313,12 +315,7 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
     const int rl = lane & 15;
     const int off = el_off;
     const int cnt = rl < R ? el_cnt : -1;                        // (shadow rows rank last: ranks 0 .. R - 1 are the real rows)
-    int rank = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      const int ck = __shfl(cnt, k, 64);
-      rank += (ck > cnt || (ck == cnt && k < rl)) ? 1 : 0;
-    }
+    const int rank = rank_by_count<false>(cnt, rl, 16);
 #pragma unroll
     for (int i = 0; i < (R == 16 ? 2 : 1); ++i) {
       // R = 16: rows of rank w and 15 - w; R = 8: rank w only; R = 4: rank w >> 1, and the row's list is halved between waves 2 q
@@ -375,44 +372,17 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
       }
     }
     STAMP(19);
-    // u_w = q_w W'_kr,w (attn_hs.hip / edge_fused.hip phase 1): K = 16, the head's query is this wave's own tile
+    // u_w = q_w W'_kr,w (edge_tile.cuh: u_gemm, the phase 1 of k_edge_fused): K = 16, the head's query is this wave's own tile
     {
-      const unsigned short* Wk = pre + (size_t)(4 + (w >> 1)) * QUARTER + (size_t)((w & 1) * 8) * 2 * 256 + lane * 4;
       v4h ah[8], al[8];
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) {
 #if IG_LP_NOAUX
-        asm volatile("" : "=v"(ah[ct]), "=v"(al[ct]));
+#pragma unroll
+      for (int ct = 0; ct < 8; ++ct) asm volatile("" : "=v"(ah[ct]), "=v"(al[ct]));
 #else
-        ah[ct] = *reinterpret_cast<const v4h*>(Wk + (ct * 2) * 256);
-        al[ct] = *reinterpret_cast<const v4h*>(Wk + (ct * 2 + 1) * 256);
+      load_wkr(pre, w, lane, ah, al);
 #endif
-      }
       *reinterpret_cast<float4*>(AG + j * LP_LDA + own) = make_float4(q[0], q[1], q[2], q[3]);
-      float m = fmaxf(fmaxf(fabsf(q[0]), fabsf(q[1])), fmaxf(fabsf(q[2]), fabsf(q[3])));
-      m = xor_lanes_max(m);
-      unsigned ebits = __float_as_uint(m) >> 23;
-      ebits = min(max(ebits, 15u), 253u);
-      const float sc = __uint_as_float((268u - ebits) << 23), inv = __uint_as_float((ebits - 14u) << 23);
-      u32x2 qh, ql;
-      {
-        unsigned hi, lo;
-        split_pair(q[0] * sc, q[1] * sc, hi, lo); qh[0] = hi; ql[0] = lo;
-        split_pair(q[2] * sc, q[3] * sc, hi, lo); qh[1] = hi; ql[1] = lo;
-      }
-      const v4h vqh = __builtin_bit_cast(v4h, qh), vql = __builtin_bit_cast(v4h, ql);
-      const float cq = inv * hdr[1];
-      f32x4 acc[8];
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], vqh, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(ah[ct], vql, acc[ct], 0, 0, 0);
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x16f16(al[ct], vqh, acc[ct], 0, 0, 0);
-      float* urow = UZ + j * LP_LDU + w * D + 4 * rg;
-#pragma unroll
-      for (int ct = 0; ct < 8; ++ct)
-        *reinterpret_cast<float4*>(urow + 16 * ct) = make_float4(acc[ct][0] * cq, acc[ct][1] * cq, acc[ct][2] * cq, acc[ct][3] * cq);
+      u_gemm(q, ah, al, hdr, UZ + j * LP_LDU + w * D + 4 * rg, MaxSwap());
     }
   };
 
@@ -430,19 +400,8 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
     wg_barrier();                                   // q / u of the previous node part
     STAMP(1);
 
-    // ---- edge loop (k_edge_fused's phase 2): this wave's two rows, lists requested a sublayer ago
+    // ---- edge loop (edge_tile.cuh: edge_row_loop, k_edge_fused's phase 2): this wave's two rows, lists requested a sublayer ago
     {
-      const bool b3 = lane & 8;
-      const unsigned lo8 = 8u * (unsigned)lane;
-      auto ld8 = [&](const float* base, bool nt) {
-        return ea_ld(reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + lo8), nt);
-      };
-      auto ld_r24 = [&](size_t e) {
-        const char* rowp = reinterpret_cast<const char*>(es.rhat) + e * R24_ROW_BYTES;
-        const unsigned hi = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(rowp + 4 * lane));
-        const unsigned lo = __builtin_nontemporal_load(reinterpret_cast<const unsigned short*>(rowp + R24_LO_PLANE + 2 * lane));
-        return pk2{__uint_as_float((hi << 16) | ((lo & 0xffu) << 8)), __uint_as_float((hi & 0xffff0000u) | (lo & 0xff00u))};
-      };
       for (int ri = 0; ri < (R == 16 ? 2 : 1); ++ri) {
         const int rl = ri == 0 ? eR[0] : eR[1];
         const int E = IG_LP_NOEDGE ? 0 : (ri == 0 ? eE[0] : eE[1]);
@@ -453,24 +412,7 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
         acc.q = *reinterpret_cast<const float2*>(AG + rl * LP_LDA + 2 * lane);
         acc.load_u(uz, lane);
         acc.reset();
-        for (int c0 = 0; c0 < E; c0 += 64) {
-          const int mc = min(64, E - c0);
-          if (c0 > 0) sv = es.src[e_base + c0 + min(lane, mc - 1)];
-          for (int i0 = 0; i0 < mc; i0 += LP_G) {
-            pk2 kb[LP_G], vb[LP_G], rb[LP_G];
-#pragma unroll
-            for (int s = 0; s < LP_G; ++s) {
-              const int ic = min(i0 + s, mc - 1);
-              const int sj = __builtin_amdgcn_readlane(sv, ic);
-              kb[s] = ld8(Ksrc + (size_t)sj * D, kv_once);
-              vb[s] = ld8(Vsrc + (size_t)sj * D, kv_once);
-              if constexpr (R24) rb[s] = ld_r24((size_t)(e_base + c0 + ic));
-              else rb[s] = ld8(es.rhat + (size_t)(e_base + c0 + ic) * D, true);
-            }
-#pragma unroll
-            for (int s = 0; s < LP_G; ++s) acc.step(kb[s], vb[s], rb[s], i0 + s < mc, b3);
-          }
-        }
+        edge_row_loop<LP_G, R24>(acc, es, Ksrc, Vsrc, kv_once, E, e_base, sv, lane);
         if constexpr (R == 4) {
           // two waves share the row: the odd one parks its un-normalised state in spare rows of the U / Z tile (rows 4 .. 11 are
           // unused with four rows per workgroup), the even one merges it into its own (running maxima may differ) and finalises
@@ -498,14 +440,7 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
             acc.zz[hd] = pk2{fmaf(z1.x, h1, acc.zz[hd][0] * h0), fmaf(z1.y, h1, acc.zz[hd][1] * h0)};
           }
         }
-        const float inv = 1.0f / (acc.lsum + 1e-16f);
-        *reinterpret_cast<float2*>(AG + rl * LP_LDA + 2 * lane) = make_float2(acc.ag[0] * inv, acc.ag[1] * inv);
-#pragma unroll
-        for (int hd = 0; hd < H; ++hd) {
-          const float ih = readlane_f(inv, 8 * hd);
-          *reinterpret_cast<float2*>(uz + hd * D + 2 * lane) = make_float2(acc.zz[hd][0] * ih, acc.zz[hd][1] * ih);
-        }
-        if ((lane & 7) == 0) SG[rl * H + (lane >> 3)] = acc.lsum * inv;
+        edge_row_finish(acc, uz, AG + rl * LP_LDA, SG + rl * H, lane);
       }
     }
     STAMP(2);
@@ -513,18 +448,12 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
     *reinterpret_cast<float4*>(Vt + to1) = tv1;
     edge_lists_request(es_next);                    // (the next sublayer's lists: three round trips under this node part)
     v8h p3h[4], p3l[4];                             // phase 3's W'vr fragments land under the barrier wait
-    {
-      const unsigned short* Wv = post + (size_t)(w >> 1) * QUARTER + (size_t)((w & 1) * 4) * 2 * 512 + lane * 8;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
 #if IG_LP_NOAUX
-        asm volatile("" : "=v"(p3h[s]), "=v"(p3l[s]));
+#pragma unroll
+    for (int s = 0; s < 4; ++s) asm volatile("" : "=v"(p3h[s]), "=v"(p3l[s]));
 #else
-        p3h[s] = *reinterpret_cast<const v8h*>(Wv + (s * 2) * 512);
-        p3l[s] = *reinterpret_cast<const v8h*>(Wv + (s * 2 + 1) * 512);
+    load_wvr(post, w, lane, p3h, p3l);
 #endif
-      }
-    }
     wg_barrier();
     STAMP(3);
 
@@ -532,29 +461,10 @@ __global__ __launch_bounds__(512, 1) void k_layers_p(LayersPArgs a) {
     f32x4 ago;
     {
       const float* hdr = Vt + VT_HDR;
-      const float* zrow = UZ + j * LP_LDU + w * D + 8 * rg;
-      const float zs = 1024.0f, zinv = hdr[4] * (1.0f / 1024.0f);
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const float4 z0 = *reinterpret_cast<const float4*>(zrow + 32 * s);
-        const float4 z1 = *reinterpret_cast<const float4*>(zrow + 32 * s + 4);
-        u32x4 bh, bl;
-        unsigned hi, lo;
-        split_pair(z0.x * zs, z0.y * zs, hi, lo); bh[0] = hi; bl[0] = lo;
-        split_pair(z0.z * zs, z0.w * zs, hi, lo); bh[1] = hi; bl[1] = lo;
-        split_pair(z1.x * zs, z1.y * zs, hi, lo); bh[2] = hi; bl[2] = lo;
-        split_pair(z1.z * zs, z1.w * zs, hi, lo); bh[3] = hi; bl[3] = lo;
-        const v8h vbh = __builtin_bit_cast(v8h, bh), vbl = __builtin_bit_cast(v8h, bl);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p3h[s], vbh, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p3h[s], vbl, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(p3l[s], vbh, acc, 0, 0, 0);
-      }
+      const f32x4 wz = z_gemm(UZ + j * LP_LDU + w * D + 8 * rg, p3h, p3l, hdr[4]);
       const float sg = SG[j * H + w];
       const f32x4 bvr = lds4(Vt + VT_BVR + own);
-      const f32x4 ag = lds4(AG + j * LP_LDA + own);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ago[r] = ag[r] + (acc[r] * zinv + bvr[r] * sg);
+      ago = agg_out(lds4(AG + j * LP_LDA + own), wz, bvr, sg);
     }
 
     // ---- post part (layers.py:94-99, 74-75, 110-112): gate / self / update, out projection + post-norm, FFN + post-norm

@@ -454,3 +454,45 @@ def test_edge_fused3_equals_the_vector_loop(env, n_dst, n_src, max_deg):
         err = float((a1 - ref).abs().max())
         assert err <= 2e-5 * scale, (qscale, err, scale)
         assert torch.equal(a1[0], ref[0]) and torch.equal(a1[7], ref[7])       # rows without edges
+
+
+@pytest.mark.parametrize('n_dst,n_src,max_deg', [(45, 150, 130), (16, 40, 9)])
+def test_edge_fused_instantiations_give_the_same_bits(env, n_dst, n_src, max_deg):
+    """every k_edge_fused instantiation an option reaches (InfgenOptions.edge_loop = 6: the one-group 16-wave kernel at this size;
+    4 and 8: the two-group one with G = 4 / 8 edges per trip) computes the same bits on fp32 rhat rows: each row is summed edge by
+    edge by one wave in list order, whatever G and however the rows are dealt - the kernels share edge_tile.cuh's row loop.  45
+    rows = 3 groups: the two-group kernel runs a tile with an absent half and a partial last group; lists of up to 130 edges: a
+    second index chunk and trips with dead slots for every G; 16 rows / 9 edges: lists shorter than one trip.  And against
+    k_edge_fused3 (edge_kernel = 2) within the fp32 summation-order bound of test_edge_fused3_equals_the_vector_loop, so that
+    four identical wrong answers do not pass.  (Packed 24-bit rows, R24 = true: tests/test_rollout_gpu.py::
+    test_packed_rhat_rows_match_fp32_rows only.)"""
+    import ctypes as C
+    from infgen_amd import _lib
+    rng = np.random.default_rng(n_dst + max_deg)
+    dev, lib = env['dev'], env['lib']
+    pack = _dev(env['packing'].pack_attention_layer(env['sd'], 'agent_encoder.a2a_attn_layers.1'), dev)
+    off, cnt, src, dst = _random_graph(rng, n_dst, n_src, max_deg, empty_rows=(0, 7, n_dst - 1))
+    E = len(src)
+    r = torch.nn.functional.layer_norm(torch.from_numpy(rng.standard_normal((E, 128)).astype(np.float32) *
+                                                        rng.uniform(0.2, 5.0, (E, 1)).astype(np.float32)), (128,)).to(dev).contiguous()
+    q = _dev(rng.standard_normal((n_dst, 128)), dev)
+    k = _dev(rng.standard_normal((n_src, 128)), dev)
+    v = _dev(rng.standard_normal((n_src, 128)) * 3.0, dev)
+    offd, cntd, srcd = (torch.from_numpy(a).to(dev) for a in (off, cnt, src))
+    o = _lib.Options()
+    _lib.check(lib.infgen_get_options(C.byref(o)))
+    outs = []
+    for kern, loop in ((0, 6), (0, 4), (0, 8), (0, 8), (2, 6)):
+        o.edge_kernel, o.edge_loop, o.use = kern, loop, 0
+        agg = torch.full((n_dst, 128), float('nan'), device=dev)
+        with _lib.thread_options(o):
+            env['ops'].edge_attn(n_dst, q, pack, k, v, offd, cntd, srcd, r, agg, None, None, wide='fused')
+        outs.append(agg)
+    torch.cuda.synchronize()
+    ref = outs.pop()
+    for a_ in outs[1:]:
+        assert torch.equal(a_.view(torch.int32), outs[0].view(torch.int32))
+    scale = float(ref.abs().max())
+    for a_ in outs:
+        err = float((a_ - ref).abs().max())
+        assert err <= 2e-5 * scale, (err, scale)
