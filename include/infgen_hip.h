@@ -123,6 +123,23 @@ typedef struct InfgenOptions {
   const int* row_groups; const int* n_row_groups;   /* optional list of the 16-row groups that hold agents (infgen_set_row_groups) */
 } InfgenOptions;
 
+/* temperature and nucleus (top-p) truncation of the top-k samplers (infgen_sample_topk_ex, infgen_heads_sample_ex,
+ * infgen_insert_decide_topk_ex; InfgenRollout.sample_* / InfgenInsertion.insert_*).  With v[0..k-1] a row's k best logits in the
+ * samplers' total order (value descending, column ascending), it = 1 / T in fp32 and u01 the caller's uniform:
+ *   1. p[j] = expf((v[j] - v[0]) * it), cdf[j] the running sum in j order, S_k = cdf[k-1]
+ *   2. the nucleus size m: the smallest m with cdf[m-1] >= top_p * S_k - the nucleus of the re-normalised top-k distribution (top-k
+ *      first, then top-p); always m >= 1; top_p >= 1: m = k, no comparison made
+ *   3. sum = cdf[m-1], u = u01 * sum, pick = the first j < m with u < cdf[j], else m - 1
+ *   4. sample_logprob = (v[pick] - v[0]) * it - logf(sum); token_logprob stays the model's own full softmax at temperature 1
+ *   5. a row with T == 0 is greedy: pick = 0, sample_logprob = 0 (its uniform is still read)
+ * temperature: finite, >= 0 and no denormal (1 / T must stay finite); top_p in (0, 1]; 0 means "unset" and equals 1 for both (a zero-filled struct is the plain top-k sampler,
+ * bit for bit); anything else is refused.  temperature_row (optional, [rows], entries >= 0) wins over the scalar, and there 0 means
+ * greedy (as does any entry below the smallest normal float); it is device memory and not checked by the library.  k <= 1: the arg-max, the parameters are ignored. */
+typedef struct InfgenSampling {
+  float temperature; float top_p;
+  const float* temperature_row;
+} InfgenSampling;
+
 typedef struct InfgenRollout {
   /* sizes / hyper-parameters */
   int S, A_cap, T, M_cap, W, ring, R, token_size, grid_size, num_layers;
@@ -195,6 +212,13 @@ typedef struct InfgenRollout {
    * (infgen/modules/agent_decoder.py:2133-2158).  A context with tap_x runs the per-sublayer launches (k_layers_p keeps the
    * stream in registers across the triples) */
   float* tap_x;
+  /* temperature / nucleus mass of the motion-token draw (InfgenSampling: 0 = unset = 1) and an optional per-row temperature
+   * [S * A_cap] that wins over the scalar (0: that row decodes greedily, sample_logprob 0) - a batch of copies is a temperature sweep.
+   * Read by sampling steps only (sample_k > 1 with sample_u); token_logprob is not tempered.  Placed in front of sample_logprob,
+   * token_logprob and the two ablation switches, whose places at the struct's end older tests pin; INFGEN_Q_SIZEOF_ROLLOUT covers the growth, INFGEN_Q_ABI_VERSION keeps answering 1.
+   * infgen_heads_sample_fused and the need for logits_scratch do not depend on them. */
+  float sample_temperature; float sample_top_p;
+  const float* sample_temp_row;
   /* optional [steps][S * A_cap]: infgen_decode_step writes step t's slice with the log-probability of the sampled motion token under
    * the sampler's OWN distribution (the softmax re-normalised over the sample_k best logits) - laid out and overridden like
    * token_logprob, independent of it.  Written by sampling steps only (sample_k > 1 with sample_u): a greedy step leaves the slice
@@ -351,6 +375,12 @@ int infgen_token_logprob(const float* logits, int rows, int n, const int* token,
 int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
                         const float* uniform, float* logits, int* next_token, int* next_state, float* token_logprob,
                         float* sample_logprob, void* stream);
+/* the same with temperature and nucleus truncation (InfgenSampling above; sampling == NULL: infgen_heads_sample).  Still one launch
+ * where infgen_heads_sample_fused holds - the rule does not look at the parameters - and the same tokens and sample_logprob, bit for
+ * bit, as infgen_heads + infgen_sample_topk_ex.  token_logprob stays the full softmax at temperature 1. */
+int infgen_heads_sample_ex(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                           const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token, int* next_state,
+                           float* token_logprob, float* sample_logprob, void* stream);
 /* 1 where top-k sampling with beam k runs inside the split heads kernel: attn_mode 1, or >= 2 beyond INFGEN_Q_ATTN_SPLIT_ROWS
  * rows, and 2 <= k <= INFGEN_Q_HEADS_SAMPLE_K.  The one statement of the rule: infgen_heads_sample, infgen_decode_step and the
  * engine's decision to allocate logits_scratch all go through it. */
@@ -397,6 +427,10 @@ int infgen_sample_topk(const float* logits, int rows, int n, int k, const float*
 /* the same, plus sample_logprob [rows] (optional): the pick's log-probability under the re-normalised top-k distribution */
 int infgen_sample_topk_logprob(const float* logits, int rows, int n, int k, const float* uniform, int* token,
                                float* sample_logprob, void* stream);
+/* the same with temperature and nucleus truncation (InfgenSampling above; NULL: infgen_sample_topk_logprob); nucleus (optional,
+ * [rows]): the nucleus size m of every row (k where top_p = 1, 1 on a greedy row) */
+int infgen_sample_topk_ex(const float* logits, int rows, int n, int k, const float* uniform, const InfgenSampling* sampling,
+                          int* token, float* sample_logprob, int* nucleus, void* stream);
 
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell
@@ -424,6 +458,12 @@ int infgen_insert_decide_topk(const InfgenRollout* r, int t, int force_enter, in
                               const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
                               const float* occ, int* active, int* n_new, int* inserted, int* new_row, float* new_shape,
                               int* new_cell, int sample_k, const float* uniform, void* stream);
+/* the same with temperature and nucleus truncation of the cell draw (InfgenSampling above, scalars only: temperature_row is ignored;
+ * NULL: infgen_insert_decide_topk) */
+int infgen_insert_decide_topk_ex(const InfgenRollout* r, int t, int force_enter, int max_new,
+                                 const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
+                                 const float* occ, int* active, int* n_new, int* inserted, int* new_row, float* new_shape,
+                                 int* new_cell, int sample_k, const float* uniform, const InfgenSampling* sampling, void* stream);
 int infgen_insert_finalize(const InfgenRollout* r, int c, float angle_interval, const int* inserted,
                            const int* new_row, const float* lg_heading, int n_heading, const float* offset,
                            float* hv_ovr, void* stream);
@@ -462,6 +502,7 @@ typedef struct InfgenInsertion {
   int* host_dec;                              /* PINNED HOST memory [3][S]: inserted, new_row, active */
   float r_seed, r_a2sa, r_pl2sa, angle_interval;
   int n_heading, force_enter, insert_k, max_new;
+  float insert_temperature, insert_top_p;     /* the cell draw's temperature / nucleus mass (InfgenSampling: 0 = unset = 1; insert_k > 1) */
   /* the ablated insertion heads (0 / NULL = the full-token model).  no_grid_token: no occupancy embedding, no occ2sa layers (the seed
    * chain is pt2sa -> a2sa x 3), head_pos_xy (seed_pos_rel_xy_predict_head, MLPLayer 128 -> 2) replaces head_pos / head_offset: the new
    * row sits at tanh(xy) * r_seed + ego pos (world frame), its grid cell is -1, insert_k is ignored.  no_head_token:

@@ -60,6 +60,7 @@ class Insertion(C.Structure):
                 ('t1', _p), ('t2', _p), ('shp', _p), ('host_dec', _p),
                 ('r_seed', C.c_float), ('r_a2sa', C.c_float), ('r_pl2sa', C.c_float), ('angle_interval', C.c_float),
                 ('n_heading', _i), ('force_enter', _i), ('insert_k', _i), ('max_new', _i),
+                ('insert_temperature', _f), ('insert_top_p', _f),
                 ('head_pos_xy', _p), ('head_heading_theta', _p), ('no_grid_token', _i), ('no_head_token', _i)]
 
 
@@ -69,6 +70,11 @@ class Options(C.Structure):
 
 
 OPTIONS_VALUE_BYTES = C.sizeof(_i) * 12       # the integer switches of Options (the two pointers follow)
+
+
+class Sampling(C.Structure):
+    """InfgenSampling (include/infgen_hip.h): temperature / nucleus mass of a top-k draw (0 = unset = 1), optional per-row temperature"""
+    _fields_ = [('temperature', _f), ('top_p', _f), ('temperature_row', _p)]
 
 
 class Rollout(C.Structure):
@@ -101,6 +107,7 @@ class Rollout(C.Structure):
         ('replay_row', _p),
         ('map_scene', _p),
         ('tap_x', _p),
+        ('sample_temperature', _f), ('sample_top_p', _f), ('sample_temp_row', _p),
         ('sample_logprob', _p),
         ('token_logprob', _p),
         ('no_grid_token', _i), ('no_state_token', _i),
@@ -180,6 +187,7 @@ SYMBOLS = {
     'infgen_heads_logprob': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     'infgen_token_logprob': (_i, [_p, _i, _i, _p, _p, _p]),
     'infgen_heads_sample': (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    'infgen_heads_sample_ex': (_i, [_p, _i, _p, _p, _i, _i, _p, C.POINTER(Sampling), _p, _p, _p, _p, _p, _p]),
     'infgen_heads_sample_fused': (_i, [_i, _i, _i]),
     'infgen_heads_logprob_fused': (_i, [_i, _i]),
     'infgen_map_token_head': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
@@ -193,6 +201,7 @@ SYMBOLS = {
     'infgen_rollout_run': (_i, [C.POINTER(Rollout), _i, _i, _p]),
     'infgen_sample_topk': (_i, [_p, _i, _i, _i, _p, _p, _p]),
     'infgen_sample_topk_logprob': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    'infgen_sample_topk_ex': (_i, [_p, _i, _i, _i, _p, C.POINTER(Sampling), _p, _p, _p, _p]),
     'infgen_occupancy': (_i, [C.POINTER(Rollout), _i, _p, _p]),
     'infgen_occupancy_embed': (_i, [C.POINTER(Rollout), _i, _p, _p, _p, _p]),
     'infgen_point_edges': (_i, [C.POINTER(Rollout), _i, _p, _p, _i, _i, _f, _i, _f, _i, C.POINTER(EdgeBuf), C.POINTER(EdgeBuf), _p]),
@@ -200,6 +209,8 @@ SYMBOLS = {
     'infgen_insert_seed': (_i, [C.POINTER(Rollout), C.POINTER(Insertion), _i, _i, _i, _p, _p]),
     'infgen_insert_heading': (_i, [C.POINTER(Rollout), C.POINTER(Insertion), _i, _i, _i, _p]),
     'infgen_insert_decide_topk': (_i, [C.POINTER(Rollout), _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
+    'infgen_insert_decide_topk_ex': (_i, [C.POINTER(Rollout), _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p,
+                                          C.POINTER(Sampling), _p]),
     'infgen_insert_finalize': (_i, [C.POINTER(Rollout), _i, _f, _p, _p, _p, _i, _p, _p, _p]),
     'infgen_prof_enable': (_i, [C.c_uint, _i]),
     'infgen_prof_collect': (_i, [C.POINTER(C.c_double), C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]),

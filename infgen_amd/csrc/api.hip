@@ -3,6 +3,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <cmath>
 #include <string>
 #include <vector>
 #include <atomic>
@@ -27,6 +28,20 @@ static int check_launch(const char* where) {
 #define RET_IF(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 extern "C" const char* infgen_last_error(void) { return g_err.c_str(); }
+
+// InfgenSampling (NULL: the defaults) -> the kernels' SamplingCtl: 0 means "unset" and equals 1; the per-row array is the caller's to
+// check (device memory: engine.py does, once per load)
+static int sampling_ctl(const char* where, const InfgenSampling* s, SamplingCtl* out) {
+  *out = SAMPLING_DEFAULT;
+  if (!s) return 0;
+  if (!std::isfinite(s->temperature) || s->temperature < 0.f) return fail(where, "temperature must be finite and >= 0 (0: unset, i.e. 1)");
+  if (s->temperature != 0.f && s->temperature < 1.17549435e-38f) return fail(where, "temperature is a denormal: 1 / T overflows");
+  if (!(s->top_p >= 0.f && s->top_p <= 1.f)) return fail(where, "top_p must be in (0, 1] (0: unset, i.e. 1)");
+  out->temperature = s->temperature == 0.f ? 1.0f : s->temperature;
+  out->top_p = s->top_p == 0.f ? 1.0f : s->top_p;
+  out->temperature_row = s->temperature_row;
+  return 0;
+}
 
 // ---------------------------------------------------------------------------------- environment knobs
 // Experiment and diagnostic switches (tools/, profiles/): each is read once, when the library is loaded.
@@ -1039,7 +1054,8 @@ static void launch_mlpemb_h(const MlpEmbHArgs& m, void* stream) {
 static int heads_impl(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
                       float* logits, int* next_token, int* next_state, unsigned long long* scratch, void* stream,
                       bool keys_stay = false, bool* split_used = nullptr, float* token_logprob = nullptr,
-                      int sample_k = 0, const float* uniform = nullptr, float* sample_logprob = nullptr) {
+                      int sample_k = 0, const float* uniform = nullptr, float* sample_logprob = nullptr,
+                      const SamplingCtl& ctl = SAMPLING_DEFAULT) {
   if (split_used) *split_used = false;
   if (rows <= 0) return 0;
   if (token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
@@ -1048,7 +1064,7 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
     return fail("infgen_heads", "sampling inside the kernel needs the split kernel, k within its width and uniforms");
   if (sample_k <= 1) { sample_k = 0; uniform = nullptr; sample_logprob = nullptr; }
   HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1, token_logprob,
-              sample_k, uniform, sample_logprob};
+              sample_k, uniform, sample_logprob, ctl};
   if (scratch && !attn_split(rows)) {
     const int no_split = knob::heads_nosplit;
     const int tiles = ceil_div(rows, TR), nchunk = token_size / 128;
@@ -1101,11 +1117,11 @@ extern "C" int infgen_heads_logprob(const float* X, int rows, const float* tok_p
 }
 
 static int sample_topk_impl(const char* me, const float* logits, int rows, int n, int k, const float* uniform, int* token,
-                            float* sample_logprob, void* stream) {
+                            float* sample_logprob, void* stream, const SamplingCtl& ctl = SAMPLING_DEFAULT, int* nucleus = nullptr) {
   if (rows <= 0) return 0;
   if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
   if (k > n) return fail(me, "k must not exceed n");      // (the k-th pick of fewer than k logits is no token)
-  SampleArgs a{logits, rows, n, k, uniform, token, sample_logprob};
+  SampleArgs a{logits, rows, n, k, uniform, token, sample_logprob, ctl, nucleus};
   hipLaunchKernelGGL(k_sample_topk, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
   return check_launch(me);
 }
@@ -1120,13 +1136,21 @@ extern "C" int infgen_sample_topk_logprob(const float* logits, int rows, int n, 
   return sample_topk_impl("infgen_sample_topk_logprob", logits, rows, n, k, uniform, token, sample_logprob, stream);
 }
 
+// ... with temperature and nucleus truncation (sampling == NULL: infgen_sample_topk_logprob); k == 1 is the arg-max, the parameters ignored
+extern "C" int infgen_sample_topk_ex(const float* logits, int rows, int n, int k, const float* uniform, const InfgenSampling* sampling,
+                                     int* token, float* sample_logprob, int* nucleus, void* stream) {
+  const char* me = "infgen_sample_topk_ex";
+  SamplingCtl ctl = SAMPLING_DEFAULT;
+  if (k > 1) RET_IF(sampling_ctl(me, sampling, &ctl));
+  return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, stream, ctl, nucleus);
+}
+
 // infgen_heads with the motion token drawn by top-k sampling (k_sample_topk's order and arithmetic) and, optionally, its two
 // log-probabilities: one launch of k_heads_h<TERMS, LP, HEADS_KS> where heads_sample_fused_for holds (logits optional); elsewhere
 // heads into the caller's logits, k_sample_topk and k_token_logprob over them.  k == 1 is the arg-max (the greedy variant)
-extern "C" int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
-                                   const float* uniform, float* logits, int* next_token, int* next_state, float* token_logprob,
-                                   float* sample_logprob, void* stream) {
-  const char* me = "infgen_heads_sample";
+static int heads_sample_impl(const char* me, const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                             const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token, int* next_state,
+                             float* token_logprob, float* sample_logprob, void* stream) {
   if (rows <= 0) return 0;
   if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
   if (k > token_size) return fail(me, "k must not exceed token_size");
@@ -1137,14 +1161,31 @@ extern "C" int infgen_heads_sample(const float* X, int rows, const float* tok_pa
     if (token_logprob) return infgen_heads_logprob(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, token_logprob, stream);
     return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream);
   }
+  SamplingCtl ctl;
+  RET_IF(sampling_ctl(me, sampling, &ctl));
   if (heads_sample_fused_for(O().attn_mode, rows, k))
     return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
-                      token_logprob, k, uniform, sample_logprob);
+                      token_logprob, k, uniform, sample_logprob, ctl);
   if (!logits) return fail(me, "this row count or beam takes k_sample_topk: it needs a logits buffer [rows][token_size]");
   RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
-  RET_IF(sample_topk_impl(me, logits, rows, token_size, k, uniform, next_token, sample_logprob, stream));
+  RET_IF(sample_topk_impl(me, logits, rows, token_size, k, uniform, next_token, sample_logprob, stream, ctl));
   if (token_logprob) RET_IF(infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream));
   return 0;
+}
+
+extern "C" int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                                   const float* uniform, float* logits, int* next_token, int* next_state, float* token_logprob,
+                                   float* sample_logprob, void* stream) {
+  return heads_sample_impl("infgen_heads_sample", X, rows, tok_pack, st_pack, token_size, k, uniform, nullptr, logits, next_token,
+                           next_state, token_logprob, sample_logprob, stream);
+}
+
+// ... with temperature and nucleus truncation (the same draw: topk_inverse_cdf of kernels.h, inside the split kernel or after it)
+extern "C" int infgen_heads_sample_ex(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                                      const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token,
+                                      int* next_state, float* token_logprob, float* sample_logprob, void* stream) {
+  return heads_sample_impl("infgen_heads_sample_ex", X, rows, tok_pack, st_pack, token_size, k, uniform, sampling, logits, next_token,
+                           next_state, token_logprob, sample_logprob, stream);
 }
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) on the rows gather[k] of X.  Split arithmetic (k_map_head_h: one
@@ -1213,7 +1254,8 @@ static SceneState scene_of(const InfgenRollout* r) {
 static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src, e.raw, e.total, e.cap}; }
 static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
-static int validate(const InfgenRollout* r, const char* where) {
+// ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
+static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr) {
   if (!r) return fail(where, "null context");
   if (r->A_cap > 1024 || r->A_cap <= 0) return fail(where, "A_cap must be in 1..1024");
   if (r->A_cap % 32) return fail(where, "A_cap must be a multiple of 32");
@@ -1221,6 +1263,13 @@ static int validate(const InfgenRollout* r, const char* where) {
   if (r->ring <= r->W) return fail(where, "ring must exceed the temporal window");
   if (r->W > 16) return fail(where, "temporal window larger than 16 columns is not supported");
   if ((r->no_grid_token | r->no_state_token) & ~1) return fail(where, "no_grid_token / no_state_token must be 0 or 1");
+  SamplingCtl own;
+  if (!ctl) ctl = &own;
+  *ctl = SAMPLING_DEFAULT;
+  if (r->sample_k > 1 && r->sample_u) {      // (a greedy context ignores the sampling parameters)
+    const InfgenSampling sp{r->sample_temperature, r->sample_top_p, r->sample_temp_row};
+    RET_IF(sampling_ctl(where, &sp, ctl));
+  }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
     const int mode = (r->opts.use ? r->opts : O()).attn_mode;
@@ -1774,7 +1823,8 @@ extern "C" int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless,
 }
 
 extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
-  RET_IF(validate(r, "infgen_decode_step"));
+  SamplingCtl ctl;
+  RET_IF(validate(r, "infgen_decode_step", &ctl));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
@@ -1797,9 +1847,9 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   // (tmp2 is scratch of the raw-feature stage, free here: the per-row keys of the split arg-max)
   RET_IF(heads_impl(r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token,
                     r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream, false, nullptr, lp_fused ? lp : nullptr,
-                    s_fused ? r->sample_k : 0, su, slp));
+                    s_fused ? r->sample_k : 0, su, slp, ctl));
   if (sample && !s_fused)
-    RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream));
+    RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream, ctl));
   if (lp && !lp_fused) RET_IF(infgen_token_logprob(lg, rows, r->token_size, r->next_token, lp, stream));
   RET_IF(infgen_integrate(r, t, stream));
   RET_IF(infgen_raw_feature(r, c + 1, stream));
@@ -1893,11 +1943,14 @@ static int insert_decide_impl(const InfgenRollout* r, int t, int force_enter, in
                               const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
                               const float* occ, int* active, int* n_new, int* inserted, int* new_row,
                               float* new_shape, int* new_cell, int sample_k, const float* uniform, void* stream,
-                              bool grid = true, float r_seed = 0.f) {
+                              bool grid = true, float r_seed = 0.f, const InfgenSampling* sampling = nullptr) {
   RET_IF(validate(r, "infgen_insert_decide"));
   if (sample_k > 16) return fail("infgen_insert_decide", "sample_k must be <= 16");
   if (sample_k > 1 && !uniform) return fail("infgen_insert_decide", "cell sampling needs uniforms");
   InsertDecideArgs a;
+  a.ctl = SAMPLING_DEFAULT;
+  if (sample_k > 1) RET_IF(sampling_ctl("infgen_insert_decide", sampling, &a.ctl));
+  a.ctl.temperature_row = nullptr;         // (one draw per scene: scalars only)
   a.st = scene_of(r); a.c = 1 + t; a.t = t; a.R = r->R; a.grid_size = r->grid_size; a.force_enter = force_enter;
   a.max_new = max_new; a.sample_k = sample_k; a.uniform = uniform;
   a.grid_xy = r->grid_xy; a.lg_state = lg_state; a.lg_type = lg_type; a.shape = shape;
@@ -1927,6 +1980,16 @@ extern "C" int infgen_insert_decide_topk(const InfgenRollout* r, int t, int forc
                                          float* new_shape, int* new_cell, int sample_k, const float* uniform, void* stream) {
   return insert_decide_impl(r, t, force_enter, max_new, lg_state, lg_type, shape, lg_pos, occ, active, n_new, inserted, new_row,
                             new_shape, new_cell, sample_k, uniform, stream);
+}
+
+// ... with temperature and nucleus truncation of the cell draw (scalars; sampling->temperature_row is ignored)
+extern "C" int infgen_insert_decide_topk_ex(const InfgenRollout* r, int t, int force_enter, int max_new,
+                                            const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
+                                            const float* occ, int* active, int* n_new, int* inserted, int* new_row,
+                                            float* new_shape, int* new_cell, int sample_k, const float* uniform,
+                                            const InfgenSampling* sampling, void* stream) {
+  return insert_decide_impl(r, t, force_enter, max_new, lg_state, lg_type, shape, lg_pos, occ, active, n_new, inserted, new_row,
+                            new_shape, new_cell, sample_k, uniform, stream, true, 0.f, sampling);
 }
 
 static int insert_finalize_impl(const InfgenRollout* r, int c, float angle_interval, const int* inserted, const int* new_row,
@@ -2067,10 +2130,11 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
   else mlp_layer_descs(I->XS, S, I->head_pos_xy, 2, I->hid + 3 * hs_, I->lg_pos, d1[3], d2[3]);
   RET_IF(infgen_linear_multi(d1, 4, stream));
   RET_IF(infgen_linear_multi(d2, 4, stream));
-  if (grid)
-    RET_IF(infgen_insert_decide_topk(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, I->occ, I->active,
-                                     I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, I->insert_k, uniform, stream));
-  else
+  if (grid) {
+    const InfgenSampling sp{I->insert_temperature, I->insert_top_p, nullptr};
+    RET_IF(infgen_insert_decide_topk_ex(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, I->occ, I->active,
+                                        I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, I->insert_k, uniform, &sp, stream));
+  } else
     RET_IF(insert_decide_impl(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, nullptr, I->active,
                               I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, 1, nullptr, stream, false, I->r_seed));
   // hand-over to the host: did any scene insert, into which rows, which scenes go on?

@@ -1011,13 +1011,10 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
       prev_v = best; prev_i = bi;
     }
     if (k > 1) {
-      float p[16], sum = 0.f;
-      for (int j = 0; j < k; ++j) { p[j] = expf(topv[j] - topv[0]); sum += p[j]; }
-      const float u = a.uniform[s] * sum;
-      float cdf = 0.f;
-      int pick = k - 1;
-      for (int j = 0; j < k; ++j) { cdf += p[j]; if (u < cdf) { pick = j; break; } }
-      bi = topi[pick];
+      float sum, it, top_p;
+      int m;
+      sampling_row(a.ctl, s, &it, &top_p);
+      bi = topi[topk_inverse_cdf<16>(topv, k, a.uniform[s], it, top_p, &sum, &m)];
     } else {
       bi = topi[0];
     }
@@ -1161,10 +1158,13 @@ __global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
     prev_v = best; prev_i = bi;
   }
   if (lane != 0) return;
-  float sum;
-  const int pick = topk_inverse_cdf<16>(topv, a.k, a.uniform[row], &sum);
+  float sum, it, top_p;
+  int m;
+  sampling_row(a.ctl, row, &it, &top_p);
+  const int pick = topk_inverse_cdf<16>(topv, a.k, a.uniform[row], it, top_p, &sum, &m);
   a.token[row] = topi[pick];
-  if (a.sample_logprob) a.sample_logprob[row] = (topv[pick] - topv[0]) - logf(sum);
+  if (a.sample_logprob) a.sample_logprob[row] = (topv[pick] - topv[0]) * it - logf(sum);
+  if (a.nucleus) a.nucleus[row] = m;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -280,6 +280,12 @@ struct MatchMapArgs {
   int* token_idx;                    // [P]
 };
 
+// temperature and nucleus (top-p) truncation of the top-k samplers (topk_inverse_cdf below; InfgenSampling of include/infgen_hip.h
+// after the host's checks): temperature > 0, top_p in (0, 1]; temperature_row (optional, one entry per row, >= 0) wins over the scalar,
+// and an entry of 0 makes that row greedy.  The defaults (1, 1, NULL) are the plain top-k sampler bit for bit
+struct SamplingCtl { float temperature; float top_p; const float* temperature_row; };
+constexpr SamplingCtl SAMPLING_DEFAULT{1.0f, 1.0f, nullptr};
+
 struct HeadsArgs {
   const float* X; int rows;
   const float* tok_pack;    // MLPLayer pack: P(128,128) W0, b0, ln g/b, P(128,2048) W3, b3
@@ -300,6 +306,7 @@ struct HeadsArgs {
   int sample_k;
   const float* uniform;
   float* sample_logprob;
+  SamplingCtl ctl;          // (KS > 0 only) temperature / top-p of the draw, read once per row next to uniform[row]
 };
 constexpr int HEADS_KS = 16;      // the one sampling width k_heads_h is instantiated with (wider beams take k_sample_topk)
 
@@ -447,6 +454,7 @@ struct InsertDecideArgs {
   SceneState st;
   int c, t, R, grid_size, force_enter, max_new;
   int sample_k; const float* uniform;   // cell sampling: top-k inverse CDF with uniform[S] (sample_k <= 1: arg-max)
+  SamplingCtl ctl;                      // ... its temperature / top-p (scalars: temperature_row is not used per scene)
   const float* grid_xy;
   const float* lg_state;            // [S][2]
   const float* lg_type;             // [S][3]
@@ -480,28 +488,61 @@ struct SampleArgs {
   int k;                                     // beam size (<= 16)
   const float* uniform;                      // [rows] caller-supplied U[0,1)
   int* token;                                // [rows] out
-  float* sample_logprob;                     // optional [rows] out: log-probability of token[row] under the re-normalised top-k distribution
+  float* sample_logprob;                     // optional [rows] out: log-probability of token[row] under the sampler's own distribution
+  SamplingCtl ctl;                           // temperature / top-p
+  int* nucleus;                              // optional [rows] out: the nucleus size m (k when top_p = 1; 1 on a greedy row)
 };
 
-// the last block of top-k sampling, shared by k_sample_topk and k_heads_h<TERMS, LP, KS> so the two cannot drift apart: inverse CDF
-// over p[j] = exp(topv[j] - topv[0]), j < k (topv descending), with the caller's uniform u01 in [0, 1); the first j with
-// u01 * sum < cdf, else k - 1.  *sum_out: the sum of the p[j] in j order.  Statically indexed (KMAX rounds, guarded by k).
-template <int KMAX> __device__ __forceinline__ int topk_inverse_cdf(const float (&topv)[KMAX], int k, float u01, float* sum_out) {
+// the row's (1 / T, top_p) for topk_inverse_cdf, read once per row.  A greedy row (T == 0; anything below the smallest normal float
+// counts: 1 / T of a denormal overflows, and 0 * inf would poison the row - the host entries refuse such values) is the
+// nucleus of mass 0: m = 1, pick = 0, sum = exp(0) = 1, sample_logprob = 0 - the same code path, no branch of its own
+__device__ __forceinline__ void sampling_row(const SamplingCtl& c, int row, float* it, float* top_p) {
+  const float T = c.temperature_row ? c.temperature_row[row] : c.temperature;
+  const bool drawn = T >= 1.17549435e-38f;      // FLT_MIN: 1 / T stays finite
+  *it = drawn ? 1.0f / T : 1.0f;
+  *top_p = drawn ? c.top_p : 0.f;
+}
+
+// the last block of top-k sampling, shared by k_sample_topk, k_heads_h<TERMS, LP, KS> and k_insert_decide so the three cannot drift
+// apart.  topv[0..k-1]: the row's k best logits, descending; it = 1 / T; u01: the caller's uniform in [0, 1).
+//   1. p[j] = expf((topv[j] - topv[0]) * it), cdf[j] the running sum in j order, S_k = cdf[k-1]
+//   2. nucleus: the smallest m with cdf[m-1] >= top_p * S_k (top-k first, then top-p; m >= 1); top_p >= 1: m = k, no comparison
+//   3. sum = cdf[m-1], u = u01 * sum, pick = the first j < m with u < cdf[j], else m - 1
+// Returns pick; *sum_out = sum, *m_out = m.  The caller's sample_logprob is (topv[pick] - topv[0]) * it - logf(sum).
+// With it = 1 and top_p = 1 this is the plain top-k draw bit for bit (x * 1.0f is exact, m = k, the additions keep their order).
+// Statically indexed (KMAX rounds, guarded by k).
+template <int KMAX>
+__device__ __forceinline__ int topk_inverse_cdf(const float (&topv)[KMAX], int k, float u01, float it, float top_p, float* sum_out,
+                                                int* m_out) {
   float p[KMAX], sum = 0.f;
 #pragma unroll
   for (int j = 0; j < KMAX; ++j)
-    if (j < k) { p[j] = expf(topv[j] - topv[0]); sum += p[j]; }
+    if (j < k) { p[j] = expf((topv[j] - topv[0]) * it); sum += p[j]; }
+  int m = k;
+  if (top_p < 1.0f) {
+    const float mass = top_p * sum;
+    float c = 0.f;                       // the same additions in the same order: c after j rounds IS cdf[j-1]
+    bool cut = false;
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j)
+      if (j < k && !cut) {
+        c += p[j];
+        if (c >= mass) { m = j + 1; cut = true; }
+      }
+    sum = c;
+  }
   const float u = u01 * sum;
   float cdf = 0.f;
-  int pick = k - 1;
+  int pick = m - 1;
   bool found = false;
 #pragma unroll
   for (int j = 0; j < KMAX; ++j)
-    if (j < k && !found) {
+    if (j < m && !found) {
       cdf += p[j];
       if (u < cdf) { pick = j; found = true; }
     }
   *sum_out = sum;
+  *m_out = m;
   return pick;
 }
 

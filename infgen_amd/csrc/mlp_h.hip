@@ -281,15 +281,17 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
           ti[KS - 1] = won ? 0x7fffffff : ti[KS - 1];
         }
       }
-      float sum;
-      const int pick = topk_inverse_cdf<KS>(mv, a.sample_k, valid ? a.uniform[row] : 0.f, &sum);
+      float sum, it = 1.0f, top_p = 1.0f;
+      int m;
+      if (valid) sampling_row(a.ctl, row, &it, &top_p);
+      const int pick = topk_inverse_cdf<KS>(mv, a.sample_k, valid ? a.uniform[row] : 0.f, it, top_p, &sum, &m);
       float pv = mv[0];
       int pi = mi[0];
 #pragma unroll
       for (int q = 1; q < KS; ++q) { pv = q == pick ? mv[q] : pv; pi = q == pick ? mi[q] : pi; }
       if (valid && rg == 0) {
         a.next_token[row] = pi;
-        if (a.sample_logprob) a.sample_logprob[row] = (pv - mv[0]) - logf(sum);
+        if (a.sample_logprob) a.sample_logprob[row] = (pv - mv[0]) * it - logf(sum);
         if constexpr (LP) a.token_logprob[row] = pv - (bv + logf(lse));
       }
     }

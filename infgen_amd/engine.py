@@ -537,6 +537,9 @@ def _lib_np_dtype(dt):
             torch.bool: np.bool_, torch.float64: np.float64}[dt]
 
 
+_FLT_MIN = float(np.finfo(np.float32).tiny)      # the smallest normal float32: below it 1 / T overflows
+
+
 class RolloutEngine:
     """Device state + launch sequence for a batch of scenes."""
     copies = 1          # rollouts per scene over one map encoding (instance attribute when given; see __init__)
@@ -550,7 +553,8 @@ class RolloutEngine:
                  insert_k: int = 1, insert_uniforms: Optional[np.ndarray] = None, seed_outputs: bool = False,
                  use_graph: Optional[bool] = None, copies: int = 1, flags: Optional[Mapping[str, bool]] = None,
                  tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None,
-                 token_logprob: bool = False, sample_logprob: bool = False):
+                 token_logprob: bool = False, sample_logprob: bool = False,
+                 sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -569,7 +573,17 @@ class RolloutEngine:
         distribution, the softmax re-normalised over the ``sample_k`` best logits (``next_token_sample_logprob``, masked by
         ``next_token_logprob_mask``; ``rollout_sample_logprob()``).  Independent of ``token_logprob``; 0 where masked when
         ``sample_k <= 1`` (a point mass).  Sampled rollouts whose every step samples inside the heads kernel
-        (``infgen_heads_sample_fused``) keep no logits in memory: ``logits_scratch`` is None."""
+        (``infgen_heads_sample_fused``) keep no logits in memory: ``logits_scratch`` is None.
+        ``sample_temperature`` / ``sample_top_p``: temperature and nucleus (top-p) truncation of the motion-token draw (DESIGN 5.10;
+        read where ``sample_k > 1``): the softmax over the ``sample_k`` best logits at temperature T, cut to the smallest prefix that
+        holds ``sample_top_p`` of its mass.  ``sample_temperature`` is a float, an array [S] (one entry per agent-side scene: with
+        ``copies = n`` one per copy - a batch of copies is a temperature sweep) or [S][rows]; 0 makes those rows greedy - also as a
+        float, which then means every row (unlike the C struct's scalar, where 0 reads "unset")
+        (``next_token_sample_logprob`` 0 there).  Arrays live in one static device buffer that ``reload*(sample_temperature=...)``
+        rewrites, so captured graphs replay the new values; rows scenario insertion appends take their scene's value.
+        ``next_token_logprob`` stays the model's own full softmax at temperature 1.  ``insert_temperature`` / ``insert_top_p``: the
+        same for the cell draw of scenario insertion (scalars; ``insert_k > 1``; a temperature of 0 is refused: the arg-max cell is
+        ``insert_k = 1``).  ``reload*(sample_top_p=...)`` changes the nucleus mass of an engine that exists.  The defaults are the plain samplers bit for bit."""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -614,6 +628,10 @@ class RolloutEngine:
         self.store_logits = store_logits
         self.sample_k = int(sample_k)
         self._sample_uniforms = sample_uniforms      # [steps][S][A] float32 in [0,1) (top-k inverse-CDF sampling)
+        self.sample_top_p = self._check_top_p(sample_top_p, 'sample_top_p')
+        self.insert_temperature = self._check_temperature(insert_temperature, 'insert_temperature')
+        self.insert_top_p = self._check_top_p(insert_top_p, 'insert_top_p')
+        self.sample_temperature, self.sample_temp_row = 1.0, None     # (set below, once the row layout is known)
         # scenario insertion: the cell of a new agent from the insert_k most probable ones (reference insert_beam_size = 10,
         # agent_decoder.py:1900-1904) with insert_uniforms [steps][10][S]; 1: arg-max
         # (use_grid_token = False: no cell is drawn - the position is regressed - and insert_k is accepted and ignored, as in the reference)
@@ -741,6 +759,8 @@ class RolloutEngine:
         if self.sample_k > 1:
             assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
             self.sample_u = torch.from_numpy(self._uniform_rows(sample_uniforms, amax)).to(dev)
+        self._ctx = None
+        self._load_temperature(sample_temperature, amax)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -834,7 +854,71 @@ class RolloutEngine:
         mmax = max(int(np.asarray(sc['pt_token']['position']).shape[0]) for sc in scenes)
         return self._fits(len(scenes), amax, mmax)
 
-    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax):
+    @staticmethod
+    def _check_temperature(t, name: str) -> float:
+        """a scalar temperature of the cell draw: finite and a normal float32 above 0 (1 / T must stay finite).  0 is refused here:
+        the C struct reads it as "unset", i.e. 1, and the cell draw has no per-row form where it could mean greedy - a greedy
+        cell is ``insert_k = 1``"""
+        t = float(t)
+        if not (np.isfinite(t) and t >= _FLT_MIN):
+            raise ValueError(f'{name} must be finite and > 0, no denormal (got {t}; the arg-max cell is insert_k = 1)')
+        return t
+
+    @staticmethod
+    def _check_top_p(p, name: str) -> float:
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f'{name} must be in (0, 1] (got {p})')
+        return p
+
+    def _load_temperature(self, temperature, amax):
+        """``sample_temperature`` into the engine (None: keep what is there).  A float is the context's scalar - unless a per-row
+        buffer exists already, which it then fills; an array [S] or [S][rows] is checked here, on the host, once per load (finite,
+        >= 0: the library cannot look into device memory) and written into the static [S * A_cap] buffer the context points at."""
+        if temperature is None:
+            return
+        S, A_cap = self.S, self.A_cap
+        t = np.asarray(temperature, dtype=np.float32)
+        if not (np.isfinite(t).all() and ((t == 0) | (t >= _FLT_MIN)).all()):
+            raise ValueError('sample_temperature must be finite and 0 (greedy) or a normal float32 above 0 (1 / T must stay finite)')
+        if t.ndim == 0 and self.sample_temp_row is None and float(t) > 0.0:      # (a scalar 0 is "every row greedy": the array's 0)
+            if float(t) != self.sample_temperature:
+                self._graph = self._wgraph = None      # (a captured graph holds the old kernel argument)
+            self.sample_temperature = float(t)
+        else:
+            if t.ndim == 0:
+                rows = np.full((S, A_cap), float(t), np.float32)
+            elif t.ndim == 1:
+                assert t.shape == (S,), f'sample_temperature {t.shape}: one entry per agent-side scene [S={S}]'
+                rows = np.repeat(t[:, None], A_cap, axis=1)      # (rows insertion appends: their scene's value)
+            else:
+                need = A_cap if self.insertion else amax
+                assert t.ndim == 2 and t.shape[0] == S and t.shape[1] >= need, \
+                    f'sample_temperature {t.shape} does not cover [S={S}][rows={need}]'
+                rows = np.ones((S, A_cap), np.float32)
+                rows[:, :min(A_cap, t.shape[1])] = t[:, :A_cap]
+            rows = torch.from_numpy(np.ascontiguousarray(rows.reshape(S * A_cap)))
+            if self.sample_temp_row is None:
+                self.sample_temp_row = rows.to(self.device)
+                self._graph = self._wgraph = None
+            else:
+                self.sample_temp_row.copy_(rows)
+        self._apply_sampling()
+
+    def _apply_sampling(self):
+        if self._ctx is not None:
+            c = self._ctx
+            c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
+            c.sample_temp_row = _lib.ptr(self.sample_temp_row)
+
+    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None):
+        if sample_top_p is not None:
+            p = self._check_top_p(sample_top_p, 'sample_top_p')
+            if p != self.sample_top_p:
+                self._graph = self._wgraph = None      # (a captured graph holds the old kernel argument)
+            self.sample_top_p = p
+            self._apply_sampling()
+        self._load_temperature(sample_temperature, amax)
         if self.sample_k > 1:
             assert sample_uniforms is not None, 'top-k sampling needs caller-supplied uniforms'
             self.sample_u.copy_(torch.from_numpy(self._uniform_rows(sample_uniforms, amax)))
@@ -891,7 +975,8 @@ class RolloutEngine:
         self._load_replay(*scene_setup.stage_replay(self.scenes, [h['filt'] for h in self.hosts[::self.copies]], replay, self.T))
 
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
-               insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None):
+               insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
+               sample_temperature=None, sample_top_p=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -904,7 +989,7 @@ class RolloutEngine:
             getattr(self, k).copy_(torch.from_numpy(arr[k]), non_blocking=False)
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
-        self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()))
+        self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p)
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -919,7 +1004,8 @@ class RolloutEngine:
         return self._fits(S, A, int(k['pt_token']['position'].shape[1]), T0)
 
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
-                      insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None) -> bool:
+                      insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
+                      sample_temperature=None, sample_top_p=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -932,7 +1018,7 @@ class RolloutEngine:
         if not self._setup_device(k, replay):
             return False
         self.scenes = scenes
-        self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'])
+        self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p)
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -992,7 +1078,8 @@ class RolloutEngine:
         return self._batch_lay is not None and self._fits(layout['B'], layout['amax'], layout['mmax'], layout['T0'])
 
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
-                     insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None):
+                     insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
+                     sample_temperature=None, sample_top_p=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1000,7 +1087,7 @@ class RolloutEngine:
         if layout is None:
             layout = read_batch_layout(batch, self.T, self.hc, self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
-        self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'])
+        self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -1406,6 +1493,7 @@ class RolloutEngine:
         b.host_dec = I['host_dec'].data_ptr()
         b.r_seed, b.r_a2sa, b.r_pl2sa, b.angle_interval = float(cfg.pl2seed_radius), float(cfg.a2sa_radius), float(cfg.pl2sa_radius), float(cfg.angle_interval)
         b.n_heading, b.force_enter, b.insert_k, b.max_new = int(360.0 / cfg.angle_interval), int(self.force_enter), self.insert_k, 10
+        b.insert_temperature, b.insert_top_p = self.insert_temperature, self.insert_top_p
         return b
 
     def _insert_step(self, t: int):
@@ -1509,6 +1597,7 @@ class RolloutEngine:
         c.token_logprob = P(self.token_logprob)
         c.sample_logprob = P(self.sample_logprob)
         self._ctx = c
+        self._apply_sampling()
         self._refresh_opts()
         _lib.check(self.lib.infgen_rollout_validate(C.byref(c)), 'infgen_rollout_validate')      # (the packs' headers, looked at afresh)
 

@@ -312,6 +312,14 @@ class InfGenDecoder(nn.Module):
         #   rollout_sample_logprob                          the masked sum, float64 on the device ([B] for a Batch), rollout_logprob's order
         # Independent of token_logprob.  False (default): the dicts have exactly the keys they had.
         self.sample_logprob = False
+        # temperature and nucleus (top-p) truncation of the two top-k draws (RolloutEngine's arguments of the same names):
+        # the motion token where motion_beam_size > 1 - sample_temperature may also hold one value per copy of inference_rollouts /
+        # inference_batch(copies=n), 0 making that copy greedy - and the inserted agent's cell where insert_beam_size > 1.  The
+        # defaults are the plain top-k samplers; next_token_logprob stays the model's own softmax at temperature 1.
+        self.sample_temperature = 1.0
+        self.sample_top_p = 1.0
+        self.insert_temperature = 1.0
+        self.insert_top_p = 1.0
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -399,11 +407,27 @@ class InfGenDecoder(nn.Module):
                     for m, p_ in zip(masks, plans)]
         return dev_form, host_form
 
+    def _sampling_kw(self, n_scenes: int, copies: int, sample_temperature=None):
+        """-> (the engine's constructor arguments, the value its reload* take): a scalar temperature, or one entry per copy spread
+        over the agent-side scenes (scene i's copies are adjacent)"""
+        t = np.asarray(self.sample_temperature if sample_temperature is None else sample_temperature, dtype=np.float32)
+        if t.ndim == 0:
+            temp = float(t)
+        else:
+            if t.shape != (copies,):
+                raise ValueError(f'sample_temperature: a float or one value per copy ({copies}), got shape {t.shape}')
+            temp = np.tile(t, n_scenes)
+        # (the cell draw's two scalars are fixed per engine and key it; the motion draw's go through reload*, like the uniforms)
+        fixed = dict(insert_temperature=float(self.insert_temperature), insert_top_p=float(self.insert_top_p))
+        live = dict(sample_temperature=temp, sample_top_p=float(self.sample_top_p))
+        return dict(fixed, **live), live, tuple(fixed.values())
+
     def _run(self, data, x_pt=None, map_only=False, batch: Optional[Sequence] = None, sample_uniforms=None,
-             batch_seed_outputs: bool = False, copies: int = 1, replay=None, replay_plan=None):
+             batch_seed_outputs: bool = False, copies: int = 1, replay=None, replay_plan=None, sample_temperature=None):
         ae = self.agent_encoder
         datas = list(batch) if batch is not None else [data]
         copies = int(copies)
+        skw, live, skey = self._sampling_kw(len(datas), copies, sample_temperature)
         # copies = n: every scene of the batch is decoded n times in lockstep over ONE map encoding (RolloutEngine(copies=n));
         # the result list holds scene 0's n rollouts, then scene 1's, ...
         # a batch of device tensors of one shape is set up on the device (RolloutEngine.reload_device); its host form is only made
@@ -451,20 +475,21 @@ class InfGenDecoder(nn.Module):
                                  seed_outputs=(batch is None or batch_seed_outputs) and not w.cfg.disable_insertion and not map_only,
                                  copies=copies, options=self._PRECISIONS[str(self.rollout_precision)], replay=rp_host(),
                                  token_logprob=bool(self.token_logprob) and not map_only,
-                                 sample_logprob=bool(self.sample_logprob) and not map_only)
+                                 sample_logprob=bool(self.sample_logprob) and not map_only, **skw)
         # one engine per batch layout is kept across calls: a second call of the same shape re-uploads the scene arrays into
         # the first call's device buffers instead of building (and allocating) an engine again
         ekey = (len(scenes), PackedWeights.tables_key(*(vocab[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab),
                 bool(w.cfg.disable_insertion), w.cfg.num_recurrent_steps_val, k if not map_only else 1,
                 ik if insert_uniforms is not None else 1, bool(int(os.getenv('DEBUG', 0))), batch is None, map_only, xo is None,
-                bool(batch_seed_outputs), copies, replay is not None, bool(self.token_logprob), bool(self.sample_logprob))
+                bool(batch_seed_outputs), copies, replay is not None, bool(self.token_logprob), bool(self.sample_logprob), skey)
         eng = self._engines.get(ekey)
         if (stk is not None and eng is not None and eng.fits_device(stk) and
                 eng.reload_device(stk, scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo,
-                                  replay=rp_dev)):
+                                  replay=rp_dev, **live)):
             pass
         elif eng is not None and eng.fits(scenes):
-            eng.reload(scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo, replay=rp_host())
+            eng.reload(scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo, replay=rp_host(),
+                       **live)
         else:
             eng = make_engine()
             if len(self._engines) >= 2:
@@ -605,7 +630,7 @@ class InfGenDecoder(nn.Module):
         return self._cached('_host_consts', [t], lambda: t.detach().cpu().numpy())
 
     def _run_graphs(self, data, sample_uniforms=None, copies: int = 1, mutate: bool = True, replay=None,
-                    replay_plan=None) -> List[Dict]:
+                    replay_plan=None, sample_temperature=None) -> List[Dict]:
         """a ragged multi-graph Batch of device tensors through RolloutEngine.reload_batch (the ingest kernel: filter, pad and
         set up every scene on the device) and the batched epilogue (outputs_batch: infgen_pack_rows).  One device -> host copy
         before the first launch (the offsets and av_index; the token vocabularies the tables are keyed by ride along unless the
@@ -654,6 +679,7 @@ class InfGenDecoder(nn.Module):
         _, vocab, tkey = hit
         B = lay['B']
         S = B * copies
+        skw, live, skey = self._sampling_kw(B, copies, sample_temperature)
         cfg.disable_insertion = bool(ae.disable_insertion)
         k = int(getattr(ae, 'motion_beam_size', 1))
         if k > 1 and sample_uniforms is None:
@@ -685,13 +711,14 @@ class InfGenDecoder(nn.Module):
                                  sample_uniforms=sample_uniforms, insert_k=ik if insert_uniforms is not None else 1,
                                  insert_uniforms=insert_uniforms, seed_outputs=not cfg.disable_insertion, copies=copies,
                                  options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay, replay=rp,
-                                 token_logprob=bool(self.token_logprob), sample_logprob=bool(self.sample_logprob))
-        ekey = ('graphs', S, tkey,
+                                 token_logprob=bool(self.token_logprob), sample_logprob=bool(self.sample_logprob), **skw)
+        ekey = ('graphs', S, tkey, skey,
                 bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies,
                 replay is not None, bool(self.token_logprob), bool(self.sample_logprob))
         eng = self._engines.get(ekey)
         if eng is not None and eng.fits_batch(lay):
-            eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay, replay=rp)
+            eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay, replay=rp,
+                             **live)
         else:
             eng = make_engine()
             if len(self._engines) >= 2:
@@ -862,29 +889,35 @@ class InfGenDecoder(nn.Module):
         return r.merged(first=map_enc)
 
     @torch.no_grad()
-    def inference_rollouts(self, data, n: int, replay=None, replay_plan=None) -> List[Dict[str, torch.Tensor]]:
+    def inference_rollouts(self, data, n: int, replay=None, replay_plan=None, sample_temperature=None,
+                           sample_uniforms=None) -> List[Dict[str, torch.Tensor]]:
         """``n`` independent rollouts of ONE scene (the reference's ``n_rollout_close_val`` loop, infgen/model/infgen.py:704-706,
         which calls ``inference(data.clone())`` n times) as one batch of n copies decoded in lockstep: with
         ``motion_beam_size`` / ``insert_beam_size`` > 1 every copy draws its own uniforms from torch's RNG, so the results are n
         samples; greedy copies are identical.  ``data`` itself is not mutated (the copies are).  ``replay`` / ``replay_plan``
-        as in ``inference``: every copy replays the same plan."""
+        as in ``inference``: every copy replays the same plan.  ``sample_temperature``: one temperature per copy (a sweep in one
+        batch; 0: that copy decodes greedily) instead of the module's ``sample_temperature``; ``sample_uniforms``
+        ([steps][graphs * n][A]): the copies' uniforms instead of torch's RNG."""
         # one engine batch of n copies of the scene over ONE map encoding (RolloutEngine(copies=n): the map-token graph, the map
         # encoder and the map K / V rows exist once - the reference offers inference_no_map(data, map_enc) for the same purpose);
         # every rollout carries what ``inference`` returns for it: the seed node's outputs and the map_next_token_* keys too
         if num_graphs(data) > 1:            # B graphs x n copies as one engine batch over B map encodings; n batched dicts
-            return self._run_graphs(data, copies=int(n), mutate=False, replay=replay, replay_plan=replay_plan)
+            return self._run_graphs(data, copies=int(n), mutate=False, replay=replay, replay_plan=replay_plan,
+                                    sample_temperature=sample_temperature, sample_uniforms=sample_uniforms)
         return self.inference_batch([data.clone() if hasattr(data, 'clone') else dict(data)], seed_outputs=True, copies=int(n),
-                                    replay=replay, replay_plan=replay_plan)
+                                    replay=replay, replay_plan=replay_plan, sample_temperature=sample_temperature,
+                                    sample_uniforms=sample_uniforms)
 
     @torch.no_grad()
     def inference_batch(self, datas: Sequence, seed_outputs: bool = False, copies: int = 1, replay=None,
-                        replay_plan=None) -> List[Dict[str, torch.Tensor]]:
+                        replay_plan=None, sample_temperature=None, sample_uniforms=None) -> List[Dict[str, torch.Tensor]]:
         """throughput entry: many independent scenes decoded in lockstep on this GPU.  Every dict has the key set of
         ``inference``; the seed node's per-insertion arrays (``*_seed``) are recorded only with ``seed_outputs=True`` (5.5 MB per
         scene), otherwise they are the zero arrays the reference initialises them to (agent_decoder.py:1746-1750).
         ``replay``: 'ego', one bool tensor per scene, or one over all scenes' rows in order; ``replay_plan``: one dict per scene
         or one over all rows (see ``inference``)."""
-        rs = self._run(None, batch=datas, batch_seed_outputs=seed_outputs, copies=copies, replay=replay, replay_plan=replay_plan)
+        rs = self._run(None, batch=datas, batch_seed_outputs=seed_outputs, copies=copies, replay=replay, replay_plan=replay_plan,
+                       sample_temperature=sample_temperature, sample_uniforms=sample_uniforms)
         if copies > 1:                          # ``copies`` rollouts per scene over one map encoding: scene 0's first, then scene 1's ...
             datas = [d for d in datas for _ in range(int(copies))]
         out = []

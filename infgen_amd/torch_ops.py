@@ -11,7 +11,10 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.token_state_head(x (N, 128), tok_pack, st_pack, token_size, want_logits) -> token, state, logits
     torch.ops.infgen_hip.token_logprob(logits (N, n), token (N,))                           -> (N,) log_softmax(logits)[token]; 0 where token < 0
     torch.ops.infgen_hip.heads_sample(x (N, 128), tok_pack, st_pack, token_size, k, uniform (N,), want_logits, want_logprob,
-                                      want_sample_logprob)                                  -> token, state, logits, token_logprob, sample_logprob
+                                      want_sample_logprob, temperature=1, top_p=1, temperature_row=None)
+                                                                                            -> token, state, logits, token_logprob, sample_logprob
+    torch.ops.infgen_hip.sample_topk(logits (N, n), k, uniform (N,), want_sample_logprob, temperature=1, top_p=1,
+                                     temperature_row=None)                                  -> token (N,), sample_logprob
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -49,6 +52,16 @@ def _ops(dev: torch.device) -> Ops:
 
 def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous().float()
+
+
+def _sampling(temperature: float, top_p: float, temperature_row: Optional[torch.Tensor], rows: int, dev: torch.device):
+    """-> (InfgenSampling, the per-row tensor it points at: keep it alive until the launch is enqueued)"""
+    row = None
+    if temperature_row is not None:
+        if temperature_row.shape != (rows,):
+            raise ValueError(f'temperature_row must hold one entry per row ({rows})')
+        row = temperature_row.to(dev, torch.float32).contiguous()
+    return _lib.Sampling(float(temperature), float(top_p), _lib.ptr(row)), row
 
 
 @torch.library.custom_op('infgen_hip::fourier_embed', mutates_args=())
@@ -181,16 +194,20 @@ def _(logits, token):
 
 @torch.library.custom_op('infgen_hip::heads_sample', mutates_args=())
 def heads_sample(x: torch.Tensor, tok_pack: torch.Tensor, st_pack: torch.Tensor, token_size: int, k: int, uniform: torch.Tensor,
-                 want_logits: bool = False, want_logprob: bool = False, want_sample_logprob: bool = False
+                 want_logits: bool = False, want_logprob: bool = False, want_sample_logprob: bool = False,
+                 temperature: float = 1.0, top_p: float = 1.0, temperature_row: Optional[torch.Tensor] = None
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """token_predict_head / state_predict_head with the motion token drawn by top-k sampling (agent_decoder.py:2162-2163, 2194-2195;
     ``infgen_heads_sample``): the ``k`` (1..16) best logits of a row in (value descending, column ascending) order, inverse CDF
     over their re-normalised probabilities with ``uniform[row]`` in [0, 1).  Returns next token (N,), next state (N,) and, each on
     request (else an empty tensor), the (N, token_size) logits, the full-softmax log-probability of the sampled token (N,) and its
     log-probability under the re-normalised top-k distribution (N,).  Where the library samples inside the split heads kernel
-    (``infgen_heads_sample_fused``) no logit reaches memory unless asked for; elsewhere the op holds the logits itself"""
+    (``infgen_heads_sample_fused``) no logit reaches memory unless asked for; elsewhere the op holds the logits itself.
+    ``temperature`` / ``top_p`` / ``temperature_row`` (N,): temperature and nucleus truncation of the draw (``InfgenSampling`` of
+    include/infgen_hip.h; a per-row temperature of 0 makes the row greedy); the full-softmax log-probability is not tempered"""
     if x.dim() != 2 or x.shape[1] != D or uniform.shape != x.shape[:1]:
         raise ValueError('heads_sample takes x (N, 128) and uniform (N,)')
+    sp, _keep = _sampling(temperature, top_p, temperature_row, x.shape[0], x.device)
     ops = _ops(x.device)
     n = x.shape[0]
     tok = torch.zeros(n, device=x.device, dtype=torch.int32)
@@ -203,20 +220,49 @@ def heads_sample(x: torch.Tensor, tok_pack: torch.Tensor, st_pack: torch.Tensor,
     slp = torch.zeros(n if want_sample_logprob else 0, device=x.device)
     if n:
         u = uniform.to(x.device, torch.float32).contiguous()
-        _lib.check(ops.lib.infgen_heads_sample(_lib.ptr(_f32(x)), n, _lib.ptr(_f32(tok_pack)), _lib.ptr(_f32(st_pack)),
-                                               int(token_size), int(k), _lib.ptr(u), _lib.ptr(lg) if keep else None, _lib.ptr(tok),
-                                               _lib.ptr(st), _lib.ptr(lp) if want_logprob else None,
-                                               _lib.ptr(slp) if want_sample_logprob else None, ops.stream), 'infgen_heads_sample')
+        _lib.check(ops.lib.infgen_heads_sample_ex(_lib.ptr(_f32(x)), n, _lib.ptr(_f32(tok_pack)), _lib.ptr(_f32(st_pack)),
+                                                  int(token_size), int(k), _lib.ptr(u), C.byref(sp), _lib.ptr(lg) if keep else None,
+                                                  _lib.ptr(tok), _lib.ptr(st), _lib.ptr(lp) if want_logprob else None,
+                                                  _lib.ptr(slp) if want_sample_logprob else None, ops.stream), 'infgen_heads_sample_ex')
     return tok, st, (lg if want_logits else lg.new_empty(0, token_size)), lp, slp
 
 
 @heads_sample.register_fake
-def _(x, tok_pack, st_pack, token_size, k, uniform, want_logits=False, want_logprob=False, want_sample_logprob=False):
+def _(x, tok_pack, st_pack, token_size, k, uniform, want_logits=False, want_logprob=False, want_sample_logprob=False,
+      temperature=1.0, top_p=1.0, temperature_row=None):
     n = x.shape[0]
     return (x.new_empty(n, dtype=torch.int32), x.new_empty(n, dtype=torch.int32),
             x.new_empty(n if want_logits else 0, token_size, dtype=torch.float32),
             x.new_empty(n if want_logprob else 0, dtype=torch.float32),
             x.new_empty(n if want_sample_logprob else 0, dtype=torch.float32))
+
+
+@torch.library.custom_op('infgen_hip::sample_topk', mutates_args=())
+def sample_topk(logits: torch.Tensor, k: int, uniform: torch.Tensor, want_sample_logprob: bool = False,
+                temperature: float = 1.0, top_p: float = 1.0, temperature_row: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """top-k sampling over stored logits (N, n) (``infgen_sample_topk_ex``; agent_decoder.py:2162-2163, 2194-2195): the ``k`` (1..16)
+    best logits of a row, inverse CDF with ``uniform[row]``; ``temperature`` / ``top_p`` / ``temperature_row`` as in ``heads_sample``.
+    Returns the token (N,) and, on request (else empty), its log-probability under the sampler's own distribution (N,)"""
+    if logits.dim() != 2 or uniform.shape != logits.shape[:1]:
+        raise ValueError('sample_topk takes logits (N, n) and uniform (N,)')
+    ops = _ops(logits.device)
+    n = logits.shape[0]
+    sp, _keep = _sampling(temperature, top_p, temperature_row, n, logits.device)
+    tok = torch.zeros(n, device=logits.device, dtype=torch.int32)
+    slp = torch.zeros(n if want_sample_logprob else 0, device=logits.device)
+    if n:
+        lg, u = _f32(logits), uniform.to(logits.device, torch.float32).contiguous()
+        _lib.check(ops.lib.infgen_sample_topk_ex(_lib.ptr(lg), n, int(lg.shape[1]), int(k), _lib.ptr(u), C.byref(sp), _lib.ptr(tok),
+                                                 _lib.ptr(slp) if want_sample_logprob else None, None, ops.stream),
+                   'infgen_sample_topk_ex')
+    return tok, slp
+
+
+@sample_topk.register_fake
+def _(logits, k, uniform, want_sample_logprob=False, temperature=1.0, top_p=1.0, temperature_row=None):
+    n = logits.shape[0]
+    return logits.new_empty(n, dtype=torch.int32), logits.new_empty(n if want_sample_logprob else 0, dtype=torch.float32)
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())

@@ -14,6 +14,16 @@ variant: the median over the samples, their spread (min .. max), the engine's de
 
 Gate: the median of ``this`` is not above the parent's own maximum (not slower beyond the parent's run-to-run spread).  A failed
 gate exits non-zero.
+
+With ``--temperature T --top-p P`` the variants are instead
+
+    parent      the parent commit
+    this        this tree with the default sampler (T = 1, top_p = 1: the same arithmetic)
+    this T/P    this tree with sample_temperature = T, sample_top_p = P
+    this sweep  this tree with one temperature per copy (0, then 0.5 .. 2 in equal steps) and top_p = P
+
+and the gate is that the median of ``this`` lies inside the parent's own min .. max; the other two are recorded, not gated.  Use
+``--rounds 5``; the log then defaults to ``profiles/sampling_controls.log``.
 """
 import argparse
 import json
@@ -44,6 +54,10 @@ w = engine.PackedWeights(sd, cfg, dev)
 torch.cuda.synchronize()
 base = torch.cuda.memory_allocated(dev)
 kw = dict(token_logprob=True, sample_logprob=True) if mode == 'lp' else {}
+if mode.startswith('tp:') or mode.startswith('sweep:'):
+    kind, T, P = mode.split(':')
+    per_copy = np.concatenate([[0.0], np.linspace(0.5, 2.0, copies - 1)]).astype(np.float32) if copies > 1 else np.float32([1.0])
+    kw = dict(sample_temperature=float(T) if kind == 'tp' else np.tile(per_copy, scenes_n), sample_top_p=float(P))
 eng = engine.RolloutEngine(w, scenes, vocab, map_vocab, grid, copies=copies, sample_k=5, sample_uniforms=u, **kw)
 for _ in range(warmup):
     eng.rollout()
@@ -78,9 +92,18 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--reps', type=int, default=3)
-    ap.add_argument('--log', default=os.path.join(REPO, 'profiles', 'heads_sample.log'))
+    ap.add_argument('--log', default=None, help='default: profiles/heads_sample.log, or profiles/sampling_controls.log with '
+                                                 '--temperature / --top-p')
+    ap.add_argument('--temperature', type=float, default=None, help='with --top-p: time the tempered / nucleus variants instead')
+    ap.add_argument('--top-p', type=float, default=None)
     a = ap.parse_args()
+    controls = a.temperature is not None or a.top_p is not None
+    if a.log is None:
+        a.log = os.path.join(REPO, 'profiles', 'sampling_controls.log' if controls else 'heads_sample.log')
     variants = [('parent', os.path.abspath(a.parent), 'plain'), ('this', REPO, 'plain'), ('this + lp', REPO, 'lp')]
+    if controls:
+        T, P = (1.0 if a.temperature is None else a.temperature), (1.0 if a.top_p is None else a.top_p)
+        variants = variants[:2] + [(f'this T={T:g} top_p={P:g}', REPO, f'tp:{T}:{P}'), ('this sweep', REPO, f'sweep:{T}:{P}')]
     got = {name: [] for name, _, _ in variants}
     for r in range(a.rounds):
         for name, root, mode in variants:          # alternating: one sample of every variant per round
@@ -94,6 +117,20 @@ def main():
                            min_ms=min(ms), max_ms=max(ms), samples=ms, logits_scratch=last['scratch'],
                            engine_bytes=last['engine_bytes'], peak_bytes=last['peak_bytes'])
         lines.append(json.dumps(stats[name]))
+    if controls:
+        par, new = stats['parent'], stats['this']
+        ok = par['min_ms'] <= new['median_ms'] <= par['max_ms']
+        lines.append(json.dumps(dict(figure='sampling controls', parent_ms=par['median_ms'], parent_min_ms=par['min_ms'],
+                                     parent_max_ms=par['max_ms'], this_default_ms=new['median_ms'],
+                                     **{name: stats[name]['median_ms'] for name, _, _ in variants[2:]}, gate='pass' if ok else 'FAIL')))
+        for l in lines:
+            print(l, flush=True)
+        os.makedirs(os.path.dirname(a.log), exist_ok=True)
+        with open(a.log, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+        if not ok:
+            raise SystemExit("gate failed: the default sampler's median lies outside the parent's own min .. max")
+        return
     par, new, lp = stats['parent'], stats['this'], stats['this + lp']
     ok = new['median_ms'] <= par['max_ms']
     lines.append(json.dumps(dict(figure='sampled rollout', parent_ms=par['median_ms'], this_ms=new['median_ms'],
