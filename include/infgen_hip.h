@@ -34,6 +34,7 @@
  *                            insertion disabled)
  *   infgen_point_edges, infgen_occupancy, infgen_insert_decide, infgen_insert_finalize, infgen_raw_feature_rows
  *                            the insertion sub-loop (infgen/modules/agent_decoder.py:1773-2105)
+ *   infgen_command_rows      no counterpart: a controller's per-step commands (token ids or target poses) for the replayed rows
  *
  * and, around the path:
  *
@@ -420,6 +421,18 @@ int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless, void* stre
 int infgen_decode_step(const InfgenRollout* r, int t, void* stream);
 /* steps t0 .. t1-1 back to back (one host call per rollout) */
 int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream);
+/* closed-loop sessions: the commands of decode step t for the rows flagged in r->replay_row, written into column 2 + t of the plan
+ * the step's infgen_integrate forces on them (r->teacher_token / teacher_state; refused without them or without replay_row); call it
+ * in front of infgen_decode_step(r, t).  kind 0: cmd_token [S][A_cap] ids (state valid; ids beyond the vocabulary are clamped).
+ * kind 1: cmd_pose [S][A_cap][3] = x, y, heading in the world frame - the row's box (shape [S][A_cap][3] = length, width, height)
+ * at that pose is matched against the last contour of every token of the row's type, moved by the row's stored pose with
+ * infgen_integrate's arithmetic; cost = sum of the four corner distances, first minimum wins.  With r->teacher_pos / teacher_head the
+ * stored pose becomes the commanded one, without them it is the matched token's integration.  cmd_mask (optional [S][A_cap]): 0 = no
+ * command, the row leaves the scene (state invalid); a row whose stored state is invalid stays invalid.  cmd_cost (optional
+ * [S][A_cap]): the winning cost (0 for token commands).  Rows without a flag, rows >= n_agents[s] and every other column are not
+ * touched.  The pointers that r declares const are written here (the plan belongs to the caller).  A_cap need not be a multiple of 32. */
+int infgen_command_rows(const InfgenRollout* r, int t, int kind, const int* cmd_token, const float* cmd_pose,
+                        const unsigned char* cmd_mask, const float* shape, float* cmd_cost, void* stream);
 
 /* reproducible stand-in for softmax -> topk(k) -> multinomial (agent_decoder.py:2162-2163,2194-2195): the k most
  * probable tokens, inverse-CDF over their probabilities with a caller-supplied uniform per row; 1 <= k <= min(16, n), else refused */

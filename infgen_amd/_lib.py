@@ -199,6 +199,7 @@ SYMBOLS = {
     'infgen_decode_layers': (_i, [C.POINTER(Rollout), _i, _i, _p]),
     'infgen_decode_step': (_i, [C.POINTER(Rollout), _i, _p]),
     'infgen_rollout_run': (_i, [C.POINTER(Rollout), _i, _i, _p]),
+    'infgen_command_rows': (_i, [C.POINTER(Rollout), _i, _i, _p, _p, _p, _p, _p, _p]),
     'infgen_sample_topk': (_i, [_p, _i, _i, _i, _p, _p, _p]),
     'infgen_sample_topk_logprob': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     'infgen_sample_topk_ex': (_i, [_p, _i, _i, _i, _p, C.POINTER(Sampling), _p, _p, _p, _p]),

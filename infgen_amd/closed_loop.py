@@ -1,0 +1,189 @@
+"""Closed-loop stepping sessions: a planner, a policy or a rule-based controller commands some rows of a rollout one
+decode step at a time, from what the other agents did so far, while the model generates everyone else.
+
+    ses = engine.RolloutEngine(..., replay=[mask]).session(pose='token')      # or InfGenDecoder.closed_loop(data, controlled='ego')
+    while not ses.done:
+        obs = ses.observe()                          # device tensors of the newest stored column, no synchronisation
+        ses.command(poses=controller(obs))           # or command(tokens=...); device tensors, [S, A_cap(, 3)] or ego-only [S(, 3)]
+        ses.advance()                                # the command kernel + one decode step (+ the step's insertion sub-loop)
+    out = ses.outputs()
+
+A session is log replay (``RolloutEngine(replay=...)``) whose plan is written column by column: ``advance`` launches
+``infgen_command_rows``, which turns the step's commands into the plan entries of column 2 + t on the device - a token id as it is, a
+target pose through the nearest motion token of the row's vocabulary - and then runs the decode step, whose ``k_integrate`` forces
+those entries on the flagged rows.  Nothing is read back per step (with scenario insertion on, the reads of its sub-loop remain).
+Sessions run eagerly: no HIP graph is captured or replayed for them.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict
+
+import torch
+
+from . import _lib
+
+KIND_TOKEN, KIND_POSE = 0, 1
+
+
+class ClosedLoopSession:
+    """one stepping pass over a ``RolloutEngine``'s batch; made by ``RolloutEngine.session`` / ``InfGenDecoder.closed_loop``.
+
+    ``t``: the decode step the next ``advance`` runs; ``done``: every step has run; ``cost`` [S, A_cap]: the matching cost of the
+    last pose command per row (sum of the four corner distances between the commanded box and the matched token's, metres)."""
+
+    def __init__(self, eng, pose: str = 'token', controlled=None, finish=None):
+        if pose not in ('token', 'exact'):
+            raise ValueError(f"pose must be 'token' or 'exact', not {pose!r}")
+        if eng.teacher_token is not None and eng.replay_row is None:
+            raise ValueError('an engine built with teacher= forces every row from its plan: a session needs replay= or controlled=')
+        if controlled is None and eng.replay_row is None:
+            raise ValueError("no controlled rows: build the engine with replay=[mask] or pass controlled='ego' / a bool tensor")
+        self.eng, self.pose, self._finish = eng, pose, finish
+        S, A_cap, dev = eng.S, eng.A_cap, eng.device
+        eng.prologue()                                  # (its reset() ends a session that was still open)
+        eng._bc_host = None
+        # the plan buffers: pointers of the context change only when this engine never had them (or had the other pose mode) - a
+        # graph captured for rollout() comes back with the pointers it was captured with when the session ends
+        had_rows = eng.replay_row is not None
+        self._restore = (had_rows, eng.teacher_pos is not None, eng._graph, eng._wgraph,
+                         eng.replay_row.clone() if had_rows and controlled is not None else None)
+        eng._alloc_replay(pose == 'exact')
+        if controlled is not None:
+            eng.replay_row.copy_(self._rows(controlled, torch.uint8, 'controlled'))
+        # only rows of the initial scene are controlled (rows scenario insertion appends are always generated)
+        rows = torch.arange(A_cap, device=dev)
+        eng.replay_row.mul_((rows[None, :] < eng.n_agents[:, None]).to(torch.uint8))
+        hc = eng.hc
+        eng.teacher_token[:, hc:].fill_(-1)             # the logged future is not the plan: "no token" until commanded
+        eng.teacher_state[:, hc:].zero_()
+        if eng._replay_pose is not None:
+            for buf in eng._replay_pose:
+                buf[:, hc:].zero_()
+        self._tok = torch.zeros(S, A_cap, dtype=torch.int32, device=dev)
+        self._pose = torch.zeros(S, A_cap, 3, device=dev)
+        self._mask = torch.ones(S, A_cap, dtype=torch.uint8, device=dev)
+        self.cost = torch.zeros(S, A_cap, device=dev)
+        self._kind = self._result = None
+        self.t = 0
+        self.steps = eng.cfg.num_decode_steps
+        eng._refresh_opts(groups=True)
+        eng._session = self
+
+    # ------------------------------------------------------------------ state
+    @property
+    def done(self) -> bool:
+        return self.t >= self.steps
+
+    @property
+    def open(self) -> bool:
+        return self.eng._session is self
+
+    def _check_open(self):
+        if not self.open:
+            raise RuntimeError('this session has ended (the engine was reset, reloaded or given a new session)')
+
+    def _end(self):
+        """called by the engine's ``reset``: the context's plan pointers go back to what a captured graph saw"""
+        eng = self.eng
+        eng._session = None
+        had_rows, had_pose, graph, wgraph, flags = self._restore
+        if had_rows:
+            eng._alloc_replay(had_pose)
+            eng._graph, eng._wgraph = graph, wgraph
+            if flags is not None:
+                eng.replay_row.copy_(flags)
+        else:
+            eng.replay_row.zero_()             # an engine that replayed nothing before the session generates every row again
+
+    def _rows(self, x, dtype, what, tail=()):
+        """[S, A_cap, ...] / [S, rows <= A_cap, ...] / ego-only [S, ...] / 'ego' -> a tensor of the full row layout (no host read)"""
+        eng = self.eng
+        S, A_cap, dev = eng.S, eng.A_cap, eng.device
+        if isinstance(x, str):
+            if x != 'ego':
+                raise ValueError(f"{what} must be 'ego' or a tensor, not {x!r}")
+            x = torch.ones(S, dtype=dtype, device=dev)
+        x = torch.as_tensor(x).to(dev)
+        if x.shape == (S,) + tuple(tail):                # one entry per scene: the ego's
+            full = torch.zeros((S, A_cap) + tuple(tail), dtype=dtype, device=dev)
+            full[torch.arange(S, device=dev), eng.av.long()] = x.to(dtype)
+            return full
+        if x.dim() == 2 + len(tail) and x.shape[0] == S and x.shape[1] <= A_cap and tuple(x.shape[2:]) == tuple(tail):
+            if x.shape[1] == A_cap:
+                return x.to(dtype)
+            full = torch.zeros((S, A_cap) + tuple(tail), dtype=dtype, device=dev)
+            full[:, :x.shape[1]] = x.to(dtype)
+            return full
+        raise ValueError(f'{what}: expected shape {(S, A_cap) + tuple(tail)} or {(S,) + tuple(tail)}, got {tuple(x.shape)}')
+
+    # ------------------------------------------------------------------ the loop
+    def observe(self) -> Dict[str, torch.Tensor]:
+        """the newest stored column as device tensors: ``pos`` [S, A_cap, 2], ``head``, ``state`` (0 = not in the scene), ``token``,
+        ``type`` [S, A_cap], ``shape`` [S, A_cap, 3] (length, width, height), ``n_agents`` / ``ego_index`` [S], ``controlled``
+        [S, A_cap] bool and ``column`` (int).  Views of the engine's buffers wherever possible: no copy, no synchronisation - and
+        overwritten by later steps, a reset or a reload (clone what has to last)."""
+        self._check_open()
+        eng, c = self.eng, self.eng.hc - 1 + self.t
+        return dict(pos=eng.pos[:, c], head=eng.head[:, c], state=eng.state[:, c], token=eng.token[:, c], type=eng.atype,
+                    shape=eng._shape10, n_agents=eng.n_agents, ego_index=eng.av, controlled=eng.replay_row.bool(), column=c)
+
+    def command(self, tokens=None, poses=None, mask=None):
+        """the controlled rows' command for step ``t``: ``tokens`` (motion-token ids, int) or ``poses`` (x, y, heading in the world
+        frame), as [S, A_cap] / [S, A_cap, 3] tensors (entries of uncontrolled rows are ignored) or [S] / [S, 3] for the ego alone;
+        ``mask`` (same layouts, optional): False = the row leaves the scene at this step and stays out.  Device tensors are taken as
+        they are (stream-ordered, no synchronisation); a later ``command`` before ``advance`` replaces this one."""
+        self._check_open()
+        if self.done:
+            raise RuntimeError('the session has run its last step')
+        if (tokens is None) == (poses is None):
+            raise ValueError('give tokens= or poses=, one of them')
+        if poses is not None and self.eng._shape10 is None:
+            raise ValueError('a pose command needs the rows\' shapes: this engine has no shape array')
+        if tokens is not None:
+            self._tok.copy_(self._rows(tokens, torch.int32, 'tokens'))
+            self._kind = KIND_TOKEN
+        else:
+            self._pose.copy_(self._rows(poses, torch.float32, 'poses', tail=(3,)))
+            self._kind = KIND_POSE
+        if mask is None:
+            self._mask.fill_(1)
+        else:
+            self._mask.copy_(self._rows(mask, torch.uint8, 'mask'))
+
+    def advance(self):
+        """the command kernel, then decode step ``t`` (with its insertion sub-loop when the engine inserts agents)"""
+        self._check_open()
+        if self.done:
+            raise RuntimeError('the session has run its last step')
+        if self._kind is None:
+            raise RuntimeError(f'no command for step {self.t}: call command() before advance()')
+        eng, P = self.eng, _lib.ptr
+        _lib.check(eng.lib.infgen_command_rows(C.byref(eng._ctx), self.t, self._kind, P(self._tok), P(self._pose), P(self._mask),
+                                               P(eng._shape10), P(self.cost), eng.ops.stream), 'infgen_command_rows')
+        for _ in eng._step_gen(self.t):         # (the generator waits for each of the insertion sub-loop's events itself)
+            pass
+        self._kind = None
+        self.t += 1
+
+    # ------------------------------------------------------------------ results
+    def _check_done(self):
+        self._check_open()
+        if not self.done:
+            raise RuntimeError(f'the session is at step {self.t} of {self.steps}: outputs exist after the last step')
+
+    def outputs(self):
+        """after the last step: what the entry that made the session returns for a rollout - the engine's ``outputs()``, or the
+        dict(s) of ``InfGenDecoder.inference`` for a session made by ``closed_loop``"""
+        if self._result is None:
+            self._check_done()
+            self._result = self._finish() if self._finish is not None else self.eng.outputs()
+        return self._result
+
+    def outputs_device(self, detach: bool = False):
+        self._check_done()
+        return self.eng.outputs_device(detach=detach)
+
+    def outputs_batch(self):
+        self._check_done()
+        return self.eng.outputs_batch()

@@ -1353,6 +1353,36 @@ extern "C" int infgen_integrate(const InfgenRollout* r, int t, void* stream) {
   return integrate_impl(r, t, stream, nullptr, false, false);
 }
 
+// ---- closed-loop sessions: the commands of decode step t -> column 2 + t of the context's plan arrays, in front of the step
+static void launch_command_rows(const CommandRowsArgs& a, void* stream) {
+  hipLaunchKernelGGL(k_command_rows, dim3(a.A_cap, a.S), dim3(256), 0, (hipStream_t)stream, a);
+}
+extern "C" int infgen_command_rows(const InfgenRollout* r, int t, int kind, const int* cmd_token, const float* cmd_pose,
+                                   const unsigned char* cmd_mask, const float* shape, float* cmd_cost, void* stream) {
+  const char* me = "infgen_command_rows";
+  if (!r) return fail(me, "null context");
+  if (r->S <= 0 || r->S > 65535 || r->A_cap <= 0 || r->A_cap > 1024) return fail(me, "S must be in 1..65535 and A_cap in 1..1024");
+  if (!(r->teacher_token && r->teacher_state && r->replay_row))
+    return fail(me, "the context has no plan to write: teacher_token, teacher_state and replay_row are needed (a replay context)");
+  if ((r->teacher_pos != nullptr) != (r->teacher_head != nullptr)) return fail(me, "teacher_pos and teacher_head come together");
+  if (!(r->n_agents && r->state && r->pos && r->head && r->type && r->vocab)) return fail(me, "null scene array");
+  if (r->token_size <= 0) return fail(me, "token_size must be positive");
+  const int c = 1 + t;
+  if (t < 0 || c + 1 > r->T - 1) return fail(me, "step beyond the column range");
+  if (kind != 0 && kind != 1) return fail(me, "kind must be 0 (token ids) or 1 (target poses)");
+  if (kind == 0 && !cmd_token) return fail(me, "a token command needs cmd_token [S][A_cap]");
+  if (kind == 1 && !(cmd_pose && shape)) return fail(me, "a pose command needs cmd_pose [S][A_cap][3] and the shape array [S][A_cap][3]");
+  CommandRowsArgs a;
+  a.S = r->S; a.A_cap = r->A_cap; a.T = r->T; a.c = c; a.kind = kind; a.token_size = r->token_size;
+  a.n_agents = r->n_agents; a.replay_row = r->replay_row; a.state = r->state; a.pos = r->pos; a.head = r->head; a.type = r->type;
+  a.vocab = r->vocab; a.shape = shape; a.cmd_token = cmd_token; a.cmd_pose = cmd_pose; a.cmd_mask = cmd_mask;
+  a.teacher_token = const_cast<int*>(r->teacher_token); a.teacher_state = const_cast<int*>(r->teacher_state);
+  a.teacher_pos = const_cast<float*>(r->teacher_pos); a.teacher_head = const_cast<float*>(r->teacher_head);
+  a.cmd_cost = cmd_cost;
+  launch_command_rows(a, stream);
+  return check_launch(me);
+}
+
 // MLPEmbedding pack (first Linear K0 -> 128): P(K0p,128) b ln_g ln_b | P(128,128) b ln_g ln_b | P(128,128) b
 static inline int mlpemb_off2(int K0p) { return K0p * 128 + 3 * 128; }
 static inline int mlpemb_off3(int K0p) { return mlpemb_off2(K0p) + 16384 + 3 * 128; }

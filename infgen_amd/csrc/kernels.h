@@ -271,6 +271,27 @@ struct MatchTokensArgs {
   float* token_contour;              // [A][T / shift][4][2]
 };
 
+// k_command_rows (token_kernels.hip): a closed-loop session's commands of one decode step -> column c + 1 of the plan arrays the
+// flagged rows follow (IntegrateArgs.teacher_*); one workgroup per (scene, row), the ones without a flag leave at once
+struct CommandRowsArgs {
+  int S, A_cap, T, c;                // writes column c + 1 (k_integrate's c / n)
+  int kind;                          // 0: token ids, 1: target poses matched against the vocabulary
+  int token_size;
+  const int* n_agents;               // [S]
+  const unsigned char* replay_row;   // [S][A_cap]
+  const int* state;                  // [S][T][A_cap] stored states (column c is read)
+  const float* pos; const float* head;   // [S][T][A_cap](x2) stored poses (column c is read)
+  const int* type;                   // [S][A_cap]
+  const float* vocab;                // [3][token_size][6][4][2]
+  const float* shape;                // [S][A_cap][3] = (length, width, height); kind 1 only
+  const int* cmd_token;              // [S][A_cap] (kind 0)
+  const float* cmd_pose;             // [S][A_cap][3] = x, y, heading in the world frame (kind 1)
+  const unsigned char* cmd_mask;     // optional [S][A_cap]: 0 = the row leaves the scene at this step
+  int* teacher_token; int* teacher_state;      // [S][T][A_cap]
+  float* teacher_pos; float* teacher_head;     // optional: the commanded pose is stored too (kind 1)
+  float* cmd_cost;                   // optional [S][A_cap]: the winning cost of a pose command (0 for a token command)
+};
+
 // k_match_map_tokens (token_kernels.hip): InfGen.match_token_map, one wave per polyline piece
 struct MatchMapArgs {
   const float* traj_pos;             // [P][3][2]
@@ -585,6 +606,7 @@ template <int TERMS> __global__ void k_map_head_h(MapHeadArgs a);     // mlp_h.h
 template <int TERMS> __global__ void k_map_head_h_b16(MapHeadArgs a);
 __global__ void k_map_topk(MapHeadArgs a);
 __global__ void k_match_map_tokens(MatchMapArgs a);
+__global__ void k_command_rows(CommandRowsArgs a);
 __global__ void k_tokenize_prep(TokenizeArgs a);
 __global__ void k_fetch_enterings(EnteringsArgs a);
 __global__ void k_pt_grid_cells(EnteringsArgs a);

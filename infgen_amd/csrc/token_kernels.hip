@@ -127,6 +127,103 @@ __global__ __launch_bounds__(MT_THREADS) void k_match_tokens(MatchTokensArgs a) 
 }
 
 // ------------------------------------------------------------------------------------------
+// k_command_rows: the commands a closed-loop session gives its controlled rows at one decode step -> column n = c + 1 of the plan
+// arrays k_integrate forces on the flagged rows (teacher_token / teacher_state [/ teacher_pos / teacher_head]).  Launched in front
+// of the step's kernels; one workgroup per (scene, row), the rows without a flag (and the rows beyond n_agents) leave at once.
+//   token command  the id as given (ids beyond the vocabulary are clamped to its last entry), state valid
+//   pose command   the commanded box (box_contour above: the row's own width / length) against the LAST contour of every token of the
+//                  row's type, moved by the row's stored pose of column c with k_integrate's arithmetic - (x cos + y (-sin)) + bx
+//                  with cosf / sinf of the stored heading - so a token is judged on the pose k_integrate will make of it; sum of the
+//                  four corner distances sqrtf(dx dx + dy dy), first minimum.  256 threads stride over token_size tokens; the arg-min
+//                  as in k_match_tokens (shuffles inside a wave, LDS across the four waves).
+//   no command (cmd_mask 0) or a row that is invalid at column c: state invalid, token -1 - a row that left stays out
+// With teacher_pos / teacher_head the stored pose of column n is the plan's: the commanded pose (pose command) or the token's own
+// integration (token command); without them k_integrate stores the token's integration itself.
+// ------------------------------------------------------------------------------------------
+constexpr int CR_THREADS = 256;
+constexpr int CR_INVALID = 0, CR_VALID = 1;      // valid_state_type ids (edge_kernels.hip)
+
+__global__ __launch_bounds__(CR_THREADS) void k_command_rows(CommandRowsArgs a) {
+  __shared__ float s_val[CR_THREADS / 64];
+  __shared__ int s_idx[CR_THREADS / 64];
+  const int r = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
+  const int row = s * a.A_cap + r;
+  if (r >= a.n_agents[s] || a.replay_row[row] == 0) return;          // (uniform over the workgroup)
+  const size_t ic = ((size_t)s * a.T + a.c) * a.A_cap + r, in_ = ic + a.A_cap;
+  if (a.state[ic] == CR_INVALID || (a.cmd_mask && a.cmd_mask[row] == 0)) {
+    if (t == 0) {
+      a.teacher_token[in_] = -1; a.teacher_state[in_] = CR_INVALID;
+      if (a.teacher_pos) { a.teacher_pos[2 * in_] = 0.f; a.teacher_pos[2 * in_ + 1] = 0.f; a.teacher_head[in_] = 0.f; }
+      if (a.cmd_cost) a.cmd_cost[row] = 0.f;
+    }
+    return;
+  }
+  const float th = a.head[ic];
+  const float cs = cosf(th), sn = sinf(th);
+  const float bx = a.pos[2 * ic], by = a.pos[2 * ic + 1];
+  const float* V = a.vocab + (size_t)a.type[row] * a.token_size * 48 + 40;      // the last (k == 5) contour of token 0
+  if (a.kind == 0) {
+    if (t != 0) return;
+    int tok = a.cmd_token[row];
+    if (tok >= a.token_size) tok = a.token_size - 1;
+    a.teacher_token[in_] = tok; a.teacher_state[in_] = CR_VALID;
+    if (a.cmd_cost) a.cmd_cost[row] = 0.f;
+    if (a.teacher_pos) {                         // the token's integration, as k_integrate computes it
+      const float* ct = V + (size_t)(tok < 0 ? 0 : tok) * 48;
+      float cx[4], cy[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float x = ct[2 * q], y = ct[2 * q + 1];
+        cx[q] = (x * cs + y * (-sn)) + bx;
+        cy[q] = (x * sn + y * cs) + by;
+      }
+      a.teacher_pos[2 * in_] = (((cx[0] + cx[1]) + cx[2]) + cx[3]) / 4.0f;
+      a.teacher_pos[2 * in_ + 1] = (((cy[0] + cy[1]) + cy[2]) + cy[3]) / 4.0f;
+      a.teacher_head[in_] = atan2f(cy[0] - cy[3], cx[0] - cx[3]);
+    }
+    return;
+  }
+  const float px = a.cmd_pose[3 * (size_t)row], py = a.cmd_pose[3 * (size_t)row + 1], ph = a.cmd_pose[3 * (size_t)row + 2];
+  const Contour cur = box_contour(px, py, ph, a.shape[3 * (size_t)row + 1], a.shape[3 * (size_t)row]);
+  float best = INFINITY;
+  int bidx = 0x7fffffff;
+  for (int k = t; k < a.token_size; k += CR_THREADS) {
+    const float4 p0 = *reinterpret_cast<const float4*>(V + (size_t)k * 48);
+    const float4 p1 = *reinterpret_cast<const float4*>(V + (size_t)k * 48 + 4);
+    const float tx[4] = {p0.x, p0.z, p1.x, p1.z}, ty[4] = {p0.y, p0.w, p1.y, p1.w};
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float wx = (tx[q] * cs + ty[q] * (-sn)) + bx;
+      const float wy = (tx[q] * sn + ty[q] * cs) + by;
+      const float dx = wx - cur.x[q], dy = wy - cur.y[q];
+      const float d = sqrtf(dx * dx + dy * dy);
+      sum = (q == 0) ? d : sum + d;
+    }
+    if (sum < best) { best = sum; bidx = k; }         // ascending k per thread: the first minimum stays
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float v2 = __shfl_xor(best, off, 64);
+    const int i2 = __shfl_xor(bidx, off, 64);
+    if (v2 < best || (v2 == best && i2 < bidx)) { best = v2; bidx = i2; }
+  }
+  if ((t & 63) == 0) { s_val[t >> 6] = best; s_idx[t >> 6] = bidx; }
+  __syncthreads();
+  if (t != 0) return;
+#pragma unroll
+  for (int w = 1; w < CR_THREADS / 64; ++w) {
+    const float v2 = s_val[w];
+    const int i2 = s_idx[w];
+    if (v2 < best || (v2 == best && i2 < bidx)) { best = v2; bidx = i2; }
+  }
+  if (bidx >= a.token_size) bidx = 0;             // a pose that is not a number matches nothing: token 0, the cost stays infinite
+  a.teacher_token[in_] = bidx; a.teacher_state[in_] = CR_VALID;
+  if (a.teacher_pos) { a.teacher_pos[2 * in_] = px; a.teacher_pos[2 * in_ + 1] = py; a.teacher_head[in_] = ph; }
+  if (a.cmd_cost) a.cmd_cost[row] = best;
+}
+
+// ------------------------------------------------------------------------------------------
 // k_match_map_tokens: InfGen.match_token_map's matching core (reference infgen/model/infgen.py:918-936): a
 // three-point polyline piece, moved to its own frame, against the sample points of the n_token map tokens; sum of
 // squared distances, first minimum.  One wave per piece, tokens spread over the lanes.

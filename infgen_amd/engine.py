@@ -727,6 +727,7 @@ class RolloutEngine:
             if tp is not None:
                 self.teacher_pos, self.teacher_head = t(tp), t(th)
         self.replay_row = None                 # [S][A_cap] uint8 once a replay was asked for (InfgenRollout.replay_row)
+        self._session = None                   # the closed-loop session stepping this engine (``session()``; ``reset`` ends it)
         self._replay_pose = None               # the pose buffers of a replay engine (teacher_pos / teacher_head point at them or are None)
         if replay is not None and teacher is not None:
             raise ValueError('teacher= forces every row; replay= forces the flagged rows: give one of them')
@@ -926,6 +927,11 @@ class RolloutEngine:
             assert insert_uniforms is not None, 'cell sampling needs caller-supplied uniforms [steps][10][S]'
             self._insert_u.copy_(torch.from_numpy(np.ascontiguousarray(insert_uniforms, dtype=np.float32)))
 
+    def _end_session(self):
+        """a closed-loop session ends before a new batch (and its plan) is loaded: its end restores the plan pointers it found"""
+        if self._session is not None:
+            self._session._end()
+
     def _invalidate(self):
         """what a new batch in the buffers outdates"""
         self._init = None                  # reset() snapshots the new initial state
@@ -980,6 +986,7 @@ class RolloutEngine:
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
+        self._end_session()
         self.scenes = scenes
         self._hosts_light = False
         hosts, staged = self._setup_scenes(scenes)
@@ -1015,6 +1022,7 @@ class RolloutEngine:
         plan is the stacked logged future) or (mask, dict of stacked token_idx / state_idx[, token_pos, token_heading]) - copied
         into the plan buffers on the device before the future columns are zeroed."""
         assert self.fits_device(k), 'batch does not fit this engine (RolloutEngine.fits_device)'
+        self._end_session()
         if not self._setup_device(k, replay):
             return False
         self.scenes = scenes
@@ -1087,6 +1095,7 @@ class RolloutEngine:
         if layout is None:
             layout = read_batch_layout(batch, self.T, self.hc, self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
+        self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
@@ -1206,7 +1215,8 @@ class RolloutEngine:
 
     # ------------------------------------------------------------------ prologue (once per rollout)
     def reset(self):
-        """restore the scene state to the rollout's initial condition (device-to-device copies)"""
+        """restore the scene state to the rollout's initial condition (device-to-device copies); ends a closed-loop session"""
+        self._end_session()
         if self._init is None:
             self._init = {k: getattr(self, k).clone() for k in self._STATE}
         else:
@@ -1373,6 +1383,7 @@ class RolloutEngine:
     def rollout(self):
         """one full pass of the hot path over the batch: prologue + every decode step"""
         self._bc_host = None
+        self._end_session()
         if (self._graph_all and not self.insertion and self._x_pt_override is None and self._mg_checked and self._init is not None
                 and self._ctx is not None and not _lib.prof_active()):
             self._rollout_graph()                # (the first rollout of a batch runs eagerly: buffers, tables, edge capacities)
@@ -1656,27 +1667,44 @@ class RolloutEngine:
                 return
             _lib.check(self.lib.infgen_rollout_run(C.byref(self._ctx), t0, t1, self.ops.stream), 'infgen_rollout_run')
             return
+        for t in range(t0, t1):
+            yield from self._step_gen(t)
+
+    def _step_gen(self, t: int):
+        """decode step t as the host sequences it (scenario insertion on, or a closed-loop session stepping an engine without
+        it): the row-group refresh, the step's insertion sub-loop, the motion stage.  A generator like ``run_gen``, which drives it
+        for every step; ``ClosedLoopSession.advance`` drives it for one.  ``_refresh_opts(groups=True)`` comes first (once)."""
+        if not self.insertion:
+            self.step(t)
+            return
         lib, I = self.lib, self.ins
         use_groups = bool(self._ctx.opts.row_groups)
-        for t in range(t0, t1):
-            if use_groups:
-                _lib.check(lib.infgen_active_row_groups(_lib.ptr(self.n_agents), self.S, self.A_cap, 10,
-                                                        _lib.ptr(I['groups']), _lib.ptr(I['n_groups']), self.ops.stream),
-                           'infgen_active_row_groups')
-            if t > 0:
-                yield from self._insert_step(t)
-            self._decoded_rows.add_(self.n_agents.sum())       # A_t: rows decoded at this step, incl. the inserted ones
-            tight = use_groups and self.flags['row_groups_tight']
-            if tight:
-                # the step's insertions are done: the motion stage runs on exactly the rows that hold agents now - the ten rows of
-                # head-room the sub-loop's lists carry put one more 16-row group per scene into 60 % of the node / edge launches
-                _lib.check(lib.infgen_active_row_groups(_lib.ptr(self.n_agents), self.S, self.A_cap, 0,
-                                                        _lib.ptr(I['groups']), _lib.ptr(I['n_groups']), self.ops.stream),
-                           'infgen_active_row_groups')
-                self._ctx.opts.row_group_margin = 0
-            self.step(t)
-            if tight:
-                self._ctx.opts.row_group_margin = 10
+        if use_groups:
+            _lib.check(lib.infgen_active_row_groups(_lib.ptr(self.n_agents), self.S, self.A_cap, 10,
+                                                    _lib.ptr(I['groups']), _lib.ptr(I['n_groups']), self.ops.stream),
+                       'infgen_active_row_groups')
+        if t > 0:
+            yield from self._insert_step(t)
+        self._decoded_rows.add_(self.n_agents.sum())       # A_t: rows decoded at this step, incl. the inserted ones (SURVEY 8d)
+        tight = use_groups and self.flags['row_groups_tight']
+        if tight:
+            # the step's insertions are done: the motion stage runs on exactly the rows that hold agents now - the ten rows of
+            # head-room the sub-loop's lists carry put one more 16-row group per scene into 60 % of the node / edge launches
+            _lib.check(lib.infgen_active_row_groups(_lib.ptr(self.n_agents), self.S, self.A_cap, 0,
+                                                    _lib.ptr(I['groups']), _lib.ptr(I['n_groups']), self.ops.stream),
+                       'infgen_active_row_groups')
+            self._ctx.opts.row_group_margin = 0
+        self.step(t)
+        if tight:
+            self._ctx.opts.row_group_margin = 10
+
+    def session(self, pose: str = 'token', controlled=None):
+        """a closed-loop stepping session on this engine (infgen_amd/closed_loop.py): the flagged rows take a command
+        per decode step - a token id or a target pose, from device tensors - instead of a plan known up front.  ``controlled``:
+        None (the rows ``replay=`` flagged), 'ego' or a bool tensor [S, rows]; ``pose``: 'token' (the stored pose is the
+        commanded / matched token's integration) or 'exact' (the commanded pose itself is stored)."""
+        from .closed_loop import ClosedLoopSession
+        return ClosedLoopSession(self, pose=pose, controlled=controlled)
 
     def _run_graph(self, t0, t1):
         """the decode steps as a HIP-graph replay.  Replays launched into the LEGACY DEFAULT stream fault now and then on this

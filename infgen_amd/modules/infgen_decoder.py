@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, logprob, scene_setup
+from ..closed_loop import ClosedLoopSession
 from ..engine import InsertionHeadroomError, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -422,8 +423,23 @@ class InfGenDecoder(nn.Module):
         live = dict(sample_temperature=temp, sample_top_p=float(self.sample_top_p))
         return dict(fixed, **live), live, tuple(fixed.values())
 
-    def _run(self, data, x_pt=None, map_only=False, batch: Optional[Sequence] = None, sample_uniforms=None,
-             batch_seed_outputs: bool = False, copies: int = 1, replay=None, replay_plan=None, sample_temperature=None):
+    @staticmethod
+    def _drive(gen):
+        """runs ``_run_gen`` / ``_run_graphs_gen`` / ``_inference_gen`` to the end -> its result (without ``session`` they never yield)"""
+        try:
+            next(gen)
+        except StopIteration as e:
+            return e.value
+        raise RuntimeError('the run yielded an engine: only closed_loop() asks for a session')
+
+    def _run(self, *args, **kw):
+        return self._drive(self._run_gen(*args, **kw))
+
+    def _run_gen(self, data, x_pt=None, map_only=False, batch: Optional[Sequence] = None, sample_uniforms=None,
+                 batch_seed_outputs: bool = False, copies: int = 1, replay=None, replay_plan=None, sample_temperature=None,
+                 session: bool = False):
+        """``_run`` as a generator: with ``session`` it yields the engine where ``rollout()`` would run - the caller steps a
+        closed-loop session on it (``closed_loop``) and resumes the generator for the epilogue - and otherwise never yields"""
         ae = self.agent_encoder
         datas = list(batch) if batch is not None else [data]
         copies = int(copies)
@@ -501,6 +517,9 @@ class InfGenDecoder(nn.Module):
         # the reference's agent arrays grow without bound; here rows are pre-allocated per scene.  If the inserted agents
         # outgrow them the (deterministic) rollout is repeated with twice the rows instead of dropping insertions
         while True:
+            if session:
+                yield eng
+                break
             try:
                 eng.rollout()
                 break
@@ -629,8 +648,11 @@ class InfGenDecoder(nn.Module):
             return np.asarray(t)
         return self._cached('_host_consts', [t], lambda: t.detach().cpu().numpy())
 
-    def _run_graphs(self, data, sample_uniforms=None, copies: int = 1, mutate: bool = True, replay=None,
-                    replay_plan=None, sample_temperature=None) -> List[Dict]:
+    def _run_graphs(self, *args, **kw) -> List[Dict]:
+        return self._drive(self._run_graphs_gen(*args, **kw))
+
+    def _run_graphs_gen(self, data, sample_uniforms=None, copies: int = 1, mutate: bool = True, replay=None,
+                        replay_plan=None, sample_temperature=None, session: bool = False):
         """a ragged multi-graph Batch of device tensors through RolloutEngine.reload_batch (the ingest kernel: filter, pad and
         set up every scene on the device) and the batched epilogue (outputs_batch: infgen_pack_rows).  One device -> host copy
         before the first launch (the offsets and av_index; the token vocabularies the tables are keyed by ride along unless the
@@ -725,6 +747,9 @@ class InfGenDecoder(nn.Module):
                 self._engines.pop(next(iter(self._engines)))
             self._engines[ekey] = eng
         while True:
+            if session:                  # (closed_loop: see _run_gen)
+                yield eng
+                break
             try:
                 eng.rollout()
                 break
@@ -872,15 +897,38 @@ class InfGenDecoder(nn.Module):
         ``pred_traj`` / ``pred_head`` the plan's tokens integrated from the plan's poses."""
         if self.map_only():
             return self._map_model(data)
+        return self._drive(self._inference_gen(data, sample_uniforms, replay, replay_plan))
+
+    def _inference_gen(self, data, sample_uniforms=None, replay=None, replay_plan=None, session: bool = False):
         if num_graphs(data) > 1:
-            return self._run_graphs(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan)[0]
-        r = self._run(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan)
+            rs = yield from self._run_graphs_gen(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan,
+                                                 session=session)
+            return rs[0]
+        r = yield from self._run_gen(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan, session=session)
         x_pt = r.pop('x_pt')
         map_enc = {'x_pt': x_pt, 'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=x_pt.device),
                    'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=x_pt.device),
                    'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=x_pt.device),
                    'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=x_pt.device)}
         return r.merged(first=map_enc, last={k: data[k] for k in self.data_keys if k in data})
+
+    @torch.no_grad()
+    def closed_loop(self, data, controlled='ego', pose: str = 'token'):
+        """a closed-loop stepping session over ``data`` (one graph or a Batch; infgen_amd/closed_loop.py): the
+        ``controlled`` rows - 'ego' or a bool tensor / list of tensors as ``inference(replay=...)`` takes - are commanded step by
+        step (``ses.observe()``, ``ses.command(tokens= | poses=)``, ``ses.advance()``), every other agent is generated around
+        them.  ``pose``: 'token' stores the commanded / matched token's integration, 'exact' the commanded pose itself.  After
+        the last step ``ses.outputs()`` is the dict ``inference(data, replay=controlled, replay_plan=<the commands>)`` returns,
+        ``replay_mask`` included.  The engine is the cached one of ``inference``: another call on this module ends the session."""
+        if self.map_only():
+            raise ValueError('the map-pretraining model decodes no agents: nothing to control')
+        gen = self._inference_gen(data, None, controlled, None, session=True)
+        eng = next(gen)
+
+        def finish():
+            with torch.no_grad():
+                return self._drive(gen)
+        return ClosedLoopSession(eng, pose=pose, finish=finish)
 
     @torch.no_grad()
     def inference_no_map(self, data, map_enc) -> Dict[str, torch.Tensor]:

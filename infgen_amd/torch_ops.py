@@ -23,6 +23,7 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
 
     torch.ops.infgen_hip.integrate_tokenise(token, state, type, pos, head, n_agents, ego, vocab, grid) -> pos', head', pred_traj, pred_head, grid, state'
     torch.ops.infgen_hip.decode_step(ctx_bytes, t, pos, head, state, token, grid, x, next_token, next_state) -> next_token, next_state
+    torch.ops.infgen_hip.command_rows(ctx_bytes, t, teacher_token, teacher_state, cmd_token?, cmd_pose?, cmd_mask?, shape?) -> cost (S, A_cap)
 
 (``decode_step`` works on the persistent state block ``InfgenRollout`` of include/infgen_hip.h, which ``RolloutEngine.ctx_tensor()``
 hands out as bytes; whole rollouts stay a C-ABI call, ``infgen_rollout_run``, driven by infgen_amd/engine.py).  ``register_fake`` gives every op a shape function, so they trace under
@@ -386,6 +387,46 @@ def decode_step(ctx: torch.Tensor, t: int, pos: torch.Tensor, head: torch.Tensor
 @decode_step.register_fake
 def _(ctx, t, pos, head, state, token, grid, x, next_token, next_state):
     return torch.empty_like(next_token), torch.empty_like(next_state)
+
+
+@torch.library.custom_op('infgen_hip::command_rows', mutates_args=('teacher_token', 'teacher_state'))
+def command_rows(ctx: torch.Tensor, t: int, teacher_token: torch.Tensor, teacher_state: torch.Tensor,
+                 cmd_token: Optional[torch.Tensor] = None, cmd_pose: Optional[torch.Tensor] = None,
+                 cmd_mask: Optional[torch.Tensor] = None, shape: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a closed-loop session's commands of decode step ``t`` -> column 2 + t of the plan the flagged rows of the state block
+    follow (``infgen_command_rows``; call it in front of ``decode_step(ctx, t, ...)``).  ``ctx`` as in ``decode_step``;
+    ``teacher_token`` / ``teacher_state`` [S][T][A_cap]: the block's plan arrays (declared mutated; with pose arrays in the block
+    the commanded pose is written there too).  One of ``cmd_token`` [S][A_cap] int (token ids) and ``cmd_pose`` [S][A_cap][3]
+    (x, y, heading; needs ``shape`` [S][A_cap][3] = length, width, height: the nearest motion token of the row's vocabulary is
+    matched on the device); ``cmd_mask`` [S][A_cap] (optional): 0 = the row leaves the scene.  Returns the matching cost [S][A_cap]
+    (0 for token commands and for rows that are not commanded).  No host read."""
+    ops = _ops(teacher_token.device)
+    dev = teacher_token.device
+    blk = _lib.Rollout.from_buffer_copy(ctx.numpy().tobytes())
+    for name, ten in (('teacher_token', teacher_token), ('teacher_state', teacher_state)):
+        if int(getattr(blk, name) or 0) != ten.data_ptr():
+            raise _lib.InfgenHipError(f'command_rows: `{name}` is not the array the state block points to')
+    if (cmd_token is None) == (cmd_pose is None):
+        raise ValueError('command_rows takes cmd_token or cmd_pose, one of them')
+    S, A_cap = int(blk.S), int(blk.A_cap)
+
+    def arr(x, dtype, tail=()):
+        if x is None:
+            return None
+        if tuple(x.shape) != (S, A_cap) + tail:
+            raise ValueError(f'command_rows: expected shape {(S, A_cap) + tail}, got {tuple(x.shape)}')
+        return x.to(dev, dtype).contiguous()
+    tok, pose = arr(cmd_token, torch.int32), arr(cmd_pose, torch.float32, (3,))
+    msk, shp = arr(cmd_mask, torch.uint8), arr(shape, torch.float32, (3,))
+    cost = torch.zeros(S, A_cap, device=dev)
+    _lib.check(ops.lib.infgen_command_rows(C.byref(blk), int(t), 0 if tok is not None else 1, _lib.ptr(tok), _lib.ptr(pose),
+                                           _lib.ptr(msk), _lib.ptr(shp), _lib.ptr(cost), ops.stream), 'infgen_command_rows')
+    return cost
+
+
+@command_rows.register_fake
+def _(ctx, t, teacher_token, teacher_state, cmd_token=None, cmd_pose=None, cmd_mask=None, shape=None):
+    return teacher_token.new_empty(teacher_token.shape[0], teacher_token.shape[2], dtype=torch.float32)
 
 
 @torch.library.custom_op('infgen_hip::bundle_scores', mutates_args=())
