@@ -6,6 +6,7 @@ libinfgen_hip.so; ``inference_batch`` is the throughput entry (many scenes in lo
 """
 from __future__ import annotations
 
+import functools
 import os
 import weakref
 from typing import Dict, List, Mapping, Optional, Sequence
@@ -16,7 +17,7 @@ import torch.nn as nn
 
 from .. import _lib, logprob, scene_setup
 from ..closed_loop import ClosedLoopSession
-from ..engine import InsertionHeadroomError, PackedWeights, RolloutEngine, read_batch_layout
+from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
 from .attr_tokenizer import Attr_Tokenizer
@@ -250,6 +251,68 @@ class _LazyScenes:
         return iter(self._get())
 
 
+# ---------------------------------------------------------------------- the rollout driver's steps (InfGenDecoder._run_gen /
+# _run_graphs_gen): plain functions over an engine dict and callables, so that they run without weights or a device
+def _draw_uniforms(cfg, k: int, ik: int, S: int, ucols: int, sample_uniforms=None):
+    """the uniforms of a stochastic decode from torch's RNG -> (sample_uniforms [steps][S][ucols] or the caller's, insert_uniforms
+    [steps][10][S] or None).  Seeded callers depend on the stream: the motion draw comes first, each only under its condition."""
+    if sample_uniforms is not None:
+        sample_uniforms = _np(sample_uniforms)
+    elif k > 1:
+        # stochastic decode like the reference's default (top-k multinomial): one uniform per decode step and agent row - with
+        # insertion on for every row a scene can ever hold (a row without its own uniform would be decoded greedily)
+        sample_uniforms = torch.rand(cfg.num_decode_steps, S, ucols).numpy()
+    insert_uniforms = None
+    if ik > 1 and not cfg.disable_insertion and cfg.use_grid_token:
+        # the cell of an inserted agent from the insert_beam_size most probable ones (agent_decoder.py:1900-1904)
+        insert_uniforms = torch.rand(cfg.num_decode_steps, 10, S).numpy()
+    return sample_uniforms, insert_uniforms
+
+
+def _engine_key(*, graphs: bool, scenes: int, tables: bytes, disable_insertion: bool, steps: int, sample_k: int, insert_k: int,
+                debug: bool, copies: int, replay: bool, token_logprob: bool, sample_logprob: bool, sampling: tuple,
+                single: bool, map_only: bool, own_map: bool, seed_outputs: bool) -> tuple:
+    """everything an engine is built from that its reload* cannot change -> its key in ``InfGenDecoder._engines``
+    (``InfGenDecoder._make_engine`` reads the same facts: an engine argument is named here or it is reloaded).  A Batch's
+    engines (set up by the ingest kernel) are apart from the list path's: 'graphs' leads their key."""
+    return ('graphs' if graphs else 'scenes', scenes, tables, disable_insertion, steps, sample_k, insert_k, debug, copies, replay,
+            token_logprob, sample_logprob, sampling, single, map_only, own_map, seed_outputs)
+
+
+def _cached_engine(engines: Dict, key, attempts, make_engine):
+    """one engine per batch layout is kept across calls: a second call of the same shape re-uploads the scene arrays into the
+    first call's device buffers instead of building (and allocating) an engine again.  ``attempts``: (fits, reload) pairs over
+    the held engine in order of preference; a reload that returns False has changed nothing and the next pair is tried.
+    -> the reloaded engine, else a new one (two are held: the oldest goes)"""
+    eng = engines.get(key)
+    if eng is not None:
+        for fits, reload in attempts:
+            if fits(eng) and reload(eng) is not False:
+                return eng
+    eng = make_engine()
+    if len(engines) >= 2:
+        engines.pop(next(iter(engines)))
+    engines[key] = eng
+    return eng
+
+
+def _rollout_or_yield(engines: Dict, key, eng, make_engine, amax: int, limit: int, session: bool = False):
+    """generator -> the engine after its rollout.  The reference's agent arrays grow without bound; here rows are pre-allocated
+    per scene: if the inserted agents outgrow them the (deterministic) rollout is repeated with twice the rows (at most ``limit``,
+    ``amax`` of them the scenes' own) instead of dropping insertions.  ``session``: yields the engine where ``rollout()`` would
+    run - the caller steps a closed-loop session on it and resumes the generator for the epilogue - and otherwise never yields."""
+    while not session:
+        try:
+            eng.rollout()
+            return eng
+        except InsertionHeadroomError:
+            if eng.A_cap >= limit:
+                raise
+            eng = engines[key] = make_engine(headroom=min(2 * eng.A_cap, limit) - amax)
+    yield eng
+    return eng
+
+
 class InfGenDecoder(nn.Module):
 
     def __init__(self, decoder_type: str, dataset: str, input_dim: int, hidden_dim: int, num_historical_steps: int,
@@ -435,12 +498,69 @@ class InfGenDecoder(nn.Module):
     def _run(self, *args, **kw):
         return self._drive(self._run_gen(*args, **kw))
 
+    def _begin(self, columns: int, replay, replay_plan):
+        """what every rollout call starts with -> (the packed weights, motion_beam_size, insert_beam_size, DEBUG).  ``columns``: the
+        time steps of the data's ``agent.position``, which set an unset rollout length."""
+        if replay is None and replay_plan is not None:
+            raise ValueError('replay_plan overrides the logged future of the rows replay= flags: give replay= too')
+        ae = self.agent_encoder
+        w = self._last_w = self._weights()
+        if ae.num_recurrent_steps_val == -1:
+            # sticky like the reference (agent_decoder.py:1633-1635)
+            ae.num_recurrent_steps_val = int(columns) - ae.num_historical_steps
+            w.cfg.num_recurrent_steps_val = ae.num_recurrent_steps_val
+        w.cfg.disable_insertion = bool(ae.disable_insertion)
+        # DEBUG=1 forces 'enter' (agent_decoder.py:1888)
+        return w, int(getattr(ae, 'motion_beam_size', 1)), int(getattr(ae, 'insert_beam_size', 1)), bool(int(os.getenv('DEBUG', 0)))
+
+    def _make_engine(self, w, facts: Dict, tables, uniforms, skw: Dict, source, headroom=None):
+        """the facts ``_engine_key`` keys + the call's arrays -> a new engine.  ``tables``: (vocab, map_vocab, grid); ``source()``:
+        the arguments of the data's form - scenes / x_pt_override of the list path, batch / batch_layout of a Batch, and replay in
+        the form that path takes (made when an engine is built: the list path's costs a host copy)."""
+        f = facts
+        agents = not f['map_only']
+        return RolloutEngine(w, vocab=tables[0], map_vocab=tables[1], grid=tables[2], insert_headroom=headroom,
+                             force_enter=f['debug'], sample_k=f['sample_k'], sample_uniforms=uniforms[0], insert_k=f['insert_k'],
+                             insert_uniforms=uniforms[1],
+                             # the seed node's per-insertion outputs (plot inputs of the reference, 5.5 MB per scene): the
+                             # single-scene entry, the n-copies batch of inference_rollouts and a Batch; the throughput entry
+                             # (inference_batch) returns the zero arrays the reference initialises them to
+                             seed_outputs=(f['single'] or f['seed_outputs']) and not f['disable_insertion'] and agents,
+                             copies=f['copies'], options=self._PRECISIONS[str(self.rollout_precision)],
+                             token_logprob=f['token_logprob'] and agents, sample_logprob=f['sample_logprob'] and agents,
+                             **skw, **source())
+
+    def _decorate(self, eng, rows, zeros):
+        """completes epilogue dicts to the reference's key set.  ``rows``: per dict (o, sel, n_graphs, n_rows, inserted) - ``o`` one
+        scene's LazyOut of the list path (its pending values stay pending) or a copy's dict over the ``n_graphs`` graphs of a Batch,
+        ``sel`` its scenes in the engine's batch (an index or a slice), ``n_rows`` its agent rows, ``inserted`` the inserted agents
+        per scene.  ``zeros(shape)`` makes the arrays nothing was recorded for."""
+        cfg = eng.cfg
+        steps, G, T_cols, hc = cfg.num_decode_steps, self.agent_encoder.grid_size, cfg.num_columns, cfg.hist_columns
+        # without insertion (or in the batched entry) the seed node's outputs stay what the reference initialises them to
+        # (:1746-1750, :1730), 11 rows per scene; use_grid_token = False: the grid's are None (reference :2376-2386)
+        seed = [(k_, (steps,) if k_in == 'state' else (steps, G), cfg.use_grid_token or k_in == 'state') for k_, k_in in eng._SEED_KEYS]
+        lp = eng.rollout_logprob() if eng.token_logprob is not None else None
+        slp = eng.rollout_sample_logprob() if eng.sample_logprob is not None else None
+        for o, sel, n_graphs, n_rows, inserted in rows:
+            put = o.set_lazy if isinstance(o, LazyOut) else (lambda k_, thunk, o=o: o.__setitem__(k_, thunk()))
+            for k_, shape, recorded in seed:
+                if k_ not in o:
+                    o[k_] = zeros((n_graphs * 11,) + shape) if recorded else None
+            if 'agent_labels' not in o:
+                put('agent_labels', lambda n=n_rows: [[None] * T_cols for _ in range(n)])
+            if lp is not None:
+                put('pred_prob', lambda o=o: logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'], hc, steps))
+                o['rollout_logprob'] = lp[sel]
+            if slp is not None:
+                o['rollout_sample_logprob'] = slp[sel]
+            o['log_message'] = '\n'.join('No agents inserted!' if x == 0 else f'Number of total inserted agents: {x}' for x in inserted)
+
     def _run_gen(self, data, x_pt=None, map_only=False, batch: Optional[Sequence] = None, sample_uniforms=None,
                  batch_seed_outputs: bool = False, copies: int = 1, replay=None, replay_plan=None, sample_temperature=None,
                  session: bool = False):
-        """``_run`` as a generator: with ``session`` it yields the engine where ``rollout()`` would run - the caller steps a
-        closed-loop session on it (``closed_loop``) and resumes the generator for the epilogue - and otherwise never yields"""
-        ae = self.agent_encoder
+        """one scene, or a list of scenes (``batch``), through per-scene host dicts or a stacked device batch.  A generator (see
+        ``_rollout_or_yield``): only ``closed_loop`` asks for a ``session``."""
         datas = list(batch) if batch is not None else [data]
         copies = int(copies)
         skw, live, skey = self._sampling_kw(len(datas), copies, sample_temperature)
@@ -450,126 +570,57 @@ class InfGenDecoder(nn.Module):
         # when something reads it (a new engine, a filtered row, the host-side outputs)
         stk = stack_datas(datas) if batch is not None and copies == 1 else None
         scenes = _LazyScenes(datas) if stk is not None else scenes_from_datas(datas)
-        if replay is None and replay_plan is not None:
-            raise ValueError('replay_plan overrides the logged future of the rows replay= flags: give replay= too')
         rp_dev, rp_host = self._replay_forms(datas, stk, replay, replay_plan) if replay is not None else (None, lambda: None)
-        w = self._last_w = self._weights()
         ag0 = datas[0]['agent']
-        if ae.num_recurrent_steps_val == -1:
-            # sticky like the reference (agent_decoder.py:1633-1635)
-            ae.num_recurrent_steps_val = int(ag0['position'].shape[1]) - ae.num_historical_steps
-            w.cfg.num_recurrent_steps_val = ae.num_recurrent_steps_val
-        vocab = {k: _np(ag0[f'trajectory_token_{k}']) for k in ('veh', 'ped', 'cyc')}
+        w, k, ik, debug = self._begin(ag0['position'].shape[1], replay, replay_plan)
+        cfg = w.cfg
+        if map_only:
+            k = ik = 1
+        vocab = {k_: _np(ag0[f'trajectory_token_{k_}']) for k_ in ('veh', 'ped', 'cyc')}
         map_vocab = _np(self.map_encoder.map_token['traj_src']).astype(np.float32)
-        grid = ae.attr_tokenizer.grid.detach().cpu().numpy()
+        grid = self.agent_encoder.attr_tokenizer.grid.detach().cpu().numpy()
         xo = None
         if x_pt is not None:
             xo = [x_pt] if batch is None else list(x_pt)
-        import os
-        w.cfg.disable_insertion = bool(ae.disable_insertion)
-        k = int(getattr(ae, 'motion_beam_size', 1))
-        if k > 1 and sample_uniforms is None and not map_only:
-            # stochastic decode like the reference's default (top-k multinomial), driven by torch's RNG: one uniform per decode
-            # step and agent row - with insertion on for every row a scene can ever hold (a row without its own uniform would
-            # be decoded greedily)
-            amax = max(int(d_['agent']['state_idx'].shape[0]) for d_ in datas)
-            ucols = amax if w.cfg.disable_insertion else int(_lib.load().infgen_layout_query(_lib.Q_MAX_AGENTS))
-            sample_uniforms = torch.rand(w.cfg.num_decode_steps, len(scenes) * copies, ucols).numpy()
-        ik = int(getattr(ae, 'insert_beam_size', 1))
-        insert_uniforms = None
-        if ik > 1 and not w.cfg.disable_insertion and not map_only and w.cfg.use_grid_token:
-            # the cell of an inserted agent from the insert_beam_size most probable ones (agent_decoder.py:1900-1904), torch's RNG
-            insert_uniforms = torch.rand(w.cfg.num_decode_steps, 10, len(scenes) * copies).numpy()
-        def make_engine(headroom=None):
-            return RolloutEngine(w, scenes, vocab, map_vocab, grid, x_pt_override=xo, insert_headroom=headroom,
-                                 force_enter=bool(int(os.getenv('DEBUG', 0))),    # DEBUG=1 forces 'enter' (agent_decoder.py:1888)
-                                 sample_k=k if not map_only else 1, sample_uniforms=sample_uniforms,
-                                 insert_k=ik if insert_uniforms is not None else 1, insert_uniforms=insert_uniforms,
-                                 # the seed node's per-insertion outputs (plot inputs of the reference, 5.5 MB per scene): the
-                                 # single-scene entry and the n-copies batch of inference_rollouts; the throughput entry
-                                 # (inference_batch) returns the zero arrays the reference initialises them to
-                                 seed_outputs=(batch is None or batch_seed_outputs) and not w.cfg.disable_insertion and not map_only,
-                                 copies=copies, options=self._PRECISIONS[str(self.rollout_precision)], replay=rp_host(),
-                                 token_logprob=bool(self.token_logprob) and not map_only,
-                                 sample_logprob=bool(self.sample_logprob) and not map_only, **skw)
-        # one engine per batch layout is kept across calls: a second call of the same shape re-uploads the scene arrays into
-        # the first call's device buffers instead of building (and allocating) an engine again
-        ekey = (len(scenes), PackedWeights.tables_key(*(vocab[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab),
-                bool(w.cfg.disable_insertion), w.cfg.num_recurrent_steps_val, k if not map_only else 1,
-                ik if insert_uniforms is not None else 1, bool(int(os.getenv('DEBUG', 0))), batch is None, map_only, xo is None,
-                bool(batch_seed_outputs), copies, replay is not None, bool(self.token_logprob), bool(self.sample_logprob), skey)
-        eng = self._engines.get(ekey)
-        if (stk is not None and eng is not None and eng.fits_device(stk) and
-                eng.reload_device(stk, scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo,
-                                  replay=rp_dev, **live)):
-            pass
-        elif eng is not None and eng.fits(scenes):
-            eng.reload(scenes, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, x_pt_override=xo, replay=rp_host(),
-                       **live)
-        else:
-            eng = make_engine()
-            if len(self._engines) >= 2:
-                self._engines.pop(next(iter(self._engines)))
-            self._engines[ekey] = eng
+        limit = int(_lib.load().infgen_layout_query(_lib.Q_MAX_AGENTS))
+        ucols = max(int(d_['agent']['state_idx'].shape[0]) for d_ in datas) if cfg.disable_insertion else limit
+        su, iu = _draw_uniforms(cfg, k, ik, len(datas) * copies, ucols, sample_uniforms)
+        facts = dict(graphs=False, scenes=len(datas), disable_insertion=cfg.disable_insertion, steps=cfg.num_recurrent_steps_val,
+                     tables=PackedWeights.tables_key(*(vocab[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab),
+                     sample_k=k, insert_k=ik if iu is not None else 1, debug=debug, copies=copies, replay=replay is not None,
+                     token_logprob=bool(self.token_logprob), sample_logprob=bool(self.sample_logprob), sampling=skey,
+                     single=batch is None, map_only=map_only, own_map=xo is None, seed_outputs=bool(batch_seed_outputs))
+        ekey = _engine_key(**facts)
+        make_engine = functools.partial(self._make_engine, w, facts, (vocab, map_vocab, grid), (su, iu), skw,
+                                        lambda: dict(scenes=scenes, x_pt_override=xo, replay=rp_host()))
+        up = dict(sample_uniforms=su, insert_uniforms=iu, x_pt_override=xo, **live)
+        attempts = [(lambda e: e.fits(scenes), lambda e: e.reload(scenes, replay=rp_host(), **up))]
+        if stk is not None:
+            attempts.insert(0, (lambda e: e.fits_device(stk), lambda e: e.reload_device(stk, scenes, replay=rp_dev, **up)))
+        eng = _cached_engine(self._engines, ekey, attempts, make_engine)
         if map_only:
             eng.prologue(map_only=True)
             return eng.x_pt[:eng.hosts[0]['M']].clone(), self._map_keys(eng, datas)[0]
-        # the reference's agent arrays grow without bound; here rows are pre-allocated per scene.  If the inserted agents
-        # outgrow them the (deterministic) rollout is repeated with twice the rows instead of dropping insertions
-        while True:
-            if session:
-                yield eng
-                break
-            try:
-                eng.rollout()
-                break
-            except InsertionHeadroomError as e:
-                amax = max(h['A'] for h in eng.hosts)
-                limit = eng.lib.infgen_layout_query(_lib.Q_MAX_AGENTS)
-                if eng.A_cap >= limit:
-                    raise
-                eng = self._engines[ekey] = make_engine(headroom=min(2 * eng.A_cap, limit) - amax)
+        # (the scenes' own rows: their kept counts, which this path knows on the host and sizes the engine's rows from)
+        eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, max(h['A'] for h in eng.hosts), limit, session)
         # the map-token head once per distinct scene (not with a caller's map encoding: inference_no_map passes its map_enc through)
         mk = self._map_keys(eng, datas) if xo is None else None
         # per-scene dicts of device tensors (no host round trip of the results), detached from the engine's buffers
         outs = eng.outputs_device(detach=True)
-        dev = w.device
-        res = []
-        steps = w.cfg.num_decode_steps
-        G = ae.grid_size
         zero = {}                              # shared (read-only) zero tensors of the seed outputs a batch does not record
 
-        def z(*shape):
+        def zeros(shape):
             if shape not in zero:
-                zero[shape] = torch.zeros(*shape, device=dev)
+                zero[shape] = torch.zeros(shape, device=w.device)
             return zero[shape]
-        T_cols = w.cfg.num_columns
-        lp_sum = eng.rollout_logprob() if eng.token_logprob is not None else None
-        slp_sum = eng.rollout_sample_logprob() if eng.sample_logprob is not None else None
         if copies > 1:                          # scene i's copies are adjacent in the engine's batch
             datas = [d_ for d_ in datas for _ in range(copies)]
-        for i_, (d, o) in enumerate(zip(datas, outs)):
-            r = o                                   # (a LazyOut: per-scene views are cut when a key is read, not here)
+        # (a LazyOut per scene: its views are cut when a key is read, not here)
+        self._decorate(eng, ((r, i_, 1, eng.hosts[i_]['A'] + r['num_inserted'], (r['num_inserted'],)) for i_, r in enumerate(outs)), zeros)
+        for i_, (d, r) in enumerate(zip(datas, outs)):
             if mk is not None:                      # (copies of a scene share its tensors)
                 for k_, v_ in mk[i_ // copies].items():
                     r[k_] = v_
-            # without insertion (or in the batched entry) these stay what the reference initialises them to (:1746-1750, :1730)
-            for k_, shp_ in (('next_state_prob_seed', (11, steps)), ('next_pos_rel_prob_seed', (11, steps, G)),
-                             ('grid_agent_occ_seed', (11, steps, G)), ('grid_pt_occ_seed', (11, steps, G)),
-                             ('grid_agent_occ_gt_seed', (11, steps, G))):
-                if k_ not in r:
-                    # (use_grid_token = False: the grid's outputs are None, reference :2376-2386)
-                    r[k_] = z(*shp_) if w.cfg.use_grid_token or k_ == 'next_state_prob_seed' else None
-            if 'agent_labels' not in r:
-                r.set_lazy('agent_labels', (lambda n=eng.hosts[i_]['A'] + o['num_inserted']: [[None] * T_cols for _ in range(n)]))
-            if lp_sum is not None:
-                r.set_lazy('pred_prob', (lambda o=o: logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'],
-                                                                       w.cfg.hist_columns, steps)))
-                r['rollout_logprob'] = lp_sum[i_]
-            if slp_sum is not None:
-                r['rollout_sample_logprob'] = slp_sum[i_]
-            r['log_message'] = ('No agents inserted!' if o['num_inserted'] == 0 else
-                                f"Number of total inserted agents: {o['num_inserted']}")
             # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649)
             try:
                 filt = eng.hosts[i_]['filt']
@@ -580,8 +631,7 @@ class InfGenDecoder(nn.Module):
                         d['batch_size_a'] -= removed
             except (KeyError, TypeError):
                 pass
-            res.append(r)
-        return res if batch is not None else res[0]
+        return outs if batch is not None else outs[0]
 
     def _empty_map_keys(self, dev) -> Dict[str, torch.Tensor]:
         return {'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
@@ -656,18 +706,16 @@ class InfGenDecoder(nn.Module):
         """a ragged multi-graph Batch of device tensors through RolloutEngine.reload_batch (the ingest kernel: filter, pad and
         set up every scene on the device) and the batched epilogue (outputs_batch: infgen_pack_rows).  One device -> host copy
         before the first launch (the offsets and av_index; the token vocabularies the tables are keyed by ride along unless the
-        same vocabulary tensors were seen before) and one after the rollout (the agent counts).  -> ``copies`` dicts"""
+        same vocabulary tensors were seen before) and one after the rollout (the agent counts).  -> ``copies`` dicts.  A
+        generator like ``_run_gen``."""
         ae = self.agent_encoder
-        w = self._last_w = self._weights()
-        cfg = w.cfg
         ag = data['agent']
         copies = int(copies)
-        if ae.num_recurrent_steps_val == -1:
-            ae.num_recurrent_steps_val = int(ag['position'].shape[1]) - ae.num_historical_steps
-            cfg.num_recurrent_steps_val = ae.num_recurrent_steps_val
-        lib = _lib.load()
+        w, k, ik, debug = self._begin(ag['position'].shape[1], replay, replay_plan)
+        cfg = w.cfg
+        limit = int(_lib.load().infgen_layout_query(_lib.Q_MAX_AGENTS))
         ts = cfg.token_size
-        voc_t = [torch.as_tensor(ag[f'trajectory_token_{k}']) for k in ('veh', 'ped', 'cyc')]
+        voc_t = [torch.as_tensor(ag[f'trajectory_token_{k_}']) for k_ in ('veh', 'ped', 'cyc')]
         map_vocab = np.asarray(self._host_const(self.map_encoder.map_token['traj_src']), np.float32)
         grid = self._host_const(ae.attr_tokenizer.grid)
         # the token vocabularies key the engine's tables by content: their host copy (1.2 MB) and hash are made once per set of
@@ -688,10 +736,10 @@ class InfGenDecoder(nn.Module):
             pm = pm.to(torch.as_tensor(ag['ptr']).device)
             mptr_d = torch.as_tensor(data['pt_token']['ptr']).to(pm.device, torch.int64)
             pm_ext = [torch.nn.functional.pad(torch.cumsum(pm, 0), (1, 0))[mptr_d]]
-        lay = read_batch_layout(data, cfg.num_columns, cfg.hist_columns, lib.infgen_layout_query(_lib.Q_MAX_AGENTS),
+        lay = read_batch_layout(data, cfg.num_columns, cfg.hist_columns, limit,
                                 extra=(() if hit is not None else tuple(t[:ts] for t in voc_t)) + tuple(pm_ext))
         if hit is None:
-            vocab_ = {k: np.asarray(v, np.float32) for k, v in zip(('veh', 'ped', 'cyc'), lay['extra'])}
+            vocab_ = {k_: np.asarray(v, np.float32) for k_, v in zip(('veh', 'ped', 'cyc'), lay['extra'])}
             tkey_ = PackedWeights.tables_key(*(vocab_[k_] for k_ in ('veh', 'ped', 'cyc')), grid, map_vocab)
             hit = (tuple(keep), vocab_, tkey_)
             if cacheable:
@@ -700,24 +748,10 @@ class InfGenDecoder(nn.Module):
                 cache[key] = hit
         _, vocab, tkey = hit
         B = lay['B']
-        S = B * copies
         skw, live, skey = self._sampling_kw(B, copies, sample_temperature)
-        cfg.disable_insertion = bool(ae.disable_insertion)
-        k = int(getattr(ae, 'motion_beam_size', 1))
-        if k > 1 and sample_uniforms is None:
-            ucols = lay['amax'] if cfg.disable_insertion else int(lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
-            sample_uniforms = torch.rand(cfg.num_decode_steps, S, ucols).numpy()
-        elif sample_uniforms is not None:
-            sample_uniforms = _np(sample_uniforms)
-        ik = int(getattr(ae, 'insert_beam_size', 1))
-        insert_uniforms = None
-        if ik > 1 and not cfg.disable_insertion and cfg.use_grid_token:
-            insert_uniforms = torch.rand(cfg.num_decode_steps, 10, S).numpy()
-        debug = bool(int(os.getenv('DEBUG', 0)))
+        su, iu = _draw_uniforms(cfg, k, ik, B * copies, lay['amax'] if cfg.disable_insertion else limit, sample_uniforms)
         # log replay: the row mask in the Batch's global row order, on its device (the ingest kernel applies the row filter)
         rp = None
-        if replay is None and replay_plan is not None:
-            raise ValueError('replay_plan overrides the logged future of the rows replay= flags: give replay= too')
         if replay is not None:
             st_idx = torch.as_tensor(ag['state_idx'])
             rp = scene_setup.replay_global(replay, int(st_idx.shape[0]), torch.as_tensor(ag['av_index']).to(st_idx.device), B)
@@ -727,40 +761,22 @@ class InfGenDecoder(nn.Module):
                                    for k_ in scene_setup.PLAN_KEYS if replay_plan[0].get(k_) is not None}
                 scene_setup.check_plan(replay_plan)
                 rp = (rp, {k_: v_ for k_, v_ in replay_plan.items() if v_ is not None})
-
-        def make_engine(headroom=None):
-            return RolloutEngine(w, None, vocab, map_vocab, grid, insert_headroom=headroom, force_enter=debug, sample_k=k,
-                                 sample_uniforms=sample_uniforms, insert_k=ik if insert_uniforms is not None else 1,
-                                 insert_uniforms=insert_uniforms, seed_outputs=not cfg.disable_insertion, copies=copies,
-                                 options=self._PRECISIONS[str(self.rollout_precision)], batch=data, batch_layout=lay, replay=rp,
-                                 token_logprob=bool(self.token_logprob), sample_logprob=bool(self.sample_logprob), **skw)
-        ekey = ('graphs', S, tkey, skey,
-                bool(cfg.disable_insertion), cfg.num_recurrent_steps_val, k, ik if insert_uniforms is not None else 1, debug, copies,
-                replay is not None, bool(self.token_logprob), bool(self.sample_logprob))
-        eng = self._engines.get(ekey)
-        if eng is not None and eng.fits_batch(lay):
-            eng.reload_batch(data, sample_uniforms=sample_uniforms, insert_uniforms=insert_uniforms, layout=lay, replay=rp,
-                             **live)
-        else:
-            eng = make_engine()
-            if len(self._engines) >= 2:
-                self._engines.pop(next(iter(self._engines)))
-            self._engines[ekey] = eng
-        while True:
-            if session:                  # (closed_loop: see _run_gen)
-                yield eng
-                break
-            try:
-                eng.rollout()
-                break
-            except InsertionHeadroomError:
-                limit = lib.infgen_layout_query(_lib.Q_MAX_AGENTS)
-                if eng.A_cap >= limit:
-                    raise
-                eng = self._engines[ekey] = make_engine(headroom=min(2 * eng.A_cap, limit) - lay['amax'])
+        # (a Batch's rollouts always record the seed node's outputs)
+        facts = dict(graphs=True, scenes=B, tables=tkey, disable_insertion=cfg.disable_insertion, steps=cfg.num_recurrent_steps_val,
+                     sample_k=k, insert_k=ik if iu is not None else 1, debug=debug, copies=copies, replay=replay is not None,
+                     token_logprob=bool(self.token_logprob), sample_logprob=bool(self.sample_logprob), sampling=skey,
+                     single=False, map_only=False, own_map=True, seed_outputs=True)
+        ekey = _engine_key(**facts)
+        make_engine = functools.partial(self._make_engine, w, facts, (vocab, map_vocab, grid), (su, iu), skw,
+                                        lambda: dict(scenes=None, batch=data, batch_layout=lay, replay=rp))
+        eng = _cached_engine(self._engines, ekey, [(lambda e: e.fits_batch(lay), lambda e: e.reload_batch(
+            data, sample_uniforms=su, insert_uniforms=iu, layout=lay, replay=rp, **live))], make_engine)
+        # (the scenes' own rows: the kept counts stay on the device until the rollout is over - the engine's rows are sized from
+        # the layout's unfiltered maximum, which the offsets give on the host, and so is the retry's head-room)
+        eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, lay['amax'], limit, session)
         outs = eng.outputs_batch()
         n_fin, c = eng.batch_counts()
-        dev, steps, G, T_cols = w.device, cfg.num_decode_steps, ae.grid_size, cfg.num_columns
+        dev = w.device
         # the map-token head once per graph, one launch: the predicted rows of the Batch in graph order (graph g's token p sits at
         # row g * M_cap + p - ptr[g] of the engine's map encoding), shared by every copy
         map_keys = self._gt_keys(data, dev)
@@ -772,25 +788,10 @@ class InfGenDecoder(nn.Module):
             map_keys.update(map_next_token_idx=top, map_next_token_prob=lg,
                             map_next_token_eval_mask=torch.ones(n_pred, dtype=torch.bool, device=dev))
         passthrough = {k_: data[k_] for k_ in self.data_keys if k_ in data}
-        res = []
-        for j, o in enumerate(outs):
-            for k_, shp_ in (('next_state_prob_seed', (11, steps)), ('next_pos_rel_prob_seed', (11, steps, G)),
-                             ('grid_agent_occ_seed', (11, steps, G)), ('grid_pt_occ_seed', (11, steps, G)),
-                             ('grid_agent_occ_gt_seed', (11, steps, G))):
-                if k_ not in o:
-                    o[k_] = (torch.zeros((B * shp_[0],) + shp_[1:], device=dev) if cfg.use_grid_token or k_ == 'next_state_prob_seed'
-                             else None)
-            if 'agent_labels' not in o:
-                o['agent_labels'] = [[None] * T_cols for _ in range(int(n_fin[j::copies].sum()))]
-            ins = (n_fin - c[:, 0])[j::copies]
-            o['log_message'] = '\n'.join('No agents inserted!' if int(x) == 0 else f'Number of total inserted agents: {int(x)}'
-                                         for x in ins)
-            if eng.token_logprob is not None:
-                o['pred_prob'] = logprob.pred_prob(o['next_token_logprob'], o['next_token_logprob_mask'], cfg.hist_columns, steps)
-                o['rollout_logprob'] = eng.rollout_logprob()[j::copies]
-            if eng.sample_logprob is not None:
-                o['rollout_sample_logprob'] = eng.rollout_sample_logprob()[j::copies]
-            res.append({**map_keys, **o, **passthrough})
+        # (copy j's scenes are j, j + copies, ... of the engine's batch)
+        self._decorate(eng, ((o, slice(j, None, copies), B, int(n_fin[j::copies].sum()), (n_fin - c[:, 0])[j::copies].tolist())
+                             for j, o in enumerate(outs)), lambda shape: torch.zeros(shape, device=dev))
+        res = [{**map_keys, **o, **passthrough} for o in outs]
         # the callee mutates data['batch_size_a'] like the reference (agent_decoder.py:1649), per graph
         removed = c[::copies, 2]
         if mutate and removed.any() and 'batch_size_a' in data:
@@ -906,11 +907,7 @@ class InfGenDecoder(nn.Module):
             return rs[0]
         r = yield from self._run_gen(data, sample_uniforms=sample_uniforms, replay=replay, replay_plan=replay_plan, session=session)
         x_pt = r.pop('x_pt')
-        map_enc = {'x_pt': x_pt, 'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=x_pt.device),
-                   'map_next_token_prob': torch.zeros(0, self.map_encoder.token_size, device=x_pt.device),
-                   'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=x_pt.device),
-                   'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=x_pt.device)}
-        return r.merged(first=map_enc, last={k: data[k] for k in self.data_keys if k in data})
+        return r.merged(first={'x_pt': x_pt, **self._empty_map_keys(x_pt.device)}, last={k: data[k] for k in self.data_keys if k in data})
 
     @torch.no_grad()
     def closed_loop(self, data, controlled='ego', pose: str = 'token'):
@@ -969,11 +966,7 @@ class InfGenDecoder(nn.Module):
         if copies > 1:                          # ``copies`` rollouts per scene over one map encoding: scene 0's first, then scene 1's ...
             datas = [d for d in datas for _ in range(int(copies))]
         out = []
-        dev, ts = self._last_w.device, self.map_encoder.token_size
-        map_keys = {'map_next_token_idx': torch.zeros(0, 10, dtype=torch.long, device=dev),
-                    'map_next_token_prob': torch.zeros(0, ts, device=dev),
-                    'map_next_token_idx_gt': torch.zeros(0, dtype=torch.long, device=dev),
-                    'map_next_token_eval_mask': torch.zeros(0, dtype=torch.bool, device=dev)}
+        map_keys = self._empty_map_keys(self._last_w.device)
         for d, r in zip(datas, rs):
             out.append(r.merged(first=map_keys, last={k: d[k] for k in self.data_keys if k in d}))
         return out
