@@ -58,6 +58,8 @@
  * functions only edit the process-wide DEFAULT block that contexts / threads without their own inherit.  Environment variables
  * (INFGEN_*) are tuning thresholds and diagnostics of the launch shapes (which kernel variant from how many rows); each is read once
  * per process and none changes the arithmetic.
+ * Style: infgen_amd/_lib.py reads its ctypes binding from this file and refuses what is not in use here - `#define NAME integer`, anonymous
+ * enums, `typedef struct X {..} X;` of scalars, pointers (one name each), fixed arrays, earlier structs; int / const char* functions, named parameters.
  */
 #ifndef INFGEN_HIP_H_
 #define INFGEN_HIP_H_

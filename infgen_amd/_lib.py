@@ -1,6 +1,6 @@
-"""ctypes binding of libinfgen_hip.so (C ABI: include/infgen_hip.h).
+"""ctypes binding of libinfgen_hip.so, derived at import from the C ABI's one source, include/infgen_hip.h.
 
-The product path has NO fallback: if the shared library is missing or an entry point fails,
+The product path has NO fallback: if the header or the shared library is missing, or an entry point fails,
 an exception is raised.
 """
 from __future__ import annotations
@@ -8,242 +8,150 @@ from __future__ import annotations
 import ctypes as C
 import threading
 import os
+import re
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libinfgen_hip.so')
-MAX_LAYERS = 8
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'infgen_hip.h')     # ../../include/infgen_hip.h of csrc/Makefile
 
 _p = C.c_void_p
 _i = C.c_int
 _f = C.c_float
 
 
-class LinearDesc(C.Structure):
-    """InfgenLinearDesc of include/infgen_hip.h"""
-    _fields_ = [('X', C.c_void_p), ('ldx', C.c_int), ('gather', C.c_void_p), ('rows', C.c_int), ('K', C.c_int),
-                ('Wp', C.c_void_p), ('Np', C.c_int), ('bias', C.c_void_p), ('N', C.c_int),
-                ('pre_g', C.c_void_p), ('pre_b', C.c_void_p), ('post_g', C.c_void_p), ('post_b', C.c_void_p), ('relu', C.c_int),
-                ('Y', C.c_void_p), ('ldy', C.c_int)]
-
-
-class EdgeBuf(C.Structure):
-    _fields_ = [('off', _p), ('cnt', _p), ('src', _p), ('raw', _p), ('rhat', _p), ('total', _p),
-                ('cap', _i), ('_pad', _i)]
-
-
-class RadiusEdges(C.Structure):
-    """InfgenRadiusEdges (include/infgen_hip.h)"""
-    _fields_ = [('n_q', _i), ('_pad0', _i),
-                ('q_node', _p), ('q_pt', _p), ('q_c0', _p), ('q_c1', _p), ('q_self', _p), ('q_pair_off', _p),
-                ('p_pos', _p), ('p_head', _p), ('p_inv', _p),
-                ('c_pos', _p), ('c_head', _p), ('c_inv', _p), ('c_ok', _p), ('c_src', _p), ('pair_ok', _p),
-                ('radius', C.c_float), ('K', _i), ('gap_rule', _i), ('index_diff', _i), ('e_base', _i), ('_pad1', _i)]
-
-
-class Insertion(C.Structure):
-    """InfgenInsertion (include/infgen_hip.h)"""
-    _fields_ = [('attn_occ2sa', _p * 3), ('attn_pt2sa', _p * 3), ('attn_a2sa', _p * 3),
-                ('four_a2sa', _p), ('four_pt2sa', _p),
-                ('head_state', _p), ('head_type', _p), ('head_shape', _p), ('head_pos', _p), ('head_heading', _p),
-                ('head_offset', _p), ('occ_embed', _p), ('shape_emb', _p), ('type_a_emb', _p), ('f_seed', _p),
-                ('occ', _p), ('occ_emb', _p), ('Kocc', _p * 3), ('Vocc', _p * 3), ('mapK', _p * 3), ('mapV', _p * 3),
-                ('Ksa', _p * 3), ('Vsa', _p * 3), ('Kh', _p * 3), ('Vh', _p * 3), ('Xc', _p),
-                ('zero_agg', _p), ('zero_z', _p), ('zero_sig', _p),
-                ('XS', _p), ('QS', _p), ('US', _p), ('AGGS', _p), ('ZS', _p), ('SIGS', _p), ('KN', _p), ('VN', _p),
-                ('ea_s', EdgeBuf), ('em_s', EdgeBuf), ('ea_h', EdgeBuf), ('em_h', EdgeBuf),
-                ('occ_off', _p), ('occ_cnt', _p), ('occ_src', _p),
-                ('active', _p), ('n_new', _p), ('inserted', _p), ('new_row', _p), ('new_cell', _p), ('new_local', _p), ('new_shape', _p),
-                ('prev_row', _p), ('prev_mask', _p), ('pend_row', _p), ('pend_mask', _p),
-                ('hv_ovr', _p), ('shape_all', _p),
-                ('hid', _p), ('lg_state', _p), ('lg_type', _p), ('shape', _p), ('lg_pos', _p), ('lg_heading', _p), ('offset', _p),
-                ('t1', _p), ('t2', _p), ('shp', _p), ('host_dec', _p),
-                ('r_seed', C.c_float), ('r_a2sa', C.c_float), ('r_pl2sa', C.c_float), ('angle_interval', C.c_float),
-                ('n_heading', _i), ('force_enter', _i), ('insert_k', _i), ('max_new', _i),
-                ('insert_temperature', _f), ('insert_top_p', _f),
-                ('head_pos_xy', _p), ('head_heading_theta', _p), ('no_grid_token', _i), ('no_head_token', _i)]
-
-
-class Options(C.Structure):
-    _fields_ = [('use', _i), ('attn_mode', _i), ('gemm_terms', _i), ('fourier_mode', _i), ('edge_fuse', _i), ('edge_loop', _i),
-                ('overlap', _i), ('row_group_margin', _i), ('layers_p', _i), ('rhat_format', _i), ('edge_kernel', _i), ('_pad0', _i), ('row_groups', _p), ('n_row_groups', _p)]
-
-
-OPTIONS_VALUE_BYTES = C.sizeof(_i) * 12       # the integer switches of Options (the two pointers follow)
-
-
-class Sampling(C.Structure):
-    """InfgenSampling (include/infgen_hip.h): temperature / nucleus mass of a top-k draw (0 = unset = 1), optional per-row temperature"""
-    _fields_ = [('temperature', _f), ('top_p', _f), ('temperature_row', _p)]
-
-
-class Rollout(C.Structure):
-    _fields_ = [
-        ('S', _i), ('A_cap', _i), ('T', _i), ('M_cap', _i), ('W', _i), ('ring', _i), ('R', _i),
-        ('token_size', _i), ('grid_size', _i), ('num_layers', _i), ('force_valid', _i), ('store_logits', _i),
-        ('r_map', _f), ('r_agent', _f),
-        ('n_agents', _p), ('n_map', _p), ('av_index', _p),
-        ('pos', _p), ('head', _p), ('state', _p), ('token', _p), ('grid', _p),
-        ('tmask', _p), ('imask', _p), ('catflag', _p), ('type', _p), ('bos', _p),
-        ('map_pos', _p), ('map_orient', _p),
-        ('attn_t', _p * MAX_LAYERS), ('attn_m', _p * MAX_LAYERS), ('attn_a', _p * MAX_LAYERS),
-        ('four_t', _p), ('four_m', _p), ('four_a', _p), ('four_xa', _p),
-        ('fusion_pack', _p), ('tok_head_pack', _p), ('st_head_pack', _p),
-        ('tok_tab', _p), ('grid_tab', _p), ('state_emb', _p), ('cat_agent', _p), ('cat_seed', _p),
-        ('vocab', _p), ('grid_xy', _p),
-        ('ringK', _p * MAX_LAYERS), ('ringV', _p * MAX_LAYERS), ('mapK', _p * MAX_LAYERS), ('mapV', _p * MAX_LAYERS),
-        ('X', _p), ('Q', _p), ('U', _p), ('Ka', _p), ('Va', _p), ('AGG', _p), ('Z', _p), ('SIG', _p),
-        ('et', EdgeBuf), ('em', EdgeBuf), ('ea', EdgeBuf),
-        ('raw2', _p), ('cat', _p), ('fus_in', _p), ('tmp1', _p), ('tmp2', _p),
-        ('next_token', _p), ('next_state', _p), ('logits', _p),
-        ('teacher_token', _p), ('teacher_state', _p),
-        ('pred_traj', _p), ('pred_head', _p), ('pred_state', _p),
-        ('first_new', _p), ('hv_ovr', _p),
-        ('sample_k', _i), ('_pad1', _i), ('sample_u', _p), ('logits_scratch', _p),
-        ('opts', Options),
-        ('teacher_grid', _p),
-        ('four_t_dt', _p),
-        ('teacher_pos', _p), ('teacher_head', _p),
-        ('replay_row', _p),
-        ('map_scene', _p),
-        ('tap_x', _p),
-        ('sample_temperature', _f), ('sample_top_p', _f), ('sample_temp_row', _p),
-        ('sample_logprob', _p),
-        ('token_logprob', _p),
-        ('no_grid_token', _i), ('no_state_token', _i),
-    ]
-
-
-class BatchIngest(C.Structure):
-    """InfgenBatchIngest (include/infgen_hip.h): a ragged Batch's device arrays and the rollout buffers they are written to"""
-    _fields_ = ([(k, _i) for k in ('S', 'copies', 'A_cap', 'M_cap', 'T', 'T0', 'P', 'hc', 'H', 'motion_cols', 'pos_dim',
-                                   'pt_pos_dim', 'n_polygons', '_pad0')] +
-                [(k, _p) for k in ('agent_ptr', 'pt_ptr', 'av_index', 'src_graph', 'state_idx', 'token_idx', 'grid_token_idx',
-                                   'token_pos', 'token_heading', 'raw_valid', 'valid_mask', 'shape', 'position', 'heading', 'type',
-                                   'id', 'pt_position', 'pt_orientation', 'pt_token_idx', 'pt_type', 'pt_pl_type', 'pt_polygon',
-                                   'light_type',
-                                   'pos', 'head', 'state', 'token', 'gridtok', 'tmask', 'imask', 'catflag', 'atype', 'bos',
-                                   'shape10', 'n_agents', 'av', 'n_map', 'map_pos', 'map_orient', 'map_tok', 'map_type', 'map_pl',
-                                   'map_light', 'htok', 'hst', 'p0', 'h0', 'shp', 'gt', 'val', 'ids', 'counts',
-                                   'replay_in', 'plan_token', 'plan_state', 'plan_pos', 'plan_head',
-                                   'teacher_token', 'teacher_state', 'teacher_pos', 'teacher_head', 'replay_row')])
-
-
-# symbol -> (restype, argtypes); every symbol include/infgen_hip.h declares
-SYMBOLS = {
-    'infgen_layout_query': (_i, [_i]),
-    'infgen_attn_pack_offset': (_i, [C.c_char_p]),
-    'infgen_fourier_pack_offset': (_i, [C.c_char_p, _i, _i]),
-    'infgen_last_error': (C.c_char_p, []),
-    'infgen_linear': (_i, [_p, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _i, _p]),
-    'infgen_linear_multi': (_i, [_p, _i, _p]),
-    'infgen_radius_edges': (_i, [_p, _p, _p]),
-    'infgen_motion_features': (_i, [_p, _p, _p, _p, _i, _i, _p, _p]),
-    'infgen_layernorm': (_i, [_p, _i, _p, _p, _p, _p]),
-    'infgen_fourier_embed': (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _i, _i, _p]),
-    'infgen_set_fourier_mode': (_i, [_i]),
-    'infgen_set_attn_mode': (_i, [_i]),
-    'infgen_set_edge_fuse': (_i, [_i]),
-    'infgen_set_layers_p': (_i, [_i]),
-    'infgen_layers_p_capacity': (_i, []),
-    'infgen_rollout_validate': (_i, [_p]),
-    'infgen_set_edge_loop': (_i, [_i]),
-    'infgen_set_rhat_format': (_i, [_i]),
-    'infgen_set_edge_kernel': (_i, [_i]),
-    'infgen_mlp_embedding': (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p]),
-    'infgen_get_options': (_i, [C.POINTER(Options)]),
-    'infgen_thread_options': (_i, [C.POINTER(Options)]),
-    'infgen_get_effective_options': (_i, [C.POINTER(Options)]),
-    'infgen_edge_fused_occupancy': (_i, []),
-    'infgen_debug_stream_read': (_i, [_p, C.c_ulonglong, _i, _p, _p]),
-    'infgen_set_overlap': (_i, [_i]),
-    'infgen_edge_attn_fused': (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'infgen_edge_attn_fused_r24': (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'infgen_fourier_embed_r24': (_i, [_p, _i, _p, _i, _p, _p, _p]),
-    'infgen_embedding_sum4': (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p]),
-    'infgen_fourier_last_dim_table': (_i, [_p, _i, _p, _p]),
-    'infgen_fourier_embed_tab': (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _p]),
-    'infgen_distance_to_nearest_object': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_float, _p, _p, _p]),
-    'infgen_kinematic_features': (_i, [_p, _p, _p, _p, _i, _i, C.c_float, _p, _p, _p, _p, _p]),
-    'infgen_time_to_collision': (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
-    'infgen_set_gemm_terms': (_i, [_i]),
-    'infgen_active_row_groups': (_i, [_p, _i, _i, _i, _p, _p, _p]),
-    'infgen_set_row_groups': (_i, [_p, _p, _i]),
-    'infgen_set_row_limits': (_i, [_p, _i, _i]),
-    'infgen_fetch_enterings': (_i, [_p] * 5 + [_i] * 3 + [_p, _i, _f, _f, _i, _i] + [_p] * 9 + [_i, _p, _i, _p, _p]),
-    'infgen_tokenize_agent': (_i, [_p] * 9 + [_i] * 10 + [_p] * 8),
-    'infgen_distance_to_road_edge': (_i, [_p] * 9 + [_i] * 4 + [_p, _p, _p, _i, _f, _p, _p]),
-    'infgen_window_log_likelihood': (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
-    'infgen_placement_features': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    'infgen_bundle_scores': (_i, [_p] * 14 + [_i] * 11 + [_p] * 5),
-    'infgen_match_map_tokens': (_i, [_p, _p, _p, _i, _i, _p, _p]),
-    'infgen_match_agent_tokens': (_i, [_p, _p, _p, _p, _p, _p, C.c_longlong, _i, _i, _i, _i, _p, _p, _p]),
-    'infgen_attn_pre': (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p]),
-    'infgen_edge_attn': (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'infgen_edge_attn_mode': (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
-    'infgen_attn_post': (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
-    'infgen_attn_post_pre': (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p]),
-    'infgen_heads': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p]),
-    'infgen_heads_logprob': (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
-    'infgen_token_logprob': (_i, [_p, _i, _i, _p, _p, _p]),
-    'infgen_heads_sample': (_i, [_p, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
-    'infgen_heads_sample_ex': (_i, [_p, _i, _p, _p, _i, _i, _p, C.POINTER(Sampling), _p, _p, _p, _p, _p, _p]),
-    'infgen_heads_sample_fused': (_i, [_i, _i, _i]),
-    'infgen_heads_logprob_fused': (_i, [_i, _i]),
-    'infgen_map_token_head': (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
-    'infgen_map_graph': (_i, [_i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _i, _p]),
-    'infgen_build_edges': (_i, [C.POINTER(Rollout), _i, _i, _p]),
-    'infgen_integrate': (_i, [C.POINTER(Rollout), _i, _p]),
-    'infgen_raw_feature': (_i, [C.POINTER(Rollout), _i, _p]),
-    'infgen_raw_feature_rows': (_i, [_p, _i, _p, _p, _i, _p]),
-    'infgen_decode_layers': (_i, [C.POINTER(Rollout), _i, _i, _p]),
-    'infgen_decode_step': (_i, [C.POINTER(Rollout), _i, _p]),
-    'infgen_rollout_run': (_i, [C.POINTER(Rollout), _i, _i, _p]),
-    'infgen_command_rows': (_i, [C.POINTER(Rollout), _i, _i, _p, _p, _p, _p, _p, _p]),
-    'infgen_sample_topk': (_i, [_p, _i, _i, _i, _p, _p, _p]),
-    'infgen_sample_topk_logprob': (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
-    'infgen_sample_topk_ex': (_i, [_p, _i, _i, _i, _p, C.POINTER(Sampling), _p, _p, _p, _p]),
-    'infgen_occupancy': (_i, [C.POINTER(Rollout), _i, _p, _p]),
-    'infgen_occupancy_embed': (_i, [C.POINTER(Rollout), _i, _p, _p, _p, _p]),
-    'infgen_point_edges': (_i, [C.POINTER(Rollout), _i, _p, _p, _i, _i, _f, _i, _f, _i, C.POINTER(EdgeBuf), C.POINTER(EdgeBuf), _p]),
-    'infgen_insert_decide': (_i, [C.POINTER(Rollout), _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
-    'infgen_insert_seed': (_i, [C.POINTER(Rollout), C.POINTER(Insertion), _i, _i, _i, _p, _p]),
-    'infgen_insert_heading': (_i, [C.POINTER(Rollout), C.POINTER(Insertion), _i, _i, _i, _p]),
-    'infgen_insert_decide_topk': (_i, [C.POINTER(Rollout), _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p]),
-    'infgen_insert_decide_topk_ex': (_i, [C.POINTER(Rollout), _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p,
-                                          C.POINTER(Sampling), _p]),
-    'infgen_insert_finalize': (_i, [C.POINTER(Rollout), _i, _f, _p, _p, _p, _i, _p, _p, _p]),
-    'infgen_prof_enable': (_i, [C.c_uint, _i]),
-    'infgen_prof_collect': (_i, [C.POINTER(C.c_double), C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]),
-    'infgen_prof_collect_steps': (_i, [C.POINTER(C.c_double), C.POINTER(_i), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong),
-                                       C.POINTER(C.c_double), C.POINTER(_i)]),
-    'infgen_prof_set_stride': (_i, [_i]),
-    'infgen_prof_seen': (_i, [C.POINTER(_i), C.POINTER(_i)]),
-    'infgen_ingest_batch': (_i, [C.POINTER(BatchIngest), _p]),
-    'infgen_pack_rows': (_i, [_i, C.POINTER(_p), C.POINTER(C.c_longlong), C.POINTER(_i), C.POINTER(_p), C.POINTER(_i),
-                              C.POINTER(_p), _i, _i, _i, _p]),
-    # validation-step metrics (infgen_amd/utils/metrics.py)
-    'infgen_state_accuracy': (_i, [_p, _i, _i, _i, C.c_longlong, _p, C.c_longlong, _i, _i, _i, _i, _p, _p]),
-    'infgen_grid_overlap': (_i, [_p, _i, C.c_longlong, _p, _i, C.c_longlong, _i, _i, _p, _i, _i, _i, _i, _p, _p]),
-    'infgen_traj_error': (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p]),
-    'infgen_masked_cross_entropy': (_i, [_p, C.c_longlong, _p, _i, _p, _p, _i, _i, _f, _p, _p, _p]),
-    'infgen_token_cls': (_i, [_p, _i, C.c_longlong, _i, _p, _i, _p, _i, _p, _p]),
-    'infgen_average_meter': (_i, [_p, C.c_longlong, _p, _p, _p]),
-}
-VM_SCRATCH_DOUBLES = 3072                # INFGEN_VM_SCRATCH_DOUBLES
-GRID_OVERLAP_MAX_CELLS = 16384           # INFGEN_GRID_OVERLAP_MAX_CELLS
-
-Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_ATTN_CAP, Q_MAX_AGENTS, \
-    Q_ABI_VERSION, Q_SIZEOF_ROLLOUT, Q_ATTN_SPLIT_ROWS, Q_HEADS_SAMPLE_K = range(11)
-
-KERNEL_IDS = ['k_linear', 'k_fourier', 'k_attn_pre', 'k_edge_attn', 'k_attn_post', 'k_heads', 'k_build_edges',
-              'k_integrate', 'k_rawfeat_prep', 'k_map_graph', 'k_map_head']
-
-_lib: Optional[C.CDLL] = None
-
-
 class InfgenHipError(RuntimeError):
     pass
+
+
+# ---- a reader for the restricted C of infgen_hip.h (its style rules are in the header's own comment block), not a C parser:
+# whatever it does not understand is an error that quotes the text, never a skipped declaration
+_SCALARS = {'int': _i, 'float': _f, 'double': C.c_double, 'unsigned': C.c_uint, 'long long': C.c_longlong,
+            'unsigned long long': C.c_ulonglong, 'uint8_t': C.c_ubyte, 'unsigned char': C.c_ubyte}
+_TOP = re.compile(r'\s*(?:enum\s*\{(?P<enum>[^{};]*)\}\s*;'
+                  r'|typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P<name>\w+)\s*;'
+                  r'|(?P<ret>[\w\s*]+?)\b(?P<fn>\w+)\s*\((?P<args>[^;{}()]*)\)\s*;)')
+_DECLARATOR = re.compile(r'\s*(?P<type>[\w\s*]*?)\s*\b(?P<name>[A-Za-z_]\w*)\s*(?:\[\s*(?P<dim>\w+)\s*\])?\s*')
+
+
+def _refuse(text: str):
+    raise InfgenHipError(f'infgen_hip.h: cannot read {" ".join(text.split())[:160]!r}')
+
+
+class Header:
+    """consts: #define / enum name -> int; structs: C name -> ctypes.Structure class; protos: name -> (restype, [argtypes])"""
+
+    def __init__(self, text: str):
+        self.consts, self.structs, self.protos, self._types = {}, {}, {}, {}
+        text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', text, flags=re.S)
+        # the two extern "C" brackets and nothing else (any other #ifdef is refused below)
+        text = re.sub(r'^#ifdef __cplusplus\n\s*(?:extern "C" \{|\})\s*\n#endif[ \t]*$', '', text, flags=re.M)
+        for line in re.findall(r'^[ \t]*#.*$', text, flags=re.M):
+            m = re.fullmatch(r'\s*#\s*define\s+(\w+)\s+(-?\d+)\s*', line)
+            if m:
+                self.consts[m[1]] = int(m[2])
+            elif not re.fullmatch(r'\s*#\s*(ifndef\s+\w+|define\s+\w+|include\s*<[\w./]+>|endif)\s*', line):
+                _refuse(line)
+        text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+        pos, end = 0, len(text.rstrip())
+        while pos < end:
+            m = _TOP.match(text, pos)
+            if not m:
+                _refuse(text[pos:])
+            pos = m.end()
+            if m['enum'] is not None:
+                self._enum(m['enum'])
+            elif m['body'] is not None:
+                if m['tag'] != m['name'] or m['name'] in self.structs:
+                    _refuse(m[0])
+                fields = [f for stmt in m['body'].split(';') if stmt.strip() for f in self._decl(stmt)]
+                self.structs[m['name']] = type(m['name'], (C.Structure,), {'_fields_': fields})
+            else:
+                res = self._ctype(m['ret'], m[0])
+                if res not in (_i, C.c_char_p) or m['fn'] in self.protos:
+                    _refuse(m[0])
+                args = [] if m['args'].strip() in ('', 'void') else m['args'].split(',')
+                self.protos[m['fn']] = (res, [self._decl(a, m[0], array=False)[0][1] for a in args])
+
+    def _enum(self, body: str):
+        value = -1
+        for item in body.split(','):
+            m = re.fullmatch(r'\s*([A-Za-z_]\w*)\s*(?:=\s*(-?\d+)\s*)?', item)
+            if m:
+                value = int(m[2]) if m[2] else value + 1
+                self.consts[m[1]] = value
+            elif item.strip():
+                _refuse(item)
+
+    def _ctype(self, spec: str, where: str):
+        if spec not in self._types:             # a few dozen spellings serve the header's thousand declarations
+            self._types[spec] = self._lookup(spec, where)
+        return self._types[spec]
+
+    def _lookup(self, spec: str, where: str):
+        words = re.findall(r'\w+', spec)
+        base, stars = ' '.join(w for w in words if w != 'const'), spec.count('*')
+        if stars == 0 and base in _SCALARS:
+            return _SCALARS[base]
+        if stars == 0 and base in self.structs:
+            return self.structs[base]
+        if stars == 1 and base == 'char' and 'const' in words:
+            return C.c_char_p
+        if stars == 1 and base in self.structs:
+            return C.POINTER(self.structs[base])
+        if stars and (base in _SCALARS or base == 'void'):
+            return _p
+        _refuse(where)
+
+    def _decl(self, text: str, where: str = '', array: bool = True):
+        """'const float* a[N]' -> [('a', c_void_p * N)]; 'int S, A_cap' -> [('S', c_int), ('A_cap', c_int)]; where: the text to quote;
+        array = False (a parameter): a dimension is refused"""
+        where = where or text
+        out, parts = [], text.split(',')
+        for k, part in enumerate(parts):
+            m = _DECLARATOR.fullmatch(part)
+            # the type stands in front of the first declarator only, and a pointer type declares one name ('float* a, b' is refused)
+            if not m or bool(m['type']) != (k == 0) or (len(parts) > 1 and '*' in m['type']):
+                _refuse(where)
+            if k == 0:
+                ctype = self._ctype(m['type'], where)
+            dim = m['dim']
+            if dim is not None and not (array and (dim.isdigit() or dim in self.consts)):
+                _refuse(where)
+            out.append((m['name'], ctype if dim is None else ctype * int(self.consts.get(dim, dim))))
+        return out
+
+
+def read_header(path: str) -> Header:
+    if not os.path.exists(path):
+        raise InfgenHipError(f'{path} not found: the binding is derived from the C header (in-tree use only)')
+    with open(path) as f:
+        return Header(f.read())
+
+
+HEADER = read_header(HEADER_PATH)
+LinearDesc, EdgeBuf, RadiusEdges, Insertion, Options, Sampling, Rollout, BatchIngest = (
+    HEADER.structs['Infgen' + n] for n in ('LinearDesc', 'EdgeBuf', 'RadiusEdges', 'Insertion', 'Options', 'Sampling', 'Rollout',
+                                           'BatchIngest'))
+SYMBOLS = HEADER.protos                        # symbol -> (restype, argtypes)
+# the one struct pointer that stays untyped: callers hand this entry the context's address as an integer (ctypes.addressof)
+SYMBOLS['infgen_raw_feature_rows'][1][0] = _p
+MAX_LAYERS, VM_SCRATCH_DOUBLES, GRID_OVERLAP_MAX_CELLS = (
+    HEADER.consts['INFGEN_' + n] for n in ('MAX_LAYERS', 'VM_SCRATCH_DOUBLES', 'GRID_OVERLAP_MAX_CELLS'))
+OPTIONS_VALUE_BYTES = Options.row_groups.offset       # the integer switches of Options (the two pointers follow)
+
+Q_ATTN_PACK_SIZE, Q_FOURIER_N2, Q_FOURIER_N3, Q_FOURIER_N4, Q_TILE_ROWS, Q_EDGE_ATTN_CAP, Q_MAX_AGENTS, \
+    Q_ABI_VERSION, Q_SIZEOF_ROLLOUT, Q_ATTN_SPLIT_ROWS, Q_HEADS_SAMPLE_K = (
+        HEADER.consts['INFGEN_Q_' + n] for n in ('ATTN_PACK_SIZE', 'FOURIER_PACK_SIZE_N2', 'FOURIER_PACK_SIZE_N3',
+                                                 'FOURIER_PACK_SIZE_N4', 'TILE_ROWS', 'EDGE_ATTN_CAP', 'MAX_AGENTS', 'ABI_VERSION',
+                                                 'SIZEOF_ROLLOUT', 'ATTN_SPLIT_ROWS', 'HEADS_SAMPLE_K'))
+
+# the profiler's names of the INFGEN_KID_* slots, in enum order (the C names do not map onto the kernels' names)
+KERNEL_IDS = ['k_linear', 'k_fourier', 'k_attn_pre', 'k_edge_attn', 'k_attn_post', 'k_heads', 'k_build_edges',
+              'k_integrate', 'k_rawfeat_prep', 'k_map_graph', 'k_map_head']
+assert len(KERNEL_IDS) == HEADER.consts['INFGEN_KID_COUNT'], 'KERNEL_IDS and the INFGEN_KID_* enum of infgen_hip.h disagree'
+
+_lib: Optional[C.CDLL] = None
 
 
 def load() -> C.CDLL:
@@ -266,7 +174,7 @@ def load() -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     if lib.infgen_layout_query(Q_SIZEOF_ROLLOUT) != C.sizeof(Rollout):
-        raise InfgenHipError('InfgenRollout layout mismatch between include/infgen_hip.h and infgen_amd/_lib.py: '
+        raise InfgenHipError('InfgenRollout layout mismatch between include/infgen_hip.h and the built library (rebuild it): '
                              f'{lib.infgen_layout_query(Q_SIZEOF_ROLLOUT)} != {C.sizeof(Rollout)}')
     _lib = lib
     return lib
