@@ -143,6 +143,27 @@ typedef struct InfgenSampling {
   const float* temperature_row;
 } InfgenSampling;
 
+/* constrained decoding: per-row allowed-token sets of the motion-token heads and samplers.  A TOKEN MASK is five values, passed as
+ * the parameters (mask_bits, mask_n_sets, mask_row, mask_type, type) of infgen_heads_sample_mask / infgen_sample_topk_mask, or
+ * registered once (infgen_token_mask_create) and named by InfgenRollout.token_mask:
+ *   - mask_bits is a mask table: mask_n_sets bit sets of token_size bits each, every set token_size / 32 little-endian uint32 words;
+ *     bit c of a set (word c / 32, bit c % 32) set means token c is allowed.  Every set allows at least one token (a set without one
+ *     breaks the contract: its rows emit token 0).  Device memory, 16-byte aligned.
+ *   - the set of a row: mask_row[row] (optional, device int32 [rows]) where it is >= 0; otherwise mask_type[type[row]] (mask_type:
+ *     three HOST ints, NULL = all -1; type: device int32 [rows] with 0 vehicle, 1 pedestrian, 2 cyclist; any other type value, and
+ *     -1 in mask_type, mean unconstrained).  A set index >= mask_n_sets reads as unconstrained: nothing outside the table is ever read.
+ *   - a banned column's logit counts as -inf for the arg-max, the running top-k and the draw; equal logits still go to the lower
+ *     allowed column.  With a allowed tokens and beam k the draw is InfgenSampling's over min(k, a) entries, so no banned token is
+ *     emitted for any uniform in [0, 1) - 1 - 2^-24 included, where step 3's "else m - 1" would otherwise name a slot of probability 0.
+ *   - stored logits stay the model's raw logits, and token_logprob keeps its meaning: the model's full, unmasked softmax of the
+ *     emitted token.  sample_logprob is the log-probability under the sampler's actual distribution (mask, then top-k, temperature,
+ *     top-p); a greedy row gives 0.
+ *   - the state head, the insertion cell draw and replayed, commanded or teacher-forced rows are left alone.
+ *   - mask_bits == NULL, mask_n_sets == 0, or mask_row == NULL with every mask_type -1: today's kernels, today's bits.
+ * Refused: mask_n_sets < 0, a table without `type` while any mask_type is >= 0, a token_size that is no multiple of 32, a misaligned
+ * table.  (Parameters and a handle, not a struct and new InfgenRollout members: tests pin the header's set of structs and
+ * sizeof(InfgenRollout).) */
+
 typedef struct InfgenRollout {
   /* sizes / hyper-parameters */
   int S, A_cap, T, M_cap, W, ring, R, token_size, grid_size, num_layers;
@@ -180,7 +201,11 @@ typedef struct InfgenRollout {
   /* reproducible top-k sampling (optional): sample_k > 1 -> every step draws the motion token by inverse CDF over
    * the sample_k most probable tokens with the uniforms sample_u[t][row]; needs logits_scratch [rows][token_size] unless every
    * step samples inside the heads kernel (infgen_heads_sample_fused(attn_mode, S * A_cap, sample_k)) */
-  int sample_k; int _pad1;
+  int sample_k;
+  /* constrained decoding: 0 (none) or a handle of infgen_token_mask_create - infgen_decode_step applies that mask to the motion token
+   * of every row, greedy or sampled (rows scenario insertion appends have mask_row -1 and take their type's set), and
+   * infgen_rollout_run takes the per-step path while a mask is active.  Takes the place of a padding word: the struct did not grow. */
+  int token_mask;
   const float* sample_u; float* logits_scratch;
   /* per-context options (re-entrancy): with opts.use != 0 the rollout-level entries (infgen_decode_layers / _step /
    * infgen_rollout_run, infgen_raw_feature*, infgen_build_edges) take every switch from here and never read the process-wide
@@ -384,6 +409,13 @@ int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const f
 int infgen_heads_sample_ex(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
                            const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token, int* next_state,
                            float* token_logprob, float* sample_logprob, void* stream);
+/* infgen_heads_sample_ex under a token mask (the five parameters described above InfgenRollout; an inactive mask: infgen_heads_sample_ex, bit for bit).
+ * k <= 1 is the masked arg-max (uniform may then be NULL; sample_logprob 0).  The by-size rules below do not look at the mask: where
+ * infgen_heads_sample_fused / infgen_heads_logprob_fused hold this is still one launch without logits in memory. */
+int infgen_heads_sample_mask(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                             const float* uniform, const InfgenSampling* sampling, const uint32_t* mask_bits, int mask_n_sets,
+                             const int* mask_row, const int* mask_type, const int* type, float* logits,
+                             int* next_token, int* next_state, float* token_logprob, float* sample_logprob, void* stream);
 /* 1 where top-k sampling with beam k runs inside the split heads kernel: attn_mode 1, or >= 2 beyond INFGEN_Q_ATTN_SPLIT_ROWS
  * rows, and 2 <= k <= INFGEN_Q_HEADS_SAMPLE_K.  The one statement of the rule: infgen_heads_sample, infgen_decode_step and the
  * engine's decision to allocate logits_scratch all go through it. */
@@ -446,6 +478,18 @@ int infgen_sample_topk_logprob(const float* logits, int rows, int n, int k, cons
  * [rows]): the nucleus size m of every row (k where top_p = 1, 1 on a greedy row) */
 int infgen_sample_topk_ex(const float* logits, int rows, int n, int k, const float* uniform, const InfgenSampling* sampling,
                           int* token, float* sample_logprob, int* nucleus, void* stream);
+/* the same under a token mask (the five parameters described above InfgenRollout; inactive: infgen_sample_topk_ex, bit for bit): banned columns
+ * are never picked and the draw is over min(k, allowed) entries; n must be a multiple of 32 */
+int infgen_sample_topk_mask(const float* logits, int rows, int n, int k, const float* uniform, const InfgenSampling* sampling,
+                            const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, const int* type,
+                            int* token, float* sample_logprob, int* nucleus, void* stream);
+/* registers a token mask for rollout contexts -> its handle (>= 1; InfgenRollout.token_mask), or -1 (infgen_last_error).  The
+ * pointers are kept, not the contents: table and selectors stay the caller's device buffers, and rewriting them changes what the
+ * next step - or the next replay of a captured graph - reads.  mask_type (three host ints, NULL = all -1) is copied.  type == NULL:
+ * the context's own row types.  The token_size-dependent checks happen when a context uses the handle (infgen_rollout_validate).
+ * infgen_token_mask_destroy frees the slot (0 on success); a context must not name a destroyed handle. */
+int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, const int* type);
+int infgen_token_mask_destroy(int handle);
 
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell

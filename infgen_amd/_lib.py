@@ -27,7 +27,7 @@ class InfgenHipError(RuntimeError):
 # ---- a reader for the restricted C of infgen_hip.h (its style rules are in the header's own comment block), not a C parser:
 # whatever it does not understand is an error that quotes the text, never a skipped declaration
 _SCALARS = {'int': _i, 'float': _f, 'double': C.c_double, 'unsigned': C.c_uint, 'long long': C.c_longlong,
-            'unsigned long long': C.c_ulonglong, 'uint8_t': C.c_ubyte, 'unsigned char': C.c_ubyte}
+            'unsigned long long': C.c_ulonglong, 'uint8_t': C.c_ubyte, 'unsigned char': C.c_ubyte, 'uint32_t': C.c_uint32}
 _TOP = re.compile(r'\s*(?:enum\s*\{(?P<enum>[^{};]*)\}\s*;'
                   r'|typedef\s+struct\s+(?P<tag>\w+)\s*\{(?P<body>[^{}]*)\}\s*(?P<name>\w+)\s*;'
                   r'|(?P<ret>[\w\s*]+?)\b(?P<fn>\w+)\s*\((?P<args>[^;{}()]*)\)\s*;)')

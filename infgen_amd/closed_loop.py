@@ -21,7 +21,7 @@ from typing import Dict
 
 import torch
 
-from . import _lib
+from . import _lib, constraints
 
 KIND_TOKEN, KIND_POSE = 0, 1
 
@@ -150,6 +150,29 @@ class ClosedLoopSession:
             self._mask.fill_(1)
         else:
             self._mask.copy_(self._rows(mask, torch.uint8, 'mask'))
+
+    def constrain(self, mask_row):
+        """the rows' allowed-token sets from the next ``advance()`` on: ``mask_row`` [S, A_cap] (or [S, rows <= A_cap]) set indices
+        into the engine's ``token_masks`` table, -1 = the row's type decides (the engine's ``token_mask_type``).  A device tensor is
+        copied into the engine's static selector buffer as it is - stream-ordered, no host read, so a controller can tighten or
+        release a row per step; an index beyond the table reads as unconstrained.  Rows the session controls keep their commands."""
+        self._check_open()
+        eng = self.eng
+        if eng.token_masks is None:
+            raise ValueError('constrain() needs an engine built with token_masks=')
+        x = torch.as_tensor(mask_row)
+        if x.is_floating_point() or x.dtype == torch.bool:
+            raise ValueError('mask_row holds integer set indices')
+        if not x.is_cuda:
+            constraints.check_row_selectors(x.numpy(), eng.token_masks.n_sets)
+        if x.dim() != 2 or x.shape[0] != eng.S or x.shape[1] > eng.A_cap:
+            raise ValueError(f'mask_row: expected shape {(eng.S, eng.A_cap)}, got {tuple(x.shape)}')
+        x = x.to(eng.device, torch.int32)
+        if x.shape[1] < eng.A_cap:
+            full = torch.full((eng.S, eng.A_cap), -1, dtype=torch.int32, device=eng.device)
+            full[:, :x.shape[1]] = x
+            x = full
+        eng.mask_row.copy_(x.reshape(-1))
 
     def advance(self):
         """the command kernel, then decode step ``t`` (with its insertion sub-loop when the engine inserts agents)"""

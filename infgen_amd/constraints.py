@@ -1,0 +1,146 @@
+"""Constrained decoding: per-row allowed-token sets for the motion-token heads (the token mask of
+include/infgen_hip.h).
+
+A ``TokenMasks`` is a mask table: ``n_sets`` sets of ``token_size`` bits, bit ``c`` set = token ``c`` allowed, packed into
+``token_size / 32`` little-endian uint32 words per set.  Which set a row takes is the caller's selection (per agent type, per row);
+the table itself knows nothing about rows.  Everything here runs on the host at construction: the table is a few KB.
+"""
+from __future__ import annotations
+
+from typing import Mapping, Optional, Sequence, Union
+
+import numpy as np
+
+TYPE_NAMES = ('veh', 'ped', 'cyc')        # the row types 0, 1, 2 (engine.py stacks the vocabulary in this order)
+RULES = ('max_speed', 'min_speed', 'no_reverse', 'max_yaw_rate')
+STEP_SECONDS = 0.5                        # one motion token spans 0.5 s (six contours, 0.1 s apart)
+
+
+def pack_bits(allowed: np.ndarray) -> np.ndarray:
+    """bool [n_sets][token_size] -> uint32 [n_sets][token_size / 32], bit c % 32 of word c / 32 = allowed[c]"""
+    allowed = np.asarray(allowed)
+    if allowed.ndim != 2 or allowed.dtype != np.bool_:
+        raise ValueError('token masks are boolean arrays [n_sets][token_size]')
+    if allowed.shape[1] == 0 or allowed.shape[1] % 32:
+        raise ValueError(f'token masks: token_size {allowed.shape[1]} is not a positive multiple of 32')
+    b = allowed.reshape(allowed.shape[0], -1, 32).astype(np.uint64)
+    return (b << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+
+
+def unpack_bits(words: np.ndarray) -> np.ndarray:
+    """the inverse of ``pack_bits``"""
+    words = np.asarray(words, dtype=np.uint32)
+    return ((words[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(np.bool_).reshape(words.shape[0], -1)
+
+
+def token_kinematics(vocab: Union[Mapping[str, np.ndarray], np.ndarray]):
+    """the motion vocabulary -> (speed [3][token_size] m/s along the agent's heading, negative = backwards; |speed| [3][token_size];
+    yaw rate [3][token_size] rad/s).  Per type and token the vocabulary holds six contours of four corners (front-left, front-right,
+    rear-right, rear-left) in the agent frame; the last contour's centre is the displacement over the 0.5 s step and its heading
+    (rear-left -> front-left) the yaw change"""
+    v = np.stack([vocab[k] for k in TYPE_NAMES]) if isinstance(vocab, Mapping) else np.asarray(vocab)
+    if v.ndim != 5 or v.shape[0] != 3 or v.shape[2:] != (6, 4, 2):
+        raise ValueError(f'the motion vocabulary is [3][token_size][6][4][2], not {v.shape}')
+    last = v[:, :, -1].astype(np.float64)                    # [3][token_size][4][2]
+    centre = last.mean(axis=2)
+    yaw = np.arctan2(last[:, :, 0, 1] - last[:, :, 3, 1], last[:, :, 0, 0] - last[:, :, 3, 0])
+    return centre[..., 0] / STEP_SECONDS, np.hypot(centre[..., 0], centre[..., 1]) / STEP_SECONDS, yaw / STEP_SECONDS
+
+
+class TokenMasks:
+    """a mask table (see the module's text).  ``TokenMasks(allowed)`` takes boolean arrays [n_sets][token_size];
+    ``TokenMasks.from_vocab(vocab, rules)`` derives one set per agent type from the motion vocabulary.  ``names[i]`` says what set i
+    is (for error messages); ``type_sets`` is the per-type selection ``from_vocab`` produced ([-1, -1, -1] otherwise)"""
+
+    def __init__(self, allowed, names: Optional[Sequence[str]] = None, type_sets: Sequence[int] = (-1, -1, -1)):
+        allowed = np.asarray(allowed)
+        if allowed.ndim == 1:
+            allowed = allowed[None]
+        self.words = pack_bits(allowed)                       # (raises on a wrong shape or width)
+        self.n_sets, self.token_size = int(allowed.shape[0]), int(allowed.shape[1])
+        self.names = [f'set {i}' for i in range(self.n_sets)] if names is None else list(names)
+        if len(self.names) != self.n_sets:
+            raise ValueError('token masks: one name per set')
+        for i in np.flatnonzero(~allowed.any(axis=1)):
+            raise ValueError(f'token masks: {self.names[i]} allows no token')
+        self.type_sets = check_type_selectors(type_sets, self.n_sets)
+        self._bits = {}
+
+    @property
+    def allowed(self) -> np.ndarray:
+        return unpack_bits(self.words)
+
+    @property
+    def bits(self):
+        """the packed table as a torch.uint32 tensor [n_sets][token_size / 32] (host memory)"""
+        import torch
+        return torch.from_numpy(self.words.view(np.int32).copy()).view(torch.uint32)
+
+    def key(self):
+        """a hashable identity of the table and its per-type selection (engine caches)"""
+        return (self.n_sets, self.token_size, self.words.tobytes(), tuple(self.type_sets))
+
+    @classmethod
+    def from_vocab(cls, vocab, rules: Mapping) -> 'TokenMasks':
+        """one set per constrained agent type.  ``rules`` maps rule names (``max_speed`` / ``min_speed`` in m/s on the displacement's
+        length, ``no_reverse`` (bool: no token whose displacement points backwards), ``max_yaw_rate`` in rad/s on the yaw change's
+        magnitude) to values for every type, or type names (``'veh'``, ``'ped'``, ``'cyc'``) to such rule mappings:
+        ``{'max_speed': 15.0}``, ``{'veh': {'no_reverse': True}, 'ped': {'max_speed': 2.0}}``.  A type without rules gets no set
+        (``type_sets`` -1).  A rule that leaves a type without a token raises ValueError naming both."""
+        fwd, speed, yaw = token_kinematics(vocab)
+        per_type = {t: {} for t in TYPE_NAMES}
+        for k, val in rules.items():
+            if k in TYPE_NAMES:
+                if not isinstance(val, Mapping):
+                    raise ValueError(f'token masks: rules[{k!r}] must map rule names to values')
+                per_type[k].update(val)
+            elif k in RULES:
+                for t in TYPE_NAMES:
+                    per_type[t].setdefault(k, val)
+            else:
+                raise ValueError(f'token masks: unknown rule or type {k!r} (rules: {", ".join(RULES)}; types: {", ".join(TYPE_NAMES)})')
+        sets, names, type_sets = [], [], [-1, -1, -1]
+        for ti, t in enumerate(TYPE_NAMES):
+            if not per_type[t]:
+                continue
+            ok = np.ones(fwd.shape[1], dtype=np.bool_)
+            for rule, val in per_type[t].items():
+                if rule not in RULES:
+                    raise ValueError(f'token masks: unknown rule {rule!r} for type {t!r}')
+                if rule == 'max_speed':
+                    ok &= speed[ti] <= float(val)
+                elif rule == 'min_speed':
+                    ok &= speed[ti] >= float(val)
+                elif rule == 'no_reverse':
+                    ok &= (fwd[ti] >= 0.0) | (not val)
+                else:
+                    ok &= np.abs(yaw[ti]) <= float(val)
+                if not ok.any():
+                    raise ValueError(f'token masks: no {t!r} token is left after rule {rule!r} = {val!r}')
+            type_sets[ti] = len(sets)
+            sets.append(ok)
+            names.append(f'type {t!r} ({", ".join(per_type[t])})')
+        if not sets:
+            raise ValueError('token masks: no rule given')
+        return cls(np.stack(sets), names, type_sets)
+
+
+def check_type_selectors(sel, n_sets: int):
+    """host-side per-type selection -> [int, int, int], each -1 (unconstrained) or a set of the table"""
+    sel = [int(v) for v in sel]
+    if len(sel) != 3:
+        raise ValueError('token_mask_type takes three set indices (vehicle, pedestrian, cyclist; -1: unconstrained)')
+    for v in sel:
+        if v < -1 or v >= n_sets:
+            raise ValueError(f'token_mask_type {v} is outside the table\'s {n_sets} sets (-1: unconstrained)')
+    return sel
+
+
+def check_row_selectors(sel: np.ndarray, n_sets: int) -> np.ndarray:
+    """host-side per-row selection -> int32 array, each entry -1 (the row's type decides) or a set of the table"""
+    sel = np.asarray(sel)
+    if sel.dtype.kind not in 'iu':
+        raise ValueError('token_mask_row holds integer set indices')
+    if sel.size and (int(sel.min()) < -1 or int(sel.max()) >= n_sets):
+        raise ValueError(f'token_mask_row has entries outside -1 .. {n_sets - 1}')
+    return sel.astype(np.int32)

@@ -43,6 +43,50 @@ static int sampling_ctl(const char* where, const InfgenSampling* s, SamplingCtl*
   return 0;
 }
 
+// a token mask as the C ABI passes it (include/infgen_hip.h: five parameters, or a handle of infgen_token_mask_create)
+struct TokenMaskDesc { const uint32_t* bits; int n_sets; const int* mask_row; int mask_type[3]; const int* type; };
+static TokenMaskDesc token_mask_desc(const uint32_t* bits, int n_sets, const int* mask_row, const int* mask_type, const int* type) {
+  return TokenMaskDesc{bits, n_sets, mask_row, {mask_type ? mask_type[0] : -1, mask_type ? mask_type[1] : -1, mask_type ? mask_type[2] : -1}, type};
+}
+// the registered masks: slot h - 1 serves handle h (in_use false: free)
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; };
+static std::mutex g_mask_mu;
+static std::vector<TokenMaskSlot> g_masks;
+
+// TokenMaskDesc (NULL: none) -> the kernels' TokenMaskCtl.  out->bits stays NULL - the unmasked kernels, today's bits - unless the
+// table can constrain some row: a table, n_sets > 0, and per-row selectors or a per-type set
+static int token_mask_ctl(const char* where, const TokenMaskDesc* m, int token_size, TokenMaskCtl* out) {
+  *out = TOKEN_MASK_NONE;
+  if (!m) return 0;
+  if (m->n_sets < 0) return fail(where, "token mask: n_sets must be >= 0");
+  if (!m->bits || m->n_sets == 0) return 0;
+  const bool by_type = m->mask_type[0] >= 0 || m->mask_type[1] >= 0 || m->mask_type[2] >= 0;
+  if (by_type && !m->type) return fail(where, "token mask: a per-type set needs the rows' types");
+  if (token_size % 32) return fail(where, "token mask: token_size must be a multiple of 32");
+  if (reinterpret_cast<uintptr_t>(m->bits) & 15) return fail(where, "token mask: the table must be 16-byte aligned");
+  if (!by_type && !m->mask_row) return 0;
+  *out = TokenMaskCtl{m->bits, m->n_sets, m->mask_row, {m->mask_type[0], m->mask_type[1], m->mask_type[2]}, by_type ? m->type : nullptr};
+  return 0;
+}
+
+extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type,
+                                        const int* type) {
+  if (mask_n_sets < 0) { fail("infgen_token_mask_create", "token mask: n_sets must be >= 0"); return -1; }
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  size_t h = 0;
+  while (h < g_masks.size() && g_masks[h].in_use) ++h;
+  if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true};
+  return (int)h + 1;
+}
+extern "C" int infgen_token_mask_destroy(int handle) {
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use)
+    return fail("infgen_token_mask_destroy", "no such token mask");
+  g_masks[handle - 1].in_use = false;
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------- environment knobs
 // Experiment and diagnostic switches (tools/, profiles/): each is read once, when the library is loaded.
 static int env_int(const char* name, int dflt, bool* is_set = nullptr) {
@@ -1028,13 +1072,27 @@ extern "C" int infgen_match_map_tokens(const float* traj_pos, const float* theta
 }
 
 // the other split families on 64-row tiles (launch_attn_h is the model)
-static void launch_heads_h(const HeadsArgs& a, void* stream) {
-  auto kern = a.sample_k > 1
-      ? (a.token_logprob ? by_terms(k_heads_h<3, true, HEADS_KS>, k_heads_h_b16<1, true, HEADS_KS>, k_heads_h<1, true, HEADS_KS>)
-                         : by_terms(k_heads_h<3, false, HEADS_KS>, k_heads_h_b16<1, false, HEADS_KS>, k_heads_h<1, false, HEADS_KS>))
-      : (a.token_logprob ? by_terms(k_heads_h<3, true, 0>, k_heads_h_b16<1, true, 0>, k_heads_h<1, true, 0>)
-                         : by_terms(k_heads_h<3, false, 0>, k_heads_h_b16<1, false, 0>, k_heads_h<1, false, 0>));
-  hipLaunchKernelGGL(kern, dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
+template <bool MK> static auto heads_h_kernel(const HeadsArgs& a) {
+  return a.sample_k > 1
+      ? (a.token_logprob ? by_terms(k_heads_h<3, true, HEADS_KS, MK>, k_heads_h_b16<1, true, HEADS_KS, MK>, k_heads_h<1, true, HEADS_KS, MK>)
+                         : by_terms(k_heads_h<3, false, HEADS_KS, MK>, k_heads_h_b16<1, false, HEADS_KS, MK>, k_heads_h<1, false, HEADS_KS, MK>))
+      : (a.token_logprob ? by_terms(k_heads_h<3, true, 0, MK>, k_heads_h_b16<1, true, 0, MK>, k_heads_h<1, true, 0, MK>)
+                         : by_terms(k_heads_h<3, false, 0, MK>, k_heads_h_b16<1, false, 0, MK>, k_heads_h<1, false, 0, MK>));
+}
+template <class A> static Masked<A> with_mask(const A& a, const TokenMaskCtl& mask) {
+  Masked<A> m;
+  static_cast<A&>(m) = a;
+  m.mask = mask;
+  return m;
+}
+static void launch_heads_h(const HeadsArgs& a, const TokenMaskCtl& mask, void* stream) {
+  if (mask.bits) hipLaunchKernelGGL(heads_h_kernel<true>(a), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, with_mask(a, mask));
+  else hipLaunchKernelGGL(heads_h_kernel<false>(a), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
+}
+// k_heads (fp32, few rows)
+static void launch_heads_fp32(const HeadsArgs& a, const TokenMaskCtl& mask, dim3 grid, void* stream) {
+  if (mask.bits) hipLaunchKernelGGL(k_heads<true>, grid, dim3(NT), 0, (hipStream_t)stream, with_mask(a, mask));
+  else hipLaunchKernelGGL(k_heads<false>, grid, dim3(NT), 0, (hipStream_t)stream, a);
 }
 static void launch_map_head_h(const MapHeadArgs& a, void* stream) {
   hipLaunchKernelGGL(by_terms(k_map_head_h<3>, k_map_head_h_b16<1>, k_map_head_h<1>), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
@@ -1055,7 +1113,7 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
                       float* logits, int* next_token, int* next_state, unsigned long long* scratch, void* stream,
                       bool keys_stay = false, bool* split_used = nullptr, float* token_logprob = nullptr,
                       int sample_k = 0, const float* uniform = nullptr, float* sample_logprob = nullptr,
-                      const SamplingCtl& ctl = SAMPLING_DEFAULT) {
+                      const SamplingCtl& ctl = SAMPLING_DEFAULT, const TokenMaskCtl& mask = TOKEN_MASK_NONE) {
   if (split_used) *split_used = false;
   if (rows <= 0) return 0;
   if (token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
@@ -1075,7 +1133,7 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
         return fail("infgen_heads", "memset failed");
       a.part = scratch; a.nsplit = ns;
       { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(rows, token_size));
-        hipLaunchKernelGGL(k_heads, dim3(tiles, ns), dim3(NT), 0, (hipStream_t)stream, a);
+        launch_heads_fp32(a, mask, dim3(tiles, ns), stream);
         if (!keys_stay)
           hipLaunchKernelGGL(k_heads_finish, dim3(ceil_div(rows, NT)), dim3(NT), 0, (hipStream_t)stream, scratch, rows, next_token); }
       if (split_used) *split_used = true;
@@ -1083,8 +1141,8 @@ static int heads_impl(const float* X, int rows, const float* tok_pack, const flo
     }
   }
   { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(rows, token_size));
-    if (attn_split(rows)) launch_heads_h(a, stream);
-    else hipLaunchKernelGGL(k_heads, dim3(ceil_div(rows, TR)), dim3(NT), 0, (hipStream_t)stream, a); }
+    if (attn_split(rows)) launch_heads_h(a, mask, stream);
+    else launch_heads_fp32(a, mask, dim3(ceil_div(rows, TR)), stream); }
   return check_launch("infgen_heads");
 }
 
@@ -1117,12 +1175,14 @@ extern "C" int infgen_heads_logprob(const float* X, int rows, const float* tok_p
 }
 
 static int sample_topk_impl(const char* me, const float* logits, int rows, int n, int k, const float* uniform, int* token,
-                            float* sample_logprob, void* stream, const SamplingCtl& ctl = SAMPLING_DEFAULT, int* nucleus = nullptr) {
+                            float* sample_logprob, void* stream, const SamplingCtl& ctl = SAMPLING_DEFAULT, int* nucleus = nullptr,
+                            const TokenMaskCtl& mask = TOKEN_MASK_NONE) {
   if (rows <= 0) return 0;
   if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
   if (k > n) return fail(me, "k must not exceed n");      // (the k-th pick of fewer than k logits is no token)
   SampleArgs a{logits, rows, n, k, uniform, token, sample_logprob, ctl, nucleus};
-  hipLaunchKernelGGL(k_sample_topk, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
+  if (mask.bits) hipLaunchKernelGGL(k_sample_topk<true>, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, with_mask(a, mask));
+  else hipLaunchKernelGGL(k_sample_topk<false>, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
   return check_launch(me);
 }
 
@@ -1145,30 +1205,57 @@ extern "C" int infgen_sample_topk_ex(const float* logits, int rows, int n, int k
   return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, stream, ctl, nucleus);
 }
 
+// ... under a token mask (mask == NULL or inactive: infgen_sample_topk_ex)
+extern "C" int infgen_sample_topk_mask(const float* logits, int rows, int n, int k, const float* uniform, const InfgenSampling* sampling,
+                                       const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type,
+                                       const int* type, int* token, float* sample_logprob, int* nucleus, void* stream) {
+  const char* me = "infgen_sample_topk_mask";
+  SamplingCtl ctl = SAMPLING_DEFAULT;
+  TokenMaskCtl mk;
+  if (k > 1) RET_IF(sampling_ctl(me, sampling, &ctl));
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
+  RET_IF(token_mask_ctl(me, &md, n, &mk));
+  return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, stream, ctl, nucleus, mk);
+}
+
 // infgen_heads with the motion token drawn by top-k sampling (k_sample_topk's order and arithmetic) and, optionally, its two
 // log-probabilities: one launch of k_heads_h<TERMS, LP, HEADS_KS> where heads_sample_fused_for holds (logits optional); elsewhere
 // heads into the caller's logits, k_sample_topk and k_token_logprob over them.  k == 1 is the arg-max (the greedy variant)
 static int heads_sample_impl(const char* me, const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
                              const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token, int* next_state,
-                             float* token_logprob, float* sample_logprob, void* stream) {
+                             float* token_logprob, float* sample_logprob, void* stream, const TokenMaskDesc* mask = nullptr) {
   if (rows <= 0) return 0;
+  if (mask && k < 1) k = 1;      // (infgen_heads_sample_mask: k <= 1 is the masked arg-max)
   if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
   if (k > token_size) return fail(me, "k must not exceed token_size");
-  if (!uniform) return fail(me, "uniform is NULL");
+  if (!uniform && !(mask && k == 1)) return fail(me, "uniform is NULL");
+  TokenMaskCtl mk;
+  RET_IF(token_mask_ctl(me, mask, token_size, &mk));
   if (k == 1) {      // a point mass on the arg-max: the greedy kernels, and log 1
     if (sample_logprob && hipMemsetAsync(sample_logprob, 0, (size_t)rows * sizeof(float), (hipStream_t)stream) != hipSuccess)
       return fail(me, "memset failed");
-    if (token_logprob) return infgen_heads_logprob(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, token_logprob, stream);
-    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream);
+    if (token_logprob && !mk.bits)
+      return infgen_heads_logprob(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, token_logprob, stream);
+    if (token_logprob) {      // infgen_heads_logprob's two routes with the mask in the arg-max
+      if (attn_split(rows))
+        return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
+                          token_logprob, 0, nullptr, nullptr, SAMPLING_DEFAULT, mk);
+      if (!logits) return fail(me, "this row count takes k_heads: it needs a logits buffer [rows][token_size]");
+      RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr, nullptr,
+                        0, nullptr, nullptr, SAMPLING_DEFAULT, mk));
+      return infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream);
+    }
+    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr, nullptr,
+                      0, nullptr, nullptr, SAMPLING_DEFAULT, mk);
   }
   SamplingCtl ctl;
   RET_IF(sampling_ctl(me, sampling, &ctl));
   if (heads_sample_fused_for(O().attn_mode, rows, k))
     return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
-                      token_logprob, k, uniform, sample_logprob, ctl);
+                      token_logprob, k, uniform, sample_logprob, ctl, mk);
   if (!logits) return fail(me, "this row count or beam takes k_sample_topk: it needs a logits buffer [rows][token_size]");
   RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
-  RET_IF(sample_topk_impl(me, logits, rows, token_size, k, uniform, next_token, sample_logprob, stream, ctl));
+  RET_IF(sample_topk_impl(me, logits, rows, token_size, k, uniform, next_token, sample_logprob, stream, ctl, nullptr, mk));
   if (token_logprob) RET_IF(infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream));
   return 0;
 }
@@ -1186,6 +1273,18 @@ extern "C" int infgen_heads_sample_ex(const float* X, int rows, const float* tok
                                       int* next_state, float* token_logprob, float* sample_logprob, void* stream) {
   return heads_sample_impl("infgen_heads_sample_ex", X, rows, tok_pack, st_pack, token_size, k, uniform, sampling, logits, next_token,
                            next_state, token_logprob, sample_logprob, stream);
+}
+
+// ... under a token mask (mask == NULL or inactive: infgen_heads_sample_ex); k <= 1 is the masked arg-max
+extern "C" int infgen_heads_sample_mask(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
+                                        const float* uniform, const InfgenSampling* sampling, const uint32_t* mask_bits,
+                                        int mask_n_sets, const int* mask_row, const int* mask_type, const int* type, float* logits,
+                                        int* next_token, int* next_state, float* token_logprob, float* sample_logprob, void* stream) {
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
+  const TokenMaskDesc* mask = mask_bits ? &md : nullptr;      // (no table: infgen_heads_sample_ex, its argument checks included)
+  if (mask_n_sets < 0) return fail("infgen_heads_sample_mask", "token mask: n_sets must be >= 0");
+  return heads_sample_impl("infgen_heads_sample_mask", X, rows, tok_pack, st_pack, token_size, k, uniform, sampling, logits, next_token,
+                           next_state, token_logprob, sample_logprob, stream, mask);
 }
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) on the rows gather[k] of X.  Split arithmetic (k_map_head_h: one
@@ -1255,7 +1354,7 @@ static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src
 static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
-static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr) {
+static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, TokenMaskCtl* mask = nullptr) {
   if (!r) return fail(where, "null context");
   if (r->A_cap > 1024 || r->A_cap <= 0) return fail(where, "A_cap must be in 1..1024");
   if (r->A_cap % 32) return fail(where, "A_cap must be a multiple of 32");
@@ -1269,6 +1368,20 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   if (r->sample_k > 1 && r->sample_u) {      // (a greedy context ignores the sampling parameters)
     const InfgenSampling sp{r->sample_temperature, r->sample_top_p, r->sample_temp_row};
     RET_IF(sampling_ctl(where, &sp, ctl));
+  }
+  TokenMaskCtl own_mask;
+  if (!mask) mask = &own_mask;
+  *mask = TOKEN_MASK_NONE;
+  if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
+    TokenMaskDesc tm;
+    {
+      std::lock_guard<std::mutex> lk(g_mask_mu);
+      if (r->token_mask < 1 || (size_t)r->token_mask > g_masks.size() || !g_masks[r->token_mask - 1].in_use)
+        return fail(where, "token_mask is no handle of infgen_token_mask_create");
+      tm = g_masks[r->token_mask - 1].d;
+    }
+    if (!tm.type) tm.type = r->type;
+    RET_IF(token_mask_ctl(where, &tm, r->token_size, mask));
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
@@ -1854,7 +1967,8 @@ extern "C" int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless,
 
 extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
-  RET_IF(validate(r, "infgen_decode_step", &ctl));
+  TokenMaskCtl mask;
+  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
@@ -1877,9 +1991,9 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   // (tmp2 is scratch of the raw-feature stage, free here: the per-row keys of the split arg-max)
   RET_IF(heads_impl(r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token,
                     r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream, false, nullptr, lp_fused ? lp : nullptr,
-                    s_fused ? r->sample_k : 0, su, slp, ctl));
+                    s_fused ? r->sample_k : 0, su, slp, ctl, mask));
   if (sample && !s_fused)
-    RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream, ctl));
+    RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream, ctl, nullptr, mask));
   if (lp && !lp_fused) RET_IF(infgen_token_logprob(lg, rows, r->token_size, r->next_token, lp, stream));
   RET_IF(infgen_integrate(r, t, stream));
   RET_IF(infgen_raw_feature(r, c + 1, stream));
@@ -1893,12 +2007,13 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
 // (memset, k_heads, k_heads_finish, k_integrate, k_rawfeat_prep, k_fourier_h, k_mlpemb_h, memset, k_build_edges,
 // k_fourier_h_multi, k_attn_hs ...).  Same arithmetic on the same data as infgen_decode_step (tests compare the two).
 extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream) {
-  RET_IF(validate(r, "infgen_rollout_run"));
+  TokenMaskCtl mask;
+  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !r->token_logprob && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !r->token_logprob && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));

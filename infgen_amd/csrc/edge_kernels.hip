@@ -1129,12 +1129,17 @@ template __global__ void k_insert_finalize<false, false>(InsertFinalizeArgs);
 // the k most probable tokens in descending order, then inverse-CDF sampling over their
 // (re-normalised) probabilities with a caller-supplied uniform.  One wave per row.
 // sample_logprob (optional): the pick's log-probability under that re-normalised distribution.
+// MK: a per-row allowed-token set (SampleArgs.mask); banned columns are skipped, so with a allowed tokens the slots from a on
+// stay (-inf, TOPK_NONE) and the draw is over min(k, a) entries (topk_inverse_cdf_masked)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
+template <bool MK>
+__global__ __launch_bounds__(NT) void k_sample_topk(ArgsFor<SampleArgs, MK> a) {
   const int row = blockIdx.x * 4 + wave_id();
   if (row >= a.rows) return;
   const int lane = lane_id();
   const float* lg = a.logits + (size_t)row * a.n;
+  const unsigned* ms = nullptr;
+  if constexpr (MK) ms = token_mask_set(a.mask, row, a.n / 32);
   float topv[16];
   int topi[16];
   float prev_v = INFINITY;
@@ -1145,7 +1150,8 @@ __global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
     int bi = 0x7fffffff;
     for (int c = lane; c < a.n; c += 64) {
       const float v = lg[c];
-      const bool after = (v < prev_v) || (v == prev_v && c > prev_i);
+      bool after = (v < prev_v) || (v == prev_v && c > prev_i);
+      if constexpr (MK) after = after && (!ms || ((ms[c >> 5] >> (c & 31)) & 1u));
       if (after && (v > best || (v == best && c < bi))) { best = v; bi = c; }
     }
 #pragma unroll
@@ -1161,11 +1167,17 @@ __global__ __launch_bounds__(NT) void k_sample_topk(SampleArgs a) {
   float sum, it, top_p;
   int m;
   sampling_row(a.ctl, row, &it, &top_p);
-  const int pick = topk_inverse_cdf<16>(topv, a.k, a.uniform[row], it, top_p, &sum, &m);
-  a.token[row] = topi[pick];
+  int pick;
+  if constexpr (MK) pick = topk_inverse_cdf_masked<16>(topv, topi, a.k, a.uniform[row], it, top_p, &sum, &m);
+  else pick = topk_inverse_cdf<16>(topv, a.k, a.uniform[row], it, top_p, &sum, &m);
+  int tok = topi[pick];
+  if constexpr (MK) tok = tok == TOPK_NONE ? 0 : tok;      // (a set without a token breaks the table's contract: never an index beyond n)
+  a.token[row] = tok;
   if (a.sample_logprob) a.sample_logprob[row] = (topv[pick] - topv[0]) * it - logf(sum);
   if (a.nucleus) a.nucleus[row] = m;
 }
+template __global__ void k_sample_topk<false>(SampleArgs);
+template __global__ void k_sample_topk<true>(Masked<SampleArgs>);
 
 // ------------------------------------------------------------------------------------------
 // k_token_logprob: log_softmax(logits[row])[token[row]] - the full-softmax log-probability of the token a step emitted, from

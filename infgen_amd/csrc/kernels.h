@@ -1,5 +1,6 @@
 // Kernel argument blocks (plain structs, device pointers) and kernel declarations.
 #pragma once
+#include <type_traits>
 #include "tile.cuh"
 #include "layout.h"
 #include "../../include/infgen_hip.h"
@@ -307,6 +308,27 @@ struct MatchMapArgs {
 struct SamplingCtl { float temperature; float top_p; const float* temperature_row; };
 constexpr SamplingCtl SAMPLING_DEFAULT{1.0f, 1.0f, nullptr};
 
+// per-row allowed-token sets of the motion-token heads and samplers (the token mask of include/infgen_hip.h after the host's checks):
+// bits = n_sets sets of token_size / 32 little-endian words, bit c set = token c allowed.  bits == NULL: no mask (today's kernels)
+struct TokenMaskCtl { const unsigned* bits; int n_sets; const int* mask_row; int mask_type[3]; const int* type; };
+constexpr TokenMaskCtl TOKEN_MASK_NONE{nullptr, 0, nullptr, {-1, -1, -1}, nullptr};
+// the masked instantiations of a kernel take its argument block with the mask appended; the unmasked ones keep the block - and so
+// their code objects - exactly as they were
+template <class A> struct Masked : A { TokenMaskCtl mask; };
+template <class A, bool MK> using ArgsFor = std::conditional_t<MK, Masked<A>, A>;
+constexpr int TOPK_NONE = 0x7fffffff;     // the column of a top-k slot that holds no token (fewer allowed tokens than slots)
+
+// the row's set (its first word), NULL where the row is unconstrained: mask_row[row] >= 0 wins, else mask_type[type[row]]; an index
+// beyond the table reads as unconstrained, so nothing outside bits[0 .. n_sets * words) is ever read
+__device__ __forceinline__ const unsigned* token_mask_set(const TokenMaskCtl& m, int row, int words) {
+  int s = m.mask_row ? m.mask_row[row] : -1;
+  if (s < 0 && m.type) {
+    const int ty = m.type[row];
+    s = ty == 0 ? m.mask_type[0] : ty == 1 ? m.mask_type[1] : ty == 2 ? m.mask_type[2] : -1;
+  }
+  return (s >= 0 && s < m.n_sets) ? m.bits + (size_t)s * words : nullptr;
+}
+
 struct HeadsArgs {
   const float* X; int rows;
   const float* tok_pack;    // MLPLayer pack: P(128,128) W0, b0, ln g/b, P(128,2048) W3, b3
@@ -329,6 +351,8 @@ struct HeadsArgs {
   float* sample_logprob;
   SamplingCtl ctl;          // (KS > 0 only) temperature / top-p of the draw, read once per row next to uniform[row]
 };
+// (the masked instantiations k_heads_h<TERMS, LP, KS, true> and k_heads<true> take Masked<HeadsArgs>: a banned column's logit counts
+// as -inf for the arg-max, the running top-k and the draw; stored logits and token_logprob stay the model's own)
 constexpr int HEADS_KS = 16;      // the one sampling width k_heads_h is instantiated with (wider beams take k_sample_topk)
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) over gathered rows: logits and the 10 most probable tokens
@@ -512,7 +536,7 @@ struct SampleArgs {
   float* sample_logprob;                     // optional [rows] out: log-probability of token[row] under the sampler's own distribution
   SamplingCtl ctl;                           // temperature / top-p
   int* nucleus;                              // optional [rows] out: the nucleus size m (k when top_p = 1; 1 on a greedy row)
-};
+};      // (k_sample_topk<true> takes Masked<SampleArgs>: banned columns are never picked; n a multiple of 32)
 
 // the row's (1 / T, top_p) for topk_inverse_cdf, read once per row.  A greedy row (T == 0; anything below the smallest normal float
 // counts: 1 / T of a denormal overflows, and 0 * inf would poison the row - the host entries refuse such values) is the
@@ -567,6 +591,17 @@ __device__ __forceinline__ int topk_inverse_cdf(const float (&topv)[KMAX], int k
   return pick;
 }
 
+// topk_inverse_cdf under a token mask: with a allowed tokens the lists hold min(k, a) entries and TOPK_NONE columns behind them; the
+// draw is over those min(k, a) only, so no uniform - 1 - 2^-24 and step 3's "else m - 1" included - lands on a slot without a token
+template <int KMAX>
+__device__ __forceinline__ int topk_inverse_cdf_masked(const float (&topv)[KMAX], const int (&topi)[KMAX], int k, float u01, float it,
+                                                       float top_p, float* sum_out, int* m_out) {
+  int live = 0;
+#pragma unroll
+  for (int j = 0; j < KMAX; ++j) live += (j < k && topi[j] != TOPK_NONE) ? 1 : 0;
+  return topk_inverse_cdf<KMAX>(topv, live > 1 ? live : 1, u01, it, top_p, sum_out, m_out);
+}
+
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]
   const int* token;                          // [rows]
@@ -601,7 +636,7 @@ __global__ void k_window_loglik(WindowLoglikArgs a);
 __global__ void k_bundle_field(BundleScoreArgs a);
 __global__ void k_bundle_meta(BundleScoreArgs a);
 __global__ void k_road_edge(RoadEdgeArgs a);
-template <int TERMS, bool LP = false, int KS = 0> __global__ void k_heads_h(HeadsArgs a);   // LP: + token_logprob; KS > 0: + top-k sampling
+template <int TERMS, bool LP = false, int KS = 0, bool MK = false> __global__ void k_heads_h(ArgsFor<HeadsArgs, MK> a);   // LP: + token_logprob; KS > 0: + top-k sampling; MK: + token mask
 template <int TERMS> __global__ void k_map_head_h(MapHeadArgs a);     // mlp_h.hip
 template <int TERMS> __global__ void k_map_head_h_b16(MapHeadArgs a);
 __global__ void k_map_topk(MapHeadArgs a);
@@ -617,7 +652,7 @@ template <int WAVES, int TERMS> __global__ void k_attn_h(AttnHArgs a);
 template <int WAVES, int TERMS> __global__ void k_attn_h_b16(AttnHArgs a);
 template <int TERMS> __global__ void k_attn_hs_b16(AttnHArgs a);
 template <int TERMS> __global__ void k_mlpemb_h_b16(MlpEmbHArgs a);
-template <int TERMS, bool LP, int KS> __global__ void k_heads_h_b16(HeadsArgs a);          // (no default: mlp_h_b16.hip renames k_heads_h to this)
+template <int TERMS, bool LP, int KS, bool MK> __global__ void k_heads_h_b16(ArgsFor<HeadsArgs, MK> a);          // (no default: mlp_h_b16.hip renames k_heads_h to this)
 template <int TERMS> __global__ void k_fourier_h_b16(FourierArgs a);
 template <int TERMS> __global__ void k_fourier_h_multi_b16(FourierMultiArgs m);
 template <int TERMS> __global__ void k_attn_hs(AttnHArgs a);             // attn_hs.hip: the same for few rows (one 16-row group per workgroup)   // attn_h.hip     // fourier_h.hip: fp16 three-term split, register resident
@@ -628,7 +663,7 @@ template <int G, bool R24, int HALVES, int WAVES> __global__ void k_edge_fused(E
 template <bool R24, int ROWS> __global__ void k_layers_p(LayersPArgs a);          // layers_p.hip
 __global__ void k_edge_attn_wide(EdgeAttnArgs a);
 __global__ void k_attn_post(AttnPostArgs a);
-__global__ void k_heads(HeadsArgs a);
+template <bool MK> __global__ void k_heads(ArgsFor<HeadsArgs, MK> a);
 template <int BT> __global__ void k_build_edges(BuildEdgesArgs a);
 template <int BT> __global__ void k_integrate(IntegrateArgs a);
 __global__ void k_rawfeat_prep(RawFeatArgs a);
@@ -652,7 +687,7 @@ __global__ void k_occupancy_embed(OccEmbedArgs a);
 template <bool kGrid> __global__ void k_insert_decide(InsertDecideArgs a);
 // kHeadToken = false: use_head_token = False (tanh * pi heading, unwrapped); kOffset = false: no xy offset (use_grid_token = False)
 template <bool kHeadToken, bool kOffset> __global__ void k_insert_finalize(InsertFinalizeArgs a);
-__global__ void k_sample_topk(SampleArgs a);
+template <bool MK> __global__ void k_sample_topk(ArgsFor<SampleArgs, MK> a);
 __global__ void k_token_logprob(TokenLogprobArgs a);
 __global__ void k_layernorm(const float* X, int rows, const float* g, const float* b, float* Y);
 __global__ void k_radius_edges(RadiusEdgesArgs a);            // forward_kernels.hip

@@ -249,8 +249,10 @@ __global__ __launch_bounds__(NT, 2) void k_attn_pre(AttnPreArgs a) {
 // logits store; state_predict_head (128 -> 128 LN ReLU -> 3) arg-max.
 // reference agent_decoder.py:2161-2167 (greedy: motion_beam_size = 1)
 // MLPLayer pack: [0] P(128,128) W0 | [16384] b0 | [16512] ln g | [16640] ln b | [16768] W3 ... | b3
+// MK: a per-row allowed-token set (HeadsArgs.mask); a banned column's logit counts as -inf before the (max, first index) is formed
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT, 2) void k_heads(HeadsArgs a) {
+template <bool MK>
+__global__ __launch_bounds__(NT, 2) void k_heads(ArgsFor<HeadsArgs, MK> a) {
   __shared__ __attribute__((aligned(16))) float Xs[TR * LDT];
   __shared__ __attribute__((aligned(16))) float Hs[TR * LDT];
   __shared__ float red_v[4][TR];
@@ -258,6 +260,13 @@ __global__ __launch_bounds__(NT, 2) void k_heads(HeadsArgs a) {
   const int row0 = blockIdx.x * TR;
   const int nvalid = min(TR, a.rows - row0);
   if (nvalid <= 0) return;
+  // MK: the rows' sets (NULL: unconstrained) in LDS, staged before the first barrier (the unmasked kernel declares nothing)
+  const unsigned** mset = nullptr;
+  if constexpr (MK) {
+    __shared__ const unsigned* mset_s[TR];
+    mset = mset_s;
+    if (threadIdx.x < TR) mset[threadIdx.x] = (int)threadIdx.x < nvalid ? token_mask_set(a.mask, row0 + threadIdx.x, a.token_size / 32) : nullptr;
+  }
   const int w = wave_id(), n0 = 32 * w, lane = lane_id();
   BHalf cur = b_load_half(a.tok_pack, 128, n0, 0);
   stage_rows_128(Xs, [&](int r) { return a.X + (size_t)(row0 + r) * D; }, nvalid);
@@ -293,7 +302,9 @@ __global__ __launch_bounds__(NT, 2) void k_heads(HeadsArgs a) {
         const float v = acc2[reg] + bb;
         const int r = acc_row(reg);
         if (a.logits && r < nvalid) a.logits[(size_t)(row0 + r) * a.token_size + col] = v;
-        if (v > bv[reg]) { bv[reg] = v; bi[reg] = col; }
+        bool ok = true;
+        if constexpr (MK) { const unsigned* ms = mset[r]; ok = !ms || ((ms[col >> 5] >> (col & 31)) & 1u); }
+        if (ok && v > bv[reg]) { bv[reg] = v; bi[reg] = col; }
       }
     }
     // reduce over the 32 lanes (columns) that share a row; ties -> smaller index
@@ -354,6 +365,8 @@ __global__ __launch_bounds__(NT, 2) void k_heads(HeadsArgs a) {
     }
   }
 }
+template __global__ void k_heads<false>(HeadsArgs);
+template __global__ void k_heads<true>(Masked<HeadsArgs>);
 
 __global__ __launch_bounds__(NT) void k_heads_finish(const unsigned long long* part, int rows, int* next_token) {
   const int r = blockIdx.x * NT + threadIdx.x;

@@ -7,6 +7,7 @@
 //               LP = true: also the full-softmax log-probability of the arg-max token (log-sum-exp beside the running arg-max)
 //               KS > 0: top-k sampling (agent_decoder.py:2162-2163, 2194-2195) instead of the arg-max - a running top-KS per lane
 //               beside the running arg-max, merged over the row's four lanes after the last chunk, then k_sample_topk's inverse CDF
+//               MK: a per-row allowed-token set (TokenMaskCtl); a banned column counts as -inf for the arg-max, the top-KS and the draw
 #include "kernels.h"
 #include "layout.h"
 #include "tile.cuh"
@@ -117,8 +118,8 @@ template <int KS> __device__ __forceinline__ void topk_insert(float (&tv)[KS], i
   }
 }
 
-template <int TERMS, bool LP, int KS>
-__global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
+template <int TERMS, bool LP, int KS, bool MK>
+__global__ __launch_bounds__(MH_NT, 2) void k_heads_h(ArgsFor<HeadsArgs, MK> a) {
   __shared__ __attribute__((aligned(16))) unsigned short Wb[MH_RING][QUARTER];
   // token head: hdr | b0 g0 be0 ; state head: hdr | b0 g0 be0 | W3 [3][128] | b3 [3]
   __shared__ __attribute__((aligned(16))) float Vt[16 + 384 + 16 + 384 + 384 + 16];
@@ -186,6 +187,12 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
     const float inv_h = frags_scaled(ht, Bh, Bl) * Vt[1];
     float bv = -INFINITY;
     int bidx = 0x7fffffff;
+    // MK: the row's set (NULL: unconstrained).  Per chunk the lane reads the chunk's four words once and keeps the 32 bits of its own
+    // columns (bit 4 t + e: column 128 c + 16 t + 4 rg + e) in one register.  Under a mask the arg-max value is no longer the
+    // maximum, so LP carries the true running maximum rmax for the log-sum-exp (without a mask bv IS it)
+    const unsigned* mset = nullptr;
+    if constexpr (MK) { if (valid) mset = token_mask_set(a.mask, row, a.token_size / 32); }
+    float rmax = -INFINITY;
     // LP: sum of exp(v - bv) over the lane's columns so far (bv, the running arg-max value, is their maximum); rescaled once per
     // 128-wide chunk, whose 32 logits of the lane wait in lg until the chunk's maximum is known
     float lse = 0.f;
@@ -202,7 +209,17 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
     for (int c = 0; c < nchunk; ++c) {
       f32x4 lg[8];
       mh_zero(lg);
-      const float m_prev = bv;
+      const float m_prev = MK ? rmax : bv;
+      unsigned lm = 0xffffffffu;
+      if constexpr (MK) {
+        if (mset) {
+          const uint4 mw = *reinterpret_cast<const uint4*>(mset + 4 * c);
+          const int sh = 4 * rg;
+          lm = ((mw.x >> sh) & 0xfu) | (((mw.x >> (16 + sh)) & 0xfu) << 4) | (((mw.y >> sh) & 0xfu) << 8) |
+               (((mw.y >> (16 + sh)) & 0xfu) << 12) | (((mw.z >> sh) & 0xfu) << 16) | (((mw.z >> (16 + sh)) & 0xfu) << 20) |
+               (((mw.w >> sh) & 0xfu) << 24) | (((mw.w >> (16 + sh)) & 0xfu) << 28);
+        }
+      }
 #pragma unroll
       for (int s = 0; s < 4; ++s) gemm_quarter<TERMS>(lg, qs.take(), Bh[s], Bl[s], lane);
 #pragma unroll
@@ -213,16 +230,36 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
         const float v2 = lg[t][2] * inv_h + bb.z, v3 = lg[t][3] * inv_h + bb.w;
         if (a.logits && valid)
           *reinterpret_cast<float4*>(a.logits + (size_t)row * a.token_size + col) = make_float4(v0, v1, v2, v3);
-        if (v0 > bv) { bv = v0; bidx = col; }
-        if (v1 > bv) { bv = v1; bidx = col + 1; }
-        if (v2 > bv) { bv = v2; bidx = col + 2; }
-        if (v3 > bv) { bv = v3; bidx = col + 3; }
-        if constexpr (LP) lg[t] = f32x4{v0, v1, v2, v3};
-        if constexpr (KS > 0) {
-          if (v0 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v0, col);
-          if (v1 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v1, col + 1);
-          if (v2 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v2, col + 2);
-          if (v3 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v3, col + 3);
+        if constexpr (!MK) {
+          if (v0 > bv) { bv = v0; bidx = col; }
+          if (v1 > bv) { bv = v1; bidx = col + 1; }
+          if (v2 > bv) { bv = v2; bidx = col + 2; }
+          if (v3 > bv) { bv = v3; bidx = col + 3; }
+          if constexpr (LP) lg[t] = f32x4{v0, v1, v2, v3};
+          if constexpr (KS > 0) {
+            if (v0 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v0, col);
+            if (v1 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v1, col + 1);
+            if (v2 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v2, col + 2);
+            if (v3 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v3, col + 3);
+          }
+        } else {
+          // the same comparisons in the same order, a banned column's logit read as -inf (it never beats bv, and never enters a list)
+          const unsigned nb = lm >> (4 * t);
+          const bool a0 = nb & 1u, a1 = nb & 2u, a2 = nb & 4u, a3 = nb & 8u;
+          if (a0 && v0 > bv) { bv = v0; bidx = col; }
+          if (a1 && v1 > bv) { bv = v1; bidx = col + 1; }
+          if (a2 && v2 > bv) { bv = v2; bidx = col + 2; }
+          if (a3 && v3 > bv) { bv = v3; bidx = col + 3; }
+          if constexpr (LP) {
+            lg[t] = f32x4{v0, v1, v2, v3};
+            rmax = fmaxf(fmaxf(rmax, fmaxf(v0, v1)), fmaxf(v2, v3));
+          }
+          if constexpr (KS > 0) {
+            if (a0 && v0 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v0, col);
+            if (a1 && v1 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v1, col + 1);
+            if (a2 && v2 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v2, col + 2);
+            if (a3 && v3 >= thr) topk_insert<KS>(tv, ti, a.sample_k, v3, col + 3);
+          }
         }
       }
       if constexpr (KS > 0) {
@@ -233,28 +270,42 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
         thr = fmaxf(thr, __shfl_xor(thr, 32, 64));
       }
       if constexpr (LP) {
-        lse *= expf(m_prev - bv);                    // (first chunk: exp(-inf) = 0 times 0)
+        const float mx = MK ? rmax : bv;
+        lse *= expf(m_prev - mx);                    // (first chunk: exp(-inf) = 0 times 0)
 #pragma unroll
         for (int t = 0; t < 8; ++t)
-          lse += (expf(lg[t][0] - bv) + expf(lg[t][1] - bv)) + (expf(lg[t][2] - bv) + expf(lg[t][3] - bv));
+          lse += (expf(lg[t][0] - mx) + expf(lg[t][1] - mx)) + (expf(lg[t][2] - mx) + expf(lg[t][3] - mx));
       }
     }
 #pragma unroll
     for (int off = 16; off < 64; off <<= 1) {
       const float ov = __shfl_xor(bv, off, 64);
       const int oi = __shfl_xor(bidx, off, 64);
-      if constexpr (LP) {                            // the row's four lanes in a fixed order: xor 16, then 32
+      if constexpr (LP && !MK) {                     // the row's four lanes in a fixed order: xor 16, then 32
         const float os = __shfl_xor(lse, off, 64);
         const float m = fmaxf(bv, ov);
         lse = lse * expf(bv - m) + os * expf(ov - m);
       }
+      if constexpr (LP && MK) {                      // the same merge around the lanes' true maxima
+        const float os = __shfl_xor(lse, off, 64);
+        const float om = __shfl_xor(rmax, off, 64);
+        const float m = fmaxf(rmax, om);
+        lse = lse * expf(rmax - m) + os * expf(om - m);
+        rmax = m;
+      }
       if (ov > bv || (ov == bv && oi < bidx)) { bv = ov; bidx = oi; }
     }
     if constexpr (KS == 0) {
+      // (MK: a set without a token breaks the table's contract; such a row emits token 0, never an index beyond the vocabulary)
+      if constexpr (MK) bidx = bidx == TOPK_NONE ? 0 : bidx;
       if (valid && rg == 0) a.next_token[row] = bidx;
-      if constexpr (LP) {
+      if constexpr (LP && !MK) {
         // best - (max + log(sum)) with best == max by construction (the arg-max value IS the maximum): -log(sum), one rounding less
         if (valid && rg == 0) a.token_logprob[row] = -logf(lse);
+      }
+      if constexpr (LP && MK) {
+        // where the allowed arg-max is the row's maximum this is the unmasked kernel's -log(sum), bit for bit
+        if (valid && rg == 0) a.token_logprob[row] = bv == rmax ? -logf(lse) : bv - (rmax + logf(lse));
       }
     } else {
       // the row's top-KS from its four lanes' lists: KS rounds, each takes the best head under the total order (the lanes' columns
@@ -284,15 +335,18 @@ __global__ __launch_bounds__(MH_NT, 2) void k_heads_h(HeadsArgs a) {
       float sum, it = 1.0f, top_p = 1.0f;
       int m;
       if (valid) sampling_row(a.ctl, row, &it, &top_p);
-      const int pick = topk_inverse_cdf<KS>(mv, a.sample_k, valid ? a.uniform[row] : 0.f, it, top_p, &sum, &m);
+      int pick;
+      if constexpr (MK) pick = topk_inverse_cdf_masked<KS>(mv, mi, a.sample_k, valid ? a.uniform[row] : 0.f, it, top_p, &sum, &m);
+      else pick = topk_inverse_cdf<KS>(mv, a.sample_k, valid ? a.uniform[row] : 0.f, it, top_p, &sum, &m);
       float pv = mv[0];
       int pi = mi[0];
 #pragma unroll
       for (int q = 1; q < KS; ++q) { pv = q == pick ? mv[q] : pv; pi = q == pick ? mi[q] : pi; }
+      if constexpr (MK) pi = pi == TOPK_NONE ? 0 : pi;
       if (valid && rg == 0) {
         a.next_token[row] = pi;
         if (a.sample_logprob) a.sample_logprob[row] = (pv - mv[0]) * it - logf(sum);
-        if constexpr (LP) a.token_logprob[row] = pv - (bv + logf(lse));
+        if constexpr (LP) a.token_logprob[row] = pv - ((MK ? rmax : bv) + logf(lse));
       }
     }
   }
@@ -416,5 +470,16 @@ template __global__ void k_heads_h<1, false, 0>(HeadsArgs);
 template __global__ void k_heads_h<1, true, 0>(HeadsArgs);
 template __global__ void k_heads_h<1, false, HEADS_KS>(HeadsArgs);
 template __global__ void k_heads_h<1, true, HEADS_KS>(HeadsArgs);
+// the masked variants (HeadsArgs.mask)
+#if !IG_BF16_OPERANDS
+template __global__ void k_heads_h<3, false, 0, true>(Masked<HeadsArgs>);
+template __global__ void k_heads_h<3, true, 0, true>(Masked<HeadsArgs>);
+template __global__ void k_heads_h<3, false, HEADS_KS, true>(Masked<HeadsArgs>);
+template __global__ void k_heads_h<3, true, HEADS_KS, true>(Masked<HeadsArgs>);
+#endif
+template __global__ void k_heads_h<1, false, 0, true>(Masked<HeadsArgs>);
+template __global__ void k_heads_h<1, true, 0, true>(Masked<HeadsArgs>);
+template __global__ void k_heads_h<1, false, HEADS_KS, true>(Masked<HeadsArgs>);
+template __global__ void k_heads_h<1, true, HEADS_KS, true>(Masked<HeadsArgs>);
 
 }  // namespace ig

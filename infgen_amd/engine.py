@@ -20,7 +20,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, logprob, packing, scene_setup
+from . import _lib, constraints, logprob, packing, scene_setup
 from .scene_setup import EVAL_SHAPE, INVALID_SHAPE
 from .synth import INVALID, VALID, ENTER, EXIT, AGENT_SHAPE, RolloutConfig
 
@@ -554,7 +554,8 @@ class RolloutEngine:
                  use_graph: Optional[bool] = None, copies: int = 1, flags: Optional[Mapping[str, bool]] = None,
                  tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None,
                  token_logprob: bool = False, sample_logprob: bool = False,
-                 sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0):
+                 sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
+                 token_masks=None, token_mask_type=None, token_mask_row=None):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -583,7 +584,15 @@ class RolloutEngine:
         rewrites, so captured graphs replay the new values; rows scenario insertion appends take their scene's value.
         ``next_token_logprob`` stays the model's own full softmax at temperature 1.  ``insert_temperature`` / ``insert_top_p``: the
         same for the cell draw of scenario insertion (scalars; ``insert_k > 1``; a temperature of 0 is refused: the arg-max cell is
-        ``insert_k = 1``).  ``reload*(sample_top_p=...)`` changes the nucleus mass of an engine that exists.  The defaults are the plain samplers bit for bit."""
+        ``insert_k = 1``).  ``reload*(sample_top_p=...)`` changes the nucleus mass of an engine that exists.  The defaults are the plain samplers bit for bit.
+        ``token_masks`` / ``token_mask_type`` / ``token_mask_row``: constrained decoding (infgen_amd/constraints.py).
+        ``token_masks`` is a ``TokenMasks`` table of allowed-token sets; a generated row takes the set ``token_mask_row`` names
+        ([S][rows] host integers, range-checked here, or an int32 device tensor [S][A_cap] taken as it is; -1 = no choice of its own)
+        and otherwise the set of its type, ``token_mask_type`` (three set indices, -1 = unconstrained; default: the table's own
+        per-type selection, ``TokenMasks.type_sets``).  Rows scenario insertion appends follow their type.  Replayed, commanded and
+        teacher-forced rows, the state head and the insertion cell draw are left alone; logits and ``next_token_logprob`` stay the
+        model's own.  Table and per-row selectors live in static device buffers that ``reload*(token_masks=..., token_mask_row=...)``
+        rewrite, so captured graphs replay the new values.  None (the default): today's kernels, bit for bit."""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -762,6 +771,10 @@ class RolloutEngine:
             self.sample_u = torch.from_numpy(self._uniform_rows(sample_uniforms, amax)).to(dev)
         self._ctx = None
         self._load_temperature(sample_temperature, amax)
+        self.token_masks, self.token_mask_type = None, [-1, -1, -1]
+        self.mask_bits = self.mask_row = None             # static device buffers: [n_sets][token_size / 32] words, [S * A_cap] int32
+        self._mask_handle = 0                             # infgen_token_mask_create's handle of (mask_bits, mask_row, token_mask_type)
+        self._load_token_masks(token_masks, token_mask_type, token_mask_row)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -906,13 +919,91 @@ class RolloutEngine:
                 self.sample_temp_row.copy_(rows)
         self._apply_sampling()
 
+    def _load_token_masks(self, token_masks=None, token_mask_type=None, token_mask_row=None):
+        """constrained decoding into the engine (None: keep what is there).  Everything on the host is checked here, before any
+        launch; a device tensor of per-row selectors is taken as it is (the kernels read an index beyond the table as
+        unconstrained).  The table and the per-row selectors are written into static buffers (allocated once per table shape)."""
+        if token_masks is None and token_mask_type is None and token_mask_row is None:
+            return
+        S, A_cap = self.S, self.A_cap
+        if token_masks is not None:
+            if not isinstance(token_masks, constraints.TokenMasks):
+                raise ValueError('token_masks takes an infgen_amd.constraints.TokenMasks')
+            if token_masks.token_size != self.cfg.token_size:
+                raise ValueError(f'token_masks are {token_masks.token_size} tokens wide, the model\'s vocabulary holds {self.cfg.token_size}')
+            words = torch.from_numpy(token_masks.words.view(np.int32).copy())
+            if self.mask_bits is None or self.mask_bits.shape != words.shape:
+                self.mask_bits = words.to(self.device)
+                self._graph = self._wgraph = None      # (a captured graph holds the old table's address and size)
+            else:
+                self.mask_bits.copy_(words)
+            if token_mask_type is None and (self.token_masks is None or token_masks.n_sets != self.token_masks.n_sets):
+                token_mask_type = token_masks.type_sets
+            self.token_masks = token_masks
+        if self.token_masks is None:
+            raise ValueError('token_mask_type / token_mask_row need token_masks (a table of allowed-token sets)')
+        n_sets = self.token_masks.n_sets
+        if token_mask_type is not None:
+            sel = constraints.check_type_selectors(token_mask_type, n_sets)
+            if sel != self.token_mask_type:
+                self._graph = self._wgraph = None      # (a captured graph holds the old kernel arguments)
+            self.token_mask_type = sel
+        elif any(v >= n_sets for v in self.token_mask_type):
+            raise ValueError('the new token_masks hold fewer sets than token_mask_type selects')
+        if self.mask_row is None:
+            self.mask_row = torch.full((S * A_cap,), -1, dtype=torch.int32, device=self.device)
+            self._graph = self._wgraph = None
+        if token_mask_row is not None:
+            if isinstance(token_mask_row, torch.Tensor) and token_mask_row.is_cuda:
+                if tuple(token_mask_row.shape) != (S, A_cap) or token_mask_row.dtype != torch.int32:
+                    raise ValueError(f'a device token_mask_row is int32 [S={S}][A_cap={A_cap}]')
+                self.mask_row.copy_(token_mask_row.reshape(-1))
+            else:
+                r = constraints.check_row_selectors(np.asarray(token_mask_row), n_sets)
+                if r.ndim != 2 or r.shape[0] != S or r.shape[1] > A_cap:
+                    raise ValueError(f'token_mask_row {r.shape} does not fit [S={S}][rows <= {A_cap}]')
+                rows = np.full((S, A_cap), -1, np.int32)
+                rows[:, :r.shape[1]] = r
+                self.mask_row.copy_(torch.from_numpy(rows.reshape(-1)))
+        self._apply_token_masks()
+
+    def _apply_token_masks(self, validate: bool = True):
+        """the library's handle of (table, per-row selectors, per-type sets) into the context: registered again when one of the
+        three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing"""
+        if self._ctx is None or self.token_masks is None:
+            return
+        reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
+        if reg != getattr(self, '_mask_reg', None):
+            self._drop_mask_handle()
+            h = self.lib.infgen_token_mask_create(reg[0], reg[1], reg[2], (C.c_int * 3)(*reg[3]), None)
+            if h < 1:
+                _lib.check(-1, 'infgen_token_mask_create')
+            self._mask_handle, self._mask_reg = h, reg
+        self._ctx.token_mask = self._mask_handle
+        if validate:
+            _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
+
+    def _drop_mask_handle(self):
+        if getattr(self, '_mask_handle', 0):
+            self.lib.infgen_token_mask_destroy(self._mask_handle)
+            self._mask_handle, self._mask_reg = 0, None
+            if getattr(self, '_ctx', None) is not None:
+                self._ctx.token_mask = 0
+
+    def __del__(self):
+        try:
+            self._drop_mask_handle()
+        except Exception:      # (interpreter shutdown: the library may be gone)
+            pass
+
     def _apply_sampling(self):
         if self._ctx is not None:
             c = self._ctx
             c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
-    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None):
+    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None):
+        self._load_token_masks(*(token_masks or (None, None, None)))
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
@@ -982,7 +1073,7 @@ class RolloutEngine:
 
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
-               sample_temperature=None, sample_top_p=None):
+               sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -996,7 +1087,8 @@ class RolloutEngine:
             getattr(self, k).copy_(torch.from_numpy(arr[k]), non_blocking=False)
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
-        self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p)
+        self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
+                            (token_masks, token_mask_type, token_mask_row))
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1012,7 +1104,8 @@ class RolloutEngine:
 
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
-                      sample_temperature=None, sample_top_p=None) -> bool:
+                      sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None,
+                      token_mask_row=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -1026,7 +1119,8 @@ class RolloutEngine:
         if not self._setup_device(k, replay):
             return False
         self.scenes = scenes
-        self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p)
+        self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
+                            (token_masks, token_mask_type, token_mask_row))
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1087,7 +1181,7 @@ class RolloutEngine:
 
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
-                     sample_temperature=None, sample_top_p=None):
+                     sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1096,7 +1190,8 @@ class RolloutEngine:
             layout = read_batch_layout(batch, self.T, self.hc, self.lib.infgen_layout_query(_lib.Q_MAX_AGENTS))
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._end_session()
-        self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p)
+        self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
+                            (token_masks, token_mask_type, token_mask_row))
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -1609,6 +1704,7 @@ class RolloutEngine:
         c.sample_logprob = P(self.sample_logprob)
         self._ctx = c
         self._apply_sampling()
+        self._apply_token_masks(validate=False)      # (validated below, once the kernel switches and the scratch are in place)
         self._refresh_opts()
         _lib.check(self.lib.infgen_rollout_validate(C.byref(c)), 'infgen_rollout_validate')      # (the packs' headers, looked at afresh)
 

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import _lib, logprob, scene_setup
 from ..closed_loop import ClosedLoopSession
+from ..constraints import TokenMasks, check_type_selectors
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -384,6 +385,10 @@ class InfGenDecoder(nn.Module):
         self.sample_top_p = 1.0
         self.insert_temperature = 1.0
         self.insert_top_p = 1.0
+        # constrained decoding (RolloutEngine's token_masks / token_mask_type): None, a constraints.TokenMasks - its own
+        # per-type selection applies (TokenMasks.from_vocab) - or (TokenMasks, [vehicle, pedestrian, cyclist] set indices, -1 =
+        # unconstrained).  Generated rows only emit motion tokens of their type's set; part of the engine cache key
+        self.token_constraints = None
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -484,7 +489,16 @@ class InfGenDecoder(nn.Module):
         # (the cell draw's two scalars are fixed per engine and key it; the motion draw's go through reload*, like the uniforms)
         fixed = dict(insert_temperature=float(self.insert_temperature), insert_top_p=float(self.insert_top_p))
         live = dict(sample_temperature=temp, sample_top_p=float(self.sample_top_p))
-        return dict(fixed, **live), live, tuple(fixed.values())
+        key = tuple(fixed.values())
+        tc = self.token_constraints
+        if tc is not None:      # (fixed per engine: engines are not shared between different constraints)
+            masks, sel = tc if isinstance(tc, (tuple, list)) else (tc, None)
+            if not isinstance(masks, TokenMasks):
+                raise ValueError('token_constraints: None, a TokenMasks or (TokenMasks, three per-type set indices)')
+            sel = check_type_selectors(masks.type_sets if sel is None else sel, masks.n_sets)
+            fixed.update(token_masks=masks, token_mask_type=sel)
+            key += (masks.key(), tuple(sel))
+        return dict(fixed, **live), live, key
 
     @staticmethod
     def _drive(gen):

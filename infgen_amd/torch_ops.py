@@ -32,7 +32,7 @@ hands out as bytes; whole rollouts stay a C-ABI call, ``infgen_rollout_run``, dr
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -193,10 +193,38 @@ def _(logits, token):
     return logits.new_empty(logits.shape[0], dtype=torch.float32)
 
 
+def _token_mask(mask_bits, mask_row, mask_type, agent_type, n: int, token_size: int, dev):
+    """the ops' trailing mask arguments -> (the C entries' five mask arguments, tensors to keep alive): ``mask_bits`` (n_sets, token_size / 32)
+    packed 32-bit words (infgen_amd.constraints.TokenMasks.bits), ``mask_row`` (N,) int set per row (-1: the type's), ``mask_type``
+    three ints (-1: unconstrained), ``type`` (N,) int row types.  Shapes are checked here; set indices are the library's to read
+    (one beyond the table means unconstrained)"""
+    if mask_bits is None:
+        if mask_row is not None or mask_type is not None:
+            raise ValueError('mask_row / mask_type need mask_bits')
+        return (None, 0, None, None, None), ()
+    if token_size % 32 or mask_bits.dim() != 2 or mask_bits.shape[1] != token_size // 32 or mask_bits.element_size() != 4 \
+            or mask_bits.is_floating_point():
+        raise ValueError(f'mask_bits must be (n_sets, {token_size} / 32) 32-bit words')
+    mt = [-1, -1, -1] if mask_type is None else [int(v) for v in mask_type]
+    if len(mt) != 3:
+        raise ValueError('mask_type takes three set indices (vehicle, pedestrian, cyclist; -1: unconstrained)')
+    if any(v >= 0 for v in mt) and agent_type is None:
+        raise ValueError('a per-type token mask needs the rows\' types')
+    for name, t in (('mask_row', mask_row), ('type', agent_type)):
+        if t is not None and tuple(t.shape) != (n,):
+            raise ValueError(f'{name} must have one entry per row')
+    bits = mask_bits.to(dev).contiguous()
+    row = None if mask_row is None else mask_row.to(dev, torch.int32).contiguous()
+    ty = None if agent_type is None else agent_type.to(dev, torch.int32).contiguous()
+    return (_lib.ptr(bits), int(bits.shape[0]), _lib.ptr(row), (C.c_int * 3)(*mt), _lib.ptr(ty)), (bits, row, ty)
+
+
 @torch.library.custom_op('infgen_hip::heads_sample', mutates_args=())
 def heads_sample(x: torch.Tensor, tok_pack: torch.Tensor, st_pack: torch.Tensor, token_size: int, k: int, uniform: torch.Tensor,
                  want_logits: bool = False, want_logprob: bool = False, want_sample_logprob: bool = False,
-                 temperature: float = 1.0, top_p: float = 1.0, temperature_row: Optional[torch.Tensor] = None
+                 temperature: float = 1.0, top_p: float = 1.0, temperature_row: Optional[torch.Tensor] = None,
+                 mask_bits: Optional[torch.Tensor] = None, mask_row: Optional[torch.Tensor] = None,
+                 mask_type: Optional[List[int]] = None, type: Optional[torch.Tensor] = None
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """token_predict_head / state_predict_head with the motion token drawn by top-k sampling (agent_decoder.py:2162-2163, 2194-2195;
     ``infgen_heads_sample``): the ``k`` (1..16) best logits of a row in (value descending, column ascending) order, inverse CDF
@@ -205,10 +233,13 @@ def heads_sample(x: torch.Tensor, tok_pack: torch.Tensor, st_pack: torch.Tensor,
     log-probability under the re-normalised top-k distribution (N,).  Where the library samples inside the split heads kernel
     (``infgen_heads_sample_fused``) no logit reaches memory unless asked for; elsewhere the op holds the logits itself.
     ``temperature`` / ``top_p`` / ``temperature_row`` (N,): temperature and nucleus truncation of the draw (``InfgenSampling`` of
-    include/infgen_hip.h; a per-row temperature of 0 makes the row greedy); the full-softmax log-probability is not tempered"""
+    include/infgen_hip.h; a per-row temperature of 0 makes the row greedy); the full-softmax log-probability is not tempered.
+    ``mask_bits`` / ``mask_row`` / ``mask_type`` / ``type``: per-row allowed-token sets (the token mask of include/infgen_hip.h; ``_token_mask``): a
+    banned token is never emitted, the logits and the full-softmax log-probability stay the model's own"""
     if x.dim() != 2 or x.shape[1] != D or uniform.shape != x.shape[:1]:
         raise ValueError('heads_sample takes x (N, 128) and uniform (N,)')
     sp, _keep = _sampling(temperature, top_p, temperature_row, x.shape[0], x.device)
+    tm, _keep_mask = _token_mask(mask_bits, mask_row, mask_type, type, x.shape[0], int(token_size), x.device)
     ops = _ops(x.device)
     n = x.shape[0]
     tok = torch.zeros(n, device=x.device, dtype=torch.int32)
@@ -221,16 +252,18 @@ def heads_sample(x: torch.Tensor, tok_pack: torch.Tensor, st_pack: torch.Tensor,
     slp = torch.zeros(n if want_sample_logprob else 0, device=x.device)
     if n:
         u = uniform.to(x.device, torch.float32).contiguous()
-        _lib.check(ops.lib.infgen_heads_sample_ex(_lib.ptr(_f32(x)), n, _lib.ptr(_f32(tok_pack)), _lib.ptr(_f32(st_pack)),
-                                                  int(token_size), int(k), _lib.ptr(u), C.byref(sp), _lib.ptr(lg) if keep else None,
-                                                  _lib.ptr(tok), _lib.ptr(st), _lib.ptr(lp) if want_logprob else None,
-                                                  _lib.ptr(slp) if want_sample_logprob else None, ops.stream), 'infgen_heads_sample_ex')
+        _lib.check(ops.lib.infgen_heads_sample_mask(_lib.ptr(_f32(x)), n, _lib.ptr(_f32(tok_pack)), _lib.ptr(_f32(st_pack)),
+                                                    int(token_size), int(k), _lib.ptr(u), C.byref(sp),
+                                                    *tm, _lib.ptr(lg) if keep else None,
+                                                    _lib.ptr(tok), _lib.ptr(st), _lib.ptr(lp) if want_logprob else None,
+                                                    _lib.ptr(slp) if want_sample_logprob else None, ops.stream),
+                   'infgen_heads_sample_mask')
     return tok, st, (lg if want_logits else lg.new_empty(0, token_size)), lp, slp
 
 
 @heads_sample.register_fake
 def _(x, tok_pack, st_pack, token_size, k, uniform, want_logits=False, want_logprob=False, want_sample_logprob=False,
-      temperature=1.0, top_p=1.0, temperature_row=None):
+      temperature=1.0, top_p=1.0, temperature_row=None, mask_bits=None, mask_row=None, mask_type=None, type=None):
     n = x.shape[0]
     return (x.new_empty(n, dtype=torch.int32), x.new_empty(n, dtype=torch.int32),
             x.new_empty(n if want_logits else 0, token_size, dtype=torch.float32),
@@ -240,28 +273,34 @@ def _(x, tok_pack, st_pack, token_size, k, uniform, want_logits=False, want_logp
 
 @torch.library.custom_op('infgen_hip::sample_topk', mutates_args=())
 def sample_topk(logits: torch.Tensor, k: int, uniform: torch.Tensor, want_sample_logprob: bool = False,
-                temperature: float = 1.0, top_p: float = 1.0, temperature_row: Optional[torch.Tensor] = None
+                temperature: float = 1.0, top_p: float = 1.0, temperature_row: Optional[torch.Tensor] = None,
+                mask_bits: Optional[torch.Tensor] = None, mask_row: Optional[torch.Tensor] = None,
+                mask_type: Optional[List[int]] = None, type: Optional[torch.Tensor] = None
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """top-k sampling over stored logits (N, n) (``infgen_sample_topk_ex``; agent_decoder.py:2162-2163, 2194-2195): the ``k`` (1..16)
     best logits of a row, inverse CDF with ``uniform[row]``; ``temperature`` / ``top_p`` / ``temperature_row`` as in ``heads_sample``.
-    Returns the token (N,) and, on request (else empty), its log-probability under the sampler's own distribution (N,)"""
+    Returns the token (N,) and, on request (else empty), its log-probability under the sampler's own distribution (N,).
+    ``mask_bits`` / ``mask_row`` / ``mask_type`` / ``type`` as in ``heads_sample`` (``infgen_sample_topk_mask``; n a multiple of 32)"""
     if logits.dim() != 2 or uniform.shape != logits.shape[:1]:
         raise ValueError('sample_topk takes logits (N, n) and uniform (N,)')
     ops = _ops(logits.device)
     n = logits.shape[0]
     sp, _keep = _sampling(temperature, top_p, temperature_row, n, logits.device)
+    tm, _keep_mask = _token_mask(mask_bits, mask_row, mask_type, type, n, int(logits.shape[1]), logits.device)
     tok = torch.zeros(n, device=logits.device, dtype=torch.int32)
     slp = torch.zeros(n if want_sample_logprob else 0, device=logits.device)
     if n:
         lg, u = _f32(logits), uniform.to(logits.device, torch.float32).contiguous()
-        _lib.check(ops.lib.infgen_sample_topk_ex(_lib.ptr(lg), n, int(lg.shape[1]), int(k), _lib.ptr(u), C.byref(sp), _lib.ptr(tok),
-                                                 _lib.ptr(slp) if want_sample_logprob else None, None, ops.stream),
-                   'infgen_sample_topk_ex')
+        _lib.check(ops.lib.infgen_sample_topk_mask(_lib.ptr(lg), n, int(lg.shape[1]), int(k), _lib.ptr(u), C.byref(sp),
+                                                   *tm, _lib.ptr(tok),
+                                                   _lib.ptr(slp) if want_sample_logprob else None, None, ops.stream),
+                   'infgen_sample_topk_mask')
     return tok, slp
 
 
 @sample_topk.register_fake
-def _(logits, k, uniform, want_sample_logprob=False, temperature=1.0, top_p=1.0, temperature_row=None):
+def _(logits, k, uniform, want_sample_logprob=False, temperature=1.0, top_p=1.0, temperature_row=None, mask_bits=None, mask_row=None,
+      mask_type=None, type=None):
     n = logits.shape[0]
     return logits.new_empty(n, dtype=torch.int32), logits.new_empty(n if want_sample_logprob else 0, dtype=torch.float32)
 
