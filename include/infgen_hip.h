@@ -491,6 +491,54 @@ int infgen_sample_topk_mask(const float* logits, int rows, int n, int k, const f
 int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, const int* type);
 int infgen_token_mask_destroy(int handle);
 
+/* collision-aware decoding: COLLISION MASKS, the allowed-token sets of one decode step computed from the agents' boxes (k_collision_mask).
+ * At decode step t the current column is c = hist_columns - 1 + t (= 1 + t).  A row i of scene s is IN THE SCENE at column c when
+ * i < n_agents[s], i < first_new[s] where that array is given (rows scenario insertion appended inside this step), and state[c][i] is
+ * not invalid (0).  For such a row:
+ *   candidate box of token k   the last contour of vocab[type[i]][k], four corners in the agent frame: its centre is the mean of the
+ *       corners, its heading atan2(c0 - c3), front-left minus rear-left (the rule of infgen_integrate / infgen_command_rows); rotated by
+ *       head[c][i] and moved by pos[c][i].  The box is the row's OWN length x width, shape[i] = (length, width, height) - box_contour's
+ *       convention -, not the vocabulary's template box.
+ *   obstacles   every other row j != i of the scene that is in the scene at column c.  predict = 0: at its pose of column c.
+ *       predict = 1 and j also in the scene at column c - 1 (state[c - 1][j] not invalid): constant velocity, position
+ *       2 pos[c] - pos[c - 1], heading head[c] + wrap(head[c] - head[c - 1]) (the orientation of a box does not depend on the branch of
+ *       wrap); otherwise the pose of column c.  Half length and half width are each enlarged by `margin` metres.
+ *   overlap   the separating-axis test of two oriented rectangles over their four axes: sep = the maximum over the axes of
+ *       |projected centre distance| - the sum of the projected half extents; the boxes overlap iff sep < 0.  Evaluated in row i's
+ *       frame - pos[c][i] is subtracted from the obstacle's centre first - so magnitudes stay at tens of metres wherever the scene
+ *       lies in the world (fp32 throughout; a pair with |sep| below ~1e-4 m may fall either way).
+ *   result   set(i) = base(i) AND NOT collides(i), collides(i) = the tokens whose candidate box overlaps an obstacle; base(i) is the
+ *       static set the token mask's selectors name (mask_row, then mask_type[type]; all tokens when neither names one).  An empty
+ *       result is replaced by base(i): the heads kernels never meet an empty set.  out_count[i] (optional) is the number of allowed
+ *       tokens BEFORE that fallback - 0 says it was taken.
+ * Rows that are not in the scene at column c, and padding rows, get base(i) (out_count: its size).  Replayed, commanded and
+ * teacher-forced rows keep their plan's tokens, as under a static mask.
+ * Left out on purpose: the contours 0..4 inside the 0.5 s step (only its end is tested); the planned next pose of replayed rows (they
+ * are obstacles like every other row, at their current or extrapolated pose); map geometry; rows scenario insertion appends inside
+ * step t are obstacles, and get sets, from step t + 1 on - during step t they take their type's static set, as before.
+ *
+ * infgen_collision_end_poses: end_pose [3][token_size][4] = (dx, dy, cos dtheta, sin dtheta) of every token's last contour in the agent
+ * frame, followed by four floats: the largest displacement sqrt(dx^2 + dy^2) of the three types, and 0 - 12 token_size + 4 floats,
+ * 16-byte aligned, computed once per vocabulary ([3][token_size][6][4][2]).
+ * infgen_collision_mask: one launch writes out_bits [S * A_cap][token_size / 32] (16-byte aligned) and out_count (optional).  The scene
+ * arrays are laid out like InfgenRollout's ([S][T][A_cap]); A_cap need not be a multiple of 32.  The base is a token mask's first
+ * four values with the rows' own `type` (mask_bits NULL: every token).  first_new: optional [S].
+ * infgen_token_mask_collision: attaches a collision configuration to a registered token mask (one created with mask_bits NULL and
+ * mask_n_sets 0 has the base "every token"): infgen_decode_step of a context that names the handle then launches k_collision_mask for
+ * the step's column in front of the heads launch - base = the handle's static mask, out_bits = dyn_bits [S * A_cap][token_size / 32],
+ * first_new = the context's - and hands the heads route dyn_bits with the identity selector identity_row ([S * A_cap], entry i = i) and no
+ * per-type set.  The pointers are kept, not the contents (static device buffers: a captured graph replays what they hold then).
+ * dyn_bits NULL detaches: the launches and the bits are those of the static mask again.
+ * Refused: margin negative or not finite, predict outside {0, 1}, a missing shape array / end-pose table / output, a token_size that
+ * is no multiple of 32 or exceeds 4096, A_cap beyond INFGEN_Q_MAX_AGENTS, a misaligned table. */
+int infgen_collision_end_poses(const float* vocab, int token_size, float* end_pose, void* stream);
+int infgen_collision_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new,
+                          const int* type, const float* shape, int S, int A_cap, int T, int c, const float* end_pose, int token_size,
+                          int predict, float margin, const uint32_t* mask_bits, int mask_n_sets, const int* mask_row,
+                          const int* mask_type, uint32_t* out_bits, int* out_count, void* stream);
+int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const int* identity_row, const float* shape, const float* end_pose,
+                                int predict, float margin, int* count);
+
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell
  *   infgen_point_edges      _build_a2sa_edge / _build_map2sa_edge for one query point per scene (:760-904):

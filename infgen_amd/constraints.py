@@ -144,3 +144,42 @@ def check_row_selectors(sel: np.ndarray, n_sets: int) -> np.ndarray:
     if sel.size and (int(sel.min()) < -1 or int(sel.max()) >= n_sets):
         raise ValueError(f'token_mask_row has entries outside -1 .. {n_sets - 1}')
     return sel.astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------- collision-aware decoding
+def check_avoid_collisions(avoid, has_shape: bool = True):
+    """``avoid_collisions`` as the engine takes it -> None (off) or dict(margin=float, predict=0 | 1).  False / None: off; True: the
+    defaults (margin 0 m, constant-velocity obstacles); a mapping with the keys ``margin`` (metres, finite, >= 0) and / or ``predict``
+    (0 or 1 / False or True).  Everything is checked here, on the host, before any launch."""
+    if avoid is None or avoid is False:
+        return None
+    if avoid is True:
+        avoid = {}
+    if not isinstance(avoid, Mapping):
+        raise ValueError('avoid_collisions takes False, True or dict(margin=, predict=)')
+    unknown = set(avoid) - {'margin', 'predict'}
+    if unknown:
+        raise ValueError(f'avoid_collisions: unknown keys {sorted(unknown)} (margin, predict)')
+    margin, predict = avoid.get('margin', 0.0), avoid.get('predict', 1)
+    if isinstance(margin, (bool, str)) or not np.isscalar(margin) or not np.isfinite(margin) or margin < 0:
+        raise ValueError(f'avoid_collisions: margin must be a finite number of metres >= 0 (got {margin!r})')
+    if isinstance(predict, str) or predict not in (0, 1, False, True):
+        raise ValueError(f'avoid_collisions: predict must be 0 or 1 (got {predict!r})')
+    if not has_shape:
+        raise ValueError('avoid_collisions needs the rows\' shapes: this engine has no shape array')
+    return dict(margin=float(margin), predict=int(predict))
+
+
+def collision_buffers(conf, rows: int, token_size: int, device='cpu'):
+    """the static buffers of collision-aware decoding for ``rows`` = S * A_cap rows, or None when ``conf`` (``check_avoid_collisions``)
+    is off: ``bits`` [rows][token_size / 32] int32 (the sets of the step that just ran), ``allowed`` [rows] int32 (their sizes before
+    the empty-set fallback), ``ident`` [rows] int32 (row i names set i), ``shape`` [rows][3]"""
+    if conf is None:
+        return None
+    import torch
+    if token_size % 32 or token_size > 4096:
+        raise ValueError(f'avoid_collisions: token_size {token_size} must be a multiple of 32, at most 4096')
+    return dict(bits=torch.full((rows, token_size // 32), -1, dtype=torch.int32, device=device),
+                allowed=torch.full((rows,), token_size, dtype=torch.int32, device=device),
+                ident=torch.arange(rows, dtype=torch.int32, device=device),
+                shape=torch.zeros(rows, 3, dtype=torch.float32, device=device))

@@ -49,7 +49,10 @@ static TokenMaskDesc token_mask_desc(const uint32_t* bits, int n_sets, const int
   return TokenMaskDesc{bits, n_sets, mask_row, {mask_type ? mask_type[0] : -1, mask_type ? mask_type[1] : -1, mask_type ? mask_type[2] : -1}, type};
 }
 // the registered masks: slot h - 1 serves handle h (in_use false: free)
-struct TokenMaskSlot { TokenMaskDesc d; bool in_use; };
+// the collision configuration a registered mask may carry (infgen_token_mask_collision; bits == NULL: none)
+struct CollisionCfg { uint32_t* bits; const int* ident; const float* shape; const float* end_pose; int predict; float margin; int* count; };
+constexpr CollisionCfg COLLISION_NONE{nullptr, nullptr, nullptr, nullptr, 1, 0.f, nullptr};
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
 
@@ -76,7 +79,7 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   size_t h = 0;
   while (h < g_masks.size() && g_masks[h].in_use) ++h;
   if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
-  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true};
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE};
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
@@ -122,6 +125,7 @@ const int no_tail_fold = env_int("INFGEN_NO_TAIL_FOLD", 0);       // 1: infgen_r
 const int lp_max_chunks = env_int("INFGEN_LP_MAX_CHUNKS", 2);     // most k_layers_p launches a batch may be split into
 const int lp_max_groups = env_int("INFGEN_LP_MAX_GROUPS", 256);   // most workgroups of one k_layers_p launch
 const int lp_rows_min = env_lp_rows_min();                        // fewest rows per k_layers_p workgroup (4, 8 or 16)
+const int cm_rows = env_int("INFGEN_CM_ROWS", 0);                 // rows of a scene per k_collision_mask workgroup (0: by launch size)
 const int lp_trace = env_int("INFGEN_LP_TRACE", 0);               // n: dump the stamps of the n-th k_layers_p launch (tools/lp_trace.py)
 // polls at a scene counter before k_layers_p traps (layers_p_launch); any strtoul base, and set differs from unset
 const char* const lp_spin_str = getenv("INFGEN_LP_SPIN_LIMIT");
@@ -1339,6 +1343,72 @@ extern "C" int infgen_map_graph(int S, int M_cap, const int* n_map, const float*
   return check_launch("infgen_map_graph");
 }
 
+// ---------------------------------------------------------------------------------- collision masks
+// the argument checks of include/infgen_hip.h ("collision masks") and the one launch of k_collision_mask
+static int collision_check(const char* where, int predict, float margin, const float* shape, const float* end_pose, const uint32_t* bits) {
+  if (!std::isfinite(margin) || margin < 0.f) return fail(where, "collision mask: margin must be finite and >= 0");
+  if (predict != 0 && predict != 1) return fail(where, "collision mask: predict must be 0 or 1");
+  if (!shape) return fail(where, "collision mask: needs the rows' shape array [S][A_cap][3]");
+  if (!end_pose) return fail(where, "collision mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!bits) return fail(where, "collision mask: needs the output table");
+  if ((reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(end_pose)) & 15)
+    return fail(where, "collision mask: the tables must be 16-byte aligned");
+  return 0;
+}
+static int launch_collision(const char* where, CollisionArgs a, void* stream) {
+  RET_IF(collision_check(where, a.predict, a.margin, a.shape, a.end_pose, a.out_bits));
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "collision mask: S, A_cap and T must be positive");
+  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "collision mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.c < 0 || a.c >= a.T) return fail(where, "collision mask: column outside [0, T)");
+  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * CM_WPL)
+    return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "collision mask: null scene array");
+  // few rows: one row per wave and workgroup round; many: 16 rows share one staging of their scene's obstacles
+  int per = knob::cm_rows > 0 ? knob::cm_rows : ((long long)a.S * a.A_cap > 4096 ? 4 * CM_WAVES : CM_WAVES);
+  per = ceil_div(per, CM_WAVES) * CM_WAVES;
+  a.rows_per_wg = per;
+  const size_t lds = (size_t)CM_WAVES * 2 * CM_LIST * sizeof(float4) + (size_t)CM_STAGE * a.A_cap * sizeof(float);
+  hipLaunchKernelGGL(k_collision_mask, dim3(ceil_div(a.A_cap, per), a.S), dim3(64 * CM_WAVES), lds, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+
+extern "C" int infgen_collision_end_poses(const float* vocab, int token_size, float* end_pose, void* stream) {
+  const char* me = "infgen_collision_end_poses";
+  if (!vocab || !end_pose) return fail(me, "null pointer");
+  if (token_size <= 0) return fail(me, "token_size must be positive");
+  if ((reinterpret_cast<uintptr_t>(vocab) | reinterpret_cast<uintptr_t>(end_pose)) & 15) return fail(me, "the tables must be 16-byte aligned");
+  hipLaunchKernelGGL(k_collision_end_poses, dim3(3), dim3(256), 0, (hipStream_t)stream, EndPoseArgs{vocab, token_size, end_pose});
+  return check_launch(me);
+}
+
+extern "C" int infgen_collision_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new,
+                                     const int* type, const float* shape, int S, int A_cap, int T, int c, const float* end_pose,
+                                     int token_size, int predict, float margin, const uint32_t* mask_bits, int mask_n_sets,
+                                     const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, void* stream) {
+  const char* me = "infgen_collision_mask";
+  CollisionArgs a{};
+  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c;
+  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.first_new = first_new; a.type = type; a.shape = shape;
+  a.end_pose = end_pose; a.token_size = token_size; a.predict = predict; a.margin = margin;
+  a.out_bits = out_bits; a.out_count = out_count;
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
+  RET_IF(token_mask_ctl(me, &md, token_size, &a.base));
+  return launch_collision(me, a, stream);
+}
+
+extern "C" int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const int* identity_row, const float* shape,
+                                           const float* end_pose, int predict, float margin, int* count) {
+  const char* me = "infgen_token_mask_collision";
+  if (dyn_bits) {
+    RET_IF(collision_check(me, predict, margin, shape, end_pose, dyn_bits));
+    if (!identity_row) return fail(me, "collision mask: needs the identity selectors [S * A_cap]");
+  }
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(me, "no such token mask");
+  g_masks[handle - 1].coll = dyn_bits ? CollisionCfg{dyn_bits, identity_row, shape, end_pose, predict, margin, count} : COLLISION_NONE;
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------- rollout context
 static SceneState scene_of(const InfgenRollout* r) {
   SceneState st;
@@ -1354,7 +1424,8 @@ static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src
 static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
-static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, TokenMaskCtl* mask = nullptr) {
+static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, TokenMaskCtl* mask = nullptr,
+                    CollisionCfg* coll = nullptr) {
   if (!r) return fail(where, "null context");
   if (r->A_cap > 1024 || r->A_cap <= 0) return fail(where, "A_cap must be in 1..1024");
   if (r->A_cap % 32) return fail(where, "A_cap must be a multiple of 32");
@@ -1372,6 +1443,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   TokenMaskCtl own_mask;
   if (!mask) mask = &own_mask;
   *mask = TOKEN_MASK_NONE;
+  CollisionCfg own_coll;
+  if (!coll) coll = &own_coll;
+  *coll = COLLISION_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
     TokenMaskDesc tm;
     {
@@ -1379,9 +1453,12 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
       if (r->token_mask < 1 || (size_t)r->token_mask > g_masks.size() || !g_masks[r->token_mask - 1].in_use)
         return fail(where, "token_mask is no handle of infgen_token_mask_create");
       tm = g_masks[r->token_mask - 1].d;
+      *coll = g_masks[r->token_mask - 1].coll;
     }
     if (!tm.type) tm.type = r->type;
     RET_IF(token_mask_ctl(where, &tm, r->token_size, mask));
+    if (coll->bits && (r->token_size % 32 || r->token_size > 64 * 32 * CM_WPL))
+      return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
@@ -1968,13 +2045,23 @@ extern "C" int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless,
 extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
   TokenMaskCtl mask;
-  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask));
+  CollisionCfg coll;
+  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask, &coll));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const int c = 1 + t;
   if (t < 0 || c + 1 > r->T - 1) return fail("infgen_decode_step", "step beyond the column range");
   RET_IF(infgen_decode_layers(r, c, 0, stream));
+  if (coll.bits) {      // collision-aware decoding: this column's sets from the boxes, then the heads read them row by row
+    CollisionArgs ca{};
+    ca.S = r->S; ca.A_cap = r->A_cap; ca.T = r->T; ca.c = c;
+    ca.pos = r->pos; ca.head = r->head; ca.state = r->state; ca.n_agents = r->n_agents; ca.first_new = r->first_new;
+    ca.type = r->type; ca.shape = coll.shape; ca.end_pose = coll.end_pose; ca.token_size = r->token_size;
+    ca.predict = coll.predict; ca.margin = coll.margin; ca.base = mask; ca.out_bits = coll.bits; ca.out_count = coll.count;
+    RET_IF(launch_collision("infgen_decode_step", ca, stream));
+    mask = TokenMaskCtl{coll.bits, rows, coll.ident, {-1, -1, -1}, nullptr};
+  }
   float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
   // sampling: inside the split heads kernel where the by-size rule allows (no logits in memory: lg stays store_logits' slice or
   // NULL); otherwise k_sample_topk over the step's logits
@@ -2008,12 +2095,13 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
 // k_fourier_h_multi, k_attn_hs ...).  Same arithmetic on the same data as infgen_decode_step (tests compare the two).
 extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream) {
   TokenMaskCtl mask;
-  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask));
+  CollisionCfg coll;
+  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask, &coll));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !r->token_logprob && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !coll.bits && !r->token_logprob && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));

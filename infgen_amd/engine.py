@@ -555,7 +555,7 @@ class RolloutEngine:
                  tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None,
                  token_logprob: bool = False, sample_logprob: bool = False,
                  sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
-                 token_masks=None, token_mask_type=None, token_mask_row=None):
+                 token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -592,7 +592,13 @@ class RolloutEngine:
         per-type selection, ``TokenMasks.type_sets``).  Rows scenario insertion appends follow their type.  Replayed, commanded and
         teacher-forced rows, the state head and the insertion cell draw are left alone; logits and ``next_token_logprob`` stay the
         model's own.  Table and per-row selectors live in static device buffers that ``reload*(token_masks=..., token_mask_row=...)``
-        rewrite, so captured graphs replay the new values.  None (the default): today's kernels, bit for bit."""
+        rewrite, so captured graphs replay the new values.  None (the default): today's kernels, bit for bit.
+        ``avoid_collisions``: collision-aware decoding ("collision masks" of include/infgen_hip.h) - False, True or
+        ``dict(margin=metres, predict=0 | 1)``.  Every decode step first computes, from the agents' boxes, which motion tokens would
+        end the step inside another agent's (constant-velocity extrapolated, ``predict``) box and bans them on top of the row's static
+        set (all tokens without ``token_masks``); a row whose every token collides keeps its static set.  ``collision_bits``
+        [S * A_cap][token_size / 32] and ``collision_allowed`` [S * A_cap] (the sets' sizes before that fallback) are static device
+        buffers that hold the sets of the step that just ran.  ``reload*(avoid_collisions=...)`` turns it on or off (None: keep)."""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -775,6 +781,10 @@ class RolloutEngine:
         self.mask_bits = self.mask_row = None             # static device buffers: [n_sets][token_size / 32] words, [S * A_cap] int32
         self._mask_handle = 0                             # infgen_token_mask_create's handle of (mask_bits, mask_row, token_mask_type)
         self._load_token_masks(token_masks, token_mask_type, token_mask_row)
+        self.avoid_collisions = None                      # dict(margin, predict) while collision-aware decoding is on
+        self.collision_bits = self.collision_allowed = None
+        self._coll = self._coll_end = self._coll_reg = None
+        self._load_collisions(avoid_collisions)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -967,18 +977,56 @@ class RolloutEngine:
                 self.mask_row.copy_(torch.from_numpy(rows.reshape(-1)))
         self._apply_token_masks()
 
+    def _load_collisions(self, avoid):
+        """``avoid_collisions`` into the engine (None: keep what is there).  The value is checked on the host before anything is
+        allocated or launched; the buffers are allocated once and stay (static addresses for captured graphs)"""
+        if avoid is None:
+            return
+        conf = constraints.check_avoid_collisions(avoid, has_shape=getattr(self, '_shape10', None) is not None)
+        if conf is None and self.avoid_collisions is None:
+            return
+        if conf is not None and self._coll is None:
+            self._coll = constraints.collision_buffers(conf, self.S * self.A_cap, self.cfg.token_size, self.device)
+            self.collision_bits, self.collision_allowed = self._coll['bits'], self._coll['allowed']
+            self._coll['shape'].copy_(self._shape10.reshape(-1, 3))
+            self._coll_cols = torch.arange(self.A_cap, device=self.device, dtype=torch.int32)[None]
+            # the per-token end poses of the vocabulary, once per engine
+            self._coll_end = torch.zeros(12 * self.cfg.token_size + 4, device=self.device)
+            _lib.check(self.lib.infgen_collision_end_poses(_lib.ptr(self.vocab), self.cfg.token_size, _lib.ptr(self._coll_end),
+                                                           self.ops.stream), 'infgen_collision_end_poses')
+        if conf != self.avoid_collisions:
+            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
+        self.avoid_collisions = conf
+        self._apply_token_masks()
+
     def _apply_token_masks(self, validate: bool = True):
         """the library's handle of (table, per-row selectors, per-type sets) into the context: registered again when one of the
-        three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing"""
-        if self._ctx is None or self.token_masks is None:
+        three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  A
+        collision configuration rides on the handle (one without a table when the engine has no ``token_masks``)"""
+        if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and not self._mask_handle):
             return
-        reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
+        if self.token_masks is not None:
+            reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
+        else:
+            reg = (None, 0, None, (-1, -1, -1))
         if reg != getattr(self, '_mask_reg', None):
             self._drop_mask_handle()
             h = self.lib.infgen_token_mask_create(reg[0], reg[1], reg[2], (C.c_int * 3)(*reg[3]), None)
             if h < 1:
                 _lib.check(-1, 'infgen_token_mask_create')
             self._mask_handle, self._mask_reg = h, reg
+        conf, P = self.avoid_collisions, _lib.ptr
+        creg = None if conf is None else (self._mask_handle, conf['predict'], conf['margin'])
+        if creg != self._coll_reg:
+            if conf is None:
+                _lib.check(self.lib.infgen_token_mask_collision(self._mask_handle, None, None, None, None, 1, 0.0, None),
+                           'infgen_token_mask_collision')
+            else:
+                k = self._coll
+                _lib.check(self.lib.infgen_token_mask_collision(self._mask_handle, P(k['bits']), P(k['ident']), P(k['shape']),
+                                                                P(self._coll_end), conf['predict'], conf['margin'], P(k['allowed'])),
+                           'infgen_token_mask_collision')
+            self._coll_reg = creg
         self._ctx.token_mask = self._mask_handle
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
@@ -986,7 +1034,7 @@ class RolloutEngine:
     def _drop_mask_handle(self):
         if getattr(self, '_mask_handle', 0):
             self.lib.infgen_token_mask_destroy(self._mask_handle)
-            self._mask_handle, self._mask_reg = 0, None
+            self._mask_handle, self._mask_reg, self._coll_reg = 0, None, None
             if getattr(self, '_ctx', None) is not None:
                 self._ctx.token_mask = 0
 
@@ -1002,8 +1050,10 @@ class RolloutEngine:
             c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
-    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None):
+    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
+                       avoid_collisions=None):
         self._load_token_masks(*(token_masks or (None, None, None)))
+        self._load_collisions(avoid_collisions)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
@@ -1073,7 +1123,8 @@ class RolloutEngine:
 
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
-               sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None):
+               sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
+               avoid_collisions=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -1088,7 +1139,7 @@ class RolloutEngine:
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row))
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions)
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1105,7 +1156,7 @@ class RolloutEngine:
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                       sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None,
-                      token_mask_row=None) -> bool:
+                      token_mask_row=None, avoid_collisions=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -1120,7 +1171,7 @@ class RolloutEngine:
             return False
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row))
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions)
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1181,7 +1232,8 @@ class RolloutEngine:
 
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
-                     sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None):
+                     sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
+                     avoid_collisions=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1191,7 +1243,7 @@ class RolloutEngine:
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row))
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -1350,6 +1402,8 @@ class RolloutEngine:
         self.tok_tab, self.grid_tab, self.cat_seed = tabs['tok_tab'], tabs['grid_tab'], tabs['cat_seed']
         self.f_seed = tabs['f_seed']                 # (this engine's entry, not whatever the pack built last)
         self.reset()
+        if self._coll is not None:                   # the rows' boxes for k_collision_mask (rows insertion appends: _step_gen)
+            self._coll['shape'].copy_(self._shape10.reshape(rows, 3))
         # categorical embedding rows (agent_decoder.py:376-380,492)
         if self.cat_agent is None:
             self.cat_agent = torch.empty(rows, D, device=dev)
@@ -1781,6 +1835,12 @@ class RolloutEngine:
                        'infgen_active_row_groups')
         if t > 0:
             yield from self._insert_step(t)
+            if self.avoid_collisions is not None:
+                # the boxes of the rows this step appended (they are obstacles, and get sets, from the next step on)
+                S, A_cap = self.S, self.A_cap
+                new = (self._coll_cols >= I['first_new'][:, None]) & (self._coll_cols < self.n_agents[:, None])
+                cs = self._coll['shape'].view(S, A_cap, 3)
+                cs.copy_(torch.where(new[..., None], I['shape_all'].view(S, A_cap, 3), cs))
         self._decoded_rows.add_(self.n_agents.sum())       # A_t: rows decoded at this step, incl. the inserted ones
         tight = use_groups and self.flags['row_groups_tight']
         if tight:

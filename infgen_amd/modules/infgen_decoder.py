@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import _lib, logprob, scene_setup
 from ..closed_loop import ClosedLoopSession
-from ..constraints import TokenMasks, check_type_selectors
+from ..constraints import TokenMasks, check_avoid_collisions, check_type_selectors
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -389,6 +389,9 @@ class InfGenDecoder(nn.Module):
         # per-type selection applies (TokenMasks.from_vocab) - or (TokenMasks, [vehicle, pedestrian, cyclist] set indices, -1 =
         # unconstrained).  Generated rows only emit motion tokens of their type's set; part of the engine cache key
         self.token_constraints = None
+        # collision-aware decoding (RolloutEngine's avoid_collisions): False, True or dict(margin=, predict=).  Taken by
+        # inference, inference_batch, inference_rollouts and closed_loop alike; part of the engine cache key
+        self.avoid_collisions = False
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -498,6 +501,10 @@ class InfGenDecoder(nn.Module):
             sel = check_type_selectors(masks.type_sets if sel is None else sel, masks.n_sets)
             fixed.update(token_masks=masks, token_mask_type=sel)
             key += (masks.key(), tuple(sel))
+        ac = check_avoid_collisions(self.avoid_collisions)
+        if ac is not None:      # (fixed per engine, like the constraints)
+            fixed.update(avoid_collisions=ac)
+            key += (('avoid_collisions', ac['margin'], ac['predict']),)
         return dict(fixed, **live), live, key
 
     @staticmethod

@@ -15,6 +15,8 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
                                                                                             -> token, state, logits, token_logprob, sample_logprob
     torch.ops.infgen_hip.sample_topk(logits (N, n), k, uniform (N,), want_sample_logprob, temperature=1, top_p=1,
                                      temperature_row=None)                                  -> token (N,), sample_logprob
+    torch.ops.infgen_hip.collision_mask(pos, head, state, n_agents, type, shape, c, end_pose, predict=1, margin=0,
+                                        mask_bits?, mask_row?, mask_type?, first_new?)      -> sets (S A, token_size / 32) int32, allowed (S A,)
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -303,6 +305,61 @@ def _(logits, k, uniform, want_sample_logprob=False, temperature=1.0, top_p=1.0,
       mask_type=None, type=None):
     n = logits.shape[0]
     return logits.new_empty(n, dtype=torch.int32), logits.new_empty(n if want_sample_logprob else 0, dtype=torch.float32)
+
+
+def collision_end_poses(vocab: torch.Tensor) -> torch.Tensor:
+    """the end-pose table of ``collision_mask`` for a vocabulary (3, token_size, 6, 4, 2): 12 token_size + 4 floats
+    (``infgen_collision_end_poses``; computed once per vocabulary)"""
+    if vocab.dim() != 5 or tuple(vocab.shape[0:1] + vocab.shape[2:]) != (3, 6, 4, 2):
+        raise ValueError('vocab must be (3, token_size, 6, 4, 2)')
+    ops, n = _ops(vocab.device), int(vocab.shape[1])
+    tab = torch.zeros(12 * n + 4, device=vocab.device)
+    _lib.check(ops.lib.infgen_collision_end_poses(_lib.ptr(_f32(vocab)), n, _lib.ptr(tab), ops.stream), 'infgen_collision_end_poses')
+    return tab
+
+
+@torch.library.custom_op('infgen_hip::collision_mask', mutates_args=())
+def collision_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+                   shape: torch.Tensor, c: int, end_pose: torch.Tensor, predict: int = 1, margin: float = 0.0,
+                   mask_bits: Optional[torch.Tensor] = None, mask_row: Optional[torch.Tensor] = None,
+                   mask_type: Optional[List[int]] = None, first_new: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the allowed-token sets of one decode step from the agents' boxes (collision-aware decoding; "collision masks" of
+    include/infgen_hip.h, ``infgen_collision_mask``): ``pos`` (S, T, A, 2), ``head`` / ``state`` (S, T, A), ``n_agents`` (S,),
+    ``type`` (S, A), ``shape`` (S, A, 3) = length, width, height, column ``c``, ``end_pose`` from ``collision_end_poses``.
+    ``mask_bits`` / ``mask_row`` (S * A,) / ``mask_type``: the static base sets (none: every token); ``first_new`` (S,): rows at or
+    beyond it are not in the scene yet.  Returns the sets (S * A, token_size / 32) int32 words and the number of allowed tokens
+    per row before the empty-set fallback (S * A,)."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or head.shape != pos.shape[:3] or state.shape != pos.shape[:3]:
+        raise ValueError('collision_mask takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,):
+        raise ValueError('collision_mask takes type (S, A), shape (S, A, 3), n_agents (S,)')
+    if first_new is not None and tuple(first_new.shape) != (S,):
+        raise ValueError('first_new must be (S,)')
+    token_size = (int(end_pose.numel()) - 4) // 12
+    if end_pose.dim() != 1 or token_size * 12 + 4 != end_pose.numel() or token_size % 32:
+        raise ValueError('end_pose is the table of collision_end_poses (12 token_size + 4 floats, token_size a multiple of 32)')
+    dev = pos.device
+    ops = _ops(dev)
+    i32 = lambda t: None if t is None else t.to(dev, torch.int32).contiguous()
+    ty = i32(type)
+    tm, _keep_mask = _token_mask(mask_bits, mask_row, mask_type, ty.reshape(-1), S * A, token_size, dev)
+    bits = torch.zeros(S * A, token_size // 32, device=dev, dtype=torch.int32)
+    count = torch.zeros(S * A, device=dev, dtype=torch.int32)
+    st, na, fn = i32(state), i32(n_agents), i32(first_new)
+    p, h, sh, ep = _f32(pos), _f32(head), _f32(shape), _f32(end_pose)
+    _lib.check(ops.lib.infgen_collision_mask(_lib.ptr(p), _lib.ptr(h), _lib.ptr(st), _lib.ptr(na), _lib.ptr(fn), _lib.ptr(ty),
+                                             _lib.ptr(sh), S, A, T, int(c), _lib.ptr(ep), token_size, int(predict), float(margin),
+                                             *tm[:4], _lib.ptr(bits), _lib.ptr(count), ops.stream), 'infgen_collision_mask')
+    return bits, count
+
+
+@collision_mask.register_fake
+def _(pos, head, state, n_agents, type, shape, c, end_pose, predict=1, margin=0.0, mask_bits=None, mask_row=None, mask_type=None,
+      first_new=None):
+    rows = pos.shape[0] * pos.shape[2]
+    return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32))
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
