@@ -514,7 +514,7 @@ int infgen_token_mask_destroy(int handle);
  * Rows that are not in the scene at column c, and padding rows, get base(i) (out_count: its size).  Replayed, commanded and
  * teacher-forced rows keep their plan's tokens, as under a static mask.
  * Left out on purpose: the contours 0..4 inside the 0.5 s step (only its end is tested); the planned next pose of replayed rows (they
- * are obstacles like every other row, at their current or extrapolated pose); map geometry; rows scenario insertion appends inside
+ * are obstacles like every other row, at their current or extrapolated pose); map geometry (the road masks below); rows scenario insertion appends inside
  * step t are obstacles, and get sets, from step t + 1 on - during step t they take their type's static set, as before.
  *
  * infgen_collision_end_poses: end_pose [3][token_size][4] = (dx, dy, cos dtheta, sin dtheta) of every token's last contour in the agent
@@ -538,6 +538,58 @@ int infgen_collision_mask(const float* pos, const float* head, const int* state,
                           const int* mask_type, uint32_t* out_bits, int* out_count, void* stream);
 int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const int* identity_row, const float* shape, const float* end_pose,
                                 int predict, float margin, int* count);
+
+/* road-aware decoding: ROAD MASKS, the allowed-token sets of one decode step computed from the map's road-edge segments (k_road_mask).
+ * Step column c = 1 + t, IN THE SCENE, first_new, base(i) and the fallback mean what they mean for the collision masks above; fp32
+ * throughout, no fused multiply-add.
+ *   road segments   row-scene s of an engine with `copies` uses the segments of map scene s / copies.  From the map: every map token
+ *       m < n_map with map_type[m] == 12 (EDGE) and 0 <= map_tok[m] < n_token contributes `detail` (1, 2, 5 or 10) chords of its
+ *       vocabulary polyline map_vocab[map_tok[m]] (11 points in the token frame), joining the points 0, 10 / detail, ..., 10, each
+ *       rotated by map_orient[m] and anchored at map_pos[m]; a token of another type, or with a token id outside the vocabulary,
+ *       contributes nothing.  Explicit: segments [S0][E][4] = (x0, y0, x1, y1) in world coordinates, the first n_segments[s] of scene s.
+ *   record   8 floats, 16-byte aligned: anchor x, y - an exact copy of an input world coordinate, map_pos[m] or the segment's p0 -,
+ *       the offset of the segment's midpoint from the anchor, cos and sin of the segment's direction (p1 - p0) / L, the half length
+ *       L / 2 and the enclosing radius L / 2.  A segment with L == 0 or a non-finite coordinate is the record (0, 0, 0, 0, 1, 0, 0, -1):
+ *       radius -1, never an obstacle.  The kernel forms (anchor - pos[c][i]) + offset: world coordinates enter through an exact
+ *       difference only, the rule of (centre - pos) + step above.  Records are compacted per scene - tokens in order, a token's chords
+ *       in order -, n_records[s] of them, records [S0][rec_cap][8]; what exceeds rec_cap is dropped (callers size rec_cap from a count).
+ *   obstacle rectangle   centre the segment's midpoint, heading its direction, half extents (L / 2 + margin, margin).
+ *   candidate shapes of token k for row i   the END BOX: the candidate box of the collision masks (the last contour's centre and heading,
+ *       the row's own length x width).  The PATH RECTANGLE (sweep = 1): centre half the end displacement (dx, dy) / 2, heading that of
+ *       (dx, dy), half extents (|d| / 2, the row's half width); skipped when |d| == 0.
+ *   overlap   the four-axis separating-axis value sep < 0 of the collision masks, in row i's frame.  Token k is OFF-ROAD for row i iff
+ *       its end box or its path rectangle overlaps an obstacle rectangle of the scene that row i does not already STRADDLE: a segment
+ *       whose obstacle rectangle overlaps the row's current box (the pose of column c, own extents) is ignored for that row in that step.
+ *   rows   the rule applies to the rows in the scene at column c whose agent type ty (0 vehicle, 1 pedestrian, 2 cyclist; others
+ *       count as 0) has types[ty] != 0.  Every other row - not in the scene, padding, >= first_new[s], a type switched off - keeps base(i).
+ *   result   set(i) = base(i) AND NOT offroad(i); an empty result is replaced by base(i); out_count[i] (optional) is the size before
+ *       that fallback.
+ * infgen_road_records_from_map / infgen_road_records_from_segments: the record table of S0 distinct scenes, once per reload.
+ * infgen_road_paths: paths [3][token_size][4] = (cos, sin of the end displacement's direction, |d| / 2, 0) - (1, 0, 0, 0) where
+ * |d| == 0 - from the end-pose table of infgen_collision_end_poses, which also holds the largest displacement per type.
+ * infgen_road_mask: one launch writes out_bits [S * A_cap][token_size / 32] and out_count (optional); the scene arrays as for
+ * infgen_collision_mask, S a multiple of copies; the base is a token mask's first four values with the rows' own `type`.
+ * infgen_token_mask_road: attaches a road configuration to a registered token mask, as infgen_token_mask_collision does:
+ * infgen_decode_step then launches k_road_mask in front of the heads launch.  With a collision configuration on the same handle
+ * k_collision_mask runs first, exactly as without this one, and the road kernel's base is its dyn_bits read through the identity
+ * selector: set = collision set AND NOT offroad, an empty one replaced by the collision set.  The heads read road_bits.  The pointers
+ * are kept, not the contents.  road_bits NULL detaches.
+ * Refused: margin negative or not finite, sweep outside {0, 1}, detail outside {1, 2, 5, 10}, copies < 1, a missing table, a
+ * token_size that is no multiple of 32 or exceeds 4096, a misaligned table. */
+int infgen_road_records_from_map(const float* map_pos, const float* map_orient, const long long* map_type, const long long* map_tok,
+                                 const int* n_map, int S0, int M_cap, const float* map_vocab, int n_token, int detail, float* records,
+                                 int rec_cap, int* n_records, void* stream);
+int infgen_road_records_from_segments(const float* segments, const int* n_segments, int S0, int E, float* records, int rec_cap,
+                                      int* n_records, void* stream);
+int infgen_road_paths(const float* end_pose, int token_size, float* paths, void* stream);
+int infgen_road_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new, const int* type,
+                     const float* shape, int S, int A_cap, int T, int c, const float* end_pose, const float* paths, int token_size,
+                     const float* records, const int* n_records, int rec_cap, int copies, int sweep, float margin, const int* types,
+                     const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, uint32_t* out_bits,
+                     int* out_count, void* stream);
+int infgen_token_mask_road(int handle, uint32_t* road_bits, const int* identity_row, const float* shape, const float* end_pose,
+                           const float* paths, const float* records, const int* n_records, int rec_cap, int copies, int sweep,
+                           float margin, const int* types, int* count);
 
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell

@@ -122,7 +122,8 @@ class ClosedLoopSession:
         """the newest stored column as device tensors: ``pos`` [S, A_cap, 2], ``head``, ``state`` (0 = not in the scene), ``token``,
         ``type`` [S, A_cap], ``shape`` [S, A_cap, 3] (length, width, height), ``n_agents`` / ``ego_index`` [S], ``controlled``
         [S, A_cap] bool and ``column`` (int); with ``avoid_collisions`` also ``allowed_tokens`` [S, A_cap], the number of motion tokens
-        every row was allowed at the step that just ran, before the empty-set fallback (0: every token collided).  Views of the engine's buffers wherever possible: no copy, no synchronisation - and
+        every row was allowed at the step that just ran, before the empty-set fallback (0: every token collided); with ``stay_on_road`` the
+        sizes of the final sets, the road masks' (0: every token of the row's collision or static set left the road).  Views of the engine's buffers wherever possible: no copy, no synchronisation - and
         overwritten by later steps, a reset or a reload (clone what has to last)."""
         self._check_open()
         eng, c = self.eng, self.eng.hc - 1 + self.t
@@ -130,6 +131,8 @@ class ClosedLoopSession:
                    shape=eng._shape10, n_agents=eng.n_agents, ego_index=eng.av, controlled=eng.replay_row.bool(), column=c)
         if eng.avoid_collisions is not None:      # collision-aware decoding: the sizes of the sets the last step decoded under
             obs['allowed_tokens'] = eng.collision_allowed.view(eng.S, eng.A_cap)
+        if eng.stay_on_road is not None:          # road-aware decoding runs last: its sets are the ones the heads read
+            obs['allowed_tokens'] = eng.road_allowed.view(eng.S, eng.A_cap)
         return obs
 
     def command(self, tokens=None, poses=None, mask=None):

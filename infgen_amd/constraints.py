@@ -183,3 +183,100 @@ def collision_buffers(conf, rows: int, token_size: int, device='cpu'):
                 allowed=torch.full((rows,), token_size, dtype=torch.int32, device=device),
                 ident=torch.arange(rows, dtype=torch.int32, device=device),
                 shape=torch.zeros(rows, 3, dtype=torch.float32, device=device))
+
+
+# ---------------------------------------------------------------------------------------- road-aware decoding
+ROAD_DETAILS = (1, 2, 5, 10)              # chords per EDGE map token: the polyline's points 0, 10 / detail, ..., 10
+
+
+def _road_types(types) -> tuple:
+    """``types`` of stay_on_road -> the three-entry switch (vehicle, pedestrian, cyclist) of 0 / 1"""
+    if isinstance(types, (str, bytes)) or not isinstance(types, (Sequence, set, frozenset, np.ndarray)):
+        raise ValueError(f'stay_on_road: types is a collection of agent types, names {TYPE_NAMES} or 0 .. 2 (got {types!r})')
+    on = [0, 0, 0]
+    for t in types:
+        if isinstance(t, str) and t in TYPE_NAMES:
+            on[TYPE_NAMES.index(t)] = 1
+        elif not isinstance(t, (bool, str)) and np.isscalar(t) and t in (0, 1, 2):
+            on[int(t)] = 1
+        else:
+            raise ValueError(f'stay_on_road: unknown agent type {t!r} (names {TYPE_NAMES} or 0 .. 2)')
+    return tuple(on)
+
+
+def _road_segments(segments):
+    """``segments`` of stay_on_road -> (float32 [S0][E][4], int32 [S0]): an array [S0][E][4] (every segment used) or one array
+    [E_s][4] = (x0, y0, x1, y1) per distinct scene, world coordinates.  Non-finite and zero-length segments are allowed: the
+    definition makes them no obstacle"""
+    if isinstance(segments, np.ndarray) and segments.ndim == 3:
+        segments = list(segments)
+    if isinstance(segments, (str, bytes)) or not isinstance(segments, Sequence) or len(segments) == 0:
+        raise ValueError('stay_on_road: segments is an array [S0][E][4] or one array [E][4] per distinct scene')
+    per = []
+    for s, seg in enumerate(segments):
+        a = np.asarray(seg)
+        if a.size == 0:
+            a = np.zeros((0, 4), np.float32)
+        if a.ndim != 2 or a.shape[1] != 4 or a.dtype.kind not in 'fiu':
+            raise ValueError(f'stay_on_road: segments[{s}] must be numbers [E][4] = (x0, y0, x1, y1), got shape {a.shape}')
+        per.append(a.astype(np.float32))
+    E = max(1, max(a.shape[0] for a in per))
+    out = np.zeros((len(per), E, 4), np.float32)
+    for s, a in enumerate(per):
+        out[s, :a.shape[0]] = a
+    return out, np.array([a.shape[0] for a in per], np.int32)
+
+
+def check_stay_on_road(stay, has_shape: bool = True, n_scenes: Optional[int] = None):
+    """``stay_on_road`` as the engine takes it -> None (off) or dict(margin=float, sweep=0 | 1, detail=1 | 2 | 5 | 10, types=(veh, ped,
+    cyc) switches, segments=None | (float32 [S0][E][4], int32 [S0])).  False / None: off; True: the defaults (margin 0 m, the path
+    rectangle on, two chords per EDGE map token, vehicles and cyclists, segments from the map); a mapping with any of those keys.
+    ``n_scenes``: the number of distinct scenes explicit segments must cover.  Everything is checked here, on the host, before any
+    launch."""
+    if stay is None or stay is False:
+        return None
+    if stay is True:
+        stay = {}
+    if not isinstance(stay, Mapping):
+        raise ValueError('stay_on_road takes False, True or dict(margin=, sweep=, detail=, types=, segments=)')
+    unknown = set(stay) - {'margin', 'sweep', 'detail', 'types', 'segments'}
+    if unknown:
+        raise ValueError(f'stay_on_road: unknown keys {sorted(unknown)} (margin, sweep, detail, types, segments)')
+    margin, sweep, detail = stay.get('margin', 0.0), stay.get('sweep', 1), stay.get('detail', 2)
+    if isinstance(margin, (bool, str)) or not np.isscalar(margin) or not np.isfinite(margin) or margin < 0:
+        raise ValueError(f'stay_on_road: margin must be a finite number of metres >= 0 (got {margin!r})')
+    if isinstance(sweep, str) or not np.isscalar(sweep) or sweep not in (0, 1, False, True):
+        raise ValueError(f'stay_on_road: sweep must be 0 or 1 (got {sweep!r})')
+    if isinstance(detail, (bool, str)) or not np.isscalar(detail) or detail not in ROAD_DETAILS:
+        raise ValueError(f'stay_on_road: detail must be one of {ROAD_DETAILS} (got {detail!r})')
+    types = _road_types(stay.get('types', ('veh', 'cyc')))
+    segments = stay.get('segments')
+    if segments is not None:
+        if isinstance(segments, tuple) and len(segments) == 2 and np.asarray(segments[1]).ndim == 1 and np.asarray(segments[0]).ndim == 3:
+            seg, n = np.ascontiguousarray(segments[0], np.float32), np.asarray(segments[1])      # (a value this function returned)
+            if seg.shape[2] != 4 or n.shape[0] != seg.shape[0] or n.dtype.kind not in 'iu' or (n < 0).any() or (n > seg.shape[1]).any():
+                raise ValueError('stay_on_road: segments as (array [S0][E][4], counts [S0]) with 0 <= counts <= E')
+            segments = (seg, n.astype(np.int32))
+        else:
+            segments = _road_segments(segments)
+        if n_scenes is not None and segments[0].shape[0] != n_scenes:
+            raise ValueError(f'stay_on_road: segments cover {segments[0].shape[0]} scenes, the batch has {n_scenes} distinct scenes')
+    if not has_shape:
+        raise ValueError('stay_on_road needs the rows\' shapes: this engine has no shape array')
+    return dict(margin=float(margin), sweep=int(sweep), detail=int(detail), types=types, segments=segments)
+
+
+def road_key(conf):
+    """the hashable part of a checked configuration that decides the launches' arguments (the segments are contents)"""
+    return None if conf is None else (conf['margin'], conf['sweep'], conf['detail'], conf['types'], conf['segments'] is not None)
+
+
+def road_buffers(conf, rows: int, token_size: int, device='cpu'):
+    """the static per-row buffers of road-aware decoding for ``rows`` = S * A_cap rows, or None when ``conf`` (``check_stay_on_road``)
+    is off: the four of ``collision_buffers`` - ``bits``, ``allowed``, ``ident``, ``shape`` - for the road kernel's own sets.  (The
+    record table is the engine's: it is sized from a count of the map's EDGE tokens.)"""
+    if conf is None:
+        return None
+    if token_size % 32 or token_size > 4096:
+        raise ValueError(f'stay_on_road: token_size {token_size} must be a multiple of 32, at most 4096')
+    return collision_buffers(conf, rows, token_size, device)

@@ -52,7 +52,13 @@ static TokenMaskDesc token_mask_desc(const uint32_t* bits, int n_sets, const int
 // the collision configuration a registered mask may carry (infgen_token_mask_collision; bits == NULL: none)
 struct CollisionCfg { uint32_t* bits; const int* ident; const float* shape; const float* end_pose; int predict; float margin; int* count; };
 constexpr CollisionCfg COLLISION_NONE{nullptr, nullptr, nullptr, nullptr, 1, 0.f, nullptr};
-struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; };
+// the road configuration a registered mask may carry (infgen_token_mask_road; bits == NULL: none)
+struct RoadCfg {
+  uint32_t* bits; const int* ident; const float* shape; const float* end_pose; const float* paths; const float* records;
+  const int* n_records; int rec_cap, copies, sweep; float margin; int types[3]; int* count;
+};
+constexpr RoadCfg ROAD_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, nullptr};
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
 
@@ -79,7 +85,7 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   size_t h = 0;
   while (h < g_masks.size() && g_masks[h].in_use) ++h;
   if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
-  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE};
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE};
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
@@ -1409,6 +1415,108 @@ extern "C" int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const
   return 0;
 }
 
+// ---------------------------------------------------------------------------------- road masks
+// the argument checks of include/infgen_hip.h ("road masks") and the one launch of k_road_mask
+static bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) != 0;
+}
+static int road_check(const char* where, int sweep, float margin, int copies, int rec_cap, const float* shape, const float* end_pose,
+                      const float* paths, const float* records, const int* n_records, const int* types, const uint32_t* bits) {
+  if (!std::isfinite(margin) || margin < 0.f) return fail(where, "road mask: margin must be finite and >= 0");
+  if (sweep != 0 && sweep != 1) return fail(where, "road mask: sweep must be 0 or 1");
+  if (copies < 1) return fail(where, "road mask: copies must be at least 1");
+  if (rec_cap < 0) return fail(where, "road mask: negative record capacity");
+  if (!shape) return fail(where, "road mask: needs the rows' shape array [S][A_cap][3]");
+  if (!end_pose) return fail(where, "road mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!paths) return fail(where, "road mask: needs the path table of infgen_road_paths");
+  if (!records || !n_records) return fail(where, "road mask: needs the record table and its counts");
+  if (!types) return fail(where, "road mask: needs the three-entry type switch");
+  if (!bits) return fail(where, "road mask: needs the output table");
+  if (misaligned16(bits, end_pose, paths, records)) return fail(where, "road mask: the tables must be 16-byte aligned");
+  return 0;
+}
+static int launch_road(const char* where, const RoadArgs& a, void* stream) {
+  RET_IF(road_check(where, a.sweep, a.margin, a.copies, a.rec_cap, a.shape, a.end_pose, a.paths, a.records, a.n_records, a.types, a.out_bits));
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "road mask: S, A_cap and T must be positive");
+  if (a.S % a.copies) return fail(where, "road mask: S must be a multiple of copies");
+  if (a.c < 0 || a.c >= a.T) return fail(where, "road mask: column outside [0, T)");
+  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RM_WPL)
+    return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "road mask: null scene array");
+  const long long rows = (long long)a.S * a.A_cap;
+  if (rows > 0x7fffffffLL) return fail(where, "road mask: too many rows");
+  hipLaunchKernelGGL(k_road_mask, dim3((unsigned)((rows + RM_WAVES - 1) / RM_WAVES)), dim3(64 * RM_WAVES), 0, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+
+extern "C" int infgen_road_records_from_map(const float* map_pos, const float* map_orient, const long long* map_type, const long long* map_tok,
+                                            const int* n_map, int S0, int M_cap, const float* map_vocab, int n_token, int detail,
+                                            float* records, int rec_cap, int* n_records, void* stream) {
+  const char* me = "infgen_road_records_from_map";
+  if (!map_pos || !map_orient || !map_type || !map_tok || !n_map || !map_vocab || !records || !n_records) return fail(me, "null pointer");
+  if (detail != 1 && detail != 2 && detail != 5 && detail != 10) return fail(me, "road mask: detail must be 1, 2, 5 or 10");
+  if (S0 <= 0 || M_cap <= 0 || n_token <= 0 || rec_cap <= 0) return fail(me, "S0, M_cap, n_token and rec_cap must be positive");
+  if (misaligned16(records)) return fail(me, "road mask: the tables must be 16-byte aligned");
+  hipLaunchKernelGGL(k_road_records_map, dim3(S0), dim3(64), 0, (hipStream_t)stream,
+                     RoadMapArgs{map_pos, map_orient, map_type, map_tok, n_map, M_cap, map_vocab, n_token, detail, records, rec_cap, n_records});
+  return check_launch(me);
+}
+
+extern "C" int infgen_road_records_from_segments(const float* segments, const int* n_segments, int S0, int E, float* records, int rec_cap,
+                                                 int* n_records, void* stream) {
+  const char* me = "infgen_road_records_from_segments";
+  if (!segments || !n_segments || !records || !n_records) return fail(me, "null pointer");
+  if (S0 <= 0 || E <= 0 || rec_cap <= 0) return fail(me, "S0, E and rec_cap must be positive");
+  if (misaligned16(records, segments)) return fail(me, "road mask: the tables must be 16-byte aligned");
+  hipLaunchKernelGGL(k_road_records_seg, dim3(S0), dim3(256), 0, (hipStream_t)stream, RoadSegArgs{segments, n_segments, E, records, rec_cap, n_records});
+  return check_launch(me);
+}
+
+extern "C" int infgen_road_paths(const float* end_pose, int token_size, float* paths, void* stream) {
+  const char* me = "infgen_road_paths";
+  if (!end_pose || !paths) return fail(me, "null pointer");
+  if (token_size <= 0) return fail(me, "token_size must be positive");
+  if (misaligned16(end_pose, paths)) return fail(me, "road mask: the tables must be 16-byte aligned");
+  hipLaunchKernelGGL(k_road_paths, dim3(ceil_div(3 * token_size, 256)), dim3(256), 0, (hipStream_t)stream, RoadPathArgs{end_pose, token_size, paths});
+  return check_launch(me);
+}
+
+extern "C" int infgen_road_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new,
+                                const int* type, const float* shape, int S, int A_cap, int T, int c, const float* end_pose,
+                                const float* paths, int token_size, const float* records, const int* n_records, int rec_cap, int copies,
+                                int sweep, float margin, const int* types, const uint32_t* mask_bits, int mask_n_sets,
+                                const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, void* stream) {
+  const char* me = "infgen_road_mask";
+  RoadArgs a{};
+  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c;
+  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.first_new = first_new; a.type = type; a.shape = shape;
+  a.end_pose = end_pose; a.paths = paths; a.token_size = token_size; a.records = records; a.n_records = n_records; a.rec_cap = rec_cap;
+  a.copies = copies; a.sweep = sweep; a.margin = margin;
+  RET_IF(road_check(me, sweep, margin, copies, rec_cap, shape, end_pose, paths, records, n_records, types, out_bits));
+  for (int k = 0; k < 3; ++k) a.types[k] = types[k];
+  a.out_bits = out_bits; a.out_count = out_count;
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
+  RET_IF(token_mask_ctl(me, &md, token_size, &a.base));
+  return launch_road(me, a, stream);
+}
+
+extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int* identity_row, const float* shape, const float* end_pose,
+                                      const float* paths, const float* records, const int* n_records, int rec_cap, int copies, int sweep,
+                                      float margin, const int* types, int* count) {
+  const char* me = "infgen_token_mask_road";
+  RoadCfg cfg = ROAD_NONE;
+  if (road_bits) {
+    RET_IF(road_check(me, sweep, margin, copies, rec_cap, shape, end_pose, paths, records, n_records, types, road_bits));
+    if (!identity_row) return fail(me, "road mask: needs the identity selectors [S * A_cap]");
+    cfg = RoadCfg{road_bits, identity_row, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin,
+                  {types[0], types[1], types[2]}, count};
+  }
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(me, "no such token mask");
+  g_masks[handle - 1].road = cfg;
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------- rollout context
 static SceneState scene_of(const InfgenRollout* r) {
   SceneState st;
@@ -1425,7 +1533,7 @@ static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
 static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, TokenMaskCtl* mask = nullptr,
-                    CollisionCfg* coll = nullptr) {
+                    CollisionCfg* coll = nullptr, RoadCfg* road = nullptr) {
   if (!r) return fail(where, "null context");
   if (r->A_cap > 1024 || r->A_cap <= 0) return fail(where, "A_cap must be in 1..1024");
   if (r->A_cap % 32) return fail(where, "A_cap must be a multiple of 32");
@@ -1446,6 +1554,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   CollisionCfg own_coll;
   if (!coll) coll = &own_coll;
   *coll = COLLISION_NONE;
+  RoadCfg own_road;
+  if (!road) road = &own_road;
+  *road = ROAD_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
     TokenMaskDesc tm;
     {
@@ -1454,11 +1565,15 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
         return fail(where, "token_mask is no handle of infgen_token_mask_create");
       tm = g_masks[r->token_mask - 1].d;
       *coll = g_masks[r->token_mask - 1].coll;
+      *road = g_masks[r->token_mask - 1].road;
     }
     if (!tm.type) tm.type = r->type;
     RET_IF(token_mask_ctl(where, &tm, r->token_size, mask));
     if (coll->bits && (r->token_size % 32 || r->token_size > 64 * 32 * CM_WPL))
       return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
+    if (road->bits && (r->token_size % 32 || r->token_size > 64 * 32 * RM_WPL))
+      return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
+    if (road->bits && r->S % road->copies) return fail(where, "road mask: S must be a multiple of copies");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
@@ -2046,7 +2161,8 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
   TokenMaskCtl mask;
   CollisionCfg coll;
-  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask, &coll));
+  RoadCfg road;
+  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask, &coll, &road));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
@@ -2061,6 +2177,18 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
     ca.predict = coll.predict; ca.margin = coll.margin; ca.base = mask; ca.out_bits = coll.bits; ca.out_count = coll.count;
     RET_IF(launch_collision("infgen_decode_step", ca, stream));
     mask = TokenMaskCtl{coll.bits, rows, coll.ident, {-1, -1, -1}, nullptr};
+  }
+  if (road.bits) {      // road-aware decoding: the sets so far (static, or this column's collision sets) without the off-road tokens
+    RoadArgs ra{};
+    ra.S = r->S; ra.A_cap = r->A_cap; ra.T = r->T; ra.c = c;
+    ra.pos = r->pos; ra.head = r->head; ra.state = r->state; ra.n_agents = r->n_agents; ra.first_new = r->first_new;
+    ra.type = r->type; ra.shape = road.shape; ra.end_pose = road.end_pose; ra.paths = road.paths; ra.token_size = r->token_size;
+    ra.records = road.records; ra.n_records = road.n_records; ra.rec_cap = road.rec_cap; ra.copies = road.copies;
+    ra.sweep = road.sweep; ra.margin = road.margin;
+    for (int k = 0; k < 3; ++k) ra.types[k] = road.types[k];
+    ra.base = mask; ra.out_bits = road.bits; ra.out_count = road.count;
+    RET_IF(launch_road("infgen_decode_step", ra, stream));
+    mask = TokenMaskCtl{road.bits, rows, road.ident, {-1, -1, -1}, nullptr};
   }
   float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
   // sampling: inside the split heads kernel where the by-size rule allows (no logits in memory: lg stays store_logits' slice or
@@ -2096,12 +2224,13 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
 extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream) {
   TokenMaskCtl mask;
   CollisionCfg coll;
-  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask, &coll));
+  RoadCfg road;
+  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask, &coll, &road));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !coll.bits && !r->token_logprob && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !coll.bits && !road.bits && !r->token_logprob && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));

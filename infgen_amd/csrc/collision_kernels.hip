@@ -15,6 +15,7 @@
 //   4. the "any token left?" of the fallback is a wave reduction of the words' OR, the count one of their popcounts.
 // fp32 throughout, no fused multiply-add (the build's -ffp-contract=off), plain stores.
 #include "kernels.h"
+#include "sat.cuh"
 #include "tile.cuh"
 
 namespace ig {
@@ -62,12 +63,7 @@ __device__ __forceinline__ unsigned collide_word(unsigned cur, const float4* __r
       const float ddx = o.x - p.x, ddy = o.y - p.y;
       const float rr = ra + q.z;
       if (ddx * ddx + ddy * ddy > rr * rr) continue;                           // the enclosing circles are apart
-      const float cc = fabsf(p.z * o.z + p.w * o.w), ss = fabsf(o.w * p.z - o.z * p.w);     // |cos|, |sin| of the relative heading
-      const float s0 = fabsf(ddx * p.z + ddy * p.w) - (hla + (q.x * cc + q.y * ss));
-      const float s1 = fabsf(ddy * p.z - ddx * p.w) - (hwa + (q.x * ss + q.y * cc));
-      const float s2 = fabsf(ddx * o.z + ddy * o.w) - (q.x + (hla * cc + hwa * ss));
-      const float s3 = fabsf(ddy * o.z - ddx * o.w) - (q.y + (hla * ss + hwa * cc));
-      hit = fmaxf(fmaxf(s0, s1), fmaxf(s2, s3)) < 0.f;
+      hit = sat_sep(ddx, ddy, p.z, p.w, hla, hwa, o.z, o.w, q.x, q.y) < 0.f;      // (sat.cuh: the four axes, shared with k_road_mask)
     }
     if (hit) out &= ~(1u << b);
   }

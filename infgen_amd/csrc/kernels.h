@@ -623,6 +623,35 @@ struct EndPoseArgs { const float* vocab; int token_size; float* end_pose; };    
 __global__ void k_collision_mask(CollisionArgs a);
 __global__ void k_collision_end_poses(EndPoseArgs a);
 
+// road_kernels.hip: the per-step allowed-token sets of road-aware decoding (include/infgen_hip.h, "road masks"):
+// set(i) = base(i) AND NOT offroad(i), written as the row's own set of out_bits
+constexpr int RM_WAVES = 4;             // rows a workgroup works on (one wave each)
+constexpr int RM_LIST = 128;            // reachable road records a wave keeps in LDS per pass over the row's tokens
+constexpr int RM_WPL = 2;               // 32-token words a lane owns at most: token_size <= 64 * 32 * RM_WPL
+constexpr int RM_REC = 8;               // floats of a record: anchor x, y, offset x, y | cos, sin, half length, radius
+struct RoadArgs {
+  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* first_new;                  // [S]; first_new optional
+  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
+  const float* end_pose; const float* paths; int token_size;  // [3][token_size][4] + 4 floats, [3][token_size][4] = (cos, sin, half length, 0)
+  const float* records; const int* n_records; int rec_cap;    // [S / copies][rec_cap][RM_REC], [S / copies]
+  int copies, sweep; float margin; int types[3];              // types[ty] != 0: the rule applies to rows of agent type ty
+  TokenMaskCtl base;                    // the sets the road rule refines (bits == NULL: every token)
+  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
+};
+struct RoadMapArgs {                    // k_road_records_map: one workgroup (one wave) per distinct scene
+  const float* map_pos; const float* map_orient; const long long* map_type; const long long* map_tok; const int* n_map;   // [S0][M_cap](x2), [S0]
+  int M_cap; const float* map_vocab; int n_token, detail;     // [n_token][11][2]
+  float* records; int rec_cap; int* n_records;
+};
+struct RoadSegArgs { const float* segments; const int* n_segments; int E; float* records; int rec_cap; int* n_records; };
+struct RoadPathArgs { const float* end_pose; int token_size; float* paths; };
+__global__ void k_road_mask(RoadArgs a);
+__global__ void k_road_records_map(RoadMapArgs a);
+__global__ void k_road_records_seg(RoadSegArgs a);
+__global__ void k_road_paths(RoadPathArgs a);
+
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]
   const int* token;                          // [rows]

@@ -555,7 +555,7 @@ class RolloutEngine:
                  tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None,
                  token_logprob: bool = False, sample_logprob: bool = False,
                  sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
-                 token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False):
+                 token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False, stay_on_road=False):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -598,7 +598,16 @@ class RolloutEngine:
         end the step inside another agent's (constant-velocity extrapolated, ``predict``) box and bans them on top of the row's static
         set (all tokens without ``token_masks``); a row whose every token collides keeps its static set.  ``collision_bits``
         [S * A_cap][token_size / 32] and ``collision_allowed`` [S * A_cap] (the sets' sizes before that fallback) are static device
-        buffers that hold the sets of the step that just ran.  ``reload*(avoid_collisions=...)`` turns it on or off (None: keep)."""
+        buffers that hold the sets of the step that just ran.  ``reload*(avoid_collisions=...)`` turns it on or off (None: keep).
+        ``stay_on_road``: road-aware decoding ("road masks" of include/infgen_hip.h) - False, True or
+        ``dict(margin=metres, sweep=0 | 1, detail=1 | 2 | 5 | 10, types=('veh', 'cyc'), segments=None)``.  Every decode step bans the
+        motion tokens whose end box or (``sweep``) path rectangle overlaps a road-edge segment the row does not already straddle, on
+        top of the static set - or of the collision set with ``avoid_collisions`` -; a row with no token left keeps that set.  The
+        segments are ``detail`` chords of every EDGE (type 12) map token's polyline, or the explicit world-coordinate ``segments``
+        ([S0][E][4] or one [E][4] array per distinct scene: the data set's real road edges).  ``road_bits`` / ``road_allowed`` (per
+        row, like the collision pair) and ``road_records`` [S0][capacity][8] / ``road_n_records`` [S0] are static device buffers;
+        the records are rebuilt after every reload.  ``reload*(stay_on_road=...)`` turns it on or off (None: keep; explicit segments
+        belong to the scenes they came with - pass new ones with new scenes)."""
         self.w = weights
         self.options = dict(options) if options else None      # per-engine kernel switches (fields of InfgenOptions)
         # per-engine launch-sequence switches (none changes what is computed beyond fp32 summation order): read from the environment
@@ -781,10 +790,15 @@ class RolloutEngine:
         self.mask_bits = self.mask_row = None             # static device buffers: [n_sets][token_size / 32] words, [S * A_cap] int32
         self._mask_handle = 0                             # infgen_token_mask_create's handle of (mask_bits, mask_row, token_mask_type)
         self._load_token_masks(token_masks, token_mask_type, token_mask_row)
+        self.stay_on_road = None                          # the checked configuration while road-aware decoding is on
+        self.road_bits = self.road_allowed = self.road_records = self.road_n_records = None
+        self._road = self._road_paths = self._road_reg = self._road_seg = None
+        self._road_cap, self._road_dirty = 0, False
         self.avoid_collisions = None                      # dict(margin, predict) while collision-aware decoding is on
         self.collision_bits = self.collision_allowed = None
         self._coll = self._coll_end = self._coll_reg = None
         self._load_collisions(avoid_collisions)
+        self._load_road(stay_on_road)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -989,21 +1003,85 @@ class RolloutEngine:
             self._coll = constraints.collision_buffers(conf, self.S * self.A_cap, self.cfg.token_size, self.device)
             self.collision_bits, self.collision_allowed = self._coll['bits'], self._coll['allowed']
             self._coll['shape'].copy_(self._shape10.reshape(-1, 3))
-            self._coll_cols = torch.arange(self.A_cap, device=self.device, dtype=torch.int32)[None]
-            # the per-token end poses of the vocabulary, once per engine
-            self._coll_end = torch.zeros(12 * self.cfg.token_size + 4, device=self.device)
-            _lib.check(self.lib.infgen_collision_end_poses(_lib.ptr(self.vocab), self.cfg.token_size, _lib.ptr(self._coll_end),
-                                                           self.ops.stream), 'infgen_collision_end_poses')
+            self._end_pose_table()
         if conf != self.avoid_collisions:
             self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
         self.avoid_collisions = conf
         self._apply_token_masks()
 
+    def _end_pose_table(self):
+        """the per-token end poses of the vocabulary, once per engine (collision and road masks read the same table)"""
+        if self._coll_end is None:
+            self._coll_cols = torch.arange(self.A_cap, device=self.device, dtype=torch.int32)[None]
+            self._coll_end = torch.zeros(12 * self.cfg.token_size + 4, device=self.device)
+            _lib.check(self.lib.infgen_collision_end_poses(_lib.ptr(self.vocab), self.cfg.token_size, _lib.ptr(self._coll_end),
+                                                           self.ops.stream), 'infgen_collision_end_poses')
+
+    def _load_road(self, stay):
+        """``stay_on_road`` into the engine (None: keep what is there), like ``_load_collisions``.  The record table is built by the
+        next prologue (``_road_build``): the map may not be in the buffers yet"""
+        if stay is None:
+            return
+        conf = constraints.check_stay_on_road(stay, has_shape=getattr(self, '_shape10', None) is not None, n_scenes=self.S0)
+        if conf is None and self.stay_on_road is None:
+            return
+        if conf is not None and self._road is None:
+            self._road = constraints.road_buffers(conf, self.S * self.A_cap, self.cfg.token_size, self.device)
+            self.road_bits, self.road_allowed = self._road['bits'], self._road['allowed']
+            self._road['shape'].copy_(self._shape10.reshape(-1, 3))
+            self.road_n_records = torch.zeros(self.S0, device=self.device, dtype=torch.int32)
+            self._end_pose_table()
+            self._road_paths = torch.zeros(12 * self.cfg.token_size, device=self.device)
+            _lib.check(self.lib.infgen_road_paths(_lib.ptr(self._coll_end), self.cfg.token_size, _lib.ptr(self._road_paths),
+                                                  self.ops.stream), 'infgen_road_paths')
+        if constraints.road_key(conf) != constraints.road_key(self.stay_on_road):
+            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
+        self.stay_on_road = conf
+        if conf is not None:
+            self._road_dirty = True
+            self._road_seg = None
+            if conf['segments'] is not None:
+                self._road_seg = tuple(torch.from_numpy(a).to(self.device) for a in conf['segments'])
+            self._road_room(64)
+        self._apply_token_masks()
+
+    def _road_room(self, need: int):
+        """a record table of at least ``need`` records per distinct scene: grown (a new buffer, so captured graphs go and the
+        configuration is attached again), never shrunk"""
+        if self.road_records is None or need > self._road_cap:
+            self._road_cap = _round_up(max(need, 1), 64)
+            self.road_records = torch.zeros(self.S0, self._road_cap, 8, device=self.device)
+            self._graph = self._wgraph = None
+
+    def _road_build(self):
+        """the record table from the map in the buffers (or the explicit segments), once per reload: one count of EDGE tokens per
+        scene sizes it (the only host synchronisation), k_road_records_map / _seg fills it"""
+        conf, P = self.stay_on_road, _lib.ptr
+        if self._road_seg is not None:
+            seg, nseg = self._road_seg
+            self._road_room(int(seg.shape[1]))
+            self._apply_token_masks(validate=False)
+            _lib.check(self.lib.infgen_road_records_from_segments(P(seg), P(nseg), self.S0, int(seg.shape[1]), P(self.road_records),
+                                                                  self._road_cap, P(self.road_n_records), self.ops.stream),
+                       'infgen_road_records_from_segments')
+        else:
+            mtok, mtype = self._map_cat[0], self._map_cat[1]
+            inmap = torch.arange(self.M_cap, device=self.device)[None] < self.n_map[:, None]
+            edges = int(((mtype == 12) & inmap).sum(dim=1).max().item())
+            self._road_room(edges * conf['detail'])
+            self._apply_token_masks(validate=False)
+            _lib.check(self.lib.infgen_road_records_from_map(P(self.map_pos), P(self.map_orient), P(mtype), P(mtok), P(self.n_map),
+                                                             self.S0, self.M_cap, P(self._map_vocab), int(self._map_vocab.shape[0]),
+                                                             conf['detail'], P(self.road_records), self._road_cap,
+                                                             P(self.road_n_records), self.ops.stream), 'infgen_road_records_from_map')
+        self._road_dirty = False
+
     def _apply_token_masks(self, validate: bool = True):
         """the library's handle of (table, per-row selectors, per-type sets) into the context: registered again when one of the
         three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  A
         collision configuration rides on the handle (one without a table when the engine has no ``token_masks``)"""
-        if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and not self._mask_handle):
+        if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and self.stay_on_road is None
+                                 and not self._mask_handle):
             return
         if self.token_masks is not None:
             reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
@@ -1027,6 +1105,21 @@ class RolloutEngine:
                                                                 P(self._coll_end), conf['predict'], conf['margin'], P(k['allowed'])),
                            'infgen_token_mask_collision')
             self._coll_reg = creg
+        road = self.stay_on_road
+        rreg = None if road is None else (self._mask_handle, road['margin'], road['sweep'], road['types'], self.road_records.data_ptr(),
+                                          self._road_cap)
+        if rreg != self._road_reg:      # road-aware decoding rides on the handle in the same way (the table's address is part of it)
+            if road is None:
+                _lib.check(self.lib.infgen_token_mask_road(self._mask_handle, None, None, None, None, None, None, None, 0, 1, 1, 0.0,
+                                                           None, None), 'infgen_token_mask_road')
+            else:
+                k = self._road
+                _lib.check(self.lib.infgen_token_mask_road(self._mask_handle, P(k['bits']), P(k['ident']), P(k['shape']),
+                                                           P(self._coll_end), P(self._road_paths), P(self.road_records),
+                                                           P(self.road_n_records), self._road_cap, self.copies, road['sweep'],
+                                                           road['margin'], (C.c_int * 3)(*road['types']), P(k['allowed'])),
+                           'infgen_token_mask_road')
+            self._road_reg = rreg
         self._ctx.token_mask = self._mask_handle
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
@@ -1034,7 +1127,7 @@ class RolloutEngine:
     def _drop_mask_handle(self):
         if getattr(self, '_mask_handle', 0):
             self.lib.infgen_token_mask_destroy(self._mask_handle)
-            self._mask_handle, self._mask_reg, self._coll_reg = 0, None, None
+            self._mask_handle, self._mask_reg, self._coll_reg, self._road_reg = 0, None, None, None
             if getattr(self, '_ctx', None) is not None:
                 self._ctx.token_mask = 0
 
@@ -1051,9 +1144,10 @@ class RolloutEngine:
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
     def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
-                       avoid_collisions=None):
+                       avoid_collisions=None, stay_on_road=None):
         self._load_token_masks(*(token_masks or (None, None, None)))
         self._load_collisions(avoid_collisions)
+        self._load_road(stay_on_road)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
@@ -1079,6 +1173,7 @@ class RolloutEngine:
         self._wgraph = None                # (the whole-rollout graph restores the state from the old snapshot's buffers)
         self._mg_checked = False           # the new map may hold more pt <-> pt edges than the buffers
         self._prologue_done = False
+        self._road_dirty = True            # the road records belong to the old map
 
     # ------------------------------------------------------------------ log replay
     def _alloc_replay(self, with_pose: bool):
@@ -1124,7 +1219,7 @@ class RolloutEngine:
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-               avoid_collisions=None):
+               avoid_collisions=None, stay_on_road=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -1139,7 +1234,7 @@ class RolloutEngine:
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road)
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1156,7 +1251,7 @@ class RolloutEngine:
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                       sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None,
-                      token_mask_row=None, avoid_collisions=None) -> bool:
+                      token_mask_row=None, avoid_collisions=None, stay_on_road=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -1171,7 +1266,7 @@ class RolloutEngine:
             return False
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road)
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1233,7 +1328,7 @@ class RolloutEngine:
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
                      sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-                     avoid_collisions=None):
+                     avoid_collisions=None, stay_on_road=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1243,7 +1338,7 @@ class RolloutEngine:
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -1404,6 +1499,10 @@ class RolloutEngine:
         self.reset()
         if self._coll is not None:                   # the rows' boxes for k_collision_mask (rows insertion appends: _step_gen)
             self._coll['shape'].copy_(self._shape10.reshape(rows, 3))
+        if self.stay_on_road is not None:            # road-aware decoding: the rows' boxes, and the record table of a new map
+            self._road['shape'].copy_(self._shape10.reshape(rows, 3))
+            if self._road_dirty:
+                self._road_build()
         # categorical embedding rows (agent_decoder.py:376-380,492)
         if self.cat_agent is None:
             self.cat_agent = torch.empty(rows, D, device=dev)
@@ -1835,12 +1934,15 @@ class RolloutEngine:
                        'infgen_active_row_groups')
         if t > 0:
             yield from self._insert_step(t)
-            if self.avoid_collisions is not None:
-                # the boxes of the rows this step appended (they are obstacles, and get sets, from the next step on)
+            live_shapes = [k['shape'] for k, on in ((self._coll, self.avoid_collisions), (self._road, self.stay_on_road)) if on is not None]
+            if live_shapes:
+                # the boxes of the rows this step appended (they are obstacles, and get sets, from the next step on): one mask, merged
+                # into the shape array of every per-step mask kernel that is on
                 S, A_cap = self.S, self.A_cap
-                new = (self._coll_cols >= I['first_new'][:, None]) & (self._coll_cols < self.n_agents[:, None])
-                cs = self._coll['shape'].view(S, A_cap, 3)
-                cs.copy_(torch.where(new[..., None], I['shape_all'].view(S, A_cap, 3), cs))
+                new = ((self._coll_cols >= I['first_new'][:, None]) & (self._coll_cols < self.n_agents[:, None]))[..., None]
+                for shp in live_shapes:
+                    cs = shp.view(S, A_cap, 3)
+                    cs.copy_(torch.where(new, I['shape_all'].view(S, A_cap, 3), cs))
         self._decoded_rows.add_(self.n_agents.sum())       # A_t: rows decoded at this step, incl. the inserted ones
         tight = use_groups and self.flags['row_groups_tight']
         if tight:

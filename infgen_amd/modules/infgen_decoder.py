@@ -17,7 +17,7 @@ import torch.nn as nn
 
 from .. import _lib, logprob, scene_setup
 from ..closed_loop import ClosedLoopSession
-from ..constraints import TokenMasks, check_avoid_collisions, check_type_selectors
+from ..constraints import TokenMasks, check_avoid_collisions, check_stay_on_road, check_type_selectors, road_key
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -392,6 +392,10 @@ class InfGenDecoder(nn.Module):
         # collision-aware decoding (RolloutEngine's avoid_collisions): False, True or dict(margin=, predict=).  Taken by
         # inference, inference_batch, inference_rollouts and closed_loop alike; part of the engine cache key
         self.avoid_collisions = False
+        # road-aware decoding (RolloutEngine's stay_on_road): False, True or dict(margin=, sweep=, detail=, types=,
+        # segments=).  Taken by the same entries; its settings are part of the engine cache key, explicit segments are contents that
+        # every call loads again with its scenes
+        self.stay_on_road = False
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -505,6 +509,13 @@ class InfGenDecoder(nn.Module):
         if ac is not None:      # (fixed per engine, like the constraints)
             fixed.update(avoid_collisions=ac)
             key += (('avoid_collisions', ac['margin'], ac['predict']),)
+        sr = check_stay_on_road(getattr(self, 'stay_on_road', False))      # (absent on a bare argument holder: off)
+        if sr is not None:
+            key += (('stay_on_road',) + road_key(sr),)
+            if sr['segments'] is None:
+                fixed.update(stay_on_road=sr)
+            else:      # (world coordinates of this call's scenes: loaded with them, like the uniforms)
+                live.update(stay_on_road=sr)
         return dict(fixed, **live), live, key
 
     @staticmethod

@@ -17,6 +17,9 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
                                      temperature_row=None)                                  -> token (N,), sample_logprob
     torch.ops.infgen_hip.collision_mask(pos, head, state, n_agents, type, shape, c, end_pose, predict=1, margin=0,
                                         mask_bits?, mask_row?, mask_type?, first_new?)      -> sets (S A, token_size / 32) int32, allowed (S A,)
+    torch.ops.infgen_hip.road_mask(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_records, copies=1,
+                                   sweep=1, margin=0, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
+                                                                                            -> sets (S A, token_size / 32) int32, allowed (S A,)
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -358,6 +361,117 @@ def collision_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n
 @collision_mask.register_fake
 def _(pos, head, state, n_agents, type, shape, c, end_pose, predict=1, margin=0.0, mask_bits=None, mask_row=None, mask_type=None,
       first_new=None):
+    rows = pos.shape[0] * pos.shape[2]
+    return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32))
+
+
+def road_paths(end_pose: torch.Tensor) -> torch.Tensor:
+    """the path table of ``road_mask`` from the end-pose table of ``collision_end_poses``: (3, token_size, 4) = cos, sin of every
+    token's end displacement, half its length, 0 (``infgen_road_paths``; computed once per vocabulary)"""
+    n = (int(end_pose.numel()) - 4) // 12
+    if end_pose.dim() != 1 or n * 12 + 4 != end_pose.numel() or n <= 0:
+        raise ValueError('end_pose is the table of collision_end_poses (12 token_size + 4 floats)')
+    ops = _ops(end_pose.device)
+    ep, tab = _f32(end_pose), torch.zeros(3, n, 4, device=end_pose.device)
+    _lib.check(ops.lib.infgen_road_paths(_lib.ptr(ep), n, _lib.ptr(tab), ops.stream), 'infgen_road_paths')
+    return tab
+
+
+def road_records_from_map(map_pos: torch.Tensor, map_orient: torch.Tensor, map_type: torch.Tensor, map_tok: torch.Tensor,
+                          n_map: torch.Tensor, map_vocab: torch.Tensor, detail: int = 2,
+                          capacity: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the road-segment records of S0 distinct scenes from their EDGE (type 12) map tokens ("road masks" of include/infgen_hip.h,
+    ``infgen_road_records_from_map``): ``map_pos`` (S0, M, 2), ``map_orient`` / ``map_type`` / ``map_tok`` (S0, M), ``n_map`` (S0,),
+    ``map_vocab`` (n_token, 11, 2) or (n_token, 22).  ``capacity``: records per scene (None: counted from ``map_type``, one
+    synchronisation).  -> records (S0, capacity, 8), n_records (S0,) int32"""
+    if map_pos.dim() != 3 or map_pos.shape[2] != 2 or any(tuple(t.shape) != tuple(map_pos.shape[:2]) for t in (map_orient, map_type, map_tok)):
+        raise ValueError('road_records_from_map takes map_pos (S0, M, 2) and map_orient, map_type, map_tok (S0, M)')
+    S0, M = (int(v) for v in map_pos.shape[:2])
+    if tuple(n_map.shape) != (S0,) or map_vocab.numel() % 22 or map_vocab.numel() == 0:
+        raise ValueError('road_records_from_map takes n_map (S0,) and map_vocab (n_token, 11, 2)')
+    if detail not in (1, 2, 5, 10):
+        raise ValueError('detail must be 1, 2, 5 or 10')
+    dev = map_pos.device
+    ops = _ops(dev)
+    ty, tk = map_type.to(dev, torch.int64).contiguous(), map_tok.to(dev, torch.int64).contiguous()
+    nm = n_map.to(dev, torch.int32).contiguous()
+    if capacity is None:
+        inmap = torch.arange(M, device=dev)[None] < nm[:, None]
+        capacity = int(((ty == 12) & inmap).sum(dim=1).max().item()) * int(detail)
+    cap = max(int(capacity), 1)
+    rec, n = torch.zeros(S0, cap, 8, device=dev), torch.zeros(S0, device=dev, dtype=torch.int32)
+    mp, mo, mv = _f32(map_pos), _f32(map_orient), _f32(map_vocab)
+    _lib.check(ops.lib.infgen_road_records_from_map(_lib.ptr(mp), _lib.ptr(mo), _lib.ptr(ty), _lib.ptr(tk), _lib.ptr(nm), S0, M,
+                                                    _lib.ptr(mv), int(mv.numel()) // 22, int(detail), _lib.ptr(rec), cap, _lib.ptr(n),
+                                                    ops.stream), 'infgen_road_records_from_map')
+    return rec, n
+
+
+def road_records_from_segments(segments: torch.Tensor, n_segments: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the records of explicit world-coordinate segments (S0, E, 4) = x0, y0, x1, y1, the first ``n_segments`` (S0,) of each scene
+    (``infgen_road_records_from_segments``) -> records (S0, E, 8), n_records (S0,) int32"""
+    if segments.dim() != 3 or segments.shape[2] != 4 or segments.shape[1] == 0 or tuple(n_segments.shape) != (segments.shape[0],):
+        raise ValueError('road_records_from_segments takes segments (S0, E, 4) and n_segments (S0,)')
+    dev = segments.device
+    ops = _ops(dev)
+    S0, E = (int(v) for v in segments.shape[:2])
+    sg, ns = _f32(segments), n_segments.to(dev, torch.int32).contiguous()
+    rec, n = torch.zeros(S0, E, 8, device=dev), torch.zeros(S0, device=dev, dtype=torch.int32)
+    _lib.check(ops.lib.infgen_road_records_from_segments(_lib.ptr(sg), _lib.ptr(ns), S0, E, _lib.ptr(rec), E, _lib.ptr(n), ops.stream),
+               'infgen_road_records_from_segments')
+    return rec, n
+
+
+@torch.library.custom_op('infgen_hip::road_mask', mutates_args=())
+def road_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+              shape: torch.Tensor, c: int, end_pose: torch.Tensor, paths: torch.Tensor, records: torch.Tensor,
+              n_records: torch.Tensor, copies: int = 1, sweep: int = 1, margin: float = 0.0, types: Optional[List[int]] = None,
+              mask_bits: Optional[torch.Tensor] = None, mask_row: Optional[torch.Tensor] = None,
+              mask_type: Optional[List[int]] = None, first_new: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the allowed-token sets of one decode step from the road-edge records (road-aware decoding; "road masks" of
+    include/infgen_hip.h, ``infgen_road_mask``): the scene arrays and ``end_pose`` as for ``collision_mask``, ``paths`` from
+    ``road_paths``, ``records`` (S / copies, capacity, 8) and ``n_records`` (S / copies,) from ``road_records_from_map`` /
+    ``_from_segments``, ``types`` the (vehicle, pedestrian, cyclist) switch (None: vehicles and cyclists).  ``mask_bits`` /
+    ``mask_row`` / ``mask_type``: the base sets (none: every token).  Returns the sets (S * A, token_size / 32) int32 words and the
+    number of allowed tokens per row before the empty-set fallback (S * A,)."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or head.shape != pos.shape[:3] or state.shape != pos.shape[:3]:
+        raise ValueError('road_mask takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,):
+        raise ValueError('road_mask takes type (S, A), shape (S, A, 3), n_agents (S,)')
+    if first_new is not None and tuple(first_new.shape) != (S,):
+        raise ValueError('first_new must be (S,)')
+    token_size = (int(end_pose.numel()) - 4) // 12
+    if end_pose.dim() != 1 or token_size * 12 + 4 != end_pose.numel() or token_size % 32:
+        raise ValueError('end_pose is the table of collision_end_poses (12 token_size + 4 floats, token_size a multiple of 32)')
+    if paths.numel() != 12 * token_size:
+        raise ValueError('paths is the table of road_paths (3, token_size, 4)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    if records.dim() != 3 or records.shape[2] != 8 or records.shape[0] != S // copies or tuple(n_records.shape) != (S // copies,):
+        raise ValueError('road_mask takes records (S / copies, capacity, 8) and n_records (S / copies,)')
+    types = [1, 0, 1] if types is None else [int(bool(v)) for v in types]
+    if len(types) != 3:
+        raise ValueError('types has three entries: vehicle, pedestrian, cyclist')
+    dev = pos.device
+    ops = _ops(dev)
+    i32 = lambda t: None if t is None else t.to(dev, torch.int32).contiguous()
+    ty = i32(type)
+    tm, _keep_mask = _token_mask(mask_bits, mask_row, mask_type, ty.reshape(-1), S * A, token_size, dev)
+    bits = torch.zeros(S * A, token_size // 32, device=dev, dtype=torch.int32)
+    count = torch.zeros(S * A, device=dev, dtype=torch.int32)
+    st, na, fn, nr = i32(state), i32(n_agents), i32(first_new), i32(n_records)
+    p, h, sh, ep, pa, rc = _f32(pos), _f32(head), _f32(shape), _f32(end_pose), _f32(paths), _f32(records)
+    _lib.check(ops.lib.infgen_road_mask(_lib.ptr(p), _lib.ptr(h), _lib.ptr(st), _lib.ptr(na), _lib.ptr(fn), _lib.ptr(ty), _lib.ptr(sh),
+                                        S, A, T, int(c), _lib.ptr(ep), _lib.ptr(pa), token_size, _lib.ptr(rc), _lib.ptr(nr),
+                                        int(records.shape[1]), int(copies), int(sweep), float(margin), (C.c_int * 3)(*types),
+                                        *tm[:4], _lib.ptr(bits), _lib.ptr(count), ops.stream), 'infgen_road_mask')
+    return bits, count
+
+
+@road_mask.register_fake
+def _(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_records, copies=1, sweep=1, margin=0.0, types=None,
+      mask_bits=None, mask_row=None, mask_type=None, first_new=None):
     rows = pos.shape[0] * pos.shape[2]
     return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32))
 
