@@ -35,6 +35,7 @@
  *   infgen_point_edges, infgen_occupancy, infgen_insert_decide, infgen_insert_finalize, infgen_raw_feature_rows
  *                            the insertion sub-loop (infgen/modules/agent_decoder.py:1773-2105)
  *   infgen_command_rows      no counterpart: a controller's per-step commands (token ids or target poses) for the replayed rows
+ *   infgen_branch_scenes, infgen_resample_parents   no counterpart: a copy of a scene continues as a clone of another copy
  *
  * and, around the path:
  *
@@ -467,6 +468,34 @@ int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream);
  * touched.  The pointers that r declares const are written here (the plan belongs to the caller).  A_cap need not be a multiple of 32. */
 int infgen_command_rows(const InfgenRollout* r, int t, int kind, const int* cmd_token, const float* cmd_pose,
                         const unsigned char* cmd_mask, const float* shape, float* cmd_cost, void* stream);
+
+/* branching rollouts: BRANCHING, "scene slot s becomes a clone of slot p as of the boundary in front of decode step t" - what tree
+ * search, MPC and sequential Monte Carlo over the copies of a scene need (k_branch_scenes: one launch, no host read).
+ * infgen_branch_scenes: parent is a device int32 array [S].  For every agent-side scene s with p = parent[s] != s, slot s receives slot
+ * p's rollout state as it stands between decode step t - 1 and decode step t, 0 <= t <= steps (= T - 2):
+ *   copied   the per-scene [T][A_cap] blocks of pos (x 2), head, state, token, grid, tmask, imask, catflag, and bos [A_cap];
+ *            every ring slot of ringK[l] / ringV[l], l < num_layers (A_cap x 128 floats per ring slot and scene);
+ *            the scene's rows of X - the fused raw feature of column 2 + t the previous step's tail left; nothing recomputes it;
+ *            pred_traj / pred_head / pred_state;
+ *            the slices [0, t) of token_logprob, sample_logprob and (store_logits) logits, where those pointers are given.
+ *   kept     what configures a slot and is not history: sample_u, sample_temp_row, the token mask's selectors and tables, replay_row,
+ *            the plan arrays teacher_* (past plan columns are not read again, future ones are the slot's own commands), the collision
+ *            and road buffers (rebuilt every step from the copied poses), type / n_agents and the map side (equal inside a copy
+ *            group).  A clone therefore diverges from its parent at the next draw or command.  Scratch is not touched.
+ *   parent   source and destination belong to one COPY GROUP, the same map-side scene: map_scene[s] == map_scene[p] (map_scene NULL:
+ *            every scene is its own group, only the identity is valid); sources are fixed points, parent[parent[s]] == parent[s] - no
+ *            slot is read and written in one launch, so the gather runs in place.  An entry that is out of range, in another group
+ *            or no fixed point is treated as parent[s] = s and counted into *n_bad (optional device int, zeroed by the call first);
+ *            nothing outside the layout is read for any content of parent, and the library never dereferences parent on the host.
+ * Refused: t out of range, a NULL parent, a context with scenario insertion (first_new != NULL: row counts, types and shapes differ
+ * between the copies and part of the bookkeeping lives in host lists - branching such a context is left out).
+ * infgen_resample_parents: arbitrary ancestor indices [S0 * copies] (global slot indices inside the slot's own group, as a resampler
+ * produces them; one outside its group counts as the slot itself) -> a valid parent vector [S0 * copies]: a slot that is named at
+ * least once keeps itself; the slots nobody names, in ascending order, receive the surplus - ancestor j's count[j] - 1 extra copies, in
+ * ascending j.  The multiset of ancestors per group is preserved and the result is deterministic.  One workgroup per group;
+ * 1 <= copies <= 1024, else refused. */
+int infgen_branch_scenes(const InfgenRollout* r, int t, const int* parent, int* n_bad, void* stream);
+int infgen_resample_parents(const int* ancestor, int S0, int copies, int* parent, void* stream);
 
 /* reproducible stand-in for softmax -> topk(k) -> multinomial (agent_decoder.py:2162-2163,2194-2195): the k most
  * probable tokens, inverse-CDF over their probabilities with a caller-supplied uniform per row; 1 <= k <= min(16, n), else refused */

@@ -181,6 +181,15 @@ class ClosedLoopSession:
             x = full
         eng.mask_row.copy_(x.reshape(-1))
 
+    def branch(self, parent):
+        """``RolloutEngine.branch(parent, t)`` at this session's step: slot s continues as a clone of slot ``parent[s]`` from the
+        next ``advance()`` on - ``observe()`` then shows the parent's newest column in the child slot.  A pending
+        command stays the slot's own, as do its controlled-row flags; past commands of the child are not read again.  The collision
+        and road buffers are not cloned (every step rebuilds them from the poses): until the next ``advance()``,
+        ``observe()['allowed_tokens']`` of a child slot still shows the sizes of the child's own sets of the step that just ran."""
+        self._check_open()
+        self.eng.branch(parent, self.t)
+
     def advance(self):
         """the command kernel, then decode step ``t`` (with its insertion sub-loop when the engine inserts agents)"""
         self._check_open()

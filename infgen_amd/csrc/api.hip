@@ -1688,6 +1688,67 @@ extern "C" int infgen_command_rows(const InfgenRollout* r, int t, int kind, cons
   return check_launch(me);
 }
 
+// ---- branching rollouts: slot s becomes a clone of slot parent[s] as of the boundary in front of decode step t (k_branch_scenes)
+// the segment table: everything a decode step reads that an earlier step (or the prologue) wrote per scene.  What configures a slot
+// (uniforms, temperatures, masks, plans, replay flags) and what every step rebuilds before reading it (edge sets, scratch) is not in it.
+static int branch_segments(const InfgenRollout* r, int t, BranchArgs* a) {
+  const long long A = r->A_cap, rows = (long long)r->S * A;
+  int n = 0, chunk = 0;
+  auto add = [&](void* base, long long bytes, int outer, long long outer_stride) {
+    if (!base || bytes <= 0 || outer <= 0) return;
+    BranchSeg& g = a->seg[n++];
+    g.base = static_cast<char*>(base); g.bytes = bytes; g.outer = outer; g.outer_stride = outer_stride;
+    g.per_block = (int)((bytes + BR_CHUNK - 1) / BR_CHUNK);
+    g.chunk0 = chunk;
+    g.wide = ((reinterpret_cast<uintptr_t>(base) | (uintptr_t)bytes | (uintptr_t)outer_stride) & 15) == 0 ? 1 : 0;
+    chunk += g.per_block * outer;
+  };
+  const long long TA = (long long)r->T * A;
+  add(r->pos, TA * 8, 1, 0); add(r->head, TA * 4, 1, 0); add(r->state, TA * 4, 1, 0); add(r->token, TA * 4, 1, 0);
+  add(r->grid, TA * 4, 1, 0); add(r->tmask, TA, 1, 0); add(r->imask, TA, 1, 0); add(r->catflag, TA, 1, 0);
+  add(r->bos, A * 4, 1, 0);
+  for (int l = 0; l < r->num_layers; ++l) {
+    add(r->ringK[l], A * D * 4, r->ring, rows * D * 4);
+    add(r->ringV[l], A * D * 4, r->ring, rows * D * 4);
+  }
+  add(r->X, A * D * 4, 1, 0);
+  add(r->pred_traj, A * r->R * 8, 1, 0); add(r->pred_head, A * r->R * 4, 1, 0); add(r->pred_state, A * r->R * 4, 1, 0);
+  // the step-major logs: the slices of the steps that ran, [0, t)
+  add(r->token_logprob, A * 4, t, rows * 4);
+  add(r->sample_logprob, A * 4, t, rows * 4);
+  add(r->store_logits ? r->logits : nullptr, A * r->token_size * 4, t, rows * r->token_size * 4);
+  a->n_seg = n;
+  return chunk;
+}
+
+extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* parent, int* n_bad, void* stream) {
+  const char* me = "infgen_branch_scenes";
+  RET_IF(validate(r, me));
+  if (r->S <= 0 || r->S > 65535) return fail(me, "S must be in 1..65535");
+  if (r->T <= 0 || r->R <= 0 || r->ring <= 0 || r->token_size <= 0) return fail(me, "bad sizes");
+  if (!parent) return fail(me, "null parent");
+  if (r->first_new) return fail(me, "contexts with scenario insertion cannot branch: row counts, types and shapes differ between the copies");
+  if (t < 0 || 1 + t > r->T - 1) return fail(me, "t must be in 0..steps (the boundary in front of decode step t)");
+  if (!(r->pos && r->head && r->state && r->token && r->grid && r->tmask && r->imask && r->catflag && r->bos && r->X))
+    return fail(me, "null scene array");
+  static_assert(BR_MAX_SEGS >= 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 3, "segment table too short");
+  BranchArgs a{};
+  a.S = r->S; a.parent = parent; a.map_scene = r->map_scene; a.n_bad = n_bad;
+  const int chunks = branch_segments(r, t, &a);
+  if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
+  hipLaunchKernelGGL(k_branch_scenes, dim3(chunks, r->S), dim3(BR_NT), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+extern "C" int infgen_resample_parents(const int* ancestor, int S0, int copies, int* parent, void* stream) {
+  const char* me = "infgen_resample_parents";
+  if (!ancestor || !parent) return fail(me, "null array");
+  if (S0 <= 0 || copies <= 0) return fail(me, "S0 and copies must be positive");
+  if (copies > RS_NT * RS_ITEMS) return fail(me, "copies must be <= 1024");
+  hipLaunchKernelGGL(k_resample_parents, dim3(S0), dim3(RS_NT), 0, (hipStream_t)stream, ResampleArgs{ancestor, copies, parent});
+  return check_launch(me);
+}
+
 // MLPEmbedding pack (first Linear K0 -> 128): P(K0p,128) b ln_g ln_b | P(128,128) b ln_g ln_b | P(128,128) b
 static inline int mlpemb_off2(int K0p) { return K0p * 128 + 3 * 128; }
 static inline int mlpemb_off3(int K0p) { return mlpemb_off2(K0p) + 16384 + 3 * 128; }

@@ -652,6 +652,31 @@ __global__ void k_road_records_map(RoadMapArgs a);
 __global__ void k_road_records_seg(RoadSegArgs a);
 __global__ void k_road_paths(RoadPathArgs a);
 
+// branch_kernels.hip: branching rollouts (include/infgen_hip.h, "branching").  k_branch_scenes gathers, for every scene s with a
+// valid parent[s] != s, slot parent[s]'s rollout state into slot s - one launch over (chunk of a segment, scene).  A SEGMENT is one
+// buffer of the context as `outer` blocks per scene: block o of scene s is the `bytes` bytes at base + o * outer_stride + s * bytes.
+constexpr int BR_MAX_SEGS = 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 3;     // scene arrays, rings, X, pred_*, the three step-major logs
+constexpr int BR_NT = 256;              // threads per workgroup
+constexpr int BR_VEC = 4;               // 16-byte words a lane moves: all loads are issued before the first store
+constexpr int BR_CHUNK = BR_NT * BR_VEC * 16;      // bytes of a block one workgroup moves
+struct BranchSeg {
+  char* base; long long bytes; long long outer_stride;
+  int outer;                            // blocks per scene (ring slots, decode steps so far; 1 for the rest)
+  int chunk0;                           // the segment's first chunk in the launch's x dimension (chunks per block = ceil(bytes / BR_CHUNK))
+  int per_block;                        // chunks per block
+  int wide;                             // 1: base, bytes and stride are multiples of 16 (16 bytes per lane), 0: byte by byte
+};
+struct BranchArgs {
+  int S, n_seg;
+  const int* parent; const int* map_scene;     // [S]; map_scene NULL: every scene is its own group
+  int* n_bad;                                  // optional: entries treated as the identity
+  BranchSeg seg[BR_MAX_SEGS];
+};
+struct ResampleArgs { const int* ancestor; int copies; int* parent; };      // [S0 * copies] each; one workgroup per group
+constexpr int RS_NT = 256, RS_ITEMS = 4;       // copies <= RS_NT * RS_ITEMS
+__global__ void k_branch_scenes(BranchArgs a);
+__global__ void k_resample_parents(ResampleArgs a);
+
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]
   const int* token;                          // [rows]

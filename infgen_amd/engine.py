@@ -806,6 +806,8 @@ class RolloutEngine:
         # [steps][rows] log-probability of the sampled token under the re-normalised top-k (InfgenRollout.sample_logprob)
         self.sample_logprob = f(steps, rows) if sample_logprob else None
         self._rollout_lp = self._rollout_slp = None
+        # [1] int32: the entries of the last ``branch`` call's parent vector that broke the contract and were read as the identity
+        self._branch_bad = torch.zeros(1, device=dev, dtype=torch.int32)      # (read through the ``branch_bad`` property)
         self.tok_tab = self.grid_tab = self.cat_agent = self.cat_seed = None
         self.x_pt = None
         self._ctx = None
@@ -2004,6 +2006,50 @@ class RolloutEngine:
 
     def step(self, t: int):
         _lib.check(self.lib.infgen_decode_step(C.byref(self._ctx), t, self.ops.stream), 'infgen_decode_step')
+
+    @property
+    def branch_bad(self) -> torch.Tensor:
+        """[1] int32 on the device: the entries of the last ``branch`` call's parent vector that broke the contract and were read
+        as the identity (0 before the first call)"""
+        if self._branch_bad is None:
+            self._branch_bad = torch.zeros(1, device=self.device, dtype=torch.int32)
+        return self._branch_bad
+
+    def branch(self, parent, t: int):
+        """branching rollouts ("branching" of include/infgen_hip.h): every slot s with ``parent[s] != s`` becomes a
+        clone of slot ``parent[s]`` as of the boundary in front of decode step ``t`` (0 .. steps) - stored columns, the temporal
+        K / V rings, the pending raw feature, ``pred_*`` and the logs of the steps that ran.  One launch of ``infgen_branch_scenes``
+        on the current stream.  Each slot keeps its own uniforms, temperature, constraints, replay flags and commands, so a clone
+        diverges from its parent at the next draw.  ``parent``: int [S] or [S0, copies], global slot indices; source and
+        destination in one copy group, every source a fixed point (``infgen_amd.branching`` makes such vectors).  A device tensor
+        is taken as it is - stream-ordered, no host read; entries that break the contract are treated as the identity and counted
+        into ``branch_bad`` (a device int the call zeroes first).  A host tensor or array is checked here (``ValueError`` naming
+        the first bad entry).  Eager: captured graphs stay as they are (``run(t0, t1)`` over a partial range is eager too).
+        Refused on an engine with scenario insertion (row counts, types and shapes differ between the copies) and before
+        ``prologue()``; with ``copies == 1`` only the identity is valid (a host vector is refused; the entries of a device one are
+        all counted into ``branch_bad``)."""
+        from . import branching
+        if self.insertion:
+            raise ValueError('branch: engines with scenario insertion cannot branch (row counts, types and shapes differ between '
+                             'the copies): left out')
+        if self._ctx is None or not self._prologue_done:
+            raise RuntimeError('branch: run prologue() first - there is no rollout state to clone yet')
+        steps = self.cfg.num_decode_steps
+        if not 0 <= int(t) <= steps:
+            raise ValueError(f'branch: t = {t} is outside 0 .. {steps}')
+        p = parent if isinstance(parent, torch.Tensor) else torch.as_tensor(np.asarray(parent))
+        if p.is_floating_point() or p.dtype == torch.bool:
+            raise ValueError('parent holds integer slot indices')
+        if tuple(p.shape) not in ((self.S,), (self.S0, self.copies)):
+            raise ValueError(f'parent: expected shape {(self.S,)} or {(self.S0, self.copies)}, got {tuple(p.shape)}')
+        if not p.is_cuda:
+            if self.copies == 1 and not torch.equal(p.reshape(-1).long(), torch.arange(self.S)):
+                raise ValueError('branch: an engine with copies == 1 has no copy to clone - only the identity is a valid parent')
+            p = torch.from_numpy(branching.check_parent(p.numpy(), self.S0, self.copies))
+        p = p.to(self.device, torch.int32).contiguous().view(-1)
+        _lib.check(self.lib.infgen_branch_scenes(C.byref(self._ctx), int(t), _lib.ptr(p), _lib.ptr(self.branch_bad), self.ops.stream),
+                   'infgen_branch_scenes')
+        self._rollout_lp = self._rollout_slp = None
 
     def ctx_tensor(self) -> torch.Tensor:
         """the bytes of this engine's InfgenRollout block (after ``prologue``) - the state handle of

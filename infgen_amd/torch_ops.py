@@ -29,6 +29,7 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.integrate_tokenise(token, state, type, pos, head, n_agents, ego, vocab, grid) -> pos', head', pred_traj, pred_head, grid, state'
     torch.ops.infgen_hip.decode_step(ctx_bytes, t, pos, head, state, token, grid, x, next_token, next_state) -> next_token, next_state
     torch.ops.infgen_hip.command_rows(ctx_bytes, t, teacher_token, teacher_state, cmd_token?, cmd_pose?, cmd_mask?, shape?) -> cost (S, A_cap)
+    torch.ops.infgen_hip.branch_scenes(ctx_bytes, t, parent (S,) int)                       -> n_bad (1,) int32; slot s := slot parent[s]
 
 (``decode_step`` works on the persistent state block ``InfgenRollout`` of include/infgen_hip.h, which ``RolloutEngine.ctx_tensor()``
 hands out as bytes; whole rollouts stay a C-ABI call, ``infgen_rollout_run``, driven by infgen_amd/engine.py).  ``register_fake`` gives every op a shape function, so they trace under
@@ -637,6 +638,32 @@ def command_rows(ctx: torch.Tensor, t: int, teacher_token: torch.Tensor, teacher
 @command_rows.register_fake
 def _(ctx, t, teacher_token, teacher_state, cmd_token=None, cmd_pose=None, cmd_mask=None, shape=None):
     return teacher_token.new_empty(teacher_token.shape[0], teacher_token.shape[2], dtype=torch.float32)
+
+
+@torch.library.custom_op('infgen_hip::branch_scenes', mutates_args=())
+def branch_scenes(ctx: torch.Tensor, t: int, parent: torch.Tensor) -> torch.Tensor:
+    """branching rollouts (``infgen_branch_scenes``; "branching" of include/infgen_hip.h): every slot s of the state block with
+    ``parent[s] != s`` becomes a clone of slot ``parent[s]`` as of the boundary in front of decode step ``t``.  ``ctx`` as in
+    ``decode_step``; ``parent`` [S] or [S0, copies] int device tensor of global slot indices (same copy group, sources fixed
+    points).  The ~30 arrays the block points to are edited in place (not declared: the block owns them); returns the number of
+    entries that broke the contract and were treated as the identity, (1,) int32.  No host read."""
+    if not parent.is_cuda:
+        raise _lib.InfgenHipError('infgen_hip ops need cuda tensors: the HIP path has no CPU fallback')
+    if parent.is_floating_point() or parent.dtype == torch.bool:
+        raise ValueError('branch_scenes: parent holds integer slot indices')
+    ops = _ops(parent.device)
+    blk = _lib.Rollout.from_buffer_copy(ctx.numpy().tobytes())
+    if parent.numel() != int(blk.S):
+        raise ValueError(f'branch_scenes: parent must hold one entry per scene slot ({int(blk.S)})')
+    p = parent.to(torch.int32).contiguous().view(-1)
+    bad = torch.zeros(1, device=parent.device, dtype=torch.int32)
+    _lib.check(ops.lib.infgen_branch_scenes(C.byref(blk), int(t), _lib.ptr(p), _lib.ptr(bad), ops.stream), 'infgen_branch_scenes')
+    return bad
+
+
+@branch_scenes.register_fake
+def _(ctx, t, parent):
+    return parent.new_empty(1, dtype=torch.int32)
 
 
 @torch.library.custom_op('infgen_hip::bundle_scores', mutates_args=())
