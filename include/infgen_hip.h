@@ -620,6 +620,49 @@ int infgen_token_mask_road(int handle, uint32_t* road_bits, const int* identity_
                            const float* paths, const float* records, const int* n_records, int rec_cap, int copies, int sweep,
                            float margin, const int* types, int* count);
 
+/* step scores: STEP SCORES, what a branching loop branches on - per scene slot and decode step the overlap, off-road and comfort terms
+ * of the column the step just produced (k_step_score: one launch, no host read, no atomics).
+ * Decode step t produces column c1 = 2 + t.  Row i of scene slot s is LIVE at a column when i < n_agents[s] and state[col][i] is not
+ * invalid (0): "in the scene" of the collision masks, without first_new.  fp32 throughout, no fused multiply-add; world coordinates
+ * enter only through differences formed directly from stored values, pos[j] - pos[i] and (anchor - pos[i]) + offset (the rules of the
+ * collision and road masks above).  Per slot and step 8 floats, step_score[s][t][0..7], 32-byte aligned:
+ *   0 n_live        rows live at c1.
+ *   1 n_overlap     live rows whose box - the pose of c1, half extents shape[i][0] / 2, shape[i][1] / 2 - overlaps at least one other live
+ *                   row's box: the separating-axis value sep < 0 of the collision masks, evaluated in row i's frame.
+ *   2 min_sep       the minimum of sep over all ordered live pairs; +inf with fewer than two live rows.
+ *   3 n_offroad     live rows whose type ty (0 vehicle, 1 pedestrian, 2 cyclist; others count as 0) has types[ty] != 0 and that are
+ *                   OFF-ROAD: the row's box overlaps an obstacle rectangle - half extents (L / 2 + road_margin, road_margin) - of a
+ *                   record of map scene s / copies (records, n_records, rec_cap and the never-used records of radius -1 as for the
+ *                   road masks); with sweep = 1 also when the row is live at c1 - 1, its displacement d = pos[c1][i] - pos[c1 - 1][i]
+ *                   is not zero and its PATH RECTANGLE - centre the midpoint of the two positions, heading that of d, half extents
+ *                   (|d| / 2, the row's half width) - overlaps one.  No straddle exemption: a row sitting on an edge is off-road.
+ *                   Without a record table (records NULL): 0.
+ *   4 max_accel     the maximum of | |p[c1] - p[c1-1]| - |p[c1-1] - p[c1-2]| | / dt^2 over the rows live at all three columns; 0 if none.
+ *   5 max_yaw_rate  the maximum of |wrap(head[c1] - head[c1-1])| / dt over the rows live at both columns; 0 if none.
+ *   6, 7            0, reserved.
+ * and one byte per row, score_row[s][i], of the newest step only (not history, like the collision and road buffers): bit 0 live,
+ * bit 1 overlap, bit 2 off-road.  Counts are exact as floats; every reduction is a count, a min or a max, so the result is bitwise
+ * reproducible whatever the reduction order.
+ * infgen_step_score: one launch for column c1 of scene arrays laid out like InfgenRollout's ([S][T][A_cap]; A_cap need not be a
+ * multiple of 32, at most INFGEN_Q_MAX_AGENTS); slot s writes the 8 floats at out_score + s * out_stride (floats); out_row optional
+ * [S][A_cap].  Columns c1 - 1 and c1 - 2 are read only where they exist (c1 >= 1, c1 >= 2).
+ * Refused: c1 outside 0 .. T - 1, a margin that is negative or not finite, dt <= 0 or not finite, sweep outside {0, 1}, copies < 1 or
+ * not dividing S, a missing output, shape array or type switch, an output that is not 32-byte aligned (or a stride that is no multiple
+ * of 8), a record table that is not 16-byte aligned or comes without its counts.
+ * infgen_token_mask_score: attaches a score configuration to a registered token mask, as infgen_token_mask_road does (a handle
+ * created with mask_bits NULL and mask_n_sets 0 constrains nothing: the heads launches stay the unmasked ones): infgen_decode_step of
+ * a context that names the handle launches k_step_score after infgen_integrate of step t, for column 2 + t, and writes
+ * step_score [S][steps][8] at [s][t] and score_row.  infgen_rollout_run's folded tail is not taken while it is set; with it unset the
+ * launches and their arguments are exactly those without it.  infgen_branch_scenes copies the parent's [steps][8] block onto the
+ * child (score_row is rebuilt by the next step).  The pointers are kept, not the contents.  step_score NULL detaches.  A context with
+ * scenario insertion (first_new != NULL) that names such a handle is refused: scoring such a context is left out, as branching is. */
+int infgen_step_score(const float* pos, const float* head, const int* state, const int* n_agents, const int* type, const float* shape,
+                      int S, int A_cap, int T, int c1, const float* records, const int* n_records, int rec_cap, int copies, int sweep,
+                      float road_margin, const int* types, float dt, float* out_score, long long out_stride, unsigned char* out_row,
+                      void* stream);
+int infgen_token_mask_score(int handle, float* step_score, int steps, unsigned char* score_row, const float* shape, const float* records,
+                            const int* n_records, int rec_cap, int copies, int sweep, float road_margin, const int* types, float dt);
+
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell
  *   infgen_point_edges      _build_a2sa_edge / _build_map2sa_edge for one query point per scene (:760-904):

@@ -7,13 +7,61 @@ A PARENT vector names, for every agent-side scene slot, the slot whose state it 
 global slot indices, source and destination in one copy group (the ``copies`` rollouts of one scene, slots g * copies ..
 g * copies + copies - 1), and every source a fixed point (``parent[parent[s]] == parent[s]``).  ``resample_parents`` turns the
 arbitrary ancestor indices a resampler draws into such a vector on the device (``infgen_resample_parents``); the two resamplers
-here are plain torch on the device.  No function reads the device."""
+here are plain torch on the device.  ``score_log_weight`` turns the engine's step scores ("step scores" of include/infgen_hip.h;
+``RolloutEngine(step_scores=...)``, ``eng.step_score`` [S, steps, 8]) into the per-copy score those resamplers take.  No function
+reads the device."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from . import _lib
+
+
+# columns of a step score (include/infgen_hip.h, "step scores")
+SCORE_N_LIVE, SCORE_N_OVERLAP, SCORE_MIN_SEP, SCORE_N_OFFROAD, SCORE_MAX_ACCEL, SCORE_MAX_YAW_RATE = range(6)
+SCORE_WIDTH = 8
+# score_log_weight's terms: weights (per count, per m/s^2, per rad/s, per metre) and the limits the comfort and gap terms start at
+SCORE_WEIGHTS = dict(w_overlap=1.0, w_offroad=1.0, w_accel=0.0, w_yaw=0.0, w_gap=0.0, accel_limit=4.0, yaw_limit=1.0, gap_limit=0.5)
+
+
+def check_score_weights(weights=None) -> dict:
+    """``weights`` (None or a dict with keys of SCORE_WEIGHTS) -> the full dict of finite floats; ValueError otherwise"""
+    out = dict(SCORE_WEIGHTS)
+    if weights is not None:
+        if not isinstance(weights, dict):
+            raise ValueError('weights is a dict with keys of branching.SCORE_WEIGHTS')
+        for k, v in weights.items():
+            if k not in out:
+                raise ValueError(f'weights: unknown key {k!r} (known: {sorted(out)})')
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+                raise ValueError(f'weights[{k!r}] must be a finite number')
+            out[k] = float(v)
+    return out
+
+
+def score_log_weight(step_score: torch.Tensor, t0: int, t1: int, weights=None, copies: int = None) -> torch.Tensor:
+    """step scores -> the log weight of every copy over the decode steps [t0, t1): ``step_score`` [S0 * n, steps, 8] (``copies`` = n)
+    or [S0, n, steps, 8] -> [S0, n] float32, the negative sum over the steps of
+    ``w_overlap n_overlap + w_offroad n_offroad + w_accel relu(max_accel - accel_limit) + w_yaw relu(max_yaw_rate - yaw_limit)
+    + w_gap relu(gap_limit - min_sep)`` (a ``min_sep`` of +inf - fewer than two live rows - contributes 0).  Plain torch on the
+    tensor's device; higher is better: feed it to ``keep_best`` or ``systematic_ancestors``."""
+    w = check_score_weights(weights)
+    x = step_score
+    if x.dim() == 3 and copies is not None and int(copies) >= 1 and x.shape[0] % int(copies) == 0:
+        x = x.view(-1, int(copies), x.shape[1], x.shape[2])
+    if x.dim() != 4 or x.shape[3] != SCORE_WIDTH:
+        raise ValueError('score_log_weight takes step_score [S0 * copies, steps, 8] with copies=, or [S0, copies, steps, 8]')
+    t0, t1 = int(t0), int(t1)
+    if not 0 <= t0 <= t1 <= x.shape[2]:
+        raise ValueError(f'steps [{t0}, {t1}) are outside the log\'s 0 .. {x.shape[2]}')
+    x = x[:, :, t0:t1].float()
+    relu = torch.relu
+    gap = relu(w['gap_limit'] - torch.clamp(x[..., SCORE_MIN_SEP], max=w['gap_limit']))
+    cost = (w['w_overlap'] * x[..., SCORE_N_OVERLAP] + w['w_offroad'] * x[..., SCORE_N_OFFROAD]
+            + w['w_accel'] * relu(x[..., SCORE_MAX_ACCEL] - w['accel_limit'])
+            + w['w_yaw'] * relu(x[..., SCORE_MAX_YAW_RATE] - w['yaw_limit']) + w['w_gap'] * gap)
+    return -cost.sum(dim=2)
 
 
 def check_parent(parent, S0: int, copies: int) -> np.ndarray:

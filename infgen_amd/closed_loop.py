@@ -133,6 +133,10 @@ class ClosedLoopSession:
             obs['allowed_tokens'] = eng.collision_allowed.view(eng.S, eng.A_cap)
         if eng.stay_on_road is not None:          # road-aware decoding runs last: its sets are the ones the heads read
             obs['allowed_tokens'] = eng.road_allowed.view(eng.S, eng.A_cap)
+        if eng.step_scores is not None:           # step scores: the step that just ran (absent before the first) and its rows' flags
+            if self.t > 0:
+                obs['step_score'] = eng.step_score[:, self.t - 1]
+            obs['score_row'] = eng.score_row
         return obs
 
     def command(self, tokens=None, poses=None, mask=None):

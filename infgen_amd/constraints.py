@@ -189,10 +189,10 @@ def collision_buffers(conf, rows: int, token_size: int, device='cpu'):
 ROAD_DETAILS = (1, 2, 5, 10)              # chords per EDGE map token: the polyline's points 0, 10 / detail, ..., 10
 
 
-def _road_types(types) -> tuple:
+def _road_types(types, what: str = 'stay_on_road') -> tuple:
     """``types`` of stay_on_road -> the three-entry switch (vehicle, pedestrian, cyclist) of 0 / 1"""
     if isinstance(types, (str, bytes)) or not isinstance(types, (Sequence, set, frozenset, np.ndarray)):
-        raise ValueError(f'stay_on_road: types is a collection of agent types, names {TYPE_NAMES} or 0 .. 2 (got {types!r})')
+        raise ValueError(f'{what}: types is a collection of agent types, names {TYPE_NAMES} or 0 .. 2 (got {types!r})')
     on = [0, 0, 0]
     for t in types:
         if isinstance(t, str) and t in TYPE_NAMES:
@@ -200,25 +200,25 @@ def _road_types(types) -> tuple:
         elif not isinstance(t, (bool, str)) and np.isscalar(t) and t in (0, 1, 2):
             on[int(t)] = 1
         else:
-            raise ValueError(f'stay_on_road: unknown agent type {t!r} (names {TYPE_NAMES} or 0 .. 2)')
+            raise ValueError(f'{what}: unknown agent type {t!r} (names {TYPE_NAMES} or 0 .. 2)')
     return tuple(on)
 
 
-def _road_segments(segments):
+def _road_segments(segments, what: str = 'stay_on_road'):
     """``segments`` of stay_on_road -> (float32 [S0][E][4], int32 [S0]): an array [S0][E][4] (every segment used) or one array
     [E_s][4] = (x0, y0, x1, y1) per distinct scene, world coordinates.  Non-finite and zero-length segments are allowed: the
     definition makes them no obstacle"""
     if isinstance(segments, np.ndarray) and segments.ndim == 3:
         segments = list(segments)
     if isinstance(segments, (str, bytes)) or not isinstance(segments, Sequence) or len(segments) == 0:
-        raise ValueError('stay_on_road: segments is an array [S0][E][4] or one array [E][4] per distinct scene')
+        raise ValueError(f'{what}: segments is an array [S0][E][4] or one array [E][4] per distinct scene')
     per = []
     for s, seg in enumerate(segments):
         a = np.asarray(seg)
         if a.size == 0:
             a = np.zeros((0, 4), np.float32)
         if a.ndim != 2 or a.shape[1] != 4 or a.dtype.kind not in 'fiu':
-            raise ValueError(f'stay_on_road: segments[{s}] must be numbers [E][4] = (x0, y0, x1, y1), got shape {a.shape}')
+            raise ValueError(f'{what}: segments[{s}] must be numbers [E][4] = (x0, y0, x1, y1), got shape {a.shape}')
         per.append(a.astype(np.float32))
     E = max(1, max(a.shape[0] for a in per))
     out = np.zeros((len(per), E, 4), np.float32)
@@ -227,10 +227,12 @@ def _road_segments(segments):
     return out, np.array([a.shape[0] for a in per], np.int32)
 
 
-def check_stay_on_road(stay, has_shape: bool = True, n_scenes: Optional[int] = None):
+def check_stay_on_road(stay, has_shape: bool = True, n_scenes: Optional[int] = None, what: str = 'stay_on_road',
+                       margin_key: str = 'margin'):
     """``stay_on_road`` as the engine takes it -> None (off) or dict(margin=float, sweep=0 | 1, detail=1 | 2 | 5 | 10, types=(veh, ped,
     cyc) switches, segments=None | (float32 [S0][E][4], int32 [S0])).  False / None: off; True: the defaults (margin 0 m, the path
     rectangle on, two chords per EDGE map token, vehicles and cyclists, segments from the map); a mapping with any of those keys.
+    ``what`` / ``margin_key``: the argument's name in the messages and the key the margin comes under (``check_step_scores``).
     ``n_scenes``: the number of distinct scenes explicit segments must cover.  Everything is checked here, on the host, before any
     launch."""
     if stay is None or stay is False:
@@ -238,31 +240,31 @@ def check_stay_on_road(stay, has_shape: bool = True, n_scenes: Optional[int] = N
     if stay is True:
         stay = {}
     if not isinstance(stay, Mapping):
-        raise ValueError('stay_on_road takes False, True or dict(margin=, sweep=, detail=, types=, segments=)')
-    unknown = set(stay) - {'margin', 'sweep', 'detail', 'types', 'segments'}
+        raise ValueError(f'{what} takes False, True or dict({margin_key}=, sweep=, detail=, types=, segments=)')
+    unknown = set(stay) - {margin_key, 'sweep', 'detail', 'types', 'segments'}
     if unknown:
-        raise ValueError(f'stay_on_road: unknown keys {sorted(unknown)} (margin, sweep, detail, types, segments)')
-    margin, sweep, detail = stay.get('margin', 0.0), stay.get('sweep', 1), stay.get('detail', 2)
+        raise ValueError(f'{what}: unknown keys {sorted(unknown)} ({margin_key}, sweep, detail, types, segments)')
+    margin, sweep, detail = stay.get(margin_key, 0.0), stay.get('sweep', 1), stay.get('detail', 2)
     if isinstance(margin, (bool, str)) or not np.isscalar(margin) or not np.isfinite(margin) or margin < 0:
-        raise ValueError(f'stay_on_road: margin must be a finite number of metres >= 0 (got {margin!r})')
+        raise ValueError(f'{what}: {margin_key} must be a finite number of metres >= 0 (got {margin!r})')
     if isinstance(sweep, str) or not np.isscalar(sweep) or sweep not in (0, 1, False, True):
-        raise ValueError(f'stay_on_road: sweep must be 0 or 1 (got {sweep!r})')
+        raise ValueError(f'{what}: sweep must be 0 or 1 (got {sweep!r})')
     if isinstance(detail, (bool, str)) or not np.isscalar(detail) or detail not in ROAD_DETAILS:
-        raise ValueError(f'stay_on_road: detail must be one of {ROAD_DETAILS} (got {detail!r})')
-    types = _road_types(stay.get('types', ('veh', 'cyc')))
+        raise ValueError(f'{what}: detail must be one of {ROAD_DETAILS} (got {detail!r})')
+    types = _road_types(stay.get('types', ('veh', 'cyc')), what)
     segments = stay.get('segments')
     if segments is not None:
         if isinstance(segments, tuple) and len(segments) == 2 and np.asarray(segments[1]).ndim == 1 and np.asarray(segments[0]).ndim == 3:
             seg, n = np.ascontiguousarray(segments[0], np.float32), np.asarray(segments[1])      # (a value this function returned)
             if seg.shape[2] != 4 or n.shape[0] != seg.shape[0] or n.dtype.kind not in 'iu' or (n < 0).any() or (n > seg.shape[1]).any():
-                raise ValueError('stay_on_road: segments as (array [S0][E][4], counts [S0]) with 0 <= counts <= E')
+                raise ValueError(f'{what}: segments as (array [S0][E][4], counts [S0]) with 0 <= counts <= E')
             segments = (seg, n.astype(np.int32))
         else:
-            segments = _road_segments(segments)
+            segments = _road_segments(segments, what)
         if n_scenes is not None and segments[0].shape[0] != n_scenes:
-            raise ValueError(f'stay_on_road: segments cover {segments[0].shape[0]} scenes, the batch has {n_scenes} distinct scenes')
+            raise ValueError(f'{what}: segments cover {segments[0].shape[0]} scenes, the batch has {n_scenes} distinct scenes')
     if not has_shape:
-        raise ValueError('stay_on_road needs the rows\' shapes: this engine has no shape array')
+        raise ValueError(f'{what} needs the rows\' shapes: this engine has no shape array')
     return dict(margin=float(margin), sweep=int(sweep), detail=int(detail), types=types, segments=segments)
 
 
@@ -280,3 +282,47 @@ def road_buffers(conf, rows: int, token_size: int, device='cpu'):
     if token_size % 32 or token_size > 4096:
         raise ValueError(f'stay_on_road: token_size {token_size} must be a multiple of 32, at most 4096')
     return collision_buffers(conf, rows, token_size, device)
+
+
+# ---------------------------------------------------------------------------------------- step scores
+def check_step_scores(scores, has_shape: bool = True, n_scenes: Optional[int] = None, stay_on_road=None):
+    """``step_scores`` as the engine takes it -> None (off) or dict(road_margin=float, sweep=0 | 1, types=(veh, ped, cyc) switches,
+    detail=1 | 2 | 5 | 10, segments=None | (float32 [S0][E][4], int32 [S0]), dt=float).  False / None: off; True: the defaults
+    (margin 0 m, the path rectangle on, vehicles and cyclists, two chords per EDGE map token, segments from the map, 0.5 s per
+    step); a mapping with any of those keys.  ``stay_on_road``: the engine's CHECKED road configuration (``check_stay_on_road``) or
+    None - the engine keeps one road table, so with road-aware decoding on the scores read that table: ``detail`` / ``segments``
+    left out are taken from it, and ones that differ from it raise.  Everything is checked here, on the host, before any launch."""
+    if scores is None or scores is False:
+        return None
+    if scores is True:
+        scores = {}
+    if not isinstance(scores, Mapping):
+        raise ValueError('step_scores takes False, True or dict(road_margin=, sweep=, types=, detail=, segments=, dt=)')
+    unknown = set(scores) - {'road_margin', 'sweep', 'types', 'detail', 'segments', 'dt'}
+    if unknown:
+        raise ValueError(f'step_scores: unknown keys {sorted(unknown)} (road_margin, sweep, types, detail, segments, dt)')
+    dt = scores.get('dt', STEP_SECONDS)
+    if isinstance(dt, (bool, str)) or not np.isscalar(dt) or not np.isfinite(dt) or dt <= 0:
+        raise ValueError(f'step_scores: dt must be a finite number of seconds > 0 (got {dt!r})')
+    road = dict(road_margin=scores.get('road_margin', 0.0), sweep=scores.get('sweep', 1), types=scores.get('types', ('veh', 'cyc')))
+    for k in ('detail', 'segments'):
+        if scores.get(k) is not None:
+            road[k] = scores[k]
+        elif stay_on_road is not None:
+            road[k] = stay_on_road[k]
+    road = check_stay_on_road(road, has_shape=has_shape, n_scenes=n_scenes, what='step_scores', margin_key='road_margin')
+    if stay_on_road is not None:
+        if road['detail'] != stay_on_road['detail']:
+            raise ValueError(f'step_scores: detail {road["detail"]} conflicts with stay_on_road\'s {stay_on_road["detail"]}: the engine '
+                             'keeps one road table')
+        a, b = road['segments'], stay_on_road['segments']
+        if (a is None) != (b is None) or (a is not None and not (np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]))):
+            raise ValueError('step_scores: segments conflict with stay_on_road\'s: the engine keeps one road table')
+    return dict(road_margin=road['margin'], sweep=road['sweep'], types=road['types'], detail=road['detail'], segments=road['segments'],
+                dt=float(dt))
+
+
+def score_key(conf):
+    """the hashable part of a checked step_scores configuration that decides the launches' arguments"""
+    return None if conf is None else (conf['road_margin'], conf['sweep'], conf['types'], conf['detail'], conf['segments'] is not None,
+                                      conf['dt'])

@@ -58,7 +58,13 @@ struct RoadCfg {
   const int* n_records; int rec_cap, copies, sweep; float margin; int types[3]; int* count;
 };
 constexpr RoadCfg ROAD_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, nullptr};
-struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; };
+// the score configuration a registered mask may carry (infgen_token_mask_score; out == NULL: none)
+struct ScoreCfg {
+  float* out; int steps; unsigned char* row; const float* shape; const float* records; const int* n_records;
+  int rec_cap, copies, sweep; float margin; int types[3]; float dt;
+};
+constexpr ScoreCfg SCORE_NONE{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, 0.5f};
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
 
@@ -85,7 +91,7 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   size_t h = 0;
   while (h < g_masks.size() && g_masks[h].in_use) ++h;
   if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
-  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE};
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE, SCORE_NONE};
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
@@ -1517,6 +1523,67 @@ extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int
   return 0;
 }
 
+// ---------------------------------------------------------------------------------- step scores
+// the argument checks of include/infgen_hip.h ("step scores") - score_check: what a configuration is checked for once, by the
+// stand-alone entry and when it is attached to a handle; launch_score: the geometry - and the one launch of k_step_score
+static int score_check(const char* where, int sweep, float margin, int copies, int rec_cap, const float* shape, const float* records,
+                       const int* n_records, const int* types, float dt, const float* out) {
+  if (!std::isfinite(margin) || margin < 0.f) return fail(where, "step score: road_margin must be finite and >= 0");
+  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(where, "step score: dt must be finite and > 0");
+  if (sweep != 0 && sweep != 1) return fail(where, "step score: sweep must be 0 or 1");
+  if (copies < 1) return fail(where, "step score: copies must be at least 1");
+  if (rec_cap < 0) return fail(where, "step score: negative record capacity");
+  if (!shape) return fail(where, "step score: needs the rows' shape array [S][A_cap][3]");
+  if (!types) return fail(where, "step score: needs the three-entry type switch");
+  if (!out) return fail(where, "step score: needs the output [S][..][8]");
+  if (reinterpret_cast<uintptr_t>(out) & 31) return fail(where, "step score: the output must be 32-byte aligned");
+  if (records && !n_records) return fail(where, "step score: a record table needs its counts");
+  if (misaligned16(records)) return fail(where, "step score: the record table must be 16-byte aligned");
+  return 0;
+}
+static int launch_score(const char* where, const ScoreArgs& a, void* stream) {
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "step score: S, A_cap and T must be positive");
+  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "step score: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.S % a.copies) return fail(where, "step score: S must be a multiple of copies");
+  if (a.c1 < 0 || a.c1 >= a.T) return fail(where, "step score: column outside [0, T)");
+  if (a.out_stride < 8 || a.out_stride % 8) return fail(where, "step score: the output stride must be a positive multiple of 8 floats");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "step score: null scene array");
+  hipLaunchKernelGGL(k_step_score, dim3((unsigned)a.S), dim3(SC_NT), 0, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+
+extern "C" int infgen_step_score(const float* pos, const float* head, const int* state, const int* n_agents, const int* type,
+                                 const float* shape, int S, int A_cap, int T, int c1, const float* records, const int* n_records,
+                                 int rec_cap, int copies, int sweep, float road_margin, const int* types, float dt, float* out_score,
+                                 long long out_stride, unsigned char* out_row, void* stream) {
+  const char* me = "infgen_step_score";
+  RET_IF(score_check(me, sweep, road_margin, copies, rec_cap, shape, records, n_records, types, dt, out_score));
+  ScoreArgs a{};
+  a.S = S; a.A_cap = A_cap; a.T = T; a.c1 = c1;
+  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.type = type; a.shape = shape;
+  a.records = records; a.n_records = n_records; a.rec_cap = rec_cap; a.copies = copies; a.sweep = sweep; a.margin = road_margin;
+  for (int k = 0; k < 3; ++k) a.types[k] = types[k];
+  a.dt = dt; a.out = out_score; a.out_stride = out_stride; a.out_row = out_row;
+  return launch_score(me, a, stream);
+}
+
+extern "C" int infgen_token_mask_score(int handle, float* step_score, int steps, unsigned char* score_row, const float* shape,
+                                       const float* records, const int* n_records, int rec_cap, int copies, int sweep, float road_margin,
+                                       const int* types, float dt) {
+  const char* me = "infgen_token_mask_score";
+  ScoreCfg cfg = SCORE_NONE;
+  if (step_score) {
+    RET_IF(score_check(me, sweep, road_margin, copies, rec_cap, shape, records, n_records, types, dt, step_score));
+    if (steps < 1) return fail(me, "step score: steps must be positive");
+    cfg = ScoreCfg{step_score, steps, score_row, shape, records, n_records, rec_cap, copies, sweep, road_margin,
+                   {types[0], types[1], types[2]}, dt};
+  }
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(me, "no such token mask");
+  g_masks[handle - 1].score = cfg;
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------- rollout context
 static SceneState scene_of(const InfgenRollout* r) {
   SceneState st;
@@ -1533,7 +1600,7 @@ static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
 static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, TokenMaskCtl* mask = nullptr,
-                    CollisionCfg* coll = nullptr, RoadCfg* road = nullptr) {
+                    CollisionCfg* coll = nullptr, RoadCfg* road = nullptr, ScoreCfg* score = nullptr) {
   if (!r) return fail(where, "null context");
   if (r->A_cap > 1024 || r->A_cap <= 0) return fail(where, "A_cap must be in 1..1024");
   if (r->A_cap % 32) return fail(where, "A_cap must be a multiple of 32");
@@ -1557,6 +1624,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   RoadCfg own_road;
   if (!road) road = &own_road;
   *road = ROAD_NONE;
+  ScoreCfg own_score;
+  if (!score) score = &own_score;
+  *score = SCORE_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
     TokenMaskDesc tm;
     {
@@ -1566,6 +1636,7 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
       tm = g_masks[r->token_mask - 1].d;
       *coll = g_masks[r->token_mask - 1].coll;
       *road = g_masks[r->token_mask - 1].road;
+      *score = g_masks[r->token_mask - 1].score;
     }
     if (!tm.type) tm.type = r->type;
     RET_IF(token_mask_ctl(where, &tm, r->token_size, mask));
@@ -1574,6 +1645,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
     if (road->bits && (r->token_size % 32 || r->token_size > 64 * 32 * RM_WPL))
       return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
     if (road->bits && r->S % road->copies) return fail(where, "road mask: S must be a multiple of copies");
+    if (score->out && r->first_new)
+      return fail(where, "step score: contexts with scenario insertion cannot be scored: rows appended inside a step are left out");
+    if (score->out && r->S % score->copies) return fail(where, "step score: S must be a multiple of copies");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
@@ -1691,7 +1765,7 @@ extern "C" int infgen_command_rows(const InfgenRollout* r, int t, int kind, cons
 // ---- branching rollouts: slot s becomes a clone of slot parent[s] as of the boundary in front of decode step t (k_branch_scenes)
 // the segment table: everything a decode step reads that an earlier step (or the prologue) wrote per scene.  What configures a slot
 // (uniforms, temperatures, masks, plans, replay flags) and what every step rebuilds before reading it (edge sets, scratch) is not in it.
-static int branch_segments(const InfgenRollout* r, int t, BranchArgs* a) {
+static int branch_segments(const InfgenRollout* r, int t, BranchArgs* a, float* score_log, long long score_bytes) {
   const long long A = r->A_cap, rows = (long long)r->S * A;
   int n = 0, chunk = 0;
   auto add = [&](void* base, long long bytes, int outer, long long outer_stride) {
@@ -1717,13 +1791,15 @@ static int branch_segments(const InfgenRollout* r, int t, BranchArgs* a) {
   add(r->token_logprob, A * 4, t, rows * 4);
   add(r->sample_logprob, A * 4, t, rows * 4);
   add(r->store_logits ? r->logits : nullptr, A * r->token_size * 4, t, rows * r->token_size * 4);
+  add(score_log, score_bytes, 1, 0);                                  // the scene's whole [steps][8] block
   a->n_seg = n;
   return chunk;
 }
 
 extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* parent, int* n_bad, void* stream) {
   const char* me = "infgen_branch_scenes";
-  RET_IF(validate(r, me));
+  ScoreCfg score;
+  RET_IF(validate(r, me, nullptr, nullptr, nullptr, nullptr, &score));
   if (r->S <= 0 || r->S > 65535) return fail(me, "S must be in 1..65535");
   if (r->T <= 0 || r->R <= 0 || r->ring <= 0 || r->token_size <= 0) return fail(me, "bad sizes");
   if (!parent) return fail(me, "null parent");
@@ -1731,10 +1807,10 @@ extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* pa
   if (t < 0 || 1 + t > r->T - 1) return fail(me, "t must be in 0..steps (the boundary in front of decode step t)");
   if (!(r->pos && r->head && r->state && r->token && r->grid && r->tmask && r->imask && r->catflag && r->bos && r->X))
     return fail(me, "null scene array");
-  static_assert(BR_MAX_SEGS >= 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 3, "segment table too short");
+  static_assert(BR_MAX_SEGS >= 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 4, "segment table too short");
   BranchArgs a{};
   a.S = r->S; a.parent = parent; a.map_scene = r->map_scene; a.n_bad = n_bad;
-  const int chunks = branch_segments(r, t, &a);
+  const int chunks = branch_segments(r, t, &a, score.out, (long long)score.steps * 8 * 4);
   if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
   hipLaunchKernelGGL(k_branch_scenes, dim3(chunks, r->S), dim3(BR_NT), 0, (hipStream_t)stream, a);
   return check_launch(me);
@@ -2223,7 +2299,8 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   TokenMaskCtl mask;
   CollisionCfg coll;
   RoadCfg road;
-  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask, &coll, &road));
+  ScoreCfg score;
+  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask, &coll, &road, &score));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
@@ -2272,6 +2349,17 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
     RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream, ctl, nullptr, mask));
   if (lp && !lp_fused) RET_IF(infgen_token_logprob(lg, rows, r->token_size, r->next_token, lp, stream));
   RET_IF(infgen_integrate(r, t, stream));
+  if (score.out) {      // step scores: the column this step produced, reduced per scene slot
+    if (t >= score.steps) return fail("infgen_decode_step", "step score: the log holds fewer steps");
+    ScoreArgs sa{};
+    sa.S = r->S; sa.A_cap = r->A_cap; sa.T = r->T; sa.c1 = c + 1;
+    sa.pos = r->pos; sa.head = r->head; sa.state = r->state; sa.n_agents = r->n_agents; sa.type = r->type; sa.shape = score.shape;
+    sa.records = score.records; sa.n_records = score.n_records; sa.rec_cap = score.rec_cap; sa.copies = score.copies;
+    sa.sweep = score.sweep; sa.margin = score.margin; sa.dt = score.dt;
+    for (int k = 0; k < 3; ++k) sa.types[k] = score.types[k];
+    sa.out = score.out + (size_t)t * 8; sa.out_stride = (long long)score.steps * 8; sa.out_row = score.row;
+    RET_IF(launch_score("infgen_decode_step", sa, stream));
+  }
   RET_IF(infgen_raw_feature(r, c + 1, stream));
   return 0;
 }
@@ -2286,12 +2374,13 @@ extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* 
   TokenMaskCtl mask;
   CollisionCfg coll;
   RoadCfg road;
-  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask, &coll, &road));
+  ScoreCfg score;
+  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask, &coll, &road, &score));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !coll.bits && !road.bits && !r->token_logprob && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !coll.bits && !road.bits && !score.out && !r->token_logprob && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));

@@ -655,7 +655,7 @@ __global__ void k_road_paths(RoadPathArgs a);
 // branch_kernels.hip: branching rollouts (include/infgen_hip.h, "branching").  k_branch_scenes gathers, for every scene s with a
 // valid parent[s] != s, slot parent[s]'s rollout state into slot s - one launch over (chunk of a segment, scene).  A SEGMENT is one
 // buffer of the context as `outer` blocks per scene: block o of scene s is the `bytes` bytes at base + o * outer_stride + s * bytes.
-constexpr int BR_MAX_SEGS = 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 3;     // scene arrays, rings, X, pred_*, the three step-major logs
+constexpr int BR_MAX_SEGS = 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 4;     // scene arrays, rings, X, pred_*, the three step-major logs, the score log
 constexpr int BR_NT = 256;              // threads per workgroup
 constexpr int BR_VEC = 4;               // 16-byte words a lane moves: all loads are issued before the first store
 constexpr int BR_CHUNK = BR_NT * BR_VEC * 16;      // bytes of a block one workgroup moves
@@ -676,6 +676,20 @@ struct ResampleArgs { const int* ancestor; int copies; int* parent; };      // [
 constexpr int RS_NT = 256, RS_ITEMS = 4;       // copies <= RS_NT * RS_ITEMS
 __global__ void k_branch_scenes(BranchArgs a);
 __global__ void k_resample_parents(ResampleArgs a);
+
+// score_kernels.hip: the step scores of one stored column (include/infgen_hip.h, "step scores"): 8 floats per scene slot, one flag byte
+// per row
+constexpr int SC_NT = 256;              // threads of the one workgroup per scene slot
+struct ScoreArgs {
+  int S, A_cap, T, c1;                  // column c1 of the [S][T][A_cap] scene arrays is the scored one
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+  const float* records; const int* n_records; int rec_cap;    // [S / copies][rec_cap][RM_REC], [S / copies]; records NULL: no table
+  int copies, sweep; float margin; int types[3]; float dt;
+  float* out; long long out_stride;     // slot s: the 8 floats at out + s * out_stride (32-byte aligned)
+  unsigned char* out_row;               // optional [S][A_cap]: bit 0 live, bit 1 overlap, bit 2 off-road
+};
+__global__ void k_step_score(ScoreArgs a);
 
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]

@@ -555,7 +555,8 @@ class RolloutEngine:
                  tap_layers: bool = False, batch=None, batch_layout: Optional[Dict] = None, replay=None,
                  token_logprob: bool = False, sample_logprob: bool = False,
                  sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
-                 token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False, stay_on_road=False):
+                 token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False, stay_on_road=False,
+                 step_scores=False):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -585,6 +586,15 @@ class RolloutEngine:
         ``next_token_logprob`` stays the model's own full softmax at temperature 1.  ``insert_temperature`` / ``insert_top_p``: the
         same for the cell draw of scenario insertion (scalars; ``insert_k > 1``; a temperature of 0 is refused: the arg-max cell is
         ``insert_k = 1``).  ``reload*(sample_top_p=...)`` changes the nucleus mass of an engine that exists.  The defaults are the plain samplers bit for bit.
+        ``step_scores``: step scores ("step scores" of include/infgen_hip.h) - False, True or ``dict(road_margin=,
+        sweep=, types=, detail=, segments=, dt=)``.  Every decode step then also reduces the column it produced per scene slot:
+        ``step_score`` [S, steps, 8] = n_live, n_overlap, min_sep, n_offroad, max_accel, max_yaw_rate, 0, 0 of step t at [:, t], and
+        ``score_row`` [S, A_cap] uint8 (bit 0 live, 1 overlap, 2 off-road) of the newest step - static device buffers, what
+        ``branching.score_log_weight`` and ``rollout_guided`` read.  The record table is the engine's one road table: shared with
+        ``stay_on_road`` when that is on (a different ``detail`` / ``segments`` raises ValueError), otherwise built the same way.
+        Tokens, poses and logits are those of the engine without it.  ``reload*(step_scores=...)`` turns it on or off (None:
+        keep).  Engines with scenario insertion refuse it.
+
         ``token_masks`` / ``token_mask_type`` / ``token_mask_row``: constrained decoding (infgen_amd/constraints.py).
         ``token_masks`` is a ``TokenMasks`` table of allowed-token sets; a generated row takes the set ``token_mask_row`` names
         ([S][rows] host integers, range-checked here, or an int32 device tensor [S][A_cap] taken as it is; -1 = no choice of its own)
@@ -797,8 +807,12 @@ class RolloutEngine:
         self.avoid_collisions = None                      # dict(margin, predict) while collision-aware decoding is on
         self.collision_bits = self.collision_allowed = None
         self._coll = self._coll_end = self._coll_reg = None
+        self.step_scores = None                           # the checked configuration while step scores are on
+        self.step_score = self.score_row = None           # [S, steps, 8] floats, [S, A_cap] flag bytes
+        self._score_arg = self._score_shape = self._score_reg = None
         self._load_collisions(avoid_collisions)
         self._load_road(stay_on_road)
+        self._load_scores(step_scores)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -1045,7 +1059,44 @@ class RolloutEngine:
             if conf['segments'] is not None:
                 self._road_seg = tuple(torch.from_numpy(a).to(self.device) for a in conf['segments'])
             self._road_room(64)
+        if self.step_scores is not None:               # the scores read the engine's one road table: checked against the new one
+            self._load_scores(self._score_arg)
         self._apply_token_masks()
+
+    def _load_scores(self, scores):
+        """``step_scores`` into the engine (None: keep what is there), like ``_load_road``, whose record table the scores share"""
+        if scores is None:
+            return
+        conf = constraints.check_step_scores(scores, has_shape=getattr(self, '_shape10', None) is not None, n_scenes=self.S0,
+                                             stay_on_road=self.stay_on_road)
+        if conf is None and self.step_scores is None:
+            return
+        if conf is not None and self.insertion:
+            raise ValueError('step_scores: engines with scenario insertion are left out (rows appended inside a step), as branching is')
+        if conf is not None and self.step_score is None:
+            self.step_score = torch.zeros(self.S, self.cfg.num_decode_steps, 8, device=self.device)
+            self.score_row = torch.zeros(self.S, self.A_cap, device=self.device, dtype=torch.uint8)
+            if self._road is None:                     # (with road buffers in the engine the scores read their shape array)
+                self._score_shape = self._shape10.reshape(-1, 3).clone()
+        if self.road_n_records is None and conf is not None:
+            self.road_n_records = torch.zeros(self.S0, device=self.device, dtype=torch.int32)
+        if constraints.score_key(conf) != constraints.score_key(self.step_scores):
+            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
+        self.step_scores, self._score_arg = conf, (scores if conf is not None else None)
+        if conf is not None and self.stay_on_road is None:      # the scores alone drive the road table
+            self._road_dirty = True
+            self._road_seg = None
+            if conf['segments'] is not None:
+                self._road_seg = tuple(torch.from_numpy(a).to(self.device) for a in conf['segments'])
+            self._road_room(64)
+        self._apply_token_masks()
+
+    def _score_boxes(self) -> torch.Tensor:
+        """the [rows, 3] shape array the score kernel reads: the road buffers' where the engine has them, else the scores' own"""
+        if self._road is not None:
+            self._score_shape = None
+            return self._road['shape']
+        return self._score_shape
 
     def _road_room(self, need: int):
         """a record table of at least ``need`` records per distinct scene: grown (a new buffer, so captured graphs go and the
@@ -1058,7 +1109,7 @@ class RolloutEngine:
     def _road_build(self):
         """the record table from the map in the buffers (or the explicit segments), once per reload: one count of EDGE tokens per
         scene sizes it (the only host synchronisation), k_road_records_map / _seg fills it"""
-        conf, P = self.stay_on_road, _lib.ptr
+        conf, P = (self.stay_on_road if self.stay_on_road is not None else self.step_scores), _lib.ptr
         if self._road_seg is not None:
             seg, nseg = self._road_seg
             self._road_room(int(seg.shape[1]))
@@ -1083,7 +1134,7 @@ class RolloutEngine:
         three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  A
         collision configuration rides on the handle (one without a table when the engine has no ``token_masks``)"""
         if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and self.stay_on_road is None
-                                 and not self._mask_handle):
+                                 and self.step_scores is None and not self._mask_handle):
             return
         if self.token_masks is not None:
             reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
@@ -1122,6 +1173,19 @@ class RolloutEngine:
                                                            road['margin'], (C.c_int * 3)(*road['types']), P(k['allowed'])),
                            'infgen_token_mask_road')
             self._road_reg = rreg
+        sc = self.step_scores
+        sreg = None if sc is None else (self._mask_handle, constraints.score_key(sc), self.road_records.data_ptr(), self._road_cap,
+                                        self._score_boxes().data_ptr())
+        if sreg != self._score_reg:     # and so do the step scores: the handle constrains nothing by itself
+            if sc is None:
+                _lib.check(self.lib.infgen_token_mask_score(self._mask_handle, None, 0, None, None, None, None, 0, 1, 1, 0.0, None, 0.5),
+                           'infgen_token_mask_score')
+            else:
+                _lib.check(self.lib.infgen_token_mask_score(self._mask_handle, P(self.step_score), int(self.step_score.shape[1]), P(self.score_row),
+                                                            P(self._score_boxes()), P(self.road_records), P(self.road_n_records),
+                                                            self._road_cap, self.copies, sc['sweep'], sc['road_margin'],
+                                                            (C.c_int * 3)(*sc['types']), sc['dt']), 'infgen_token_mask_score')
+            self._score_reg = sreg
         self._ctx.token_mask = self._mask_handle
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
@@ -1129,7 +1193,7 @@ class RolloutEngine:
     def _drop_mask_handle(self):
         if getattr(self, '_mask_handle', 0):
             self.lib.infgen_token_mask_destroy(self._mask_handle)
-            self._mask_handle, self._mask_reg, self._coll_reg, self._road_reg = 0, None, None, None
+            self._mask_handle, self._mask_reg, self._coll_reg, self._road_reg, self._score_reg = 0, None, None, None, None
             if getattr(self, '_ctx', None) is not None:
                 self._ctx.token_mask = 0
 
@@ -1146,10 +1210,15 @@ class RolloutEngine:
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
     def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
-                       avoid_collisions=None, stay_on_road=None):
+                       avoid_collisions=None, stay_on_road=None, step_scores=None):
         self._load_token_masks(*(token_masks or (None, None, None)))
         self._load_collisions(avoid_collisions)
+        if step_scores is not None:     # (both arguments are resolved before they are checked against each other)
+            self._score_arg = step_scores if step_scores is not False else None
+            if step_scores is False:
+                self._load_scores(False)
         self._load_road(stay_on_road)
+        self._load_scores(step_scores)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
@@ -1221,7 +1290,7 @@ class RolloutEngine:
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-               avoid_collisions=None, stay_on_road=None):
+               avoid_collisions=None, stay_on_road=None, step_scores=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -1236,7 +1305,7 @@ class RolloutEngine:
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1253,7 +1322,7 @@ class RolloutEngine:
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                       sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None,
-                      token_mask_row=None, avoid_collisions=None, stay_on_road=None) -> bool:
+                      token_mask_row=None, avoid_collisions=None, stay_on_road=None, step_scores=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -1268,7 +1337,7 @@ class RolloutEngine:
             return False
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1330,7 +1399,7 @@ class RolloutEngine:
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
                      sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-                     avoid_collisions=None, stay_on_road=None):
+                     avoid_collisions=None, stay_on_road=None, step_scores=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1340,7 +1409,7 @@ class RolloutEngine:
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -1503,6 +1572,11 @@ class RolloutEngine:
             self._coll['shape'].copy_(self._shape10.reshape(rows, 3))
         if self.stay_on_road is not None:            # road-aware decoding: the rows' boxes, and the record table of a new map
             self._road['shape'].copy_(self._shape10.reshape(rows, 3))
+            if self._road_dirty:
+                self._road_build()
+        if self.step_scores is not None:             # step scores: the rows' boxes, and the record table where the scores alone drive it
+            if self.stay_on_road is None:            # (otherwise the one shape array was refreshed just above)
+                self._score_boxes().copy_(self._shape10.reshape(rows, 3))
             if self._road_dirty:
                 self._road_build()
         # categorical embedding rows (agent_decoder.py:376-380,492)
@@ -2050,6 +2124,48 @@ class RolloutEngine:
         _lib.check(self.lib.infgen_branch_scenes(C.byref(self._ctx), int(t), _lib.ptr(p), _lib.ptr(self.branch_bad), self.ops.stream),
                    'infgen_branch_scenes')
         self._rollout_lp = self._rollout_slp = None
+
+    def rollout_guided(self, every: int = 4, keep: Optional[int] = None, weights=None, u=None):
+        """a guided rollout: ``prologue``, then for every block of ``every`` decode steps ``run(t0, t1)``,
+        ``branching.score_log_weight`` over the block's step scores, ``branching.keep_best(.., keep)`` - or, with ``keep=None``,
+        ``resample_parents(systematic_ancestors(.., u[b]))`` - and ``branch(parent, t1)``: the copies of every scene are pruned or
+        resampled on overlaps, road departures and comfort while they run.  Everything is enqueued on the current stream; nothing
+        is read on the host.  ``weights``: a dict with keys of ``branching.SCORE_WEIGHTS``; ``u``: the systematic resampler's
+        uniforms [n_blocks, S0] in [0, 1) (an array or a tensor; needed when ``keep`` is None).  ``ancestry`` [n_blocks, S] int32
+        holds the parent vector of every block, on the device.  Needs ``copies > 1``, ``step_scores`` and no scenario insertion."""
+        from . import branching
+        if self.copies <= 1:
+            raise ValueError('rollout_guided: needs copies > 1 - there is nothing to prune or resample among one copy')
+        if self.step_scores is None:
+            raise ValueError('rollout_guided: needs step_scores (the engine logs no score to guide on)')
+        if self.insertion:
+            raise ValueError('rollout_guided: engines with scenario insertion cannot branch: left out')
+        steps, every = self.cfg.num_decode_steps, int(every)
+        if every < 1:
+            raise ValueError('rollout_guided: every must be at least 1')
+        weights = branching.check_score_weights(weights)
+        if keep is not None and not 1 <= int(keep) <= self.copies:
+            raise ValueError(f'rollout_guided: keep must be in 1 .. {self.copies}')
+        blocks = [(t0, min(t0 + every, steps)) for t0 in range(0, steps, every)]
+        if keep is None:
+            if u is None:
+                raise ValueError(f'rollout_guided: the systematic resampler (keep=None) needs uniforms u [{len(blocks)}, {self.S0}]')
+            u = torch.as_tensor(u).to(self.device, torch.float32)
+            if tuple(u.shape) != (len(blocks), self.S0):
+                raise ValueError(f'rollout_guided: u must be [{len(blocks)}, {self.S0}], got {tuple(u.shape)}')
+        self._bc_host = None
+        self._end_session()
+        self.prologue()
+        self.ancestry = torch.empty(len(blocks), self.S, device=self.device, dtype=torch.int32)
+        for b, (t0, t1) in enumerate(blocks):
+            self.run(t0, t1)
+            lw = branching.score_log_weight(self.step_score, t0, t1, weights, copies=self.copies)
+            if keep is not None:
+                parent = branching.keep_best(lw, int(keep))
+            else:
+                parent = branching.resample_parents(branching.systematic_ancestors(lw, u[b]), self.copies)
+            self.ancestry[b].copy_(parent.reshape(-1))
+            self.branch(self.ancestry[b], t1)
 
     def ctx_tensor(self) -> torch.Tensor:
         """the bytes of this engine's InfgenRollout block (after ``prologue``) - the state handle of

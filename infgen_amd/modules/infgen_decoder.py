@@ -17,7 +17,8 @@ import torch.nn as nn
 
 from .. import _lib, logprob, scene_setup
 from ..closed_loop import ClosedLoopSession
-from ..constraints import TokenMasks, check_avoid_collisions, check_stay_on_road, check_type_selectors, road_key
+from ..constraints import (TokenMasks, check_avoid_collisions, check_stay_on_road, check_step_scores, check_type_selectors, road_key,
+                           score_key)
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -297,14 +298,18 @@ def _cached_engine(engines: Dict, key, attempts, make_engine):
     return eng
 
 
-def _rollout_or_yield(engines: Dict, key, eng, make_engine, amax: int, limit: int, session: bool = False):
+def _rollout_or_yield(engines: Dict, key, eng, make_engine, amax: int, limit: int, session: bool = False, guided=None):
     """generator -> the engine after its rollout.  The reference's agent arrays grow without bound; here rows are pre-allocated
     per scene: if the inserted agents outgrow them the (deterministic) rollout is repeated with twice the rows (at most ``limit``,
     ``amax`` of them the scenes' own) instead of dropping insertions.  ``session``: yields the engine where ``rollout()`` would
-    run - the caller steps a closed-loop session on it and resumes the generator for the epilogue - and otherwise never yields."""
+    run - the caller steps a closed-loop session on it and resumes the generator for the epilogue - and otherwise never yields.
+    ``guided``: the arguments of ``RolloutEngine.rollout_guided``, which then runs in place of ``rollout``."""
     while not session:
         try:
-            eng.rollout()
+            if guided is not None:
+                eng.rollout_guided(**guided)
+            else:
+                eng.rollout()
             return eng
         except InsertionHeadroomError:
             if eng.A_cap >= limit:
@@ -396,6 +401,12 @@ class InfGenDecoder(nn.Module):
         # segments=).  Taken by the same entries; its settings are part of the engine cache key, explicit segments are contents that
         # every call loads again with its scenes
         self.stay_on_road = False
+        # step scores (RolloutEngine's step_scores): False, True or dict(road_margin=, sweep=, types=, detail=,
+        # segments=, dt=) - every rollout dict then carries ``step_score`` [steps, 8]; keyed and loaded like stay_on_road.
+        # guided_rollouts: None or a dict of RolloutEngine.rollout_guided's arguments (every=, keep=, weights=, u=): the copies of
+        # inference_rollouts / inference_batch(copies=n) are pruned or resampled on those scores while they run
+        self.step_scores = False
+        self.guided_rollouts = None
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -516,7 +527,26 @@ class InfGenDecoder(nn.Module):
                 fixed.update(stay_on_road=sr)
             else:      # (world coordinates of this call's scenes: loaded with them, like the uniforms)
                 live.update(stay_on_road=sr)
+        ss = check_step_scores(getattr(self, 'step_scores', False), stay_on_road=sr)
+        if getattr(self, 'guided_rollouts', None) is not None and ss is None:
+            raise ValueError('guided_rollouts needs step_scores')
+        if ss is not None:
+            key += (('step_scores',) + score_key(ss),)
+            # (the engine takes the caller's own form: its check resolves it against its road table; explicit segments are
+            # contents of this call's scenes, loaded with them)
+            (fixed if ss['segments'] is None else live).update(step_scores=self.step_scores)
         return dict(fixed, **live), live, key
+
+    def _guided(self, copies: int):
+        """``guided_rollouts`` as ``_rollout_or_yield`` takes it: None, or the driver's arguments (a dict)"""
+        g = getattr(self, 'guided_rollouts', None)
+        if g is None:
+            return None
+        if not isinstance(g, dict) or set(g) - {'every', 'keep', 'weights', 'u'}:
+            raise ValueError('guided_rollouts: None or dict(every=, keep=, weights=, u=)')
+        if int(copies) <= 1:
+            raise ValueError('guided_rollouts needs copies > 1 (inference_rollouts, or inference_batch(copies=n))')
+        return dict(g)
 
     @staticmethod
     def _drive(gen):
@@ -586,6 +616,8 @@ class InfGenDecoder(nn.Module):
                 o['rollout_logprob'] = lp[sel]
             if slp is not None:
                 o['rollout_sample_logprob'] = slp[sel]
+            if eng.step_scores is not None:         # [steps, 8] of the rollout (a copy's dict over B graphs: [B, steps, 8])
+                o['step_score'] = eng.step_score[sel].clone()
             o['log_message'] = '\n'.join('No agents inserted!' if x == 0 else f'Number of total inserted agents: {x}' for x in inserted)
 
     def _run_gen(self, data, x_pt=None, map_only=False, batch: Optional[Sequence] = None, sample_uniforms=None,
@@ -634,7 +666,8 @@ class InfGenDecoder(nn.Module):
             eng.prologue(map_only=True)
             return eng.x_pt[:eng.hosts[0]['M']].clone(), self._map_keys(eng, datas)[0]
         # (the scenes' own rows: their kept counts, which this path knows on the host and sizes the engine's rows from)
-        eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, max(h['A'] for h in eng.hosts), limit, session)
+        eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, max(h['A'] for h in eng.hosts), limit, session,
+                                           self._guided(copies))
         # the map-token head once per distinct scene (not with a caller's map encoding: inference_no_map passes its map_enc through)
         mk = self._map_keys(eng, datas) if xo is None else None
         # per-scene dicts of device tensors (no host round trip of the results), detached from the engine's buffers
@@ -805,7 +838,7 @@ class InfGenDecoder(nn.Module):
             data, sample_uniforms=su, insert_uniforms=iu, layout=lay, replay=rp, **live))], make_engine)
         # (the scenes' own rows: the kept counts stay on the device until the rollout is over - the engine's rows are sized from
         # the layout's unfiltered maximum, which the offsets give on the host, and so is the retry's head-room)
-        eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, lay['amax'], limit, session)
+        eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, lay['amax'], limit, session, self._guided(copies))
         outs = eng.outputs_batch()
         n_fin, c = eng.batch_counts()
         dev = w.device

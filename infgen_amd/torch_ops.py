@@ -20,6 +20,8 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.road_mask(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_records, copies=1,
                                    sweep=1, margin=0, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
                                                                                             -> sets (S A, token_size / 32) int32, allowed (S A,)
+    torch.ops.infgen_hip.step_score(pos, head, state, n_agents, type, shape, c1, records?, n_records?, copies=1, sweep=1,
+                                    road_margin=0, types=[1, 0, 1], dt=0.5)                 -> score (S, 8), flags (S, A) uint8
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -475,6 +477,52 @@ def _(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_re
       mask_bits=None, mask_row=None, mask_type=None, first_new=None):
     rows = pos.shape[0] * pos.shape[2]
     return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32))
+
+
+@torch.library.custom_op('infgen_hip::step_score', mutates_args=())
+def step_score(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+               shape: torch.Tensor, c1: int, records: Optional[torch.Tensor] = None, n_records: Optional[torch.Tensor] = None,
+               copies: int = 1, sweep: int = 1, road_margin: float = 0.0, types: Optional[List[int]] = None,
+               dt: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the step scores of stored column ``c1`` ("step scores" of include/infgen_hip.h, ``infgen_step_score``): the scene arrays as
+    for ``road_mask``, ``records`` (S / copies, capacity, 8) and ``n_records`` (S / copies,) from ``road_records_from_map`` /
+    ``_from_segments`` (None: no road table, ``n_offroad`` 0), ``types`` the (vehicle, pedestrian, cyclist) switch of the off-road
+    term (None: vehicles and cyclists).  Returns score (S, 8) = n_live, n_overlap, min_sep, n_offroad, max_accel, max_yaw_rate, 0, 0
+    and the rows' flag bytes (S, A) uint8: bit 0 live, bit 1 overlap, bit 2 off-road."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or tuple(head.shape) != tuple(pos.shape[:3]) or tuple(state.shape) != tuple(pos.shape[:3]):
+        raise ValueError('step_score takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,):
+        raise ValueError('step_score takes type (S, A), shape (S, A, 3), n_agents (S,)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    if (records is None) != (n_records is None):
+        raise ValueError('records and n_records come together')
+    if records is not None and (records.dim() != 3 or records.shape[2] != 8 or records.shape[0] != S // copies
+                                or tuple(n_records.shape) != (S // copies,)):
+        raise ValueError('step_score takes records (S / copies, capacity, 8) and n_records (S / copies,)')
+    types = [1, 0, 1] if types is None else [int(bool(v)) for v in types]
+    if len(types) != 3:
+        raise ValueError('types has three entries: vehicle, pedestrian, cyclist')
+    dev = pos.device
+    ops = _ops(dev)
+    i32 = lambda t: None if t is None else t.to(dev, torch.int32).contiguous()
+    st, na, ty, nr = i32(state), i32(n_agents), i32(type), i32(n_records)
+    p, h, sh = _f32(pos), _f32(head), _f32(shape)
+    rc = None if records is None else _f32(records)
+    score = torch.zeros(S, 8, device=dev)
+    row = torch.zeros(S, A, device=dev, dtype=torch.uint8)
+    _lib.check(ops.lib.infgen_step_score(_lib.ptr(p), _lib.ptr(h), _lib.ptr(st), _lib.ptr(na), _lib.ptr(ty), _lib.ptr(sh), S, A, T,
+                                         int(c1), _lib.ptr(rc), _lib.ptr(nr), 0 if records is None else int(records.shape[1]),
+                                         int(copies), int(sweep), float(road_margin), (C.c_int * 3)(*types), float(dt),
+                                         _lib.ptr(score), 8, _lib.ptr(row), ops.stream), 'infgen_step_score')
+    return score, row
+
+
+@step_score.register_fake
+def _(pos, head, state, n_agents, type, shape, c1, records=None, n_records=None, copies=1, sweep=1, road_margin=0.0, types=None,
+      dt=0.5):
+    return pos.new_empty(pos.shape[0], 8, dtype=torch.float32), pos.new_empty(pos.shape[0], pos.shape[2], dtype=torch.uint8)
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
