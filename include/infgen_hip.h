@@ -36,6 +36,7 @@
  *                            the insertion sub-loop (infgen/modules/agent_decoder.py:1773-2105)
  *   infgen_command_rows      no counterpart: a controller's per-step commands (token ids or target poses) for the replayed rows
  *   infgen_branch_scenes, infgen_resample_parents   no counterpart: a copy of a scene continues as a clone of another copy
+ *   infgen_snapshot_scenes, infgen_restore_scenes, infgen_snapshot_bytes   no counterpart: a slot's decode state saved and put back
  *
  * and, around the path:
  *
@@ -469,8 +470,9 @@ int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream);
 int infgen_command_rows(const InfgenRollout* r, int t, int kind, const int* cmd_token, const float* cmd_pose,
                         const unsigned char* cmd_mask, const float* shape, float* cmd_cost, void* stream);
 
-/* branching rollouts: BRANCHING, "scene slot s becomes a clone of slot p as of the boundary in front of decode step t" - what tree
- * search, MPC and sequential Monte Carlo over the copies of a scene need (k_branch_scenes: one launch, no host read).
+/* branching rollouts: BRANCHING, "scene slot s becomes a clone of slot p as of the boundary in front of decode step t" - what
+ * beam pruning and sequential Monte Carlo over the copies of a scene need (k_branch_scenes: one launch, no host read); the way back in
+ * time that MPC and tree search with backtracking need is "snapshots" below.
  * infgen_branch_scenes: parent is a device int32 array [S].  For every agent-side scene s with p = parent[s] != s, slot s receives slot
  * p's rollout state as it stands between decode step t - 1 and decode step t, 0 <= t <= steps (= T - 2):
  *   copied   the per-scene [T][A_cap] blocks of pos (x 2), head, state, token, grid, tmask, imask, catflag, and bos [A_cap];
@@ -496,6 +498,41 @@ int infgen_command_rows(const InfgenRollout* r, int t, int kind, const int* cmd_
  * 1 <= copies <= 1024, else refused. */
 int infgen_branch_scenes(const InfgenRollout* r, int t, const int* parent, int* n_bad, void* stream);
 int infgen_resample_parents(const int* ancestor, int S0, int copies, int* parent, void* stream);
+
+/* snapshots: SNAPSHOTS, "the decode state of scene slot s as of the boundary in front of decode step t, kept outside the context and put
+ * back later" - the way back in time: an MPC planner's look-ahead, tree search with backtracking, counterfactual re-runs
+ * (k_snapshot_scenes<RESTORE>: one launch per call, no host read).  Without scenario insertion a decode step is a function of the
+ * context and t, so a restored slot continues exactly as the saved one would have.
+ * A snapshot ENTRY holds exactly what infgen_branch_scenes copies (its "copied" list, the same segment table):
+ *   the per-scene [T][A_cap] blocks of pos (x 2), head, state, token, grid, tmask, imask, catflag, and bos [A_cap];
+ *   every ring slot of ringK[l] / ringV[l], l < num_layers; the scene's rows of X; pred_traj / pred_head / pred_state;
+ *   the slices [0, t) of token_logprob, sample_logprob and (store_logits) logits, where those pointers are given;
+ *   the scene's [steps][8] step-score block, where the context scores ("step scores").
+ * and nothing of its "kept" list (uniforms, temperatures, mask selectors and tables, replay flags, plans, collision and road buffers,
+ * scratch): a restored slot runs under the configuration the context has THEN, which is what a planner varies between two tries.
+ * Layout: the segments in table order (the order above; absent buffers take no room), each segment as its blocks per scene - one for
+ * the scene arrays, X and pred_*, `ring` for a ring, t for a log - every block starting on a 16-byte boundary (a block of b bytes takes
+ * (b + 15) & ~15; the library's own layouts have b % 16 == 0).  The bytes between a block's end and the boundary are written as 0.
+ * infgen_snapshot_bytes: host only, launches nothing: *bytes = the bytes of one entry at step t (a multiple of 16); returns 0 or a
+ *   negative code like every entry.  Monotone in t - the bytes at t = steps are the capacity for any step.
+ * infgen_snapshot_scenes: slots is a device int32 array [n], 0 <= n <= 65535; entry e (the entry_stride bytes at snap + e *
+ *   entry_stride) receives slot slots[e], and head [n][4] (device int32) receives {slot, group, t, valid} with group = map_scene[slot]
+ *   (map_scene NULL: the slot itself).  A slot out of range writes {slot, -1, t, 0}, moves nothing and is counted into *n_bad (optional
+ *   device int, zeroed by the call first).  The context is not written.
+ * infgen_restore_scenes: index is a device int32 array [S]; slot s receives entry index[s], -1 = keep.  One entry may go to several
+ *   slots (fan-out: the same as a branch from the saved slot).  An entry is applied only if 0 <= index[s] < n, its head says valid,
+ *   head.t == t and head.group is slot s's group; any other entry is read as -1 and counted into *n_bad.
+ * Nothing outside the two layouts (the context's buffers, n entries of entry_stride bytes, head [n][4]) is read or written for any
+ * content of slots, index or head, and the library never dereferences them on the host.  A context-side segment whose base, block size
+ * or stride is no multiple of 16 is moved byte by byte on that side; the snapshot side is always 16-byte aligned.
+ * Refused: t outside 0..steps, NULL arrays, entry_stride below the bytes of infgen_snapshot_bytes(r, t) or no multiple of 16, snap not 16-byte aligned,
+ * n outside 0..65535, a context with scenario insertion (first_new != NULL: left out for the reason branching gives).
+ * Cost: an entry is dominated by the rings, 2 * num_layers * ring * A_cap * 512 bytes per slot. */
+int infgen_snapshot_bytes(const InfgenRollout* r, int t, long long* bytes);
+int infgen_snapshot_scenes(const InfgenRollout* r, int t, const int* slots, int n, void* snap, long long entry_stride, int* head,
+                           int* n_bad, void* stream);
+int infgen_restore_scenes(const InfgenRollout* r, int t, const int* index, const void* snap, long long entry_stride, const int* head,
+                          int n, int* n_bad, void* stream);
 
 /* reproducible stand-in for softmax -> topk(k) -> multinomial (agent_decoder.py:2162-2163,2194-2195): the k most
  * probable tokens, inverse-CDF over their probabilities with a caller-supplied uniform per row; 1 <= k <= min(16, n), else refused */

@@ -65,6 +65,7 @@ class ClosedLoopSession:
         self._mask = torch.ones(S, A_cap, dtype=torch.uint8, device=dev)
         self.cost = torch.zeros(S, A_cap, device=dev)
         self._kind = self._result = None
+        self._look = None                               # lookahead()'s snapshot buffer, allocated at its first call
         self.t = 0
         self.steps = eng.cfg.num_decode_steps
         eng._refresh_opts(groups=True)
@@ -193,6 +194,81 @@ class ClosedLoopSession:
         ``observe()['allowed_tokens']`` of a child slot still shows the sizes of the child's own sets of the step that just ran."""
         self._check_open()
         self.eng.branch(parent, self.t)
+
+    # ------------------------------------------------------------------ snapshots (DESIGN 3.10)
+    def snapshot(self, slots=None, out=None):
+        """``RolloutEngine.snapshot(t, ...)`` at this session's step: the decode state of every slot (or ``slots``) in front of the
+        next ``advance()``, on the device.  The plan is not part of it: a restored slot follows the commands given after the
+        restore."""
+        self._check_open()
+        return self.eng.snapshot(self.t, slots=slots, out=out)
+
+    def restore(self, snap, index=None):
+        """``RolloutEngine.restore(snap, index)``, and the session stands at step ``snap.t`` again: ``t = snap.t``, a pending command
+        is dropped and the plan columns from that step on read "no token" again, as after ``__init__`` - the commands of the steps
+        that are run again come from the caller.  ``observe()`` shows the restored newest column at once; the collision and road
+        buffers are not part of a snapshot (every step rebuilds them), so ``observe()['allowed_tokens']`` stays that of the last
+        step that ran - the look-ahead's, say - until the next ``advance()``."""
+        self._check_open()
+        eng = self.eng
+        eng.restore(snap, index)
+        self.t = int(snap.t)
+        self._kind = None
+        c = eng.hc + self.t
+        eng.teacher_token[:, c:].fill_(-1)
+        eng.teacher_state[:, c:].zero_()
+        if eng._replay_pose is not None:
+            for buf in eng._replay_pose:
+                buf[:, c:].zero_()
+        self._result = None
+
+    def lookahead(self, horizon: int, tokens=None, poses=None, mask=None, weights=None) -> torch.Tensor:
+        """try the given commands for ``H = min(horizon, steps - t)`` steps and come back: a snapshot of all slots into a buffer the
+        session keeps, H x (``command``, ``advance``), ``branching.score_log_weight`` over the step scores of those steps, restore.
+        ``tokens`` / ``poses`` / ``mask``: what ``command`` takes with a leading step axis, [>= H, ...]; ``weights``: a dict with
+        keys of ``branching.SCORE_WEIGHTS``.  Returns the log weight [S0, copies] on the device (higher is better); nothing is read
+        on the host.  With ``copies = K`` and one candidate plan per copy, ``argmax`` over the result gathered into the next
+        ``command`` is one model-predictive-control step.  A command that was pending is pending again afterwards; ``cost`` is
+        that of before the call.  Needs an engine built with ``step_scores``."""
+        from . import branching
+        self._check_open()
+        eng = self.eng
+        if eng.step_scores is None:
+            raise ValueError('lookahead: needs step_scores (the engine logs no score to weigh the tries by)')
+        if self.done:
+            raise RuntimeError('the session has run its last step')
+        if (tokens is None) == (poses is None):
+            raise ValueError('give tokens= or poses=, one of them')
+        if int(horizon) < 1:
+            raise ValueError('lookahead: horizon must be at least 1')
+        weights = branching.check_score_weights(weights)
+        t0 = self.t
+        H = min(int(horizon), self.steps - t0)
+        cmd = tokens if tokens is not None else poses
+        for what, x in (('commands', cmd), ('mask', mask)):
+            if x is not None and (not isinstance(x, torch.Tensor) or x.dim() < 2 or x.shape[0] < H):
+                raise ValueError(f'lookahead: {what} need a leading step axis of at least {H} entries')
+        pending = None
+        if self._kind is not None:
+            pending = (self._kind, self._tok.clone(), self._pose.clone(), self._mask.clone())
+        cost = self.cost.clone()
+        if self._look is None:              # (a reload ends the session, so the layout cannot change under the buffer)
+            self._look = eng.snapshot_buffer()
+        snap = self.snapshot(out=self._look)
+        for h in range(H):
+            m = None if mask is None else mask[h]
+            if tokens is not None:
+                self.command(tokens=tokens[h], mask=m)
+            else:
+                self.command(poses=poses[h], mask=m)
+            self.advance()
+        lw = branching.score_log_weight(eng.step_score, t0, t0 + H, weights, copies=eng.copies)
+        self.restore(snap)
+        self.cost.copy_(cost)
+        if pending is not None:
+            self._kind = pending[0]
+            self._tok.copy_(pending[1]); self._pose.copy_(pending[2]); self._mask.copy_(pending[3])
+        return lw
 
     def advance(self):
         """the command kernel, then decode step ``t`` (with its insertion sub-loop when the engine inserts agents)"""

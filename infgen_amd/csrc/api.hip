@@ -1765,12 +1765,12 @@ extern "C" int infgen_command_rows(const InfgenRollout* r, int t, int kind, cons
 // ---- branching rollouts: slot s becomes a clone of slot parent[s] as of the boundary in front of decode step t (k_branch_scenes)
 // the segment table: everything a decode step reads that an earlier step (or the prologue) wrote per scene.  What configures a slot
 // (uniforms, temperatures, masks, plans, replay flags) and what every step rebuilds before reading it (edge sets, scratch) is not in it.
-static int branch_segments(const InfgenRollout* r, int t, BranchArgs* a, float* score_log, long long score_bytes) {
+static int branch_segments(const InfgenRollout* r, int t, BranchSeg* seg, int* n_seg, float* score_log, long long score_bytes) {
   const long long A = r->A_cap, rows = (long long)r->S * A;
   int n = 0, chunk = 0;
   auto add = [&](void* base, long long bytes, int outer, long long outer_stride) {
     if (!base || bytes <= 0 || outer <= 0) return;
-    BranchSeg& g = a->seg[n++];
+    BranchSeg& g = seg[n++];
     g.base = static_cast<char*>(base); g.bytes = bytes; g.outer = outer; g.outer_stride = outer_stride;
     g.per_block = (int)((bytes + BR_CHUNK - 1) / BR_CHUNK);
     g.chunk0 = chunk;
@@ -1792,7 +1792,7 @@ static int branch_segments(const InfgenRollout* r, int t, BranchArgs* a, float* 
   add(r->sample_logprob, A * 4, t, rows * 4);
   add(r->store_logits ? r->logits : nullptr, A * r->token_size * 4, t, rows * r->token_size * 4);
   add(score_log, score_bytes, 1, 0);                                  // the scene's whole [steps][8] block
-  a->n_seg = n;
+  *n_seg = n;
   return chunk;
 }
 
@@ -1810,9 +1810,78 @@ extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* pa
   static_assert(BR_MAX_SEGS >= 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 4, "segment table too short");
   BranchArgs a{};
   a.S = r->S; a.parent = parent; a.map_scene = r->map_scene; a.n_bad = n_bad;
-  const int chunks = branch_segments(r, t, &a, score.out, (long long)score.steps * 8 * 4);
+  const int chunks = branch_segments(r, t, a.seg, &a.n_seg, score.out, (long long)score.steps * 8 * 4);
   if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
   hipLaunchKernelGGL(k_branch_scenes, dim3(chunks, r->S), dim3(BR_NT), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+// ---- snapshots: the segments of branch_segments between the context and a caller's buffer of entries (k_snapshot_scenes)
+// the checks both directions and infgen_snapshot_bytes share; fills the segment table and every segment's offset in an entry
+static int snapshot_layout(const InfgenRollout* r, int t, const char* me, SnapArgs* a, int* chunks, long long* entry_bytes) {
+  ScoreCfg score;
+  RET_IF(validate(r, me, nullptr, nullptr, nullptr, nullptr, &score));
+  if (r->S <= 0 || r->S > 65535) return fail(me, "S must be in 1..65535");
+  if (r->T <= 0 || r->R <= 0 || r->ring <= 0 || r->token_size <= 0) return fail(me, "bad sizes");
+  if (r->first_new) return fail(me, "contexts with scenario insertion cannot be saved or restored: row counts, types and shapes differ between the copies");
+  if (t < 0 || 1 + t > r->T - 1) return fail(me, "t must be in 0..steps (the boundary in front of decode step t)");
+  if (!(r->pos && r->head && r->state && r->token && r->grid && r->tmask && r->imask && r->catflag && r->bos && r->X))
+    return fail(me, "null scene array");
+  *chunks = branch_segments(r, t, a->seg, &a->n_seg, score.out, (long long)score.steps * 8 * 4);
+  long long off = 0;
+  for (int k = 0; k < a->n_seg; ++k) {
+    a->entry_off[k] = off;
+    off += ((a->seg[k].bytes + 15) & ~15LL) * a->seg[k].outer;
+  }
+  *entry_bytes = off;
+  a->S = r->S; a->t = t; a->map_scene = r->map_scene;
+  return 0;
+}
+static int snapshot_buffer(const char* me, const void* snap, long long entry_stride, long long entry_bytes, int n) {
+  if (n < 0 || n > 65535) return fail(me, "n must be in 0..65535");
+  if (!snap) return fail(me, "null snapshot buffer");
+  if (reinterpret_cast<uintptr_t>(snap) & 15) return fail(me, "snap must be 16-byte aligned");
+  if (entry_stride & 15) return fail(me, "entry_stride must be a multiple of 16");
+  if (entry_stride < entry_bytes) return fail(me, "entry_stride is smaller than infgen_snapshot_bytes(r, t)");
+  return 0;
+}
+
+extern "C" int infgen_snapshot_bytes(const InfgenRollout* r, int t, long long* bytes) {
+  SnapArgs a{};
+  int chunks;
+  if (!bytes) return fail("infgen_snapshot_bytes", "null bytes");
+  return snapshot_layout(r, t, "infgen_snapshot_bytes", &a, &chunks, bytes);
+}
+
+extern "C" int infgen_snapshot_scenes(const InfgenRollout* r, int t, const int* slots, int n, void* snap, long long entry_stride,
+                                      int* head, int* n_bad, void* stream) {
+  const char* me = "infgen_snapshot_scenes";
+  SnapArgs a{};
+  int chunks;
+  long long bytes;
+  RET_IF(snapshot_layout(r, t, me, &a, &chunks, &bytes));
+  if (!slots || !head) return fail(me, "null slots or head");
+  RET_IF(snapshot_buffer(me, snap, entry_stride, bytes, n));
+  a.n = n; a.sel = slots; a.head = head; a.snap = static_cast<char*>(snap); a.stride = entry_stride; a.n_bad = n_bad;
+  if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_snapshot_scenes<false>, dim3(chunks, n), dim3(BR_NT), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+extern "C" int infgen_restore_scenes(const InfgenRollout* r, int t, const int* index, const void* snap, long long entry_stride,
+                                     const int* head, int n, int* n_bad, void* stream) {
+  const char* me = "infgen_restore_scenes";
+  SnapArgs a{};
+  int chunks;
+  long long bytes;
+  RET_IF(snapshot_layout(r, t, me, &a, &chunks, &bytes));
+  if (!index || !head) return fail(me, "null index or head");
+  RET_IF(snapshot_buffer(me, snap, entry_stride, bytes, n));
+  a.n = n; a.sel = index; a.head = const_cast<int*>(head); a.snap = static_cast<char*>(const_cast<void*>(snap));
+  a.stride = entry_stride; a.n_bad = n_bad;
+  if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
+  hipLaunchKernelGGL(k_snapshot_scenes<true>, dim3(chunks, r->S), dim3(BR_NT), 0, (hipStream_t)stream, a);
   return check_launch(me);
 }
 

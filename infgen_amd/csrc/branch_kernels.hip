@@ -7,6 +7,11 @@
 //                      held in registers, all four loads in flight before the first store (26 VGPRs, no LDS, no scratch).  Sources are fixed points, so no slot is read and written in one
 //                      launch: the gather runs in place without a staging copy.  A segment whose base, block size or stride is no
 //                      multiple of 16 is moved byte by byte (the library's own layouts never are: A_cap % 32 == 0).
+// k_snapshot_scenes    (include/infgen_hip.h, "snapshots") the same segments and the same chunk scheme between the context and
+//                      a caller's buffer of entries: <false> saves slot slots[e] into entry e and writes its head, <true> puts entry
+//                      index[s] back into slot s where the head allows it.  A workgroup whose entry is skipped returns before it
+//                      reads anything else.  The entry side is always 16-byte aligned; an unaligned context side goes byte by byte
+//                      (save 62 VGPRs - the byte-wise gather -, restore 30, no LDS, no scratch).
 // k_resample_parents   one workgroup per copy group: arbitrary ancestor indices -> a parent vector whose sources are fixed points.
 //                      Counts in LDS, one exclusive scan of (free slots, surplus copies) packed into a word, then every ancestor
 //                      writes itself into the free slots its surplus owns.
@@ -62,6 +67,103 @@ __global__ __launch_bounds__(BR_NT) void k_branch_scenes(BranchArgs a) {
     for (long long off = off0 + threadIdx.x; off < end; off += BR_NT) dst[off] = src[off];
   }
 }
+
+// ---- snapshots: the same segments between the context and a buffer of entries (kernels.h: SnapArgs)
+// 16 bytes of a context-side block that is not 16-byte aligned, byte by byte; bytes past the block's end read as 0 / are not written
+__device__ __forceinline__ uint4 snap_load_bytes(const char* p, long long off, long long bytes) {
+  unsigned w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    unsigned v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long o = off + i * 4 + j;
+      const unsigned b = static_cast<unsigned char>(p[o < bytes ? o : 0]);
+      v |= (o < bytes ? b : 0u) << (8 * j);
+    }
+    w[i] = v;
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+__device__ __forceinline__ void snap_store_bytes(char* p, long long off, long long bytes, uint4 v) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long o = off + i * 4 + j;
+      if (o < bytes) p[o] = static_cast<char>(w[i] >> (8 * j));
+    }
+}
+
+template <bool RESTORE> __global__ __launch_bounds__(BR_NT) void k_snapshot_scenes(SnapArgs a) {
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  int slot, e;
+  if (!RESTORE) {
+    e = blockIdx.y;
+    slot = a.sel[e];
+    const bool ok = slot >= 0 && slot < a.S;
+    if (first) {
+      int* h = a.head + 4 * (long long)e;
+      h[0] = slot; h[1] = !ok ? -1 : a.map_scene ? a.map_scene[slot] : slot; h[2] = a.t; h[3] = ok ? 1 : 0;
+      if (!ok && a.n_bad) atomicAdd(a.n_bad, 1);
+    }
+    if (!ok) return;
+  } else {
+    slot = blockIdx.y;
+    e = a.sel[slot];
+    if (e == -1) return;
+    bool ok = e >= 0 && e < a.n;
+    if (ok) {
+      const int* h = a.head + 4 * (long long)e;
+      ok = h[3] != 0 && h[2] == a.t && h[1] == (a.map_scene ? a.map_scene[slot] : slot);
+    }
+    if (!ok) {
+      if (first && a.n_bad) atomicAdd(a.n_bad, 1);
+      return;
+    }
+  }
+  int k = 0;
+  const int x = blockIdx.x;
+  while (k + 1 < a.n_seg && x >= a.seg[k + 1].chunk0) ++k;
+  const BranchSeg& g = a.seg[k];
+  const int local = x - g.chunk0;
+  const int o = local / g.per_block;
+  if (o >= g.outer) return;
+  const long long off0 = (long long)(local - o * g.per_block) * BR_CHUNK;
+  const long long padded = (g.bytes + 15) & ~15LL;          // a block's bytes in the entry
+  char* ctx = g.base + (long long)o * g.outer_stride + (long long)slot * g.bytes;
+  char* ent = a.snap + (long long)e * a.stride + a.entry_off[k] + (long long)o * padded;
+  // as in k_branch_scenes: four words per lane, every load unconditional (a lane past the end reads the block's first word, inside
+  // both layouts) and issued before the first store
+  const long long o0 = off0 + (long long)threadIdx.x * 16, o1 = o0 + BR_NT * 16, o2 = o1 + BR_NT * 16, o3 = o2 + BR_NT * 16;
+  static_assert(BR_VEC == 4, "four named words");
+  const bool in0 = o0 < padded, in1 = o1 < padded, in2 = o2 < padded, in3 = o3 < padded;
+  const long long l0 = in0 ? o0 : 0, l1 = in1 ? o1 : 0, l2 = in2 ? o2 : 0, l3 = in3 ? o3 : 0;
+  uint4 v0, v1, v2, v3;
+  if (RESTORE || g.wide) {
+    const char* src = RESTORE ? ent : ctx;
+    v0 = *reinterpret_cast<const uint4*>(src + l0); v1 = *reinterpret_cast<const uint4*>(src + l1);
+    v2 = *reinterpret_cast<const uint4*>(src + l2); v3 = *reinterpret_cast<const uint4*>(src + l3);
+  } else {
+    v0 = snap_load_bytes(ctx, l0, g.bytes); v1 = snap_load_bytes(ctx, l1, g.bytes);
+    v2 = snap_load_bytes(ctx, l2, g.bytes); v3 = snap_load_bytes(ctx, l3, g.bytes);
+  }
+  if (!RESTORE || g.wide) {
+    char* dst = RESTORE ? ctx : ent;
+    if (in0) *reinterpret_cast<uint4*>(dst + o0) = v0;
+    if (in1) *reinterpret_cast<uint4*>(dst + o1) = v1;
+    if (in2) *reinterpret_cast<uint4*>(dst + o2) = v2;
+    if (in3) *reinterpret_cast<uint4*>(dst + o3) = v3;
+  } else {
+    if (in0) snap_store_bytes(ctx, o0, g.bytes, v0);
+    if (in1) snap_store_bytes(ctx, o1, g.bytes, v1);
+    if (in2) snap_store_bytes(ctx, o2, g.bytes, v2);
+    if (in3) snap_store_bytes(ctx, o3, g.bytes, v3);
+  }
+}
+template __global__ void k_snapshot_scenes<false>(SnapArgs a);
+template __global__ void k_snapshot_scenes<true>(SnapArgs a);
 
 // ancestor[i] (a global slot index; outside slot i's group: i itself) for the copies of group blockIdx.x -> parent:
 //   a slot some entry names keeps itself; the slots nobody names, in ascending order, receive the surplus - ancestor j's count[j] - 1

@@ -677,6 +677,22 @@ constexpr int RS_NT = 256, RS_ITEMS = 4;       // copies <= RS_NT * RS_ITEMS
 __global__ void k_branch_scenes(BranchArgs a);
 __global__ void k_resample_parents(ResampleArgs a);
 
+// snapshots (include/infgen_hip.h, "snapshots"): the same segments between the context and a caller's buffer of ENTRIES.  Entry e is the
+// `stride` bytes at snap + e * stride; in it block o of segment k is the `bytes` bytes at entry_off[k] + o * align16(bytes) - segments in
+// table order, every block on a 16-byte boundary.  k_snapshot_scenes<false>: (chunk, entry) - entry e := slot sel[e], head[e] written;
+// k_snapshot_scenes<true>: (chunk, scene) - slot s := entry sel[s] where head[sel[s]] allows it.
+struct SnapArgs {
+  int S, n, t, n_seg;                          // scene slots, entries, the decode step of the boundary
+  const int* sel;                              // save: slots [n]; restore: index [S]
+  const int* map_scene;                        // [S] or NULL (a slot's group is the slot itself)
+  int* head;                                   // [n][4] = slot, group, t, valid: written by the save, read by the restore
+  char* snap; long long stride;
+  int* n_bad;                                  // optional: entries skipped
+  BranchSeg seg[BR_MAX_SEGS];
+  long long entry_off[BR_MAX_SEGS];
+};
+template <bool RESTORE> __global__ void k_snapshot_scenes(SnapArgs a);
+
 // score_kernels.hip: the step scores of one stored column (include/infgen_hip.h, "step scores"): 8 floats per scene slot, one flag byte
 // per row
 constexpr int SC_NT = 256;              // threads of the one workgroup per scene slot

@@ -822,6 +822,11 @@ class RolloutEngine:
         self._rollout_lp = self._rollout_slp = None
         # [1] int32: the entries of the last ``branch`` call's parent vector that broke the contract and were read as the identity
         self._branch_bad = torch.zeros(1, device=dev, dtype=torch.int32)      # (read through the ``branch_bad`` property)
+        # snapshots: the same counters for ``snapshot`` (slots out of range) and ``restore`` (entries read as "keep"), this engine's
+        # mark in a snapshot's layout signature, and the number of batches loaded so far (a reload outdates the snapshots before it)
+        self.snapshot_bad = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.restore_bad = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._snap_token, self._reload_gen = object(), 0
         self.tok_tab = self.grid_tab = self.cat_agent = self.cat_seed = None
         self.x_pt = None
         self._ctx = None
@@ -1245,6 +1250,7 @@ class RolloutEngine:
         self._mg_checked = False           # the new map may hold more pt <-> pt edges than the buffers
         self._prologue_done = False
         self._road_dirty = True            # the road records belong to the old map
+        self._reload_gen += 1              # snapshots of the old batch are refused (``restore``)
 
     # ------------------------------------------------------------------ log replay
     def _alloc_replay(self, with_pose: bool):
@@ -2123,6 +2129,100 @@ class RolloutEngine:
         p = p.to(self.device, torch.int32).contiguous().view(-1)
         _lib.check(self.lib.infgen_branch_scenes(C.byref(self._ctx), int(t), _lib.ptr(p), _lib.ptr(self.branch_bad), self.ops.stream),
                    'infgen_branch_scenes')
+        self._rollout_lp = self._rollout_slp = None
+
+    # ------------------------------------------------------------------ snapshots
+    def _check_snapshot_call(self, what: str, t: int):
+        if self.insertion:
+            raise ValueError(f'{what}: engines with scenario insertion are left out (row counts, types and shapes differ between '
+                             'the copies, as for branch)')
+        if self._ctx is None or not self._prologue_done:
+            raise RuntimeError(f'{what}: run prologue() first - there is no rollout state yet')
+        steps = self.cfg.num_decode_steps
+        if not 0 <= int(t) <= steps:
+            raise ValueError(f'{what}: t = {t} is outside 0 .. {steps}')
+
+    def snapshot_buffer(self, n: Optional[int] = None):
+        """an empty ``Snapshot`` with room for ``n`` slots (default: all) at any decode step - for ``snapshot(t, out=...)``"""
+        from . import snapshots
+        self._check_snapshot_call('snapshot_buffer', 0)
+        return snapshots.allocate(self, self.S if n is None else int(n))
+
+    def snapshot(self, t: int, slots=None, out=None):
+        """snapshots ("snapshots" of include/infgen_hip.h): the decode state of the named slots as of the boundary in
+        front of decode step ``t`` (0 .. steps) -> a ``snapshots.Snapshot`` on the device: what ``branch`` copies between slots
+        (stored columns, the temporal K / V rings, the pending raw feature, ``pred_*``, the logs of the steps that ran, the
+        step-score block), one entry per slot.  One launch of ``infgen_snapshot_scenes`` on the current stream; the engine is not
+        written.  ``slots``: None (all), a host list (checked here: ``ValueError`` naming the first bad entry) or a device int
+        tensor [n], taken as it is - stream-ordered, no host read; a slot out of range leaves an entry ``restore`` skips and is
+        counted into ``snapshot_bad``.  ``out``: a ``Snapshot`` of this engine with enough capacity (``snapshot_buffer()``) to
+        reuse instead of allocating - an entry is about ``2 * layers * ring * A_cap * 512`` bytes.  Refused on an engine with
+        scenario insertion and before ``prologue()``."""
+        from . import snapshots
+        self._check_snapshot_call('snapshot', t)
+        t = int(t)
+        host = None
+        if slots is None:
+            host = np.arange(self.S, dtype=np.int32)
+            sl = torch.arange(self.S, device=self.device, dtype=torch.int32)
+        elif isinstance(slots, torch.Tensor) and slots.is_cuda:
+            if slots.is_floating_point() or slots.dtype == torch.bool or slots.dim() != 1:
+                raise ValueError('slots: a device tensor holds integer slot indices, shape [n]')
+            if slots.numel() > 65535:
+                raise ValueError('slots: at most 65535 entries')
+            sl = slots.to(self.device, torch.int32).contiguous()
+        else:
+            host = snapshots.check_slots(slots.numpy() if isinstance(slots, torch.Tensor) else slots, self.S)
+            sl = torch.from_numpy(host).to(self.device)
+        n, need = int(sl.numel()), snapshots.entry_bytes(self, t)
+        if out is None:
+            out = snapshots.allocate(self, n, t)
+        else:
+            if not isinstance(out, snapshots.Snapshot) or out.signature != snapshots.signature(self):
+                raise ValueError('snapshot: out= is no Snapshot of this engine\'s layout')
+            if out.capacity < n or out.stride < need:
+                raise ValueError(f'snapshot: out= holds {out.capacity} entries of {out.stride} bytes, {n} of {need} are needed')
+        _lib.check(self.lib.infgen_snapshot_scenes(C.byref(self._ctx), t, _lib.ptr(sl), n, _lib.ptr(out.buf), out.stride,
+                                                   _lib.ptr(out.head), _lib.ptr(self.snapshot_bad), self.ops.stream),
+                   'infgen_snapshot_scenes')
+        out.t, out.n, out.slots, out.slots_host, out.generation = t, n, sl, host, self._reload_gen
+        return out
+
+    def restore(self, snap, index=None):
+        """the way back: slot s takes over entry ``index[s]`` of ``snap`` and stands at the boundary in front of decode step
+        ``snap.t`` again (``run(snap.t, ...)`` or ``step(snap.t)`` continues from there, bit for bit as the saved slot would have,
+        under the uniforms, temperatures, constraints and commands the engine has now).  ``index``: None - every saved slot back
+        onto itself (built on the device) - or int [S] / [S0, copies] of entry numbers, -1 = keep the slot as it is; one entry may
+        go to several slots of its copy group (the same as a branch from the saved slot).  A host ``index`` is checked here
+        (``ValueError`` naming the first bad entry); a device tensor is taken as it is - stream-ordered, no host read - and the
+        entries the kernel refuses (out of range, not valid, another step, another copy group) are read as -1 and counted into
+        ``restore_bad``.  One launch of ``infgen_restore_scenes``.  Raises for a snapshot of another engine layout or from before
+        a ``reload*()``, on engines with scenario insertion and before ``prologue()``.  Clears the cached rollout
+        log-probabilities.  Eager: captured graphs stay as they are."""
+        from . import snapshots
+        if not isinstance(snap, snapshots.Snapshot):
+            raise ValueError('restore takes a snapshots.Snapshot')
+        self._check_snapshot_call('restore', snap.t)
+        if snap.signature != snapshots.signature(self):
+            raise ValueError('restore: the snapshot belongs to another engine layout')
+        if snap.generation != self._reload_gen:
+            raise ValueError('restore: the snapshot was taken before a reload: its scenes are no longer in this engine')
+        if snap.n < 1:
+            raise ValueError('restore: the snapshot holds no entry')
+        if index is None:
+            idx = snapshots.identity_index(snap, self.S)
+        else:
+            x = index if isinstance(index, torch.Tensor) else torch.as_tensor(np.asarray(index))
+            if x.is_floating_point() or x.dtype == torch.bool:
+                raise ValueError('index holds integer entry indices')
+            if tuple(x.shape) not in ((self.S,), (self.S0, self.copies)):
+                raise ValueError(f'index: expected shape {(self.S,)} or {(self.S0, self.copies)}, got {tuple(x.shape)}')
+            if not x.is_cuda:
+                x = torch.from_numpy(snapshots.check_index(x.numpy(), self.S, snap.n, self.copies, snap.slots_host))
+            idx = x.to(self.device, torch.int32).contiguous().view(-1)
+        _lib.check(self.lib.infgen_restore_scenes(C.byref(self._ctx), int(snap.t), _lib.ptr(idx), _lib.ptr(snap.buf), snap.stride,
+                                                  _lib.ptr(snap.head), snap.n, _lib.ptr(self.restore_bad), self.ops.stream),
+                   'infgen_restore_scenes')
         self._rollout_lp = self._rollout_slp = None
 
     def rollout_guided(self, every: int = 4, keep: Optional[int] = None, weights=None, u=None):

@@ -32,6 +32,8 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.decode_step(ctx_bytes, t, pos, head, state, token, grid, x, next_token, next_state) -> next_token, next_state
     torch.ops.infgen_hip.command_rows(ctx_bytes, t, teacher_token, teacher_state, cmd_token?, cmd_pose?, cmd_mask?, shape?) -> cost (S, A_cap)
     torch.ops.infgen_hip.branch_scenes(ctx_bytes, t, parent (S,) int)                       -> n_bad (1,) int32; slot s := slot parent[s]
+    torch.ops.infgen_hip.snapshot_scenes(ctx_bytes, t, slots (n,) int, snap (n, stride) uint8, head (n, 4) int32) -> n_bad; entry e := slot slots[e]
+    torch.ops.infgen_hip.restore_scenes(ctx_bytes, t, index (S,) int, snap, head)           -> n_bad (1,) int32; slot s := entry index[s]
 
 (``decode_step`` works on the persistent state block ``InfgenRollout`` of include/infgen_hip.h, which ``RolloutEngine.ctx_tensor()``
 hands out as bytes; whole rollouts stay a C-ABI call, ``infgen_rollout_run``, driven by infgen_amd/engine.py).  ``register_fake`` gives every op a shape function, so they trace under
@@ -712,6 +714,62 @@ def branch_scenes(ctx: torch.Tensor, t: int, parent: torch.Tensor) -> torch.Tens
 @branch_scenes.register_fake
 def _(ctx, t, parent):
     return parent.new_empty(1, dtype=torch.int32)
+
+
+def _snapshot_args(what, blk, sel, snap, head):
+    if not (sel.is_cuda and snap.is_cuda and head.is_cuda):
+        raise _lib.InfgenHipError('infgen_hip ops need cuda tensors: the HIP path has no CPU fallback')
+    if sel.is_floating_point() or sel.dtype == torch.bool:
+        raise ValueError(f'{what}: slot and entry indices are integers')
+    if snap.dtype != torch.uint8 or snap.dim() != 2 or not snap.is_contiguous():
+        raise ValueError(f'{what}: snap is a contiguous uint8 tensor [entries, stride]')
+    if head.dtype != torch.int32 or tuple(head.shape) != (snap.shape[0], 4) or not head.is_contiguous():
+        raise ValueError(f'{what}: head is a contiguous int32 tensor [entries, 4]')
+    return sel.to(torch.int32).contiguous().view(-1)
+
+
+@torch.library.custom_op('infgen_hip::snapshot_scenes', mutates_args=('snap', 'head'))
+def snapshot_scenes(ctx: torch.Tensor, t: int, slots: torch.Tensor, snap: torch.Tensor, head: torch.Tensor) -> torch.Tensor:
+    """snapshots (``infgen_snapshot_scenes``; "snapshots" of include/infgen_hip.h): entry e of ``snap`` (uint8 [n, stride], stride at
+    least ``infgen_snapshot_bytes``) receives the decode state of slot ``slots[e]`` of the state block as of the boundary in front
+    of decode step ``t``, and ``head`` (int32 [n, 4]) its {slot, group, t, valid}.  ``ctx`` as in ``decode_step``; ``slots`` [n] int
+    device tensor.  The block's arrays are not written.  Returns the number of slots out of range, (1,) int32.  No host read."""
+    ops = _ops(snap.device)
+    blk = _lib.Rollout.from_buffer_copy(ctx.numpy().tobytes())
+    s = _snapshot_args('snapshot_scenes', blk, slots, snap, head)
+    if s.numel() != snap.shape[0]:
+        raise ValueError(f'snapshot_scenes: one slot per entry ({int(snap.shape[0])})')
+    bad = torch.zeros(1, device=snap.device, dtype=torch.int32)
+    _lib.check(ops.lib.infgen_snapshot_scenes(C.byref(blk), int(t), _lib.ptr(s), int(s.numel()), _lib.ptr(snap), int(snap.shape[1]),
+                                              _lib.ptr(head), _lib.ptr(bad), ops.stream), 'infgen_snapshot_scenes')
+    return bad
+
+
+@snapshot_scenes.register_fake
+def _(ctx, t, slots, snap, head):
+    return slots.new_empty(1, dtype=torch.int32)
+
+
+@torch.library.custom_op('infgen_hip::restore_scenes', mutates_args=())
+def restore_scenes(ctx: torch.Tensor, t: int, index: torch.Tensor, snap: torch.Tensor, head: torch.Tensor) -> torch.Tensor:
+    """snapshots (``infgen_restore_scenes``): slot s of the state block receives entry ``index[s]`` of ``snap`` (-1: keep), where that
+    entry's ``head`` row says valid, step ``t`` and slot s's copy group.  ``index`` [S] or [S0, copies] int device tensor.  The ~30
+    arrays the block points to are edited in place (not declared: the block owns them); returns the number of entries that were
+    refused and read as -1, (1,) int32.  No host read."""
+    ops = _ops(snap.device)
+    blk = _lib.Rollout.from_buffer_copy(ctx.numpy().tobytes())
+    x = _snapshot_args('restore_scenes', blk, index, snap, head)
+    if x.numel() != int(blk.S):
+        raise ValueError(f'restore_scenes: index must hold one entry per scene slot ({int(blk.S)})')
+    bad = torch.zeros(1, device=snap.device, dtype=torch.int32)
+    _lib.check(ops.lib.infgen_restore_scenes(C.byref(blk), int(t), _lib.ptr(x), _lib.ptr(snap), int(snap.shape[1]), _lib.ptr(head),
+                                             int(snap.shape[0]), _lib.ptr(bad), ops.stream), 'infgen_restore_scenes')
+    return bad
+
+
+@restore_scenes.register_fake
+def _(ctx, t, index, snap, head):
+    return index.new_empty(1, dtype=torch.int32)
 
 
 @torch.library.custom_op('infgen_hip::bundle_scores', mutates_args=())
