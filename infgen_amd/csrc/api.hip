@@ -67,6 +67,21 @@ constexpr ScoreCfg SCORE_NONE{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0,
 struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
+// what rides on a context's decode step: the static mask as the kernels take it and the three configurations of its handle
+// (validate fills it).  A new rider adds a Cfg, an args builder and one line in any()
+struct StepRiders {
+  TokenMaskCtl mask; CollisionCfg coll; RoadCfg road; ScoreCfg score;
+  bool any() const { return mask.bits || coll.bits || road.bits || score.out; }
+};
+constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, COLLISION_NONE, ROAD_NONE, SCORE_NONE};
+// the one handle lookup: f(slot) under g_mask_mu, or the error `what` where the handle names no registered mask
+constexpr const char* NO_TOKEN_MASK = "no such token mask";
+template <class F> static int with_mask_slot(const char* where, int handle, const char* what, F f) {
+  std::lock_guard<std::mutex> lk(g_mask_mu);
+  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(where, what);
+  f(g_masks[handle - 1]);
+  return 0;
+}
 
 // TokenMaskDesc (NULL: none) -> the kernels' TokenMaskCtl.  out->bits stays NULL - the unmasked kernels, today's bits - unless the
 // table can constrain some row: a table, n_sets > 0, and per-row selectors or a per-type set
@@ -95,11 +110,7 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
-  std::lock_guard<std::mutex> lk(g_mask_mu);
-  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use)
-    return fail("infgen_token_mask_destroy", "no such token mask");
-  g_masks[handle - 1].in_use = false;
-  return 0;
+  return with_mask_slot("infgen_token_mask_destroy", handle, NO_TOKEN_MASK, [](TokenMaskSlot& s) { s.in_use = false; });
 }
 
 // ---------------------------------------------------------------------------------- environment knobs
@@ -1355,8 +1366,33 @@ extern "C" int infgen_map_graph(int S, int M_cap, const int* n_map, const float*
   return check_launch("infgen_map_graph");
 }
 
+// ---------------------------------------------------------------------------------- step riders: the scene they read
+// the scene arrays a rider's kernel reads, as a stand-alone entry's parameters or a context hold them (the scores read no first_new
+// and no token_size), and the fields CollisionArgs, RoadArgs and ScoreArgs share
+struct RiderScene {
+  int S, A_cap, T; const float* pos; const float* head; const int* state; const int* n_agents; const int* first_new; const int* type;
+  int token_size;
+};
+static RiderScene rider_scene(const InfgenRollout* r) {
+  return RiderScene{r->S, r->A_cap, r->T, r->pos, r->head, r->state, r->n_agents, r->first_new, r->type, r->token_size};
+}
+template <class A, class Cfg> static A rider_args(const RiderScene& sc, const Cfg& k) {
+  A a{};
+  a.S = sc.S; a.A_cap = sc.A_cap; a.T = sc.T;
+  a.pos = sc.pos; a.head = sc.head; a.state = sc.state; a.n_agents = sc.n_agents; a.type = sc.type; a.shape = k.shape;
+  return a;
+}
+
 // ---------------------------------------------------------------------------------- collision masks
-// the argument checks of include/infgen_hip.h ("collision masks") and the one launch of k_collision_mask
+// the argument checks of include/infgen_hip.h ("collision masks"), the argument block of column c from a configuration (base: the
+// sets it refines) and the one launch of k_collision_mask
+static CollisionArgs collision_args(const RiderScene& sc, int c, const CollisionCfg& k, const TokenMaskCtl& base) {
+  CollisionArgs a = rider_args<CollisionArgs>(sc, k);
+  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
+  a.end_pose = k.end_pose; a.predict = k.predict; a.margin = k.margin;
+  a.base = base; a.out_bits = k.bits; a.out_count = k.count;
+  return a;
+}
 static int collision_check(const char* where, int predict, float margin, const float* shape, const float* end_pose, const uint32_t* bits) {
   if (!std::isfinite(margin) || margin < 0.f) return fail(where, "collision mask: margin must be finite and >= 0");
   if (predict != 0 && predict != 1) return fail(where, "collision mask: predict must be 0 or 1");
@@ -1398,14 +1434,11 @@ extern "C" int infgen_collision_mask(const float* pos, const float* head, const 
                                      int token_size, int predict, float margin, const uint32_t* mask_bits, int mask_n_sets,
                                      const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, void* stream) {
   const char* me = "infgen_collision_mask";
-  CollisionArgs a{};
-  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c;
-  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.first_new = first_new; a.type = type; a.shape = shape;
-  a.end_pose = end_pose; a.token_size = token_size; a.predict = predict; a.margin = margin;
-  a.out_bits = out_bits; a.out_count = out_count;
+  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
   const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  RET_IF(token_mask_ctl(me, &md, token_size, &a.base));
-  return launch_collision(me, a, stream);
+  TokenMaskCtl base;
+  RET_IF(token_mask_ctl(me, &md, token_size, &base));
+  return launch_collision(me, collision_args(sc, c, CollisionCfg{out_bits, nullptr, shape, end_pose, predict, margin, out_count}, base), stream);
 }
 
 extern "C" int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const int* identity_row, const float* shape,
@@ -1415,10 +1448,8 @@ extern "C" int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const
     RET_IF(collision_check(me, predict, margin, shape, end_pose, dyn_bits));
     if (!identity_row) return fail(me, "collision mask: needs the identity selectors [S * A_cap]");
   }
-  std::lock_guard<std::mutex> lk(g_mask_mu);
-  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(me, "no such token mask");
-  g_masks[handle - 1].coll = dyn_bits ? CollisionCfg{dyn_bits, identity_row, shape, end_pose, predict, margin, count} : COLLISION_NONE;
-  return 0;
+  const CollisionCfg cfg = dyn_bits ? CollisionCfg{dyn_bits, identity_row, shape, end_pose, predict, margin, count} : COLLISION_NONE;
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.coll = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- road masks
@@ -1426,13 +1457,17 @@ extern "C" int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const
 static bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) != 0;
 }
+// what road masks and step scores ask alike of a configuration that reads the road table, in the order both ask it.  (Each keeps
+// its margin check in front of this - the scores' dt check sits between the two - and its types check behind its own pointers')
+static int road_table_check(const char* where, const char* prefix, int sweep, int copies, int rec_cap, const float* shape) {
+  const char* what = sweep != 0 && sweep != 1 ? "sweep must be 0 or 1" : copies < 1 ? "copies must be at least 1"
+                     : rec_cap < 0 ? "negative record capacity" : !shape ? "needs the rows' shape array [S][A_cap][3]" : nullptr;
+  return what ? fail(where, (std::string(prefix) + what).c_str()) : 0;
+}
 static int road_check(const char* where, int sweep, float margin, int copies, int rec_cap, const float* shape, const float* end_pose,
                       const float* paths, const float* records, const int* n_records, const int* types, const uint32_t* bits) {
   if (!std::isfinite(margin) || margin < 0.f) return fail(where, "road mask: margin must be finite and >= 0");
-  if (sweep != 0 && sweep != 1) return fail(where, "road mask: sweep must be 0 or 1");
-  if (copies < 1) return fail(where, "road mask: copies must be at least 1");
-  if (rec_cap < 0) return fail(where, "road mask: negative record capacity");
-  if (!shape) return fail(where, "road mask: needs the rows' shape array [S][A_cap][3]");
+  RET_IF(road_table_check(where, "road mask: ", sweep, copies, rec_cap, shape));
   if (!end_pose) return fail(where, "road mask: needs the end-pose table of infgen_collision_end_poses");
   if (!paths) return fail(where, "road mask: needs the path table of infgen_road_paths");
   if (!records || !n_records) return fail(where, "road mask: needs the record table and its counts");
@@ -1440,6 +1475,15 @@ static int road_check(const char* where, int sweep, float margin, int copies, in
   if (!bits) return fail(where, "road mask: needs the output table");
   if (misaligned16(bits, end_pose, paths, records)) return fail(where, "road mask: the tables must be 16-byte aligned");
   return 0;
+}
+static RoadArgs road_args(const RiderScene& sc, int c, const RoadCfg& k, const TokenMaskCtl& base) {
+  RoadArgs a = rider_args<RoadArgs>(sc, k);
+  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
+  a.end_pose = k.end_pose; a.paths = k.paths; a.records = k.records; a.n_records = k.n_records; a.rec_cap = k.rec_cap;
+  a.copies = k.copies; a.sweep = k.sweep; a.margin = k.margin;
+  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
+  a.base = base; a.out_bits = k.bits; a.out_count = k.count;
+  return a;
 }
 static int launch_road(const char* where, const RoadArgs& a, void* stream) {
   RET_IF(road_check(where, a.sweep, a.margin, a.copies, a.rec_cap, a.shape, a.end_pose, a.paths, a.records, a.n_records, a.types, a.out_bits));
@@ -1493,17 +1537,14 @@ extern "C" int infgen_road_mask(const float* pos, const float* head, const int* 
                                 int sweep, float margin, const int* types, const uint32_t* mask_bits, int mask_n_sets,
                                 const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, void* stream) {
   const char* me = "infgen_road_mask";
-  RoadArgs a{};
-  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c;
-  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.first_new = first_new; a.type = type; a.shape = shape;
-  a.end_pose = end_pose; a.paths = paths; a.token_size = token_size; a.records = records; a.n_records = n_records; a.rec_cap = rec_cap;
-  a.copies = copies; a.sweep = sweep; a.margin = margin;
   RET_IF(road_check(me, sweep, margin, copies, rec_cap, shape, end_pose, paths, records, n_records, types, out_bits));
-  for (int k = 0; k < 3; ++k) a.types[k] = types[k];
-  a.out_bits = out_bits; a.out_count = out_count;
+  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
+  const RoadCfg cfg{out_bits, nullptr, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin,
+                    {types[0], types[1], types[2]}, out_count};
   const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  RET_IF(token_mask_ctl(me, &md, token_size, &a.base));
-  return launch_road(me, a, stream);
+  TokenMaskCtl base;
+  RET_IF(token_mask_ctl(me, &md, token_size, &base));
+  return launch_road(me, road_args(sc, c, cfg, base), stream);
 }
 
 extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int* identity_row, const float* shape, const float* end_pose,
@@ -1517,10 +1558,7 @@ extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int
     cfg = RoadCfg{road_bits, identity_row, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin,
                   {types[0], types[1], types[2]}, count};
   }
-  std::lock_guard<std::mutex> lk(g_mask_mu);
-  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(me, "no such token mask");
-  g_masks[handle - 1].road = cfg;
-  return 0;
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.road = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- step scores
@@ -1530,16 +1568,22 @@ static int score_check(const char* where, int sweep, float margin, int copies, i
                        const int* n_records, const int* types, float dt, const float* out) {
   if (!std::isfinite(margin) || margin < 0.f) return fail(where, "step score: road_margin must be finite and >= 0");
   if (!std::isfinite(dt) || !(dt > 0.f)) return fail(where, "step score: dt must be finite and > 0");
-  if (sweep != 0 && sweep != 1) return fail(where, "step score: sweep must be 0 or 1");
-  if (copies < 1) return fail(where, "step score: copies must be at least 1");
-  if (rec_cap < 0) return fail(where, "step score: negative record capacity");
-  if (!shape) return fail(where, "step score: needs the rows' shape array [S][A_cap][3]");
+  RET_IF(road_table_check(where, "step score: ", sweep, copies, rec_cap, shape));
   if (!types) return fail(where, "step score: needs the three-entry type switch");
   if (!out) return fail(where, "step score: needs the output [S][..][8]");
   if (reinterpret_cast<uintptr_t>(out) & 31) return fail(where, "step score: the output must be 32-byte aligned");
   if (records && !n_records) return fail(where, "step score: a record table needs its counts");
   if (misaligned16(records)) return fail(where, "step score: the record table must be 16-byte aligned");
   return 0;
+}
+// column c1 scored into the slots' 8 floats at out + s * out_stride (a context: step t's slice of the configuration's log)
+static ScoreArgs score_args(const RiderScene& sc, int c1, const ScoreCfg& k, float* out, long long out_stride) {
+  ScoreArgs a = rider_args<ScoreArgs>(sc, k);
+  a.c1 = c1;
+  a.records = k.records; a.n_records = k.n_records; a.rec_cap = k.rec_cap; a.copies = k.copies; a.sweep = k.sweep; a.margin = k.margin;
+  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
+  a.dt = k.dt; a.out = out; a.out_stride = out_stride; a.out_row = k.row;
+  return a;
 }
 static int launch_score(const char* where, const ScoreArgs& a, void* stream) {
   if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "step score: S, A_cap and T must be positive");
@@ -1558,13 +1602,9 @@ extern "C" int infgen_step_score(const float* pos, const float* head, const int*
                                  long long out_stride, unsigned char* out_row, void* stream) {
   const char* me = "infgen_step_score";
   RET_IF(score_check(me, sweep, road_margin, copies, rec_cap, shape, records, n_records, types, dt, out_score));
-  ScoreArgs a{};
-  a.S = S; a.A_cap = A_cap; a.T = T; a.c1 = c1;
-  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.type = type; a.shape = shape;
-  a.records = records; a.n_records = n_records; a.rec_cap = rec_cap; a.copies = copies; a.sweep = sweep; a.margin = road_margin;
-  for (int k = 0; k < 3; ++k) a.types[k] = types[k];
-  a.dt = dt; a.out = out_score; a.out_stride = out_stride; a.out_row = out_row;
-  return launch_score(me, a, stream);
+  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, nullptr, type, 0};
+  const ScoreCfg cfg{out_score, 0, out_row, shape, records, n_records, rec_cap, copies, sweep, road_margin, {types[0], types[1], types[2]}, dt};
+  return launch_score(me, score_args(sc, c1, cfg, out_score, out_stride), stream);
 }
 
 extern "C" int infgen_token_mask_score(int handle, float* step_score, int steps, unsigned char* score_row, const float* shape,
@@ -1578,10 +1618,7 @@ extern "C" int infgen_token_mask_score(int handle, float* step_score, int steps,
     cfg = ScoreCfg{step_score, steps, score_row, shape, records, n_records, rec_cap, copies, sweep, road_margin,
                    {types[0], types[1], types[2]}, dt};
   }
-  std::lock_guard<std::mutex> lk(g_mask_mu);
-  if (handle < 1 || (size_t)handle > g_masks.size() || !g_masks[handle - 1].in_use) return fail(me, "no such token mask");
-  g_masks[handle - 1].score = cfg;
-  return 0;
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.score = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- rollout context
@@ -1599,8 +1636,8 @@ static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src
 static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
-static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, TokenMaskCtl* mask = nullptr,
-                    CollisionCfg* coll = nullptr, RoadCfg* road = nullptr, ScoreCfg* score = nullptr) {
+// riders (optional): what rides on the context's decode step, from its token-mask handle (RIDERS_NONE without one)
+static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, StepRiders* riders = nullptr) {
   if (!r) return fail(where, "null context");
   if (r->A_cap > 1024 || r->A_cap <= 0) return fail(where, "A_cap must be in 1..1024");
   if (r->A_cap % 32) return fail(where, "A_cap must be a multiple of 32");
@@ -1615,39 +1652,25 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
     const InfgenSampling sp{r->sample_temperature, r->sample_top_p, r->sample_temp_row};
     RET_IF(sampling_ctl(where, &sp, ctl));
   }
-  TokenMaskCtl own_mask;
-  if (!mask) mask = &own_mask;
-  *mask = TOKEN_MASK_NONE;
-  CollisionCfg own_coll;
-  if (!coll) coll = &own_coll;
-  *coll = COLLISION_NONE;
-  RoadCfg own_road;
-  if (!road) road = &own_road;
-  *road = ROAD_NONE;
-  ScoreCfg own_score;
-  if (!score) score = &own_score;
-  *score = SCORE_NONE;
+  StepRiders own_riders;
+  if (!riders) riders = &own_riders;
+  *riders = RIDERS_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
     TokenMaskDesc tm;
-    {
-      std::lock_guard<std::mutex> lk(g_mask_mu);
-      if (r->token_mask < 1 || (size_t)r->token_mask > g_masks.size() || !g_masks[r->token_mask - 1].in_use)
-        return fail(where, "token_mask is no handle of infgen_token_mask_create");
-      tm = g_masks[r->token_mask - 1].d;
-      *coll = g_masks[r->token_mask - 1].coll;
-      *road = g_masks[r->token_mask - 1].road;
-      *score = g_masks[r->token_mask - 1].score;
-    }
+    RET_IF(with_mask_slot(where, r->token_mask, "token_mask is no handle of infgen_token_mask_create", [&](const TokenMaskSlot& s) {
+      tm = s.d; riders->coll = s.coll; riders->road = s.road; riders->score = s.score;
+    }));
     if (!tm.type) tm.type = r->type;
-    RET_IF(token_mask_ctl(where, &tm, r->token_size, mask));
-    if (coll->bits && (r->token_size % 32 || r->token_size > 64 * 32 * CM_WPL))
+    RET_IF(token_mask_ctl(where, &tm, r->token_size, &riders->mask));
+    const auto& [mask, coll, road, score] = *riders;
+    if (coll.bits && (r->token_size % 32 || r->token_size > 64 * 32 * CM_WPL))
       return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
-    if (road->bits && (r->token_size % 32 || r->token_size > 64 * 32 * RM_WPL))
+    if (road.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RM_WPL))
       return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
-    if (road->bits && r->S % road->copies) return fail(where, "road mask: S must be a multiple of copies");
-    if (score->out && r->first_new)
+    if (road.bits && r->S % road.copies) return fail(where, "road mask: S must be a multiple of copies");
+    if (score.out && r->first_new)
       return fail(where, "step score: contexts with scenario insertion cannot be scored: rows appended inside a step are left out");
-    if (score->out && r->S % score->copies) return fail(where, "step score: S must be a multiple of copies");
+    if (score.out && r->S % score.copies) return fail(where, "step score: S must be a multiple of copies");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
@@ -1798,8 +1821,8 @@ static int branch_segments(const InfgenRollout* r, int t, BranchSeg* seg, int* n
 
 extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* parent, int* n_bad, void* stream) {
   const char* me = "infgen_branch_scenes";
-  ScoreCfg score;
-  RET_IF(validate(r, me, nullptr, nullptr, nullptr, nullptr, &score));
+  StepRiders riders;
+  RET_IF(validate(r, me, nullptr, &riders));
   if (r->S <= 0 || r->S > 65535) return fail(me, "S must be in 1..65535");
   if (r->T <= 0 || r->R <= 0 || r->ring <= 0 || r->token_size <= 0) return fail(me, "bad sizes");
   if (!parent) return fail(me, "null parent");
@@ -1810,7 +1833,7 @@ extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* pa
   static_assert(BR_MAX_SEGS >= 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 4, "segment table too short");
   BranchArgs a{};
   a.S = r->S; a.parent = parent; a.map_scene = r->map_scene; a.n_bad = n_bad;
-  const int chunks = branch_segments(r, t, a.seg, &a.n_seg, score.out, (long long)score.steps * 8 * 4);
+  const int chunks = branch_segments(r, t, a.seg, &a.n_seg, riders.score.out, (long long)riders.score.steps * 8 * 4);
   if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
   hipLaunchKernelGGL(k_branch_scenes, dim3(chunks, r->S), dim3(BR_NT), 0, (hipStream_t)stream, a);
   return check_launch(me);
@@ -1819,15 +1842,15 @@ extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* pa
 // ---- snapshots: the segments of branch_segments between the context and a caller's buffer of entries (k_snapshot_scenes)
 // the checks both directions and infgen_snapshot_bytes share; fills the segment table and every segment's offset in an entry
 static int snapshot_layout(const InfgenRollout* r, int t, const char* me, SnapArgs* a, int* chunks, long long* entry_bytes) {
-  ScoreCfg score;
-  RET_IF(validate(r, me, nullptr, nullptr, nullptr, nullptr, &score));
+  StepRiders riders;
+  RET_IF(validate(r, me, nullptr, &riders));
   if (r->S <= 0 || r->S > 65535) return fail(me, "S must be in 1..65535");
   if (r->T <= 0 || r->R <= 0 || r->ring <= 0 || r->token_size <= 0) return fail(me, "bad sizes");
   if (r->first_new) return fail(me, "contexts with scenario insertion cannot be saved or restored: row counts, types and shapes differ between the copies");
   if (t < 0 || 1 + t > r->T - 1) return fail(me, "t must be in 0..steps (the boundary in front of decode step t)");
   if (!(r->pos && r->head && r->state && r->token && r->grid && r->tmask && r->imask && r->catflag && r->bos && r->X))
     return fail(me, "null scene array");
-  *chunks = branch_segments(r, t, a->seg, &a->n_seg, score.out, (long long)score.steps * 8 * 4);
+  *chunks = branch_segments(r, t, a->seg, &a->n_seg, riders.score.out, (long long)riders.score.steps * 8 * 4);
   long long off = 0;
   for (int k = 0; k < a->n_seg; ++k) {
     a->entry_off[k] = off;
@@ -2365,36 +2388,22 @@ extern "C" int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless,
 
 extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
-  TokenMaskCtl mask;
-  CollisionCfg coll;
-  RoadCfg road;
-  ScoreCfg score;
-  RET_IF(validate(r, "infgen_decode_step", &ctl, &mask, &coll, &road, &score));
+  StepRiders riders;
+  RET_IF(validate(r, "infgen_decode_step", &ctl, &riders));
+  auto& [mask, coll, road, score] = riders;
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const int c = 1 + t;
   if (t < 0 || c + 1 > r->T - 1) return fail("infgen_decode_step", "step beyond the column range");
+  const RiderScene sc = rider_scene(r);
   RET_IF(infgen_decode_layers(r, c, 0, stream));
   if (coll.bits) {      // collision-aware decoding: this column's sets from the boxes, then the heads read them row by row
-    CollisionArgs ca{};
-    ca.S = r->S; ca.A_cap = r->A_cap; ca.T = r->T; ca.c = c;
-    ca.pos = r->pos; ca.head = r->head; ca.state = r->state; ca.n_agents = r->n_agents; ca.first_new = r->first_new;
-    ca.type = r->type; ca.shape = coll.shape; ca.end_pose = coll.end_pose; ca.token_size = r->token_size;
-    ca.predict = coll.predict; ca.margin = coll.margin; ca.base = mask; ca.out_bits = coll.bits; ca.out_count = coll.count;
-    RET_IF(launch_collision("infgen_decode_step", ca, stream));
+    RET_IF(launch_collision("infgen_decode_step", collision_args(sc, c, coll, mask), stream));
     mask = TokenMaskCtl{coll.bits, rows, coll.ident, {-1, -1, -1}, nullptr};
   }
   if (road.bits) {      // road-aware decoding: the sets so far (static, or this column's collision sets) without the off-road tokens
-    RoadArgs ra{};
-    ra.S = r->S; ra.A_cap = r->A_cap; ra.T = r->T; ra.c = c;
-    ra.pos = r->pos; ra.head = r->head; ra.state = r->state; ra.n_agents = r->n_agents; ra.first_new = r->first_new;
-    ra.type = r->type; ra.shape = road.shape; ra.end_pose = road.end_pose; ra.paths = road.paths; ra.token_size = r->token_size;
-    ra.records = road.records; ra.n_records = road.n_records; ra.rec_cap = road.rec_cap; ra.copies = road.copies;
-    ra.sweep = road.sweep; ra.margin = road.margin;
-    for (int k = 0; k < 3; ++k) ra.types[k] = road.types[k];
-    ra.base = mask; ra.out_bits = road.bits; ra.out_count = road.count;
-    RET_IF(launch_road("infgen_decode_step", ra, stream));
+    RET_IF(launch_road("infgen_decode_step", road_args(sc, c, road, mask), stream));
     mask = TokenMaskCtl{road.bits, rows, road.ident, {-1, -1, -1}, nullptr};
   }
   float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
@@ -2420,14 +2429,7 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   RET_IF(infgen_integrate(r, t, stream));
   if (score.out) {      // step scores: the column this step produced, reduced per scene slot
     if (t >= score.steps) return fail("infgen_decode_step", "step score: the log holds fewer steps");
-    ScoreArgs sa{};
-    sa.S = r->S; sa.A_cap = r->A_cap; sa.T = r->T; sa.c1 = c + 1;
-    sa.pos = r->pos; sa.head = r->head; sa.state = r->state; sa.n_agents = r->n_agents; sa.type = r->type; sa.shape = score.shape;
-    sa.records = score.records; sa.n_records = score.n_records; sa.rec_cap = score.rec_cap; sa.copies = score.copies;
-    sa.sweep = score.sweep; sa.margin = score.margin; sa.dt = score.dt;
-    for (int k = 0; k < 3; ++k) sa.types[k] = score.types[k];
-    sa.out = score.out + (size_t)t * 8; sa.out_stride = (long long)score.steps * 8; sa.out_row = score.row;
-    RET_IF(launch_score("infgen_decode_step", sa, stream));
+    RET_IF(launch_score("infgen_decode_step", score_args(sc, c + 1, score, score.out + (size_t)t * 8, (long long)score.steps * 8), stream));
   }
   RET_IF(infgen_raw_feature(r, c + 1, stream));
   return 0;
@@ -2440,16 +2442,13 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
 // (memset, k_heads, k_heads_finish, k_integrate, k_rawfeat_prep, k_fourier_h, k_mlpemb_h, memset, k_build_edges,
 // k_fourier_h_multi, k_attn_hs ...).  Same arithmetic on the same data as infgen_decode_step (tests compare the two).
 extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream) {
-  TokenMaskCtl mask;
-  CollisionCfg coll;
-  RoadCfg road;
-  ScoreCfg score;
-  RET_IF(validate(r, "infgen_rollout_run", nullptr, &mask, &coll, &road, &score));
+  StepRiders riders;
+  RET_IF(validate(r, "infgen_rollout_run", nullptr, &riders));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !mask.bits && !coll.bits && !road.bits && !score.out && !r->token_logprob && !r->first_new &&
+  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !riders.any() && !r->token_logprob && !r->first_new &&
                     r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
   if (!fold) {
     for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));

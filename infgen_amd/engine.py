@@ -799,7 +799,6 @@ class RolloutEngine:
         self.token_masks, self.token_mask_type = None, [-1, -1, -1]
         self.mask_bits = self.mask_row = None             # static device buffers: [n_sets][token_size / 32] words, [S * A_cap] int32
         self._mask_handle = 0                             # infgen_token_mask_create's handle of (mask_bits, mask_row, token_mask_type)
-        self._load_token_masks(token_masks, token_mask_type, token_mask_row)
         self.stay_on_road = None                          # the checked configuration while road-aware decoding is on
         self.road_bits = self.road_allowed = self.road_records = self.road_n_records = None
         self._road = self._road_paths = self._road_reg = self._road_seg = None
@@ -810,9 +809,7 @@ class RolloutEngine:
         self.step_scores = None                           # the checked configuration while step scores are on
         self.step_score = self.score_row = None           # [S, steps, 8] floats, [S, A_cap] flag bytes
         self._score_arg = self._score_shape = self._score_reg = None
-        self._load_collisions(avoid_collisions)
-        self._load_road(stay_on_road)
-        self._load_scores(step_scores)
+        self._load_riders((token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -1059,11 +1056,7 @@ class RolloutEngine:
             self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
         self.stay_on_road = conf
         if conf is not None:
-            self._road_dirty = True
-            self._road_seg = None
-            if conf['segments'] is not None:
-                self._road_seg = tuple(torch.from_numpy(a).to(self.device) for a in conf['segments'])
-            self._road_room(64)
+            self._road_source(conf)
         if self.step_scores is not None:               # the scores read the engine's one road table: checked against the new one
             self._load_scores(self._score_arg)
         self._apply_token_masks()
@@ -1089,12 +1082,17 @@ class RolloutEngine:
             self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
         self.step_scores, self._score_arg = conf, (scores if conf is not None else None)
         if conf is not None and self.stay_on_road is None:      # the scores alone drive the road table
-            self._road_dirty = True
-            self._road_seg = None
-            if conf['segments'] is not None:
-                self._road_seg = tuple(torch.from_numpy(a).to(self.device) for a in conf['segments'])
-            self._road_room(64)
+            self._road_source(conf)
         self._apply_token_masks()
+
+    def _road_source(self, conf):
+        """``conf`` (road or scores) drives the engine's one road table: built again by the next prologue, from conf's explicit
+        segments where it has some, else from the map"""
+        self._road_dirty = True
+        self._road_seg = None
+        if conf['segments'] is not None:
+            self._road_seg = tuple(torch.from_numpy(a).to(self.device) for a in conf['segments'])
+        self._road_room(64)
 
     def _score_boxes(self) -> torch.Tensor:
         """the [rows, 3] shape array the score kernel reads: the road buffers' where the engine has them, else the scores' own"""
@@ -1151,47 +1149,35 @@ class RolloutEngine:
             if h < 1:
                 _lib.check(-1, 'infgen_token_mask_create')
             self._mask_handle, self._mask_reg = h, reg
-        conf, P = self.avoid_collisions, _lib.ptr
-        creg = None if conf is None else (self._mask_handle, conf['predict'], conf['margin'])
-        if creg != self._coll_reg:
-            if conf is None:
-                _lib.check(self.lib.infgen_token_mask_collision(self._mask_handle, None, None, None, None, 1, 0.0, None),
-                           'infgen_token_mask_collision')
-            else:
-                k = self._coll
-                _lib.check(self.lib.infgen_token_mask_collision(self._mask_handle, P(k['bits']), P(k['ident']), P(k['shape']),
-                                                                P(self._coll_end), conf['predict'], conf['margin'], P(k['allowed'])),
-                           'infgen_token_mask_collision')
-            self._coll_reg = creg
-        road = self.stay_on_road
-        rreg = None if road is None else (self._mask_handle, road['margin'], road['sweep'], road['types'], self.road_records.data_ptr(),
-                                          self._road_cap)
-        if rreg != self._road_reg:      # road-aware decoding rides on the handle in the same way (the table's address is part of it)
-            if road is None:
-                _lib.check(self.lib.infgen_token_mask_road(self._mask_handle, None, None, None, None, None, None, None, 0, 1, 1, 0.0,
-                                                           None, None), 'infgen_token_mask_road')
-            else:
-                k = self._road
-                _lib.check(self.lib.infgen_token_mask_road(self._mask_handle, P(k['bits']), P(k['ident']), P(k['shape']),
-                                                           P(self._coll_end), P(self._road_paths), P(self.road_records),
-                                                           P(self.road_n_records), self._road_cap, self.copies, road['sweep'],
-                                                           road['margin'], (C.c_int * 3)(*road['types']), P(k['allowed'])),
-                           'infgen_token_mask_road')
-            self._road_reg = rreg
+        h, P = self._mask_handle, _lib.ptr
+
+        def attach(reg_name, reg, entry, off, on):
+            """a rider's configuration onto the handle where its registration changed: ``on()``'s arguments, ``off``'s without one"""
+            if reg != getattr(self, reg_name):
+                _lib.check(getattr(self.lib, entry)(h, *(off if reg is None else on())), entry)
+                setattr(self, reg_name, reg)
+
+        conf, k = self.avoid_collisions, self._coll
+        attach('_coll_reg', None if conf is None else (h, conf['predict'], conf['margin']), 'infgen_token_mask_collision',
+               (None, None, None, None, 1, 0.0, None),
+               lambda: (P(k['bits']), P(k['ident']), P(k['shape']), P(self._coll_end), conf['predict'], conf['margin'], P(k['allowed'])))
+        # road-aware decoding rides on the handle in the same way (the table's address is part of it)
+        road, kr = self.stay_on_road, self._road
+        attach('_road_reg', None if road is None else (h, road['margin'], road['sweep'], road['types'], self.road_records.data_ptr(),
+                                                       self._road_cap), 'infgen_token_mask_road',
+               (None, None, None, None, None, None, None, 0, 1, 1, 0.0, None, None),
+               lambda: (P(kr['bits']), P(kr['ident']), P(kr['shape']), P(self._coll_end), P(self._road_paths), P(self.road_records),
+                        P(self.road_n_records), self._road_cap, self.copies, road['sweep'], road['margin'],
+                        (C.c_int * 3)(*road['types']), P(kr['allowed'])))
+        # and so do the step scores: the handle constrains nothing by itself
         sc = self.step_scores
-        sreg = None if sc is None else (self._mask_handle, constraints.score_key(sc), self.road_records.data_ptr(), self._road_cap,
-                                        self._score_boxes().data_ptr())
-        if sreg != self._score_reg:     # and so do the step scores: the handle constrains nothing by itself
-            if sc is None:
-                _lib.check(self.lib.infgen_token_mask_score(self._mask_handle, None, 0, None, None, None, None, 0, 1, 1, 0.0, None, 0.5),
-                           'infgen_token_mask_score')
-            else:
-                _lib.check(self.lib.infgen_token_mask_score(self._mask_handle, P(self.step_score), int(self.step_score.shape[1]), P(self.score_row),
-                                                            P(self._score_boxes()), P(self.road_records), P(self.road_n_records),
-                                                            self._road_cap, self.copies, sc['sweep'], sc['road_margin'],
-                                                            (C.c_int * 3)(*sc['types']), sc['dt']), 'infgen_token_mask_score')
-            self._score_reg = sreg
-        self._ctx.token_mask = self._mask_handle
+        attach('_score_reg', None if sc is None else (h, constraints.score_key(sc), self.road_records.data_ptr(), self._road_cap,
+                                                      self._score_boxes().data_ptr()), 'infgen_token_mask_score',
+               (None, 0, None, None, None, None, 0, 1, 1, 0.0, None, 0.5),
+               lambda: (P(self.step_score), int(self.step_score.shape[1]), P(self.score_row), P(self._score_boxes()),
+                        P(self.road_records), P(self.road_n_records), self._road_cap, self.copies, sc['sweep'], sc['road_margin'],
+                        (C.c_int * 3)(*sc['types']), sc['dt']))
+        self._ctx.token_mask = h
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
 
@@ -1214,16 +1200,23 @@ class RolloutEngine:
             c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
-    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
-                       avoid_collisions=None, stay_on_road=None, step_scores=None):
+    def _load_riders(self, token_masks=None, avoid_collisions=None, stay_on_road=None, step_scores=None):
+        """what rides on the decode step into the engine, in the one order it is resolved in: masks, collisions, road, scores (each
+        None: keep what is there; ``token_masks`` a (table, per-type, per-row) triple).  Road and scores are checked against each
+        other once both are resolved: the scores' argument is recorded - and scores that go are gone - before ``_load_road``
+        checks the scores that are on against the new road"""
         self._load_token_masks(*(token_masks or (None, None, None)))
         self._load_collisions(avoid_collisions)
-        if step_scores is not None:     # (both arguments are resolved before they are checked against each other)
+        if step_scores is not None:
             self._score_arg = step_scores if step_scores is not False else None
             if step_scores is False:
                 self._load_scores(False)
         self._load_road(stay_on_road)
         self._load_scores(step_scores)
+
+    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
+                       avoid_collisions=None, stay_on_road=None, step_scores=None):
+        self._load_riders(token_masks, avoid_collisions, stay_on_road, step_scores)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:

@@ -171,3 +171,77 @@ def test_abi_follows_the_header():
     ctx.token_mask, ctx.token_size = h, 2048
     assert lib.infgen_rollout_validate(C.byref(ctx)) != 0 and b'16-byte aligned' in lib.infgen_last_error()
     assert lib.infgen_token_mask_destroy(h) == 0
+
+
+def test_handles_that_name_nothing_are_refused_with_these_words():
+    """zero, a negative, one past the end and a destroyed handle: destroy and the three attach entries (turning a rider off or on)
+    say 'no such token mask', a context says it is 'no handle' (0 in a context: no mask at all); an attach entry checks its own
+    arguments before the handle; the next create takes the freed slot.  No device: every call returns before any launch"""
+    from infgen_amd import _lib
+    lib = _lib.load()
+    t3 = (C.c_int * 3)(1, 0, 1)
+    live = lib.infgen_token_mask_create(None, 0, None, None, None)
+    dead = lib.infgen_token_mask_create(None, 0, None, None, None)
+    assert live >= 1 and dead >= 1 and lib.infgen_token_mask_destroy(dead) == 0
+    ctx = _lib.Rollout()
+    ctx.S, ctx.A_cap, ctx.T, ctx.W, ctx.ring, ctx.num_layers, ctx.token_size = 1, 32, 4, 1, 2, 1, 2048
+    for bad in (0, -3, 10 ** 6, dead):
+        calls = (('infgen_token_mask_destroy', (bad,)),
+                 ('infgen_token_mask_collision', (bad, None, None, None, None, 1, 0.0, None)),
+                 ('infgen_token_mask_collision', (bad, 4096, 8192, 12288, 16384, 1, 0.0, None)),
+                 ('infgen_token_mask_road', (bad, None, None, None, None, None, None, None, 0, 1, 1, 0.0, None, None)),
+                 ('infgen_token_mask_road', (bad, 4096, 8192, 12288, 16384, 20480, 24576, 28672, 64, 1, 1, 0.0, t3, None)),
+                 ('infgen_token_mask_score', (bad, None, 0, None, None, None, None, 0, 1, 1, 0.0, None, 0.5)),
+                 ('infgen_token_mask_score', (bad, 4096, 4, None, 12288, None, None, 0, 1, 1, 0.0, t3, 0.5)))
+        for fn, args in calls:
+            assert getattr(lib, fn)(*args) == -1, (fn, bad)
+            assert lib.infgen_last_error() == fn.encode() + b': no such token mask', (fn, bad)
+        ctx.token_mask = bad
+        if bad == 0:
+            assert lib.infgen_rollout_validate(C.byref(ctx)) == 0
+        else:
+            assert lib.infgen_rollout_validate(C.byref(ctx)) == -1
+            assert lib.infgen_last_error() == b'infgen_rollout_validate: token_mask is no handle of infgen_token_mask_create'
+    assert lib.infgen_token_mask_collision(0, 4096, 8192, 12288, 16384, 2, 0.0, None) == -1
+    assert lib.infgen_last_error() == b'infgen_token_mask_collision: collision mask: predict must be 0 or 1'
+    assert lib.infgen_token_mask_road(0, 4096, 8192, 12288, 16384, 20480, 24576, 28672, 64, 1, 2, 0.0, t3, None) == -1
+    assert lib.infgen_last_error() == b'infgen_token_mask_road: road mask: sweep must be 0 or 1'
+    assert lib.infgen_token_mask_score(0, 4096, 0, None, 12288, None, None, 0, 1, 1, 0.0, t3, 0.5) == -1
+    assert lib.infgen_last_error() == b'infgen_token_mask_score: step score: steps must be positive'
+    assert lib.infgen_token_mask_create(None, 0, None, None, None) == dead
+    assert lib.infgen_token_mask_destroy(dead) == 0 and lib.infgen_token_mask_destroy(live) == 0
+
+
+def test_road_table_checks_fire_in_this_order_with_these_words():
+    """what a road and a score configuration are asked alike - each argument set below is bad in everything not yet reported, so
+    the message names the first check that fires (the scores' dt sits between the margin and the sweep)"""
+    from infgen_amd import _lib
+    lib = _lib.load()
+    t3 = (C.c_int * 3)(1, 0, 1)
+    h = lib.infgen_token_mask_create(None, 0, None, None, None)
+
+    def road(rec_cap, copies, sweep, margin, shape=None, end_pose=None, types=None):
+        assert lib.infgen_token_mask_road(h, 4096, 8192, shape, end_pose, 20480, 24576, 28672, rec_cap, copies, sweep, margin,
+                                          types, None) == -1
+        return lib.infgen_last_error()
+
+    def score(rec_cap, copies, sweep, margin, dt, shape=None, types=None):
+        assert lib.infgen_token_mask_score(h, 4096, 4, None, shape, None, None, rec_cap, copies, sweep, margin, types, dt) == -1
+        return lib.infgen_last_error()
+
+    assert road(-1, 0, 2, -1.0) == b'infgen_token_mask_road: road mask: margin must be finite and >= 0'
+    assert road(-1, 0, 2, 0.0) == b'infgen_token_mask_road: road mask: sweep must be 0 or 1'
+    assert road(-1, 0, 1, 0.0) == b'infgen_token_mask_road: road mask: copies must be at least 1'
+    assert road(-1, 1, 1, 0.0) == b'infgen_token_mask_road: road mask: negative record capacity'
+    assert road(0, 1, 1, 0.0) == b"infgen_token_mask_road: road mask: needs the rows' shape array [S][A_cap][3]"
+    assert road(0, 1, 1, 0.0, 12288) == b'infgen_token_mask_road: road mask: needs the end-pose table of infgen_collision_end_poses'
+    assert road(0, 1, 1, 0.0, 12288, 16384) == b'infgen_token_mask_road: road mask: needs the three-entry type switch'
+    assert score(-1, 0, 2, float('nan'), 0.0) == b'infgen_token_mask_score: step score: road_margin must be finite and >= 0'
+    assert score(-1, 0, 2, 0.0, 0.0) == b'infgen_token_mask_score: step score: dt must be finite and > 0'
+    assert score(-1, 0, 2, 0.0, 0.5) == b'infgen_token_mask_score: step score: sweep must be 0 or 1'
+    assert score(-1, 0, 1, 0.0, 0.5) == b'infgen_token_mask_score: step score: copies must be at least 1'
+    assert score(-1, 1, 1, 0.0, 0.5) == b'infgen_token_mask_score: step score: negative record capacity'
+    assert score(0, 1, 1, 0.0, 0.5) == b"infgen_token_mask_score: step score: needs the rows' shape array [S][A_cap][3]"
+    assert score(0, 1, 1, 0.0, 0.5, 12288) == b'infgen_token_mask_score: step score: needs the three-entry type switch'
+    assert lib.infgen_token_mask_road(h, 4096, 8192, 12288, 16384, 20480, 24576, 28672, 64, 1, 1, 0.0, t3, None) == 0
+    assert lib.infgen_token_mask_destroy(h) == 0
