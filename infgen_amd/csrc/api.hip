@@ -1408,15 +1408,15 @@ static int launch_collision(const char* where, CollisionArgs a, void* stream) {
   if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "collision mask: S, A_cap and T must be positive");
   if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "collision mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
   if (a.c < 0 || a.c >= a.T) return fail(where, "collision mask: column outside [0, T)");
-  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * CM_WPL)
+  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
     return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
   if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "collision mask: null scene array");
   // few rows: one row per wave and workgroup round; many: 16 rows share one staging of their scene's obstacles
-  int per = knob::cm_rows > 0 ? knob::cm_rows : ((long long)a.S * a.A_cap > 4096 ? 4 * CM_WAVES : CM_WAVES);
-  per = ceil_div(per, CM_WAVES) * CM_WAVES;
+  int per = knob::cm_rows > 0 ? knob::cm_rows : ((long long)a.S * a.A_cap > 4096 ? 4 * RIDER_WAVES : RIDER_WAVES);
+  per = ceil_div(per, RIDER_WAVES) * RIDER_WAVES;
   a.rows_per_wg = per;
-  const size_t lds = (size_t)CM_WAVES * 2 * CM_LIST * sizeof(float4) + (size_t)CM_STAGE * a.A_cap * sizeof(float);
-  hipLaunchKernelGGL(k_collision_mask, dim3(ceil_div(a.A_cap, per), a.S), dim3(64 * CM_WAVES), lds, (hipStream_t)stream, a);
+  const size_t lds = (size_t)RIDER_WAVES * 2 * RIDER_LIST * sizeof(float4) + (size_t)CM_STAGE * a.A_cap * sizeof(float);
+  hipLaunchKernelGGL(k_collision_mask, dim3(ceil_div(a.A_cap, per), a.S), dim3(64 * RIDER_WAVES), lds, (hipStream_t)stream, a);
   return check_launch(where);
 }
 
@@ -1490,12 +1490,12 @@ static int launch_road(const char* where, const RoadArgs& a, void* stream) {
   if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "road mask: S, A_cap and T must be positive");
   if (a.S % a.copies) return fail(where, "road mask: S must be a multiple of copies");
   if (a.c < 0 || a.c >= a.T) return fail(where, "road mask: column outside [0, T)");
-  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RM_WPL)
+  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
     return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
   if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "road mask: null scene array");
   const long long rows = (long long)a.S * a.A_cap;
   if (rows > 0x7fffffffLL) return fail(where, "road mask: too many rows");
-  hipLaunchKernelGGL(k_road_mask, dim3((unsigned)((rows + RM_WAVES - 1) / RM_WAVES)), dim3(64 * RM_WAVES), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_road_mask, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
   return check_launch(where);
 }
 
@@ -1663,9 +1663,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
     if (!tm.type) tm.type = r->type;
     RET_IF(token_mask_ctl(where, &tm, r->token_size, &riders->mask));
     const auto& [mask, coll, road, score] = *riders;
-    if (coll.bits && (r->token_size % 32 || r->token_size > 64 * 32 * CM_WPL))
+    if (coll.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
       return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
-    if (road.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RM_WPL))
+    if (road.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
       return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
     if (road.bits && r->S % road.copies) return fail(where, "road mask: S must be a multiple of copies");
     if (score.out && r->first_new)

@@ -602,15 +602,17 @@ __device__ __forceinline__ int topk_inverse_cdf_masked(const float (&topv)[KMAX]
   return topk_inverse_cdf<KMAX>(topv, live > 1 ? live : 1, u01, it, top_p, sum_out, m_out);
 }
 
+// the row skeleton k_collision_mask and k_road_mask share (rider.cuh): one wave per row
+constexpr int RIDER_WAVES = 4;          // rows a workgroup works on at a time (one wave each)
+constexpr int RIDER_LIST = 128;         // reachable obstacles a wave keeps in LDS per pass over the row's tokens
+constexpr int RIDER_WPL = 2;            // 32-token words a lane owns at most: token_size <= 64 * 32 * RIDER_WPL
+
 // k_collision_mask (collision_kernels.hip): the per-step allowed-token sets of collision-aware decoding (include/infgen_hip.h, "collision
 // masks"): set(i) = base(i) AND NOT collides(i) for every row of the layout, written as the row's own set of out_bits
-constexpr int CM_WAVES = 4;             // rows a workgroup works on at a time (one wave each)
-constexpr int CM_LIST = 128;            // reachable obstacles a wave keeps in LDS per pass over the row's tokens
-constexpr int CM_WPL = 2;               // 32-token words a lane owns at most: token_size <= 64 * 32 * CM_WPL
 constexpr int CM_STAGE = 9;             // floats the workgroup stages per obstacle row of the scene
 struct CollisionArgs {
   int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
-  int rows_per_wg;                      // rows of one scene a workgroup covers (a multiple of CM_WAVES)
+  int rows_per_wg;                      // rows of one scene a workgroup covers (a multiple of RIDER_WAVES)
   const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
   const int* n_agents; const int* first_new;                  // [S]; first_new optional: rows >= first_new[s] were appended inside this step
   const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
@@ -625,9 +627,6 @@ __global__ void k_collision_end_poses(EndPoseArgs a);
 
 // road_kernels.hip: the per-step allowed-token sets of road-aware decoding (include/infgen_hip.h, "road masks"):
 // set(i) = base(i) AND NOT offroad(i), written as the row's own set of out_bits
-constexpr int RM_WAVES = 4;             // rows a workgroup works on (one wave each)
-constexpr int RM_LIST = 128;            // reachable road records a wave keeps in LDS per pass over the row's tokens
-constexpr int RM_WPL = 2;               // 32-token words a lane owns at most: token_size <= 64 * 32 * RM_WPL
 constexpr int RM_REC = 8;               // floats of a record: anchor x, y, offset x, y | cos, sin, half length, radius
 struct RoadArgs {
   int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one

@@ -4,24 +4,16 @@
 // k_road_records_map / k_road_records_seg   once per reload: the compacted table of segment records of every distinct scene, from the
 //                         EDGE map tokens' vocabulary polylines or from explicit world-coordinate segments.
 // k_road_paths            once per vocabulary: direction and half length of every token's end displacement (the path rectangle).
-// k_road_mask             one wave per row:
-//   1. the wave streams its map scene's records 64 at a time from global memory (two 16-byte loads per lane) and keeps the ones the
-//      row can reach at all (midpoint distance <= own radius + the type's largest token displacement + the obstacle's radius), moved
-//      into the ROW's frame: (anchor - pos[c][i]) + offset first - world coordinates enter through that exact difference only -, then
-//      rotated by -head[c][i];
-//   2. a record whose obstacle rectangle overlaps the row's current box (the identity pose of that frame) is straddled and dropped;
-//      the others are ballot-compacted into the wave's LDS list;
-//   3. lane l owns the 32-token words l, l + 64 of the set: every token still allowed is tested against the list, its end box and
-//      (sweep) its path rectangle, each behind a circle reject; the word is assembled in a register and leaves with one store.
-//      A row with an empty list writes base(i) without reading a token; more than RM_LIST kept records take further passes;
-//   4. the fallback's "any token left?" is a wave reduction of the words' OR, the count one of their popcounts.
+// k_road_mask             the row skeleton of rider.cuh, one wave per row.  Its own part is the obstacle source: the wave streams its map
+//                         scene's records 64 at a time from global memory (two 16-byte loads per lane), keeps the ones the row can
+//                         reach at all (midpoint distance <= own radius + the type's largest displacement + the obstacle's radius)
+//                         and drops the straddled ones, whose obstacle rectangle overlaps the row's current box.
 // fp32 throughout, no fused multiply-add (the build's -ffp-contract=off), plain vector stores.
 #include "kernels.h"
-#include "sat.cuh"
+#include "rider.cuh"
 
 namespace ig {
 
-constexpr int RM_INVALID = 0;           // valid_state_type id of 'invalid' (edge_kernels.hip)
 constexpr long long RM_EDGE = 12;       // the map-token type EDGE
 constexpr int RM_POLY = 11;             // points of a map-vocabulary polyline
 
@@ -91,134 +83,49 @@ __global__ __launch_bounds__(256) void k_road_paths(RoadPathArgs a) {
   *reinterpret_cast<float4*>(a.paths + (size_t)k * 4) = d > 0.f ? make_float4(p.x / d, p.y / d, 0.5f * d, 0.f) : make_float4(1.0f, 0.f, 0.f, 0.f);
 }
 
-// the tokens of word `cur` (bits still allowed) of a row with half extents (hla, hwa) and radius ra against the n list entries of the
-// wave: returns the word without the off-road tokens.  pose / path: the type's end poses and path entries of the word's 32 tokens
-__device__ __forceinline__ unsigned road_word(unsigned cur, const float4* __restrict__ pose, const float4* __restrict__ path, const float4* la,
-                                              const float4* lb, int n, float hla, float hwa, float ra, int sweep) {
-  unsigned out = cur;
-  for (int b = 0; b < 32; ++b) {
-    if (!((cur >> b) & 1u)) continue;
-    const float4 p = pose[b];                                                  // dx, dy, cos, sin of the end box in the row's frame
-    float4 w = make_float4(1.0f, 0.f, 0.f, 0.f);
-    if (sweep) w = path[b];                                                    // cos, sin, half length of the path rectangle
-    const bool swept = w.z > 0.f;
-    const float mx = 0.5f * p.x, my = 0.5f * p.y, rp = w.z + hwa;              // its centre and a radius that encloses it
-    bool hit = false;
-    for (int e = 0; e < n && !hit; ++e) {
-      const float4 o = la[e];                                                  // midpoint, cos, sin of the record in the row's frame
-      const float4 q = lb[e];                                                  // half length, half width, radius of its obstacle rectangle
-      const float ddx = o.x - p.x, ddy = o.y - p.y;
-      const float rr = ra + q.z;
-      if (ddx * ddx + ddy * ddy <= rr * rr) hit = sat_sep(ddx, ddy, p.z, p.w, hla, hwa, o.z, o.w, q.x, q.y) < 0.f;
-      if (!hit && swept) {
-        const float ex = o.x - mx, ey = o.y - my;
-        const float rs = rp + q.z;
-        if (ex * ex + ey * ey <= rs * rs) hit = sat_sep(ex, ey, w.x, w.y, w.z, hwa, o.z, o.w, q.x, q.y) < 0.f;
-      }
-    }
-    if (hit) out &= ~(1u << b);
-  }
-  return out;
-}
-
-__global__ __launch_bounds__(64 * RM_WAVES) void k_road_mask(RoadArgs a) {
-  __shared__ float4 rm_lds[RM_WAVES * 2 * RM_LIST];
+__global__ __launch_bounds__(64 * RIDER_WAVES) void k_road_mask(RoadArgs a) {
+  __shared__ float4 rm_lds[RIDER_WAVES * 2 * RIDER_LIST];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float4* const list_a = rm_lds + wave * (2 * RM_LIST);
-  float4* const list_b = list_a + RM_LIST;
-  const long long row_at = (long long)blockIdx.x * RM_WAVES + wave;
+  float4* const list_a = rm_lds + wave * (2 * RIDER_LIST);
+  float4* const list_b = list_a + RIDER_LIST;
+  const long long row_at = (long long)blockIdx.x * RIDER_WAVES + wave;
   if (row_at >= (long long)a.S * a.A_cap) return;                              // (uniform per wave; the kernel has no workgroup barrier)
   const int row = (int)row_at, A_cap = a.A_cap, words = a.token_size >> 5;
   const int s = row / A_cap, i = row - s * A_cap;
-  int n = a.n_agents[s];
-  if (a.first_new) n = min(n, a.first_new[s]);
-  n = min(n, A_cap);
+  const int n = scene_rows(a.n_agents, a.first_new, s, A_cap);
   const size_t col = ((size_t)s * a.T + a.c) * A_cap;                          // row 0 of column c
-  const unsigned* bset = a.base.bits ? token_mask_set(a.base, row, words) : nullptr;
-  unsigned* const out = a.out_bits + (size_t)row * words;
-  unsigned cur[RM_WPL];
-#pragma unroll
-  for (int q = 0; q < RM_WPL; ++q) {
-    const int w = lane + 64 * q;
-    cur[q] = w < words ? (bset ? bset[w] : 0xffffffffu) : 0u;
-  }
-  int ty = a.type[row];
-  if (ty < 0 || ty > 2) ty = 0;
-  const int ruled = ty == 0 ? a.types[0] : ty == 1 ? a.types[1] : a.types[2];
-  const bool live = i < n && a.state[col + i] != RM_INVALID && ruled != 0;
-  if (live) {
-    const float px = a.pos[2 * (col + i)], py = a.pos[2 * (col + i) + 1], ph = a.head[col + i];
-    const float ci = cosf(ph), si = sinf(ph);
-    const float hla = 0.5f * a.shape[3 * (size_t)row], hwa = 0.5f * a.shape[3 * (size_t)row + 1];
-    const float ra = sqrtf(hla * hla + hwa * hwa);
-    const float reach = ra + a.end_pose[(size_t)3 * a.token_size * 4 + ty];
-    const float4* pose = reinterpret_cast<const float4*>(a.end_pose) + (size_t)ty * a.token_size;
+    unsigned cur[RIDER_WPL];
+  const unsigned* bset = base_words(cur, a.base, row, words, lane);
+  const int ty = clamp_type(a.type[row]);
+  if (i < n && a.state[col + i] != INVALID && type_ruled(a.types, ty) != 0) {
+    const RowBox r = row_box(a.pos, a.head, a.shape, a.end_pose, a.token_size, col, row, i, ty);
     const float4* path = reinterpret_cast<const float4*>(a.paths) + (size_t)ty * a.token_size;
+    auto pass = [&](int m) __attribute__((always_inline)) { token_pass<true>(cur, lane, r, path, list_a, list_b, m, a.sweep); };
     const int ms = s / a.copies;
     const int nr = min(max(a.n_records[ms], 0), a.rec_cap);
     const float4* rec = reinterpret_cast<const float4*>(a.records) + (size_t)ms * a.rec_cap * 2;
-    const float hwo = a.margin;                                                // the obstacle rectangle's half width
     int m = 0;
     for (int j0 = 0; j0 < nr; j0 += 64) {
       const int j = j0 + lane;
       bool in = false;
-      float ox = 0.f, oy = 0.f, oc = 1.0f, os = 0.f, hlo = 0.f, orad = 0.f;
+      float4 ea = make_float4(0.f, 0.f, 1.0f, 0.f), eb = make_float4(0.f, 0.f, 0.f, 0.f);
       if (j < nr) {
         const float4 r0 = rec[2 * j], r1 = rec[2 * j + 1];
-        const float rx = (r0.x - px) + r0.z, ry = (r0.y - py) + r0.w;
-        hlo = r1.z + a.margin;
-        orad = sqrtf(hlo * hlo + hwo * hwo);
-        const float lim = reach + orad;
-        in = r1.w >= 0.f && rx * rx + ry * ry <= lim * lim;
-        if (in) {
-          ox = rx * ci + ry * si; oy = ry * ci - rx * si;
-          oc = r1.x * ci + r1.y * si; os = r1.y * ci - r1.x * si;
-          // astride the row's current box (the identity pose of its own frame): not an obstacle of this row in this step
-          in = !(sat_sep(ox, oy, 1.0f, 0.f, hla, hwa, oc, os, hlo, hwo) < 0.f);
-        }
+        const RoadRel e = road_rel(r0, r1, r.px, r.py, a.margin);
+        const float lim = r.reach + e.orad;
+        in = r1.w >= 0.f && e.rx * e.rx + e.ry * e.ry <= lim * lim;
+        // astride the row's current box: not an obstacle of this row in this step
+        if (in) in = !(road_own_sep(e, r1, r.ci, r.si, r.hla, r.hwa, a.margin, &ea) < 0.f);
+        eb = make_float4(e.hlo, a.margin, e.orad, 0.f);
       }
-      unsigned long long bal = __ballot(in);
-      while (bal) {                                                             // (uniform: at most two rounds per 64 records)
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        const bool put = in && ((bal >> lane) & 1ull) && m + before < RM_LIST;
-        if (put) {
-          list_a[m + before] = make_float4(ox, oy, oc, os);
-          list_b[m + before] = make_float4(hlo, hwo, orad, 0.f);
-        }
-        const unsigned long long done = __ballot(put);
-        m += (int)__popcll(done);
-        bal &= ~done;
-        if (bal) {                                                              // the list is full: a pass over the tokens, then go on
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int q = 0; q < RM_WPL; ++q)
-            if (cur[q]) cur[q] = road_word(cur[q], pose + 32 * (lane + 64 * q), path + 32 * (lane + 64 * q), list_a, list_b, m, hla, hwa, ra, a.sweep);
-          __builtin_amdgcn_wave_barrier();
-          m = 0;
-        }
-      }
+      list_put(in, ea, eb, list_a, list_b, m, lane, pass);
     }
     if (m > 0) {
       __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int q = 0; q < RM_WPL; ++q)
-        if (cur[q]) cur[q] = road_word(cur[q], pose + 32 * (lane + 64 * q), path + 32 * (lane + 64 * q), list_a, list_b, m, hla, hwa, ra, a.sweep);
+      pass(m);
     }
   }
-  // the fallback's "any token left?" and the count: wave reductions over the words
-  unsigned any = 0u;
-  int cnt = 0;
-#pragma unroll
-  for (int q = 0; q < RM_WPL; ++q) { any |= cur[q]; cnt += __popc(cur[q]); }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { any |= __shfl_xor(any, off, 64); cnt += __shfl_xor(cnt, off, 64); }
-  if (a.out_count && lane == 0) a.out_count[row] = cnt;
-  const bool fallback = any == 0u;      // (every token left the road: the row keeps base(i))
-#pragma unroll
-  for (int q = 0; q < RM_WPL; ++q) {
-    const int w = lane + 64 * q;
-    if (w < words) out[w] = fallback ? (bset ? bset[w] : 0xffffffffu) : cur[q];
-  }
+  row_store(cur, bset, a.out_bits, a.out_count, row, words, lane);
 }
 
 }  // namespace ig

@@ -1,5 +1,5 @@
-// The separating-axis value of two oriented rectangles, shared by k_collision_mask and k_road_mask (include/infgen_hip.h, "collision
-// masks" / "road masks"): the candidate A has the heading (ca, sa) and the half extents (hla, hwa), the obstacle B the heading (cb, sb)
+// The separating-axis value of two oriented rectangles, shared by the step riders (rider.cuh, k_step_score; include/infgen_hip.h,
+// "collision masks" / "road masks" / "step scores"): the candidate A has the heading (ca, sa) and the half extents (hla, hwa), the obstacle B the heading (cb, sb)
 // and the half extents (hlb, hwb); (ddx, ddy) is B's centre minus A's, all in one frame.  Returns the maximum over the four axes of
 // |projected centre distance| - the sum of the projected half extents: the rectangles overlap iff the value is < 0.
 // fp32, no fused multiply-add (the build's -ffp-contract=off): the order of the operations below is part of the definition's bits.

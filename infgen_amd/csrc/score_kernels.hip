@@ -9,18 +9,16 @@
 //      lane's running minimum: with D the centre distance, sep >= D / sqrt(2) - (r_i + r_j), so a pair whose bound is neither below
 //      0 nor below the minimum so far can change neither the flag nor min_sep;
 //   2. the road pass: the same lanes cover (row, slice of records); the records stream from global memory (two 16-byte loads per
-//      lane) and enter through (anchor - pos[i]) + offset, the row's box (its own frame) and, with sweep, its path rectangle each
-//      behind a circle reject;
+//      lane) and enter through rider.cuh's road-record entry - the one k_road_mask bans by -, the row's box (its own frame) and,
+//      with sweep, its path rectangle (world axes) each behind a circle reject;
 //   3. counts, the minimum and the two maxima: a wave reduction each, one LDS combine over the waves, two 16-byte stores; the flag
 //      bytes leave LDS with plain byte stores.
 // Every reduction is a count, a min or a max: the result does not depend on the order.  fp32 throughout, no fused multiply-add (the
 // build's -ffp-contract=off), no atomics, plain vector stores.
 #include "kernels.h"
-#include "sat.cuh"
+#include "rider.cuh"
 
 namespace ig {
-
-constexpr int SC_INVALID = 0;           // valid_state_type id of 'invalid' (edge_kernels.hip)
 
 __device__ __forceinline__ float score_abs_wrap(float a) {          // |wrap to [-pi, pi)| of a heading difference
   const float PI_F = 3.14159274f, TWO_PI_F = 6.28318548f;
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(SC_NT) void k_step_score(ScoreArgs a) {
   // 0. staging, and the comfort terms of the rows this lane stages
   const float dt2 = a.dt * a.dt;
   for (int i = tid; i < A_cap; i += SC_NT) {
-    const bool live = i < n && a.state[col + i] != SC_INVALID;
+    const bool live = i < n && a.state[col + i] != INVALID;
     float4 ra = make_float4(0.f, 0.f, 1.0f, 0.f), rb = make_float4(0.f, 0.f, -1.0f, 0.f);
     if (live) {
       const float px = a.pos[2 * (col + i)], py = a.pos[2 * (col + i) + 1], ph = a.head[col + i];
@@ -54,10 +52,10 @@ __global__ __launch_bounds__(SC_NT) void k_step_score(ScoreArgs a) {
       ra = make_float4(px, py, cosf(ph), sinf(ph));
       rb = make_float4(hl, hw, sqrtf(hl * hl + hw * hw), 0.f);
       ++n_live;
-      if (c1 >= 1 && a.state[col - A_cap + i] != SC_INVALID) {
+      if (c1 >= 1 && a.state[col - A_cap + i] != INVALID) {
         const size_t p1 = col - A_cap + i;
         max_yaw = fmaxf(max_yaw, score_abs_wrap(ph - a.head[p1]) / a.dt);
-        if (c1 >= 2 && a.state[p1 - A_cap] != SC_INVALID) {
+        if (c1 >= 2 && a.state[p1 - A_cap] != INVALID) {
           const size_t p2 = p1 - A_cap;
           const float x1 = a.pos[2 * p1], y1 = a.pos[2 * p1 + 1];
           const float ux = px - x1, uy = py - y1, vx = x1 - a.pos[2 * p2], vy = y1 - a.pos[2 * p2 + 1];
@@ -112,35 +110,26 @@ __global__ __launch_bounds__(SC_NT) void k_step_score(ScoreArgs a) {
     int off_road = 0;
     if (nr > 0) {                                                                 // (uniform)
       if (live) {
-        int ty = a.type[(size_t)s * A_cap + i];
-        if (ty < 0 || ty > 2) ty = 0;
-        const int ruled = ty == 0 ? a.types[0] : ty == 1 ? a.types[1] : a.types[2];
-        if (ruled != 0) {
+        if (type_ruled(a.types, clamp_type(a.type[(size_t)s * A_cap + i])) != 0) {
           float ddx = 0.f, ddy = 0.f, ux = 1.0f, uy = 0.f, hd = 0.f;             // the displacement, its direction and half length
-          if (a.sweep && c1 >= 1 && a.state[col - A_cap + i] != SC_INVALID) {
+          if (a.sweep && c1 >= 1 && a.state[col - A_cap + i] != INVALID) {
             ddx = ia.x - a.pos[2 * (col - A_cap + i)]; ddy = ia.y - a.pos[2 * (col - A_cap + i) + 1];
             const float d = sqrtf(ddx * ddx + ddy * ddy);
             if (d > 0.f) { ux = ddx / d; uy = ddy / d; hd = 0.5f * d; }
           }
           const bool swept = hd > 0.f;
           const float rp = hd + ib.y;                                             // a radius that encloses the path rectangle
-          const float hwo = a.margin;
           for (int j = q; j < nr && !off_road; j += P) {
             const float4 r0 = rec[2 * j], r1 = rec[2 * j + 1];
             if (!(r1.w >= 0.f)) continue;
-            const float rx = (r0.x - ia.x) + r0.z, ry = (r0.y - ia.y) + r0.w;
-            const float hlo = r1.z + a.margin;
-            const float orad = sqrtf(hlo * hlo + hwo * hwo);
-            const float rr = ib.z + orad;
-            if (rx * rx + ry * ry <= rr * rr) {
-              const float ox = rx * ia.z + ry * ia.w, oy = ry * ia.z - rx * ia.w;
-              const float oc = r1.x * ia.z + r1.y * ia.w, os = r1.y * ia.z - r1.x * ia.w;
-              off_road = sat_sep(ox, oy, 1.0f, 0.f, ib.x, ib.y, oc, os, hlo, hwo) < 0.f ? 1 : 0;
-            }
+            const RoadRel e = road_rel(r0, r1, ia.x, ia.y, a.margin);
+            const float rr = ib.z + e.orad;
+            float4 at;
+            if (e.rx * e.rx + e.ry * e.ry <= rr * rr) off_road = road_own_sep(e, r1, ia.z, ia.w, ib.x, ib.y, a.margin, &at) < 0.f ? 1 : 0;
             if (!off_road && swept) {
-              const float ex = rx + 0.5f * ddx, ey = ry + 0.5f * ddy;            // the record seen from the displacement's midpoint
-              const float rs = rp + orad;
-              if (ex * ex + ey * ey <= rs * rs) off_road = sat_sep(ex, ey, ux, uy, hd, ib.y, r1.x, r1.y, hlo, hwo) < 0.f ? 1 : 0;
+              const float ex = e.rx + 0.5f * ddx, ey = e.ry + 0.5f * ddy;        // the record seen from the displacement's midpoint
+              const float rs = rp + e.orad;
+              if (ex * ex + ey * ey <= rs * rs) off_road = sat_sep(ex, ey, ux, uy, hd, ib.y, r1.x, r1.y, e.hlo, a.margin) < 0.f ? 1 : 0;
             }
           }
         }

@@ -122,7 +122,10 @@ def reference(pos, head, state, n_agents, atype, shape, vocab, c, predict=1, mar
 # ------------------------------------------------------------------------------------------ the shared operator-level cases
 # token_size 2048 and 64 (lanes without a word), A_cap 8 and 33 (the compaction crosses a 32-bit boundary), predict 0 / 1,
 # margin 0 / 0.5, with and without a base table.  Seeds chosen so the band holds at most 0.1 % of a case's (row, token) pairs
-# (tests/test_collision_masks_cpu.py checks that)
+# (tests/test_collision_masks_cpu.py checks that).  The dense case: 160 small boxes in a 16 m square, so that rows have more than LIST
+# obstacles within reach and the kernel's list overflows into further passes over the tokens (seed: the first from 33 on that the CPU
+# test accepts; with 33 a row's fallback decision hangs on a pair inside the band)
+LIST = 128           # RIDER_LIST of infgen_amd/csrc/kernels.h
 CASES = {
     'k2048_a8_p1_m0': dict(token_size=2048, A=8, predict=1, margin=0.0, base=False, seed=11),
     'k2048_a33_p1_m05_base': dict(token_size=2048, A=33, predict=1, margin=0.5, base=True, seed=12),
@@ -130,6 +133,7 @@ CASES = {
     'k64_a8_p1_m05': dict(token_size=64, A=8, predict=1, margin=0.5, base=False, seed=14),
     'k2048_a33_p0_m0': dict(token_size=2048, A=33, predict=0, margin=0.0, base=False, seed=15),
     'k2048_a8_p0_m05_base': dict(token_size=2048, A=8, predict=0, margin=0.5, base=True, seed=16),
+    'k64_a160_p1_m0_dense': dict(token_size=64, A=160, predict=1, margin=0.0, base=False, seed=34, dense=True),
 }
 T_CASE, C_CASE = 4, 2
 ORIGIN = np.array([5000.0, -5000.0])      # the 64 m square lies 5 km from the origin: the relative-frame rule matters
@@ -144,13 +148,16 @@ def thin_vocab(vocab, token_size):
 
 def make_case(name, vocab):
     """-> the arrays of an operator-level case.  Four scenes: 0 full (A rows; row 1 absent at c - 1, row 2 invalid at c, rows 3 and 6 in line), 1 one agent,
-    2 every row invalid, 3 a row boxed in on purpose (a 60 m box sits on it: every token collides, the fallback fires)."""
+    2 every row invalid, 3 a row boxed in on purpose (a 60 m box sits on it: every token collides, the fallback fires).
+    dense: the square is 16 m wide, column c - 1 at most 1 m behind, and every row of scene 0 is live with a 0.8 x 0.8 m box."""
     k = CASES[name]
+    dense = k.get('dense', False)
     rng = np.random.default_rng(k['seed'])
     A, K, S, T, c = k['A'], k['token_size'], 4, T_CASE, C_CASE
-    pos = (ORIGIN + rng.uniform(0.0, 64.0, (S, T, A, 2))).astype(np.float32)
+    side, step = (16.0, 1.0) if dense else (64.0, 3.0)
+    pos = (ORIGIN + rng.uniform(0.0, side, (S, T, A, 2))).astype(np.float32)
     # column c - 1 a short step behind column c, so the extrapolation stays inside the square's scale
-    pos[:, c - 1] = pos[:, c] - rng.uniform(-3.0, 3.0, (S, A, 2)).astype(np.float32)
+    pos[:, c - 1] = pos[:, c] - rng.uniform(-step, step, (S, A, 2)).astype(np.float32)
     head = rng.uniform(-np.pi, np.pi, (S, T, A)).astype(np.float32)
     head[:, c - 1] = head[:, c] + rng.uniform(-0.3, 0.3, (S, A)).astype(np.float32)
     # rows 3 and 6 of scene 0 (both vehicles) drive in line, 7 m apart: some of their tokens end inside the other's box, most do not
@@ -161,11 +168,13 @@ def make_case(name, vocab):
     state = np.ones((S, T, A), np.int32)
     n_agents = np.array([A, 1, min(A, 5), 2], np.int32)
     state[0, c - 1, 1] = INVALID
-    state[0, c, 2] = INVALID
+    state[0, c, 2] = 1 if dense else INVALID
     state[2] = INVALID
     atype = (np.arange(S * A).reshape(S, A) % 3).astype(np.int32)
     shape = np.stack([rng.uniform(3.5, 5.5, (S, A)), rng.uniform(1.6, 2.2, (S, A)), rng.uniform(1.4, 1.9, (S, A))], -1).astype(np.float32)
     shape[atype == 1, :2] = [0.8, 0.8]
+    if dense:
+        shape[0, :, :2] = [0.8, 0.8]
     pos[BOXED_SCENE, :, 1] = pos[BOXED_SCENE, :, 0]
     shape[BOXED_SCENE, 1, :2] = [60.0, 60.0]
     out = dict(k, pos=pos, head=head, state=state, n_agents=n_agents, atype=atype, shape=shape, c=c,
@@ -180,6 +189,22 @@ def make_case(name, vocab):
     else:
         out['base_rows'] = None
     return out
+
+
+def reachable(case):
+    """-> [A] obstacles within reach of every row of scene 0: centre distance <= own radius + the type's largest token displacement +
+    the obstacle's radius, obstacles at their extrapolated centres (what k_collision_mask puts on a row's list)"""
+    c, A = case['c'], case['A']
+    far = np.linalg.norm(token_end_poses(case['vocab'])[0], axis=-1).max(axis=1)
+    p = case['pos'][0].astype(np.float64)
+    here = case['state'][0, c] != INVALID
+    vel = here & (case['state'][0, c - 1] != INVALID) & bool(case['predict'])
+    q = p[c] + np.where(vel[:, None], p[c] - p[c - 1], 0.0)
+    rad = np.linalg.norm(0.5 * case['shape'][0, :, :2].astype(np.float64) + case['margin'], axis=-1)
+    own = np.linalg.norm(0.5 * case['shape'][0, :, :2].astype(np.float64), axis=-1)
+    dist = np.linalg.norm(q[None] - p[c][:, None], axis=-1)
+    near = (dist <= (own + far[case['atype'][0]])[:, None] + rad[None]) & here[None] & here[:, None] & ~np.eye(A, dtype=bool)
+    return near.sum(axis=1)
 
 
 def case_reference(case):

@@ -6,9 +6,9 @@ import torch
 
 import collision_ref as cr
 from conftest import load_case
+from rider_helpers import DEV, _emitted_in_sets, _make, _t, _weights
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 
 
 @pytest.fixture(scope='module')
@@ -18,10 +18,10 @@ def vocabs():
     return {2048: full, 64: cr.thin_vocab(full, 64)}
 
 
-def _op(case, dev=DEV):
+def _op(case):
     """the operator on a case of collision_ref.make_case -> (bits bool [rows][K], raw words, count)"""
     from infgen_amd import torch_ops  # noqa: F401
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t = _t
     end = torch_ops.collision_end_poses(t(case['vocab']))
     kw = {}
     if case['base_rows'] is not None:
@@ -68,7 +68,7 @@ def test_first_new_keeps_appended_rows_out(vocabs):
     """rows at or beyond first_new[s] are neither obstacles nor constrained: the sets equal those of a scene that ends there"""
     case = cr.make_case('k2048_a33_p0_m0', vocabs[2048])
     from infgen_amd import torch_ops
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    t = _t
     end = torch_ops.collision_end_poses(t(case['vocab']))
     first_new = np.array([20, 1, 2, 1], np.int32)
     args = lambda n, fn: (t(case['pos']), t(case['head']), t(case['state']), t(n), t(case['atype']), t(case['shape']), case['c'], end,
@@ -83,16 +83,6 @@ def test_first_new_keeps_appended_rows_out(vocabs):
 
 
 # ------------------------------------------------------------------------------------------ engine level
-def _weights(c, cfg=None):
-    from infgen_amd import engine
-    return engine.PackedWeights(c['sd'], cfg or c['cfg'], torch.device(DEV))
-
-
-def _make(c, w, scenes=None, **kw):
-    from infgen_amd import engine
-    return engine.RolloutEngine(w, scenes or [c['scene']], c['vocab'], c['map_vocab'], c['grid'], **kw)
-
-
 def _op_on_engine(eng, col, first_new=None, masks=None):
     """the operator applied to column col of the engine's state, with the engine's own shape array and end-pose table"""
     kw = {}
@@ -102,22 +92,6 @@ def _op_on_engine(eng, col, first_new=None, masks=None):
     return torch.ops.infgen_hip.collision_mask(eng.pos, eng.head, eng.state, eng.n_agents, eng.atype,
                                                eng._coll['shape'].view(eng.S, eng.A_cap, 3), col, eng._coll_end, conf['predict'],
                                                conf['margin'], first_new=first_new, **kw)
-
-
-def _emitted_in_sets(eng, col, bits, skip=None):
-    """every generated live row's token of column col + 1 lies in its set of column col; -> rows checked"""
-    K = eng.cfg.token_size
-    sets = cr.unpack(bits.cpu().numpy(), K).reshape(eng.S, eng.A_cap, K)
-    tok = eng.token[:, col + 1].cpu().numpy()
-    st0, st1 = eng.state[:, col].cpu().numpy(), eng.state[:, col + 1].cpu().numpy()
-    n = 0
-    for s in range(eng.S):
-        for r in range(eng.A_cap):
-            if st0[s, r] == 0 or st1[s, r] == 0 or tok[s, r] < 0 or (skip is not None and skip[s, r]):
-                continue
-            assert sets[s, r, tok[s, r]], (s, r, col, int(tok[s, r]))
-            n += 1
-    return n
 
 
 @pytest.mark.parametrize('sampled', [False, True], ids=['greedy', 'k5'])

@@ -9,9 +9,9 @@ import torch
 import collision_ref as cr
 import road_ref as rr
 from conftest import load_case
+from rider_helpers import _emitted_in_sets, _make, _t, _weights
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 
 
 @pytest.fixture(scope='module')
@@ -28,10 +28,6 @@ def _ref(name):
     K = rr.CASES[name]['token_size']
     case = rr.make_case(name, full if K == 2048 else rr.thin_vocab(full, K))
     return case, rr.case_reference(case)
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _op(case, first_new=None, n_agents=None):
@@ -123,16 +119,6 @@ def test_first_new_keeps_appended_rows_out():
 
 
 # ------------------------------------------------------------------------------------------ engine level
-def _weights(c, cfg=None):
-    from infgen_amd import engine
-    return engine.PackedWeights(c['sd'], cfg or c['cfg'], torch.device(DEV))
-
-
-def _make(c, w, scenes=None, **kw):
-    from infgen_amd import engine
-    return engine.RolloutEngine(w, scenes or [c['scene']], c['vocab'], c['map_vocab'], c['grid'], **kw)
-
-
 def _road_op(eng, col, base=None, first_new=None):
     """the operator applied to column col of the engine's state, with the engine's own tables; base: (bits, ident) of a per-row base"""
     from infgen_amd import torch_ops  # noqa: F401  (registers torch.ops.infgen_hip)
@@ -141,21 +127,6 @@ def _road_op(eng, col, base=None, first_new=None):
     return torch.ops.infgen_hip.road_mask(eng.pos, eng.head, eng.state, eng.n_agents, eng.atype, eng._road['shape'].view(eng.S, eng.A_cap, 3),
                                           col, eng._coll_end, eng._road_paths, eng.road_records, eng.road_n_records, eng.copies,
                                           conf['sweep'], conf['margin'], list(conf['types']), first_new=first_new, **kw)
-
-
-def _emitted_in_sets(eng, col, bits, skip=None):
-    K = eng.cfg.token_size
-    sets = cr.unpack(bits.cpu().numpy(), K).reshape(eng.S, eng.A_cap, K)
-    tok = eng.token[:, col + 1].cpu().numpy()
-    st0, st1 = eng.state[:, col].cpu().numpy(), eng.state[:, col + 1].cpu().numpy()
-    n = 0
-    for s in range(eng.S):
-        for r in range(eng.A_cap):
-            if st0[s, r] == 0 or st1[s, r] == 0 or tok[s, r] < 0 or (skip is not None and skip[s, r]):
-                continue
-            assert sets[s, r, tok[s, r]], (s, r, col, int(tok[s, r]))
-            n += 1
-    return n
 
 
 def _same_outputs(x, y):

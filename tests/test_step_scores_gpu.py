@@ -7,19 +7,15 @@ import pytest
 import torch
 
 import step_score_ref as R
+from rider_helpers import DEV, _make, _t, _weights
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda:0'
 
 
 @functools.lru_cache(maxsize=None)
 def _ref(name):
     case = R.make_case(name)
     return case, R.case_reference(case)
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 def _op(case, records=True):
@@ -84,16 +80,6 @@ def test_operator_without_a_record_table_and_its_refusals():
 
 
 # ------------------------------------------------------------------------------------------ engine level
-def _weights(c, cfg=None):
-    from infgen_amd import engine
-    return engine.PackedWeights(c['sd'], cfg or c['cfg'], torch.device(DEV))
-
-
-def _make(c, w, scenes=None, **kw):
-    from infgen_amd import engine
-    return engine.RolloutEngine(w, scenes or [c['scene']], c['vocab'], c['map_vocab'], c['grid'], **kw)
-
-
 def _op_on_engine(eng, t):
     """the operator applied to the engine's stored columns at c1 = 2 + t, with the engine's own shape array and road table"""
     sc = eng.step_scores
