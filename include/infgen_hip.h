@@ -49,6 +49,8 @@
  *   infgen_bundle_scores                               the same for all rollouts of all scenarios of a batch (:891-1103)
  *   infgen_state_accuracy, infgen_grid_overlap, infgen_traj_error, infgen_token_cls, infgen_average_meter,
  *   infgen_masked_cross_entropy                        the validation step's bookkeeping (infgen/utils/metrics.py) and open-loop loss
+ *   infgen_select_modes, infgen_multi_traj_error       K modes per agent from the copies' rollouts (batch_nms / new_batch_nms,
+ *                                                      infgen/utils/metrics.py:143-256) and minMultiADE / minMultiFDE (:339-427)
  *
  * Conventions: every pointer is a DEVICE pointer (fp32 / int32 / uint8) borrowed for the duration
  * of the call; outputs are pre-allocated by the caller; `stream` is a hipStream_t; nothing
@@ -1053,6 +1055,50 @@ int infgen_token_cls(const void* pred, int pred64, long long ld_pred, int n_gues
                      const unsigned char* mask, int R, long long* acc, void* stream);
 /* AverageMeter.update (infgen/utils/metrics.py:477-479): acc [2] = (float64 sum += sum of val [n], int64 count += n) */
 int infgen_average_meter(const float* val, long long n, void* acc, double* scratch, void* stream);
+/* minMultiADE.update (infgen/utils/metrics.py:403-424) and minMultiFDE.update (:349-361) in one pass, valid_filter (:115-140) and
+ * topk (:43-76, the plain form: no joint / ptr variants) included: pred [N][M][T][2], target [N][T][2], prob [N][M] or NULL,
+ * valid [N][T]; M <= 64.  A row takes part if any step is valid (keep_invalid_final_step != 0) or if its last step is (== 0).
+ * The guesses are all M modes when max_guesses >= M, else the max_guesses largest prob - PINNED: ties go to the lower index, where
+ * torch.topk leaves them open - or, without prob, the first max_guesses modes.  last = the last valid step.  FDE = the minimum
+ * over the guesses of the distance at `last`.  ADE, ade_criterion 0 ('FDE'): the masked mean distance of the guess with the
+ * smallest FDE - PINNED: the first minimum in guess order; 1 ('ADE'): the minimum over the guesses of the masked mean.
+ * ade_acc / fde_acc [2] = (float64 sum, int64 count += rows taking part), either may be NULL.  Distances and sums are float64. */
+int infgen_multi_traj_error(const float* pred, const float* target, const float* prob, const unsigned char* valid, int N, int M,
+                            int T, int max_guesses, int keep_invalid_final_step, int ade_criterion, void* ade_acc, void* fde_acc,
+                            double* scratch, void* stream);
+
+/* ---- modes: K representative futures per agent from N candidate trajectories (the copies of a scene) ----
+ * batch_nms (infgen/utils/metrics.py:198-256, mode 'static') and new_batch_nms (:143-195) in one launch: one wave per row, one
+ * candidate per lane, 1 <= N <= 64, 1 <= K <= min(N, 16); anything else is refused.
+ * Layout: row b < B is row r = b % rows_per_group of group g = b / rows_per_group; step t of its candidate j starts at
+ *   traj + g group_stride + r row_stride + j cand_stride + t step_stride   (strides in elements, step_stride >= F)
+ * and holds F floats, the first two (x, y).  A contiguous [B][N][T][F] is (rows_per_group 1, group_stride N T F, row_stride 0,
+ * cand_stride T F, step_stride F); a rollout's pred_traj [S0][copies][A_cap][R][2] is read in place with rows_per_group A_cap,
+ * group_stride copies A_cap R 2, row_stride R 2, cand_stride A_cap R 2, step_stride 2.
+ * Goal: (x, y) at step t_goal.  Score: score [B][N] (score_per_group != 0: [groups][N], every row of a group takes its group's),
+ * finite and >= 0 - or NULL: the density of new_batch_nms, float(count_j) / float(N) with count_j the valid candidates i, j
+ * included, whose goal is within dist_thresh of j's.
+ * PINNED by definition, where the reference leaves it open:
+ *   order      score descending, then candidate index ascending (argsort(descending=True) leaves ties open);
+ *   selection  K times: among the unselected valid candidates the largest value, value = score if the candidate is not covered
+ *              and 0 if it is, ties to the earlier candidate of the order; the pick is marked selected and every candidate whose
+ *              goal is within dist_thresh of the pick's - the pick included - covered.  For scores >= 0 this is the reference's
+ *              point_val bookkeeping (covered -> 0, selected -> negative, K <= N);
+ *   distance   fp32 sqrt(dx dx + dy dy) < dist_thresh: products and sum rounded separately, no contraction, square root and the
+ *              density's division correctly rounded;
+ *   validity   a candidate is valid unless cand_valid [B][N] (bytes, optional) is 0, or cand_state (optional, f32, addressed
+ *              g state_group_stride + r state_row_stride + j state_cand_stride + t_goal) equals state_invalid or state_enter, or
+ *              r >= row_limit[g limit_stride] (optional).  An invalid candidate is never picked, covers nothing and counts in no
+ *              density; a row with fewer than K valid candidates fills the rest with index -1, score 0 and a zero trajectory.
+ *              The reference has no mask: with every candidate valid the result is its result.
+ * Outputs: mode_idx [B][K] the candidate index, mode_score [B][K] the pick's own score (covered or not, as the reference returns
+ * it), mode_traj [B][K][T][F] (optional) the K winning trajectories, copied 16 bytes per lane where the addresses allow. */
+int infgen_select_modes(const float* traj, long long group_stride, long long row_stride, long long cand_stride, long long step_stride,
+                        int rows_per_group, long long B, int N, int T, int F, int t_goal, int K, float dist_thresh,
+                        const float* score, int score_per_group, const unsigned char* cand_valid, const float* cand_state,
+                        long long state_group_stride, long long state_row_stride, long long state_cand_stride, float state_invalid,
+                        float state_enter, const int* row_limit, long long limit_stride, int* mode_idx, float* mode_score,
+                        float* mode_traj, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1037,6 +1037,57 @@ extern "C" int infgen_traj_error(const float* pred, const float* target, const u
   return check_launch(me);
 }
 
+// minMultiADE.update (infgen/utils/metrics.py:403-424) and minMultiFDE.update (:349-361)
+extern "C" int infgen_multi_traj_error(const float* pred, const float* target, const float* prob, const unsigned char* valid, int N,
+                                      int M, int T, int max_guesses, int keep_invalid_final_step, int ade_criterion, void* ade_acc,
+                                      void* fde_acc, double* scratch, void* stream) {
+  const char* me = "infgen_multi_traj_error";
+  if (N < 0) return fail(me, "N is negative");
+  if (T < 1) return fail(me, "T must be at least 1");
+  if (M < 1 || M > MTE_MAX_MODES) return fail(me, "M must be in 1..64");
+  if (max_guesses < 1) return fail(me, "max_guesses must be at least 1");
+  if (ade_criterion != 0 && ade_criterion != 1) return fail(me, "ade_criterion must be 0 ('FDE') or 1 ('ADE')");
+  if (!ade_acc && !fde_acc) return fail(me, "both accumulators are NULL");
+  if (!scratch) return fail(me, "scratch is NULL");
+  if (N == 0) return 0;
+  if (!pred || !target || !valid) return fail(me, "pred, target or valid is NULL");
+  const int nb = vm_blocks(N, 256);
+  MultiTrajErrArgs a{pred, target, prob, valid, N, M, T, max_guesses < M ? max_guesses : M, keep_invalid_final_step ? 1 : 0,
+                     ade_criterion, ade_acc ? (unsigned long long*)ade_acc + 1 : nullptr,
+                     fde_acc ? (unsigned long long*)fde_acc + 1 : nullptr, scratch};
+  hipLaunchKernelGGL(k_multi_traj_error, dim3(nb), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(k_vm_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, 2, (double*)ade_acc,
+                     (double*)fde_acc, (double*)nullptr);
+  return check_launch(me);
+}
+
+// batch_nms / new_batch_nms (infgen/utils/metrics.py:198-256, :143-195): "modes" of include/infgen_hip.h
+extern "C" int infgen_select_modes(const float* traj, long long group_stride, long long row_stride, long long cand_stride,
+                                  long long step_stride, int rows_per_group, long long B, int N, int T, int F, int t_goal, int K,
+                                  float dist_thresh, const float* score, int score_per_group, const unsigned char* cand_valid,
+                                  const float* cand_state, long long state_group_stride, long long state_row_stride,
+                                  long long state_cand_stride, float state_invalid, float state_enter, const int* row_limit,
+                                  long long limit_stride, int* mode_idx, float* mode_score, float* mode_traj, void* stream) {
+  const char* me = "infgen_select_modes";
+  if (B < 0) return fail(me, "B is negative");
+  if (N < 1 || N > SM_MAX_CAND) return fail(me, "N must be in 1..64 (one candidate per lane of a wave)");
+  if (K < 1 || K > SM_MAX_MODES || K > N) return fail(me, "K must be in 1..min(N, 16)");
+  if (T < 1 || F < 2) return fail(me, "T must be at least 1 and F at least 2 (x, y)");
+  if (t_goal < 0 || t_goal >= T) return fail(me, "t_goal must be in 0..T-1");
+  if (rows_per_group < 1) return fail(me, "rows_per_group must be at least 1");
+  if (step_stride < F || group_stride < 0 || row_stride < 0 || cand_stride < 0) return fail(me, "a stride is negative or step_stride < F");
+  if (!(dist_thresh == dist_thresh)) return fail(me, "dist_thresh is NaN");
+  if (!mode_idx || !mode_score) return fail(me, "mode_idx or mode_score is NULL");
+  if (B == 0) return 0;
+  if (!traj) return fail(me, "traj is NULL");
+  if (B > 4ll * 0x7fffffffll) return fail(me, "too many rows");
+  SelectModesArgs a{traj, group_stride, row_stride, cand_stride, step_stride, rows_per_group, B, N, T, F, t_goal, K, dist_thresh,
+                    score, score_per_group ? 1 : 0, cand_valid, cand_state, state_group_stride, state_row_stride, state_cand_stride,
+                    state_invalid, state_enter, row_limit, limit_stride, mode_idx, mode_score, mode_traj};
+  hipLaunchKernelGGL(k_select_modes, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
 // pred[mask] + nn.CrossEntropyLoss (infgen/model/infgen.py:147-152, :644, :655)
 extern "C" int infgen_masked_cross_entropy(const float* logits, long long ld, const void* target, int target64,
                                           const unsigned char* mask, const float* weight, int R, int C, float label_smoothing,

@@ -853,5 +853,31 @@ template <bool T64> __global__ void k_masked_ce(MaskedCeArgs a);
 template <bool P64, bool T64> __global__ void k_token_cls(TokenClsArgs a);
 __global__ void k_vm_sum(const float* val, long long n, double* partials, unsigned long long* count);   // AverageMeter: partial sums; *count += n
 __global__ void k_vm_finish(const double* partials, int nb, int K, double* dst0, double* dst1, double* dst2);
+constexpr int MTE_MAX_MODES = 64;    // modes per row of k_multi_traj_error (the top-k's taken set is one 64-bit word)
+struct MultiTrajErrArgs {            // k_multi_traj_error (minMultiFDE.update / minMultiADE.update)
+  const float* pred; const float* target; const float* prob; const unsigned char* valid;   // [N][M][T][2], [N][T][2], [N][M] or null, [N][T]
+  int N, M, T, G;                                           // G: guesses used, 1 <= G <= M
+  int keep_invalid_final_step, ade_by_ade;                  // row filter: any valid step / the last step; ADE criterion: 0 'FDE', 1 'ADE'
+  unsigned long long* ade_count; unsigned long long* fde_count;             // slot 1 of the two accumulators; either may be null
+  double* partials;                                                         // [gridDim.x][2]: ade, fde
+};
+__global__ void k_multi_traj_error(MultiTrajErrArgs a);
+
+// modes from a scene's rollouts (mode_kernels.hip; reference batch_nms / new_batch_nms).  Row b = group g = b / rows_per_group, row
+// r = b % rows_per_group of it; candidate j's step t starts at traj + g group_stride + r row_stride + j cand_stride + t step_stride
+// (elements), F contiguous floats of which the first two are (x, y).
+constexpr int SM_MAX_CAND = 64, SM_MAX_MODES = 16;
+struct SelectModesArgs {             // k_select_modes
+  const float* traj; long long group_stride, row_stride, cand_stride, step_stride;
+  int rows_per_group; long long B; int N, T, F, t_goal, K;
+  float dist_thresh;
+  const float* score; int score_per_group;                  // [B][N] ([groups][N] with score_per_group), or null: density
+  const unsigned char* cand_valid;                          // [B][N] or null
+  const float* cand_state; long long state_group_stride, state_row_stride, state_cand_stride;   // optional: state at t_goal, unit step stride
+  float state_invalid, state_enter;
+  const int* row_limit; long long limit_stride;             // optional: row r of group g is valid while r < row_limit[g limit_stride]
+  int* mode_idx; float* mode_score; float* mode_traj;       // [B][K], [B][K], [B][K][T][F] or null
+};
+__global__ void k_select_modes(SelectModesArgs a);
 
 }  // namespace ig

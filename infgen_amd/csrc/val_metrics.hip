@@ -3,6 +3,7 @@
 //                      first enter / first (part 2: last) exit column, popcounts for the slices
 //   k_grid_overlap     GridOverlapRate.update (:574-591): one workgroup per (group, step), two LDS bitmaps over the grid cells
 //   k_traj_error       minADE.update (:441-464) and minFDE.update (:378-387) in one pass
+//   k_multi_traj_error minMultiADE.update (:403-424) and minMultiFDE.update (:349-361) in one pass, with valid_filter and topk
 //   k_masked_ce        pred[mask] + torch.nn.CrossEntropyLoss (weights, label smoothing) without the gather: one wave per row
 //   k_token_cls        TokenCls.update (:326-333)
 //   k_vm_sum           AverageMeter.update (:477-479)
@@ -212,6 +213,69 @@ __global__ __launch_bounds__(256) void k_traj_error(TrajErrArgs a) {
     const long long na = s_c[0][0] + s_c[1][0] + s_c[2][0] + s_c[3][0], nf = s_c[0][1] + s_c[1][1] + s_c[2][1] + s_c[3][1];
     if (a.ade_count && na) atomicAdd(a.ade_count, (unsigned long long)na);
     if (a.fde_count && nf) atomicAdd(a.fde_count, (unsigned long long)nf);
+  }
+}
+
+// --------------------------------------------------------------------------------------------------- minMultiFDE / minMultiADE
+// minMultiFDE.update (:349-361) and minMultiADE.update (:403-424) in one pass, k_traj_error's accumulation scheme.  A row takes part
+// if any step is valid (keep_invalid_final_step) or if its last step is (valid_filter :115-140).  The guesses are the G largest
+// prob in (prob descending, index ascending) order - torch.topk leaves ties open, this pins them - or the first G modes without
+// prob (topk :43-76); last = the last valid step (argmax of valid * arange(1..T)).  FDE = the minimum over the guesses of the
+// distance at `last`; ADE = the masked mean distance of the guess with the smallest FDE (first minimum in guess order), or
+// (ade_by_ade) the minimum over the guesses of the masked mean.
+__global__ __launch_bounds__(256) void k_multi_traj_error(MultiTrajErrArgs a) {
+  __shared__ double s_red[256];
+  __shared__ long long s_c[4];
+  const int tid = threadIdx.x, T = a.T, M = a.M, G = a.G;
+  double ade = 0.0, fde = 0.0;
+  int cnt = 0;
+  for (long long row = (long long)blockIdx.x * 256 + tid; row < a.N; row += (long long)gridDim.x * 256) {
+    const unsigned char* v = a.valid + (size_t)row * T;
+    int last = -1, nv = 0;
+    for (int t = 0; t < T; ++t)
+      if (v[t]) { last = t; ++nv; }
+    if (a.keep_invalid_final_step ? nv == 0 : v[T - 1] == 0) continue;
+    const float* q = a.target + (size_t)row * T * 2;
+    const float* pr = a.prob ? a.prob + (size_t)row * M : nullptr;
+    const bool pick = pr && G < M;
+    unsigned long long taken = 0ull;
+    double best_f = 0.0, ade_of_best_f = 0.0, best_a = 0.0;
+    for (int gi = 0; gi < G; ++gi) {
+      int m = gi;
+      if (pick) {
+        m = -1;
+        float pm = 0.f;
+        for (int j = 0; j < M; ++j)
+          if (!((taken >> j) & 1ull) && (m < 0 || pr[j] > pm)) { m = j; pm = pr[j]; }
+        taken |= 1ull << m;
+      }
+      const float* p = a.pred + ((size_t)row * M + m) * T * 2;
+      double s = 0.0, f = 0.0;
+      for (int t = 0; t < T; ++t) {
+        const double dx = (double)p[2 * t] - (double)q[2 * t], dy = (double)p[2 * t + 1] - (double)q[2 * t + 1];
+        const double d = sqrt(dx * dx + dy * dy);
+        if (v[t]) s += d;
+        if (t == last) f = d;
+      }
+      const double mean = s / (double)nv;
+      if (gi == 0 || f < best_f) { best_f = f; ade_of_best_f = mean; }
+      if (gi == 0 || mean < best_a) best_a = mean;
+    }
+    fde += best_f;
+    ade += a.ade_by_ade ? best_a : ade_of_best_f;
+    ++cnt;
+  }
+  const double ade_b = block_sum(ade, s_red);
+  const double fde_b = block_sum(fde, s_red);
+  cnt = wave_sum(cnt);
+  if ((tid & 63) == 0) s_c[tid >> 6] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    a.partials[(size_t)blockIdx.x * 2] = ade_b;
+    a.partials[(size_t)blockIdx.x * 2 + 1] = fde_b;
+    const long long n = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+    if (a.ade_count && n) atomicAdd(a.ade_count, (unsigned long long)n);
+    if (a.fde_count && n) atomicAdd(a.fde_count, (unsigned long long)n);
   }
 }
 

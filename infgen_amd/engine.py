@@ -20,7 +20,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, constraints, logprob, packing, scene_setup
+from . import _lib, constraints, logprob, modes, packing, scene_setup
 from .scene_setup import EVAL_SHAPE, INVALID_SHAPE
 from .synth import INVALID, VALID, ENTER, EXIT, AGENT_SHAPE, RolloutConfig
 
@@ -2569,6 +2569,54 @@ class RolloutEngine:
         """[S] float64 on the device: every scene's masked sum of ``next_token_sample_logprob``, as ``rollout_logprob`` sums"""
         assert getattr(self, '_rollout_slp', None) is not None, 'needs sample_logprob=True and an outputs_device() / outputs_batch() call'
         return self._rollout_slp
+
+    def _initial_rows(self):
+        """(int32 device tensor, stride): entry ``s * stride`` is scene s's initial agent count - no device work after the first
+        call for a batch"""
+        c = getattr(self, '_n0_dev', None)
+        if c is None or c[0] != self._reload_gen:
+            if self._batch_lay is not None:
+                c = (self._reload_gen, self._ing['counts'], 3)            # [S][3]: kept rows first
+            else:
+                c = (self._reload_gen, torch.tensor([h['A'] for h in self.hosts], dtype=torch.int32).to(self.device), 1)
+            self._n0_dev = c
+        return c[1], c[2]
+
+    def select_modes(self, k: int = 6, dist_thresh: float = 2.5, scores='density', t_goal: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """K representative futures per agent out of the ``copies`` rollouts of its scene, after a rollout with ``copies > 1``
+        (``infgen_amd.modes``; "modes" of include/infgen_hip.h): candidate j of row a is agent a in copy j, its goal the (x, y) of
+        ``pred_traj`` at step ``t_goal`` (None: the last of the R steps).  ``pred_traj`` is read in place - one launch, nothing
+        read on the host.  A candidate is valid if its ``pred_state`` at ``t_goal`` is neither INVALID nor ENTER and the row is
+        below the scene's initial agent count: with scenario insertion only the initial rows are the same agent in every copy, so
+        rows at or above that count return index -1.  ``scores``: 'density' (the share of valid copies whose goal lies within
+        ``dist_thresh``), 'logprob' (the softmax over the copies of the scene-level ``rollout_logprob()``, for every row; needs
+        ``token_logprob=True`` and an ``outputs_device()`` / ``outputs_batch()`` call) or a tensor [S0, copies] >= 0.
+        -> dict of device tensors: ``mode_idx`` [S0, A_cap, k] int32 (the copy; -1: none), ``mode_score``, ``mode_prob`` (the scores
+        renormalised over the k slots), ``mode_traj`` [S0, A_cap, k, R, 2].  Tokens, poses and logits of the rollout are untouched.
+        Before anything has run on the current batch (a new engine, or after a reload) the call raises RuntimeError."""
+        modes.check_engine_args(self.copies, k, scores)
+        if not self._prologue_done:
+            raise RuntimeError('select_modes reads the pred_traj a rollout leaves behind: nothing has run on the current batch yet '
+                               '(call rollout() first; a reload outdates the previous batch\'s rollout)')
+        n, S0, A_cap, R, dev = self.copies, self.S0, self.A_cap, self.R, self.device
+        t = R - 1 if t_goal is None else int(t_goal)
+        if not -R <= t < R:
+            raise ValueError(f't_goal = {t_goal} is outside the {R} predicted steps')
+        sc = None
+        if isinstance(scores, str) and scores == 'logprob':
+            if self.token_logprob is None:
+                raise ValueError("scores='logprob' needs an engine built with token_logprob=True")
+            sc = torch.softmax(self.rollout_logprob().view(S0, n), dim=1).to(torch.float32).contiguous()
+        elif torch.is_tensor(scores):
+            if tuple(scores.shape) != (S0, n):
+                raise ValueError(f'scores must be [scenes, copies] = {(S0, n)}, not {tuple(scores.shape)}')
+            sc = scores.to(dev, torch.float32).contiguous()
+        n0, n0_stride = self._initial_rows()
+        traj = self.pred_traj.view(S0, n, A_cap, R, 2).permute(0, 2, 1, 3, 4)              # [S0, A_cap, copies, R, 2], in place
+        state = self.pred_state.view(S0, n, A_cap, R).permute(0, 2, 1, 3)
+        out, score, idx = modes.launch(traj, int(k), dist_thresh, t % R, scores=sc, score_per_group=True, cand_state=state,
+                                       state_values=(float(INVALID), float(ENTER)), row_limit=n0, limit_stride=n0_stride * n)
+        return dict(mode_idx=idx, mode_score=score, mode_prob=modes.mode_prob(score, idx), mode_traj=out)
 
     def agent_steps(self) -> int:
         """agent-steps (10 Hz) decoded by the last full rollout of this batch (the rows decoded at every step, incl. the

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import _lib, logprob, scene_setup
+from .. import _lib, logprob, modes, scene_setup
 from ..closed_loop import ClosedLoopSession
 from ..constraints import (TokenMasks, check_avoid_collisions, check_stay_on_road, check_step_scores, check_type_selectors, road_key,
                            score_key)
@@ -672,6 +672,7 @@ class InfGenDecoder(nn.Module):
         mk = self._map_keys(eng, datas) if xo is None else None
         # per-scene dicts of device tensors (no host round trip of the results), detached from the engine's buffers
         outs = eng.outputs_device(detach=True)
+        self._last_engine = eng                 # (predict_modes reads the copies' pred_traj where the rollout left it)
         zero = {}                              # shared (read-only) zero tensors of the seed outputs a batch does not record
 
         def zeros(shape):
@@ -840,6 +841,7 @@ class InfGenDecoder(nn.Module):
         # the layout's unfiltered maximum, which the offsets give on the host, and so is the retry's head-room)
         eng = yield from _rollout_or_yield(self._engines, ekey, eng, make_engine, lay['amax'], limit, session, self._guided(copies))
         outs = eng.outputs_batch()
+        self._last_engine = eng
         n_fin, c = eng.batch_counts()
         dev = w.device
         # the map-token head once per graph, one launch: the predicted rows of the Batch in graph order (graph g's token p sits at
@@ -1017,6 +1019,30 @@ class InfGenDecoder(nn.Module):
         return self.inference_batch([data.clone() if hasattr(data, 'clone') else dict(data)], seed_outputs=True, copies=int(n),
                                     replay=replay, replay_plan=replay_plan, sample_temperature=sample_temperature,
                                     sample_uniforms=sample_uniforms)
+
+    @torch.no_grad()
+    def predict_modes(self, data, n: int, k: int = 6, dist_thresh: float = 2.5, scores='density', **rollout_kwargs):
+        """K representative futures per agent with probabilities - the 6-mode output of WOMD-style motion prediction - from ``n``
+        rollouts of the scene: ``inference_rollouts(data, n, **rollout_kwargs)``, then ``RolloutEngine.select_modes`` on the
+        copies where the rollout left them (one launch; ``infgen_amd.modes``).  ``scores``: 'density' or 'logprob' (needs
+        ``token_logprob``).  -> per graph a dict of ``agent_id`` [A], ``pred_traj_modes`` [A, k, R, 2], ``pred_prob_modes`` [A, k]
+        and ``mode_idx`` [A, k] (the rollout a mode came from; -1: fewer than k rollouts hold the agent at the goal step) over
+        the graph's A initial agents: one dict for a single graph, a list for a multi-graph ``Batch``."""
+        modes.check_engine_args(int(n), k, scores)
+        B = num_graphs(data)
+        self._last_engine = None                # (set by the rollout path that runs below: a stale engine is never read)
+        self.inference_rollouts(data, int(n), **rollout_kwargs)
+        eng = self._last_engine
+        if eng is None:
+            raise RuntimeError('predict_modes: the rollout path did not hand over its engine')
+        m = eng.select_modes(k=k, dist_thresh=dist_thresh, scores=scores)
+        ids = eng._epi['ids']
+        res = []
+        for g in range(B):
+            A = int(eng.hosts[g * eng.copies]['A'])
+            res.append(dict(agent_id=ids[g * eng.copies, :A], pred_traj_modes=m['mode_traj'][g, :A],
+                            pred_prob_modes=m['mode_prob'][g, :A], mode_idx=m['mode_idx'][g, :A]))
+        return res if B > 1 else res[0]
 
     @torch.no_grad()
     def inference_batch(self, datas: Sequence, seed_outputs: bool = False, copies: int = 1, replay=None,

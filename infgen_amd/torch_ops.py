@@ -34,6 +34,7 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.branch_scenes(ctx_bytes, t, parent (S,) int)                       -> n_bad (1,) int32; slot s := slot parent[s]
     torch.ops.infgen_hip.snapshot_scenes(ctx_bytes, t, slots (n,) int, snap (n, stride) uint8, head (n, 4) int32) -> n_bad; entry e := slot slots[e]
     torch.ops.infgen_hip.restore_scenes(ctx_bytes, t, index (S,) int, snap, head)           -> n_bad (1,) int32; slot s := entry index[s]
+    torch.ops.infgen_hip.select_modes(traj (B, N, T, F), k, dist_thresh, scores?, valid?, t_goal=-1) -> mode_traj, mode_score, mode_idx (B, k)
 
 (``decode_step`` works on the persistent state block ``InfgenRollout`` of include/infgen_hip.h, which ``RolloutEngine.ctx_tensor()``
 hands out as bytes; whole rollouts stay a C-ABI call, ``infgen_rollout_run``, driven by infgen_amd/engine.py).  ``register_fake`` gives every op a shape function, so they trace under
@@ -813,3 +814,20 @@ def _(valid, collision, linear_speed, linear_acceleration, angular_speed, angula
     W = (valid.shape[2] - size) // step + 1
     f = lambda *shape: valid.new_empty(*shape, dtype=torch.float32)
     return f(n_scenario, 13), f(n_scenario, 12, W), f(valid.shape[0], 2, W), valid.new_empty(3, dtype=torch.int32)
+
+
+@torch.library.custom_op('infgen_hip::select_modes', mutates_args=())
+def select_modes(traj: torch.Tensor, k: int = 6, dist_thresh: float = 2.5, scores: Optional[torch.Tensor] = None,
+                 valid: Optional[torch.Tensor] = None, t_goal: int = -1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """K modes per row out of N candidate trajectories (the reference's batch_nms / new_batch_nms; ``infgen_select_modes``,
+    "modes" of include/infgen_hip.h): ``traj`` (B, N, T, F) read in place, ``scores`` (B, N) >= 0 or None (the goals' density),
+    ``valid`` (B, N) or None -> mode_traj (B, k, T, F), mode_score (B, k), mode_idx (B, k) int32 (-1: fewer than k valid candidates)"""
+    from . import modes
+    return modes.select_modes(traj, k=int(k), dist_thresh=float(dist_thresh), scores=scores, valid=valid, t_goal=int(t_goal))
+
+
+@select_modes.register_fake
+def _(traj, k=6, dist_thresh=2.5, scores=None, valid=None, t_goal=-1):
+    lead = tuple(traj.shape[:-3])
+    return (traj.new_empty(lead + (k,) + tuple(traj.shape[-2:]), dtype=torch.float32), traj.new_empty(lead + (k,), dtype=torch.float32),
+            traj.new_empty(lead + (k,), dtype=torch.int32))

@@ -14,10 +14,13 @@ return float64 where the reference returns float32.  The product path has no hos
 Index tensors may be int32 or int64, masks bool or uint8 - what ``InfGenDecoder.inference`` / ``forward`` / ``fetch_enterings``
 deliver - and are read in place (a view with a unit inner stride included); any other mask dtype is converted to uint8 first.
 
+``minMultiADE`` / ``minMultiFDE`` (:339-427; nothing in the reference's validation constructs them, a user of many rollouts per
+scene does) run ``valid_filter`` and the plain ``topk`` inside their one kernel, ``k_multi_traj_error``; their ``update`` takes the
+K modes ``infgen_amd.modes`` selects - the reference's ``batch_nms`` / ``new_batch_nms`` live there, not in this module.
+
 Left out on purpose:
-  * ``topk``, ``valid_filter``, ``batch_nms``, ``batch_nms_token`` (the NMS / top-k helpers): only ``minMultiADE`` / ``minMultiFDE``
-    call them, and
-  * ``minMultiADE`` / ``minMultiFDE``: nothing in the reference's validation constructs them (infgen/model/infgen.py:136-143).
+  * ``batch_nms_token`` and ``batch_nms(mode='speed')``: ``infgen_amd.modes`` raises NotImplementedError naming them.
+  * the joint / ``ptr`` variants of ``topk`` (:58-67) and ``topkind``: nothing in the reference calls them.
   * the ``val_insert`` branch (infgen/model/infgen.py:688-700): it calls ``NumInsertAccuracy.update`` with keyword names the method
     does not have and the attribute is commented out at :144 - the class is mirrored, the branch is not.
   * ``CustomCrossEntropyLoss``: ``masked_cross_entropy(label_smoothing=...)`` covers it.
@@ -194,6 +197,76 @@ class minADE(_TrajMetric):
                valid_mask: Optional[torch.Tensor] = None, keep_invalid_final_step: bool = True,
                min_criterion: str = 'ADE') -> None:
         update_traj_metrics(self, None, pred, target, valid_mask)
+
+
+_MIN_CRITERIA = {'FDE': 0, 'ADE': 1}
+
+
+def update_multi_traj_metrics(ade: Optional['minMultiADE'], fde: Optional['minMultiFDE'], pred: torch.Tensor, target: torch.Tensor,
+                              prob: Optional[torch.Tensor] = None, valid_mask: Optional[torch.Tensor] = None,
+                              keep_invalid_final_step: bool = True, min_criterion: str = 'FDE') -> None:
+    """``minMultiADE.update`` and ``minMultiFDE.update`` of the same arguments in ONE pass over pred [N, M, T, 2], target [N, T, 2],
+    prob [N, M] or None, valid_mask [N, T] or None (all valid); ``max_guesses`` is the ADE object's (the FDE object's without one)"""
+    if min_criterion not in _MIN_CRITERIA:
+        raise ValueError('{} is not a valid criterion'.format(min_criterion))
+    dev = _dev(pred, 'pred')
+    _dev(target, 'target')
+    if pred.dim() != 4 or pred.shape[-1] != 2 or target.dim() != 3 or tuple(target.shape) != (pred.shape[0],) + tuple(pred.shape[2:]):
+        raise InfgenHipError(f'need pred [N, M, T, 2] and target [N, T, 2], got {tuple(pred.shape)}, {tuple(target.shape)}')
+    N, M, T = (int(v) for v in pred.shape[:3])
+    if valid_mask is None:
+        valid_mask = torch.ones(N, T, dtype=torch.bool, device=dev)
+    if tuple(valid_mask.shape) != (N, T) or (prob is not None and tuple(prob.shape) != (N, M)):
+        raise InfgenHipError(f'need valid_mask [N, T] = {(N, T)} and prob [N, M] = {(N, M)}, got {tuple(valid_mask.shape)}'
+                             + ('' if prob is None else f', {tuple(prob.shape)}'))
+    p, q = pred.to(torch.float32).contiguous(), target.to(torch.float32).contiguous()
+    v = _bytes(valid_mask, 'valid_mask', dev).contiguous()
+    w = None
+    if prob is not None:
+        _dev(prob, 'prob')
+        w = prob.to(torch.float32).contiguous()
+    owner = ade if ade is not None else fde
+    _lib.check(_lib.load().infgen_multi_traj_error(p.data_ptr(), q.data_ptr(), w.data_ptr() if w is not None else None, v.data_ptr(),
+                                                   N, M, T, int(owner.max_guesses), int(bool(keep_invalid_final_step)),
+                                                   _MIN_CRITERIA[min_criterion],
+                                                   ade._state_buf(dev).data_ptr() if ade is not None else None,
+                                                   fde._state_buf(dev).data_ptr() if fde is not None else None,
+                                                   owner._scratch_buf(dev).data_ptr(), _stream(dev)), 'infgen_multi_traj_error')
+
+
+class _MultiTrajMetric(_DeviceMetric):
+    _slots = 2
+    _float_slots = (0,)
+
+    def __init__(self, max_guesses: int = 6, **kwargs) -> None:
+        super().__init__(**kwargs)
+        self.max_guesses = max_guesses
+
+    sum = property(lambda self: self._state_buf().view(torch.float64)[0])
+    count = property(lambda self: self._state_buf()[1])
+
+    def compute(self) -> torch.Tensor:
+        b = self._state_buf()
+        return b.view(torch.float64)[0] / b[1]
+
+
+class minMultiFDE(_MultiTrajMetric):
+    """reference :339-364: over the rows ``valid_filter`` keeps, the minimum over the ``max_guesses`` most probable modes of the
+    distance at the row's last valid step (``topk`` ties: the lower index)"""
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor, prob: Optional[torch.Tensor] = None,
+               valid_mask: Optional[torch.Tensor] = None, keep_invalid_final_step: bool = True) -> None:
+        update_multi_traj_metrics(None, self, pred, target, prob, valid_mask, keep_invalid_final_step)
+
+
+class minMultiADE(_MultiTrajMetric):
+    """reference :393-427: the masked mean distance of the guess with the smallest final error (``min_criterion='FDE'``, first
+    minimum) or the smallest masked mean over the guesses (``'ADE'``); any other criterion raises ValueError like the reference"""
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor, prob: Optional[torch.Tensor] = None,
+               valid_mask: Optional[torch.Tensor] = None, keep_invalid_final_step: bool = True,
+               min_criterion: str = 'FDE') -> None:
+        update_multi_traj_metrics(self, None, pred, target, prob, valid_mask, keep_invalid_final_step, min_criterion)
 
 
 class AverageMeter(_DeviceMetric):
