@@ -543,12 +543,27 @@ extern "C" int infgen_set_attn_mode(int mode) {
 // the kernels of the other split families (k_heads_h, k_mlpemb_h) keep the by-size rule of the 64-row tiles
 static inline bool attn_split_for(int mode, int rows) { return mode == 1 || (mode >= 2 && rows > ATTN_SPLIT_ROWS); }
 static inline bool attn_split(int rows) { return attn_split_for(O().attn_mode, rows); }
-// the by-size rule of top-k sampling: inside the split heads kernel (k_heads_h<TERMS, LP, HEADS_KS>, no logits in memory) where that
-// kernel runs and the beam fits its lists; elsewhere k_sample_topk over stored logits.  One rule for infgen_heads_sample,
-// infgen_decode_step, validate() and, through infgen_heads_sample_fused, the engine
-static inline bool heads_sample_fused_for(int mode, int rows, int k) { return k > 1 && k <= HEADS_KS && attn_split_for(mode, rows); }
-extern "C" int infgen_heads_sample_fused(int attn_mode, int rows, int k) { return heads_sample_fused_for(attn_mode, rows, k) ? 1 : 0; }
-extern "C" int infgen_heads_logprob_fused(int attn_mode, int rows) { return attn_split_for(attn_mode, rows) ? 1 : 0; }
+// How one emission - heads, the draw, the log-probabilities - runs: the one statement of its by-size rules.  Every entry that emits
+// motion tokens, validate() and, through the two exported queries, the engine read it; emit_tokens issues what it names
+struct EmitPlan {
+  bool split;          // the heads run as the split kernel (k_heads_h, 64-row tiles), else as k_heads (fp32 MFMA)
+  bool sample_fused;   // the top-k draw runs inside the split kernel (k_heads_h<TERMS, LP, HEADS_KS>): it runs and the beam fits its lists
+  bool lp_fused;       // token_logprob comes out of the split kernel: beside the arg-max, or beside the draw made inside it
+  bool need_logits;    // the chain reads logits [rows][token_size] from memory: k_sample_topk and / or k_token_logprob after the heads
+  int ns;              // the workgroups per row tile that share k_heads' logit chunks (1: no column split, no keys)
+};
+// k <= 1: arg-max; col_split: keys for k_heads' column split are there and INFGEN_HEADS_NOSPLIT is off.  Pure: it reads nothing but
+// its arguments (attn_mode is the caller's: O()'s, or a context's own) and launches nothing
+static EmitPlan emit_plan(int attn_mode, int rows, int token_size, int k, bool want_token_lp, bool col_split) {
+  const bool split = attn_split_for(attn_mode, rows), sample_fused = k > 1 && k <= HEADS_KS && split;
+  const bool lp_fused = want_token_lp && (k > 1 ? sample_fused : split);      // (after k_sample_topk only the chain knows the token)
+  const int tiles = ceil_div(rows, TR), nchunk = token_size / 128;
+  int ns = 1;
+  while (col_split && !split && 2 * ns <= nchunk && nchunk % (2 * ns) == 0 && tiles * 2 * ns <= 512) ns *= 2;
+  return EmitPlan{split, sample_fused, lp_fused, (k > 1 && !sample_fused) || (want_token_lp && !lp_fused), ns};
+}
+extern "C" int infgen_heads_sample_fused(int attn_mode, int rows, int k) { return emit_plan(attn_mode, rows, 0, k, false, false).sample_fused; }
+extern "C" int infgen_heads_logprob_fused(int attn_mode, int rows) { return emit_plan(attn_mode, rows, 0, 1, true, false).lp_fused; }
 // 0: fp32 kernels, 1: k_attn_h, 2: k_attn_hs
 static inline int attn_kind(int rows) {
   switch (O().attn_mode) {
@@ -1157,20 +1172,15 @@ template <bool MK> static auto heads_h_kernel(const HeadsArgs& a) {
       : (a.token_logprob ? by_terms(k_heads_h<3, true, 0, MK>, k_heads_h_b16<1, true, 0, MK>, k_heads_h<1, true, 0, MK>)
                          : by_terms(k_heads_h<3, false, 0, MK>, k_heads_h_b16<1, false, 0, MK>, k_heads_h<1, false, 0, MK>));
 }
-template <class A> static Masked<A> with_mask(const A& a, const TokenMaskCtl& mask) {
+// a kernel with a <MK> instantiation pair: the unmasked one with its block as it was, or, where a mask is set, the masked one
+// with the mask appended to the block
+template <class KM, class KU, class A>
+static void launch_masked(KM masked, KU unmasked, dim3 grid, dim3 block, const A& a, const TokenMaskCtl& mask, void* stream) {
   Masked<A> m;
   static_cast<A&>(m) = a;
   m.mask = mask;
-  return m;
-}
-static void launch_heads_h(const HeadsArgs& a, const TokenMaskCtl& mask, void* stream) {
-  if (mask.bits) hipLaunchKernelGGL(heads_h_kernel<true>(a), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, with_mask(a, mask));
-  else hipLaunchKernelGGL(heads_h_kernel<false>(a), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
-}
-// k_heads (fp32, few rows)
-static void launch_heads_fp32(const HeadsArgs& a, const TokenMaskCtl& mask, dim3 grid, void* stream) {
-  if (mask.bits) hipLaunchKernelGGL(k_heads<true>, grid, dim3(NT), 0, (hipStream_t)stream, with_mask(a, mask));
-  else hipLaunchKernelGGL(k_heads<false>, grid, dim3(NT), 0, (hipStream_t)stream, a);
+  if (mask.bits) hipLaunchKernelGGL(masked, grid, block, 0, (hipStream_t)stream, m);
+  else hipLaunchKernelGGL(unmasked, grid, block, 0, (hipStream_t)stream, a);
 }
 static void launch_map_head_h(const MapHeadArgs& a, void* stream) {
   hipLaunchKernelGGL(by_terms(k_map_head_h<3>, k_map_head_h_b16<1>, k_map_head_h<1>), dim3(grid64(a.rows)), dim3(256), 0, (hipStream_t)stream, a);
@@ -1180,53 +1190,24 @@ static void launch_mlpemb_h(const MlpEmbHArgs& m, void* stream) {
   hipLaunchKernelGGL(by_terms(k_mlpemb_h<3>, k_mlpemb_h_b16<1>, k_mlpemb_h<1>), dim3(grid64(m.rows)), dim3(256), 0, (hipStream_t)stream, m);
 }
 
-// scratch: optional rows x 8 bytes - with it, launches of few row tiles deal the logit chunks to several workgroups per tile
-// keys_stay (infgen_rollout_run's folded tail): the split path neither clears the keys before (k_integrate of the previous step
-// did) nor decodes them after (k_integrate of this step will); *split_used tells the caller whether that path ran
-// token_logprob: only where attn_split(rows) holds (the fused k_heads_h<TERMS, true>); elsewhere the caller runs infgen_token_logprob
-// on the stored logits once next_token is final
-// sample_k > 1 (with uniform [rows], sample_logprob optional): next_token is sampled inside the kernel - only where
-// heads_sample_fused_for holds; elsewhere the caller runs infgen_sample_topk on the stored logits
-static int heads_impl(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
-                      float* logits, int* next_token, int* next_state, unsigned long long* scratch, void* stream,
-                      bool keys_stay = false, bool* split_used = nullptr, float* token_logprob = nullptr,
-                      int sample_k = 0, const float* uniform = nullptr, float* sample_logprob = nullptr,
-                      const SamplingCtl& ctl = SAMPLING_DEFAULT, const TokenMaskCtl& mask = TOKEN_MASK_NONE) {
-  if (split_used) *split_used = false;
-  if (rows <= 0) return 0;
-  if (token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
-  if (token_logprob && !attn_split(rows)) return fail("infgen_heads", "the fused log-probability needs the split kernel");
-  if (sample_k > 1 && (!uniform || !heads_sample_fused_for(O().attn_mode, rows, sample_k)))
-    return fail("infgen_heads", "sampling inside the kernel needs the split kernel, k within its width and uniforms");
-  if (sample_k <= 1) { sample_k = 0; uniform = nullptr; sample_logprob = nullptr; }
-  HeadsArgs a{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, 1, token_logprob,
-              sample_k, uniform, sample_logprob, ctl};
-  if (scratch && !attn_split(rows)) {
-    const int no_split = knob::heads_nosplit;
-    const int tiles = ceil_div(rows, TR), nchunk = token_size / 128;
-    int ns = 1;
-    while (!no_split && 2 * ns <= nchunk && nchunk % (2 * ns) == 0 && tiles * 2 * ns <= 512) ns *= 2;
-    if (ns > 1) {
-      if (!keys_stay && hipMemsetAsync(scratch, 0, (size_t)rows * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
-        return fail("infgen_heads", "memset failed");
-      a.part = scratch; a.nsplit = ns;
-      { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(rows, token_size));
-        launch_heads_fp32(a, mask, dim3(tiles, ns), stream);
-        if (!keys_stay)
-          hipLaunchKernelGGL(k_heads_finish, dim3(ceil_div(rows, NT)), dim3(NT), 0, (hipStream_t)stream, scratch, rows, next_token); }
-      if (split_used) *split_used = true;
-      return check_launch("infgen_heads");
-    }
-  }
-  { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(rows, token_size));
-    if (attn_split(rows)) launch_heads_h(a, mask, stream);
-    else launch_heads_fp32(a, mask, dim3(ceil_div(rows, TR)), stream); }
-  return check_launch("infgen_heads");
-}
-
-extern "C" int infgen_heads(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
-                            float* logits, int* next_token, int* next_state, void* stream) {
-  return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream);
+// One emission: the residual stream X [rows][128] -> next_state, the motion token and up to two log-probabilities.  The first eight
+// members are infgen_heads' own parameters in its order (EmitReq{X, ..., next_state}); the rest is set by name, and off where it is not
+struct EmitReq {
+  const float* X; int rows; const float* tok_pack; const float* st_pack; int token_size;
+  float* logits;                      // optional [rows][token_size]: written when set; the plan's chain (need_logits) reads it back
+  int* next_token; int* next_state;   // [rows]
+  int k = 1; const float* uniform = nullptr;      // k <= 1: the arg-max (uniform, ctl and sample_logprob unused), else the top-k beam
+  SamplingCtl ctl = SAMPLING_DEFAULT;             // and its draw: [rows] U[0, 1), temperature / top-p
+  TokenMaskCtl mask = TOKEN_MASK_NONE;      // per-row allowed tokens of the arg-max or the draw (bits == NULL: the unmasked kernels)
+  bool mask_chain_heads = false;      // heads whose arg-max k_sample_topk overwrites take the mask too (infgen_decode_step; not the entries)
+  float* token_logprob = nullptr;     // optional [rows], full softmax: out of the split kernel (plan.lp_fused), else k_token_logprob over logits
+  float* sample_logprob = nullptr;    // optional [rows], k > 1: log-probability of the pick under the sampler's own distribution
+  unsigned long long* keys = nullptr; // optional rows x 8 bytes: with them k_heads deals the logit chunks of few row tiles to plan.ns
+                                      // workgroups per tile - cleared before, decoded after (k_heads_finish) ...
+  bool keys_stay = false;             // ... or neither (infgen_rollout_run's folded tail: the previous and this step's k_integrate do)
+};
+static EmitPlan emit_plan(const EmitReq& q) {
+  return emit_plan(O().attn_mode, q.rows, q.token_size, q.k, q.token_logprob != nullptr, q.keys && !knob::heads_nosplit);
 }
 
 extern "C" int infgen_token_logprob(const float* logits, int rows, int n, const int* token, float* out, void* stream) {
@@ -1238,40 +1219,24 @@ extern "C" int infgen_token_logprob(const float* logits, int rows, int n, const 
   return check_launch("infgen_token_logprob");
 }
 
-// infgen_heads + the log-probability of next_token: fused (k_heads_h<TERMS, true>, logits optional) where attn_split picks the
-// split kernel, otherwise k_heads into the caller's logits and k_token_logprob over them
-extern "C" int infgen_heads_logprob(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
-                                    float* logits, int* next_token, int* next_state, float* token_logprob, void* stream) {
-  if (rows <= 0) return 0;
-  if (!token_logprob) return fail("infgen_heads_logprob", "token_logprob is NULL (infgen_heads is the entry without it)");
-  if (attn_split(rows))
-    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
-                      token_logprob);
-  if (!logits) return fail("infgen_heads_logprob", "this row count takes k_heads: it needs a logits buffer [rows][token_size]");
-  RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
-  return infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream);
-}
-
 static int sample_topk_impl(const char* me, const float* logits, int rows, int n, int k, const float* uniform, int* token,
-                            float* sample_logprob, void* stream, const SamplingCtl& ctl = SAMPLING_DEFAULT, int* nucleus = nullptr,
-                            const TokenMaskCtl& mask = TOKEN_MASK_NONE) {
+                            float* sample_logprob, const SamplingCtl& ctl, const TokenMaskCtl& mask, int* nucleus, void* stream) {
   if (rows <= 0) return 0;
   if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
   if (k > n) return fail(me, "k must not exceed n");      // (the k-th pick of fewer than k logits is no token)
   SampleArgs a{logits, rows, n, k, uniform, token, sample_logprob, ctl, nucleus};
-  if (mask.bits) hipLaunchKernelGGL(k_sample_topk<true>, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, with_mask(a, mask));
-  else hipLaunchKernelGGL(k_sample_topk<false>, dim3(ceil_div(rows, 4)), dim3(NT), 0, (hipStream_t)stream, a);
+  launch_masked(k_sample_topk<true>, k_sample_topk<false>, dim3(ceil_div(rows, 4)), dim3(NT), a, mask, stream);
   return check_launch(me);
 }
 
 extern "C" int infgen_sample_topk(const float* logits, int rows, int n, int k, const float* uniform, int* token,
                                   void* stream) {
-  return sample_topk_impl("infgen_sample_topk", logits, rows, n, k, uniform, token, nullptr, stream);
+  return sample_topk_impl("infgen_sample_topk", logits, rows, n, k, uniform, token, nullptr, SAMPLING_DEFAULT, TOKEN_MASK_NONE, nullptr, stream);
 }
 
 extern "C" int infgen_sample_topk_logprob(const float* logits, int rows, int n, int k, const float* uniform, int* token,
                                           float* sample_logprob, void* stream) {
-  return sample_topk_impl("infgen_sample_topk_logprob", logits, rows, n, k, uniform, token, sample_logprob, stream);
+  return sample_topk_impl("infgen_sample_topk_logprob", logits, rows, n, k, uniform, token, sample_logprob, SAMPLING_DEFAULT, TOKEN_MASK_NONE, nullptr, stream);
 }
 
 // ... with temperature and nucleus truncation (sampling == NULL: infgen_sample_topk_logprob); k == 1 is the arg-max, the parameters ignored
@@ -1280,7 +1245,7 @@ extern "C" int infgen_sample_topk_ex(const float* logits, int rows, int n, int k
   const char* me = "infgen_sample_topk_ex";
   SamplingCtl ctl = SAMPLING_DEFAULT;
   if (k > 1) RET_IF(sampling_ctl(me, sampling, &ctl));
-  return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, stream, ctl, nucleus);
+  return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, ctl, TOKEN_MASK_NONE, nucleus, stream);
 }
 
 // ... under a token mask (mask == NULL or inactive: infgen_sample_topk_ex)
@@ -1293,64 +1258,96 @@ extern "C" int infgen_sample_topk_mask(const float* logits, int rows, int n, int
   if (k > 1) RET_IF(sampling_ctl(me, sampling, &ctl));
   const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
   RET_IF(token_mask_ctl(me, &md, n, &mk));
-  return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, stream, ctl, nucleus, mk);
+  return sample_topk_impl(me, logits, rows, n, k, uniform, token, sample_logprob, ctl, mk, nucleus, stream);
+}
+
+// The launches the plan names, in order: [keys cleared] the heads - k_heads_h, or k_heads over ns column parts - [k_heads_finish]
+// [k_sample_topk] [k_token_logprob].  The heads stage reports as infgen_heads, the log-probability as infgen_token_logprob; `me`
+// names the chain's draw.  *split_used: the column split ran (with keys_stay: the keys wait for the caller's k_integrate)
+static int emit_tokens(const char* me, const EmitReq& q, const EmitPlan& p, void* stream, bool* split_used = nullptr) {
+  if (split_used) *split_used = false;
+  if (q.rows <= 0) return 0;
+  if (q.token_size % 128) return fail("infgen_heads", "token_size must be a multiple of 128");
+  const bool draw_after = q.k > 1 && !p.sample_fused;
+  const TokenMaskCtl& heads_mask = draw_after && !q.mask_chain_heads ? TOKEN_MASK_NONE : q.mask;
+  HeadsArgs a{q.X, q.rows, q.tok_pack, q.st_pack, q.token_size, q.logits, q.next_token, q.next_state, nullptr, 1,
+              p.lp_fused ? q.token_logprob : nullptr, p.sample_fused ? q.k : 0, p.sample_fused ? q.uniform : nullptr,
+              p.sample_fused ? q.sample_logprob : nullptr, q.ctl};
+  const bool parts = p.ns > 1, finish = parts && !q.keys_stay;
+  if (parts) { a.part = q.keys; a.nsplit = p.ns; }
+  if (finish && hipMemsetAsync(q.keys, 0, (size_t)q.rows * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
+    return fail("infgen_heads", "memset failed");
+  { ProfScope _ps(INFGEN_KID_HEADS, stream, heads_macs(q.rows, q.token_size));
+    if (p.split) launch_masked(heads_h_kernel<true>(a), heads_h_kernel<false>(a), dim3(grid64(q.rows)), dim3(256), a, heads_mask, stream);
+    else launch_masked(k_heads<true>, k_heads<false>, dim3(ceil_div(q.rows, TR), p.ns), dim3(NT), a, heads_mask, stream);
+    if (finish)
+      hipLaunchKernelGGL(k_heads_finish, dim3(ceil_div(q.rows, NT)), dim3(NT), 0, (hipStream_t)stream, q.keys, q.rows, q.next_token); }
+  if (split_used) *split_used = parts;
+  RET_IF(check_launch("infgen_heads"));
+  if (draw_after)
+    RET_IF(sample_topk_impl(me, q.logits, q.rows, q.token_size, q.k, q.uniform, q.next_token, q.sample_logprob, q.ctl, q.mask, nullptr, stream));
+  if (q.token_logprob && !p.lp_fused) RET_IF(infgen_token_logprob(q.logits, q.rows, q.token_size, q.next_token, q.token_logprob, stream));
+  return 0;
+}
+// the stand-alone entries: the plan under the caller's switches, refused where its chain would read logits the caller did not pass
+static int emit_entry(const char* me, const EmitReq& q, void* stream) {
+  const EmitPlan p = emit_plan(q);
+  if (p.need_logits && !q.logits)
+    return fail(me, q.k > 1 ? "this row count or beam takes k_sample_topk: it needs a logits buffer [rows][token_size]"
+                            : "this row count takes k_heads: it needs a logits buffer [rows][token_size]");
+  return emit_tokens(me, q, p, stream);
+}
+
+extern "C" int infgen_heads(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
+                            float* logits, int* next_token, int* next_state, void* stream) {
+  return emit_entry("infgen_heads", EmitReq{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state}, stream);
+}
+
+// infgen_heads + the log-probability of next_token: out of the split kernel where the plan says so (logits optional), otherwise
+// k_heads into the caller's logits and k_token_logprob over them
+extern "C" int infgen_heads_logprob(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size,
+                                    float* logits, int* next_token, int* next_state, float* token_logprob, void* stream) {
+  if (rows <= 0) return 0;
+  if (!token_logprob) return fail("infgen_heads_logprob", "token_logprob is NULL (infgen_heads is the entry without it)");
+  EmitReq q{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state};
+  q.token_logprob = token_logprob;
+  return emit_entry("infgen_heads_logprob", q, stream);
 }
 
 // infgen_heads with the motion token drawn by top-k sampling (k_sample_topk's order and arithmetic) and, optionally, its two
-// log-probabilities: one launch of k_heads_h<TERMS, LP, HEADS_KS> where heads_sample_fused_for holds (logits optional); elsewhere
-// heads into the caller's logits, k_sample_topk and k_token_logprob over them.  k == 1 is the arg-max (the greedy variant)
-static int heads_sample_impl(const char* me, const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
-                             const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token, int* next_state,
-                             float* token_logprob, float* sample_logprob, void* stream, const TokenMaskDesc* mask = nullptr) {
-  if (rows <= 0) return 0;
-  if (mask && k < 1) k = 1;      // (infgen_heads_sample_mask: k <= 1 is the masked arg-max)
-  if (k < 1 || k > 16) return fail(me, "k must be in 1..16");
-  if (k > token_size) return fail(me, "k must not exceed token_size");
-  if (!uniform && !(mask && k == 1)) return fail(me, "uniform is NULL");
-  TokenMaskCtl mk;
-  RET_IF(token_mask_ctl(me, mask, token_size, &mk));
-  if (k == 1) {      // a point mass on the arg-max: the greedy kernels, and log 1
-    if (sample_logprob && hipMemsetAsync(sample_logprob, 0, (size_t)rows * sizeof(float), (hipStream_t)stream) != hipSuccess)
+// log-probabilities: one launch where the plan draws inside the split kernel (logits optional); elsewhere heads into the caller's
+// logits, k_sample_topk and k_token_logprob over them.  k == 1 is the arg-max (the greedy variant): a point mass, and log 1
+static int heads_sample_impl(const char* me, EmitReq q, const InfgenSampling* sampling, const TokenMaskDesc* mask, void* stream) {
+  if (q.rows <= 0) return 0;
+  if (mask && q.k < 1) q.k = 1;      // (infgen_heads_sample_mask: k <= 1 is the masked arg-max)
+  if (q.k < 1 || q.k > 16) return fail(me, "k must be in 1..16");
+  if (q.k > q.token_size) return fail(me, "k must not exceed token_size");
+  if (!q.uniform && !(mask && q.k == 1)) return fail(me, "uniform is NULL");
+  RET_IF(token_mask_ctl(me, mask, q.token_size, &q.mask));
+  if (q.k == 1) {
+    if (q.sample_logprob && hipMemsetAsync(q.sample_logprob, 0, (size_t)q.rows * sizeof(float), (hipStream_t)stream) != hipSuccess)
       return fail(me, "memset failed");
-    if (token_logprob && !mk.bits)
-      return infgen_heads_logprob(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, token_logprob, stream);
-    if (token_logprob) {      // infgen_heads_logprob's two routes with the mask in the arg-max
-      if (attn_split(rows))
-        return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
-                          token_logprob, 0, nullptr, nullptr, SAMPLING_DEFAULT, mk);
-      if (!logits) return fail(me, "this row count takes k_heads: it needs a logits buffer [rows][token_size]");
-      RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr, nullptr,
-                        0, nullptr, nullptr, SAMPLING_DEFAULT, mk));
-      return infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream);
-    }
-    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr, nullptr,
-                      0, nullptr, nullptr, SAMPLING_DEFAULT, mk);
-  }
-  SamplingCtl ctl;
-  RET_IF(sampling_ctl(me, sampling, &ctl));
-  if (heads_sample_fused_for(O().attn_mode, rows, k))
-    return heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream, false, nullptr,
-                      token_logprob, k, uniform, sample_logprob, ctl, mk);
-  if (!logits) return fail(me, "this row count or beam takes k_sample_topk: it needs a logits buffer [rows][token_size]");
-  RET_IF(heads_impl(X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state, nullptr, stream));
-  RET_IF(sample_topk_impl(me, logits, rows, token_size, k, uniform, next_token, sample_logprob, stream, ctl, nullptr, mk));
-  if (token_logprob) RET_IF(infgen_token_logprob(logits, rows, token_size, next_token, token_logprob, stream));
-  return 0;
+    if (q.token_logprob && !q.mask.bits)      // (unmasked: infgen_heads_logprob itself, its refusals under its own name)
+      return infgen_heads_logprob(q.X, q.rows, q.tok_pack, q.st_pack, q.token_size, q.logits, q.next_token, q.next_state, q.token_logprob, stream);
+  } else RET_IF(sampling_ctl(me, sampling, &q.ctl));
+  return emit_entry(me, q, stream);
 }
 
 extern "C" int infgen_heads_sample(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
                                    const float* uniform, float* logits, int* next_token, int* next_state, float* token_logprob,
                                    float* sample_logprob, void* stream) {
-  return heads_sample_impl("infgen_heads_sample", X, rows, tok_pack, st_pack, token_size, k, uniform, nullptr, logits, next_token,
-                           next_state, token_logprob, sample_logprob, stream);
+  EmitReq q{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state};
+  q.k = k; q.uniform = uniform; q.token_logprob = token_logprob; q.sample_logprob = sample_logprob;
+  return heads_sample_impl("infgen_heads_sample", q, nullptr, nullptr, stream);
 }
 
 // ... with temperature and nucleus truncation (the same draw: topk_inverse_cdf of kernels.h, inside the split kernel or after it)
 extern "C" int infgen_heads_sample_ex(const float* X, int rows, const float* tok_pack, const float* st_pack, int token_size, int k,
                                       const float* uniform, const InfgenSampling* sampling, float* logits, int* next_token,
                                       int* next_state, float* token_logprob, float* sample_logprob, void* stream) {
-  return heads_sample_impl("infgen_heads_sample_ex", X, rows, tok_pack, st_pack, token_size, k, uniform, sampling, logits, next_token,
-                           next_state, token_logprob, sample_logprob, stream);
+  EmitReq q{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state};
+  q.k = k; q.uniform = uniform; q.token_logprob = token_logprob; q.sample_logprob = sample_logprob;
+  return heads_sample_impl("infgen_heads_sample_ex", q, sampling, nullptr, stream);
 }
 
 // ... under a token mask (mask == NULL or inactive: infgen_heads_sample_ex); k <= 1 is the masked arg-max
@@ -1359,10 +1356,11 @@ extern "C" int infgen_heads_sample_mask(const float* X, int rows, const float* t
                                         int mask_n_sets, const int* mask_row, const int* mask_type, const int* type, float* logits,
                                         int* next_token, int* next_state, float* token_logprob, float* sample_logprob, void* stream) {
   const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  const TokenMaskDesc* mask = mask_bits ? &md : nullptr;      // (no table: infgen_heads_sample_ex, its argument checks included)
   if (mask_n_sets < 0) return fail("infgen_heads_sample_mask", "token mask: n_sets must be >= 0");
-  return heads_sample_impl("infgen_heads_sample_mask", X, rows, tok_pack, st_pack, token_size, k, uniform, sampling, logits, next_token,
-                           next_state, token_logprob, sample_logprob, stream, mask);
+  EmitReq q{X, rows, tok_pack, st_pack, token_size, logits, next_token, next_state};
+  q.k = k; q.uniform = uniform; q.token_logprob = token_logprob; q.sample_logprob = sample_logprob;
+  // (no table: infgen_heads_sample_ex, its argument checks included)
+  return heads_sample_impl("infgen_heads_sample_mask", q, sampling, mask_bits ? &md : nullptr, stream);
 }
 
 // the map encoder's token_predict_head (map_decoder.py:119-121) on the rows gather[k] of X.  Split arithmetic (k_map_head_h: one
@@ -1724,11 +1722,11 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
     if (score.out && r->S % score.copies) return fail(where, "step score: S must be a multiple of copies");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
-    // only the fused kernel needs no logits in memory: greedy rows on the split path (attn_split under the context's own switches)
+    // only the fused kernel needs no logits in memory: the plan under the context's own switches
     const int mode = (r->opts.use ? r->opts : O()).attn_mode;
-    const bool sampled = r->sample_k > 1 && r->sample_u;
-    const bool fused = sampled ? heads_sample_fused_for(mode, r->S * r->A_cap, r->sample_k) : attn_split_for(mode, r->S * r->A_cap);
-    if (!fused) return fail(where, "token_logprob needs store_logits or logits_scratch [rows][token_size] (few rows, or sampling)");
+    const int k = r->sample_k > 1 && r->sample_u ? r->sample_k : 1;
+    if (emit_plan(mode, r->S * r->A_cap, r->token_size, k, true, false).need_logits)
+      return fail(where, "token_logprob needs store_logits or logits_scratch [rows][token_size] (few rows, or sampling)");
   }
   return 0;
 }
@@ -2437,6 +2435,13 @@ extern "C" int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless,
   return layers_core(r, c, edgeless, stream, !lp);
 }
 
+// step t's emission over the context's rows, greedy and bare: logits is store_logits' slice of the step, or NULL
+static EmitReq step_emit_req(const InfgenRollout* r, int t) {
+  const int rows = r->S * r->A_cap;
+  float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
+  return EmitReq{r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token, r->next_state};
+}
+
 extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
   StepRiders riders;
@@ -2457,26 +2462,20 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
     RET_IF(launch_road("infgen_decode_step", road_args(sc, c, road, mask), stream));
     mask = TokenMaskCtl{road.bits, rows, road.ident, {-1, -1, -1}, nullptr};
   }
-  float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
-  // sampling: inside the split heads kernel where the by-size rule allows (no logits in memory: lg stays store_logits' slice or
-  // NULL); otherwise k_sample_topk over the step's logits
-  const bool s_fused = r->sample_k > 1 && r->sample_u && heads_sample_fused_for(O().attn_mode, rows, r->sample_k);
-  const bool sample = r->sample_k > 1 && r->sample_u && (s_fused || lg || r->logits_scratch);
-  if (sample && !s_fused && !lg) lg = r->logits_scratch;
-  const float* su = sample ? r->sample_u + (size_t)t * rows : nullptr;
-  float* slp = (sample && r->sample_logprob) ? r->sample_logprob + (size_t)t * rows : nullptr;
-  // token_logprob: rows on the split path take the fused kernel (greedy, or sampled inside it); otherwise from the logits in
-  // memory (validate: there are some), once the emitted token is final
-  float* lp = r->token_logprob ? r->token_logprob + (size_t)t * rows : nullptr;
-  const bool lp_fused = lp && (sample ? s_fused : attn_split(rows));
-  if (lp && !lp_fused && !lg) lg = r->logits_scratch;
-  // (tmp2 is scratch of the raw-feature stage, free here: the per-row keys of the split arg-max)
-  RET_IF(heads_impl(r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token,
-                    r->next_state, reinterpret_cast<unsigned long long*>(r->tmp2), stream, false, nullptr, lp_fused ? lp : nullptr,
-                    s_fused ? r->sample_k : 0, su, slp, ctl, mask));
-  if (sample && !s_fused)
-    RET_IF(sample_topk_impl("infgen_sample_topk", lg, rows, r->token_size, r->sample_k, su, r->next_token, slp, stream, ctl, nullptr, mask));
-  if (lp && !lp_fused) RET_IF(infgen_token_logprob(lg, rows, r->token_size, r->next_token, lp, stream));
+  EmitReq q = step_emit_req(r, t);
+  q.ctl = ctl; q.mask = mask; q.mask_chain_heads = true;
+  q.keys = reinterpret_cast<unsigned long long*>(r->tmp2);      // (scratch of the raw-feature stage, free here)
+  if (r->token_logprob) q.token_logprob = r->token_logprob + (size_t)t * rows;
+  q.k = r->sample_u ? r->sample_k : 1;
+  // a draw outside the split kernel with no logits to draw from: the arg-max, silently (sample_logprob unwritten, like a greedy context's)
+  if (q.k > 1 && !q.logits && !r->logits_scratch && !emit_plan(q).sample_fused) q.k = 1;
+  if (q.k > 1) {
+    q.uniform = r->sample_u + (size_t)t * rows;
+    if (r->sample_logprob) q.sample_logprob = r->sample_logprob + (size_t)t * rows;
+  }
+  const EmitPlan plan = emit_plan(q);
+  if (plan.need_logits && !q.logits) q.logits = r->logits_scratch;      // (validate: token_logprob's chain has one)
+  RET_IF(emit_tokens("infgen_sample_topk", q, plan, stream));
   RET_IF(infgen_integrate(r, t, stream));
   if (score.out) {      // step scores: the column this step produced, reduced per scene slot
     if (t >= score.steps) return fail("infgen_decode_step", "step score: the log holds fewer steps");
@@ -2517,10 +2516,10 @@ extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* 
   for (int t = t0; t < t1; ++t) {
     const int c = 1 + t;
     RET_IF(layers_core(r, c, 0, stream, !lp_steps));
-    float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
+    EmitReq q = step_emit_req(r, t);
+    q.keys = keys; q.keys_stay = true;
     bool split = false;
-    RET_IF(heads_impl(r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token, r->next_state, keys, stream,
-                      true, &split));
+    RET_IF(emit_tokens("infgen_rollout_run", q, emit_plan(q), stream, &split));
     // (the last step keeps its edge totals, like infgen_decode_step: RolloutEngine.edge_totals() / overflow checks read them)
     RET_IF(integrate_impl(r, t, stream, split ? keys : nullptr, t + 1 < t1, true, t + 1 < t1 && lp_steps));
     if (t + 1 < t1) {
