@@ -1,7 +1,8 @@
 """Device-side helpers shared by the operator-level GPU tests (test_edge_builders_gpu.py, test_insertion_ops_gpu.py,
-test_step_advance_gpu.py): guarded
-device buffers, InfgenEdgeBuf / InfgenRollout blocks over device copies of a graph_ref block.  Not a test module and not a conftest;
-torch and the library are only needed by the callers, which are GPU tests."""
+test_step_advance_gpu.py, test_forward_ops_gpu.py): guarded device buffers, InfgenEdgeBuf (whole, or the upper zone of a buffer
+that several edge sets share) / InfgenRollout blocks over device copies of a graph_ref block.  What the tests assert of an edge
+buffer's contents is graph_ref.compare_lists.  Not a test module and not a conftest; torch and the library are only needed by
+the callers, which are GPU tests."""
 import numpy as np
 import torch
 
@@ -39,24 +40,28 @@ def guarded_copy(v):
 
 
 class Edges:
-    """an InfgenEdgeBuf of `rows` destinations and `cap` edges, every array guarded"""
+    """an InfgenEdgeBuf of `rows` destinations and `cap` edges, every array guarded.  base > 0: the zone [base, base + cap) of a
+    src / raw buffer of base + cap edges, as the forward shares one buffer between two edge sets (off entries then carry the base)"""
 
-    def __init__(self, rows, cap):
+    def __init__(self, rows, cap, base=0):
         from infgen_amd import _lib
-        self.rows, self.cap = rows, cap
+        self.rows, self.cap, self.base = rows, cap, base
         self.off, self.cnt = guarded(rows, torch.int32), guarded(rows, torch.int32)
-        self.src, self.raw = guarded(cap, torch.int32), guarded(cap, torch.float32, 4)
+        self.src, self.raw = guarded(base + cap, torch.int32), guarded(base + cap, torch.float32, 4)
         self.total = guarded(1, torch.int32)
         self.buf = _lib.EdgeBuf()
-        self.buf.off, self.buf.cnt, self.buf.src, self.buf.raw = (t.data_ptr() for t in (self.off, self.cnt, self.src, self.raw))
+        self.buf.off, self.buf.cnt = self.off.data_ptr(), self.cnt.data_ptr()
+        self.buf.src, self.buf.raw = self.src.data_ptr() + 4 * base, self.raw.data_ptr() + 16 * base
         self.buf.total, self.buf.cap = self.total.data_ptr(), cap
 
     def host(self):
+        """-> (off, cnt, src, raw, total): src / raw of the whole buffer, the zone's base included"""
         torch.cuda.synchronize()
+        n = self.base + self.cap
         assert guard_intact(self.off, self.rows) and guard_intact(self.cnt, self.rows) and guard_intact(self.total, 1)
-        assert guard_intact(self.src, self.cap) and guard_intact(self.raw, self.cap, 4), 'written at or beyond cap'
-        return (self.off[:self.rows].cpu().numpy(), self.cnt[:self.rows].cpu().numpy(), self.src[:self.cap].cpu().numpy(),
-                self.raw[:4 * self.cap].cpu().numpy().reshape(-1, 4), int(self.total[0].item()))
+        assert guard_intact(self.src, n) and guard_intact(self.raw, n, 4), 'written at or beyond cap'
+        return (self.off[:self.rows].cpu().numpy(), self.cnt[:self.rows].cpu().numpy(), self.src[:n].cpu().numpy(),
+                self.raw[:4 * n].cpu().numpy().reshape(-1, 4), int(self.total[0].item()))
 
 
 STEP_POINTERS = ('next_token', 'next_state', 'teacher_token', 'teacher_state', 'teacher_grid', 'teacher_pos', 'teacher_head',

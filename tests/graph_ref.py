@@ -1,7 +1,13 @@
 """Plain references of the integer-and-geometry kernels (edge builders, insertion decisions, top-k sampling) and the input
 generators their tests share.  numpy only, float64, loops over scenes and destinations; written from the header comments of
 infgen_amd/csrc/edge_kernels.hip and the reference lines they cite (agent_decoder.py:540-904, 1852-2074, 2162-2195;
-map_decoder.py:91-93; attr_tokenizer.py:91-110) - nothing is shared with oracle/ or infgen_amd/.
+map_decoder.py:91-93; attr_tokenizer.py:91-110) - nothing is shared with oracle/ or infgen_amd/.  The step-advance kernels
+(k_integrate, the raw-feature gather: agent_decoder.py:2168-2285, :426-447) and the two geometry kernels of the teacher-forced
+forward, k_radius_edges and k_motion_features of infgen_amd/csrc/forward_kernels.hip, follow: the latter from the text of
+include/infgen_hip.h ("edge sets of the teacher-forced forward") and the lines it cites (agent_decoder.py:595-601, :632, :710,
+:722-723, :780, :875, :426-447, :1327; map_decoder.py:91).  compare_lists is what every GPU test of an edge builder asserts of a
+device CSR against these lists; test_graph_ref_cpu.py runs the deliberately wrong variants of the references (mutate=...) through
+the same comparison, so that the generated inputs are known to tell those errors apart.
 
 A scene block (`new_state`) is a dict of numpy arrays in the device layout of InfgenRollout (include/infgen_hip.h): the per-column
 arrays are [S][T][A_cap], the map side [Sm][M_cap]."""
@@ -246,6 +252,37 @@ def raw_errors(ref_lists, other_lists):
         if len(ra):
             e = np.maximum(e, [np.abs(ra[:, 0] - rb[:, 0]).max(), ang_err(ra[:, 1], rb[:, 1]).max(), ang_err(ra[:, 2], rb[:, 2]).max()])
     return e
+
+
+def compare_lists(kind, off, cnt, src, raw, ref, cap=None, written=None):
+    """what the GPU tests of the edge builders assert of a device CSR (off / cnt per destination row, src / raw [cap][4] in fp32)
+    against reference lists: per row the count, the source list in order, raw features within the bars, raw[:, 3] and the rule
+    constants exact.  With cap: rows whose range passes it are compared for their count only (written = False) or must report
+    cnt = 0 (written = None: the compacting kernels).  -> the largest device errors (distance, bearing, heading difference)"""
+    err = np.zeros(3)
+    for row, r in enumerate(ref):
+        want_src, want_raw = r[0], np.asarray(r[1], np.float64)
+        n = len(want_src)
+        over = cap is not None and off[row] + n > cap
+        if over and written is None:
+            assert cnt[row] == 0, (kind, row)
+            continue
+        assert cnt[row] == n, (kind, row, cnt[row], n)
+        if n == 0 or over:
+            continue
+        o = off[row]
+        assert 0 <= o and (cap is None or o + n <= cap)
+        assert np.array_equal(src[o:o + n], want_src), (kind, row, src[o:o + n], want_src)
+        got = raw[o:o + n].astype(np.float64)
+        e = [np.abs(got[:, 0] - want_raw[:, 0]).max(), ang_err(got[:, 1], want_raw[:, 1]).max(), ang_err(got[:, 2], want_raw[:, 2]).max()]
+        assert e[0] <= BAR_DIST and e[1] <= BAR_BEARING and e[2] <= BAR_DTH, (kind, row, e)
+        assert np.array_equal(got[:, 3], want_raw[:, 3]), (kind, row)
+        if len(r) > 2 and r[2].any():                  # gap rules: -1 / 1 / -2, and the distance float32(sqrt 2) / float32(2 sqrt 2)
+            dth_c, dist_c = (r[2] & RULED_DTH) != 0, (r[2] & RULED_DIST) != 0
+            assert np.array_equal(got[dth_c, 2], want_raw[dth_c, 2]), (kind, row, 'a gap-rule constant is not exact')
+            assert np.array_equal(raw[o:o + n][dist_c, 0], want_raw[dist_c, 0].astype(np.float32)), (kind, row, 'a gap-rule distance is not exact')
+        err = np.maximum(err, e)
+    return err
 
 
 # ------------------------------------------------------------------------------------------------ insertion / sampling
@@ -1185,3 +1222,352 @@ def take_step_scenes(st, ext, scenes):
                 assert v.shape[0] == S, k
                 o[k] = np.ascontiguousarray(v[scenes])
     return o_st, o_ext
+
+
+# ------------------------------------------------------------------------------------------------ teacher-forced forward: edge builder, motion features
+def pack_lists(lists, e_base=0, f=np.float32):
+    """reference lists [(src, raw, ...)] as a compact CSR in list order: (off, cnt, src, raw [total][4] in f, total); off carries
+    e_base, src / raw start at the zone's first edge"""
+    cnt = np.asarray([len(r[0]) for r in lists], np.int64)
+    off = e_base + np.cumsum(cnt) - cnt
+    total = int(cnt.sum())
+    src = np.concatenate([np.asarray(r[0], np.int64) for r in lists] + [np.zeros(0, np.int64)])
+    raw = np.concatenate([np.asarray(r[1], f).reshape(-1, 4) for r in lists] + [np.zeros((0, 4), f)])
+    pad_i, pad_f = np.zeros(e_base, np.int64), np.zeros((e_base, 4), f)
+    return off, cnt, np.concatenate([pad_i, src]), np.concatenate([pad_f, raw]), total
+
+
+RADIUS_EDGES_MUTANTS = ('filtered_not_counted', 'le_radius', 'pair_abs_index', 'index_diff_sign', 'rule1_dst_dth', 'rule2_keep_dth',
+                        'bearing_pre_override')
+_GAP_KIND = {0: 'point', 1: 'agent', 2: 'map'}
+
+
+def radius_edges_ref(case, f=np.float64, mutate=None):
+    """infgen_radius_edges (include/infgen_hip.h, "edge sets of the teacher-forced forward"; agent_decoder.py:632, :710, :780, :875,
+    map_decoder.py:91 with the filters the reference applies after the radius call, gap rules :595-601 / :722-723) of a case dict
+    (gen_radius_edges: the fields of InfgenRadiusEdges as numpy arrays or None, n_nodes).  Per query q: candidates [q_c0, q_c1) in
+    ascending index, the first K with d^2 < r^2 (strict) are found; of those the ones with index != q_self, c_ok[index] and
+    pair_ok[q_pair_off + index - q_c0] (q_pair_off < 0: no pair filter) are emitted with src = c_src[index] (else the index) and
+    raw = (|d|, bearing in the query's heading frame, wrap(c_head - p_head), index_diff ? index - q_pt : 0), gap_rule 1 = edge_raw's
+    'agent', 2 = 'map', 0 = 'point'.  Which candidates are found is decided in float64; f is the type of the features.
+    -> ([(src in order, raw [n][4], ruled bits)] per destination NODE (nodes without a query: empty), the smallest relative gap
+    |d^2 - r^2| / r^2 of any (query, candidate) pair).
+    mutate: one deliberate deviation, for the tests that show the cases tell it apart - 'filtered_not_counted' (the filters run
+    before the K cap), 'le_radius' (d^2 <= r^2), 'pair_abs_index' (pair_ok read at q_pair_off + index), 'index_diff_sign',
+    'rule1_dst_dth' (gap rule 1, destination invalid only: dth = the gap too), 'rule2_keep_dth' (gap rule 2 leaves dth),
+    'bearing_pre_override' (the bearing of d before a gap rule replaced it)."""
+    assert mutate is None or mutate in RADIUS_EDGES_MUTANTS
+    g = case
+    K, kind, r = int(g['K']), _GAP_KIND[g['gap_rule']], float(g['radius'])
+    empty = (np.zeros(0, np.int64), np.zeros((0, 4), f), np.zeros(0, np.int8))
+    out, gap = [empty] * g['n_nodes'], math.inf
+    opt = lambda k, i, d: d if g[k] is None else g[k][i]
+    for q in range(len(g['q_node'])):
+        node, qp, c0, c1 = (int(g[k][q]) for k in ('q_node', 'q_pt', 'q_c0', 'q_c1'))
+        idx = np.arange(c0, c1)
+        centre = g['p_pos'][qp]
+        found, gq = first_k_within(centre, g['c_pos'][c0:c1], r, 10 ** 9 if mutate == 'filtered_not_counted' else K)
+        gap = min(gap, gq)
+        if mutate == 'le_radius':
+            cand = g['c_pos'][c0:c1].astype(np.float64).reshape(-1, 2)
+            d2 = (float(centre[0]) - cand[:, 0]) ** 2 + (float(centre[1]) - cand[:, 1]) ** 2
+            found = np.nonzero(d2 <= r * r)[0][:K]
+        m = idx[found]
+        keep = np.ones(len(m), bool)
+        if g['q_self'] is not None:
+            keep &= m != int(g['q_self'][q])
+        if g['c_ok'] is not None:
+            keep &= g['c_ok'][m] != 0
+        if g['pair_ok'] is not None and g['q_pair_off'] is not None and g['q_pair_off'][q] >= 0:
+            at = int(g['q_pair_off'][q]) + (m if mutate == 'pair_abs_index' else m - c0)
+            keep &= g['pair_ok'].reshape(-1)[at % g['pair_ok'].size] != 0           # (the modulus only keeps the mutant inside the array)
+        m = m[keep]
+        if mutate == 'filtered_not_counted':
+            m = m[:K]
+        if len(m) == 0:
+            continue
+        assert out[node] is empty, 'two queries of one destination node'
+        dpose = (g['p_pos'][qp, 0], g['p_pos'][qp, 1], g['p_head'][qp])
+        spose = (g['c_pos'][m, 0], g['c_pos'][m, 1], g['c_head'][m])
+        d_inv, s_inv = bool(opt('p_inv', qp, 0)), np.asarray(opt('c_inv', m, np.zeros(len(m), np.uint8))) != 0
+        raw, ruled = edge_raw(dpose, spose, d_inv, s_inv, kind, f=f)
+        plain = edge_raw(dpose, spose, False, False, 'point', f=f)[0]
+        if mutate == 'rule1_dst_dth' and kind == 'agent' and d_inv:
+            raw[~s_inv, 2] = f(HEADING_GAP)
+        if mutate == 'rule2_keep_dth' and kind == 'map':
+            raw[:, 2] = plain[:, 2]
+        if mutate == 'bearing_pre_override':
+            raw[:, 1] = plain[:, 1]
+        if g['index_diff']:
+            raw[:, 3] = ((qp - m) if mutate == 'index_diff_sign' else (m - qp)).astype(f)
+        out[node] = (np.asarray(opt('c_src', m, m), np.int64), raw, ruled)
+    return out, gap
+
+
+MOTION_FEATURES_MUTANTS = ('swap_invalid_and_leave', 'gap_mask_first', 't0_reads_previous_row', 'no_gap_mask')
+
+
+def motion_features_ref(pos, head, state, gap_mask, f=np.float64, mutate=None, with_ruled=False):
+    """infgen_motion_features (_build_vector_a, agent_decoder.py:426-447, gap mask :1327) of agent-major [rows][T] arrays: the motion
+    vector pos[t] - pos[t - 1], (0, 0) at t = 0; then, in this order, (1) INVALID: (-2, -2), (2) previous INVALID and this not -
+    at t = 0: state == ENTER - : (1, 1), (3) t > 0, previous not INVALID and this INVALID: (-1, -1), (4) gap_mask: (1, 1).
+    -> [rows][T][4] = (norm, angle(head vector, motion vector), 0, 0) [, ruled [rows][T]: 1 the motion is a rule's (+-1, +-1), 2
+    (-2, -2): the norm is then the rounded root of 2 or 8].
+    mutate: 'swap_invalid_and_leave' (rule 3 before rule 1), 'gap_mask_first' (rule 4 before the others), 't0_reads_previous_row'
+    (column 0 treated like any other column of the flat arrays: it reads the previous row's last column), 'no_gap_mask'."""
+    assert mutate is None or mutate in MOTION_FEATURES_MUTANTS
+    pos, state = np.asarray(pos), np.asarray(state)
+    rows, T = state.shape
+    p = pos.astype(f).reshape(rows * T, 2)
+    st = state.reshape(-1)
+    first = np.arange(rows * T) % T == 0
+    if mutate == 't0_reads_previous_row':
+        first = np.arange(rows * T) == 0
+    prev = np.maximum(np.arange(rows * T) - 1, 0)
+    m = np.where(first[:, None], f(0), p - p[prev])
+    inv = st == INVALID
+    pinv = np.where(first, False, st[prev] == INVALID)
+    enter = np.where(first, st == ENTER, pinv & ~inv)
+    leave = ~first & ~pinv & inv
+    gm = np.zeros(rows * T, bool) if gap_mask is None or mutate == 'no_gap_mask' else np.asarray(gap_mask).reshape(-1) != 0
+    rules = [(inv, INVALID_MOTION, 2), (enter, MOTION_GAP, 1), (leave, -MOTION_GAP, 1), (gm, MOTION_GAP, 1)]
+    if mutate == 'swap_invalid_and_leave':
+        rules = [rules[2], rules[1], rules[0], rules[3]]
+    if mutate == 'gap_mask_first':
+        rules = [rules[3]] + rules[:3]
+    ruled = np.zeros(rows * T, np.int8)
+    for mask, value, bit in rules:
+        m = np.where(mask[:, None], f(value), m)
+        ruled = np.where(mask, bit, ruled).astype(np.int8)
+    h = np.asarray(head).astype(f).reshape(-1)
+    hc, hs = np.cos(h), np.sin(h)
+    mx, my = m[:, 0], m[:, 1]
+    out = np.stack([np.sqrt(mx * mx + my * my), np.arctan2(hc * my - hs * mx, (f(0) + hc * mx) + hs * my),
+                    np.zeros(rows * T, f), np.zeros(rows * T, f)], -1).astype(f).reshape(rows, T, 4)
+    return (out, ruled.reshape(rows, T)) if with_ruled else out
+
+
+# Largest error of a plain fp32 numpy evaluation of motion_features_ref against float64 over gen_motion_features (all shapes, with
+# and without the gap mask): norm [m], angle [rad].  The figures tests/test_graph_ref_cpu.py measures, rounded up in the fourth
+# digit; the device bar is four times the figure, as above.  (Apart from FP32_ERR_MOTION_NORM / _BEARING of the rollout's raw
+# feature: the last column of these rows jumps by up to 300 m.)
+FP32_ERR_MOTION_FEAT_NORM, FP32_ERR_MOTION_FEAT_ANGLE = 2.363e-5, 2.863e-7
+BAR_MOTION_FEAT_NORM, BAR_MOTION_FEAT_ANGLE = 4 * FP32_ERR_MOTION_FEAT_NORM, 4 * FP32_ERR_MOTION_FEAT_ANGLE
+
+
+
+def compare_motion(got, ref, ruled):
+    """what the GPU test asserts of infgen_motion_features' fp32 output [rows][T][4] against motion_features_ref(with_ruled=True):
+    columns 2 and 3 exactly 0, the norm of a ruled motion exactly float32(sqrt 2) / float32(2 sqrt 2), norm and angle within the
+    bars.  -> the largest errors (norm, angle)"""
+    got = np.asarray(got)
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    assert np.array_equal(got[..., 2:].view(np.int32), np.zeros(got[..., 2:].shape, np.int32)), 'columns 2 and 3 are not +0'
+    want = np.where(ruled == 2, np.float32(math.sqrt(8.0)), np.float32(math.sqrt(2.0)))
+    assert np.array_equal(got[..., 0][ruled != 0], want[ruled != 0]), 'the norm of a rule constant is not exact'
+    e = np.asarray([np.abs(got[..., 0].astype(np.float64) - ref[..., 0]).max(), ang_err(got[..., 1], ref[..., 1]).max()])
+    assert e[0] <= BAR_MOTION_FEAT_NORM and e[1] <= BAR_MOTION_FEAT_ANGLE, e
+    return e
+
+
+RADIUS_EDGES_CASES = {
+    # name: (radius, K, gap_rule, index_diff, what it is for) - the forward's use it stands for in forward_engine.py
+    'temporal': (1e30, 12, 1, 1, '5 agents x 20 columns, window 12: r * r overflows in fp32, history mask, permuted node map, empty ranges'),
+    'agent': (60.0, 301, 1, 0, 'scenes of 1 / 70 / 330 agents in one launch: self dropped, the cap truncates after several chunks'),
+    'seed_pair': (50.0, 300, 0, 0, 'per-pair filter with per-query offsets (some -1); the upper zone of a shared buffer'),
+    'map': (30.0, 5, 2, 0, '200 map tokens per scene (one scene without): no candidate validity, queries valid and invalid'),
+    'map_graph': (20.0, 101, 0, 0, 'the map-token graph: no validity arrays at all, self dropped, scenes of 150 tokens and 1'),
+}
+
+
+def _new_radius_case(name, n_nodes, **kw):
+    radius, K, gap_rule, index_diff, _ = RADIUS_EDGES_CASES[name]
+    g = dict(name=name, n_nodes=n_nodes, radius=float(np.float32(radius)), K=K, gap_rule=gap_rule, index_diff=index_diff, e_base=0,
+             q_self=None, q_pair_off=None, p_inv=None, c_inv=None, c_ok=None, c_src=None, pair_ok=None)
+    g.update(kw)
+    for k in ('q_node', 'q_pt', 'q_c0', 'q_c1', 'q_self', 'q_pair_off', 'c_src'):
+        if g[k] is not None:
+            g[k] = np.ascontiguousarray(g[k], np.int32)
+    for k in ('p_inv', 'c_inv', 'c_ok', 'pair_ok'):
+        if g[k] is not None:
+            g[k] = np.ascontiguousarray(g[k], np.uint8)
+    for k in ('p_pos', 'p_head', 'c_pos', 'c_head'):
+        if k in g:
+            g[k] = np.ascontiguousarray(g[k], np.float32)
+    return g
+
+
+def _disc(rng, n, radius):
+    ang, rad = rng.uniform(0, 2 * math.pi, n), radius * np.sqrt(rng.uniform(0, 1, n))
+    return np.stack([rad * np.cos(ang), rad * np.sin(ang)], -1)
+
+
+def gen_radius_edges(name, seed=0):
+    """-> the case dict of a RADIUS_EDGES_CASES entry: the arrays of InfgenRadiusEdges (None: a null pointer), n_nodes (rows of off /
+    cnt), e_base.  Coordinates within +-200 m; every (query, candidate) pair clears MARGIN.  Cached: do not write to the result."""
+    if ('radius_edges', name, seed) in _CASES:
+        return _CASES['radius_edges', name, seed]
+    rng = np.random.default_rng([seed, sum(map(ord, name)), 31])
+    r = float(np.float32(RADIUS_EDGES_CASES[name][0]))
+    heads = lambda n: rng.uniform(-math.pi, math.pi, n).astype(np.float32)
+    if name == 'temporal':
+        A, T, W, N = 5, 20, 12, 7                 # N rows per column: the agents and two rows that are never a destination
+        pos = (rng.uniform(-150, 150, (A, 1, 2)) + np.cumsum(rng.uniform(-2.5, 2.5, (A, T, 2)), 1)).astype(np.float32)
+        inv = rng.uniform(size=(A, T)) < 0.4
+        hist = rng.uniform(size=(A, T)) > 0.25
+        hist[:, 0] = [1, 1, 0, 1, 1]
+        hist[2, :4] = 0                           # an agent whose history starts late
+        rowp = rng.permutation(N)[:A]
+        node_of = np.arange(T)[None, :] * N + rowp[:, None]
+        qa, qj = np.nonzero(hist)
+        g = _new_radius_case(name, T * N, q_node=node_of[qa, qj], q_pt=qa * T + qj, q_c0=qa * T + np.maximum(qj - W, 0), q_c1=qa * T + qj,
+                             p_pos=pos.reshape(-1, 2), p_head=heads(A * T), p_inv=inv.reshape(-1), c_ok=hist.reshape(-1),
+                             c_src=node_of.reshape(-1))
+        g['c_pos'], g['c_head'], g['c_inv'] = g['p_pos'], g['p_head'], g['p_inv']
+    elif name == 'agent':
+        sizes = [1, 70, 330]
+        start = np.concatenate([[0], np.cumsum(sizes)])
+        n = int(start[-1])
+        pos = np.zeros((n, 2), np.float32)
+        for s, A in enumerate(sizes):
+            centre = rng.uniform(-100, 100, 2)
+
+            def draw(k, A=A, centre=centre):
+                if A == 330:                      # 312 rows within 25 m of the centre (all inside each other's radius), 18 far out
+                    nc = 312 if k is None else k
+                    p = centre + _disc(rng, nc, 25.0)
+                    if k is None:
+                        p = np.concatenate([p, centre + rng.uniform(-95, 95, (A - nc, 2))])[rng.permutation(A)]
+                    return p.astype(np.float32)
+                return (centre + rng.uniform(-80, 80, (A if k is None else k, 2))).astype(np.float32)
+            pos[start[s]:start[s + 1]] = _resample(rng, draw, _cloud_offenders(r))
+        ok = rng.uniform(size=n) > 0.12
+        ok[0] = True
+        if ok.sum() % 4 == 0:
+            ok[start[2] + 5] = not ok[start[2] + 5]
+        qd = np.nonzero(ok)[0]
+        scene = np.searchsorted(start, qd, side='right') - 1
+        inv = rng.uniform(size=n) < 0.3
+        g = _new_radius_case(name, n, q_node=qd, q_pt=qd, q_c0=start[scene], q_c1=start[scene + 1], q_self=qd, p_pos=pos, p_head=heads(n),
+                             p_inv=inv, c_ok=ok)
+        g['c_pos'], g['c_head'], g['c_inv'] = g['p_pos'], g['p_head'], g['p_inv']
+    elif name == 'seed_pair':
+        NS, sizes = 3, [40, 90]                   # scene-contiguous rows: the agents, then NS seed rows at the ego's pose
+        grp = np.concatenate([[0], np.cumsum([A + NS for A in sizes])])
+        n = int(grp[-1])
+        pos, is_agent = np.zeros((n, 2), np.float32), np.zeros(n, bool)
+        for s, A in enumerate(sizes):
+            centre = rng.uniform(-80, 80, 2)
+            ego = rng.integers(0, A)
+            ext = 45.0 if s == 0 else 90.0
+
+            def draw(k, A=A, centre=centre, ext=ext):
+                return (centre + rng.uniform(-ext, ext, (A if k is None else k, 2))).astype(np.float32)
+
+            def offenders(p, ego=ego):            # the seed rows sit at the ego: only the distances to the ego decide
+                d2 = ((p.astype(np.float64) - p[ego].astype(np.float64)[None]) ** 2).sum(-1)
+                bad = _pairs_near(d2, r)
+                return np.nonzero(bad)[0]
+            p = _resample(rng, draw, offenders)
+            pos[grp[s]:grp[s] + A] = p
+            pos[grp[s] + A:grp[s + 1]] = p[ego]
+            is_agent[grp[s]:grp[s] + A] = True
+        ok = is_agent & (rng.uniform(size=n) > 0.1)
+        qs = np.nonzero(~is_agent)[0]
+        scene = np.searchsorted(grp, qs, side='right') - 1
+        width = max(sizes) + NS
+        pair = (rng.uniform(size=(len(qs), width)) > 0.35).astype(np.uint8)
+        pair_off = np.arange(len(qs)) * width
+        pair_off[[1, 4]] = -1                     # one seed row of each scene without a pair filter
+        g = _new_radius_case(name, n, q_node=qs, q_pt=qs, q_c0=grp[scene], q_c1=grp[scene + 1], q_pair_off=pair_off, p_pos=pos,
+                             p_head=heads(n), p_inv=rng.uniform(size=n) < 0.3, c_ok=ok, pair_ok=pair, e_base=1000)
+        g['c_pos'], g['c_head'], g['c_inv'] = g['p_pos'], g['p_head'], g['p_inv']
+    elif name == 'map':
+        n_map, n_ag = [200, 0, 200], [12, 9, 6]
+        mp = np.concatenate([[0], np.cumsum(n_map)])
+        ag = np.concatenate([[0], np.cumsum(n_ag)])
+        M, n = int(mp[-1]), int(ag[-1])
+        map_pos, pos = np.zeros((M, 2), np.float32), np.zeros((n, 2), np.float32)
+        for s in range(3):
+            centre = rng.uniform(-60, 60, 2)
+            map_pos[mp[s]:mp[s + 1]] = (centre + rng.uniform(-90, 90, (n_map[s], 2))).astype(np.float32)
+            fixed = map_pos[mp[s]:mp[s + 1]]
+
+            def draw(k, s=s, centre=centre):
+                return (centre + rng.uniform(-125, 125, (n_ag[s] if k is None else k, 2))).astype(np.float32)
+            pos[ag[s]:ag[s + 1]] = _resample(rng, draw, _cloud_offenders(r, fixed, r, self_pairs=False))
+        scene = np.repeat(np.arange(3), n_ag)
+        inv = np.arange(n) % 3 == 1
+        g = _new_radius_case(name, n + 3, q_node=np.arange(n), q_pt=np.arange(n), q_c0=mp[scene], q_c1=mp[scene + 1], p_pos=pos,
+                             p_head=heads(n), p_inv=inv, c_pos=map_pos, c_head=heads(M))
+    else:
+        assert name == 'map_graph'
+        sizes = [150, 1]
+        start = np.concatenate([[0], np.cumsum(sizes)])
+        n = int(start[-1])
+        pos = np.zeros((n, 2), np.float32)
+        for s, Mn in enumerate(sizes):
+            centre = rng.uniform(-100, 100, 2)
+
+            def draw(k, Mn=Mn, centre=centre):
+                if Mn == 150:                     # 115 tokens within 8 m of the centre, 35 spread out
+                    nc = 115 if k is None else k
+                    p = centre + _disc(rng, nc, 8.0)
+                    if k is None:
+                        p = np.concatenate([p, centre + rng.uniform(-95, 95, (Mn - nc, 2))])[rng.permutation(Mn)]
+                    return p.astype(np.float32)
+                return (centre + rng.uniform(-95, 95, (Mn if k is None else k, 2))).astype(np.float32)
+            pos[start[s]:start[s + 1]] = _resample(rng, draw, _cloud_offenders(r))
+        scene = np.repeat(np.arange(2), sizes)
+        g = _new_radius_case(name, n, q_node=np.arange(n), q_pt=np.arange(n), q_c0=start[scene], q_c1=start[scene + 1], q_self=np.arange(n),
+                             p_pos=pos, p_head=heads(n))
+        g['c_pos'], g['c_head'] = g['p_pos'], g['p_head']
+    _CASES['radius_edges', name, seed] = g
+    return g
+
+
+def gen_strict_radius_edges():
+    """gen_strict_radius's exact-coordinate points as infgen_radius_edges cases: one query at the origin over all five points, self
+    dropped.  -> [(case, index of the point at exactly the rounded radius, present?)]; the margin does not hold here by design"""
+    pts, cases = gen_strict_radius()
+    n = len(pts)
+    out = []
+    for r, i, present in cases:
+        g = dict(name='strict', n_nodes=1, radius=float(r), K=16, gap_rule=0, index_diff=0, e_base=0, q_self=np.zeros(1, np.int32),
+                 q_pair_off=None, p_inv=None, c_inv=None, c_ok=None, c_src=None, pair_ok=None, q_node=np.zeros(1, np.int32),
+                 q_pt=np.zeros(1, np.int32), q_c0=np.zeros(1, np.int32), q_c1=np.full(1, n, np.int32), p_pos=pts.copy(),
+                 p_head=np.zeros(n, np.float32), c_pos=pts.copy(), c_head=np.zeros(n, np.float32))
+        out.append((g, i, present))
+    return out
+
+
+MOTION_FEATURES_SHAPES = [(7, 1), (3, 2), (37, 19)]
+
+
+def gen_motion_features(seed=0):
+    """-> [dict(pos [rows][T][2], head, state, gap_mask)] for MOTION_FEATURES_SHAPES (37 * 19 = 703 elements: not a multiple of the
+    256-thread workgroup).  Poses a random walk within +-60 m of the origin with steps up to 9 m, the last column of every row a
+    jump to the far side (|coordinate| up to 200 m): a column 0 that reads across the row boundary shows.  States over all four
+    values with hand-set rows, so that every rule, every pair of rules that can coincide and EXIT occur at t = 0 and at t > 0; the
+    gap mask (the GPU test also runs without it) hits every rule.  Cached: do not write to the result."""
+    if ('motion_features', seed) in _CASES:
+        return _CASES['motion_features', seed]
+    out = []
+    for rows, T in MOTION_FEATURES_SHAPES:
+        rng = np.random.default_rng([seed, rows, T, 808])
+        pos = rng.uniform(-60, 60, (rows, 1, 2)) + np.cumsum(rng.uniform(-9, 9, (rows, T, 2)), 1)
+        far = np.where(pos[:, -1] >= 0, -1.0, 1.0) * rng.uniform(120, 200, (rows, 2))
+        pos[:, -1] = far
+        state = rng.choice([INVALID, VALID, VALID, ENTER, EXIT], (rows, T))
+        gm = rng.uniform(size=(rows, T)) < 0.25
+        # hand-set heads of rows: (state at t = 0, mask at t = 0[, state at t = 1, mask at t = 1])
+        hand = [(INVALID, 0, VALID, 0), (VALID, 0, INVALID, 0), (ENTER, 0, EXIT, 0), (EXIT, 0, INVALID, 1), (INVALID, 1, INVALID, 1),
+                (ENTER, 1, VALID, 1), (VALID, 1, EXIT, 1), (INVALID, 0, ENTER, 1), (EXIT, 1, EXIT, 0), (INVALID, 0, INVALID, 0)]
+        for a, hs in enumerate(hand[:rows]):
+            state[a, 0], gm[a, 0] = hs[0], hs[1]
+            if T > 1:
+                state[a, 1], gm[a, 1] = hs[2], hs[3]
+        out.append(dict(pos=pos.astype(np.float32), head=rng.uniform(-math.pi, math.pi, (rows, T)).astype(np.float32),
+                        state=state.astype(np.int32), gap_mask=gm.astype(np.uint8)))
+    _CASES['motion_features', seed] = out
+    return out

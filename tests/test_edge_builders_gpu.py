@@ -10,39 +10,10 @@ import pytest
 import torch
 
 import graph_ref as gr
+from graph_ref import compare_lists
 from gpu_blocks import SENT_F, SENT_I, Edges, dev, device_block, lib_and_check
 
 pytestmark = pytest.mark.gpu
-
-
-def compare_lists(kind, off, cnt, src, raw, ref, cap=None, written=None):
-    """per destination row: count, the source list in order, raw features within the bars, rule constants exact.  With cap: rows
-    whose range passes it are compared for their count only (written = False) or must report cnt = 0 (written = None: the compacting
-    kernels).  -> the largest device errors (distance, bearing, heading difference)"""
-    err = np.zeros(3)
-    for row, r in enumerate(ref):
-        want_src, want_raw = r[0], np.asarray(r[1], np.float64)
-        n = len(want_src)
-        over = cap is not None and off[row] + n > cap
-        if over and written is None:
-            assert cnt[row] == 0, (kind, row)
-            continue
-        assert cnt[row] == n, (kind, row, cnt[row], n)
-        if n == 0 or over:
-            continue
-        o = off[row]
-        assert 0 <= o and (cap is None or o + n <= cap)
-        assert np.array_equal(src[o:o + n], want_src), (kind, row, src[o:o + n], want_src)
-        got = raw[o:o + n].astype(np.float64)
-        e = [np.abs(got[:, 0] - want_raw[:, 0]).max(), gr.ang_err(got[:, 1], want_raw[:, 1]).max(), gr.ang_err(got[:, 2], want_raw[:, 2]).max()]
-        assert e[0] <= gr.BAR_DIST and e[1] <= gr.BAR_BEARING and e[2] <= gr.BAR_DTH, (kind, row, e)
-        assert np.array_equal(got[:, 3], want_raw[:, 3]), (kind, row)
-        if len(r) > 2 and r[2].any():                  # gap rules: -1 / 1 / -2, and the distance float32(sqrt 2) / float32(2 sqrt 2)
-            dth_c, dist_c = (r[2] & gr.RULED_DTH) != 0, (r[2] & gr.RULED_DIST) != 0
-            assert np.array_equal(got[dth_c, 2], want_raw[dth_c, 2]), (kind, row, 'a gap-rule constant is not exact')
-            assert np.array_equal(raw[o:o + n][dist_c, 0], want_raw[dist_c, 0].astype(np.float32)), (kind, row, 'a gap-rule distance is not exact')
-        err = np.maximum(err, e)
-    return err
 
 
 # ------------------------------------------------------------------------------------------------ infgen_map_graph

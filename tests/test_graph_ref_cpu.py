@@ -1,7 +1,8 @@
 """Anchors of tests/graph_ref.py (the plain float64 reference of the edge builders and insertion kernels) and of the input
 generators the GPU tests use: the reference agrees with the oracle's helpers, with the reference project's own edge lists
 (tests/golden/*_internals.npz) and with torch's softmax -> topk -> cumsum; every generator clears its ambiguity margin and reaches
-the branch it is meant for; the fp32 figures the device bars are derived from still hold."""
+the branch it is meant for; the fp32 figures the device bars are derived from still hold; the deliberately wrong variants of the
+forward's two references fail the comparison the GPU tests apply."""
 import math
 import os
 
@@ -557,3 +558,231 @@ def test_step_figures_are_the_recorded_ones():
     assert gr.GRID_MARGIN == 10 * gr.BAR_STEP_POS == 40 * gr.FP32_ERR_STEP_POS
     assert (gr.BAR_STEP_HEAD, gr.BAR_MOTION_NORM, gr.BAR_MOTION_BEARING) == (4 * gr.FP32_ERR_STEP_HEAD, 4 * gr.FP32_ERR_MOTION_NORM,
                                                                            4 * gr.FP32_ERR_MOTION_BEARING)
+
+
+# ------------------------------------------------------------------------------------------------ teacher-forced forward: edge builder, motion features
+def _found(g, q, k=None):
+    """candidate indices the radius call of query q finds (before the filters), all of them with k = a large number"""
+    c0, c1 = int(g['q_c0'][q]), int(g['q_c1'][q])
+    return c0 + gr.first_k_within(g['p_pos'][g['q_pt'][q]], g['c_pos'][c0:c1], g['radius'], g['K'] if k is None else k)[0]
+
+
+def _passes(g, q, m):
+    """the emit filters of query q on candidate indices m"""
+    keep = np.ones(len(m), bool)
+    if g['q_self'] is not None:
+        keep &= m != g['q_self'][q]
+    if g['c_ok'] is not None:
+        keep &= g['c_ok'][m] != 0
+    if g['pair_ok'] is not None and g['q_pair_off'][q] >= 0:
+        keep &= g['pair_ok'].reshape(-1)[g['q_pair_off'][q] + m - g['q_c0'][q]] != 0
+    return keep
+
+
+def _validity_combinations(g, ref):
+    """the (source invalid, query invalid) pairs over all emitted edges; indices recovered from a run without c_src"""
+    plain = gr.radius_edges_ref(dict(g, c_src=None))[0]
+    combos = set()
+    for q, node in enumerate(g['q_node']):
+        m = plain[node][0]
+        assert len(m) == len(ref[node][0])
+        d_inv = bool(g['p_inv'][g['q_pt'][q]]) if g['p_inv'] is not None else False
+        s_inv = g['c_inv'][m] != 0 if g['c_inv'] is not None else np.zeros(len(m), bool)
+        combos |= {(bool(s), d_inv) for s in s_inv}
+    return combos
+
+
+@pytest.mark.parametrize('name', list(gr.RADIUS_EDGES_CASES))
+def test_radius_edges_generator(name):
+    """the margin holds for every (query, candidate) pair, the case reaches what RADIUS_EDGES_CASES says it is for, coordinates stay
+    within +-200 m, and the fp32 figures of the raw features stay within the recorded ones (the device bars do not move)"""
+    g = gr.gen_radius_edges(name)
+    ref, gap = gr.radius_edges_ref(g)
+    assert gap > gr.MARGIN, gap
+    assert max(np.abs(g['p_pos']).max(), np.abs(g['c_pos']).max()) <= 200.0
+    nq, K = len(g['q_node']), g['K']
+    assert len(set(g['q_node'].tolist())) == nq and len(ref) == g['n_nodes']
+    width = g['q_c1'] - g['q_c0']
+    n_in = np.asarray([len(_found(g, q, 10 ** 9)) for q in range(nq)])
+    found = [_found(g, q) for q in range(nq)]
+    dropped = [(~_passes(g, q, found[q])).sum() for q in range(nq)]
+    combos = _validity_combinations(g, ref)
+    if name == 'temporal':
+        with np.errstate(over='ignore'):
+            assert np.isinf(np.float32(g['radius']) * np.float32(g['radius'])) and np.isfinite(np.float32(g['radius']))
+        assert (g['p_pos'].shape[0], K, g['gap_rule'], g['index_diff']) == (5 * 20, 12, 1, 1)
+        assert (width == 0).any() and width.max() == 12 and (n_in == width).all()           # empty ranges at column 0; all in radius
+        assert max(dropped) > 0 and (g['c_ok'] == 0).any()                                  # holes of the history mask inside a window
+        assert not np.array_equal(g['c_src'], np.arange(len(g['c_src']))) and (g['q_node'] != g['q_pt']).any()
+        assert combos == {(False, False), (False, True), (True, False), (True, True)}
+        assert nq < g['n_nodes']                                                            # nodes without a query
+        diffs = np.concatenate([r[1][:, 3] for r in ref])
+        assert diffs.min() == -12 and diffs.max() == -1
+    elif name == 'agent':
+        assert sorted(set(width.tolist())) == [1, 70, 330] and (g['q_self'] == g['q_pt']).all() and (K, g['gap_rule']) == (301, 1)
+        assert nq % 4 != 0 and nq < g['n_nodes']
+        cut = [q for q in range(nq) if n_in[q] > K]
+        assert len(cut) >= 100                                                              # the cap truncates ...
+        assert all((found[q][-1] - g['q_c0'][q]) // 64 >= 4 for q in cut)                   # ... after several 64-candidate chunks
+        assert any((g['c_ok'][found[q]] == 0).any() and g['q_self'][q] in found[q] for q in cut)     # found, counted, not emitted
+        assert any(g['q_self'][q] not in found[q] for q in cut)                             # and a query beyond its own first K
+        assert combos == {(False, False), (False, True), (True, False), (True, True)}
+        assert any(len(ref[node][0]) == 0 for node in g['q_node'])                          # the scene of one agent: self only
+    elif name == 'seed_pair':
+        assert (K, g['gap_rule']) == (300, 0) and g['e_base'] > 0
+        assert (g['q_pair_off'] == -1).any() and (g['q_pair_off'] >= 0).any() and (g['q_c0'] > 0).any()
+        assert width.max() > 64 and max(len(f) for f in found) > 0
+        for q in range(nq):                       # the pair filter alone drops candidates that pass c_ok, where it applies
+            m = found[q][g['c_ok'][found[q]] != 0]
+            assert (~_passes(g, q, m)).any() == (g['q_pair_off'][q] >= 0)
+        assert any(np.abs(r[1][:, 0]).min(initial=1.0) == 0.0 for r in ref)                  # the ego under its seed row: d = 0
+    elif name == 'map':
+        assert (K, g['gap_rule']) == (5, 2) and g['c_inv'] is None and g['c_ok'] is None and g['q_self'] is None
+        assert sorted(set(width.tolist())) == [0, 200]
+        assert (n_in > K).any() and ((n_in < K) & (n_in > 0)).any()
+        assert combos == {(False, False), (False, True)}
+        assert nq < g['n_nodes']
+    else:
+        assert g['p_inv'] is None and g['c_inv'] is None and K == 101 and sorted(set(width.tolist())) == [1, 150]
+        assert (n_in > K).sum() >= 50 and (n_in < K).any()
+        assert any(g['q_self'][q] in found[q] for q in range(nq) if n_in[q] > K)
+        assert any(g['q_self'][q] not in found[q] for q in range(nq) if n_in[q] > K)
+    f32 = gr.radius_edges_ref(g, f=np.float32)[0]
+    e = gr.raw_errors(ref, f32)
+    print(f'radius_edges {name}: {sum(len(r[0]) for r in ref)} edges, fp32 numpy errors dist {e[0]:.4g} bearing {e[1]:.4g} dth {e[2]:.4g}')
+    assert e[0] <= gr.FP32_ERR_DIST and e[1] <= gr.FP32_ERR_BEARING and e[2] <= gr.FP32_ERR_DTH
+
+
+@pytest.mark.parametrize('name', list(gr.RADIUS_EDGES_CASES))
+def test_radius_edges_ref_agrees_with_the_oracle_helpers(name):
+    """the found sets against oracle.rollout_oracle.radius_first_k (filters applied here, after the call), the gap rules against
+    oracle.forward_oracle._gap_rules (rule 2, two assignments in the reference, by hand)"""
+    from oracle.forward_oracle import _gap_rules
+    from oracle.rollout_oracle import radius_first_k, wrap_angle
+    g = gr.gen_radius_edges(name)
+    plain = gr.radius_edges_ref(dict(g, c_src=None))[0]
+    ref = gr.radius_edges_ref(g)[0]
+    t64 = lambda a: torch.from_numpy(np.asarray(a)).double()
+    for q, node in enumerate(g['q_node']):
+        qp, c0, c1 = int(g['q_pt'][q]), int(g['q_c0'][q]), int(g['q_c1'][q])
+        _, xi = radius_first_k(t64(g['c_pos'][c0:c1]), t64(g['p_pos'][qp][None]), g['radius'], g['K'])
+        m = c0 + xi.numpy()
+        m = m[_passes(g, q, m)]
+        assert np.array_equal(m, plain[node][0]), (name, q)
+        assert np.array_equal(g['c_src'][m] if g['c_src'] is not None else m, ref[node][0])
+        if len(m) == 0:
+            continue
+        dp = t64(g['c_pos'][m]) - t64(g['p_pos'][qp])[None]
+        dth = wrap_angle(t64(g['c_head'][m]) - float(g['p_head'][qp]))
+        s_inv = torch.from_numpy(g['c_inv'][m] != 0) if g['c_inv'] is not None else torch.zeros(len(m), dtype=torch.bool)
+        d_inv = torch.full((len(m),), bool(g['p_inv'][qp]) if g['p_inv'] is not None else False)
+        if g['gap_rule'] == 1:
+            _gap_rules(dp, dth, s_inv, d_inv)
+        elif g['gap_rule'] == 2:
+            dp[d_inv], dth[d_inv] = gr.MOTION_GAP, gr.HEADING_GAP
+        assert np.abs(dp.norm(dim=-1).numpy() - ref[node][1][:, 0]).max() < 1e-12
+        assert gr.ang_err(dth.numpy(), ref[node][1][:, 2]).max() < 1e-12
+
+
+def _differs(name, lists, ref):
+    """does the device comparison (compare_lists with its bars) tell `lists`, packed as fp32 device arrays, from the reference?"""
+    off, cnt, src, raw, _ = gr.pack_lists(lists)
+    try:
+        gr.compare_lists(name, off, cnt, src, raw, ref)
+    except AssertionError:
+        return True
+    return False
+
+
+def test_radius_edges_mutants_are_told_apart():
+    """every deliberate deviation of radius_edges_ref fails, on at least one case, the very comparison the GPU test applies to the
+    kernel's output - and an fp32 evaluation of the unmutated reference passes it on every case"""
+    cases = [(n, gr.gen_radius_edges(n)) for n in gr.RADIUS_EDGES_CASES] + [(f'strict{k}', c[0]) for k, c in enumerate(gr.gen_strict_radius_edges())]
+    caught = {m: [] for m in gr.RADIUS_EDGES_MUTANTS}
+    for name, g in cases:
+        ref = gr.radius_edges_ref(g)[0]
+        assert not _differs(name, gr.radius_edges_ref(g, f=np.float32)[0], ref), name
+        for m in gr.RADIUS_EDGES_MUTANTS:
+            if _differs(name, gr.radius_edges_ref(g, mutate=m)[0], ref):
+                caught[m].append(name)
+    print('radius_edges mutants caught by:', caught)
+    assert all(caught.values()), caught
+    # and by the case meant for each
+    assert 'agent' in caught['filtered_not_counted'] and 'seed_pair' in caught['pair_abs_index'] and 'temporal' in caught['index_diff_sign']
+    assert {'temporal', 'agent'} <= set(caught['rule1_dst_dth']) and 'map' in caught['rule2_keep_dth']
+    assert {'temporal', 'agent', 'map'} <= set(caught['bearing_pre_override'])
+    assert any(n.startswith('strict') for n in caught['le_radius'])
+
+
+def test_strict_radius_edges_cases():
+    for g, i, present in gr.gen_strict_radius_edges():
+        ref, gap = gr.radius_edges_ref(g)
+        assert (i in ref[0][0]) == present and 0 not in ref[0][0]
+        assert present or gap == 0.0                  # (the point at exactly r: the margin does not hold here by design)
+
+
+def test_motion_features_generator():
+    """shapes, the far last column, every rule and every pair of rules that can coincide at t = 0 and at t > 0, EXIT at both; the
+    motion vectors agree with oracle.forward_oracle.build_vector; the fp32 figures are the recorded ones"""
+    from oracle.forward_oracle import build_vector
+    from oracle.rollout_oracle import angle_between
+    cases = gr.gen_motion_features()
+    assert [c['state'].shape for c in cases] == gr.MOTION_FEATURES_SHAPES == [(7, 1), (3, 2), (37, 19)] and (37 * 19) % 256
+    seen0, seen1 = set(), set()
+    en = ea = 0.0
+    for c in cases:
+        st, gm = c['state'], c['gap_mask'] != 0
+        rows, T = st.shape
+        assert np.abs(c['pos']).max() <= 200 and np.abs(c['pos'][:, -1]).min() >= 120
+        assert (np.abs(c['pos'][:, :-1]).max() < 200) if T > 1 else True
+        inv = st == gr.INVALID
+        pinv = np.concatenate([np.zeros((rows, 1), bool), inv[:, :-1]], 1)
+        for t in range(T):
+            for a in range(rows):
+                if t == 0:
+                    fired = (('invalid',) if inv[a, 0] else ()) + (('enter',) if st[a, 0] == gr.ENTER else ()) + (('mask',) if gm[a, 0] else ())
+                    seen0.add(fired)
+                    seen0.add(('exit',) if st[a, 0] == gr.EXIT else fired)
+                else:
+                    fired = (('invalid',) if inv[a, t] else ()) + (('enter',) if pinv[a, t] and not inv[a, t] else ()) + \
+                            (('leave',) if not pinv[a, t] and inv[a, t] else ()) + (('mask',) if gm[a, t] else ())
+                    seen1.add(fired)
+                    seen1.add(('exit',) if st[a, t] == gr.EXIT else fired)
+        for mask in (None, c['gap_mask']):
+            ref, ruled = gr.motion_features_ref(c['pos'], c['head'], st, mask, with_ruled=True)
+            f32 = gr.motion_features_ref(c['pos'], c['head'], st, mask, f=np.float32)
+            en = max(en, np.abs(ref[..., 0] - f32[..., 0]).max())
+            ea = max(ea, gr.ang_err(ref[..., 1], f32[..., 1]).max())
+            gr.compare_motion(f32.astype(np.float32), ref, ruled)
+            assert (ref[..., 2:] == 0).all()
+            mv, hv = build_vector(torch.from_numpy(c['pos']).double(), torch.from_numpy(c['head']).double(), torch.from_numpy(st))
+            if mask is not None:
+                mv[torch.from_numpy(gm)] = gr.MOTION_GAP                                    # agent_decoder.py:1327
+            assert np.abs(mv.norm(dim=-1).numpy() - ref[..., 0]).max() < 1e-12
+            assert gr.ang_err(angle_between(hv, mv).numpy(), ref[..., 1]).max() < 1e-12
+            want = np.where((mv == -2).all(-1).numpy(), 2, np.where((mv.abs() == 1).all(-1).numpy(), 1, 0))
+            assert np.array_equal(ruled, want)
+    assert seen0 >= {(), ('invalid',), ('enter',), ('mask',), ('invalid', 'mask'), ('enter', 'mask'), ('exit',)}, seen0
+    assert seen1 >= {(), ('invalid',), ('enter',), ('invalid', 'leave'), ('mask',), ('invalid', 'mask'), ('enter', 'mask'),
+                     ('invalid', 'leave', 'mask'), ('exit',)}, seen1
+    print(f'motion features: fp32 numpy errors norm {en:.4g} angle {ea:.4g}')
+    assert en <= gr.FP32_ERR_MOTION_FEAT_NORM and ea <= gr.FP32_ERR_MOTION_FEAT_ANGLE
+    assert (gr.BAR_MOTION_FEAT_NORM, gr.BAR_MOTION_FEAT_ANGLE) == (4 * gr.FP32_ERR_MOTION_FEAT_NORM, 4 * gr.FP32_ERR_MOTION_FEAT_ANGLE)
+
+
+def test_motion_features_mutants_are_told_apart():
+    """every deliberate deviation of motion_features_ref fails, on at least one (shape, mask) input, the comparison the GPU test
+    applies (compare_motion)"""
+    caught = {m: [] for m in gr.MOTION_FEATURES_MUTANTS}
+    for c in gr.gen_motion_features():
+        for mask in (None, c['gap_mask']):
+            ref, ruled = gr.motion_features_ref(c['pos'], c['head'], c['state'], mask, with_ruled=True)
+            for m in gr.MOTION_FEATURES_MUTANTS:
+                mut = gr.motion_features_ref(c['pos'], c['head'], c['state'], mask, mutate=m).astype(np.float32)
+                try:
+                    gr.compare_motion(mut, ref, ruled)
+                except AssertionError:
+                    caught[m].append((c['state'].shape, mask is not None))
+    print('motion_features mutants caught by:', caught)
+    assert all(caught.values()), caught
+    assert ((7, 1), False) in caught['t0_reads_previous_row']          # a single column: every element but the first reads across
