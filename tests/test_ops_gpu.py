@@ -464,8 +464,8 @@ def test_edge_fused_instantiations_give_the_same_bits(env, n_dst, n_src, max_deg
     rows = 3 groups: the two-group kernel runs a tile with an absent half and a partial last group; lists of up to 130 edges: a
     second index chunk and trips with dead slots for every G; 16 rows / 9 edges: lists shorter than one trip.  And against
     k_edge_fused3 (edge_kernel = 2) within the fp32 summation-order bound of test_edge_fused3_equals_the_vector_loop, so that
-    four identical wrong answers do not pass.  (Packed 24-bit rows, R24 = true: tests/test_rollout_gpu.py::
-    test_packed_rhat_rows_match_fp32_rows only.)"""
+    four identical wrong answers do not pass.  (Packed 24-bit rows, R24 = true, and every instantiation against float64:
+    tests/test_edge_attn_gpu.py.)"""
     import ctypes as C
     from infgen_amd import _lib
     rng = np.random.default_rng(n_dst + max_deg)
