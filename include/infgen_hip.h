@@ -702,6 +702,53 @@ int infgen_step_score(const float* pos, const float* head, const int* state, con
 int infgen_token_mask_score(int handle, float* step_score, int steps, unsigned char* score_row, const float* shape, const float* records,
                             const int* n_records, int rec_cap, int copies, int sweep, float road_margin, const int* types, float dt);
 
+/* observations: OBSERVATIONS, what a controller reads per commanded row - for each of the N rows named, in the row's own frame, the
+ * row's own features, its K nearest live agents and its Km nearest map tokens (k_observe_rows: one launch, no host read, no
+ * atomics; the scene is only read).  fp32 throughout, no fused multiply-add; world coordinates enter only through differences formed
+ * directly from stored values, pos[j] - pos[i] and map_pos[m] - pos[i] (the rule of the blocks above).
+ *   inputs   the scene arrays laid out like InfgenRollout's ([S][T][A_cap], A_cap need not be a multiple of 32, at most
+ *       INFGEN_Q_MAX_AGENTS), type [S * A_cap], shape [S * A_cap][3], column c in 0 .. T - 1, dt > 0; the map map_pos [S0][M_cap][2],
+ *       map_orient [S0][M_cap], map_type [S0][M_cap] (long long, as infgen_road_records_from_map takes it), n_map [S0], S0 = S / copies:
+ *       scene slot s reads map scene s / copies.  obs_row: optional int32 [N] of global rows s * A_cap + i, any order, repeats
+ *       allowed; NULL: row n is n, and N must be S * A_cap.  K, Km in 0 .. INFGEN_OBS_MAX_K; radius, map_radius >= 0 or +inf.
+ *   live, frame   row i of slot s is LIVE at a column iff i < n_agents[s] and state[col][i] != 0 (the step scores' rule).  An
+ *       obs_row entry that is out of range or not live at c gets all-zero features, indices -1 and counts 0.  With
+ *       ci = cosf(head[c][i]), si = sinf(head[c][i]) a world difference (dx, dy) becomes x' = dx * ci + dy * si, y' = dy * ci - dx * si.
+ *       wrap(a) = r - pi, r = fmodf(a + pi, 2 pi), + 2 pi where negative (pi, 2 pi the nearest floats): the step scores', signed.
+ *       The VELOCITY of a row j live at c and, with c >= 1, at c - 1 is ((pos[c][j] - pos[c-1][j]) / dt) - difference, then
+ *       division, per component -, rotated into row i's frame; it is (0, 0) when c == 0 or j is not live at c - 1.
+ *   self_feat [N][INFGEN_OBS_SELF = 8]   0 live (0 / 1); 1, 2 the row's own velocity in its own frame; 3 wrap(head[c] - head[c-1]) / dt;
+ *       4, 5 length, width = shape[row][0], shape[row][1]; 6 the type as a float (0 vehicle, 1 pedestrian, 2 cyclist; others count as
+ *       0); 7 has-previous: 1 iff c >= 1 and the row is live at c - 1.  Entries 1 to 3 are 0 when entry 7 is.
+ *   neighbours   the candidates are the rows j != i of the same slot that are live at c; d2 = fl(fl(dx * dx) + fl(dy * dy)) with
+ *       dx = pos[c][j].x - pos[c][i].x and dy likewise; j is kept iff d2 <= fl(radius * radius) (+inf keeps all; a NaN d2 is never
+ *       kept).  Order: ascending d2, ties by ascending j; the first K are written.
+ *       nbr_feat [N][K][INFGEN_OBS_NBR = 10]: 0, 1 x', y' of (dx, dy); 2, 3 cos D = cj * ci + sj * si, sin D = sj * ci - cj * si from
+ *       cosf / sinf of the two headings (no wrap, no atan2); 4, 5 j's velocity in i's frame (an absolute velocity, not a relative
+ *       one); 6, 7 j's length, width; 8 j's type; 9 1.0.  nbr_index [N][K] int32 = j.  nbr_count [N] int32 = the number of
+ *       candidates inside the radius: it may exceed K, so a caller sees truncation.  Unused entries: features 0, index -1.
+ *   map tokens   the candidates are m < n_map[s / copies] (at most M_cap); d2 as above from map_pos[m] - pos[c][i]; kept iff
+ *       d2 <= fl(map_radius * map_radius); ascending d2, ties by ascending m; the first Km are written.
+ *       map_feat [N][Km][INFGEN_OBS_MAP = 6]: 0, 1 x', y'; 2, 3 cos D, sin D of map_orient[m] against the row's heading (formulas as
+ *       above); 4 (float)map_type[m]; 5 1.0.  map_index [N][Km], map_count [N] as for the neighbours.
+ * Every output entry has one writer and every selection is by distinct keys (d2, index): the result is bitwise reproducible.  For any
+ * content of obs_row, n_agents, n_map and state nothing outside the layouts is read or written (counts are clamped to 0 .. capacity).
+ * K = 0: nbr_feat and nbr_index may be NULL, and nbr_count too (no scan then; given, it is still the count).  Km = 0 likewise; the
+ * four map arrays may then be NULL (map_count, where given, is 0 without them).
+ * Refused: c outside 0 .. T - 1, K or Km outside 0 .. INFGEN_OBS_MAX_K, dt <= 0 or not finite, a radius that is negative or NaN,
+ * copies < 1 or not dividing S, a missing output (self_feat; with K > 0 the three nbr arrays; with Km > 0 the three map outputs and
+ * the four map inputs), an output that is not 16-byte aligned, A_cap beyond INFGEN_Q_MAX_AGENTS, N < 0, or N != S * A_cap without
+ * obs_row. */
+#define INFGEN_OBS_SELF 8
+#define INFGEN_OBS_NBR 10
+#define INFGEN_OBS_MAP 6
+#define INFGEN_OBS_MAX_K 64
+int infgen_observe_rows(const float* pos, const float* head, const int* state, const int* n_agents, const int* type, const float* shape,
+                        int S, int A_cap, int T, int c, float dt, const float* map_pos, const float* map_orient,
+                        const long long* map_type, const int* n_map, int M_cap, int copies, const int* obs_row, int N, int K,
+                        float radius, int Km, float map_radius, float* self_feat, float* nbr_feat, int* nbr_index, int* nbr_count,
+                        float* map_feat, int* map_index, int* map_count, void* stream);
+
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell
  *   infgen_point_edges      _build_a2sa_edge / _build_map2sa_edge for one query point per scene (:760-904):

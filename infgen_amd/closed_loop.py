@@ -21,7 +21,7 @@ from typing import Dict
 
 import torch
 
-from . import _lib, constraints
+from . import _lib, constraints, observe
 
 KIND_TOKEN, KIND_POSE = 0, 1
 
@@ -66,6 +66,7 @@ class ClosedLoopSession:
         self.cost = torch.zeros(S, A_cap, device=dev)
         self._kind = self._result = None
         self._look = None                               # lookahead()'s snapshot buffer, allocated at its first call
+        self._obs_rows, self._obs_out, self._obs_key = {}, None, None     # observe(frame='agent'): row lists, the last result
         self.t = 0
         self.steps = eng.cfg.num_decode_steps
         eng._refresh_opts(groups=True)
@@ -119,14 +120,26 @@ class ClosedLoopSession:
         raise ValueError(f'{what}: expected shape {(S, A_cap) + tuple(tail)} or {(S,) + tuple(tail)}, got {tuple(x.shape)}')
 
     # ------------------------------------------------------------------ the loop
-    def observe(self) -> Dict[str, torch.Tensor]:
+    def observe(self, frame: str = 'world', rows='controlled', neighbors: int = 8, radius: float = float('inf'),
+                map_tokens: int = 0, map_radius: float = float('inf')) -> Dict[str, torch.Tensor]:
         """the newest stored column as device tensors: ``pos`` [S, A_cap, 2], ``head``, ``state`` (0 = not in the scene), ``token``,
         ``type`` [S, A_cap], ``shape`` [S, A_cap, 3] (length, width, height), ``n_agents`` / ``ego_index`` [S], ``controlled``
         [S, A_cap] bool and ``column`` (int); with ``avoid_collisions`` also ``allowed_tokens`` [S, A_cap], the number of motion tokens
         every row was allowed at the step that just ran, before the empty-set fallback (0: every token collided); with ``stay_on_road`` the
         sizes of the final sets, the road masks' (0: every token of the row's collision or static set left the road).  Views of the engine's buffers wherever possible: no copy, no synchronisation - and
-        overwritten by later steps, a reset or a reload (clone what has to last)."""
+        overwritten by later steps, a reset or a reload (clone what has to last).
+
+        ``frame='agent'`` adds the agent-centric observation of that column (``RolloutEngine.observe_rows``: one launch,
+        no host read): ``obs_row`` [N] int32, the global rows s * A_cap + i observed, and per observed row ``self_feat`` [N, 8],
+        the ``neighbors`` nearest live agents within ``radius`` - ``nbr_feat`` [N, K, 10], ``nbr_index`` [N, K], ``nbr_count`` [N] -
+        and the ``map_tokens`` nearest map tokens within ``map_radius`` - ``map_feat`` [N, Km, 6], ``map_index``, ``map_count`` -, in
+        the row's own frame.  ``rows``: 'controlled' (the rows this session commands, in row order), 'all' or an int tensor of global
+        rows.  The list of controlled rows is built once per session, on the device, at the first such call - its length is the
+        one host read, none per step.  The result's tensors are the session's own and are written again by the next call of the
+        same sizes.  The arguments other than ``frame`` are read only with ``frame='agent'``."""
         self._check_open()
+        if frame not in ('world', 'agent'):
+            raise ValueError(f"frame must be 'world' or 'agent', not {frame!r}")
         eng, c = self.eng, self.eng.hc - 1 + self.t
         obs = dict(pos=eng.pos[:, c], head=eng.head[:, c], state=eng.state[:, c], token=eng.token[:, c], type=eng.atype,
                    shape=eng._shape10, n_agents=eng.n_agents, ego_index=eng.av, controlled=eng.replay_row.bool(), column=c)
@@ -138,7 +151,27 @@ class ClosedLoopSession:
             if self.t > 0:
                 obs['step_score'] = eng.step_score[:, self.t - 1]
             obs['score_row'] = eng.score_row
+        if frame == 'agent':
+            obs_row = self._observed_rows(rows)
+            out = self._obs_out if self._obs_out is not None and self._obs_key == (int(obs_row.numel()), neighbors, map_tokens) else None
+            self._obs_out = eng.observe_rows(c, rows=None if isinstance(rows, str) and rows == 'all' else obs_row, neighbors=neighbors,
+                                             radius=radius, map_tokens=map_tokens, map_radius=map_radius, out=out)
+            self._obs_key = (int(obs_row.numel()), neighbors, map_tokens)
+            obs.update(self._obs_out, obs_row=obs_row)
         return obs
+
+    def _observed_rows(self, rows) -> torch.Tensor:
+        """'controlled' | 'all' | int tensor -> int32 [N] global rows on the device ('controlled' and 'all': made once per session)"""
+        eng = self.eng
+        if isinstance(rows, str):
+            if rows not in ('controlled', 'all'):
+                raise ValueError(f"rows must be 'controlled', 'all' or an int tensor, not {rows!r}")
+            if rows not in self._obs_rows:
+                self._obs_rows[rows] = (torch.nonzero(eng.replay_row.reshape(-1)).reshape(-1).to(torch.int32) if rows == 'controlled'
+                                        else torch.arange(eng.S * eng.A_cap, device=eng.device, dtype=torch.int32))
+            return self._obs_rows[rows]
+        observe.check_rows(rows)
+        return rows.to(eng.device, torch.int32).contiguous()
 
     def command(self, tokens=None, poses=None, mask=None):
         """the controlled rows' command for step ``t``: ``tokens`` (motion-token ids, int) or ``poses`` (x, y, heading in the world

@@ -1670,6 +1670,51 @@ extern "C" int infgen_token_mask_score(int handle, float* step_score, int steps,
   return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.score = cfg; });
 }
 
+// ---------------------------------------------------------------------------------- observations
+// the argument checks of include/infgen_hip.h ("observations") and the one launch of k_observe_rows
+struct ObserveCfg { const float* shape; };
+static int launch_observe(const char* where, const ObserveArgs& a, void* stream) {
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "observe: S, A_cap and T must be positive");
+  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "observe: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.c < 0 || a.c >= a.T) return fail(where, "observe: column outside [0, T)");
+  if (a.K < 0 || a.K > OBS_MAX_K || a.Km < 0 || a.Km > OBS_MAX_K) return fail(where, "observe: K and Km must be in 0 .. INFGEN_OBS_MAX_K");
+  if (!std::isfinite(a.dt) || !(a.dt > 0.f)) return fail(where, "observe: dt must be finite and > 0");
+  if (!(a.radius >= 0.f) || !(a.map_radius >= 0.f)) return fail(where, "observe: a radius must be >= 0 (or +inf)");
+  if (a.copies < 1) return fail(where, "observe: copies must be at least 1");
+  if (a.S % a.copies) return fail(where, "observe: S must be a multiple of copies");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type || !a.shape) return fail(where, "observe: null scene array");
+  const long long rows = (long long)a.S * a.A_cap;
+  if (rows > 0x7fffffffLL) return fail(where, "observe: too many rows");
+  if (a.N < 0 || (!a.obs_row && a.N != rows)) return fail(where, "observe: N must be S * A_cap without obs_row, and never negative");
+  if (!a.self_feat) return fail(where, "observe: needs the output self_feat [N][8]");
+  if (a.K > 0 && (!a.nbr_feat || !a.nbr_index || !a.nbr_count)) return fail(where, "observe: K > 0 needs nbr_feat, nbr_index and nbr_count");
+  if (a.Km > 0 && (!a.map_feat || !a.map_index || !a.map_count)) return fail(where, "observe: Km > 0 needs map_feat, map_index and map_count");
+  if (a.Km > 0 && (!a.map_pos || !a.map_orient || !a.map_type || !a.n_map)) return fail(where, "observe: Km > 0 needs the map arrays");
+  if (a.map_pos && (!a.n_map || a.M_cap <= 0)) return fail(where, "observe: map_pos needs n_map and a positive M_cap");
+  if (misaligned16(a.self_feat, a.nbr_feat, a.nbr_index, a.nbr_count) || misaligned16(a.map_feat, a.map_index, a.map_count))
+    return fail(where, "observe: the outputs must be 16-byte aligned");
+  if (a.N == 0) return 0;
+  hipLaunchKernelGGL(k_observe_rows, dim3((unsigned)ceil_div(a.N, OB_WAVES)), dim3(64 * OB_WAVES), 0, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+
+extern "C" int infgen_observe_rows(const float* pos, const float* head, const int* state, const int* n_agents, const int* type,
+                                   const float* shape, int S, int A_cap, int T, int c, float dt, const float* map_pos,
+                                   const float* map_orient, const long long* map_type, const int* n_map, int M_cap, int copies,
+                                   const int* obs_row, int N, int K, float radius, int Km, float map_radius, float* self_feat,
+                                   float* nbr_feat, int* nbr_index, int* nbr_count, float* map_feat, int* map_index, int* map_count,
+                                   void* stream) {
+  const char* me = "infgen_observe_rows";
+  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, nullptr, type, 0};
+  ObserveArgs a = rider_args<ObserveArgs>(sc, ObserveCfg{shape});
+  a.c = c; a.dt = dt;
+  a.map_pos = map_pos; a.map_orient = map_orient; a.map_type = map_type; a.n_map = n_map; a.M_cap = M_cap; a.copies = copies;
+  a.obs_row = obs_row; a.N = N; a.K = K; a.Km = Km; a.radius = radius; a.map_radius = map_radius;
+  a.self_feat = self_feat; a.nbr_feat = nbr_feat; a.nbr_index = nbr_index; a.nbr_count = nbr_count;
+  a.map_feat = map_feat; a.map_index = map_index; a.map_count = map_count;
+  return launch_observe(me, a, stream);
+}
+
 // ---------------------------------------------------------------------------------- rollout context
 static SceneState scene_of(const InfgenRollout* r) {
   SceneState st;

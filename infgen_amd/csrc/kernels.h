@@ -706,6 +706,26 @@ struct ScoreArgs {
 };
 __global__ void k_step_score(ScoreArgs a);
 
+// observe_kernels.hip: the agent-frame observation of the rows named (include/infgen_hip.h, "observations"): own features, the K
+// nearest live agents and the Km nearest map tokens of every row, one wave per row
+constexpr int OB_WAVES = 4;             // rows a workgroup works on (one wave each)
+constexpr int OB_LIST = 512;            // 64-bit keys a wave keeps in LDS; a fuller list is cut down to its K best first
+constexpr int OBS_SELF = INFGEN_OBS_SELF, OBS_NBR = INFGEN_OBS_NBR, OBS_MAP = INFGEN_OBS_MAP, OBS_MAX_K = INFGEN_OBS_MAX_K;
+static_assert(OBS_MAX_K <= 64 && OB_LIST >= 2 * 64, "one lane per selected entry; a cut-down list has room for 64 more");
+struct ObserveArgs {
+  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the observed one
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+  float dt;
+  const float* map_pos; const float* map_orient; const long long* map_type; const int* n_map;   // [S / copies][M_cap](x2), [S / copies]
+  int M_cap, copies;
+  const int* obs_row; int N, K, Km;     // optional [N] global rows s * A_cap + i (NULL: row n is n)
+  float radius, map_radius;
+  float* self_feat; float* nbr_feat; int* nbr_index; int* nbr_count;     // [N][8], [N][K][10], [N][K], [N]
+  float* map_feat; int* map_index; int* map_count;                       // [N][Km][6], [N][Km], [N]
+};
+__global__ void k_observe_rows(ObserveArgs a);
+
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]
   const int* token;                          // [rows]

@@ -20,7 +20,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, constraints, logprob, modes, packing, scene_setup
+from . import _lib, constraints, logprob, modes, observe, packing, scene_setup
 from .scene_setup import EVAL_SHAPE, INVALID_SHAPE
 from .synth import INVALID, VALID, ENTER, EXIT, AGENT_SHAPE, RolloutConfig
 
@@ -2038,6 +2038,28 @@ class RolloutEngine:
         commanded / matched token's integration) or 'exact' (the commanded pose itself is stored)."""
         from .closed_loop import ClosedLoopSession
         return ClosedLoopSession(self, pose=pose, controlled=controlled)
+
+    def observe_rows(self, c: int, rows=None, neighbors: int = 8, radius: float = float('inf'), map_tokens: int = 0,
+                     map_radius: float = float('inf'), out=None) -> Dict[str, torch.Tensor]:
+        """the agent-frame observation of stored column ``c`` ("observations" of include/infgen_hip.h): for every row of
+        ``rows`` - int tensor [N] of global rows s * A_cap + i, None: all S * A_cap in order - ``self_feat`` [N, 8], the
+        ``neighbors`` nearest live agents within ``radius`` (``nbr_feat`` [N, K, 10], ``nbr_index`` [N, K], ``nbr_count`` [N]) and the
+        ``map_tokens`` nearest map tokens within ``map_radius`` (``map_feat`` [N, Km, 6], ``map_index`` [N, Km], ``map_count`` [N]),
+        in the row's own frame.  One launch of ``infgen_observe_rows`` on the engine's own buffers and the current stream, no host
+        read; ``dt`` is the step length the step scores use by default.  ``out``: an earlier result of the same sizes, whose
+        tensors are written again instead of new ones.  The scene is only read (``n_agents`` on the device, at launch), so an
+        engine with scenario insertion observes like any other."""
+        if getattr(self, '_shape10', None) is None:
+            raise ValueError('observe_rows needs the rows\' shapes: this engine has no shape array')
+        observe.check_params(c, self.T, constraints.STEP_SECONDS, neighbors, radius, map_tokens, map_radius, True)
+        observe.check_rows(rows)
+        r = None if rows is None else rows.to(self.device, torch.int32).contiguous()
+        N = self.S * self.A_cap if r is None else int(r.numel())
+        res = observe.outputs(N, int(neighbors), int(map_tokens), self.device, out)
+        observe.launch(self.lib, self.ops.stream, self.pos, self.head, self.state, self.n_agents, self.atype, self._shape10, c,
+                       constraints.STEP_SECONDS, self.map_pos, self.map_orient, self._map_cat[1], self.n_map, self.copies, r,
+                       neighbors, radius, map_tokens, map_radius, res)
+        return res
 
     def _run_graph(self, t0, t1):
         """the decode steps as a HIP-graph replay.  Replays launched into the LEGACY DEFAULT stream fault now and then on this

@@ -22,6 +22,10 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
                                                                                             -> sets (S A, token_size / 32) int32, allowed (S A,)
     torch.ops.infgen_hip.step_score(pos, head, state, n_agents, type, shape, c1, records?, n_records?, copies=1, sweep=1,
                                     road_margin=0, types=[1, 0, 1], dt=0.5)                 -> score (S, 8), flags (S, A) uint8
+    torch.ops.infgen_hip.observe_rows(pos, head, state, n_agents, type, shape, c, dt, map_pos?, map_orient?, map_type?, n_map?,
+                                      copies=1, rows=None, neighbors=8, radius=None (inf), map_tokens=0, map_radius=None (inf))
+                                                                                            -> self_feat (N, 8), nbr_feat (N, K, 10), nbr_index (N, K),
+                                                                                               nbr_count (N,), map_feat (N, Km, 6), map_index (N, Km), map_count (N,)
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -47,7 +51,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, observe
 from .engine import Ops, D
 
 _OPS = {}
@@ -526,6 +530,56 @@ def step_score(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_age
 def _(pos, head, state, n_agents, type, shape, c1, records=None, n_records=None, copies=1, sweep=1, road_margin=0.0, types=None,
       dt=0.5):
     return pos.new_empty(pos.shape[0], 8, dtype=torch.float32), pos.new_empty(pos.shape[0], pos.shape[2], dtype=torch.uint8)
+
+
+@torch.library.custom_op('infgen_hip::observe_rows', mutates_args=())
+def observe_rows(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+                 shape: torch.Tensor, c: int, dt: float, map_pos: Optional[torch.Tensor] = None,
+                 map_orient: Optional[torch.Tensor] = None, map_type: Optional[torch.Tensor] = None,
+                 n_map: Optional[torch.Tensor] = None, copies: int = 1, rows: Optional[torch.Tensor] = None, neighbors: int = 8,
+                 radius: Optional[float] = None, map_tokens: int = 0, map_radius: Optional[float] = None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the agent-frame observation of stored column ``c`` ("observations" of include/infgen_hip.h, ``infgen_observe_rows``): the
+    scene arrays as for ``step_score``, the map as ``map_pos`` (S / copies, M, 2), ``map_orient`` (S / copies, M), ``map_type``
+    (S / copies, M) and ``n_map`` (S / copies,) - all four or none -, ``rows`` (N,) int global row indices s * A + i (None: every
+    row in order), ``radius`` / ``map_radius`` None or inf: no limit (an operator schema cannot spell an infinite default, so None
+    stands for it).  Returns self_feat (N, 8), nbr_feat (N, neighbors, 10), nbr_index (N, neighbors) int32, nbr_count (N,) int32,
+    map_feat (N, map_tokens, 6), map_index (N, map_tokens) int32, map_count (N,) int32."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or tuple(head.shape) != tuple(pos.shape[:3]) or tuple(state.shape) != tuple(pos.shape[:3]):
+        raise ValueError('observe_rows takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,):
+        raise ValueError('observe_rows takes type (S, A), shape (S, A, 3), n_agents (S,)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    maps = (map_pos, map_orient, map_type, n_map)
+    if any(m is None for m in maps) != all(m is None for m in maps):
+        raise ValueError('map_pos, map_orient, map_type and n_map come together')
+    if map_pos is not None and (map_pos.dim() != 3 or map_pos.shape[0] != S // copies or map_pos.shape[2] != 2 or map_pos.shape[1] < 1
+                                or tuple(map_orient.shape) != tuple(map_pos.shape[:2]) or tuple(map_type.shape) != tuple(map_pos.shape[:2])
+                                or tuple(n_map.shape) != (S // copies,)):
+        raise ValueError('observe_rows takes map_pos (S / copies, M, 2), map_orient (S / copies, M), map_type (S / copies, M), n_map (S / copies,)')
+    radius, map_radius = (float('inf') if r is None else float(r) for r in (radius, map_radius))
+    observe.check_params(c, T, dt, neighbors, radius, map_tokens, map_radius, map_pos is not None)
+    observe.check_rows(rows)
+    dev = pos.device
+    ops = _ops(dev)
+    i32 = lambda t: None if t is None else t.to(dev, torch.int32).contiguous()
+    f32 = lambda t: None if t is None else _f32(t)
+    r = i32(rows)
+    res = observe.outputs(S * A if r is None else int(r.numel()), int(neighbors), int(map_tokens), dev)
+    observe.launch(ops.lib, ops.stream, _f32(pos), _f32(head), i32(state), i32(n_agents), i32(type), _f32(shape), c, dt, f32(map_pos),
+                   f32(map_orient), None if map_type is None else map_type.to(dev, torch.int64).contiguous(), i32(n_map), copies, r,
+                   neighbors, radius, map_tokens, map_radius, res)
+    return tuple(res[k] for k in observe.KEYS)
+
+
+@observe_rows.register_fake
+def _(pos, head, state, n_agents, type, shape, c, dt, map_pos=None, map_orient=None, map_type=None, n_map=None, copies=1, rows=None,
+      neighbors=8, radius=None, map_tokens=0, map_radius=None):
+    N = pos.shape[0] * pos.shape[2] if rows is None else rows.shape[0]
+    f, i = (lambda *s: pos.new_empty(*s, dtype=torch.float32)), (lambda *s: pos.new_empty(*s, dtype=torch.int32))
+    return (f(N, observe.SELF), f(N, neighbors, observe.NBR), i(N, neighbors), i(N), f(N, map_tokens, observe.MAP), i(N, map_tokens), i(N))
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
