@@ -459,6 +459,17 @@ int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless, void* stre
 int infgen_decode_step(const InfgenRollout* r, int t, void* stream);
 /* steps t0 .. t1-1 back to back (one host call per rollout) */
 int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream);
+/* The split mode of infgen_rollout_run: a large batch runs as two halves of S / 2 scenes on two streams of the
+ * library's own, forked from `stream` at entry and joined to it at exit - the caller sees one ordered call and, per scene, the same
+ * kernels on the same rows, bit for bit.  The second half's step starts INFGEN_SPLIT_OFFSET sublayers (two launches each; default 4, a
+ * quarter step of six layers; 0: no phase control) behind the first half's.  INFGEN_SPLIT_HALVES: 0 never; 1 (default) when each half keeps every
+ * by-size kernel choice of the whole batch (more than 10,240 rows per half, no k_layers_p), S is even and its middle no inside of a
+ * copy group (map_scene), without scenario insertion, a token-mask handle, tap_x or per-kernel profiling, and `stream` is not being
+ * captured into a graph; 2: the same without the size rule (tests).  The halves own their share of the three edge buffers and their own
+ * totals, summed into the context's after the last step (a half that overflows its share reports more than the whole capacity).
+ * infgen_set_overlap's side stream is not used by a split rollout.  infgen_split_stats: calls of infgen_rollout_run that took the
+ * split / the single-stream path since the library was loaded (either pointer may be NULL). */
+int infgen_split_stats(int* split_runs, int* single_runs);
 /* closed-loop sessions: the commands of decode step t for the rows flagged in r->replay_row, written into column 2 + t of the plan
  * the step's infgen_integrate forces on them (r->teacher_token / teacher_state; refused without them or without replay_row); call it
  * in front of infgen_decode_step(r, t).  kind 0: cmd_token [S][A_cap] ids (state valid; ids beyond the vocabulary are clamped).

@@ -154,6 +154,9 @@ const int lp_trace = env_int("INFGEN_LP_TRACE", 0);               // n: dump the
 const char* const lp_spin_str = getenv("INFGEN_LP_SPIN_LIMIT");
 const unsigned lp_spin_limit = lp_spin_str ? (unsigned)strtoul(lp_spin_str, nullptr, 0) : 0u;
 }  // namespace knob
+// the two knobs of infgen_rollout_run's split mode, read at every call (a process may run both paths: tests/test_split_halves_gpu.py)
+static int split_halves_knob() { return env_int("INFGEN_SPLIT_HALVES", 1); }      // 0 never, 1 by the rule of run_split_mode, 2 at every even S
+static int split_offset_knob() { return env_int("INFGEN_SPLIT_OFFSET", 4); }      // sublayers (two launches each) the second half's step starts behind the first half's; 0: no phase control
 
 // ---------------------------------------------------------------------------------- options
 // Every switch that changes what a launch does lives in an InfgenOptions.  g_def holds the process-wide defaults the
@@ -200,6 +203,15 @@ extern "C" int infgen_get_effective_options(InfgenOptions* out) {
   *out = O();
   return 0;
 }
+
+// A half of a split rollout (infgen_rollout_run) is a context of half the scenes inside the caller's arrays.
+// What a launch sizes by the WHOLE layout comes from here while a half is being enqueued (thread-local, zero outside):
+//   full_rows  the stride of the K / V ring's slots and of the step-major logs (logits, log-probabilities, uniforms)
+//   cap_scale  whole / half edge capacity: the by-capacity Fourier variant stays the whole batch's (launch_fourier)
+//   mark_ev    recorded on the half's stream behind sublayer mark_at of the step (layers_core): the other half's step waits for it
+struct SplitTl { int full_rows; int cap_scale; hipEvent_t mark_ev; int mark_at; };
+static thread_local SplitTl tl_split = {0, 1, nullptr, -1};
+static inline int stride_rows(const InfgenRollout* r) { return tl_split.full_rows ? tl_split.full_rows : r->S * r->A_cap; }
 
 // ---------------------------------------------------------------------------------- profiling
 // Optional, process-global, off by default: HIP events recorded on the launch stream around the
@@ -496,7 +508,7 @@ static int launch_fourier(const FourierArgs& a_in, void* stream) {
       hipLaunchKernelGGL(k_fourier, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);
     } else {
       // large sets: the three-wave-group variant (fourier_h12.hip)
-      const bool wide = knob::fh12_min > 0 && a.e_cap >= knob::fh12_min && three_terms() && FH_WAVES == 8;
+      const bool wide = knob::fh12_min > 0 && (long long)a.e_cap * tl_split.cap_scale >= knob::fh12_min && three_terms() && FH_WAVES == 8;
       const int grid = fourier_h_grid(a.e_cap, wide);
       if (wide) hipLaunchKernelGGL(k_fourier_h12<3>, dim3(grid), dim3(FH12_NT), 0, (hipStream_t)stream, a);
       else hipLaunchKernelGGL(by_terms(k_fourier_h<3>, k_fourier_h_b16<1>, k_fourier_h<1>), dim3(grid), dim3(FH_NT), 0, (hipStream_t)stream, a);
@@ -1792,7 +1804,7 @@ static int build_edges_impl(const InfgenRollout* r, int c, int edgeless, void* s
   }
   BuildEdgesArgs a;
   a.st = scene_of(r); a.c = c; a.edgeless = edgeless; a.r_map = r->r_map; a.r_agent = r->r_agent;
-  a.rows = r->S * r->A_cap; a.t = ebuf(r->et); a.m = ebuf(r->em); a.a = ebuf(r->ea);
+  a.rows = stride_rows(r); a.t = ebuf(r->et); a.m = ebuf(r->em); a.a = ebuf(r->ea);
   a.clear_keys = clear_keys;
   a.clear_sync = clear_sync ? reinterpret_cast<int*>(r->SIG) : nullptr;      // (k_layers_p's per-scene counters: layers_p_launch)
   a.prof = (g_prof.mask & ((1u << INFGEN_KID_EDGE_ATTN) | (1u << INFGEN_KID_BUILD_EDGES))) ? g_prof.rows_dev : nullptr;
@@ -2203,6 +2215,7 @@ static bool lp_packs_ok(const InfgenRollout* r, bool refresh = false, void* stre
     if (!ok(r->attn_t[i]) || !ok(r->attn_m[i]) || !ok(r->attn_a[i])) return false;
   return true;
 }
+static bool split_copy_boundary(const InfgenRollout* r, bool refresh);      // (the split mode of infgen_rollout_run, below)
 // A context's packs looked at afresh (a device address may have held another pack before): callers that build a context call
 // this once (infgen_amd/engine.py: _build_ctx); without it a pack is examined when its address is first seen.  Synchronous.
 extern "C" int infgen_rollout_validate(const InfgenRollout* r) {
@@ -2212,6 +2225,7 @@ extern "C" int infgen_rollout_validate(const InfgenRollout* r) {
   if ((r->teacher_pos != nullptr) != (r->teacher_head != nullptr))
     return fail("infgen_rollout_validate", "teacher_pos and teacher_head come together");
   (void)lp_packs_ok(r, true);
+  (void)split_copy_boundary(r, true);
   return 0;
 }
 static bool layers_p_shape(const InfgenRollout* r, int rows, int edgeless, void* stream) {
@@ -2310,7 +2324,7 @@ static int layers_p_launch(const InfgenRollout* r, int c, const StepMode& sm, vo
     a.attn_t[i] = r->attn_t[i]; a.attn_m[i] = r->attn_m[i]; a.attn_a[i] = r->attn_a[i];
     a.ringK[i] = r->ringK[i]; a.ringV[i] = r->ringV[i]; a.mapK[i] = r->mapK[i]; a.mapV[i] = r->mapV[i];
   }
-  a.slot_off = (size_t)(c % r->ring) * rows * D;
+  a.slot_off = (size_t)(c % r->ring) * stride_rows(r) * D;
   // the agent set's K / V rows double buffered by layer parity: the context's Ka / Va, and the first rows of its U array (4 KB per
   // row, unused while U stays on chip); the scenes' counters in its SIG array (unused for the same reason)
   a.Ka[0] = r->Ka; a.Va[0] = r->Va; a.Ka[1] = r->U; a.Va[1] = r->U + (size_t)rows * D;
@@ -2406,14 +2420,21 @@ static int layers_p_launch(const InfgenRollout* r, int c, const StepMode& sm, vo
 static int layers_core(const InfgenRollout* r, int c, int edgeless, void* stream, bool lp_sync_clear = true) {
   const int rows = r->S * r->A_cap;
   const StepMode sm = step_mode(r, rows, edgeless, stream);
+  // a split rollout's phase mark (tl_split): recorded once per step, behind sublayer mark_at or the step's last launch
+  bool marked = tl_split.mark_ev == nullptr;
+  auto mark = [&](int sublayer, bool last) {
+    if (marked || !(last || sublayer >= tl_split.mark_at)) return 0;
+    marked = true;
+    return hipEventRecord(tl_split.mark_ev, (hipStream_t)stream) == hipSuccess ? 0 : fail("infgen_rollout_run", "phase mark failed");
+  };
   if (sm.lp && sm.fuse) {
     const int rc = layers_p_launch(r, c, sm, stream, lp_sync_clear);
-    if (rc != LP_REFUSED) return rc;
+    if (rc != LP_REFUSED) { if (rc == 0) RET_IF(mark(0, true)); return rc; }
     // the runtime refused the cooperative launch: the per-sublayer launches below, with the fused edge kernel (the step's rhat
     // rows are already in its format); later calls do not try again (layers_p_shape)
   }
   const bool overlap = sm.overlap, fuse = sm.fuse; const int r24 = sm.r24;
-  const size_t slot = (size_t)(c % r->ring) * rows * D;
+  const size_t slot = (size_t)(c % r->ring) * stride_rows(r) * D;
   const int L = r->num_layers;
   // prologue of the first (temporal) layer; every later layer's prologue is fused into the previous
   // layer's k_attn_post
@@ -2444,6 +2465,7 @@ static int layers_core(const InfgenRollout* r, int c, int edgeless, void* stream
     warm_post(r->attn_m[i]);
     RET_IF(infgen_attn_post_pre(r->X, rows, r->attn_t[i], r->AGG, Z, SIG, has_pos, r->attn_m[i], r->Q, U,
                                 nullptr, nullptr, stream));
+    RET_IF(mark(3 * i, false));
     // map -> agent (bipartite: K/V of the map tokens are per-scene constants)
     if (overlap && i == 0 && hipStreamWaitEvent((hipStream_t)stream, g_ev_m, 0) != hipSuccess)
       return fail("infgen_decode_layers", "join failed");
@@ -2451,6 +2473,7 @@ static int layers_core(const InfgenRollout* r, int c, int edgeless, void* stream
     warm_post(r->attn_a[i]);
     RET_IF(infgen_attn_post_pre(r->X, rows, r->attn_m[i], r->AGG, Z, SIG, has_pos, r->attn_a[i], r->Q, U,
                                 r->Ka, r->Va, stream));
+    RET_IF(mark(3 * i + 1, false));
     // agent <-> agent
     if (overlap && i == 0 && hipStreamWaitEvent((hipStream_t)stream, g_ev_a, 0) != hipSuccess)
       return fail("infgen_decode_layers", "join failed");
@@ -2462,6 +2485,7 @@ static int layers_core(const InfgenRollout* r, int c, int edgeless, void* stream
     } else {
       RET_IF(infgen_attn_post(r->X, rows, r->attn_a[i], r->AGG, Z, SIG, has_pos, stream));
     }
+    RET_IF(mark(3 * i + 2, i + 1 == L));
     // test hook (InfgenRollout.tap_x): the residual stream after triple i
     if (r->tap_x && hipMemcpyAsync(r->tap_x + (size_t)i * rows * D, r->X, (size_t)rows * D * sizeof(float), hipMemcpyDeviceToDevice,
                                    (hipStream_t)stream) != hipSuccess)
@@ -2483,7 +2507,7 @@ extern "C" int infgen_decode_layers(const InfgenRollout* r, int c, int edgeless,
 // step t's emission over the context's rows, greedy and bare: logits is store_logits' slice of the step, or NULL
 static EmitReq step_emit_req(const InfgenRollout* r, int t) {
   const int rows = r->S * r->A_cap;
-  float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * rows * r->token_size : nullptr;
+  float* lg = (r->store_logits && r->logits) ? r->logits + (size_t)t * stride_rows(r) * r->token_size : nullptr;
   return EmitReq{r->X, rows, r->tok_head_pack, r->st_head_pack, r->token_size, lg, r->next_token, r->next_state};
 }
 
@@ -2510,13 +2534,13 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   EmitReq q = step_emit_req(r, t);
   q.ctl = ctl; q.mask = mask; q.mask_chain_heads = true;
   q.keys = reinterpret_cast<unsigned long long*>(r->tmp2);      // (scratch of the raw-feature stage, free here)
-  if (r->token_logprob) q.token_logprob = r->token_logprob + (size_t)t * rows;
+  if (r->token_logprob) q.token_logprob = r->token_logprob + (size_t)t * stride_rows(r);
   q.k = r->sample_u ? r->sample_k : 1;
   // a draw outside the split kernel with no logits to draw from: the arg-max, silently (sample_logprob unwritten, like a greedy context's)
   if (q.k > 1 && !q.logits && !r->logits_scratch && !emit_plan(q).sample_fused) q.k = 1;
   if (q.k > 1) {
-    q.uniform = r->sample_u + (size_t)t * rows;
-    if (r->sample_logprob) q.sample_logprob = r->sample_logprob + (size_t)t * rows;
+    q.uniform = r->sample_u + (size_t)t * stride_rows(r);
+    if (r->sample_logprob) q.sample_logprob = r->sample_logprob + (size_t)t * stride_rows(r);
   }
   const EmitPlan plan = emit_plan(q);
   if (plan.need_logits && !q.logits) q.logits = r->logits_scratch;      // (validate: token_logprob's chain has one)
@@ -2536,45 +2560,216 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
 // gathers the raw features - 8 dependent launches between the last sublayer of a step and the first of the next instead of 13
 // (memset, k_heads, k_heads_finish, k_integrate, k_rawfeat_prep, k_fourier_h, k_mlpemb_h, memset, k_build_edges,
 // k_fourier_h_multi, k_attn_hs ...).  Same arithmetic on the same data as infgen_decode_step (tests compare the two).
-extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream) {
+struct RunPlan { bool fold = false, lp_steps = false; unsigned long long* keys = nullptr; StepMode sm0{}; };
+// what comes in front of the first step: the fold decision and, folded, the cleared keys and the first column's edge sets
+static int run_begin(const InfgenRollout* r, int t0, int t1, void* stream, RunPlan* p) {
   StepRiders riders;
   RET_IF(validate(r, "infgen_rollout_run", nullptr, &riders));
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const bool sample = r->sample_k > 1 && r->sample_u;
-  const bool fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !riders.any() && !r->token_logprob && !r->first_new &&
-                    r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
-  if (!fold) {
-    for (int t = t0; t < t1; ++t) RET_IF(infgen_decode_step(r, t, stream));
-    return 0;
-  }
+  p->fold = !knob::no_tail_fold && t1 > t0 && fourier_multi_ok(rows, 0) && O().attn_mode != 0 && !sample && !riders.any() && !r->token_logprob && !r->first_new &&
+            r->et.total && r->em.total == r->et.total + 1 && r->ea.total == r->et.total + 2;
+  if (!p->fold) return 0;
   if (t0 < 0 || 1 + t1 > r->T - 1) return fail("infgen_rollout_run", "step beyond the column range");
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(r->tmp2);     // (free scratch under attn_mode != 0)
-  if (hipMemsetAsync(keys, 0, (size_t)rows * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
+  p->keys = reinterpret_cast<unsigned long long*>(r->tmp2);     // (free scratch under attn_mode != 0)
+  if (hipMemsetAsync(p->keys, 0, (size_t)rows * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess)
     return fail("infgen_rollout_run", "memset failed");
-  const StepMode sm0 = step_mode(r, rows, 0, stream);
-  const bool lp_steps = sm0.lp && sm0.fuse && r->SIG != nullptr;       // the steps' sublayers run as k_layers_p launches
+  p->sm0 = step_mode(r, rows, 0, stream);
+  p->lp_steps = p->sm0.lp && p->sm0.fuse && r->SIG != nullptr;       // the steps' sublayers run as k_layers_p launches
   // (their per-scene counters are zeroed by the kernel in front of every launch - k_build_edges before the first step, k_integrate
   // before the later ones - not by a fill: one launch less per step, and no memset node between the kernels of a captured graph)
-  RET_IF(prepare_edges(r, 1 + t0, 0, stream, true, false, nullptr, lp_steps));
-  for (int t = t0; t < t1; ++t) {
-    const int c = 1 + t;
-    RET_IF(layers_core(r, c, 0, stream, !lp_steps));
-    EmitReq q = step_emit_req(r, t);
-    q.keys = keys; q.keys_stay = true;
-    bool split = false;
-    RET_IF(emit_tokens("infgen_rollout_run", q, emit_plan(q), stream, &split));
-    // (the last step keeps its edge totals, like infgen_decode_step: RolloutEngine.edge_totals() / overflow checks read them)
-    RET_IF(integrate_impl(r, t, stream, split ? keys : nullptr, t + 1 < t1, true, t + 1 < t1 && lp_steps));
-    if (t + 1 < t1) {
-      RET_IF(prepare_edges(r, c + 1, 0, stream, false, true, split && integrate_groups(r) > 1 ? keys : nullptr));
-    } else {          // after the last step only the raw feature of the new column is left (kept: the context's X stays what
-                      // infgen_decode_step leaves)
-      RET_IF(launch_fourier(step_fourier_set(r, FS_XA, sm0), stream));
-    }
-    RET_IF(raw_feature_fusion(r, stream));
+  return prepare_edges(r, 1 + t0, 0, stream, true, false, nullptr, p->lp_steps);
+}
+static int run_step(const InfgenRollout* r, int t, int t1, void* stream, const RunPlan& p) {
+  if (!p.fold) return infgen_decode_step(r, t, stream);
+  OptScope _opts(r);
+  ProfPhase _pp(1);
+  const int c = 1 + t;
+  RET_IF(layers_core(r, c, 0, stream, !p.lp_steps));
+  EmitReq q = step_emit_req(r, t);
+  q.keys = p.keys; q.keys_stay = true;
+  bool split = false;
+  RET_IF(emit_tokens("infgen_rollout_run", q, emit_plan(q), stream, &split));
+  // (the last step keeps its edge totals, like infgen_decode_step: RolloutEngine.edge_totals() / overflow checks read them)
+  RET_IF(integrate_impl(r, t, stream, split ? p.keys : nullptr, t + 1 < t1, true, t + 1 < t1 && p.lp_steps));
+  if (t + 1 < t1) {
+    RET_IF(prepare_edges(r, c + 1, 0, stream, false, true, split && integrate_groups(r) > 1 ? p.keys : nullptr));
+  } else {          // after the last step only the raw feature of the new column is left (kept: the context's X stays what
+                    // infgen_decode_step leaves)
+    RET_IF(launch_fourier(step_fourier_set(r, FS_XA, p.sm0), stream));
   }
+  return raw_feature_fusion(r, stream);
+}
+
+// ---- the split mode: the batch as two halves of S / 2 scenes on two streams of the library's own, the second
+// half a set number of sublayers behind the first, so that one half's edge launches (memory requests in flight) share the CUs
+// with the other half's Fourier and node launches (matrix and vector pipes, LDS).  A half is a by-value copy of the context with
+// every per-scene and per-row pointer advanced to its first scene: the same kernels on the same rows as the whole batch runs.
+namespace {
+struct SplitRes {                        // what one caller stream's split rollouts run on (never freed: a handful per process)
+  hipStream_t st[2] = {nullptr, nullptr};
+  hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr}, mark = nullptr;
+  int* totals = nullptr;                 // device [6]: the halves' three edge totals each
+};
+std::mutex g_split_mu;                   // held while a split rollout is enqueued (the table below, and the halves' launch order)
+std::unordered_map<void*, SplitRes> g_split_res;      // by the caller's stream handle (a key only: the handle is never used)
+constexpr size_t SPLIT_MAX_STREAMS = 8;  // caller streams beyond these keep the single-stream path
+std::atomic<int> g_split_runs{0}, g_single_runs{0};
+std::mutex g_split_copy_mu;
+std::unordered_map<const int*, std::pair<int, bool>> g_split_copy_ok;      // map_scene -> (S, the middle is a copy-group boundary)
+}  // namespace
+extern "C" int infgen_split_stats(int* split_runs, int* single_runs) {
+  if (split_runs) *split_runs = g_split_runs.load();
+  if (single_runs) *single_runs = g_single_runs.load();
+  return 0;
+}
+static SplitRes* split_res(void* stream) {      // g_split_mu held
+  auto it = g_split_res.find(stream);
+  if (it != g_split_res.end()) return &it->second;
+  if (g_split_res.size() >= SPLIT_MAX_STREAMS) return nullptr;
+  SplitRes v;
+  bool ok = hipMalloc(&v.totals, 8 * sizeof(int)) == hipSuccess;
+  for (int h = 0; h < 2 && ok; ++h)
+    ok = hipStreamCreateWithFlags(&v.st[h], hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&v.join[h], hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreateWithFlags(&v.fork, hipEventDisableTiming) == hipSuccess &&
+       hipEventCreateWithFlags(&v.mark, hipEventDisableTiming) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); return nullptr; }      // (the caller keeps the single-stream path)
+  return &(g_split_res[stream] = v);
+}
+// copies of a scene (map_scene) stay in one half: the two entries around the middle, read once per array (8 bytes, synchronous -
+// like lp_packs_ok; infgen_rollout_validate looks again)
+static bool split_copy_boundary(const InfgenRollout* r, bool refresh) {
+  if (!r->map_scene || r->S < 2 || r->S % 2) return true;
+  std::lock_guard<std::mutex> lk(g_split_copy_mu);
+  auto it = g_split_copy_ok.find(r->map_scene);
+  if (!refresh && it != g_split_copy_ok.end() && it->second.first == r->S) return it->second.second;
+  int mid[2] = {0, 0};
+  const bool ok = hipMemcpy(mid, r->map_scene + r->S / 2 - 1, sizeof(mid), hipMemcpyDeviceToHost) == hipSuccess && mid[0] != mid[1];
+  (void)hipGetLastError();
+  g_split_copy_ok[r->map_scene] = {r->S, ok};
+  return ok;
+}
+// 0: the single-stream path.  Never: an odd S, a split inside a copy group, scenario insertion, a row-group list, a token-mask handle
+// (its riders address rows of the whole layout), the residual tap, per-kernel profiling, a stream under capture (no graph with
+// parallel branches comes from here).  INFGEN_SPLIT_HALVES=1 (default) additionally wants every by-size kernel choice of the whole
+// batch kept by the halves: the big-batch node / heads / embedding kernels and k_edge_fused3 (more than 10,240 rows per half), no
+// k_layers_p, k_build_edges and k_integrate on the same side of their scene thresholds (the Fourier variant is carried: tl_split)
+static bool run_split_mode(const InfgenRollout* r, int t0, int t1, void* stream) {
+  const int mode = split_halves_knob();
+  if (mode <= 0 || t1 <= t0 || r->S < 2 || r->S % 2) return false;
+  if (r->first_new || O().row_groups || r->token_mask || r->tap_x || g_prof.mask || tl_split.full_rows) return false;
+  if (r->et.cap < 2 || r->em.cap < 2 || r->ea.cap < 2 || !r->et.total || !r->em.total || !r->ea.total) return false;
+  if (is_capturing(stream)) return false;
+  if (mode == 1) {
+    const int rows = r->S * r->A_cap, half = r->S / 2;
+    if (rows / 2 <= 10240 || rows / 2 <= knob::edge_small || rows / 2 <= knob::attn_hs_max) return false;
+    if ((r->S > knob::be_wide_scenes) != (half > knob::be_wide_scenes) || (r->S > knob::int_group_scenes) != (half > knob::int_group_scenes)) return false;
+    if (step_mode(r, rows, 0, stream).lp) return false;
+  }
+  return split_copy_boundary(r, false);
+}
+static InfgenRollout split_half(const InfgenRollout* r, int h, int* totals) {
+  InfgenRollout q = *r;
+  q.S = r->S / 2;
+  const size_t s0 = h ? (size_t)q.S : 0, A = r->A_cap, row0 = s0 * A, col0 = s0 * r->T * A, m0 = s0 * r->M_cap;
+  auto adv = [](auto*& p, size_t n) { if (p) p += n; };
+  adv(q.n_agents, s0); adv(q.av_index, s0);
+  if (q.map_scene) adv(q.map_scene, s0);      // the map side is shared and only read; without the indirection it is per scene
+  else { adv(q.n_map, s0); adv(q.map_pos, 2 * m0); adv(q.map_orient, m0); }
+  adv(q.pos, 2 * col0); adv(q.head, col0); adv(q.state, col0); adv(q.token, col0); adv(q.grid, col0);
+  adv(q.tmask, col0); adv(q.imask, col0); adv(q.catflag, col0); adv(q.type, row0); adv(q.bos, row0);
+  adv(q.cat_agent, row0 * D);
+  for (int l = 0; l < INFGEN_MAX_LAYERS; ++l) {
+    adv(q.ringK[l], row0 * D); adv(q.ringV[l], row0 * D);      // (the slots keep the whole layout's stride: stride_rows)
+    if (!q.map_scene) { adv(q.mapK[l], m0 * D); adv(q.mapV[l], m0 * D); }
+  }
+  adv(q.X, row0 * D); adv(q.Q, row0 * D); adv(q.U, row0 * 8 * D); adv(q.Ka, row0 * D); adv(q.Va, row0 * D); adv(q.AGG, row0 * D);
+  adv(q.Z, row0 * 8 * D); adv(q.SIG, row0 * 8);
+  int k = 0;
+  for (InfgenEdgeBuf* e : {&q.et, &q.em, &q.ea}) {      // rows of off / cnt, its own half of the capacity, its own total
+    const int capA = e->cap / 2;
+    adv(e->off, row0); adv(e->cnt, row0);
+    if (h) { adv(e->src, (size_t)capA); adv(e->raw, (size_t)capA * 4); adv(e->rhat, (size_t)capA * D); }
+    e->cap = h ? e->cap - capA : capA;
+    e->total = totals + 3 * h + k++;
+  }
+  adv(q.raw2, row0 * 4); adv(q.cat, row0 * D); adv(q.fus_in, row0 * 512); adv(q.tmp1, row0 * D); adv(q.tmp2, row0 * D);
+  adv(q.next_token, row0); adv(q.next_state, row0); adv(q.logits, row0 * r->token_size);
+  adv(q.teacher_token, col0); adv(q.teacher_state, col0); adv(q.teacher_grid, col0); adv(q.teacher_pos, 2 * col0); adv(q.teacher_head, col0);
+  adv(q.replay_row, row0);
+  adv(q.pred_traj, row0 * r->R * 2); adv(q.pred_head, row0 * r->R); adv(q.pred_state, row0 * r->R);
+  adv(q.sample_u, row0); adv(q.logits_scratch, row0 * r->token_size); adv(q.sample_temp_row, row0);
+  adv(q.sample_logprob, row0); adv(q.token_logprob, row0);
+  q.opts = O(); q.opts.use = 1;
+  q.opts.overlap = 0;                      // (infgen_set_overlap's side stream and the split exclude each other: the split wins)
+  return q;
+}
+// the context's totals from the halves': the sums - or, where a half ran over its own share of the capacity, more than the whole
+// capacity, so that the callers' overflow checks answer as they would for the whole batch
+__global__ void k_split_totals(const int* half, int* t, int* m, int* a, int cap_t, int cap_m, int cap_a) {
+  if (threadIdx.x >= 3 || blockIdx.x) return;
+  const int k = threadIdx.x, cap = k == 0 ? cap_t : k == 1 ? cap_m : cap_a, capA = cap / 2;
+  const int na = half[k], nb = half[3 + k];
+  int n = na + nb;
+  if ((na > capA || nb > cap - capA) && n <= cap) n = cap + 1;
+  *(k == 0 ? t : k == 1 ? m : a) = n;
+}
+static int run_split(const InfgenRollout* r, int t0, int t1, void* stream, SplitRes& res) {
+  hipStream_t cs = (hipStream_t)stream;
+  const int full_rows = r->S * r->A_cap;
+  InfgenRollout half[2] = {split_half(r, 0, res.totals), split_half(r, 1, res.totals)};
+  const int L3 = 3 * r->num_layers;
+  const int off_knob = split_offset_knob(), off = off_knob < 0 ? 0 : off_knob > L3 ? L3 : off_knob;
+  if (hipEventRecord(res.fork, cs) != hipSuccess || hipStreamWaitEvent(res.st[0], res.fork, 0) != hipSuccess ||
+      hipStreamWaitEvent(res.st[1], res.fork, 0) != hipSuccess)
+    return fail("infgen_rollout_run", "fork failed");
+  struct TlScope { ~TlScope() { tl_split = SplitTl{0, 1, nullptr, -1}; } } _tl;
+  auto body = [&]() {
+    RunPlan plan[2];
+    for (int h = 0; h < 2; ++h) {
+      tl_split = SplitTl{full_rows, 2, nullptr, -1};
+      RET_IF(run_begin(&half[h], t0, t1, res.st[h], &plan[h]));
+    }
+    for (int t = t0; t < t1; ++t) {
+      // the first half marks its stream `off` sublayers into the step; the second half's step starts behind the mark
+      tl_split = SplitTl{full_rows, 2, off > 0 ? res.mark : nullptr, off - 1};
+      RET_IF(run_step(&half[0], t, t1, res.st[0], plan[0]));
+      tl_split = SplitTl{full_rows, 2, nullptr, -1};
+      if (off > 0 && hipStreamWaitEvent(res.st[1], res.mark, 0) != hipSuccess) return fail("infgen_rollout_run", "phase wait failed");
+      RET_IF(run_step(&half[1], t, t1, res.st[1], plan[1]));
+    }
+    return 0;
+  };
+  const int rc = body();
+  // the join comes whatever happened: the caller's stream stays ordered behind everything that was enqueued
+  bool joined = true;
+  for (int h = 0; h < 2; ++h)
+    joined = hipEventRecord(res.join[h], res.st[h]) == hipSuccess && hipStreamWaitEvent(cs, res.join[h], 0) == hipSuccess && joined;
+  if (rc) return rc;
+  if (!joined) return fail("infgen_rollout_run", "join failed");
+  hipLaunchKernelGGL(k_split_totals, dim3(1), dim3(64), 0, cs, res.totals, r->et.total, r->em.total, r->ea.total, r->et.cap, r->em.cap, r->ea.cap);
+  return check_launch("infgen_rollout_run(totals)");
+}
+
+extern "C" int infgen_rollout_run(const InfgenRollout* r, int t0, int t1, void* stream) {
+  RET_IF(validate(r, "infgen_rollout_run"));
+  {
+    OptScope _opts(r);
+    if (run_split_mode(r, t0, t1, stream)) {
+      std::lock_guard<std::mutex> lk(g_split_mu);
+      if (SplitRes* res = split_res(stream)) {
+        ++g_split_runs;
+        return run_split(r, t0, t1, stream, *res);
+      }
+    }
+  }
+  ++g_single_runs;
+  RunPlan plan;
+  RET_IF(run_begin(r, t0, t1, stream, &plan));
+  for (int t = t0; t < t1; ++t) RET_IF(run_step(r, t, t1, stream, plan));
   return 0;
 }
 
