@@ -351,7 +351,8 @@ def attn_mode(request, env):
                                         ('agent_encoder.t_attn_layers.0', False)])
 def test_attention_layer(env, prefix, bip, wide, attn_mode):
     """pre + edge attention + post == AttentionLayer.forward (layers.py:61-113), incl. rows without
-    incoming edges (exact-zero aggregate) and ragged degrees up to 70."""
+    incoming edges (exact-zero aggregate) and ragged degrees up to 70.  (The per-output checks of the node kernels - Q, U, K, V and x
+    each against float64, spread operand scales, separated LayerNorms, guard rows - are tests/test_node_attn_gpu.py's.)"""
     from oracle import rollout_oracle as ro
     rng = np.random.default_rng(11)
     n_dst, n_src = 45, (60 if bip else 45)
