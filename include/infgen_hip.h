@@ -495,7 +495,8 @@ int infgen_command_rows(const InfgenRollout* r, int t, int kind, const int* cmd_
  *            the slices [0, t) of token_logprob, sample_logprob and (store_logits) logits, where those pointers are given.
  *   kept     what configures a slot and is not history: sample_u, sample_temp_row, the token mask's selectors and tables, replay_row,
  *            the plan arrays teacher_* (past plan columns are not read again, future ones are the slot's own commands), the collision
- *            and road buffers (rebuilt every step from the copied poses), type / n_agents and the map side (equal inside a copy
+ *            and road buffers (rebuilt every step from the copied poses), the routes, their records and the route buffers (route_bits,
+ *            count and progress are rebuilt every step too), type / n_agents and the map side (equal inside a copy
  *            group).  A clone therefore diverges from its parent at the next draw or command.  Scratch is not touched.
  *   parent   source and destination belong to one COPY GROUP, the same map-side scene: map_scene[s] == map_scene[p] (map_scene NULL:
  *            every scene is its own group, only the identity is valid); sources are fixed points, parent[parent[s]] == parent[s] - no
@@ -522,7 +523,7 @@ int infgen_resample_parents(const int* ancestor, int S0, int copies, int* parent
  *   the slices [0, t) of token_logprob, sample_logprob and (store_logits) logits, where those pointers are given;
  *   the scene's [steps][8] step-score block, where the context scores ("step scores").
  * and nothing of its "kept" list (uniforms, temperatures, mask selectors and tables, replay flags, plans, collision and road buffers,
- * scratch): a restored slot runs under the configuration the context has THEN, which is what a planner varies between two tries.
+ * routes, route records and route buffers, scratch): a restored slot runs under the configuration the context has THEN, which is what a planner varies between two tries.
  * Layout: the segments in table order (the order above; absent buffers take no room), each segment as its blocks per scene - one for
  * the scene arrays, X and pred_*, `ring` for a ring, t for a log - every block starting on a 16-byte boundary (a block of b bytes takes
  * (b + 15) & ~15; the library's own layouts have b % 16 == 0).  The bytes between a block's end and the boundary are written as 0.
@@ -569,6 +570,11 @@ int infgen_sample_topk_mask(const float* logits, int rows, int n, int k, const f
  * infgen_token_mask_destroy frees the slot (0 on success); a context must not name a destroyed handle. */
 int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, const int* type);
 int infgen_token_mask_destroy(int handle);
+/* test and diagnostic entry, host only, launches nothing: copies out the library's step-rider block - the static mask as the kernels
+ * take it, then the collision, road, score and route configurations, in that order - that a context with row types `type` and this
+ * token_size would run under `handle` (0: no handle, the block of a context without token_mask).  -> the block's size in bytes, or a
+ * negative code; capacity below that size is refused.  The layout is the library's own and may grow at its end. */
+int infgen_token_mask_riders(int handle, const int* type, int token_size, void* out, int capacity);
 
 /* collision-aware decoding: COLLISION MASKS, the allowed-token sets of one decode step computed from the agents' boxes (k_collision_mask).
  * At decode step t the current column is c = hist_columns - 1 + t (= 1 + t).  A row i of scene s is IN THE SCENE at column c when
@@ -669,6 +675,58 @@ int infgen_road_mask(const float* pos, const float* head, const int* state, cons
 int infgen_token_mask_road(int handle, uint32_t* road_bits, const int* identity_row, const float* shape, const float* end_pose,
                            const float* paths, const float* records, const int* n_records, int rec_cap, int copies, int sweep,
                            float margin, const int* types, int* count);
+
+/* route-following decoding: ROUTE MASKS, the allowed-token sets of one decode step computed from the rows' own routes (k_route_mask):
+ * where the collision and road masks say where a row may not go, this one says where it should - the model still decides speed, gaps
+ * and lateral detail inside the corridor.  Step column c = 1 + t, IN THE SCENE, first_new, base(i) and the fallback mean what they
+ * mean for the collision masks above; fp32 throughout, no fused multiply-add; world coordinates enter only through the exact
+ * difference (p0 - pos[c][i]).
+ *   route   row (s, i) of `copies` copies per scene reads the route of row (s / copies, i): n_points waypoints in world coordinates,
+ *       routes [S0][A_cap][P][2], n_points [S0][A_cap], 0 <= n_points <= P (values outside are clamped), 2 <= P <= 32.  Longer paths
+ *       are the caller's to window between steps.
+ *   record   built once per (re)load by k_route_records, one per segment j (the points j, j + 1), records [S0][A_cap][P - 1][8],
+ *       16-byte aligned: p0.x, p0.y (exact copies of the input), ux, uy = (p1 - p0) / L, L = sqrt(dx * dx + dy * dy), cum = the arc
+ *       length in front of the segment - the live L before it, summed in segment order -, 0, 0.  A segment with L == 0, a non-finite
+ *       L or p0, or an end beyond n_points is the DEAD record (0, 0, 1, 0, -1, 0, 0, 0): it is skipped and cum does not advance.
+ *       total [S0][A_cap] = the sum over all live segments.  A row HAS A ROUTE iff total > 0 (fewer than two points: none).
+ *   projection   a point e of the row's frame - translate by pos[c][i] first, then rotate by -head[c][i]: q0 = R(p0 - pos), u = R(ux, uy)
+ *       with R(x, y) = (x ci + y si, y ci - x si) - over the live segments in order: a = min(max((e - q0) . u, 0), L),
+ *       d2 = |e - q0 - a u|^2; the FIRST segment of least d2 gives s(e) = cum + a and d(e) = sqrt(d2).  s0, d0: the values of the
+ *       row's current centre, e = (0, 0); s_k, d_k: those of the centre (dx, dy) of token k's END BOX (the end-pose table, the row's type).
+ *   on-route   token k is ON-ROUTE iff (d_k <= corridor or d_k < d0) - the second clause lets a row that starts outside the corridor
+ *       come back - and s_k >= s0 - back (the difference formed once per row).
+ *   pace   0 <= pace <= 1, 0: off.  gmax = the maximum of s_k - s0 over the tokens in base(i) that are on-route.  With pace > 0 and
+ *       gmax > 0 the tokens with s_k - s0 < pace * gmax (the product formed once per row) are banned too.
+ *   rows   the rule applies to the rows in the scene at column c that have a route, whose agent type ty (0 vehicle, 1 pedestrian,
+ *       2 cyclist; others count as 0) has types[ty] != 0 and that are not FINISHED: s0 < total - finish (the difference in fp32).  Every
+ *       other row - no route, finished, not in the scene, padding, >= first_new[s], a type switched off - keeps base(i).  Replayed,
+ *       commanded and teacher-forced rows keep their plan's tokens, as under any mask.
+ *   result   set(i) = base(i) AND onroute(i) (AND the pace bar); an empty result is replaced by base(i); out_count[i] (optional) is
+ *       the size before that fallback.  out_progress [S * A_cap][4] (optional, 16-byte aligned) = (s0, d0, total, flag): flag 1 =
+ *       ruled, 2 = finished; a row in the scene with a route and its type on has s0 and d0, every other row (0, 0, total, 0).
+ *       A d or s within ~1e-4 m of one of its thresholds, or two segments whose d2 tie that closely, may fall either way.
+ * infgen_route_records: records and total of S0 * A_cap rows from routes and n_points.
+ * infgen_route_mask: one launch writes out_bits [S * A_cap][token_size / 32], out_count and out_progress; the scene arrays as for
+ * infgen_collision_mask, S a multiple of copies; the base is a token mask's first four values with the rows' own `type`.  shape is
+ * the rows' [S][A_cap][3] array of the collision masks (the row skeleton reads it; the rule itself tests centres, not boxes).
+ * infgen_token_mask_route: attaches a route configuration to a registered token mask, as infgen_token_mask_road does:
+ * infgen_decode_step then launches k_route_mask in front of the heads launch, after k_collision_mask and k_road_mask where the
+ * handle carries those: collision, then road, then route - each stage's base is the previous stage's bits read through the identity
+ * selector, each stage's fallback returns the previous stage's set, and the heads read route_bits.  With no route configuration
+ * attached the launches and their arguments are exactly those without this entry.  progress is rebuilt every step, like count.  The
+ * pointers are kept, not the contents: records and total may be rebuilt between two steps.  route_bits NULL detaches.  Rows scenario
+ * insertion appends have no route (their n_points is 0) and keep their base.
+ * Refused: corridor, back or finish negative or not finite, pace outside [0, 1], P outside 2..32, copies < 1 or not dividing S, a
+ * token_size that is no multiple of 32 or exceeds 4096, A_cap beyond INFGEN_Q_MAX_AGENTS, a missing or misaligned table. */
+int infgen_route_records(const float* routes, const int* n_points, int S, int A_cap, int P, float* records, float* total, void* stream);
+int infgen_route_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new, const int* type,
+                      const float* shape, int S, int A_cap, int T, int c, const float* end_pose, int token_size, const float* records,
+                      const float* total, int P, int copies, float corridor, float back, float pace, float finish, const int* types,
+                      const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, uint32_t* out_bits,
+                      int* out_count, float* out_progress, void* stream);
+int infgen_token_mask_route(int handle, uint32_t* route_bits, const int* identity_row, const float* shape, const float* end_pose,
+                            const float* records, const float* total, int P, int copies, float corridor, float back, float pace,
+                            float finish, const int* types, int* count, float* progress);
 
 /* step scores: STEP SCORES, what a branching loop branches on - per scene slot and decode step the overlap, off-road and comfort terms
  * of the column the step just produced (k_step_score: one launch, no host read, no atomics).

@@ -145,8 +145,11 @@ class ClosedLoopSession:
                    shape=eng._shape10, n_agents=eng.n_agents, ego_index=eng.av, controlled=eng.replay_row.bool(), column=c)
         if eng.avoid_collisions is not None:      # collision-aware decoding: the sizes of the sets the last step decoded under
             obs['allowed_tokens'] = eng.collision_allowed.view(eng.S, eng.A_cap)
-        if eng.stay_on_road is not None:          # road-aware decoding runs last: its sets are the ones the heads read
+        if eng.stay_on_road is not None:          # road-aware decoding runs behind the collision masks
             obs['allowed_tokens'] = eng.road_allowed.view(eng.S, eng.A_cap)
+        if eng.follow_routes is not None:         # route-following decoding runs last: its sets are the ones the heads read
+            obs['allowed_tokens'] = eng.route_allowed.view(eng.S, eng.A_cap)
+            obs['route_progress'] = eng.route_progress.view(eng.S, eng.A_cap, 4)
         if eng.step_scores is not None:           # step scores: the step that just ran (absent before the first) and its rows' flags
             if self.t > 0:
                 obs['step_score'] = eng.step_score[:, self.t - 1]
@@ -218,6 +221,12 @@ class ClosedLoopSession:
             full[:, :x.shape[1]] = x
             x = full
         eng.mask_row.copy_(x.reshape(-1))
+
+    def set_routes(self, routes, n_points):
+        """new routes for the rows of an engine with ``follow_routes`` (``RolloutEngine.set_routes``): they rule from the next
+        ``advance()`` on; ``observe()['route_progress']`` [S, A_cap, 4] = s0, d0, total, flag stays that of the step that just ran"""
+        self._check_open()
+        self.eng.set_routes(routes, n_points)
 
     def branch(self, parent):
         """``RolloutEngine.branch(parent, t)`` at this session's step: slot s continues as a clone of slot ``parent[s]`` from the

@@ -326,3 +326,105 @@ def score_key(conf):
     """the hashable part of a checked step_scores configuration that decides the launches' arguments"""
     return None if conf is None else (conf['road_margin'], conf['sweep'], conf['types'], conf['detail'], conf['segments'] is not None,
                                       conf['dt'])
+
+
+# ---------------------------------------------------------------------------------------- route-following decoding (DESIGN 5.17)
+ROUTE_MAX_POINTS = 32                     # RT_MAX_POINTS of csrc/kernels.h
+
+
+def route_arrays(routes, n_points, n_scenes: Optional[int] = None, a_cap: Optional[int] = None, what: str = 'follow_routes'):
+    """``routes`` [S0][A][P][2] world-coordinate waypoints and ``n_points`` [S0][A] as the engine takes them -> (float32, int32)
+    arrays, checked: 2 <= P <= 32, 0 <= n_points <= P, one entry per distinct scene, A within the engine's rows.  Non-finite and
+    repeated waypoints are allowed: the definition makes their segments dead"""
+    r, n = np.asarray(routes), np.asarray(n_points)
+    if r.ndim != 4 or r.shape[3] != 2 or r.dtype.kind not in 'fiu':
+        raise ValueError(f'{what}: routes are numbers [S0][A][P][2], got shape {r.shape}')
+    if not 2 <= r.shape[2] <= ROUTE_MAX_POINTS:
+        raise ValueError(f'{what}: P = {r.shape[2]} waypoints per route, must be 2 .. {ROUTE_MAX_POINTS} (window longer paths)')
+    if n.shape != r.shape[:2] or n.dtype.kind not in 'iu':
+        raise ValueError(f'{what}: n_points holds integers [S0][A] = {r.shape[:2]}, got shape {n.shape}')
+    if n.size and (int(n.min()) < 0 or int(n.max()) > r.shape[2]):
+        raise ValueError(f'{what}: n_points has entries outside 0 .. P = {r.shape[2]}')
+    if n_scenes is not None and r.shape[0] != n_scenes:
+        raise ValueError(f'{what}: routes cover {r.shape[0]} scenes, the batch has {n_scenes} distinct scenes')
+    if a_cap is not None and r.shape[1] > a_cap:
+        raise ValueError(f'{what}: routes for {r.shape[1]} rows, the engine has {a_cap} per scene')
+    return np.ascontiguousarray(r, np.float32), np.ascontiguousarray(n, np.int32)
+
+
+def check_follow_routes(follow, n_scenes: Optional[int] = None, a_cap: Optional[int] = None):
+    """``follow_routes`` as the engine takes it -> None (off) or dict(routes=float32 [S0][A][P][2], n_points=int32 [S0][A],
+    corridor=, back=, pace=, finish= floats, types=(veh, ped, cyc) switches).  False / None: off; a mapping with ``routes`` and
+    ``n_points`` and any of ``corridor`` (2 m), ``back`` (0.5 m), ``pace`` (0: off), ``finish`` (1 m), ``types`` (vehicles and
+    cyclists).  Everything is checked here, on the host, before any launch."""
+    if follow is None or follow is False:
+        return None
+    what = 'follow_routes'
+    if not isinstance(follow, Mapping):
+        raise ValueError(f'{what} takes False or dict(routes=, n_points=, corridor=, back=, pace=, finish=, types=)')
+    unknown = set(follow) - {'routes', 'n_points', 'corridor', 'back', 'pace', 'finish', 'types'}
+    if unknown:
+        raise ValueError(f'{what}: unknown keys {sorted(unknown)} (routes, n_points, corridor, back, pace, finish, types)')
+    if follow.get('routes') is None or follow.get('n_points') is None:
+        raise ValueError(f'{what} needs routes [S0][A][P][2] and n_points [S0][A]')
+    out = {}
+    for key, dflt in (('corridor', 2.0), ('back', 0.5), ('finish', 1.0)):
+        v = follow.get(key, dflt)
+        if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isfinite(v) or v < 0:
+            raise ValueError(f'{what}: {key} must be a finite number of metres >= 0 (got {v!r})')
+        out[key] = float(v)
+    pace = follow.get('pace', 0.0)
+    if isinstance(pace, (bool, str)) or not np.isscalar(pace) or not 0 <= pace <= 1:
+        raise ValueError(f'{what}: pace must be a number in [0, 1] (got {pace!r})')
+    out['pace'] = float(pace)
+    out['types'] = _road_types(follow.get('types', ('veh', 'cyc')), what)
+    out['routes'], out['n_points'] = route_arrays(follow['routes'], follow['n_points'], n_scenes, a_cap, what)
+    return out
+
+
+def route_key(conf):
+    """the hashable part of a checked follow_routes configuration that decides the launches' arguments (the routes are contents)"""
+    return None if conf is None else (conf['corridor'], conf['back'], conf['pace'], conf['finish'], conf['types'])
+
+
+def route_buffers(n_scenes: int, rows: int, a_cap: int, P: int, token_size: int, device='cpu'):
+    """the static buffers of route-following decoding: the four of ``collision_buffers`` - ``bits``, ``allowed``, ``ident``,
+    ``shape`` (the row skeleton reads it, the rule does not: it stays zero) -, ``progress`` [rows][4], and per distinct scene
+    ``routes`` [S0][A_cap][P][2], ``n_points`` [S0][A_cap], ``records`` [S0][A_cap][P - 1][8], ``total`` [S0][A_cap]"""
+    import torch
+    if token_size % 32 or token_size > 4096:
+        raise ValueError(f'follow_routes: token_size {token_size} must be a multiple of 32, at most 4096')
+    k = collision_buffers({}, rows, token_size, device)
+    k.update(P=P, progress=torch.zeros(rows, 4, device=device), routes=torch.zeros(n_scenes, a_cap, P, 2, device=device),
+             n_points=torch.zeros(n_scenes, a_cap, dtype=torch.int32, device=device),
+             records=torch.zeros(n_scenes, a_cap, P - 1, 8, device=device), total=torch.zeros(n_scenes, a_cap, device=device))
+    return k
+
+
+def routes_from_logged(data_or_staged, stride: int = 1, start: int = 0, points: int = ROUTE_MAX_POINTS):
+    """every agent's logged positions as its route: "follow your own log".  ``data_or_staged``: a scene (its ``agent`` holds
+    ``token_pos`` [A][T0][2] and ``state_idx`` [A][T0]), a sequence of scenes, or a mapping of stacked ``token_pos`` [S][A][T0][2] /
+    ``state_idx`` [S][A][T0].  From column ``start`` on every ``stride``-th column where the agent is valid (state != 0) is a
+    waypoint; a point equal to the one before it is dropped, and the route is cut after ``points`` waypoints.
+    -> routes float32 [S][A][points][2], n_points int32 [S][A] (A: the largest scene's rows).  Pure host code."""
+    if stride < 1 or start < 0 or not 2 <= points <= ROUTE_MAX_POINTS:
+        raise ValueError(f'routes_from_logged: stride >= 1, start >= 0 and 2 <= points <= {ROUTE_MAX_POINTS}')
+    if isinstance(data_or_staged, Mapping) and 'token_pos' in data_or_staged:
+        pos, st = np.asarray(data_or_staged['token_pos']), np.asarray(data_or_staged['state_idx'])
+        scenes = [(pos[s], st[s]) for s in range(pos.shape[0])]
+    else:
+        datas = [data_or_staged] if isinstance(data_or_staged, Mapping) else list(data_or_staged)
+        scenes = [(np.asarray(d['agent']['token_pos']), np.asarray(d['agent']['state_idx'])) for d in datas]
+    A = max(p.shape[0] for p, _ in scenes)
+    routes, n_points = np.zeros((len(scenes), A, points, 2), np.float32), np.zeros((len(scenes), A), np.int32)
+    for s, (pos, st) in enumerate(scenes):
+        for i in range(pos.shape[0]):
+            n = 0
+            for col in range(start, pos.shape[1], stride):
+                p = pos[i, col, :2].astype(np.float32)
+                if st[i, col] == 0 or n == points or (n and np.array_equal(p, routes[s, i, n - 1])):
+                    continue
+                routes[s, i, n] = p
+                n += 1
+            n_points[s, i] = n
+    return routes, n_points

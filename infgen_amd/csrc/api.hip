@@ -64,16 +64,22 @@ struct ScoreCfg {
   int rec_cap, copies, sweep; float margin; int types[3]; float dt;
 };
 constexpr ScoreCfg SCORE_NONE{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, 0.5f};
-struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; };
+// the route configuration a registered mask may carry (infgen_token_mask_route; bits == NULL: none)
+struct RouteCfg {
+  uint32_t* bits; const int* ident; const float* shape; const float* end_pose; const float* records; const float* total;
+  int P, copies; float corridor, back, pace, finish; int types[3]; int* count; float* progress;
+};
+constexpr RouteCfg ROUTE_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, 1, 0.f, 0.f, 0.f, 0.f, {0, 0, 0}, nullptr, nullptr};
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
-// what rides on a context's decode step: the static mask as the kernels take it and the three configurations of its handle
+// what rides on a context's decode step: the static mask as the kernels take it and the four configurations of its handle
 // (validate fills it).  A new rider adds a Cfg, an args builder and one line in any()
 struct StepRiders {
-  TokenMaskCtl mask; CollisionCfg coll; RoadCfg road; ScoreCfg score;
-  bool any() const { return mask.bits || coll.bits || road.bits || score.out; }
+  TokenMaskCtl mask; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route;
+  bool any() const { return mask.bits || coll.bits || road.bits || score.out || route.bits; }
 };
-constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, COLLISION_NONE, ROAD_NONE, SCORE_NONE};
+constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE};
 // the one handle lookup: f(slot) under g_mask_mu, or the error `what` where the handle names no registered mask
 constexpr const char* NO_TOKEN_MASK = "no such token mask";
 template <class F> static int with_mask_slot(const char* where, int handle, const char* what, F f) {
@@ -106,7 +112,7 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   size_t h = 0;
   while (h < g_masks.size() && g_masks[h].in_use) ++h;
   if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
-  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE, SCORE_NONE};
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE};
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
@@ -1622,6 +1628,97 @@ extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int
   return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.road = cfg; });
 }
 
+// ---------------------------------------------------------------------------------- route masks
+// the argument checks of include/infgen_hip.h ("route masks") - route_check: what a configuration is checked for once, by the
+// stand-alone entry and when it is attached to a handle; launch_route: the geometry - and the one launch of k_route_mask
+static int route_check(const char* where, int P, int copies, float corridor, float back, float pace, float finish, const float* shape,
+                       const float* end_pose, const float* records, const float* total, const int* types, const uint32_t* bits,
+                       const float* progress) {
+  if (!std::isfinite(corridor) || corridor < 0.f) return fail(where, "route mask: corridor must be finite and >= 0");
+  if (!std::isfinite(back) || back < 0.f) return fail(where, "route mask: back must be finite and >= 0");
+  if (!std::isfinite(finish) || finish < 0.f) return fail(where, "route mask: finish must be finite and >= 0");
+  if (!(pace >= 0.f && pace <= 1.f)) return fail(where, "route mask: pace must be in [0, 1]");
+  if (P < 2 || P > RT_MAX_POINTS) return fail(where, "route mask: P must be in 2..32");
+  if (copies < 1) return fail(where, "route mask: copies must be at least 1");
+  if (!shape) return fail(where, "route mask: needs the rows' shape array [S][A_cap][3]");
+  if (!end_pose) return fail(where, "route mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!records || !total) return fail(where, "route mask: needs the record table and the routes' lengths");
+  if (!types) return fail(where, "route mask: needs the three-entry type switch");
+  if (!bits) return fail(where, "route mask: needs the output table");
+  if (misaligned16(bits, end_pose, records, progress)) return fail(where, "route mask: the tables must be 16-byte aligned");
+  return 0;
+}
+static RouteArgs route_args(const RiderScene& sc, int c, const RouteCfg& k, const TokenMaskCtl& base) {
+  RouteArgs a = rider_args<RouteArgs>(sc, k);
+  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
+  a.end_pose = k.end_pose; a.records = k.records; a.total = k.total; a.P = k.P; a.copies = k.copies;
+  a.corridor = k.corridor; a.back = k.back; a.pace = k.pace; a.finish = k.finish;
+  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
+  a.base = base; a.out_bits = k.bits; a.out_count = k.count; a.out_progress = k.progress;
+  return a;
+}
+static int launch_route(const char* where, const RouteArgs& a, void* stream) {
+  RET_IF(route_check(where, a.P, a.copies, a.corridor, a.back, a.pace, a.finish, a.shape, a.end_pose, a.records, a.total, a.types,
+                     a.out_bits, a.out_progress));
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "route mask: S, A_cap and T must be positive");
+  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "route mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.S % a.copies) return fail(where, "route mask: S must be a multiple of copies");
+  if (a.c < 0 || a.c >= a.T) return fail(where, "route mask: column outside [0, T)");
+  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
+    return fail(where, "route mask: token_size must be a multiple of 32, at most 4096");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "route mask: null scene array");
+  const long long rows = (long long)a.S * a.A_cap;
+  if (rows > 0x7fffffffLL) return fail(where, "route mask: too many rows");
+  hipLaunchKernelGGL(k_route_mask, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+
+extern "C" int infgen_route_records(const float* routes, const int* n_points, int S, int A_cap, int P, float* records, float* total,
+                                    void* stream) {
+  const char* me = "infgen_route_records";
+  if (!routes || !n_points || !records || !total) return fail(me, "null pointer");
+  if (P < 2 || P > RT_MAX_POINTS) return fail(me, "route mask: P must be in 2..32");
+  if (S <= 0 || A_cap <= 0) return fail(me, "S and A_cap must be positive");
+  if (A_cap > MAX_SCENE_AGENTS) return fail(me, "route mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (misaligned16(records)) return fail(me, "route mask: the tables must be 16-byte aligned");
+  const long long rows = (long long)S * A_cap;
+  if (rows > 0x7fffffffLL) return fail(me, "route mask: too many rows");
+  hipLaunchKernelGGL(k_route_records, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream,
+                     RouteRecArgs{routes, n_points, (int)rows, P, records, total});
+  return check_launch(me);
+}
+
+extern "C" int infgen_route_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new,
+                                 const int* type, const float* shape, int S, int A_cap, int T, int c, const float* end_pose,
+                                 int token_size, const float* records, const float* total, int P, int copies, float corridor, float back,
+                                 float pace, float finish, const int* types, const uint32_t* mask_bits, int mask_n_sets,
+                                 const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, float* out_progress,
+                                 void* stream) {
+  const char* me = "infgen_route_mask";
+  RET_IF(route_check(me, P, copies, corridor, back, pace, finish, shape, end_pose, records, total, types, out_bits, out_progress));
+  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
+  const RouteCfg cfg{out_bits, nullptr, shape, end_pose, records, total, P, copies, corridor, back, pace, finish,
+                     {types[0], types[1], types[2]}, out_count, out_progress};
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
+  TokenMaskCtl base;
+  RET_IF(token_mask_ctl(me, &md, token_size, &base));
+  return launch_route(me, route_args(sc, c, cfg, base), stream);
+}
+
+extern "C" int infgen_token_mask_route(int handle, uint32_t* route_bits, const int* identity_row, const float* shape, const float* end_pose,
+                                       const float* records, const float* total, int P, int copies, float corridor, float back, float pace,
+                                       float finish, const int* types, int* count, float* progress) {
+  const char* me = "infgen_token_mask_route";
+  RouteCfg cfg = ROUTE_NONE;
+  if (route_bits) {
+    RET_IF(route_check(me, P, copies, corridor, back, pace, finish, shape, end_pose, records, total, types, route_bits, progress));
+    if (!identity_row) return fail(me, "route mask: needs the identity selectors [S * A_cap]");
+    cfg = RouteCfg{route_bits, identity_row, shape, end_pose, records, total, P, copies, corridor, back, pace, finish,
+                   {types[0], types[1], types[2]}, count, progress};
+  }
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.route = cfg; });
+}
+
 // ---------------------------------------------------------------------------------- step scores
 // the argument checks of include/infgen_hip.h ("step scores") - score_check: what a configuration is checked for once, by the
 // stand-alone entry and when it is attached to a handle; launch_score: the geometry - and the one launch of k_step_score
@@ -1742,6 +1839,20 @@ static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src
 static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
+// the riders of a registered handle as a context with these row types and token_size sees them (memberwise: a riders block that
+// was zeroed keeps its padding)
+static int handle_riders(const char* where, int handle, const int* type, int token_size, StepRiders* riders, bool memberwise = false) {
+  TokenMaskDesc tm;
+  RET_IF(with_mask_slot(where, handle, "token_mask is no handle of infgen_token_mask_create", [&](const TokenMaskSlot& s) {
+    tm = s.d; riders->coll = s.coll; riders->road = s.road; riders->score = s.score; riders->route = s.route;
+  }));
+  if (!tm.type) tm.type = type;
+  TokenMaskCtl ctl;
+  RET_IF(token_mask_ctl(where, &tm, token_size, &ctl));
+  riders->mask = ctl;
+  return 0;
+}
+
 // riders (optional): what rides on the context's decode step, from its token-mask handle (RIDERS_NONE without one)
 static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl = nullptr, StepRiders* riders = nullptr) {
   if (!r) return fail(where, "null context");
@@ -1762,13 +1873,8 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   if (!riders) riders = &own_riders;
   *riders = RIDERS_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
-    TokenMaskDesc tm;
-    RET_IF(with_mask_slot(where, r->token_mask, "token_mask is no handle of infgen_token_mask_create", [&](const TokenMaskSlot& s) {
-      tm = s.d; riders->coll = s.coll; riders->road = s.road; riders->score = s.score;
-    }));
-    if (!tm.type) tm.type = r->type;
-    RET_IF(token_mask_ctl(where, &tm, r->token_size, &riders->mask));
-    const auto& [mask, coll, road, score] = *riders;
+    RET_IF(handle_riders(where, r->token_mask, r->type, r->token_size, riders));
+    const auto& [mask, coll, road, score, route] = *riders;
     if (coll.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
       return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
     if (road.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
@@ -1777,6 +1883,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
     if (score.out && r->first_new)
       return fail(where, "step score: contexts with scenario insertion cannot be scored: rows appended inside a step are left out");
     if (score.out && r->S % score.copies) return fail(where, "step score: S must be a multiple of copies");
+    if (route.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
+      return fail(where, "route mask: token_size must be a multiple of 32, at most 4096");
+    if (route.bits && r->S % route.copies) return fail(where, "route mask: S must be a multiple of copies");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: the plan under the context's own switches
@@ -1786,6 +1895,19 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
       return fail(where, "token_logprob needs store_logits or logits_scratch [rows][token_size] (few rows, or sampling)");
   }
   return 0;
+}
+
+// test and diagnostic entry: the step riders a context of this token_size (row types `type`) would run under the handle
+extern "C" int infgen_token_mask_riders(int handle, const int* type, int token_size, void* out, int capacity) {
+  const char* me = "infgen_token_mask_riders";
+  if (!out || capacity < (int)sizeof(StepRiders)) return fail(me, "needs a buffer of at least sizeof(StepRiders) bytes");
+  StepRiders riders;
+  std::memset(&riders, 0, sizeof riders);               // (padding bytes too: the caller compares bytes)
+  const StepRiders none = RIDERS_NONE;
+  riders.mask = none.mask; riders.coll = none.coll; riders.road = none.road; riders.score = none.score; riders.route = none.route;
+  if (handle != 0) RET_IF(handle_riders(me, handle, type, token_size, &riders, true));
+  std::memcpy(out, &riders, sizeof riders);
+  return (int)sizeof riders;
 }
 
 // zero_totals = false: the three totals were cleared by the previous step's k_integrate (IntegrateArgs.edge_totals)
@@ -2515,7 +2637,7 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
   StepRiders riders;
   RET_IF(validate(r, "infgen_decode_step", &ctl, &riders));
-  auto& [mask, coll, road, score] = riders;
+  auto& [mask, coll, road, score, route] = riders;
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
@@ -2530,6 +2652,10 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   if (road.bits) {      // road-aware decoding: the sets so far (static, or this column's collision sets) without the off-road tokens
     RET_IF(launch_road("infgen_decode_step", road_args(sc, c, road, mask), stream));
     mask = TokenMaskCtl{road.bits, rows, road.ident, {-1, -1, -1}, nullptr};
+  }
+  if (route.bits) {     // route-following decoding: the sets so far without the tokens that leave the row's route or fall behind on it
+    RET_IF(launch_route("infgen_decode_step", route_args(sc, c, route, mask), stream));
+    mask = TokenMaskCtl{route.bits, rows, route.ident, {-1, -1, -1}, nullptr};
   }
   EmitReq q = step_emit_req(r, t);
   q.ctl = ctl; q.mask = mask; q.mask_chain_heads = true;

@@ -651,6 +651,26 @@ __global__ void k_road_records_map(RoadMapArgs a);
 __global__ void k_road_records_seg(RoadSegArgs a);
 __global__ void k_road_paths(RoadPathArgs a);
 
+// route_kernels.hip: the per-step allowed-token sets of route-following decoding (include/infgen_hip.h, "route masks"):
+// set(i) = base(i) AND onroute(i), written as the row's own set of out_bits
+constexpr int RT_REC = 8;               // floats of a record: p0 x, y, direction x, y | L, cum, 0, 0
+constexpr int RT_MAX_POINTS = 32;       // waypoints of a route at most: its segments fit the lanes of half a wave
+struct RouteArgs {
+  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* first_new;                  // [S]; first_new optional
+  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
+  const float* end_pose; int token_size;                      // [3][token_size][4] + 4 floats
+  const float* records; const float* total; int P;            // [S / copies][A_cap][P - 1][RT_REC], [S / copies][A_cap]
+  int copies; float corridor, back, pace, finish; int types[3];      // types[ty] != 0: the rule applies to rows of agent type ty
+  TokenMaskCtl base;                    // the sets the route rule refines (bits == NULL: every token)
+  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
+  float* out_progress;                  // optional [S * A_cap][4] = s0, d0, total, flag
+};
+struct RouteRecArgs { const float* routes; const int* n_points; int rows, P; float* records; float* total; };   // rows = S * A_cap
+__global__ void k_route_mask(RouteArgs a);
+__global__ void k_route_records(RouteRecArgs a);
+
 // branch_kernels.hip: branching rollouts (include/infgen_hip.h, "branching").  k_branch_scenes gathers, for every scene s with a
 // valid parent[s] != s, slot parent[s]'s rollout state into slot s - one launch over (chunk of a segment, scene).  A SEGMENT is one
 // buffer of the context as `outer` blocks per scene: block o of scene s is the `bytes` bytes at base + o * outer_stride + s * bytes.

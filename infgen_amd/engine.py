@@ -556,7 +556,7 @@ class RolloutEngine:
                  token_logprob: bool = False, sample_logprob: bool = False,
                  sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
                  token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False, stay_on_road=False,
-                 step_scores=False):
+                 step_scores=False, follow_routes=False):
         """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
@@ -609,6 +609,16 @@ class RolloutEngine:
         set (all tokens without ``token_masks``); a row whose every token collides keeps its static set.  ``collision_bits``
         [S * A_cap][token_size / 32] and ``collision_allowed`` [S * A_cap] (the sets' sizes before that fallback) are static device
         buffers that hold the sets of the step that just ran.  ``reload*(avoid_collisions=...)`` turns it on or off (None: keep).
+        ``follow_routes``: route-following decoding ("route masks" of include/infgen_hip.h) - False or
+        ``dict(routes=, n_points=, corridor=2.0, back=0.5, pace=0.0, finish=1.0, types=('veh', 'cyc'))``: ``routes`` [S0][A][P][2]
+        world-coordinate waypoints per distinct scene and initial row (2 <= P <= 32, A <= A_cap), ``n_points`` [S0][A].  Every
+        decode step bans, for the generated rows of those types that have a route and have not finished it, the motion tokens
+        whose end box's centre leaves the corridor around the route (unless it ends nearer to it than the row is), falls more
+        than ``back`` metres behind the row's arc position or - ``pace`` > 0 - gains less than ``pace`` times the best gain; on top
+        of the static, collision or road set, and a row with no token left keeps that set.  ``route_bits`` / ``route_allowed`` /
+        ``route_progress`` ([rows, 4] = s0, d0, total, flag) are static device buffers of the step that just ran;
+        ``set_routes(routes, n_points)`` replaces the routes between two steps.  ``reload*(follow_routes=...)`` turns it on or
+        off (None: keep).  Rows scenario insertion appends have no route.
         ``stay_on_road``: road-aware decoding ("road masks" of include/infgen_hip.h) - False, True or
         ``dict(margin=metres, sweep=0 | 1, detail=1 | 2 | 5 | 10, types=('veh', 'cyc'), segments=None)``.  Every decode step bans the
         motion tokens whose end box or (``sweep``) path rectangle overlaps a road-edge segment the row does not already straddle, on
@@ -809,7 +819,10 @@ class RolloutEngine:
         self.step_scores = None                           # the checked configuration while step scores are on
         self.step_score = self.score_row = None           # [S, steps, 8] floats, [S, A_cap] flag bytes
         self._score_arg = self._score_shape = self._score_reg = None
-        self._load_riders((token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
+        self.follow_routes = None                         # the checked configuration while route-following decoding is on
+        self.route_bits = self.route_allowed = self.route_progress = None
+        self._route = self._route_reg = None
+        self._load_riders((token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores, follow_routes)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -1061,6 +1074,48 @@ class RolloutEngine:
             self._load_scores(self._score_arg)
         self._apply_token_masks()
 
+    def _load_routes(self, follow):
+        """``follow_routes`` into the engine (None: keep what is there), like ``_load_collisions``; the routes are uploaded and
+        their records built at once (they do not depend on the scene in the buffers)"""
+        if follow is None:
+            return
+        conf = constraints.check_follow_routes(follow, n_scenes=self.S0, a_cap=self.A_cap)
+        if conf is None and self.follow_routes is None:
+            return
+        if constraints.route_key(conf) != constraints.route_key(self.follow_routes):
+            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
+        self.follow_routes = conf
+        if conf is not None:
+            self._upload_routes(conf.pop('routes'), conf.pop('n_points'))
+        else:      # off: nothing of the last routed step stays readable
+            self._route = self.route_bits = self.route_allowed = self.route_progress = None
+        self._apply_token_masks()
+
+    def set_routes(self, routes, n_points):
+        """new routes for an engine with ``follow_routes`` on - allowed between two steps of a rollout or session: uploaded into
+        the static buffers (new ones when P changes), the records rebuilt by k_route_records on the engine's stream.  A captured
+        graph is dropped, as after every change of a pointer"""
+        if self.follow_routes is None:
+            raise ValueError('set_routes: the engine was built without follow_routes')
+        self._upload_routes(*constraints.route_arrays(routes, n_points, n_scenes=self.S0, a_cap=self.A_cap))
+        self._graph = self._wgraph = None
+        self._apply_token_masks()
+
+    def _upload_routes(self, routes: np.ndarray, n_points: np.ndarray):
+        P = int(routes.shape[2])
+        if self._route is None or self._route['P'] != P:
+            self._route = constraints.route_buffers(self.S0, self.S * self.A_cap, self.A_cap, P, self.cfg.token_size, self.device)
+            self.route_bits, self.route_allowed, self.route_progress = (self._route[k] for k in ('bits', 'allowed', 'progress'))
+            self._end_pose_table()
+            self._graph = self._wgraph = None          # (a captured graph holds the old buffers' addresses)
+        k, A = self._route, int(routes.shape[1])
+        full, n = np.zeros((self.S0, self.A_cap, P, 2), np.float32), np.zeros((self.S0, self.A_cap), np.int32)
+        full[:, :A], n[:, :A] = routes, n_points
+        k['routes'].copy_(torch.from_numpy(full))
+        k['n_points'].copy_(torch.from_numpy(n))
+        _lib.check(self.lib.infgen_route_records(_lib.ptr(k['routes']), _lib.ptr(k['n_points']), self.S0, self.A_cap, P,
+                                                 _lib.ptr(k['records']), _lib.ptr(k['total']), self.ops.stream), 'infgen_route_records')
+
     def _load_scores(self, scores):
         """``step_scores`` into the engine (None: keep what is there), like ``_load_road``, whose record table the scores share"""
         if scores is None:
@@ -1137,7 +1192,7 @@ class RolloutEngine:
         three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  A
         collision configuration rides on the handle (one without a table when the engine has no ``token_masks``)"""
         if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and self.stay_on_road is None
-                                 and self.step_scores is None and not self._mask_handle):
+                                 and self.step_scores is None and self.follow_routes is None and not self._mask_handle):
             return
         if self.token_masks is not None:
             reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
@@ -1177,6 +1232,13 @@ class RolloutEngine:
                lambda: (P(self.step_score), int(self.step_score.shape[1]), P(self.score_row), P(self._score_boxes()),
                         P(self.road_records), P(self.road_n_records), self._road_cap, self.copies, sc['sweep'], sc['road_margin'],
                         (C.c_int * 3)(*sc['types']), sc['dt']))
+        # and the route configuration, the last stage in front of the heads
+        rt, kt = self.follow_routes, self._route
+        attach('_route_reg', None if rt is None else (h, constraints.route_key(rt), kt['records'].data_ptr()), 'infgen_token_mask_route',
+               (None, None, None, None, None, None, 2, 1, 0.0, 0.0, 0.0, 0.0, None, None, None),
+               lambda: (P(kt['bits']), P(kt['ident']), P(kt['shape']), P(self._coll_end), P(kt['records']), P(kt['total']), kt['P'],
+                        self.copies, rt['corridor'], rt['back'], rt['pace'], rt['finish'], (C.c_int * 3)(*rt['types']),
+                        P(kt['allowed']), P(kt['progress'])))
         self._ctx.token_mask = h
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
@@ -1185,6 +1247,7 @@ class RolloutEngine:
         if getattr(self, '_mask_handle', 0):
             self.lib.infgen_token_mask_destroy(self._mask_handle)
             self._mask_handle, self._mask_reg, self._coll_reg, self._road_reg, self._score_reg = 0, None, None, None, None
+            self._route_reg = None
             if getattr(self, '_ctx', None) is not None:
                 self._ctx.token_mask = 0
 
@@ -1200,7 +1263,7 @@ class RolloutEngine:
             c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
-    def _load_riders(self, token_masks=None, avoid_collisions=None, stay_on_road=None, step_scores=None):
+    def _load_riders(self, token_masks=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
         """what rides on the decode step into the engine, in the one order it is resolved in: masks, collisions, road, scores (each
         None: keep what is there; ``token_masks`` a (table, per-type, per-row) triple).  Road and scores are checked against each
         other once both are resolved: the scores' argument is recorded - and scores that go are gone - before ``_load_road``
@@ -1213,10 +1276,11 @@ class RolloutEngine:
                 self._load_scores(False)
         self._load_road(stay_on_road)
         self._load_scores(step_scores)
+        self._load_routes(follow_routes)
 
     def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
-                       avoid_collisions=None, stay_on_road=None, step_scores=None):
-        self._load_riders(token_masks, avoid_collisions, stay_on_road, step_scores)
+                       avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
+        self._load_riders(token_masks, avoid_collisions, stay_on_road, step_scores, follow_routes)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
@@ -1289,7 +1353,7 @@ class RolloutEngine:
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-               avoid_collisions=None, stay_on_road=None, step_scores=None):
+               avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -1304,7 +1368,8 @@ class RolloutEngine:
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
+                            follow_routes)
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1321,7 +1386,7 @@ class RolloutEngine:
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                       sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None,
-                      token_mask_row=None, avoid_collisions=None, stay_on_road=None, step_scores=None) -> bool:
+                      token_mask_row=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -1336,7 +1401,8 @@ class RolloutEngine:
             return False
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
+                            follow_routes)
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1398,7 +1464,7 @@ class RolloutEngine:
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
                      sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-                     avoid_collisions=None, stay_on_road=None, step_scores=None):
+                     avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1408,7 +1474,8 @@ class RolloutEngine:
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores)
+                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
+                            follow_routes)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 

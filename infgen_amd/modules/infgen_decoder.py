@@ -17,8 +17,8 @@ import torch.nn as nn
 
 from .. import _lib, logprob, modes, scene_setup
 from ..closed_loop import ClosedLoopSession
-from ..constraints import (TokenMasks, check_avoid_collisions, check_stay_on_road, check_step_scores, check_type_selectors, road_key,
-                           score_key)
+from ..constraints import (TokenMasks, check_avoid_collisions, check_follow_routes, check_stay_on_road, check_step_scores,
+                           check_type_selectors, road_key, route_key, score_key)
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -401,6 +401,10 @@ class InfGenDecoder(nn.Module):
         # segments=).  Taken by the same entries; its settings are part of the engine cache key, explicit segments are contents that
         # every call loads again with its scenes
         self.stay_on_road = False
+        # route-following decoding (RolloutEngine's follow_routes): False or dict(routes=, n_points=, corridor=, back=,
+        # pace=, finish=, types=), routes [scenes][A][P][2] for the scenes of the call (with copies = n a scene's routes apply to each
+        # of its copies).  Its scalars and P are part of the engine cache key; the routes are contents loaded with every call
+        self.follow_routes = False
         # step scores (RolloutEngine's step_scores): False, True or dict(road_margin=, sweep=, types=, detail=,
         # segments=, dt=) - every rollout dict then carries ``step_score`` [steps, 8]; keyed and loaded like stay_on_road.
         # guided_rollouts: None or a dict of RolloutEngine.rollout_guided's arguments (every=, keep=, weights=, u=): the copies of
@@ -527,6 +531,10 @@ class InfGenDecoder(nn.Module):
                 fixed.update(stay_on_road=sr)
             else:      # (world coordinates of this call's scenes: loaded with them, like the uniforms)
                 live.update(stay_on_road=sr)
+        fr = check_follow_routes(getattr(self, 'follow_routes', False), n_scenes=n_scenes)
+        if fr is not None:      # (the engine takes the caller's own form; the waypoints are world coordinates of this call's scenes)
+            key += (('follow_routes',) + route_key(fr) + (int(fr['routes'].shape[2]),),)
+            live.update(follow_routes=self.follow_routes)
         ss = check_step_scores(getattr(self, 'step_scores', False), stay_on_road=sr)
         if getattr(self, 'guided_rollouts', None) is not None and ss is None:
             raise ValueError('guided_rollouts needs step_scores')

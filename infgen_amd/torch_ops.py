@@ -20,6 +20,9 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.road_mask(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_records, copies=1,
                                    sweep=1, margin=0, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
                                                                                             -> sets (S A, token_size / 32) int32, allowed (S A,)
+    torch.ops.infgen_hip.route_mask(pos, head, state, n_agents, type, shape, c, end_pose, records, total, copies=1, corridor=2,
+                                    back=0.5, pace=0, finish=1, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
+                                                                                            -> sets, allowed (S A,), progress (S A, 4)
     torch.ops.infgen_hip.step_score(pos, head, state, n_agents, type, shape, c1, records?, n_records?, copies=1, sweep=1,
                                     road_margin=0, types=[1, 0, 1], dt=0.5)                 -> score (S, 8), flags (S, A) uint8
     torch.ops.infgen_hip.observe_rows(pos, head, state, n_agents, type, shape, c, dt, map_pos?, map_orient?, map_type?, n_map?,
@@ -484,6 +487,77 @@ def _(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_re
       mask_bits=None, mask_row=None, mask_type=None, first_new=None):
     rows = pos.shape[0] * pos.shape[2]
     return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32))
+
+
+def route_records(routes: torch.Tensor, n_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the segment records of per-row routes ("route masks" of include/infgen_hip.h, ``infgen_route_records``): ``routes``
+    (S0, A, P, 2) world-coordinate waypoints, 2 <= P <= 32, ``n_points`` (S0, A) -> records (S0, A, P - 1, 8), total (S0, A)"""
+    if routes.dim() != 4 or routes.shape[3] != 2 or not 2 <= routes.shape[2] <= 32 or tuple(n_points.shape) != tuple(routes.shape[:2]):
+        raise ValueError('route_records takes routes (S0, A, P, 2) with 2 <= P <= 32 and n_points (S0, A)')
+    dev = routes.device
+    ops = _ops(dev)
+    S0, A, P = (int(v) for v in routes.shape[:3])
+    rt, n = _f32(routes), n_points.to(dev, torch.int32).contiguous()
+    rec, total = torch.zeros(S0, A, P - 1, 8, device=dev), torch.zeros(S0, A, device=dev)
+    _lib.check(ops.lib.infgen_route_records(_lib.ptr(rt), _lib.ptr(n), S0, A, P, _lib.ptr(rec), _lib.ptr(total), ops.stream),
+               'infgen_route_records')
+    return rec, total
+
+
+@torch.library.custom_op('infgen_hip::route_mask', mutates_args=())
+def route_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+               shape: torch.Tensor, c: int, end_pose: torch.Tensor, records: torch.Tensor, total: torch.Tensor, copies: int = 1,
+               corridor: float = 2.0, back: float = 0.5, pace: float = 0.0, finish: float = 1.0, types: Optional[List[int]] = None,
+               mask_bits: Optional[torch.Tensor] = None, mask_row: Optional[torch.Tensor] = None,
+               mask_type: Optional[List[int]] = None, first_new: Optional[torch.Tensor] = None
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the allowed-token sets of one decode step from the rows' routes (route-following decoding; "route masks" of
+    include/infgen_hip.h, ``infgen_route_mask``): the scene arrays and ``end_pose`` as for ``collision_mask``, ``records``
+    (S / copies, A, P - 1, 8) and ``total`` (S / copies, A) from ``route_records``, ``types`` the (vehicle, pedestrian, cyclist)
+    switch (None: vehicles and cyclists).  ``mask_bits`` / ``mask_row`` / ``mask_type``: the base sets (none: every token).  Returns
+    the sets (S * A, token_size / 32) int32 words, the number of allowed tokens per row before the empty-set fallback (S * A,) and
+    the progress (S * A, 4) = s0, d0, total, flag (1 ruled, 2 finished)."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or head.shape != pos.shape[:3] or state.shape != pos.shape[:3]:
+        raise ValueError('route_mask takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,):
+        raise ValueError('route_mask takes type (S, A), shape (S, A, 3), n_agents (S,)')
+    if first_new is not None and tuple(first_new.shape) != (S,):
+        raise ValueError('first_new must be (S,)')
+    token_size = (int(end_pose.numel()) - 4) // 12
+    if end_pose.dim() != 1 or token_size * 12 + 4 != end_pose.numel() or token_size % 32:
+        raise ValueError('end_pose is the table of collision_end_poses (12 token_size + 4 floats, token_size a multiple of 32)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    if records.dim() != 4 or records.shape[3] != 8 or tuple(records.shape[:2]) != (S // copies, A) or tuple(total.shape) != (S // copies, A):
+        raise ValueError('route_mask takes records (S / copies, A, P - 1, 8) and total (S / copies, A)')
+    types = [1, 0, 1] if types is None else [int(bool(v)) for v in types]
+    if len(types) != 3:
+        raise ValueError('types has three entries: vehicle, pedestrian, cyclist')
+    dev = pos.device
+    ops = _ops(dev)
+    i32 = lambda t: None if t is None else t.to(dev, torch.int32).contiguous()
+    ty = i32(type)
+    tm, _keep_mask = _token_mask(mask_bits, mask_row, mask_type, ty.reshape(-1), S * A, token_size, dev)
+    bits = torch.zeros(S * A, token_size // 32, device=dev, dtype=torch.int32)
+    count = torch.zeros(S * A, device=dev, dtype=torch.int32)
+    progress = torch.zeros(S * A, 4, device=dev)
+    st, na, fn = i32(state), i32(n_agents), i32(first_new)
+    p, h, sh, ep, rc, tt = _f32(pos), _f32(head), _f32(shape), _f32(end_pose), _f32(records), _f32(total)
+    _lib.check(ops.lib.infgen_route_mask(_lib.ptr(p), _lib.ptr(h), _lib.ptr(st), _lib.ptr(na), _lib.ptr(fn), _lib.ptr(ty), _lib.ptr(sh),
+                                         S, A, T, int(c), _lib.ptr(ep), token_size, _lib.ptr(rc), _lib.ptr(tt),
+                                         int(records.shape[2]) + 1, int(copies), float(corridor), float(back), float(pace),
+                                         float(finish), (C.c_int * 3)(*types), *tm[:4], _lib.ptr(bits), _lib.ptr(count),
+                                         _lib.ptr(progress), ops.stream), 'infgen_route_mask')
+    return bits, count, progress
+
+
+@route_mask.register_fake
+def _(pos, head, state, n_agents, type, shape, c, end_pose, records, total, copies=1, corridor=2.0, back=0.5, pace=0.0, finish=1.0,
+      types=None, mask_bits=None, mask_row=None, mask_type=None, first_new=None):
+    rows = pos.shape[0] * pos.shape[2]
+    return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32),
+            pos.new_empty(rows, 4, dtype=torch.float32))
 
 
 @torch.library.custom_op('infgen_hip::step_score', mutates_args=())
