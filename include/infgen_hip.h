@@ -818,6 +818,54 @@ int infgen_observe_rows(const float* pos, const float* head, const int* state, c
                         float radius, int Km, float map_radius, float* self_feat, float* nbr_feat, int* nbr_index, int* nbr_count,
                         float* map_feat, int* map_index, int* map_count, void* stream);
 
+/* rule-based controlled agents: IDM COMMANDS, the next target pose of rows that follow their route under the intelligent-driver
+ * car-following law (k_idm_command: one launch, no host read, no atomics) - what a closed-loop session hands to infgen_command_rows
+ * as a pose command.  fp32 throughout, no fused multiply-add; world coordinates enter only through the exact differences
+ * p0 - pos[c][i] and pos[c][j] - pos[c][i] (and pos[c][j] - pos[c-1][j] for the speeds).
+ *   column   c is the newest stored column, 1 <= c < T.  Row i of scene slot s is LIVE at a column when i < n_agents[s] and its state
+ *       there is not invalid (0): the step scores' notion, without first_new.
+ *   ruled   a row is RULED iff ctl_row[s][i] != 0 (a byte per row), it is live at c, its type ty (0 vehicle, 1 pedestrian, 2 cyclist;
+ *       others count as 0) has types[ty] != 0, and total > 0.  The route tables - records, total of infgen_route_records and the
+ *       optional v_des [S / copies][A_cap] - are read at row (s / copies, i), as by k_route_mask.  cmd_pose is NOT written for any
+ *       other row (not ruled, or padding); their out_state row is eight zeros and their out_lead is -1.
+ *   speed   v = |pos[c][i] - pos[c-1][i]| / dt if the row is live at c - 1, else 0: the difference first, then
+ *       sqrtf(dx * dx + dy * dy) / dt.
+ *   own projection   the row's live records are moved into its frame once - translate by pos[c][i], then rotate by -head[c][i]:
+ *       q0 = R(p0 - pos), u = R(ux, uy) with R(x, y) = (x ci + y si, y ci - x si), ci = cosf(head), si = sinf(head) - and the origin is
+ *       projected by the route masks' rule: over the live segments in order a = min(max((e - q0) . u, 0), L), f = e - q0 - a u,
+ *       d2 = |f|^2, the FIRST segment of least d2.  That gives s0 = cum + a, the segment g0 and the offset vector f;
+ *       e0 = f.x * n.x + f.y * n.y with n = (-u.y, u.x) of g0 is the signed lateral offset (left of the route: positive).
+ *   lead search   for every j != i live at c: the centre pos[c][j] - pos[c][i], rotated into the row's frame, is projected the same
+ *       way: s_j, d_j = sqrtf(d2), the segment g_j.  j is a CANDIDATE iff d_j <= lateral + 0.5f * (w_i + w_j) and s_j > s0
+ *       (w = shape[.][1], len = shape[.][0]); gap_j = (s_j - s0) - 0.5f * (len_i + len_j);
+ *       vl_j = max(0, (R(pos[c][j] - pos[c-1][j]) . u(g_j)) / dt) if j is live at c - 1, else 0.  The LEAD is the candidate of least
+ *       gap_j, ties to the lowest j.  With stop_at_end != 0 the route's end is a standing candidate: gap = (total - s0) - 0.5f * len_i,
+ *       vl = 0, index -2; it wins only if its gap is strictly less than the best agent gap.  No candidate: lead -1, gap = +inf, and
+ *       the interaction term of the law is 0.
+ *   law   g = max(gap, 0.1f); v0 = v_des[route row] where v_des is given and that entry is > 0, else v0_type[ty];
+ *       sstar = s_min + max(0, v * headway + v * (v - vl) / (2 * sqrtf(a_max * b_comf))); r = v / v0, free = 1 - (r * r) * (r * r),
+ *       q = sstar / g (0 without a lead); acc = a_max * (free - q * q), clamped to [-b_max, a_max]; v1 = max(0, v + acc * dt);
+ *       s1 = min(s0 + 0.5f * (v + v1) * dt, total).
+ *   target   the first live segment in order with s1 <= cum + L, or the last live one if there is none; a1 = min(max(s1 - cum, 0), L);
+ *       the point of the row's frame t = (q0 + a1 * u) + (keep * e0) * n, with that segment's u and n, is rotated back by +head -
+ *       (t.x ci - t.y si, t.x si + t.y ci) - and added to pos[c][i]; heading = atan2f(uy, ux) of the record's stored world direction.
+ *       cmd_pose[s][i] = (x, y, heading).
+ *   outputs   out_state [S * A_cap][8] (optional, 16-byte aligned) = (s0, e0, v, gap, acc, v1, s1, 1); out_lead [S * A_cap]
+ *       (optional) = j, -1 or -2.  A d_j within ~1e-4 m of its threshold, two gaps or two segments' d2 that tie that closely, or an
+ *       s_j that close to s0 may fall either way.
+ * infgen_idm_command: one launch of k_idm_command over the S * A_cap rows; v0_type (three floats) and types (three ints) are host
+ * arrays read at the call, like the route masks' types.  A session launches it in front of infgen_command_rows with ctl_row = its
+ * controlled-row flags; rows scenario insertion appends are never ruled there but count as obstacles once live.
+ * Refused, each with a message and no launch: a parameter that is not finite; dt, a_max, b_comf, b_max or a v0_type entry <= 0;
+ * headway, s_min or lateral < 0; keep outside [0, 1]; P outside 2..32; copies < 1 or not dividing S; c < 1 or c >= T; A_cap beyond
+ * INFGEN_Q_MAX_AGENTS; a missing required pointer (everything but v_des, out_state and out_lead); records or out_state that are not
+ * 16-byte aligned. */
+int infgen_idm_command(const float* pos, const float* head, const int* state, const int* n_agents, const int* type, const float* shape,
+                       const uint8_t* ctl_row, int S, int A_cap, int T, int c, const float* records, const float* total, int P,
+                       int copies, const float* v_des, float dt, const float* v0_type, float headway, float s_min, float a_max,
+                       float b_comf, float b_max, float lateral, float keep, const int* types, int stop_at_end, float* cmd_pose,
+                       float* out_state, int* out_lead, void* stream);
+
 /* ---- scenario insertion (reference agent_decoder.py:1773-2105); the sub-loop is sequenced by the host ----
  *   infgen_occupancy        one-hot sum of the grid tokens of column c (:1852-1854); tokens outside [0, grid_size) mark no cell
  *   infgen_point_edges      _build_a2sa_edge / _build_map2sa_edge for one query point per scene (:760-904):

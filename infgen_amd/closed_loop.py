@@ -8,6 +8,9 @@ decode step at a time, from what the other agents did so far, while the model ge
         ses.advance()                                # the command kernel + one decode step (+ the step's insertion sub-loop)
     out = ses.outputs()
 
+The repository's own controller is ``ses.command_idm(routes=...)`` in place of ``command`` (``run_idm`` loops it to the end): the
+controlled rows follow their routes under the intelligent-driver car-following law, computed on the device.
+
 A session is log replay (``RolloutEngine(replay=...)``) whose plan is written column by column: ``advance`` launches
 ``infgen_command_rows``, which turns the step's commands into the plan entries of column 2 + t on the device - a token id as it is, a
 target pose through the nearest motion token of the row's vocabulary - and then runs the decode step, whose ``k_integrate`` forces
@@ -21,7 +24,7 @@ from typing import Dict
 
 import torch
 
-from . import _lib, constraints, observe
+from . import _lib, constraints, controllers, observe
 
 KIND_TOKEN, KIND_POSE = 0, 1
 
@@ -65,6 +68,7 @@ class ClosedLoopSession:
         self._mask = torch.ones(S, A_cap, dtype=torch.uint8, device=dev)
         self.cost = torch.zeros(S, A_cap, device=dev)
         self._kind = self._result = None
+        self._idm = None                                # command_idm()'s result buffers, allocated at its first call
         self._look = None                               # lookahead()'s snapshot buffer, allocated at its first call
         self._obs_rows, self._obs_out, self._obs_key = {}, None, None     # observe(frame='agent'): row lists, the last result
         self.t = 0
@@ -154,6 +158,9 @@ class ClosedLoopSession:
             if self.t > 0:
                 obs['step_score'] = eng.step_score[:, self.t - 1]
             obs['score_row'] = eng.score_row
+        if self._idm is not None:                 # command_idm: what the last call found (s0, e0, v, gap, acc, v1, s1, flag; the lead)
+            obs['idm_state'] = self._idm['state'].view(eng.S, eng.A_cap, 8)
+            obs['idm_lead'] = self._idm['lead'].view(eng.S, eng.A_cap)
         if frame == 'agent':
             obs_row = self._observed_rows(rows)
             out = self._obs_out if self._obs_out is not None and self._obs_key == (int(obs_row.numel()), neighbors, map_tokens) else None
@@ -194,6 +201,29 @@ class ClosedLoopSession:
         else:
             self._pose.copy_(self._rows(poses, torch.float32, 'poses', tail=(3,)))
             self._kind = KIND_POSE
+        if mask is None:
+            self._mask.fill_(1)
+        else:
+            self._mask.copy_(self._rows(mask, torch.uint8, 'mask'))
+
+    def command_idm(self, routes=None, n_points=None, v_des=None, mask=None, **params):
+        """the controlled rows' command for step ``t`` from the rule-based controller (``RolloutEngine.idm_command``):
+        the session's pose buffer is filled with every row's current pose - a controlled row without a route, or of a type the
+        rule does not cover, stands still -, ``infgen_idm_command`` writes the targets of the ruled rows over it from the newest
+        stored column, and the pending command becomes that pose command.  ``routes`` / ``n_points``: the routes (None: the
+        engine's ``follow_routes`` tables); ``v_des`` [S0][A]: own desired speeds; ``params``: the keys of
+        ``controllers.check_idm``; ``mask`` as for ``command``.  Nothing is read on the host.  ``observe()['idm_state']``
+        [S, A_cap, 8] = s0, e0, v, gap, acc, v1, s1, flag and ``['idm_lead']`` [S, A_cap] = j, -1, -2 show what it found."""
+        self._check_open()
+        if self.done:
+            raise RuntimeError('the session has run its last step')
+        eng, c = self.eng, self.eng.hc - 1 + self.t
+        self._pose[..., :2].copy_(eng.pos[:, c])
+        self._pose[..., 2].copy_(eng.head[:, c])
+        if self._idm is None:
+            self._idm = dict(controllers.idm_buffers(eng.S, eng.A_cap, eng.device), pose=self._pose)
+        eng.idm_command(c, ctl_row=eng.replay_row, routes=routes, n_points=n_points, v_des=v_des, out=self._idm, **params)
+        self._kind = KIND_POSE
         if mask is None:
             self._mask.fill_(1)
         else:
@@ -348,3 +378,11 @@ class ClosedLoopSession:
     def outputs_batch(self):
         self._check_done()
         return self.eng.outputs_batch()
+
+
+def run_idm(session: ClosedLoopSession, **kw):
+    """``command_idm(**kw)`` + ``advance()`` until the session's last step -> the session (``outputs()`` is ready)"""
+    while not session.done:
+        session.command_idm(**kw)
+        session.advance()
+    return session

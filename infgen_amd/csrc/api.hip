@@ -1824,6 +1824,46 @@ extern "C" int infgen_observe_rows(const float* pos, const float* head, const in
   return launch_observe(me, a, stream);
 }
 
+// ---------------------------------------------------------------------------------- IDM commands
+// the argument checks of include/infgen_hip.h ("IDM commands") and the one launch of k_idm_command
+extern "C" int infgen_idm_command(const float* pos, const float* head, const int* state, const int* n_agents, const int* type,
+                                  const float* shape, const uint8_t* ctl_row, int S, int A_cap, int T, int c, const float* records,
+                                  const float* total, int P, int copies, const float* v_des, float dt, const float* v0_type,
+                                  float headway, float s_min, float a_max, float b_comf, float b_max, float lateral, float keep,
+                                  const int* types, int stop_at_end, float* cmd_pose, float* out_state, int* out_lead, void* stream) {
+  const char* me = "infgen_idm_command";
+  if (!v0_type || !types) return fail(me, "idm: needs the three desired speeds v0_type and the three-entry type switch");
+  const float values[] = {dt, v0_type[0], v0_type[1], v0_type[2], headway, s_min, a_max, b_comf, b_max, lateral, keep};
+  for (float x : values)
+    if (!std::isfinite(x)) return fail(me, "idm: every parameter must be finite");
+  if (!(dt > 0.f) || !(a_max > 0.f) || !(b_comf > 0.f) || !(b_max > 0.f)) return fail(me, "idm: dt, a_max, b_comf and b_max must be > 0");
+  if (!(v0_type[0] > 0.f) || !(v0_type[1] > 0.f) || !(v0_type[2] > 0.f)) return fail(me, "idm: every v0_type must be > 0");
+  if (headway < 0.f || s_min < 0.f || lateral < 0.f) return fail(me, "idm: headway, s_min and lateral must be >= 0");
+  if (keep < 0.f || keep > 1.f) return fail(me, "idm: keep must be in [0, 1]");
+  if (P < 2 || P > RT_MAX_POINTS) return fail(me, "idm: P must be in 2..32");
+  if (copies < 1) return fail(me, "idm: copies must be at least 1");
+  if (S <= 0 || A_cap <= 0 || T <= 0) return fail(me, "idm: S, A_cap and T must be positive");
+  if (S % copies) return fail(me, "idm: S must be a multiple of copies");
+  if (c < 1 || c >= T) return fail(me, "idm: column outside [1, T)");
+  if (A_cap > MAX_SCENE_AGENTS) return fail(me, "idm: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (!pos || !head || !state || !n_agents || !type || !shape || !ctl_row) return fail(me, "idm: null scene array");
+  if (!records || !total) return fail(me, "idm: needs the record table and the routes' lengths");
+  if (!cmd_pose) return fail(me, "idm: needs the pose buffer cmd_pose [S][A_cap][3]");
+  if (misaligned16(records, out_state)) return fail(me, "idm: records and out_state must be 16-byte aligned");
+  const long long rows = (long long)S * A_cap;
+  if (rows > 0x7fffffffLL) return fail(me, "idm: too many rows");
+  IdmArgs a{};
+  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c;
+  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.type = type; a.shape = shape; a.ctl_row = ctl_row;
+  a.records = records; a.total = total; a.P = P; a.copies = copies; a.v_des = v_des;
+  a.dt = dt; a.headway = headway; a.s_min = s_min; a.a_max = a_max; a.b_comf = b_comf; a.b_max = b_max; a.lateral = lateral; a.keep = keep;
+  for (int i = 0; i < 3; ++i) { a.v0_type[i] = v0_type[i]; a.types[i] = types[i]; }
+  a.stop_at_end = stop_at_end;
+  a.cmd_pose = cmd_pose; a.out_state = out_state; a.out_lead = out_lead;
+  hipLaunchKernelGGL(k_idm_command, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
 // ---------------------------------------------------------------------------------- rollout context
 static SceneState scene_of(const InfgenRollout* r) {
   SceneState st;

@@ -746,6 +746,22 @@ struct ObserveArgs {
 };
 __global__ void k_observe_rows(ObserveArgs a);
 
+// controller_kernels.hip: the target poses of rule-based controlled rows (include/infgen_hip.h, "IDM commands"): route projection,
+// lead search and the car-following law, one wave per row
+struct IdmArgs {
+  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the newest stored one, c >= 1
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+  const unsigned char* ctl_row;         // [S][A_cap]: != 0, the row is controlled
+  const float* records; const float* total; int P, copies;    // [S / copies][A_cap][P - 1][RT_REC], [S / copies][A_cap]
+  const float* v_des;                   // optional [S / copies][A_cap]: the row's own desired speed where > 0
+  float dt, v0_type[3], headway, s_min, a_max, b_comf, b_max, lateral, keep;
+  int types[3], stop_at_end;            // types[ty] != 0: rows of agent type ty may be ruled
+  float* cmd_pose;                      // [S][A_cap][3], written for ruled rows only
+  float* out_state; int* out_lead;      // optional [S * A_cap][8], [S * A_cap]
+};
+__global__ void k_idm_command(IdmArgs a);
+
 struct TokenLogprobArgs {
   const float* logits; int rows; int n;      // [rows][n]
   const int* token;                          // [rows]

@@ -11,10 +11,9 @@
 // fp32 throughout, no fused multiply-add (the build's -ffp-contract=off), no atomics, plain vector stores.
 #include "kernels.h"
 #include "rider.cuh"
+#include "route.cuh"
 
 namespace ig {
-
-constexpr int RT_SEGS = RT_MAX_POINTS;  // list entries per wave (31 used at most)
 
 __global__ __launch_bounds__(64 * RIDER_WAVES) void k_route_records(RouteRecArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -45,23 +44,6 @@ __global__ __launch_bounds__(64 * RIDER_WAVES) void k_route_records(RouteRecArgs
     out[1] = make_float4(L, L > 0.f ? cum : 0.f, 0.f, 0.f);
   }
   if (lane == 0) a.total[row] = run;
-}
-
-// the point (ex, ey) of the row's frame on the m list entries (la = q0 x, y, direction x, y; lb = L, cum): the arc length s of its
-// projection onto the FIRST segment of least squared distance d2
-struct RouteHit { float s, d2; };
-__device__ __forceinline__ RouteHit route_project(float ex, float ey, const float4* la, const float4* lb, int m) {
-  RouteHit h{0.f, __builtin_inff()};
-  for (int e = 0; e < m; ++e) {
-    const float4 g = la[e];
-    const float4 q = lb[e];
-    const float rx = ex - g.x, ry = ey - g.y;
-    const float t = fminf(fmaxf(rx * g.z + ry * g.w, 0.f), q.x);
-    const float fx = rx - t * g.z, fy = ry - t * g.w;
-    const float d2 = fx * fx + fy * fy;
-    if (d2 < h.d2) { h.d2 = d2; h.s = q.y + t; }
-  }
-  return h;
 }
 
 __global__ __launch_bounds__(64 * RIDER_WAVES) void k_route_mask(RouteArgs a) {

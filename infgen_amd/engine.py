@@ -20,7 +20,7 @@ from typing import Dict, List, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, constraints, logprob, modes, observe, packing, scene_setup
+from . import _lib, constraints, controllers, logprob, modes, observe, packing, scene_setup
 from .scene_setup import EVAL_SHAPE, INVALID_SHAPE
 from .synth import INVALID, VALID, ENTER, EXIT, AGENT_SHAPE, RolloutConfig
 
@@ -2127,6 +2127,88 @@ class RolloutEngine:
                        constraints.STEP_SECONDS, self.map_pos, self.map_orient, self._map_cat[1], self.n_map, self.copies, r,
                        neighbors, radius, map_tokens, map_radius, res)
         return res
+
+    def idm_command(self, c: int, ctl_row=None, routes=None, n_points=None, v_des=None, out=None, **params) -> Dict[str, torch.Tensor]:
+        """the target poses of rule-based controlled rows from stored column ``c >= 1`` ("IDM commands" of
+        include/infgen_hip.h): every row of ``ctl_row`` ([S, A_cap] uint8 / bool device tensor, None: ``replay_row``) that is live,
+        of a ruled type and has a route follows that route under the intelligent-driver law behind the nearest agent ahead of it.
+        ``routes`` [S0][A][P][2] / ``n_points`` [S0][A]: the routes (``constraints.routes_from_logged`` makes them from a log); the
+        engine keeps tables of its own for them, built by ``infgen_route_records`` and rebuilt only when the routes change (the same
+        array objects as at the last call count as unchanged: pass new arrays for new routes).
+        Without ``routes`` the tables of ``follow_routes`` are read.  ``v_des`` [S0][A]: the rows' own desired speeds where > 0;
+        ``params``: the keys of ``controllers.check_idm``.  One launch of ``infgen_idm_command`` on the engine's own buffers and the
+        current stream, no host read.  -> dict(``pose`` [S, A_cap, 3] - written for ruled rows only, so ``out['pose']`` may hold a
+        fill -, ``state`` [S * A_cap, 8], ``lead`` [S * A_cap]); ``out``: an earlier result, written again.  The scene is only read
+        (``n_agents`` on the device, at launch): rows scenario insertion appends have no route, so they are never ruled, and count
+        as obstacles once live."""
+        if getattr(self, '_shape10', None) is None:
+            raise ValueError('idm_command needs the rows\' shapes: this engine has no shape array')
+        if not 1 <= int(c) < self.T:
+            raise ValueError(f'idm_command: column {c} outside 1 .. {self.T - 1}')
+        conf = controllers.check_idm(params)
+        if routes is not None:
+            if n_points is None:
+                raise ValueError('idm_command: routes come with n_points')
+            tab = self._idm_tables(routes, n_points)
+        elif self._route is not None:
+            tab = self._route
+        else:
+            raise ValueError('idm_command: no routes - pass routes= and n_points= (constraints.routes_from_logged makes them from '
+                             'a log) or build the engine with follow_routes=')
+        if ctl_row is None:
+            ctl_row = self.replay_row
+            if ctl_row is None:
+                raise ValueError('idm_command: no controlled rows - pass ctl_row= or build the engine with replay=')
+        if tuple(ctl_row.shape) != (self.S, self.A_cap):
+            raise ValueError(f'idm_command: ctl_row must be {(self.S, self.A_cap)}, got {tuple(ctl_row.shape)}')
+        ctl_row = ctl_row.to(self.device, torch.uint8).contiguous()
+        vd = None
+        if v_des is not None:
+            vd = torch.as_tensor(v_des, dtype=torch.float32)
+            if vd.dim() != 2 or vd.shape[0] != self.S0 or vd.shape[1] > self.A_cap:
+                raise ValueError(f'idm_command: v_des must be [{self.S0}][<= {self.A_cap}], got {tuple(vd.shape)}')
+            if vd.shape[1] < self.A_cap:
+                vd = torch.nn.functional.pad(vd, (0, self.A_cap - vd.shape[1]))
+            vd = vd.to(self.device).contiguous()
+        res = controllers.idm_buffers(self.S, self.A_cap, self.device, out)
+        pose = None if out is None else out.get('pose')
+        if pose is None:
+            pose = torch.zeros(self.S, self.A_cap, 3, device=self.device)
+        elif tuple(pose.shape) != (self.S, self.A_cap, 3) or pose.dtype != torch.float32 or not pose.is_contiguous() \
+                or pose.device != self.device:
+            raise ValueError(f'idm: out[\'pose\'] must be a contiguous float32 tensor of shape {(self.S, self.A_cap, 3)} on {self.device}')
+        controllers.launch(self.lib, self.ops.stream, self.pos, self.head, self.state, self.n_agents, self.atype, self._shape10, ctl_row,
+                           c, tab['records'], tab['total'], self.copies, vd, conf, pose, res)
+        res['pose'] = pose
+        return res
+
+    def _idm_tables(self, routes, n_points):
+        """the engine's own route tables for ``idm_command(routes=...)``: uploaded and their records rebuilt only when the routes
+        differ from the ones the tables were built from.  The same two array objects as last time are taken as unchanged
+        routes without looking inside - the loop of ``run_idm`` costs no host work per step -, so new routes come as new arrays"""
+        tab = getattr(self, '_idm_route', None)
+        if tab is not None and routes is tab['src'][0] and n_points is tab['src'][1]:
+            return tab
+        r, n = constraints.route_arrays(routes, n_points, n_scenes=self.S0, a_cap=self.A_cap, what='idm_command')
+        if tab is not None and tab['host'][0].shape == r.shape and np.array_equal(tab['host'][0], r, equal_nan=True) \
+                and np.array_equal(tab['host'][1], n):
+            tab['src'] = (routes, n_points)
+            return tab
+        P, A = int(r.shape[2]), int(r.shape[1])
+        if tab is None or tab['P'] != P:
+            dev = self.device
+            tab = dict(P=P, routes=torch.zeros(self.S0, self.A_cap, P, 2, device=dev),
+                       n_points=torch.zeros(self.S0, self.A_cap, dtype=torch.int32, device=dev),
+                       records=torch.zeros(self.S0, self.A_cap, P - 1, 8, device=dev), total=torch.zeros(self.S0, self.A_cap, device=dev))
+        full, cnt = np.zeros((self.S0, self.A_cap, P, 2), np.float32), np.zeros((self.S0, self.A_cap), np.int32)
+        full[:, :A], cnt[:, :A] = r, n
+        tab['routes'].copy_(torch.from_numpy(full))
+        tab['n_points'].copy_(torch.from_numpy(cnt))
+        _lib.check(self.lib.infgen_route_records(_lib.ptr(tab['routes']), _lib.ptr(tab['n_points']), self.S0, self.A_cap, P,
+                                                 _lib.ptr(tab['records']), _lib.ptr(tab['total']), self.ops.stream), 'infgen_route_records')
+        tab['host'], tab['src'] = (r.copy(), n.copy()), (routes, n_points)
+        self._idm_route = tab
+        return tab
 
     def _run_graph(self, t0, t1):
         """the decode steps as a HIP-graph replay.  Replays launched into the LEGACY DEFAULT stream fault now and then on this

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, logprob, modes, scene_setup
-from ..closed_loop import ClosedLoopSession
+from ..closed_loop import ClosedLoopSession, run_idm
 from ..constraints import (TokenMasks, check_avoid_collisions, check_follow_routes, check_stay_on_road, check_step_scores,
                            check_type_selectors, road_key, route_key, score_key)
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
@@ -985,13 +985,16 @@ class InfGenDecoder(nn.Module):
         return r.merged(first={'x_pt': x_pt, **self._empty_map_keys(x_pt.device)}, last={k: data[k] for k in self.data_keys if k in data})
 
     @torch.no_grad()
-    def closed_loop(self, data, controlled='ego', pose: str = 'token'):
+    def closed_loop(self, data, controlled='ego', pose: str = 'token', idm=None):
         """a closed-loop stepping session over ``data`` (one graph or a Batch; infgen_amd/closed_loop.py): the
         ``controlled`` rows - 'ego' or a bool tensor / list of tensors as ``inference(replay=...)`` takes - are commanded step by
         step (``ses.observe()``, ``ses.command(tokens= | poses=)``, ``ses.advance()``), every other agent is generated around
         them.  ``pose``: 'token' stores the commanded / matched token's integration, 'exact' the commanded pose itself.  After
         the last step ``ses.outputs()`` is the dict ``inference(data, replay=controlled, replay_plan=<the commands>)`` returns,
-        ``replay_mask`` included.  The engine is the cached one of ``inference``: another call on this module ends the session."""
+        ``replay_mask`` included.  The engine is the cached one of ``inference``: another call on this module ends the session.
+        ``idm=dict(routes=, n_points=, v_des=, ...)`` (the arguments of ``ClosedLoopSession.command_idm``; an empty dict reads the
+        tables of ``follow_routes``): the controlled rows are driven by the rule-based IDM route follower to the last step
+        (``closed_loop.run_idm``) and the finished outputs are returned instead of the session."""
         if self.map_only():
             raise ValueError('the map-pretraining model decodes no agents: nothing to control')
         gen = self._inference_gen(data, None, controlled, None, session=True)
@@ -1000,7 +1003,10 @@ class InfGenDecoder(nn.Module):
         def finish():
             with torch.no_grad():
                 return self._drive(gen)
-        return ClosedLoopSession(eng, pose=pose, finish=finish)
+        ses = ClosedLoopSession(eng, pose=pose, finish=finish)
+        if idm is None:
+            return ses
+        return run_idm(ses, **idm).outputs()
 
     @torch.no_grad()
     def inference_no_map(self, data, map_enc) -> Dict[str, torch.Tensor]:

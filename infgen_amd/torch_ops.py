@@ -29,6 +29,10 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
                                       copies=1, rows=None, neighbors=8, radius=None (inf), map_tokens=0, map_radius=None (inf))
                                                                                             -> self_feat (N, 8), nbr_feat (N, K, 10), nbr_index (N, K),
                                                                                                nbr_count (N,), map_feat (N, Km, 6), map_index (N, Km), map_count (N,)
+    torch.ops.infgen_hip.idm_command(pos, head, state, n_agents, type, shape, ctl_row, c, records, total, cmd_pose, copies=1,
+                                     v_des?, dt=0.5, v0=[15, 1.5, 6], headway=1.5, s_min=2, a_max=1.5, b_comf=2, b_max=6,
+                                     lateral=0.5, keep=0.5, types=[1, 0, 1], stop_at_end=True)
+                                                                                            -> state (S A, 8), lead (S A,); writes cmd_pose
     torch.ops.infgen_hip.map_token_head(x (N, 128), rows (n,), pack)                        -> logits (n, 1024), top-10 (n, 10) int64
     torch.ops.infgen_hip.mlp_layer(x (N, K), pack, n_out)                                   -> (N, n_out)
     torch.ops.infgen_hip.mlp_embedding(x (N, K), pack)                                      -> (N, 128)
@@ -54,7 +58,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from . import _lib, observe
+from . import _lib, controllers, observe
 from .engine import Ops, D
 
 _OPS = {}
@@ -654,6 +658,59 @@ def _(pos, head, state, n_agents, type, shape, c, dt, map_pos=None, map_orient=N
     N = pos.shape[0] * pos.shape[2] if rows is None else rows.shape[0]
     f, i = (lambda *s: pos.new_empty(*s, dtype=torch.float32)), (lambda *s: pos.new_empty(*s, dtype=torch.int32))
     return (f(N, observe.SELF), f(N, neighbors, observe.NBR), i(N, neighbors), i(N), f(N, map_tokens, observe.MAP), i(N, map_tokens), i(N))
+
+
+@torch.library.custom_op('infgen_hip::idm_command', mutates_args=('cmd_pose',))
+def idm_command(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+                shape: torch.Tensor, ctl_row: torch.Tensor, c: int, records: torch.Tensor, total: torch.Tensor,
+                cmd_pose: torch.Tensor, copies: int = 1, v_des: Optional[torch.Tensor] = None, dt: float = 0.5,
+                v0: Optional[List[float]] = None, headway: float = 1.5, s_min: float = 2.0, a_max: float = 1.5, b_comf: float = 2.0,
+                b_max: float = 6.0, lateral: float = 0.5, keep: float = 0.5, types: Optional[List[int]] = None,
+                stop_at_end: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the target poses of the rule-based controlled rows ("IDM commands" of include/infgen_hip.h, ``infgen_idm_command``): the
+    scene arrays as for ``step_score``, ``ctl_row`` (S, A) bool / uint8 (the controlled rows), ``c >= 1`` the newest stored column,
+    ``records`` (S / copies, A, P - 1, 8) and ``total`` (S / copies, A) from ``route_records``, ``v_des`` (S / copies, A) the rows'
+    own desired speeds where > 0, ``v0`` the (vehicle, pedestrian, cyclist) desired speeds and ``types`` their switch (None: the
+    defaults of ``controllers.check_idm``).  Writes (x, y, heading) of every ruled row into the caller's ``cmd_pose`` (S, A, 3),
+    contiguous float32 - the other rows keep what they hold - and returns state (S * A, 8) = s0, e0, v, gap, acc, v1, s1, flag and
+    lead (S * A,) int32 = j, -1 (none) or -2 (the route's end)."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or tuple(head.shape) != tuple(pos.shape[:3]) or tuple(state.shape) != tuple(pos.shape[:3]):
+        raise ValueError('idm_command takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,) or tuple(ctl_row.shape) != (S, A):
+        raise ValueError('idm_command takes type (S, A), shape (S, A, 3), n_agents (S,), ctl_row (S, A)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    if not 1 <= int(c) < T:
+        raise ValueError(f'idm_command: column {c} outside 1 .. {T - 1}')
+    if records.dim() != 4 or records.shape[3] != 8 or tuple(records.shape[:2]) != (S // copies, A) or tuple(total.shape) != (S // copies, A):
+        raise ValueError('idm_command takes records (S / copies, A, P - 1, 8) and total (S / copies, A)')
+    if v_des is not None and tuple(v_des.shape) != (S // copies, A):
+        raise ValueError('v_des must be (S / copies, A)')
+    dev = pos.device
+    if tuple(cmd_pose.shape) != (S, A, 3) or cmd_pose.dtype != torch.float32 or not cmd_pose.is_contiguous() or cmd_pose.device != dev:
+        raise ValueError('cmd_pose is written in place: a contiguous float32 tensor (S, A, 3) on the scene\'s device')
+    conf = dict(dt=dt, headway=headway, s_min=s_min, a_max=a_max, b_comf=b_comf, b_max=b_max, lateral=lateral, keep=keep,
+                stop_at_end=bool(stop_at_end))
+    if v0 is not None:
+        conf['v0'] = list(v0)
+    if types is not None:
+        conf['types'] = [int(bool(v)) for v in types]
+    conf = controllers.check_idm(conf)
+    ops = _ops(dev)
+    i32 = lambda t: t.to(dev, torch.int32).contiguous()
+    out = controllers.idm_buffers(S, A, dev)
+    controllers.launch(ops.lib, ops.stream, _f32(pos), _f32(head), i32(state), i32(n_agents), i32(type), _f32(shape),
+                       ctl_row.to(dev, torch.uint8).contiguous(), c, _f32(records), _f32(total), copies,
+                       None if v_des is None else _f32(v_des), conf, cmd_pose, out)
+    return out['state'], out['lead']
+
+
+@idm_command.register_fake
+def _(pos, head, state, n_agents, type, shape, ctl_row, c, records, total, cmd_pose, copies=1, v_des=None, dt=0.5, v0=None, headway=1.5,
+      s_min=2.0, a_max=1.5, b_comf=2.0, b_max=6.0, lateral=0.5, keep=0.5, types=None, stop_at_end=True):
+    rows = pos.shape[0] * pos.shape[2]
+    return pos.new_empty(rows, 8, dtype=torch.float32), pos.new_empty(rows, dtype=torch.int32)
 
 
 @torch.library.custom_op('infgen_hip::map_token_head', mutates_args=())
