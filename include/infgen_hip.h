@@ -902,6 +902,77 @@ int infgen_insert_finalize(const InfgenRollout* r, int c, float angle_interval, 
                            const int* new_row, const float* lg_heading, int n_heading, const float* offset,
                            float* hv_ovr, void* stream);
 
+/* insertion rules: INSERTION RULES, the allowed cells of scenario insertion for one column (k_insert_cell_mask: one launch, one
+ * workgroup per scene, no host read, no atomics, no scratch) and the decision under them (k_insert_decide<true, true>).  Where the
+ * collision, road and route masks constrain the motion tokens of rows that exist, these constrain where, what and how many rows the
+ * insertion sub-loop appends.  fp32 throughout, no fused multiply-add.
+ *   cells   grid_xy [G][2], the tokenizer's grid in the EGO FRAME (+y forward), G <= 8192; its values are used as stored.  allowed
+ *       [S][W] little-endian 32-bit words, bit g of a scene's set = cell g allowed, W = ceil(G / 32) rounded up to a multiple of 4
+ *       (16-byte rows); bits at positions >= G are 0.
+ *   ego frame   column c, ego row av = av_index[s] (clamped to the layout): e = pos[c][av], phi = head[c][av] - pi / 2 (pi / 2 the
+ *       nearest float), cs = cosf(phi), sn = sinf(phi).  A world point p enters only through the exact difference d = p - e (per
+ *       component, formed directly from stored values), rotated: R(d) = (d.x * cs + d.y * sn, d.y * cs - d.x * sn) - the inverse of
+ *       the rotation infgen_insert_decide places a cell with.  A world direction (ux, uy) is rotated by the same R.  Every test below is
+ *       between a cell's grid value g = (gx, gy) and such ego-frame quantities, so magnitudes stay below ~100 m wherever the scene lies.
+ *   A cell is BANNED when any rule that is switched on (`rules`, the INFGEN_IM_* bits) bans it:
+ *   ego_keepout (back, front, half_width)   banned iff -back <= gy <= front and |gx| <= half_width: comparisons of stored grid
+ *       values, exact.
+ *   clearance   for every row j IN THE SCENE at column c (j < n_agents[s] and state[c][j] not invalid (0): the ego row and rows
+ *       appended by earlier iterations of the same step included): centre q = R(pos[c][j] - e), axis u = R(cosf(head[c][j]),
+ *       sinf(head[c][j])), half extents hl = max(shape[j][0] / 2, 0), hw = max(shape[j][1] / 2, 0) - the row's own length x width.
+ *       With f = g - q: lx = f.x * u.x + f.y * u.y, ly = f.y * u.x - f.x * u.y, dist = sqrtf(ox * ox + oy * oy) with
+ *       ox = max(|lx| - hl, 0), oy = max(|ly| - hw, 0); banned iff dist < clearance.  A row with f.x * f.x + f.y * f.y >= rr * rr,
+ *       rr = (hl + hw) + clearance, is skipped first (the circle test: it cannot change a verdict beyond rounding).
+ *   edge_clearance   the road-record table of the road masks (8 floats per record; map scene s / copies, its first n_records):
+ *       a record of radius < 0 is never an obstacle; otherwise midpoint m = R((anchor - e) + offset), direction u = R(cos, sin),
+ *       f = g - m, al = f.x * u.x + f.y * u.y, ac = f.y * u.x - f.x * u.y, dist = sqrtf(ox * ox + ac * ac) with
+ *       ox = max(|al| - half_length, 0); banned iff dist < edge_clearance.
+ *   near_lane (dist, types)   the cell is banned UNLESS some map token m < n_map[s / copies] (at most M_cap) whose map_type[m] is in
+ *       0..31 and has its bit set in lane_types lies within dist: q = R(map_pos[m] - e), f = g - q,
+ *       f.x * f.x + f.y * f.y <= dist * dist (both sides rounded to float).
+ *   zones [S0][Z][4] = (x, y, r, mode) in world coordinates, the first n_zones[s / copies] of map scene s / copies: a zone whose r is
+ *       not finite or <= 0, or whose mode is neither 0 nor 1, is VOID and ignored.  q = R((x, y) - e); the cell is INSIDE iff
+ *       f.x * f.x + f.y * f.y <= r * r.  mode 0: a cell inside is banned.  mode 1 (allow-only): if the scene has at least one
+ *       non-void zone of mode 1, a cell that is inside none of them is banned.
+ *   A distance within ~1e-4 m of its threshold may fall either way (cosf / sinf and the rounding of the rotations).
+ *   static / dynamic   keep-out, edges, lanes and zones depend only on the ego pose of column c: static_pass 1 evaluates them and
+ *       stores static_bits [S][W] (bit = no static rule bans the cell), static_pass 2 reads static_bits instead of evaluating them
+ *       (the later iterations of a step), static_pass 0 evaluates them without storing.  The clearance rule is evaluated by every
+ *       pass: allowed = static AND NOT near_agent.  The same launch writes allowed_count[s] = the population count of the scene's
+ *       allowed bits and live[s] = the number of rows in the scene at column c (whatever rules are on).
+ *   Left out on purpose: only the cell CENTRE is tested; the offset head moves the new row by up to 2 m per axis afterwards
+ *       (infgen_insert_finalize) and the new agent's own extents are not considered - callers fold both into `clearance`.  Rows not in
+ *       the scene at column c (exited, not yet entered) are no obstacles.  The reference's occupied-cell test stays as it is.
+ *   the decision under rules (infgen_insert_decide_mask)   as infgen_insert_decide_topk_ex, except: a banned cell is NO CANDIDATE of
+ *       the rank search, greedy or sampled - with sample_k > 1 the list holds min(sample_k, allowed_count) cells and the inverse CDF
+ *       re-normalises over those (the token masks' rule); a scene without an allowed cell takes the "no cell" exit (inserted = 0,
+ *       active = 0, nothing else touched; there is no fallback set: a scene may simply not insert).  The occupied-cell rule applies
+ *       to the chosen cell as before.  type_allowed (three host ints: vehicle, pedestrian, cyclist): the type arg-max runs over the
+ *       allowed types only, first index on ties.  max_agents (optional [S], with live [S] from infgen_insert_cell_mask): enter is
+ *       additionally false when live[s] >= max_agents[s]; the scene stops for the step like a lost enter logit.
+ * infgen_insert_cell_mask: the operator entry; the scene arrays are laid out like infgen_collision_mask's ([S][T][A_cap], A_cap at most
+ * INFGEN_Q_MAX_AGENTS), shape [S * A_cap][3]; keepout: three host floats (back, front, half_width).  Tables of rules that are off may be
+ * NULL.  count_log (optional): allowed_count[s] is also written to count_log[s * count_stride].
+ * Refused, each with a message and no launch: a distance that is negative or not finite; copies < 1 or not dividing S; G outside
+ * 1..8192; words != W; c outside 0 .. T - 1; A_cap beyond INFGEN_Q_MAX_AGENTS; static_pass outside 0..2; a missing table of a rule
+ * that is on (shape, records / n_records, map_pos / map_type / n_map, zones / n_zones, static_bits for pass 1 and 2); a missing
+ * output; a bit table, record table or zone table that is not 16-byte aligned.  infgen_insert_decide_mask refuses type_allowed all
+ * zero, max_agents without live, a missing or misaligned allowed table and words < ceil(grid_size / 32). */
+enum { INFGEN_IM_KEEPOUT = 1, INFGEN_IM_CLEARANCE = 2, INFGEN_IM_EDGES = 4, INFGEN_IM_LANES = 8, INFGEN_IM_ZONES = 16 };
+int infgen_insert_cell_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* av_index,
+                            const float* shape, int S, int A_cap, int T, int c, const float* grid_xy, int G, int rules,
+                            const float* keepout, float clearance, float edge_clearance, float lane_dist, unsigned lane_types,
+                            const float* records, const int* n_records, int rec_cap, const float* map_pos,
+                            const long long* map_type, const int* n_map, int M_cap, const float* zones, const int* n_zones, int Z,
+                            int copies, int static_pass, uint32_t* static_bits, uint32_t* allowed, int words, int* allowed_count,
+                            int* live, int* count_log, long long count_stride, void* stream);
+int infgen_insert_decide_mask(const InfgenRollout* r, int t, int force_enter, int max_new,
+                              const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
+                              const float* occ, int* active, int* n_new, int* inserted, int* new_row, float* new_shape,
+                              int* new_cell, int sample_k, const float* uniform, const InfgenSampling* sampling,
+                              const uint32_t* allowed, int words, const int* type_allowed, const int* max_agents, const int* live,
+                              void* stream);
+
 /* ---- the insertion sub-loop of one decode step, sequenced in the library (reference agent_decoder.py:1773-2105) ----
  * One iteration = infgen_insert_seed (occupancy + its embedding, edges into the seed node, the nine seed sublayers with the
  * previous iteration's new rows riding along edgelessly, the seed heads, the decision) -> the caller reads the per-scene
@@ -948,6 +1019,21 @@ typedef struct InfgenInsertion {
 /* it: iteration of the step (0: map edges of the seed are built and the agents' edgeless chains are computed); riders != 0: the
  * previous iteration appended rows (prev_row / prev_mask); uniform: [S] for the cell draw when insert_k > 1 */
 int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform, void* stream);
+/* infgen_insert_seed under insertion rules ("INSERTION RULES" above): the same launches, plus k_insert_cell_mask for the step's column
+ * in front of the decision - static_pass 1 when it == 0, 2 afterwards - and the masked decision, which also writes an appended row's
+ * shape to box_shape, so that the next iteration's clearance test sees its box.  The rule arguments are infgen_insert_cell_mask's
+ * (keepout: three host floats, may be NULL with the rule off; the map arrays are the context's map_pos / n_map, map scene
+ * s / copies, plus map_type), type_allowed / max_agents infgen_insert_decide_mask's.  box_shape [S * A_cap][3]: the caller fills the
+ * rows that exist.  count_log (optional) [S][log_steps]: the iteration-0 allowed count of step t at [s][t].  Nothing is kept
+ * between calls: zones / n_zones may be rewritten between two steps.  InfgenInsertion.max_new is the rules' per_step and must be
+ * in 1..10; a block with no_grid_token is refused (there is no cell to mask).  infgen_insert_seed itself is unchanged. */
+int infgen_insert_seed_rules(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform,
+                             int rules, const float* keepout, float clearance, float edge_clearance, float lane_dist,
+                             unsigned lane_types, const float* records, const int* n_records, int rec_cap,
+                             const long long* map_type, const float* zones, const int* n_zones, int Z, int copies,
+                             const int* type_allowed, const int* max_agents, float* box_shape, uint32_t* static_bits,
+                             uint32_t* allowed, int words, int* allowed_count, int* live, int* count_log, int log_steps,
+                             void* stream);
 /* h_ready == 0: the agents' edgeless chain through motion layers 0..2 is computed first; riders != 0: pend_row / pend_mask ride.
  * Must not be entered once a scene reported inserted[s] = -1 (host_dec): k_insert_cat and k_insert_finalize skip such a scene, but
  * the point edges, the raw feature rows and the rider masks of this stage take any non-zero inserted[s] as "a row was appended" and

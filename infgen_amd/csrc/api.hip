@@ -2979,7 +2979,8 @@ static int insert_decide_impl(const InfgenRollout* r, int t, int force_enter, in
                               const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
                               const float* occ, int* active, int* n_new, int* inserted, int* new_row,
                               float* new_shape, int* new_cell, int sample_k, const float* uniform, void* stream,
-                              bool grid = true, float r_seed = 0.f, const InfgenSampling* sampling = nullptr) {
+                              bool grid = true, float r_seed = 0.f, const InfgenSampling* sampling = nullptr,
+                              const InsertMaskCtl* mask = nullptr) {
   RET_IF(validate(r, "infgen_insert_decide"));
   if (sample_k > 16) return fail("infgen_insert_decide", "sample_k must be <= 16");
   if (sample_k > 1 && !uniform) return fail("infgen_insert_decide", "cell sampling needs uniforms");
@@ -2994,9 +2995,78 @@ static int insert_decide_impl(const InfgenRollout* r, int t, int force_enter, in
   a.active = active; a.n_new = n_new; a.inserted = inserted; a.new_row = new_row; a.new_shape = new_shape;
   a.new_cell = new_cell; a.pred_traj = r->pred_traj; a.pred_head = r->pred_head; a.pred_state = r->pred_state;
   a.r_seed = r_seed;
-  if (grid) hipLaunchKernelGGL(k_insert_decide<true>, dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_insert_decide<false>, dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
+  if (mask) {
+    if (!grid) return fail("infgen_insert_decide", "insertion rules: a model without the grid token has no cell to mask");
+    InsertDecideMaskArgs ma;
+    static_cast<InsertDecideArgs&>(ma) = a;
+    ma.m = *mask;
+    hipLaunchKernelGGL((k_insert_decide<true, true>), dim3(r->S), dim3(64), 0, (hipStream_t)stream, ma);
+  } else if (grid) hipLaunchKernelGGL((k_insert_decide<true, false>), dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((k_insert_decide<false, false>), dim3(r->S), dim3(64), 0, (hipStream_t)stream, a);
   return check_launch("infgen_insert_decide");
+}
+
+// ---------------------------------------------------------------------------------- insertion rules
+// the argument checks of include/infgen_hip.h ("insertion rules") and the one launch of k_insert_cell_mask
+static int insert_cell_mask_launch(const char* me, const InsertCellMaskArgs& a, void* stream) {
+  const float dist[6] = {a.ko_back, a.ko_front, a.ko_half, a.clearance, a.edge_clearance, a.lane_dist};
+  for (float x : dist)
+    if (!std::isfinite(x) || x < 0.f) return fail(me, "insertion rules: every distance must be finite and >= 0");
+  if (a.S < 1 || a.T < 1 || a.A_cap < 1) return fail(me, "insertion rules: empty layout");
+  if (a.copies < 1 || a.S % a.copies != 0) return fail(me, "insertion rules: copies must be at least 1 and divide S");
+  if (a.G < 1 || a.G > IM_MAX_CELLS) return fail(me, "insertion rules: G must be in 1..8192");
+  if (a.W != (a.G + 127) / 128 * 4) return fail(me, "insertion rules: words must be ceil(G / 32) rounded up to a multiple of 4");
+  if (a.c < 0 || a.c >= a.T) return fail(me, "insertion rules: column out of range");
+  if (a.A_cap > MAX_SCENE_AGENTS) return fail(me, "insertion rules: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.static_pass < 0 || a.static_pass > 2) return fail(me, "insertion rules: static_pass must be 0, 1 or 2");
+  if (a.rules & ~(IM_KEEPOUT | IM_CLEARANCE | IM_EDGES | IM_LANES | IM_ZONES)) return fail(me, "insertion rules: unknown rule bit");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.av_index || !a.grid_xy) return fail(me, "insertion rules: needs the scene arrays and the grid");
+  if (!a.allowed || !a.allowed_count || !a.live) return fail(me, "insertion rules: needs allowed, allowed_count and live");
+  if (a.static_pass != 0 && !a.static_bits) return fail(me, "insertion rules: static_pass 1 and 2 need static_bits");
+  if ((a.rules & IM_CLEARANCE) && !a.shape) return fail(me, "insertion rules: clearance needs the rows' shape array [S][A_cap][3]");
+  if ((a.rules & IM_EDGES) && (!a.records || !a.n_records || a.rec_cap < 0))
+    return fail(me, "insertion rules: edge_clearance needs the road-record table and its counts");
+  if ((a.rules & IM_LANES) && (!a.map_pos || !a.map_type || !a.n_map || a.M_cap < 0))
+    return fail(me, "insertion rules: near_lane needs map_pos, map_type and n_map");
+  if ((a.rules & IM_ZONES) && (!a.zones || !a.n_zones || a.Z < 0)) return fail(me, "insertion rules: zones need the zone table and its counts");
+  if (misaligned16(a.allowed, a.static_bits, a.records, a.zones)) return fail(me, "insertion rules: the bit, record and zone tables must be 16-byte aligned");
+  hipLaunchKernelGGL(k_insert_cell_mask, dim3(a.S), dim3(IM_NT), 0, (hipStream_t)stream, a);
+  return check_launch(me);
+}
+
+extern "C" int infgen_insert_cell_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* av_index,
+                                       const float* shape, int S, int A_cap, int T, int c, const float* grid_xy, int G, int rules,
+                                       const float* keepout, float clearance, float edge_clearance, float lane_dist,
+                                       unsigned lane_types, const float* records, const int* n_records, int rec_cap,
+                                       const float* map_pos, const long long* map_type, const int* n_map, int M_cap,
+                                       const float* zones, const int* n_zones, int Z, int copies, int static_pass,
+                                       uint32_t* static_bits, uint32_t* allowed, int words, int* allowed_count, int* live,
+                                       int* count_log, long long count_stride, void* stream) {
+  const char* me = "infgen_insert_cell_mask";
+  if ((rules & IM_KEEPOUT) && !keepout) return fail(me, "insertion rules: ego_keepout needs its three floats");
+  InsertCellMaskArgs a{};
+  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c; a.G = G; a.W = words;
+  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.av_index = av_index; a.shape = shape; a.grid_xy = grid_xy;
+  a.rules = rules; a.static_pass = static_pass;
+  if (rules & IM_KEEPOUT) { a.ko_back = keepout[0]; a.ko_front = keepout[1]; a.ko_half = keepout[2]; }
+  a.clearance = clearance; a.edge_clearance = edge_clearance; a.lane_dist = lane_dist; a.lane_types = lane_types;
+  a.records = records; a.n_records = n_records; a.rec_cap = rec_cap;
+  a.map_pos = map_pos; a.map_type = map_type; a.n_map = n_map; a.M_cap = M_cap;
+  a.zones = zones; a.n_zones = n_zones; a.Z = Z; a.copies = copies;
+  a.static_bits = static_bits; a.allowed = allowed; a.allowed_count = allowed_count; a.live = live;
+  a.count_log = count_log; a.count_stride = count_stride;
+  return insert_cell_mask_launch(me, a, stream);
+}
+
+static int insert_mask_ctl(const char* me, int grid_size, const uint32_t* allowed, int words, const int* type_allowed,
+                           const int* max_agents, const int* live, float* box_shape, InsertMaskCtl* m) {
+  if (!allowed || misaligned16(allowed)) return fail(me, "insertion rules: needs a 16-byte aligned allowed table");
+  if (words < (grid_size + 31) / 32) return fail(me, "insertion rules: words is below ceil(grid_size / 32)");
+  if (!type_allowed || !(type_allowed[0] || type_allowed[1] || type_allowed[2]))
+    return fail(me, "insertion rules: types must allow at least one agent type");
+  if (max_agents && !live) return fail(me, "insertion rules: max_agents needs the live counts of infgen_insert_cell_mask");
+  *m = InsertMaskCtl{allowed, words, {type_allowed[0], type_allowed[1], type_allowed[2]}, max_agents, live, box_shape};
+  return 0;
 }
 
 extern "C" int infgen_insert_decide(const InfgenRollout* r, int t, int force_enter, int max_new,
@@ -3026,6 +3096,21 @@ extern "C" int infgen_insert_decide_topk_ex(const InfgenRollout* r, int t, int f
                                             const InfgenSampling* sampling, void* stream) {
   return insert_decide_impl(r, t, force_enter, max_new, lg_state, lg_type, shape, lg_pos, occ, active, n_new, inserted, new_row,
                             new_shape, new_cell, sample_k, uniform, stream, true, 0.f, sampling);
+}
+
+// ... under insertion rules: banned cells are no candidates, banned types are not chosen, a scene at its budget does not enter
+extern "C" int infgen_insert_decide_mask(const InfgenRollout* r, int t, int force_enter, int max_new,
+                                         const float* lg_state, const float* lg_type, const float* shape, const float* lg_pos,
+                                         const float* occ, int* active, int* n_new, int* inserted, int* new_row,
+                                         float* new_shape, int* new_cell, int sample_k, const float* uniform,
+                                         const InfgenSampling* sampling, const uint32_t* allowed, int words, const int* type_allowed,
+                                         const int* max_agents, const int* live, void* stream) {
+  RET_IF(validate(r, "infgen_insert_decide_mask"));
+  if (r->no_grid_token) return fail("infgen_insert_decide_mask", "insertion rules: a model without the grid token has no cell to mask");
+  InsertMaskCtl m;
+  RET_IF(insert_mask_ctl("infgen_insert_decide_mask", r->grid_size, allowed, words, type_allowed, max_agents, live, nullptr, &m));
+  return insert_decide_impl(r, t, force_enter, max_new, lg_state, lg_type, shape, lg_pos, occ, active, n_new, inserted, new_row,
+                            new_shape, new_cell, sample_k, uniform, stream, true, 0.f, sampling, &m);
 }
 
 static int insert_finalize_impl(const InfgenRollout* r, int c, float angle_interval, const int* inserted, const int* new_row,
@@ -3096,12 +3181,28 @@ int edgeless(float* X, int rows, const float* pack, const InfgenInsertion* I, vo
 }
 }  // namespace
 
-extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform,
-                                  void* stream) {
+// the rule arguments of infgen_insert_seed_rules, checked by the two launches they reach
+struct InsertSeedRules {
+  InsertCellMaskArgs mask;      // the rule parameters and outputs; the scene, the column and the pass are filled in per call
+  const int* type_allowed; const int* max_agents; float* box_shape; int log_steps;
+};
+
+static int insert_seed_impl(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform,
+                            void* stream, const InsertSeedRules* rules) {
   RET_IF(validate(r, "infgen_insert_seed"));
   if (!I) return fail("infgen_insert_seed", "null insertion block");
   if (I->no_grid_token != r->no_grid_token) return fail("infgen_insert_seed", "no_grid_token differs between the context and the block");
   if (I->no_grid_token && !I->head_pos_xy) return fail("infgen_insert_seed", "no_grid_token needs head_pos_xy");
+  InsertMaskCtl rules_ctl;
+  if (rules) {
+    if (I->no_grid_token) return fail("infgen_insert_seed_rules", "insertion rules: a model without the grid token has no cell to mask");
+    if (I->max_new < 1 || I->max_new > 10) return fail("infgen_insert_seed_rules", "insertion rules: per_step must be in 1..10");
+    if (!rules->box_shape) return fail("infgen_insert_seed_rules", "insertion rules: needs the rows' shape array [S][A_cap][3]");
+    if (rules->mask.count_log && (rules->log_steps < 1 || t >= rules->log_steps))
+      return fail("infgen_insert_seed_rules", "insertion rules: the count log is too short");
+    RET_IF(insert_mask_ctl("infgen_insert_seed_rules", r->grid_size, rules->mask.allowed, rules->mask.W, rules->type_allowed,
+                           rules->max_agents, rules->mask.live, rules->box_shape, &rules_ctl));
+  }
   OptScope _opts(r);
   hipStream_t hs = (hipStream_t)stream;
   const int S = r->S, rows = r->S * r->A_cap, c = 1 + t, G = r->grid_size;
@@ -3166,7 +3267,20 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
   else mlp_layer_descs(I->XS, S, I->head_pos_xy, 2, I->hid + 3 * hs_, I->lg_pos, d1[3], d2[3]);
   RET_IF(infgen_linear_multi(d1, 4, stream));
   RET_IF(infgen_linear_multi(d2, 4, stream));
-  if (grid) {
+  if (grid && rules) {
+    // the allowed cells of this iteration (the static rules once per step), then the decision under them
+    InsertCellMaskArgs ma = rules->mask;
+    ma.S = S; ma.A_cap = r->A_cap; ma.T = r->T; ma.c = c; ma.G = G;
+    ma.pos = r->pos; ma.head = r->head; ma.state = r->state; ma.n_agents = r->n_agents; ma.av_index = r->av_index;
+    ma.shape = rules->box_shape; ma.grid_xy = r->grid_xy; ma.static_pass = it == 0 ? 1 : 2;
+    ma.map_pos = r->map_pos; ma.n_map = r->n_map; ma.M_cap = r->M_cap;
+    if (it == 0 && ma.count_log) { ma.count_log += t; ma.count_stride = rules->log_steps; }
+    else ma.count_log = nullptr;
+    RET_IF(insert_cell_mask_launch("infgen_insert_seed_rules", ma, stream));
+    const InfgenSampling sp{I->insert_temperature, I->insert_top_p, nullptr};
+    RET_IF(insert_decide_impl(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, I->occ, I->active, I->n_new,
+                              I->inserted, I->new_row, I->new_shape, I->new_cell, I->insert_k, uniform, stream, true, 0.f, &sp, &rules_ctl));
+  } else if (grid) {
     const InfgenSampling sp{I->insert_temperature, I->insert_top_p, nullptr};
     RET_IF(infgen_insert_decide_topk_ex(r, t, I->force_enter, I->max_new, I->lg_state, I->lg_type, I->shape, I->lg_pos, I->occ, I->active,
                                         I->n_new, I->inserted, I->new_row, I->new_shape, I->new_cell, I->insert_k, uniform, &sp, stream));
@@ -3183,6 +3297,31 @@ extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion*
              hipMemcpyAsync(I->host_dec + 2 * S, I->active, S * sizeof(int), hipMemcpyDeviceToHost, hs) != hipSuccess)
     return fail("infgen_insert_seed", "hand-over copy failed");
   return 0;
+}
+
+extern "C" int infgen_insert_seed(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform,
+                                  void* stream) {
+  return insert_seed_impl(r, I, t, it, riders, uniform, stream, nullptr);
+}
+
+extern "C" int infgen_insert_seed_rules(const InfgenRollout* r, const InfgenInsertion* I, int t, int it, int riders, const float* uniform,
+                                        int rules, const float* keepout, float clearance, float edge_clearance, float lane_dist,
+                                        unsigned lane_types, const float* records, const int* n_records, int rec_cap,
+                                        const long long* map_type, const float* zones, const int* n_zones, int Z, int copies,
+                                        const int* type_allowed, const int* max_agents, float* box_shape, uint32_t* static_bits,
+                                        uint32_t* allowed, int words, int* allowed_count, int* live, int* count_log, int log_steps,
+                                        void* stream) {
+  if ((rules & IM_KEEPOUT) && !keepout) return fail("infgen_insert_seed_rules", "insertion rules: ego_keepout needs its three floats");
+  InsertSeedRules k{};
+  InsertCellMaskArgs& a = k.mask;
+  a.W = words; a.rules = rules;
+  if (rules & IM_KEEPOUT) { a.ko_back = keepout[0]; a.ko_front = keepout[1]; a.ko_half = keepout[2]; }
+  a.clearance = clearance; a.edge_clearance = edge_clearance; a.lane_dist = lane_dist; a.lane_types = lane_types;
+  a.records = records; a.n_records = n_records; a.rec_cap = rec_cap; a.map_type = map_type;
+  a.zones = zones; a.n_zones = n_zones; a.Z = Z; a.copies = copies;
+  a.static_bits = static_bits; a.allowed = allowed; a.allowed_count = allowed_count; a.live = live; a.count_log = count_log;
+  k.type_allowed = type_allowed; k.max_agents = max_agents; k.box_shape = box_shape; k.log_steps = log_steps;
+  return insert_seed_impl(r, I, t, it, riders, uniform, stream, &k);
 }
 
 extern "C" int infgen_insert_heading(const InfgenRollout* r, const InfgenInsertion* I, int t, int h_ready, int riders, void* stream) {

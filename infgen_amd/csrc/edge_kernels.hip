@@ -975,8 +975,11 @@ __global__ __launch_bounds__(NT) void k_occupancy_embed(OccEmbedArgs a) {
 // rejection; append the new row (:1883-1999).  One wave per scene.
 // kGrid = false (use_grid_token = False, :1910-1912): no cell and no occupancy test; the new row sits at
 // tanh(lg_pos[s][0..1]) * r_seed + ego pos in the world frame (not rotated by the ego heading) with grid cell -1.
-template <bool kGrid>
-__global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
+// kMask (insertion rules, include/infgen_hip.h): a banned cell is no candidate of the rank search - the list then holds
+// min(k, allowed) cells and the draw is topk_inverse_cdf_masked's -, the type arg-max runs over the allowed types, and a scene at
+// its agent budget does not enter.  kMask = false is the code as it was.
+template <bool kGrid, bool kMask>
+__global__ __launch_bounds__(64) void k_insert_decide(std::conditional_t<kMask, InsertDecideMaskArgs, InsertDecideArgs> a) {
   const SceneState& st = a.st;
   const int s = blockIdx.x, lane = threadIdx.x;
   const int c = a.c;
@@ -987,6 +990,8 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   // softmax -> topk(insert_beam_size) -> multinomial (:1900-1904) in its reproducible form: the k largest in (value desc,
   // index asc) order, inverse CDF over their probabilities with the caller's uniform (like k_sample_topk)
   const float* lp = a.lg_pos + (size_t)s * a.grid_size;
+  const unsigned* al = nullptr;
+  if constexpr (kMask) al = a.m.allowed + (size_t)s * a.m.words;
   float best = -INFINITY;
   {
     const int k = a.sample_k > 1 ? min(a.sample_k, 16) : 1;
@@ -998,7 +1003,8 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
       best = -INFINITY; bi = 0x7fffffff;
       for (int g = lane; g < a.grid_size; g += 64) {
         const float v = lp[g];
-        const bool after = (v < prev_v) || (v == prev_v && g > prev_i);
+        bool after = (v < prev_v) || (v == prev_v && g > prev_i);
+        if constexpr (kMask) after = after && ((al[g >> 5] >> (g & 31)) & 1u);
         if (after && (v > best || (v == best && g < bi))) { best = v; bi = g; }
       }
 #pragma unroll
@@ -1014,7 +1020,8 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
       float sum, it, top_p;
       int m;
       sampling_row(a.ctl, s, &it, &top_p);
-      bi = topi[topk_inverse_cdf<16>(topv, k, a.uniform[s], it, top_p, &sum, &m)];
+      if constexpr (kMask) bi = topi[topk_inverse_cdf_masked<16>(topv, topi, k, a.uniform[s], it, top_p, &sum, &m)];
+      else bi = topi[topk_inverse_cdf<16>(topv, k, a.uniform[s], it, top_p, &sum, &m)];
     } else {
       bi = topi[0];
     }
@@ -1028,10 +1035,20 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   const float* ls = a.lg_state + 2 * s;
   bool enter = ls[1] > ls[0];
   if (a.force_enter) enter = true;
+  if constexpr (kMask) {
+    if (a.m.max_agents && a.m.live[s] >= a.m.max_agents[s]) enter = false;      // the scene's budget: it stops like a lost enter logit
+  }
   const float* lt = a.lg_type + 3 * s;
   int ty = 0;
-  if (lt[1] > lt[ty]) ty = 1;
-  if (lt[2] > lt[ty]) ty = 2;
+  if constexpr (kMask) {
+    ty = -1;                                                                     // (the host refuses a set without a type)
+    for (int k = 0; k < 3; ++k)
+      if (a.m.type_allowed[k] && (ty < 0 || lt[k] > lt[ty])) ty = k;
+    if (ty < 0) ty = 0;
+  } else {
+    if (lt[1] > lt[ty]) ty = 1;
+    if (lt[2] > lt[ty]) ty = 2;
+  }
   const bool occupied = kGrid && a.occ[(size_t)s * a.grid_size + cell] != 0.f;
   const int A = a.n_agents[s];
   // :1906-1909: an occupied cell `continue`s - the iteration is spent, nothing is appended and, when cells are sampled, the
@@ -1070,6 +1087,12 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   st.bos[row] = c;
   a.new_shape[3 * s] = a.shape[3 * s]; a.new_shape[3 * s + 1] = a.shape[3 * s + 1]; a.new_shape[3 * s + 2] = a.shape[3 * s + 2];
   a.new_cell[s] = cell;
+  if constexpr (kMask) {
+    if (a.m.box_shape) {
+      float* bs = a.m.box_shape + 3 * (size_t)row;
+      bs[0] = a.shape[3 * s]; bs[1] = a.shape[3 * s + 1]; bs[2] = a.shape[3 * s + 2];
+    }
+  }
   if (a.t > 0) {
     for (int k = 0; k < 5; ++k) {
       const size_t o = (size_t)row * a.R + (a.t - 1) * 5 + k;
@@ -1082,8 +1105,9 @@ __global__ __launch_bounds__(64) void k_insert_decide(InsertDecideArgs a) {
   a.new_row[s] = row;
   a.inserted[s] = 1;
 }
-template __global__ void k_insert_decide<true>(InsertDecideArgs);
-template __global__ void k_insert_decide<false>(InsertDecideArgs);
+template __global__ void k_insert_decide<true, false>(InsertDecideArgs);
+template __global__ void k_insert_decide<false, false>(InsertDecideArgs);
+template __global__ void k_insert_decide<true, true>(InsertDecideMaskArgs);
 
 // k_insert_finalize: heading token + xy offset of the new row (:2060-2074), head-vector override.
 // kHeadToken = false (use_head_token = False): heading tanh(lg_heading[s][0]) * pi + ego heading, not wrapped;

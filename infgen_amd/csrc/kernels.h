@@ -843,8 +843,44 @@ __global__ void k_map_graph(MapGraphArgs a);
 __global__ void k_point_edges(PointEdgesArgs a);
 __global__ void k_occupancy(OccupancyArgs a);
 __global__ void k_occupancy_embed(OccEmbedArgs a);
-// kGrid = false: use_grid_token = False (regressed world-frame position, no cell, no occupancy test)
-template <bool kGrid> __global__ void k_insert_decide(InsertDecideArgs a);
+// insertion rules of the decision (include/infgen_hip.h, "insertion rules"): the masked instantiation k_insert_decide<true, true> takes
+// the decision's argument block with these appended; the unmasked ones keep the block - and so their code - exactly as they were
+struct InsertMaskCtl {
+  const unsigned* allowed; int words;   // [S][words]: bit g set = cell g allowed (k_insert_cell_mask)
+  int type_allowed[3];                  // vehicle, pedestrian, cyclist: 0 = never inserted
+  const int* max_agents;                // optional [S]: no row is appended while live[s] >= max_agents[s]
+  const int* live;                      // [S] (with max_agents): the rows in the scene at the step's column
+  float* box_shape;                     // optional [S * A_cap][3]: the appended row's shape is written here too (the clearance rule's boxes)
+};
+struct InsertDecideMaskArgs : InsertDecideArgs { InsertMaskCtl m; };
+// kGrid = false: use_grid_token = False (regressed world-frame position, no cell, no occupancy test); kMask: under insertion rules
+template <bool kGrid, bool kMask = false>
+__global__ void k_insert_decide(std::conditional_t<kMask, InsertDecideMaskArgs, InsertDecideArgs> a);
+
+// k_insert_cell_mask (insert_mask_kernels.hip): the allowed cells of scenario insertion, one workgroup per scene
+constexpr int IM_NT = 256;              // threads: wave w takes the 64-cell chunks w, w + 4, ..
+constexpr int IM_TILE = 1024;           // entries (boxes, records, map tokens, zones) staged in LDS at a time; = MAX_SCENE_AGENTS
+constexpr int IM_F = 6;                 // floats per staged entry
+constexpr int IM_MAX_CELLS = 8192;      // a thread keeps one verdict bit per 256-cell round in a 32-bit register
+enum { IM_KEEPOUT = 1, IM_CLEARANCE = 2, IM_EDGES = 4, IM_LANES = 8, IM_ZONES = 16 };
+struct InsertCellMaskArgs {
+  int S, A_cap, T, c, G, W;             // column c of the [S][T][A_cap] scene arrays; G cells, W words per scene
+  const float* pos; const float* head; const int* state; const int* n_agents; const int* av_index;
+  const float* shape;                   // [S * A_cap][3] = (length, width, height)
+  const float* grid_xy;                 // [G][2], ego frame
+  int rules;                            // IM_* bits
+  int static_pass;                      // 0: static rules computed, not stored; 1: computed and stored; 2: read from static_bits
+  float ko_back, ko_front, ko_half, clearance, edge_clearance, lane_dist;
+  unsigned lane_types;                  // bit ty: map tokens of type ty count as lanes
+  const float* records; const int* n_records; int rec_cap;
+  const float* map_pos; const long long* map_type; const int* n_map; int M_cap;
+  const float* zones; const int* n_zones; int Z;
+  int copies;
+  unsigned* static_bits; unsigned* allowed;     // [S][W]
+  int* allowed_count; int* live;                // [S]
+  int* count_log; long long count_stride;       // optional: count_log[s * count_stride] = allowed_count[s] as well
+};
+__global__ void k_insert_cell_mask(InsertCellMaskArgs a);
 // kHeadToken = false: use_head_token = False (tanh * pi heading, unwrapped); kOffset = false: no xy offset (use_grid_token = False)
 template <bool kHeadToken, bool kOffset> __global__ void k_insert_finalize(InsertFinalizeArgs a);
 template <bool MK> __global__ void k_sample_topk(ArgsFor<SampleArgs, MK> a);

@@ -14,13 +14,14 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
+from dataclasses import replace as dataclasses_replace
 import os
 from typing import Dict, List, Mapping, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib, constraints, controllers, logprob, modes, observe, packing, scene_setup
+from . import _lib, constraints, controllers, insertion_rules, logprob, modes, observe, packing, scene_setup
 from .scene_setup import EVAL_SHAPE, INVALID_SHAPE
 from .synth import INVALID, VALID, ENTER, EXIT, AGENT_SHAPE, RolloutConfig
 
@@ -556,8 +557,14 @@ class RolloutEngine:
                  token_logprob: bool = False, sample_logprob: bool = False,
                  sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
                  token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False, stay_on_road=False,
-                 step_scores=False, follow_routes=False):
-        """``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
+                 step_scores=False, follow_routes=False, insert_rules=None):
+        """``insert_rules``: insertion rules ("INSERTION RULES" of include/infgen_hip.h) - None or dict(clearance=,
+        ego_keepout=(back, front, half_width), edge_clearance=, near_lane=dict(dist=, types=), zones=, types=, max_agents=,
+        per_step=): a cell mask computed on the device in front of every insertion decision (``infgen_amd.insertion_rules``).
+        ``insert_allowed`` [S, W] holds the bits of the last iteration, ``insert_allowed_count`` [S, steps] the iteration-0 count of
+        every step; ``set_insert_zones`` rewrites the zone table.  Engines without scenario insertion or without the grid token
+        refuse it.
+        ``batch``: a ragged PyG-style Batch of device tensors instead of host ``scenes`` (pass ``scenes=None``): the engine
         is sized from its offsets (``read_batch_layout``; A_cap from the unfiltered per-graph maxima, which the filtered counts
         never exceed) and set up on the device by the ingest kernel (``reload_batch``).
         ``replay``: log replay - the flagged rows follow a plan (their logged future, or a planner's), every other row is
@@ -706,6 +713,14 @@ class RolloutEngine:
         self.force_valid = bool(cfg.disable_insertion) and not live_state
         self.insertion = not cfg.disable_insertion
         self.force_enter = force_enter
+        # insertion rules: checked here, the device tables are allocated with the insertion buffers
+        self.insert_rules = insertion_rules.InsertRules.from_config(insert_rules, n_scenes=self.S0, n_slots=self.S)
+        self._ins_rules, self._ins_map_dirty = None, True
+        if self.insert_rules is not None and not self.insertion:
+            raise ValueError('insert_rules: engines with disable_insertion insert nothing: there is no decision to rule')
+        if self.insert_rules is not None and not cfg.use_grid_token:
+            raise ValueError('insert_rules: a model with use_grid_token = False draws no cell (the position is regressed): there is '
+                             'no cell to mask')
 
         # ------------------------------------------------ host-side scene setup
         self._hosts_light = False
@@ -1307,6 +1322,7 @@ class RolloutEngine:
         self._mg_checked = False           # the new map may hold more pt <-> pt edges than the buffers
         self._prologue_done = False
         self._road_dirty = True            # the road records belong to the old map
+        self._ins_map_dirty = True         # ... and so do the insertion rules'
         self._reload_gen += 1              # snapshots of the old batch are refused (``restore``)
 
     # ------------------------------------------------------------------ log replay
@@ -1816,6 +1832,7 @@ class RolloutEngine:
             if self.seed_out is not None:
                 for v in self.seed_out.values():
                     v.zero_()
+            self._reset_insert_rules()
             return
         dev, S, rows, A_cap, M_cap, G = self.device, self.S, self.rows, self.A_cap, self.M_cap, self.G
         f = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)
@@ -1847,6 +1864,7 @@ class RolloutEngine:
         # inserted | new_row | active back to back: one device-to-host copy per iteration hands all three over
         d3 = self.ins['dec3']
         self.ins['inserted'], self.ins['new_row'], self.ins['active'] = d3[:S], d3[S:2 * S], d3[2 * S:]
+        self._reset_insert_rules()
         if self.seed_outputs and not self.cfg.use_grid_token:
             # use_grid_token = False: next_pos_rel_prob_seed and grid_*_occ_seed are None in the reference (agent_decoder.py:2376-2386)
             self.seed_out = dict(state=f(S, 11, self.cfg.num_decode_steps))
@@ -1858,6 +1876,72 @@ class RolloutEngine:
             if not hasattr(self.w, 'fwd_heads'):
                 self.w.fwd_heads = {k: torch.from_numpy(np.ascontiguousarray(packing.pack_mlp_layer(sd, f'{ap}.{k}'), dtype=np.float32)).to(dv)
                                     for k in ('grid_index_head', 'grid_agent_occ_head', 'grid_pt_occ_head')}
+
+    def _reset_insert_rules(self):
+        """the device tables of the insertion rules, allocated once and brought back to the start of a rollout: the boxes of the
+        rows that exist (the masked decision adds the appended rows'), an empty count log, and - with ``edge_clearance`` - the
+        road-record table of the map in the buffers (two chords per EDGE token, the road masks' default; its size takes one count)"""
+        rules = self.insert_rules
+        if rules is None:
+            return
+        P = _lib.ptr
+        if self._ins_rules is None:
+            self._ins_rules = insertion_rules.device_tables(rules, self.S, self.S0, self.A_cap, self.G, self.cfg.num_decode_steps,
+                                                            self.device)
+            self.ins['struct'] = None
+        k = self._ins_rules
+        k['shape'].copy_(self._shape10.reshape(self.rows, 3))
+        k['count_log'].zero_()
+        if rules.edge_clearance is not None and self._ins_map_dirty:
+            self._ins_map_dirty = False
+            mtok, mtype = self._map_cat[0], self._map_cat[1]
+            inmap = torch.arange(self.M_cap, device=self.device)[None] < self.n_map[:, None]
+            cap = _round_up(max(2 * int(((mtype == 12) & inmap).sum(dim=1).max().item()), 1), 64)
+            if k.get('records') is None or k['records'].shape[1] < cap:
+                k['records'], k['n_records'] = torch.zeros(self.S0, cap, 8, device=self.device), torch.zeros(self.S0, device=self.device, dtype=torch.int32)
+                self.ins['struct'] = None
+            _lib.check(self.lib.infgen_road_records_from_map(P(self.map_pos), P(self.map_orient), P(mtype), P(mtok), P(self.n_map),
+                                                             self.S0, self.M_cap, P(self._map_vocab), int(self._map_vocab.shape[0]), 2,
+                                                             P(k['records']), int(k['records'].shape[1]), P(k['n_records']),
+                                                             self.ops.stream), 'infgen_road_records_from_map')
+
+    def _insert_rule_args(self):
+        """the rule arguments of infgen_insert_seed_rules (None without insert_rules); the ctypes arrays are kept alive with them"""
+        rules, k = self.insert_rules, self._ins_rules
+        if rules is None:
+            return None
+        P = _lib.ptr
+        ko = (C.c_float * 3)(*rules.ego_keepout) if rules.ego_keepout is not None else None
+        edges, lanes, zones = rules.edge_clearance is not None, rules.near_lane is not None, rules.zones is not None
+        return (rules.rule_bits, ko, rules.clearance or 0.0, rules.edge_clearance or 0.0, rules.near_lane[0] if lanes else 0.0,
+                rules.lane_type_mask, P(k['records']) if edges else None, P(k['n_records']) if edges else None,
+                int(k['records'].shape[1]) if edges else 0, P(self._map_cat[1]) if lanes else None,
+                P(k['zones']) if zones else None, P(k['n_zones']) if zones else None, int(k['zones'].shape[1]) if zones else 0,
+                self.copies, (C.c_int * 3)(*rules.types), P(k['max_agents']), P(k['shape']), P(k['static']), P(k['allowed']), k['W'],
+                P(k['count']), P(k['live']), P(k['count_log']), int(k['count_log'].shape[1]))
+
+    @property
+    def insert_allowed(self):
+        """[S, W] int32 words: the allowed cells of the last insertion iteration (``insertion_rules.cells_allowed_to_indices``)"""
+        return None if self._ins_rules is None else self._ins_rules['allowed']
+
+    @property
+    def insert_allowed_count(self):
+        """[S, steps] int32: the allowed cells at iteration 0 of every decode step (0 where no insertion ran: step 0)"""
+        return None if self._ins_rules is None else self._ins_rules['count_log']
+
+    def set_insert_zones(self, zones, n_zones=None):
+        """rewrites the zone table of the insertion rules between rollouts or steps (the library keeps the pointers, not the
+        contents): the same capacity Z, other circles or counts"""
+        if self.insert_rules is None or self.insert_rules.zones is None:
+            raise ValueError('set_insert_zones: the engine has no insert_rules with zones')
+        z, n = insertion_rules.check_zones(zones, n_zones, n_scenes=self.S0)
+        if z.shape != self.insert_rules.zones[0].shape:
+            raise ValueError(f'set_insert_zones: the zone table is {self.insert_rules.zones[0].shape}, got {z.shape}')
+        self.insert_rules = dataclasses_replace(self.insert_rules, zones=(z, n))
+        if self._ins_rules is not None:
+            self._ins_rules['zones'].copy_(torch.from_numpy(z))
+            self._ins_rules['n_zones'].copy_(torch.from_numpy(n))
 
     def _ebuf_struct(self, e):
         b = _lib.EdgeBuf()
@@ -1895,6 +1979,8 @@ class RolloutEngine:
         b.r_seed, b.r_a2sa, b.r_pl2sa, b.angle_interval = float(cfg.pl2seed_radius), float(cfg.a2sa_radius), float(cfg.pl2sa_radius), float(cfg.angle_interval)
         b.n_heading, b.force_enter, b.insert_k, b.max_new = int(360.0 / cfg.angle_interval), int(self.force_enter), self.insert_k, 10
         b.insert_temperature, b.insert_top_p = self.insert_temperature, self.insert_top_p
+        if self.insert_rules is not None:
+            b.max_new = self.insert_rules.per_step
         return b
 
     def _insert_step(self, t: int):
@@ -1912,11 +1998,15 @@ class RolloutEngine:
         I['active'].fill_(1)
         I['n_new'].zero_()
         riders = riders_h = h_ready = False
+        rule_args = self._insert_rule_args()
         hd = I['host_dec'].numpy()
         for it in range(10):
             st = self.ops.stream
             u = _lib.ptr(self._insert_u[t, it]) if self._insert_u is not None else None
-            _lib.check(lib.infgen_insert_seed(ctx, blk, t, it, int(riders), u, st), 'infgen_insert_seed')
+            if rule_args is None:
+                _lib.check(lib.infgen_insert_seed(ctx, blk, t, it, int(riders), u, st), 'infgen_insert_seed')
+            else:
+                _lib.check(lib.infgen_insert_seed_rules(ctx, blk, t, it, int(riders), u, *rule_args, st), 'infgen_insert_seed_rules')
             ev = I['host_ev']
             ev.record(torch.cuda.current_stream(self.device))
             yield ev

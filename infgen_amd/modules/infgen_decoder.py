@@ -411,6 +411,9 @@ class InfGenDecoder(nn.Module):
         # inference_rollouts / inference_batch(copies=n) are pruned or resampled on those scores while they run
         self.step_scores = False
         self.guided_rollouts = None
+        # insertion rules (RolloutEngine's insert_rules): None or dict(clearance=, ego_keepout=, edge_clearance=,
+        # near_lane=, zones=, types=, max_agents=, per_step=); fixed per engine and part of its cache key (the zone table by content)
+        self.insert_rules = None
         self._packed = None
         self._param_dicts = None
         self._last_w = None
@@ -543,6 +546,15 @@ class InfGenDecoder(nn.Module):
             # (the engine takes the caller's own form: its check resolves it against its road table; explicit segments are
             # contents of this call's scenes, loaded with them)
             (fixed if ss['segments'] is None else live).update(step_scores=self.step_scores)
+        ir = getattr(self, 'insert_rules', None)
+        if ir is not None:      # (checked by the engine against its own scene counts; keyed by value, arrays by their bytes)
+            if not isinstance(ir, dict):
+                raise ValueError('insert_rules: None or dict(clearance=, ego_keepout=, edge_clearance=, near_lane=, zones=, types=, '
+                                 'max_agents=, per_step=)')
+            fixed.update(insert_rules=ir)
+            by_value = lambda v: (tuple(np.asarray(x).tobytes() for x in v) if isinstance(v, tuple) and len(v) == 2 and np.ndim(v[0]) >= 2
+                                  else np.asarray(v).tobytes() if isinstance(v, (np.ndarray, list)) else repr(v))
+            key += (('insert_rules',) + tuple((k, by_value(v)) for k, v in sorted(ir.items())),)
         return dict(fixed, **live), live, key
 
     def _guided(self, copies: int):

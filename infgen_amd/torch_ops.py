@@ -20,6 +20,9 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.road_mask(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_records, copies=1,
                                    sweep=1, margin=0, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
                                                                                             -> sets (S A, token_size / 32) int32, allowed (S A,)
+    torch.ops.infgen_hip.insert_cell_mask(pos, head, state, n_agents, av_index, shape, c, grid_xy, keepout?, clearance?,
+                                          edge_clearance?, records?, n_records?, lane_dist?, lane_types?, map_pos?, map_type?, n_map?,
+                                          zones?, n_zones?, copies=1)                       -> sets (S, W) int32, allowed (S,), live (S,)
     torch.ops.infgen_hip.route_mask(pos, head, state, n_agents, type, shape, c, end_pose, records, total, copies=1, corridor=2,
                                     back=0.5, pace=0, finish=1, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
                                                                                             -> sets, allowed (S A,), progress (S A, 4)
@@ -491,6 +494,77 @@ def _(pos, head, state, n_agents, type, shape, c, end_pose, paths, records, n_re
       mask_bits=None, mask_row=None, mask_type=None, first_new=None):
     rows = pos.shape[0] * pos.shape[2]
     return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32))
+
+
+@torch.library.custom_op('infgen_hip::insert_cell_mask', mutates_args=())
+def insert_cell_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, av_index: torch.Tensor,
+                     shape: torch.Tensor, c: int, grid_xy: torch.Tensor, keepout: Optional[List[float]] = None,
+                     clearance: Optional[float] = None, edge_clearance: Optional[float] = None,
+                     records: Optional[torch.Tensor] = None, n_records: Optional[torch.Tensor] = None,
+                     lane_dist: Optional[float] = None, lane_types: Optional[List[int]] = None,
+                     map_pos: Optional[torch.Tensor] = None, map_type: Optional[torch.Tensor] = None,
+                     n_map: Optional[torch.Tensor] = None, zones: Optional[torch.Tensor] = None,
+                     n_zones: Optional[torch.Tensor] = None, copies: int = 1) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the allowed cells of scenario insertion for column ``c`` (insertion rules; "INSERTION RULES" of include/infgen_hip.h,
+    ``infgen_insert_cell_mask``): pos (S, T, A, 2), head / state (S, T, A), n_agents / av_index (S,), shape (S, A, 3), grid_xy
+    (G, 2) in the ego frame.  A rule whose arguments are None is off: ``keepout`` (back, front, half_width); ``clearance``;
+    ``edge_clearance`` with ``records`` (S / copies, capacity, 8) / ``n_records``; ``lane_dist`` with ``lane_types`` / ``map_pos``
+    (S / copies, M, 2) / ``map_type`` (S / copies, M) / ``n_map``; ``zones`` (S / copies, Z, 4) / ``n_zones``.  Returns the sets
+    (S, W) int32 words, W = ceil(G / 32) rounded up to a multiple of 4, the number of allowed cells (S,) and the number of rows in
+    the scene at the column (S,)."""
+    from . import insertion_rules as ir
+    if pos.dim() != 4 or pos.shape[3] != 2 or head.shape != pos.shape[:3] or state.shape != pos.shape[:3]:
+        raise ValueError('insert_cell_mask takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,) or tuple(av_index.shape) != (S,):
+        raise ValueError('insert_cell_mask takes shape (S, A, 3), n_agents (S,), av_index (S,)')
+    if grid_xy.dim() != 2 or grid_xy.shape[1] != 2:
+        raise ValueError('grid_xy is (G, 2)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    dev, G, S0 = pos.device, int(grid_xy.shape[0]), S // max(copies, 1)
+    ops = _ops(dev)
+    i32 = lambda t: None if t is None else t.to(dev, torch.int32).contiguous()
+    rules = 0
+    if keepout is not None:
+        if len(keepout) != 3:
+            raise ValueError('keepout has three entries: back, front, half_width')
+        rules |= ir.KEEPOUT
+    rules |= ir.CLEARANCE * (clearance is not None) | ir.EDGES * (edge_clearance is not None) | ir.LANES * (lane_dist is not None)
+    rules |= ir.ZONES * (zones is not None)
+    if edge_clearance is not None and (records is None or n_records is None or records.dim() != 3 or records.shape[2] != 8
+                                       or records.shape[0] != S0 or tuple(n_records.shape) != (S0,)):
+        raise ValueError('edge_clearance takes records (S / copies, capacity, 8) and n_records (S / copies,)')
+    if lane_dist is not None and (map_pos is None or map_type is None or n_map is None or lane_types is None or map_pos.dim() != 3
+                                  or map_pos.shape[0] != S0 or tuple(map_type.shape) != tuple(map_pos.shape[:2])
+                                  or tuple(n_map.shape) != (S0,) or any(not 0 <= int(t) < 32 for t in lane_types)):
+        raise ValueError('lane_dist takes lane_types in 0..31, map_pos (S / copies, M, 2), map_type (S / copies, M), n_map (S / copies,)')
+    if zones is not None and (n_zones is None or zones.dim() != 3 or zones.shape[2] != 4 or zones.shape[0] != S0
+                              or tuple(n_zones.shape) != (S0,)):
+        raise ValueError('zones takes zones (S / copies, Z, 4) and n_zones (S / copies,)')
+    W = ir.words_for(G)
+    bits = torch.zeros(S, W, device=dev, dtype=torch.int32)
+    count, live = torch.zeros(S, device=dev, dtype=torch.int32), torch.zeros(S, device=dev, dtype=torch.int32)
+    p, h, sh, gx = _f32(pos), _f32(head), _f32(shape), _f32(grid_xy)
+    st, na, av, nr, nm, nz = i32(state), i32(n_agents), i32(av_index), i32(n_records), i32(n_map), i32(n_zones)
+    rc, mp, zn = (None if t is None else _f32(t) for t in (records, map_pos, zones))
+    mt = None if map_type is None else map_type.to(dev, torch.int64).contiguous()
+    ko = (C.c_float * 3)(*[float(v) for v in keepout]) if keepout is not None else None
+    _lib.check(ops.lib.infgen_insert_cell_mask(
+        _lib.ptr(p), _lib.ptr(h), _lib.ptr(st), _lib.ptr(na), _lib.ptr(av), _lib.ptr(sh), S, A, T, int(c), _lib.ptr(gx), G, rules, ko,
+        float(clearance or 0.0), float(edge_clearance or 0.0), float(lane_dist or 0.0), sum(1 << int(t) for t in set(lane_types or ())),
+        _lib.ptr(rc), _lib.ptr(nr), 0 if rc is None else int(rc.shape[1]), _lib.ptr(mp), _lib.ptr(mt), _lib.ptr(nm),
+        0 if mp is None else int(mp.shape[1]), _lib.ptr(zn), _lib.ptr(nz), 0 if zn is None else int(zn.shape[1]), int(copies), 0, None,
+        _lib.ptr(bits), W, _lib.ptr(count), _lib.ptr(live), None, 0, ops.stream), 'infgen_insert_cell_mask')
+    return bits, count, live
+
+
+@insert_cell_mask.register_fake
+def _(pos, head, state, n_agents, av_index, shape, c, grid_xy, keepout=None, clearance=None, edge_clearance=None, records=None,
+      n_records=None, lane_dist=None, lane_types=None, map_pos=None, map_type=None, n_map=None, zones=None, n_zones=None, copies=1):
+    S = pos.shape[0]
+    return (pos.new_empty(S, (grid_xy.shape[0] + 127) // 128 * 4, dtype=torch.int32), pos.new_empty(S, dtype=torch.int32),
+            pos.new_empty(S, dtype=torch.int32))
 
 
 def route_records(routes: torch.Tensor, n_points: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
