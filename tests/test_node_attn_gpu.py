@@ -10,7 +10,8 @@ layer; input regimes scale rows by 2^-20 .. 2^20 and add degenerate rows.  tests
 comparison tells the reference's deliberately wrong variants apart.  The largest device error / bar per output, regime and kernel
 family is printed at the end of the module and written as JSON to the file INFGEN_NODE_ATTN_RECORD names, if it is set.
 
-Out of scope here: gemm_terms 1 and 2, k_attn_h<8, 3> (an environment knob read at load time), the row-group list path and k_layers_p."""
+Out of scope here: gemm_terms 1 and 2, k_attn_h<8, 3> (an environment knob read at load time) and the row-group list path; k_layers_p
+has its own operator-level tests in tests/test_layers_stack_gpu.py."""
 import ctypes as C
 import json
 import os
