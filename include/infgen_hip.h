@@ -728,6 +728,77 @@ int infgen_token_mask_route(int handle, uint32_t* route_bits, const int* identit
                             const float* records, const float* total, int P, int copies, float corridor, float back, float pace,
                             float finish, const int* types, int* count, float* progress);
 
+/* signal-aware decoding: SIGNAL MASKS, the allowed-token sets of one decode step computed from the map scene's stop lines and their
+ * phase at that step (k_signal_mask): a stop line is DIRECTIONAL (it bars the traffic that approaches it lawfully, never the cross or
+ * oncoming traffic), TIME-VARYING (closed or open per decode step) and governs only rows that are still IN FRONT of it - three things a
+ * road record is not.  Step column c = 1 + t, IN THE SCENE, first_new, base(i) and the fallback mean what they mean for the collision
+ * masks above; fp32 throughout, no fused multiply-add, every sum and product in the order written here; world coordinates enter only
+ * through the exact difference (m - pos[c][i]).
+ *   lines   per map scene: lines [S0][K][4] = (ax, ay, bx, by) in world coordinates and n_lines [S0], 1 <= K <= 64, counts clamped to
+ *       0 .. K.  a is the LEFT end and b the RIGHT end as the traffic the line stops sees them.  Row (s, i) of `copies` copies per
+ *       scene reads the lines of map scene s / copies.
+ *   record   built once per (re)load by k_signal_records, records [S0][K][8], 16-byte aligned: mx, my, nx, ny, half, 0, 0, 0 with
+ *       d = b - a, L = sqrt(d.x * d.x + d.y * d.y), m = a + 0.5 * d (the midpoint), u = d / L, n = (-u.y, u.x) - the direction of lawful
+ *       travel across the line - and half = 0.5 * L.  The rule below is stated on the record as stored: the fp32 midpoint IS the line
+ *       (rounding it to a world coordinate moves the line by half an ulp at most, 0.25 mm at 5 km).  A line with L == 0, a
+ *       non-finite L or a, or an index >= n_lines is the DEAD record (0, 0, 1, 0, -1, 0, 0, 0): it is skipped.
+ *   phase   phase [S0][n_phase][K] bytes, n_phase >= 1: record j is CLOSED at decode step t iff phase[s0][t mod n_phase][j] != 0.  The
+ *       table is cyclic: one signal cycle serves a rollout of any length.
+ *   frame   as for the route masks, translate by pos[c][i] first, then rotate by -head[c][i]: with R(x, y) = (x ci + y si, y ci - x si),
+ *       q = R(m - pos), v = R(n), and the line's own axis tau = (v.y, -v.x).
+ *   front points   the row's own front bumper f0 = (hla, 0); token k's f_k = (dx + hla * cos_k, dy + hla * sin_k), with (dx, dy, cos_k,
+ *       sin_k) the entry of the end-pose table (infgen_collision_end_poses) of the row's type, hla = shape[i][0] / 2 and
+ *       hwa = shape[i][1] / 2.  For a point f: e = f - q, g(f) = (e.x * v.x + e.y * v.y) + setback, l(f) = e.x * v.y - e.y * v.x.
+ *   governs   a closed live record j GOVERNS row i iff v.x >= align - the row faces the way the line is crossed - and g0 = g(f0) <= 0:
+ *       its front bumper has not passed the line moved back by `setback` metres.  l0 = l(f0).
+ *   runs   token k RUNS record j iff j governs the row, g_k = g(f_k) > 0 and the crossing lies on the line widened by the row's half
+ *       width: | l0 * g_k - l_k * g0 | <= (half + hwa) * (g_k - g0) - the lateral offset of the point where f0 -> f_k meets the moved
+ *       line, cross-multiplied: there is no division.
+ *   rows   the rule applies to the rows in the scene at column c whose agent type ty (0 vehicle, 1 pedestrian, 2 cyclist; others count
+ *       as 0) has types[ty] != 0.  Every other row - not in the scene, padding, >= first_new[s], a type switched off - keeps base(i).
+ *       Replayed, commanded and teacher-forced rows keep their plan's tokens, as under any mask.
+ *   result   set(i) = base(i) AND NOT runs(i), runs(i) = the tokens that run at least one record; an empty result is replaced by
+ *       base(i) (a token that does not move the front point never runs a line, so the fallback is for rows whose base lacks every
+ *       such token); out_count[i] (optional) is the size before that fallback.  out_info [S * A_cap][4] (optional, 16-byte aligned) =
+ *       (gap, j, flag, 0) - what an observer, or a later car-following rule, reads: among the records that govern the row and have
+ *       |l0| <= half + hwa - the line lies across the row's present lane - the one of smallest gap = -g0, ties to the smaller index; j
+ *       is its index as a float, (0, -1) when there is none.  flag 1 = ruled; 2 = ruled with such a record WITHIN REACH: gap <= the
+ *       largest displacement of the row's type (the end-pose table's tail).  Rows the rule does not apply to get (0, -1, 0, 0).
+ *       A g, a lateral value (the crossing's offset, l0) or gap against its threshold within ~1e-4 m, or v.x within 1e-4 of align, may
+ *       fall either way - the band of the route masks.
+ * The kernel may skip a record whose midpoint is farther from the row than anything its tokens can make cross it (the largest
+ * displacement + hla + half + hwa + setback, plus a centimetre): that changes no result.
+ * infgen_signal_records: the record table of S0 distinct scenes from lines and n_lines.
+ * infgen_signal_mask: one launch writes out_bits [S * A_cap][token_size / 32], out_count and out_info for decode step t (which selects
+ * the phase row) at column c; the scene arrays as for infgen_collision_mask, S a multiple of copies; the base is a token mask's first
+ * four values with the rows' own `type`.
+ * infgen_token_mask_signal: attaches a signal configuration to a registered token mask, as infgen_token_mask_route does:
+ * infgen_decode_step then launches k_signal_mask for its step t and column 1 + t AFTER k_road_mask AND BEFORE k_route_mask - collision,
+ * then road, then signal, then route; each stage's base is the previous stage's bits read through the identity selector, each
+ * stage's fallback returns the previous stage's set, and the heads read the last stage's bits.  Route comes last on purpose: a pace bar
+ * that would push a row through a red empties the route set, and its fallback keeps the signal set.  With no signal configuration
+ * attached the launches and their arguments are exactly those without this entry.  info is rebuilt every step, like count.  The
+ * pointers are kept, not the contents: phase (and records) may be rewritten between two steps.  signal_bits NULL detaches.  Rows
+ * scenario insertion appends keep their base in the step that appends them and are ruled from the next.  The state of a signal
+ * is a function of t and the map scene alone: branching and snapshots copy nothing for it.
+ * infgen_token_mask_signal_get: test and diagnostic entry, host only: copies out the handle's signal configuration (0: the empty
+ * one) -> its size in bytes; infgen_token_mask_riders keeps reporting the five configurations it always did, byte for byte.
+ * Left out on purpose: a closed line as a standing lead of infgen_idm_command (out_info is shaped for it); re-encoding the map's
+ * light_type when a signal changes; any notion of CAUTION - the caller decides which states close a line.
+ * Refused ("signal mask" in the message), on the host, before any launch: setback negative or not finite, align outside [-1, 1], K
+ * outside 1..64, n_phase < 1, t < 0, copies < 1 or not dividing S, a token_size that is no multiple of 32 or exceeds 4096, A_cap
+ * beyond INFGEN_Q_MAX_AGENTS, a missing or misaligned table. */
+int infgen_signal_records(const float* lines, const int* n_lines, int S0, int K, float* records, void* stream);
+int infgen_signal_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new, const int* type,
+                       const float* shape, int S, int A_cap, int T, int c, const float* end_pose, int token_size, const float* records,
+                       const unsigned char* phase, int n_phase, int K, int t, int copies, float setback, float align, const int* types,
+                       const uint32_t* mask_bits, int mask_n_sets, const int* mask_row, const int* mask_type, uint32_t* out_bits,
+                       int* out_count, float* out_info, void* stream);
+int infgen_token_mask_signal(int handle, uint32_t* signal_bits, const int* identity_row, const float* shape, const float* end_pose,
+                             const float* records, const unsigned char* phase, int n_phase, int K, int copies, float setback,
+                             float align, const int* types, int* count, float* info);
+int infgen_token_mask_signal_get(int handle, void* out, int capacity);
+
 /* step scores: STEP SCORES, what a branching loop branches on - per scene slot and decode step the overlap, off-road and comfort terms
  * of the column the step just produced (k_step_score: one launch, no host read, no atomics).
  * Decode step t produces column c1 = 2 + t.  Row i of scene slot s is LIVE at a column when i < n_agents[s] and state[col][i] is not

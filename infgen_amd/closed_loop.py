@@ -151,6 +151,9 @@ class ClosedLoopSession:
             obs['allowed_tokens'] = eng.collision_allowed.view(eng.S, eng.A_cap)
         if eng.stay_on_road is not None:          # road-aware decoding runs behind the collision masks
             obs['allowed_tokens'] = eng.road_allowed.view(eng.S, eng.A_cap)
+        if eng.obey_signals is not None:          # signal-aware decoding runs behind the road masks; gap, line, flag, 0 per row
+            obs['allowed_tokens'] = eng.signal_allowed.view(eng.S, eng.A_cap)
+            obs['signal'] = eng.signal_info.view(eng.S, eng.A_cap, 4)
         if eng.follow_routes is not None:         # route-following decoding runs last: its sets are the ones the heads read
             obs['allowed_tokens'] = eng.route_allowed.view(eng.S, eng.A_cap)
             obs['route_progress'] = eng.route_progress.view(eng.S, eng.A_cap, 4)
@@ -257,6 +260,13 @@ class ClosedLoopSession:
         ``advance()`` on; ``observe()['route_progress']`` [S, A_cap, 4] = s0, d0, total, flag stays that of the step that just ran"""
         self._check_open()
         self.eng.set_routes(routes, n_points)
+
+    def set_signals(self, phase=None, lines=None, n_lines=None):
+        """new phase and / or stop-line tables for an engine with ``obey_signals`` (``RolloutEngine.set_signals``): they rule from
+        the next ``advance()`` on - a planner's way to switch a light; ``observe()['signal']`` [S, A_cap, 4] = gap, line, flag, 0
+        stays that of the step that just ran"""
+        self._check_open()
+        self.eng.set_signals(phase=phase, lines=lines, n_lines=n_lines)
 
     def branch(self, parent):
         """``RolloutEngine.branch(parent, t)`` at this session's step: slot s continues as a clone of slot ``parent[s]`` from the

@@ -401,6 +401,154 @@ def route_buffers(n_scenes: int, rows: int, a_cap: int, P: int, token_size: int,
     return k
 
 
+# ---------------------------------------------------------------------------------------- signal-aware decoding
+SIGNAL_MAX_LINES = 64                     # SG_MAX_LINES of csrc/kernels.h
+LIGHT_STOP, LIGHT_GO, LIGHT_CAUTION, LIGHT_UNKNOWN = 0, 1, 2, 3      # map_polygon.light_type
+
+
+def signal_lines(lines, n_lines=None, n_scenes: Optional[int] = None, what: str = 'obey_signals'):
+    """``lines`` [S0][K][4] = (ax, ay, bx, by) world coordinates - a the left and b the right end as the traffic the line stops sees
+    them - and ``n_lines`` [S0] (None: every line) -> (float32, int32) arrays, checked: 1 <= K <= 64, 0 <= n_lines <= K, one entry
+    per distinct scene.  Non-finite and zero-length lines are allowed: the definition makes their records dead"""
+    a = np.asarray(lines)
+    if a.ndim != 3 or a.shape[2] != 4 or a.dtype.kind not in 'fiu':
+        raise ValueError(f'{what}: lines are numbers [S0][K][4] = (ax, ay, bx, by), got shape {a.shape}')
+    if not 1 <= a.shape[1] <= SIGNAL_MAX_LINES:
+        raise ValueError(f'{what}: K = {a.shape[1]} lines per scene, must be 1 .. {SIGNAL_MAX_LINES}')
+    n = np.full(a.shape[0], a.shape[1], np.int32) if n_lines is None else np.asarray(n_lines)
+    if n.shape != a.shape[:1] or n.dtype.kind not in 'iu':
+        raise ValueError(f'{what}: n_lines holds integers [S0] = {a.shape[:1]}, got shape {n.shape}')
+    if n.size and (int(n.min()) < 0 or int(n.max()) > a.shape[1]):
+        raise ValueError(f'{what}: n_lines has entries outside 0 .. K = {a.shape[1]}')
+    if n_scenes is not None and a.shape[0] != n_scenes:
+        raise ValueError(f'{what}: lines cover {a.shape[0]} scenes, the batch has {n_scenes} distinct scenes')
+    return np.ascontiguousarray(a, np.float32), np.ascontiguousarray(n, np.int32)
+
+
+def signal_phase_table(phase, n_scenes: int, K: int, what: str = 'obey_signals'):
+    """``phase`` [S0][n_phase][K] (or [S0][K]: one row) -> uint8, non-zero = closed; checked against the lines' [S0][K]"""
+    p = np.asarray(phase)
+    if p.ndim == 2:
+        p = p[:, None]
+    if p.ndim != 3 or p.dtype.kind not in 'biu' or p.shape[1] < 1:
+        raise ValueError(f'{what}: phase holds bytes [S0][n_phase >= 1][K] (non-zero: closed), got shape {p.shape} of {p.dtype}')
+    if p.shape[0] != n_scenes or p.shape[2] != K:
+        raise ValueError(f'{what}: phase {p.shape} does not fit the lines\' [S0 = {n_scenes}][n_phase][K = {K}]')
+    return np.ascontiguousarray(p != 0, np.uint8)
+
+
+def check_obey_signals(obey, has_shape: bool = True, n_scenes: Optional[int] = None):
+    """``obey_signals`` as the engine takes it -> None (off) or dict(lines=float32 [S0][K][4], n_lines=int32 [S0], phase=uint8
+    [S0][n_phase][K], setback=, align= floats, types=(veh, ped, cyc) switches).  False / None: off; a mapping with ``lines`` and
+    ``phase`` and any of ``n_lines`` (every line), ``setback`` (0.5 m), ``align`` (0.5: the cosine a row's heading must make with a
+    line's direction of travel to be stopped by it), ``types`` (vehicles and cyclists).  Everything is checked here, on the host,
+    before any launch."""
+    if obey is None or obey is False:
+        return None
+    what = 'obey_signals'
+    if not isinstance(obey, Mapping):
+        raise ValueError(f'{what} takes False or dict(lines=, n_lines=, phase=, setback=, align=, types=)')
+    unknown = set(obey) - {'lines', 'n_lines', 'phase', 'setback', 'align', 'types'}
+    if unknown:
+        raise ValueError(f'{what}: unknown keys {sorted(unknown)} (lines, n_lines, phase, setback, align, types)')
+    if obey.get('lines') is None or obey.get('phase') is None:
+        raise ValueError(f'{what} needs lines [S0][K][4] and phase [S0][n_phase][K]')
+    setback, align = obey.get('setback', 0.5), obey.get('align', 0.5)
+    if isinstance(setback, (bool, str)) or not np.isscalar(setback) or not np.isfinite(setback) or setback < 0:
+        raise ValueError(f'{what}: setback must be a finite number of metres >= 0 (got {setback!r})')
+    if isinstance(align, (bool, str)) or not np.isscalar(align) or not -1 <= align <= 1:
+        raise ValueError(f'{what}: align must be a number in [-1, 1] (got {align!r})')
+    out = dict(setback=float(setback), align=float(align), types=_road_types(obey.get('types', ('veh', 'cyc')), what))
+    out['lines'], out['n_lines'] = signal_lines(obey['lines'], obey.get('n_lines'), n_scenes, what)
+    out['phase'] = signal_phase_table(obey['phase'], out['lines'].shape[0], out['lines'].shape[1], what)
+    if not has_shape:
+        raise ValueError(f'{what} needs the rows\' shapes: this engine has no shape array')
+    return out
+
+
+def signal_key(conf):
+    """the hashable part of a checked obey_signals configuration that decides the launches' arguments (lines and phase bytes are
+    contents; the table's extents K and n_phase are arguments - an engine keeps them in place of the arrays it has uploaded)"""
+    if conf is None:
+        return None
+    K = conf['K'] if 'K' in conf else int(conf['lines'].shape[1])
+    n_phase = conf['n_phase'] if 'n_phase' in conf else int(conf['phase'].shape[1])
+    return (conf['setback'], conf['align'], conf['types'], K, n_phase)
+
+
+def signal_buffers(n_scenes: int, rows: int, K: int, n_phase: int, token_size: int, device='cpu'):
+    """the static buffers of signal-aware decoding: the four of ``collision_buffers`` - ``bits``, ``allowed``, ``ident``, ``shape`` -,
+    ``info`` [rows][4], and per distinct scene ``lines`` [S0][K][4], ``n_lines`` [S0], ``records`` [S0][K][8], ``phase``
+    [S0][n_phase][K] bytes"""
+    import torch
+    if token_size % 32 or token_size > 4096:
+        raise ValueError(f'obey_signals: token_size {token_size} must be a multiple of 32, at most 4096')
+    k = collision_buffers({}, rows, token_size, device)
+    info = torch.zeros(rows, 4, device=device)
+    info[:, 1] = -1.0
+    k.update(K=K, n_phase=n_phase, info=info, lines=torch.zeros(n_scenes, K, 4, device=device),
+             n_lines=torch.zeros(n_scenes, dtype=torch.int32, device=device), records=torch.zeros(n_scenes, K, 8, device=device),
+             phase=torch.zeros(n_scenes, n_phase, K, dtype=torch.uint8, device=device))
+    return k
+
+
+def signal_phase(n_lines: int, period: int, red_from, red_to, offset=0):
+    """a cyclic phase table [period][n_lines] (uint8, 1 = closed) from per-line schedules: line j is closed at the steps t with
+    red_from[j] <= (t + offset[j]) mod period < red_to[j]; red_from > red_to wraps around the cycle's end, red_from == red_to is
+    never closed.  ``red_from`` / ``red_to`` / ``offset``: scalars or [n_lines] integers in 0 .. period.  numpy, host only; stack one
+    table per distinct scene for ``obey_signals['phase']``."""
+    if n_lines < 1 or period < 1:
+        raise ValueError('signal_phase: n_lines and period must be at least 1')
+    lo, hi, off = (np.broadcast_to(np.asarray(v), (n_lines,)) for v in (red_from, red_to, offset))
+    if any(v.dtype.kind not in 'iu' for v in (lo, hi, off)):
+        raise ValueError('signal_phase: red_from, red_to and offset are integers (decode steps)')
+    if (lo < 0).any() or (lo > period).any() or (hi < 0).any() or (hi > period).any():
+        raise ValueError(f'signal_phase: red_from and red_to must lie in 0 .. period = {period}')
+    at = (np.arange(period)[:, None] + off[None]) % period
+    plain = (at >= lo[None]) & (at < hi[None])
+    wrapped = (at >= lo[None]) | (at < hi[None])
+    return np.where((lo <= hi)[None], plain, wrapped).astype(np.uint8)
+
+
+def stop_lines_from_map(data_or_staged, states=(LIGHT_STOP,), half_width: float = 1.8):
+    """one stop line per map polygon whose ``light_type`` is in ``states`` (WOMD codes: 0 STOP, 1 GO, 2 CAUTION, 3 unknown - the caller
+    decides which close a line).  ``data_or_staged``: a scene (``map_polygon.light_type`` [P], ``pt_token.position`` [M][>= 2],
+    ``pt_token.orientation`` [M] and ``pt_token__to__map_polygon`` - or ``('pt_token', 'to', 'map_polygon')`` - ``['edge_index']`` [2][M],
+    map token -> polygon) or a sequence of scenes.  The
+    line is centred on the polygon's FIRST map token - the smallest token index mapped to it -, perpendicular to that token's
+    orientation, and spans +- ``half_width`` metres: a = centre + half_width * left, b = centre - half_width * left.
+    -> lines float32 [S][K][4], n_lines int32 [S], phase uint8 [S][1][K] with those lines closed (K: the largest scene's count, at
+    least 1; more than 64 raises).  Pure host code."""
+    if not np.isscalar(half_width) or not np.isfinite(half_width) or half_width <= 0:
+        raise ValueError('stop_lines_from_map: half_width must be a finite number of metres > 0')
+    datas = [data_or_staged] if isinstance(data_or_staged, Mapping) else list(data_or_staged)
+    per = []
+    for d in datas:
+        light = np.asarray(d['map_polygon']['light_type']).reshape(-1)
+        pos = np.asarray(d['pt_token']['position'], np.float64)[:, :2]
+        ori = np.asarray(d['pt_token']['orientation'], np.float64).reshape(-1)
+        key = ('pt_token', 'to', 'map_polygon')
+        edge = np.asarray(d[key if key in d else 'pt_token__to__map_polygon']['edge_index'])
+        first = {}
+        for tok, poly in zip(edge[0].tolist(), edge[1].tolist()):
+            first[poly] = min(tok, first.get(poly, tok))
+        out = []
+        for poly in range(light.shape[0]):
+            if int(light[poly]) in states and poly in first:
+                m, th = pos[first[poly]], ori[first[poly]]
+                left = np.array([-np.sin(th), np.cos(th)])
+                out.append(np.concatenate([m + half_width * left, m - half_width * left]))
+        per.append(np.array(out, np.float64).reshape(-1, 4))
+    K = max(1, max(a.shape[0] for a in per))
+    if K > SIGNAL_MAX_LINES:
+        raise ValueError(f'stop_lines_from_map: a scene has {K} such polygons, more than {SIGNAL_MAX_LINES} lines (choose among them)')
+    lines, n_lines = np.zeros((len(per), K, 4), np.float32), np.zeros(len(per), np.int32)
+    phase = np.zeros((len(per), 1, K), np.uint8)
+    for s, a in enumerate(per):
+        lines[s, :a.shape[0]], n_lines[s], phase[s, 0, :a.shape[0]] = a, a.shape[0], 1
+    return lines, n_lines, phase
+
+
 def routes_from_logged(data_or_staged, stride: int = 1, start: int = 0, points: int = ROUTE_MAX_POINTS):
     """every agent's logged positions as its route: "follow your own log".  ``data_or_staged``: a scene (its ``agent`` holds
     ``token_pos`` [A][T0][2] and ``state_idx`` [A][T0]), a sequence of scenes, or a mapping of stacked ``token_pos`` [S][A][T0][2] /

@@ -70,16 +70,24 @@ struct RouteCfg {
   int P, copies; float corridor, back, pace, finish; int types[3]; int* count; float* progress;
 };
 constexpr RouteCfg ROUTE_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, 1, 0.f, 0.f, 0.f, 0.f, {0, 0, 0}, nullptr, nullptr};
-struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; };
+// the signal configuration a registered mask may carry (infgen_token_mask_signal; bits == NULL: none)
+struct SignalCfg {
+  uint32_t* bits; const int* ident; const float* shape; const float* end_pose; const float* records; const unsigned char* phase;
+  int n_phase, K, copies; float setback, align; int types[3]; int* count; float* info;
+};
+constexpr SignalCfg SIGNAL_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, 1, 0.f, 0.f, {0, 0, 0}, nullptr, nullptr};
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; SignalCfg signal; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
-// what rides on a context's decode step: the static mask as the kernels take it and the four configurations of its handle
-// (validate fills it).  A new rider adds a Cfg, an args builder and one line in any()
+// what rides on a context's decode step: the static mask as the kernels take it and the configurations of its handle
+// (validate fills it).  A new rider adds a Cfg, an args builder and one line in any().  The members up to `route` are the block
+// infgen_token_mask_riders copies out, byte for byte (RIDERS_EXPORT_BYTES); later riders stand behind it
 struct StepRiders {
-  TokenMaskCtl mask; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route;
-  bool any() const { return mask.bits || coll.bits || road.bits || score.out || route.bits; }
+  TokenMaskCtl mask; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; SignalCfg signal;
+  bool any() const { return mask.bits || coll.bits || road.bits || score.out || route.bits || signal.bits; }
 };
-constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE};
+constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE, SIGNAL_NONE};
+constexpr size_t RIDERS_EXPORT_BYTES = offsetof(StepRiders, signal);
 // the one handle lookup: f(slot) under g_mask_mu, or the error `what` where the handle names no registered mask
 constexpr const char* NO_TOKEN_MASK = "no such token mask";
 template <class F> static int with_mask_slot(const char* where, int handle, const char* what, F f) {
@@ -112,7 +120,8 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   size_t h = 0;
   while (h < g_masks.size() && g_masks[h].in_use) ++h;
   if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
-  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE};
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE,
+                             SIGNAL_NONE};
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
@@ -1719,6 +1728,96 @@ extern "C" int infgen_token_mask_route(int handle, uint32_t* route_bits, const i
   return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.route = cfg; });
 }
 
+// ---------------------------------------------------------------------------------- signal masks
+// the argument checks of include/infgen_hip.h ("signal masks") - signal_check: what a configuration is checked for once, by the
+// stand-alone entry and when it is attached to a handle; launch_signal: the geometry - and the one launch of k_signal_mask
+static int signal_check(const char* where, int K, int n_phase, int copies, float setback, float align, const float* shape,
+                        const float* end_pose, const float* records, const unsigned char* phase, const int* types, const uint32_t* bits,
+                        const float* info) {
+  if (!std::isfinite(setback) || setback < 0.f) return fail(where, "signal mask: setback must be finite and >= 0");
+  if (!(align >= -1.f && align <= 1.f)) return fail(where, "signal mask: align must be in [-1, 1]");
+  if (K < 1 || K > SG_MAX_LINES) return fail(where, "signal mask: K must be in 1..64");
+  if (n_phase < 1) return fail(where, "signal mask: n_phase must be at least 1");
+  if (copies < 1) return fail(where, "signal mask: copies must be at least 1");
+  if (!shape) return fail(where, "signal mask: needs the rows' shape array [S][A_cap][3]");
+  if (!end_pose) return fail(where, "signal mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!records || !phase) return fail(where, "signal mask: needs the record table and the phase table");
+  if (!types) return fail(where, "signal mask: needs the three-entry type switch");
+  if (!bits) return fail(where, "signal mask: needs the output table");
+  if (misaligned16(bits, end_pose, records, info)) return fail(where, "signal mask: the tables must be 16-byte aligned");
+  return 0;
+}
+static SignalArgs signal_args(const RiderScene& sc, int c, int t, const SignalCfg& k, const TokenMaskCtl& base) {
+  SignalArgs a = rider_args<SignalArgs>(sc, k);
+  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
+  a.end_pose = k.end_pose; a.records = k.records; a.phase = k.phase; a.n_phase = k.n_phase; a.K = k.K; a.t = t; a.copies = k.copies;
+  a.setback = k.setback; a.align = k.align;
+  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
+  a.base = base; a.out_bits = k.bits; a.out_count = k.count; a.out_info = k.info;
+  return a;
+}
+static int launch_signal(const char* where, const SignalArgs& a, void* stream) {
+  RET_IF(signal_check(where, a.K, a.n_phase, a.copies, a.setback, a.align, a.shape, a.end_pose, a.records, a.phase, a.types, a.out_bits,
+                      a.out_info));
+  if (a.t < 0) return fail(where, "signal mask: step t must be >= 0");
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "signal mask: S, A_cap and T must be positive");
+  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "signal mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.S % a.copies) return fail(where, "signal mask: S must be a multiple of copies");
+  if (a.c < 0 || a.c >= a.T) return fail(where, "signal mask: column outside [0, T)");
+  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
+    return fail(where, "signal mask: token_size must be a multiple of 32, at most 4096");
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "signal mask: null scene array");
+  const long long rows = (long long)a.S * a.A_cap;
+  if (rows > 0x7fffffffLL) return fail(where, "signal mask: too many rows");
+  hipLaunchKernelGGL(k_signal_mask, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+
+extern "C" int infgen_signal_records(const float* lines, const int* n_lines, int S0, int K, float* records, void* stream) {
+  const char* me = "infgen_signal_records";
+  if (!lines || !n_lines || !records) return fail(me, "signal mask: null pointer");
+  if (K < 1 || K > SG_MAX_LINES) return fail(me, "signal mask: K must be in 1..64");
+  if (S0 <= 0) return fail(me, "signal mask: S0 must be positive");
+  if (misaligned16(lines, records)) return fail(me, "signal mask: the tables must be 16-byte aligned");
+  const long long n = (long long)S0 * K;
+  if (n > 0x7fffffffLL) return fail(me, "signal mask: too many lines");
+  const int nt = 64 * RIDER_WAVES;
+  hipLaunchKernelGGL(k_signal_records, dim3((unsigned)((n + nt - 1) / nt)), dim3(nt), 0, (hipStream_t)stream,
+                     SignalRecArgs{lines, n_lines, S0, K, records});
+  return check_launch(me);
+}
+
+extern "C" int infgen_signal_mask(const float* pos, const float* head, const int* state, const int* n_agents, const int* first_new,
+                                  const int* type, const float* shape, int S, int A_cap, int T, int c, const float* end_pose,
+                                  int token_size, const float* records, const unsigned char* phase, int n_phase, int K, int t, int copies,
+                                  float setback, float align, const int* types, const uint32_t* mask_bits, int mask_n_sets,
+                                  const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, float* out_info,
+                                  void* stream) {
+  const char* me = "infgen_signal_mask";
+  RET_IF(signal_check(me, K, n_phase, copies, setback, align, shape, end_pose, records, phase, types, out_bits, out_info));
+  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
+  const SignalCfg cfg{out_bits, nullptr, shape, end_pose, records, phase, n_phase, K, copies, setback, align,
+                      {types[0], types[1], types[2]}, out_count, out_info};
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
+  TokenMaskCtl base;
+  RET_IF(token_mask_ctl(me, &md, token_size, &base));
+  return launch_signal(me, signal_args(sc, c, t, cfg, base), stream);
+}
+
+extern "C" int infgen_token_mask_signal(int handle, uint32_t* signal_bits, const int* identity_row, const float* shape,
+                                        const float* end_pose, const float* records, const unsigned char* phase, int n_phase, int K,
+                                        int copies, float setback, float align, const int* types, int* count, float* info) {
+  const char* me = "infgen_token_mask_signal";
+  SignalCfg cfg = SIGNAL_NONE;
+  if (signal_bits) {
+    RET_IF(signal_check(me, K, n_phase, copies, setback, align, shape, end_pose, records, phase, types, signal_bits, info));
+    if (!identity_row) return fail(me, "signal mask: needs the identity selectors [S * A_cap]");
+    cfg = SignalCfg{signal_bits, identity_row, shape, end_pose, records, phase, n_phase, K, copies, setback, align,
+                    {types[0], types[1], types[2]}, count, info};
+  }
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.signal = cfg; });
+}
+
 // ---------------------------------------------------------------------------------- step scores
 // the argument checks of include/infgen_hip.h ("step scores") - score_check: what a configuration is checked for once, by the
 // stand-alone entry and when it is attached to a handle; launch_score: the geometry - and the one launch of k_step_score
@@ -1885,6 +1984,7 @@ static int handle_riders(const char* where, int handle, const int* type, int tok
   TokenMaskDesc tm;
   RET_IF(with_mask_slot(where, handle, "token_mask is no handle of infgen_token_mask_create", [&](const TokenMaskSlot& s) {
     tm = s.d; riders->coll = s.coll; riders->road = s.road; riders->score = s.score; riders->route = s.route;
+    riders->signal = s.signal;
   }));
   if (!tm.type) tm.type = type;
   TokenMaskCtl ctl;
@@ -1914,7 +2014,7 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   *riders = RIDERS_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
     RET_IF(handle_riders(where, r->token_mask, r->type, r->token_size, riders));
-    const auto& [mask, coll, road, score, route] = *riders;
+    const auto& [mask, coll, road, score, route, signal] = *riders;
     if (coll.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
       return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
     if (road.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
@@ -1926,6 +2026,9 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
     if (route.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
       return fail(where, "route mask: token_size must be a multiple of 32, at most 4096");
     if (route.bits && r->S % route.copies) return fail(where, "route mask: S must be a multiple of copies");
+    if (signal.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
+      return fail(where, "signal mask: token_size must be a multiple of 32, at most 4096");
+    if (signal.bits && r->S % signal.copies) return fail(where, "signal mask: S must be a multiple of copies");
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: the plan under the context's own switches
@@ -1940,14 +2043,24 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
 // test and diagnostic entry: the step riders a context of this token_size (row types `type`) would run under the handle
 extern "C" int infgen_token_mask_riders(int handle, const int* type, int token_size, void* out, int capacity) {
   const char* me = "infgen_token_mask_riders";
-  if (!out || capacity < (int)sizeof(StepRiders)) return fail(me, "needs a buffer of at least sizeof(StepRiders) bytes");
+  if (!out || capacity < (int)RIDERS_EXPORT_BYTES) return fail(me, "needs a buffer of at least the block's size in bytes");
   StepRiders riders;
   std::memset(&riders, 0, sizeof riders);               // (padding bytes too: the caller compares bytes)
   const StepRiders none = RIDERS_NONE;
   riders.mask = none.mask; riders.coll = none.coll; riders.road = none.road; riders.score = none.score; riders.route = none.route;
   if (handle != 0) RET_IF(handle_riders(me, handle, type, token_size, &riders, true));
-  std::memcpy(out, &riders, sizeof riders);
-  return (int)sizeof riders;
+  std::memcpy(out, &riders, RIDERS_EXPORT_BYTES);          // (the signal configuration behind it: infgen_token_mask_signal_get)
+  return (int)RIDERS_EXPORT_BYTES;
+}
+
+extern "C" int infgen_token_mask_signal_get(int handle, void* out, int capacity) {
+  const char* me = "infgen_token_mask_signal_get";
+  static_assert(sizeof(SignalCfg) == 6 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(void*), "SignalCfg has no padding: its bytes are compared");
+  if (!out || capacity < (int)sizeof(SignalCfg)) return fail(me, "needs a buffer of at least the configuration's size in bytes");
+  SignalCfg cfg = SIGNAL_NONE;
+  if (handle != 0) RET_IF(with_mask_slot(me, handle, NO_TOKEN_MASK, [&](const TokenMaskSlot& s) { cfg = s.signal; }));
+  std::memcpy(out, &cfg, sizeof cfg);
+  return (int)sizeof cfg;
 }
 
 // zero_totals = false: the three totals were cleared by the previous step's k_integrate (IntegrateArgs.edge_totals)
@@ -2677,7 +2790,7 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
   StepRiders riders;
   RET_IF(validate(r, "infgen_decode_step", &ctl, &riders));
-  auto& [mask, coll, road, score, route] = riders;
+  auto& [mask, coll, road, score, route, signal] = riders;
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
@@ -2692,6 +2805,10 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   if (road.bits) {      // road-aware decoding: the sets so far (static, or this column's collision sets) without the off-road tokens
     RET_IF(launch_road("infgen_decode_step", road_args(sc, c, road, mask), stream));
     mask = TokenMaskCtl{road.bits, rows, road.ident, {-1, -1, -1}, nullptr};
+  }
+  if (signal.bits) {    // signal-aware decoding: the sets so far without the tokens that run a stop line closed at step t
+    RET_IF(launch_signal("infgen_decode_step", signal_args(sc, c, t, signal, mask), stream));
+    mask = TokenMaskCtl{signal.bits, rows, signal.ident, {-1, -1, -1}, nullptr};
   }
   if (route.bits) {     // route-following decoding: the sets so far without the tokens that leave the row's route or fall behind on it
     RET_IF(launch_route("infgen_decode_step", route_args(sc, c, route, mask), stream));

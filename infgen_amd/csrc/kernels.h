@@ -671,6 +671,27 @@ struct RouteRecArgs { const float* routes; const int* n_points; int rows, P; flo
 __global__ void k_route_mask(RouteArgs a);
 __global__ void k_route_records(RouteRecArgs a);
 
+// signal_kernels.hip: the per-step allowed-token sets of signal-aware decoding (include/infgen_hip.h, "signal masks"):
+// set(i) = base(i) AND NOT runs(i), written as the row's own set of out_bits
+constexpr int SG_REC = 8;               // floats of a record: midpoint x, y, direction of lawful travel x, y | half length, 0, 0, 0
+constexpr int SG_MAX_LINES = 64;        // stop lines of a map scene at most: one per lane of a wave
+struct SignalArgs {
+  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* first_new;                  // [S]; first_new optional
+  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
+  const float* end_pose; int token_size;                      // [3][token_size][4] + 4 floats
+  const float* records; const unsigned char* phase;           // [S / copies][K][SG_REC], [S / copies][n_phase][K]
+  int n_phase, K, t;                    // decode step t reads phase row t % n_phase
+  int copies; float setback, align; int types[3];             // types[ty] != 0: the rule applies to rows of agent type ty
+  TokenMaskCtl base;                    // the sets the signal rule refines (bits == NULL: every token)
+  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
+  float* out_info;                      // optional [S * A_cap][4] = gap, j, flag, 0
+};
+struct SignalRecArgs { const float* lines; const int* n_lines; int S0, K; float* records; };
+__global__ void k_signal_mask(SignalArgs a);
+__global__ void k_signal_records(SignalRecArgs a);
+
 // branch_kernels.hip: branching rollouts (include/infgen_hip.h, "branching").  k_branch_scenes gathers, for every scene s with a
 // valid parent[s] != s, slot parent[s]'s rollout state into slot s - one launch over (chunk of a segment, scene).  A SEGMENT is one
 // buffer of the context as `outer` blocks per scene: block o of scene s is the `bytes` bytes at base + o * outer_stride + s * bytes.

@@ -557,7 +557,7 @@ class RolloutEngine:
                  token_logprob: bool = False, sample_logprob: bool = False,
                  sample_temperature=1.0, sample_top_p: float = 1.0, insert_temperature: float = 1.0, insert_top_p: float = 1.0,
                  token_masks=None, token_mask_type=None, token_mask_row=None, avoid_collisions=False, stay_on_road=False,
-                 step_scores=False, follow_routes=False, insert_rules=None):
+                 step_scores=False, follow_routes=False, insert_rules=None, obey_signals=False):
         """``insert_rules``: insertion rules ("INSERTION RULES" of include/infgen_hip.h) - None or dict(clearance=,
         ego_keepout=(back, front, half_width), edge_clearance=, near_lane=dict(dist=, types=), zones=, types=, max_agents=,
         per_step=): a cell mask computed on the device in front of every insertion decision (``infgen_amd.insertion_rules``).
@@ -626,6 +626,19 @@ class RolloutEngine:
         ``route_progress`` ([rows, 4] = s0, d0, total, flag) are static device buffers of the step that just ran;
         ``set_routes(routes, n_points)`` replaces the routes between two steps.  ``reload*(follow_routes=...)`` turns it on or
         off (None: keep).  Rows scenario insertion appends have no route.
+        ``obey_signals``: signal-aware decoding ("signal masks" of include/infgen_hip.h) - False or
+        ``dict(lines=, n_lines=, phase=, setback=0.5, align=0.5, types=('veh', 'cyc'))``: ``lines`` [S0][K][4] = (ax, ay, bx, by)
+        world-coordinate stop lines per distinct scene (K <= 64; a the left, b the right end as the stopped traffic sees them),
+        ``n_lines`` [S0] (default: all K), ``phase`` [S0][n_phase][K] bytes, non-zero = closed at the decode steps t with
+        t mod n_phase == that row (``constraints.signal_phase`` / ``stop_lines_from_map`` make them).  Every decode step bans,
+        for the generated rows of those types, the motion tokens that carry the row's front bumper across a closed line it faces
+        and has not passed; on top of the static, collision or road set and underneath the route set, and a row with no token
+        left keeps the set it had.  ``signal_bits`` / ``signal_allowed`` / ``signal_info`` ([rows, 4] = gap, line, flag, 0) are
+        static device buffers of the step that just ran; ``set_signals(phase=, lines=, n_lines=)`` rewrites the tables between two
+        steps.  ``reload*(obey_signals=...)`` turns it on or off (None: keep).  A signal's state is a function of the step and the
+        map scene alone, so branching and snapshots copy nothing for it: a branched or restored slot sees the phase row of its
+        step.  Engines with scenario insertion are allowed: appended rows keep their base in the step that appends them and are
+        ruled from the next.
         ``stay_on_road``: road-aware decoding ("road masks" of include/infgen_hip.h) - False, True or
         ``dict(margin=metres, sweep=0 | 1, detail=1 | 2 | 5 | 10, types=('veh', 'cyc'), segments=None)``.  Every decode step bans the
         motion tokens whose end box or (``sweep``) path rectangle overlaps a road-edge segment the row does not already straddle, on
@@ -837,7 +850,11 @@ class RolloutEngine:
         self.follow_routes = None                         # the checked configuration while route-following decoding is on
         self.route_bits = self.route_allowed = self.route_progress = None
         self._route = self._route_reg = None
-        self._load_riders((token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores, follow_routes)
+        self.obey_signals = None                          # the checked configuration while signal-aware decoding is on
+        self.signal_bits = self.signal_allowed = self.signal_info = None
+        self._signal = self._signal_reg = None
+        self._load_riders((token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores, follow_routes,
+                          obey_signals)
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -1131,6 +1148,77 @@ class RolloutEngine:
         _lib.check(self.lib.infgen_route_records(_lib.ptr(k['routes']), _lib.ptr(k['n_points']), self.S0, self.A_cap, P,
                                                  _lib.ptr(k['records']), _lib.ptr(k['total']), self.ops.stream), 'infgen_route_records')
 
+    def _load_signals(self, obey):
+        """``obey_signals`` into the engine (None: keep what is there), like ``_load_routes``; lines and phase are uploaded and the
+        records built at once (they do not depend on the scene in the buffers)"""
+        if obey is None:
+            return
+        conf = constraints.check_obey_signals(obey, has_shape=getattr(self, '_shape10', None) is not None, n_scenes=self.S0)
+        if conf is None and self.obey_signals is None:
+            return
+        if constraints.signal_key(conf) != constraints.signal_key(self.obey_signals):
+            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
+        if conf is not None:
+            self._upload_signals(conf.pop('phase'), conf.pop('lines'), conf.pop('n_lines'))
+            conf.update(K=self._signal['K'], n_phase=self._signal['n_phase'])
+        else:      # off: nothing of the last ruled step stays readable
+            self._signal = self.signal_bits = self.signal_allowed = self.signal_info = None
+        self.obey_signals = conf
+        self._apply_token_masks()
+
+    def set_signals(self, phase=None, lines=None, n_lines=None):
+        """new signal tables for an engine with ``obey_signals`` on - allowed between two steps of a rollout or session, and between
+        two rollouts: ``phase`` [S0][n_phase][K] (or [S0][K]) and / or ``lines`` [S0][K][4] with ``n_lines`` [S0] (default: all K) are
+        uploaded into the static buffers (new ones when K or n_phase changes), and new lines' records rebuilt by k_signal_records
+        on the engine's stream.  A captured graph is dropped by every upload (``_upload_signals``), as ``set_routes`` drops it: the
+        next rollout captures again."""
+        if self.obey_signals is None:
+            raise ValueError('set_signals: the engine was built without obey_signals')
+        if phase is None and lines is None:
+            if n_lines is not None:
+                raise ValueError('set_signals: n_lines comes with lines')
+            return
+        k = self._signal
+        if lines is not None:
+            lines, n_lines = constraints.signal_lines(lines, n_lines, n_scenes=self.S0, what='set_signals')
+            if phase is None and lines.shape[1] != k['K']:
+                raise ValueError(f'set_signals: lines for K = {lines.shape[1]} need a phase table of that K (the engine holds K = {k["K"]})')
+        elif n_lines is not None:
+            raise ValueError('set_signals: n_lines comes with lines')
+        if phase is not None:
+            phase = constraints.signal_phase_table(phase, self.S0, k['K'] if lines is None else lines.shape[1], 'set_signals')
+        self._upload_signals(phase, lines, n_lines)
+        conf = self.obey_signals
+        if (conf['K'], conf['n_phase']) != (self._signal['K'], self._signal['n_phase']):
+            conf.update(K=self._signal['K'], n_phase=self._signal['n_phase'])
+        self._apply_token_masks()
+
+    def _upload_signals(self, phase, lines, n_lines):
+        """phase and / or lines (checked host arrays, None: keep) into the static buffers; new extents take new buffers"""
+        k = self._signal
+        K = int(lines.shape[1]) if lines is not None else k['K']
+        n_phase = int(phase.shape[1]) if phase is not None else k['n_phase']
+        if k is None or (k['K'], k['n_phase']) != (K, n_phase):
+            if lines is None or phase is None:
+                if k is None or k['K'] != K:
+                    raise ValueError('set_signals: a new K needs both lines and phase')
+                # a phase table of another length over the lines that are there
+                lines, n_lines = k['lines'].cpu().numpy(), k['n_lines'].cpu().numpy()
+            self._signal = k = constraints.signal_buffers(self.S0, self.S * self.A_cap, K, n_phase, self.cfg.token_size, self.device)
+            self.signal_bits, self.signal_allowed, self.signal_info = k['bits'], k['allowed'], k['info']
+            k['shape'].copy_(self._shape10.reshape(-1, 3))
+            self._end_pose_table()
+        # every upload drops a captured graph - through set_signals and through reload*(obey_signals=...) alike -, also where the
+        # buffers keep their addresses: the next rollout captures again and no graph is replayed over tables rewritten under it
+        self._graph = self._wgraph = None
+        if phase is not None:
+            k['phase'].copy_(torch.from_numpy(phase))
+        if lines is not None:
+            k['lines'].copy_(torch.from_numpy(lines))
+            k['n_lines'].copy_(torch.from_numpy(n_lines))
+            _lib.check(self.lib.infgen_signal_records(_lib.ptr(k['lines']), _lib.ptr(k['n_lines']), self.S0, K, _lib.ptr(k['records']),
+                                                      self.ops.stream), 'infgen_signal_records')
+
     def _load_scores(self, scores):
         """``step_scores`` into the engine (None: keep what is there), like ``_load_road``, whose record table the scores share"""
         if scores is None:
@@ -1207,7 +1295,8 @@ class RolloutEngine:
         three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  A
         collision configuration rides on the handle (one without a table when the engine has no ``token_masks``)"""
         if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and self.stay_on_road is None
-                                 and self.step_scores is None and self.follow_routes is None and not self._mask_handle):
+                                 and self.step_scores is None and self.follow_routes is None and self.obey_signals is None
+                                 and not self._mask_handle):
             return
         if self.token_masks is not None:
             reg = (self.mask_bits.data_ptr(), self.token_masks.n_sets, self.mask_row.data_ptr(), tuple(self.token_mask_type))
@@ -1254,6 +1343,12 @@ class RolloutEngine:
                lambda: (P(kt['bits']), P(kt['ident']), P(kt['shape']), P(self._coll_end), P(kt['records']), P(kt['total']), kt['P'],
                         self.copies, rt['corridor'], rt['back'], rt['pace'], rt['finish'], (C.c_int * 3)(*rt['types']),
                         P(kt['allowed']), P(kt['progress'])))
+        # the signal configuration: the library runs it after road and before route
+        sg, kg = self.obey_signals, self._signal
+        attach('_signal_reg', None if sg is None else (h, constraints.signal_key(sg), kg['records'].data_ptr(), kg['phase'].data_ptr()),
+               'infgen_token_mask_signal', (None, None, None, None, None, None, 1, 1, 1, 0.0, 0.0, None, None, None),
+               lambda: (P(kg['bits']), P(kg['ident']), P(kg['shape']), P(self._coll_end), P(kg['records']), P(kg['phase']), kg['n_phase'],
+                        kg['K'], self.copies, sg['setback'], sg['align'], (C.c_int * 3)(*sg['types']), P(kg['allowed']), P(kg['info'])))
         self._ctx.token_mask = h
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
@@ -1262,7 +1357,7 @@ class RolloutEngine:
         if getattr(self, '_mask_handle', 0):
             self.lib.infgen_token_mask_destroy(self._mask_handle)
             self._mask_handle, self._mask_reg, self._coll_reg, self._road_reg, self._score_reg = 0, None, None, None, None
-            self._route_reg = None
+            self._route_reg = self._signal_reg = None
             if getattr(self, '_ctx', None) is not None:
                 self._ctx.token_mask = 0
 
@@ -1278,7 +1373,8 @@ class RolloutEngine:
             c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
-    def _load_riders(self, token_masks=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
+    def _load_riders(self, token_masks=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None,
+                     obey_signals=None):
         """what rides on the decode step into the engine, in the one order it is resolved in: masks, collisions, road, scores (each
         None: keep what is there; ``token_masks`` a (table, per-type, per-row) triple).  Road and scores are checked against each
         other once both are resolved: the scores' argument is recorded - and scores that go are gone - before ``_load_road``
@@ -1292,10 +1388,11 @@ class RolloutEngine:
         self._load_road(stay_on_road)
         self._load_scores(step_scores)
         self._load_routes(follow_routes)
+        self._load_signals(obey_signals)
 
     def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
-                       avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
-        self._load_riders(token_masks, avoid_collisions, stay_on_road, step_scores, follow_routes)
+                       avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None, obey_signals=None):
+        self._load_riders(token_masks, avoid_collisions, stay_on_road, step_scores, follow_routes, obey_signals)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
@@ -1369,7 +1466,7 @@ class RolloutEngine:
     def reload(self, scenes: Sequence[Mapping], sample_uniforms: Optional[np.ndarray] = None,
                insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-               avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
+               avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None, obey_signals=None):
         """a new batch of scenes of the same layout into this engine's device buffers: one upload per array, no allocation, the
         context block / captured graph / scratch stay (the drop-in entry keeps one engine per layout across calls)"""
         assert self.fits(scenes), 'batch does not fit this engine (RolloutEngine.fits)'
@@ -1385,7 +1482,7 @@ class RolloutEngine:
             dst.copy_(torch.from_numpy(arr[k]))
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
                             (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
-                            follow_routes)
+                            follow_routes, obey_signals)
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1402,7 +1499,8 @@ class RolloutEngine:
     def reload_device(self, k: Mapping, scenes, sample_uniforms: Optional[np.ndarray] = None,
                       insert_uniforms: Optional[np.ndarray] = None, x_pt_override: Optional[Sequence] = None, replay=None,
                       sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None,
-                      token_mask_row=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None) -> bool:
+                      token_mask_row=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None,
+                      obey_signals=None) -> bool:
         """``reload`` for a batch whose scenes arrive as DEVICE tensors of one shape, stacked per key (``k``: what
         ``modules.infgen_decoder.stack_datas`` returns): the setup statements (``scene_setup.setup_agents``) and the epilogue's
         input arrays run as torch ops on the device and write this engine's buffers - no device -> host -> device
@@ -1418,7 +1516,7 @@ class RolloutEngine:
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
                             (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
-                            follow_routes)
+                            follow_routes, obey_signals)
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1480,7 +1578,7 @@ class RolloutEngine:
     def reload_batch(self, batch, src_graph: Optional[torch.Tensor] = None, sample_uniforms: Optional[np.ndarray] = None,
                      insert_uniforms: Optional[np.ndarray] = None, layout: Optional[Mapping] = None, replay=None,
                      sample_temperature=None, sample_top_p=None, token_masks=None, token_mask_type=None, token_mask_row=None,
-                     avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None):
+                     avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None, obey_signals=None):
         """``reload`` for a ragged PyG-style Batch of device tensors: the ingest kernel (infgen_ingest_batch) filters, pads and
         writes every scene buffer and the epilogue inputs from the concatenated arrays - no host copy of the scene data; the
         only device -> host copy before the first launch is the offsets' (``read_batch_layout``, skipped when ``layout`` is
@@ -1491,7 +1589,7 @@ class RolloutEngine:
         self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
                             (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
-                            follow_routes)
+                            follow_routes, obey_signals)
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -1656,6 +1754,8 @@ class RolloutEngine:
             self._road['shape'].copy_(self._shape10.reshape(rows, 3))
             if self._road_dirty:
                 self._road_build()
+        if self._signal is not None:                 # signal-aware decoding: the rows' boxes (the lines are the caller's)
+            self._signal['shape'].copy_(self._shape10.reshape(rows, 3))
         if self.step_scores is not None:             # step scores: the rows' boxes, and the record table where the scores alone drive it
             if self.stay_on_road is None:            # (otherwise the one shape array was refreshed just above)
                 self._score_boxes().copy_(self._shape10.reshape(rows, 3))
@@ -2166,7 +2266,8 @@ class RolloutEngine:
                        'infgen_active_row_groups')
         if t > 0:
             yield from self._insert_step(t)
-            live_shapes = [k['shape'] for k, on in ((self._coll, self.avoid_collisions), (self._road, self.stay_on_road)) if on is not None]
+            live_shapes = [k['shape'] for k, on in ((self._coll, self.avoid_collisions), (self._road, self.stay_on_road),
+                                                        (self._signal, self.obey_signals)) if on is not None]
             if live_shapes:
                 # the boxes of the rows this step appended (they are obstacles, and get sets, from the next step on): one mask, merged
                 # into the shape array of every per-step mask kernel that is on

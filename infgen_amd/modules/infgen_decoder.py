@@ -17,8 +17,8 @@ import torch.nn as nn
 
 from .. import _lib, logprob, modes, scene_setup
 from ..closed_loop import ClosedLoopSession, run_idm
-from ..constraints import (TokenMasks, check_avoid_collisions, check_follow_routes, check_stay_on_road, check_step_scores,
-                           check_type_selectors, road_key, route_key, score_key)
+from ..constraints import (TokenMasks, check_avoid_collisions, check_follow_routes, check_obey_signals, check_stay_on_road,
+                           check_step_scores, check_type_selectors, road_key, route_key, score_key, signal_key)
 from ..engine import InsertionHeadroomError, LazyOut, PackedWeights, RolloutEngine, read_batch_layout
 from ..synth import RolloutConfig
 from .agent_decoder import InfGenAgentDecoder
@@ -405,6 +405,11 @@ class InfGenDecoder(nn.Module):
         # pace=, finish=, types=), routes [scenes][A][P][2] for the scenes of the call (with copies = n a scene's routes apply to each
         # of its copies).  Its scalars and P are part of the engine cache key; the routes are contents loaded with every call
         self.follow_routes = False
+        # signal-aware decoding (RolloutEngine's obey_signals): False or dict(lines=, n_lines=, phase=, setback=, align=,
+        # types=), lines [scenes][K][4] and phase [scenes][n_phase][K] for the scenes of the call (with copies = n a scene's lines
+        # apply to each of its copies).  Its scalars, K and n_phase are part of the engine cache key; the tables are contents loaded
+        # with every call
+        self.obey_signals = False
         # step scores (RolloutEngine's step_scores): False, True or dict(road_margin=, sweep=, types=, detail=,
         # segments=, dt=) - every rollout dict then carries ``step_score`` [steps, 8]; keyed and loaded like stay_on_road.
         # guided_rollouts: None or a dict of RolloutEngine.rollout_guided's arguments (every=, keep=, weights=, u=): the copies of
@@ -538,6 +543,10 @@ class InfGenDecoder(nn.Module):
         if fr is not None:      # (the engine takes the caller's own form; the waypoints are world coordinates of this call's scenes)
             key += (('follow_routes',) + route_key(fr) + (int(fr['routes'].shape[2]),),)
             live.update(follow_routes=self.follow_routes)
+        og = check_obey_signals(getattr(self, 'obey_signals', False), n_scenes=n_scenes)      # (absent on a bare argument holder: off)
+        if og is not None:      # (the engine takes the caller's own form; lines and phase are contents of this call's scenes)
+            key += (('obey_signals',) + signal_key(og),)
+            live.update(obey_signals=self.obey_signals)
         ss = check_step_scores(getattr(self, 'step_scores', False), stay_on_road=sr)
         if getattr(self, 'guided_rollouts', None) is not None and ss is None:
             raise ValueError('guided_rollouts needs step_scores')

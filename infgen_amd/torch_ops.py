@@ -26,6 +26,9 @@ take the PACKED parameter blocks the library reads (``infgen_amd.packing``; the 
     torch.ops.infgen_hip.route_mask(pos, head, state, n_agents, type, shape, c, end_pose, records, total, copies=1, corridor=2,
                                     back=0.5, pace=0, finish=1, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
                                                                                             -> sets, allowed (S A,), progress (S A, 4)
+    torch.ops.infgen_hip.signal_mask(pos, head, state, n_agents, type, shape, c, end_pose, records, phase, t, copies=1,
+                                     setback=0.5, align=0.5, types=[1, 0, 1], mask_bits?, mask_row?, mask_type?, first_new?)
+                                                                                            -> sets, allowed (S A,), info (S A, 4)
     torch.ops.infgen_hip.step_score(pos, head, state, n_agents, type, shape, c1, records?, n_records?, copies=1, sweep=1,
                                     road_margin=0, types=[1, 0, 1], dt=0.5)                 -> score (S, 8), flags (S, A) uint8
     torch.ops.infgen_hip.observe_rows(pos, head, state, n_agents, type, shape, c, dt, map_pos?, map_orient?, map_type?, n_map?,
@@ -633,6 +636,78 @@ def route_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_age
 @route_mask.register_fake
 def _(pos, head, state, n_agents, type, shape, c, end_pose, records, total, copies=1, corridor=2.0, back=0.5, pace=0.0, finish=1.0,
       types=None, mask_bits=None, mask_row=None, mask_type=None, first_new=None):
+    rows = pos.shape[0] * pos.shape[2]
+    return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32),
+            pos.new_empty(rows, 4, dtype=torch.float32))
+
+
+def signal_records(lines: torch.Tensor, n_lines: torch.Tensor) -> torch.Tensor:
+    """the records of per-scene stop lines ("signal masks" of include/infgen_hip.h, ``infgen_signal_records``): ``lines`` (S0, K, 4) =
+    (ax, ay, bx, by) world coordinates, 1 <= K <= 64, ``n_lines`` (S0,) -> records (S0, K, 8)"""
+    if lines.dim() != 3 or lines.shape[2] != 4 or not 1 <= lines.shape[1] <= 64 or tuple(n_lines.shape) != tuple(lines.shape[:1]):
+        raise ValueError('signal_records takes lines (S0, K, 4) with 1 <= K <= 64 and n_lines (S0,)')
+    dev = lines.device
+    ops = _ops(dev)
+    S0, K = (int(v) for v in lines.shape[:2])
+    ln, n = _f32(lines), n_lines.to(dev, torch.int32).contiguous()
+    rec = torch.zeros(S0, K, 8, device=dev)
+    _lib.check(ops.lib.infgen_signal_records(_lib.ptr(ln), _lib.ptr(n), S0, K, _lib.ptr(rec), ops.stream), 'infgen_signal_records')
+    return rec
+
+
+@torch.library.custom_op('infgen_hip::signal_mask', mutates_args=())
+def signal_mask(pos: torch.Tensor, head: torch.Tensor, state: torch.Tensor, n_agents: torch.Tensor, type: torch.Tensor,
+                shape: torch.Tensor, c: int, end_pose: torch.Tensor, records: torch.Tensor, phase: torch.Tensor, t: int,
+                copies: int = 1, setback: float = 0.5, align: float = 0.5, types: Optional[List[int]] = None,
+                mask_bits: Optional[torch.Tensor] = None, mask_row: Optional[torch.Tensor] = None,
+                mask_type: Optional[List[int]] = None, first_new: Optional[torch.Tensor] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """the allowed-token sets of one decode step from the scene's stop lines (signal-aware decoding; "signal masks" of
+    include/infgen_hip.h, ``infgen_signal_mask``): the scene arrays and ``end_pose`` as for ``collision_mask``, ``records``
+    (S / copies, K, 8) from ``signal_records``, ``phase`` (S / copies, n_phase, K) uint8 (non-zero: closed), ``t`` the decode step
+    whose phase row t mod n_phase is read, ``types`` the (vehicle, pedestrian, cyclist) switch (None: vehicles and cyclists).
+    ``mask_bits`` / ``mask_row`` / ``mask_type``: the base sets (none: every token).  Returns the sets (S * A, token_size / 32) int32
+    words, the number of allowed tokens per row before the empty-set fallback (S * A,) and info (S * A, 4) = gap, line, flag, 0."""
+    if pos.dim() != 4 or pos.shape[3] != 2 or head.shape != pos.shape[:3] or state.shape != pos.shape[:3]:
+        raise ValueError('signal_mask takes pos (S, T, A, 2), head (S, T, A), state (S, T, A)')
+    S, T, A = (int(v) for v in pos.shape[:3])
+    if tuple(type.shape) != (S, A) or tuple(shape.shape) != (S, A, 3) or tuple(n_agents.shape) != (S,):
+        raise ValueError('signal_mask takes type (S, A), shape (S, A, 3), n_agents (S,)')
+    if first_new is not None and tuple(first_new.shape) != (S,):
+        raise ValueError('first_new must be (S,)')
+    token_size = (int(end_pose.numel()) - 4) // 12
+    if end_pose.dim() != 1 or token_size * 12 + 4 != end_pose.numel() or token_size % 32:
+        raise ValueError('end_pose is the table of collision_end_poses (12 token_size + 4 floats, token_size a multiple of 32)')
+    if copies < 1 or S % copies:
+        raise ValueError('copies must be at least 1 and divide S')
+    if records.dim() != 3 or records.shape[2] != 8 or records.shape[0] != S // copies:
+        raise ValueError('signal_mask takes records (S / copies, K, 8)')
+    K = int(records.shape[1])
+    if phase.dim() != 3 or phase.dtype != torch.uint8 or phase.shape[0] != S // copies or phase.shape[1] < 1 or phase.shape[2] != K:
+        raise ValueError('signal_mask takes phase (S / copies, n_phase >= 1, K) uint8')
+    types = [1, 0, 1] if types is None else [int(bool(v)) for v in types]
+    if len(types) != 3:
+        raise ValueError('types has three entries: vehicle, pedestrian, cyclist')
+    dev = pos.device
+    ops = _ops(dev)
+    i32 = lambda x: None if x is None else x.to(dev, torch.int32).contiguous()
+    ty = i32(type)
+    tm, _keep_mask = _token_mask(mask_bits, mask_row, mask_type, ty.reshape(-1), S * A, token_size, dev)
+    bits = torch.zeros(S * A, token_size // 32, device=dev, dtype=torch.int32)
+    count = torch.zeros(S * A, device=dev, dtype=torch.int32)
+    info = torch.zeros(S * A, 4, device=dev)
+    st, na, fn = i32(state), i32(n_agents), i32(first_new)
+    p, h, sh, ep, rc, ph = _f32(pos), _f32(head), _f32(shape), _f32(end_pose), _f32(records), phase.to(dev).contiguous()
+    _lib.check(ops.lib.infgen_signal_mask(_lib.ptr(p), _lib.ptr(h), _lib.ptr(st), _lib.ptr(na), _lib.ptr(fn), _lib.ptr(ty), _lib.ptr(sh),
+                                          S, A, T, int(c), _lib.ptr(ep), token_size, _lib.ptr(rc), _lib.ptr(ph), int(phase.shape[1]), K,
+                                          int(t), int(copies), float(setback), float(align), (C.c_int * 3)(*types), *tm[:4],
+                                          _lib.ptr(bits), _lib.ptr(count), _lib.ptr(info), ops.stream), 'infgen_signal_mask')
+    return bits, count, info
+
+
+@signal_mask.register_fake
+def _(pos, head, state, n_agents, type, shape, c, end_pose, records, phase, t, copies=1, setback=0.5, align=0.5, types=None,
+      mask_bits=None, mask_row=None, mask_type=None, first_new=None):
     rows = pos.shape[0] * pos.shape[2]
     return (pos.new_empty(rows, (end_pose.shape[0] - 4) // 12 // 32, dtype=torch.int32), pos.new_empty(rows, dtype=torch.int32),
             pos.new_empty(rows, 4, dtype=torch.float32))
