@@ -20,6 +20,7 @@ static int fail(const char* where, const char* what) {
   g_err = std::string(where) + ": " + what;
   return -1;
 }
+static int fail(const char* where, const char* prefix, const char* what) { return fail(where, (std::string(prefix) + what).c_str()); }
 static int check_launch(const char* where) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(where, hipGetErrorString(e));
@@ -48,46 +49,24 @@ struct TokenMaskDesc { const uint32_t* bits; int n_sets; const int* mask_row; in
 static TokenMaskDesc token_mask_desc(const uint32_t* bits, int n_sets, const int* mask_row, const int* mask_type, const int* type) {
   return TokenMaskDesc{bits, n_sets, mask_row, {mask_type ? mask_type[0] : -1, mask_type ? mask_type[1] : -1, mask_type ? mask_type[2] : -1}, type};
 }
-// the registered masks: slot h - 1 serves handle h (in_use false: free)
-// the collision configuration a registered mask may carry (infgen_token_mask_collision; bits == NULL: none)
-struct CollisionCfg { uint32_t* bits; const int* ident; const float* shape; const float* end_pose; int predict; float margin; int* count; };
-constexpr CollisionCfg COLLISION_NONE{nullptr, nullptr, nullptr, nullptr, 1, 0.f, nullptr};
-// the road configuration a registered mask may carry (infgen_token_mask_road; bits == NULL: none)
-struct RoadCfg {
-  uint32_t* bits; const int* ident; const float* shape; const float* end_pose; const float* paths; const float* records;
-  const int* n_records; int rec_cap, copies, sweep; float margin; int types[3]; int* count;
-};
-constexpr RoadCfg ROAD_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, nullptr};
-// the score configuration a registered mask may carry (infgen_token_mask_score; out == NULL: none)
-struct ScoreCfg {
-  float* out; int steps; unsigned char* row; const float* shape; const float* records; const int* n_records;
-  int rec_cap, copies, sweep; float margin; int types[3]; float dt;
-};
-constexpr ScoreCfg SCORE_NONE{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, 0.5f};
-// the route configuration a registered mask may carry (infgen_token_mask_route; bits == NULL: none)
-struct RouteCfg {
-  uint32_t* bits; const int* ident; const float* shape; const float* end_pose; const float* records; const float* total;
-  int P, copies; float corridor, back, pace, finish; int types[3]; int* count; float* progress;
-};
-constexpr RouteCfg ROUTE_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 2, 1, 0.f, 0.f, 0.f, 0.f, {0, 0, 0}, nullptr, nullptr};
-// the signal configuration a registered mask may carry (infgen_token_mask_signal; bits == NULL: none)
-struct SignalCfg {
-  uint32_t* bits; const int* ident; const float* shape; const float* end_pose; const float* records; const unsigned char* phase;
-  int n_phase, K, copies; float setback, align; int types[3]; int* count; float* info;
-};
-constexpr SignalCfg SIGNAL_NONE{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, 1, 0.f, 0.f, {0, 0, 0}, nullptr, nullptr};
-struct TokenMaskSlot { TokenMaskDesc d; bool in_use; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; SignalCfg signal; };
+// the registered masks: slot h - 1 serves handle h (in_use false: free).  The rider configurations a mask may carry (kernels.h, next
+// to their rules; infgen_token_mask_collision / _road / _score / _route / _signal attach them)
+struct RiderCfgs { CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; SignalCfg signal; };
+constexpr RiderCfgs CFGS_NONE{COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE, SIGNAL_NONE};
+struct TokenMaskSlot { TokenMaskDesc d; bool in_use; RiderCfgs cfg; };
 static std::mutex g_mask_mu;
 static std::vector<TokenMaskSlot> g_masks;
 // what rides on a context's decode step: the static mask as the kernels take it and the configurations of its handle
-// (validate fills it).  A new rider adds a Cfg, an args builder and one line in any().  The members up to `route` are the block
-// infgen_token_mask_riders copies out, byte for byte (RIDERS_EXPORT_BYTES); later riders stand behind it
+// (validate fills it).  A new mask rider adds to kernels.h a rule, an Args and a Cfg with its NONE, and here a member of RiderCfgs
+// and of any(), a MaskKind, a check, a Cfg constructor and its two entries, a launch, a line in validate and a stage in
+// infgen_decode_step.  The members up to `route` are the block infgen_token_mask_riders copies out, byte for byte
+// (RIDERS_EXPORT_BYTES); later riders stand behind it
 struct StepRiders {
-  TokenMaskCtl mask; CollisionCfg coll; RoadCfg road; ScoreCfg score; RouteCfg route; SignalCfg signal;
-  bool any() const { return mask.bits || coll.bits || road.bits || score.out || route.bits || signal.bits; }
+  TokenMaskCtl mask; RiderCfgs cfg;
+  bool any() const { return mask.bits || cfg.coll.bits || cfg.road.bits || cfg.score.out || cfg.route.bits || cfg.signal.bits; }
 };
-constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE, SIGNAL_NONE};
-constexpr size_t RIDERS_EXPORT_BYTES = offsetof(StepRiders, signal);
+constexpr StepRiders RIDERS_NONE{TOKEN_MASK_NONE, CFGS_NONE};
+constexpr size_t RIDERS_EXPORT_BYTES = offsetof(StepRiders, cfg) + offsetof(RiderCfgs, signal);
 // the one handle lookup: f(slot) under g_mask_mu, or the error `what` where the handle names no registered mask
 constexpr const char* NO_TOKEN_MASK = "no such token mask";
 template <class F> static int with_mask_slot(const char* where, int handle, const char* what, F f) {
@@ -120,8 +99,7 @@ extern "C" int infgen_token_mask_create(const uint32_t* mask_bits, int mask_n_se
   size_t h = 0;
   while (h < g_masks.size() && g_masks[h].in_use) ++h;
   if (h == g_masks.size()) g_masks.push_back(TokenMaskSlot{});
-  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, COLLISION_NONE, ROAD_NONE, SCORE_NONE, ROUTE_NONE,
-                             SIGNAL_NONE};
+  g_masks[h] = TokenMaskSlot{token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type), true, CFGS_NONE};
   return (int)h + 1;
 }
 extern "C" int infgen_token_mask_destroy(int handle) {
@@ -1443,50 +1421,102 @@ extern "C" int infgen_map_graph(int S, int M_cap, const int* n_map, const float*
 }
 
 // ---------------------------------------------------------------------------------- step riders: the scene they read
-// the scene arrays a rider's kernel reads, as a stand-alone entry's parameters or a context hold them (the scores read no first_new
-// and no token_size), and the fields CollisionArgs, RoadArgs and ScoreArgs share
-struct RiderScene {
-  int S, A_cap, T; const float* pos; const float* head; const int* state; const int* n_agents; const int* first_new; const int* type;
-  int token_size;
-};
-static RiderScene rider_scene(const InfgenRollout* r) {
-  return RiderScene{r->S, r->A_cap, r->T, r->pos, r->head, r->state, r->n_agents, r->first_new, r->type, r->token_size};
-}
-template <class A, class Cfg> static A rider_args(const RiderScene& sc, const Cfg& k) {
+// the one args builder of the step riders and the closed-loop operators.  head: the scene as a stand-alone entry's parameters or a
+// context give it - a SceneHead, or a mask rider's MaskHead (mask_head below); k: the configuration, which adds the shape, the rule
+// and a mask rider's tables (NoCfg: an operator without one, whose head brings the shape).  What a block holds beyond these - a
+// step, an output of the rider's own - its launch sets
+struct NoCfg {};
+template <class A, class Head, class Cfg = NoCfg> static A rider_args(const Head& head, const Cfg& k = Cfg{}) {
   A a{};
-  a.S = sc.S; a.A_cap = sc.A_cap; a.T = sc.T;
-  a.pos = sc.pos; a.head = sc.head; a.state = sc.state; a.n_agents = sc.n_agents; a.type = sc.type; a.shape = k.shape;
+  static_cast<Head&>(a) = head;
+  if constexpr (!std::is_same_v<Cfg, NoCfg>) {
+    a.shape = k.shape;
+    static_cast<decltype(Cfg::rule)&>(a) = k.rule;
+  }
+  if constexpr (std::is_same_v<Head, MaskHead>) { a.end_pose = k.end_pose; a.out_bits = k.bits; a.out_count = k.count; }
   return a;
 }
-
-// ---------------------------------------------------------------------------------- collision masks
-// the argument checks of include/infgen_hip.h ("collision masks"), the argument block of column c from a configuration (base: the
-// sets it refines) and the one launch of k_collision_mask
-static CollisionArgs collision_args(const RiderScene& sc, int c, const CollisionCfg& k, const TokenMaskCtl& base) {
-  CollisionArgs a = rider_args<CollisionArgs>(sc, k);
-  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
-  a.end_pose = k.end_pose; a.predict = k.predict; a.margin = k.margin;
-  a.base = base; a.out_bits = k.bits; a.out_count = k.count;
-  return a;
+static SceneHead scene_head(const InfgenRollout* r) {
+  return SceneHead{r->S, r->A_cap, r->T, r->pos, r->head, r->state, r->n_agents, r->type, nullptr};
 }
-static int collision_check(const char* where, int predict, float margin, const float* shape, const float* end_pose, const uint32_t* bits) {
-  if (!std::isfinite(margin) || margin < 0.f) return fail(where, "collision mask: margin must be finite and >= 0");
-  if (predict != 0 && predict != 1) return fail(where, "collision mask: predict must be 0 or 1");
-  if (!shape) return fail(where, "collision mask: needs the rows' shape array [S][A_cap][3]");
-  if (!end_pose) return fail(where, "collision mask: needs the end-pose table of infgen_collision_end_poses");
-  if (!bits) return fail(where, "collision mask: needs the output table");
-  if ((reinterpret_cast<uintptr_t>(bits) | reinterpret_cast<uintptr_t>(end_pose)) & 15)
-    return fail(where, "collision mask: the tables must be 16-byte aligned");
+// column c of a scene under the sets `base`, for a mask rider to refine
+static MaskHead mask_head(const SceneHead& sc, int c, const int* first_new, int token_size, const TokenMaskCtl& base) {
+  MaskHead h{};
+  static_cast<SceneHead&>(h) = sc;
+  h.c = c; h.first_new = first_new; h.token_size = token_size; h.base = base;
+  return h;
+}
+// ... as a stand-alone entry's parameters name it: the static mask comes as the C ABI passes it
+static int entry_head(const char* me, const SceneHead& sc, int c, const int* first_new, int token_size, const uint32_t* mask_bits,
+                      int mask_n_sets, const int* mask_row, const int* mask_type, MaskHead* out) {
+  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, sc.type);
+  TokenMaskCtl base;
+  RET_IF(token_mask_ctl(me, &md, token_size, &base));
+  *out = mask_head(sc, c, first_new, token_size, base);
   return 0;
 }
-static int launch_collision(const char* where, CollisionArgs a, void* stream) {
-  RET_IF(collision_check(where, a.predict, a.margin, a.shape, a.end_pose, a.out_bits));
-  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "collision mask: S, A_cap and T must be positive");
-  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "collision mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
-  if (a.c < 0 || a.c >= a.T) return fail(where, "collision mask: column outside [0, T)");
-  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
-    return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
-  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "collision mask: null scene array");
+
+// a mask rider's name in the error texts, and which of the optional geometry checks its launches make
+enum { GEO_CAP = 1, GEO_ROWS = 2 };
+struct MaskKind { const char* prefix; int checks; };
+constexpr MaskKind COLLISION_KIND{"collision mask: ", GEO_CAP}, ROAD_KIND{"road mask: ", GEO_ROWS},
+    ROUTE_KIND{"route mask: ", GEO_CAP | GEO_ROWS}, SIGNAL_KIND{"signal mask: ", GEO_CAP | GEO_ROWS};
+constexpr const char* TOKEN_SIZE_UNFIT = "token_size must be a multiple of 32, at most 4096";
+static bool token_size_unfit(int token_size) { return token_size % 32 || token_size > 64 * 32 * RIDER_WPL; }
+// the one geometry check of a mask rider's launch (copies: 1 for a rider without scene groups)
+static int mask_geometry(const char* where, const MaskKind& k, const MaskHead& a, int copies) {
+  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, k.prefix, "S, A_cap and T must be positive");
+  if ((k.checks & GEO_CAP) && a.A_cap > MAX_SCENE_AGENTS) return fail(where, k.prefix, "A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (a.S % copies) return fail(where, k.prefix, "S must be a multiple of copies");
+  if (a.c < 0 || a.c >= a.T) return fail(where, k.prefix, "column outside [0, T)");
+  if (a.token_size <= 0 || token_size_unfit(a.token_size)) return fail(where, k.prefix, TOKEN_SIZE_UNFIT);
+  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, k.prefix, "null scene array");
+  if ((k.checks & GEO_ROWS) && (long long)a.S * a.A_cap > 0x7fffffffLL) return fail(where, k.prefix, "too many rows");
+  return 0;
+}
+// what validate asks of a context that carries the rider
+static int mask_fits(const char* where, const MaskKind& k, const InfgenRollout* r, int copies) {
+  if (token_size_unfit(r->token_size)) return fail(where, k.prefix, TOKEN_SIZE_UNFIT);
+  if (r->S % copies) return fail(where, k.prefix, "S must be a multiple of copies");
+  return 0;
+}
+// the launch of a kernel that takes the S * A_cap rows of the layout one wave each
+template <class A> static int launch_rows(const char* where, void (*kernel)(A), const A& a, void* stream) {
+  const long long rows = (long long)a.S * a.A_cap;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
+  return check_launch(where);
+}
+// the three-entry type switch a configuration holds by value (NULL: the check that follows refuses it)
+static const int* types_or_zeros(const int* types) {
+  static const int zeros[3] = {0, 0, 0};
+  return types ? types : zeros;
+}
+static bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) != 0;
+}
+
+// Every rider below has the same parts.  x_check: what include/infgen_hip.h asks of a configuration (types: the caller's pointer
+// behind rule.types); x_cfg: the one place a configuration is built and checked - by the stand-alone entry (ident NULL) and when it
+// is attached to a handle, so a launch meets checked configurations only; launch_mask / launch_score: the geometry and the one
+// launch of the kernel (t: the decode step, which the signal rule reads)
+// ---------------------------------------------------------------------------------- collision masks
+static int collision_check(const char* where, const CollisionCfg& k) {
+  if (!std::isfinite(k.rule.margin) || k.rule.margin < 0.f) return fail(where, "collision mask: margin must be finite and >= 0");
+  if (k.rule.predict != 0 && k.rule.predict != 1) return fail(where, "collision mask: predict must be 0 or 1");
+  if (!k.shape) return fail(where, "collision mask: needs the rows' shape array [S][A_cap][3]");
+  if (!k.end_pose) return fail(where, "collision mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!k.bits) return fail(where, "collision mask: needs the output table");
+  if (misaligned16(k.bits, k.end_pose)) return fail(where, "collision mask: the tables must be 16-byte aligned");
+  return 0;
+}
+static int collision_cfg(const char* where, uint32_t* bits, const int* ident, const float* shape, const float* end_pose, int predict,
+                         float margin, int* count, CollisionCfg* out) {
+  *out = CollisionCfg{bits, ident, shape, end_pose, {predict, margin}, count};
+  return collision_check(where, *out);
+}
+static int launch_mask(const char* where, const MaskHead& h, const CollisionCfg& k, int t, void* stream) {
+  RET_IF(mask_geometry(where, COLLISION_KIND, h, 1));
+  CollisionArgs a = rider_args<CollisionArgs>(h, k);
   // few rows: one row per wave and workgroup round; many: 16 rows share one staging of their scene's obstacles
   int per = knob::cm_rows > 0 ? knob::cm_rows : ((long long)a.S * a.A_cap > 4096 ? 4 * RIDER_WAVES : RIDER_WAVES);
   per = ceil_div(per, RIDER_WAVES) * RIDER_WAVES;
@@ -1510,69 +1540,54 @@ extern "C" int infgen_collision_mask(const float* pos, const float* head, const 
                                      int token_size, int predict, float margin, const uint32_t* mask_bits, int mask_n_sets,
                                      const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, void* stream) {
   const char* me = "infgen_collision_mask";
-  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
-  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  TokenMaskCtl base;
-  RET_IF(token_mask_ctl(me, &md, token_size, &base));
-  return launch_collision(me, collision_args(sc, c, CollisionCfg{out_bits, nullptr, shape, end_pose, predict, margin, out_count}, base), stream);
+  MaskHead h;
+  RET_IF(entry_head(me, SceneHead{S, A_cap, T, pos, head, state, n_agents, type}, c, first_new, token_size, mask_bits, mask_n_sets, mask_row,
+                    mask_type, &h));
+  CollisionCfg cfg;
+  RET_IF(collision_cfg(me, out_bits, nullptr, shape, end_pose, predict, margin, out_count, &cfg));
+  return launch_mask(me, h, cfg, 0, stream);
 }
 
 extern "C" int infgen_token_mask_collision(int handle, uint32_t* dyn_bits, const int* identity_row, const float* shape,
                                            const float* end_pose, int predict, float margin, int* count) {
   const char* me = "infgen_token_mask_collision";
+  CollisionCfg cfg = COLLISION_NONE;
   if (dyn_bits) {
-    RET_IF(collision_check(me, predict, margin, shape, end_pose, dyn_bits));
+    RET_IF(collision_cfg(me, dyn_bits, identity_row, shape, end_pose, predict, margin, count, &cfg));
     if (!identity_row) return fail(me, "collision mask: needs the identity selectors [S * A_cap]");
   }
-  const CollisionCfg cfg = dyn_bits ? CollisionCfg{dyn_bits, identity_row, shape, end_pose, predict, margin, count} : COLLISION_NONE;
-  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.coll = cfg; });
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.cfg.coll = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- road masks
-// the argument checks of include/infgen_hip.h ("road masks") and the one launch of k_road_mask
-static bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) != 0;
-}
 // what road masks and step scores ask alike of a configuration that reads the road table, in the order both ask it.  (Each keeps
 // its margin check in front of this - the scores' dt check sits between the two - and its types check behind its own pointers')
-static int road_table_check(const char* where, const char* prefix, int sweep, int copies, int rec_cap, const float* shape) {
-  const char* what = sweep != 0 && sweep != 1 ? "sweep must be 0 or 1" : copies < 1 ? "copies must be at least 1"
-                     : rec_cap < 0 ? "negative record capacity" : !shape ? "needs the rows' shape array [S][A_cap][3]" : nullptr;
-  return what ? fail(where, (std::string(prefix) + what).c_str()) : 0;
+template <class Rule> static int road_table_check(const char* where, const char* prefix, const Rule& r, const float* shape) {
+  const char* what = r.sweep != 0 && r.sweep != 1 ? "sweep must be 0 or 1" : r.copies < 1 ? "copies must be at least 1"
+                     : r.rec_cap < 0 ? "negative record capacity" : !shape ? "needs the rows' shape array [S][A_cap][3]" : nullptr;
+  return what ? fail(where, prefix, what) : 0;
 }
-static int road_check(const char* where, int sweep, float margin, int copies, int rec_cap, const float* shape, const float* end_pose,
-                      const float* paths, const float* records, const int* n_records, const int* types, const uint32_t* bits) {
-  if (!std::isfinite(margin) || margin < 0.f) return fail(where, "road mask: margin must be finite and >= 0");
-  RET_IF(road_table_check(where, "road mask: ", sweep, copies, rec_cap, shape));
-  if (!end_pose) return fail(where, "road mask: needs the end-pose table of infgen_collision_end_poses");
-  if (!paths) return fail(where, "road mask: needs the path table of infgen_road_paths");
-  if (!records || !n_records) return fail(where, "road mask: needs the record table and its counts");
+static int road_check(const char* where, const RoadCfg& k, const int* types) {
+  if (!std::isfinite(k.rule.margin) || k.rule.margin < 0.f) return fail(where, "road mask: margin must be finite and >= 0");
+  RET_IF(road_table_check(where, "road mask: ", k.rule, k.shape));
+  if (!k.end_pose) return fail(where, "road mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!k.rule.paths) return fail(where, "road mask: needs the path table of infgen_road_paths");
+  if (!k.rule.records || !k.rule.n_records) return fail(where, "road mask: needs the record table and its counts");
   if (!types) return fail(where, "road mask: needs the three-entry type switch");
-  if (!bits) return fail(where, "road mask: needs the output table");
-  if (misaligned16(bits, end_pose, paths, records)) return fail(where, "road mask: the tables must be 16-byte aligned");
+  if (!k.bits) return fail(where, "road mask: needs the output table");
+  if (misaligned16(k.bits, k.end_pose, k.rule.paths, k.rule.records)) return fail(where, "road mask: the tables must be 16-byte aligned");
   return 0;
 }
-static RoadArgs road_args(const RiderScene& sc, int c, const RoadCfg& k, const TokenMaskCtl& base) {
-  RoadArgs a = rider_args<RoadArgs>(sc, k);
-  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
-  a.end_pose = k.end_pose; a.paths = k.paths; a.records = k.records; a.n_records = k.n_records; a.rec_cap = k.rec_cap;
-  a.copies = k.copies; a.sweep = k.sweep; a.margin = k.margin;
-  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
-  a.base = base; a.out_bits = k.bits; a.out_count = k.count;
-  return a;
+static int road_cfg(const char* where, uint32_t* bits, const int* ident, const float* shape, const float* end_pose, const float* paths,
+                    const float* records, const int* n_records, int rec_cap, int copies, int sweep, float margin, const int* types,
+                    int* count, RoadCfg* out) {
+  const int* ty = types_or_zeros(types);
+  *out = RoadCfg{bits, ident, shape, end_pose, {paths, records, n_records, rec_cap, copies, sweep, margin, {ty[0], ty[1], ty[2]}}, count};
+  return road_check(where, *out, types);
 }
-static int launch_road(const char* where, const RoadArgs& a, void* stream) {
-  RET_IF(road_check(where, a.sweep, a.margin, a.copies, a.rec_cap, a.shape, a.end_pose, a.paths, a.records, a.n_records, a.types, a.out_bits));
-  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "road mask: S, A_cap and T must be positive");
-  if (a.S % a.copies) return fail(where, "road mask: S must be a multiple of copies");
-  if (a.c < 0 || a.c >= a.T) return fail(where, "road mask: column outside [0, T)");
-  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
-    return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
-  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "road mask: null scene array");
-  const long long rows = (long long)a.S * a.A_cap;
-  if (rows > 0x7fffffffLL) return fail(where, "road mask: too many rows");
-  hipLaunchKernelGGL(k_road_mask, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
-  return check_launch(where);
+static int launch_mask(const char* where, const MaskHead& h, const RoadCfg& k, int t, void* stream) {
+  RET_IF(mask_geometry(where, ROAD_KIND, h, k.rule.copies));
+  return launch_rows(where, k_road_mask, rider_args<RoadArgs>(h, k), stream);
 }
 
 extern "C" int infgen_road_records_from_map(const float* map_pos, const float* map_orient, const long long* map_type, const long long* map_tok,
@@ -1613,14 +1628,12 @@ extern "C" int infgen_road_mask(const float* pos, const float* head, const int* 
                                 int sweep, float margin, const int* types, const uint32_t* mask_bits, int mask_n_sets,
                                 const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, void* stream) {
   const char* me = "infgen_road_mask";
-  RET_IF(road_check(me, sweep, margin, copies, rec_cap, shape, end_pose, paths, records, n_records, types, out_bits));
-  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
-  const RoadCfg cfg{out_bits, nullptr, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin,
-                    {types[0], types[1], types[2]}, out_count};
-  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  TokenMaskCtl base;
-  RET_IF(token_mask_ctl(me, &md, token_size, &base));
-  return launch_road(me, road_args(sc, c, cfg, base), stream);
+  RoadCfg cfg;
+  RET_IF(road_cfg(me, out_bits, nullptr, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin, types, out_count, &cfg));
+  MaskHead h;
+  RET_IF(entry_head(me, SceneHead{S, A_cap, T, pos, head, state, n_agents, type}, c, first_new, token_size, mask_bits, mask_n_sets, mask_row,
+                    mask_type, &h));
+  return launch_mask(me, h, cfg, 0, stream);
 }
 
 extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int* identity_row, const float* shape, const float* end_pose,
@@ -1629,57 +1642,41 @@ extern "C" int infgen_token_mask_road(int handle, uint32_t* road_bits, const int
   const char* me = "infgen_token_mask_road";
   RoadCfg cfg = ROAD_NONE;
   if (road_bits) {
-    RET_IF(road_check(me, sweep, margin, copies, rec_cap, shape, end_pose, paths, records, n_records, types, road_bits));
+    RET_IF(road_cfg(me, road_bits, identity_row, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin, types, count, &cfg));
     if (!identity_row) return fail(me, "road mask: needs the identity selectors [S * A_cap]");
-    cfg = RoadCfg{road_bits, identity_row, shape, end_pose, paths, records, n_records, rec_cap, copies, sweep, margin,
-                  {types[0], types[1], types[2]}, count};
   }
-  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.road = cfg; });
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.cfg.road = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- route masks
-// the argument checks of include/infgen_hip.h ("route masks") - route_check: what a configuration is checked for once, by the
-// stand-alone entry and when it is attached to a handle; launch_route: the geometry - and the one launch of k_route_mask
-static int route_check(const char* where, int P, int copies, float corridor, float back, float pace, float finish, const float* shape,
-                       const float* end_pose, const float* records, const float* total, const int* types, const uint32_t* bits,
-                       const float* progress) {
-  if (!std::isfinite(corridor) || corridor < 0.f) return fail(where, "route mask: corridor must be finite and >= 0");
-  if (!std::isfinite(back) || back < 0.f) return fail(where, "route mask: back must be finite and >= 0");
-  if (!std::isfinite(finish) || finish < 0.f) return fail(where, "route mask: finish must be finite and >= 0");
-  if (!(pace >= 0.f && pace <= 1.f)) return fail(where, "route mask: pace must be in [0, 1]");
-  if (P < 2 || P > RT_MAX_POINTS) return fail(where, "route mask: P must be in 2..32");
-  if (copies < 1) return fail(where, "route mask: copies must be at least 1");
-  if (!shape) return fail(where, "route mask: needs the rows' shape array [S][A_cap][3]");
-  if (!end_pose) return fail(where, "route mask: needs the end-pose table of infgen_collision_end_poses");
-  if (!records || !total) return fail(where, "route mask: needs the record table and the routes' lengths");
+static int route_check(const char* where, const RouteCfg& k, const int* types) {
+  const RouteRule& r = k.rule;
+  if (!std::isfinite(r.corridor) || r.corridor < 0.f) return fail(where, "route mask: corridor must be finite and >= 0");
+  if (!std::isfinite(r.back) || r.back < 0.f) return fail(where, "route mask: back must be finite and >= 0");
+  if (!std::isfinite(r.finish) || r.finish < 0.f) return fail(where, "route mask: finish must be finite and >= 0");
+  if (!(r.pace >= 0.f && r.pace <= 1.f)) return fail(where, "route mask: pace must be in [0, 1]");
+  if (r.P < 2 || r.P > RT_MAX_POINTS) return fail(where, "route mask: P must be in 2..32");
+  if (r.copies < 1) return fail(where, "route mask: copies must be at least 1");
+  if (!k.shape) return fail(where, "route mask: needs the rows' shape array [S][A_cap][3]");
+  if (!k.end_pose) return fail(where, "route mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!r.records || !r.total) return fail(where, "route mask: needs the record table and the routes' lengths");
   if (!types) return fail(where, "route mask: needs the three-entry type switch");
-  if (!bits) return fail(where, "route mask: needs the output table");
-  if (misaligned16(bits, end_pose, records, progress)) return fail(where, "route mask: the tables must be 16-byte aligned");
+  if (!k.bits) return fail(where, "route mask: needs the output table");
+  if (misaligned16(k.bits, k.end_pose, r.records, k.progress)) return fail(where, "route mask: the tables must be 16-byte aligned");
   return 0;
 }
-static RouteArgs route_args(const RiderScene& sc, int c, const RouteCfg& k, const TokenMaskCtl& base) {
-  RouteArgs a = rider_args<RouteArgs>(sc, k);
-  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
-  a.end_pose = k.end_pose; a.records = k.records; a.total = k.total; a.P = k.P; a.copies = k.copies;
-  a.corridor = k.corridor; a.back = k.back; a.pace = k.pace; a.finish = k.finish;
-  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
-  a.base = base; a.out_bits = k.bits; a.out_count = k.count; a.out_progress = k.progress;
-  return a;
+static int route_cfg(const char* where, uint32_t* bits, const int* ident, const float* shape, const float* end_pose, const float* records,
+                     const float* total, int P, int copies, float corridor, float back, float pace, float finish, const int* types,
+                     int* count, float* progress, RouteCfg* out) {
+  const int* ty = types_or_zeros(types);
+  *out = RouteCfg{bits, ident, shape, end_pose, {records, total, P, copies, corridor, back, pace, finish, {ty[0], ty[1], ty[2]}}, count, progress};
+  return route_check(where, *out, types);
 }
-static int launch_route(const char* where, const RouteArgs& a, void* stream) {
-  RET_IF(route_check(where, a.P, a.copies, a.corridor, a.back, a.pace, a.finish, a.shape, a.end_pose, a.records, a.total, a.types,
-                     a.out_bits, a.out_progress));
-  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "route mask: S, A_cap and T must be positive");
-  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "route mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
-  if (a.S % a.copies) return fail(where, "route mask: S must be a multiple of copies");
-  if (a.c < 0 || a.c >= a.T) return fail(where, "route mask: column outside [0, T)");
-  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
-    return fail(where, "route mask: token_size must be a multiple of 32, at most 4096");
-  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "route mask: null scene array");
-  const long long rows = (long long)a.S * a.A_cap;
-  if (rows > 0x7fffffffLL) return fail(where, "route mask: too many rows");
-  hipLaunchKernelGGL(k_route_mask, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
-  return check_launch(where);
+static int launch_mask(const char* where, const MaskHead& h, const RouteCfg& k, int t, void* stream) {
+  RET_IF(mask_geometry(where, ROUTE_KIND, h, k.rule.copies));
+  RouteArgs a = rider_args<RouteArgs>(h, k);
+  a.out_progress = k.progress;
+  return launch_rows(where, k_route_mask, a, stream);
 }
 
 extern "C" int infgen_route_records(const float* routes, const int* n_points, int S, int A_cap, int P, float* records, float* total,
@@ -1704,14 +1701,13 @@ extern "C" int infgen_route_mask(const float* pos, const float* head, const int*
                                  const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, float* out_progress,
                                  void* stream) {
   const char* me = "infgen_route_mask";
-  RET_IF(route_check(me, P, copies, corridor, back, pace, finish, shape, end_pose, records, total, types, out_bits, out_progress));
-  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
-  const RouteCfg cfg{out_bits, nullptr, shape, end_pose, records, total, P, copies, corridor, back, pace, finish,
-                     {types[0], types[1], types[2]}, out_count, out_progress};
-  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  TokenMaskCtl base;
-  RET_IF(token_mask_ctl(me, &md, token_size, &base));
-  return launch_route(me, route_args(sc, c, cfg, base), stream);
+  RouteCfg cfg;
+  RET_IF(route_cfg(me, out_bits, nullptr, shape, end_pose, records, total, P, copies, corridor, back, pace, finish, types, out_count,
+                   out_progress, &cfg));
+  MaskHead h;
+  RET_IF(entry_head(me, SceneHead{S, A_cap, T, pos, head, state, n_agents, type}, c, first_new, token_size, mask_bits, mask_n_sets, mask_row,
+                    mask_type, &h));
+  return launch_mask(me, h, cfg, 0, stream);
 }
 
 extern "C" int infgen_token_mask_route(int handle, uint32_t* route_bits, const int* identity_row, const float* shape, const float* end_pose,
@@ -1720,57 +1716,42 @@ extern "C" int infgen_token_mask_route(int handle, uint32_t* route_bits, const i
   const char* me = "infgen_token_mask_route";
   RouteCfg cfg = ROUTE_NONE;
   if (route_bits) {
-    RET_IF(route_check(me, P, copies, corridor, back, pace, finish, shape, end_pose, records, total, types, route_bits, progress));
+    RET_IF(route_cfg(me, route_bits, identity_row, shape, end_pose, records, total, P, copies, corridor, back, pace, finish, types, count,
+                     progress, &cfg));
     if (!identity_row) return fail(me, "route mask: needs the identity selectors [S * A_cap]");
-    cfg = RouteCfg{route_bits, identity_row, shape, end_pose, records, total, P, copies, corridor, back, pace, finish,
-                   {types[0], types[1], types[2]}, count, progress};
   }
-  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.route = cfg; });
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.cfg.route = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- signal masks
-// the argument checks of include/infgen_hip.h ("signal masks") - signal_check: what a configuration is checked for once, by the
-// stand-alone entry and when it is attached to a handle; launch_signal: the geometry - and the one launch of k_signal_mask
-static int signal_check(const char* where, int K, int n_phase, int copies, float setback, float align, const float* shape,
-                        const float* end_pose, const float* records, const unsigned char* phase, const int* types, const uint32_t* bits,
-                        const float* info) {
-  if (!std::isfinite(setback) || setback < 0.f) return fail(where, "signal mask: setback must be finite and >= 0");
-  if (!(align >= -1.f && align <= 1.f)) return fail(where, "signal mask: align must be in [-1, 1]");
-  if (K < 1 || K > SG_MAX_LINES) return fail(where, "signal mask: K must be in 1..64");
-  if (n_phase < 1) return fail(where, "signal mask: n_phase must be at least 1");
-  if (copies < 1) return fail(where, "signal mask: copies must be at least 1");
-  if (!shape) return fail(where, "signal mask: needs the rows' shape array [S][A_cap][3]");
-  if (!end_pose) return fail(where, "signal mask: needs the end-pose table of infgen_collision_end_poses");
-  if (!records || !phase) return fail(where, "signal mask: needs the record table and the phase table");
+static int signal_check(const char* where, const SignalCfg& k, const int* types) {
+  const SignalRule& r = k.rule;
+  if (!std::isfinite(r.setback) || r.setback < 0.f) return fail(where, "signal mask: setback must be finite and >= 0");
+  if (!(r.align >= -1.f && r.align <= 1.f)) return fail(where, "signal mask: align must be in [-1, 1]");
+  if (r.K < 1 || r.K > SG_MAX_LINES) return fail(where, "signal mask: K must be in 1..64");
+  if (r.n_phase < 1) return fail(where, "signal mask: n_phase must be at least 1");
+  if (r.copies < 1) return fail(where, "signal mask: copies must be at least 1");
+  if (!k.shape) return fail(where, "signal mask: needs the rows' shape array [S][A_cap][3]");
+  if (!k.end_pose) return fail(where, "signal mask: needs the end-pose table of infgen_collision_end_poses");
+  if (!r.records || !r.phase) return fail(where, "signal mask: needs the record table and the phase table");
   if (!types) return fail(where, "signal mask: needs the three-entry type switch");
-  if (!bits) return fail(where, "signal mask: needs the output table");
-  if (misaligned16(bits, end_pose, records, info)) return fail(where, "signal mask: the tables must be 16-byte aligned");
+  if (!k.bits) return fail(where, "signal mask: needs the output table");
+  if (misaligned16(k.bits, k.end_pose, r.records, k.info)) return fail(where, "signal mask: the tables must be 16-byte aligned");
   return 0;
 }
-static SignalArgs signal_args(const RiderScene& sc, int c, int t, const SignalCfg& k, const TokenMaskCtl& base) {
-  SignalArgs a = rider_args<SignalArgs>(sc, k);
-  a.c = c; a.first_new = sc.first_new; a.token_size = sc.token_size;
-  a.end_pose = k.end_pose; a.records = k.records; a.phase = k.phase; a.n_phase = k.n_phase; a.K = k.K; a.t = t; a.copies = k.copies;
-  a.setback = k.setback; a.align = k.align;
-  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
-  a.base = base; a.out_bits = k.bits; a.out_count = k.count; a.out_info = k.info;
-  return a;
+static int signal_cfg(const char* where, uint32_t* bits, const int* ident, const float* shape, const float* end_pose, const float* records,
+                      const unsigned char* phase, int n_phase, int K, int copies, float setback, float align, const int* types, int* count,
+                      float* info, SignalCfg* out) {
+  const int* ty = types_or_zeros(types);
+  *out = SignalCfg{bits, ident, shape, end_pose, {records, phase, n_phase, K, copies, setback, align, {ty[0], ty[1], ty[2]}}, count, info};
+  return signal_check(where, *out, types);
 }
-static int launch_signal(const char* where, const SignalArgs& a, void* stream) {
-  RET_IF(signal_check(where, a.K, a.n_phase, a.copies, a.setback, a.align, a.shape, a.end_pose, a.records, a.phase, a.types, a.out_bits,
-                      a.out_info));
-  if (a.t < 0) return fail(where, "signal mask: step t must be >= 0");
-  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "signal mask: S, A_cap and T must be positive");
-  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "signal mask: A_cap exceeds INFGEN_Q_MAX_AGENTS");
-  if (a.S % a.copies) return fail(where, "signal mask: S must be a multiple of copies");
-  if (a.c < 0 || a.c >= a.T) return fail(where, "signal mask: column outside [0, T)");
-  if (a.token_size <= 0 || a.token_size % 32 || a.token_size > 64 * 32 * RIDER_WPL)
-    return fail(where, "signal mask: token_size must be a multiple of 32, at most 4096");
-  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "signal mask: null scene array");
-  const long long rows = (long long)a.S * a.A_cap;
-  if (rows > 0x7fffffffLL) return fail(where, "signal mask: too many rows");
-  hipLaunchKernelGGL(k_signal_mask, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
-  return check_launch(where);
+static int launch_mask(const char* where, const MaskHead& h, const SignalCfg& k, int t, void* stream) {
+  if (t < 0) return fail(where, "signal mask: step t must be >= 0");
+  RET_IF(mask_geometry(where, SIGNAL_KIND, h, k.rule.copies));
+  SignalArgs a = rider_args<SignalArgs>(h, k);
+  a.t = t; a.out_info = k.info;
+  return launch_rows(where, k_signal_mask, a, stream);
 }
 
 extern "C" int infgen_signal_records(const float* lines, const int* n_lines, int S0, int K, float* records, void* stream) {
@@ -1794,14 +1775,13 @@ extern "C" int infgen_signal_mask(const float* pos, const float* head, const int
                                   const int* mask_row, const int* mask_type, uint32_t* out_bits, int* out_count, float* out_info,
                                   void* stream) {
   const char* me = "infgen_signal_mask";
-  RET_IF(signal_check(me, K, n_phase, copies, setback, align, shape, end_pose, records, phase, types, out_bits, out_info));
-  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, first_new, type, token_size};
-  const SignalCfg cfg{out_bits, nullptr, shape, end_pose, records, phase, n_phase, K, copies, setback, align,
-                      {types[0], types[1], types[2]}, out_count, out_info};
-  const TokenMaskDesc md = token_mask_desc(mask_bits, mask_n_sets, mask_row, mask_type, type);
-  TokenMaskCtl base;
-  RET_IF(token_mask_ctl(me, &md, token_size, &base));
-  return launch_signal(me, signal_args(sc, c, t, cfg, base), stream);
+  SignalCfg cfg;
+  RET_IF(signal_cfg(me, out_bits, nullptr, shape, end_pose, records, phase, n_phase, K, copies, setback, align, types, out_count, out_info,
+                    &cfg));
+  MaskHead h;
+  RET_IF(entry_head(me, SceneHead{S, A_cap, T, pos, head, state, n_agents, type}, c, first_new, token_size, mask_bits, mask_n_sets, mask_row,
+                    mask_type, &h));
+  return launch_mask(me, h, cfg, t, stream);
 }
 
 extern "C" int infgen_token_mask_signal(int handle, uint32_t* signal_bits, const int* identity_row, const float* shape,
@@ -1810,45 +1790,43 @@ extern "C" int infgen_token_mask_signal(int handle, uint32_t* signal_bits, const
   const char* me = "infgen_token_mask_signal";
   SignalCfg cfg = SIGNAL_NONE;
   if (signal_bits) {
-    RET_IF(signal_check(me, K, n_phase, copies, setback, align, shape, end_pose, records, phase, types, signal_bits, info));
+    RET_IF(signal_cfg(me, signal_bits, identity_row, shape, end_pose, records, phase, n_phase, K, copies, setback, align, types, count, info,
+                      &cfg));
     if (!identity_row) return fail(me, "signal mask: needs the identity selectors [S * A_cap]");
-    cfg = SignalCfg{signal_bits, identity_row, shape, end_pose, records, phase, n_phase, K, copies, setback, align,
-                    {types[0], types[1], types[2]}, count, info};
   }
-  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.signal = cfg; });
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.cfg.signal = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- step scores
-// the argument checks of include/infgen_hip.h ("step scores") - score_check: what a configuration is checked for once, by the
-// stand-alone entry and when it is attached to a handle; launch_score: the geometry - and the one launch of k_step_score
-static int score_check(const char* where, int sweep, float margin, int copies, int rec_cap, const float* shape, const float* records,
-                       const int* n_records, const int* types, float dt, const float* out) {
-  if (!std::isfinite(margin) || margin < 0.f) return fail(where, "step score: road_margin must be finite and >= 0");
-  if (!std::isfinite(dt) || !(dt > 0.f)) return fail(where, "step score: dt must be finite and > 0");
-  RET_IF(road_table_check(where, "step score: ", sweep, copies, rec_cap, shape));
+static int score_check(const char* where, const ScoreCfg& k, const int* types) {
+  const ScoreRule& r = k.rule;
+  if (!std::isfinite(r.margin) || r.margin < 0.f) return fail(where, "step score: road_margin must be finite and >= 0");
+  if (!std::isfinite(r.dt) || !(r.dt > 0.f)) return fail(where, "step score: dt must be finite and > 0");
+  RET_IF(road_table_check(where, "step score: ", r, k.shape));
   if (!types) return fail(where, "step score: needs the three-entry type switch");
-  if (!out) return fail(where, "step score: needs the output [S][..][8]");
-  if (reinterpret_cast<uintptr_t>(out) & 31) return fail(where, "step score: the output must be 32-byte aligned");
-  if (records && !n_records) return fail(where, "step score: a record table needs its counts");
-  if (misaligned16(records)) return fail(where, "step score: the record table must be 16-byte aligned");
+  if (!k.out) return fail(where, "step score: needs the output [S][..][8]");
+  if (reinterpret_cast<uintptr_t>(k.out) & 31) return fail(where, "step score: the output must be 32-byte aligned");
+  if (r.records && !r.n_records) return fail(where, "step score: a record table needs its counts");
+  if (misaligned16(r.records)) return fail(where, "step score: the record table must be 16-byte aligned");
   return 0;
 }
-// column c1 scored into the slots' 8 floats at out + s * out_stride (a context: step t's slice of the configuration's log)
-static ScoreArgs score_args(const RiderScene& sc, int c1, const ScoreCfg& k, float* out, long long out_stride) {
-  ScoreArgs a = rider_args<ScoreArgs>(sc, k);
-  a.c1 = c1;
-  a.records = k.records; a.n_records = k.n_records; a.rec_cap = k.rec_cap; a.copies = k.copies; a.sweep = k.sweep; a.margin = k.margin;
-  for (int i = 0; i < 3; ++i) a.types[i] = k.types[i];
-  a.dt = k.dt; a.out = out; a.out_stride = out_stride; a.out_row = k.row;
-  return a;
+// (out, steps: the log of a handle's configuration; a stand-alone entry's holds its output and no steps)
+static int score_cfg(const char* where, float* out, int steps, unsigned char* row, const float* shape, const float* records,
+                     const int* n_records, int rec_cap, int copies, int sweep, float margin, const int* types, float dt, ScoreCfg* cfg) {
+  const int* ty = types_or_zeros(types);
+  *cfg = ScoreCfg{out, steps, row, shape, {records, n_records, rec_cap, copies, sweep, margin, {ty[0], ty[1], ty[2]}, dt}};
+  return score_check(where, *cfg, types);
 }
-static int launch_score(const char* where, const ScoreArgs& a, void* stream) {
-  if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "step score: S, A_cap and T must be positive");
-  if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "step score: A_cap exceeds INFGEN_Q_MAX_AGENTS");
-  if (a.S % a.copies) return fail(where, "step score: S must be a multiple of copies");
-  if (a.c1 < 0 || a.c1 >= a.T) return fail(where, "step score: column outside [0, T)");
-  if (a.out_stride < 8 || a.out_stride % 8) return fail(where, "step score: the output stride must be a positive multiple of 8 floats");
-  if (!a.pos || !a.head || !a.state || !a.n_agents || !a.type) return fail(where, "step score: null scene array");
+// column c1 scored into the slots' 8 floats at out + s * out_stride (a context: step t's slice of the configuration's log)
+static int launch_score(const char* where, const SceneHead& sc, int c1, const ScoreCfg& k, float* out, long long out_stride, void* stream) {
+  if (sc.S <= 0 || sc.A_cap <= 0 || sc.T <= 0) return fail(where, "step score: S, A_cap and T must be positive");
+  if (sc.A_cap > MAX_SCENE_AGENTS) return fail(where, "step score: A_cap exceeds INFGEN_Q_MAX_AGENTS");
+  if (sc.S % k.rule.copies) return fail(where, "step score: S must be a multiple of copies");
+  if (c1 < 0 || c1 >= sc.T) return fail(where, "step score: column outside [0, T)");
+  if (out_stride < 8 || out_stride % 8) return fail(where, "step score: the output stride must be a positive multiple of 8 floats");
+  if (!sc.pos || !sc.head || !sc.state || !sc.n_agents || !sc.type) return fail(where, "step score: null scene array");
+  ScoreArgs a = rider_args<ScoreArgs>(sc, k);
+  a.c1 = c1; a.out = out; a.out_stride = out_stride; a.out_row = k.row;
   hipLaunchKernelGGL(k_step_score, dim3((unsigned)a.S), dim3(SC_NT), 0, (hipStream_t)stream, a);
   return check_launch(where);
 }
@@ -1858,10 +1836,9 @@ extern "C" int infgen_step_score(const float* pos, const float* head, const int*
                                  int rec_cap, int copies, int sweep, float road_margin, const int* types, float dt, float* out_score,
                                  long long out_stride, unsigned char* out_row, void* stream) {
   const char* me = "infgen_step_score";
-  RET_IF(score_check(me, sweep, road_margin, copies, rec_cap, shape, records, n_records, types, dt, out_score));
-  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, nullptr, type, 0};
-  const ScoreCfg cfg{out_score, 0, out_row, shape, records, n_records, rec_cap, copies, sweep, road_margin, {types[0], types[1], types[2]}, dt};
-  return launch_score(me, score_args(sc, c1, cfg, out_score, out_stride), stream);
+  ScoreCfg cfg;
+  RET_IF(score_cfg(me, out_score, 0, out_row, shape, records, n_records, rec_cap, copies, sweep, road_margin, types, dt, &cfg));
+  return launch_score(me, SceneHead{S, A_cap, T, pos, head, state, n_agents, type}, c1, cfg, out_score, out_stride, stream);
 }
 
 extern "C" int infgen_token_mask_score(int handle, float* step_score, int steps, unsigned char* score_row, const float* shape,
@@ -1870,17 +1847,14 @@ extern "C" int infgen_token_mask_score(int handle, float* step_score, int steps,
   const char* me = "infgen_token_mask_score";
   ScoreCfg cfg = SCORE_NONE;
   if (step_score) {
-    RET_IF(score_check(me, sweep, road_margin, copies, rec_cap, shape, records, n_records, types, dt, step_score));
+    RET_IF(score_cfg(me, step_score, steps, score_row, shape, records, n_records, rec_cap, copies, sweep, road_margin, types, dt, &cfg));
     if (steps < 1) return fail(me, "step score: steps must be positive");
-    cfg = ScoreCfg{step_score, steps, score_row, shape, records, n_records, rec_cap, copies, sweep, road_margin,
-                   {types[0], types[1], types[2]}, dt};
   }
-  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.score = cfg; });
+  return with_mask_slot(me, handle, NO_TOKEN_MASK, [&](TokenMaskSlot& s) { s.cfg.score = cfg; });
 }
 
 // ---------------------------------------------------------------------------------- observations
 // the argument checks of include/infgen_hip.h ("observations") and the one launch of k_observe_rows
-struct ObserveCfg { const float* shape; };
 static int launch_observe(const char* where, const ObserveArgs& a, void* stream) {
   if (a.S <= 0 || a.A_cap <= 0 || a.T <= 0) return fail(where, "observe: S, A_cap and T must be positive");
   if (a.A_cap > MAX_SCENE_AGENTS) return fail(where, "observe: A_cap exceeds INFGEN_Q_MAX_AGENTS");
@@ -1913,8 +1887,7 @@ extern "C" int infgen_observe_rows(const float* pos, const float* head, const in
                                    float* nbr_feat, int* nbr_index, int* nbr_count, float* map_feat, int* map_index, int* map_count,
                                    void* stream) {
   const char* me = "infgen_observe_rows";
-  const RiderScene sc{S, A_cap, T, pos, head, state, n_agents, nullptr, type, 0};
-  ObserveArgs a = rider_args<ObserveArgs>(sc, ObserveCfg{shape});
+  ObserveArgs a = rider_args<ObserveArgs>(SceneHead{S, A_cap, T, pos, head, state, n_agents, type, shape});
   a.c = c; a.dt = dt;
   a.map_pos = map_pos; a.map_orient = map_orient; a.map_type = map_type; a.n_map = n_map; a.M_cap = M_cap; a.copies = copies;
   a.obs_row = obs_row; a.N = N; a.K = K; a.Km = Km; a.radius = radius; a.map_radius = map_radius;
@@ -1951,16 +1924,14 @@ extern "C" int infgen_idm_command(const float* pos, const float* head, const int
   if (misaligned16(records, out_state)) return fail(me, "idm: records and out_state must be 16-byte aligned");
   const long long rows = (long long)S * A_cap;
   if (rows > 0x7fffffffLL) return fail(me, "idm: too many rows");
-  IdmArgs a{};
-  a.S = S; a.A_cap = A_cap; a.T = T; a.c = c;
-  a.pos = pos; a.head = head; a.state = state; a.n_agents = n_agents; a.type = type; a.shape = shape; a.ctl_row = ctl_row;
+  IdmArgs a = rider_args<IdmArgs>(SceneHead{S, A_cap, T, pos, head, state, n_agents, type, shape});
+  a.c = c; a.ctl_row = ctl_row;
   a.records = records; a.total = total; a.P = P; a.copies = copies; a.v_des = v_des;
   a.dt = dt; a.headway = headway; a.s_min = s_min; a.a_max = a_max; a.b_comf = b_comf; a.b_max = b_max; a.lateral = lateral; a.keep = keep;
   for (int i = 0; i < 3; ++i) { a.v0_type[i] = v0_type[i]; a.types[i] = types[i]; }
   a.stop_at_end = stop_at_end;
   a.cmd_pose = cmd_pose; a.out_state = out_state; a.out_lead = out_lead;
-  hipLaunchKernelGGL(k_idm_command, dim3((unsigned)((rows + RIDER_WAVES - 1) / RIDER_WAVES)), dim3(64 * RIDER_WAVES), 0, (hipStream_t)stream, a);
-  return check_launch(me);
+  return launch_rows(me, k_idm_command, a, stream);
 }
 
 // ---------------------------------------------------------------------------------- rollout context
@@ -1978,13 +1949,11 @@ static EdgeBuf ebuf(const InfgenEdgeBuf& e) { return EdgeBuf{e.off, e.cnt, e.src
 static EdgeSet eset(const InfgenEdgeBuf& e) { return EdgeSet{e.off, e.cnt, e.src, e.rhat}; }
 
 // ctl (optional): the context's sampling parameters as the kernels take them (the defaults for a greedy context, which ignores them)
-// the riders of a registered handle as a context with these row types and token_size sees them (memberwise: a riders block that
-// was zeroed keeps its padding)
-static int handle_riders(const char* where, int handle, const int* type, int token_size, StepRiders* riders, bool memberwise = false) {
+// the riders of a registered handle as a context with these row types and token_size sees them
+static int handle_riders(const char* where, int handle, const int* type, int token_size, StepRiders* riders) {
   TokenMaskDesc tm;
   RET_IF(with_mask_slot(where, handle, "token_mask is no handle of infgen_token_mask_create", [&](const TokenMaskSlot& s) {
-    tm = s.d; riders->coll = s.coll; riders->road = s.road; riders->score = s.score; riders->route = s.route;
-    riders->signal = s.signal;
+    tm = s.d; riders->cfg = s.cfg;
   }));
   if (!tm.type) tm.type = type;
   TokenMaskCtl ctl;
@@ -2014,21 +1983,14 @@ static int validate(const InfgenRollout* r, const char* where, SamplingCtl* ctl 
   *riders = RIDERS_NONE;
   if (r->token_mask) {      // the context's token mask (registered without types: the context's own row types)
     RET_IF(handle_riders(where, r->token_mask, r->type, r->token_size, riders));
-    const auto& [mask, coll, road, score, route, signal] = *riders;
-    if (coll.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
-      return fail(where, "collision mask: token_size must be a multiple of 32, at most 4096");
-    if (road.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
-      return fail(where, "road mask: token_size must be a multiple of 32, at most 4096");
-    if (road.bits && r->S % road.copies) return fail(where, "road mask: S must be a multiple of copies");
+    const auto& [coll, road, score, route, signal] = riders->cfg;
+    if (coll.bits) RET_IF(mask_fits(where, COLLISION_KIND, r, 1));
+    if (road.bits) RET_IF(mask_fits(where, ROAD_KIND, r, road.rule.copies));
     if (score.out && r->first_new)
       return fail(where, "step score: contexts with scenario insertion cannot be scored: rows appended inside a step are left out");
-    if (score.out && r->S % score.copies) return fail(where, "step score: S must be a multiple of copies");
-    if (route.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
-      return fail(where, "route mask: token_size must be a multiple of 32, at most 4096");
-    if (route.bits && r->S % route.copies) return fail(where, "route mask: S must be a multiple of copies");
-    if (signal.bits && (r->token_size % 32 || r->token_size > 64 * 32 * RIDER_WPL))
-      return fail(where, "signal mask: token_size must be a multiple of 32, at most 4096");
-    if (signal.bits && r->S % signal.copies) return fail(where, "signal mask: S must be a multiple of copies");
+    if (score.out && r->S % score.rule.copies) return fail(where, "step score: S must be a multiple of copies");
+    if (route.bits) RET_IF(mask_fits(where, ROUTE_KIND, r, route.rule.copies));
+    if (signal.bits) RET_IF(mask_fits(where, SIGNAL_KIND, r, signal.rule.copies));
   }
   if (r->token_logprob && !(r->store_logits && r->logits) && !r->logits_scratch) {
     // only the fused kernel needs no logits in memory: the plan under the context's own switches
@@ -2046,9 +2008,8 @@ extern "C" int infgen_token_mask_riders(int handle, const int* type, int token_s
   if (!out || capacity < (int)RIDERS_EXPORT_BYTES) return fail(me, "needs a buffer of at least the block's size in bytes");
   StepRiders riders;
   std::memset(&riders, 0, sizeof riders);               // (padding bytes too: the caller compares bytes)
-  const StepRiders none = RIDERS_NONE;
-  riders.mask = none.mask; riders.coll = none.coll; riders.road = none.road; riders.score = none.score; riders.route = none.route;
-  if (handle != 0) RET_IF(handle_riders(me, handle, type, token_size, &riders, true));
+  riders.mask = TOKEN_MASK_NONE; riders.cfg = CFGS_NONE;
+  if (handle != 0) RET_IF(handle_riders(me, handle, type, token_size, &riders));
   std::memcpy(out, &riders, RIDERS_EXPORT_BYTES);          // (the signal configuration behind it: infgen_token_mask_signal_get)
   return (int)RIDERS_EXPORT_BYTES;
 }
@@ -2058,7 +2019,7 @@ extern "C" int infgen_token_mask_signal_get(int handle, void* out, int capacity)
   static_assert(sizeof(SignalCfg) == 6 * sizeof(void*) + 8 * sizeof(int) + 2 * sizeof(void*), "SignalCfg has no padding: its bytes are compared");
   if (!out || capacity < (int)sizeof(SignalCfg)) return fail(me, "needs a buffer of at least the configuration's size in bytes");
   SignalCfg cfg = SIGNAL_NONE;
-  if (handle != 0) RET_IF(with_mask_slot(me, handle, NO_TOKEN_MASK, [&](const TokenMaskSlot& s) { cfg = s.signal; }));
+  if (handle != 0) RET_IF(with_mask_slot(me, handle, NO_TOKEN_MASK, [&](const TokenMaskSlot& s) { cfg = s.cfg.signal; }));
   std::memcpy(out, &cfg, sizeof cfg);
   return (int)sizeof cfg;
 }
@@ -2214,7 +2175,7 @@ extern "C" int infgen_branch_scenes(const InfgenRollout* r, int t, const int* pa
   static_assert(BR_MAX_SEGS >= 9 + 2 * INFGEN_MAX_LAYERS + 1 + 3 + 4, "segment table too short");
   BranchArgs a{};
   a.S = r->S; a.parent = parent; a.map_scene = r->map_scene; a.n_bad = n_bad;
-  const int chunks = branch_segments(r, t, a.seg, &a.n_seg, riders.score.out, (long long)riders.score.steps * 8 * 4);
+  const int chunks = branch_segments(r, t, a.seg, &a.n_seg, riders.cfg.score.out, (long long)riders.cfg.score.steps * 8 * 4);
   if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(int), (hipStream_t)stream) != hipSuccess) return fail(me, "memset failed");
   hipLaunchKernelGGL(k_branch_scenes, dim3(chunks, r->S), dim3(BR_NT), 0, (hipStream_t)stream, a);
   return check_launch(me);
@@ -2231,7 +2192,7 @@ static int snapshot_layout(const InfgenRollout* r, int t, const char* me, SnapAr
   if (t < 0 || 1 + t > r->T - 1) return fail(me, "t must be in 0..steps (the boundary in front of decode step t)");
   if (!(r->pos && r->head && r->state && r->token && r->grid && r->tmask && r->imask && r->catflag && r->bos && r->X))
     return fail(me, "null scene array");
-  *chunks = branch_segments(r, t, a->seg, &a->n_seg, riders.score.out, (long long)riders.score.steps * 8 * 4);
+  *chunks = branch_segments(r, t, a->seg, &a->n_seg, riders.cfg.score.out, (long long)riders.cfg.score.steps * 8 * 4);
   long long off = 0;
   for (int k = 0; k < a->n_seg; ++k) {
     a->entry_off[k] = off;
@@ -2790,30 +2751,27 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   SamplingCtl ctl;
   StepRiders riders;
   RET_IF(validate(r, "infgen_decode_step", &ctl, &riders));
-  auto& [mask, coll, road, score, route, signal] = riders;
+  TokenMaskCtl& mask = riders.mask;
+  const auto& [coll, road, score, route, signal] = riders.cfg;
   OptScope _opts(r);
   ProfPhase _pp(1);
   const int rows = r->S * r->A_cap;
   const int c = 1 + t;
   if (t < 0 || c + 1 > r->T - 1) return fail("infgen_decode_step", "step beyond the column range");
-  const RiderScene sc = rider_scene(r);
+  const SceneHead sc = scene_head(r);
   RET_IF(infgen_decode_layers(r, c, 0, stream));
-  if (coll.bits) {      // collision-aware decoding: this column's sets from the boxes, then the heads read them row by row
-    RET_IF(launch_collision("infgen_decode_step", collision_args(sc, c, coll, mask), stream));
-    mask = TokenMaskCtl{coll.bits, rows, coll.ident, {-1, -1, -1}, nullptr};
-  }
-  if (road.bits) {      // road-aware decoding: the sets so far (static, or this column's collision sets) without the off-road tokens
-    RET_IF(launch_road("infgen_decode_step", road_args(sc, c, road, mask), stream));
-    mask = TokenMaskCtl{road.bits, rows, road.ident, {-1, -1, -1}, nullptr};
-  }
-  if (signal.bits) {    // signal-aware decoding: the sets so far without the tokens that run a stop line closed at step t
-    RET_IF(launch_signal("infgen_decode_step", signal_args(sc, c, t, signal, mask), stream));
-    mask = TokenMaskCtl{signal.bits, rows, signal.ident, {-1, -1, -1}, nullptr};
-  }
-  if (route.bits) {     // route-following decoding: the sets so far without the tokens that leave the row's route or fall behind on it
-    RET_IF(launch_route("infgen_decode_step", route_args(sc, c, route, mask), stream));
-    mask = TokenMaskCtl{route.bits, rows, route.ident, {-1, -1, -1}, nullptr};
-  }
+  // a mask stage: the rider refines the sets so far (static, or an earlier stage's) into this column's own, which the next stage
+  // and then the heads read row by row
+  auto stage = [&](const auto& k) {
+    if (!k.bits) return 0;
+    RET_IF(launch_mask("infgen_decode_step", mask_head(sc, c, r->first_new, r->token_size, mask), k, t, stream));
+    mask = TokenMaskCtl{k.bits, rows, k.ident, {-1, -1, -1}, nullptr};
+    return 0;
+  };
+  RET_IF(stage(coll));      // collision-aware decoding: without the tokens that end in another agent's box
+  RET_IF(stage(road));      // road-aware decoding: without the off-road tokens
+  RET_IF(stage(signal));    // signal-aware decoding: without the tokens that run a stop line closed at step t
+  RET_IF(stage(route));     // route-following decoding: without the tokens that leave the row's route or fall behind on it
   EmitReq q = step_emit_req(r, t);
   q.ctl = ctl; q.mask = mask; q.mask_chain_heads = true;
   q.keys = reinterpret_cast<unsigned long long*>(r->tmp2);      // (scratch of the raw-feature stage, free here)
@@ -2831,7 +2789,7 @@ extern "C" int infgen_decode_step(const InfgenRollout* r, int t, void* stream) {
   RET_IF(infgen_integrate(r, t, stream));
   if (score.out) {      // step scores: the column this step produced, reduced per scene slot
     if (t >= score.steps) return fail("infgen_decode_step", "step score: the log holds fewer steps");
-    RET_IF(launch_score("infgen_decode_step", score_args(sc, c + 1, score, score.out + (size_t)t * 8, (long long)score.steps * 8), stream));
+    RET_IF(launch_score("infgen_decode_step", sc, c + 1, score, score.out + (size_t)t * 8, (long long)score.steps * 8, stream));
   }
   RET_IF(infgen_raw_feature(r, c + 1, stream));
   return 0;

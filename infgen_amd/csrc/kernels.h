@@ -607,20 +607,32 @@ constexpr int RIDER_WAVES = 4;          // rows a workgroup works on at a time (
 constexpr int RIDER_LIST = 128;         // reachable obstacles a wave keeps in LDS per pass over the row's tokens
 constexpr int RIDER_WPL = 2;            // 32-token words a lane owns at most: token_size <= 64 * 32 * RIDER_WPL
 
+// The argument block of a step rider or a closed-loop operator, in layers: the scene head every one of them reads, the mask head of
+// the four mask riders on top of it, and the rider's RULE - its own parameters, the one definition its *Args inherits and its *Cfg
+// (the configuration a registered mask carries; bits / out == NULL: none) embeds.  A rule's members lie in the order the
+// infgen_token_mask_riders / infgen_token_mask_signal_get blocks export them
+struct SceneHead {
+  int S, A_cap, T;                      // the [S][T][A_cap] scene arrays (each block names its own column of them)
+  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
+  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+};
+struct MaskHead : SceneHead {           // (member order: the one under which the four mask kernels keep their register counts)
+  const float* end_pose; int token_size;      // [3][token_size][4] = (dx, dy, cos, sin) + the three largest displacements
+  const int* first_new;                 // optional [S]: rows >= first_new[s] were appended inside this step
+  int* out_count; int c;                // optional [S * A_cap]; column c of the scene arrays is the current one
+  unsigned* out_bits;                   // [S * A_cap][token_size / 32]
+  TokenMaskCtl base;                    // the sets the rule refines (bits == NULL: every token)
+};
+
 // k_collision_mask (collision_kernels.hip): the per-step allowed-token sets of collision-aware decoding (include/infgen_hip.h, "collision
 // masks"): set(i) = base(i) AND NOT collides(i) for every row of the layout, written as the row's own set of out_bits
 constexpr int CM_STAGE = 9;             // floats the workgroup stages per obstacle row of the scene
-struct CollisionArgs {
-  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
+struct CollisionRule { int predict; float margin; };
+struct CollisionArgs : MaskHead, CollisionRule {
   int rows_per_wg;                      // rows of one scene a workgroup covers (a multiple of RIDER_WAVES)
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* first_new;                  // [S]; first_new optional: rows >= first_new[s] were appended inside this step
-  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
-  const float* end_pose; int token_size;                      // [3][token_size][4] = (dx, dy, cos, sin) + the three largest displacements
-  int predict; float margin;
-  TokenMaskCtl base;                    // the static sets (bits == NULL: every token)
-  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
 };
+struct CollisionCfg { unsigned* bits; const int* ident; const float* shape; const float* end_pose; CollisionRule rule; int* count; };
+constexpr CollisionCfg COLLISION_NONE{nullptr, nullptr, nullptr, nullptr, {1, 0.f}, nullptr};
 struct EndPoseArgs { const float* vocab; int token_size; float* end_pose; };     // vocab [3][token_size][6][4][2]
 __global__ void k_collision_mask(CollisionArgs a);
 __global__ void k_collision_end_poses(EndPoseArgs a);
@@ -628,17 +640,14 @@ __global__ void k_collision_end_poses(EndPoseArgs a);
 // road_kernels.hip: the per-step allowed-token sets of road-aware decoding (include/infgen_hip.h, "road masks"):
 // set(i) = base(i) AND NOT offroad(i), written as the row's own set of out_bits
 constexpr int RM_REC = 8;               // floats of a record: anchor x, y, offset x, y | cos, sin, half length, radius
-struct RoadArgs {
-  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* first_new;                  // [S]; first_new optional
-  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
-  const float* end_pose; const float* paths; int token_size;  // [3][token_size][4] + 4 floats, [3][token_size][4] = (cos, sin, half length, 0)
+struct RoadRule {
+  const float* paths;                                         // [3][token_size][4] = (cos, sin, half length, 0)
   const float* records; const int* n_records; int rec_cap;    // [S / copies][rec_cap][RM_REC], [S / copies]
   int copies, sweep; float margin; int types[3];              // types[ty] != 0: the rule applies to rows of agent type ty
-  TokenMaskCtl base;                    // the sets the road rule refines (bits == NULL: every token)
-  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
 };
+struct RoadArgs : MaskHead, RoadRule {};
+struct RoadCfg { unsigned* bits; const int* ident; const float* shape; const float* end_pose; RoadRule rule; int* count; };
+constexpr RoadCfg ROAD_NONE{nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}}, nullptr};
 struct RoadMapArgs {                    // k_road_records_map: one workgroup (one wave) per distinct scene
   const float* map_pos; const float* map_orient; const long long* map_type; const long long* map_tok; const int* n_map;   // [S0][M_cap](x2), [S0]
   int M_cap; const float* map_vocab; int n_token, detail;     // [n_token][11][2]
@@ -655,18 +664,17 @@ __global__ void k_road_paths(RoadPathArgs a);
 // set(i) = base(i) AND onroute(i), written as the row's own set of out_bits
 constexpr int RT_REC = 8;               // floats of a record: p0 x, y, direction x, y | L, cum, 0, 0
 constexpr int RT_MAX_POINTS = 32;       // waypoints of a route at most: its segments fit the lanes of half a wave
-struct RouteArgs {
-  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* first_new;                  // [S]; first_new optional
-  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
-  const float* end_pose; int token_size;                      // [3][token_size][4] + 4 floats
+struct RouteRule {
   const float* records; const float* total; int P;            // [S / copies][A_cap][P - 1][RT_REC], [S / copies][A_cap]
   int copies; float corridor, back, pace, finish; int types[3];      // types[ty] != 0: the rule applies to rows of agent type ty
-  TokenMaskCtl base;                    // the sets the route rule refines (bits == NULL: every token)
-  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
+};
+struct RouteArgs : MaskHead, RouteRule {
   float* out_progress;                  // optional [S * A_cap][4] = s0, d0, total, flag
 };
+struct RouteCfg {
+  unsigned* bits; const int* ident; const float* shape; const float* end_pose; RouteRule rule; int* count; float* progress;
+};
+constexpr RouteCfg ROUTE_NONE{nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, 2, 1, 0.f, 0.f, 0.f, 0.f, {0, 0, 0}}, nullptr, nullptr};
 struct RouteRecArgs { const float* routes; const int* n_points; int rows, P; float* records; float* total; };   // rows = S * A_cap
 __global__ void k_route_mask(RouteArgs a);
 __global__ void k_route_records(RouteRecArgs a);
@@ -675,19 +683,19 @@ __global__ void k_route_records(RouteRecArgs a);
 // set(i) = base(i) AND NOT runs(i), written as the row's own set of out_bits
 constexpr int SG_REC = 8;               // floats of a record: midpoint x, y, direction of lawful travel x, y | half length, 0, 0, 0
 constexpr int SG_MAX_LINES = 64;        // stop lines of a map scene at most: one per lane of a wave
-struct SignalArgs {
-  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the current one
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* first_new;                  // [S]; first_new optional
-  const int* type; const float* shape;                        // [S][A_cap], [S][A_cap][3] = (length, width, height)
-  const float* end_pose; int token_size;                      // [3][token_size][4] + 4 floats
+struct SignalRule {
   const float* records; const unsigned char* phase;           // [S / copies][K][SG_REC], [S / copies][n_phase][K]
-  int n_phase, K, t;                    // decode step t reads phase row t % n_phase
+  int n_phase, K;
   int copies; float setback, align; int types[3];             // types[ty] != 0: the rule applies to rows of agent type ty
-  TokenMaskCtl base;                    // the sets the signal rule refines (bits == NULL: every token)
-  unsigned* out_bits; int* out_count;   // [S * A_cap][token_size / 32], optional [S * A_cap]
+};
+struct SignalArgs : MaskHead, SignalRule {
+  int t;                                // decode step t reads phase row t % n_phase
   float* out_info;                      // optional [S * A_cap][4] = gap, j, flag, 0
 };
+struct SignalCfg {
+  unsigned* bits; const int* ident; const float* shape; const float* end_pose; SignalRule rule; int* count; float* info;
+};
+constexpr SignalCfg SIGNAL_NONE{nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, 1, 1, 1, 0.f, 0.f, {0, 0, 0}}, nullptr, nullptr};
 struct SignalRecArgs { const float* lines; const int* n_lines; int S0, K; float* records; };
 __global__ void k_signal_mask(SignalArgs a);
 __global__ void k_signal_records(SignalRecArgs a);
@@ -736,15 +744,17 @@ template <bool RESTORE> __global__ void k_snapshot_scenes(SnapArgs a);
 // score_kernels.hip: the step scores of one stored column (include/infgen_hip.h, "step scores"): 8 floats per scene slot, one flag byte
 // per row
 constexpr int SC_NT = 256;              // threads of the one workgroup per scene slot
-struct ScoreArgs {
-  int S, A_cap, T, c1;                  // column c1 of the [S][T][A_cap] scene arrays is the scored one
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+struct ScoreRule {
   const float* records; const int* n_records; int rec_cap;    // [S / copies][rec_cap][RM_REC], [S / copies]; records NULL: no table
   int copies, sweep; float margin; int types[3]; float dt;
+};
+struct ScoreArgs : SceneHead, ScoreRule {
+  int c1;                               // column c1 of the scene arrays is the scored one
   float* out; long long out_stride;     // slot s: the 8 floats at out + s * out_stride (32-byte aligned)
   unsigned char* out_row;               // optional [S][A_cap]: bit 0 live, bit 1 overlap, bit 2 off-road
 };
+struct ScoreCfg { float* out; int steps; unsigned char* row; const float* shape; ScoreRule rule; };      // steps: decode steps the log `out` holds
+constexpr ScoreCfg SCORE_NONE{nullptr, 0, nullptr, nullptr, {nullptr, nullptr, 0, 1, 1, 0.f, {0, 0, 0}, 0.5f}};
 __global__ void k_step_score(ScoreArgs a);
 
 // observe_kernels.hip: the agent-frame observation of the rows named (include/infgen_hip.h, "observations"): own features, the K
@@ -753,10 +763,8 @@ constexpr int OB_WAVES = 4;             // rows a workgroup works on (one wave e
 constexpr int OB_LIST = 512;            // 64-bit keys a wave keeps in LDS; a fuller list is cut down to its K best first
 constexpr int OBS_SELF = INFGEN_OBS_SELF, OBS_NBR = INFGEN_OBS_NBR, OBS_MAP = INFGEN_OBS_MAP, OBS_MAX_K = INFGEN_OBS_MAX_K;
 static_assert(OBS_MAX_K <= 64 && OB_LIST >= 2 * 64, "one lane per selected entry; a cut-down list has room for 64 more");
-struct ObserveArgs {
-  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the observed one
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+struct ObserveArgs : SceneHead {
+  int c;                                // column c of the scene arrays is the observed one
   float dt;
   const float* map_pos; const float* map_orient; const long long* map_type; const int* n_map;   // [S / copies][M_cap](x2), [S / copies]
   int M_cap, copies;
@@ -769,10 +777,8 @@ __global__ void k_observe_rows(ObserveArgs a);
 
 // controller_kernels.hip: the target poses of rule-based controlled rows (include/infgen_hip.h, "IDM commands"): route projection,
 // lead search and the car-following law, one wave per row
-struct IdmArgs {
-  int S, A_cap, T, c;                   // column c of the [S][T][A_cap] scene arrays is the newest stored one, c >= 1
-  const float* pos; const float* head; const int* state;      // [S][T][A_cap](x2)
-  const int* n_agents; const int* type; const float* shape;   // [S], [S][A_cap], [S][A_cap][3] = (length, width, height)
+struct IdmArgs : SceneHead {
+  int c;                                // column c of the scene arrays is the newest stored one, c >= 1
   const unsigned char* ctl_row;         // [S][A_cap]: != 0, the row is controlled
   const float* records; const float* total; int P, copies;    // [S / copies][A_cap][P - 1][RT_REC], [S / copies][A_cap]
   const float* v_des;                   // optional [S / copies][A_cap]: the row's own desired speed where > 0
