@@ -146,6 +146,37 @@ def check_row_selectors(sel: np.ndarray, n_sets: int) -> np.ndarray:
     return sel.astype(np.int32)
 
 
+# ---------------------------------------------------------------------------------------- what the step riders' checks share
+def _check_metres(what: str, key: str, v) -> float:
+    if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isfinite(v) or v < 0:
+        raise ValueError(f'{what}: {key} must be a finite number of metres >= 0 (got {v!r})')
+    return float(v)
+
+
+def _check_switch(what: str, key: str, v) -> int:
+    if isinstance(v, str) or not np.isscalar(v) or v not in (0, 1, False, True):
+        raise ValueError(f'{what}: {key} must be 0 or 1 (got {v!r})')
+    return int(v)
+
+
+def _check_within(what: str, key: str, v, lo, hi) -> float:
+    if isinstance(v, (bool, str)) or not np.isscalar(v) or not lo <= v <= hi:
+        raise ValueError(f'{what}: {key} must be a number in [{lo}, {hi}] (got {v!r})')
+    return float(v)
+
+
+def _row_buffers(what: str, rows: int, token_size: int, device):
+    """every per-step mask kernel's own, ``rows`` = S * A_cap: ``bits`` [rows][token_size / 32] int32 (the sets of the step that just
+    ran), ``allowed`` [rows] int32 (their sizes before the empty-set fallback), ``ident`` [rows] int32 (row i is set i), ``shape`` [rows][3]"""
+    import torch
+    if token_size % 32 or token_size > 4096:
+        raise ValueError(f'{what}: token_size {token_size} must be a multiple of 32, at most 4096')
+    return dict(bits=torch.full((rows, token_size // 32), -1, dtype=torch.int32, device=device),
+                allowed=torch.full((rows,), token_size, dtype=torch.int32, device=device),
+                ident=torch.arange(rows, dtype=torch.int32, device=device),
+                shape=torch.zeros(rows, 3, dtype=torch.float32, device=device))
+
+
 # ---------------------------------------------------------------------------------------- collision-aware decoding (DESIGN 5.12)
 def check_avoid_collisions(avoid, has_shape: bool = True):
     """``avoid_collisions`` as the engine takes it -> None (off) or dict(margin=float, predict=0 | 1).  False / None: off; True: the
@@ -160,29 +191,22 @@ def check_avoid_collisions(avoid, has_shape: bool = True):
     unknown = set(avoid) - {'margin', 'predict'}
     if unknown:
         raise ValueError(f'avoid_collisions: unknown keys {sorted(unknown)} (margin, predict)')
-    margin, predict = avoid.get('margin', 0.0), avoid.get('predict', 1)
-    if isinstance(margin, (bool, str)) or not np.isscalar(margin) or not np.isfinite(margin) or margin < 0:
-        raise ValueError(f'avoid_collisions: margin must be a finite number of metres >= 0 (got {margin!r})')
-    if isinstance(predict, str) or predict not in (0, 1, False, True):
-        raise ValueError(f'avoid_collisions: predict must be 0 or 1 (got {predict!r})')
+    margin = _check_metres('avoid_collisions', 'margin', avoid.get('margin', 0.0))
+    predict = _check_switch('avoid_collisions', 'predict', avoid.get('predict', 1))
     if not has_shape:
         raise ValueError('avoid_collisions needs the rows\' shapes: this engine has no shape array')
-    return dict(margin=float(margin), predict=int(predict))
+    return dict(margin=margin, predict=predict)
+
+
+def collision_key(conf):
+    """the hashable form of a checked avoid_collisions configuration: both of its values are launch arguments"""
+    return None if conf is None else (conf['margin'], conf['predict'])
 
 
 def collision_buffers(conf, rows: int, token_size: int, device='cpu'):
     """the static buffers of collision-aware decoding for ``rows`` = S * A_cap rows, or None when ``conf`` (``check_avoid_collisions``)
-    is off: ``bits`` [rows][token_size / 32] int32 (the sets of the step that just ran), ``allowed`` [rows] int32 (their sizes before
-    the empty-set fallback), ``ident`` [rows] int32 (row i names set i), ``shape`` [rows][3]"""
-    if conf is None:
-        return None
-    import torch
-    if token_size % 32 or token_size > 4096:
-        raise ValueError(f'avoid_collisions: token_size {token_size} must be a multiple of 32, at most 4096')
-    return dict(bits=torch.full((rows, token_size // 32), -1, dtype=torch.int32, device=device),
-                allowed=torch.full((rows,), token_size, dtype=torch.int32, device=device),
-                ident=torch.arange(rows, dtype=torch.int32, device=device),
-                shape=torch.zeros(rows, 3, dtype=torch.float32, device=device))
+    is off: the four of ``_row_buffers`` - ``bits``, ``allowed``, ``ident``, ``shape``"""
+    return None if conf is None else _row_buffers('avoid_collisions', rows, token_size, device)
 
 
 # ---------------------------------------------------------------------------------------- road-aware decoding (DESIGN 5.13)
@@ -244,11 +268,8 @@ def check_stay_on_road(stay, has_shape: bool = True, n_scenes: Optional[int] = N
     unknown = set(stay) - {margin_key, 'sweep', 'detail', 'types', 'segments'}
     if unknown:
         raise ValueError(f'{what}: unknown keys {sorted(unknown)} ({margin_key}, sweep, detail, types, segments)')
-    margin, sweep, detail = stay.get(margin_key, 0.0), stay.get('sweep', 1), stay.get('detail', 2)
-    if isinstance(margin, (bool, str)) or not np.isscalar(margin) or not np.isfinite(margin) or margin < 0:
-        raise ValueError(f'{what}: {margin_key} must be a finite number of metres >= 0 (got {margin!r})')
-    if isinstance(sweep, str) or not np.isscalar(sweep) or sweep not in (0, 1, False, True):
-        raise ValueError(f'{what}: sweep must be 0 or 1 (got {sweep!r})')
+    margin = _check_metres(what, margin_key, stay.get(margin_key, 0.0))
+    sweep, detail = _check_switch(what, 'sweep', stay.get('sweep', 1)), stay.get('detail', 2)
     if isinstance(detail, (bool, str)) or not np.isscalar(detail) or detail not in ROAD_DETAILS:
         raise ValueError(f'{what}: detail must be one of {ROAD_DETAILS} (got {detail!r})')
     types = _road_types(stay.get('types', ('veh', 'cyc')), what)
@@ -265,7 +286,7 @@ def check_stay_on_road(stay, has_shape: bool = True, n_scenes: Optional[int] = N
             raise ValueError(f'{what}: segments cover {segments[0].shape[0]} scenes, the batch has {n_scenes} distinct scenes')
     if not has_shape:
         raise ValueError(f'{what} needs the rows\' shapes: this engine has no shape array')
-    return dict(margin=float(margin), sweep=int(sweep), detail=int(detail), types=types, segments=segments)
+    return dict(margin=margin, sweep=sweep, detail=int(detail), types=types, segments=segments)
 
 
 def road_key(conf):
@@ -277,11 +298,7 @@ def road_buffers(conf, rows: int, token_size: int, device='cpu'):
     """the static per-row buffers of road-aware decoding for ``rows`` = S * A_cap rows, or None when ``conf`` (``check_stay_on_road``)
     is off: the four of ``collision_buffers`` - ``bits``, ``allowed``, ``ident``, ``shape`` - for the road kernel's own sets.  (The
     record table is the engine's: it is sized from a count of the map's EDGE tokens.)"""
-    if conf is None:
-        return None
-    if token_size % 32 or token_size > 4096:
-        raise ValueError(f'stay_on_road: token_size {token_size} must be a multiple of 32, at most 4096')
-    return collision_buffers(conf, rows, token_size, device)
+    return None if conf is None else _row_buffers('stay_on_road', rows, token_size, device)
 
 
 # ---------------------------------------------------------------------------------------- step scores (DESIGN 5.14)
@@ -369,14 +386,8 @@ def check_follow_routes(follow, n_scenes: Optional[int] = None, a_cap: Optional[
         raise ValueError(f'{what} needs routes [S0][A][P][2] and n_points [S0][A]')
     out = {}
     for key, dflt in (('corridor', 2.0), ('back', 0.5), ('finish', 1.0)):
-        v = follow.get(key, dflt)
-        if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isfinite(v) or v < 0:
-            raise ValueError(f'{what}: {key} must be a finite number of metres >= 0 (got {v!r})')
-        out[key] = float(v)
-    pace = follow.get('pace', 0.0)
-    if isinstance(pace, (bool, str)) or not np.isscalar(pace) or not 0 <= pace <= 1:
-        raise ValueError(f'{what}: pace must be a number in [0, 1] (got {pace!r})')
-    out['pace'] = float(pace)
+        out[key] = _check_metres(what, key, follow.get(key, dflt))
+    out['pace'] = _check_within(what, 'pace', follow.get('pace', 0.0), 0, 1)
     out['types'] = _road_types(follow.get('types', ('veh', 'cyc')), what)
     out['routes'], out['n_points'] = route_arrays(follow['routes'], follow['n_points'], n_scenes, a_cap, what)
     return out
@@ -392,9 +403,7 @@ def route_buffers(n_scenes: int, rows: int, a_cap: int, P: int, token_size: int,
     ``shape`` (the row skeleton reads it, the rule does not: it stays zero) -, ``progress`` [rows][4], and per distinct scene
     ``routes`` [S0][A_cap][P][2], ``n_points`` [S0][A_cap], ``records`` [S0][A_cap][P - 1][8], ``total`` [S0][A_cap]"""
     import torch
-    if token_size % 32 or token_size > 4096:
-        raise ValueError(f'follow_routes: token_size {token_size} must be a multiple of 32, at most 4096')
-    k = collision_buffers({}, rows, token_size, device)
+    k = _row_buffers('follow_routes', rows, token_size, device)
     k.update(P=P, progress=torch.zeros(rows, 4, device=device), routes=torch.zeros(n_scenes, a_cap, P, 2, device=device),
              n_points=torch.zeros(n_scenes, a_cap, dtype=torch.int32, device=device),
              records=torch.zeros(n_scenes, a_cap, P - 1, 8, device=device), total=torch.zeros(n_scenes, a_cap, device=device))
@@ -453,12 +462,9 @@ def check_obey_signals(obey, has_shape: bool = True, n_scenes: Optional[int] = N
         raise ValueError(f'{what}: unknown keys {sorted(unknown)} (lines, n_lines, phase, setback, align, types)')
     if obey.get('lines') is None or obey.get('phase') is None:
         raise ValueError(f'{what} needs lines [S0][K][4] and phase [S0][n_phase][K]')
-    setback, align = obey.get('setback', 0.5), obey.get('align', 0.5)
-    if isinstance(setback, (bool, str)) or not np.isscalar(setback) or not np.isfinite(setback) or setback < 0:
-        raise ValueError(f'{what}: setback must be a finite number of metres >= 0 (got {setback!r})')
-    if isinstance(align, (bool, str)) or not np.isscalar(align) or not -1 <= align <= 1:
-        raise ValueError(f'{what}: align must be a number in [-1, 1] (got {align!r})')
-    out = dict(setback=float(setback), align=float(align), types=_road_types(obey.get('types', ('veh', 'cyc')), what))
+    setback = _check_metres(what, 'setback', obey.get('setback', 0.5))
+    align = _check_within(what, 'align', obey.get('align', 0.5), -1, 1)
+    out = dict(setback=setback, align=align, types=_road_types(obey.get('types', ('veh', 'cyc')), what))
     out['lines'], out['n_lines'] = signal_lines(obey['lines'], obey.get('n_lines'), n_scenes, what)
     out['phase'] = signal_phase_table(obey['phase'], out['lines'].shape[0], out['lines'].shape[1], what)
     if not has_shape:
@@ -481,9 +487,7 @@ def signal_buffers(n_scenes: int, rows: int, K: int, n_phase: int, token_size: i
     ``info`` [rows][4], and per distinct scene ``lines`` [S0][K][4], ``n_lines`` [S0], ``records`` [S0][K][8], ``phase``
     [S0][n_phase][K] bytes"""
     import torch
-    if token_size % 32 or token_size > 4096:
-        raise ValueError(f'obey_signals: token_size {token_size} must be a multiple of 32, at most 4096')
-    k = collision_buffers({}, rows, token_size, device)
+    k = _row_buffers('obey_signals', rows, token_size, device)
     info = torch.zeros(rows, 4, device=device)
     info[:, 1] = -1.0
     k.update(K=K, n_phase=n_phase, info=info, lines=torch.zeros(n_scenes, K, 4, device=device),

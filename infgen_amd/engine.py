@@ -12,6 +12,7 @@ map_decoder.py:70-130, agent_decoder.py:1605-2389), greedy decoding, insertion d
 """
 from __future__ import annotations
 
+from collections import namedtuple
 import ctypes as C
 import hashlib
 from dataclasses import replace as dataclasses_replace
@@ -540,6 +541,38 @@ def _lib_np_dtype(dt):
 
 _FLT_MIN = float(np.finfo(np.float32).tiny)      # the smallest normal float32: below it 1 / T overflows
 
+# The step riders in the order the engine resolves them.  ``name``: the keyword, and the engine attribute that holds the
+# checked configuration while the rider is on; ``buffers`` / ``reg``: the attributes of its buffer dict and of what the handle has
+# registered; ``check(engine, value)`` / ``key(conf)``: the constraints.py check and the part of its result that decides launches;
+# ``entry`` / ``off``: the library's attach entry and the arguments that detach; ``public``: the buffer attributes the engine exposes.
+_Rider = namedtuple('_Rider', 'name buffers reg check key entry off public')
+RIDERS = (
+    _Rider('avoid_collisions', '_coll', '_coll_reg',
+           lambda e, v: constraints.check_avoid_collisions(v, has_shape=e._has_shape), constraints.collision_key,
+           'infgen_token_mask_collision', (None, None, None, None, 1, 0.0, None), ('collision_bits', 'collision_allowed')),
+    _Rider('stay_on_road', '_road', '_road_reg',
+           lambda e, v: constraints.check_stay_on_road(v, has_shape=e._has_shape, n_scenes=e.S0), constraints.road_key,
+           'infgen_token_mask_road', (None, None, None, None, None, None, None, 0, 1, 1, 0.0, None, None), ('road_bits', 'road_allowed')),
+    _Rider('step_scores', None, '_score_reg',
+           lambda e, v: constraints.check_step_scores(v, has_shape=e._has_shape, n_scenes=e.S0, stay_on_road=e.stay_on_road),
+           constraints.score_key, 'infgen_token_mask_score', (None, 0, None, None, None, None, 0, 1, 1, 0.0, None, 0.5),
+           ('step_score', 'score_row')),
+    _Rider('follow_routes', '_route', '_route_reg',
+           lambda e, v: constraints.check_follow_routes(v, n_scenes=e.S0, a_cap=e.A_cap), constraints.route_key,
+           'infgen_token_mask_route', (None, None, None, None, None, None, 2, 1, 0.0, 0.0, 0.0, 0.0, None, None, None),
+           ('route_bits', 'route_allowed', 'route_progress')),
+    _Rider('obey_signals', '_signal', '_signal_reg',
+           lambda e, v: constraints.check_obey_signals(v, has_shape=e._has_shape, n_scenes=e.S0), constraints.signal_key,
+           'infgen_token_mask_signal', (None, None, None, None, None, None, 1, 1, 1, 0.0, 0.0, None, None, None),
+           ('signal_bits', 'signal_allowed', 'signal_info')))
+_SCORES = RIDERS[2]
+STEP_KEYWORDS = ('token_masks', 'token_mask_type', 'token_mask_row') + tuple(r.name for r in RIDERS)
+
+
+def _step_keywords(args: Mapping) -> Dict:
+    """what rides on the decode step, out of the ``locals()`` of the constructor or a reload entry: gathered once per entry"""
+    return {k: args[k] for k in STEP_KEYWORDS}
+
 
 class RolloutEngine:
     """Device state + launch sequence for a batch of scenes."""
@@ -837,24 +870,13 @@ class RolloutEngine:
         self.token_masks, self.token_mask_type = None, [-1, -1, -1]
         self.mask_bits = self.mask_row = None             # static device buffers: [n_sets][token_size / 32] words, [S * A_cap] int32
         self._mask_handle = 0                             # infgen_token_mask_create's handle of (mask_bits, mask_row, token_mask_type)
-        self.stay_on_road = None                          # the checked configuration while road-aware decoding is on
-        self.road_bits = self.road_allowed = self.road_records = self.road_n_records = None
-        self._road = self._road_paths = self._road_reg = self._road_seg = None
+        for r in RIDERS:      # per rider: the checked configuration while it is on, its buffers, what the handle has registered
+            for attr in filter(None, (r.name, r.buffers, r.reg) + r.public):
+                setattr(self, attr, None)
+        self.road_records = self.road_n_records = self._road_paths = self._road_seg = None      # the engine's one road table
         self._road_cap, self._road_dirty = 0, False
-        self.avoid_collisions = None                      # dict(margin, predict) while collision-aware decoding is on
-        self.collision_bits = self.collision_allowed = None
-        self._coll = self._coll_end = self._coll_reg = None
-        self.step_scores = None                           # the checked configuration while step scores are on
-        self.step_score = self.score_row = None           # [S, steps, 8] floats, [S, A_cap] flag bytes
-        self._score_arg = self._score_shape = self._score_reg = None
-        self.follow_routes = None                         # the checked configuration while route-following decoding is on
-        self.route_bits = self.route_allowed = self.route_progress = None
-        self._route = self._route_reg = None
-        self.obey_signals = None                          # the checked configuration while signal-aware decoding is on
-        self.signal_bits = self.signal_allowed = self.signal_info = None
-        self._signal = self._signal_reg = None
-        self._load_riders((token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores, follow_routes,
-                          obey_signals)
+        self._coll_end = self._score_arg = self._score_shape = None
+        self._load_riders(_step_keywords(locals()))
         # (the sampler's logits scratch, where the context needs one, is allocated once the kernel switches are known: _refresh_opts)
         # [steps][rows] log-probability of the emitted token (InfgenRollout.token_logprob); its logits scratch, where the context
         # needs one, is allocated once the kernel switches are known (_refresh_opts)
@@ -984,7 +1006,7 @@ class RolloutEngine:
             raise ValueError('sample_temperature must be finite and 0 (greedy) or a normal float32 above 0 (1 / T must stay finite)')
         if t.ndim == 0 and self.sample_temp_row is None and float(t) > 0.0:      # (a scalar 0 is "every row greedy": the array's 0)
             if float(t) != self.sample_temperature:
-                self._graph = self._wgraph = None      # (a captured graph holds the old kernel argument)
+                self._drop_graphs()      # (a captured graph holds the old kernel argument)
             self.sample_temperature = float(t)
         else:
             if t.ndim == 0:
@@ -1001,7 +1023,7 @@ class RolloutEngine:
             rows = torch.from_numpy(np.ascontiguousarray(rows.reshape(S * A_cap)))
             if self.sample_temp_row is None:
                 self.sample_temp_row = rows.to(self.device)
-                self._graph = self._wgraph = None
+                self._drop_graphs()
             else:
                 self.sample_temp_row.copy_(rows)
         self._apply_sampling()
@@ -1021,7 +1043,7 @@ class RolloutEngine:
             words = torch.from_numpy(token_masks.words.view(np.int32).copy())
             if self.mask_bits is None or self.mask_bits.shape != words.shape:
                 self.mask_bits = words.to(self.device)
-                self._graph = self._wgraph = None      # (a captured graph holds the old table's address and size)
+                self._drop_graphs()      # (a captured graph holds the old table's address and size)
             else:
                 self.mask_bits.copy_(words)
             if token_mask_type is None and (self.token_masks is None or token_masks.n_sets != self.token_masks.n_sets):
@@ -1033,13 +1055,13 @@ class RolloutEngine:
         if token_mask_type is not None:
             sel = constraints.check_type_selectors(token_mask_type, n_sets)
             if sel != self.token_mask_type:
-                self._graph = self._wgraph = None      # (a captured graph holds the old kernel arguments)
+                self._drop_graphs()      # (a captured graph holds the old kernel arguments)
             self.token_mask_type = sel
         elif any(v >= n_sets for v in self.token_mask_type):
             raise ValueError('the new token_masks hold fewer sets than token_mask_type selects')
         if self.mask_row is None:
             self.mask_row = torch.full((S * A_cap,), -1, dtype=torch.int32, device=self.device)
-            self._graph = self._wgraph = None
+            self._drop_graphs()
         if token_mask_row is not None:
             if isinstance(token_mask_row, torch.Tensor) and token_mask_row.is_cuda:
                 if tuple(token_mask_row.shape) != (S, A_cap) or token_mask_row.dtype != torch.int32:
@@ -1054,23 +1076,38 @@ class RolloutEngine:
                 self.mask_row.copy_(torch.from_numpy(rows.reshape(-1)))
         self._apply_token_masks()
 
-    def _load_collisions(self, avoid):
-        """``avoid_collisions`` into the engine (None: keep what is there).  The value is checked on the host before anything is
-        allocated or launched; the buffers are allocated once and stay (static addresses for captured graphs)"""
-        if avoid is None:
+    def _drop_graphs(self):
+        """a captured graph holds the launches, kernel arguments and addresses of its capture: whatever changes one drops both"""
+        self._graph = self._wgraph = None
+
+    @property
+    def _has_shape(self) -> bool:
+        return getattr(self, '_shape10', None) is not None
+
+    def _load_rider(self, rider, value):
+        """one rider's keyword into the engine (None: keep what is there), checked on the host before anything is allocated or
+        launched.  ``_settle_<name>`` does what is the rider's own around ``store()``: a new key drops the graphs, ``conf`` is kept"""
+        if value is None:
             return
-        conf = constraints.check_avoid_collisions(avoid, has_shape=getattr(self, '_shape10', None) is not None)
-        if conf is None and self.avoid_collisions is None:
+        conf, old = rider.check(self, value), getattr(self, rider.name)
+        if conf is None and old is None:
             return
+
+        def store():
+            if rider.key(conf) != rider.key(old):
+                self._drop_graphs()
+            setattr(self, rider.name, conf)
+        getattr(self, '_settle_' + rider.name)(conf, value, store)
+        self._apply_token_masks()
+
+    def _settle_avoid_collisions(self, conf, value, store):
+        """the buffers are allocated once and stay, also while the rider is off (static addresses for captured graphs)"""
         if conf is not None and self._coll is None:
             self._coll = constraints.collision_buffers(conf, self.S * self.A_cap, self.cfg.token_size, self.device)
             self.collision_bits, self.collision_allowed = self._coll['bits'], self._coll['allowed']
             self._coll['shape'].copy_(self._shape10.reshape(-1, 3))
             self._end_pose_table()
-        if conf != self.avoid_collisions:
-            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
-        self.avoid_collisions = conf
-        self._apply_token_masks()
+        store()
 
     def _end_pose_table(self):
         """the per-token end poses of the vocabulary, once per engine (collision and road masks read the same table)"""
@@ -1080,14 +1117,8 @@ class RolloutEngine:
             _lib.check(self.lib.infgen_collision_end_poses(_lib.ptr(self.vocab), self.cfg.token_size, _lib.ptr(self._coll_end),
                                                            self.ops.stream), 'infgen_collision_end_poses')
 
-    def _load_road(self, stay):
-        """``stay_on_road`` into the engine (None: keep what is there), like ``_load_collisions``.  The record table is built by the
-        next prologue (``_road_build``): the map may not be in the buffers yet"""
-        if stay is None:
-            return
-        conf = constraints.check_stay_on_road(stay, has_shape=getattr(self, '_shape10', None) is not None, n_scenes=self.S0)
-        if conf is None and self.stay_on_road is None:
-            return
+    def _settle_stay_on_road(self, conf, value, store):
+        """the record table is built by the next prologue (``_road_build``): the map may not be in the buffers yet"""
         if conf is not None and self._road is None:
             self._road = constraints.road_buffers(conf, self.S * self.A_cap, self.cfg.token_size, self.device)
             self.road_bits, self.road_allowed = self._road['bits'], self._road['allowed']
@@ -1097,31 +1128,19 @@ class RolloutEngine:
             self._road_paths = torch.zeros(12 * self.cfg.token_size, device=self.device)
             _lib.check(self.lib.infgen_road_paths(_lib.ptr(self._coll_end), self.cfg.token_size, _lib.ptr(self._road_paths),
                                                   self.ops.stream), 'infgen_road_paths')
-        if constraints.road_key(conf) != constraints.road_key(self.stay_on_road):
-            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
-        self.stay_on_road = conf
+        store()
         if conf is not None:
             self._road_source(conf)
         if self.step_scores is not None:               # the scores read the engine's one road table: checked against the new one
-            self._load_scores(self._score_arg)
-        self._apply_token_masks()
+            self._load_rider(_SCORES, self._score_arg)
 
-    def _load_routes(self, follow):
-        """``follow_routes`` into the engine (None: keep what is there), like ``_load_collisions``; the routes are uploaded and
-        their records built at once (they do not depend on the scene in the buffers)"""
-        if follow is None:
-            return
-        conf = constraints.check_follow_routes(follow, n_scenes=self.S0, a_cap=self.A_cap)
-        if conf is None and self.follow_routes is None:
-            return
-        if constraints.route_key(conf) != constraints.route_key(self.follow_routes):
-            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
-        self.follow_routes = conf
+    def _settle_follow_routes(self, conf, value, store):
+        """the routes are uploaded and their records built at once (they do not depend on the scene in the buffers)"""
+        store()
         if conf is not None:
             self._upload_routes(conf.pop('routes'), conf.pop('n_points'))
         else:      # off: nothing of the last routed step stays readable
             self._route = self.route_bits = self.route_allowed = self.route_progress = None
-        self._apply_token_masks()
 
     def set_routes(self, routes, n_points):
         """new routes for an engine with ``follow_routes`` on - allowed between two steps of a rollout or session: uploaded into
@@ -1130,7 +1149,7 @@ class RolloutEngine:
         if self.follow_routes is None:
             raise ValueError('set_routes: the engine was built without follow_routes')
         self._upload_routes(*constraints.route_arrays(routes, n_points, n_scenes=self.S0, a_cap=self.A_cap))
-        self._graph = self._wgraph = None
+        self._drop_graphs()
         self._apply_token_masks()
 
     def _upload_routes(self, routes: np.ndarray, n_points: np.ndarray):
@@ -1139,7 +1158,7 @@ class RolloutEngine:
             self._route = constraints.route_buffers(self.S0, self.S * self.A_cap, self.A_cap, P, self.cfg.token_size, self.device)
             self.route_bits, self.route_allowed, self.route_progress = (self._route[k] for k in ('bits', 'allowed', 'progress'))
             self._end_pose_table()
-            self._graph = self._wgraph = None          # (a captured graph holds the old buffers' addresses)
+            self._drop_graphs()          # (a captured graph holds the old buffers' addresses)
         k, A = self._route, int(routes.shape[1])
         full, n = np.zeros((self.S0, self.A_cap, P, 2), np.float32), np.zeros((self.S0, self.A_cap), np.int32)
         full[:, :A], n[:, :A] = routes, n_points
@@ -1148,23 +1167,14 @@ class RolloutEngine:
         _lib.check(self.lib.infgen_route_records(_lib.ptr(k['routes']), _lib.ptr(k['n_points']), self.S0, self.A_cap, P,
                                                  _lib.ptr(k['records']), _lib.ptr(k['total']), self.ops.stream), 'infgen_route_records')
 
-    def _load_signals(self, obey):
-        """``obey_signals`` into the engine (None: keep what is there), like ``_load_routes``; lines and phase are uploaded and the
-        records built at once (they do not depend on the scene in the buffers)"""
-        if obey is None:
-            return
-        conf = constraints.check_obey_signals(obey, has_shape=getattr(self, '_shape10', None) is not None, n_scenes=self.S0)
-        if conf is None and self.obey_signals is None:
-            return
-        if constraints.signal_key(conf) != constraints.signal_key(self.obey_signals):
-            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
+    def _settle_obey_signals(self, conf, value, store):
+        """uploaded at once like the routes; every upload drops the graphs, not only a new key (``_upload_signals``)"""
         if conf is not None:
             self._upload_signals(conf.pop('phase'), conf.pop('lines'), conf.pop('n_lines'))
             conf.update(K=self._signal['K'], n_phase=self._signal['n_phase'])
         else:      # off: nothing of the last ruled step stays readable
             self._signal = self.signal_bits = self.signal_allowed = self.signal_info = None
-        self.obey_signals = conf
-        self._apply_token_masks()
+        store()
 
     def set_signals(self, phase=None, lines=None, n_lines=None):
         """new signal tables for an engine with ``obey_signals`` on - allowed between two steps of a rollout or session, and between
@@ -1210,7 +1220,7 @@ class RolloutEngine:
             self._end_pose_table()
         # every upload drops a captured graph - through set_signals and through reload*(obey_signals=...) alike -, also where the
         # buffers keep their addresses: the next rollout captures again and no graph is replayed over tables rewritten under it
-        self._graph = self._wgraph = None
+        self._drop_graphs()
         if phase is not None:
             k['phase'].copy_(torch.from_numpy(phase))
         if lines is not None:
@@ -1219,14 +1229,8 @@ class RolloutEngine:
             _lib.check(self.lib.infgen_signal_records(_lib.ptr(k['lines']), _lib.ptr(k['n_lines']), self.S0, K, _lib.ptr(k['records']),
                                                       self.ops.stream), 'infgen_signal_records')
 
-    def _load_scores(self, scores):
-        """``step_scores`` into the engine (None: keep what is there), like ``_load_road``, whose record table the scores share"""
-        if scores is None:
-            return
-        conf = constraints.check_step_scores(scores, has_shape=getattr(self, '_shape10', None) is not None, n_scenes=self.S0,
-                                             stay_on_road=self.stay_on_road)
-        if conf is None and self.step_scores is None:
-            return
+    def _settle_step_scores(self, conf, value, store):
+        """the scores share road's record table and drive it where road is off; ``value`` is kept for road's re-check"""
         if conf is not None and self.insertion:
             raise ValueError('step_scores: engines with scenario insertion are left out (rows appended inside a step), as branching is')
         if conf is not None and self.step_score is None:
@@ -1236,12 +1240,10 @@ class RolloutEngine:
                 self._score_shape = self._shape10.reshape(-1, 3).clone()
         if self.road_n_records is None and conf is not None:
             self.road_n_records = torch.zeros(self.S0, device=self.device, dtype=torch.int32)
-        if constraints.score_key(conf) != constraints.score_key(self.step_scores):
-            self._graph = self._wgraph = None          # (a captured graph holds the old launches and kernel arguments)
-        self.step_scores, self._score_arg = conf, (scores if conf is not None else None)
+        store()
+        self._score_arg = value if conf is not None else None
         if conf is not None and self.stay_on_road is None:      # the scores alone drive the road table
             self._road_source(conf)
-        self._apply_token_masks()
 
     def _road_source(self, conf):
         """``conf`` (road or scores) drives the engine's one road table: built again by the next prologue, from conf's explicit
@@ -1265,7 +1267,7 @@ class RolloutEngine:
         if self.road_records is None or need > self._road_cap:
             self._road_cap = _round_up(max(need, 1), 64)
             self.road_records = torch.zeros(self.S0, self._road_cap, 8, device=self.device)
-            self._graph = self._wgraph = None
+            self._drop_graphs()
 
     def _road_build(self):
         """the record table from the map in the buffers (or the explicit segments), once per reload: one count of EDGE tokens per
@@ -1292,10 +1294,9 @@ class RolloutEngine:
 
     def _apply_token_masks(self, validate: bool = True):
         """the library's handle of (table, per-row selectors, per-type sets) into the context: registered again when one of the
-        three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  A
-        collision configuration rides on the handle (one without a table when the engine has no ``token_masks``)"""
-        if self._ctx is None or (self.token_masks is None and self.avoid_collisions is None and self.stay_on_road is None
-                                 and self.step_scores is None and self.follow_routes is None and self.obey_signals is None
+        three changed as a VALUE of the registration (a new buffer, other per-type indices) - new contents need nothing.  The
+        riders' configurations ride on the handle (one without a table when the engine has no ``token_masks``)"""
+        if self._ctx is None or (self.token_masks is None and all(getattr(self, r.name) is None for r in RIDERS)
                                  and not self._mask_handle):
             return
         if self.token_masks is not None:
@@ -1308,56 +1309,58 @@ class RolloutEngine:
             if h < 1:
                 _lib.check(-1, 'infgen_token_mask_create')
             self._mask_handle, self._mask_reg = h, reg
-        h, P = self._mask_handle, _lib.ptr
-
-        def attach(reg_name, reg, entry, off, on):
-            """a rider's configuration onto the handle where its registration changed: ``on()``'s arguments, ``off``'s without one"""
-            if reg != getattr(self, reg_name):
-                _lib.check(getattr(self.lib, entry)(h, *(off if reg is None else on())), entry)
-                setattr(self, reg_name, reg)
-
-        conf, k = self.avoid_collisions, self._coll
-        attach('_coll_reg', None if conf is None else (h, conf['predict'], conf['margin']), 'infgen_token_mask_collision',
-               (None, None, None, None, 1, 0.0, None),
-               lambda: (P(k['bits']), P(k['ident']), P(k['shape']), P(self._coll_end), conf['predict'], conf['margin'], P(k['allowed'])))
-        # road-aware decoding rides on the handle in the same way (the table's address is part of it)
-        road, kr = self.stay_on_road, self._road
-        attach('_road_reg', None if road is None else (h, road['margin'], road['sweep'], road['types'], self.road_records.data_ptr(),
-                                                       self._road_cap), 'infgen_token_mask_road',
-               (None, None, None, None, None, None, None, 0, 1, 1, 0.0, None, None),
-               lambda: (P(kr['bits']), P(kr['ident']), P(kr['shape']), P(self._coll_end), P(self._road_paths), P(self.road_records),
-                        P(self.road_n_records), self._road_cap, self.copies, road['sweep'], road['margin'],
-                        (C.c_int * 3)(*road['types']), P(kr['allowed'])))
-        # and so do the step scores: the handle constrains nothing by itself
-        sc = self.step_scores
-        attach('_score_reg', None if sc is None else (h, constraints.score_key(sc), self.road_records.data_ptr(), self._road_cap,
-                                                      self._score_boxes().data_ptr()), 'infgen_token_mask_score',
-               (None, 0, None, None, None, None, 0, 1, 1, 0.0, None, 0.5),
-               lambda: (P(self.step_score), int(self.step_score.shape[1]), P(self.score_row), P(self._score_boxes()),
-                        P(self.road_records), P(self.road_n_records), self._road_cap, self.copies, sc['sweep'], sc['road_margin'],
-                        (C.c_int * 3)(*sc['types']), sc['dt']))
-        # and the route configuration, the last stage in front of the heads
-        rt, kt = self.follow_routes, self._route
-        attach('_route_reg', None if rt is None else (h, constraints.route_key(rt), kt['records'].data_ptr()), 'infgen_token_mask_route',
-               (None, None, None, None, None, None, 2, 1, 0.0, 0.0, 0.0, 0.0, None, None, None),
-               lambda: (P(kt['bits']), P(kt['ident']), P(kt['shape']), P(self._coll_end), P(kt['records']), P(kt['total']), kt['P'],
-                        self.copies, rt['corridor'], rt['back'], rt['pace'], rt['finish'], (C.c_int * 3)(*rt['types']),
-                        P(kt['allowed']), P(kt['progress'])))
-        # the signal configuration: the library runs it after road and before route
-        sg, kg = self.obey_signals, self._signal
-        attach('_signal_reg', None if sg is None else (h, constraints.signal_key(sg), kg['records'].data_ptr(), kg['phase'].data_ptr()),
-               'infgen_token_mask_signal', (None, None, None, None, None, None, 1, 1, 1, 0.0, 0.0, None, None, None),
-               lambda: (P(kg['bits']), P(kg['ident']), P(kg['shape']), P(self._coll_end), P(kg['records']), P(kg['phase']), kg['n_phase'],
-                        kg['K'], self.copies, sg['setback'], sg['align'], (C.c_int * 3)(*sg['types']), P(kg['allowed']), P(kg['info'])))
+        h = self._mask_handle
+        # every rider onto the handle where its registration changed: ``_attach_<name>``'s arguments, the table's "off" ones without
+        for r in RIDERS:
+            conf = getattr(self, r.name)
+            reg, args = (None, r.off) if conf is None else getattr(self, '_attach_' + r.name)(conf)
+            reg = None if conf is None else (h,) + reg
+            if reg != getattr(self, r.reg):
+                _lib.check(getattr(self.lib, r.entry)(h, *args), r.entry)
+                setattr(self, r.reg, reg)
         self._ctx.token_mask = h
         if validate:
             _lib.check(self.lib.infgen_rollout_validate(C.byref(self._ctx)), 'infgen_rollout_validate')
 
+    # per rider -> (what the registration depends on besides the handle, the attach entry's arguments behind the handle)
+    def _attach_avoid_collisions(self, conf):
+        k, P = self._coll, _lib.ptr
+        return ((conf['predict'], conf['margin']),
+                (P(k['bits']), P(k['ident']), P(k['shape']), P(self._coll_end), conf['predict'], conf['margin'], P(k['allowed'])))
+
+    def _attach_stay_on_road(self, conf):      # (the table's address is part of the registration)
+        k, P = self._road, _lib.ptr
+        return ((conf['margin'], conf['sweep'], conf['types'], self.road_records.data_ptr(), self._road_cap),
+                (P(k['bits']), P(k['ident']), P(k['shape']), P(self._coll_end), P(self._road_paths), P(self.road_records),
+                 P(self.road_n_records), self._road_cap, self.copies, conf['sweep'], conf['margin'], (C.c_int * 3)(*conf['types']),
+                 P(k['allowed'])))
+
+    def _attach_step_scores(self, conf):
+        P, boxes = _lib.ptr, self._score_boxes()
+        return ((constraints.score_key(conf), self.road_records.data_ptr(), self._road_cap, boxes.data_ptr()),
+                (P(self.step_score), int(self.step_score.shape[1]), P(self.score_row), P(boxes), P(self.road_records),
+                 P(self.road_n_records), self._road_cap, self.copies, conf['sweep'], conf['road_margin'],
+                 (C.c_int * 3)(*conf['types']), conf['dt']))
+
+    def _attach_follow_routes(self, conf):
+        k, P = self._route, _lib.ptr
+        return ((constraints.route_key(conf), k['records'].data_ptr()),
+                (P(k['bits']), P(k['ident']), P(k['shape']), P(self._coll_end), P(k['records']), P(k['total']), k['P'], self.copies,
+                 conf['corridor'], conf['back'], conf['pace'], conf['finish'], (C.c_int * 3)(*conf['types']), P(k['allowed']),
+                 P(k['progress'])))
+
+    def _attach_obey_signals(self, conf):
+        k, P = self._signal, _lib.ptr
+        return ((constraints.signal_key(conf), k['records'].data_ptr(), k['phase'].data_ptr()),
+                (P(k['bits']), P(k['ident']), P(k['shape']), P(self._coll_end), P(k['records']), P(k['phase']), k['n_phase'], k['K'],
+                 self.copies, conf['setback'], conf['align'], (C.c_int * 3)(*conf['types']), P(k['allowed']), P(k['info'])))
+
     def _drop_mask_handle(self):
         if getattr(self, '_mask_handle', 0):
             self.lib.infgen_token_mask_destroy(self._mask_handle)
-            self._mask_handle, self._mask_reg, self._coll_reg, self._road_reg, self._score_reg = 0, None, None, None, None
-            self._route_reg = self._signal_reg = None
+            self._mask_handle, self._mask_reg = 0, None
+            for r in RIDERS:
+                setattr(self, r.reg, None)
             if getattr(self, '_ctx', None) is not None:
                 self._ctx.token_mask = 0
 
@@ -1373,30 +1376,25 @@ class RolloutEngine:
             c.sample_temperature, c.sample_top_p = self.sample_temperature, self.sample_top_p
             c.sample_temp_row = _lib.ptr(self.sample_temp_row)
 
-    def _load_riders(self, token_masks=None, avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None,
-                     obey_signals=None):
-        """what rides on the decode step into the engine, in the one order it is resolved in: masks, collisions, road, scores (each
-        None: keep what is there; ``token_masks`` a (table, per-type, per-row) triple).  Road and scores are checked against each
-        other once both are resolved: the scores' argument is recorded - and scores that go are gone - before ``_load_road``
+    def _load_riders(self, step: Mapping):
+        """what rides on the decode step (``STEP_KEYWORDS``; each None: keep what is there) into the engine, in the one order it is
+        resolved in: masks, collisions, road, scores, routes, signals.  Road and scores are checked against each other once both
+        are resolved: the scores' argument is recorded - and scores that go are gone - before road's ``_settle_stay_on_road``
         checks the scores that are on against the new road"""
-        self._load_token_masks(*(token_masks or (None, None, None)))
-        self._load_collisions(avoid_collisions)
-        if step_scores is not None:
-            self._score_arg = step_scores if step_scores is not False else None
-            if step_scores is False:
-                self._load_scores(False)
-        self._load_road(stay_on_road)
-        self._load_scores(step_scores)
-        self._load_routes(follow_routes)
-        self._load_signals(obey_signals)
+        self._load_token_masks(*(step[k] for k in STEP_KEYWORDS[:3]))
+        for r in RIDERS:
+            if r.name == 'stay_on_road' and step['step_scores'] is not None:
+                self._score_arg = step['step_scores'] if step['step_scores'] is not False else None
+                if step['step_scores'] is False:
+                    self._load_rider(_SCORES, False)
+            self._load_rider(r, step[r.name])
 
-    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature=None, sample_top_p=None, token_masks=None,
-                       avoid_collisions=None, stay_on_road=None, step_scores=None, follow_routes=None, obey_signals=None):
-        self._load_riders(token_masks, avoid_collisions, stay_on_road, step_scores, follow_routes, obey_signals)
+    def _load_uniforms(self, sample_uniforms, insert_uniforms, amax, sample_temperature, sample_top_p, step: Mapping):
+        self._load_riders(step)
         if sample_top_p is not None:
             p = self._check_top_p(sample_top_p, 'sample_top_p')
             if p != self.sample_top_p:
-                self._graph = self._wgraph = None      # (a captured graph holds the old kernel argument)
+                self._drop_graphs()      # (a captured graph holds the old kernel argument)
             self.sample_top_p = p
             self._apply_sampling()
         self._load_temperature(sample_temperature, amax)
@@ -1443,7 +1441,7 @@ class RolloutEngine:
             c, P = self._ctx, _lib.ptr
             c.teacher_token, c.teacher_state, c.replay_row = P(self.teacher_token), P(self.teacher_state), P(self.replay_row)
             c.teacher_pos, c.teacher_head = P(self.teacher_pos), P(self.teacher_head)
-            self._graph = self._wgraph = None
+            self._drop_graphs()
             _lib.check(self.lib.infgen_rollout_validate(C.byref(c)), 'infgen_rollout_validate')
 
     def _load_replay(self, mask: Optional[torch.Tensor], plan: Optional[Mapping[str, torch.Tensor]]):
@@ -1481,8 +1479,7 @@ class RolloutEngine:
         for dst, k in zip(self._map_cat, ('map_tok', 'map_type', 'map_pl', 'map_light')):
             dst.copy_(torch.from_numpy(arr[k]))
         self._load_uniforms(sample_uniforms, insert_uniforms, int(staged['A'].max()), sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
-                            follow_routes, obey_signals)
+                            _step_keywords(locals()))
         self._x_pt_override = x_pt_override
         self._epi = None
         self._replay_from_hosts(replay)
@@ -1515,8 +1512,7 @@ class RolloutEngine:
             return False
         self.scenes = scenes
         self._load_uniforms(sample_uniforms, insert_uniforms, self.hosts[0]['A'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
-                            follow_routes, obey_signals)
+                            _step_keywords(locals()))
         self._x_pt_override = x_pt_override
         self._invalidate()
         return True
@@ -1588,8 +1584,7 @@ class RolloutEngine:
         assert self.fits_batch(layout), 'batch does not fit this engine (RolloutEngine.fits_batch)'
         self._end_session()
         self._load_uniforms(sample_uniforms, insert_uniforms, layout['amax'], sample_temperature, sample_top_p,
-                            (token_masks, token_mask_type, token_mask_row), avoid_collisions, stay_on_road, step_scores,
-                            follow_routes, obey_signals)
+                            _step_keywords(locals()))
         self._ingest(batch, layout, src_graph, replay=replay)
         self._invalidate()
 
@@ -2219,7 +2214,7 @@ class RolloutEngine:
         if not in_kernel and self.logits is None and self.logits_scratch is None:
             self.logits_scratch = torch.zeros(self.rows, self.cfg.token_size, device=self.device)
             self._ctx.logits_scratch = _lib.ptr(self.logits_scratch)
-            self._graph = self._wgraph = None          # (a captured graph holds the old pointers)
+            self._drop_graphs()          # (a captured graph holds the old pointers)
         o.row_groups = o.n_row_groups = None
         o.row_group_margin = 0
         if groups and self.insertion and self.ins is not None and self.flags['row_groups']:
